@@ -34,7 +34,8 @@ def build(force: bool = False) -> None:
     if stale:
         subprocess.run(["make", "-C", _HERE, "liboracle.so"], check=True, capture_output=True)
     if os.path.isdir("/root/reference/src"):
-        for target, name in (("ref", "libnblic_ref.so"), ("ref_big", "libnblic_ref_big.so")):       # ref_big: config 5's raised pixel limit
+        for target, name in (("ref", "libnblic_ref.so"), ("ref_big", "libnblic_ref_big.so"),       # ref_big: config 5's raised pixel limit
+                             ("ref_fileio", "libfileio_ref.so"), ("ref_main", "NBLIC_main.o")):       # the front end's checks
             if force or not os.path.exists(os.path.join(_HERE, "_ref", name)):
                 subprocess.run(["make", "-C", _HERE, target], check=True, capture_output=True)
 

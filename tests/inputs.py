@@ -58,7 +58,47 @@ def case_id(content, h, w, near, effort):
     return f"{content}_{h}x{w}_n{near}_e{effort}"
 
 
+def random_cases():
+    """The oracle-vs-reference sample of test_oracle.py: (img, near, effort) on random shapes up to 47x47."""
+    rng = np.random.default_rng(1234)
+    out = []
+    for _ in range(25):
+        h, w = int(rng.integers(1, 48)), int(rng.integers(1, 48))
+        img = rng.integers(0, 256, (h, w), dtype=np.uint8)
+        if rng.random() < 0.5:
+            img = (img // 16 + make("ramp", h, w) // 2).astype(np.uint8)
+        out.append((img, int(rng.integers(0, 10)), int(rng.integers(1, 4))))
+    return out
+
+
+def random_q_cases():
+    """The effort-0 sample of test_oracle_q.py: random shapes up to 39x39 plus one 200x300 SYN-1 frame."""
+    rng = np.random.default_rng(77)
+    out = []
+    for _ in range(30):
+        h, w = int(rng.integers(1, 40)), int(rng.integers(1, 40))
+        img = rng.integers(0, 256, (h, w), dtype=np.uint8)
+        if rng.random() < 0.6:
+            img = (img // 32 + make("ramp", h, w) // 2 + 40).astype(np.uint8)
+        out.append(img)
+    return out + [syn1(200, 300, 4)]
+
+
 KODAK_DIR = "/root/reference/img_kodak"      # read in place, container only; never copied into the repo
+KODAK_CROP = (slice(192, 256), slice(320, 416))   # the 64x96 window of every Kodak image kept in tests/golden/reference_fixtures.npz
+
+
+def fixtures():
+    """tests/golden/reference_fixtures.{npz,json}: data the compiled reference produced (tests/golden/make_fixtures.py),
+    so that the checks against it run without the reference tree."""
+    import json
+    import os
+    g = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    with open(os.path.join(g, "reference_fixtures.json")) as f:
+        meta = json.load(f)
+    with np.load(os.path.join(g, "reference_fixtures.npz"), allow_pickle=False) as z:
+        arrays = {k: z[k] for k in z.files}
+    return meta, arrays
 
 
 def read_gray_bmp(path):

@@ -13,6 +13,7 @@ import torch.distributed as dist  # noqa: E402
 import torch.multiprocessing as mp  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+VISIBILITY = ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES")     # bench.gpu_local_cpulists applies these to sysfs
 
 
 def _streams_for(rank, n):
@@ -105,10 +106,12 @@ def _fake_sysfs(root, nps=2):
     with open(os.path.join(d, "local_cpulist"), "w") as f: f.write("0-255\n")
 
 
-def test_cpu_slices_follow_the_gpus_numa_nodes(tmp_path):
+def test_cpu_slices_follow_the_gpus_numa_nodes(tmp_path, monkeypatch):
     """Each rank's CPU slice comes from ITS GPU's NUMA node (sysfs local_cpulist), the node's cores split between the
     GPUs on it; a lone visible GPU still takes only the share it would have in the full node; without sysfs the old
     even split by rank."""
+    for var in VISIBILITY:                                     # the fake host's eight GPUs, whatever this host shows
+        monkeypatch.delenv(var, raising=False)
     sys.path.insert(0, ROOT)
     import bench
     _fake_sysfs(str(tmp_path))
@@ -122,11 +125,9 @@ def test_cpu_slices_follow_the_gpus_numa_nodes(tmp_path):
         assert not (seen & set(cpus))
         seen |= set(cpus)
     assert len(seen) == 256
-    os.environ["HIP_VISIBLE_DEVICES"] = "5"                    # a one-GPU container on that host: GPU 5 is ordinal 0
-    try:
-        cpus, how = bench.cpu_share(0, 8, str(tmp_path), range(256))
-    finally:
-        del os.environ["HIP_VISIBLE_DEVICES"]
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "5")             # a one-GPU container on that host: GPU 5 is ordinal 0
+    cpus, how = bench.cpu_share(0, 8, str(tmp_path), range(256))
+    monkeypatch.delenv("HIP_VISIBLE_DEVICES")
     assert cpus == list(range(64, 80)) + list(range(192, 208)) and "numa node 1" in how
     empty = tmp_path / "nothing"
     (empty / "class" / "drm").mkdir(parents=True)
@@ -145,7 +146,7 @@ def test_bench_eight_ranks_report_distinct_numa_correct_slices(tmp_path):
     import json
     import subprocess
     _fake_sysfs(str(tmp_path))
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT") + VISIBILITY}
     env.update(NBLIC_BENCH_SYSFS=str(tmp_path), NBLIC_BENCH_ASSUME_CPUS="256")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--launch-check"], env=env,
                        capture_output=True, text=True, timeout=600)

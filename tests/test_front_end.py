@@ -1,8 +1,10 @@
 """The front end either side of the hot path: the reference tool's switch grammar
 and its PGM / BMP files.  CPU tests cover the grammar, the file formats (against an independent
-construction of the bytes, against the reference's own FileIO.c compiled in place, and on the Kodak
-BMPs -- the last two only where /root/reference exists) and that the reference's own main() links
-against libnblic_amd.so; the -m gpu tests run the command line end to end."""
+construction of the bytes, against the reference's own FileIO.c, and on the Kodak BMPs' headers) and
+that the reference's own main() finds every codec symbol it calls in libnblic_amd.so.  What the
+reference produced is stored in tests/golden/reference_fixtures.*; where oracle/_ref was built the
+reference's FileIO library and main() objects are also used live.  The -m gpu tests run the command
+line end to end."""
 import hashlib
 import os
 import struct
@@ -15,7 +17,7 @@ import pytest
 import inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SRC = "/root/reference/src"
+REF_BUILT = os.path.join(ROOT, "oracle", "_ref")                  # reference objects oracle.build() compiled, when it could
 
 
 def bmp_bytes(img):
@@ -93,8 +95,22 @@ def test_readers_accept_and_reject_like_the_reference(pkg, tmp_path):
     assert pkg.read_gray(str(tmp_path / "missing.pgm")) is None
 
 
-@pytest.mark.skipif(not os.path.isdir(inputs.KODAK_DIR), reason="Kodak BMPs live only in the build container")
-def test_kodak_bmps_read_like_the_reference_reader(pkg, golden):
+def test_kodak_bmps_read_like_the_reference_reader(pkg, golden, tmp_path):
+    """The Kodak files' own headers (stored) over a known plane of their size; and the files themselves, hashed as
+    the reference's reader saw them, where they can be read."""
+    _, stored = inputs.fixtures()
+    for k, head in enumerate(stored["kodak_bmp_headers"]):
+        off = struct.unpack_from("<I", head, 10)[0]
+        w, h = struct.unpack_from("<ii", head, 18)
+        assert off == len(head) and h > 0
+        img = inputs.noise(h, w, k)
+        stride = (w + 3) & ~3
+        path = str(tmp_path / f"{k}.bmp")
+        open(path, "wb").write(head.tobytes() + b"".join(img[i].tobytes() + bytes(stride - w) for i in range(h - 1, -1, -1)))
+        got = pkg.read_gray(path)
+        assert got is not None and got[1] == "BMP" and np.array_equal(got[0], img), k
+    if not os.path.isdir(inputs.KODAK_DIR):
+        return
     manifest, _ = golden
     for name in sorted(os.listdir(inputs.KODAK_DIR)):
         got = pkg.read_gray(os.path.join(inputs.KODAK_DIR, name))
@@ -104,44 +120,52 @@ def test_kodak_bmps_read_like_the_reference_reader(pkg, golden):
 
 @pytest.fixture(scope="module")
 def ref_fileio():
-    """The reference's own FileIO.c compiled in place into oracle/_ref (container only)."""
+    """The reference's own FileIO.c as oracle.build() compiled it into oracle/_ref; None where it was not built."""
     import ctypes as C
-    if not os.path.isdir(REF_SRC):
-        pytest.skip("reference sources absent")
-    so = os.path.join(ROOT, "oracle", "_ref", "libfileio_ref.so")
-    os.makedirs(os.path.dirname(so), exist_ok=True)
-    subprocess.run(["gcc", "-O2", "-fPIC", "-shared", "-o", so, os.path.join(REF_SRC, "FileIO.c")], check=True)
-    return C.CDLL(so)
+    so = os.path.join(REF_BUILT, "libfileio_ref.so")
+    return C.CDLL(so) if os.path.exists(so) else None
 
 
 def test_files_against_the_reference_fileio(pkg, ref_fileio, tmp_path):
     import ctypes as C
     u8p = C.POINTER(C.c_uint8)
+    _, stored = inputs.fixtures()
     for shape in [(1, 1), (3, 5), (17, 13), (64, 61), (30, 128)]:
         img = inputs.make("noise", *shape)
-        for as_bmp, writer, reader in ((False, ref_fileio.writePGMImageFile, ref_fileio.loadPGMImageFile),
-                                       (True, ref_fileio.writeBMPGrayImageFile, ref_fileio.loadBMPGrayImageFile)):
+        for as_bmp, fmt in ((False, "pgm"), (True, "bmp")):
             mine, theirs = str(tmp_path / "mine"), str(tmp_path / "theirs")
             assert pkg.write_gray(mine, img, as_bmp)
+            open(theirs, "wb").write(stored[f"fileio_{fmt}_{shape[0]}x{shape[1]}"].tobytes())     # what the reference's writer wrote
+            assert open(mine, "rb").read() == open(theirs, "rb").read(), (shape, as_bmp)
+            assert np.array_equal(pkg.read_gray(theirs)[0], img)                                      # and we read what it wrote
+            if ref_fileio is None:
+                continue
+            writer, reader = ((ref_fileio.writeBMPGrayImageFile, ref_fileio.loadBMPGrayImageFile) if as_bmp else
+                              (ref_fileio.writePGMImageFile, ref_fileio.loadPGMImageFile))
             assert writer(theirs.encode(), img.ctypes.data_as(u8p), shape[0], shape[1]) == 0
             assert open(mine, "rb").read() == open(theirs, "rb").read(), (shape, as_bmp)
             back = np.zeros_like(img)
             h, w = C.c_int(), C.c_int()
             assert reader(mine.encode(), back.ctypes.data_as(u8p), C.byref(h), C.byref(w)) == 0      # the reference reads what we wrote
             assert (h.value, w.value) == shape and np.array_equal(back, img)
-            assert np.array_equal(pkg.read_gray(theirs)[0], img)                                      # and we read what it wrote
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="reference sources absent")
 def test_reference_main_links_against_the_library(pkg):
-    """The reference's own caller (NBLIC_main.c + FileIO.c) built against libnblic_amd.so instead of
-    NBLIC.c / QNBLIC.c: it links without an unresolved symbol and starts (usage text, exit status -1)."""
+    """The reference's own caller (NBLIC_main.c + FileIO.c) against libnblic_amd.so instead of NBLIC.c / QNBLIC.c:
+    every codec symbol it calls (stored) is exported; where oracle/_ref holds its objects it links without an
+    unresolved symbol and starts (usage text, exit status -1)."""
+    meta, _ = inputs.fixtures()
+    lib = pkg.load_library()
+    assert meta["main_codec_symbols"] and all(hasattr(lib, n) for n in meta["main_codec_symbols"]), meta["main_codec_symbols"]
+    objs = [os.path.join(REF_BUILT, "NBLIC_main.o"), os.path.join(REF_BUILT, "FileIO.o")]
+    if not all(os.path.exists(o) for o in objs):
+        return
     pkg.build()
     out = os.path.join(ROOT, "tests", "_build", "ref_main_on_amd")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     lib_dir = os.path.dirname(pkg.LIB_PATH)
-    r = subprocess.run(["gcc", "-O2", "-w", "-o", out, os.path.join(REF_SRC, "NBLIC_main.c"), os.path.join(REF_SRC, "FileIO.c"),
-                        "-L" + lib_dir, "-lnblic_amd", "-Wl,-rpath," + lib_dir, "-Wl,--no-undefined"], capture_output=True, text=True)
+    r = subprocess.run(["gcc", "-O2", "-w", "-o", out] + objs + ["-L" + lib_dir, "-lnblic_amd", "-Wl,-rpath," + lib_dir, "-Wl,--no-undefined"],
+                       capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     r = subprocess.run([out], capture_output=True, text=True, timeout=120)
     assert r.returncode == 255 and "nblic_codec" in r.stdout

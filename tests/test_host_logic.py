@@ -74,9 +74,10 @@ def test_model_headers_and_f64_least_squares_equal_oracle(harness, pkg, oracle, 
 
 
 def test_f64_least_squares_on_a_photograph_and_noise(harness, pkg, oracle):
-    """A Kodak crop (read in place; skipped where the reference tree is absent) and uniform noise at effort 3:
-    the exact-range guard may send pixels to the integer redo, the bytes must not change."""
-    frames = [inputs.noise(96, 96, 3)]
+    """Kodak crops (the stored 64x96 one; a 128x160 one read in place where the images are) and uniform noise at
+    effort 3: the exact-range guard may send pixels to the integer redo, the bytes must not change."""
+    meta, stored = inputs.fixtures()
+    frames = [inputs.noise(96, 96, 3), stored["kodak_crops"][sorted(meta["kodak_crops"]).index("05.bmp")]]
     kodak = os.path.join(inputs.KODAK_DIR, "05.bmp")
     if os.path.exists(kodak):
         frames.append(np.ascontiguousarray(inputs.read_gray_bmp(kodak)[100:228, 200:360]))

@@ -102,25 +102,29 @@ def test_limits_and_clamps(oracle):
     assert oracle.lib.orc_nblic_encode(_ptr(out), _ptr(big), 10001, 10000, C.byref(n), C.byref(e), 0, None) == -1
 
 
-def test_oracle_vs_live_reference(oracle, reference):
-    rng = np.random.default_rng(1234)
-    for _ in range(25):
-        h, w = int(rng.integers(1, 48)), int(rng.integers(1, 48))
-        img = rng.integers(0, 256, (h, w), dtype=np.uint8)
-        if rng.random() < 0.5:
-            img = (img // 16 + inputs.make("ramp", h, w) // 2).astype(np.uint8)
-        near, effort = int(rng.integers(0, 10)), int(rng.integers(1, 4))
+def test_oracle_vs_live_reference(oracle):
+    """Random shapes and parameters: the reference's streams and decodes stored in tests/golden/reference_fixtures.*
+    (make_fixtures.py), and the compiled reference itself wherever oracle/_ref was built."""
+    from oracle.oracle import Reference
+    meta, stored = inputs.fixtures()
+    reference = Reference() if Reference.available() else None
+    for k, (img, near, effort) in enumerate(inputs.random_cases()):
+        h, w = img.shape
         a = oracle.encode(img, near, effort)
-        b = reference.encode(img, near, effort)
-        assert a[0] == b[0] and np.array_equal(a[1], b[1]), (h, w, near, effort)
-        d = reference.decode(a[0])
-        assert d is not None and np.array_equal(d[0], a[1])
+        assert a[0] == stored[f"case_{k}"].tobytes(), (h, w, near, effort)
+        assert sha(a[1].tobytes()) == meta["case_recon_sha256"][k], (h, w, near, effort)      # the reference decodes to it
+        if reference is not None:
+            b = reference.encode(img, near, effort)
+            assert a[0] == b[0] and np.array_equal(a[1], b[1]), (h, w, near, effort)
+            d = reference.decode(a[0])
+            assert d is not None and np.array_equal(d[0], a[1])
 
 
 def test_oracle_on_kodak_matches_reference_and_readme(oracle, golden):
     """BASELINE config 3 content.  The 24 Kodak BMPs are third-party files and are read in place
     (container only); the manifest holds the compiled reference's length + SHA-256 per image, whose
-    totals reproduce the reference README's 4.146 bpp (-e1) and 4.227 bpp (-e0)."""
+    totals reproduce the reference README's 4.146 bpp (-e1) and 4.227 bpp (-e0).  A 64x96 crop of
+    every image is stored with the reference's streams of it (tests/golden/reference_fixtures.*)."""
     import os
     manifest, _ = golden
     k = manifest["kodak_e1"]
@@ -129,8 +133,16 @@ def test_oracle_on_kodak_matches_reference_and_readme(oracle, golden):
     px = sum(v["shape"][0] * v["shape"][1] for v in k.values())
     assert (total_e1, total_e0, px) == (4891174, 4985986, 9437184)
     assert round(8 * total_e1 / px, 3) == 4.146 and round(8 * total_e0 / px, 3) == 4.227   # README.md:256-257
-    if not os.path.isdir(inputs.KODAK_DIR):
-        pytest.skip("Kodak images are only present in the build container")
+    meta, stored = inputs.fixtures()
+    assert sorted(meta["kodak_crops"]) == sorted(k)
+    for name, crop in zip(sorted(meta["kodak_crops"]), stored["kodak_crops"]):     # the crops, everywhere
+        want = meta["kodak_crops"][name]
+        s = oracle.encode(crop, 0, 1)[0]
+        assert (len(s), sha(s)) == (want["len"], want["sha256"]), name
+        q = oracle.qencode(crop)
+        assert (len(q), sha(q)) == (want["q_len"], want["q_sha256"]), name
+    if not os.path.isdir(inputs.KODAK_DIR):                               # the whole images where they can be read
+        return
     for name in sorted(k):                                                # all 24 images
         img = inputs.read_gray_bmp(os.path.join(inputs.KODAK_DIR, name))
         assert sha(img.tobytes()) == k[name]["input_sha256"]

@@ -11,7 +11,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 frames = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 if len(sys.argv) > 3 and sys.argv[3] == "torch-first":       # the comparison: the wheel's bundled runtime
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     import torch
     torch.cuda.init()
 pkg = importlib.import_module("nblic-image-compression_amd")
