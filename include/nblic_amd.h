@@ -192,6 +192,45 @@ int nblic_amd_stream_progress(nblic_amd_stream *s, int *rows_done, unsigned long
 int nblic_amd_stream_recon(nblic_amd_stream *s, unsigned char *plane, int *first_row, int *end_row);
 void nblic_amd_stream_end(nblic_amd_stream *s);
 
+/* ONE stream DECODED in ROW BANDS (src/NBLIC.c:807-898 is a single pass over the rows): the caller feeds the stream in
+ * pieces of any size as it arrives and takes the rows as they are finished; the device workspace depends on band_rows
+ * and the width, never on the height ((band_rows + 2) x width reconstruction rows, the least-squares statistics at
+ * efforts 2 / 3, one state record, a stream window of max(4 MiB, 2 x band_rows x width + 8 x width + 2048) bytes), and
+ * between two _run calls the decoder can be SUSPENDED: nblic_amd_dstream_checkpoint writes down everything it carries,
+ * nblic_amd_dstream_resume -- in another call, another process, on another GPU -- carries on from there, fed from the
+ * checkpoint's feed_from offset on.  A running SHA-256 of every decoded row travels with the checkpoint, so a split
+ * decode can be checked against a golden reconstruction hash without ever holding the plane.  NBLIC and QNBLIC streams
+ * alike (told apart by the magic); the context's pixel limit (nblic_amd_set_max_pixels) applies.  Each object has a HIP
+ * stream and a workspace of its own, so it can run next to batches, band encoders and other band decoders of its context;
+ * one object is driven by one thread at a time.
+ *   _begin    band_rows <= 0: sized automatically (a launch of a few seconds).  NULL on failure.
+ *   _resume   a checkpoint of _checkpoint; every field is checked (magic, format version, checksum over the whole body,
+ *             sizes against the geometry, the header fields, the state) before anything reaches the device: NULL if any is off.
+ *   _check    the same checks alone, on the host (no device is touched): 0 valid, -1 refused.
+ *   _feed     appends n bytes of the stream (after a resume: the stream from feed_from on); final_ != 0: the stream ends
+ *             with these bytes.  Only the bytes from the decoder's window on are kept.  0 / -1.
+ *   _info     1 once the header (QNBLIC: and its tables) is in, 0 not yet, -1 refused (not a stream this library decodes).
+ *   _run      decodes until the image is finished (returns 1), budget_seconds (> 0) have passed or rows_out is full
+ *             (returns 0), or the fed bytes run out before the stream is complete (returns 2: feed more, call again); -1
+ *             on error (damaged or truncated stream, rows_out smaller than one band).  The rows finished by THIS call are
+ *             written to rows_out one after the other (cap bytes, at least band_rows x width) and are rows
+ *             [*first_row, *end_row) of the image.
+ *   _progress rows finished, the offset the stream would have to be fed from after a checkpoint taken now, the SHA-256 of
+ *             the rows finished so far, device bytes held; returns 1 finished / 0 / -1 failed.
+ *   _checkpoint  writes the checkpoint into buf (cap bytes) and returns its size; with buf == NULL or cap too small it only
+ *             returns the size needed; 0 before the header is in or after the image is finished.  Valid between two _run calls. */
+typedef struct nblic_amd_dstream nblic_amd_dstream;
+nblic_amd_dstream *nblic_amd_dstream_begin(nblic_amd_ctx *ctx, int band_rows);
+nblic_amd_dstream *nblic_amd_dstream_resume(nblic_amd_ctx *ctx, const void *checkpoint, size_t bytes);
+int nblic_amd_dstream_check(nblic_amd_ctx *ctx, const void *checkpoint, size_t bytes);
+int nblic_amd_dstream_feed(nblic_amd_dstream *d, const unsigned char *bytes, size_t n, int final_);
+int nblic_amd_dstream_info(nblic_amd_dstream *d, int *kind, int *height, int *width, int *near, int *effort);
+int nblic_amd_dstream_run(nblic_amd_dstream *d, double budget_seconds, unsigned char *rows_out, size_t cap, int *first_row, int *end_row);
+int nblic_amd_dstream_progress(nblic_amd_dstream *d, int *rows_done, unsigned long long *feed_from, unsigned char sha256[32],
+                               size_t *device_bytes);
+size_t nblic_amd_dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap);
+void nblic_amd_dstream_end(nblic_amd_dstream *d);
+
 /* The reference's decoders take no stream length (src/NBLIC.h:72, src/QNBLIC.h:16).  NBLICdecompress / QNBLICdecompress
  * therefore fetch the caller's stream ON DEMAND in steps of `bytes` (default 1 MiB, at least 4096): the decoder stops in
  * front of a row when it is about to run short, the next step is copied in, it resumes.  No byte beyond the last one the

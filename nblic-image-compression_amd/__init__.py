@@ -41,6 +41,8 @@ EXPORTS = (
     "nblic_amd_set_serial_rows", "nblic_amd_serial_launches", "nblic_amd_set_feed_chunk", "nblic_amd_last_fed_bytes",
     "nblic_amd_stream_begin", "nblic_amd_stream_resume", "nblic_amd_stream_run", "nblic_amd_stream_checkpoint", "nblic_amd_stream_progress",
     "nblic_amd_stream_recon", "nblic_amd_stream_end",
+    "nblic_amd_dstream_begin", "nblic_amd_dstream_resume", "nblic_amd_dstream_check", "nblic_amd_dstream_feed", "nblic_amd_dstream_info",
+    "nblic_amd_dstream_run", "nblic_amd_dstream_progress", "nblic_amd_dstream_checkpoint", "nblic_amd_dstream_end",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -140,6 +142,24 @@ def load_library() -> C.CDLL:
     lib.nblic_amd_stream_recon.argtypes = [C.c_void_p, C.c_void_p, ip, ip]
     lib.nblic_amd_stream_end.restype = None
     lib.nblic_amd_stream_end.argtypes = [C.c_void_p]
+    lib.nblic_amd_dstream_begin.restype = C.c_void_p
+    lib.nblic_amd_dstream_begin.argtypes = [C.c_void_p, C.c_int]
+    lib.nblic_amd_dstream_resume.restype = C.c_void_p
+    lib.nblic_amd_dstream_resume.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.nblic_amd_dstream_check.restype = C.c_int
+    lib.nblic_amd_dstream_check.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.nblic_amd_dstream_feed.restype = C.c_int
+    lib.nblic_amd_dstream_feed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    lib.nblic_amd_dstream_info.restype = C.c_int
+    lib.nblic_amd_dstream_info.argtypes = [C.c_void_p, ip, ip, ip, ip, ip]
+    lib.nblic_amd_dstream_run.restype = C.c_int
+    lib.nblic_amd_dstream_run.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_size_t, ip, ip]
+    lib.nblic_amd_dstream_progress.restype = C.c_int
+    lib.nblic_amd_dstream_progress.argtypes = [C.c_void_p, ip, C.POINTER(C.c_ulonglong), C.c_void_p, C.POINTER(C.c_size_t)]
+    lib.nblic_amd_dstream_checkpoint.restype = C.c_size_t
+    lib.nblic_amd_dstream_checkpoint.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.nblic_amd_dstream_end.restype = None
+    lib.nblic_amd_dstream_end.argtypes = [C.c_void_p]
     lib.nblic_amd_enable_timing.restype = None
     lib.nblic_amd_enable_timing.argtypes = [C.c_void_p, C.c_int]
     lib.nblic_amd_stage_times.restype = C.c_int
@@ -368,8 +388,12 @@ class Context:
         if not self.handle:
             raise RuntimeError("nblic_amd_create failed: no usable HIP device (the hot path has no CPU fallback)")
         self.device, self.n_slots, self.n_coders = device, n_slots, n_coders
+        self._decoders = []                 # BandDecoders handed out: closed before the context is destroyed
 
     def close(self):
+        for d in getattr(self, "_decoders", []):
+            d.close()
+        self._decoders = []
         if self.handle:
             self.lib.nblic_amd_destroy(self.handle)
             self.handle = None
@@ -447,6 +471,17 @@ class Context:
     def stream(self, img: np.ndarray, near: int, effort: int, band_rows: int = 0, checkpoint: Optional[bytes] = None) -> "BandStream":
         """One image in row bands (``nblic_amd_stream_*``): bounded workspace, suspend / resume through checkpoints."""
         return BandStream(self, img, near, effort, band_rows, checkpoint)
+
+    def decoder(self, band_rows: int = 0, checkpoint: Optional[bytes] = None) -> "BandDecoder":
+        """One stream decoded in row bands (``nblic_amd_dstream_*``): fed piece by piece, rows as they finish, bounded
+        workspace, suspend / resume through checkpoints.  The context closes it before it is destroyed itself."""
+        d = BandDecoder(self, band_rows, checkpoint)
+        self._decoders = [x for x in self._decoders if x.handle] + [d]
+        return d
+
+    def check_decoder_checkpoint(self, checkpoint: bytes) -> bool:
+        """Host-side validation of a band decoder checkpoint (``nblic_amd_dstream_check``); touches no device."""
+        return check_decoder_checkpoint(checkpoint, self)
 
     def set_serial_rows(self, rows: int):
         """Rows per launch of the resumable serial kernels (``nblic_amd_set_serial_rows``); 0 = automatic."""
@@ -623,3 +658,122 @@ class BandStream:
             self.close()
         except Exception:
             pass
+
+
+NEEDS_INPUT = 2
+
+
+def check_decoder_checkpoint(checkpoint: bytes, ctx: Optional[Context] = None) -> bool:
+    """True when ``checkpoint`` would be accepted by ``Context.decoder(checkpoint=...)`` (magic, version, checksum, sizes,
+    header fields, state).  Host only: needs no device."""
+    lib = load_library()
+    buf = np.frombuffer(bytes(checkpoint), np.uint8).copy()
+    handle = ctx.handle if ctx is not None else None
+    return lib.nblic_amd_dstream_check(handle, C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size) == 0
+
+
+class BandDecoder:
+    """A stream decoded in row bands (``nblic_amd_dstream``).  ``feed(data, final)`` appends bytes; ``run(budget)`` returns
+    (status, rows, first_row) with status 1 finished, 0 suspended, 2 needs input; ``checkpoint()`` the state to hand to
+    ``Context.decoder(checkpoint=...)``, which is then fed from ``progress()["feed_from"]`` on."""
+
+    def __init__(self, ctx: Context, band_rows: int = 0, checkpoint: Optional[bytes] = None):
+        self.ctx, self.lib, self.handle = ctx, ctx.lib, None
+        if not ctx.handle:
+            raise RuntimeError("BandDecoder: the context is closed (no HIP device behind it)")
+        if checkpoint is None:
+            self.handle = self.lib.nblic_amd_dstream_begin(ctx.handle, int(band_rows))
+        else:
+            ck = np.frombuffer(bytes(checkpoint), np.uint8).copy()
+            self.handle = self.lib.nblic_amd_dstream_resume(ctx.handle, C.c_void_p(ck.ctypes.data if ck.size else 0), ck.size)
+        if not self.handle:
+            raise RuntimeError("nblic_amd_dstream_begin / _resume failed" + (" (checkpoint refused)" if checkpoint is not None else ""))
+        self._out = None
+
+    def _live(self):
+        if not self.handle:
+            raise RuntimeError("BandDecoder is closed")
+        return self.handle
+
+    def feed(self, data: bytes, final: bool = False) -> None:
+        buf = np.frombuffer(bytes(data), np.uint8)
+        if self.lib.nblic_amd_dstream_feed(self._live(), C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size, int(final)) != 0:
+            raise RuntimeError("nblic_amd_dstream_feed failed")
+
+    def info(self) -> Optional[dict]:
+        """None while the header is not in; raises for a stream this library does not decode."""
+        v = [C.c_int() for _ in range(5)]
+        rc = self.lib.nblic_amd_dstream_info(self._live(), *[C.byref(x) for x in v])
+        if rc < 0:
+            raise RuntimeError("nblic_amd_dstream_info: not a stream this library decodes")
+        if rc == 0:
+            return None
+        return {"kind": "QNBLIC" if v[0].value else "NBLIC", "height": v[1].value, "width": v[2].value, "near": v[3].value, "effort": v[4].value}
+
+    def run(self, budget_seconds: float = 0.0, max_rows: int = 0) -> Tuple[int, np.ndarray, int]:
+        """Decodes what it can; returns (status, rows [n, w] uint8, first_row).  max_rows > 0 bounds the rows of one call."""
+        inf = self.info()
+        w = inf["width"] if inf else 1
+        h = inf["height"] if inf else 1
+        rows = max(1, min(max_rows, h) if max_rows > 0 else h)
+        if self._out is None or self._out.shape != (rows, w):
+            self._out = np.empty((rows, w), np.uint8)
+        a, b = C.c_int(), C.c_int()
+        rc = self.lib.nblic_amd_dstream_run(self._live(), float(budget_seconds), C.c_void_p(self._out.ctypes.data), self._out.nbytes, C.byref(a), C.byref(b))
+        if rc < 0:
+            raise RuntimeError("nblic_amd_dstream_run failed")
+        return rc, self._out[: b.value - a.value].copy(), a.value
+
+    def progress(self) -> dict:
+        rows, ff, nb = C.c_int(), C.c_ulonglong(), C.c_size_t()
+        digest = (C.c_ubyte * 32)()
+        state = self.lib.nblic_amd_dstream_progress(self._live(), C.byref(rows), C.byref(ff), digest, C.byref(nb))
+        return {"state": state, "rows_done": rows.value, "feed_from": ff.value, "sha256": bytes(digest).hex(), "device_bytes": nb.value}
+
+    def checkpoint(self) -> bytes:
+        need = self.lib.nblic_amd_dstream_checkpoint(self._live(), None, 0)
+        if need == 0:
+            raise RuntimeError("nblic_amd_dstream_checkpoint: nothing to write down (header not in, finished or failed)")
+        buf = np.empty(need, np.uint8)
+        if self.lib.nblic_amd_dstream_checkpoint(self.handle, C.c_void_p(buf.ctypes.data), need) != need:
+            raise RuntimeError("nblic_amd_dstream_checkpoint failed")
+        return buf.tobytes()
+
+    def close(self):
+        if self.handle:
+            self.lib.nblic_amd_dstream_end(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def decompress_bands(stream: bytes, band_rows: int = 0, chunk: int = 1 << 20, ctx: Optional[Context] = None) -> np.ndarray:
+    """A whole stream through a BandDecoder, fed ``chunk`` bytes at a time; returns the plane."""
+    own = ctx is None
+    if own:
+        ctx = Context(device=0, n_slots=1, n_coders=1)
+    try:
+        d = ctx.decoder(band_rows)
+        data = bytes(stream)
+        at, parts = 0, []
+        while True:
+            rc, rows, _ = d.run()
+            if rows.size:
+                parts.append(rows)
+            if rc == 1:
+                break
+            if rc == NEEDS_INPUT:
+                if at >= len(data):
+                    raise RuntimeError("decompress_bands: the stream ended before the image")
+                d.feed(data[at: at + chunk], final=at + chunk >= len(data))
+                at += chunk
+        w = d.info()["width"]
+        d.close()
+        return np.concatenate(parts) if parts else np.zeros((0, w), np.uint8)
+    finally:
+        if own:
+            ctx.close()

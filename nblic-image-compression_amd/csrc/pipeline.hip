@@ -24,6 +24,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include <pthread.h>
@@ -1350,7 +1351,7 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         for (int i = ch.i0; i < ch.i1; i++) launches = std::max(launches, serial_launches(jobs[size_t(i)].h, jobs[size_t(i)].rows));
         for (int l = 0; l < launches; l++)
             if (!decode_launch(items[size_t(ch.i0)], c->dec_jobs + ch.i0, jobs.data() + ch.i0, ch.i1 - ch.i0, st, true)) return false;
-        c->serial_launch_count += launches;
+        { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count += launches; }
         return true;
     };
     auto download = [&](const Chunk &ch) {
@@ -1490,7 +1491,7 @@ static int decode_fed(nblic_amd_ctx *c, const unsigned char *p, bool qnblic, uns
             if (hipMemcpyAsync(J.state, &S, sizeof S, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
             for (int l = 0; l < launches; l++)                           // launches after a stop return at once
                 if (!decode_launch(it, c->dec_jobs, &J, 1, st, false)) return -1;
-            c->serial_launch_count += launches;
+            { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count += launches; }
             if (hipMemcpyAsync(&S, J.state, sizeof S, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
             if (S.status == kStarved && !final_) { if (!feed(host.size() + chunk)) return -1; continue; }
             break;
@@ -1723,6 +1724,391 @@ static nblic_amd_stream *stream_resume(nblic_amd_ctx *c, const unsigned char *im
     }
     if (!ok || s->bytes_total == 0) { stream_free(s); return nullptr; }
     return s;
+}
+
+// ---- a stream decoded in ROW BANDS: bounded workspace, fed piece by piece, rows as they finish ----------------
+// The decoders are resumable row by row (serial_engine.h): what crosses a row boundary is the state record, the
+// least-squares column statistics B and the two rows above.  So a band decoder needs, whatever the image height:
+//   (band_rows + 2) x w reconstruction rows   the two rows above the band at index 0 / 1 (SerialJob::recon_row0), the
+//                                             band's rows after them; after a launch the last two rows move to the front
+//   2 x w x stats_stride(effort) doubles      [B | F], efforts 2 / 3, plus a snapshot of B (below)
+//   one state record, 2 x w bytes of carry, the QNBLIC tables
+//   a stream window of win_cap bytes          from absolute offset pos & ~511 (SerialJob::stream_off), + 2 KB of padding
+//                                             for the 512-byte block fetches beyond what is there
+// The caller's bytes are kept on the host only from the window's base on.  `final_` is set only when the window holds
+// the rest of a stream the caller has declared complete; a launch that stops for want of bytes (kStarved) and finds
+// nothing more to put in the window returns "needs input" instead of launching again.
+//
+// kStarvedMidRow (a row dearer than starve_margin(w), i.e. more than four bytes per pixel: no valid stream seen so far
+// comes near it) leaves the launch's rows unfinished, and the non-lean decoder -- a band decoder always launches one
+// image, so never the lean one -- has then changed nothing in the state record but its status.  What it HAS changed in
+// place is B (every pixel's update).  So B is copied aside before every launch of effort 2 / 3 and copied back after a
+// mid-row stop; the band is then run again from the same record once the window holds more bytes (the caller feeds more,
+// or, when the window was what ran out, the window grows: the only case in which the workspace grows).
+constexpr uint32_t kDecodeCheckpointVersion = 1;
+struct DecodeCheckpoint {              // followed by: state record | B | two rows above next_row | QNBLIC tables | SHA-256 of all before it
+    char magic[8];                     // "NBLDCKPT"
+    uint32_t version;                  // kDecodeCheckpointVersion
+    int32_t kind, h, w, near, k_step, effort, band_rows, next_row;
+    uint32_t reserved;
+    unsigned long long feed_from;      // absolute stream offset from which the resumed decoder must be fed (pos & ~511)
+    unsigned long long body_bytes;     // bytes between this head and the checksum
+    Sha256 rows_sha;                   // of rows [0, next_row)
+};
+static_assert(std::is_trivially_copyable<DecodeCheckpoint>::value, "written and read as bytes");
+constexpr unsigned long long kMaxStreamPos = 1ull << 48;   // no stream this library decodes comes near it
+
+static size_t dstream_state_bytes(int kind) { return kind ? kQDecodeStateBytes : kDecodeStateBytes; }
+static size_t dstream_body_bytes(int kind, int w, int effort) {
+    return dstream_state_bytes(kind) + stats_doubles(kind ? 0 : effort, w) * sizeof(double) / 2 + 2 * size_t(w) + (kind ? kQTab : 0);
+}
+
+// Every field of a checkpoint, before anything of it reaches the device.  0 = valid (head filled in), -1 = refused.
+static int dstream_check(const void *ck, size_t len, long max_px, DecodeCheckpoint &H) {
+    if (!ck || len < sizeof(DecodeCheckpoint) + 32) return -1;
+    const uint8_t *p = static_cast<const uint8_t *>(ck);
+    memcpy(&H, p, sizeof H);
+    if (memcmp(H.magic, "NBLDCKPT", 8) != 0 || H.version != kDecodeCheckpointVersion) return -1;
+    {
+        Sha256 sum;
+        sum.update(p, len - 32);
+        uint8_t d[32];
+        sum.digest(d);
+        if (memcmp(d, p + len - 32, 32) != 0) return -1;
+    }
+    if (H.kind != 0 && H.kind != 1) return -1;
+    if (!size_ok(H.h, H.w, max_px)) return -1;
+    if (H.kind == 0 && (H.near < 0 || H.near > kMaxNear || H.k_step < kMinKStep || H.k_step > kLevels || H.effort < 1 || H.effort > 3)) return -1;
+    if (H.kind == 1 && (H.near != 0 || H.effort != 0 || H.k_step != kMinKStep)) return -1;
+    if (H.band_rows < 1 || H.band_rows > H.h || H.next_row < 0 || H.next_row >= H.h) return -1;
+    if (H.body_bytes != dstream_body_bytes(H.kind, H.w, H.effort) || len != sizeof H + H.body_bytes + 32) return -1;
+    if (H.rows_sha.total != (unsigned long long)(H.next_row) * (unsigned long long)(H.w)) return -1;
+    SerialState S;
+    memcpy(&S, p + sizeof H, sizeof S);
+    const unsigned long long first = H.kind ? 8 : (unsigned long long)(kHeaderBytes);
+    if (S.status != kRunning || S.next_row != H.next_row || S.pos < first || S.pos >= kMaxStreamPos || (S.pos & ~511ull) != H.feed_from) return -1;
+    const uint8_t *tab = p + sizeof H + sizeof S;
+    if (H.kind == 0 && H.next_row > 0) {                                 // the tables a resumed launch loads: every value an index can come from
+        const uint32_t *cnt = reinterpret_cast<const uint32_t *>(tab) + kContexts;
+        for (int k = 0; k < kLevels * kTreeNodes; k++) {
+            uint32_t c;
+            memcpy(&c, cnt + k, 4);
+            if ((c & 0xFFFFu) == 0 || (c >> 16) == 0) return -1;             // bin probabilities divide by c0 + c1
+        }
+        const uint8_t *rank = tab + (size_t(kContexts) + size_t(kLevels) * kTreeNodes + 512 * kMapSyms) * 4, *sym = rank + 512 * kMapSyms;
+        for (int m = 0; m < 512; m++)
+            for (int z = 0; z < kMapSyms; z++) {
+                const int y = sym[m * kMapSyms + z];
+                if (y >= kMapSyms || rank[m * kMapSyms + y] != z) return -1;     // a permutation and its inverse
+            }
+    }
+    const size_t b_bytes = stats_doubles(H.kind ? 0 : H.effort, H.w) * sizeof(double) / 2;
+    const uint8_t *b = tab + dstream_state_bytes(H.kind) - sizeof S;
+    for (size_t k = 0; k < b_bytes; k += 8) {
+        double v;
+        memcpy(&v, b + k, 8);
+        if (!(v == v) || v - v != 0.0) return -1;                       // NaN / infinity: never a sum of pixel products
+    }
+    if (H.kind == 1) {                                                   // the twelve frequency tables and their cumulative starts
+        const uint8_t *q = b + b_bytes + 2 * size_t(H.w);
+        uint32_t freq[12 * 256], start[12 * 256];
+        memcpy(freq, q, sizeof freq); memcpy(start, q + sizeof freq, sizeof start);
+        for (int l = 0; l < 12; l++) {
+            uint32_t acc = 0;
+            for (int s = 0; s < 256; s++) {
+                if (start[l * 256 + s] != acc || freq[l * 256 + s] > 32768u) return -1;
+                acc += freq[l * 256 + s];
+            }
+            if (acc != 32768u) return -1;
+        }
+    }
+    return 0;
+}
+
+}  // namespace nblic
+
+struct nblic_amd_dstream {
+    nblic_amd_ctx *c = nullptr;
+    int device = 0;
+    hipStream_t st = nullptr;
+    int band_rows_req = 0;
+    // the header (kind 0 NBLIC, 1 QNBLIC) and the workspace it sizes
+    bool have_head = false, refused = false, failed = false, done = false;
+    nblic::DecodeItem it{};
+    int band_rows = 0;
+    uint8_t *d_rows = nullptr, *d_carry = nullptr, *d_win = nullptr, *d_tab = nullptr;
+    double *d_stats = nullptr, *d_snap = nullptr;
+    nblic::SerialState *d_state = nullptr;
+    nblic::SerialJob *d_job = nullptr;
+    size_t stats_bytes = 0, win_cap = 0, device_bytes = 0;
+    std::vector<uint8_t> qtab;                           // QNBLIC: host copy of the tables (they travel with a checkpoint)
+    // the stream as fed: bytes [pend_off, pend_off + pend.size()) of it; [win_off, win_off + win_len) are on the device
+    std::vector<uint8_t> pend;
+    unsigned long long pend_off = 0, win_off = 0, win_len = 0;
+    bool complete = false;
+    // progress
+    nblic::SerialState H{};                              // the record's header as of the last finished launch
+    int row0 = 0;                                        // image row at d_rows[0]: max(0, H.next_row - 2)
+    nblic::Sha256 sha;
+    long launches = 0;
+};
+
+namespace nblic {
+
+static void dstream_free_device(nblic_amd_dstream *d) {
+    hipFree(d->d_rows); hipFree(d->d_carry); hipFree(d->d_win); hipFree(d->d_tab); hipFree(d->d_stats); hipFree(d->d_snap);
+    hipFree(d->d_state); hipFree(d->d_job);
+    d->d_rows = d->d_carry = d->d_win = d->d_tab = nullptr; d->d_stats = d->d_snap = nullptr; d->d_state = nullptr; d->d_job = nullptr;
+}
+
+static void dstream_free(nblic_amd_dstream *d) {
+    if (!d) return;
+    if (hipSetDevice(d->device) == hipSuccess) {
+        if (d->st) hipStreamSynchronize(d->st);
+        dstream_free_device(d);
+        if (d->st) hipStreamDestroy(d->st);
+    }
+    delete d;
+}
+
+static size_t dstream_win_cap(int band_rows, int w) {
+    const size_t want = 2 * size_t(band_rows) * size_t(w) + 2 * starve_margin(w);
+    const size_t cap = want > (size_t(4) << 20) ? want : (size_t(4) << 20);
+    return (cap + 511) & ~size_t(511);
+}
+
+// The workspace of a header that has just been parsed (or of a checkpoint): depends on band_rows and w, never on h.
+static bool dstream_setup(nblic_amd_dstream *d) {
+    const DecodeItem &it = d->it;
+    d->band_rows = d->band_rows_req > 0 ? std::min(d->band_rows_req, it.h)
+                                        : std::min(it.h, std::max(1, int((long(1) << 22) / (it.kind ? 1 : (it.effort == 3 ? 8 : (it.effort == 2 ? 4 : 1))) / it.w)));
+    d->stats_bytes = stats_doubles(it.kind ? 0 : it.effort, it.w) * sizeof(double);
+    d->win_cap = dstream_win_cap(d->band_rows, it.w);
+    const size_t rows_bytes = size_t(d->band_rows + 2) * size_t(it.w);
+    bool ok = hipMalloc((void **)&d->d_rows, rows_bytes) == hipSuccess && hipMalloc((void **)&d->d_carry, 2 * size_t(it.w)) == hipSuccess &&
+              hipMalloc((void **)&d->d_win, d->win_cap + 2048) == hipSuccess &&
+              hipMalloc((void **)&d->d_state, up256(dstream_state_bytes(it.kind))) == hipSuccess &&
+              hipMalloc((void **)&d->d_job, sizeof(SerialJob)) == hipSuccess;
+    if (ok && d->stats_bytes) ok = hipMalloc((void **)&d->d_stats, d->stats_bytes) == hipSuccess && hipMalloc((void **)&d->d_snap, d->stats_bytes / 2) == hipSuccess &&
+                                   hipMemsetAsync(d->d_stats, 0, d->stats_bytes, d->st) == hipSuccess;     // NBLIC.c:789
+    if (ok && it.kind) ok = hipMalloc((void **)&d->d_tab, kQTab) == hipSuccess;
+    ok = ok && hipMemsetAsync(d->d_state, 0, up256(dstream_state_bytes(it.kind)), d->st) == hipSuccess &&
+         hipMemsetAsync(d->d_rows, 0, rows_bytes, d->st) == hipSuccess && hipMemsetAsync(d->d_win, 0, d->win_cap + 2048, d->st) == hipSuccess;
+    if (!ok) { fprintf(stderr, "[nblic_amd] band decoder: cannot set up the workspace\n"); dstream_free_device(d); return false; }
+    d->device_bytes = rows_bytes + 2 * size_t(it.w) + d->win_cap + 2048 + up256(dstream_state_bytes(it.kind)) + sizeof(SerialJob) +
+                      d->stats_bytes + d->stats_bytes / 2 + (it.kind ? kQTab : 0);
+    return true;
+}
+
+// The header (QNBLIC: and its tables) from the bytes fed so far.  Sets have_head or refused; neither: not all there yet.
+static void dstream_try_header(nblic_amd_dstream *d) {
+    if (d->have_head || d->refused) return;
+    const size_t n = d->pend.size();
+    const uint8_t *p = d->pend.data();
+    DecodeItem it{0, 0, 0, 0, 0, 0, 0, n, -1, -1};
+    const bool q = n >= 1 && p[0] == 'Q';
+    const size_t head = q ? 8 : size_t(kHeaderBytes);
+    if (n < head) { if (d->complete) d->refused = true; return; }
+    if (!parse_stream_header(p, n, d->c->max_px, it)) { d->refused = true; return; }
+    SerialState H{};
+    if (it.kind == 1) {
+        d->qtab.assign(kQTab, 0);
+        uint32_t *freq = reinterpret_cast<uint32_t *>(d->qtab.data()), *start = freq + 12 * 256;
+        int hh = 0, ww = 0;
+        std::vector<uint16_t> words(n / 2);
+        memcpy(words.data(), p, words.size() * 2);
+        const long pos = q_decode_tables(words.data(), words.size(), &hh, &ww, freq, start, nullptr);
+        if (pos < 0) {                                                   // the tables may simply not be in hand yet (at most 12 x 256 codes)
+            if (d->complete || n >= 65536) d->refused = true;
+            return;
+        }
+        H.pos = (unsigned long long)(pos) * 2ull;
+    } else {
+        H.pos = kHeaderBytes;
+    }
+    d->it = it;
+    if (!dstream_setup(d)) { d->failed = true; return; }
+    if (it.kind == 1 && hipMemcpyAsync(d->d_tab, d->qtab.data(), kQTab, hipMemcpyHostToDevice, d->st) != hipSuccess) { d->failed = true; return; }
+    d->H = H;
+    d->win_off = d->win_len = 0;
+    d->have_head = true;
+}
+
+// Slides the device window to the record's position and tops it up from what has been fed.
+static bool dstream_fill_window(nblic_amd_dstream *d) {
+    const unsigned long long base = d->H.pos & ~511ull, pend_end = d->pend_off + d->pend.size();
+    if (base < d->pend_off) return false;                               // bytes the decoder needs were never fed (resume fed from the wrong offset)
+    if (base != d->win_off) { d->win_off = base; d->win_len = 0; }
+    const unsigned long long want_end = std::min(pend_end, base + d->win_cap);
+    const unsigned long long have_end = d->win_off + d->win_len;
+    if (want_end > have_end) {
+        if (hipMemcpyAsync(d->d_win + (have_end - base), d->pend.data() + (have_end - d->pend_off), size_t(want_end - have_end), hipMemcpyHostToDevice, d->st) != hipSuccess ||
+            hipStreamSynchronize(d->st) != hipSuccess) return false;
+        d->win_len = want_end - base;
+    }
+    if (base > d->pend_off) {                                            // keep only the bytes at or after the window base
+        d->pend.erase(d->pend.begin(), d->pend.begin() + ptrdiff_t(base - d->pend_off));
+        d->pend_off = base;
+    }
+    return true;
+}
+
+static bool dstream_window_holds_all_fed(const nblic_amd_dstream *d) { return d->win_off + d->win_len == d->pend_off + d->pend.size(); }
+
+// 1 finished, 0 suspended (budget spent, or rows_out full), 2 needs input, -1 error.
+static int dstream_run(nblic_amd_dstream *d, double budget_s, unsigned char *rows_out, size_t cap, int *first_row, int *end_row) {
+    int first = d->have_head ? d->H.next_row : 0, end = first;
+    auto report = [&](int rc) { if (first_row) *first_row = first; if (end_row) *end_row = end; return rc; };
+    if (d->failed || d->refused) return report(-1);
+    if (d->done) return report(1);
+    if (hipSetDevice(d->device) != hipSuccess) return report(-1);
+    dstream_try_header(d);
+    if (d->failed || d->refused) return report(-1);
+    if (!d->have_head) return report(d->complete ? -1 : 2);
+    const DecodeItem &it = d->it;
+    const size_t w = size_t(it.w);
+    first = end = d->H.next_row;
+    auto fail = [&](const char *what) { fprintf(stderr, "[nblic_amd] band decoder: %s\n", what); d->failed = true; hipStreamSynchronize(d->st); return report(-1); };
+    if (!rows_out || cap < size_t(d->band_rows) * w) return report(-1);          // rows_out holds less than one band (nothing has happened)
+    const auto t0 = std::chrono::steady_clock::now();
+    size_t written = 0;                                                  // rows in rows_out
+    while (d->H.next_row < it.h) {
+        const int i0 = d->H.next_row, rows = std::min(d->band_rows, it.h - i0);
+        if ((written + size_t(rows)) * w > cap) return report(0);                 // rows_out is full
+        if (!dstream_fill_window(d)) return fail("stream window");
+        const bool final_ = d->complete && dstream_window_holds_all_fed(d);
+        SerialJob J{};
+        J.recon = d->d_rows; J.recon_row0 = d->row0;
+        J.stream = d->d_win; J.stream_off = d->win_off;
+        J.stats = d->d_stats; J.state = d->d_state;
+        J.h = it.h; J.w = it.w; J.near = it.near; J.k_step = it.k_step; J.effort = it.effort; J.rows = rows;
+        if (it.kind) { J.q_freq = reinterpret_cast<const uint32_t *>(d->d_tab); J.q_start = J.q_freq + 12 * 256; J.q_slot = nullptr; }
+        SerialState S = d->H;
+        S.avail = d->win_off + d->win_len; S.final_ = final_ ? 1 : 0; S.status = kRunning;
+        if (d->d_snap && hipMemcpyAsync(d->d_snap, d->d_stats, d->stats_bytes / 2, hipMemcpyDeviceToDevice, d->st) != hipSuccess) return fail("snapshot");
+        if (hipMemcpyAsync(d->d_state, &S, sizeof S, hipMemcpyHostToDevice, d->st) != hipSuccess ||
+            hipMemcpyAsync(d->d_job, &J, sizeof J, hipMemcpyHostToDevice, d->st) != hipSuccess) return fail("upload");
+        if (!decode_launch(it, d->d_job, &J, 1, d->st, false)) return fail("launch");
+        if (hipMemcpyAsync(&S, d->d_state, sizeof S, hipMemcpyDeviceToHost, d->st) != hipSuccess || hipStreamSynchronize(d->st) != hipSuccess) return fail("state");
+        d->launches++;
+        { std::lock_guard<std::mutex> l(d->c->stat_m); d->c->serial_launch_count++; }
+        if (S.status == kFailed) return fail("the stream is damaged or ends too early");
+        if (S.status == kStarvedMidRow) {
+            // nothing of the launch is kept: B back from the snapshot, the record's header is still d->H (see above)
+            if (d->d_snap && (hipMemcpyAsync(d->d_stats, d->d_snap, d->stats_bytes / 2, hipMemcpyDeviceToDevice, d->st) != hipSuccess ||
+                              hipStreamSynchronize(d->st) != hipSuccess)) return fail("restore");
+            if (dstream_window_holds_all_fed(d)) return report(2);       // more bytes have to come first
+            // the window itself was too small for the row: grow it (the caller has fed the bytes)
+            hipFree(d->d_win); d->d_win = nullptr;
+            const size_t cap2 = d->win_cap * 2;
+            if (hipMalloc((void **)&d->d_win, cap2 + 2048) != hipSuccess || hipMemsetAsync(d->d_win, 0, cap2 + 2048, d->st) != hipSuccess) return fail("window");
+            d->device_bytes += cap2 - d->win_cap;
+            d->win_cap = cap2; d->win_len = 0;
+            continue;
+        }
+        const int at = S.next_row;
+        if (at < i0 || at > i0 + rows) return fail("decoder state");
+        if (at > i0) {                                                   // rows [i0, at) are final: to the caller, into the hash, the last two to the front
+            const size_t n = size_t(at - i0) * w;
+            if (hipMemcpyAsync(rows_out + written * w, d->d_rows + size_t(i0 - d->row0) * w, n, hipMemcpyDeviceToHost, d->st) != hipSuccess) return fail("rows to the host");
+            const int r0 = std::max(0, at - 2);
+            if (r0 > d->row0) {
+                const size_t keep = size_t(at - r0) * w;
+                if (hipMemcpyAsync(d->d_carry, d->d_rows + size_t(r0 - d->row0) * w, keep, hipMemcpyDeviceToDevice, d->st) != hipSuccess ||
+                    hipMemcpyAsync(d->d_rows, d->d_carry, keep, hipMemcpyDeviceToDevice, d->st) != hipSuccess) return fail("carry");
+                d->row0 = r0;
+            }
+            if (hipStreamSynchronize(d->st) != hipSuccess) return fail("rows to the host");
+            d->sha.update(rows_out + written * w, n);
+            written += size_t(at - i0);
+            end = at;
+        }
+        const bool moved = S.pos != d->H.pos || at > i0;
+        d->H = S;
+        d->H.status = kRunning;
+        if (S.status == kDone) { d->done = true; break; }
+        if (S.status == kStarved && !moved && dstream_window_holds_all_fed(d)) { d->H.status = kRunning; return report(2); }
+        if (S.status == kStarved && !moved) return fail("no progress");
+        if (budget_s > 0 && d->H.next_row < it.h && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= budget_s) return report(0);
+    }
+    return report(d->done ? 1 : 0);
+}
+
+static size_t dstream_checkpoint_bytes(const nblic_amd_dstream *d) {
+    return sizeof(DecodeCheckpoint) + dstream_body_bytes(d->it.kind, d->it.w, d->it.effort) + 32;
+}
+
+static size_t dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap) {
+    if (!d->have_head || d->failed || d->done) return 0;
+    const size_t need = dstream_checkpoint_bytes(d);
+    if (!buf || cap < need) return need;
+    if (hipSetDevice(d->device) != hipSuccess) return 0;
+    const DecodeItem &it = d->it;
+    DecodeCheckpoint H{};
+    memcpy(H.magic, "NBLDCKPT", 8);
+    H.version = kDecodeCheckpointVersion;
+    H.kind = it.kind; H.h = it.h; H.w = it.w; H.near = it.near; H.k_step = it.k_step; H.effort = it.effort;
+    H.band_rows = d->band_rows; H.next_row = d->H.next_row;
+    H.feed_from = d->H.pos & ~511ull;
+    H.body_bytes = dstream_body_bytes(it.kind, it.w, it.effort);
+    H.rows_sha = d->sha;
+    uint8_t *p = static_cast<uint8_t *>(buf);
+    memcpy(p, &H, sizeof H);
+    uint8_t *q = p + sizeof H;
+    const size_t sb = dstream_state_bytes(it.kind), b_bytes = d->stats_bytes / 2;
+    bool ok = hipMemcpyAsync(q, d->d_state, sb, hipMemcpyDeviceToHost, d->st) == hipSuccess;
+    if (b_bytes) ok = ok && hipMemcpyAsync(q + sb, d->d_stats, b_bytes, hipMemcpyDeviceToHost, d->st) == hipSuccess;
+    uint8_t *rows = q + sb + b_bytes;
+    memset(rows, 0, 2 * size_t(it.w));
+    const int r0 = std::max(0, d->H.next_row - 2), nr = d->H.next_row - r0;      // the two rows above next_row (fewer at the top: zeros in front)
+    if (nr > 0) ok = ok && hipMemcpyAsync(rows + size_t(2 - nr) * size_t(it.w), d->d_rows + size_t(r0 - d->row0) * size_t(it.w), size_t(nr) * size_t(it.w), hipMemcpyDeviceToHost, d->st) == hipSuccess;
+    ok = ok && hipStreamSynchronize(d->st) == hipSuccess;
+    if (!ok) return 0;
+    SerialState S = d->H;                                                // the header as the host holds it (the device copy may say kStarved)
+    S.status = kRunning; S.avail = 0; S.final_ = 0;
+    memcpy(q, &S, sizeof S);
+    if (it.kind) memcpy(rows + 2 * size_t(it.w), d->qtab.data(), kQTab);
+    Sha256 sum;
+    sum.update(p, need - 32);
+    sum.digest(p + need - 32);
+    return need;
+}
+
+static nblic_amd_dstream *dstream_new(nblic_amd_ctx *c, int band_rows) {
+    if (!c || hipSetDevice(c->device) != hipSuccess) return nullptr;
+    auto *d = new nblic_amd_dstream;
+    d->c = c; d->device = c->device; d->band_rows_req = band_rows;
+    if (hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking) != hipSuccess) { d->st = nullptr; dstream_free(d); return nullptr; }
+    return d;
+}
+
+static nblic_amd_dstream *dstream_resume(nblic_amd_ctx *c, const void *ck, size_t len) {
+    if (!c) return nullptr;
+    DecodeCheckpoint H;
+    if (dstream_check(ck, len, c->max_px, H) != 0) return nullptr;
+    nblic_amd_dstream *d = dstream_new(c, H.band_rows);
+    if (!d) return nullptr;
+    d->it = DecodeItem{0, H.h, H.w, H.near, H.k_step, H.effort, H.kind, 0, -1, -1};
+    if (!dstream_setup(d) || d->band_rows != H.band_rows) { dstream_free(d); return nullptr; }
+    const uint8_t *q = static_cast<const uint8_t *>(ck) + sizeof H;
+    const size_t sb = dstream_state_bytes(H.kind), b_bytes = d->stats_bytes / 2;
+    memcpy(&d->H, q, sizeof(SerialState));
+    d->sha = H.rows_sha;
+    d->row0 = std::max(0, H.next_row - 2);
+    const uint8_t *rows = q + sb + b_bytes;
+    const int nr = H.next_row - d->row0;
+    bool ok = hipMemcpyAsync(d->d_state, q, sb, hipMemcpyHostToDevice, d->st) == hipSuccess;
+    if (b_bytes) ok = ok && hipMemcpyAsync(d->d_stats, q + sb, b_bytes, hipMemcpyHostToDevice, d->st) == hipSuccess;
+    if (nr > 0) ok = ok && hipMemcpyAsync(d->d_rows, rows + size_t(2 - nr) * size_t(H.w), size_t(nr) * size_t(H.w), hipMemcpyHostToDevice, d->st) == hipSuccess;
+    if (H.kind) {
+        d->qtab.assign(rows + 2 * size_t(H.w), rows + 2 * size_t(H.w) + kQTab);
+        ok = ok && hipMemcpyAsync(d->d_tab, d->qtab.data(), kQTab, hipMemcpyHostToDevice, d->st) == hipSuccess;
+    }
+    ok = ok && hipStreamSynchronize(d->st) == hipSuccess;
+    if (!ok) { dstream_free(d); return nullptr; }
+    d->pend_off = d->win_off = H.feed_from; d->win_len = 0;
+    d->have_head = true;
+    return d;
 }
 
 // ---- default context behind the drop-in entry points ---------------------------------------
@@ -2046,6 +2432,45 @@ int nblic_amd_stream_recon(nblic_amd_stream *s, unsigned char *plane, int *first
     return hipMemcpy(plane + at, (s->near > 0 ? s->d_recon : s->d_img) + at, n, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 void nblic_amd_stream_end(nblic_amd_stream *s) { stream_free(s); }
+
+nblic_amd_dstream *nblic_amd_dstream_begin(nblic_amd_ctx *c, int band_rows) { return dstream_new(c, band_rows); }
+nblic_amd_dstream *nblic_amd_dstream_resume(nblic_amd_ctx *c, const void *checkpoint, size_t bytes) { return dstream_resume(c, checkpoint, bytes); }
+int nblic_amd_dstream_check(nblic_amd_ctx *c, const void *checkpoint, size_t bytes) {
+    DecodeCheckpoint H;
+    return dstream_check(checkpoint, bytes, c ? c->max_px : kMaxPixels, H);
+}
+int nblic_amd_dstream_feed(nblic_amd_dstream *d, const unsigned char *bytes, size_t n, int final_) {
+    if (!d || d->failed || (n && !bytes) || (d->complete && n)) return -1;
+    d->pend.insert(d->pend.end(), bytes, bytes + n);
+    if (final_) d->complete = true;
+    return 0;
+}
+int nblic_amd_dstream_info(nblic_amd_dstream *d, int *kind, int *height, int *width, int *near, int *effort) {
+    if (!d) return -1;
+    if (!d->have_head && !d->refused && !d->failed && hipSetDevice(d->device) == hipSuccess) dstream_try_header(d);
+    if (d->refused || (d->failed && !d->have_head)) return -1;
+    if (!d->have_head) return 0;
+    if (kind) *kind = d->it.kind;
+    if (height) *height = d->it.h;
+    if (width) *width = d->it.w;
+    if (near) *near = d->it.near;
+    if (effort) *effort = d->it.effort;
+    return 1;
+}
+int nblic_amd_dstream_run(nblic_amd_dstream *d, double budget_seconds, unsigned char *rows_out, size_t cap, int *first_row, int *end_row) {
+    if (!d) return -1;
+    return dstream_run(d, budget_seconds, rows_out, cap, first_row, end_row);
+}
+int nblic_amd_dstream_progress(nblic_amd_dstream *d, int *rows_done, unsigned long long *feed_from, unsigned char sha256[32], size_t *device_bytes) {
+    if (!d) return -1;
+    if (rows_done) *rows_done = d->have_head ? d->H.next_row : 0;
+    if (feed_from) *feed_from = d->have_head ? (d->H.pos & ~511ull) : 0ull;
+    if (sha256) { Sha256 copy = d->sha; copy.digest(sha256); }
+    if (device_bytes) *device_bytes = d->device_bytes;
+    return (d->failed || d->refused) ? -1 : (d->done ? 1 : 0);
+}
+size_t nblic_amd_dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap) { return d ? dstream_checkpoint(d, buf, cap) : 0; }
+void nblic_amd_dstream_end(nblic_amd_dstream *d) { dstream_free(d); }
 
 int nblic_amd_set_device_coder(nblic_amd_ctx *c, int n_packs, int min_outstanding) {
     if (!c || n_packs < 0 || n_packs > 64) return -1;

@@ -47,7 +47,9 @@ enum : int { kRunning = 0, kDone = 1, kFailed = -1, kStarved = 2, kStarvedMidRow
 // kStarved: a decoder of a stream that is still being fed stopped cleanly in front of row next_row because fewer than
 // starve_margin(w) bytes were left -- feed more, set status back to kRunning, launch again.  kStarvedMidRow: it ran dry
 // inside a row although the margin was there (a row that costs more than four bytes per pixel: never seen, possible
-// for a damaged stream); the record is then NOT resumable and the image has to be decoded again with the whole stream.
+// for a damaged stream); the record is then NOT resumable as it stands: the lean decoder has changed the hit counts in
+// it and every decoder has changed B in place.  decode_fed decodes the image again with the whole stream; the band
+// decoder (pipeline.hip, nblic_amd_dstream) never launches the lean one and restores B from a copy taken before the launch.
 constexpr size_t starve_margin(int w) { return size_t(4) * size_t(w) + 1024; }
 constexpr size_t kModelStateBytes = sizeof(SerialState) + 2048 * sizeof(int);
 constexpr size_t kDecodeStateBytes = sizeof(SerialState) + (2048 + 4096 + 512 * 20) * sizeof(int) + 2 * 512 * 20;
@@ -65,6 +67,8 @@ struct SerialJob {
     int h, w, near, k_step, effort;
     int rows;                  // rows per launch (>= 1)
     int out_row0;              // encode: the row whose records sit at index 0 of rec1 / pxs (0, or the first row of the band they hold)
+    int recon_row0;            // decode: the image row stored at index 0 of recon (0: the whole plane; a band decoder: the first row it holds)
+    unsigned long long stream_off;   // decode: absolute stream offset of byte 0 of `stream` (a multiple of 512; SerialState::pos / avail stay absolute)
     // QNBLIC decode only
     const uint32_t *q_freq, *q_start; const uint8_t *q_slot;      // 12 x 256 frequencies and cumulative starts; q_slot: unused (the kernel searches q_start)
 };

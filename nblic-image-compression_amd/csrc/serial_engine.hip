@@ -842,18 +842,21 @@ __global__ void __launch_bounds__(64 * WAVES) k_serial_model(const SerialJob *__
 // read, not a trip to HBM in the middle of the chain.  `len` is what is PRESENT of the stream (the device
 // copy is padded so that whole 512-byte blocks can be fetched); consuming a byte at or beyond it raises
 // `dry` and returns zeros without moving on, and the caller winds the image up at once.
+// `len` and `pos` are ABSOLUTE stream offsets; `base` holds the stream from absolute offset `off` on (a multiple of 512:
+// 0 for a whole stream, the window's start for a band decoder), so only the block fetch subtracts it.
 struct StreamWindow {
     const uint8_t *base; size_t len, pos;      // pos = next byte to consume
+    size_t off;                                // absolute offset of base[0]
     uint32_t *sbuf;
     bool dry;
     __device__ void fill_half(size_t from) {   // bytes [from, from + 512) -> sbuf half (from / 512) & 1; from is a multiple of 512
         const auto src = gp(reinterpret_cast<const uint32_t *>(base));       // device copies are 16-byte aligned and padded by 2 KB
-        const size_t word = from / 4 + threadIdx.x * 2;
+        const size_t word = (from - off) / 4 + threadIdx.x * 2;
         sbuf[((from >> 9) & 1) * 128 + threadIdx.x * 2] = src[word];
         sbuf[((from >> 9) & 1) * 128 + threadIdx.x * 2 + 1] = src[word + 1];
     }
-    __device__ void start(const uint8_t *b, size_t n, size_t at, uint32_t *buf) {
-        base = b; len = n; pos = at; sbuf = buf; dry = false;
+    __device__ void start(const uint8_t *b, size_t b_off, size_t n, size_t at, uint32_t *buf) {
+        base = b; off = b_off; len = n; pos = at; sbuf = buf; dry = false;
         fill_half(at & ~size_t(511)); fill_half((at & ~size_t(511)) + 512);
         wave_sync();
     }
@@ -967,7 +970,7 @@ __device__ __forceinline__ int decode_body(Lds &S, uint8_t *rows, const SerialJo
     }();
     const NearParams np = near_params(J.near);
     const uint64_t ktab = level_shift_table(k_step);
-    const auto out = gp(J.recon);
+    const auto out = gp(J.recon - size_t(J.recon_row0) * size_t(w));        // indexed by image row: recon holds rows from recon_row0 on
     LsqWalk<N> lw;
     if constexpr (N > 0) lw.init(J.stats, w, lane, 0, bias_io);
     LaneFront lf;
@@ -1110,10 +1113,10 @@ __global__ void __launch_bounds__(64) k_serial_decode(const SerialJob *__restric
     uint32_t cs[3] = {0u, 0xFFFFFFFFu, 0u};                              // NBLIC.c:536-549
     int bias = lsq::kBiasInit;
     if (i0 == 0) {
-        sw.start(J.stream, avail, kHeaderBytes, S.sbuf);
+        sw.start(J.stream, size_t(J.stream_off), avail, kHeaderBytes, S.sbuf);
         for (int k = 0; k < 4; k++) cs[2] = (cs[2] << 8) | sw.next();
     } else {
-        sw.start(J.stream, avail, size_t(st->pos), S.sbuf);
+        sw.start(J.stream, size_t(J.stream_off), avail, size_t(st->pos), S.sbuf);
         cs[0] = st->lo; cs[1] = st->hi; cs[2] = st->window; bias = st->bias;
     }
     const int rs = (J.w + kRowPad + 15) & ~15;
@@ -1177,7 +1180,7 @@ template <bool CACHED>
 __device__ __forceinline__ int qdecode_rows(QDecodeLds &S, uint8_t *rows, const SerialJob &J, const int rs, const int i0, const int i1,
                                             StreamWindow &sw, QRans &rans, const bool final_, const size_t row_need, int &stop) {
     const int lane = int(threadIdx.x), w = J.w;
-    const auto out = gp(J.recon);
+    const auto out = gp(J.recon - size_t(J.recon_row0) * size_t(w));        // indexed by image row: recon holds rows from recon_row0 on
     const QLaneConst lc = kQLanes.l[lane];
     if (CACHED && i0 > 0) {
         for (int r = i0 > 1 ? i0 - 2 : i0 - 1; r < i0; r++) {
@@ -1353,7 +1356,7 @@ __global__ void __launch_bounds__(64) k_serial_qdecode(const SerialJob *__restri
     uint8_t *rows = rows_raw + 4;
     if (lane < 4) rows_raw[lane] = 0;
     StreamWindow sw;
-    sw.start(J.stream, avail, size_t(st->pos), S.sbuf);                   // a fresh image: the host has set pos to the first word after the tables
+    sw.start(J.stream, size_t(J.stream_off), avail, size_t(st->pos), S.sbuf);                   // a fresh image: the host has set pos to the first word after the tables
     auto next_word = [&]() { const uint32_t lo = sw.next(); return lo | (sw.next() << 8); };
     QRans rans;
     if (i0 == 0) { rans.x = next_word() << 16; rans.x |= next_word(); }
