@@ -212,9 +212,9 @@ void nblic_amd_stream_end(nblic_amd_stream *s);
  *   _info     1 once the header (QNBLIC: and its tables) is in, 0 not yet, -1 refused (not a stream this library decodes).
  *   _run      decodes until the image is finished (returns 1), budget_seconds (> 0) have passed or rows_out is full
  *             (returns 0), or the fed bytes run out before the stream is complete (returns 2: feed more, call again); -1
- *             on error (damaged or truncated stream, rows_out smaller than one band).  The rows finished by THIS call are
- *             written to rows_out one after the other (cap bytes, at least band_rows x width) and are rows
- *             [*first_row, *end_row) of the image.
+ *             on error (damaged or truncated stream, rows_out smaller than the next band).  The rows finished by THIS call
+ *             are written to rows_out one after the other (cap bytes, at least min(band_rows, rows left) x width) and are
+ *             rows [*first_row, *end_row) of the image.
  *   _progress rows finished, the offset the stream would have to be fed from after a checkpoint taken now, the SHA-256 of
  *             the rows finished so far, device bytes held; returns 1 finished / 0 / -1 failed.
  *   _checkpoint  writes the checkpoint into buf (cap bytes) and returns its size; with buf == NULL or cap too small it only
@@ -232,10 +232,13 @@ size_t nblic_amd_dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap)
 void nblic_amd_dstream_end(nblic_amd_dstream *d);
 
 /* The reference's decoders take no stream length (src/NBLIC.h:72, src/QNBLIC.h:16).  NBLICdecompress / QNBLICdecompress
- * therefore fetch the caller's stream ON DEMAND in steps of `bytes` (default 1 MiB, at least 4096): the decoder stops in
- * front of a row when it is about to run short, the next step is copied in, it resumes.  No byte beyond the last one the
- * decoder consumes plus one step is read, and each step is copied by the kernel (a pipe write), so a stream that ends
- * right in front of an unmapped page is read exactly to its end instead of faulting.  ctx == NULL: the drop-in context.
+ * therefore run a band decoder (nblic_amd_dstream above, band_rows as set by nblic_amd_set_serial_rows) and fetch the
+ * caller's stream ON DEMAND in steps of `bytes` (default 1 MiB, at least 4096): the decoder stops in front of a row when
+ * it is about to run short, the next step is copied in, it resumes.  No byte beyond the last one the decoder consumes
+ * plus one step and the starvation margin is read, and each step is copied by the kernel (a pipe write), so a stream
+ * that ends right in front of an unmapped page is read exactly to its end instead of faulting.  There is no cap on the
+ * stream's length, the device workspace is the band decoder's, and the rows are written into p_img as they finish
+ * (after a failure, those decoded before it may be there).  ctx == NULL: the drop-in context.
  * nblic_amd_last_fed_bytes: how many bytes the last drop-in decode read from the caller's buffer.                      */
 void nblic_amd_set_feed_chunk(nblic_amd_ctx *ctx, size_t bytes);
 long nblic_amd_last_fed_bytes(nblic_amd_ctx *ctx);

@@ -1224,6 +1224,18 @@ constexpr int kDecodeChunk = 1024;                                              
 constexpr size_t kQTab = 2 * 12 * 256 * sizeof(uint32_t);                                   // QNBLIC: frequencies, cumulative starts (the kernel derives its symbol index from them)
 static size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
 
+// QNBLIC: the header and the twelve histogram tables in front of the rANS words -- at most 4 + 12 x 256 16-bit codes
+// (q_entropy.cpp q_read_hist) -- from the n bytes at p into a kQTab buffer.  Returns the index of the first rANS word,
+// or -1 when the tables do not parse from those bytes.
+static long q_parse_tables(const unsigned char *p, size_t n, uint8_t *tab) {
+    uint16_t words[4 + 12 * 256];
+    const size_t n_words = std::min(n / 2, sizeof words / 2);
+    memcpy(words, p, n_words * 2);
+    uint32_t *freq = reinterpret_cast<uint32_t *>(tab);
+    int hh = 0, ww = 0;
+    return q_decode_tables(words, n_words, &hh, &ww, freq, freq + 12 * 256, nullptr);
+}
+
 // Header of a stream of which `len` bytes are in hand (NBLIC.c:698-745, QNBLIC.c:475-486).  0 = not a stream this
 // library decodes (or refused: size, parameters), 1 = fields filled in.
 static int parse_stream_header(const unsigned char *p, size_t len, long max_px, DecodeItem &it) {
@@ -1277,9 +1289,7 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         if (size_t(it.h) * size_t(it.w) > img_caps[k]) continue;
         if (it.kind == 1) {                                              // QNBLIC: histogram tables parsed on the host; a stream whose tables
             std::vector<uint8_t> tab(kQTab);                             // do not parse is refused here and never reaches the GPU
-            uint32_t *freq = reinterpret_cast<uint32_t *>(tab.data()), *start = freq + 12 * 256;
-            int hh = 0, ww = 0;
-            it.q_pos = q_decode_tables(reinterpret_cast<const uint16_t *>(streams[k]), lens[k] / 2, &hh, &ww, freq, start, nullptr);
+            it.q_pos = q_parse_tables(streams[k], lens[k], tab.data());
             if (it.q_pos < 0 || size_t(it.q_pos) * 2 + 4 > lens[k]) continue;
             it.qtab = int(qtabs.size());
             qtabs.push_back(std::move(tab));
@@ -1375,9 +1385,10 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
 
 // ---- the drop-in decoders: a stream whose length nobody tells us ------------------------------------
 // The reference's decoders take no length (NBLIC.h:72, QNBLIC.h:16): they read what the encoder wrote, byte by byte.
-// The shims fetch the stream in steps of `feed_chunk` bytes ON DEMAND -- the decoder stops in front of a row when it is
-// about to run short (SerialState kStarved), the next step is copied in, it goes on -- so that no byte beyond what the
-// decoder consumes plus one step is read from the caller's buffer.  Every step is copied by the KERNEL (write(2) into a
+// The shims run a band decoder (nblic_amd_dstream, decode_dropin below) and feed it the stream in steps of `feed_chunk`
+// bytes ON DEMAND -- it asks for input when the kernel stops in front of a row it is about to run short in (SerialState
+// kStarved), the next step is copied in, it goes on -- so that no byte beyond what the decoder consumes plus one step
+// and the starvation margin is read from the caller's buffer.  Every step is copied by the KERNEL (write(2) into a
 // pipe, read back): where the caller's memory ends (the next page unmapped or protected, a file mapping past its end)
 // the copy comes back short instead of raising a signal, and a stream that sits right at the end of a mapping is read
 // exactly to its last byte.
@@ -1414,97 +1425,6 @@ static size_t safe_copy(nblic_amd_ctx *c, void *dst, const void *src, size_t n) 
         if (size_t(k) < want) break;                                                // stopped at the end of the readable memory
     }
     return done;
-}
-
-// Decodes ONE stream that starts at p; *ph .. *peffort receive the header fields.  0 / -1.
-static int decode_fed(nblic_amd_ctx *c, const unsigned char *p, bool qnblic, unsigned char *img, int *ph, int *pw, int *pnear, int *peffort) {
-    if (hipSetDevice(c->device) != hipSuccess) return -1;
-    c->fed_bytes = 0;
-    unsigned char head[kHeaderBytes];
-    const size_t head_want = qnblic ? 8 : size_t(kHeaderBytes);
-    if (safe_copy(c, head, p, head_want) < head_want) return -1;
-    DecodeItem it{0, 0, 0, 0, 0, 0, 0, head_want, -1, -1};
-    if (!parse_stream_header(head, head_want, c->max_px, it) || (it.kind == 1) != qnblic) return -1;
-    *ph = it.h; *pw = it.w;
-    if (pnear) *pnear = it.near;
-    if (peffort) *peffort = it.effort;
-    const size_t npx = size_t(it.h) * size_t(it.w);
-    // no valid stream of this geometry is longer (worst case seen: 1.0025 B/px + 20; QNBLIC: a word per pixel + tables)
-    const size_t bound = qnblic ? 2 * npx + 32768 + 16 : npx + npx / 8 + 4096;
-    const size_t sb = stats_doubles(it.effort, it.w) * sizeof(double);
-    const size_t arena = up256(bound + 2048) + up256(npx) + up256(sb) + decode_state_bytes(it) + (qnblic ? up256(kQTab) : 0);
-    if (!ensure_decode_space(c, arena, 1)) return -1;
-    hipStream_t st = c->dec_stream;
-    size_t off = 0;
-    uint8_t *d_stream = c->dec_arena + off; off += up256(bound + 2048);
-    SerialJob J{};
-    J.recon = c->dec_arena + off; off += up256(npx);
-    if (sb) { J.stats = reinterpret_cast<double *>(c->dec_arena + off); off += up256(sb); }
-    J.state = reinterpret_cast<SerialState *>(c->dec_arena + off); off += decode_state_bytes(it);
-    uint8_t *d_tab = qnblic ? c->dec_arena + off : nullptr;
-    J.stream = d_stream;
-    J.h = it.h; J.w = it.w; J.near = it.near; J.k_step = it.k_step; J.effort = it.effort;
-    J.rows = serial_rows_per_launch(it.h, it.w, qnblic ? 1 : it.effort, c->serial_rows);
-    if (qnblic) { J.q_freq = reinterpret_cast<const uint32_t *>(d_tab); J.q_start = J.q_freq + 12 * 256; J.q_slot = nullptr; }
-    if (hipMemcpyAsync(c->dec_jobs, &J, sizeof J, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-
-    std::vector<uint8_t> host;                                           // the stream as far as it has been fetched
-    bool final_ = false;
-    auto feed = [&](size_t want_total) -> bool {                         // extends `host` (and the device copy) to want_total bytes, or to where the memory ends
-        if (want_total > bound) want_total = bound;
-        const size_t have = host.size();
-        if (want_total <= have) { if (have >= bound) final_ = true; return true; }
-        host.resize(want_total);
-        const size_t got = safe_copy(c, host.data() + have, p + have, want_total - have);
-        host.resize(have + got);
-        if (got < want_total - have || host.size() >= bound) final_ = true;
-        c->fed_bytes = long(host.size());
-        if (got == 0) return true;
-        // (the kernel fetches whole 512-byte blocks beyond what is there; it never CONSUMES a byte at or beyond `avail`)
-        return hipMemcpyAsync(d_stream + have, host.data() + have, got, hipMemcpyHostToDevice, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-    };
-    const size_t chunk = c->feed_chunk < 4096 ? 4096 : c->feed_chunk;
-    if (!feed(chunk)) return -1;
-    SerialState H{};
-    if (qnblic) {                                                        // the histogram tables sit in front of the rANS words: at most 12 x 256 codes
-        std::vector<uint8_t> tab(kQTab);
-        uint32_t *freq = reinterpret_cast<uint32_t *>(tab.data()), *start = freq + 12 * 256;
-        int hh = 0, ww = 0;
-        long pos = q_decode_tables(reinterpret_cast<const uint16_t *>(host.data()), host.size() / 2, &hh, &ww, freq, start, nullptr);
-        if (pos < 0 && !final_ && host.size() < 65536) {                 // the tables may simply not be in hand yet
-            if (!feed(65536)) return -1;
-            pos = q_decode_tables(reinterpret_cast<const uint16_t *>(host.data()), host.size() / 2, &hh, &ww, freq, start, nullptr);
-        }
-        if (pos < 0) return -1;
-        if (hipMemcpyAsync(d_tab, tab.data(), kQTab, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-        H.pos = (unsigned long long)(pos) * 2ull;
-    } else {
-        H.pos = kHeaderBytes;
-    }
-    const int launches = serial_launches(it.h, J.rows);
-    for (int attempt = 0; attempt < 2; attempt++) {                      // the second attempt (whole stream in hand) only after kStarvedMidRow
-        if (sb && hipMemsetAsync(J.stats, 0, sb, st) != hipSuccess) return -1;
-        SerialState S = H;
-        for (;;) {
-            S.avail = host.size(); S.final_ = final_ ? 1 : 0; S.status = kRunning;
-            // header fields the host owns are rewritten; on a resumed image the kernel's own fields come back unchanged
-            if (hipMemcpyAsync(J.state, &S, sizeof S, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-            for (int l = 0; l < launches; l++)                           // launches after a stop return at once
-                if (!decode_launch(it, c->dec_jobs, &J, 1, st, false)) return -1;
-            { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count += launches; }
-            if (hipMemcpyAsync(&S, J.state, sizeof S, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-            if (S.status == kStarved && !final_) { if (!feed(host.size() + chunk)) return -1; continue; }
-            break;
-        }
-        if (S.status == kDone) {
-            if (hipMemcpyAsync(img, J.recon, npx, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1;
-            return 0;
-        }
-        if (S.status != kStarvedMidRow || final_) return -1;
-        if (!feed(bound)) return -1;                                      // a row dearer than the margin allows: everything there is, from the top
-        final_ = true;
-    }
-    return -1;
 }
 
 // ---- one image in ROW BANDS: bounded workspace, bounded launches, suspend and resume ----------------
@@ -1831,6 +1751,7 @@ struct nblic_amd_dstream {
     nblic_amd_ctx *c = nullptr;
     int device = 0;
     hipStream_t st = nullptr;
+    bool own_st = false;                                 // st is this object's own (else lent by decode_dropin: the context's dec_stream)
     int band_rows_req = 0;
     // the header (kind 0 NBLIC, 1 QNBLIC) and the workspace it sizes
     bool have_head = false, refused = false, failed = false, done = false;
@@ -1866,7 +1787,7 @@ static void dstream_free(nblic_amd_dstream *d) {
     if (hipSetDevice(d->device) == hipSuccess) {
         if (d->st) hipStreamSynchronize(d->st);
         dstream_free_device(d);
-        if (d->st) hipStreamDestroy(d->st);
+        if (d->own_st) hipStreamDestroy(d->st);
     }
     delete d;
 }
@@ -1880,8 +1801,7 @@ static size_t dstream_win_cap(int band_rows, int w) {
 // The workspace of a header that has just been parsed (or of a checkpoint): depends on band_rows and w, never on h.
 static bool dstream_setup(nblic_amd_dstream *d) {
     const DecodeItem &it = d->it;
-    d->band_rows = d->band_rows_req > 0 ? std::min(d->band_rows_req, it.h)
-                                        : std::min(it.h, std::max(1, int((long(1) << 22) / (it.kind ? 1 : (it.effort == 3 ? 8 : (it.effort == 2 ? 4 : 1))) / it.w)));
+    d->band_rows = serial_rows_per_launch(it.h, it.w, it.kind ? 1 : it.effort, d->band_rows_req);
     d->stats_bytes = stats_doubles(it.kind ? 0 : it.effort, it.w) * sizeof(double);
     d->win_cap = dstream_win_cap(d->band_rows, it.w);
     const size_t rows_bytes = size_t(d->band_rows + 2) * size_t(it.w);
@@ -1913,11 +1833,7 @@ static void dstream_try_header(nblic_amd_dstream *d) {
     SerialState H{};
     if (it.kind == 1) {
         d->qtab.assign(kQTab, 0);
-        uint32_t *freq = reinterpret_cast<uint32_t *>(d->qtab.data()), *start = freq + 12 * 256;
-        int hh = 0, ww = 0;
-        std::vector<uint16_t> words(n / 2);
-        memcpy(words.data(), p, words.size() * 2);
-        const long pos = q_decode_tables(words.data(), words.size(), &hh, &ww, freq, start, nullptr);
+        const long pos = q_parse_tables(p, n, d->qtab.data());
         if (pos < 0) {                                                   // the tables may simply not be in hand yet (at most 12 x 256 codes)
             if (d->complete || n >= 65536) d->refused = true;
             return;
@@ -1969,7 +1885,7 @@ static int dstream_run(nblic_amd_dstream *d, double budget_s, unsigned char *row
     const size_t w = size_t(it.w);
     first = end = d->H.next_row;
     auto fail = [&](const char *what) { fprintf(stderr, "[nblic_amd] band decoder: %s\n", what); d->failed = true; hipStreamSynchronize(d->st); return report(-1); };
-    if (!rows_out || cap < size_t(d->band_rows) * w) return report(-1);          // rows_out holds less than one band (nothing has happened)
+    if (!rows_out || cap < size_t(std::min(d->band_rows, it.h - first)) * w) return report(-1);    // rows_out holds less than the next band (nothing has happened)
     const auto t0 = std::chrono::steady_clock::now();
     size_t written = 0;                                                  // rows in rows_out
     while (d->H.next_row < it.h) {
@@ -2074,11 +1990,15 @@ static size_t dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap) {
     return need;
 }
 
-static nblic_amd_dstream *dstream_new(nblic_amd_ctx *c, int band_rows) {
+// st: a stream the caller keeps for the object's lifetime; nullptr: one of its own
+static nblic_amd_dstream *dstream_new(nblic_amd_ctx *c, int band_rows, hipStream_t st = nullptr) {
     if (!c || hipSetDevice(c->device) != hipSuccess) return nullptr;
     auto *d = new nblic_amd_dstream;
-    d->c = c; d->device = c->device; d->band_rows_req = band_rows;
-    if (hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking) != hipSuccess) { d->st = nullptr; dstream_free(d); return nullptr; }
+    d->c = c; d->device = c->device; d->band_rows_req = band_rows; d->st = st;
+    if (!st) {
+        if (hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking) != hipSuccess) { d->st = nullptr; dstream_free(d); return nullptr; }
+        d->own_st = true;
+    }
     return d;
 }
 
@@ -2109,6 +2029,40 @@ static nblic_amd_dstream *dstream_resume(nblic_amd_ctx *c, const void *ck, size_
     d->pend_off = d->win_off = H.feed_from; d->win_len = 0;
     d->have_head = true;
     return d;
+}
+
+// The drop-in decoders (see safe_copy): ONE stream that starts at p, through a band decoder, rows straight into img;
+// *ph .. *peffort receive the header fields.  0 / -1.  The caller holds c->api, so the decoder may run on dec_stream
+// (a stream of its own costs about 3 ms per call to create and destroy).
+static int decode_dropin(nblic_amd_ctx *c, const unsigned char *p, bool qnblic, unsigned char *img, int *ph, int *pw, int *pnear, int *peffort) {
+    c->fed_bytes = 0;
+    nblic_amd_dstream *d = dstream_new(c, c->serial_rows, c->dec_stream);
+    if (!d) return -1;
+    const size_t step = std::max(size_t(4096), c->feed_chunk);
+    int rc = 2;
+    while (rc == 2 && !d->complete) {                                    // the next step only when the decoder asks for it
+        const size_t have = d->pend.size();
+        d->pend.resize(have + step);
+        const size_t got = safe_copy(c, d->pend.data() + have, p + c->fed_bytes, step);
+        d->pend.resize(have + got);
+        d->complete = got < step;                                        // the caller's memory ends here
+        c->fed_bytes += long(got);
+        const bool had_head = d->have_head;
+        dstream_try_header(d);
+        if (d->refused || d->failed) break;
+        if (!d->have_head) continue;
+        const DecodeItem &it = d->it;
+        if (!had_head) {
+            if ((it.kind == 1) != qnblic) break;                         // before any launch: cli.cpp tries QNBLICdecompress on every file first
+            *ph = it.h; *pw = it.w;
+            if (pnear) *pnear = it.near;
+            if (peffort) *peffort = it.effort;
+        }
+        const size_t r0 = size_t(d->H.next_row), w = size_t(it.w);
+        rc = dstream_run(d, 0.0, img + r0 * w, (size_t(it.h) - r0) * w, nullptr, nullptr);
+    }
+    dstream_free(d);
+    return rc == 1 ? 0 : -1;
 }
 
 // ---- default context behind the drop-in entry points ---------------------------------------
@@ -2527,7 +2481,7 @@ int NBLICdecompress(int verbose, unsigned char *p_buf, unsigned char *p_img, int
     nblic_amd_ctx *c = default_ctx();
     if (!c) return -1;
     std::lock_guard<std::mutex> g(c->api);
-    return decode_fed(c, p_buf, false, p_img, p_height, p_width, p_near, p_effort);          // NBLIC.c:698-712, :924-926
+    return decode_dropin(c, p_buf, false, p_img, p_height, p_width, p_near, p_effort);          // NBLIC.c:698-712, :924-926
 }
 
 int nblic_amd_qencode_batch(nblic_amd_ctx *c, int n_images, const unsigned char *const *imgs, int imgs_on_device,
@@ -2553,7 +2507,7 @@ int QNBLICdecompress(uint16_t *p_buf, unsigned char *p_img, int *p_height, int *
     nblic_amd_ctx *c = default_ctx();
     if (!c) return -1;
     std::lock_guard<std::mutex> g(c->api);
-    return decode_fed(c, reinterpret_cast<const unsigned char *>(p_buf), true, p_img, p_height, p_width, nullptr, nullptr);   // QNBLIC.c:475-555
+    return decode_dropin(c, reinterpret_cast<const unsigned char *>(p_buf), true, p_img, p_height, p_width, nullptr, nullptr);   // QNBLIC.c:475-555
 }
 int QNBLICcompressMultiThread(uint16_t *p_buf, unsigned char *p_img, int height, int width) {
     return QNBLICcompress(p_buf, p_img, height, width);                      // QNBLIC.c:872-883: same stream either way

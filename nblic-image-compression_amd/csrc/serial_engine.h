@@ -48,8 +48,8 @@ enum : int { kRunning = 0, kDone = 1, kFailed = -1, kStarved = 2, kStarvedMidRow
 // starve_margin(w) bytes were left -- feed more, set status back to kRunning, launch again.  kStarvedMidRow: it ran dry
 // inside a row although the margin was there (a row that costs more than four bytes per pixel: never seen, possible
 // for a damaged stream); the record is then NOT resumable as it stands: the lean decoder has changed the hit counts in
-// it and every decoder has changed B in place.  decode_fed decodes the image again with the whole stream; the band
-// decoder (pipeline.hip, nblic_amd_dstream) never launches the lean one and restores B from a copy taken before the launch.
+// it and every decoder has changed B in place.  The band decoder (pipeline.hip, nblic_amd_dstream; the drop-in decoders
+// run it too) never launches the lean one and restores B from a copy taken before the launch.
 constexpr size_t starve_margin(int w) { return size_t(4) * size_t(w) + 1024; }
 constexpr size_t kModelStateBytes = sizeof(SerialState) + 2048 * sizeof(int);
 constexpr size_t kDecodeStateBytes = sizeof(SerialState) + (2048 + 4096 + 512 * 20) * sizeof(int) + 2 * 512 * 20;

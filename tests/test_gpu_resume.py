@@ -120,6 +120,42 @@ def test_dropin_decoder_at_the_very_end_of_a_mapping(gpu_ctx, pkg, oracle):
         mm.close()
 
 
+def test_dropin_decoders_refuse_the_other_codec_before_any_launch(gpu_ctx, pkg, oracle):
+    """A CLI tries QNBLICdecompress on every file first and falls through to NBLICdecompress on -1: each drop-in
+    decoder refuses the other codec's stream from its header, and nothing is launched."""
+    img = inputs.syn1(40, 37, 3)
+    s, q = oracle.encode(img, 2, 2)[0], oracle.qencode(img)
+    launches = pkg.default_serial_launches()
+    assert pkg.qdecompress(s) is None
+    assert pkg.decompress(q) is None
+    assert pkg.default_serial_launches() == launches
+
+
+def test_dropin_decoders_end_on_a_short_band(gpu_ctx, pkg, oracle):
+    """Three rows per launch (nblic_amd_set_serial_rows): the drop-in decoders write the rows straight into the
+    caller's plane, so an image whose height is no multiple of three ends on a short band that must still fit."""
+    modes = [(0, 2), (0, 3), (1, 1), (2, 2), (9, 1), (3, 3), (2, 1), (5, 2)]
+    shapes = [(17, 13), (40, 37), (9, 130)]
+    pkg.set_default_serial_rows(3)
+    try:
+        for k, (near, effort) in enumerate(modes):
+            h, w = shapes[k % 3]
+            img = inputs.syn1(h, w, k + 2) if k % 2 else inputs.make("noise", h, w)
+            s = oracle.encode(img, near, effort)[0]
+            launches = pkg.default_serial_launches()
+            d = pkg.decompress(s)
+            assert d is not None and np.array_equal(d[0], oracle.decode(s)[0]) and d[1:] == (near, effort), (h, w, near, effort)
+            assert pkg.default_serial_launches() - launches >= -(-h // 3), (h, w, near, effort)
+        for k, (h, w) in enumerate(shapes):
+            img = inputs.syn1(h, w, k + 20)
+            launches = pkg.default_serial_launches()
+            dq = pkg.qdecompress(oracle.qencode(img))
+            assert dq is not None and np.array_equal(dq, img), (h, w)
+            assert pkg.default_serial_launches() - launches >= -(-h // 3), (h, w)
+    finally:
+        pkg.set_default_serial_rows(0)
+
+
 def test_damaged_streams_fail_fast_and_never_fault(gpu_ctx, pkg, oracle):
     """(advisor, round 2) A QNBLIC stream whose histogram tables do not parse (it ends inside them) must never reach
     the GPU; four megabytes of nonsense behind a QNBLIC header parse as SOME tables and may decode to anything, but
