@@ -191,6 +191,14 @@ size_t nblic_amd_stream_checkpoint(nblic_amd_stream *s, void *buf, size_t cap);
 int nblic_amd_stream_progress(nblic_amd_stream *s, int *rows_done, unsigned long long *bytes_total, unsigned char sha256[32], double *model_ms);
 int nblic_amd_stream_recon(nblic_amd_stream *s, unsigned char *plane, int *first_row, int *end_row);
 void nblic_amd_stream_end(nblic_amd_stream *s);
+/* The band encoder's SEEK INDEX (nblic_amd_index_* below), at no extra decode: _set_index, before the first _run, asks
+ * for an entry in front of every row every_rows, 2 every_rows, ... (1 <= every_rows < height; 0 / -1); bands are then
+ * cut short at those rows, which never shows in the stream.  _index, after the image is finished, writes the index
+ * into buf (cap bytes) and returns its size (buf == NULL or cap too small: only the size); it is byte-identical to
+ * nblic_amd_index_build(every_rows) of the same stream.  0 for an object that was resumed from a checkpoint or never
+ * asked for an index. */
+int nblic_amd_stream_set_index(nblic_amd_stream *s, int every_rows);
+size_t nblic_amd_stream_index(nblic_amd_stream *s, void *buf, size_t cap);
 
 /* ONE stream DECODED in ROW BANDS (src/NBLIC.c:807-898 is a single pass over the rows): the caller feeds the stream in
  * pieces of any size as it arrives and takes the rows as they are finished; the device workspace depends on band_rows
@@ -230,6 +238,39 @@ int nblic_amd_dstream_progress(nblic_amd_dstream *d, int *rows_done, unsigned lo
                                size_t *device_bytes);
 size_t nblic_amd_dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap);
 void nblic_amd_dstream_end(nblic_amd_dstream *d);
+
+/* SEEK INDEX: band-decoder checkpoints (the _checkpoint format above, band_rows = R) taken in front of every row R, 2R, ...
+ * below the height, kept NEXT TO the stream -- the stream's bytes do not change, and an index can be made for any stream,
+ * the reference's included.  Each entry is an entry point: the rows below it decode without the rows above.  So one image
+ * decodes as (h - 1) / R + 1 segments side by side, one wave each, and any row range decodes from the entry at or above it.
+ * An index is bound to one stream (its length and SHA-256) and checksummed as a whole and entry by entry.
+ * SIZE: a 96-byte head, 32 bytes of checksum, and per entry 8 + 200 bytes (length, checkpoint head, its checksum) + a body of:
+ *   NBLIC      the decoder record (86,080 bytes) + 2 x width (the rows above the entry), + 512 x width (-e2) / 1024 x width
+ *              (-e3) bytes of least-squares statistics.  At -e2 / -e3 an index is large unless R is large: a 16384 x 16384
+ *              -e3 image at R = 1024 has 15 entries of 16.9 MB, 254 MB in all.
+ *   QNBLIC     the record (12,352 bytes) + 2 x width + the 24,576 bytes of frequency tables.
+ *   _check          every field of the index and of each entry (nblic_amd_dstream_check), the entries' rows R, 2R, ... and
+ *                   their geometry against the head; with stream != NULL also that it is the stream the index was made for.
+ *                   Host only (no device is touched): 0 valid, -1 refused.  The decoders below run it before any launch.
+ *   _build          the index of `stream` (one serial band-decoder pass over the whole image, which must decode) into out
+ *                   (cap bytes); returns its size.  With out == NULL or cap too small it only returns the size needed
+ *                   (ctx may then be NULL).  -1:
+ *                   not a stream this library decodes, every_rows < 1 or every_rows >= height, or the stream does not decode.
+ *   decode_indexed  the whole plane into img (img_cap >= height x width) from the whole stream and its index, every segment
+ *                   side by side.  Each segment's final state, statistics and last two rows are compared with the next
+ *                   entry: any difference refuses the result (-1, img zeroed: no unverified pixel is left there).  0 on
+ *                   success.  Segments run in rounds of at most 1 GiB of per-segment state;
+ *                   nblic_amd_set_index_round(ctx, n > 0) caps a round at n segments (0: the memory bound alone).
+ *   decode_rows     rows [row0, row1) alone into out (cap >= (row1 - row0) x width), from the last entry at or above row0;
+ *                   nothing else is written.  0 / -1.
+ * Each call has a HIP stream and a workspace of its own, so it can run next to batches and band coders of its context. */
+void nblic_amd_set_index_round(nblic_amd_ctx *ctx, int segments);
+int nblic_amd_index_check(nblic_amd_ctx *ctx, const void *index, size_t index_bytes, const unsigned char *stream, size_t stream_bytes);
+long nblic_amd_index_build(nblic_amd_ctx *ctx, const unsigned char *stream, size_t stream_bytes, int every_rows, unsigned char *out, size_t cap);
+int nblic_amd_decode_indexed(nblic_amd_ctx *ctx, const unsigned char *stream, size_t stream_bytes, const void *index, size_t index_bytes,
+                             unsigned char *img, size_t img_cap);
+int nblic_amd_decode_rows(nblic_amd_ctx *ctx, const unsigned char *stream, size_t stream_bytes, const void *index, size_t index_bytes,
+                          int row0, int row1, unsigned char *out, size_t cap);
 
 /* The reference's decoders take no stream length (src/NBLIC.h:72, src/QNBLIC.h:16).  NBLICdecompress / QNBLICdecompress
  * therefore run a band decoder (nblic_amd_dstream above, band_rows as set by nblic_amd_set_serial_rows) and fetch the

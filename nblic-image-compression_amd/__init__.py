@@ -43,6 +43,8 @@ EXPORTS = (
     "nblic_amd_stream_recon", "nblic_amd_stream_end",
     "nblic_amd_dstream_begin", "nblic_amd_dstream_resume", "nblic_amd_dstream_check", "nblic_amd_dstream_feed", "nblic_amd_dstream_info",
     "nblic_amd_dstream_run", "nblic_amd_dstream_progress", "nblic_amd_dstream_checkpoint", "nblic_amd_dstream_end",
+    "nblic_amd_index_check", "nblic_amd_index_build", "nblic_amd_decode_indexed", "nblic_amd_decode_rows",
+    "nblic_amd_stream_set_index", "nblic_amd_stream_index", "nblic_amd_set_index_round",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -160,6 +162,20 @@ def load_library() -> C.CDLL:
     lib.nblic_amd_dstream_checkpoint.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.nblic_amd_dstream_end.restype = None
     lib.nblic_amd_dstream_end.argtypes = [C.c_void_p]
+    lib.nblic_amd_stream_set_index.restype = C.c_int
+    lib.nblic_amd_stream_set_index.argtypes = [C.c_void_p, C.c_int]
+    lib.nblic_amd_stream_index.restype = C.c_size_t
+    lib.nblic_amd_stream_index.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.nblic_amd_set_index_round.restype = None
+    lib.nblic_amd_set_index_round.argtypes = [C.c_void_p, C.c_int]
+    lib.nblic_amd_index_check.restype = C.c_int
+    lib.nblic_amd_index_check.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    lib.nblic_amd_index_build.restype = C.c_long
+    lib.nblic_amd_index_build.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]
+    lib.nblic_amd_decode_indexed.restype = C.c_int
+    lib.nblic_amd_decode_indexed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    lib.nblic_amd_decode_rows.restype = C.c_int
+    lib.nblic_amd_decode_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     lib.nblic_amd_enable_timing.restype = None
     lib.nblic_amd_enable_timing.argtypes = [C.c_void_p, C.c_int]
     lib.nblic_amd_stage_times.restype = C.c_int
@@ -468,9 +484,11 @@ class Context:
     def set_max_pixels(self, n: int):
         self.lib.nblic_amd_set_max_pixels(self.handle, n)
 
-    def stream(self, img: np.ndarray, near: int, effort: int, band_rows: int = 0, checkpoint: Optional[bytes] = None) -> "BandStream":
-        """One image in row bands (``nblic_amd_stream_*``): bounded workspace, suspend / resume through checkpoints."""
-        return BandStream(self, img, near, effort, band_rows, checkpoint)
+    def stream(self, img: np.ndarray, near: int, effort: int, band_rows: int = 0, checkpoint: Optional[bytes] = None,
+               index_every: int = 0) -> "BandStream":
+        """One image in row bands (``nblic_amd_stream_*``): bounded workspace, suspend / resume through checkpoints.
+        ``index_every`` > 0: the encoder also writes the stream's seek index (``BandStream.index()``)."""
+        return BandStream(self, img, near, effort, band_rows, checkpoint, index_every)
 
     def decoder(self, band_rows: int = 0, checkpoint: Optional[bytes] = None) -> "BandDecoder":
         """One stream decoded in row bands (``nblic_amd_dstream_*``): fed piece by piece, rows as they finish, bounded
@@ -482,6 +500,42 @@ class Context:
     def check_decoder_checkpoint(self, checkpoint: bytes) -> bool:
         """Host-side validation of a band decoder checkpoint (``nblic_amd_dstream_check``); touches no device."""
         return check_decoder_checkpoint(checkpoint, self)
+
+    def build_index(self, stream: bytes, every_rows: int) -> bytes:
+        """The seek index of ``stream`` (``nblic_amd_index_build``): a decoder checkpoint in front of every row
+        ``every_rows``, ``2 * every_rows``, ... below the height.  One serial decode of the whole stream."""
+        s = _bytes_arg(stream)
+        need = self.lib.nblic_amd_index_build(self.handle, _ptr(s), s.size, int(every_rows), None, 0)
+        if need < 0:
+            raise RuntimeError("nblic_amd_index_build: not a stream this library decodes, or every_rows outside [1, height)")
+        out = np.empty(need, np.uint8)
+        if self.lib.nblic_amd_index_build(self.handle, _ptr(s), s.size, int(every_rows), _ptr(out), out.size) != need:
+            raise RuntimeError("nblic_amd_index_build failed (the stream does not decode)")
+        return out.tobytes()
+
+    def decode_indexed(self, stream: bytes, index: bytes) -> np.ndarray:
+        """The whole plane, every segment of the index side by side (``nblic_amd_decode_indexed``); raises when the index
+        is refused or a segment does not end where the next entry starts."""
+        s, x = _bytes_arg(stream), _bytes_arg(index)
+        h, w = _checked_dims(self, s, x)
+        img = np.empty((h, w), np.uint8)
+        if self.lib.nblic_amd_decode_indexed(self.handle, _ptr(s), s.size, _ptr(x), x.size, _ptr(img), img.size) != 0:
+            raise RuntimeError("nblic_amd_decode_indexed failed (index refused, or index and stream disagree)")
+        return img
+
+    def decode_rows(self, stream: bytes, index: bytes, r0: int, r1: int) -> np.ndarray:
+        """Rows [r0, r1) of the image alone, from the last index entry at or above r0 (``nblic_amd_decode_rows``)."""
+        s, x = _bytes_arg(stream), _bytes_arg(index)
+        _, w = _checked_dims(self, s, x)
+        out = np.empty((max(int(r1) - int(r0), 0), w), np.uint8)
+        if self.lib.nblic_amd_decode_rows(self.handle, _ptr(s), s.size, _ptr(x), x.size, int(r0), int(r1), _ptr(out), out.size) != 0:
+            raise RuntimeError("nblic_amd_decode_rows failed (index refused, rows outside the image, or a damaged stream)")
+        return out
+
+    def set_index_round(self, segments: int):
+        """At most ``segments`` segments per round of ``decode_indexed`` (``nblic_amd_set_index_round``); 0 = bounded by
+        device memory alone."""
+        self.lib.nblic_amd_set_index_round(self.handle, int(segments))
 
     def set_serial_rows(self, rows: int):
         """Rows per launch of the resumable serial kernels (``nblic_amd_set_serial_rows``); 0 = automatic."""
@@ -606,7 +660,8 @@ class BandStream:
     """An encode in progress (``nblic_amd_stream``).  ``run(budget_seconds)`` returns (finished, bytes of this call);
     ``checkpoint()`` the state to hand to ``Context.stream(..., checkpoint=...)`` in another call or process."""
 
-    def __init__(self, ctx: Context, img: np.ndarray, near: int, effort: int, band_rows: int = 0, checkpoint: Optional[bytes] = None):
+    def __init__(self, ctx: Context, img: np.ndarray, near: int, effort: int, band_rows: int = 0, checkpoint: Optional[bytes] = None,
+                 index_every: int = 0):
         self.ctx, self.lib = ctx, ctx.lib
         self.img = np.ascontiguousarray(img, np.uint8)
         h, w = self.img.shape
@@ -617,6 +672,9 @@ class BandStream:
             self.handle = self.lib.nblic_amd_stream_resume(ctx.handle, C.c_void_p(self.img.ctypes.data), 0, C.c_void_p(self._ck.ctypes.data), self._ck.size)
         if not self.handle:
             raise RuntimeError("nblic_amd_stream_begin / _resume failed")
+        if index_every and self.lib.nblic_amd_stream_set_index(self.handle, int(index_every)) != 0:
+            self.close()
+            raise RuntimeError("nblic_amd_stream_set_index: every_rows outside [1, height), or a resumed encoder")
         self.out = np.empty(h * w + h * w // 8 + 65536, np.uint8)
 
     def run(self, budget_seconds: float = 0.0) -> Tuple[bool, bytes]:
@@ -637,6 +695,17 @@ class BandStream:
         buf = np.empty(need, np.uint8)
         if self.lib.nblic_amd_stream_checkpoint(self.handle, C.c_void_p(buf.ctypes.data), need) != need:
             raise RuntimeError("nblic_amd_stream_checkpoint failed")
+        return buf.tobytes()
+
+    def index(self) -> Optional[bytes]:
+        """The seek index of the finished stream (``nblic_amd_stream_index``), byte-identical to
+        ``Context.build_index(stream, index_every)``; None when this object was resumed or asked for no index."""
+        need = self.lib.nblic_amd_stream_index(self.handle, None, 0)
+        if need == 0:
+            return None
+        buf = np.empty(need, np.uint8)
+        if self.lib.nblic_amd_stream_index(self.handle, C.c_void_p(buf.ctypes.data), need) != need:
+            raise RuntimeError("nblic_amd_stream_index failed")
         return buf.tobytes()
 
     def recon(self, plane: Optional[np.ndarray] = None) -> Tuple[np.ndarray, int, int]:
@@ -670,6 +739,51 @@ def check_decoder_checkpoint(checkpoint: bytes, ctx: Optional[Context] = None) -
     buf = np.frombuffer(bytes(checkpoint), np.uint8).copy()
     handle = ctx.handle if ctx is not None else None
     return lib.nblic_amd_dstream_check(handle, C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size) == 0
+
+
+def _bytes_arg(b: bytes) -> np.ndarray:
+    """A read-only view of bytes-like data (no copy); anything else is turned into bytes first."""
+    return np.frombuffer(b if isinstance(b, (bytes, bytearray, memoryview)) else bytes(b), np.uint8)
+
+
+def _ptr(a: np.ndarray):
+    return C.c_void_p(a.ctypes.data if a.size else 0)
+
+
+INDEX_HEAD_BYTES = 96         # "NBLSIDX1", version, kind, h, w, near, k_step, effort, R, count, 12 reserved, stream length, SHA-256
+
+
+def _checked_dims(ctx, stream: np.ndarray, index: np.ndarray) -> Tuple[int, int]:
+    """(h, w) of an index that ``nblic_amd_index_check`` accepts for this stream; raises before anything is allocated."""
+    if ctx.lib.nblic_amd_index_check(ctx.handle, _ptr(index), index.size, _ptr(stream), stream.size) != 0:
+        raise RuntimeError("the seek index is refused (damaged, or not the index of this stream)")
+    h, w = np.frombuffer(index[16:24].tobytes(), "<i4")
+    return int(h), int(w)
+
+
+def check_index(index: bytes, stream: Optional[bytes] = None, ctx: Optional[Context] = None) -> bool:
+    """True when ``index`` is a valid seek index (``nblic_amd_index_check``: head, checksums, every entry) and, when
+    ``stream`` is given, the index of that stream.  Host only: needs no device."""
+    lib = load_library()
+    x = _bytes_arg(index)
+    s = _bytes_arg(stream) if stream is not None else None       # (stream=None: the index alone)
+    handle = ctx.handle if ctx is not None else None
+    return lib.nblic_amd_index_check(handle, _ptr(x), x.size, _ptr(s) if s is not None else None, s.size if s is not None else 0) == 0
+
+
+def index_entries(index: bytes) -> List[bytes]:
+    """The entries of a valid seek index: band-decoder checkpoints for ``Context.decoder(checkpoint=...)``, in row order
+    (the decoder is then fed from its ``progress()["feed_from"]`` on)."""
+    if not check_index(index):
+        raise ValueError("index_entries: not a valid seek index")
+    b = bytes(index)
+    count = int.from_bytes(b[40:44], "little")
+    at, out = INDEX_HEAD_BYTES, []
+    for _ in range(count):
+        n = int.from_bytes(b[at:at + 8], "little")
+        out.append(b[at + 8:at + 8 + n])
+        at += 8 + n
+    return out
 
 
 class BandDecoder:

@@ -287,6 +287,7 @@ struct nblic_amd_ctx {
     hipStream_t dec_stream = nullptr, dec_stream2 = nullptr;           // decode_batch alternates its chunks between the two
     uint8_t *dec_arena = nullptr; size_t dec_arena_cap = 0;
     SerialJob *dec_jobs = nullptr; int dec_jobs_cap = 0;
+    int index_round_segments = 0;         // > 0: at most this many segments per round of decode_indexed (nblic_amd_set_index_round)
     int serial_rows = 0;                  // rows per launch of the serial kernels; 0 = sized for a few seconds per launch (nblic_amd_set_serial_rows)
     long serial_launch_count = 0;         // launches of the serial model / decode kernels since the context was created (reporting, tests)
     size_t feed_chunk = size_t(1) << 20;  // bytes per step in which the drop-in decoders fetch a stream of unknown length (nblic_amd_set_feed_chunk)
@@ -1465,6 +1466,15 @@ struct nblic_amd_stream {
     bool finished = false, failed = false;
     long bands = 0;
     double model_ms = 0;
+    // seek index (nblic_amd_stream_set_index): an entry in front of every row index_every, 2 index_every, ...  An entry
+    // waits for the four stream bytes that follow its position (the decoder's window) before it is sealed.
+    int index_every = 0;
+    struct PendingEntry { std::vector<uint8_t> ck; unsigned long long at; int got; uint32_t window; };
+    std::vector<PendingEntry> pending;
+    std::vector<std::vector<uint8_t>> entries;                          // sealed, in row order
+    unsigned long long index_fed = 0;                                   // stream bytes handed to the pending entries so far
+    nblic::Sha256 rows_sha;                                             // of the reconstruction rows coded so far
+    std::vector<uint8_t> band_rows_host;
 };
 
 namespace nblic {
@@ -1518,6 +1528,9 @@ static void stream_band_jobs(nblic_amd_stream *s, Group &g, int i0, int rows, ui
     Q.h = s->h; Q.w = s->w; Q.near = s->near; Q.k_step = s->k_step; Q.effort = s->effort; Q.rows = rows; Q.out_row0 = i0;
 }
 
+static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8_t *out, const uint8_t *end, uint32_t lo, uint32_t hi);
+static void stream_index_bytes(nblic_amd_stream *s, const uint8_t *out, const uint8_t *end);
+
 // Runs bands until the image is finished or the budget is spent.  1 finished, 0 suspended between two bands, -1 error.
 static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, size_t cap, size_t *out_len) {
     *out_len = 0;
@@ -1543,7 +1556,9 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
     rc.begin(p, cap - size_t(p - out));
     rc.lo = s->lo; rc.hi = s->hi;
     while (s->next_row < s->h) {
-        const int i0 = s->next_row, rows = std::min(s->band_rows, s->h - i0);
+        int rows = std::min(s->band_rows, s->h - s->next_row);
+        const int i0 = s->next_row;
+        if (s->index_every > 0) rows = std::min(rows, s->index_every - i0 % s->index_every);     // a band never crosses an entry row
         stream_band_jobs(s, g, i0, rows, 0);
         hipEvent_t e0 = g.tm.ev[0], e1 = g.tm.ev[1];
         if (hipMemcpyAsync(g.d_jobs, g.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, g.stream) != hipSuccess ||
@@ -1573,6 +1588,7 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
         if (rc.overflow) return fail("output buffer too small");
         s->next_row = i0 + rows; s->bands++;
         { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count++; }
+        if (s->index_every > 0 && !stream_index_band(s, i0, rows, out, rc.p, rc.lo, rc.hi)) return fail("index entry");
         if (budget_s > 0 && s->next_row < s->h && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= budget_s) break;
     }
     s->lo = rc.lo; s->hi = rc.hi;
@@ -1583,6 +1599,7 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
         n = size_t(rc.p - out);
         s->finished = true;
     }
+    if (s->index_every > 0) stream_index_bytes(s, out, out + n);
     s->sha.update(out, n);
     s->bytes_total += n;
     *out_len = n;
@@ -1770,6 +1787,7 @@ struct nblic_amd_dstream {
     // progress
     nblic::SerialState H{};                              // the record's header as of the last finished launch
     int row0 = 0;                                        // image row at d_rows[0]: max(0, H.next_row - 2)
+    int stop_row = 0;                                    // > 0: _run stops in front of this row (index_build: the entry rows)
     nblic::Sha256 sha;
     long launches = 0;
 };
@@ -1888,8 +1906,9 @@ static int dstream_run(nblic_amd_dstream *d, double budget_s, unsigned char *row
     if (!rows_out || cap < size_t(std::min(d->band_rows, it.h - first)) * w) return report(-1);    // rows_out holds less than the next band (nothing has happened)
     const auto t0 = std::chrono::steady_clock::now();
     size_t written = 0;                                                  // rows in rows_out
-    while (d->H.next_row < it.h) {
-        const int i0 = d->H.next_row, rows = std::min(d->band_rows, it.h - i0);
+    const int limit = d->stop_row > 0 ? std::min(d->stop_row, it.h) : it.h;
+    while (d->H.next_row < limit) {
+        const int i0 = d->H.next_row, rows = std::min(d->band_rows, limit - i0);
         if ((written + size_t(rows)) * w > cap) return report(0);                 // rows_out is full
         if (!dstream_fill_window(d)) return fail("stream window");
         const bool final_ = d->complete && dstream_window_holds_all_fed(d);
@@ -2063,6 +2082,519 @@ static int decode_dropin(nblic_amd_ctx *c, const unsigned char *p, bool qnblic, 
     }
     dstream_free(d);
     return rc == 1 ? 0 : -1;
+}
+
+// ---- seek index: decoder checkpoints every R rows, kept next to the stream ------------------------------------------
+// A band decoder's checkpoint taken in front of row r is an ENTRY POINT: rows [r, h) decode from it alone.  An index is a
+// list of them, one in front of every row R, 2R, ... below h, bound to one stream by its length and SHA-256.  The stream
+// itself is untouched.  Layout: IndexHead | count x (uint64 length | NBLDCKPT checkpoint with band_rows = R) | SHA-256 of
+// all before it.  An entry is the decoder record (kDecodeStateBytes, ~86 KB; QNBLIC 12 KB + the 24 KB tables), B
+// (efforts 2 / 3: 512 / 1024 bytes per column) and the two rows above r.
+constexpr uint32_t kIndexVersion = 1;
+struct IndexHead {
+    char magic[8];                     // "NBLSIDX1"
+    uint32_t version;                  // kIndexVersion
+    int32_t kind, h, w, near, k_step, effort, every_rows, count;
+    uint32_t reserved[3];              // zero
+    unsigned long long stream_len;
+    uint8_t stream_sha[32];
+};
+static_assert(sizeof(IndexHead) == 96, "written and read as bytes");
+
+struct IndexView {                     // a checked index: its head and where its entries are
+    IndexHead H;
+    std::vector<const uint8_t *> ent;  // entry k + 1 (the checkpoint in front of row (k + 1) R) at ent[k]
+};
+
+static size_t index_entry_bytes(int kind, int w, int effort) { return sizeof(DecodeCheckpoint) + dstream_body_bytes(kind, w, effort) + 32; }
+
+static void sha256_of(const void *p, size_t n, uint8_t out[32]) {
+    Sha256 s;
+    s.update(static_cast<const uint8_t *>(p), n);
+    s.digest(out);
+}
+
+// A checkpoint's running row hash, written canonically: the bytes of the partial block past total % 64 are whatever
+// earlier updates left there, and which those are depends on how the rows were cut into updates.
+static Sha256 canonical_sha(Sha256 s) {
+    const size_t fill = size_t(s.total & 63);
+    memset(s.block + fill, 0, sizeof s.block - fill);
+    return s;
+}
+
+// Every field of an index, every entry (dstream_check), and -- when `stream` is given -- that it is the stream the index
+// was made for.  Host only.  0 = valid (V filled in), -1 = refused.
+static int index_check(const void *idx, size_t ilen, const void *stream, size_t slen, long max_px, IndexView &V) {
+    if (!idx || ilen < sizeof(IndexHead) + 32) return -1;
+    const uint8_t *p = static_cast<const uint8_t *>(idx);
+    IndexHead &H = V.H;
+    memcpy(&H, p, sizeof H);
+    if (memcmp(H.magic, "NBLSIDX1", 8) != 0 || H.version != kIndexVersion) return -1;
+    {
+        uint8_t d[32];
+        sha256_of(p, ilen - 32, d);
+        if (memcmp(d, p + ilen - 32, 32) != 0) return -1;
+    }
+    if (H.kind != 0 && H.kind != 1) return -1;
+    if (!size_ok(H.h, H.w, max_px) || H.reserved[0] != 0 || H.reserved[1] != 0 || H.reserved[2] != 0) return -1;
+    if (H.kind == 0 && (H.near < 0 || H.near > kMaxNear || H.k_step < kMinKStep || H.k_step > kLevels || H.effort < 1 || H.effort > 3)) return -1;
+    if (H.kind == 1 && (H.near != 0 || H.effort != 0 || H.k_step != kMinKStep)) return -1;
+    if (H.every_rows < 1 || H.every_rows >= H.h || H.count != (H.h - 1) / H.every_rows) return -1;
+    if (H.stream_len >= kMaxStreamPos) return -1;
+    V.ent.clear();
+    size_t at = sizeof H;
+    const size_t end = ilen - 32;
+    for (int k = 0; k < H.count; k++) {
+        unsigned long long n;
+        if (end - at < 8) return -1;
+        memcpy(&n, p + at, 8);
+        at += 8;
+        if (n > end - at) return -1;
+        DecodeCheckpoint C;
+        if (dstream_check(p + at, size_t(n), max_px, C) != 0) return -1;
+        if (C.kind != H.kind || C.h != H.h || C.w != H.w || C.near != H.near || C.k_step != H.k_step || C.effort != H.effort ||
+            C.band_rows != H.every_rows || C.next_row != (k + 1) * H.every_rows || C.feed_from > H.stream_len) return -1;
+        SerialState S;
+        memcpy(&S, p + at + sizeof C, sizeof S);
+        if (S.pos > H.stream_len) return -1;
+        V.ent.push_back(p + at);
+        at += size_t(n);
+    }
+    if (at != end) return -1;
+    if (stream) {
+        if (slen != H.stream_len) return -1;
+        DecodeItem it{0, 0, 0, 0, 0, 0, 0, slen, -1, -1};
+        if (!parse_stream_header(static_cast<const uint8_t *>(stream), slen, max_px, it)) return -1;
+        if (it.kind != H.kind || it.h != H.h || it.w != H.w || it.near != H.near || it.k_step != H.k_step || it.effort != H.effort) return -1;
+        uint8_t d[32];
+        sha256_of(stream, slen, d);
+        if (memcmp(d, H.stream_sha, 32) != 0) return -1;
+    }
+    return 0;
+}
+
+// One band-decoder pass with band_rows = R, a checkpoint in front of every row R, 2R, ...; the pass runs to the end of the
+// image, so a stream that does not decode gets no index.  With out == NULL or cap too small only the size (the header
+// alone is parsed; ctx may then be NULL).  -1: a stream this library does not decode, R < 1 or R >= h.
+static long index_build(nblic_amd_ctx *c, const unsigned char *stream, size_t slen, int every, unsigned char *out, size_t cap) {
+    if (!stream) return -1;
+    DecodeItem it{0, 0, 0, 0, 0, 0, 0, slen, -1, -1};
+    if (!parse_stream_header(stream, slen, c ? c->max_px : kMaxPixels, it)) return -1;
+    if (every < 1 || every >= it.h) return -1;
+    const int count = (it.h - 1) / every;
+    const size_t eb = index_entry_bytes(it.kind, it.w, it.effort);
+    const size_t need = sizeof(IndexHead) + size_t(count) * (8 + eb) + 32;
+    if (!out || cap < need) return long(need);
+    if (!c) return -1;
+    IndexHead H{};
+    memcpy(H.magic, "NBLSIDX1", 8);
+    H.version = kIndexVersion;
+    H.kind = it.kind; H.h = it.h; H.w = it.w; H.near = it.near; H.k_step = it.k_step; H.effort = it.effort;
+    H.every_rows = every; H.count = count;
+    H.stream_len = slen;
+    sha256_of(stream, slen, H.stream_sha);
+    memcpy(out, &H, sizeof H);
+    // the pass runs in bands of at most serial_rows_per_launch rows (a launch lasts seconds at most); the entries say R
+    const int band = std::min(every, serial_rows_per_launch(it.h, it.w, it.kind ? 1 : it.effort, c->serial_rows));
+    nblic_amd_dstream *d = dstream_new(c, band);
+    if (!d) return -1;
+    d->pend.assign(stream, stream + slen);
+    d->complete = true;
+    std::vector<uint8_t> rows(size_t(band) * size_t(it.w));
+    size_t at = sizeof H;
+    bool ok = true;
+    for (int k = 1; ok && k <= count + 1; k++) {
+        const int limit = k <= count ? k * every : it.h;
+        d->stop_row = limit;
+        int rc;
+        do rc = dstream_run(d, 0.0, rows.data(), rows.size(), nullptr, nullptr);
+        while (rc == 0 && d->H.next_row < limit);
+        if (k > count) { ok = rc == 1; break; }
+        ok = rc == 0 && d->H.next_row == limit;
+        if (!ok) break;
+        uint8_t *e = out + at + 8;
+        const unsigned long long n = eb;
+        memcpy(out + at, &n, 8);
+        ok = dstream_checkpoint(d, e, eb) == eb;
+        if (ok) {                                                        // R as the band height, the row hash canonical (the band encoder's index is byte-identical)
+            DecodeCheckpoint C;
+            memcpy(&C, e, sizeof C);
+            C.band_rows = every;
+            C.rows_sha = canonical_sha(C.rows_sha);
+            memcpy(e, &C, sizeof C);
+            sha256_of(e, eb - 32, e + eb - 32);
+        }
+        at += 8 + eb;
+    }
+    if (!ok) fprintf(stderr, "[nblic_amd] index: the stream does not decode\n");
+    dstream_free(d);
+    if (!ok) return -1;
+    sha256_of(out, need - 32, out + need - 32);
+    return long(need);
+}
+
+// Seals an entry: its checksum over everything before it.
+static void seal_entry(std::vector<uint8_t> &ck) { sha256_of(ck.data(), ck.size() - 32, ck.data() + ck.size() - 32); }
+
+// ---- the band ENCODER's index: the decoder's entry record, converted from the encoder's state at an entry row -------
+// The encoder carries the same adaptive state as the decoder in other layouts (kernels_e1.hip): the model record holds
+// the 2048 context biases and `bias`; cnt_state the 4096 counters as {c0, c1} pairs keyed parity | tree / 2 | node
+// (touch_of); map_state per re-mapper 60 ints: symbol -> rank, rank -> symbol, hit counts by rank (k_init_state,
+// k_mapper_chains).  The coder: the decoder's interval is the encoder's, and it has read the four bytes that follow
+// the ones emitted (NBLIC.c:527-586): pos = emitted + 4, window = those four bytes -- not written yet when the row is
+// reached, so the entry waits for them (the final flush always provides them).
+
+// The stream bytes emitted by this call so far, [out, end): what the pending entries are waiting for.
+static void stream_index_bytes(nblic_amd_stream *s, const uint8_t *out, const uint8_t *end) {
+    const unsigned long long base = s->bytes_total, stop = base + (unsigned long long)(end - out);
+    for (unsigned long long a = std::max(s->index_fed, base); a < stop; a++)
+        for (auto &e : s->pending)
+            if (a >= e.at && a < e.at + 4) { e.window = (e.window << 8) | out[a - base]; e.got++; }
+    s->index_fed = std::max(s->index_fed, stop);
+    while (!s->pending.empty() && s->pending.front().got == 4) {
+        auto &e = s->pending.front();
+        SerialState S;
+        memcpy(&S, e.ck.data() + sizeof(DecodeCheckpoint), sizeof S);
+        S.window = e.window;
+        memcpy(e.ck.data() + sizeof(DecodeCheckpoint), &S, sizeof S);
+        seal_entry(e.ck);
+        s->entries.push_back(std::move(e.ck));
+        s->pending.erase(s->pending.begin());
+    }
+}
+
+// After the band [i0, i0 + rows) has been coded: the bytes it emitted go to the pending entries, its rows into the row
+// hash, and at an entry row the entry is written down (all but its window).
+static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8_t *out, const uint8_t *end, uint32_t lo, uint32_t hi) {
+    stream_index_bytes(s, out, end);
+    const size_t w = size_t(s->w), at = size_t(i0) * w;
+    const uint8_t *plane = s->near > 0 ? s->d_recon : s->d_img;       // lossless: the reconstruction is the input
+    Group &g = s->c->groups[size_t(s->gid)];
+    Slot &sl = g.slots[0];
+    s->band_rows_host.resize(size_t(rows) * w);
+    if (hipMemcpyAsync(s->band_rows_host.data(), plane + at, size_t(rows) * w, hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+        hipStreamSynchronize(g.stream) != hipSuccess) return false;
+    s->rows_sha.update(s->band_rows_host.data(), s->band_rows_host.size());
+    const int r = i0 + rows, R = s->index_every;
+    if (r % R != 0 || r >= s->h) return true;
+    const size_t body = dstream_body_bytes(0, s->w, s->effort), b_bytes = s->stats_bytes / 2;
+    std::vector<uint8_t> ck(sizeof(DecodeCheckpoint) + body + 32, 0);
+    std::vector<uint8_t> model(kModelStateBytes);
+    std::vector<int32_t> map(512 * 60), cnt(4096 * 2);
+    uint8_t *rec = ck.data() + sizeof(DecodeCheckpoint), *b = rec + kDecodeStateBytes, *above = b + b_bytes;
+    const int r0 = r >= 2 ? r - 2 : 0, nr = r - r0;
+    bool ok = hipMemcpyAsync(model.data(), sl.d_state, kModelStateBytes, hipMemcpyDeviceToHost, g.stream) == hipSuccess &&
+              hipMemcpyAsync(map.data(), sl.b.map_state, map.size() * 4, hipMemcpyDeviceToHost, g.stream) == hipSuccess &&
+              hipMemcpyAsync(cnt.data(), sl.b.cnt_state, cnt.size() * 4, hipMemcpyDeviceToHost, g.stream) == hipSuccess &&
+              hipMemcpyAsync(above + size_t(2 - nr) * w, plane + size_t(r0) * w, size_t(nr) * w, hipMemcpyDeviceToHost, g.stream) == hipSuccess;
+    if (b_bytes) ok = ok && hipMemcpyAsync(b, s->d_stats, b_bytes, hipMemcpyDeviceToHost, g.stream) == hipSuccess;
+    if (!ok || hipStreamSynchronize(g.stream) != hipSuccess) return false;
+    SerialState M;
+    memcpy(&M, model.data(), sizeof M);
+    SerialState S{};
+    S.next_row = r; S.status = kRunning;
+    const unsigned long long emitted = s->bytes_total + (unsigned long long)(end - out);
+    S.pos = emitted + 4; S.lo = lo; S.hi = hi; S.bias = M.bias;
+    memcpy(rec, &S, sizeof S);
+    uint8_t *tab = rec + sizeof S;
+    memcpy(tab, model.data() + sizeof M, size_t(kContexts) * 4);                       // context biases
+    uint32_t *dcnt = reinterpret_cast<uint32_t *>(tab) + kContexts;                   // counters, tree-major
+    for (int key = 0; key < 4096; key++) {
+        const int tree = ((key >> 8) & 7) * 2 + (key >> 11), node = key & 255;
+        const uint32_t c = uint32_t(cnt[size_t(key) * 2]) | (uint32_t(cnt[size_t(key) * 2 + 1]) << 16);
+        memcpy(dcnt + tree * kTreeNodes + node, &c, 4);
+    }
+    int32_t *hits = reinterpret_cast<int32_t *>(tab) + kRecCount;
+    uint8_t *rank = tab + size_t(kRecRank) * 4, *sym = tab + size_t(kRecSym) * 4;
+    for (int m = 0; m < 512; m++)
+        for (int k = 0; k < kMapSyms; k++) {
+            rank[m * kMapSyms + k] = uint8_t(map[size_t(m) * 60 + k]);
+            sym[m * kMapSyms + k] = uint8_t(map[size_t(m) * 60 + 20 + k]);
+            memcpy(hits + m * kMapSyms + k, &map[size_t(m) * 60 + 40 + k], 4);
+        }
+    DecodeCheckpoint H{};
+    memcpy(H.magic, "NBLDCKPT", 8);
+    H.version = kDecodeCheckpointVersion;
+    H.kind = 0; H.h = s->h; H.w = s->w; H.near = s->near; H.k_step = s->k_step; H.effort = s->effort;
+    H.band_rows = R; H.next_row = r;
+    H.feed_from = S.pos & ~511ull;
+    H.body_bytes = body;
+    H.rows_sha = canonical_sha(s->rows_sha);
+    memcpy(ck.data(), &H, sizeof H);
+    s->pending.push_back(nblic_amd_stream::PendingEntry{std::move(ck), emitted, 0, 0u});
+    return true;
+}
+
+static int stream_set_index(nblic_amd_stream *s, int every) {
+    if (!s || s->bytes_total != 0 || s->first_row != 0 || every < 1 || every >= s->h) return -1;
+    s->index_every = every;
+    return 0;
+}
+
+// The index of a finished image whose every band this object coded; 0 otherwise.  Same layout as index_build.
+static size_t stream_index(nblic_amd_stream *s, void *buf, size_t cap) {
+    if (!s || s->index_every <= 0 || s->first_row != 0 || !s->finished || !s->pending.empty()) return 0;
+    const int count = (s->h - 1) / s->index_every;
+    if (int(s->entries.size()) != count) return 0;
+    size_t need = sizeof(IndexHead) + 32;
+    for (const auto &e : s->entries) need += 8 + e.size();
+    if (!buf || cap < need) return need;
+    IndexHead H{};
+    memcpy(H.magic, "NBLSIDX1", 8);
+    H.version = kIndexVersion;
+    H.kind = 0; H.h = s->h; H.w = s->w; H.near = s->near; H.k_step = s->k_step; H.effort = s->effort;
+    H.every_rows = s->index_every; H.count = count;
+    H.stream_len = s->bytes_total;
+    s->sha.digest(H.stream_sha);
+    uint8_t *p = static_cast<uint8_t *>(buf);
+    memcpy(p, &H, sizeof H);
+    size_t at = sizeof H;
+    for (const auto &e : s->entries) {
+        const unsigned long long n = e.size();
+        memcpy(p + at, &n, 8);
+        memcpy(p + at + 8, e.data(), e.size());
+        at += 8 + e.size();
+    }
+    sha256_of(p, need - 32, p + need - 32);
+    return need;
+}
+
+// The device side of one indexed decode call: its own HIP stream and buffers, freed on every path out.
+struct IndexedRun {
+    hipStream_t st = nullptr;
+    std::vector<void *> bufs;
+    ~IndexedRun() {
+        if (st) hipStreamSynchronize(st);
+        for (void *p : bufs) hipFree(p);
+        if (st) hipStreamDestroy(st);
+    }
+    template <class T>
+    T *alloc(size_t bytes) {
+        void *p = nullptr;
+        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return nullptr;
+        bufs.push_back(p);
+        return static_cast<T *>(p);
+    }
+};
+
+// A checked index's entry k (1-based: the entry in front of row k R), split into its parts
+struct EntryParts { const DecodeCheckpoint *head; const uint8_t *state, *b, *rows; };
+static EntryParts entry_parts(const IndexView &V, int k) {
+    const uint8_t *e = V.ent[size_t(k - 1)];
+    const size_t sb = dstream_state_bytes(V.H.kind), bb = stats_doubles(V.H.kind ? 0 : V.H.effort, V.H.w) * sizeof(double) / 2;
+    return EntryParts{reinterpret_cast<const DecodeCheckpoint *>(e), e + sizeof(DecodeCheckpoint), e + sizeof(DecodeCheckpoint) + sb,
+                      e + sizeof(DecodeCheckpoint) + sb + bb};
+}
+
+// The state record a job starts from: the stream's start (segment 0) or entry k; the whole stream is in device memory.
+static void start_record(const IndexView &V, const DecodeItem &it, int k, size_t slen, uint8_t *rec) {
+    const size_t sb = dstream_state_bytes(it.kind);
+    SerialState S{};
+    if (k > 0) {
+        memcpy(rec, entry_parts(V, k).state, sb);
+        memcpy(&S, rec, sizeof S);
+    } else {
+        memset(rec, 0, sb);
+        S.pos = it.kind ? (unsigned long long)(it.q_pos) * 2ull : (unsigned long long)(kHeaderBytes);
+    }
+    S.status = kRunning; S.avail = slen; S.final_ = 1;
+    memcpy(rec, &S, sizeof S);
+}
+
+// Parses the stream's header (QNBLIC: its tables) for an indexed decode; false: refused.
+static bool indexed_item(const unsigned char *stream, size_t slen, long max_px, DecodeItem &it, std::vector<uint8_t> &qtab) {
+    it = DecodeItem{0, 0, 0, 0, 0, 0, 0, slen, -1, -1};
+    if (!parse_stream_header(stream, slen, max_px, it)) return false;
+    if (it.kind == 0) return slen >= size_t(kHeaderBytes) + 4;
+    qtab.assign(kQTab, 0);
+    it.q_pos = q_parse_tables(stream, slen, qtab.data());
+    return it.q_pos >= 0 && size_t(it.q_pos) * 2 + 4 <= slen;
+}
+
+// Segment k of an indexed decode ends in front of entry k + 1's row; its final record, B and rows must be that entry.
+// The record's header fields and tables are compared except the rank -> symbol words (kRecRank): the lean decoder never
+// writes them back, and dstream_check has verified that the entry's are the inverse of its sym_at, which IS compared.
+static bool chain_matches(const IndexView &V, int k, const uint8_t *rec, const uint8_t *b, const uint8_t *plane) {
+    const EntryParts E = entry_parts(V, k + 1);
+    SerialState got, want;
+    memcpy(&got, rec, sizeof got); memcpy(&want, E.state, sizeof want);
+    if (got.status != kRunning || got.next_row != want.next_row || got.pos != want.pos || got.lo != want.lo || got.bias != want.bias) return false;
+    if (V.H.kind == 0 && (got.hi != want.hi || got.window != want.window)) return false;
+    const uint8_t *tg = rec + sizeof(SerialState), *tw = E.state + sizeof(SerialState);
+    const size_t tab = dstream_state_bytes(V.H.kind) - sizeof(SerialState);
+    if (V.H.kind == 0) {
+        const size_t rank0 = size_t(kRecRank) * 4, sym0 = size_t(kRecSym) * 4;
+        if (memcmp(tg, tw, rank0) != 0 || memcmp(tg + sym0, tw + sym0, tab - sym0) != 0) return false;
+    } else if (memcmp(tg, tw, tab) != 0) {
+        return false;
+    }
+    const size_t bb = stats_doubles(V.H.kind ? 0 : V.H.effort, V.H.w) * sizeof(double) / 2;
+    if (bb && memcmp(b, E.b, bb) != 0) return false;
+    const size_t w = size_t(V.H.w);
+    const int r = want.next_row, nr = r >= 2 ? 2 : r;
+    return memcmp(plane + size_t(r - nr) * w, E.rows + size_t(2 - nr) * w, size_t(nr) * w) == 0;
+}
+
+constexpr size_t kIndexedRoundBytes = size_t(1) << 30;   // device memory of one round's per-segment records and statistics
+
+// Every segment of the image side by side, one wave each (serial_decode_launch with whole streams: more segments than
+// CUs take the lean image), in rounds that bound the per-segment memory; the plane is copied out once, then the chain
+// check (chain_matches) refuses the result on any difference.  0 / -1.
+static int decode_indexed(nblic_amd_ctx *c, const unsigned char *stream, size_t slen, const void *idx, size_t ilen, unsigned char *img, size_t img_cap) {
+    if (!c || !stream || !img) return -1;
+    IndexView V;
+    if (index_check(idx, ilen, stream, slen, c->max_px, V) != 0) return -1;
+    DecodeItem it;
+    std::vector<uint8_t> qtab;
+    if (!indexed_item(stream, slen, c->max_px, it, qtab)) return -1;
+    const size_t w = size_t(it.w), plane_bytes = size_t(it.h) * w;
+    if (img_cap < plane_bytes) return -1;
+    if (hipSetDevice(c->device) != hipSuccess) return -1;
+    const int R = V.H.every_rows, nseg = V.H.count + 1;
+    const size_t sb = dstream_state_bytes(it.kind), rec_bytes = up256(sb);
+    const size_t stats_bytes = stats_doubles(it.kind ? 0 : it.effort, it.w) * sizeof(double), bb = stats_bytes / 2;
+    const size_t per_seg = rec_bytes + up256(stats_bytes);
+    int per_round = int(std::max<size_t>(1, std::min<size_t>(size_t(nseg), kIndexedRoundBytes / per_seg)));
+    if (c->index_round_segments > 0) per_round = std::min(per_round, c->index_round_segments);
+    IndexedRun run;
+    if (hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking) != hipSuccess) { run.st = nullptr; return -1; }
+    uint8_t *d_stream = run.alloc<uint8_t>(up256(slen + 2048)), *d_plane = run.alloc<uint8_t>(plane_bytes);
+    uint8_t *d_recs = run.alloc<uint8_t>(size_t(per_round) * per_seg);
+    SerialJob *d_jobs = run.alloc<SerialJob>(size_t(per_round) * sizeof(SerialJob));
+    uint8_t *d_tab = it.kind ? run.alloc<uint8_t>(kQTab) : nullptr;
+    auto fail = [&](const char *what) { fprintf(stderr, "[nblic_amd] indexed decode: %s\n", what); return -1; };
+    if (!d_stream || !d_plane || !d_recs || !d_jobs || (it.kind && !d_tab)) return fail("cannot allocate the workspace");
+    const hipStream_t st = run.st;
+    bool ok = hipMemsetAsync(d_stream + (slen & ~size_t(3)), 0, up256(slen + 2048) - (slen & ~size_t(3)), st) == hipSuccess &&
+              hipMemcpyAsync(d_stream, stream, slen, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (it.kind) ok = ok && hipMemcpyAsync(d_tab, qtab.data(), kQTab, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (!ok) return fail("upload");
+    const int rows_per_launch = serial_rows_per_launch(it.h, it.w, it.kind ? 1 : it.effort, c->serial_rows);
+    std::vector<uint8_t> host_recs(size_t(nseg) * sb), host_b(size_t(nseg) * bb), starts(size_t(per_round) * sb);
+    std::vector<SerialJob> jobs(static_cast<size_t>(per_round));
+    long launches_total = 0;
+    // rounds from the last segments to the first: the rows above a segment (from its entry) are written into the plane
+    // before the segment that owns them decodes, so every row of the plane ends as its own segment decoded it
+    for (int s1 = nseg; s1 > 0;) {
+        const int s0 = std::max(0, s1 - per_round), n = s1 - s0;
+        int launches = 1;
+        for (int k = s0; k < s1; k++) {
+            const int j = k - s0, r0 = k * R, r1 = k + 1 < nseg ? (k + 1) * R : it.h;
+            uint8_t *rec = d_recs + size_t(j) * per_seg;
+            SerialJob &J = jobs[size_t(j)];
+            J = SerialJob{};
+            J.recon = d_plane; J.recon_row0 = 0;
+            J.stream = d_stream; J.stream_off = 0;
+            J.state = reinterpret_cast<SerialState *>(rec);
+            J.stats = stats_bytes ? reinterpret_cast<double *>(rec + rec_bytes) : nullptr;
+            J.h = it.h; J.w = it.w; J.near = it.near; J.k_step = it.k_step; J.effort = it.effort;
+            J.rows = rows_per_launch; J.end_row = r1 < it.h ? r1 : 0;
+            if (it.kind) { J.q_freq = reinterpret_cast<const uint32_t *>(d_tab); J.q_start = J.q_freq + 12 * 256; J.q_slot = nullptr; }
+            launches = std::max(launches, serial_launches(r1 - r0, rows_per_launch));
+            start_record(V, it, k, slen, starts.data() + size_t(j) * sb);
+            ok = hipMemcpyAsync(rec, starts.data() + size_t(j) * sb, sb, hipMemcpyHostToDevice, st) == hipSuccess;
+            if (stats_bytes) ok = ok && hipMemsetAsync(J.stats, 0, stats_bytes, st) == hipSuccess;
+            if (k > 0) {
+                const EntryParts E = entry_parts(V, k);
+                const int nr = r0 >= 2 ? 2 : r0;
+                if (bb) ok = ok && hipMemcpyAsync(J.stats, E.b, bb, hipMemcpyHostToDevice, st) == hipSuccess;
+                ok = ok && hipMemcpyAsync(d_plane + size_t(r0 - nr) * w, E.rows + size_t(2 - nr) * w, size_t(nr) * w, hipMemcpyHostToDevice, st) == hipSuccess;
+            }
+            if (!ok) return fail("upload");
+        }
+        if (hipMemcpyAsync(d_jobs, jobs.data(), size_t(n) * sizeof(SerialJob), hipMemcpyHostToDevice, st) != hipSuccess) return fail("upload");
+        for (int l = 0; l < launches; l++)
+            if (!decode_launch(it, d_jobs, jobs.data(), n, st, true)) return fail("launch");
+        launches_total += launches;
+        for (int k = s0; k < s1; k++) {
+            const uint8_t *rec = d_recs + size_t(k - s0) * per_seg;
+            ok = hipMemcpyAsync(host_recs.data() + size_t(k) * sb, rec, sb, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (bb) ok = ok && hipMemcpyAsync(host_b.data() + size_t(k) * bb, rec + rec_bytes, bb, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (!ok) return fail("state");
+        }
+        if (hipStreamSynchronize(st) != hipSuccess) return fail("a round");       // `starts` and `jobs` are reused by the next round
+        s1 = s0;
+    }
+    { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count += launches_total; }
+    if (hipMemcpyAsync(img, d_plane, plane_bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        memset(img, 0, plane_bytes);
+        return fail("plane");
+    }
+    for (int k = 0; k < nseg; k++) {
+        const uint8_t *rec = host_recs.data() + size_t(k) * sb;
+        if (k + 1 == nseg) {
+            SerialState S;
+            memcpy(&S, rec, sizeof S);
+            if (S.status != kDone) { memset(img, 0, plane_bytes); return fail("the stream is damaged or ends too early"); }
+        } else if (!chain_matches(V, k, rec, host_b.data() + size_t(k) * bb, img)) {
+            memset(img, 0, plane_bytes);                                 // nothing unverified is left in the caller's buffer
+            return fail("a segment does not end where the next entry starts (index and stream disagree)");
+        }
+    }
+    return 0;
+}
+
+// Rows [row0, row1) alone: one job from the last entry at or before row0 (the stream's start for row0 < R), fed from the
+// entry's feed_from, ending in front of row1.  Writes only out[0, (row1 - row0) w).  0 / -1.
+static int decode_rows(nblic_amd_ctx *c, const unsigned char *stream, size_t slen, const void *idx, size_t ilen, int row0, int row1,
+                       unsigned char *out, size_t cap) {
+    if (!c || !stream || !out) return -1;
+    IndexView V;
+    if (index_check(idx, ilen, stream, slen, c->max_px, V) != 0) return -1;
+    DecodeItem it;
+    std::vector<uint8_t> qtab;
+    if (!indexed_item(stream, slen, c->max_px, it, qtab)) return -1;
+    if (row0 < 0 || row1 <= row0 || row1 > it.h) return -1;
+    const size_t w = size_t(it.w);
+    if (cap < size_t(row1 - row0) * w) return -1;
+    if (hipSetDevice(c->device) != hipSuccess) return -1;
+    const int k = row0 / V.H.every_rows, r0 = k * V.H.every_rows, base = std::max(0, r0 - 2);
+    const unsigned long long off = k > 0 ? entry_parts(V, k).head->feed_from : 0;    // <= slen (index_check)
+    const size_t win = size_t(slen - off), sb = dstream_state_bytes(it.kind);
+    const size_t stats_bytes = stats_doubles(it.kind ? 0 : it.effort, it.w) * sizeof(double), bb = stats_bytes / 2;
+    IndexedRun run;
+    if (hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking) != hipSuccess) { run.st = nullptr; return -1; }
+    uint8_t *d_win = run.alloc<uint8_t>(up256(win + 2048)), *d_rows = run.alloc<uint8_t>(size_t(row1 - base) * w);
+    uint8_t *d_rec = run.alloc<uint8_t>(up256(sb));
+    double *d_stats = stats_bytes ? run.alloc<double>(stats_bytes) : nullptr;
+    SerialJob *d_job = run.alloc<SerialJob>(sizeof(SerialJob));
+    uint8_t *d_tab = it.kind ? run.alloc<uint8_t>(kQTab) : nullptr;
+    auto fail = [&](const char *what) { fprintf(stderr, "[nblic_amd] row-range decode: %s\n", what); return -1; };
+    if (!d_win || !d_rows || !d_rec || !d_job || (stats_bytes && !d_stats) || (it.kind && !d_tab)) return fail("cannot allocate the workspace");
+    const hipStream_t st = run.st;
+    std::vector<uint8_t> start(sb);
+    start_record(V, it, k, slen, start.data());
+    SerialJob J{};
+    J.recon = d_rows; J.recon_row0 = base;
+    J.stream = d_win; J.stream_off = off;
+    J.state = reinterpret_cast<SerialState *>(d_rec); J.stats = d_stats;
+    J.h = it.h; J.w = it.w; J.near = it.near; J.k_step = it.k_step; J.effort = it.effort;
+    J.rows = serial_rows_per_launch(it.h, it.w, it.kind ? 1 : it.effort, c->serial_rows);
+    J.end_row = row1 < it.h ? row1 : 0;
+    if (it.kind) { J.q_freq = reinterpret_cast<const uint32_t *>(d_tab); J.q_start = J.q_freq + 12 * 256; J.q_slot = nullptr; }
+    bool ok = hipMemsetAsync(d_win + (win & ~size_t(3)), 0, up256(win + 2048) - (win & ~size_t(3)), st) == hipSuccess &&
+              hipMemcpyAsync(d_win, stream + off, win, hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(d_rec, start.data(), sb, hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(d_job, &J, sizeof J, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (stats_bytes) ok = ok && hipMemsetAsync(d_stats, 0, stats_bytes, st) == hipSuccess;
+    if (it.kind) ok = ok && hipMemcpyAsync(d_tab, qtab.data(), kQTab, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (k > 0) {
+        const EntryParts E = entry_parts(V, k);
+        const int nr = r0 - base;
+        if (bb) ok = ok && hipMemcpyAsync(d_stats, E.b, bb, hipMemcpyHostToDevice, st) == hipSuccess;
+        ok = ok && hipMemcpyAsync(d_rows, E.rows + size_t(2 - nr) * w, size_t(nr) * w, hipMemcpyHostToDevice, st) == hipSuccess;
+    }
+    if (!ok) return fail("upload");
+    const int launches = serial_launches(row1 - r0, J.rows);
+    for (int l = 0; l < launches; l++)
+        if (!decode_launch(it, d_job, &J, 1, st, false)) return fail("launch");
+    { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count += launches; }
+    SerialState S;
+    if (hipMemcpyAsync(&S, d_rec, sizeof S, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail("state");
+    if (row1 == it.h ? S.status != kDone : (S.status != kRunning || S.next_row != row1)) return fail("the stream is damaged or ends too early");
+    if (hipMemcpyAsync(out, d_rows + size_t(row0 - base) * w, size_t(row1 - row0) * w, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) return fail("rows");
+    return 0;
 }
 
 // ---- default context behind the drop-in entry points ---------------------------------------
@@ -2386,6 +2918,8 @@ int nblic_amd_stream_recon(nblic_amd_stream *s, unsigned char *plane, int *first
     return hipMemcpy(plane + at, (s->near > 0 ? s->d_recon : s->d_img) + at, n, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 void nblic_amd_stream_end(nblic_amd_stream *s) { stream_free(s); }
+int nblic_amd_stream_set_index(nblic_amd_stream *s, int every_rows) { return stream_set_index(s, every_rows); }
+size_t nblic_amd_stream_index(nblic_amd_stream *s, void *buf, size_t cap) { return stream_index(s, buf, cap); }
 
 nblic_amd_dstream *nblic_amd_dstream_begin(nblic_amd_ctx *c, int band_rows) { return dstream_new(c, band_rows); }
 nblic_amd_dstream *nblic_amd_dstream_resume(nblic_amd_ctx *c, const void *checkpoint, size_t bytes) { return dstream_resume(c, checkpoint, bytes); }
@@ -2425,6 +2959,23 @@ int nblic_amd_dstream_progress(nblic_amd_dstream *d, int *rows_done, unsigned lo
 }
 size_t nblic_amd_dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap) { return d ? dstream_checkpoint(d, buf, cap) : 0; }
 void nblic_amd_dstream_end(nblic_amd_dstream *d) { dstream_free(d); }
+
+void nblic_amd_set_index_round(nblic_amd_ctx *c, int segments) { if (c) c->index_round_segments = segments > 0 ? segments : 0; }
+int nblic_amd_index_check(nblic_amd_ctx *c, const void *index, size_t index_bytes, const unsigned char *stream, size_t stream_bytes) {
+    IndexView V;
+    return index_check(index, index_bytes, stream, stream_bytes, c ? c->max_px : kMaxPixels, V);
+}
+long nblic_amd_index_build(nblic_amd_ctx *c, const unsigned char *stream, size_t stream_bytes, int every_rows, unsigned char *out, size_t cap) {
+    return index_build(c, stream, stream_bytes, every_rows, out, cap);
+}
+int nblic_amd_decode_indexed(nblic_amd_ctx *c, const unsigned char *stream, size_t stream_bytes, const void *index, size_t index_bytes,
+                             unsigned char *img, size_t img_cap) {
+    return decode_indexed(c, stream, stream_bytes, index, index_bytes, img, img_cap);
+}
+int nblic_amd_decode_rows(nblic_amd_ctx *c, const unsigned char *stream, size_t stream_bytes, const void *index, size_t index_bytes, int row0,
+                          int row1, unsigned char *out, size_t cap) {
+    return decode_rows(c, stream, stream_bytes, index, index_bytes, row0, row1, out, cap);
+}
 
 int nblic_amd_set_device_coder(nblic_amd_ctx *c, int n_packs, int min_outstanding) {
     if (!c || n_packs < 0 || n_packs > 64) return -1;

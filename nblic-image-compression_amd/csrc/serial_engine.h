@@ -53,6 +53,10 @@ enum : int { kRunning = 0, kDone = 1, kFailed = -1, kStarved = 2, kStarvedMidRow
 constexpr size_t starve_margin(int w) { return size_t(4) * size_t(w) + 1024; }
 constexpr size_t kModelStateBytes = sizeof(SerialState) + 2048 * sizeof(int);
 constexpr size_t kDecodeStateBytes = sizeof(SerialState) + (2048 + 4096 + 512 * 20) * sizeof(int) + 2 * 512 * 20;
+// word offsets of the decoder record's tables after SerialState: context biases and counters, then the re-mappers' hit
+// counts (kRecCount), symbol -> rank (kRecRank) and rank -> symbol (kRecSym) bytes.  The lean decoder keeps the hit
+// counts there and never writes the symbol -> rank bytes back (serial_engine.hip DecodeLdsLean).
+constexpr int kRecCount = 2048 + 4096, kRecRank = kRecCount + 512 * 20, kRecSym = kRecRank + 512 * 20 / 4;
 constexpr size_t kQDecodeStateBytes = sizeof(SerialState) + 3072 * sizeof(int);
 
 // One image of a serial launch (array in device memory, job = blockIdx.x).
@@ -69,6 +73,8 @@ struct SerialJob {
     int out_row0;              // encode: the row whose records sit at index 0 of rec1 / pxs (0, or the first row of the band they hold)
     int recon_row0;            // decode: the image row stored at index 0 of recon (0: the whole plane; a band decoder: the first row it holds)
     unsigned long long stream_off;   // decode: absolute stream offset of byte 0 of `stream` (a multiple of 512; SerialState::pos / avail stay absolute)
+    int end_row;               // decode: the job stops in front of this row (0: h).  Reaching end_row < h leaves the record as a band
+                               // boundary leaves it (tables written back, status kRunning, next_row == end_row); further launches return at once
     // QNBLIC decode only
     const uint32_t *q_freq, *q_start; const uint8_t *q_slot;      // 12 x 256 frequencies and cumulative starts; q_slot: unused (the kernel searches q_start)
 };

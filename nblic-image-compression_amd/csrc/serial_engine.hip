@@ -158,8 +158,9 @@ struct DecodeLdsLean {
     LsqLds q;
 };
 static_assert(sizeof(DecodeLdsLean) <= 38 * 1024, "four lean decoder images (+ their row rings) per 160 KB of LDS");
-constexpr int kRecCount = kContexts + kLevels * kTreeNodes;              // word offsets of the tables in the state record (after SerialState)
-constexpr int kRecRank = kRecCount + 512 * kMapSyms, kRecSym = kRecRank + 512 * kMapSyms / 4;
+static_assert(kRecCount == kContexts + kLevels * kTreeNodes && kRecRank == kRecCount + 512 * kMapSyms && kRecSym == kRecRank + 512 * kMapSyms / 4 &&
+              offsetof(DecodeLds, count) == size_t(kRecCount) * 4 && offsetof(DecodeLds, rank_of) == size_t(kRecRank) * 4 &&
+              offsetof(DecodeLds, sym_at) == size_t(kRecSym) * 4, "serial_engine.h: the decoder record's table offsets");
 
 // activity -> (qu, qv, qw) (model.h quantise) as a table: the interpolation divides by a level gap
 __device__ void fill_qlut(uint16_t *qlut) {
@@ -1086,7 +1087,9 @@ __global__ void __launch_bounds__(64) k_serial_decode(const SerialJob *__restric
         }
     };
     if (st->status != kRunning) return;                                  // finished, failed, or waiting for the host to feed the stream
-    const int i0 = st->next_row, i1 = i0 + J.rows < J.h ? i0 + J.rows : J.h;
+    const int end = J.end_row > 0 && J.end_row < J.h ? J.end_row : J.h;     // a segment of an indexed decode ends in front of end_row
+    const int i0 = st->next_row, i1 = i0 + J.rows < end ? i0 + J.rows : end;
+    if (i0 >= end) return;                                               // the segment is complete: its record stays as it is
     const bool final_ = st->final_ != 0;
     const size_t avail = size_t(st->avail);
     if (!final_ && avail < size_t(kHeaderBytes) + 4 + starve_margin(J.w) && i0 == 0) {       // not even the start of the stream is there yet
@@ -1329,7 +1332,9 @@ __global__ void __launch_bounds__(64) k_serial_qdecode(const SerialJob *__restri
     const auto st_ctx = gp(reinterpret_cast<int *>(J.state + 1));
     const int lane = int(threadIdx.x), w = J.w, h = J.h;
     if (st->status != kRunning) return;
-    const int i0 = st->next_row, i1 = i0 + J.rows < h ? i0 + J.rows : h;
+    const int end = J.end_row > 0 && J.end_row < h ? J.end_row : h;       // see k_serial_decode
+    const int i0 = st->next_row, i1 = i0 + J.rows < end ? i0 + J.rows : end;
+    if (i0 >= end) return;
     const bool final_ = st->final_ != 0;
     const size_t avail = size_t(st->avail) & ~size_t(1), row_need = size_t(2) * size_t(w) + 8;
     if (!final_ && (avail < size_t(st->pos) || avail - size_t(st->pos) < row_need)) { if (lane == 0) st->status = kStarved; return; }
