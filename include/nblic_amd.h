@@ -177,7 +177,14 @@ long nblic_amd_serial_launches(nblic_amd_ctx *ctx);
  *             in *out_len: concatenate the pieces of successive calls.
  *   _progress rows finished, bytes emitted so far, their SHA-256, milliseconds spent in the model kernel; returns 1 / 0 / -1.
  *   _checkpoint  writes the checkpoint into buf (cap bytes) and returns its size; with buf == NULL or cap too small it
- *             only returns the size needed.  Valid between two _run calls.
+ *             only returns the size needed; 0 before the first _run, after the image is finished or after a failure.
+ *             Valid between two _run calls.
+ *   _resume   a checkpoint of _checkpoint; every field is checked (magic, format version, checksum over the whole body,
+ *             sizes against the geometry and mode, the header fields, the state and its tables) before anything is
+ *             allocated or reaches the device: NULL if any is off.  A damaged checkpoint is refused, and so is one
+ *             written by an earlier build ("NBLCKPT1").  img must be the plane the checkpoint was taken from.
+ *   _check    the same checks alone, on the host (no device is touched; ctx may be NULL, it only supplies the pixel
+ *             limit): 0 valid, -1 refused.
  *   _recon    the reconstruction the reference leaves in p_img (NBLIC.c:876), as far as THIS object has produced it:
  *             rows [*first_row, *end_row) are written at their place in `plane` (a whole h x w plane); an object resumed
  *             from a checkpoint starts at the checkpoint's row, the rows before it came out of the earlier objects.   */
@@ -188,6 +195,7 @@ nblic_amd_stream *nblic_amd_stream_resume(nblic_amd_ctx *ctx, const unsigned cha
                                           size_t checkpoint_bytes);
 int nblic_amd_stream_run(nblic_amd_stream *s, double budget_seconds, unsigned char *out, size_t out_cap, size_t *out_len);
 size_t nblic_amd_stream_checkpoint(nblic_amd_stream *s, void *buf, size_t cap);
+int nblic_amd_stream_check(nblic_amd_ctx *ctx, const void *checkpoint, size_t bytes);
 int nblic_amd_stream_progress(nblic_amd_stream *s, int *rows_done, unsigned long long *bytes_total, unsigned char sha256[32], double *model_ms);
 int nblic_amd_stream_recon(nblic_amd_stream *s, unsigned char *plane, int *first_row, int *end_row);
 void nblic_amd_stream_end(nblic_amd_stream *s);

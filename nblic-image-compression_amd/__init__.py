@@ -16,6 +16,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import weakref
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -40,7 +41,7 @@ EXPORTS = (
     "nblic_amd_encode_batch_modes", "nblic_amd_decode_batch", "nblic_amd_serial_selftest",
     "nblic_amd_set_serial_rows", "nblic_amd_serial_launches", "nblic_amd_set_feed_chunk", "nblic_amd_last_fed_bytes",
     "nblic_amd_stream_begin", "nblic_amd_stream_resume", "nblic_amd_stream_run", "nblic_amd_stream_checkpoint", "nblic_amd_stream_progress",
-    "nblic_amd_stream_recon", "nblic_amd_stream_end",
+    "nblic_amd_stream_recon", "nblic_amd_stream_end", "nblic_amd_stream_check",
     "nblic_amd_dstream_begin", "nblic_amd_dstream_resume", "nblic_amd_dstream_check", "nblic_amd_dstream_feed", "nblic_amd_dstream_info",
     "nblic_amd_dstream_run", "nblic_amd_dstream_progress", "nblic_amd_dstream_checkpoint", "nblic_amd_dstream_end",
     "nblic_amd_index_check", "nblic_amd_index_build", "nblic_amd_decode_indexed", "nblic_amd_decode_rows",
@@ -144,6 +145,8 @@ def load_library() -> C.CDLL:
     lib.nblic_amd_stream_recon.argtypes = [C.c_void_p, C.c_void_p, ip, ip]
     lib.nblic_amd_stream_end.restype = None
     lib.nblic_amd_stream_end.argtypes = [C.c_void_p]
+    lib.nblic_amd_stream_check.restype = C.c_int
+    lib.nblic_amd_stream_check.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.nblic_amd_dstream_begin.restype = C.c_void_p
     lib.nblic_amd_dstream_begin.argtypes = [C.c_void_p, C.c_int]
     lib.nblic_amd_dstream_resume.restype = C.c_void_p
@@ -404,12 +407,14 @@ class Context:
         if not self.handle:
             raise RuntimeError("nblic_amd_create failed: no usable HIP device (the hot path has no CPU fallback)")
         self.device, self.n_slots, self.n_coders = device, n_slots, n_coders
-        self._decoders = []                 # BandDecoders handed out: closed before the context is destroyed
+        # BandDecoders and BandStreams handed out, closed before the context is destroyed.  Weak: one the caller drops is
+        # freed at once (a BandStream holds one of the context's groups for as long as it lives).
+        self._objects = weakref.WeakSet()
 
     def close(self):
-        for d in getattr(self, "_decoders", []):
+        for d in list(getattr(self, "_objects", ())):
             d.close()
-        self._decoders = []
+        self._objects = weakref.WeakSet()
         if self.handle:
             self.lib.nblic_amd_destroy(self.handle)
             self.handle = None
@@ -487,19 +492,26 @@ class Context:
     def stream(self, img: np.ndarray, near: int, effort: int, band_rows: int = 0, checkpoint: Optional[bytes] = None,
                index_every: int = 0) -> "BandStream":
         """One image in row bands (``nblic_amd_stream_*``): bounded workspace, suspend / resume through checkpoints.
-        ``index_every`` > 0: the encoder also writes the stream's seek index (``BandStream.index()``)."""
-        return BandStream(self, img, near, effort, band_rows, checkpoint, index_every)
+        ``index_every`` > 0: the encoder also writes the stream's seek index (``BandStream.index()``).  The context
+        closes it before it is destroyed itself."""
+        s = BandStream(self, img, near, effort, band_rows, checkpoint, index_every)
+        self._objects.add(s)
+        return s
 
     def decoder(self, band_rows: int = 0, checkpoint: Optional[bytes] = None) -> "BandDecoder":
         """One stream decoded in row bands (``nblic_amd_dstream_*``): fed piece by piece, rows as they finish, bounded
         workspace, suspend / resume through checkpoints.  The context closes it before it is destroyed itself."""
         d = BandDecoder(self, band_rows, checkpoint)
-        self._decoders = [x for x in self._decoders if x.handle] + [d]
+        self._objects.add(d)
         return d
 
     def check_decoder_checkpoint(self, checkpoint: bytes) -> bool:
         """Host-side validation of a band decoder checkpoint (``nblic_amd_dstream_check``); touches no device."""
         return check_decoder_checkpoint(checkpoint, self)
+
+    def check_encoder_checkpoint(self, checkpoint: bytes) -> bool:
+        """Host-side validation of a band encoder checkpoint (``nblic_amd_stream_check``); touches no device."""
+        return check_encoder_checkpoint(checkpoint, self)
 
     def build_index(self, stream: bytes, every_rows: int) -> bytes:
         """The seek index of ``stream`` (``nblic_amd_index_build``): a decoder checkpoint in front of every row
@@ -692,6 +704,8 @@ class BandStream:
 
     def checkpoint(self) -> bytes:
         need = self.lib.nblic_amd_stream_checkpoint(self.handle, None, 0)
+        if need == 0:
+            raise RuntimeError("nblic_amd_stream_checkpoint: nothing to resume (not started, finished or failed)")
         buf = np.empty(need, np.uint8)
         if self.lib.nblic_amd_stream_checkpoint(self.handle, C.c_void_p(buf.ctypes.data), need) != need:
             raise RuntimeError("nblic_amd_stream_checkpoint failed")
@@ -735,10 +749,15 @@ NEEDS_INPUT = 2
 def check_decoder_checkpoint(checkpoint: bytes, ctx: Optional[Context] = None) -> bool:
     """True when ``checkpoint`` would be accepted by ``Context.decoder(checkpoint=...)`` (magic, version, checksum, sizes,
     header fields, state).  Host only: needs no device."""
-    lib = load_library()
-    buf = np.frombuffer(bytes(checkpoint), np.uint8).copy()
-    handle = ctx.handle if ctx is not None else None
-    return lib.nblic_amd_dstream_check(handle, C.c_void_p(buf.ctypes.data if buf.size else 0), buf.size) == 0
+    buf = _bytes_arg(checkpoint)
+    return load_library().nblic_amd_dstream_check(ctx.handle if ctx is not None else None, _ptr(buf), buf.size) == 0
+
+
+def check_encoder_checkpoint(checkpoint: bytes, ctx: Optional[Context] = None) -> bool:
+    """True when ``checkpoint`` would be accepted by ``Context.stream(..., checkpoint=...)`` (magic, version, checksum,
+    sizes, header fields, state and its tables).  Host only: needs no device."""
+    buf = _bytes_arg(checkpoint)
+    return load_library().nblic_amd_stream_check(ctx.handle if ctx is not None else None, _ptr(buf), buf.size) == 0
 
 
 def _bytes_arg(b: bytes) -> np.ndarray:

@@ -1225,6 +1225,22 @@ constexpr int kDecodeChunk = 1024;                                              
 constexpr size_t kQTab = 2 * 12 * 256 * sizeof(uint32_t);                                   // QNBLIC: frequencies, cumulative starts (the kernel derives its symbol index from them)
 static size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
 
+// ---- what every decoder (and the band encoder's records) shares: one place for each decision ---------------------------
+// The codec fields a stream header, a checkpoint or an index names (NBLIC.c:717-729, QNBLIC.c:475-486).
+static bool codec_fields_ok(int kind, int h, int w, int near, int k_step, int effort, long max_px) {
+    if (!size_ok(h, w, max_px)) return false;
+    if (kind == 0) return near >= 0 && near <= kMaxNear && k_step >= kMinKStep && k_step <= kLevels && effort >= 1 && effort <= 3;
+    return kind == 1 && near == 0 && effort == 0 && k_step == kMinKStep;
+}
+
+// Sizes of one image's decode: its state record, its least-squares statistics [B | F] (efforts 2 / 3; B is the first
+// half), the rows one launch covers.
+static size_t record_state_bytes(int kind) { return kind ? kQDecodeStateBytes : kDecodeStateBytes; }
+static size_t lsq_stats_bytes(int kind, int effort, int w) { return stats_doubles(kind ? 0 : effort, w) * sizeof(double); }
+static int rows_per_launch(const DecodeItem &it, int override_rows) { return serial_rows_per_launch(it.h, it.w, it.kind ? 1 : it.effort, override_rows); }
+static unsigned long long first_pos(const DecodeItem &it) { return it.kind ? (unsigned long long)(it.q_pos) * 2ull : (unsigned long long)(kHeaderBytes); }
+static size_t stream_buf_bytes(size_t n) { return up256(n + 2048); }                      // a device copy of n stream bytes (upload_stream)
+
 // QNBLIC: the header and the twelve histogram tables in front of the rANS words -- at most 4 + 12 x 256 16-bit codes
 // (q_entropy.cpp q_read_hist) -- from the n bytes at p into a kQTab buffer.  Returns the index of the first rANS word,
 // or -1 when the tables do not parse from those bytes.
@@ -1237,25 +1253,155 @@ static long q_parse_tables(const unsigned char *p, size_t n, uint8_t *tab) {
     return q_decode_tables(words, n_words, &hh, &ww, freq, freq + 12 * 256, nullptr);
 }
 
-// Header of a stream of which `len` bytes are in hand (NBLIC.c:698-745, QNBLIC.c:475-486).  0 = not a stream this
-// library decodes (or refused: size, parameters), 1 = fields filled in.
-static int parse_stream_header(const unsigned char *p, size_t len, long max_px, DecodeItem &it) {
+// Header of a stream of which `len` bytes are in hand (NBLIC.c:698-745, QNBLIC.c:475-486).  false = not a stream this
+// library decodes (or refused: size, parameters); true = fields filled in (`it` is left alone otherwise).
+static bool parse_stream_header(const unsigned char *p, size_t len, long max_px, DecodeItem &it) {
+    DecodeItem h = it;
     if (len >= size_t(kHeaderBytes) && memcmp(p, "NBLIC0.3", 8) == 0) {
-        const int n_channel = p[8];
-        it.kind = 0; it.h = (p[9] << 8) | p[10]; it.w = (p[11] << 8) | p[12]; it.near = p[13]; it.k_step = p[14]; it.effort = p[15];
-        return size_ok(it.h, it.w, max_px) && n_channel <= 1 && it.near <= kMaxNear && it.k_step >= kMinKStep && it.k_step <= kLevels &&
-               it.effort >= 1 && it.effort <= 3;
-    }
-    if (len >= 8 && p[0] == 'Q' && p[1] == '0' && p[2] == '.' && p[3] == '2') {
+        if (p[8] > 1) return false;                                      // n_channel
+        h.kind = 0; h.h = (p[9] << 8) | p[10]; h.w = (p[11] << 8) | p[12]; h.near = p[13]; h.k_step = p[14]; h.effort = p[15];
+    } else if (len >= 8 && p[0] == 'Q' && p[1] == '0' && p[2] == '.' && p[3] == '2') {
         uint16_t q[4];
         memcpy(q, p, 8);
-        it.kind = 1; it.h = q[2]; it.w = q[3]; it.near = it.effort = 0; it.k_step = kMinKStep;
-        return size_ok(it.h, it.w, max_px);
+        h.kind = 1; h.h = q[2]; h.w = q[3]; h.near = h.effort = 0; h.k_step = kMinKStep;
+    } else {
+        return false;
     }
-    return 0;
+    if (!codec_fields_ok(h.kind, h.h, h.w, h.near, h.k_step, h.effort, max_px)) return false;
+    it = h;
+    return true;
 }
 
-static size_t decode_state_bytes(const DecodeItem &it) { return up256(it.kind ? kQDecodeStateBytes : kDecodeStateBytes); }
+// A stream's description from the `len` bytes of it at p: the header, it.len, and for QNBLIC the tables (into tab) and
+// q_pos.  A complete stream (partial = false) is refused unless it holds what the decoder reads before the first pixel:
+// NBLIC the header and the coder's first four bytes, QNBLIC the tables and the four bytes of the rANS state.  The prefix
+// of a stream still being fed (partial) needs more while its header or tables are not all there -- the tables are at
+// most 12 x 256 codes, so 64 KB that do not parse never will.
+enum class Described { ok, more, refused };
+static Described describe_stream(const unsigned char *p, size_t len, bool partial, long max_px, DecodeItem &it, std::vector<uint8_t> &tab) {
+    if (partial && len < ((len >= 1 && p[0] == 'Q') ? size_t(8) : size_t(kHeaderBytes))) return Described::more;
+    if (!parse_stream_header(p, len, max_px, it)) return Described::refused;
+    it.len = len;
+    if (it.kind == 0) return partial || len >= size_t(kHeaderBytes) + 4 ? Described::ok : Described::refused;
+    tab.assign(kQTab, 0);
+    it.q_pos = q_parse_tables(p, len, tab.data());
+    if (it.q_pos < 0) return partial && len < 65536 ? Described::more : Described::refused;
+    return partial || size_t(it.q_pos) * 2 + 4 <= len ? Described::ok : Described::refused;
+}
+
+// The decode job of an item.  The buffers are the driver's: the plane (recon; recon_row0 the image row at its index 0),
+// the stream (stream_off its absolute offset), the state record, the statistics, the QNBLIC tables; end_row 0 = h.
+static SerialJob decode_job(const DecodeItem &it, uint8_t *recon, int recon_row0, const uint8_t *stream, unsigned long long stream_off,
+                            SerialState *state, double *stats, const uint8_t *tab, int rows, int end_row) {
+    SerialJob J{};
+    J.recon = recon; J.recon_row0 = recon_row0;
+    J.stream = stream; J.stream_off = stream_off;
+    J.state = state; J.stats = stats;
+    J.h = it.h; J.w = it.w; J.near = it.near; J.k_step = it.k_step; J.effort = it.effort;
+    J.rows = rows; J.end_row = end_row;
+    if (it.kind) { J.q_freq = reinterpret_cast<const uint32_t *>(tab); J.q_start = J.q_freq + 12 * 256; J.q_slot = nullptr; }
+    return J;
+}
+
+// n stream bytes into a device buffer of stream_buf_bytes(n) bytes, zeros from n & ~3 to its end: the window reads whole
+// 512-byte blocks past the end.
+static bool upload_stream(uint8_t *d, const unsigned char *src, size_t n, hipStream_t st) {
+    const size_t z = n & ~size_t(3);
+    return hipMemsetAsync(d + z, 0, stream_buf_bytes(n) - z, st) == hipSuccess && hipMemcpyAsync(d, src, n, hipMemcpyHostToDevice, st) == hipSuccess;
+}
+
+static void sha256_of(const void *p, size_t n, uint8_t out[32]) {
+    Sha256 s;
+    s.update(static_cast<const uint8_t *>(p), n);
+    s.digest(out);
+}
+
+// A sealed record: a head (magic, format version, ...), a body, and the SHA-256 of both in its last 32 bytes.
+static void seal(uint8_t *buf, size_t n) { sha256_of(buf, n - 32, buf + n - 32); }
+// The head (into H) and the body of the len bytes at p if they are a sealed record of this magic and version; else null.
+template <class Head> static const uint8_t *sealed_body(const void *p, size_t len, const char *magic, uint32_t version, Head &H) {
+    uint8_t d[32];
+    if (!p || len < sizeof(Head) + 32) return nullptr;
+    memcpy(&H, p, sizeof H);
+    sha256_of(p, len - 32, d);
+    const uint8_t *b = static_cast<const uint8_t *>(p);
+    return memcmp(H.magic, magic, 8) == 0 && H.version == version && memcmp(d, b + len - 32, 32) == 0 ? b + sizeof H : nullptr;
+}
+
+// A decoder checkpoint (NBLDCKPT): this head, the body (RecordLayout), sealed.  The band decoder's checkpoint and every
+// entry of a seek index.
+constexpr uint32_t kDecodeCheckpointVersion = 1;
+struct DecodeCheckpoint {              // followed by: state record | B | two rows above next_row | QNBLIC tables | SHA-256 of all before it
+    char magic[8];                     // "NBLDCKPT"
+    uint32_t version;                  // kDecodeCheckpointVersion
+    int32_t kind, h, w, near, k_step, effort, band_rows, next_row;
+    uint32_t reserved;
+    unsigned long long feed_from;      // absolute stream offset from which the resumed decoder must be fed (pos & ~511)
+    unsigned long long body_bytes;     // bytes between this head and the checksum
+    Sha256 rows_sha;                   // of rows [0, next_row)
+};
+static_assert(std::is_trivially_copyable<DecodeCheckpoint>::value, "written and read as bytes");
+constexpr unsigned long long kMaxStreamPos = 1ull << 48;   // no stream this library decodes comes near it
+
+// Where the parts of a decoder record's body are, in bytes from its start (the state record is at 0).
+struct RecordLayout { size_t b, b_bytes, rows, tab, bytes; };
+static RecordLayout record_layout(int kind, int w, int effort) {
+    RecordLayout L;
+    L.b = record_state_bytes(kind);
+    L.b_bytes = lsq_stats_bytes(kind, effort, w) / 2;
+    L.rows = L.b + L.b_bytes;
+    L.tab = L.rows + 2 * size_t(w);
+    L.bytes = L.tab + (kind ? kQTab : 0);
+    return L;
+}
+
+static DecodeCheckpoint decode_head(const DecodeItem &it, int band_rows, int next_row, unsigned long long feed_from, const Sha256 &rows_sha) {
+    DecodeCheckpoint H{};
+    memcpy(H.magic, "NBLDCKPT", 8);
+    H.version = kDecodeCheckpointVersion;
+    H.kind = it.kind; H.h = it.h; H.w = it.w; H.near = it.near; H.k_step = it.k_step; H.effort = it.effort;
+    H.band_rows = band_rows; H.next_row = next_row;
+    H.feed_from = feed_from;
+    H.body_bytes = record_layout(it.kind, it.w, it.effort).bytes;
+    H.rows_sha = rows_sha;
+    return H;
+}
+
+// The two rows above row r as a record holds them (decoder and encoder alike): rows [r - n, r), n = min(r, 2), at byte
+// (2 - n) w of a 2 w-byte slot, zeros in front.  Between a plane on the device (plane_row0: the image row at its index 0)
+// and a slot, queued on st.
+struct RowsAbove { int first, n; size_t at; };
+static RowsAbove rows_above(int r, int w) { const int n = r < 2 ? r : 2; return RowsAbove{r - n, n, size_t(2 - n) * size_t(w)}; }
+static bool rows_above_out(uint8_t *slot, const uint8_t *plane, int plane_row0, int r, int w, hipStream_t st) {
+    const RowsAbove A = rows_above(r, w);
+    memset(slot, 0, A.at);
+    return A.n == 0 || hipMemcpyAsync(slot + A.at, plane + size_t(A.first - plane_row0) * size_t(w), size_t(A.n) * size_t(w), hipMemcpyDeviceToHost, st) == hipSuccess;
+}
+static bool rows_above_in(uint8_t *plane, int plane_row0, const uint8_t *slot, int r, int w, hipStream_t st) {
+    const RowsAbove A = rows_above(r, w);
+    return A.n == 0 || hipMemcpyAsync(plane + size_t(A.first - plane_row0) * size_t(w), slot + A.at, size_t(A.n) * size_t(w), hipMemcpyHostToDevice, st) == hipSuccess;
+}
+
+// Adaptive state a record carries that the kernels divide by or index with.  A counter pair {c0, c1}: the probability
+// divides by c0 + c1, and the counter walks (kernels_e1.hip k_counter_epochs) start from a sum of at most kCountLimit;
+// neither half ever falls below 1 (k_init_state, counter_add).  A re-mapper: symbol -> rank and rank -> symbol are
+// inverse permutations of 0 .. 19.  B: sums of pixel products, never NaN or infinite.
+static bool counter_ok(int c0, int c1) { return c0 >= 1 && c1 >= 1 && c0 + c1 <= kCountLimit; }
+template <class T> static bool remapper_ok(const T *rank_of, const T *sym_at) {
+    for (int z = 0; z < kMapSyms; z++) {
+        const int y = int(sym_at[z]);
+        if (y < 0 || y >= kMapSyms || int(rank_of[y]) != z) return false;
+    }
+    return true;
+}
+static bool finite_doubles(const uint8_t *p, size_t bytes) {
+    for (size_t k = 0; k < bytes; k += 8) {
+        double v;
+        memcpy(&v, p + k, 8);
+        if (!(v == v) || v - v != 0.0) return false;
+    }
+    return true;
+}
 
 // One launch round of a (codec, effort) class: every job advances by its `rows`.
 static bool decode_launch(const DecodeItem &first, const SerialJob *d_jobs, const SerialJob *h_jobs, int n, hipStream_t st, bool whole_streams) {
@@ -1283,21 +1429,18 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
     size_t arena = 0;
     for (int k = 0; k < n; k++) {
         status[k] = -1; hs[k] = ws[k] = 0; nears[k] = efforts[k] = 0;
-        DecodeItem it{k, 0, 0, 0, 0, 0, 0, lens[k], -1, -1};
-        if (!parse_stream_header(streams[k], lens[k], c->max_px, it)) continue;
-        if (it.kind == 0 && lens[k] < size_t(kHeaderBytes) + 4) continue;
-        hs[k] = it.h; ws[k] = it.w; nears[k] = it.near; efforts[k] = it.effort;
-        if (size_t(it.h) * size_t(it.w) > img_caps[k]) continue;
-        if (it.kind == 1) {                                              // QNBLIC: histogram tables parsed on the host; a stream whose tables
-            std::vector<uint8_t> tab(kQTab);                             // do not parse is refused here and never reaches the GPU
-            it.q_pos = q_parse_tables(streams[k], lens[k], tab.data());
-            if (it.q_pos < 0 || size_t(it.q_pos) * 2 + 4 > lens[k]) continue;
+        DecodeItem it{k, 0, 0, 0, 0, 0, 0, 0, -1, -1};
+        std::vector<uint8_t> tab;                                        // QNBLIC: histogram tables parsed on the host; a stream whose tables
+        const Described r = describe_stream(streams[k], lens[k], false, c->max_px, it, tab);     // do not parse never reaches the GPU
+        if (it.h > 0) { hs[k] = it.h; ws[k] = it.w; nears[k] = it.near; efforts[k] = it.effort; }     // the header parsed
+        if (r != Described::ok || size_t(it.h) * size_t(it.w) > img_caps[k]) continue;
+        if (it.kind == 1) {
             it.qtab = int(qtabs.size());
             qtabs.push_back(std::move(tab));
         }
         items.push_back(it);
-        arena += up256(lens[k] + 2048) + up256(size_t(it.h) * size_t(it.w)) + up256(stats_doubles(it.effort, it.w) * sizeof(double)) +
-                 decode_state_bytes(it) + (it.kind ? up256(kQTab) : 0);
+        arena += stream_buf_bytes(it.len) + up256(size_t(it.h) * size_t(it.w)) + up256(lsq_stats_bytes(it.kind, it.effort, it.w)) +
+                 up256(record_state_bytes(it.kind)) + (it.kind ? up256(kQTab) : 0);
     }
     if (items.empty()) return true;
     std::stable_sort(items.begin(), items.end(), [](const DecodeItem &a, const DecodeItem &b) { return a.kind * 4 + a.effort < b.kind * 4 + b.effort; });
@@ -1309,24 +1452,16 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
     size_t off = 0;
     for (int i = 0; i < m; i++) {                                        // the arena's layout
         const DecodeItem &it = items[size_t(i)];
-        SerialJob &J = jobs[size_t(i)];
-        J = SerialJob{};
-        d_streams[size_t(i)] = c->dec_arena + off; off += up256(it.len + 2048);
-        J.recon = c->dec_arena + off; off += up256(size_t(it.h) * size_t(it.w));
-        const size_t sb = stats_doubles(it.effort, it.w) * sizeof(double);
-        if (sb) { J.stats = reinterpret_cast<double *>(c->dec_arena + off); off += up256(sb); }
-        J.state = reinterpret_cast<SerialState *>(c->dec_arena + off); off += decode_state_bytes(it);
-        J.stream = d_streams[size_t(i)];
-        J.h = it.h; J.w = it.w; J.near = it.near; J.k_step = it.k_step; J.effort = it.effort;
-        J.rows = serial_rows_per_launch(it.h, it.w, it.kind ? 1 : it.effort, c->serial_rows);
+        d_streams[size_t(i)] = c->dec_arena + off; off += stream_buf_bytes(it.len);
+        uint8_t *recon = c->dec_arena + off; off += up256(size_t(it.h) * size_t(it.w));
+        const size_t sb = lsq_stats_bytes(it.kind, it.effort, it.w);
+        double *stats = sb ? reinterpret_cast<double *>(c->dec_arena + off) : nullptr; off += up256(sb);
+        SerialState *state = reinterpret_cast<SerialState *>(c->dec_arena + off); off += up256(record_state_bytes(it.kind));
+        if (it.kind == 1) { d_tabs[size_t(i)] = c->dec_arena + off; off += up256(kQTab); }
+        jobs[size_t(i)] = decode_job(it, recon, 0, d_streams[size_t(i)], 0, state, stats, d_tabs[size_t(i)], rows_per_launch(it, c->serial_rows), 0);
         SerialState &H = heads[size_t(i)];
         H = SerialState{};
-        H.pos = it.kind ? (unsigned long long)(it.q_pos) * 2ull : (unsigned long long)(kHeaderBytes);
-        H.avail = it.len; H.final_ = 1;
-        if (it.kind == 1) {
-            d_tabs[size_t(i)] = c->dec_arena + off; off += up256(kQTab);
-            J.q_freq = reinterpret_cast<const uint32_t *>(d_tabs[size_t(i)]); J.q_start = J.q_freq + 12 * 256; J.q_slot = nullptr;
-        }
+        H.pos = first_pos(it); H.avail = it.len; H.final_ = 1;
     }
     // Chunks of one (codec, effort) class, at most kDecodeChunk images each, alternate between two streams: a chunk's uploads,
     // its launches (`rows` rows of every image per launch) and its copies back are all on ITS stream, and the host issues
@@ -1350,10 +1485,8 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         for (int i = ch.i0; i < ch.i1; i++) {
             const DecodeItem &it = items[size_t(i)];
             const SerialJob &J = jobs[size_t(i)];
-            const size_t sb = stats_doubles(it.effort, it.w) * sizeof(double);
-            if (sb && hipMemsetAsync(J.stats, 0, sb, st) != hipSuccess) return false;
-            if (hipMemsetAsync(d_streams[size_t(i)] + (it.len & ~size_t(3)), 0, 2048, st) != hipSuccess) return false;      // the window reads whole 512-byte blocks past the end
-            if (hipMemcpyAsync(d_streams[size_t(i)], streams[it.k], it.len, hipMemcpyHostToDevice, st) != hipSuccess) return false;
+            if (J.stats && hipMemsetAsync(J.stats, 0, lsq_stats_bytes(it.kind, it.effort, it.w), st) != hipSuccess) return false;
+            if (!upload_stream(d_streams[size_t(i)], streams[it.k], it.len, st)) return false;
             if (hipMemcpyAsync(J.state, &heads[size_t(i)], sizeof(SerialState), hipMemcpyHostToDevice, st) != hipSuccess) return false;
             if (it.kind == 1 && hipMemcpyAsync(d_tabs[size_t(i)], qtabs[size_t(it.qtab)].data(), kQTab, hipMemcpyHostToDevice, st) != hipSuccess) return false;
         }
@@ -1439,14 +1572,64 @@ static size_t safe_copy(nblic_amd_ctx *c, void *dst, const void *src, size_t n) 
 // a band, and between bands EVERYTHING the encoder carries is small enough to be written down: a checkpoint
 // (model state record, the least-squares column statistics, the two tables, the coder interval, a running SHA-256
 // of the bytes emitted so far) from which another call -- another process -- carries on.
-struct BandCheckpoint {                 // followed by: model state record | B statistics | map_state | cnt_state | two reconstruction rows (if kept)
-    char magic[8];                      // "NBLCKPT1"
-    int h, w, near, effort, band_rows, next_row;
+// The checkpoint is framed as the decoder's (DecodeCheckpoint): a head with its format version and body length, the body,
+// sealed.  Every field is checked on the host (stream_check) before a resume allocates anything.
+constexpr uint32_t kEncodeCheckpointVersion = 1;
+struct EncodeCheckpoint {               // followed by: model state record | B | map_state | cnt_state | two rows above next_row (if kept) | SHA-256 of all before it
+    char magic[8];                      // "NBLECKPT"
+    uint32_t version;                   // kEncodeCheckpointVersion
+    int32_t h, w, near, effort, band_rows, next_row;
     uint32_t lo, hi;                    // coder interval (NBLIC.c:527-533)
+    uint32_t reserved;                  // zero
     unsigned long long bytes_total;     // stream bytes emitted so far, header included
     Sha256 sha;                         // of exactly those bytes
-    unsigned long long stats_bytes, recon_bytes;
+    unsigned long long stats_bytes, recon_bytes;   // of B and of the rows above (0 or 2 w)
+    unsigned long long body_bytes;      // bytes between this head and the checksum
 };
+static_assert(sizeof(EncodeCheckpoint) == 184 && std::is_trivially_copyable<EncodeCheckpoint>::value, "written and read as bytes");
+constexpr size_t kMapStateBytes = 512 * 60 * sizeof(int), kCntStateBytes = 4096 * 2 * sizeof(int);
+
+// near > 0, or rows too wide for the model kernel's LDS: the encoder keeps a whole reconstruction on the device
+static bool encoder_keeps_recon(int near, int w) { return near > 0 || !serial_model_rows_fit(w); }
+
+// Where the parts of an encoder checkpoint's body are, in bytes from its start (the model state record is at 0).
+struct EncodeLayout { size_t b, b_bytes, map, cnt, rows, rows_bytes, bytes; };
+static EncodeLayout encode_layout(int w, int near, int effort) {
+    EncodeLayout L;
+    L.b = kModelStateBytes;
+    L.b_bytes = lsq_stats_bytes(0, effort, w) / 2;                       // the column statistics B; the row pre-pass F is recomputed
+    L.map = L.b + L.b_bytes;
+    L.cnt = L.map + kMapStateBytes;
+    L.rows = L.cnt + kCntStateBytes;
+    L.rows_bytes = encoder_keeps_recon(near, w) ? 2 * size_t(w) : 0;
+    L.bytes = L.rows + L.rows_bytes;
+    return L;
+}
+
+// Every field of an encoder checkpoint, on the host alone.  0 = valid (head filled in), -1 = refused.
+static int stream_check(const void *ck, size_t len, long max_px, EncodeCheckpoint &H) {
+    const uint8_t *body = sealed_body(ck, len, "NBLECKPT", kEncodeCheckpointVersion, H);
+    if (!body || !codec_fields_ok(0, H.h, H.w, H.near, k_step_for_near(H.near), H.effort, max_px) || H.reserved != 0) return -1;
+    if (H.band_rows < 1 || H.band_rows > H.h || H.next_row < 1 || H.next_row >= H.h) return -1;
+    if (H.bytes_total == 0 || H.sha.total != H.bytes_total || H.lo >= H.hi) return -1;
+    const EncodeLayout L = encode_layout(H.w, H.near, H.effort);
+    if (H.stats_bytes != L.b_bytes || H.recon_bytes != L.rows_bytes || H.body_bytes != L.bytes || len != sizeof H + L.bytes + 32) return -1;
+    SerialState S;
+    memcpy(&S, body, sizeof S);
+    if (S.status != kRunning || S.next_row != H.next_row) return -1;
+    if (!finite_doubles(body + L.b, L.b_bytes)) return -1;
+    int32_t st[60];
+    for (int m = 0; m < 512; m++) {                                      // k_mapper_chains: symbol -> rank, rank -> symbol, hit counts
+        memcpy(st, body + L.map + size_t(m) * sizeof st, sizeof st);
+        if (!remapper_ok(st, st + kMapSyms)) return -1;
+    }
+    for (int k = 0; k < 4096; k++) {                                     // k_counter_epochs: {c0, c1}
+        int32_t c[2];
+        memcpy(c, body + L.cnt + size_t(k) * sizeof c, sizeof c);
+        if (!counter_ok(c[0], c[1])) return -1;
+    }
+    return 0;
+}
 
 }  // namespace nblic
 
@@ -1504,8 +1687,8 @@ static nblic_amd_stream *stream_open(nblic_amd_ctx *c, const unsigned char *img,
     bool ok = true;
     if (on_device) s->d_img = img;
     else ok = hipMalloc((void **)&s->own_img, n) == hipSuccess && hipMemcpyAsync(s->own_img, img, n, hipMemcpyHostToDevice, g.stream) == hipSuccess && (s->d_img = s->own_img, true);
-    if (ok && (s->near > 0 || !serial_model_rows_fit(w))) ok = hipMalloc((void **)&s->d_recon, n) == hipSuccess;
-    s->stats_bytes = stats_doubles(s->effort, w) * sizeof(double);
+    if (ok && encoder_keeps_recon(s->near, w)) ok = hipMalloc((void **)&s->d_recon, n) == hipSuccess;
+    s->stats_bytes = lsq_stats_bytes(0, s->effort, w);
     if (ok && s->stats_bytes) ok = hipMalloc((void **)&s->d_stats, s->stats_bytes) == hipSuccess && hipMemsetAsync(s->d_stats, 0, s->stats_bytes, g.stream) == hipSuccess;   // NBLIC.c:789
     Slot &sl = g.slots[0];
     ok = ok && ensure_pixels(sl, size_t(s->band_rows) * size_t(w));
@@ -1606,60 +1789,54 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
     return s->finished ? 1 : 0;
 }
 
-static size_t stream_checkpoint_bytes(const nblic_amd_stream *s) {
-    return sizeof(BandCheckpoint) + kModelStateBytes + s->stats_bytes / 2 + 512 * 60 * sizeof(int) + 4096 * 2 * sizeof(int) + (s->d_recon ? 2 * size_t(s->w) : 0);
-}
-
+// The checkpoint of an encoder between two bands; 0 when there is nothing to resume (never run, finished or failed: a
+// finished encoder resumed would emit its four flush bytes again).
 static size_t stream_checkpoint(nblic_amd_stream *s, void *buf, size_t cap) {
-    const size_t need = stream_checkpoint_bytes(s);
+    if (s->failed || s->finished || s->bytes_total == 0) return 0;
+    const EncodeLayout L = encode_layout(s->w, s->near, s->effort);
+    const size_t need = sizeof(EncodeCheckpoint) + L.bytes + 32;
     if (!buf || cap < need) return need;
-    if (s->failed || hipSetDevice(s->c->device) != hipSuccess) return 0;
+    if (hipSetDevice(s->c->device) != hipSuccess) return 0;
     Group &g = s->c->groups[size_t(s->gid)];
     Slot &sl = g.slots[0];
-    BandCheckpoint H{};
-    memcpy(H.magic, "NBLCKPT1", 8);
+    EncodeCheckpoint H{};
+    memcpy(H.magic, "NBLECKPT", 8);
+    H.version = kEncodeCheckpointVersion;
     H.h = s->h; H.w = s->w; H.near = s->near; H.effort = s->effort; H.band_rows = s->band_rows; H.next_row = s->next_row;
     H.lo = s->lo; H.hi = s->hi; H.bytes_total = s->bytes_total; H.sha = s->sha;
-    H.stats_bytes = s->stats_bytes / 2; H.recon_bytes = s->d_recon ? 2 * size_t(s->w) : 0;
-    uint8_t *p = static_cast<uint8_t *>(buf);
-    memcpy(p, &H, sizeof H); p += sizeof H;
-    bool ok = hipMemcpy(p, sl.d_state, kModelStateBytes, hipMemcpyDeviceToHost) == hipSuccess; p += kModelStateBytes;
-    if (H.stats_bytes) ok = ok && hipMemcpy(p, s->d_stats, H.stats_bytes, hipMemcpyDeviceToHost) == hipSuccess;       // the column statistics B; the row pre-pass F is recomputed
-    p += H.stats_bytes;
-    ok = ok && hipMemcpy(p, sl.b.map_state, 512 * 60 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess; p += 512 * 60 * sizeof(int);
-    ok = ok && hipMemcpy(p, sl.b.cnt_state, 4096 * 2 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess; p += 4096 * 2 * sizeof(int);
-    if (H.recon_bytes) {                                                  // the two rows above the next one (fewer at the top of the image: zeros)
-        memset(p, 0, H.recon_bytes);
-        const int r0 = s->next_row >= 2 ? s->next_row - 2 : 0, nr = s->next_row - r0;
-        if (nr > 0) ok = ok && hipMemcpy(p + size_t(2 - nr) * size_t(s->w), s->d_recon + size_t(r0) * size_t(s->w), size_t(nr) * size_t(s->w), hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    return ok ? need : 0;
+    H.stats_bytes = L.b_bytes; H.recon_bytes = L.rows_bytes; H.body_bytes = L.bytes;
+    uint8_t *p = static_cast<uint8_t *>(buf), *body = p + sizeof H;
+    memcpy(p, &H, sizeof H);
+    const hipStream_t st = g.stream;
+    bool ok = hipMemcpyAsync(body, sl.d_state, kModelStateBytes, hipMemcpyDeviceToHost, st) == hipSuccess &&
+              (!L.b_bytes || hipMemcpyAsync(body + L.b, s->d_stats, L.b_bytes, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+              hipMemcpyAsync(body + L.map, sl.b.map_state, kMapStateBytes, hipMemcpyDeviceToHost, st) == hipSuccess &&
+              hipMemcpyAsync(body + L.cnt, sl.b.cnt_state, kCntStateBytes, hipMemcpyDeviceToHost, st) == hipSuccess &&
+              (!L.rows_bytes || rows_above_out(body + L.rows, s->d_recon, 0, s->next_row, s->w, st)) &&
+              hipStreamSynchronize(st) == hipSuccess;
+    if (!ok) return 0;
+    seal(p, need);
+    return need;
 }
 
 static nblic_amd_stream *stream_resume(nblic_amd_ctx *c, const unsigned char *img, bool on_device, const void *ck, size_t ck_len) {
-    if (!ck || ck_len < sizeof(BandCheckpoint)) return nullptr;
-    BandCheckpoint H;
-    memcpy(&H, ck, sizeof H);
-    if (memcmp(H.magic, "NBLCKPT1", 8) != 0) return nullptr;
+    EncodeCheckpoint H;
+    if (!c || stream_check(ck, ck_len, c->max_px, H) != 0) return nullptr;
     nblic_amd_stream *s = stream_open(c, img, on_device, H.h, H.w, H.near, H.effort, H.band_rows);
     if (!s) return nullptr;
-    if (ck_len != stream_checkpoint_bytes(s) || H.stats_bytes != s->stats_bytes / 2 || H.next_row < 0 || H.next_row > H.h) { stream_free(s); return nullptr; }
+    const EncodeLayout L = encode_layout(H.w, H.near, H.effort);
     Group &g = c->groups[size_t(s->gid)];
     Slot &sl = g.slots[0];
     s->next_row = s->first_row = H.next_row; s->lo = H.lo; s->hi = H.hi; s->bytes_total = H.bytes_total; s->sha = H.sha;
-    s->finished = false;
-    const uint8_t *p = static_cast<const uint8_t *>(ck) + sizeof H;
-    bool ok = hipStreamSynchronize(g.stream) == hipSuccess;
-    ok = ok && hipMemcpy(sl.d_state, p, kModelStateBytes, hipMemcpyHostToDevice) == hipSuccess; p += kModelStateBytes;
-    if (H.stats_bytes) ok = ok && hipMemcpy(s->d_stats, p, H.stats_bytes, hipMemcpyHostToDevice) == hipSuccess;
-    p += H.stats_bytes;
-    ok = ok && hipMemcpy(sl.b.map_state, p, 512 * 60 * sizeof(int), hipMemcpyHostToDevice) == hipSuccess; p += 512 * 60 * sizeof(int);
-    ok = ok && hipMemcpy(sl.b.cnt_state, p, 4096 * 2 * sizeof(int), hipMemcpyHostToDevice) == hipSuccess; p += 4096 * 2 * sizeof(int);
-    if (H.recon_bytes && s->d_recon) {
-        const int r0 = s->next_row >= 2 ? s->next_row - 2 : 0, nr = s->next_row - r0;
-        if (nr > 0) ok = ok && hipMemcpy(s->d_recon + size_t(r0) * size_t(s->w), p + size_t(2 - nr) * size_t(s->w), size_t(nr) * size_t(s->w), hipMemcpyHostToDevice) == hipSuccess;
-    }
-    if (!ok || s->bytes_total == 0) { stream_free(s); return nullptr; }
+    const uint8_t *body = static_cast<const uint8_t *>(ck) + sizeof H;
+    const hipStream_t st = g.stream;                                     // behind stream_open's uploads
+    const bool ok = hipMemcpyAsync(sl.d_state, body, kModelStateBytes, hipMemcpyHostToDevice, st) == hipSuccess &&
+                    (!L.b_bytes || hipMemcpyAsync(s->d_stats, body + L.b, L.b_bytes, hipMemcpyHostToDevice, st) == hipSuccess) &&
+                    hipMemcpyAsync(sl.b.map_state, body + L.map, kMapStateBytes, hipMemcpyHostToDevice, st) == hipSuccess &&
+                    hipMemcpyAsync(sl.b.cnt_state, body + L.cnt, kCntStateBytes, hipMemcpyHostToDevice, st) == hipSuccess &&
+                    (!L.rows_bytes || rows_above_in(s->d_recon, 0, body + L.rows, s->next_row, s->w, st)) &&
+                    hipStreamSynchronize(st) == hipSuccess;
+    if (!ok) { stream_free(s); return nullptr; }
     return s;
 }
 
@@ -1682,74 +1859,35 @@ static nblic_amd_stream *stream_resume(nblic_amd_ctx *c, const unsigned char *im
 // place is B (every pixel's update).  So B is copied aside before every launch of effort 2 / 3 and copied back after a
 // mid-row stop; the band is then run again from the same record once the window holds more bytes (the caller feeds more,
 // or, when the window was what ran out, the window grows: the only case in which the workspace grows).
-constexpr uint32_t kDecodeCheckpointVersion = 1;
-struct DecodeCheckpoint {              // followed by: state record | B | two rows above next_row | QNBLIC tables | SHA-256 of all before it
-    char magic[8];                     // "NBLDCKPT"
-    uint32_t version;                  // kDecodeCheckpointVersion
-    int32_t kind, h, w, near, k_step, effort, band_rows, next_row;
-    uint32_t reserved;
-    unsigned long long feed_from;      // absolute stream offset from which the resumed decoder must be fed (pos & ~511)
-    unsigned long long body_bytes;     // bytes between this head and the checksum
-    Sha256 rows_sha;                   // of rows [0, next_row)
-};
-static_assert(std::is_trivially_copyable<DecodeCheckpoint>::value, "written and read as bytes");
-constexpr unsigned long long kMaxStreamPos = 1ull << 48;   // no stream this library decodes comes near it
-
-static size_t dstream_state_bytes(int kind) { return kind ? kQDecodeStateBytes : kDecodeStateBytes; }
-static size_t dstream_body_bytes(int kind, int w, int effort) {
-    return dstream_state_bytes(kind) + stats_doubles(kind ? 0 : effort, w) * sizeof(double) / 2 + 2 * size_t(w) + (kind ? kQTab : 0);
-}
-
+// The checkpoint: DecodeCheckpoint (the record layer above).
 // Every field of a checkpoint, before anything of it reaches the device.  0 = valid (head filled in), -1 = refused.
 static int dstream_check(const void *ck, size_t len, long max_px, DecodeCheckpoint &H) {
-    if (!ck || len < sizeof(DecodeCheckpoint) + 32) return -1;
-    const uint8_t *p = static_cast<const uint8_t *>(ck);
-    memcpy(&H, p, sizeof H);
-    if (memcmp(H.magic, "NBLDCKPT", 8) != 0 || H.version != kDecodeCheckpointVersion) return -1;
-    {
-        Sha256 sum;
-        sum.update(p, len - 32);
-        uint8_t d[32];
-        sum.digest(d);
-        if (memcmp(d, p + len - 32, 32) != 0) return -1;
-    }
-    if (H.kind != 0 && H.kind != 1) return -1;
-    if (!size_ok(H.h, H.w, max_px)) return -1;
-    if (H.kind == 0 && (H.near < 0 || H.near > kMaxNear || H.k_step < kMinKStep || H.k_step > kLevels || H.effort < 1 || H.effort > 3)) return -1;
-    if (H.kind == 1 && (H.near != 0 || H.effort != 0 || H.k_step != kMinKStep)) return -1;
+    const uint8_t *body = sealed_body(ck, len, "NBLDCKPT", kDecodeCheckpointVersion, H);
+    if (!body || !codec_fields_ok(H.kind, H.h, H.w, H.near, H.k_step, H.effort, max_px)) return -1;
     if (H.band_rows < 1 || H.band_rows > H.h || H.next_row < 0 || H.next_row >= H.h) return -1;
-    if (H.body_bytes != dstream_body_bytes(H.kind, H.w, H.effort) || len != sizeof H + H.body_bytes + 32) return -1;
+    const RecordLayout L = record_layout(H.kind, H.w, H.effort);
+    if (H.body_bytes != L.bytes || len != sizeof H + H.body_bytes + 32) return -1;
     if (H.rows_sha.total != (unsigned long long)(H.next_row) * (unsigned long long)(H.w)) return -1;
     SerialState S;
-    memcpy(&S, p + sizeof H, sizeof S);
+    memcpy(&S, body, sizeof S);
     const unsigned long long first = H.kind ? 8 : (unsigned long long)(kHeaderBytes);
     if (S.status != kRunning || S.next_row != H.next_row || S.pos < first || S.pos >= kMaxStreamPos || (S.pos & ~511ull) != H.feed_from) return -1;
-    const uint8_t *tab = p + sizeof H + sizeof S;
+    const uint8_t *tab = body + sizeof S;
     if (H.kind == 0 && H.next_row > 0) {                                 // the tables a resumed launch loads: every value an index can come from
         const uint32_t *cnt = reinterpret_cast<const uint32_t *>(tab) + kContexts;
         for (int k = 0; k < kLevels * kTreeNodes; k++) {
             uint32_t c;
             memcpy(&c, cnt + k, 4);
-            if ((c & 0xFFFFu) == 0 || (c >> 16) == 0) return -1;             // bin probabilities divide by c0 + c1
+            if (!counter_ok(int(c & 0xFFFFu), int(c >> 16))) return -1;
         }
-        const uint8_t *rank = tab + (size_t(kContexts) + size_t(kLevels) * kTreeNodes + 512 * kMapSyms) * 4, *sym = rank + 512 * kMapSyms;
+        const uint8_t *rank = tab + size_t(kRecRank) * 4, *sym = tab + size_t(kRecSym) * 4;
         for (int m = 0; m < 512; m++)
-            for (int z = 0; z < kMapSyms; z++) {
-                const int y = sym[m * kMapSyms + z];
-                if (y >= kMapSyms || rank[m * kMapSyms + y] != z) return -1;     // a permutation and its inverse
-            }
+            if (!remapper_ok(rank + m * kMapSyms, sym + m * kMapSyms)) return -1;
     }
-    const size_t b_bytes = stats_doubles(H.kind ? 0 : H.effort, H.w) * sizeof(double) / 2;
-    const uint8_t *b = tab + dstream_state_bytes(H.kind) - sizeof S;
-    for (size_t k = 0; k < b_bytes; k += 8) {
-        double v;
-        memcpy(&v, b + k, 8);
-        if (!(v == v) || v - v != 0.0) return -1;                       // NaN / infinity: never a sum of pixel products
-    }
+    if (!finite_doubles(body + L.b, L.b_bytes)) return -1;
     if (H.kind == 1) {                                                   // the twelve frequency tables and their cumulative starts
-        const uint8_t *q = b + b_bytes + 2 * size_t(H.w);
         uint32_t freq[12 * 256], start[12 * 256];
-        memcpy(freq, q, sizeof freq); memcpy(start, q + sizeof freq, sizeof start);
+        memcpy(freq, body + L.tab, sizeof freq); memcpy(start, body + L.tab + sizeof freq, sizeof start);
         for (int l = 0; l < 12; l++) {
             uint32_t acc = 0;
             for (int s = 0; s < 256; s++) {
@@ -1819,21 +1957,21 @@ static size_t dstream_win_cap(int band_rows, int w) {
 // The workspace of a header that has just been parsed (or of a checkpoint): depends on band_rows and w, never on h.
 static bool dstream_setup(nblic_amd_dstream *d) {
     const DecodeItem &it = d->it;
-    d->band_rows = serial_rows_per_launch(it.h, it.w, it.kind ? 1 : it.effort, d->band_rows_req);
-    d->stats_bytes = stats_doubles(it.kind ? 0 : it.effort, it.w) * sizeof(double);
+    d->band_rows = rows_per_launch(it, d->band_rows_req);
+    d->stats_bytes = lsq_stats_bytes(it.kind, it.effort, it.w);
     d->win_cap = dstream_win_cap(d->band_rows, it.w);
     const size_t rows_bytes = size_t(d->band_rows + 2) * size_t(it.w);
     bool ok = hipMalloc((void **)&d->d_rows, rows_bytes) == hipSuccess && hipMalloc((void **)&d->d_carry, 2 * size_t(it.w)) == hipSuccess &&
               hipMalloc((void **)&d->d_win, d->win_cap + 2048) == hipSuccess &&
-              hipMalloc((void **)&d->d_state, up256(dstream_state_bytes(it.kind))) == hipSuccess &&
+              hipMalloc((void **)&d->d_state, up256(record_state_bytes(it.kind))) == hipSuccess &&
               hipMalloc((void **)&d->d_job, sizeof(SerialJob)) == hipSuccess;
     if (ok && d->stats_bytes) ok = hipMalloc((void **)&d->d_stats, d->stats_bytes) == hipSuccess && hipMalloc((void **)&d->d_snap, d->stats_bytes / 2) == hipSuccess &&
                                    hipMemsetAsync(d->d_stats, 0, d->stats_bytes, d->st) == hipSuccess;     // NBLIC.c:789
     if (ok && it.kind) ok = hipMalloc((void **)&d->d_tab, kQTab) == hipSuccess;
-    ok = ok && hipMemsetAsync(d->d_state, 0, up256(dstream_state_bytes(it.kind)), d->st) == hipSuccess &&
+    ok = ok && hipMemsetAsync(d->d_state, 0, up256(record_state_bytes(it.kind)), d->st) == hipSuccess &&
          hipMemsetAsync(d->d_rows, 0, rows_bytes, d->st) == hipSuccess && hipMemsetAsync(d->d_win, 0, d->win_cap + 2048, d->st) == hipSuccess;
     if (!ok) { fprintf(stderr, "[nblic_amd] band decoder: cannot set up the workspace\n"); dstream_free_device(d); return false; }
-    d->device_bytes = rows_bytes + 2 * size_t(it.w) + d->win_cap + 2048 + up256(dstream_state_bytes(it.kind)) + sizeof(SerialJob) +
+    d->device_bytes = rows_bytes + 2 * size_t(it.w) + d->win_cap + 2048 + up256(record_state_bytes(it.kind)) + sizeof(SerialJob) +
                       d->stats_bytes + d->stats_bytes / 2 + (it.kind ? kQTab : 0);
     return true;
 }
@@ -1841,29 +1979,17 @@ static bool dstream_setup(nblic_amd_dstream *d) {
 // The header (QNBLIC: and its tables) from the bytes fed so far.  Sets have_head or refused; neither: not all there yet.
 static void dstream_try_header(nblic_amd_dstream *d) {
     if (d->have_head || d->refused) return;
-    const size_t n = d->pend.size();
-    const uint8_t *p = d->pend.data();
-    DecodeItem it{0, 0, 0, 0, 0, 0, 0, n, -1, -1};
-    const bool q = n >= 1 && p[0] == 'Q';
-    const size_t head = q ? 8 : size_t(kHeaderBytes);
-    if (n < head) { if (d->complete) d->refused = true; return; }
-    if (!parse_stream_header(p, n, d->c->max_px, it)) { d->refused = true; return; }
-    SerialState H{};
-    if (it.kind == 1) {
-        d->qtab.assign(kQTab, 0);
-        const long pos = q_parse_tables(p, n, d->qtab.data());
-        if (pos < 0) {                                                   // the tables may simply not be in hand yet (at most 12 x 256 codes)
-            if (d->complete || n >= 65536) d->refused = true;
-            return;
-        }
-        H.pos = (unsigned long long)(pos) * 2ull;
-    } else {
-        H.pos = kHeaderBytes;
+    DecodeItem it{0, 0, 0, 0, 0, 0, 0, 0, -1, -1};
+    const Described r = describe_stream(d->pend.data(), d->pend.size(), true, d->c->max_px, it, d->qtab);
+    if (r != Described::ok) {                                            // what is not there yet never will be once the stream is complete
+        if (r == Described::refused || d->complete) d->refused = true;
+        return;
     }
     d->it = it;
     if (!dstream_setup(d)) { d->failed = true; return; }
     if (it.kind == 1 && hipMemcpyAsync(d->d_tab, d->qtab.data(), kQTab, hipMemcpyHostToDevice, d->st) != hipSuccess) { d->failed = true; return; }
-    d->H = H;
+    d->H = SerialState{};
+    d->H.pos = first_pos(it);
     d->win_off = d->win_len = 0;
     d->have_head = true;
 }
@@ -1912,12 +2038,7 @@ static int dstream_run(nblic_amd_dstream *d, double budget_s, unsigned char *row
         if ((written + size_t(rows)) * w > cap) return report(0);                 // rows_out is full
         if (!dstream_fill_window(d)) return fail("stream window");
         const bool final_ = d->complete && dstream_window_holds_all_fed(d);
-        SerialJob J{};
-        J.recon = d->d_rows; J.recon_row0 = d->row0;
-        J.stream = d->d_win; J.stream_off = d->win_off;
-        J.stats = d->d_stats; J.state = d->d_state;
-        J.h = it.h; J.w = it.w; J.near = it.near; J.k_step = it.k_step; J.effort = it.effort; J.rows = rows;
-        if (it.kind) { J.q_freq = reinterpret_cast<const uint32_t *>(d->d_tab); J.q_start = J.q_freq + 12 * 256; J.q_slot = nullptr; }
+        const SerialJob J = decode_job(it, d->d_rows, d->row0, d->d_win, d->win_off, d->d_state, d->d_stats, d->d_tab, rows, 0);
         SerialState S = d->H;
         S.avail = d->win_off + d->win_len; S.final_ = final_ ? 1 : 0; S.status = kRunning;
         if (d->d_snap && hipMemcpyAsync(d->d_snap, d->d_stats, d->stats_bytes / 2, hipMemcpyDeviceToDevice, d->st) != hipSuccess) return fail("snapshot");
@@ -1969,43 +2090,28 @@ static int dstream_run(nblic_amd_dstream *d, double budget_s, unsigned char *row
     return report(d->done ? 1 : 0);
 }
 
-static size_t dstream_checkpoint_bytes(const nblic_amd_dstream *d) {
-    return sizeof(DecodeCheckpoint) + dstream_body_bytes(d->it.kind, d->it.w, d->it.effort) + 32;
-}
-
-static size_t dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap) {
+// The decoder's record in front of row H.next_row, with band_rows and rows_sha as its head is to say (the API: the
+// decoder's own; index_build: the index spacing and the canonical row hash).
+static size_t dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap, int band_rows, const Sha256 &rows_sha) {
     if (!d->have_head || d->failed || d->done) return 0;
-    const size_t need = dstream_checkpoint_bytes(d);
+    const DecodeItem &it = d->it;
+    const RecordLayout L = record_layout(it.kind, it.w, it.effort);
+    const size_t need = sizeof(DecodeCheckpoint) + L.bytes + 32;
     if (!buf || cap < need) return need;
     if (hipSetDevice(d->device) != hipSuccess) return 0;
-    const DecodeItem &it = d->it;
-    DecodeCheckpoint H{};
-    memcpy(H.magic, "NBLDCKPT", 8);
-    H.version = kDecodeCheckpointVersion;
-    H.kind = it.kind; H.h = it.h; H.w = it.w; H.near = it.near; H.k_step = it.k_step; H.effort = it.effort;
-    H.band_rows = d->band_rows; H.next_row = d->H.next_row;
-    H.feed_from = d->H.pos & ~511ull;
-    H.body_bytes = dstream_body_bytes(it.kind, it.w, it.effort);
-    H.rows_sha = d->sha;
-    uint8_t *p = static_cast<uint8_t *>(buf);
+    const DecodeCheckpoint H = decode_head(it, band_rows, d->H.next_row, d->H.pos & ~511ull, rows_sha);
+    uint8_t *p = static_cast<uint8_t *>(buf), *body = p + sizeof H;
     memcpy(p, &H, sizeof H);
-    uint8_t *q = p + sizeof H;
-    const size_t sb = dstream_state_bytes(it.kind), b_bytes = d->stats_bytes / 2;
-    bool ok = hipMemcpyAsync(q, d->d_state, sb, hipMemcpyDeviceToHost, d->st) == hipSuccess;
-    if (b_bytes) ok = ok && hipMemcpyAsync(q + sb, d->d_stats, b_bytes, hipMemcpyDeviceToHost, d->st) == hipSuccess;
-    uint8_t *rows = q + sb + b_bytes;
-    memset(rows, 0, 2 * size_t(it.w));
-    const int r0 = std::max(0, d->H.next_row - 2), nr = d->H.next_row - r0;      // the two rows above next_row (fewer at the top: zeros in front)
-    if (nr > 0) ok = ok && hipMemcpyAsync(rows + size_t(2 - nr) * size_t(it.w), d->d_rows + size_t(r0 - d->row0) * size_t(it.w), size_t(nr) * size_t(it.w), hipMemcpyDeviceToHost, d->st) == hipSuccess;
-    ok = ok && hipStreamSynchronize(d->st) == hipSuccess;
+    const bool ok = hipMemcpyAsync(body, d->d_state, L.b, hipMemcpyDeviceToHost, d->st) == hipSuccess &&
+                    (!L.b_bytes || hipMemcpyAsync(body + L.b, d->d_stats, L.b_bytes, hipMemcpyDeviceToHost, d->st) == hipSuccess) &&
+                    rows_above_out(body + L.rows, d->d_rows, d->row0, d->H.next_row, it.w, d->st) &&
+                    hipStreamSynchronize(d->st) == hipSuccess;
     if (!ok) return 0;
     SerialState S = d->H;                                                // the header as the host holds it (the device copy may say kStarved)
     S.status = kRunning; S.avail = 0; S.final_ = 0;
-    memcpy(q, &S, sizeof S);
-    if (it.kind) memcpy(rows + 2 * size_t(it.w), d->qtab.data(), kQTab);
-    Sha256 sum;
-    sum.update(p, need - 32);
-    sum.digest(p + need - 32);
+    memcpy(body, &S, sizeof S);
+    if (it.kind) memcpy(body + L.tab, d->qtab.data(), kQTab);
+    seal(p, need);
     return need;
 }
 
@@ -2029,18 +2135,16 @@ static nblic_amd_dstream *dstream_resume(nblic_amd_ctx *c, const void *ck, size_
     if (!d) return nullptr;
     d->it = DecodeItem{0, H.h, H.w, H.near, H.k_step, H.effort, H.kind, 0, -1, -1};
     if (!dstream_setup(d) || d->band_rows != H.band_rows) { dstream_free(d); return nullptr; }
-    const uint8_t *q = static_cast<const uint8_t *>(ck) + sizeof H;
-    const size_t sb = dstream_state_bytes(H.kind), b_bytes = d->stats_bytes / 2;
-    memcpy(&d->H, q, sizeof(SerialState));
+    const RecordLayout L = record_layout(H.kind, H.w, H.effort);
+    const uint8_t *body = static_cast<const uint8_t *>(ck) + sizeof H;
+    memcpy(&d->H, body, sizeof(SerialState));
     d->sha = H.rows_sha;
     d->row0 = std::max(0, H.next_row - 2);
-    const uint8_t *rows = q + sb + b_bytes;
-    const int nr = H.next_row - d->row0;
-    bool ok = hipMemcpyAsync(d->d_state, q, sb, hipMemcpyHostToDevice, d->st) == hipSuccess;
-    if (b_bytes) ok = ok && hipMemcpyAsync(d->d_stats, q + sb, b_bytes, hipMemcpyHostToDevice, d->st) == hipSuccess;
-    if (nr > 0) ok = ok && hipMemcpyAsync(d->d_rows, rows + size_t(2 - nr) * size_t(H.w), size_t(nr) * size_t(H.w), hipMemcpyHostToDevice, d->st) == hipSuccess;
+    bool ok = hipMemcpyAsync(d->d_state, body, L.b, hipMemcpyHostToDevice, d->st) == hipSuccess &&
+              (!L.b_bytes || hipMemcpyAsync(d->d_stats, body + L.b, L.b_bytes, hipMemcpyHostToDevice, d->st) == hipSuccess) &&
+              rows_above_in(d->d_rows, d->row0, body + L.rows, H.next_row, H.w, d->st);
     if (H.kind) {
-        d->qtab.assign(rows + 2 * size_t(H.w), rows + 2 * size_t(H.w) + kQTab);
+        d->qtab.assign(body + L.tab, body + L.tab + kQTab);
         ok = ok && hipMemcpyAsync(d->d_tab, d->qtab.data(), kQTab, hipMemcpyHostToDevice, d->st) == hipSuccess;
     }
     ok = ok && hipStreamSynchronize(d->st) == hipSuccess;
@@ -2101,18 +2205,22 @@ struct IndexHead {
 };
 static_assert(sizeof(IndexHead) == 96, "written and read as bytes");
 
+static IndexHead index_head(const DecodeItem &it, int every, int count, unsigned long long stream_len) {     // all but stream_sha
+    IndexHead H{};
+    memcpy(H.magic, "NBLSIDX1", 8);
+    H.version = kIndexVersion;
+    H.kind = it.kind; H.h = it.h; H.w = it.w; H.near = it.near; H.k_step = it.k_step; H.effort = it.effort;
+    H.every_rows = every; H.count = count;
+    H.stream_len = stream_len;
+    return H;
+}
+
 struct IndexView {                     // a checked index: its head and where its entries are
     IndexHead H;
+    RecordLayout L;                    // of every entry's body
     std::vector<const uint8_t *> ent;  // entry k + 1 (the checkpoint in front of row (k + 1) R) at ent[k]
+    const uint8_t *body(int k) const { return ent[size_t(k - 1)] + sizeof(DecodeCheckpoint); }     // entry k, 1-based
 };
-
-static size_t index_entry_bytes(int kind, int w, int effort) { return sizeof(DecodeCheckpoint) + dstream_body_bytes(kind, w, effort) + 32; }
-
-static void sha256_of(const void *p, size_t n, uint8_t out[32]) {
-    Sha256 s;
-    s.update(static_cast<const uint8_t *>(p), n);
-    s.digest(out);
-}
 
 // A checkpoint's running row hash, written canonically: the bytes of the partial block past total % 64 are whatever
 // earlier updates left there, and which those are depends on how the rows were cut into updates.
@@ -2125,22 +2233,13 @@ static Sha256 canonical_sha(Sha256 s) {
 // Every field of an index, every entry (dstream_check), and -- when `stream` is given -- that it is the stream the index
 // was made for.  Host only.  0 = valid (V filled in), -1 = refused.
 static int index_check(const void *idx, size_t ilen, const void *stream, size_t slen, long max_px, IndexView &V) {
-    if (!idx || ilen < sizeof(IndexHead) + 32) return -1;
-    const uint8_t *p = static_cast<const uint8_t *>(idx);
     IndexHead &H = V.H;
-    memcpy(&H, p, sizeof H);
-    if (memcmp(H.magic, "NBLSIDX1", 8) != 0 || H.version != kIndexVersion) return -1;
-    {
-        uint8_t d[32];
-        sha256_of(p, ilen - 32, d);
-        if (memcmp(d, p + ilen - 32, 32) != 0) return -1;
-    }
-    if (H.kind != 0 && H.kind != 1) return -1;
-    if (!size_ok(H.h, H.w, max_px) || H.reserved[0] != 0 || H.reserved[1] != 0 || H.reserved[2] != 0) return -1;
-    if (H.kind == 0 && (H.near < 0 || H.near > kMaxNear || H.k_step < kMinKStep || H.k_step > kLevels || H.effort < 1 || H.effort > 3)) return -1;
-    if (H.kind == 1 && (H.near != 0 || H.effort != 0 || H.k_step != kMinKStep)) return -1;
+    if (!sealed_body(idx, ilen, "NBLSIDX1", kIndexVersion, H)) return -1;
+    const uint8_t *p = static_cast<const uint8_t *>(idx);
+    if (!codec_fields_ok(H.kind, H.h, H.w, H.near, H.k_step, H.effort, max_px) || H.reserved[0] != 0 || H.reserved[1] != 0 || H.reserved[2] != 0) return -1;
     if (H.every_rows < 1 || H.every_rows >= H.h || H.count != (H.h - 1) / H.every_rows) return -1;
     if (H.stream_len >= kMaxStreamPos) return -1;
+    V.L = record_layout(H.kind, H.w, H.effort);
     V.ent.clear();
     size_t at = sizeof H;
     const size_t end = ilen - 32;
@@ -2174,28 +2273,24 @@ static int index_check(const void *idx, size_t ilen, const void *stream, size_t 
 }
 
 // One band-decoder pass with band_rows = R, a checkpoint in front of every row R, 2R, ...; the pass runs to the end of the
-// image, so a stream that does not decode gets no index.  With out == NULL or cap too small only the size (the header
-// alone is parsed; ctx may then be NULL).  -1: a stream this library does not decode, R < 1 or R >= h.
+// image, so a stream that does not decode gets no index.  With out == NULL or cap too small only the size (the stream is
+// only described; ctx may then be NULL).  -1: a stream this library does not decode, R < 1 or R >= h.
 static long index_build(nblic_amd_ctx *c, const unsigned char *stream, size_t slen, int every, unsigned char *out, size_t cap) {
     if (!stream) return -1;
-    DecodeItem it{0, 0, 0, 0, 0, 0, 0, slen, -1, -1};
-    if (!parse_stream_header(stream, slen, c ? c->max_px : kMaxPixels, it)) return -1;
+    DecodeItem it{0, 0, 0, 0, 0, 0, 0, 0, -1, -1};
+    std::vector<uint8_t> qtab;
+    if (describe_stream(stream, slen, false, c ? c->max_px : kMaxPixels, it, qtab) != Described::ok) return -1;
     if (every < 1 || every >= it.h) return -1;
     const int count = (it.h - 1) / every;
-    const size_t eb = index_entry_bytes(it.kind, it.w, it.effort);
+    const size_t eb = sizeof(DecodeCheckpoint) + record_layout(it.kind, it.w, it.effort).bytes + 32;
     const size_t need = sizeof(IndexHead) + size_t(count) * (8 + eb) + 32;
     if (!out || cap < need) return long(need);
     if (!c) return -1;
-    IndexHead H{};
-    memcpy(H.magic, "NBLSIDX1", 8);
-    H.version = kIndexVersion;
-    H.kind = it.kind; H.h = it.h; H.w = it.w; H.near = it.near; H.k_step = it.k_step; H.effort = it.effort;
-    H.every_rows = every; H.count = count;
-    H.stream_len = slen;
+    IndexHead H = index_head(it, every, count, slen);
     sha256_of(stream, slen, H.stream_sha);
     memcpy(out, &H, sizeof H);
     // the pass runs in bands of at most serial_rows_per_launch rows (a launch lasts seconds at most); the entries say R
-    const int band = std::min(every, serial_rows_per_launch(it.h, it.w, it.kind ? 1 : it.effort, c->serial_rows));
+    const int band = std::min(every, rows_per_launch(it, c->serial_rows));
     nblic_amd_dstream *d = dstream_new(c, band);
     if (!d) return -1;
     d->pend.assign(stream, stream + slen);
@@ -2212,29 +2307,18 @@ static long index_build(nblic_amd_ctx *c, const unsigned char *stream, size_t sl
         if (k > count) { ok = rc == 1; break; }
         ok = rc == 0 && d->H.next_row == limit;
         if (!ok) break;
-        uint8_t *e = out + at + 8;
         const unsigned long long n = eb;
         memcpy(out + at, &n, 8);
-        ok = dstream_checkpoint(d, e, eb) == eb;
-        if (ok) {                                                        // R as the band height, the row hash canonical (the band encoder's index is byte-identical)
-            DecodeCheckpoint C;
-            memcpy(&C, e, sizeof C);
-            C.band_rows = every;
-            C.rows_sha = canonical_sha(C.rows_sha);
-            memcpy(e, &C, sizeof C);
-            sha256_of(e, eb - 32, e + eb - 32);
-        }
+        // R as the band height, the row hash canonical (the band encoder's index is byte-identical)
+        ok = dstream_checkpoint(d, out + at + 8, eb, every, canonical_sha(d->sha)) == eb;
         at += 8 + eb;
     }
     if (!ok) fprintf(stderr, "[nblic_amd] index: the stream does not decode\n");
     dstream_free(d);
     if (!ok) return -1;
-    sha256_of(out, need - 32, out + need - 32);
+    seal(out, need);
     return long(need);
 }
-
-// Seals an entry: its checksum over everything before it.
-static void seal_entry(std::vector<uint8_t> &ck) { sha256_of(ck.data(), ck.size() - 32, ck.data() + ck.size() - 32); }
 
 // ---- the band ENCODER's index: the decoder's entry record, converted from the encoder's state at an entry row -------
 // The encoder carries the same adaptive state as the decoder in other layouts (kernels_e1.hip): the model record holds
@@ -2257,7 +2341,7 @@ static void stream_index_bytes(nblic_amd_stream *s, const uint8_t *out, const ui
         memcpy(&S, e.ck.data() + sizeof(DecodeCheckpoint), sizeof S);
         S.window = e.window;
         memcpy(e.ck.data() + sizeof(DecodeCheckpoint), &S, sizeof S);
-        seal_entry(e.ck);
+        seal(e.ck.data(), e.ck.size());
         s->entries.push_back(std::move(e.ck));
         s->pending.erase(s->pending.begin());
     }
@@ -2277,17 +2361,17 @@ static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8
     s->rows_sha.update(s->band_rows_host.data(), s->band_rows_host.size());
     const int r = i0 + rows, R = s->index_every;
     if (r % R != 0 || r >= s->h) return true;
-    const size_t body = dstream_body_bytes(0, s->w, s->effort), b_bytes = s->stats_bytes / 2;
-    std::vector<uint8_t> ck(sizeof(DecodeCheckpoint) + body + 32, 0);
+    const DecodeItem it{0, s->h, s->w, s->near, s->k_step, s->effort, 0, 0, -1, -1};
+    const RecordLayout L = record_layout(0, s->w, s->effort);
+    std::vector<uint8_t> ck(sizeof(DecodeCheckpoint) + L.bytes + 32, 0);
     std::vector<uint8_t> model(kModelStateBytes);
     std::vector<int32_t> map(512 * 60), cnt(4096 * 2);
-    uint8_t *rec = ck.data() + sizeof(DecodeCheckpoint), *b = rec + kDecodeStateBytes, *above = b + b_bytes;
-    const int r0 = r >= 2 ? r - 2 : 0, nr = r - r0;
+    uint8_t *rec = ck.data() + sizeof(DecodeCheckpoint);
     bool ok = hipMemcpyAsync(model.data(), sl.d_state, kModelStateBytes, hipMemcpyDeviceToHost, g.stream) == hipSuccess &&
-              hipMemcpyAsync(map.data(), sl.b.map_state, map.size() * 4, hipMemcpyDeviceToHost, g.stream) == hipSuccess &&
-              hipMemcpyAsync(cnt.data(), sl.b.cnt_state, cnt.size() * 4, hipMemcpyDeviceToHost, g.stream) == hipSuccess &&
-              hipMemcpyAsync(above + size_t(2 - nr) * w, plane + size_t(r0) * w, size_t(nr) * w, hipMemcpyDeviceToHost, g.stream) == hipSuccess;
-    if (b_bytes) ok = ok && hipMemcpyAsync(b, s->d_stats, b_bytes, hipMemcpyDeviceToHost, g.stream) == hipSuccess;
+              hipMemcpyAsync(map.data(), sl.b.map_state, kMapStateBytes, hipMemcpyDeviceToHost, g.stream) == hipSuccess &&
+              hipMemcpyAsync(cnt.data(), sl.b.cnt_state, kCntStateBytes, hipMemcpyDeviceToHost, g.stream) == hipSuccess &&
+              rows_above_out(rec + L.rows, plane, 0, r, s->w, g.stream);
+    if (L.b_bytes) ok = ok && hipMemcpyAsync(rec + L.b, s->d_stats, L.b_bytes, hipMemcpyDeviceToHost, g.stream) == hipSuccess;
     if (!ok || hipStreamSynchronize(g.stream) != hipSuccess) return false;
     SerialState M;
     memcpy(&M, model.data(), sizeof M);
@@ -2312,14 +2396,7 @@ static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8
             sym[m * kMapSyms + k] = uint8_t(map[size_t(m) * 60 + 20 + k]);
             memcpy(hits + m * kMapSyms + k, &map[size_t(m) * 60 + 40 + k], 4);
         }
-    DecodeCheckpoint H{};
-    memcpy(H.magic, "NBLDCKPT", 8);
-    H.version = kDecodeCheckpointVersion;
-    H.kind = 0; H.h = s->h; H.w = s->w; H.near = s->near; H.k_step = s->k_step; H.effort = s->effort;
-    H.band_rows = R; H.next_row = r;
-    H.feed_from = S.pos & ~511ull;
-    H.body_bytes = body;
-    H.rows_sha = canonical_sha(s->rows_sha);
+    const DecodeCheckpoint H = decode_head(it, R, r, S.pos & ~511ull, canonical_sha(s->rows_sha));
     memcpy(ck.data(), &H, sizeof H);
     s->pending.push_back(nblic_amd_stream::PendingEntry{std::move(ck), emitted, 0, 0u});
     return true;
@@ -2339,12 +2416,7 @@ static size_t stream_index(nblic_amd_stream *s, void *buf, size_t cap) {
     size_t need = sizeof(IndexHead) + 32;
     for (const auto &e : s->entries) need += 8 + e.size();
     if (!buf || cap < need) return need;
-    IndexHead H{};
-    memcpy(H.magic, "NBLSIDX1", 8);
-    H.version = kIndexVersion;
-    H.kind = 0; H.h = s->h; H.w = s->w; H.near = s->near; H.k_step = s->k_step; H.effort = s->effort;
-    H.every_rows = s->index_every; H.count = count;
-    H.stream_len = s->bytes_total;
+    IndexHead H = index_head(DecodeItem{0, s->h, s->w, s->near, s->k_step, s->effort, 0, 0, -1, -1}, s->index_every, count, s->bytes_total);
     s->sha.digest(H.stream_sha);
     uint8_t *p = static_cast<uint8_t *>(buf);
     memcpy(p, &H, sizeof H);
@@ -2355,13 +2427,20 @@ static size_t stream_index(nblic_amd_stream *s, void *buf, size_t cap) {
         memcpy(p + at + 8, e.data(), e.size());
         at += 8 + e.size();
     }
-    sha256_of(p, need - 32, p + need - 32);
+    seal(p, need);
     return need;
 }
 
-// The device side of one indexed decode call: its own HIP stream and buffers, freed on every path out.
+// One indexed decode call: the checked index, the described stream, and the device side -- its own HIP stream and
+// buffers, freed on every path out.
 struct IndexedRun {
+    IndexView V;
+    DecodeItem it{};
+    std::vector<uint8_t> qtab;
+    size_t slen = 0;
+    int rows = 0;                      // rows per launch
     hipStream_t st = nullptr;
+    uint8_t *d_tab = nullptr;          // QNBLIC tables
     std::vector<void *> bufs;
     ~IndexedRun() {
         if (st) hipStreamSynchronize(st);
@@ -2377,62 +2456,73 @@ struct IndexedRun {
     }
 };
 
-// A checked index's entry k (1-based: the entry in front of row k R), split into its parts
-struct EntryParts { const DecodeCheckpoint *head; const uint8_t *state, *b, *rows; };
-static EntryParts entry_parts(const IndexView &V, int k) {
-    const uint8_t *e = V.ent[size_t(k - 1)];
-    const size_t sb = dstream_state_bytes(V.H.kind), bb = stats_doubles(V.H.kind ? 0 : V.H.effort, V.H.w) * sizeof(double) / 2;
-    return EntryParts{reinterpret_cast<const DecodeCheckpoint *>(e), e + sizeof(DecodeCheckpoint), e + sizeof(DecodeCheckpoint) + sb,
-                      e + sizeof(DecodeCheckpoint) + sb + bb};
+// The host half of an indexed decode: the index against the stream, the stream's description.  false: refused.
+static bool indexed_check(IndexedRun &run, nblic_amd_ctx *c, const unsigned char *stream, size_t slen, const void *idx, size_t ilen) {
+    if (!c || !stream || index_check(idx, ilen, stream, slen, c->max_px, run.V) != 0) return false;
+    run.it = DecodeItem{0, 0, 0, 0, 0, 0, 0, 0, -1, -1};
+    if (describe_stream(stream, slen, false, c->max_px, run.it, run.qtab) != Described::ok) return false;
+    run.slen = slen;
+    run.rows = rows_per_launch(run.it, c->serial_rows);
+    return true;
 }
 
-// The state record a job starts from: the stream's start (segment 0) or entry k; the whole stream is in device memory.
-static void start_record(const IndexView &V, const DecodeItem &it, int k, size_t slen, uint8_t *rec) {
-    const size_t sb = dstream_state_bytes(it.kind);
+// The device half: the call's HIP stream, and the QNBLIC tables on the device.
+static bool indexed_begin(IndexedRun &run, nblic_amd_ctx *c) {
+    if (hipSetDevice(c->device) != hipSuccess) return false;
+    if (hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking) != hipSuccess) { run.st = nullptr; return false; }
+    if (!run.it.kind) return true;
+    run.d_tab = run.alloc<uint8_t>(kQTab);
+    return run.d_tab && hipMemcpyAsync(run.d_tab, run.qtab.data(), kQTab, hipMemcpyHostToDevice, run.st) == hipSuccess;
+}
+
+// Segment k of an indexed decode, set up on run.st: its job, the record it starts from -- the stream's start (k = 0) or
+// entry k, staged in `stage` (L.b host bytes that live until run.st is synchronised) -- zeroed statistics, and from
+// entry k its B and the two rows above row kR into the plane `recon` (recon_row0: the image row at its index 0).
+static bool segment_start(IndexedRun &run, int k, uint8_t *d_rec, double *d_stats, uint8_t *recon, int recon_row0, const uint8_t *d_stream,
+                          unsigned long long stream_off, int end_row, uint8_t *stage, SerialJob &J) {
+    const RecordLayout &L = run.V.L;
     SerialState S{};
     if (k > 0) {
-        memcpy(rec, entry_parts(V, k).state, sb);
-        memcpy(&S, rec, sizeof S);
+        memcpy(stage, run.V.body(k), L.b);
+        memcpy(&S, stage, sizeof S);
     } else {
-        memset(rec, 0, sb);
-        S.pos = it.kind ? (unsigned long long)(it.q_pos) * 2ull : (unsigned long long)(kHeaderBytes);
+        memset(stage, 0, L.b);
+        S.pos = first_pos(run.it);
     }
-    S.status = kRunning; S.avail = slen; S.final_ = 1;
-    memcpy(rec, &S, sizeof S);
-}
-
-// Parses the stream's header (QNBLIC: its tables) for an indexed decode; false: refused.
-static bool indexed_item(const unsigned char *stream, size_t slen, long max_px, DecodeItem &it, std::vector<uint8_t> &qtab) {
-    it = DecodeItem{0, 0, 0, 0, 0, 0, 0, slen, -1, -1};
-    if (!parse_stream_header(stream, slen, max_px, it)) return false;
-    if (it.kind == 0) return slen >= size_t(kHeaderBytes) + 4;
-    qtab.assign(kQTab, 0);
-    it.q_pos = q_parse_tables(stream, slen, qtab.data());
-    return it.q_pos >= 0 && size_t(it.q_pos) * 2 + 4 <= slen;
+    S.status = kRunning; S.avail = run.slen; S.final_ = 1;               // the whole stream is in device memory
+    memcpy(stage, &S, sizeof S);
+    J = decode_job(run.it, recon, recon_row0, d_stream, stream_off, reinterpret_cast<SerialState *>(d_rec), d_stats, run.d_tab, run.rows, end_row);
+    bool ok = hipMemcpyAsync(d_rec, stage, L.b, hipMemcpyHostToDevice, run.st) == hipSuccess;
+    if (d_stats) ok = ok && hipMemsetAsync(d_stats, 0, 2 * L.b_bytes, run.st) == hipSuccess;
+    if (k > 0) {
+        const uint8_t *E = run.V.body(k);
+        if (d_stats) ok = ok && hipMemcpyAsync(d_stats, E + L.b, L.b_bytes, hipMemcpyHostToDevice, run.st) == hipSuccess;
+        ok = ok && rows_above_in(recon, recon_row0, E + L.rows, k * run.V.H.every_rows, run.it.w, run.st);
+    }
+    return ok;
 }
 
 // Segment k of an indexed decode ends in front of entry k + 1's row; its final record, B and rows must be that entry.
 // The record's header fields and tables are compared except the rank -> symbol words (kRecRank): the lean decoder never
 // writes them back, and dstream_check has verified that the entry's are the inverse of its sym_at, which IS compared.
 static bool chain_matches(const IndexView &V, int k, const uint8_t *rec, const uint8_t *b, const uint8_t *plane) {
-    const EntryParts E = entry_parts(V, k + 1);
+    const uint8_t *E = V.body(k + 1);
     SerialState got, want;
-    memcpy(&got, rec, sizeof got); memcpy(&want, E.state, sizeof want);
+    memcpy(&got, rec, sizeof got); memcpy(&want, E, sizeof want);
     if (got.status != kRunning || got.next_row != want.next_row || got.pos != want.pos || got.lo != want.lo || got.bias != want.bias) return false;
     if (V.H.kind == 0 && (got.hi != want.hi || got.window != want.window)) return false;
-    const uint8_t *tg = rec + sizeof(SerialState), *tw = E.state + sizeof(SerialState);
-    const size_t tab = dstream_state_bytes(V.H.kind) - sizeof(SerialState);
+    const uint8_t *tg = rec + sizeof(SerialState), *tw = E + sizeof(SerialState);
+    const size_t tab = V.L.b - sizeof(SerialState);
     if (V.H.kind == 0) {
         const size_t rank0 = size_t(kRecRank) * 4, sym0 = size_t(kRecSym) * 4;
         if (memcmp(tg, tw, rank0) != 0 || memcmp(tg + sym0, tw + sym0, tab - sym0) != 0) return false;
     } else if (memcmp(tg, tw, tab) != 0) {
         return false;
     }
-    const size_t bb = stats_doubles(V.H.kind ? 0 : V.H.effort, V.H.w) * sizeof(double) / 2;
-    if (bb && memcmp(b, E.b, bb) != 0) return false;
+    if (V.L.b_bytes && memcmp(b, E + V.L.b, V.L.b_bytes) != 0) return false;
     const size_t w = size_t(V.H.w);
-    const int r = want.next_row, nr = r >= 2 ? 2 : r;
-    return memcmp(plane + size_t(r - nr) * w, E.rows + size_t(2 - nr) * w, size_t(nr) * w) == 0;
+    const RowsAbove A = rows_above(want.next_row, V.H.w);
+    return memcmp(plane + size_t(A.first) * w, E + V.L.rows + A.at, size_t(A.n) * w) == 0;
 }
 
 constexpr size_t kIndexedRoundBytes = size_t(1) << 30;   // device memory of one round's per-segment records and statistics
@@ -2441,36 +2531,26 @@ constexpr size_t kIndexedRoundBytes = size_t(1) << 30;   // device memory of one
 // CUs take the lean image), in rounds that bound the per-segment memory; the plane is copied out once, then the chain
 // check (chain_matches) refuses the result on any difference.  0 / -1.
 static int decode_indexed(nblic_amd_ctx *c, const unsigned char *stream, size_t slen, const void *idx, size_t ilen, unsigned char *img, size_t img_cap) {
-    if (!c || !stream || !img) return -1;
-    IndexView V;
-    if (index_check(idx, ilen, stream, slen, c->max_px, V) != 0) return -1;
-    DecodeItem it;
-    std::vector<uint8_t> qtab;
-    if (!indexed_item(stream, slen, c->max_px, it, qtab)) return -1;
-    const size_t w = size_t(it.w), plane_bytes = size_t(it.h) * w;
+    IndexedRun run;
+    if (!img || !indexed_check(run, c, stream, slen, idx, ilen)) return -1;
+    const DecodeItem &it = run.it;
+    const RecordLayout &L = run.V.L;
+    const size_t plane_bytes = size_t(it.h) * size_t(it.w);
     if (img_cap < plane_bytes) return -1;
-    if (hipSetDevice(c->device) != hipSuccess) return -1;
-    const int R = V.H.every_rows, nseg = V.H.count + 1;
-    const size_t sb = dstream_state_bytes(it.kind), rec_bytes = up256(sb);
-    const size_t stats_bytes = stats_doubles(it.kind ? 0 : it.effort, it.w) * sizeof(double), bb = stats_bytes / 2;
+    auto fail = [&](const char *what) { fprintf(stderr, "[nblic_amd] indexed decode: %s\n", what); return -1; };
+    if (!indexed_begin(run, c)) return fail("cannot set up the workspace");
+    const int R = run.V.H.every_rows, nseg = run.V.H.count + 1;
+    const size_t rec_bytes = up256(L.b), stats_bytes = 2 * L.b_bytes;
     const size_t per_seg = rec_bytes + up256(stats_bytes);
     int per_round = int(std::max<size_t>(1, std::min<size_t>(size_t(nseg), kIndexedRoundBytes / per_seg)));
     if (c->index_round_segments > 0) per_round = std::min(per_round, c->index_round_segments);
-    IndexedRun run;
-    if (hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking) != hipSuccess) { run.st = nullptr; return -1; }
-    uint8_t *d_stream = run.alloc<uint8_t>(up256(slen + 2048)), *d_plane = run.alloc<uint8_t>(plane_bytes);
+    uint8_t *d_stream = run.alloc<uint8_t>(stream_buf_bytes(slen)), *d_plane = run.alloc<uint8_t>(plane_bytes);
     uint8_t *d_recs = run.alloc<uint8_t>(size_t(per_round) * per_seg);
     SerialJob *d_jobs = run.alloc<SerialJob>(size_t(per_round) * sizeof(SerialJob));
-    uint8_t *d_tab = it.kind ? run.alloc<uint8_t>(kQTab) : nullptr;
-    auto fail = [&](const char *what) { fprintf(stderr, "[nblic_amd] indexed decode: %s\n", what); return -1; };
-    if (!d_stream || !d_plane || !d_recs || !d_jobs || (it.kind && !d_tab)) return fail("cannot allocate the workspace");
+    if (!d_stream || !d_plane || !d_recs || !d_jobs) return fail("cannot allocate the workspace");
     const hipStream_t st = run.st;
-    bool ok = hipMemsetAsync(d_stream + (slen & ~size_t(3)), 0, up256(slen + 2048) - (slen & ~size_t(3)), st) == hipSuccess &&
-              hipMemcpyAsync(d_stream, stream, slen, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (it.kind) ok = ok && hipMemcpyAsync(d_tab, qtab.data(), kQTab, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (!ok) return fail("upload");
-    const int rows_per_launch = serial_rows_per_launch(it.h, it.w, it.kind ? 1 : it.effort, c->serial_rows);
-    std::vector<uint8_t> host_recs(size_t(nseg) * sb), host_b(size_t(nseg) * bb), starts(size_t(per_round) * sb);
+    if (!upload_stream(d_stream, stream, slen, st)) return fail("upload");
+    std::vector<uint8_t> host_recs(size_t(nseg) * L.b), host_b(size_t(nseg) * L.b_bytes), stage(size_t(per_round) * L.b);
     std::vector<SerialJob> jobs(static_cast<size_t>(per_round));
     long launches_total = 0;
     // rounds from the last segments to the first: the rows above a segment (from its entry) are written into the plane
@@ -2479,28 +2559,12 @@ static int decode_indexed(nblic_amd_ctx *c, const unsigned char *stream, size_t 
         const int s0 = std::max(0, s1 - per_round), n = s1 - s0;
         int launches = 1;
         for (int k = s0; k < s1; k++) {
-            const int j = k - s0, r0 = k * R, r1 = k + 1 < nseg ? (k + 1) * R : it.h;
+            const int j = k - s0, r1 = k + 1 < nseg ? (k + 1) * R : it.h;
             uint8_t *rec = d_recs + size_t(j) * per_seg;
-            SerialJob &J = jobs[size_t(j)];
-            J = SerialJob{};
-            J.recon = d_plane; J.recon_row0 = 0;
-            J.stream = d_stream; J.stream_off = 0;
-            J.state = reinterpret_cast<SerialState *>(rec);
-            J.stats = stats_bytes ? reinterpret_cast<double *>(rec + rec_bytes) : nullptr;
-            J.h = it.h; J.w = it.w; J.near = it.near; J.k_step = it.k_step; J.effort = it.effort;
-            J.rows = rows_per_launch; J.end_row = r1 < it.h ? r1 : 0;
-            if (it.kind) { J.q_freq = reinterpret_cast<const uint32_t *>(d_tab); J.q_start = J.q_freq + 12 * 256; J.q_slot = nullptr; }
-            launches = std::max(launches, serial_launches(r1 - r0, rows_per_launch));
-            start_record(V, it, k, slen, starts.data() + size_t(j) * sb);
-            ok = hipMemcpyAsync(rec, starts.data() + size_t(j) * sb, sb, hipMemcpyHostToDevice, st) == hipSuccess;
-            if (stats_bytes) ok = ok && hipMemsetAsync(J.stats, 0, stats_bytes, st) == hipSuccess;
-            if (k > 0) {
-                const EntryParts E = entry_parts(V, k);
-                const int nr = r0 >= 2 ? 2 : r0;
-                if (bb) ok = ok && hipMemcpyAsync(J.stats, E.b, bb, hipMemcpyHostToDevice, st) == hipSuccess;
-                ok = ok && hipMemcpyAsync(d_plane + size_t(r0 - nr) * w, E.rows + size_t(2 - nr) * w, size_t(nr) * w, hipMemcpyHostToDevice, st) == hipSuccess;
-            }
-            if (!ok) return fail("upload");
+            double *stats = stats_bytes ? reinterpret_cast<double *>(rec + rec_bytes) : nullptr;
+            if (!segment_start(run, k, rec, stats, d_plane, 0, d_stream, 0, r1 < it.h ? r1 : 0, stage.data() + size_t(j) * L.b, jobs[size_t(j)]))
+                return fail("upload");
+            launches = std::max(launches, serial_launches(r1 - k * R, run.rows));
         }
         if (hipMemcpyAsync(d_jobs, jobs.data(), size_t(n) * sizeof(SerialJob), hipMemcpyHostToDevice, st) != hipSuccess) return fail("upload");
         for (int l = 0; l < launches; l++)
@@ -2508,11 +2572,11 @@ static int decode_indexed(nblic_amd_ctx *c, const unsigned char *stream, size_t 
         launches_total += launches;
         for (int k = s0; k < s1; k++) {
             const uint8_t *rec = d_recs + size_t(k - s0) * per_seg;
-            ok = hipMemcpyAsync(host_recs.data() + size_t(k) * sb, rec, sb, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (bb) ok = ok && hipMemcpyAsync(host_b.data() + size_t(k) * bb, rec + rec_bytes, bb, hipMemcpyDeviceToHost, st) == hipSuccess;
+            bool ok = hipMemcpyAsync(host_recs.data() + size_t(k) * L.b, rec, L.b, hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (L.b_bytes) ok = ok && hipMemcpyAsync(host_b.data() + size_t(k) * L.b_bytes, rec + rec_bytes, L.b_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
             if (!ok) return fail("state");
         }
-        if (hipStreamSynchronize(st) != hipSuccess) return fail("a round");       // `starts` and `jobs` are reused by the next round
+        if (hipStreamSynchronize(st) != hipSuccess) return fail("a round");       // `stage` and `jobs` are reused by the next round
         s1 = s0;
     }
     { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count += launches_total; }
@@ -2521,12 +2585,12 @@ static int decode_indexed(nblic_amd_ctx *c, const unsigned char *stream, size_t 
         return fail("plane");
     }
     for (int k = 0; k < nseg; k++) {
-        const uint8_t *rec = host_recs.data() + size_t(k) * sb;
+        const uint8_t *rec = host_recs.data() + size_t(k) * L.b;
         if (k + 1 == nseg) {
             SerialState S;
             memcpy(&S, rec, sizeof S);
             if (S.status != kDone) { memset(img, 0, plane_bytes); return fail("the stream is damaged or ends too early"); }
-        } else if (!chain_matches(V, k, rec, host_b.data() + size_t(k) * bb, img)) {
+        } else if (!chain_matches(run.V, k, rec, host_b.data() + size_t(k) * L.b_bytes, img)) {
             memset(img, 0, plane_bytes);                                 // nothing unverified is left in the caller's buffer
             return fail("a segment does not end where the next entry starts (index and stream disagree)");
         }
@@ -2534,57 +2598,36 @@ static int decode_indexed(nblic_amd_ctx *c, const unsigned char *stream, size_t 
     return 0;
 }
 
-// Rows [row0, row1) alone: one job from the last entry at or before row0 (the stream's start for row0 < R), fed from the
-// entry's feed_from, ending in front of row1.  Writes only out[0, (row1 - row0) w).  0 / -1.
+// Rows [row0, row1) alone: the one segment from the last entry at or before row0 (the stream's start for row0 < R), fed
+// from the entry's feed_from, ending in front of row1.  Writes only out[0, (row1 - row0) w).  0 / -1.
 static int decode_rows(nblic_amd_ctx *c, const unsigned char *stream, size_t slen, const void *idx, size_t ilen, int row0, int row1,
                        unsigned char *out, size_t cap) {
-    if (!c || !stream || !out) return -1;
-    IndexView V;
-    if (index_check(idx, ilen, stream, slen, c->max_px, V) != 0) return -1;
-    DecodeItem it;
-    std::vector<uint8_t> qtab;
-    if (!indexed_item(stream, slen, c->max_px, it, qtab)) return -1;
+    IndexedRun run;
+    if (!out || !indexed_check(run, c, stream, slen, idx, ilen)) return -1;
+    const DecodeItem &it = run.it;
     if (row0 < 0 || row1 <= row0 || row1 > it.h) return -1;
     const size_t w = size_t(it.w);
     if (cap < size_t(row1 - row0) * w) return -1;
-    if (hipSetDevice(c->device) != hipSuccess) return -1;
-    const int k = row0 / V.H.every_rows, r0 = k * V.H.every_rows, base = std::max(0, r0 - 2);
-    const unsigned long long off = k > 0 ? entry_parts(V, k).head->feed_from : 0;    // <= slen (index_check)
-    const size_t win = size_t(slen - off), sb = dstream_state_bytes(it.kind);
-    const size_t stats_bytes = stats_doubles(it.kind ? 0 : it.effort, it.w) * sizeof(double), bb = stats_bytes / 2;
-    IndexedRun run;
-    if (hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking) != hipSuccess) { run.st = nullptr; return -1; }
-    uint8_t *d_win = run.alloc<uint8_t>(up256(win + 2048)), *d_rows = run.alloc<uint8_t>(size_t(row1 - base) * w);
-    uint8_t *d_rec = run.alloc<uint8_t>(up256(sb));
+    auto fail = [&](const char *what) { fprintf(stderr, "[nblic_amd] row-range decode: %s\n", what); return -1; };
+    if (!indexed_begin(run, c)) return fail("cannot set up the workspace");
+    const int k = row0 / run.V.H.every_rows, r0 = k * run.V.H.every_rows, base = std::max(0, r0 - 2);
+    unsigned long long off = 0;
+    if (k > 0) {                                                         // <= slen (index_check)
+        DecodeCheckpoint E;
+        memcpy(&E, run.V.ent[size_t(k - 1)], sizeof E);
+        off = E.feed_from;
+    }
+    const size_t win = size_t(slen - off), stats_bytes = 2 * run.V.L.b_bytes;
+    uint8_t *d_win = run.alloc<uint8_t>(stream_buf_bytes(win)), *d_rows = run.alloc<uint8_t>(size_t(row1 - base) * w);
+    uint8_t *d_rec = run.alloc<uint8_t>(up256(run.V.L.b));
     double *d_stats = stats_bytes ? run.alloc<double>(stats_bytes) : nullptr;
     SerialJob *d_job = run.alloc<SerialJob>(sizeof(SerialJob));
-    uint8_t *d_tab = it.kind ? run.alloc<uint8_t>(kQTab) : nullptr;
-    auto fail = [&](const char *what) { fprintf(stderr, "[nblic_amd] row-range decode: %s\n", what); return -1; };
-    if (!d_win || !d_rows || !d_rec || !d_job || (stats_bytes && !d_stats) || (it.kind && !d_tab)) return fail("cannot allocate the workspace");
+    if (!d_win || !d_rows || !d_rec || !d_job || (stats_bytes && !d_stats)) return fail("cannot allocate the workspace");
     const hipStream_t st = run.st;
-    std::vector<uint8_t> start(sb);
-    start_record(V, it, k, slen, start.data());
-    SerialJob J{};
-    J.recon = d_rows; J.recon_row0 = base;
-    J.stream = d_win; J.stream_off = off;
-    J.state = reinterpret_cast<SerialState *>(d_rec); J.stats = d_stats;
-    J.h = it.h; J.w = it.w; J.near = it.near; J.k_step = it.k_step; J.effort = it.effort;
-    J.rows = serial_rows_per_launch(it.h, it.w, it.kind ? 1 : it.effort, c->serial_rows);
-    J.end_row = row1 < it.h ? row1 : 0;
-    if (it.kind) { J.q_freq = reinterpret_cast<const uint32_t *>(d_tab); J.q_start = J.q_freq + 12 * 256; J.q_slot = nullptr; }
-    bool ok = hipMemsetAsync(d_win + (win & ~size_t(3)), 0, up256(win + 2048) - (win & ~size_t(3)), st) == hipSuccess &&
-              hipMemcpyAsync(d_win, stream + off, win, hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(d_rec, start.data(), sb, hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(d_job, &J, sizeof J, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (stats_bytes) ok = ok && hipMemsetAsync(d_stats, 0, stats_bytes, st) == hipSuccess;
-    if (it.kind) ok = ok && hipMemcpyAsync(d_tab, qtab.data(), kQTab, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (k > 0) {
-        const EntryParts E = entry_parts(V, k);
-        const int nr = r0 - base;
-        if (bb) ok = ok && hipMemcpyAsync(d_stats, E.b, bb, hipMemcpyHostToDevice, st) == hipSuccess;
-        ok = ok && hipMemcpyAsync(d_rows, E.rows + size_t(2 - nr) * w, size_t(nr) * w, hipMemcpyHostToDevice, st) == hipSuccess;
-    }
-    if (!ok) return fail("upload");
+    std::vector<uint8_t> stage(run.V.L.b);
+    SerialJob J;
+    if (!upload_stream(d_win, stream + off, win, st) || !segment_start(run, k, d_rec, d_stats, d_rows, base, d_win, off, row1 < it.h ? row1 : 0, stage.data(), J) ||
+        hipMemcpyAsync(d_job, &J, sizeof J, hipMemcpyHostToDevice, st) != hipSuccess) return fail("upload");
     const int launches = serial_launches(row1 - r0, J.rows);
     for (int l = 0; l < launches; l++)
         if (!decode_launch(it, d_job, &J, 1, st, false)) return fail("launch");
@@ -2923,6 +2966,10 @@ size_t nblic_amd_stream_index(nblic_amd_stream *s, void *buf, size_t cap) { retu
 
 nblic_amd_dstream *nblic_amd_dstream_begin(nblic_amd_ctx *c, int band_rows) { return dstream_new(c, band_rows); }
 nblic_amd_dstream *nblic_amd_dstream_resume(nblic_amd_ctx *c, const void *checkpoint, size_t bytes) { return dstream_resume(c, checkpoint, bytes); }
+int nblic_amd_stream_check(nblic_amd_ctx *c, const void *checkpoint, size_t bytes) {
+    EncodeCheckpoint H;
+    return stream_check(checkpoint, bytes, c ? c->max_px : kMaxPixels, H);
+}
 int nblic_amd_dstream_check(nblic_amd_ctx *c, const void *checkpoint, size_t bytes) {
     DecodeCheckpoint H;
     return dstream_check(checkpoint, bytes, c ? c->max_px : kMaxPixels, H);
@@ -2957,7 +3004,7 @@ int nblic_amd_dstream_progress(nblic_amd_dstream *d, int *rows_done, unsigned lo
     if (device_bytes) *device_bytes = d->device_bytes;
     return (d->failed || d->refused) ? -1 : (d->done ? 1 : 0);
 }
-size_t nblic_amd_dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap) { return d ? dstream_checkpoint(d, buf, cap) : 0; }
+size_t nblic_amd_dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap) { return d ? dstream_checkpoint(d, buf, cap, d->band_rows, d->sha) : 0; }
 void nblic_amd_dstream_end(nblic_amd_dstream *d) { dstream_free(d); }
 
 void nblic_amd_set_index_round(nblic_amd_ctx *c, int segments) { if (c) c->index_round_segments = segments > 0 ? segments : 0; }

@@ -266,3 +266,81 @@ def test_lean_decoder_many_images_side_by_side(gpu_ctx, pkg, oracle):
             assert all(d is not None and np.array_equal(d[0], e[1]) for e, d in zip(enc, dec)), effort
     finally:
         ctx.close()
+
+
+def test_damaged_encoder_checkpoints_are_refused(gpu_ctx, pkg, oracle):
+    """The band encoder's checkpoint is sealed and checked on the host before a resume allocates anything (mirrors
+    test_band_decoder.py::test_damaged_checkpoints_and_streams_are_refused); the undamaged one resumes to the oracle's stream."""
+    img = inputs.syn1(20, 120, 5)
+    want = oracle.encode(img, 2, 2)[0]
+    st = gpu_ctx.stream(img, 2, 2, band_rows=5)
+    done, first = st.run(1e-9)                                      # the budget is spent after one band
+    assert not done
+    ck = st.checkpoint()
+    st.close()
+    assert gpu_ctx.check_encoder_checkpoint(ck) and pkg.check_encoder_checkpoint(ck)
+
+    def flip(b, at):
+        b = bytearray(b)
+        b[at] ^= 0x10
+        return bytes(b)
+
+    version_bumped = bytearray(ck)
+    version_bumped[8] += 1
+    version_bumped[-32:] = hashlib.sha256(bytes(version_bumped[:-32])).digest()     # a consistent checksum: the version alone refuses it
+    bad = {"header": flip(ck, 16), "body": flip(ck, len(ck) // 2), "checksum": flip(ck, len(ck) - 1),
+           "truncated": ck[:-1], "version": bytes(version_bumped), "empty": b"", "junk": bytes(len(ck)),
+           "NBLCKPT1": b"NBLCKPT1" + ck[8:]}
+    for name, b in bad.items():
+        assert not gpu_ctx.check_encoder_checkpoint(b), name
+        with pytest.raises(RuntimeError):
+            gpu_ctx.stream(img, 2, 2, checkpoint=b)
+    res = gpu_ctx.stream(img, 2, 2, checkpoint=ck)
+    done, rest = res.run()
+    assert done and first + rest == want
+    with pytest.raises(RuntimeError):                               # a finished encoder has nothing to resume
+        res.checkpoint()
+    res.close()
+
+
+def test_context_close_closes_its_band_streams(gpu_ctx, pkg):
+    """Context.close() ends the BandStreams it handed out; closing or dropping one afterwards touches nothing."""
+    img = inputs.syn1(16, 64, 3)
+    ctx = pkg.Context(device=0, n_slots=2, n_coders=1)              # two groups: one per open stream
+    st = ctx.stream(img, 0, 1, band_rows=4)
+    dropped = ctx.stream(img, 1, 2, band_rows=4)
+    assert not st.run(1e-9)[0]
+    ctx.close()
+    assert st.handle is None and dropped.handle is None
+    st.close()
+    del dropped, st
+
+
+def test_dropped_band_streams_give_their_group_back(gpu_ctx, pkg):
+    """A BandStream holds one of the context's groups while it lives.  Streams the caller drops unclosed -- more of them
+    than the context has groups -- are freed at once, so the next stream and a batch encode still find a group."""
+    import threading
+    img = inputs.syn1(16, 64, 4)
+    ctx = pkg.Context(device=0, n_slots=2, n_coders=1)              # two groups
+    result = {}
+
+    def work():
+        try:
+            for _ in range(5):
+                st = ctx.stream(img, 0, 1, band_rows=4)
+                assert not st.run(1e-9)[0]
+                del st                                              # dropped, never closed
+            st = ctx.stream(img, 0, 1, band_rows=4)
+            result["finished"] = st.run()[0]
+            st.close()
+            result["batch"] = ctx.encode_batch([img])[0]
+        except Exception as e:                                      # reported below
+            result["error"] = repr(e)
+
+    t = threading.Thread(target=work, daemon=True)
+    t.start()
+    t.join(120)
+    assert not t.is_alive(), "a dropped BandStream kept its group: the next one waits for ever"
+    ctx.close()
+    assert "error" not in result, result.get("error")
+    assert result["finished"] and len(result["batch"]) > 16
