@@ -9,7 +9,13 @@ feed would be -- step k+1 is handed to the pipeline (nblic_amd_encode_batch_begi
 collected -- and every one of the K timed steps is complete before the closing barrier; use
 --no-overlap-steps to collect each step before submitting the next.  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps, the dump if asked
+for, the line (with what the timed steps' own counters and stage timers say).  --full adds everything else, all
+of it after the timed steps: the bit-exact checks of what was timed (golden hash, every step against the first,
+frames against the CPU encoder; exit status 3 on a mismatch), the single-thread CPU baseline, and the extra legs
+(every stage timed, one group alone, the 8-frame batch, one frame, the H2D-inclusive rate).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 """
 import argparse
 import hashlib
@@ -19,6 +25,7 @@ import os
 import sys
 import time
 
+T_START = time.perf_counter()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 # The pipeline keeps 6 group streams + 8 copy streams + 1 serial-engine stream busy; the HIP runtime
@@ -277,13 +284,15 @@ def main():
                                                                  "(default: measured on MI355X a lane codes ~7 Mbins/s, a pack of 64 4096^2 frames takes ~11 s and its kernel stalls the streams that share its hardware queue: 5.4 -> 2.9 Gpx/s with one pack, DESIGN.md section 4)")
     ap.add_argument("--steps-in-flight", type=int, default=0, help="steps submitted ahead of the one being collected (0 = 4 with the device coder, else 2)")
     ap.add_argument("--device-min-outstanding", type=int, default=-1, help="images that must be unfinished for the device coder to take a pack (-1 = 2.8 x batch: its seconds of latency never become the tail of the run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also check what was timed bit for bit, time the CPU baseline and run the extra legs "
+                                                        "(off: set-up, warm-up, timed steps, dump, line, and nothing else)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline, and no frames checked against the CPU encoder")
     ap.add_argument("--stage-timing", choices=("roofline", "all", "off"), default="roofline",
                     help="HIP events around k_touch_scatter and k_predict only (default), around every stage, or none")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) for real runs; gloo lets the N>1 path be rehearsed with every rank on one GPU")
     ap.add_argument("--node-gpus", type=int, default=8, help="GPUs the host is shared between: a rank confines itself (threads and all) to 1/NODE_GPUS of the host's cores, both SMT siblings of each; 0 = no confinement")
     ap.add_argument("--launch-check", action="store_true", help="no GPU work: every rank joins a gloo group, rank 0 prints how many ranks it saw (tests the --gpus N launcher on a CPU-only box)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the extra measurements (single frame, 8-frame batch, the H2D-inclusive leg, the all-stage timing passes)")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the extra measurements (single frame, 8-frame batch, the H2D-inclusive leg, the all-stage timing passes)")
     ap.add_argument("--effort", type=int, choices=(0, 1), default=1, help="1: the graded -n0 -e1 path (BASELINE config 2); 0: QNBLIC (config 1's mode) on the same frames, one synchronous batch call per step")
     ap.add_argument("--h2d-steps", type=int, default=10, help="timed steps of the H2D-inclusive leg (SURVEY 8(d): >= 10 after >= 3 warm-ups); 0 skips it")
     ap.add_argument("--h2d-warmup", type=int, default=3)
@@ -479,13 +488,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    t_setup = time.perf_counter()
     run(args.warmup)
     del all_lens[:]
     fence()
     t0 = time.perf_counter()
     run(args.steps)
     fence()
-    dt = time.perf_counter() - t0
+    t1 = time.perf_counter()
+    dt = t1 - t0
     step_median_ms, step_min_ms = step_stats(t0)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=comm_dev)
@@ -530,7 +541,7 @@ def main():
     timed_per_launch = {k: v / timed_launches for k, v in timed_stage.items() if k != "host_gap" and v > 0}
 
     gathered_ok = None
-    if world > 1 and rank == 0:
+    if args.full and world > 1 and rank == 0:
         payloads, lens_all = last["gathered"]             # the step's last exchange (frames gathered_first ..)
         k0 = last["gathered_first"]
         gathered_ok = (len(payloads) == world and all(int(l.sum()) == p.numel() for p, l in zip(payloads, lens_all)) and
@@ -539,7 +550,7 @@ def main():
 
     # ---- correctness of what was timed (outside the timed region; before the extra legs reuse the buffers) --------
     bit_exact, checks = None, {}
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             with open(os.path.join(ROOT, "tests", "golden", "manifest.json")) as f:
                 m = json.load(f)["large"].get(f"syn1s1_{H}x{W}_n0_e1" if args.effort else f"syn1s1_{H}x{W}_q0")
@@ -557,7 +568,7 @@ def main():
                 same = same and all(bool(torch.equal(slabs[0][k, :n], sl[k, :n])) for sl in slabs[1:])
             checks[f"last_{in_flight}_steps_identical"] = same
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, ref_streams, enc = cpu_baseline(frames, args.effort)
         ok = [ref_streams[k] == last["outs"][k][: int(lens[k])].tobytes() for k in range(len(ref_streams))]
         spread = [k for k in sorted({(B * j) // 16 + (j % 16) for j in range(1, 16)}) if len(ref_streams) <= k < B]   # other packs, other lanes
@@ -566,12 +577,13 @@ def main():
         checks["frames_vs_cpu_encoder"] = f"{sum(ok)}/{len(ok)}"
         checks["frames_checked"] = list(range(len(ref_streams))) + spread
         checks["all_frames_vs_cpu_ok"] = all(ok)
-    if rank == 0:
+    if args.full and rank == 0:
         bit_exact = all(v for k, v in checks.items() if isinstance(v, bool))
 
     # ---- extra legs (outside the headline's region): the H2D-inclusive rate under the same protocol, every stage timed
     # under load and alone, one frame alone, the 8-frame batch north_star names ----------------------------------------
     extra = {}
+    extra_legs = args.full and not args.no_extra_legs
     all_per_launch, alone_per_launch = {}, {}
 
     def timed_call(fn):
@@ -585,7 +597,7 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             d = float(tt.item())
         return d
-    if not args.no_extra_legs and args.effort == 1:
+    if extra_legs and args.effort == 1:
         # every one of the 31 stages timed in THIS run: two overlapped steps under the same six-group concurrency as the
         # headline (thirty-two events per group launch cost ~2 %, which is why the timed region carries only two stages) ...
         ctx.enable_timing(1)
@@ -601,7 +613,7 @@ def main():
         alone_per_launch = {k: v / ln for k, v in st.items() if k != "host_gap"}
         extra["frames_per_launch_alone"] = n_alone / ln
         ctx.enable_timing(0)
-    if not args.no_extra_legs:
+    if extra_legs:
         one = max(1, 8 // world)                                     # 8 frames over the whole job: 8 / N per GPU
         enc_some = (lambda k: ctx.qencode_ptrs(ptrs[:k], shapes[:k], not args.host_inputs, outs16[0][:k])) if args.effort == 0 else \
                    (lambda k: ctx.encode_ptrs(ptrs[:k], shapes[:k], not args.host_inputs, outs[:k]))
@@ -613,7 +625,7 @@ def main():
             d1 = sorted(timed_call(lambda: enc_some(1)) for _ in range(13))[:-3]     # 13 repetitions, the three slowest (warm-up) dropped
             extra["single_frame_ms"] = round(d1[len(d1) // 2] * 1e3, 2)
             extra["single_frame"] = {"median_ms": round(d1[len(d1) // 2] * 1e3, 2), "min_ms": round(d1[0] * 1e3, 2), "repetitions": len(d1)}
-    if not args.no_extra_legs and world == 1 and not args.host_inputs and args.h2d_steps > 0 and args.effort == 1:
+    if extra_legs and world == 1 and not args.host_inputs and args.h2d_steps > 0 and args.effort == 1:
         # SURVEY 8(d)'s quantity: input in (pinned) host memory, every frame uploaded over PCIe INSIDE the region, same
         # protocol as the headline: warm-up steps, then K timed steps submitted back to back, barrier to barrier
         hslab = torch.empty((B, H * W), dtype=torch.uint8, pin_memory=True)
@@ -664,7 +676,7 @@ def main():
                        "device_coder_pack_threads": dev_packs,
                        "parallelism": f"image-per-GPU x{world}, RCCL gather of streams" if world > 1 else "single GPU",
                        "host": dict(host_description(), cpu_slice=share_how, pinned_host_memory=pinned)},
-            "bit_exact": bit_exact, "bit_exact_checks": checks, "gathered_ok": gathered_ok,
+            **({"bit_exact": bit_exact, "bit_exact_checks": checks, "gathered_ok": gathered_ok} if args.full else {}),
             "bits_per_pixel": round(8.0 * float(np.mean(lens)) / (H * W), 4),
         }
         if args.effort:
@@ -698,13 +710,15 @@ def main():
             line["cpu_baseline"] = cpu
             line["speedup_vs_cpu_baseline"] = round(value / cpu["value"], 2)
         print(json.dumps(line), flush=True)
-        if bit_exact is False:
-            print("[bench] a stream differs from the CPU encoder / golden hash / previous step", file=sys.stderr)
-            ctx.close()
-            sys.exit(3)
     ctx.close()
     if world > 1:
         dist.destroy_process_group()
+    if rank == 0:
+        print(f"[bench] wall clock: set-up {t_setup - T_START:.1f} s, warm-up {t0 - t_setup:.1f} s, timed steps {t1 - t0:.1f} s, "
+              f"after them {time.perf_counter() - t1:.1f} s" + ("" if args.full else " (--full adds the checks, the CPU baseline and the extra legs)"), file=sys.stderr)
+    if bit_exact is False:
+        print("[bench] a stream differs from the CPU encoder / golden hash / previous step", file=sys.stderr)
+        sys.exit(3)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,7 @@
 """bench.py --dump-outputs: the last timed step's streams as .npy files (a fixed, seeded sample under 64 MB), and a
 result line whose step count and ms_per_step describe the timed region.  The CPU test pins the file format; the
--m gpu test runs the bench at a small size and checks the dump against the oracle's streams of the same frames."""
+-m gpu tests run the bench at a small size, plain and with --full, and check the dump against the oracle's streams
+of the same frames."""
 import json
 import os
 import subprocess
@@ -55,12 +56,37 @@ def test_bench_steps_and_dumped_streams(pkg, oracle, tmp_path):
     steps, batch, h, w = 3, 4, 512, 512
     dump = tmp_path / "dump"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
-                        "--batch", str(batch), "--height", str(h), "--width", str(w), "--no-extra-legs", "--no-cpu-baseline",
+                        "--batch", str(batch), "--height", str(h), "--width", str(w), "--full", "--no-extra-legs", "--no-cpu-baseline",
                         "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["steps"] == steps and line["bit_exact"] is True, line
     assert line["ms_per_step"] > 0 and line["bit_exact_checks"]["every_step_same_lengths"] is True
+    streams = [np.frombuffer(oracle.encode(pkg.syn1(h, w, seed=k + 1), 0, 1)[0], np.uint8) for k in range(batch)]
+    want = tmp_path / "want"
+    bench.dump_outputs(str(want), [len(s) for s in streams], streams)
+    for name in ("stream_lengths.npy", "stream_bytes.npy"):
+        assert np.array_equal(np.load(dump / name), np.load(want / name)), name
+
+
+@pytest.mark.gpu
+def test_plain_bench_runs_only_the_headline(pkg, oracle, tmp_path):
+    """Without --full the bench sets up, warms up, times its steps, dumps and prints the line, and nothing else: the
+    line's value and ms_per_step describe the timed steps, it carries no checks, CPU baseline or extra legs, and the
+    dump is still the oracle's streams of the same seeded frames."""
+    steps, batch, h, w = 2, 3, 256, 384
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                        "--batch", str(batch), "--height", str(h), "--width", str(w), "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == steps and line["warmup"] == 1 and line["ms_per_step"] > 0, line
+    assert line["unit"] == "Mpixel/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert line["value"] == pytest.approx(batch * h * w / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+    for moved in ("bit_exact", "bit_exact_checks", "gathered_ok", "cpu_baseline", "batch8_Mpixel_per_s", "single_frame_ms",
+                  "value_h2d_inclusive"):
+        assert moved not in line, moved
     streams = [np.frombuffer(oracle.encode(pkg.syn1(h, w, seed=k + 1), 0, 1)[0], np.uint8) for k in range(batch)]
     want = tmp_path / "want"
     bench.dump_outputs(str(want), [len(s) for s in streams], streams)

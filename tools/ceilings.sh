@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/$1
 mkdir -p $OUT
-COMMON="--steps 8 --warmup 2 --no-extra-legs --no-cpu-baseline"
+COMMON="--steps 8 --warmup 2 --full --no-extra-legs --no-cpu-baseline"
 NBLIC_AMD_DBG=16 python3 $R/bench.py $COMMON > $OUT/device_side_only.json 2> $OUT/device_side_only.err
 NBLIC_AMD_DBG=128 python3 $R/bench.py $COMMON > $OUT/no_coding.json 2> $OUT/no_coding.err
 python3 $R/bench.py $COMMON > $OUT/plain8.json 2> $OUT/plain8.err
