@@ -161,6 +161,23 @@ void nblic_amd_set_max_pixels(nblic_amd_ctx *ctx, long max_pixels);
 void nblic_amd_set_serial_rows(nblic_amd_ctx *ctx, int rows);
 long nblic_amd_serial_launches(nblic_amd_ctx *ctx);
 
+/* Efforts 2 / 3 carry the reference's int64 least squares in doubles and redo a pixel with plain 64-bit integers when
+ * one of its two systems leaves the range in which the doubles are exact.  counts[0] / counts[1]: the pixels
+ * whose system 0 / system 1 did, over every encode and decode of the context since it was created or last reset
+ * (reset != 0 clears the pair after reading it; 64-bit counters; a decoder launch that is thrown away and run again
+ * because it ran dry inside a row adds nothing).  Reporting and tests: hard-edged content (text, charts) coded
+ * near-lossless reaches the redo, photographs practically never.  ctx == NULL addresses the context behind the drop-in
+ * entry points.  Call it between batches.  Returns 0, or -1.                                                       */
+int nblic_amd_lsq_redo_counts(nblic_amd_ctx *ctx, unsigned long long counts[2], int reset);
+
+/* Which variant of the serial kernels a launch of `images` images of one effort (1..3), the widest `width` pixels wide,
+ * gets -- decided by the very functions the launchers go by (reporting, tests; no device needed).  decode == 0: the
+ * model stage of an encode; decode != 0: the NBLIC decoder (whole_streams: every stream is there in full, as in
+ * nblic_amd_decode_batch).  Bits: 1 = two waves per image (effort-3 encodes of few images), 2 = the lean decoder image
+ * (many streams side by side), 4 = the rows of the widest image are kept in LDS (otherwise its taps come from memory).
+ * Returns -1 for arguments out of range.                                                                             */
+int nblic_amd_serial_plan(int decode, int effort, int images, int width, int whole_streams);
+
 /* ONE image of any mode, worked through in ROW BANDS (src/NBLIC.c:749-908 is one loop over the rows; every piece of
  * state it carries from row to row is small).  Per band: the model stage for the band's rows, the entropy stages for
  * those pixels (their adaptive tables carried from band to band), the band's bins through the range coder.  The device
@@ -366,6 +383,19 @@ int nblic_amd_write_gray(const char *path, const unsigned char *px, int h, int w
 /* Device self-test of the serial kernels' arithmetic: the double-carried truncating divisions of the
  * least-squares predictor against 64-bit integer division on 65536 operand triples.  0 = pass.   */
 int nblic_amd_serial_selftest(nblic_amd_ctx *ctx);
+
+/* Test entry point: both least-squares solvers of the serial kernels on `count` given systems, no image and no coder.
+ * stats: count x (1 + n + n*n) integer-valued statistics [s | b | A]; regressors: count x 10; bias: per item the
+ * regularisation strength the pixel starts from (its two systems are regularised with the pair around it).  n = 6
+ * (effort 2) or 10 (effort 3); waves = 2 (n = 10) runs the two-wave kernel's hand-over of system 1.  Per item
+ *   out_f64[12]: double path -- clamped Q12 prediction of system 0, 1; largest product, entry, quotient, pivot of
+ *                system 0; the same of system 1;
+ *   out_i64[14]: what the kernels deliver for the pixel -- p1, p2, ok1, ok2; the double path's ok of system 0, 1 and
+ *                whether its magnitudes stayed in the exact range (0, 1); the integer path's raw Q12 sum of system 0, 1
+ *                and its ok (0, 1); the redo counts the item raised (0, 1).
+ * Both paths are always computed.  Returns 0, or -1.                                                           */
+int nblic_amd_lsq_probe(nblic_amd_ctx *ctx, int n, int waves, int count, const double *stats, const signed char *regressors, const int *bias,
+                        double *out_f64, long long *out_i64);
 
 const char *nblic_amd_version(void);
 

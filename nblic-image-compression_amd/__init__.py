@@ -39,7 +39,7 @@ EXPORTS = (
     "nblic_amd_create", "nblic_amd_create_ex", "nblic_amd_destroy", "nblic_amd_encode_batch", "nblic_amd_encode_batch_begin", "nblic_amd_encode_batch_end", "nblic_amd_qencode_batch", "nblic_amd_set_max_pixels",
     "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage",
     "nblic_amd_encode_batch_modes", "nblic_amd_decode_batch", "nblic_amd_serial_selftest",
-    "nblic_amd_set_serial_rows", "nblic_amd_serial_launches", "nblic_amd_set_feed_chunk", "nblic_amd_last_fed_bytes",
+    "nblic_amd_set_serial_rows", "nblic_amd_serial_launches", "nblic_amd_lsq_redo_counts", "nblic_amd_serial_plan", "nblic_amd_lsq_probe", "nblic_amd_set_feed_chunk", "nblic_amd_last_fed_bytes",
     "nblic_amd_stream_begin", "nblic_amd_stream_resume", "nblic_amd_stream_run", "nblic_amd_stream_checkpoint", "nblic_amd_stream_progress",
     "nblic_amd_stream_recon", "nblic_amd_stream_end", "nblic_amd_stream_check",
     "nblic_amd_dstream_begin", "nblic_amd_dstream_resume", "nblic_amd_dstream_check", "nblic_amd_dstream_feed", "nblic_amd_dstream_info",
@@ -127,6 +127,13 @@ def load_library() -> C.CDLL:
     lib.nblic_amd_set_serial_rows.argtypes = [C.c_void_p, C.c_int]
     lib.nblic_amd_serial_launches.restype = C.c_long
     lib.nblic_amd_serial_launches.argtypes = [C.c_void_p]
+    lib.nblic_amd_lsq_redo_counts.restype = C.c_int
+    lib.nblic_amd_lsq_redo_counts.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
+    lib.nblic_amd_serial_plan.restype = C.c_int
+    lib.nblic_amd_serial_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.nblic_amd_lsq_probe.restype = C.c_int
+    lib.nblic_amd_lsq_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int8), ip,
+                                        C.POINTER(C.c_double), C.POINTER(C.c_longlong)]
     lib.nblic_amd_set_feed_chunk.restype = None
     lib.nblic_amd_set_feed_chunk.argtypes = [C.c_void_p, C.c_size_t]
     lib.nblic_amd_last_fed_bytes.restype = C.c_long
@@ -260,6 +267,29 @@ def set_default_serial_rows(rows: int) -> None:
 
 def default_serial_launches() -> int:
     return int(load_library().nblic_amd_serial_launches(None))
+
+
+def _lsq_redo_counts(handle, reset: bool) -> Tuple[int, int]:
+    v = (C.c_ulonglong * 2)()
+    if load_library().nblic_amd_lsq_redo_counts(handle, v, int(reset)) != 0:
+        raise RuntimeError("nblic_amd_lsq_redo_counts failed")
+    return int(v[0]), int(v[1])
+
+
+def default_lsq_redo_counts(reset: bool = False) -> Tuple[int, int]:
+    """Pixels whose least-squares system 0 / 1 was redone with integers by the drop-in entry points' context."""
+    return _lsq_redo_counts(None, reset)
+
+
+PLAN_TWO_WAVES, PLAN_LEAN, PLAN_ROWS_IN_LDS = 1, 2, 4
+
+
+def serial_plan(decode: bool, effort: int, images: int, width: int, whole_streams: bool = True) -> int:
+    """The serial kernel variant a launch gets (``nblic_amd_serial_plan``): PLAN_* bits.  Needs no device."""
+    r = load_library().nblic_amd_serial_plan(int(decode), effort, images, width, int(whole_streams))
+    if r < 0:
+        raise ValueError("serial_plan: arguments out of range")
+    return r
 
 
 def last_fed_bytes() -> int:
@@ -555,6 +585,27 @@ class Context:
 
     def serial_launches(self) -> int:
         return int(self.lib.nblic_amd_serial_launches(self.handle))
+
+    def lsq_redo_counts(self, reset: bool = False) -> Tuple[int, int]:
+        """Pixels (efforts 2 / 3) whose least-squares system 0 / 1 left the exact range of the doubles and was redone with
+        64-bit integers, over the context's encodes and decodes since it was created or last reset (reset=True clears the pair after reading)."""
+        return _lsq_redo_counts(self.handle, reset)
+
+    def lsq_probe(self, n: int, waves: int, stats: np.ndarray, regressors: np.ndarray, bias: np.ndarray):
+        """Test entry point (include/nblic_amd.h nblic_amd_lsq_probe): both least-squares solvers on given systems.
+        stats (K, 1 + n + n*n) float64 holding integers, regressors (K, 10) int8, bias (K,) int32 -> (K, 12) float64, (K, 14) int64."""
+        stats = np.ascontiguousarray(stats, np.float64)
+        regressors = np.ascontiguousarray(regressors, np.int8)
+        bias = np.ascontiguousarray(bias, np.int32)
+        k = int(bias.shape[0])
+        assert stats.shape == (k, 1 + n + n * n) and regressors.shape == (k, 10)
+        of, oi = np.zeros((k, 12), np.float64), np.zeros((k, 14), np.int64)
+        rc = self.lib.nblic_amd_lsq_probe(self.handle, n, waves, k, stats.ctypes.data_as(C.POINTER(C.c_double)),
+                                          regressors.ctypes.data_as(C.POINTER(C.c_int8)), bias.ctypes.data_as(C.POINTER(C.c_int)),
+                                          of.ctypes.data_as(C.POINTER(C.c_double)), oi.ctypes.data_as(C.POINTER(C.c_longlong)))
+        if rc != 0:
+            raise RuntimeError("nblic_amd_lsq_probe failed")
+        return of, oi
 
     def encode_ptrs(self, ptrs: Sequence[int], shapes: Sequence[Tuple[int, int]], on_device: bool,
                     outs: Optional[List[np.ndarray]] = None) -> Tuple[List[np.ndarray], np.ndarray]:

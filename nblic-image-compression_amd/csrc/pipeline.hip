@@ -289,6 +289,7 @@ struct nblic_amd_ctx {
     SerialJob *dec_jobs = nullptr; int dec_jobs_cap = 0;
     int index_round_segments = 0;         // > 0: at most this many segments per round of decode_indexed (nblic_amd_set_index_round)
     int serial_rows = 0;                  // rows per launch of the serial kernels; 0 = sized for a few seconds per launch (nblic_amd_set_serial_rows)
+    unsigned long long *d_redo = nullptr;       // device: pixels whose least-squares system 0 / 1 was redone with integers (SerialJob::redo of every job of the context)
     long serial_launch_count = 0;         // launches of the serial model / decode kernels since the context was created (reporting, tests)
     size_t feed_chunk = size_t(1) << 20;  // bytes per step in which the drop-in decoders fetch a stream of unknown length (nblic_amd_set_feed_chunk)
     long fed_bytes = 0;                   // bytes the last drop-in decode read from the caller's stream
@@ -420,7 +421,7 @@ static bool launch_front_serial(nblic_amd_ctx *c, Group &g, const uint8_t *const
         Q = SerialJob{};
         Q.img = s.b.img; Q.recon = want_recon ? s.d_recon : nullptr; Q.rec1 = s.b.rec1; Q.pxs = s.b.pxs; Q.stats = s.d_stats;
         Q.h = s.h; Q.w = s.w; Q.near = s.near; Q.k_step = J.k_step; Q.effort = s.effort;
-        Q.state = s.d_state; Q.rows = serial_rows_per_launch(s.h, s.w, s.effort, c->serial_rows);
+        Q.state = s.d_state; Q.rows = serial_rows_per_launch(s.h, s.w, s.effort, c->serial_rows); Q.redo = c->d_redo;
         HIP_OK(hipMemsetAsync(s.d_state, 0, sizeof(SerialState), g.stream));               // a fresh image: row 0, running
     }
     HIP_OK(hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(g.n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, g.stream));
@@ -1292,8 +1293,9 @@ static Described describe_stream(const unsigned char *p, size_t len, bool partia
 // The decode job of an item.  The buffers are the driver's: the plane (recon; recon_row0 the image row at its index 0),
 // the stream (stream_off its absolute offset), the state record, the statistics, the QNBLIC tables; end_row 0 = h.
 static SerialJob decode_job(const DecodeItem &it, uint8_t *recon, int recon_row0, const uint8_t *stream, unsigned long long stream_off,
-                            SerialState *state, double *stats, const uint8_t *tab, int rows, int end_row) {
+                            SerialState *state, double *stats, const uint8_t *tab, int rows, int end_row, unsigned long long *redo) {
     SerialJob J{};
+    J.redo = redo;
     J.recon = recon; J.recon_row0 = recon_row0;
     J.stream = stream; J.stream_off = stream_off;
     J.state = state; J.stats = stats;
@@ -1458,7 +1460,7 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         double *stats = sb ? reinterpret_cast<double *>(c->dec_arena + off) : nullptr; off += up256(sb);
         SerialState *state = reinterpret_cast<SerialState *>(c->dec_arena + off); off += up256(record_state_bytes(it.kind));
         if (it.kind == 1) { d_tabs[size_t(i)] = c->dec_arena + off; off += up256(kQTab); }
-        jobs[size_t(i)] = decode_job(it, recon, 0, d_streams[size_t(i)], 0, state, stats, d_tabs[size_t(i)], rows_per_launch(it, c->serial_rows), 0);
+        jobs[size_t(i)] = decode_job(it, recon, 0, d_streams[size_t(i)], 0, state, stats, d_tabs[size_t(i)], rows_per_launch(it, c->serial_rows), 0, c->d_redo);
         SerialState &H = heads[size_t(i)];
         H = SerialState{};
         H.pos = first_pos(it); H.avail = it.len; H.final_ = 1;
@@ -1708,7 +1710,7 @@ static void stream_band_jobs(nblic_amd_stream *s, Group &g, int i0, int rows, ui
     SerialJob &Q = g.h_sjobs[0];
     Q = SerialJob{};
     Q.img = s->d_img; Q.recon = s->d_recon; Q.rec1 = sl.b.rec1; Q.pxs = sl.b.pxs; Q.stats = s->d_stats; Q.state = sl.d_state;
-    Q.h = s->h; Q.w = s->w; Q.near = s->near; Q.k_step = s->k_step; Q.effort = s->effort; Q.rows = rows; Q.out_row0 = i0;
+    Q.h = s->h; Q.w = s->w; Q.near = s->near; Q.k_step = s->k_step; Q.effort = s->effort; Q.rows = rows; Q.out_row0 = i0; Q.redo = g.ctx->d_redo;
 }
 
 static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8_t *out, const uint8_t *end, uint32_t lo, uint32_t hi);
@@ -2038,7 +2040,7 @@ static int dstream_run(nblic_amd_dstream *d, double budget_s, unsigned char *row
         if ((written + size_t(rows)) * w > cap) return report(0);                 // rows_out is full
         if (!dstream_fill_window(d)) return fail("stream window");
         const bool final_ = d->complete && dstream_window_holds_all_fed(d);
-        const SerialJob J = decode_job(it, d->d_rows, d->row0, d->d_win, d->win_off, d->d_state, d->d_stats, d->d_tab, rows, 0);
+        const SerialJob J = decode_job(it, d->d_rows, d->row0, d->d_win, d->win_off, d->d_state, d->d_stats, d->d_tab, rows, 0, d->c->d_redo);
         SerialState S = d->H;
         S.avail = d->win_off + d->win_len; S.final_ = final_ ? 1 : 0; S.status = kRunning;
         if (d->d_snap && hipMemcpyAsync(d->d_snap, d->d_stats, d->stats_bytes / 2, hipMemcpyDeviceToDevice, d->st) != hipSuccess) return fail("snapshot");
@@ -2439,6 +2441,7 @@ struct IndexedRun {
     std::vector<uint8_t> qtab;
     size_t slen = 0;
     int rows = 0;                      // rows per launch
+    unsigned long long *redo = nullptr; // the context's redo counters (SerialJob::redo)
     hipStream_t st = nullptr;
     uint8_t *d_tab = nullptr;          // QNBLIC tables
     std::vector<void *> bufs;
@@ -2463,6 +2466,7 @@ static bool indexed_check(IndexedRun &run, nblic_amd_ctx *c, const unsigned char
     if (describe_stream(stream, slen, false, c->max_px, run.it, run.qtab) != Described::ok) return false;
     run.slen = slen;
     run.rows = rows_per_launch(run.it, c->serial_rows);
+    run.redo = c->d_redo;
     return true;
 }
 
@@ -2491,7 +2495,7 @@ static bool segment_start(IndexedRun &run, int k, uint8_t *d_rec, double *d_stat
     }
     S.status = kRunning; S.avail = run.slen; S.final_ = 1;               // the whole stream is in device memory
     memcpy(stage, &S, sizeof S);
-    J = decode_job(run.it, recon, recon_row0, d_stream, stream_off, reinterpret_cast<SerialState *>(d_rec), d_stats, run.d_tab, run.rows, end_row);
+    J = decode_job(run.it, recon, recon_row0, d_stream, stream_off, reinterpret_cast<SerialState *>(d_rec), d_stats, run.d_tab, run.rows, end_row, run.redo);
     bool ok = hipMemcpyAsync(d_rec, stage, L.b, hipMemcpyHostToDevice, run.st) == hipSuccess;
     if (d_stats) ok = ok && hipMemsetAsync(d_stats, 0, 2 * L.b_bytes, run.st) == hipSuccess;
     if (k > 0) {
@@ -2764,6 +2768,7 @@ nblic_amd_ctx *nblic_amd_create_ex(int device, int n_groups, int group_size, int
     c->cbufs.resize(size_t(n_host_buffers));
     for (int i = 0; i < n_host_buffers; i++) c->free_cbufs.push_back(i);
     if (hipStreamCreateWithFlags(&c->dec_stream, hipStreamNonBlocking) != hipSuccess) { c->dec_stream = nullptr; nblic_amd_destroy(c); return nullptr; }
+    if (hipMalloc((void **)&c->d_redo, 2 * sizeof(unsigned long long)) != hipSuccess || hipMemset(c->d_redo, 0, 2 * sizeof(unsigned long long)) != hipSuccess) { nblic_amd_destroy(c); return nullptr; }
     if (hipStreamCreateWithFlags(&c->dec_stream2, hipStreamNonBlocking) != hipSuccess) { c->dec_stream2 = nullptr; nblic_amd_destroy(c); return nullptr; }
     // (Measured and rejected: creating the copy streams with the highest stream priority, so that the
     // coder threads' short interleave kernels and copies overtake the encoder's long kernels -- the
@@ -2809,7 +2814,7 @@ void nblic_amd_destroy(nblic_amd_ctx *c) {
     for (auto &g : c->groups) group_free(g);
     for (auto &cb : c->cbufs) if (cb.p) hipFree(cb.p);
     for (auto &cs : c->copy_streams) if (cs) hipStreamDestroy(cs);
-    hipFree(c->dec_arena); hipFree(c->dec_jobs);
+    hipFree(c->dec_arena); hipFree(c->dec_jobs); hipFree(c->d_redo);
     if (c->feed_pipe[0] >= 0) { close(c->feed_pipe[0]); close(c->feed_pipe[1]); }
     if (c->dec_stream) hipStreamDestroy(c->dec_stream);
     if (c->dec_stream2) hipStreamDestroy(c->dec_stream2);
@@ -2829,6 +2834,16 @@ long nblic_amd_serial_launches(nblic_amd_ctx *c) {
     if (!c) return -1;
     std::lock_guard<std::mutex> l(c->stat_m);
     return c->serial_launch_count;
+}
+int nblic_amd_lsq_redo_counts(nblic_amd_ctx *c, unsigned long long counts[2], int reset) {
+    if (!c) c = default_ctx();
+    if (!c || !counts) return -1;
+    std::lock_guard<std::mutex> g(c->api);                                   // no batch of this context is in flight
+    unsigned long long v[2] = {0, 0};
+    if (hipSetDevice(c->device) != hipSuccess || hipMemcpy(v, c->d_redo, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (reset && hipMemset(c->d_redo, 0, sizeof v) != hipSuccess) return -1;
+    counts[0] = v[0]; counts[1] = v[1];
+    return 0;
 }
 void nblic_amd_set_feed_chunk(nblic_amd_ctx *c, size_t bytes) {
     if (!c) c = default_ctx();
@@ -3042,6 +3057,18 @@ void nblic_amd_device_coder_stats(nblic_amd_ctx *c, double *bins, long *packs, l
 int nblic_amd_serial_selftest(nblic_amd_ctx *c) {
     if (!c || hipSetDevice(c->device) != hipSuccess) return -1;
     return serial_selftest(c->dec_stream);
+}
+
+int nblic_amd_serial_plan(int decode, int effort, int images, int width, int whole_streams) {
+    if (images < 1 || width < 1 || effort < 1 || effort > 3) return -1;
+    return decode ? serial_decode_plan(images, width, whole_streams != 0) : serial_model_plan(effort, images, width);
+}
+
+int nblic_amd_lsq_probe(nblic_amd_ctx *c, int n, int waves, int count, const double *stats, const signed char *regressors, const int *bias,
+                        double *out_f64, long long *out_i64) {
+    if (!c || !stats || !regressors || !bias || !out_f64 || !out_i64 || hipSetDevice(c->device) != hipSuccess) return -1;
+    std::lock_guard<std::mutex> g(c->api);
+    return serial_lsq_probe(c->dec_stream, n, waves, count, stats, reinterpret_cast<const int8_t *>(regressors), bias, out_f64, out_i64) ? 0 : -1;
 }
 
 // ---- drop-in entry points --------------------------------------------------------------------

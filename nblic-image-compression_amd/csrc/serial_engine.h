@@ -75,6 +75,8 @@ struct SerialJob {
     unsigned long long stream_off;   // decode: absolute stream offset of byte 0 of `stream` (a multiple of 512; SerialState::pos / avail stay absolute)
     int end_row;               // decode: the job stops in front of this row (0: h).  Reaching end_row < h leaves the record as a band
                                // boundary leaves it (tables written back, status kRunning, next_row == end_row); further launches return at once
+    unsigned long long *redo;  // efforts 2/3: two counters the launch adds to -- pixels whose system 0 / system 1 of the least squares left the
+                               // exact range of the doubles and were redone with 64-bit integers (lsq_f64.h Guard).  Jobs may share a pair; null: not counted
     // QNBLIC decode only
     const uint32_t *q_freq, *q_start; const uint8_t *q_slot;      // 12 x 256 frequencies and cumulative starts; q_slot: unused (the kernel searches q_start)
 };
@@ -96,12 +98,26 @@ inline int serial_launches(int h, int rows) { return (h + rows - 1) / rows; }
 // true when the three rows a pixel's taps can touch fit in the LDS the model kernel has left, i.e. the kernel will keep
 // them there; otherwise it reads its taps from SerialJob::recon, which then has to be there even for lossless jobs
 bool serial_model_rows_fit(int w);
+// The kernel variant a launch of n images (widest: max_w) gets, as the launchers below decide it: kPlanTwoWaves (model,
+// effort 3: a second wave per image), kPlanLean (decoders: the lean LDS image), kPlanRowsInLds (the widest image's rows
+// are cached in LDS; a kernel compares per job, so narrower jobs of the same launch still are).
+enum : int { kPlanTwoWaves = 1, kPlanLean = 2, kPlanRowsInLds = 4 };
+int serial_model_plan(int effort, int n, int max_w);
+int serial_decode_plan(int n, int max_w, bool whole_streams);
 
 // d_jobs[0..n): all of one effort (1, 2 or 3); h_jobs: host copy, read to size the launch.  ONE launch: every job
 // advances by its `rows`; call serial_launches(h, rows) times (maximum over the jobs) to finish them.
 bool serial_model_launch(const SerialJob *d_jobs, const SerialJob *h_jobs, int n, hipStream_t s);
 bool serial_decode_launch(const SerialJob *d_jobs, const SerialJob *h_jobs, int n, hipStream_t s, bool whole_streams);   // whole_streams: every job's stream is final (SerialState::final_)
 bool serial_qdecode_launch(const SerialJob *d_jobs, const SerialJob *h_jobs, int n, hipStream_t s);
+// Both least-squares solvers of the serial kernels on `count` given systems, no image and no coder (tests): stats = count x vec_len(n)
+// integer-valued statistics [s | b | A], vn = count x 10 regressors, bias = the regularisation strength the pixel starts from (the two
+// systems of an item are the ones bias_pair makes of it).  n = 6 or 10; waves = 2 (n = 10 only) runs the two-wave hand-over.  Per item
+// out_f64[12] = the double path's clamped Q12 predictions of system 0 / 1, then the Guard maxima (product, entry, quotient, pivot) of
+// system 0 and of system 1; out_i64[14] = what the kernels' own predict / solve_one + take_other deliver (p1, p2, ok1, ok2), the double
+// path's ok of system 0 / 1, its Guard verdicts, the integer path's raw Q12 sums, its ok of system 0 / 1, and the redo counts the item
+// added.  Both paths are always computed.  false: a HIP call failed or the arguments are out of range.
+bool serial_lsq_probe(hipStream_t s, int n, int waves, int count, const double *stats, const int8_t *vn, const int *bias, double *out_f64, long long *out_i64);
 int serial_selftest(hipStream_t s);                    // device check of the double-carried divisions against 64-bit integers and of the half-wave exchange; 0 = pass
 
 }  // namespace nblic

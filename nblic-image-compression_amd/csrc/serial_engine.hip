@@ -123,6 +123,7 @@ struct LsqLds {
     double D[128];                           // statistics of the pixel about to be predicted: [s | b | A] (E + F)
     int8_t vn8[16];                          // regressors 0..9 (tap - 128); [14] = 0
     int xch[3], bias_pub;                    // two-wave solve: the second wave's prediction / verdict / "redo with integers"; the regularisation strength for it
+    int redo[2];                             // pixels of this launch whose system 0 / system 1 left the exact range (lane 0 of the main wave counts; lsq_redo_flush)
     i64 Mi[lsq::kMaxN][lsq::kMaxN + 1];      // integer redo of a pixel (rare): augmented system, terms
     i64 termi[lsq::kMaxN];
     int8_t dump[64];                         // lane-parallel front: where the lanes without a regressor store theirs
@@ -225,6 +226,12 @@ __device__ __noinline__ int lsq_solve_int(LsqLds &S, int n, i64 bias, i64 *px_q1
     wave_sync();
     *px_q12 = px;
     return 1;
+}
+
+// The launch's redo counts into the job's counter pair (SerialJob::redo): once per launch, and only when there were any.
+__device__ __forceinline__ void lsq_redo_flush(const LsqLds &S, unsigned long long *redo) {
+    const int r0 = S.redo[0], r1 = S.redo[1];
+    if (redo && (r0 | r1)) { atomicAdd(redo, u64(r0)); atomicAdd(redo + 1, u64(r1)); }
 }
 
 // ---- least squares in registers: the pixel's two systems side by side, their columns split over the wave ----
@@ -475,6 +482,8 @@ struct LsqWalk {
             ok1 = __builtin_amdgcn_readfirstlane(lsq_solve_int(S, N, b1, &q1)) != 0;
             ok2 = __builtin_amdgcn_readfirstlane(lsq_solve_int(S, N, b2, &q2)) != 0;
             p1 = __builtin_amdgcn_readfirstlane(clamp_q12(q1)); p2 = __builtin_amdgcn_readfirstlane(clamp_q12(q2));
+            constexpr u64 kSys0 = L::R == 8 ? 0x00FF00FF00FF00FFull : 0x0000FFFF0000FFFFull;     // the lanes of system 0
+            if (lane == 0) { S.redo[0] += int((bad & kSys0) != 0); S.redo[1] += int((bad & ~kSys0) != 0); }
         }
     }
     // WAVES = 2: this wave's ONE system.  The main wave keeps p1 / ok1 (and redoes its system with integers at once if
@@ -490,7 +499,10 @@ struct LsqWalk {
         const bool ok_mine = (__ballot(ok != 0) & 1ull) != 0;
         if (main) {
             p1 = mine; ok1 = ok_mine;
-            if (bad) { i64 q1 = 0; ok1 = __builtin_amdgcn_readfirstlane(lsq_solve_int(S, N, b1, &q1)) != 0; p1 = __builtin_amdgcn_readfirstlane(clamp_q12(q1)); }
+            if (bad) {
+                i64 q1 = 0; ok1 = __builtin_amdgcn_readfirstlane(lsq_solve_int(S, N, b1, &q1)) != 0; p1 = __builtin_amdgcn_readfirstlane(clamp_q12(q1));
+                if (lane == 0) S.redo[0]++;
+            }
         } else {
             S.xch[0] = mine; S.xch[1] = int(ok_mine); S.xch[2] = int(bad);
         }
@@ -499,7 +511,10 @@ struct LsqWalk {
     __device__ __forceinline__ void take_other(LsqLds &S) {
         const int x0 = S.xch[0], x1 = S.xch[1], x2 = S.xch[2];           // one round trip for the three
         p2 = __builtin_amdgcn_readfirstlane(x0); ok2 = __builtin_amdgcn_readfirstlane(x1) != 0;
-        if (__builtin_amdgcn_readfirstlane(x2)) { i64 q2 = 0; ok2 = __builtin_amdgcn_readfirstlane(lsq_solve_int(S, N, b2, &q2)) != 0; p2 = __builtin_amdgcn_readfirstlane(clamp_q12(q2)); }
+        if (__builtin_amdgcn_readfirstlane(x2)) {
+            i64 q2 = 0; ok2 = __builtin_amdgcn_readfirstlane(lsq_solve_int(S, N, b2, &q2)) != 0; p2 = __builtin_amdgcn_readfirstlane(clamp_q12(q2));
+            if (lane == 0) S.redo[1]++;
+        }
     }
     // fold the coded pixel in (NBLIC.c:242-283, :882-893) and publish the next pixel's statistics
     __device__ __forceinline__ void update(LsqLds &S, int j, int xr, int p1_used) {
@@ -828,6 +843,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_serial_model(const SerialJob *__
     for (int k = tid; k < kContexts; k += 64 * WAVES) S.ctx[k] = i0 ? st_ctx[k] : 0;
     if (tid < 64) fill_qlut(S.qlut);
     if (tid < 16) S.q.vn8[tid] = 0;
+    if (tid < 2) S.q.redo[tid] = 0;
     if (tid < 4) rows_raw[tid] = 0;
     if (WAVES == 2) block_sync(); else wave_sync();
     const int rs = (J.w + kRowPad + 15) & ~15;
@@ -836,6 +852,7 @@ __global__ void __launch_bounds__(64 * WAVES) k_serial_model(const SerialJob *__
     if (WAVES == 2) block_sync(); else wave_sync();
     if (i1 < J.h) for (int k = tid; k < kContexts; k += 64 * WAVES) st_ctx[k] = S.ctx[k];
     if (tid == 0) { st->next_row = i1; st->bias = bias; st->status = i1 < J.h ? kRunning : kDone; }
+    if (N > 0 && tid == 0) lsq_redo_flush(S.q, J.redo);
 }
 
 // ---- decoder: the whole NBLIC loop (NBLIC.c:749-908 with decode = 1) ----------------------------
@@ -1111,6 +1128,7 @@ __global__ void __launch_bounds__(64) k_serial_decode(const SerialJob *__restric
     }
     fill_qlut(S.qlut);
     if (lane < 16) S.q.vn8[lane] = 0;
+    if (lane < 2) S.q.redo[lane] = 0;
     wave_sync();
     StreamWindow sw;
     uint32_t cs[3] = {0u, 0xFFFFFFFFu, 0u};                              // NBLIC.c:536-549
@@ -1129,7 +1147,8 @@ __global__ void __launch_bounds__(64) k_serial_decode(const SerialJob *__restric
     else if (3 * rs + 4 <= dyn_bytes) at = decode_body<N, true>(S, rows, J, rs, i0, i1, sw, cs, bias, final_, stop);
     else at = decode_body<N, false>(S, rows, J, rs, i0, i1, sw, cs, bias, final_, stop);
     wave_sync();
-    if (stop == kFailed || stop == kStarvedMidRow) { if (lane == 0) st->status = stop; return; }
+    if (stop == kFailed || stop == kStarvedMidRow) { if (lane == 0) st->status = stop; return; }     // nothing of such a launch is kept, its redo counts included
+    if (N > 0 && lane == 0) lsq_redo_flush(S.q, J.redo);
     if (at < J.h) tables([](uint32_t &lds, NB_GLOBAL uint32_t &rec) { rec = lds; });
     if (lane == 0) {
         st->next_row = at; st->pos = sw.pos; st->lo = cs[0]; st->hi = cs[1]; st->window = cs[2]; st->bias = bias;
@@ -1436,6 +1455,98 @@ int serial_selftest(hipStream_t s) {
     return int(bad);
 }
 
+// ---- probe: both least-squares solvers on given systems, no image and no coder (serial_engine.h serial_lsq_probe) ----
+// One workgroup per item, shaped like the model kernel's: the statistics and regressors go into LsqLds the way a pixel's
+// do, then (1) the kernels' own predict / solve_one + take_other, (2) solve_with alone with its Guard reduced over the
+// lanes of each system, (3) lsq_solve_int alone for both systems.
+constexpr int kProbeF64 = 12, kProbeI64 = 14;
+template <int N, int WAVES>
+__global__ void __launch_bounds__(64 * WAVES) k_lsq_probe(const double *__restrict__ stats, const int8_t *__restrict__ vn, const int *__restrict__ bias,
+                                                         double *zero_stats, double *out_f64, i64 *out_i64) {
+    using L = SplitLayout<N, WAVES>;
+    constexpr int m = LsqEntries<N>::kM, kThreads = 64 * WAVES;
+    __shared__ LsqLds S;
+    __shared__ double seen[kThreads][4];
+    const int tid = int(threadIdx.x), lane = tid & 63, wave = WAVES == 1 ? 0 : __builtin_amdgcn_readfirstlane(tid) >> 6;
+    const bool main = wave == 0;
+    const size_t item = blockIdx.x;
+    const int bias0 = bias[item];
+    for (int k = tid; k < 128; k += kThreads) S.D[k] = k < m ? stats[item * m + k] : 0.0;
+    if (tid < 16) S.vn8[tid] = tid < lsq::kMaxN ? vn[item * lsq::kMaxN + tid] : int8_t(0);
+    if (tid < 2) S.redo[tid] = 0;
+    if (tid == 0) S.bias_pub = bias0;
+    __syncthreads();
+    LsqWalk<N, WAVES> lw;
+    lw.init(zero_stats, 1, lane, wave, bias0);
+    if constexpr (WAVES == 2) {                                          // the model kernel's sequence for a pixel (model_body)
+        block_sync(); lw.solve_one(S, 0, main);
+        block_sync(); if (main) lw.take_other(S);
+    } else {
+        wave_sync(); lw.predict(S, 0);
+    }
+    __syncthreads();
+    int b1, b2;
+    lsq::bias_pair(bias0, b1, b2);
+    lsq::Guard g;
+    int ok;
+    const double pd = lw.solve_with(S, lw.sys ? b2 : b1, g, ok);
+    seen[tid][0] = g.product; seen[tid][1] = g.entry; seen[tid][2] = g.quotient; seen[tid][3] = g.pivot;
+    if (lane == 0 || (WAVES == 1 && lane == L::R)) {                     // column group 0 of the system, as predict / solve_one read it
+        out_f64[item * kProbeF64 + lw.sys] = pd;
+        out_i64[item * kProbeI64 + 4 + lw.sys] = ok;
+    }
+    __syncthreads();
+    if (tid < 2) {                                                       // the Guard of system `tid` over all its lanes
+        lsq::Guard all;
+        for (int t = 0; t < kThreads; t++) {
+            const int sys_t = WAVES == 2 ? t >> 6 : (t / L::R) & 1;
+            if (sys_t != tid) continue;
+            all.see_product(seen[t][0]); all.see_entry(seen[t][1]); all.see_quotient(seen[t][2]); all.see_pivot(seen[t][3]);
+        }
+        double *o = out_f64 + item * kProbeF64 + 2 + 4 * tid;
+        o[0] = all.product; o[1] = all.entry; o[2] = all.quotient; o[3] = all.pivot;
+        out_i64[item * kProbeI64 + 6 + tid] = all.ok();
+    }
+    __syncthreads();
+    if (main) {
+        i64 q1 = 0, q2 = 0;
+        const int o1 = lsq_solve_int(S, N, b1, &q1), o2 = lsq_solve_int(S, N, b2, &q2);
+        if (lane == 0) {
+            i64 *o = out_i64 + item * kProbeI64;
+            o[0] = lw.p1; o[1] = lw.p2; o[2] = lw.ok1; o[3] = lw.ok2;
+            o[8] = q1; o[9] = q2; o[10] = o1; o[11] = o2; o[12] = S.redo[0]; o[13] = S.redo[1];
+        }
+    }
+}
+
+bool serial_lsq_probe(hipStream_t s, int n, int waves, int count, const double *stats, const int8_t *vn, const int *bias, double *out_f64, long long *out_i64) {
+    if ((n != 6 && n != lsq::kMaxN) || (waves != 1 && !(waves == 2 && n == lsq::kMaxN)) || count <= 0 || count > (1 << 20)) return false;
+    const size_t c = size_t(count), m = size_t(lsq::vec_len(n));
+    const size_t b_stats = c * m * sizeof(double), b_vn = (c * lsq::kMaxN + 7) & ~size_t(7), b_bias = (c * sizeof(int) + 7) & ~size_t(7), b_zero = 256 * sizeof(double);
+    const size_t b_f64 = c * kProbeF64 * sizeof(double), b_i64 = c * kProbeI64 * sizeof(i64);
+    uint8_t *d = nullptr;
+    if (hipMalloc((void **)&d, b_stats + b_zero + b_f64 + b_i64 + b_vn + b_bias) != hipSuccess) return false;
+    double *d_stats = reinterpret_cast<double *>(d), *d_zero = d_stats + c * m, *d_f64 = d_zero + 256;
+    i64 *d_i64 = reinterpret_cast<i64 *>(d_f64 + c * kProbeF64);
+    int *d_bias = reinterpret_cast<int *>(d_i64 + c * kProbeI64);
+    int8_t *d_vn = reinterpret_cast<int8_t *>(d) + b_stats + b_zero + b_f64 + b_i64 + b_bias;
+    bool ok = hipMemcpyAsync(d_stats, stats, b_stats, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync(d_vn, vn, c * lsq::kMaxN, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync(d_bias, bias, c * sizeof(int), hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemsetAsync(d_zero, 0, b_zero + b_f64 + b_i64, s) == hipSuccess;
+    if (ok) {
+        if (n == 6) hipLaunchKernelGGL((k_lsq_probe<6, 1>), dim3(unsigned(count)), dim3(64), 0, s, d_stats, d_vn, d_bias, d_zero, d_f64, d_i64);
+        else if (waves == 1) hipLaunchKernelGGL((k_lsq_probe<10, 1>), dim3(unsigned(count)), dim3(64), 0, s, d_stats, d_vn, d_bias, d_zero, d_f64, d_i64);
+        else hipLaunchKernelGGL((k_lsq_probe<10, 2>), dim3(unsigned(count)), dim3(128), 0, s, d_stats, d_vn, d_bias, d_zero, d_f64, d_i64);
+        ok = hipGetLastError() == hipSuccess &&
+             hipMemcpyAsync(out_f64, d_f64, b_f64, hipMemcpyDeviceToHost, s) == hipSuccess &&
+             hipMemcpyAsync(out_i64, d_i64, b_i64, hipMemcpyDeviceToHost, s) == hipSuccess;
+    }
+    ok = hipStreamSynchronize(s) == hipSuccess && ok;
+    hipFree(d);
+    return ok;
+}
+
 // ---- launchers ----------------------------------------------------------------------------------
 constexpr int kLdsBudget = 160 * 1024;
 constexpr int kLeanImages = 256;                  // decode launches of more images than this keep the hit counts in memory (four waves per CU)
@@ -1443,6 +1554,16 @@ constexpr int kTwoWaveImages = 64;               // effort-3 launches of at most
 constexpr int lds_room(size_t static_lds) { return int(kLdsBudget - static_lds - 256) & ~15; }
 
 bool serial_model_rows_fit(int w) { return 3 * ((w + kRowPad + 15) & ~15) + 4 <= lds_room(sizeof(ModelLds)); }
+
+// Which kernel a launch gets: the launchers below go by these and by nothing else.
+int serial_model_plan(int effort, int n, int max_w) {
+    return (effort == 3 && n <= kTwoWaveImages ? kPlanTwoWaves : 0) | (serial_model_rows_fit(max_w) ? kPlanRowsInLds : 0);
+}
+int serial_decode_plan(int n, int max_w, bool whole_streams) {
+    const bool lean = whole_streams && n > kLeanImages;
+    const bool fit = 3 * ((max_w + kRowPad + 15) & ~15) + 4 <= lds_room(lean ? sizeof(DecodeLdsLean) : sizeof(DecodeLds));
+    return (lean ? kPlanLean : 0) | (fit ? kPlanRowsInLds : 0);
+}
 
 template <class K>
 static bool launch_rows(K kernel, size_t static_lds, const SerialJob *d_jobs, const SerialJob *h_jobs, int n, hipStream_t s, int threads = 64,
@@ -1467,7 +1588,7 @@ bool serial_model_launch(const SerialJob *d_jobs, const SerialJob *h_jobs, int n
             // two barriers per pixel eat two thirds of what the shorter elimination saves).  Many images: the second wave
             // would take a SIMD slot from another image for a 3 % shorter chain (2048 images: 156 against 261 Mpx/s), so
             // a batch that can fill the GPU with single waves keeps them.
-            if (n <= kTwoWaveImages) return launch_rows(k_serial_model<10, 2>, sizeof(ModelLds), d_jobs, h_jobs, n, s, 128, kRowPad);
+            if (serial_model_plan(3, n, 1) & kPlanTwoWaves) return launch_rows(k_serial_model<10, 2>, sizeof(ModelLds), d_jobs, h_jobs, n, s, 128, kRowPad);
             return launch_rows(k_serial_model<10, 1>, sizeof(ModelLds), d_jobs, h_jobs, n, s, 64, kRowPad);
     }
 }
@@ -1477,7 +1598,7 @@ bool serial_decode_launch(const SerialJob *d_jobs, const SerialJob *h_jobs, int 
     // More images than CUs: the lean LDS image (four waves per CU instead of one; a pixel pays two reads of its hit counts
     // in L2 instead of LDS).  Only for streams that are there in full: a launch that runs dry inside a row is REDONE from
     // the state record, and the lean image has already changed the counts in it.
-    if (whole_streams && n > kLeanImages) {
+    if (serial_decode_plan(n, 1, whole_streams) & kPlanLean) {
         switch (h_jobs[0].effort) {
             case 1: return launch_rows(k_serial_decode<0, true>, sizeof(DecodeLdsLean), d_jobs, h_jobs, n, s, 64, kRowPad);
             case 2: return launch_rows(k_serial_decode<6, true>, sizeof(DecodeLdsLean), d_jobs, h_jobs, n, s, 64, kRowPad);

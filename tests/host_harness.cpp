@@ -97,10 +97,25 @@ bool solve_f64(int n, double M[lsq::kMaxN][lsq::kMaxN + 1], const int *vn, lsq::
     return true;
 }
 
+// the augmented system of strength bs from a pixel's statistics D = [s | b | A] (NBLIC.c:213-230)
+void assemble(int n, const double *D, int bs, double M[lsq::kMaxN][lsq::kMaxN + 1]) {
+    for (int r = 0; r < n; r++) {
+        for (int c = 0; c < n; c++) M[r][c] = D[1 + n + r * n + c] + (r == c ? double(bs * n) : 0.0);
+        M[r][n] = D[1 + r] + double(bs) * double(1 << lsq::kFb3);
+    }
+}
+
 }  // namespace
 
+// The assembled least-squares inputs of chosen pixels, for the tests that feed them to the device solvers directly:
+// per pixel vec_len(n) statistics, the ten regressors, the regularisation strength the pixel starts from, and which of
+// its two systems the guard sent to the integer redo (bit 0 / bit 1).  Every redo pixel is kept, as many ordinary
+// pixels (the first after each), and every `every`-th pixel when every > 0; `count` runs on past `cap`.
+struct HhSystems { long cap, count; int every; double *D; int8_t *vn; int *bias; uint8_t *redo; };
+
+// `fallbacks`: solves the guard sent to the integer redo; by_system[2]: the same split by system (0: strength b1, 1: b2)
 extern "C" long hh_model_encode(const uint8_t *img_in, uint8_t *recon, int h, int w, int near, int effort, uint16_t *coded, long cap,
-                                long *fallbacks) {
+                                long *fallbacks, long *by_system, HhSystems *dump) {
     const int n = lsq::order_of(effort), m = lsq::vec_len(n);
     const int k_step = k_step_for_near(near);
     std::vector<int> ctx(kContexts, 0);
@@ -110,7 +125,8 @@ extern "C" long hh_model_encode(const uint8_t *img_in, uint8_t *recon, int h, in
     for (auto &mp : maps) for (int s = 0; s < kMapSyms; s++) { mp.count[s] = 2 * (kMapSyms - 1 - s); mp.rank_of[s] = mp.sym_at[s] = uint8_t(s); }
     std::vector<double> B(size_t(n ? w : 0) * m, 0.0), F(size_t(n ? w : 0) * m, 0.0), E(m, 0.0);
     memcpy(recon, img_in, size_t(h) * w);
-    long n_bins = 0, n_fallback = 0;
+    long n_bins = 0, n_fallback = 0, n_by_system[2] = {0, 0}, owed = 0, n_px = 0;
+    std::vector<double> Dj(size_t(m), 0.0);
     int bias = lsq::kBiasInit;
     auto pix = [&](int r, int c) { return int(recon[size_t(r) * w + c]); };
     for (int i = 0; i < h; i++) {
@@ -131,22 +147,35 @@ extern "C" long hh_model_encode(const uint8_t *img_in, uint8_t *recon, int h, in
             double *Bj = n ? &B[size_t(j) * m] : nullptr, *Fj = n ? &F[size_t(j) * m] : nullptr;
             if (n) {
                 lsq::bias_pair(bias, b1, b2);
+                for (int k = 0; k < m; k++) Dj[k] = E[k] + Fj[k];
+                int redone = 0;
                 for (int s = 0; s < 2; s++) {
                     const int bs = s ? b2 : b1;
                     double M[lsq::kMaxN][lsq::kMaxN + 1], Mi[lsq::kMaxN][lsq::kMaxN + 1];
-                    for (int r = 0; r < n; r++) {
-                        for (int c = 0; c < n; c++) M[r][c] = E[1 + n + r * n + c] + Fj[1 + n + r * n + c] + (r == c ? double(bs * n) : 0.0);
-                        M[r][n] = E[1 + r] + Fj[1 + r] + double(bs) * double(1 << lsq::kFb3);
-                    }
+                    assemble(n, Dj.data(), bs, M);
                     memcpy(Mi, M, sizeof M);
                     lsq::Guard g;
                     double pd = 0.0;
                     bool ok = solve_f64(n, M, vn, g, &pd);
                     i64 p = i64(pd);
-                    if (!g.ok()) { n_fallback++; ok = solve_int(n, Mi, vn, &p); }
+                    if (!g.ok()) { n_fallback++; n_by_system[s]++; redone |= 1 << s; ok = solve_int(n, Mi, vn, &p); }
                     p = p < 0 ? 0 : (p > (i64(kMaxVal) << lsq::kFb1) ? (i64(kMaxVal) << lsq::kFb1) : p);
                     if (s) { ok2 = ok; p2 = p; } else { ok1 = ok; p1 = p; }
                 }
+                if (dump) {
+                    const bool take = redone || owed > 0 || (dump->every > 0 && n_px % dump->every == 0);
+                    if (redone) owed++; else if (owed > 0) owed--;
+                    if (take) {
+                        if (dump->count < dump->cap) {
+                            const size_t at = size_t(dump->count);
+                            memcpy(dump->D + at * m, Dj.data(), size_t(m) * sizeof(double));
+                            for (int k = 0; k < lsq::kMaxN; k++) dump->vn[at * lsq::kMaxN + k] = int8_t(vn[k]);
+                            dump->bias[at] = bias; dump->redo[at] = uint8_t(redone);
+                        }
+                        dump->count++;
+                    }
+                }
+                n_px++;
             }
             if (ok1) px0 = int((p1 + (1 << (lsq::kFb1 - 1))) >> lsq::kFb1);
             else { px0 = predict(t); p1 = i64(px0) << lsq::kFb1; }
@@ -199,7 +228,39 @@ extern "C" long hh_model_encode(const uint8_t *img_in, uint8_t *recon, int h, in
         }
     }
     if (fallbacks) *fallbacks = n_fallback;
+    if (by_system) { by_system[0] = n_by_system[0]; by_system[1] = n_by_system[1]; }
     return n_bins;
+}
+
+// Both host solves on `count` given pixels (statistics, regressors, starting strength: the layout of HhSystems), the way
+// hh_model_encode runs them.  Per pixel and system s (0: b1, 1: b2 of bias_pair):
+//   out_i64[s]     solve_int's Q12 sum (the reference's integer; 0 when it reports no solution)     out_i64[2 + s]  its ok
+//   out_i64[4 + s] solve_f64's prediction, clamped to [0, 255 << 12]                                out_i64[6 + s]  its ok
+//   out_i64[8 + s] Guard::ok() of that solve
+//   out_f64[4 s .. 4 s + 3]  the Guard's largest product, entry, quotient, pivot
+extern "C" void hh_lsq_solve(int n, long count, const double *D, const int8_t *vn8, const int *bias, long long *out_i64, double *out_f64) {
+    const int m = lsq::vec_len(n);
+    for (long t = 0; t < count; t++) {
+        int vn[lsq::kMaxN], b1, b2;
+        for (int k = 0; k < lsq::kMaxN; k++) vn[k] = vn8[t * lsq::kMaxN + k];
+        lsq::bias_pair(bias[t], b1, b2);
+        long long *oi = out_i64 + t * 10;
+        double *of = out_f64 + t * 8;
+        for (int s = 0; s < 2; s++) {
+            double M[lsq::kMaxN][lsq::kMaxN + 1], Mi[lsq::kMaxN][lsq::kMaxN + 1];
+            assemble(n, D + size_t(t) * m, s ? b2 : b1, M);
+            memcpy(Mi, M, sizeof M);
+            i64 p = 0;
+            const bool oki = solve_int(n, Mi, vn, &p);
+            oi[s] = oki ? p : 0; oi[2 + s] = oki;
+            lsq::Guard g;
+            double pd = 0.0;
+            const bool okd = solve_f64(n, M, vn, g, &pd);
+            const double top = double(kMaxVal << lsq::kFb1);
+            oi[4 + s] = okd ? i64(pd < 0.0 ? 0.0 : (pd > top ? top : pd)) : 0; oi[6 + s] = okd; oi[8 + s] = g.ok();
+            of[4 * s] = g.product; of[4 * s + 1] = g.entry; of[4 * s + 2] = g.quotient; of[4 * s + 3] = g.pivot;
+        }
+    }
 }
 
 // Exhaustive comparison of the divide-free helpers the serial kernels use (model.h NearParams,

@@ -54,6 +54,41 @@ def make(content, h, w):
     raise ValueError(content)
 
 
+# Hard-edged planes (two levels, 0 and 255: text scans, charts, screenshots).  Coded near-lossless at efforts 2 / 3 they
+# push the least-squares systems out of the range in which the kernels' doubles are exact, so pixels are redone with
+# 64-bit integers (csrc/lsq_f64.h Guard) -- which CONTENTS practically never does.  Not part of CONTENTS: the golden
+# streams are made from that list.
+HARD_EDGED = ["step_v", "step_h", "stripes_h", "bars_v"]
+
+
+def blocks(h, w, block, seed):
+    """Random 0 / 255 squares of side `block` (xorshift32, one draw per square)."""
+    gh, gw = -(-h // block), -(-w // block)
+    bits = np.empty(gh * gw, np.uint8)
+    s = (seed * 2654435761 + 1) & 0xFFFFFFFF
+    for k in range(gh * gw):
+        s ^= (s << 13) & 0xFFFFFFFF
+        s ^= s >> 17
+        s ^= (s << 5) & 0xFFFFFFFF
+        bits[k] = (s >> 7) & 1
+    grid = bits.reshape(gh, gw) * np.uint8(255)
+    return np.ascontiguousarray(np.repeat(np.repeat(grid, block, 0), block, 1)[:h, :w])
+
+
+def make_hard(content, h, w):
+    if content == "step_v":                       # left half 0, right half 255
+        return np.ascontiguousarray(np.broadcast_to(((np.arange(w) >= w // 2) * 255).astype(np.uint8)[None, :], (h, w)))
+    if content == "step_h":                       # top half 0, bottom half 255
+        return np.ascontiguousarray(np.broadcast_to(((np.arange(h) >= h // 2) * 255).astype(np.uint8)[:, None], (h, w)))
+    if content == "stripes_h":                    # rows alternate 0 / 255
+        return np.ascontiguousarray(np.broadcast_to(((np.arange(h) & 1) * 255).astype(np.uint8)[:, None], (h, w)))
+    if content == "bars_v":                       # columns alternate 0 / 255 in bars of 64: an edge every 64 pixels of however wide a row
+        return np.ascontiguousarray(np.broadcast_to((((np.arange(w) >> 6) & 1) * 255).astype(np.uint8)[None, :], (h, w)))
+    if content == "blocks_lossless":              # the one of 60 block planes (block 1..16, 20..80 x 20..120) that reaches the redo LOSSLESS
+        return blocks(33, 81, 13, 28)             # with several pixels (-e2: 4, -e3: 15); h and w are not used
+    raise ValueError(content)
+
+
 def case_id(content, h, w, near, effort):
     return f"{content}_{h}x{w}_n{near}_e{effort}"
 

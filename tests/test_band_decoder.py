@@ -347,3 +347,23 @@ def test_coexists_with_band_encoder_and_decode_batch(gpu_ctx, oracle):
     enc.close()
     assert np.array_equal(np.concatenate(parts), drec)
     assert b"".join(pieces) == es_want
+
+
+def test_integer_redo_in_random_pieces_and_on_wide_rows(gpu_ctx, pkg, oracle):
+    """Hard-edged planes coded near-lossless send pixels of efforts 2 / 3 to the integer redo of the least squares
+    (test_gpu_resume.py test_integer_redo_runs_in_every_kernel_variant).  The band decoder, fed in seeded random pieces,
+    bands of 5 rows: the oracle's plane, and the device counted redone pixels; the same for a row too wide for the LDS row
+    cache (30000 pixels, an edge every 64: the decoder that reads its taps from memory), which syn1 never does."""
+    # (nblic_amd_serial_plan: the launchers' own decision) 64 pixels are cached in LDS, 30000 are not; one stream is never lean
+    assert pkg.serial_plan(True, 2, 1, 64, False) == pkg.PLAN_ROWS_IN_LDS and pkg.serial_plan(True, 3, 1, 64, False) == pkg.PLAN_ROWS_IN_LDS
+    assert pkg.serial_plan(True, 2, 1, 30000, False) == 0 and pkg.serial_plan(True, 3, 1, 30000, False) == 0
+    for name, h, w, br in (("step_v", 64, 64, 5), ("bars_v", 6, 30000, 3)):
+        img = inputs.make_hard(name, h, w)
+        for near, effort in ((2, 2), (2, 3)):
+            s, rec, *_ = oracle.encode(img, near, effort)
+            gpu_ctx.lsq_redo_counts(reset=True)
+            plane, prog = band_decode(gpu_ctx, s, br, np.random.default_rng(near + effort))
+            assert np.array_equal(plane, rec) and prog["sha256"] == sha(plane.tobytes()), (name, near, effort)
+            c = gpu_ctx.lsq_redo_counts(reset=True)
+            print(f"lsq redo on the device: band decoder{' uncached' if w > 20000 else ''} {name} {h}x{w} -n{near} -e{effort}: system 0 {c[0]}, system 1 {c[1]}")
+            assert c[0] >= 1, (name, near, effort)

@@ -344,3 +344,112 @@ def test_dropped_band_streams_give_their_group_back(gpu_ctx, pkg):
     ctx.close()
     assert "error" not in result, result.get("error")
     assert result["finished"] and len(result["batch"]) > 16
+
+
+def _redo_row(rows, name, counts):
+    rows.append((name, counts))
+    print(f"lsq redo on the device: {name}: system 0 {counts[0]}, system 1 {counts[1]}")
+    assert counts[0] >= 1, name
+
+
+def test_integer_redo_runs_in_every_kernel_variant(gpu_ctx, pkg, oracle):
+    """Efforts 2 / 3 redo a pixel with 64-bit integers when its least squares leave the exact range of the doubles
+    (csrc/lsq_f64.h Guard, serial_engine.hip lsq_solve_int); hard-edged planes coded near-lossless do that (tests/inputs.py
+    HARD_EDGED; the CPU harness shows >= 8 such pixels for every case here, test_lsq_limits.py / DESIGN.md), the suite's
+    other contents practically never.  Every kernel that holds the redo, per call: the bytes are the oracle's, the plane
+    the oracle's reconstruction, AND the device's own count of redone pixels (Context.lsq_redo_counts) is not zero --
+    model <6,1>, <10,1> (65 or more effort-3 images in a launch), <10,2> (64 or fewer: the main wave's redo), the model with
+    its rows in memory (a row too wide for LDS), the decoder (cached; lean: more than 256 streams in a call), the band
+    encoder across checkpoints, and the drop-in entry points.  A lossless syn1 job must count nothing."""
+    step64, step33 = inputs.make_hard("step_v", 64, 64), inputs.make_hard("step_v", 33, 57)
+    rows = []
+    # the variant each row below names is the one the launchers choose for it (nblic_amd_serial_plan: their own decision
+    # functions), so a threshold that moves cannot quietly move a row to another kernel
+    two, lean, lds = pkg.PLAN_TWO_WAVES, pkg.PLAN_LEAN, pkg.PLAN_ROWS_IN_LDS
+    assert pkg.serial_plan(False, 2, 1, 64) == lds and pkg.serial_plan(False, 3, 1, 64) == two | lds       # <6,1>, <10,2>
+    assert pkg.serial_plan(False, 3, 65, 57) == lds                                                        # <10,1>
+    assert pkg.serial_plan(False, 2, 1, 52000) == 0 and pkg.serial_plan(False, 3, 1, 52000) == two         # rows in memory
+    assert pkg.serial_plan(True, 2, 1, 64) == lds and pkg.serial_plan(True, 3, 1, 64) == lds               # decoder, cached, not lean
+    assert pkg.serial_plan(True, 2, 300, 57) == lean | lds and pkg.serial_plan(True, 3, 300, 57) == lean | lds
+    ctx = pkg.Context(device=0, n_slots=80, n_coders=4, n_groups=1, n_host_buffers=100)
+    try:
+        ctx.lsq_redo_counts(reset=True)
+        # the control: nothing is redone, nothing is counted
+        for effort in (2, 3):
+            img = inputs.syn1(64, 64, 1)
+            s, _ = ctx.encode_modes([img], [0], [effort])
+            assert s[0] == oracle.encode(img, 0, effort)[0]
+            d = ctx.decode_batch(s)[0]
+            assert np.array_equal(d[0], img) and ctx.lsq_redo_counts(reset=True) == (0, 0), effort
+        # model <6,1> and <10,2>; the cached decoder
+        for near, effort in [(2, 2), (9, 2), (1, 3), (2, 3), (9, 3)]:
+            ws, wrec, *_ = oracle.encode(step64, near, effort)
+            s, r = ctx.encode_modes([step64], [near], [effort])
+            assert s[0] == ws and np.array_equal(r[0], wrec), (near, effort)
+            _redo_row(rows, f"model <{6 if effort == 2 else 10},{1 if effort == 2 else 2}> step_v 64x64 -n{near} -e{effort}", ctx.lsq_redo_counts(reset=True))
+            d = ctx.decode_batch([ws])[0]
+            assert d is not None and np.array_equal(d[0], wrec) and d[1:] == (near, effort)
+            _redo_row(rows, f"decoder cached step_v 64x64 -n{near} -e{effort}", ctx.lsq_redo_counts(reset=True))
+        # lossless reaches the redo as well, rarely: a block plane found by search (inputs.make_hard)
+        lossless = inputs.make_hard("blocks_lossless", 0, 0)
+        for effort in (2, 3):
+            ws, wrec, *_ = oracle.encode(lossless, 0, effort)
+            s, r = ctx.encode_modes([lossless], [0], [effort])
+            d = ctx.decode_batch(s)[0]
+            assert s[0] == ws and np.array_equal(r[0], lossless) and d is not None and np.array_equal(d[0], lossless), effort
+            _redo_row(rows, f"model + decoder blocks 33x81 -n0 -e{effort}", ctx.lsq_redo_counts(reset=True))
+        # model <10,1>: 65 images of effort 3 in one launch (ONE group of 80 slots: a call's images of one effort share a launch)
+        for near in (1, 2, 9):
+            ws, wrec, *_ = oracle.encode(step33, near, 3)
+            launches = ctx.serial_launches()
+            s, r = ctx.encode_modes([step33] * 65, [near] * 65, [3] * 65)
+            assert ctx.serial_launches() - launches == 1                 # all 65 in one launch
+            assert all(x == ws for x in s) and all(np.array_equal(x, wrec) for x in r), near
+            c = ctx.lsq_redo_counts(reset=True)
+            _redo_row(rows, f"model <10,1> 65 x step_v 33x57 -n{near} -e3", c)
+            assert c[0] % 65 == 0                                          # the same image 65 times: the same pixels 65 times
+        # the lean decoder: 300 streams in one call
+        for near, effort in [(2, 2), (2, 3)]:
+            ws, wrec, *_ = oracle.encode(step33, near, effort)
+            dec = ctx.decode_batch([ws] * 300)
+            assert all(d is not None and np.array_equal(d[0], wrec) for d in dec), (near, effort)
+            c = ctx.lsq_redo_counts(reset=True)
+            _redo_row(rows, f"decoder lean 300 x step_v 33x57 -n{near} -e{effort}", c)
+            assert c[0] % 300 == 0
+        # the model with its rows in memory: 52000 pixels do not fit in LDS
+        wide = inputs.make_hard("bars_v", 4, 52000)
+        for near, effort in [(2, 2), (2, 3)]:
+            ws, wrec, *_ = oracle.encode(wide, near, effort)
+            s, r = ctx.encode_modes([wide], [near], [effort])
+            assert s[0] == ws and np.array_equal(r[0], wrec), (near, effort)
+            _redo_row(rows, f"model rows in memory bars_v 4x52000 -n{near} -e{effort}", ctx.lsq_redo_counts(reset=True))
+        # the band encoder, suspended after every band and resumed from the checkpoint
+        for near, effort in [(2, 2), (2, 3)]:
+            ws, wrec, *_ = oracle.encode(step64, near, effort)
+            pieces, ck, rec, total = [], None, np.zeros_like(step64), [0, 0]
+            while True:
+                st = ctx.stream(step64, near, effort, band_rows=24, checkpoint=ck)
+                done, piece = st.run(1e-9)
+                pieces.append(piece)
+                st.recon(rec)
+                if not done:
+                    ck = st.checkpoint()
+                st.close()
+                c = ctx.lsq_redo_counts(reset=True)
+                total = [total[0] + c[0], total[1] + c[1]]
+                if done:
+                    break
+            assert len(pieces) == 3 and b"".join(pieces) == ws and np.array_equal(rec, wrec), (near, effort)
+            _redo_row(rows, f"band encoder across checkpoints step_v 64x64 -n{near} -e{effort}", tuple(total))
+    finally:
+        ctx.close()
+    # the drop-in entry points (their own context)
+    pkg.default_lsq_redo_counts(reset=True)
+    for near, effort in [(2, 2), (2, 3)]:
+        ws, wrec, *_ = oracle.encode(step64, near, effort)
+        s, rec, _, _ = pkg.compress(step64, near, effort)
+        assert s == ws and np.array_equal(rec, wrec)
+        _redo_row(rows, f"NBLICcompress step_v 64x64 -n{near} -e{effort}", pkg.default_lsq_redo_counts(reset=True))
+        d = pkg.decompress(ws)
+        assert d is not None and np.array_equal(d[0], wrec)
+        _redo_row(rows, f"NBLICdecompress step_v 64x64 -n{near} -e{effort}", pkg.default_lsq_redo_counts(reset=True))

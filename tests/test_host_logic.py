@@ -2,46 +2,28 @@
 least-squares arithmetic (csrc/lsq_f64.h) that the serial GPU kernels use, compiled into a scalar
 harness (tests/host_harness.cpp) and checked against the oracle.  No GPU, no product library paths
 beyond the host range coder."""
-import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import inputs
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-u8p = C.POINTER(C.c_uint8)
+import lsq_cases
 
 
 @pytest.fixture(scope="module")
 def harness():
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libhost_harness.so")
-    src = os.path.join(ROOT, "tests", "host_harness.cpp")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-o", so, src], check=True)
-    lib = C.CDLL(so)
-    lib.hh_model_encode.restype = C.c_long
-    lib.hh_model_encode.argtypes = [u8p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint16), C.c_long, C.POINTER(C.c_long)]
-    lib.hh_check_divide_free.restype = C.c_long
-    lib.hh_check_lane_front.restype = C.c_long
-    lib.hh_check_symbol_lanes.restype = C.c_long
-    lib.hh_check_lane_front.argtypes = [C.c_int, C.c_int]
-    return lib
+    return lsq_cases.load_harness()
 
 
 def harness_encode(lib, pkg, img, near, effort):
+    """(stream, reconstruction, solves redone with integers, the same split by system)"""
     h, w = img.shape
-    rec = np.empty_like(img)
-    coded = np.empty(40 * h * w + 64, np.uint16)
-    fb = C.c_long(0)
-    n = lib.hh_model_encode(img.ctypes.data_as(u8p), rec.ctypes.data_as(u8p), h, w, near, effort,
-                            coded.ctypes.data_as(C.POINTER(C.c_uint16)), coded.size, C.byref(fb))
+    coded, rec, fallbacks, by_system, _ = lsq_cases.model_encode(lib, img, near, effort)
+    assert fallbacks == sum(by_system)
     k_step = min(max(3 + 2 * near, 3), 16)
     header = b"NBLIC0.3" + bytes([1, h >> 8, h & 255, w >> 8, w & 255, near, k_step, effort])
-    return header + pkg.range_code(coded[:n]), rec, fb.value
+    return header + pkg.range_code(coded), rec, fallbacks, by_system
 
 
 def test_divide_free_helpers_exhaustive(harness):
@@ -68,14 +50,21 @@ def test_model_headers_and_f64_least_squares_equal_oracle(harness, pkg, oracle, 
     for (h, w) in [(17, 13), (64, 64), (5, 300)]:
         for content in inputs.CONTENTS:
             img = inputs.make(content, h, w)
-            s, rec, _ = harness_encode(harness, pkg, img, near, effort)
+            s, rec, *_ = harness_encode(harness, pkg, img, near, effort)
+            ws, wrec, *_ = oracle.encode(img, near, effort)
+            assert s == ws and np.array_equal(rec, wrec), (h, w, content)
+        for content in inputs.HARD_EDGED:                       # two-level planes: the ones that reach the integer redo
+            img = inputs.make_hard(content, h, w)
+            s, rec, *_ = harness_encode(harness, pkg, img, near, effort)
             ws, wrec, *_ = oracle.encode(img, near, effort)
             assert s == ws and np.array_equal(rec, wrec), (h, w, content)
 
 
 def test_f64_least_squares_on_a_photograph_and_noise(harness, pkg, oracle):
     """Kodak crops (the stored 64x96 one; a 128x160 one read in place where the images are) and uniform noise at
-    effort 3: the exact-range guard may send pixels to the integer redo, the bytes must not change."""
+    effort 3: the exact-range guard may send pixels to the integer redo, the bytes must not change.  On these inputs it
+    sends none (the count is 0 in every case); the hard-edged planes below are the ones where it does -- at least eight
+    solves each, all of them system 0 -- and there the bytes must not change either."""
     meta, stored = inputs.fixtures()
     frames = [inputs.noise(96, 96, 3), stored["kodak_crops"][sorted(meta["kodak_crops"]).index("05.bmp")]]
     kodak = os.path.join(inputs.KODAK_DIR, "05.bmp")
@@ -83,6 +72,17 @@ def test_f64_least_squares_on_a_photograph_and_noise(harness, pkg, oracle):
         frames.append(np.ascontiguousarray(inputs.read_gray_bmp(kodak)[100:228, 200:360]))
     for img in frames:
         for near, effort in [(0, 3), (2, 2)]:
-            s, rec, fallbacks = harness_encode(harness, pkg, img, near, effort)
+            s, rec, fallbacks, _ = harness_encode(harness, pkg, img, near, effort)
             ws, wrec, *_ = oracle.encode(img, near, effort)
             assert s == ws and np.array_equal(rec, wrec)
+            assert fallbacks == 0                                # photographs and noise never reach the redo: hence the planes below
+    hard = [("step_v", 64, 64, [(2, 2), (9, 2), (1, 3), (2, 3), (9, 3)]), ("step_v", 33, 57, [(2, 2), (9, 2), (1, 3), (2, 3), (9, 3)]),
+            ("stripes_h", 64, 64, [(2, 2), (9, 2)]), ("step_h", 24, 1500, [(2, 2), (9, 2)]), ("stripes_h", 24, 1500, [(2, 2), (9, 2)]),
+            ("bars_v", 4, 52000, [(2, 2), (2, 3)]), ("bars_v", 6, 30000, [(2, 2), (2, 3)])]
+    for content, h, w, modes in hard:
+        img = inputs.make_hard(content, h, w)
+        for near, effort in modes:
+            s, rec, fallbacks, by_system = harness_encode(harness, pkg, img, near, effort)
+            ws, wrec, *_ = oracle.encode(img, near, effort)
+            assert s == ws and np.array_equal(rec, wrec), (content, h, w, near, effort)
+            assert fallbacks >= 8 and by_system == (fallbacks, 0), (content, h, w, near, effort, fallbacks, by_system)

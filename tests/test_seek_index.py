@@ -287,3 +287,30 @@ def test_indexed_decode_next_to_encode_batch(gpu_ctx, oracle):
     t.join()
     assert not errs, errs
     assert len(got) == 4 and all(np.array_equal(g, rec) for g in got)
+
+
+def test_integer_redo_on_each_side_of_a_segment_cut(gpu_ctx, pkg, oracle):
+    """A 64x64 step edge coded near-lossless at efforts 2 / 3 has pixels that the least squares redo with integers in its
+    upper AND its lower 32 rows (CPU harness: 9 + 40 at -n2 -e2, 19 + 3 at -n2 -e3).  With an index entry at row 32 the
+    two segments decode side by side to the oracle's plane; each row range decoded on its own counts redone pixels on the
+    device (Context.lsq_redo_counts), so the record the second segment starts from carries what the redo needs."""
+    img = inputs.make_hard("step_v", 64, 64)
+    for near, effort in ((2, 2), (2, 3)):
+        s, rec, *_ = oracle.encode(img, near, effort)
+        ix = gpu_ctx.build_index(s, 32)
+        assert pkg.check_index(ix, s) and len(pkg.index_entries(ix)) == 1
+        gpu_ctx.lsq_redo_counts(reset=True)
+        assert np.array_equal(gpu_ctx.decode_indexed(s, ix), rec), (near, effort)
+        both = gpu_ctx.lsq_redo_counts(reset=True)
+        assert np.array_equal(gpu_ctx.decode_rows(s, ix, 0, 32), rec[:32])
+        upper = gpu_ctx.lsq_redo_counts(reset=True)
+        assert np.array_equal(gpu_ctx.decode_rows(s, ix, 32, 64), rec[32:])
+        lower = gpu_ctx.lsq_redo_counts(reset=True)
+        print(f"lsq redo on the device: indexed decode step_v 64x64 -n{near} -e{effort}: rows 0..31 {upper}, rows 32..63 {lower}, both segments {both}")
+        assert upper[0] >= 1 and lower[0] >= 1 and both[0] == upper[0] + lower[0], (near, effort)
+        # the band encoder's own index cuts at the same row
+        st = gpu_ctx.stream(img, near, effort, band_rows=20, index_every=32)
+        done, whole = st.run()
+        own = st.index()
+        st.close()
+        assert done and whole == s and own == ix
