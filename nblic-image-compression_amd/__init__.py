@@ -424,6 +424,14 @@ def range_code_chunked(streams: Sequence[np.ndarray], chunk: int, caps: Optional
 # ---------------------------------------------------------------------------------------------
 # batch context
 # ---------------------------------------------------------------------------------------------
+def _batch_args(ptrs: Sequence[int], shapes: Sequence[Tuple[int, int]], outs: Sequence[np.ndarray]):
+    """The ctypes arrays every batch encode entry point takes: (imgs, hs, ws, outs, caps, lens); caps in elements of ``outs``."""
+    k = len(ptrs)
+    return ((C.c_void_p * k)(*[C.c_void_p(int(p)) for p in ptrs]),
+            (C.c_int * k)(*[int(s[0]) for s in shapes]), (C.c_int * k)(*[int(s[1]) for s in shapes]),
+            (C.c_void_p * k)(*[C.c_void_p(o.ctypes.data) for o in outs]), (C.c_size_t * k)(*[o.size for o in outs]), (C.c_long * k)())
+
+
 class Context:
     """Several images in flight on one GPU (``nblic_amd_create``)."""
 
@@ -477,14 +485,9 @@ class Context:
         k = len(planes)
         outs = [np.empty(out_capacity(*p.shape), np.uint8) for p in planes]
         recs = [np.empty_like(p) for p in planes] if want_recon else None
-        ip_ = (C.c_void_p * k)(*[C.c_void_p(p.ctypes.data) for p in planes])
-        hs = (C.c_int * k)(*[p.shape[0] for p in planes])
-        ws = (C.c_int * k)(*[p.shape[1] for p in planes])
+        ip_, hs, ws, op, caps, lens = _batch_args([p.ctypes.data for p in planes], [p.shape for p in planes], outs)
         nn = (C.c_int * k)(*[int(v) for v in nears])
         ee = (C.c_int * k)(*[int(v) for v in efforts])
-        op = (C.c_void_p * k)(*[C.c_void_p(o.ctypes.data) for o in outs])
-        caps = (C.c_size_t * k)(*[o.size for o in outs])
-        lens = (C.c_long * k)()
         rp = (C.c_void_p * k)(*[C.c_void_p(r.ctypes.data) for r in recs]) if want_recon else None
         if self.lib.nblic_amd_encode_batch_modes(self.handle, k, ip_, 0, hs, ws, nn, ee, op, caps, lens, rp) != 0:
             raise RuntimeError(f"nblic_amd_encode_batch_modes failed (lengths {list(lens)[:8]}...)")
@@ -613,12 +616,7 @@ class Context:
         k = len(ptrs)
         if outs is None:
             outs = [np.empty(out_capacity(h, w), np.uint8) for (h, w) in shapes]
-        imgs = (C.c_void_p * k)(*[C.c_void_p(int(p)) for p in ptrs])
-        hs = (C.c_int * k)(*[int(s[0]) for s in shapes])
-        ws = (C.c_int * k)(*[int(s[1]) for s in shapes])
-        op = (C.c_void_p * k)(*[C.c_void_p(o.ctypes.data) for o in outs])
-        caps = (C.c_size_t * k)(*[o.size for o in outs])
-        lens = (C.c_long * k)()
+        imgs, hs, ws, op, caps, lens = _batch_args(ptrs, shapes, outs)
         rc = self.lib.nblic_amd_encode_batch(self.handle, k, imgs, int(on_device), hs, ws, op, caps, lens)
         arr = np.array(list(lens), dtype=np.int64)
         if rc != 0:
@@ -632,12 +630,7 @@ class Context:
         k = len(ptrs)
         if outs is None:
             outs = [np.empty(out_capacity(h, w), np.uint8) for (h, w) in shapes]
-        imgs = (C.c_void_p * k)(*[C.c_void_p(int(p)) for p in ptrs])
-        hs = (C.c_int * k)(*[int(s[0]) for s in shapes])
-        ws = (C.c_int * k)(*[int(s[1]) for s in shapes])
-        op = (C.c_void_p * k)(*[C.c_void_p(o.ctypes.data) for o in outs])
-        caps = (C.c_size_t * k)(*[o.size for o in outs])
-        lens = (C.c_long * k)()
+        imgs, hs, ws, op, caps, lens = _batch_args(ptrs, shapes, outs)
         handle = self.lib.nblic_amd_encode_batch_begin(self.handle, k, imgs, int(on_device), hs, ws, op, caps, lens)
         if not handle:
             raise RuntimeError("nblic_amd_encode_batch_begin failed")
@@ -661,33 +654,18 @@ class Context:
                      outs: Optional[List[np.ndarray]] = None) -> Tuple[List[np.ndarray], np.ndarray]:
         """Effort-0 (QNBLIC) encode of planes given as raw addresses (host or device).  Returns
         (uint16 out buffers, lengths in 16-bit words)."""
-        k = len(ptrs)
         if outs is None:
             outs = [np.empty(out_capacity(h, w) // 2, np.uint16) for (h, w) in shapes]
-        ip_ = (C.c_void_p * k)(*[C.c_void_p(int(p)) for p in ptrs])
-        hs = (C.c_int * k)(*[int(s[0]) for s in shapes])
-        ws = (C.c_int * k)(*[int(s[1]) for s in shapes])
-        op = (C.c_void_p * k)(*[C.c_void_p(o.ctypes.data) for o in outs])
-        caps = (C.c_size_t * k)(*[o.size for o in outs])
-        lens = (C.c_long * k)()
-        if self.lib.nblic_amd_qencode_batch(self.handle, k, ip_, int(on_device), hs, ws, op, caps, lens) != 0:
+        ip_, hs, ws, op, caps, lens = _batch_args(ptrs, shapes, outs)
+        if self.lib.nblic_amd_qencode_batch(self.handle, len(ptrs), ip_, int(on_device), hs, ws, op, caps, lens) != 0:
             raise RuntimeError(f"nblic_amd_qencode_batch failed (lengths {list(lens)})")
         return outs, np.array(lens[:], np.int64)
 
     def qencode_batch(self, imgs: Sequence[np.ndarray]) -> List[bytes]:
         """Effort-0 (QNBLIC) encode of host planes; returns the streams as bytes (little-endian words)."""
         planes = [np.ascontiguousarray(i, np.uint8) for i in imgs]
-        k = len(planes)
-        outs = [np.empty(out_capacity(*p.shape) // 2, np.uint16) for p in planes]
-        ip_ = (C.c_void_p * k)(*[C.c_void_p(p.ctypes.data) for p in planes])
-        hs = (C.c_int * k)(*[p.shape[0] for p in planes])
-        ws = (C.c_int * k)(*[p.shape[1] for p in planes])
-        op = (C.c_void_p * k)(*[C.c_void_p(o.ctypes.data) for o in outs])
-        caps = (C.c_size_t * k)(*[o.size for o in outs])
-        lens = (C.c_long * k)()
-        if self.lib.nblic_amd_qencode_batch(self.handle, k, ip_, 0, hs, ws, op, caps, lens) != 0:
-            raise RuntimeError(f"nblic_amd_qencode_batch failed (lengths {list(lens)})")
-        return [o[: lens[i]].tobytes() for i, o in enumerate(outs)]
+        outs, lens = self.qencode_ptrs([p.ctypes.data for p in planes], [p.shape for p in planes], False)
+        return [o[:int(n)].tobytes() for o, n in zip(outs, lens)]
 
     def stage_times(self) -> dict:
         ms = (C.c_double * 64)()

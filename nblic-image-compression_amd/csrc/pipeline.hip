@@ -54,6 +54,21 @@ namespace nblic {
         }                                                                                     \
     } while (0)
 
+// NBLIC_AMD_DBG: OR-able measurement aids, read once per process.  Bits 8 and 256 mean something to the
+// kernels and travel there in E1Job::dbg (kernels_e1.h); the rest are the host's.
+enum DbgFlag : int {
+    kDbgDeviceOnly = 16,      // bins are produced but neither copied nor coded: device side alone
+    kDbgReport = 32,          // coder / driver accounting on stderr when a batch ends
+    kDbgTrace = 64,           // timeline of groups and coder takes on stderr
+    kDbgFeedOnly = 128,       // bins reach the host but are not coded
+    kDbgNoPackKernel = 512,   // (with kDbgFeedOnly) no pack kernel
+    kDbgNoCopy = 1024,        // (with kDbgFeedOnly) no copy
+};
+static int dbg_flags() {
+    static const int flags = [] { const char *v = getenv("NBLIC_AMD_DBG"); return v ? atoi(v) : 0; }();
+    return flags;
+}
+
 // ---- S6: 32-bit carry-less binary range coder (NBLIC.c:527-586), encoder side ------------
 // (range_coder.h: resumable, because the coder threads stream the bins from HBM in chunks)
 void RangeScalar::feed(const uint16_t *coded, size_t n) {
@@ -232,7 +247,7 @@ struct nblic_amd_ctx {
     std::mutex fm;                        // free groups / free coded-bin buffers / outstanding work
     std::condition_variable fcv;
     std::deque<int> free_groups;
-    bool trace = false;                      // NBLIC_AMD_DBG & 64: timeline of groups and coder takes on stderr
+    const bool trace = (dbg_flags() & kDbgTrace) != 0;   // timeline of groups and coder takes on stderr
     std::chrono::steady_clock::time_point t_batch;
     double now() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_batch).count(); }
     int coders_wanted = 0;                   // coder threads of this context (set before they start: pinning needs it)
@@ -270,7 +285,8 @@ struct nblic_amd_ctx {
     // Submission is asynchronous: _begin only queues the batch; the submitter thread hands its images to the groups
     // (which blocks while every group is busy), so a caller can keep several batches ahead of the pipeline.
     struct SubmitItem {
-        ::nblic_amd_batch *b; int n; const uint8_t *const *imgs; bool on_device; const int *hs, *ws;
+        ::nblic_amd_batch *b; int kind;       // 0 NBLIC (per image near / effort), 1 QNBLIC (outs are uint16_t streams, caps / lens in words)
+        int n; const uint8_t *const *imgs; bool on_device; const int *hs, *ws;
         uint8_t *const *outs; const size_t *caps; long *lens; const int *nears, *efforts; unsigned char *const *recons;
     };
     std::thread submitter;
@@ -297,6 +313,54 @@ struct nblic_amd_ctx {
 };
 
 namespace nblic {
+
+// ---- the small protocols under ctx->fm: groups, coded-bin buffers, outstanding images --------------------------------
+// A free group of the context (waits for one: every group busy is the back-pressure on submission).
+static int take_group(nblic_amd_ctx *c) {
+    std::unique_lock<std::mutex> l(c->fm);
+    c->fcv.wait(l, [c] { return !c->free_groups.empty(); });
+    const int id = c->free_groups.front();
+    c->free_groups.pop_front();
+    return id;
+}
+
+static void release_group(nblic_amd_ctx *c, int id) {
+    { std::lock_guard<std::mutex> g(c->fm); c->free_groups.push_back(id); }
+    c->fcv.notify_all();
+}
+
+static bool nothing_outstanding(nblic_amd_ctx *c) {
+    std::lock_guard<std::mutex> l(c->fm);
+    return c->coding == 0;
+}
+
+// The coded-bin buffer a slot took for an image that will not reach a coder goes back to the pool.
+static void return_coded(nblic_amd_ctx *c, Slot &s) {
+    if (s.cb < 0) return;
+    std::lock_guard<std::mutex> l(c->fm);
+    c->free_cbufs.push_back(s.cb);
+    s.cb = -1;
+}
+
+// n images are finished (lens written): their coded-bin buffers go back, and they are counted off their batches and
+// off the context's outstanding work.
+static void finish_images(nblic_amd_ctx *c, const ReadyImage *im, int n) {
+    {
+        std::lock_guard<std::mutex> l(c->fm);
+        for (int k = 0; k < n; k++) { c->free_cbufs.push_back(im[k].cb); im[k].batch->remaining -= 1; }
+        c->coding -= n;
+    }
+    c->fcv.notify_all();
+}
+
+// Where an NBLIC image's coder bytes go: the caller's capacity clamped (SIZE_MAX means "no limit"), the 16-byte header
+// written if it fits.  Returns the first byte after the header; *room = bytes the coder may write there.
+static uint8_t *begin_stream_out(const ReadyImage &im, size_t *room) {
+    const size_t cap = std::min(im.caps[im.job], size_t(1) << 46);
+    *room = cap >= size_t(kHeaderBytes) ? cap - kHeaderBytes : 0;
+    if (cap >= size_t(kHeaderBytes)) write_header(im.outs[im.job], im.h, im.w, im.near, im.k_step, im.effort);
+    return im.outs[im.job] + kHeaderBytes;
+}
 
 static bool group_init(Group &g, int id, int n_slots, nblic_amd_ctx *c) {
     g.id = id; g.ctx = c;
@@ -368,23 +432,57 @@ static bool ensure_pixels(Slot &s, size_t n, bool with_events = true) {
     return with_events ? ensure_events(s, 5 * n) : true;   // typical images need 4.3-4.5 bins/px (ensure_events adds 1/8); grown on demand
 }
 
+// ---- job records: the only code that fills an E1Job, or a SerialJob for the encoders' model stage -------------------
+// The back half's view of a job: the buffers as they are now (the event-sized ones may have grown, `coded` is known)
+// and the bin count with its partition plan.
+static void e1_job_back(E1Job &J, const E1Buffers &b, uint32_t n_ev) {
+    J.b = b; J.n_ev = n_ev; J.pe = make_plan(n_ev, kTouchSegments);
+}
+
+// The job of `rows` x w pixels in workspace b as a front half sees it: no bins yet (their count is its result).
+// near is 0 for the staged -e1 and the QNBLIC kernels, which use the lossless constants whatever the record says;
+// dbg is NBLIC_AMD_DBG for the staged -e1 kernels and 0 for everything else.
+static E1Job e1_job_front(const E1Buffers &b, int rows, int w, int near, int dbg) {
+    E1Job J{};
+    J.h = rows; J.w = w; J.n = uint32_t(size_t(rows) * size_t(w)); J.pp = make_plan(J.n); J.dbg = dbg;
+    J.near = near; J.k_step = k_step_for_near(near); J.ktab = level_shift_table(J.k_step);
+    e1_job_back(J, b, 0);
+    return J;
+}
+
+// The job of k_serial_model for an image of h x w: `rows` rows per launch, whose records go to b.rec1 / b.pxs from
+// index 0 on (out_row0: the image row that sits there -- 0, or the first row of a band).
+static SerialJob model_job(const uint8_t *img, uint8_t *recon, const E1Buffers &b, double *stats, SerialState *state, int h, int w,
+                           int near, int effort, int rows, int out_row0, unsigned long long *redo) {
+    SerialJob Q{};
+    Q.img = img; Q.recon = recon; Q.rec1 = b.rec1; Q.pxs = b.pxs; Q.stats = stats; Q.state = state;
+    Q.h = h; Q.w = w; Q.near = near; Q.k_step = k_step_for_near(near); Q.effort = effort;
+    Q.rows = rows; Q.out_row0 = out_row0; Q.redo = redo;
+    return Q;
+}
+
+// What every front half starts with for slot k of group g (which already carries job / h / w / near): its workspace,
+// its input plane on the device -- the caller's, or a copy on the group's stream -- and its job record.
+static bool slot_begin(Group &g, int k, const uint8_t *const *imgs, bool on_device, bool with_events, int dbg) {
+    Slot &s = g.slots[size_t(k)];
+    const size_t n = size_t(s.h) * size_t(s.w);
+    if (!ensure_pixels(s, n, with_events)) return false;
+    if (on_device) {
+        s.b.img = imgs[s.job];
+    } else {
+        if (n > s.img_cap) { if (!dev_alloc(s.d_img, n)) return false; s.img_cap = n; }
+        HIP_OK(hipMemcpyAsync(s.d_img, imgs[s.job], n, hipMemcpyHostToDevice, g.stream));
+        s.b.img = s.d_img;
+    }
+    s.n_ev = 0;
+    g.h_jobs[k] = e1_job_front(s.b, s.h, s.w, s.near, dbg);
+    return true;
+}
+
 // Front half for the images assigned to group g (slots 0..n_jobs-1 already carry job/h/w).
 static bool launch_front(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device) {
-    for (int k = 0; k < g.n_jobs; k++) {
-        Slot &s = g.slots[size_t(k)];
-        size_t n = size_t(s.h) * size_t(s.w);
-        if (!ensure_pixels(s, n)) return false;
-        if (on_device) {
-            s.b.img = imgs[s.job];
-        } else {
-            if (n > s.img_cap) { if (!dev_alloc(s.d_img, n)) return false; s.img_cap = n; }
-            HIP_OK(hipMemcpyAsync(s.d_img, imgs[s.job], n, hipMemcpyHostToDevice, g.stream));
-            s.b.img = s.d_img;
-        }
-        E1Job &J = g.h_jobs[k];
-        J.b = s.b; J.h = s.h; J.w = s.w; J.n = uint32_t(n); J.pp = make_plan(J.n); J.n_ev = 0; J.pe = make_plan(0, kTouchSegments);
-        { static const int dbg = getenv("NBLIC_AMD_DBG") ? atoi(getenv("NBLIC_AMD_DBG")) : 0; J.dbg = dbg; }
-    }
+    for (int k = 0; k < g.n_jobs; k++)
+        if (!slot_begin(g, k, imgs, on_device, true, dbg_flags())) return false;
     HIP_OK(hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(g.n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, g.stream));
     g.tm.mask = c->timing_mask;
     e1_launch_front(g.d_jobs, g.h_jobs, g.n_jobs, g.stream, c->timing ? &g.tm : nullptr);
@@ -398,30 +496,17 @@ static bool launch_front(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs,
 // the re-mapper partition and chains and the bin counts.
 static bool launch_front_serial(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device) {
     for (int k = 0; k < g.n_jobs; k++) {
+        if (!slot_begin(g, k, imgs, on_device, true, 0)) return false;
         Slot &s = g.slots[size_t(k)];
         const size_t n = size_t(s.h) * size_t(s.w);
-        if (!ensure_pixels(s, n)) return false;
-        if (on_device) {
-            s.b.img = imgs[s.job];
-        } else {
-            if (n > s.img_cap) { if (!dev_alloc(s.d_img, n)) return false; s.img_cap = n; }
-            HIP_OK(hipMemcpyAsync(s.d_img, imgs[s.job], n, hipMemcpyHostToDevice, g.stream));
-            s.b.img = s.d_img;
-        }
         const bool wide = !serial_model_rows_fit(s.w);                   // rows do not fit in LDS: taps come from the reconstruction in memory
         const bool want_recon = s.near > 0 || wide;
         if (want_recon && n > s.recon_cap) { if (!dev_alloc(s.d_recon, n)) return false; s.recon_cap = n; }
         const size_t st = stats_doubles(s.effort, s.w);
         if (st > s.stats_cap) { if (!dev_alloc(s.d_stats, st)) return false; s.stats_cap = st; }
         if (st) HIP_OK(hipMemsetAsync(s.d_stats, 0, st * sizeof(double), g.stream));         // NBLIC.c:789
-        E1Job &J = g.h_jobs[k];
-        J.b = s.b; J.h = s.h; J.w = s.w; J.n = uint32_t(n); J.pp = make_plan(J.n); J.n_ev = 0; J.pe = make_plan(0, kTouchSegments); J.dbg = 0;
-        J.near = s.near; J.k_step = k_step_for_near(s.near); J.ktab = level_shift_table(J.k_step);
-        SerialJob &Q = g.h_sjobs[k];
-        Q = SerialJob{};
-        Q.img = s.b.img; Q.recon = want_recon ? s.d_recon : nullptr; Q.rec1 = s.b.rec1; Q.pxs = s.b.pxs; Q.stats = s.d_stats;
-        Q.h = s.h; Q.w = s.w; Q.near = s.near; Q.k_step = J.k_step; Q.effort = s.effort;
-        Q.state = s.d_state; Q.rows = serial_rows_per_launch(s.h, s.w, s.effort, c->serial_rows); Q.redo = c->d_redo;
+        g.h_sjobs[k] = model_job(s.b.img, want_recon ? s.d_recon : nullptr, s.b, s.d_stats, s.d_state, s.h, s.w, s.near, s.effort,
+                                 serial_rows_per_launch(s.h, s.w, s.effort, c->serial_rows), 0, c->d_redo);
         HIP_OK(hipMemsetAsync(s.d_state, 0, sizeof(SerialState), g.stream));               // a fresh image: row 0, running
     }
     HIP_OK(hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(g.n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, g.stream));
@@ -554,6 +639,21 @@ struct CoderThread {
     uint64_t *dev_rows(size_t chunk) { return d_rows + size_t(chunk % kRingDepth) * group_words(ring_chunk, ring_lanes); }
 };
 
+// How `take` images go to the AVX-512 packs (the coder threads, and nblic_amd_range_code_chunked that tests them).
+// More than one image: packs in lock-step -- a lone pack is bound by the latency of its own dependent chain, a second
+// one rides along almost for free, a third on what the core's ports have left (+20 % bins per CPU-second on the
+// records of real frames, and the rank's CPU quota is what bounds the pipeline).  Up to sixteen images make two packs
+// (16 lanes per word-row), more make three (24 lanes); the images are dealt to the packs in order, as evenly as they
+// go: pack p owns lanes 8p .. 8p + pack_n[p] - 1.  One image: no pack, the scalar coder.
+struct PackDeal {
+    int n_packs, pack_n[3] = {0, 0, 0}, pack_first[3] = {0, 0, 0};
+    explicit PackDeal(int take) : n_packs(take > 16 ? 3 : (take > 1 ? 2 : 0)) {
+        for (int p = 0, at = 0; p < n_packs; p++) { pack_n[p] = take / n_packs + (p < take % n_packs ? 1 : 0); pack_first[p] = at; at += pack_n[p]; }
+    }
+    size_t lanes() const { return size_t(8 * n_packs); }
+    int lane_of(int k) const { int p = 0; while (p + 1 < n_packs && k >= pack_first[p + 1]) p++; return 8 * p + (k - pack_first[p]); }
+};
+
 // Streams `take` images' bins from HBM and codes them: one image with the scalar coder, up to
 // eight in the lanes of the AVX-512 coder, up to sixteen as two packs in lock-step.
 // lens[k] = coder bytes or SIZE_MAX.
@@ -561,19 +661,12 @@ static bool code_streamed(CoderThread &t, const uint16_t *const *dev, const size
                           const size_t *caps, size_t *lens, size_t chunk_bins) {
     size_t n_max = 0;
     for (int k = 0; k < take; k++) n_max = n[k] > n_max ? n[k] : n_max;
-    // More than one image: AVX-512 packs in lock-step -- a lone pack is bound by the latency of its own dependent
-    // chain, a second one rides along almost for free, a third on what the core's ports have left (+20 % bins per
-    // CPU-second on the records of real frames, and the rank's CPU quota is what bounds the pipeline).  Up to sixteen
-    // images make two packs (16 lanes per word-row), more make three (24 lanes); the images are dealt to the packs
-    // in order, as evenly as they go: pack p owns lanes 8p .. 8p + count_p - 1.
-    const int n_packs = take > 16 ? 3 : (take > 1 ? 2 : 0);
-    const size_t lanes = size_t(8 * n_packs);
-    int pack_n[3] = {0, 0, 0}, pack_first[3] = {0, 0, 0};
-    for (int p = 0, at = 0; p < n_packs; p++) { pack_n[p] = take / n_packs + (p < take % n_packs ? 1 : 0); pack_first[p] = at; at += pack_n[p]; }
+    const PackDeal deal(take);
+    const int n_packs = deal.n_packs;
+    const size_t lanes = deal.lanes();
     if (!t.ensure_ring(take > 1 ? lanes : 1, n_max < chunk_bins ? n_max + 4 : chunk_bins, take > 1)) return false;
     const size_t chunks = (n_max + chunk_bins - 1) / chunk_bins;                     // chunk_bins <= kChunkBins, the ring's slot size
     auto chunk_len = [&](size_t c, int k) { const size_t off = c * chunk_bins; return off >= n[k] ? size_t(0) : (n[k] - off < chunk_bins ? n[k] - off : chunk_bins); };
-    auto lane_of = [&](int k) { int p = 0; while (p + 1 < n_packs && k >= pack_first[p + 1]) p++; return 8 * p + (k - pack_first[p]); };
     auto issue = [&](size_t c) -> bool {
         if (take == 1) {                                      // one image: its bins as they are, for the scalar coder
             HIP_OK(hipMemcpyAsync(t.slot(c), dev[0] + c * chunk_bins, chunk_len(c, 0) * sizeof(uint16_t), hipMemcpyDeviceToHost, t.stream));
@@ -582,7 +675,7 @@ static bool code_streamed(CoderThread &t, const uint16_t *const *dev, const size
             size_t longest = 0;
             for (int k = 0; k < take; k++) {
                 const size_t len = chunk_len(c, k);
-                a.src[lane_of(k)] = dev[k] + c * chunk_bins; a.len[lane_of(k)] = uint32_t(len);
+                a.src[deal.lane_of(k)] = dev[k] + c * chunk_bins; a.len[deal.lane_of(k)] = uint32_t(len);
                 longest = len > longest ? len : longest;
             }
             const uint32_t n_groups = uint32_t((longest + kGroupBins - 1) / kGroupBins);
@@ -590,14 +683,13 @@ static bool code_streamed(CoderThread &t, const uint16_t *const *dev, const size
             // grid: 4.6 -> 2.4 Gpx/s.  Round 2, small grids so that few CUs wait on the link: 3.34 / 2.68 / 2.46 Gpx/s with
             // 16 / 48 / 128 workgroups per chunk against 5.5 with the staging pass + runtime copy.)
             uint64_t *d = t.dev_rows(c);
-            static const int feed_dbg = getenv("NBLIC_AMD_DBG") ? atoi(getenv("NBLIC_AMD_DBG")) : 0;      // measurement aids (with & 128): & 512 no pack kernel, & 1024 no copy
             if (n_groups) {
-                if (!(feed_dbg & 512)) hipLaunchKernelGGL(k_pack_groups, dim3((n_groups * uint32_t(kGroupWords) * uint32_t(lanes) + 255u) / 256u), dim3(256), 0, t.stream, a, d, n_groups * uint32_t(kGroupWords), uint32_t(lanes));
+                if (!(dbg_flags() & kDbgNoPackKernel)) hipLaunchKernelGGL(k_pack_groups, dim3((n_groups * uint32_t(kGroupWords) * uint32_t(lanes) + 255u) / 256u), dim3(256), 0, t.stream, a, d, n_groups * uint32_t(kGroupWords), uint32_t(lanes));
                 HIP_OK(hipGetLastError());
                 // (In this pipeline the runtime performs the copy with its blit kernel -- four 32 MB dispatches per 128 MB chunk --
                 // whatever was tried: ring from hipHostMalloc instead of hipHostRegister, 2 / 4 / 8 copy streams, the copy cut
                 // into 8 or 16 MB pieces; the same copy from a bare test program goes through SDMA.  DESIGN.md section 4.)
-                if (!(feed_dbg & 1024)) HIP_OK(hipMemcpyAsync(t.rows(c), d, group_words(longest, lanes) * sizeof(uint64_t), hipMemcpyDeviceToHost, t.stream));
+                if (!(dbg_flags() & kDbgNoCopy)) HIP_OK(hipMemcpyAsync(t.rows(c), d, group_words(longest, lanes) * sizeof(uint64_t), hipMemcpyDeviceToHost, t.stream));
             }
         }
         // (Measured and rejected: sleeping on a condition variable woken by a host function behind the copy, as the
@@ -608,7 +700,7 @@ static bool code_streamed(CoderThread &t, const uint16_t *const *dev, const size
         return true;
     };
     RangeX8 *const packs[3] = {&t.x8, &t.x8b, &t.x8c};
-    if (take > 1) { for (int p = 0; p < n_packs; p++) packs[p]->begin(pack_n[p], dst + pack_first[p], caps + pack_first[p]); }
+    if (take > 1) { for (int p = 0; p < n_packs; p++) packs[p]->begin(deal.pack_n[p], dst + deal.pack_first[p], caps + deal.pack_first[p]); }
     else t.x1.begin(dst[0], caps[0]);
     for (size_t c = 0; c + 1 < size_t(kRingDepth) && c < chunks; c++) if (!issue(c)) return false;
     for (size_t c = 0; c < chunks; c++) {
@@ -627,16 +719,15 @@ static bool code_streamed(CoderThread &t, const uint16_t *const *dev, const size
         t.wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
         if (take > 1) {
             size_t len[kMaxTake] = {0};
-            for (int k = 0; k < take; k++) len[lane_of(k)] = chunk_len(c, k);
-            static const bool feed_only = getenv("NBLIC_AMD_DBG") && (atoi(getenv("NBLIC_AMD_DBG")) & 128);   // measurement aid: bins reach the host but are not coded
-            if (feed_only) {}
+            for (int k = 0; k < take; k++) len[deal.lane_of(k)] = chunk_len(c, k);
+            if (dbg_flags() & kDbgFeedOnly) {}
             else if (n_packs == 3) feed_triple_groups(t.x8, t.x8b, t.x8c, t.rows(c), len);
             else feed_pair_groups(t.x8, t.x8b, t.rows(c), len);
         } else {
             t.x1.feed(t.slot(c), chunk_len(c, 0));
         }
     }
-    if (take > 1) { for (int p = 0; p < n_packs; p++) packs[p]->end(lens + pack_first[p]); }
+    if (take > 1) { for (int p = 0; p < n_packs; p++) packs[p]->end(lens + deal.pack_first[p]); }
     else lens[0] = t.x1.finish();
     return true;
 }
@@ -748,8 +839,7 @@ static void coder_main(nblic_amd_ctx *c, int index) {
                 if (words_out < 0) fprintf(stderr, "[nblic_amd] image %d: output buffer of %zu words is too small\n", q.job, q.caps[q.job]);
             }
             q.lens[q.job] = words_out;                           // -1: the batch this image belongs to reports the failure
-            { std::lock_guard<std::mutex> l(c->fm); c->free_cbufs.push_back(q.cb); c->coding -= 1; if (q.batch) q.batch->remaining -= 1; }
-            c->fcv.notify_all();
+            finish_images(c, im, 1);
             continue;
         }
         auto t0 = std::chrono::steady_clock::now();
@@ -758,13 +848,9 @@ static void coder_main(nblic_amd_ctx *c, int index) {
         double bins = 0;
         for (int k = 0; k < take; k++) {
             src[k] = c->cbufs[size_t(im[k].cb)].p; n[k] = im[k].n_ev; bins += double(im[k].n_ev);
-            const size_t cap = im[k].caps[im[k].job] < (size_t(1) << 46) ? im[k].caps[im[k].job] : (size_t(1) << 46);   // SIZE_MAX = "no limit"
-            dst[k] = im[k].outs[im[k].job] + kHeaderBytes;
-            caps[k] = cap >= size_t(kHeaderBytes) ? cap - kHeaderBytes : 0;
-            if (cap >= size_t(kHeaderBytes)) write_header(im[k].outs[im[k].job], im[k].h, im[k].w, im[k].near, im[k].k_step, im[k].effort);
+            dst[k] = begin_stream_out(im[k], &caps[k]);
         }
-        static const bool skip_coding = getenv("NBLIC_AMD_DBG") && (atoi(getenv("NBLIC_AMD_DBG")) & 16);   // measurement aid: device side alone
-        if (skip_coding) { for (int k = 0; k < take; k++) lens[k] = 0; }
+        if (dbg_flags() & kDbgDeviceOnly) { for (int k = 0; k < take; k++) lens[k] = 0; }
         else if (!code_streamed(t, src, n, take, dst, caps, lens, c->chunk_bins)) {
             hipDeviceSynchronize();
             for (int k = 0; k < take; k++) lens[k] = SIZE_MAX;
@@ -776,12 +862,7 @@ static void coder_main(nblic_amd_ctx *c, int index) {
         double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (c->trace) fprintf(stderr, "[trace] %.3f coder %d finished %d in %.3f s\n", c->now(), index, take, dt);
         { std::lock_guard<std::mutex> l(c->stat_m); c->total_bins += bins; c->coder_s += dt; if (take > 1) { c->pack_bins += bins; c->pack_s += dt; } c->wait_s += t.wait_s; t.wait_s = 0; c->issue_s += t.issue_s; t.issue_s = 0; c->takes[take]++; }
-        {
-            std::lock_guard<std::mutex> l(c->fm);
-            for (int k = 0; k < take; k++) { c->free_cbufs.push_back(im[k].cb); if (im[k].batch) im[k].batch->remaining -= 1; }
-            c->coding -= take;
-        }
-        c->fcv.notify_all();
+        finish_images(c, im, take);
     }
     t.destroy();
 }
@@ -835,10 +916,11 @@ static void dev_coder_main(nblic_amd_ctx *c, int index) {
         bool good = ok;
         if (good && need > out_cap) { hipFree(d_out); d_out = nullptr; out_cap = 0; good = hipMalloc((void **)&d_out, need) == hipSuccess; if (good) out_cap = need; }
         double bins = 0;
+        uint8_t *dst[kDevPack];
         for (int k = 0; k < take && good; k++) {
-            const size_t cap_user = im[k].caps[im[k].job] < (size_t(1) << 40) ? im[k].caps[im[k].job] : (size_t(1) << 40);
-            const size_t cap_dev = (k + 1 < take ? off[k + 1] : need) - off[k];
-            const size_t cap = cap_user > size_t(kHeaderBytes) ? (cap_user - kHeaderBytes < cap_dev ? cap_user - kHeaderBytes : cap_dev) : 0;
+            size_t room;
+            dst[k] = begin_stream_out(im[k], &room);
+            const size_t cap = std::min(room, (k + 1 < take ? off[k + 1] : need) - off[k]);
             h_jobs[k] = RcJob{c->cbufs[size_t(im[k].cb)].p, d_out + off[k], d_lens + k, im[k].n_ev, uint32_t(cap < 0xFFFFFFF0u ? cap : 0xFFFFFFF0u)};
             bins += double(im[k].n_ev);
         }
@@ -849,9 +931,7 @@ static void dev_coder_main(nblic_amd_ctx *c, int index) {
         for (int k = 0; k < take; k++) {
             long len = -1;
             if (good && h_lens[k] != 0xFFFFFFFFu) {
-                unsigned char *dst = im[k].outs[im[k].job];
-                write_header(dst, im[k].h, im[k].w, im[k].near, im[k].k_step, im[k].effort);
-                if (hipMemcpyAsync(dst + kHeaderBytes, d_out + off[k], h_lens[k], hipMemcpyDeviceToHost, st) == hipSuccess) len = long(kHeaderBytes) + long(h_lens[k]);
+                if (hipMemcpyAsync(dst[k], d_out + off[k], h_lens[k], hipMemcpyDeviceToHost, st) == hipSuccess) len = long(kHeaderBytes) + long(h_lens[k]);
             } else if (good) {
                 fprintf(stderr, "[nblic_amd] image %d: output buffer of %zu bytes is too small\n", im[k].job, im[k].caps[im[k].job]);
             }
@@ -860,12 +940,7 @@ static void dev_coder_main(nblic_amd_ctx *c, int index) {
         if (hipStreamSynchronize(st) != hipSuccess) good = false;
         if (!good) { for (int k = 0; k < take; k++) im[k].lens[im[k].job] = -1; }
         { std::lock_guard<std::mutex> l(c->stat_m); c->dev_bins += bins; c->dev_packs++; c->dev_images += take; }
-        {
-            std::lock_guard<std::mutex> l(c->fm);
-            for (int k = 0; k < take; k++) { c->free_cbufs.push_back(im[k].cb); if (im[k].batch) im[k].batch->remaining -= 1; }
-            c->coding -= take;
-        }
-        c->fcv.notify_all();
+        finish_images(c, im, take);
     }
     hipFree(d_out); hipFree(d_jobs); hipFree(d_lens);
     if (h_jobs) hipHostFree(h_jobs);
@@ -908,8 +983,7 @@ static void on_group_done(void *vp) {
         c->batch_to_come -= gp->n_jobs;
     }
     c->rcv.notify_all();
-    { std::lock_guard<std::mutex> l(c->fm); c->free_groups.push_back(gp->id); }
-    c->fcv.notify_all();
+    release_group(c, gp->id);
 }
 
 static double thread_cpu_s();
@@ -940,8 +1014,7 @@ static bool launch_back(nblic_amd_ctx *c, Group &g, bool with_coders, bool gener
         // the coded bins go straight into a pool buffer that outlives this group's turn on the slot
         if (!acquire_coded(c, s, size_t(s.n_ev) + 8)) return false;
         s.b.coded = c->cbufs[size_t(s.cb)].p;
-        E1Job &J = g.h_jobs[k];
-        J.b = s.b; J.n_ev = s.n_ev; J.pe = make_plan(s.n_ev, kTouchSegments);
+        e1_job_back(g.h_jobs[k], s.b, s.n_ev);
     }
     HIP_OK(hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(g.n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, g.stream));
     e1_launch_back(g.d_jobs, g.h_jobs, g.n_jobs, g.stream, (c->timing && !general) ? &g.tm : nullptr, general);
@@ -961,11 +1034,6 @@ static void collect_timing(nblic_amd_ctx *c, Group &g) {
         if (((g.tm.mask >> k) & 1ull) && hipEventElapsedTime(&ms, g.tm.ev[k], g.tm.ev[k + 1]) == hipSuccess) c->stage_ms[k] += ms;
     }
     c->stage_launches++;
-}
-
-static void release_group(nblic_amd_ctx *c, int id) {
-    { std::lock_guard<std::mutex> g(c->fm); c->free_groups.push_back(id); }
-    c->fcv.notify_all();
 }
 
 static bool launch_q(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device);
@@ -994,16 +1062,10 @@ static void driver_main(nblic_amd_ctx *c, int id) {
         { std::lock_guard<std::mutex> l(c->stat_m); c->driver_cpu_s += thread_cpu_s() - cpu0; c->driver_launches++; }
         if (!ok) {
             hipStreamSynchronize(g.stream);
-            {   // coded-bin buffers the failed launch had already taken go back to the pool
-                std::lock_guard<std::mutex> l(c->fm);
-                for (int k = 0; k < g.n_jobs; k++) {
-                    Slot &s = g.slots[size_t(k)];
-                    if (s.cb >= 0) { c->free_cbufs.push_back(s.cb); s.cb = -1; }
-                }
-            }
+            for (int k = 0; k < g.n_jobs; k++) return_coded(c, g.slots[size_t(k)]);   // what the failed launch had already taken
             { std::lock_guard<std::mutex> l(c->rm); c->batch_to_come -= g.n_jobs; }
             c->rcv.notify_all();                                 // a pack may be waiting for images that will not come
-            { std::lock_guard<std::mutex> l(c->fm); c->coding -= g.n_jobs; if (g.batch) { g.batch->remaining -= g.n_jobs; g.batch->ok = false; } }
+            { std::lock_guard<std::mutex> l(c->fm); c->coding -= g.n_jobs; g.batch->remaining -= g.n_jobs; g.batch->ok = false; }
             release_group(c, id);
         }
     }
@@ -1012,7 +1074,7 @@ static void driver_main(nblic_amd_ctx *c, int id) {
 // The images are counted as outstanding BEFORE the driver thread is woken, so the batch's final
 // wait cannot slip through between the hand-over and the launch.
 static void start_group(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device) {
-    { std::lock_guard<std::mutex> l(c->fm); c->coding += g.n_jobs; if (g.batch) g.batch->remaining += g.n_jobs; }
+    { std::lock_guard<std::mutex> l(c->fm); c->coding += g.n_jobs; g.batch->remaining += g.n_jobs; }
     { std::lock_guard<std::mutex> l(c->dm); g.imgs = imgs; g.on_device = on_device; g.has_work = true; }
     c->dcv.notify_all();
 }
@@ -1023,61 +1085,54 @@ static void start_group(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, 
 // busy, i.e. until the GPU is down to its last few groups of this batch).  The coder threads and the
 // groups still in flight finish on their own; encode_wait() collects.  Several batches may be
 // outstanding: the next one fills the pipeline while this one drains.
-static void encode_submit(nblic_amd_ctx *c, nblic_amd_batch *b, int n_images, const uint8_t *const *imgs, bool on_device,
-                          const int *hs, const int *ws, uint8_t *const *outs, const size_t *caps, long *lens,
-                          const int *nears = nullptr, const int *efforts = nullptr, unsigned char *const *recons = nullptr) {
-    bool idle;
-    { std::lock_guard<std::mutex> l(c->fm); idle = c->coding == 0; }
-    if (idle) {                                                   // nothing outstanding: start the reporting afresh
+static void encode_submit(nblic_amd_ctx *c, const nblic_amd_ctx::SubmitItem &it) {
+    nblic_amd_batch *const b = it.b;
+    if (nothing_outstanding(c)) {                                 // start the reporting afresh
         for (auto &gr : c->groups) gr.tm_pending = false;         // (timer events of earlier batches that nobody collected belong to THEIR figures, not to this batch's)
         for (auto &v : c->stage_ms) v = 0;
         c->stage_launches = 0;
         c->total_bins = 0; c->coder_s = 0; c->pack_bins = 0; c->pack_s = 0; c->wait_s = 0; c->issue_s = 0; c->driver_cpu_s = 0; c->driver_wait_cpu_s = 0; c->driver_launches = 0; for (auto &v : c->takes) v = 0;
         c->dev_bins = 0; c->dev_packs = 0; c->dev_images = 0;
         c->t_batch = std::chrono::steady_clock::now();
-        c->trace = getenv("NBLIC_AMD_DBG") && (atoi(getenv("NBLIC_AMD_DBG")) & 64);
     }
-    b->n_images = n_images; b->lens = lens;
-    for (int k = 0; k < n_images; k++) lens[k] = -1;
+    b->n_images = it.n; b->lens = it.lens;
+    for (int k = 0; k < it.n; k++) it.lens[k] = -1;
     // modes: (near, effort) clamped as the reference clamps them (NBLIC.c:768-770); -n0 -e1 images take the
-    // staged pipeline (kind 0), everything else the serial model stage (kind 2).  Images are handed out kind by
-    // kind and, inside kind 2, effort by effort, so a group's launches are homogeneous.
-    auto near_of = [&](int k) { return nears ? iclip(nears[k], 0, kMaxNear) : 0; };
-    auto effort_of = [&](int k) { return efforts ? iclip(efforts[k], 1, 3) : 1; };
-    auto class_of = [&](int k) { return (near_of(k) == 0 && effort_of(k) == 1) ? 0 : effort_of(k); };   // 0 staged; 1..3 serial by effort
+    // staged pipeline (kind 0), everything else the serial model stage (kind 2); a QNBLIC batch is one class of its
+    // own (kind 1).  Images are handed out kind by kind and, inside kind 2, effort by effort, so a group's launches
+    // are homogeneous.
+    auto near_of = [&](int k) { return it.nears ? iclip(it.nears[k], 0, kMaxNear) : 0; };
+    auto effort_of = [&](int k) { return it.efforts ? iclip(it.efforts[k], 1, 3) : 1; };
+    auto class_of = [&](int k) { return it.kind == 1 ? 4 : (near_of(k) == 0 && effort_of(k) == 1) ? 0 : effort_of(k); };   // 0 staged; 1..3 serial by effort; 4 QNBLIC
+    auto kind_of = [&](int k) { const int cls = class_of(k); return cls == 0 ? 0 : (cls == 4 ? 1 : 2); };
     std::vector<int> order;
-    order.reserve(size_t(n_images));
-    for (int cls = 0; cls <= 3; cls++)
-        for (int k = 0; k < n_images; k++) {
+    order.reserve(size_t(it.n));
+    for (int cls = 0; cls <= 4; cls++)
+        for (int k = 0; k < it.n; k++) {
             if (class_of(k) != cls) continue;
-            if (!size_ok(hs[k], ws[k], c->max_px)) { b->ok = false; continue; }
+            if (!size_ok(it.hs[k], it.ws[k], c->max_px)) { b->ok = false; continue; }
             order.push_back(k);
         }
     { std::lock_guard<std::mutex> l(c->rm); c->batch_to_come += int(order.size()); }
     size_t next = 0;
     while (next < order.size()) {
-        int id;
-        {
-            std::unique_lock<std::mutex> l(c->fm);
-            c->fcv.wait(l, [c] { return !c->free_groups.empty(); });
-            id = c->free_groups.front(); c->free_groups.pop_front();
-        }
-        Group &g = c->groups[size_t(id)];
+        Group &g = c->groups[size_t(take_group(c))];
         collect_timing(c, g);                               // events of its previous use are complete by now
-        const int kind = class_of(order[next]) == 0 ? 0 : 2;
-        g.outs = outs; g.caps = caps; g.lens = lens; g.kind = kind; g.batch = b; g.recons = recons;
+        const int kind = kind_of(order[next]);
+        g.outs = it.outs; g.caps = it.caps; g.lens = it.lens; g.kind = kind; g.batch = b; g.recons = it.recons;
         g.n_jobs = 0;
-        while (next < order.size() && g.n_jobs < int(g.slots.size()) && (class_of(order[next]) == 0 ? 0 : 2) == kind) {
+        while (next < order.size() && g.n_jobs < int(g.slots.size()) && kind_of(order[next]) == kind) {
             const int k = order[next++];
             Slot &s = g.slots[size_t(g.n_jobs++)];
-            s.job = k; s.h = hs[k]; s.w = ws[k]; s.cb = -1; s.near = near_of(k); s.effort = effort_of(k);
-            if (kind == 0 && recons && recons[k]) {                       // -n0 -e1: the reconstruction IS the input (NBLIC.c:876 rewrites the same bytes)
-                const size_t n = size_t(hs[k]) * size_t(ws[k]);
-                if (on_device) { if (hipMemcpy(recons[k], imgs[k], n, hipMemcpyDeviceToHost) != hipSuccess) b->ok = false; }
-                else if (recons[k] != imgs[k]) memcpy(recons[k], imgs[k], n);
+            s.job = k; s.h = it.hs[k]; s.w = it.ws[k]; s.cb = -1; s.near = near_of(k); s.effort = effort_of(k);
+            unsigned char *const rec = it.recons ? it.recons[k] : nullptr;
+            if (kind == 0 && rec) {                       // -n0 -e1: the reconstruction IS the input (NBLIC.c:876 rewrites the same bytes)
+                const size_t n = size_t(s.h) * size_t(s.w);
+                if (it.on_device) { if (hipMemcpy(rec, it.imgs[k], n, hipMemcpyDeviceToHost) != hipSuccess) b->ok = false; }
+                else if (rec != it.imgs[k]) memcpy(rec, it.imgs[k], n);
             }
         }
-        start_group(c, g, imgs, on_device);
+        start_group(c, g, it.imgs, it.on_device);
     }
 }
 
@@ -1095,7 +1150,7 @@ static void submitter_main(nblic_amd_ctx *c) {
         {
             std::lock_guard<std::mutex> g(c->api);
             { std::lock_guard<std::mutex> l(c->rm); c->queued_images -= it.n; }         // from here on they are counted in batch_to_come
-            encode_submit(c, it.b, it.n, it.imgs, it.on_device, it.hs, it.ws, it.outs, it.caps, it.lens, it.nears, it.efforts, it.recons);
+            encode_submit(c, it);
         }
         { std::lock_guard<std::mutex> l(c->fm); it.b->submitted = true; }
         c->fcv.notify_all();
@@ -1110,9 +1165,7 @@ static void queue_batch(nblic_amd_ctx *c, const nblic_amd_ctx::SubmitItem &it) {
 }
 
 static void report_coders(nblic_amd_ctx *c) {                        // NBLIC_AMD_DBG & 32, when nothing is outstanding
-    bool idle;
-    { std::lock_guard<std::mutex> l(c->fm); idle = c->coding == 0; }
-    if (!idle || !(getenv("NBLIC_AMD_DBG") && (atoi(getenv("NBLIC_AMD_DBG")) & 32))) return;
+    if (!(dbg_flags() & kDbgReport) || !nothing_outstanding(c)) return;
     fprintf(stderr, "[nblic_amd] coder: singles %.0f Mbins in %.2f thread-s (%.0f Mbins/s), packs %.0f Mbins in %.2f thread-s (%.0f Mbins/s)\n",
             (c->total_bins - c->pack_bins) / 1e6, c->coder_s - c->pack_s, (c->total_bins - c->pack_bins) / 1e6 / (c->coder_s - c->pack_s + 1e-9),
             c->pack_bins / 1e6, c->pack_s, c->pack_bins / 1e6 / (c->pack_s + 1e-9));
@@ -1137,36 +1190,20 @@ static bool encode_wait(nblic_amd_ctx *c, nblic_amd_batch *b) {
     return ok;
 }
 
-static bool encode_batch(nblic_amd_ctx *c, int n_images, const uint8_t *const *imgs, bool on_device, const int *hs,
-                         const int *ws, uint8_t *const *outs, const size_t *caps, long *lens) {
-    if (hipSetDevice(c->device) != hipSuccess) return false;
+// A whole batch on the caller's thread: queued like any other, then waited for -- for ITS images only, whatever else
+// is outstanding on the context.  The caller must not hold c->api (the submitter takes it).
+static bool run_batch(nblic_amd_ctx *c, nblic_amd_ctx::SubmitItem it) {
+    if (it.n < 0 || hipSetDevice(c->device) != hipSuccess) return false;
     nblic_amd_batch b;
-    queue_batch(c, nblic_amd_ctx::SubmitItem{&b, n_images, imgs, on_device, hs, ws, outs, caps, lens, nullptr, nullptr, nullptr});
-    bool ok = encode_wait(c, &b);
-    bool idle;
-    { std::lock_guard<std::mutex> l(c->fm); idle = c->coding == 0; }
-    if (idle) for (auto &g : c->groups) collect_timing(c, g);
-    report_coders(c);
-    return ok && !c->broken;
+    it.b = &b;
+    queue_batch(c, it);
+    return encode_wait(c, &b) && !c->broken;
 }
 
 // ---- QNBLIC (effort 0): model on the GPU, entropy stage on a coder thread ---------------------
 static bool launch_q(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device) {
-    for (int k = 0; k < g.n_jobs; k++) {
-        Slot &s = g.slots[size_t(k)];
-        size_t n = size_t(s.h) * size_t(s.w);
-        if (!ensure_pixels(s, n, false)) return false;
-        if (on_device) {
-            s.b.img = imgs[s.job];
-        } else {
-            if (n > s.img_cap) { if (!dev_alloc(s.d_img, n)) return false; s.img_cap = n; }
-            HIP_OK(hipMemcpyAsync(s.d_img, imgs[s.job], n, hipMemcpyHostToDevice, g.stream));
-            s.b.img = s.d_img;
-        }
-        E1Job &J = g.h_jobs[k];
-        J.b = s.b; J.h = s.h; J.w = s.w; J.n = uint32_t(n); J.pp = make_plan(J.n); J.n_ev = 0; J.pe = make_plan(0, kTouchSegments); J.dbg = 0;
-        s.n_ev = 0;
-    }
+    for (int k = 0; k < g.n_jobs; k++)
+        if (!slot_begin(g, k, imgs, on_device, false, 0)) return false;
     HIP_OK(hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(g.n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, g.stream));
     q_launch_model(g.d_jobs, g.h_jobs, g.n_jobs, g.stream);
     g.tm_pending = false;
@@ -1180,41 +1217,6 @@ static bool launch_q(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, boo
     }
     HIP_OK(hipLaunchHostFunc(g.stream, on_group_done, &g));
     return true;
-}
-
-static bool encode_q_batch(nblic_amd_ctx *c, int n_images, const uint8_t *const *imgs, bool on_device, const int *hs,
-                           const int *ws, uint16_t *const *outs, const size_t *caps_words, long *len_words) {
-    if (hipSetDevice(c->device) != hipSuccess) return false;
-    bool ok = true;
-    for (int k = 0; k < n_images; k++) len_words[k] = -1;
-    { std::lock_guard<std::mutex> l(c->rm); c->batch_to_come += n_images; }
-    int next = 0;
-    while (next < n_images) {
-        int id;
-        {
-            std::unique_lock<std::mutex> l(c->fm);
-            c->fcv.wait(l, [c] { return !c->free_groups.empty(); });
-            id = c->free_groups.front(); c->free_groups.pop_front();
-        }
-        Group &g = c->groups[size_t(id)];
-        collect_timing(c, g);
-        g.outs = reinterpret_cast<unsigned char *const *>(outs); g.caps = caps_words; g.lens = len_words; g.kind = 1; g.batch = nullptr;
-        g.n_jobs = 0;
-        while (next < n_images && g.n_jobs < int(g.slots.size())) {
-            int k = next++;
-            if (!size_ok(hs[k], ws[k], c->max_px)) { ok = false; std::lock_guard<std::mutex> l(c->rm); c->batch_to_come--; continue; }
-            Slot &s = g.slots[size_t(g.n_jobs++)];
-            s.job = k; s.h = hs[k]; s.w = ws[k]; s.cb = -1; s.near = 0; s.effort = 1;
-        }
-        if (g.n_jobs == 0) { release_group(c, id); continue; }
-        start_group(c, g, imgs, on_device);
-    }
-    {
-        std::unique_lock<std::mutex> l(c->fm);
-        c->fcv.wait(l, [c] { return c->coding == 0; });
-    }
-    for (int k = 0; k < n_images; k++) if (len_words[k] < 0) ok = false;
-    return ok && !c->broken;
 }
 
 // ---- decoders: every stream of a batch side by side, one wave per image (serial_engine.hip) -----
@@ -1679,11 +1681,7 @@ static nblic_amd_stream *stream_open(nblic_amd_ctx *c, const unsigned char *img,
     auto *s = new nblic_amd_stream;
     s->c = c; s->h = h; s->w = w; s->near = iclip(near, 0, kMaxNear); s->effort = iclip(effort, 1, 3); s->k_step = k_step_for_near(s->near);
     s->band_rows = band_rows > 0 ? (band_rows < h ? band_rows : h) : serial_rows_per_launch(h, w, s->effort, 0);
-    {   // a group of the context for as long as the stream lives: its first slot's band workspace, its stream, its pinned job records
-        std::unique_lock<std::mutex> l(c->fm);
-        c->fcv.wait(l, [c] { return !c->free_groups.empty(); });
-        s->gid = c->free_groups.front(); c->free_groups.pop_front();
-    }
+    s->gid = take_group(c);   // for as long as the stream lives: its first slot's band workspace, its stream, its pinned job records
     Group &g = c->groups[size_t(s->gid)];
     const size_t n = size_t(h) * size_t(w);
     bool ok = true;
@@ -1698,19 +1696,18 @@ static nblic_amd_stream *stream_open(nblic_amd_ctx *c, const unsigned char *img,
     return s;
 }
 
-// the job records of the band that starts at row i0
-static void stream_band_jobs(nblic_amd_stream *s, Group &g, int i0, int rows, uint32_t n_ev) {
-    Slot &sl = g.slots[0];
-    E1Job &J = g.h_jobs[0];
-    J = E1Job{};
-    J.b = sl.b; J.b.img = s->d_img + size_t(i0) * size_t(s->w); J.b.coded = s->d_coded;
-    J.h = rows; J.w = s->w; J.n = uint32_t(size_t(rows) * size_t(s->w)); J.pp = make_plan(J.n);
-    J.n_ev = n_ev; J.pe = make_plan(n_ev, kTouchSegments); J.dbg = 0;
-    J.near = s->near; J.k_step = s->k_step; J.ktab = level_shift_table(s->k_step);
-    SerialJob &Q = g.h_sjobs[0];
-    Q = SerialJob{};
-    Q.img = s->d_img; Q.recon = s->d_recon; Q.rec1 = sl.b.rec1; Q.pxs = sl.b.pxs; Q.stats = s->d_stats; Q.state = sl.d_state;
-    Q.h = s->h; Q.w = s->w; Q.near = s->near; Q.k_step = s->k_step; Q.effort = s->effort; Q.rows = rows; Q.out_row0 = i0; Q.redo = g.ctx->d_redo;
+// the band workspace as the kernels see it for the band that starts at row i0: the band's rows of the plane, the band's bins
+static E1Buffers stream_band_buffers(const nblic_amd_stream *s, const Slot &sl, int i0) {
+    E1Buffers b = sl.b;
+    b.img = s->d_img + size_t(i0) * size_t(s->w); b.coded = s->d_coded;
+    return b;
+}
+
+// the front-half job records of the band that starts at row i0
+static void stream_band_jobs(nblic_amd_stream *s, Group &g, int i0, int rows) {
+    const Slot &sl = g.slots[0];
+    g.h_jobs[0] = e1_job_front(stream_band_buffers(s, sl, i0), rows, s->w, s->near, 0);
+    g.h_sjobs[0] = model_job(s->d_img, s->d_recon, sl.b, s->d_stats, sl.d_state, s->h, s->w, s->near, s->effort, rows, i0, g.ctx->d_redo);
 }
 
 static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8_t *out, const uint8_t *end, uint32_t lo, uint32_t hi);
@@ -1732,7 +1729,7 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
         if (cap < size_t(kHeaderBytes) + 4) return fail("output buffer too small");
         write_header(p, s->h, s->w, s->near, s->k_step, s->effort);
         p += kHeaderBytes;
-        stream_band_jobs(s, g, 0, 1, 0);
+        stream_band_jobs(s, g, 0, 1);
         if (hipMemcpyAsync(g.d_jobs, g.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, g.stream) != hipSuccess) return fail("upload");
         e1_launch_init(g.d_jobs, 1, g.stream);
         if (hipMemsetAsync(sl.d_state, 0, sizeof(SerialState), g.stream) != hipSuccess) return fail("state");
@@ -1744,7 +1741,7 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
         int rows = std::min(s->band_rows, s->h - s->next_row);
         const int i0 = s->next_row;
         if (s->index_every > 0) rows = std::min(rows, s->index_every - i0 % s->index_every);     // a band never crosses an entry row
-        stream_band_jobs(s, g, i0, rows, 0);
+        stream_band_jobs(s, g, i0, rows);
         hipEvent_t e0 = g.tm.ev[0], e1 = g.tm.ev[1];
         if (hipMemcpyAsync(g.d_jobs, g.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, g.stream) != hipSuccess ||
             hipMemcpyAsync(g.d_sjobs, g.h_sjobs, sizeof(SerialJob), hipMemcpyHostToDevice, g.stream) != hipSuccess) return fail("upload");
@@ -1764,7 +1761,7 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
             s->h_coded = locked_alloc(s->coded_cap);
             if (!s->h_coded) return fail("pinned bins");
         }
-        stream_band_jobs(s, g, i0, rows, n_ev);
+        e1_job_back(g.h_jobs[0], stream_band_buffers(s, sl, i0), n_ev);
         if (hipMemcpyAsync(g.d_jobs, g.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, g.stream) != hipSuccess) return fail("upload");
         e1_launch_back(g.d_jobs, g.h_jobs, 1, g.stream, nullptr, true);
         if (n_ev && hipMemcpyAsync(s->h_coded, s->d_coded, size_t(n_ev) * sizeof(uint16_t), hipMemcpyDeviceToHost, g.stream) != hipSuccess) return fail("bins to the host");
@@ -2694,15 +2691,13 @@ int nblic_amd_range_code_chunked(const uint16_t *const *coded, const size_t *n, 
         }
         return 0;
     }
-    // as in the coder threads: two packs up to sixteen streams, three beyond (dealt in order, as evenly as they go;
-    // pack p owns lanes 8p ..), each chunk laid out as 13-bit groups (here on the host, in the pipeline by
+    // the coder threads' deal (PackDeal), each chunk laid out as 13-bit groups (here on the host, in the pipeline by
     // k_pack_groups on the GPU) and fed through feed_pair_groups / feed_triple_groups
     RangeX8 x[3];
-    const int n_packs = count > 16 ? 3 : 2;
-    const size_t lanes = size_t(8 * n_packs);
-    int pack_n[3] = {0, 0, 0}, pack_first[3] = {0, 0, 0};
-    for (int p = 0, at = 0; p < n_packs; p++) { pack_n[p] = count / n_packs + (p < count % n_packs ? 1 : 0); pack_first[p] = at; at += pack_n[p]; }
-    for (int p = 0; p < n_packs; p++) x[p].begin(pack_n[p], outs + pack_first[p], caps + pack_first[p]);
+    const PackDeal deal(count);
+    const int n_packs = deal.n_packs;
+    const size_t lanes = deal.lanes();
+    for (int p = 0; p < n_packs; p++) x[p].begin(deal.pack_n[p], outs + deal.pack_first[p], caps + deal.pack_first[p]);
     const size_t rows_cap = group_words(chunk, lanes);
     uint64_t *rows = static_cast<uint64_t *>(aligned_alloc(64, (rows_cap * sizeof(uint64_t) + 63) & ~size_t(63)));
     if (!rows) return -1;
@@ -2710,9 +2705,7 @@ int nblic_amd_range_code_chunked(const uint16_t *const *coded, const size_t *n, 
         size_t len[kMaxTake] = {0};
         memset(rows, 0, rows_cap * sizeof(uint64_t));
         for (int k = 0; k < count; k++) {
-            int p = 0;
-            while (p + 1 < n_packs && k >= pack_first[p + 1]) p++;
-            const int lane = 8 * p + (k - pack_first[p]);
+            const int lane = deal.lane_of(k);
             len[lane] = off >= n[k] ? 0 : (n[k] - off < chunk ? n[k] - off : chunk);
             pack_groups_host(rows, lane, coded[k] + off, len[lane], int(lanes));
         }
@@ -2720,7 +2713,7 @@ int nblic_amd_range_code_chunked(const uint16_t *const *coded, const size_t *n, 
         else feed_pair_groups(x[0], x[1], rows, len);
     }
     free(rows);
-    for (int p = 0; p < n_packs; p++) x[p].end(lens + pack_first[p]);
+    for (int p = 0; p < n_packs; p++) x[p].end(lens + deal.pack_first[p]);
     return 0;
 }
 
@@ -2871,8 +2864,11 @@ void nblic_amd_last_stats(nblic_amd_ctx *c, double *total_bins, double *coder_se
 int nblic_amd_encode_batch(nblic_amd_ctx *c, int n_images, const unsigned char *const *imgs, int imgs_on_device,
                            const int *heights, const int *widths, unsigned char *const *outs, const size_t *out_caps,
                            long *out_lens) {
-    if (!c || n_images < 0) return -1;
-    return encode_batch(c, n_images, imgs, imgs_on_device != 0, heights, widths, outs, out_caps, out_lens) ? 0 : -1;
+    if (!c) return -1;
+    const bool ok = run_batch(c, nblic_amd_ctx::SubmitItem{nullptr, 0, n_images, imgs, imgs_on_device != 0, heights, widths, outs, out_caps, out_lens, nullptr, nullptr, nullptr});
+    if (nothing_outstanding(c)) for (auto &g : c->groups) collect_timing(c, g);
+    report_coders(c);
+    return ok ? 0 : -1;
 }
 
 nblic_amd_batch *nblic_amd_encode_batch_begin(nblic_amd_ctx *c, int n_images, const unsigned char *const *imgs, int imgs_on_device,
@@ -2880,7 +2876,7 @@ nblic_amd_batch *nblic_amd_encode_batch_begin(nblic_amd_ctx *c, int n_images, co
                                               const size_t *out_caps, long *out_lens) {
     if (!c || n_images < 0 || hipSetDevice(c->device) != hipSuccess) return nullptr;
     auto *b = new nblic_amd_batch;
-    queue_batch(c, nblic_amd_ctx::SubmitItem{b, n_images, imgs, imgs_on_device != 0, heights, widths, outs, out_caps, out_lens, nullptr, nullptr, nullptr});
+    queue_batch(c, nblic_amd_ctx::SubmitItem{b, 0, n_images, imgs, imgs_on_device != 0, heights, widths, outs, out_caps, out_lens, nullptr, nullptr, nullptr});
     return b;
 }
 
@@ -2896,8 +2892,7 @@ long nblic_amd_debug_stage(nblic_amd_ctx *c, const unsigned char *img, int h, in
     if (!c || !size_ok(h, w, c->max_px)) return -1;
     std::lock_guard<std::mutex> g(c->api);
     if (hipSetDevice(c->device) != hipSuccess) return -1;
-    int id;
-    { std::unique_lock<std::mutex> l(c->fm); c->fcv.wait(l, [c] { return !c->free_groups.empty(); }); id = c->free_groups.front(); c->free_groups.pop_front(); }
+    const int id = take_group(c);
     Group &grp = c->groups[size_t(id)];
     Slot &s = grp.slots[0];
     grp.n_jobs = 1; s.job = 0; s.h = h; s.w = w; s.cb = -1; s.near = 0; s.effort = 1;
@@ -2920,7 +2915,7 @@ long nblic_amd_debug_stage(nblic_amd_ctx *c, const unsigned char *img, int h, in
         }
         if (src && cnt * esz <= out_bytes && hipMemcpy(out, src, cnt * esz, hipMemcpyDeviceToHost) == hipSuccess) count = long(cnt);
     }
-    if (s.cb >= 0) { std::lock_guard<std::mutex> l(c->fm); c->free_cbufs.push_back(s.cb); s.cb = -1; }
+    return_coded(c, s);
     release_group(c, id);
     return count;
 }
@@ -2928,11 +2923,8 @@ long nblic_amd_debug_stage(nblic_amd_ctx *c, const unsigned char *img, int h, in
 int nblic_amd_encode_batch_modes(nblic_amd_ctx *c, int n_images, const unsigned char *const *imgs, int imgs_on_device,
                                  const int *heights, const int *widths, const int *nears, const int *efforts,
                                  unsigned char *const *outs, const size_t *out_caps, long *out_lens, unsigned char *const *recons) {
-    if (!c || n_images < 0 || hipSetDevice(c->device) != hipSuccess) return -1;
-    nblic_amd_batch b;
-    queue_batch(c, nblic_amd_ctx::SubmitItem{&b, n_images, imgs, imgs_on_device != 0, heights, widths, outs, out_caps, out_lens, nears, efforts, recons});
-    const bool ok = encode_wait(c, &b);
-    return ok && !c->broken ? 0 : -1;
+    if (!c) return -1;
+    return run_batch(c, nblic_amd_ctx::SubmitItem{nullptr, 0, n_images, imgs, imgs_on_device != 0, heights, widths, outs, out_caps, out_lens, nears, efforts, recons}) ? 0 : -1;
 }
 
 int nblic_amd_decode_batch(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
@@ -3112,9 +3104,9 @@ int NBLICdecompress(int verbose, unsigned char *p_buf, unsigned char *p_img, int
 int nblic_amd_qencode_batch(nblic_amd_ctx *c, int n_images, const unsigned char *const *imgs, int imgs_on_device,
                             const int *heights, const int *widths, uint16_t *const *outs, const size_t *out_caps_words,
                             long *out_len_words) {
-    if (!c || n_images < 0) return -1;
-    std::lock_guard<std::mutex> g(c->api);
-    return encode_q_batch(c, n_images, imgs, imgs_on_device != 0, heights, widths, outs, out_caps_words, out_len_words) ? 0 : -1;
+    if (!c) return -1;
+    return run_batch(c, nblic_amd_ctx::SubmitItem{nullptr, 1, n_images, imgs, imgs_on_device != 0, heights, widths, reinterpret_cast<unsigned char *const *>(outs),
+                                                  out_caps_words, out_len_words, nullptr, nullptr, nullptr}) ? 0 : -1;
 }
 
 int QNBLICcompress(uint16_t *p_buf, unsigned char *p_img, int height, int width) {
