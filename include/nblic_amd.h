@@ -332,6 +332,11 @@ void nblic_amd_last_stats(nblic_amd_ctx *ctx, double *total_bins, double *coder_
 long nblic_amd_debug_stage(nblic_amd_ctx *ctx, const unsigned char *img, int height, int width, int which,
                            void *out, size_t out_bytes);
 
+/* Debug hook used by the leak tests: what the library holds right now, over every context of the process --
+ * counts[0] device allocations, [1] runtime-pinned host allocations, [2] page-locked host buffers of the coder threads
+ * and band encoders, [3] streams + events.  Needs no context and makes no GPU call.                                  */
+void nblic_amd_debug_live(long counts[4]);
+
 /* Device self-test of the wave primitives the chain kernels rely on (DPP prefix sum against the
  * shuffle formulation).  Returns the number of mismatching lanes (0 = pass) or -1.           */
 int nblic_amd_selftest(nblic_amd_ctx *ctx);

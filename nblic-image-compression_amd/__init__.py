@@ -37,7 +37,7 @@ _lib = None
 EXPORTS = (
     "NBLICcompress", "NBLICdecompress", "QNBLICcompress", "QNBLICdecompress", "QNBLICcompressMultiThread",
     "nblic_amd_create", "nblic_amd_create_ex", "nblic_amd_destroy", "nblic_amd_encode_batch", "nblic_amd_encode_batch_begin", "nblic_amd_encode_batch_end", "nblic_amd_qencode_batch", "nblic_amd_set_max_pixels",
-    "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage",
+    "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage", "nblic_amd_debug_live",
     "nblic_amd_encode_batch_modes", "nblic_amd_decode_batch", "nblic_amd_serial_selftest",
     "nblic_amd_set_serial_rows", "nblic_amd_serial_launches", "nblic_amd_lsq_redo_counts", "nblic_amd_serial_plan", "nblic_amd_lsq_probe", "nblic_amd_set_feed_chunk", "nblic_amd_last_fed_bytes",
     "nblic_amd_stream_begin", "nblic_amd_stream_resume", "nblic_amd_stream_run", "nblic_amd_stream_checkpoint", "nblic_amd_stream_progress",
@@ -196,6 +196,8 @@ def load_library() -> C.CDLL:
     lib.nblic_amd_last_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.nblic_amd_debug_stage.restype = C.c_long
     lib.nblic_amd_debug_stage.argtypes = [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    lib.nblic_amd_debug_live.restype = None
+    lib.nblic_amd_debug_live.argtypes = [C.POINTER(C.c_long)]
     lib.nblic_amd_range_code.restype = C.c_size_t
     lib.nblic_amd_range_code.argtypes = [C.POINTER(C.c_uint16), C.c_size_t, _u8p, C.c_size_t]
     lib.nblic_amd_range_code_multi.restype = C.c_int
@@ -290,6 +292,13 @@ def serial_plan(decode: bool, effort: int, images: int, width: int, whole_stream
     if r < 0:
         raise ValueError("serial_plan: arguments out of range")
     return r
+
+
+def live_resources() -> dict:
+    """What the library holds right now, over every context of the process (``nblic_amd_debug_live``); makes no GPU call."""
+    v = (C.c_long * 4)()
+    load_library().nblic_amd_debug_live(v)
+    return {"device": v[0], "pinned": v[1], "locked": v[2], "streams_events": v[3]}
 
 
 def last_fed_bytes() -> int:

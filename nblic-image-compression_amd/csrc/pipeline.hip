@@ -30,11 +30,11 @@
 #include <pthread.h>
 #include <sched.h>
 #include <fcntl.h>
-#include <sys/mman.h>
 #include <unistd.h>
 
 #include "../../include/nblic_amd.h"
 #include "device_coder.h"
+#include "hip_owned.h"
 #include "kernels_e1.h"
 #include "model.h"
 #include "range_coder.h"
@@ -125,40 +125,7 @@ bool size_ok(int h, int w, long max_px) {                                       
 // The backlog lives in HBM: a finished image's coded bins stay in a device buffer until a coder
 // thread streams them to the host chunk by chunk (its own small pinned ring), so the pinned host
 // memory is per THREAD, not per image, and the GPU never waits for host buffers.
-// Host memory the coder threads READ at full speed: ordinary pages, first touched by the thread
-// that will read them (so they sit on its NUMA node), then page-locked in place.  hipHostMalloc'ed
-// memory reads 14-18 % slower from these threads (measured: 1650 vs 1950 Mbins/s through the
-// sixteen-lane coder, tools/pinned_coder_bench.py).
-static std::mutex g_locked_m;
-static std::vector<void *> g_from_runtime;                          // the few buffers that had to come from hipHostMalloc instead
-
-static uint16_t *locked_alloc(size_t words) {
-    const size_t bytes = (words * sizeof(uint16_t) + (size_t(2) << 20) - 1) & ~((size_t(2) << 20) - 1);
-    if (!getenv("NBLIC_AMD_HOSTMALLOC")) {
-        if (void *p = aligned_alloc(size_t(2) << 20, bytes)) {
-            madvise(p, bytes, MADV_HUGEPAGE);
-            memset(p, 0, bytes);
-            if (hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess) return static_cast<uint16_t *>(p);
-            free(p);
-        }
-    }
-    void *q = nullptr;                                              // registration refused (or disabled): the runtime's own pinned memory
-    if (hipHostMalloc(&q, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
-    { std::lock_guard<std::mutex> l(g_locked_m); g_from_runtime.push_back(q); }
-    return static_cast<uint16_t *>(q);
-}
-static void locked_free(uint16_t *p) {
-    if (!p) return;
-    {
-        std::lock_guard<std::mutex> l(g_locked_m);
-        auto it = std::find(g_from_runtime.begin(), g_from_runtime.end(), static_cast<void *>(p));
-        if (it != g_from_runtime.end()) { g_from_runtime.erase(it); hipHostFree(p); return; }
-    }
-    hipHostUnregister(p);
-    free(p);
-}
-
-struct CodedBuf { uint16_t *p = nullptr; size_t cap = 0; };        // device; one image's coded bins (QNBLIC: pairs + histograms)
+using CodedBuf = DevBuf<uint16_t>;                                 // device; one image's coded bins (QNBLIC: pairs + histograms)
 // Bins per lane per chunk of the host ring.  Every chunk costs the GPU two dispatches per thread (the
 // interleave kernel and the copy, which the runtime performs with a blit kernel) that have to find
 // room between the encoder's own kernels: with 1 Mbin chunks the coder threads waited for their
@@ -184,17 +151,17 @@ struct ReadyImage {                                                  // everythi
 
 // ---- one image in flight -------------------------------------------------------------------
 struct Slot {
-    E1Buffers b{};
-    size_t px_cap = 0, ev_cap = 0, img_cap = 0;
-    uint8_t *d_img = nullptr;         // device copy when the caller hands a host image
+    E1Buffers b{};                    // the kernels' view; `mem` owns what it points at, except img, coded and totals (borrowed)
+    DevPool mem;
+    size_t px_cap = 0, ev_cap = 0;    // what the pixel-sized / event-sized buffers of b hold
+    DevBuf<uint8_t> d_img;            // device copy when the caller hands a host image
     int cb = -1;                      // coded-bin buffer (HBM) this image's back half writes to
     int job = -1, h = 0, w = 0;       // current image
     int near = 0, effort = 1;         // its mode (kind 2 groups; 0 / 1 otherwise)
     uint32_t n_ev = 0;
     // serial modes: reconstruction (near > 0) and least-squares statistics (efforts 2/3)
-    uint8_t *d_recon = nullptr; size_t recon_cap = 0;
-    double *d_stats = nullptr; size_t stats_cap = 0;
-    SerialState *d_state = nullptr;   // what the model stage carries from launch to launch (serial_engine.h)
+    DevBuf<uint8_t> d_recon; DevBuf<double> d_stats;
+    SerialState *d_state = nullptr;   // what the model stage carries from launch to launch (serial_engine.h); in `mem`
 };
 
 // ---- a group of images that shares every kernel launch ---------------------------------------
@@ -206,14 +173,14 @@ struct GroupWait { std::mutex m; std::condition_variable cv; bool ready = false;
 struct Group {
     int id = 0;
     std::unique_ptr<GroupWait> front = std::make_unique<GroupWait>();
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    E1Timers tm{};
+    Stream stream;
+    Event done, tm_ev[kE1Marks];
+    E1Timers tm{};                                     // its events are tm_ev's
     std::vector<Slot> slots;
-    E1Job *h_jobs = nullptr, *d_jobs = nullptr;        // pinned host / device job records
-    SerialJob *h_sjobs = nullptr, *d_sjobs = nullptr;  // the same images for the serial model stage (kind 2)
+    Pinned<E1Job> h_jobs; DevBuf<E1Job> d_jobs;        // pinned host / device job records
+    Pinned<SerialJob> h_sjobs; DevBuf<SerialJob> d_sjobs;   // the same images for the serial model stage (kind 2)
     unsigned char *const *recons = nullptr;            // kind 2: where each image's reconstruction goes (host; entries may be null)
-    uint32_t *h_totals = nullptr, *d_totals = nullptr; // kTotalsStride words per slot
+    Pinned<uint32_t> h_totals; DevBuf<uint32_t> d_totals;   // kTotalsStride words per slot
     int n_jobs = 0;
     bool tm_pending = false;                           // timer events recorded, not yet read
     ::nblic_amd_ctx *ctx = nullptr;
@@ -224,13 +191,6 @@ struct Group {
     // hand-over to the group's driver thread (guarded by ctx->dm)
     const uint8_t *const *imgs = nullptr; bool on_device = false; bool has_work = false;
 };
-
-template <class T> static bool dev_alloc(T *&p, size_t count) {
-    if (p) hipFree(p);
-    p = nullptr;
-    HIP_OK(hipMalloc((void **)&p, count * sizeof(T)));
-    return true;
-}
 
 }  // namespace nblic
 
@@ -252,7 +212,7 @@ struct nblic_amd_ctx {
     double now() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_batch).count(); }
     int coders_wanted = 0;                   // coder threads of this context (set before they start: pinning needs it)
     int max_take = kMaxTake;                 // images a coder thread takes together: 24 = three AVX-512 packs (NBLIC_AMD_MAX_TAKE=16: two, for A/B runs)
-    std::vector<hipStream_t> copy_streams;   // shared by the coder threads (device -> host chunk copies)
+    std::vector<Stream> copy_streams;        // shared by the coder threads (device -> host chunk copies)
     size_t chunk_bins = kChunkBins;          // bins per lane per chunk (NBLIC_AMD_CHUNK_BINS shrinks it, for tests of the chunk boundaries)
     std::vector<CodedBuf> cbufs;
     std::deque<int> free_cbufs;
@@ -300,12 +260,12 @@ struct nblic_amd_ctx {
     int dev_min_outstanding = 0;          // a pack is taken only while at least this many images of the submitted batches are unfinished
     double dev_bins = 0; long dev_packs = 0, dev_images = 0;
     // decode batches (nblic_amd_decode_batch): a stream of their own and grow-only device / pinned arenas
-    hipStream_t dec_stream = nullptr, dec_stream2 = nullptr;           // decode_batch alternates its chunks between the two
-    uint8_t *dec_arena = nullptr; size_t dec_arena_cap = 0;
-    SerialJob *dec_jobs = nullptr; int dec_jobs_cap = 0;
+    Stream dec_stream, dec_stream2;                                    // decode_batch alternates its chunks between the two
+    DevBuf<uint8_t> dec_arena;
+    DevBuf<SerialJob> dec_jobs;
     int index_round_segments = 0;         // > 0: at most this many segments per round of decode_indexed (nblic_amd_set_index_round)
     int serial_rows = 0;                  // rows per launch of the serial kernels; 0 = sized for a few seconds per launch (nblic_amd_set_serial_rows)
-    unsigned long long *d_redo = nullptr;       // device: pixels whose least-squares system 0 / 1 was redone with integers (SerialJob::redo of every job of the context)
+    DevBuf<unsigned long long> d_redo;          // device: pixels whose least-squares system 0 / 1 was redone with integers (SerialJob::redo of every job of the context)
     long serial_launch_count = 0;         // launches of the serial model / decode kernels since the context was created (reporting, tests)
     size_t feed_chunk = size_t(1) << 20;  // bytes per step in which the drop-in decoders fetch a stream of unknown length (nblic_amd_set_feed_chunk)
     long fed_bytes = 0;                   // bytes the last drop-in decode read from the caller's stream
@@ -365,69 +325,49 @@ static uint8_t *begin_stream_out(const ReadyImage &im, size_t *room) {
 static bool group_init(Group &g, int id, int n_slots, nblic_amd_ctx *c) {
     g.id = id; g.ctx = c;
     g.slots.resize(size_t(n_slots));
-    HIP_OK(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
-    HIP_OK(hipEventCreateWithFlags(&g.done, hipEventDisableTiming | hipEventBlockingSync));
-    for (auto &e : g.tm.ev) HIP_OK(hipEventCreate(&e));
-    HIP_OK(hipHostMalloc((void **)&g.h_jobs, size_t(n_slots) * sizeof(E1Job), hipHostMallocDefault));
-    HIP_OK(hipMalloc((void **)&g.d_jobs, size_t(n_slots) * sizeof(E1Job)));
-    HIP_OK(hipHostMalloc((void **)&g.h_sjobs, size_t(n_slots) * sizeof(SerialJob), hipHostMallocDefault));
-    HIP_OK(hipMalloc((void **)&g.d_sjobs, size_t(n_slots) * sizeof(SerialJob)));
-    HIP_OK(hipHostMalloc((void **)&g.h_totals, size_t(n_slots) * kTotalsStride * sizeof(uint32_t), hipHostMallocDefault));
-    HIP_OK(hipMalloc((void **)&g.d_totals, size_t(n_slots) * kTotalsStride * sizeof(uint32_t)));
+    HIP_OK(g.stream.create(hipStreamNonBlocking));
+    HIP_OK(g.done.create(hipEventDisableTiming | hipEventBlockingSync));
+    for (int k = 0; k < kE1Marks; k++) { HIP_OK(g.tm_ev[k].create(hipEventDefault)); g.tm.ev[k] = g.tm_ev[k]; }
+    HIP_OK(g.h_jobs.alloc(size_t(n_slots))); HIP_OK(g.d_jobs.alloc(size_t(n_slots)));
+    HIP_OK(g.h_sjobs.alloc(size_t(n_slots))); HIP_OK(g.d_sjobs.alloc(size_t(n_slots)));
+    HIP_OK(g.h_totals.alloc(size_t(n_slots) * kTotalsStride)); HIP_OK(g.d_totals.alloc(size_t(n_slots) * kTotalsStride));
     for (int k = 0; k < n_slots; k++) {
         Slot &s = g.slots[size_t(k)];
-        HIP_OK(hipMalloc((void **)&s.b.table, size_t(4096) * kMaxSegments * sizeof(uint32_t)));
-        HIP_OK(hipMalloc((void **)&s.b.scan_sums, size_t(1) << 20));
+        DevPool &m = s.mem;
+        HIP_OK(m.renew(s.b.table, size_t(4096) * kMaxSegments)); HIP_OK(m.renew(s.b.scan_sums, (size_t(1) << 20) / sizeof(uint32_t)));
         s.b.totals = g.d_totals + size_t(k) * kTotalsStride;
-        HIP_OK(hipMalloc((void **)&s.b.ctx_state, 4096 * sizeof(int)));           // 2048 (NBLIC) or 3072 (QNBLIC) contexts
-        HIP_OK(hipMalloc((void **)&s.b.qhist, 12 * 256 * sizeof(uint32_t)));
-        HIP_OK(hipMalloc((void **)&s.b.map_state, 512 * 60 * sizeof(int)));
-        HIP_OK(hipMalloc((void **)&s.b.cnt_state, 4096 * 2 * sizeof(int)));
-        HIP_OK(hipMalloc((void **)&s.b.win_base, (4097 + 4096) * sizeof(uint32_t)));
-        HIP_OK(hipMalloc((void **)&s.b.blk_base, 4097 * sizeof(uint32_t)));
-        HIP_OK(hipMalloc((void **)&s.b.dbg_out, 4096 * sizeof(unsigned long long)));
+        HIP_OK(m.renew(s.b.ctx_state, 4096));                                        // 2048 (NBLIC) or 3072 (QNBLIC) contexts
+        HIP_OK(m.renew(s.b.qhist, 12 * 256)); HIP_OK(m.renew(s.b.map_state, 512 * 60)); HIP_OK(m.renew(s.b.cnt_state, 4096 * 2));
+        HIP_OK(m.renew(s.b.win_base, 4097 + 4096)); HIP_OK(m.renew(s.b.blk_base, 4097)); HIP_OK(m.renew(s.b.dbg_out, 4096));
         HIP_OK(hipMemset(s.b.dbg_out, 0, 4096 * sizeof(unsigned long long)));
-        HIP_OK(hipMalloc((void **)&s.d_state, kModelStateBytes));
+        uint8_t *state = nullptr;
+        HIP_OK(m.renew(state, kModelStateBytes));
+        s.d_state = reinterpret_cast<SerialState *>(state);
     }
     return true;
 }
 
-static void group_free(Group &g) {
-    for (auto &s : g.slots) {
-        hipFree(s.b.rec1); hipFree(s.b.s2in); hipFree(s.b.pos2); hipFree(s.b.s2out); hipFree(s.b.pxs); hipFree(s.b.s3in);
-        hipFree(s.b.pos3); hipFree(s.b.s3out); hipFree(s.b.z); hipFree(s.b.cnt); hipFree(s.b.ev_off); hipFree(s.b.table);
-        hipFree(s.b.scan_sums); hipFree(s.b.ctx_state); hipFree(s.b.map_state); hipFree(s.b.cnt_state); hipFree(s.b.events);
-        hipFree(s.b.tin); hipFree(s.b.tpos); hipFree(s.b.tout); hipFree(s.b.win_base); hipFree(s.b.win_recs); hipFree(s.b.blk_base); hipFree(s.b.dbg_out); hipFree(s.b.qhist); hipFree(s.b.blk_end); hipFree(s.b.blk_ok); hipFree(s.d_img);
-        hipFree(s.d_recon); hipFree(s.d_stats); hipFree(s.d_state);
-    }
-    hipFree(g.d_jobs); hipFree(g.d_totals); hipFree(g.d_sjobs);
-    if (g.h_sjobs) hipHostFree(g.h_sjobs);
-    if (g.h_jobs) hipHostFree(g.h_jobs);
-    if (g.h_totals) hipHostFree(g.h_totals);
-    for (auto &e : g.tm.ev) if (e) hipEventDestroy(e);
-    if (g.done) hipEventDestroy(g.done);
-    if (g.stream) hipStreamDestroy(g.stream);
-}
-
+// The event-sized / pixel-sized buffers of a slot grow together; while they do their capacity is 0, so after a failure half way the next call replaces them all.
 static bool ensure_events(Slot &s, size_t n_ev) {
     if (n_ev <= s.ev_cap) return true;
-    size_t cap = n_ev + n_ev / 8 + 1024;
-    if (!dev_alloc(s.b.events, cap) || !dev_alloc(s.b.tin, 2 * cap + kStreamPad) || !dev_alloc(s.b.tpos, cap + 64) ||
-        !dev_alloc(s.b.tout, 2 * cap + kStreamPad) ||
-        !dev_alloc(s.b.win_recs, (2 * cap / 512 + 4096 + 8) * 24)) return false;
+    const size_t cap = n_ev + n_ev / 8 + 1024;
+    DevPool &m = s.mem;
+    s.ev_cap = 0;
+    HIP_OK(m.renew(s.b.events, cap)); HIP_OK(m.renew(s.b.tin, 2 * cap + kStreamPad)); HIP_OK(m.renew(s.b.tpos, cap + 64));
+    HIP_OK(m.renew(s.b.tout, 2 * cap + kStreamPad)); HIP_OK(m.renew(s.b.win_recs, (2 * cap / 512 + 4096 + 8) * 24));
     s.ev_cap = cap;
     return true;
 }
 
 static bool ensure_pixels(Slot &s, size_t n, bool with_events = true) {
     if (n > s.px_cap) {
-        size_t cap = n;
-        if (!dev_alloc(s.b.rec1, cap) || !dev_alloc(s.b.s2in, cap + kStreamPad) || !dev_alloc(s.b.pos2, cap) ||
-            !dev_alloc(s.b.s2out, cap + kStreamPad) || !dev_alloc(s.b.pxs, cap) || !dev_alloc(s.b.s3in, cap + kStreamPad) ||
-            !dev_alloc(s.b.pos3, cap) || !dev_alloc(s.b.s3out, cap + kStreamPad) || !dev_alloc(s.b.z, cap) ||
-            !dev_alloc(s.b.cnt, cap) || !dev_alloc(s.b.ev_off, cap) || !dev_alloc(s.b.blk_end, cap / 4096 + 4096 + 64) ||
-            !dev_alloc(s.b.blk_ok, cap / 4096 + 4096 + 64)) return false;
-        s.px_cap = cap;
+        DevPool &m = s.mem;
+        s.px_cap = 0;
+        HIP_OK(m.renew(s.b.rec1, n)); HIP_OK(m.renew(s.b.s2in, n + kStreamPad)); HIP_OK(m.renew(s.b.pos2, n)); HIP_OK(m.renew(s.b.s2out, n + kStreamPad));
+        HIP_OK(m.renew(s.b.pxs, n)); HIP_OK(m.renew(s.b.s3in, n + kStreamPad)); HIP_OK(m.renew(s.b.pos3, n)); HIP_OK(m.renew(s.b.s3out, n + kStreamPad));
+        HIP_OK(m.renew(s.b.z, n)); HIP_OK(m.renew(s.b.cnt, n)); HIP_OK(m.renew(s.b.ev_off, n));
+        HIP_OK(m.renew(s.b.blk_end, n / 4096 + 4096 + 64)); HIP_OK(m.renew(s.b.blk_ok, n / 4096 + 4096 + 64));
+        s.px_cap = n;
     }
     return with_events ? ensure_events(s, 5 * n) : true;   // typical images need 4.3-4.5 bins/px (ensure_events adds 1/8); grown on demand
 }
@@ -470,7 +410,7 @@ static bool slot_begin(Group &g, int k, const uint8_t *const *imgs, bool on_devi
     if (on_device) {
         s.b.img = imgs[s.job];
     } else {
-        if (n > s.img_cap) { if (!dev_alloc(s.d_img, n)) return false; s.img_cap = n; }
+        HIP_OK(s.d_img.reserve(n));
         HIP_OK(hipMemcpyAsync(s.d_img, imgs[s.job], n, hipMemcpyHostToDevice, g.stream));
         s.b.img = s.d_img;
     }
@@ -501,11 +441,11 @@ static bool launch_front_serial(nblic_amd_ctx *c, Group &g, const uint8_t *const
         const size_t n = size_t(s.h) * size_t(s.w);
         const bool wide = !serial_model_rows_fit(s.w);                   // rows do not fit in LDS: taps come from the reconstruction in memory
         const bool want_recon = s.near > 0 || wide;
-        if (want_recon && n > s.recon_cap) { if (!dev_alloc(s.d_recon, n)) return false; s.recon_cap = n; }
+        if (want_recon) HIP_OK(s.d_recon.reserve(n));
         const size_t st = stats_doubles(s.effort, s.w);
-        if (st > s.stats_cap) { if (!dev_alloc(s.d_stats, st)) return false; s.stats_cap = st; }
+        HIP_OK(s.d_stats.reserve(st));
         if (st) HIP_OK(hipMemsetAsync(s.d_stats, 0, st * sizeof(double), g.stream));         // NBLIC.c:789
-        g.h_sjobs[k] = model_job(s.b.img, want_recon ? s.d_recon : nullptr, s.b, s.d_stats, s.d_state, s.h, s.w, s.near, s.effort,
+        g.h_sjobs[k] = model_job(s.b.img, want_recon ? s.d_recon.get() : nullptr, s.b, s.d_stats, s.d_state, s.h, s.w, s.near, s.effort,
                                  serial_rows_per_launch(s.h, s.w, s.effort, c->serial_rows), 0, c->d_redo);
         HIP_OK(hipMemsetAsync(s.d_state, 0, sizeof(SerialState), g.stream));               // a fresh image: row 0, running
     }
@@ -589,49 +529,35 @@ __global__ void __launch_bounds__(256) k_pack_groups(InterleaveArgs a, uint64_t 
 // copy streams: a stream per thread would outnumber the hardware queues, and streams that share a
 // hardware queue with a group's kernels have their copies stuck behind those kernels.
 struct CoderThread {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[kRingDepth] = {};
-    uint16_t *ring = nullptr;
-    uint64_t *d_rows = nullptr;                          // device: two halves of 13-bit groups (k_pack_groups' output)
-    uint16_t *whole = nullptr; size_t whole_cap = 0;     // pinned; one whole QNBLIC image (its rANS runs last pixel first)
+    hipStream_t stream = nullptr;                        // one of the context's copy streams
+    Event ev[kRingDepth];
+    Locked ring;
+    DevBuf<uint64_t> d_rows;                             // device: two halves of 13-bit groups (k_pack_groups' output)
+    Locked whole;                                        // one whole QNBLIC image (its rANS runs last pixel first)
     RangeX8 x8, x8b, x8c;
     RangeScalar x1;
     double wait_s = 0, issue_s = 0;                      // time spent waiting for chunks / inside the runtime calls that queue a chunk (reporting)
     bool init(int device, hipStream_t copy_stream) {
         HIP_OK(hipSetDevice(device));
         stream = copy_stream;
-        for (auto &e : ev) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventBlockingSync));
+        for (auto &e : ev) HIP_OK(e.create(hipEventDisableTiming | hipEventBlockingSync));
         return true;
-    }
-    void destroy() {
-        locked_free(ring);
-        locked_free(whole);
-        if (d_rows) hipFree(d_rows);
-        for (auto &e : ev) if (e) hipEventDestroy(e);
     }
     // The ring holds kRingDepth slots of ring_lanes x ring_chunk bins; it is sized by what the thread has actually been
     // asked to code (one lane for an image coded alone, sixteen for a pack pair; the chunk no longer than the longest
     // image) and only grows: a context that codes one small image through the drop-in entry points pins kilobytes,
     // the bench's threads end up at 3 x 24 x 4 Mbin x 1.625 B = 491 MB each.
-    size_t ring_lanes = 0, ring_chunk = 0, rows_cap = 0;
+    size_t ring_lanes = 0, ring_chunk = 0;
     // 16-bit words per ring slot: a lone image's chunk as it is, or the 13-bit groups of ring_lanes lanes
     size_t slot_words() const { return ring_lanes > 1 ? group_words(ring_chunk, ring_lanes) * 4 : ring_chunk; }
     bool ensure_ring(size_t lanes, size_t chunk, bool need_rows) {
         chunk = (chunk + 4095) & ~size_t(4095);
         if (lanes > ring_lanes || chunk > ring_chunk) {
             const size_t nl = lanes > ring_lanes ? lanes : ring_lanes, nc = chunk > ring_chunk ? chunk : ring_chunk;
-            locked_free(ring);
             ring_lanes = nl; ring_chunk = nc;
-            ring = locked_alloc(kRingDepth * slot_words());
-            if (!ring) { ring_lanes = ring_chunk = 0; fprintf(stderr, "[nblic_amd] cannot allocate the coder thread's ring\n"); return false; }
+            if (!ring.alloc(kRingDepth * slot_words())) { ring_lanes = ring_chunk = 0; fprintf(stderr, "[nblic_amd] cannot allocate the coder thread's ring\n"); return false; }
         }
-        const size_t want_rows = need_rows ? kRingDepth * group_words(ring_chunk, ring_lanes) : 0;
-        if (want_rows > rows_cap) {
-            if (d_rows) hipFree(d_rows);
-            d_rows = nullptr; rows_cap = 0;
-            HIP_OK(hipMalloc((void **)&d_rows, want_rows * sizeof(uint64_t)));
-            rows_cap = want_rows;
-        }
+        HIP_OK(d_rows.reserve(need_rows ? kRingDepth * group_words(ring_chunk, ring_lanes) : 0));
         return true;
     }
     uint16_t *slot(size_t chunk) { return ring + size_t(chunk % kRingDepth) * slot_words(); }            // a lone image's chunk
@@ -824,13 +750,8 @@ static void coder_main(nblic_amd_ctx *c, int index) {
             const ReadyImage &q = im[0];
             const size_t n = size_t(q.h) * size_t(q.w), n_pad = (n + 1) & ~size_t(1), words = n_pad + 2 * 12 * 256;
             bool ok = true;
-            if (t.whole_cap < words) {
-                locked_free(t.whole);
-                t.whole = nullptr; t.whole_cap = 0;
-                if ((t.whole = locked_alloc(words + 1024)) != nullptr) t.whole_cap = words + 1024;
-                else ok = false;
-            }
-            ok = ok && hipMemcpyAsync(t.whole, c->cbufs[size_t(q.cb)].p, words * sizeof(uint16_t), hipMemcpyDeviceToHost, t.stream) == hipSuccess &&
+            if (t.whole.capacity() < words) ok = t.whole.alloc(words + 1024);
+            ok = ok && hipMemcpyAsync(t.whole, c->cbufs[size_t(q.cb)], words * sizeof(uint16_t), hipMemcpyDeviceToHost, t.stream) == hipSuccess &&
                  hipEventRecord(t.ev[0], t.stream) == hipSuccess && hipEventSynchronize(t.ev[0]) == hipSuccess;
             long words_out = -1;
             if (ok) {
@@ -847,7 +768,7 @@ static void coder_main(nblic_amd_ctx *c, int index) {
         const uint16_t *src[kMaxTake]; size_t n[kMaxTake], caps[kMaxTake], lens[kMaxTake]; uint8_t *dst[kMaxTake];
         double bins = 0;
         for (int k = 0; k < take; k++) {
-            src[k] = c->cbufs[size_t(im[k].cb)].p; n[k] = im[k].n_ev; bins += double(im[k].n_ev);
+            src[k] = c->cbufs[size_t(im[k].cb)]; n[k] = im[k].n_ev; bins += double(im[k].n_ev);
             dst[k] = begin_stream_out(im[k], &caps[k]);
         }
         if (dbg_flags() & kDbgDeviceOnly) { for (int k = 0; k < take; k++) lens[k] = 0; }
@@ -864,7 +785,6 @@ static void coder_main(nblic_amd_ctx *c, int index) {
         { std::lock_guard<std::mutex> l(c->stat_m); c->total_bins += bins; c->coder_s += dt; if (take > 1) { c->pack_bins += bins; c->pack_s += dt; } c->wait_s += t.wait_s; t.wait_s = 0; c->issue_s += t.issue_s; t.issue_s = 0; c->takes[take]++; }
         finish_images(c, im, take);
     }
-    t.destroy();
 }
 
 // ---- device coder pack threads -----------------------------------------------------------------
@@ -887,17 +807,15 @@ static int dev_take(const nblic_amd_ctx *c) {                  // call with c->r
 static void dev_coder_main(nblic_amd_ctx *c, int index) {
     pthread_setname_np(pthread_self(), "nblic-devcoder");
     (void)index;
-    hipStream_t st = nullptr;
-    hipEvent_t done = nullptr;
-    RcJob *h_jobs = nullptr, *d_jobs = nullptr;
-    uint32_t *h_lens = nullptr, *d_lens = nullptr;
-    uint8_t *d_out = nullptr; size_t out_cap = 0;
-    bool ok = hipSetDevice(c->device) == hipSuccess && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&done, hipEventDisableTiming | hipEventBlockingSync) == hipSuccess &&
-              hipHostMalloc((void **)&h_jobs, kDevPack * sizeof(RcJob), hipHostMallocDefault) == hipSuccess &&
-              hipMalloc((void **)&d_jobs, kDevPack * sizeof(RcJob)) == hipSuccess &&
-              hipHostMalloc((void **)&h_lens, kDevPack * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess &&
-              hipMalloc((void **)&d_lens, kDevPack * sizeof(uint32_t)) == hipSuccess;
+    Stream st;
+    Event done;
+    Pinned<RcJob> h_jobs; DevBuf<RcJob> d_jobs;
+    Pinned<uint32_t> h_lens; DevBuf<uint32_t> d_lens;
+    DevBuf<uint8_t> d_out;
+    bool ok = hipSetDevice(c->device) == hipSuccess && st.create(hipStreamNonBlocking) == hipSuccess &&
+              done.create(hipEventDisableTiming | hipEventBlockingSync) == hipSuccess &&
+              h_jobs.alloc(kDevPack) == hipSuccess && d_jobs.alloc(kDevPack) == hipSuccess &&
+              h_lens.alloc(kDevPack) == hipSuccess && d_lens.alloc(kDevPack) == hipSuccess;
     if (!ok) c->broken = true;
     for (;;) {
         ReadyImage im[kDevPack];
@@ -914,14 +832,14 @@ static void dev_coder_main(nblic_amd_ctx *c, int index) {
         size_t need = 0, off[kDevPack];
         for (int k = 0; k < take; k++) { off[k] = need; need += (size_t(im[k].h) * size_t(im[k].w) * 9 / 8 + 4096 + 255) & ~size_t(255); }
         bool good = ok;
-        if (good && need > out_cap) { hipFree(d_out); d_out = nullptr; out_cap = 0; good = hipMalloc((void **)&d_out, need) == hipSuccess; if (good) out_cap = need; }
+        good = good && d_out.reserve(need) == hipSuccess;
         double bins = 0;
         uint8_t *dst[kDevPack];
         for (int k = 0; k < take && good; k++) {
             size_t room;
             dst[k] = begin_stream_out(im[k], &room);
             const size_t cap = std::min(room, (k + 1 < take ? off[k + 1] : need) - off[k]);
-            h_jobs[k] = RcJob{c->cbufs[size_t(im[k].cb)].p, d_out + off[k], d_lens + k, im[k].n_ev, uint32_t(cap < 0xFFFFFFF0u ? cap : 0xFFFFFFF0u)};
+            h_jobs[k] = RcJob{c->cbufs[size_t(im[k].cb)], d_out + off[k], d_lens + k, im[k].n_ev, uint32_t(cap < 0xFFFFFFF0u ? cap : 0xFFFFFFF0u)};
             bins += double(im[k].n_ev);
         }
         good = good && hipMemcpyAsync(d_jobs, h_jobs, size_t(take) * sizeof(RcJob), hipMemcpyHostToDevice, st) == hipSuccess &&
@@ -942,11 +860,6 @@ static void dev_coder_main(nblic_amd_ctx *c, int index) {
         { std::lock_guard<std::mutex> l(c->stat_m); c->dev_bins += bins; c->dev_packs++; c->dev_images += take; }
         finish_images(c, im, take);
     }
-    hipFree(d_out); hipFree(d_jobs); hipFree(d_lens);
-    if (h_jobs) hipHostFree(h_jobs);
-    if (h_lens) hipHostFree(h_lens);
-    if (done) hipEventDestroy(done);
-    if (st) hipStreamDestroy(st);
 }
 
 // Takes a coded-bin buffer of at least `words` for slot s (waits for one if the coder threads are
@@ -958,13 +871,7 @@ static bool acquire_coded(nblic_amd_ctx *c, Slot &s, size_t words) {
         s.cb = c->free_cbufs.front(); c->free_cbufs.pop_front();
     }
     CodedBuf &cb = c->cbufs[size_t(s.cb)];
-    if (cb.cap < words) {
-        if (cb.p) hipFree(cb.p);
-        cb.p = nullptr; cb.cap = 0;
-        const size_t cap = words + words / 8 + 1024;
-        HIP_OK(hipMalloc((void **)&cb.p, cap * sizeof(uint16_t)));
-        cb.cap = cap;
-    }
+    if (cb.capacity() < words) HIP_OK(cb.alloc(words + words / 8 + 1024));
     return true;
 }
 
@@ -1013,7 +920,7 @@ static bool launch_back(nblic_amd_ctx *c, Group &g, bool with_coders, bool gener
         if (!ensure_events(s, s.n_ev)) return false;
         // the coded bins go straight into a pool buffer that outlives this group's turn on the slot
         if (!acquire_coded(c, s, size_t(s.n_ev) + 8)) return false;
-        s.b.coded = c->cbufs[size_t(s.cb)].p;
+        s.b.coded = c->cbufs[size_t(s.cb)];
         e1_job_back(g.h_jobs[k], s.b, s.n_ev);
     }
     HIP_OK(hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(g.n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, g.stream));
@@ -1211,7 +1118,7 @@ static bool launch_q(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, boo
         Slot &s = g.slots[size_t(k)];
         const size_t n = size_t(s.h) * size_t(s.w), n_pad = (n + 1) & ~size_t(1), need = n_pad + 2 * 12 * 256;
         if (!acquire_coded(c, s, need)) return false;
-        uint16_t *dst = c->cbufs[size_t(s.cb)].p;
+        uint16_t *dst = c->cbufs[size_t(s.cb)];
         HIP_OK(hipMemcpyAsync(dst, s.b.pxs, n * sizeof(uint16_t), hipMemcpyDeviceToDevice, g.stream));
         HIP_OK(hipMemcpyAsync(dst + n_pad, s.b.qhist, 12 * 256 * sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream));
     }
@@ -1412,16 +1319,6 @@ static bool decode_launch(const DecodeItem &first, const SerialJob *d_jobs, cons
     return first.kind == 1 ? serial_qdecode_launch(d_jobs, h_jobs, n, st) : serial_decode_launch(d_jobs, h_jobs, n, st, whole_streams);
 }
 
-static bool ensure_decode_space(nblic_amd_ctx *c, size_t arena, int m) {
-    if (arena > c->dec_arena_cap) { hipFree(c->dec_arena); c->dec_arena = nullptr; c->dec_arena_cap = 0; HIP_OK(hipMalloc((void **)&c->dec_arena, arena)); c->dec_arena_cap = arena; }
-    if (m > c->dec_jobs_cap) {
-        hipFree(c->dec_jobs); c->dec_jobs = nullptr; c->dec_jobs_cap = 0;
-        HIP_OK(hipMalloc((void **)&c->dec_jobs, size_t(m) * sizeof(SerialJob)));
-        c->dec_jobs_cap = m;
-    }
-    return true;
-}
-
 // Parses and validates the headers, uploads the streams (their lengths are known here: running dry is an error),
 // works every (codec, effort) class present through its launches -- `rows` rows of every image per launch, the
 // state records carry the images from one launch to the next -- and copies the planes back.  status[k] = 0 / -1.
@@ -1449,7 +1346,7 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
     if (items.empty()) return true;
     std::stable_sort(items.begin(), items.end(), [](const DecodeItem &a, const DecodeItem &b) { return a.kind * 4 + a.effort < b.kind * 4 + b.effort; });
     const int m = int(items.size());
-    if (!ensure_decode_space(c, arena, m)) return false;
+    HIP_OK(c->dec_arena.reserve(arena)); HIP_OK(c->dec_jobs.reserve(size_t(m)));      // grow-only, like every workspace
     std::vector<SerialJob> jobs(static_cast<size_t>(m));
     std::vector<SerialState> heads(static_cast<size_t>(m));
     std::vector<uint8_t *> d_streams(static_cast<size_t>(m)), d_tabs(static_cast<size_t>(m), nullptr);
@@ -1642,11 +1539,11 @@ struct nblic_amd_stream {
     int gid = -1;
     int h = 0, w = 0, near = 0, effort = 1, k_step = 3, band_rows = 1, next_row = 0;
     int first_row = 0;                                                  // the first row THIS object coded (> 0 after a resume)
-    const uint8_t *d_img = nullptr; uint8_t *own_img = nullptr;        // the whole plane on the device
-    uint8_t *d_recon = nullptr;                                         // whole reconstruction (near > 0 or rows too wide for LDS)
-    double *d_stats = nullptr; size_t stats_bytes = 0;                  // [B | F], efforts 2 / 3
-    uint16_t *d_coded = nullptr; size_t coded_cap = 0;                  // one band's coded bins
-    uint16_t *h_coded = nullptr; size_t h_coded_cap = 0;                // the same, page-locked host memory
+    const uint8_t *d_img = nullptr; nblic::DevBuf<uint8_t> own_img;    // the whole plane on the device (the caller's, or a copy)
+    nblic::DevBuf<uint8_t> d_recon;                                     // whole reconstruction (near > 0 or rows too wide for LDS)
+    nblic::DevBuf<double> d_stats; size_t stats_bytes = 0;              // [B | F], efforts 2 / 3
+    nblic::DevBuf<uint16_t> d_coded;                                    // one band's coded bins
+    nblic::Locked h_coded;                                              // the same, page-locked host memory
     uint32_t lo = 0, hi = 0xFFFFFFFFu;
     unsigned long long bytes_total = 0;
     nblic::Sha256 sha;
@@ -1668,12 +1565,10 @@ namespace nblic {
 
 static void stream_free(nblic_amd_stream *s) {
     if (!s) return;
-    if (s->c && hipSetDevice(s->c->device) == hipSuccess) {
-        hipFree(s->own_img); hipFree(s->d_recon); hipFree(s->d_stats); hipFree(s->d_coded);
-        locked_free(s->h_coded);
-    }
-    if (s->c && s->gid >= 0) release_group(s->c, s->gid);
-    delete s;
+    nblic_amd_ctx *const c = s->c; const int gid = s->gid;
+    if (c) hipSetDevice(c->device);
+    delete s;                                                            // its buffers, before the group serves somebody else
+    if (c && gid >= 0) release_group(c, gid);
 }
 
 static nblic_amd_stream *stream_open(nblic_amd_ctx *c, const unsigned char *img, bool on_device, int h, int w, int near, int effort, int band_rows) {
@@ -1686,10 +1581,10 @@ static nblic_amd_stream *stream_open(nblic_amd_ctx *c, const unsigned char *img,
     const size_t n = size_t(h) * size_t(w);
     bool ok = true;
     if (on_device) s->d_img = img;
-    else ok = hipMalloc((void **)&s->own_img, n) == hipSuccess && hipMemcpyAsync(s->own_img, img, n, hipMemcpyHostToDevice, g.stream) == hipSuccess && (s->d_img = s->own_img, true);
-    if (ok && encoder_keeps_recon(s->near, w)) ok = hipMalloc((void **)&s->d_recon, n) == hipSuccess;
+    else ok = s->own_img.alloc(n) == hipSuccess && hipMemcpyAsync(s->own_img, img, n, hipMemcpyHostToDevice, g.stream) == hipSuccess && (s->d_img = s->own_img, true);
+    if (ok && encoder_keeps_recon(s->near, w)) ok = s->d_recon.alloc(n) == hipSuccess;
     s->stats_bytes = lsq_stats_bytes(0, s->effort, w);
-    if (ok && s->stats_bytes) ok = hipMalloc((void **)&s->d_stats, s->stats_bytes) == hipSuccess && hipMemsetAsync(s->d_stats, 0, s->stats_bytes, g.stream) == hipSuccess;   // NBLIC.c:789
+    if (ok && s->stats_bytes) ok = s->d_stats.alloc(s->stats_bytes / sizeof(double)) == hipSuccess && hipMemsetAsync(s->d_stats, 0, s->stats_bytes, g.stream) == hipSuccess;   // NBLIC.c:789
     Slot &sl = g.slots[0];
     ok = ok && ensure_pixels(sl, size_t(s->band_rows) * size_t(w));
     if (!ok) { fprintf(stderr, "[nblic_amd] stream: cannot set up the band workspace\n"); stream_free(s); return nullptr; }
@@ -1754,12 +1649,10 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
         { float ms = 0.f; if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) s->model_ms += ms; }
         const uint32_t n_ev = g.h_totals[2];
         if (n_ev >= 0x7FFFFFFFu || !ensure_events(sl, n_ev)) return fail("bin count");
-        if (size_t(n_ev) + 8 > s->coded_cap) {
-            hipFree(s->d_coded); s->d_coded = nullptr; locked_free(s->h_coded); s->h_coded = nullptr;
-            s->coded_cap = size_t(n_ev) + size_t(n_ev) / 4 + 4096;
-            if (hipMalloc((void **)&s->d_coded, s->coded_cap * sizeof(uint16_t)) != hipSuccess) return fail("coded bins");
-            s->h_coded = locked_alloc(s->coded_cap);
-            if (!s->h_coded) return fail("pinned bins");
+        if (size_t(n_ev) + 8 > std::min(s->d_coded.capacity(), s->h_coded.capacity())) {
+            const size_t cap = size_t(n_ev) + size_t(n_ev) / 4 + 4096;
+            if (s->d_coded.alloc(cap) != hipSuccess) return fail("coded bins");
+            if (!s->h_coded.alloc(cap)) return fail("pinned bins");
         }
         e1_job_back(g.h_jobs[0], stream_band_buffers(s, sl, i0), n_ev);
         if (hipMemcpyAsync(g.d_jobs, g.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, g.stream) != hipSuccess) return fail("upload");
@@ -1904,18 +1797,18 @@ static int dstream_check(const void *ck, size_t len, long max_px, DecodeCheckpoi
 struct nblic_amd_dstream {
     nblic_amd_ctx *c = nullptr;
     int device = 0;
-    hipStream_t st = nullptr;
-    bool own_st = false;                                 // st is this object's own (else lent by decode_dropin: the context's dec_stream)
+    nblic::Stream st;                                    // this object's own, or lent by decode_dropin: the context's dec_stream
     int band_rows_req = 0;
     // the header (kind 0 NBLIC, 1 QNBLIC) and the workspace it sizes
     bool have_head = false, refused = false, failed = false, done = false;
     nblic::DecodeItem it{};
     int band_rows = 0;
+    nblic::DevPool mem;                                  // owns the workspace: what the pointers below see
     uint8_t *d_rows = nullptr, *d_carry = nullptr, *d_win = nullptr, *d_tab = nullptr;
     double *d_stats = nullptr, *d_snap = nullptr;
     nblic::SerialState *d_state = nullptr;
     nblic::SerialJob *d_job = nullptr;
-    size_t stats_bytes = 0, win_cap = 0, device_bytes = 0;
+    size_t stats_bytes = 0, win_cap = 0;
     std::vector<uint8_t> qtab;                           // QNBLIC: host copy of the tables (they travel with a checkpoint)
     // the stream as fed: bytes [pend_off, pend_off + pend.size()) of it; [win_off, win_off + win_len) are on the device
     std::vector<uint8_t> pend;
@@ -1931,20 +1824,10 @@ struct nblic_amd_dstream {
 
 namespace nblic {
 
-static void dstream_free_device(nblic_amd_dstream *d) {
-    hipFree(d->d_rows); hipFree(d->d_carry); hipFree(d->d_win); hipFree(d->d_tab); hipFree(d->d_stats); hipFree(d->d_snap);
-    hipFree(d->d_state); hipFree(d->d_job);
-    d->d_rows = d->d_carry = d->d_win = d->d_tab = nullptr; d->d_stats = d->d_snap = nullptr; d->d_state = nullptr; d->d_job = nullptr;
-}
-
 static void dstream_free(nblic_amd_dstream *d) {
     if (!d) return;
-    if (hipSetDevice(d->device) == hipSuccess) {
-        if (d->st) hipStreamSynchronize(d->st);
-        dstream_free_device(d);
-        if (d->own_st) hipStreamDestroy(d->st);
-    }
-    delete d;
+    if (hipSetDevice(d->device) == hipSuccess && d->st) hipStreamSynchronize(d->st);
+    delete d;                                                            // the workspace, then the stream
 }
 
 static size_t dstream_win_cap(int band_rows, int w) {
@@ -1960,18 +1843,17 @@ static bool dstream_setup(nblic_amd_dstream *d) {
     d->stats_bytes = lsq_stats_bytes(it.kind, it.effort, it.w);
     d->win_cap = dstream_win_cap(d->band_rows, it.w);
     const size_t rows_bytes = size_t(d->band_rows + 2) * size_t(it.w);
-    bool ok = hipMalloc((void **)&d->d_rows, rows_bytes) == hipSuccess && hipMalloc((void **)&d->d_carry, 2 * size_t(it.w)) == hipSuccess &&
-              hipMalloc((void **)&d->d_win, d->win_cap + 2048) == hipSuccess &&
-              hipMalloc((void **)&d->d_state, up256(record_state_bytes(it.kind))) == hipSuccess &&
-              hipMalloc((void **)&d->d_job, sizeof(SerialJob)) == hipSuccess;
-    if (ok && d->stats_bytes) ok = hipMalloc((void **)&d->d_stats, d->stats_bytes) == hipSuccess && hipMalloc((void **)&d->d_snap, d->stats_bytes / 2) == hipSuccess &&
+    DevPool &m = d->mem;
+    bool ok = (d->d_rows = m.make<uint8_t>(rows_bytes)) && (d->d_carry = m.make<uint8_t>(2 * size_t(it.w))) &&
+              (d->d_win = m.make<uint8_t>(d->win_cap + 2048)) &&
+              (d->d_state = reinterpret_cast<SerialState *>(m.make<uint8_t>(up256(record_state_bytes(it.kind))))) &&
+              (d->d_job = m.make<SerialJob>(1));
+    if (ok && d->stats_bytes) ok = (d->d_stats = m.make<double>(d->stats_bytes / sizeof(double))) && (d->d_snap = m.make<double>(d->stats_bytes / 2 / sizeof(double))) &&
                                    hipMemsetAsync(d->d_stats, 0, d->stats_bytes, d->st) == hipSuccess;     // NBLIC.c:789
-    if (ok && it.kind) ok = hipMalloc((void **)&d->d_tab, kQTab) == hipSuccess;
+    if (ok && it.kind) ok = (d->d_tab = m.make<uint8_t>(kQTab)) != nullptr;
     ok = ok && hipMemsetAsync(d->d_state, 0, up256(record_state_bytes(it.kind)), d->st) == hipSuccess &&
          hipMemsetAsync(d->d_rows, 0, rows_bytes, d->st) == hipSuccess && hipMemsetAsync(d->d_win, 0, d->win_cap + 2048, d->st) == hipSuccess;
-    if (!ok) { fprintf(stderr, "[nblic_amd] band decoder: cannot set up the workspace\n"); dstream_free_device(d); return false; }
-    d->device_bytes = rows_bytes + 2 * size_t(it.w) + d->win_cap + 2048 + up256(record_state_bytes(it.kind)) + sizeof(SerialJob) +
-                      d->stats_bytes + d->stats_bytes / 2 + (it.kind ? kQTab : 0);
+    if (!ok) { fprintf(stderr, "[nblic_amd] band decoder: cannot set up the workspace\n"); m.reset(); return false; }     // (the caller marks d failed or frees it: nothing looks at the workspace again)
     return true;
 }
 
@@ -2054,10 +1936,8 @@ static int dstream_run(nblic_amd_dstream *d, double budget_s, unsigned char *row
                               hipStreamSynchronize(d->st) != hipSuccess)) return fail("restore");
             if (dstream_window_holds_all_fed(d)) return report(2);       // more bytes have to come first
             // the window itself was too small for the row: grow it (the caller has fed the bytes)
-            hipFree(d->d_win); d->d_win = nullptr;
             const size_t cap2 = d->win_cap * 2;
-            if (hipMalloc((void **)&d->d_win, cap2 + 2048) != hipSuccess || hipMemsetAsync(d->d_win, 0, cap2 + 2048, d->st) != hipSuccess) return fail("window");
-            d->device_bytes += cap2 - d->win_cap;
+            if (d->mem.renew(d->d_win, cap2 + 2048) != hipSuccess || hipMemsetAsync(d->d_win, 0, cap2 + 2048, d->st) != hipSuccess) return fail("window");
             d->win_cap = cap2; d->win_len = 0;
             continue;
         }
@@ -2118,11 +1998,8 @@ static size_t dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap, in
 static nblic_amd_dstream *dstream_new(nblic_amd_ctx *c, int band_rows, hipStream_t st = nullptr) {
     if (!c || hipSetDevice(c->device) != hipSuccess) return nullptr;
     auto *d = new nblic_amd_dstream;
-    d->c = c; d->device = c->device; d->band_rows_req = band_rows; d->st = st;
-    if (!st) {
-        if (hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking) != hipSuccess) { d->st = nullptr; dstream_free(d); return nullptr; }
-        d->own_st = true;
-    }
+    d->c = c; d->device = c->device; d->band_rows_req = band_rows; d->st = Stream::lent(st);
+    if (!st && d->st.create(hipStreamNonBlocking) != hipSuccess) { dstream_free(d); return nullptr; }
     return d;
 }
 
@@ -2431,7 +2308,7 @@ static size_t stream_index(nblic_amd_stream *s, void *buf, size_t cap) {
 }
 
 // One indexed decode call: the checked index, the described stream, and the device side -- its own HIP stream and
-// buffers, freed on every path out.
+// buffers (mem), released on every path out: the stream synchronised, then the buffers, then the stream.
 struct IndexedRun {
     IndexView V;
     DecodeItem it{};
@@ -2439,21 +2316,10 @@ struct IndexedRun {
     size_t slen = 0;
     int rows = 0;                      // rows per launch
     unsigned long long *redo = nullptr; // the context's redo counters (SerialJob::redo)
-    hipStream_t st = nullptr;
+    Stream st;
+    DevPool mem;
     uint8_t *d_tab = nullptr;          // QNBLIC tables
-    std::vector<void *> bufs;
-    ~IndexedRun() {
-        if (st) hipStreamSynchronize(st);
-        for (void *p : bufs) hipFree(p);
-        if (st) hipStreamDestroy(st);
-    }
-    template <class T>
-    T *alloc(size_t bytes) {
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return nullptr;
-        bufs.push_back(p);
-        return static_cast<T *>(p);
-    }
+    ~IndexedRun() { if (st) hipStreamSynchronize(st); }
 };
 
 // The host half of an indexed decode: the index against the stream, the stream's description.  false: refused.
@@ -2470,9 +2336,9 @@ static bool indexed_check(IndexedRun &run, nblic_amd_ctx *c, const unsigned char
 // The device half: the call's HIP stream, and the QNBLIC tables on the device.
 static bool indexed_begin(IndexedRun &run, nblic_amd_ctx *c) {
     if (hipSetDevice(c->device) != hipSuccess) return false;
-    if (hipStreamCreateWithFlags(&run.st, hipStreamNonBlocking) != hipSuccess) { run.st = nullptr; return false; }
+    if (run.st.create(hipStreamNonBlocking) != hipSuccess) return false;
     if (!run.it.kind) return true;
-    run.d_tab = run.alloc<uint8_t>(kQTab);
+    run.d_tab = run.mem.make<uint8_t>(kQTab);
     return run.d_tab && hipMemcpyAsync(run.d_tab, run.qtab.data(), kQTab, hipMemcpyHostToDevice, run.st) == hipSuccess;
 }
 
@@ -2545,9 +2411,9 @@ static int decode_indexed(nblic_amd_ctx *c, const unsigned char *stream, size_t 
     const size_t per_seg = rec_bytes + up256(stats_bytes);
     int per_round = int(std::max<size_t>(1, std::min<size_t>(size_t(nseg), kIndexedRoundBytes / per_seg)));
     if (c->index_round_segments > 0) per_round = std::min(per_round, c->index_round_segments);
-    uint8_t *d_stream = run.alloc<uint8_t>(stream_buf_bytes(slen)), *d_plane = run.alloc<uint8_t>(plane_bytes);
-    uint8_t *d_recs = run.alloc<uint8_t>(size_t(per_round) * per_seg);
-    SerialJob *d_jobs = run.alloc<SerialJob>(size_t(per_round) * sizeof(SerialJob));
+    uint8_t *d_stream = run.mem.make<uint8_t>(stream_buf_bytes(slen)), *d_plane = run.mem.make<uint8_t>(plane_bytes);
+    uint8_t *d_recs = run.mem.make<uint8_t>(size_t(per_round) * per_seg);
+    SerialJob *d_jobs = run.mem.make<SerialJob>(size_t(per_round));
     if (!d_stream || !d_plane || !d_recs || !d_jobs) return fail("cannot allocate the workspace");
     const hipStream_t st = run.st;
     if (!upload_stream(d_stream, stream, slen, st)) return fail("upload");
@@ -2619,10 +2485,10 @@ static int decode_rows(nblic_amd_ctx *c, const unsigned char *stream, size_t sle
         off = E.feed_from;
     }
     const size_t win = size_t(slen - off), stats_bytes = 2 * run.V.L.b_bytes;
-    uint8_t *d_win = run.alloc<uint8_t>(stream_buf_bytes(win)), *d_rows = run.alloc<uint8_t>(size_t(row1 - base) * w);
-    uint8_t *d_rec = run.alloc<uint8_t>(up256(run.V.L.b));
-    double *d_stats = stats_bytes ? run.alloc<double>(stats_bytes) : nullptr;
-    SerialJob *d_job = run.alloc<SerialJob>(sizeof(SerialJob));
+    uint8_t *d_win = run.mem.make<uint8_t>(stream_buf_bytes(win)), *d_rows = run.mem.make<uint8_t>(size_t(row1 - base) * w);
+    uint8_t *d_rec = run.mem.make<uint8_t>(up256(run.V.L.b));
+    double *d_stats = stats_bytes ? run.mem.make<double>(stats_bytes / sizeof(double)) : nullptr;
+    SerialJob *d_job = run.mem.make<SerialJob>(1);
     if (!d_win || !d_rows || !d_rec || !d_job || (stats_bytes && !d_stats)) return fail("cannot allocate the workspace");
     const hipStream_t st = run.st;
     std::vector<uint8_t> stage(run.V.L.b);
@@ -2760,9 +2626,8 @@ nblic_amd_ctx *nblic_amd_create_ex(int device, int n_groups, int group_size, int
     }
     c->cbufs.resize(size_t(n_host_buffers));
     for (int i = 0; i < n_host_buffers; i++) c->free_cbufs.push_back(i);
-    if (hipStreamCreateWithFlags(&c->dec_stream, hipStreamNonBlocking) != hipSuccess) { c->dec_stream = nullptr; nblic_amd_destroy(c); return nullptr; }
-    if (hipMalloc((void **)&c->d_redo, 2 * sizeof(unsigned long long)) != hipSuccess || hipMemset(c->d_redo, 0, 2 * sizeof(unsigned long long)) != hipSuccess) { nblic_amd_destroy(c); return nullptr; }
-    if (hipStreamCreateWithFlags(&c->dec_stream2, hipStreamNonBlocking) != hipSuccess) { c->dec_stream2 = nullptr; nblic_amd_destroy(c); return nullptr; }
+    if (c->dec_stream.create(hipStreamNonBlocking) != hipSuccess || c->d_redo.alloc(2) != hipSuccess || hipMemset(c->d_redo, 0, 2 * sizeof(unsigned long long)) != hipSuccess ||
+        c->dec_stream2.create(hipStreamNonBlocking) != hipSuccess) { nblic_amd_destroy(c); return nullptr; }
     // (Measured and rejected: creating the copy streams with the highest stream priority, so that the
     // coder threads' short interleave kernels and copies overtake the encoder's long kernels -- the
     // pipeline drops from 4.9 to 3.1 Gpx/s.)
@@ -2774,7 +2639,7 @@ nblic_amd_ctx *nblic_amd_create_ex(int device, int n_groups, int group_size, int
     if (const char *cs = getenv("NBLIC_AMD_COPY_STREAMS")) { const int v = atoi(cs); if (v >= 1 && v <= 32) n_copy = v; }   // experiments with the copy engines
     c->copy_streams.resize(size_t(n_copy));
     for (auto &cs : c->copy_streams)
-        if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess) { cs = nullptr; nblic_amd_destroy(c); return nullptr; }
+        if (cs.create(hipStreamNonBlocking) != hipSuccess) { nblic_amd_destroy(c); return nullptr; }
     c->coders_wanted = n_coders;
     if (const char *mt = getenv("NBLIC_AMD_MAX_TAKE")) { const int v = atoi(mt); if (v >= 2 && v <= kMaxTake) c->max_take = v; }
     for (int i = 0; i < n_coders; i++) c->coders.emplace_back(coder_main, c, i);
@@ -2804,15 +2669,11 @@ void nblic_amd_destroy(nblic_amd_ctx *c) {
     { std::lock_guard<std::mutex> l(c->dm); c->stop_drivers = true; }
     c->dcv.notify_all();
     for (auto &t : c->drivers) t.join();
-    for (auto &g : c->groups) group_free(g);
-    for (auto &cb : c->cbufs) if (cb.p) hipFree(cb.p);
-    for (auto &cs : c->copy_streams) if (cs) hipStreamDestroy(cs);
-    hipFree(c->dec_arena); hipFree(c->dec_jobs); hipFree(c->d_redo);
     if (c->feed_pipe[0] >= 0) { close(c->feed_pipe[0]); close(c->feed_pipe[1]); }
-    if (c->dec_stream) hipStreamDestroy(c->dec_stream);
-    if (c->dec_stream2) hipStreamDestroy(c->dec_stream2);
-    delete c;
+    delete c;                                                                // every thread has ended: the members release what they own
 }
+
+void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
 
 void nblic_amd_set_max_pixels(nblic_amd_ctx *c, long max_pixels) {
     if (!c) c = default_ctx();                                               // NULL: the context behind the drop-in entry points
@@ -3008,7 +2869,7 @@ int nblic_amd_dstream_progress(nblic_amd_dstream *d, int *rows_done, unsigned lo
     if (rows_done) *rows_done = d->have_head ? d->H.next_row : 0;
     if (feed_from) *feed_from = d->have_head ? (d->H.pos & ~511ull) : 0ull;
     if (sha256) { Sha256 copy = d->sha; copy.digest(sha256); }
-    if (device_bytes) *device_bytes = d->device_bytes;
+    if (device_bytes) *device_bytes = d->mem.bytes();
     return (d->failed || d->refused) ? -1 : (d->done ? 1 : 0);
 }
 size_t nblic_amd_dstream_checkpoint(nblic_amd_dstream *d, void *buf, size_t cap) { return d ? dstream_checkpoint(d, buf, cap, d->band_rows, d->sha) : 0; }
