@@ -128,6 +128,28 @@ static void lsq_update(int n, int m, i64 *E, i64 *B, const i64 *vn, int x, i64 s
 /* ------------------------------------------------------------------------
  * Engine: all adaptive state of one image stream.
  * ---------------------------------------------------------------------- */
+/* Coverage of the binarisation walk over one encode (tests/: which decoder regimes a case set reaches).
+ * qu[]: symbols per starting level; k[]: symbols per suffix length actually coded; escalations: moves to the next
+ * level's tree; beyond_lanes: symbols whose prefix has at least min(NB_TREE >> k_max, 64) ones.                 */
+typedef struct { long qu[NB_NQD]; long k[8]; long escalations; long beyond_lanes; } walk_cov;
+enum { WALK_COV_LONGS = NB_NQD + 8 + 2 };
+static walk_cov last_cov;
+
+/* the prefix of nb_walk_symbol for a known symbol, counted; codes nothing */
+static void walk_count(walk_cov *c, int k_step, int qu, int z) {
+    const int k_max = (NB_NQD - 1) / k_step;
+    const int reach = (NB_TREE >> k_max) < 64 ? (NB_TREE >> k_max) : 64;
+    int node = 0, ones = 0, k = qu / k_step;
+    c->qu[qu]++;
+    while ((node >> k_max) < (z >> k)) {
+        ones++;
+        node += 1 << k_max;
+        if (node >= NB_TREE) { node >>= 1; qu = (k + 1) * k_step; k = qu / k_step; c->escalations++; }
+    }
+    c->k[k]++;
+    if (ones >= reach) c->beyond_lanes++;
+}
+
 typedef struct {
     int        near, k_step, effort, n, m, w, h;
     int        ctx[NB_NCTX];
@@ -140,6 +162,7 @@ typedef struct {
     i64        bias;
     /* statistics, filled when non-NULL */
     long       n_bins;
+    walk_cov   cov;                  /* encoder only: which parts of the binarisation walk the image visits */
 } engine;
 
 static int engine_bin(void *vp, int qu, int qv, int node, int qw, int bin) {
@@ -205,6 +228,7 @@ static void engine_pixel(engine *en, uint8_t *recon, int i, int j, int decoding,
     if (!decoding) {
         int x = recon[(size_t)i * w + j];
         y = nb_x_to_y(x, px, sign, en->near);
+        walk_count(&en->cov, en->k_step, qu, nb_mapper_y2z(mp, y));
         nb_walk_symbol(en->k_step, qu, qv, qw, nb_mapper_y2z(mp, y), engine_bin, en);
     } else {
         y = nb_mapper_z2y(mp, nb_walk_symbol(en->k_step, qu, qv, qw, -1, engine_bin, en));
@@ -246,6 +270,25 @@ static int size_ok(int h, int w, long max_px) {          /* NBLIC.c:717-729 */
  * Exported entry points
  * ---------------------------------------------------------------------- */
 
+/* Header, then the body, with the k_step given: what both encode entry points do once their arguments are settled. */
+static long encode_with(uint8_t *out, uint8_t *img, int h, int w, int near, int k_step, int effort, long max_px, long *n_bins) {
+    uint8_t *p = out;
+    memcpy(p, NB_MAGIC, 8); p += 8;
+    *p++ = 1;
+    *p++ = (uint8_t)(h >> 8); *p++ = (uint8_t)h;
+    *p++ = (uint8_t)(w >> 8); *p++ = (uint8_t)w;
+    *p++ = (uint8_t)near; *p++ = (uint8_t)k_step; *p++ = (uint8_t)effort;
+    if (!size_ok(h, w, max_px)) return -1;
+    engine *en = (engine *)malloc(sizeof(engine));
+    if (!en || engine_init(en, h, w, near, k_step, effort, p, 0)) { free(en); return -1; }
+    engine_run(en, img, 0);
+    long len = (long)(en->rc.p - out);
+    if (n_bins) *n_bins = en->n_bins;
+    last_cov = en->cov;
+    free(en);
+    return len;
+}
+
 /* Encode.  `img` is overwritten with the reconstruction exactly like the reference
  * (NBLIC.c:876).  *near / *effort are clamped and written back (:768-770).
  * max_px <= 0 selects the reference limit of 100,000,000 pixels.  Returns stream bytes or -1. */
@@ -254,21 +297,20 @@ long orc_nblic_encode(uint8_t *out, uint8_t *img, int h, int w, int *near, int *
     *near   = nb_clip(*near, 0, NB_MAX_NEAR);
     *effort = nb_clip(*effort, 1, 3);
     int k_step = nb_clip(NB_MIN_KSTEP + 2 * *near, NB_MIN_KSTEP, NB_NQD);
-    uint8_t *p = out;
-    memcpy(p, NB_MAGIC, 8); p += 8;
-    *p++ = 1;
-    *p++ = (uint8_t)(h >> 8); *p++ = (uint8_t)h;
-    *p++ = (uint8_t)(w >> 8); *p++ = (uint8_t)w;
-    *p++ = (uint8_t)*near; *p++ = (uint8_t)k_step; *p++ = (uint8_t)*effort;
-    if (!size_ok(h, w, max_px)) return -1;
-    engine *en = (engine *)malloc(sizeof(engine));
-    if (!en || engine_init(en, h, w, *near, k_step, *effort, p, 0)) { free(en); return -1; }
-    engine_run(en, img, 0);
-    long len = (long)(en->rc.p - out);
-    if (n_bins) *n_bins = en->n_bins;
-    free(en);
-    return len;
+    return encode_with(out, img, h, w, *near, k_step, *effort, max_px, n_bins);
 }
+
+/* Encode with the k_step given instead of derived from near: the streams the reference's decoder accepts
+ * (NBLIC.c:733-745, :765) and no encoder writes.  Nothing is clamped: arguments the decoder's header check would
+ * refuse give -1 before anything is written.                                                                    */
+long orc_nblic_encode_kstep(uint8_t *out, uint8_t *img, int h, int w, int near, int k_step, int effort) {
+    if (near < 0 || near > NB_MAX_NEAR || k_step < NB_MIN_KSTEP || k_step > NB_NQD || effort < 1 || effort > 3 ||
+        !size_ok(h, w, 100000000L)) return -1;
+    return encode_with(out, img, h, w, near, k_step, effort, 100000000L, NULL);
+}
+
+/* The walk coverage of the last encode of this library: qu[16], k[8], escalations, beyond_lanes. */
+void orc_walk_coverage(long *out) { memcpy(out, &last_cov, sizeof(long) * WALK_COV_LONGS); }
 
 /* Decode.  Returns 0 / -1; all four geometry/parameter outputs come from the header. */
 int orc_nblic_decode(const uint8_t *in, uint8_t *img, int *h, int *w, int *near, int *effort, long max_px) {

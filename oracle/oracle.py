@@ -62,6 +62,10 @@ class Oracle:
             lib = C.CDLL(os.path.join(_HERE, "liboracle.so"))
             lib.orc_nblic_encode.restype = C.c_long
             lib.orc_nblic_encode.argtypes = [_u8p, _u8p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_long, C.POINTER(C.c_long)]
+            lib.orc_nblic_encode_kstep.restype = C.c_long
+            lib.orc_nblic_encode_kstep.argtypes = [_u8p, _u8p] + [C.c_int] * 5
+            lib.orc_walk_coverage.restype = None
+            lib.orc_walk_coverage.argtypes = [C.POINTER(C.c_long)]
             lib.orc_nblic_decode.restype = C.c_int
             lib.orc_nblic_decode.argtypes = [_u8p, _u8p] + [C.POINTER(C.c_int)] * 4 + [C.c_long]
             lib.orc_nblic_encode_staged.restype = C.c_long
@@ -75,17 +79,30 @@ class Oracle:
         self.lib = Oracle._lib
 
     # -- fused engine -----------------------------------------------------
-    def encode(self, img: np.ndarray, near: int = 0, effort: int = 1, max_px: int = 0):
-        """Returns (stream bytes, reconstruction, near_out, effort_out, n_bins)."""
+    def encode(self, img: np.ndarray, near: int = 0, effort: int = 1, max_px: int = 0, k_step=None):
+        """Returns (stream bytes, reconstruction, near_out, effort_out, n_bins).  k_step=None: the encoders' own
+        clip(3 + 2 near, 3, 16).  A k_step given goes into the header as it is (orc_nblic_encode_kstep): nothing is
+        clamped, arguments a decoder would refuse give a None stream, and n_bins is not counted (0)."""
         img = np.ascontiguousarray(img, np.uint8)
         h, w = img.shape
         rec = img.copy()
         out = np.empty(out_capacity(h, w), np.uint8)
+        if k_step is not None:
+            ln = self.lib.orc_nblic_encode_kstep(_ptr(out), _ptr(rec), h, w, int(near), int(k_step), int(effort))
+            return (None if ln < 0 else out[:ln].tobytes()), rec, int(near), int(effort), 0
         n, e, nb = C.c_int(near), C.c_int(effort), C.c_long(0)
         ln = self.lib.orc_nblic_encode(_ptr(out), _ptr(rec), h, w, C.byref(n), C.byref(e), max_px, C.byref(nb))
         if ln < 0:
             return None, rec, n.value, e.value, 0
         return out[:ln].tobytes(), rec, n.value, e.value, nb.value
+
+    def walk_coverage(self) -> dict:
+        """Which parts of the binarisation walk the last ``encode`` visited (the oracle's own counters; the product has
+        none): symbols per starting level ``qu`` (16) and per suffix length ``k``, ``escalations`` to the next level's
+        tree, and ``beyond_lanes``, symbols whose prefix has at least min(256 >> k_max, 64) ones."""
+        v = (C.c_long * 26)()
+        self.lib.orc_walk_coverage(v)
+        return {"qu": list(v[:16]), "k": list(v[16:24]), "escalations": int(v[24]), "beyond_lanes": int(v[25])}
 
     def decode(self, stream: bytes, max_px: int = 0):
         """Returns (image, near, effort) or None."""

@@ -276,7 +276,8 @@ extern "C" long hh_check_divide_free(void) {
                 for (int y = 0; y < 300; y++) bad += symbol_to_pixel(y, px, sign, np) != symbol_to_pixel(y, px, sign, near);
                 for (int x = 0; x < 256; x++) bad += reconstruct_pixel(x, px, np) != symbol_to_pixel(residual_to_symbol(x, px, sign, near), px, sign, near);
             }
-        const int k_step = k_step_for_near(near);
+    }
+    for (int k_step = kMinKStep; k_step <= kLevels; k_step++) {   // every step a decoder accepts, not only the encoders' k_step_for_near
         const uint64_t ktab = level_shift_table(k_step);
         for (int qu = 0; qu < kLevels; qu++)
             for (int dq = -1; dq <= 1; dq++) {
@@ -381,25 +382,36 @@ extern "C" long hh_check_lane_front(int qnblic, int seed) {
 
 // The decoders' lane layout of a symbol's bins (serial_engine.hip decode_symbol) against the walk itself: for every
 // k_step, level pair and symbol, the nodes walk_symbol visits must be node t << k_max for the t-th prefix bin (while the
-// prefix stays inside the level's tree and the lanes: afterwards the kernel walks bin by bin like the reference) and, for
-// the suffix, root + suffix_lane_offset(k, d, prefix) with the lane moving 2 l + 1 + bin in heap order.
+// prefix stays inside the level's tree and the lanes: afterwards the kernel walks bin by bin like the reference, and the
+// nodes and trees of that continuation are compared too) and, for the suffix, root + suffix_lane_offset(k, d, prefix) with the lane moving 2 l + 1 + bin in heap order.
 extern "C" long hh_check_symbol_lanes(void) {
     long bad = 0, checked = 0;
-    for (int near = 0; near <= kMaxNear; near++) {
-        const int k_step = k_step_for_near(near), k_max = (kLevels - 1) / k_step;
+    for (int k_step = kMinKStep; k_step <= kLevels; k_step++) {   // every step a decoder accepts, not only the encoders' k_step_for_near
+        const int k_max = (kLevels - 1) / k_step;
         const int reach = (kTreeNodes >> k_max) < 64 ? (kTreeNodes >> k_max) : 64;
         for (int qu = 0; qu < kLevels; qu++)
             for (int dq = -1; dq <= 1; dq++) {
                 const int qv = qu + dq;
                 if (qv < 0 || qv >= kLevels) continue;
                 for (int z = 0; z < 400; z++) {
-                    std::vector<int> nodes, bins;
-                    walk_symbol(k_step, qu, qv, z, [&](int, int, int node, int bin) { nodes.push_back(node); bins.push_back(bin); return bin; });
+                    std::vector<int> nodes, bins, trees;
+                    walk_symbol(k_step, qu, qv, z, [&](int tu, int, int node, int bin) { nodes.push_back(node); bins.push_back(bin); trees.push_back(tu); return bin; });
                     // prefix: bins up to and including the first zero
                     size_t n_prefix = 0;
                     while (bins[n_prefix]) n_prefix++;
                     n_prefix++;
-                    for (size_t t = 0; t < n_prefix && int(t) < reach; t++) { bad += nodes[t] != int(t) << k_max; checked++; }
+                    for (size_t t = 0; t < n_prefix && int(t) < reach; t++) { bad += nodes[t] != int(t) << k_max || trees[t] != qu; checked++; }
+                    // beyond the lanes the kernel goes on bin by bin from node reach << k_max: on in the same tree, or, at the
+                    // tree's end, from the middle of the next level's (symbols a stream can hold: escalation stays below level 16)
+                    if (z < 256) {
+                        int node = reach << k_max, k = qu / k_step, tree = qu;
+                        for (size_t t = size_t(reach); t < n_prefix; t++) {
+                            if (node >= kTreeNodes) { node >>= 1; k++; tree = k * k_step; }
+                            bad += nodes[t] != node || trees[t] != tree || tree >= kLevels;
+                            checked++;
+                            node += 1 << k_max;
+                        }
+                    }
                     // suffix: heap order below the node after the prefix's last
                     const int k = int(nodes.size() - n_prefix), root = nodes[n_prefix - 1] + 1;
                     int lane = 0;

@@ -89,6 +89,59 @@ def make_hard(content, h, w):
     raise ValueError(content)
 
 
+def spikes(h=32, w=48):
+    """A flat plane (77) with isolated extremes: 255 on a 7 x 5 grid, 0 on an 11 x 9 grid.  In a quiet context every
+    spike is a symbol of a hundred and more, so the binarisation's unary prefix runs far past 64 ones."""
+    img = np.full((h, w), 77, np.uint8)
+    img[::7, ::5] = 255
+    img[3::11, 2::9] = 0
+    return img
+
+
+# Streams no encoder writes.  A decoder takes k_step from byte 14 of the header and accepts 3..16 with any near 0..9
+# (NBLIC.c:733-745, :765); the encoders only ever write clip(3 + 2 near, 3, 16).  The 140 pairs, in the fixed order the
+# hashes of tests/golden/foreign_streams.json are taken in:
+FOREIGN_PAIRS = [(near, k_step) for near in range(10) for k_step in range(3, 17)]
+FOREIGN_EFFORTS = (1, 2, 3)
+
+
+def paired_k_step(near):
+    return min(max(3 + 2 * near, 3), 16)
+
+
+def foreign_planes():
+    """name -> plane: the smallest planes that between them reach every regime of the binarisation walk at every k_step
+    (test_oracle.py test_foreign_planes_reach_every_walk_regime); at most 2700 pixels each."""
+    _, arrays = fixtures()
+    return {
+        "kodak05": np.ascontiguousarray(arrays["kodak_crops"][4][:40, :56]),
+        "blocks": make_hard("blocks_lossless", 33, 81),
+        "noise": noise(24, 40),
+        "syn1": syn1(24, 40),
+        "spikes": spikes(),
+        "checker": make("checker", 17, 13),
+    }
+
+
+def foreign_streams(oracle, plane, efforts=FOREIGN_EFFORTS, pairs=None):
+    """[((near, k_step, effort), stream, reconstruction)] from the oracle, efforts outermost, pairs in FOREIGN_PAIRS order."""
+    out = []
+    for effort in efforts:
+        for near, k_step in (FOREIGN_PAIRS if pairs is None else pairs):
+            s, rec, *_ = oracle.encode(plane, near, effort, k_step=k_step)
+            out.append(((near, k_step, effort), s, rec))
+    return out
+
+
+def foreign_golden():
+    """tests/golden/foreign_streams.json (make_foreign.py): per "<plane>_e<effort>" the SHA-256 of the 140 oracle streams
+    concatenated and of the 140 planes the compiled reference decoded them to."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "foreign_streams.json")) as f:
+        return json.load(f)
+
+
 def case_id(content, h, w, near, effort):
     return f"{content}_{h}x{w}_n{near}_e{effort}"
 

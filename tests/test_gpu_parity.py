@@ -37,28 +37,89 @@ def test_wave_primitives_selftest(gpu_ctx):
 STAGE_SHAPES = [(1, 1), (1, 9), (9, 1), (2, 2), (3, 5), (17, 13), (40, 37), (64, 64), (96, 128), (5, 300)]
 
 
+def _assert_stage_parity(gpu_ctx, oracle, img, content):
+    """Every intermediate array of the staged -e1 pipeline for one image, against oracle.stages."""
+    st = oracle.stages(img)
+    px0, adr, qu, qv, qw = unpack_rec1(gpu_ctx.debug_stage(img, "rec1"))
+    assert np.array_equal(px0, st["px0"]), ("px0", content)
+    assert np.array_equal(adr, st["adr"]), ("adr", content)
+    assert np.array_equal(qu, st["qu"]) and np.array_equal(qv, st["qv"]) and np.array_equal(qw, st["qw"]), ("level", content)
+    pxs = gpu_ctx.debug_stage(img, "pxs")
+    assert np.array_equal(pxs & 0xFF, st["px"]) and np.array_equal(pxs >> 8, st["sign"]), ("S2", content)
+    assert np.array_equal(gpu_ctx.debug_stage(img, "z"), st["z"]), ("S3", content)
+    assert np.array_equal(gpu_ctx.debug_stage(img, "cnt"), st["ev_count"]), ("S4 count", content)
+    ev = gpu_ctx.debug_stage(img, "events")
+    assert len(ev) == len(st["cu"])
+    e_qu, e_qv, node = ev & 15, (ev >> 4) & 15, (ev >> 8) & 255
+    assert np.array_equal(e_qu * 256 + node, st["cu"]) and np.array_equal(e_qv * 256 + node, st["cv"]), ("S4 path", content)
+    assert np.array_equal((ev >> 16) & 31, st["ev_qw"]) and np.array_equal((ev >> 21) & 1, st["ev_bin"]), ("S4 bins", content)
+    coded = gpu_ctx.debug_stage(img, "coded")
+    assert np.array_equal(coded & 0xFFF, st["prob"]), ("S5 prob", content)
+    assert np.array_equal(coded >> 15, st["ev_bin"]), ("S5 bin", content)
+    return st
+
+
 @pytest.mark.parametrize("shape", STAGE_SHAPES)
 def test_stage_parity(gpu_ctx, oracle, shape):
     h, w = shape
     for content in ("syn1", "noise", "checker", "const", "ramp"):
-        img = inputs.make(content, h, w)
-        st = oracle.stages(img)
-        px0, adr, qu, qv, qw = unpack_rec1(gpu_ctx.debug_stage(img, "rec1"))
-        assert np.array_equal(px0, st["px0"]), ("px0", content)
-        assert np.array_equal(adr, st["adr"]), ("adr", content)
-        assert np.array_equal(qu, st["qu"]) and np.array_equal(qv, st["qv"]) and np.array_equal(qw, st["qw"]), ("level", content)
-        pxs = gpu_ctx.debug_stage(img, "pxs")
-        assert np.array_equal(pxs & 0xFF, st["px"]) and np.array_equal(pxs >> 8, st["sign"]), ("S2", content)
-        assert np.array_equal(gpu_ctx.debug_stage(img, "z"), st["z"]), ("S3", content)
-        assert np.array_equal(gpu_ctx.debug_stage(img, "cnt"), st["ev_count"]), ("S4 count", content)
-        ev = gpu_ctx.debug_stage(img, "events")
-        assert len(ev) == len(st["cu"])
-        e_qu, e_qv, node = ev & 15, (ev >> 4) & 15, (ev >> 8) & 255
-        assert np.array_equal(e_qu * 256 + node, st["cu"]) and np.array_equal(e_qv * 256 + node, st["cv"]), ("S4 path", content)
-        assert np.array_equal((ev >> 16) & 31, st["ev_qw"]) and np.array_equal((ev >> 21) & 1, st["ev_bin"]), ("S4 bins", content)
-        coded = gpu_ctx.debug_stage(img, "coded")
-        assert np.array_equal(coded & 0xFFF, st["prob"]), ("S5 prob", content)
-        assert np.array_equal(coded >> 15, st["ev_bin"]), ("S5 bin", content)
+        _assert_stage_parity(gpu_ctx, oracle, inputs.make(content, h, w), content)
+
+
+def kodak_crops():
+    """The 24 stored 64x96 Kodak crops (tests/golden/reference_fixtures.npz) and the reference's figures for them."""
+    meta, arrays = inputs.fixtures()
+    names = sorted(meta["kodak_crops"])
+    return names, [np.ascontiguousarray(c) for c in arrays["kodak_crops"]], [meta["kodak_crops"][n] for n in names]
+
+
+@pytest.mark.parametrize("content", ["kodak05_crop", "kodak_mosaic"])
+def test_stage_parity_photographic(gpu_ctx, oracle, content):
+    """Photographic pixels through every stage: one 64x96 crop, and a mosaic of 4 x 4 crops (256 x 384, 98304 pixels)
+    whose counter chains run through many windows of 512 touches (the longest has 14836; asserted on the oracle's arrays,
+    so that the mosaic cannot quietly stop being long enough).  A photograph spreads its pixels over the contexts: the
+    longest context chain of the mosaic has 1452 records and stays inside one 4096-record block of k_bias_blocks; chains
+    of several blocks are test_flat_and_structured_images_multi_block's."""
+    _, crops, _ = kodak_crops()
+    if content == "kodak05_crop":
+        img = crops[4]
+    else:
+        img = np.ascontiguousarray(np.block([[crops[4 * r + c] for c in range(4)] for r in range(4)]))
+        assert img.shape == (256, 384)
+    st = _assert_stage_parity(gpu_ctx, oracle, img, content)
+    if content == "kodak_mosaic":
+        print("longest context chain", int(np.bincount(st["adr"], minlength=2048).max()), "records; longest counter chain",
+              int(np.bincount(st["cu"], minlength=4096).max()), "touches")
+        assert int(np.bincount(st["cu"], minlength=4096).max()) > 8 * 512
+
+
+def test_kodak_crops_give_the_reference_hashes(gpu_ctx):
+    """encode_batch / qencode_batch of the 24 stored crops: length and SHA-256 of the compiled reference's -e1 and -e0
+    streams (tests/golden/reference_fixtures.json, make_fixtures.py) -- expected values that no code of ours produced."""
+    names, crops, want = kodak_crops()
+    assert len(crops) == 24 and crops[0].shape == (64, 96)
+    got = gpu_ctx.encode_batch(crops)
+    gotq = gpu_ctx.qencode_batch(crops)
+    for name, s, q, m in zip(names, got, gotq, want):
+        assert (len(s), sha(s)) == (m["len"], m["sha256"]), name
+        assert (len(q), sha(q)) == (m["q_len"], m["q_sha256"]), name
+
+
+def test_kodak_crops_every_mode(gpu_ctx, pkg, oracle):
+    """The crops with inputs.PARAM_CLASSES cycled through encode_modes: streams and reconstructions against the oracle;
+    then decode_batch of all of them and the band decoder on three."""
+    names, crops, _ = kodak_crops()
+    classes = [inputs.PARAM_CLASSES[k % len(inputs.PARAM_CLASSES)] for k in range(len(crops))]
+    want = [oracle.encode(c, n, e) for c, (n, e) in zip(crops, classes)]
+    streams, recs = gpu_ctx.encode_modes(crops, [c[0] for c in classes], [c[1] for c in classes])
+    for name, s, r, w_, cl in zip(names, streams, recs, want, classes):
+        assert s == w_[0], (name, cl)
+        assert np.array_equal(r, w_[1]), (name, cl)
+        assert int(np.abs(r.astype(int) - crops[names.index(name)].astype(int)).max()) <= w_[2], (name, cl)
+    for name, g, w_, cl in zip(names, gpu_ctx.decode_batch(streams), want, classes):
+        assert g is not None and np.array_equal(g[0], w_[1]) and g[1:] == (w_[2], w_[3]), (name, cl)
+    for k, br in ((2, 1), (7, 5), (23, 0)):                               # (0, 3), (3, 3), (2, 2)
+        assert np.array_equal(pkg.decompress_bands(streams[k], band_rows=br, chunk=1000, ctx=gpu_ctx), want[k][1]), (names[k], classes[k])
 
 
 def test_batch_streams_equal_golden(gpu_ctx, golden):

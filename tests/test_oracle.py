@@ -120,6 +120,72 @@ def test_oracle_vs_live_reference(oracle):
             assert d is not None and np.array_equal(d[0], a[1])
 
 
+def test_kstep_entry_point_with_the_paired_step_is_encode(oracle):
+    """orc_nblic_encode_kstep given the k_step the encoders derive: encode's bytes and reconstruction; what a decoder's
+    header check refuses is refused before anything is coded."""
+    for img, near, effort in inputs.random_cases():
+        a = oracle.encode(img, near, effort)
+        b = oracle.encode(img, near, effort, k_step=inputs.paired_k_step(near))
+        assert a[0] == b[0] and np.array_equal(a[1], b[1]) and b[2:4] == (near, effort), (img.shape, near, effort)
+    img = inputs.make("syn1", 8, 8)
+    for near, k_step, effort in ((0, 2, 1), (0, 17, 1), (-1, 3, 1), (10, 16, 1), (0, 3, 0), (0, 3, 4)):
+        s, rec, *_ = oracle.encode(img, near, effort, k_step=k_step)
+        assert s is None and np.array_equal(rec, img), (near, k_step, effort)
+
+
+def test_foreign_planes_reach_every_walk_regime(oracle):
+    """The coverage condition of the foreign case set (inputs.foreign_planes), from the oracle's own counters, effort 1,
+    lossless: at every k_step symbols whose prefix outlasts the decoder's lanes, every level as the starting level,
+    every suffix length 0..k_max, escalations to the next tree wherever there is one (k_max = 0 at k_step 16: a valid
+    symbol cannot leave its tree)."""
+    planes = inputs.foreign_planes()
+    assert all(p.size <= 2700 for p in planes.values())
+    for k_step in range(3, 17):
+        k_max = 15 // k_step
+        qu, k, esc, beyond = [0] * 16, [0] * 8, 0, 0
+        for plane in planes.values():
+            assert oracle.encode(plane, 0, 1, k_step=k_step)[0] is not None
+            c = oracle.walk_coverage()
+            assert sum(c["qu"]) == sum(c["k"]) == plane.size
+            qu = [a + b for a, b in zip(qu, c["qu"])]
+            k = [a + b for a, b in zip(k, c["k"])]
+            esc += c["escalations"]
+            beyond += c["beyond_lanes"]
+        print(f"k_step {k_step}: beyond_lanes {beyond}, escalations {esc}, per suffix length {k[:k_max + 1]}, least-used level {min(qu)}")
+        assert beyond > 0, k_step
+        assert all(v > 0 for v in qu), (k_step, qu)
+        assert all(v > 0 for v in k[:k_max + 1]) and not any(k[k_max + 1:]), (k_step, k)
+        assert (esc > 0) if k_step <= 15 else (esc == 0), (k_step, esc)
+
+
+@pytest.mark.parametrize("name", ["kodak05", "blocks", "noise", "syn1", "spikes", "checker"])
+def test_foreign_streams_round_trip_and_reference_decodes_them(oracle, name):
+    """All 420 (near, k_step, effort) streams of one foreign plane: the oracle decodes each to its own reconstruction,
+    within near of the plane; their concatenation has the stored hash, and the stored hash of the planes the compiled
+    reference decoded them to (tests/golden/make_foreign.py) is the hash of the oracle's reconstructions.  Wherever
+    oracle/_ref was built the reference decodes every stream again, live."""
+    from oracle.oracle import Reference
+    plane = inputs.foreign_planes()[name]
+    stored = inputs.foreign_golden()
+    reference = Reference() if Reference.available() else None
+    for effort in inputs.FOREIGN_EFFORTS:
+        hs, hp = hashlib.sha256(), hashlib.sha256()
+        for (near, k_step, _), s, rec in inputs.foreign_streams(oracle, plane, (effort,)):
+            case = (name, near, k_step, effort)
+            assert s is not None and (s[13], s[14], s[15]) == (near, k_step, effort), case
+            assert int(np.abs(rec.astype(int) - plane.astype(int)).max()) <= near, case
+            d = oracle.decode(s)
+            assert d is not None and np.array_equal(d[0], rec) and d[1:] == (near, effort), case
+            if reference is not None:
+                r = reference.decode(s)
+                assert r is not None and np.array_equal(r[0], rec) and r[1:] == (near, effort), case
+            hs.update(s)
+            hp.update(rec.tobytes())
+        want = stored[f"{name}_e{effort}"]
+        assert hs.hexdigest() == want["streams_sha256"], (name, effort)
+        assert hp.hexdigest() == want["planes_sha256"], (name, effort)
+
+
 def test_oracle_on_kodak_matches_reference_and_readme(oracle, golden):
     """BASELINE config 3 content.  The 24 Kodak BMPs are third-party files and are read in place
     (container only); the manifest holds the compiled reference's length + SHA-256 per image, whose
