@@ -224,6 +224,17 @@ void nblic_amd_stream_end(nblic_amd_stream *s);
  * asked for an index. */
 int nblic_amd_stream_set_index(nblic_amd_stream *s, int every_rows);
 size_t nblic_amd_stream_index(nblic_amd_stream *s, void *buf, size_t cap);
+/* The FRONT a band's model stage runs on, per object: after _begin or _resume and before that object's first _run
+ * (0 / -1; -1 too for s == NULL, for a front other than 0 or 1, and for a mode the front does not take -- a refusal
+ * launches nothing and leaves the object as it was).
+ *   0  serial (the default): the one-wave model kernel of the serial modes, every near and effort.
+ *   1  staged: the band's rows go through the key-partitioned kernels of the batch pipeline (prediction, partition
+ *      by context, context-bias chains).  -n0 -e1 only: lossless -e1 is the one mode without a pixel-to-pixel
+ *      prediction chain.
+ * The stream bytes, the checkpoints and the index are byte-identical under both; the front is a property of the
+ * object, not of the checkpoint, so a checkpoint written under one front resumes under the other.  _progress's
+ * model_ms is the serial model kernel under front 0, the launches that replace it under front 1. */
+int nblic_amd_stream_set_front(nblic_amd_stream *s, int front);
 
 /* ONE stream DECODED in ROW BANDS (src/NBLIC.c:807-898 is a single pass over the rows): the caller feeds the stream in
  * pieces of any size as it arrives and takes the rows as they are finished; the device workspace depends on band_rows

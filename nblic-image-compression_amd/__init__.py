@@ -45,7 +45,7 @@ EXPORTS = (
     "nblic_amd_dstream_begin", "nblic_amd_dstream_resume", "nblic_amd_dstream_check", "nblic_amd_dstream_feed", "nblic_amd_dstream_info",
     "nblic_amd_dstream_run", "nblic_amd_dstream_progress", "nblic_amd_dstream_checkpoint", "nblic_amd_dstream_end",
     "nblic_amd_index_check", "nblic_amd_index_build", "nblic_amd_decode_indexed", "nblic_amd_decode_rows",
-    "nblic_amd_stream_set_index", "nblic_amd_stream_index", "nblic_amd_set_index_round",
+    "nblic_amd_stream_set_index", "nblic_amd_stream_index", "nblic_amd_set_index_round", "nblic_amd_stream_set_front",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -174,6 +174,8 @@ def load_library() -> C.CDLL:
     lib.nblic_amd_dstream_end.argtypes = [C.c_void_p]
     lib.nblic_amd_stream_set_index.restype = C.c_int
     lib.nblic_amd_stream_set_index.argtypes = [C.c_void_p, C.c_int]
+    lib.nblic_amd_stream_set_front.restype = C.c_int
+    lib.nblic_amd_stream_set_front.argtypes = [C.c_void_p, C.c_int]
     lib.nblic_amd_stream_index.restype = C.c_size_t
     lib.nblic_amd_stream_index.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     lib.nblic_amd_set_index_round.restype = None
@@ -532,11 +534,14 @@ class Context:
         self.lib.nblic_amd_set_max_pixels(self.handle, n)
 
     def stream(self, img: np.ndarray, near: int, effort: int, band_rows: int = 0, checkpoint: Optional[bytes] = None,
-               index_every: int = 0) -> "BandStream":
+               index_every: int = 0, front: str = "serial") -> "BandStream":
         """One image in row bands (``nblic_amd_stream_*``): bounded workspace, suspend / resume through checkpoints.
-        ``index_every`` > 0: the encoder also writes the stream's seek index (``BandStream.index()``).  The context
-        closes it before it is destroyed itself."""
-        s = BandStream(self, img, near, effort, band_rows, checkpoint, index_every)
+        ``index_every`` > 0: the encoder also writes the stream's seek index (``BandStream.index()``).
+        ``front``: what a band's model stage runs on (``nblic_amd_stream_set_front``) -- "serial", the one-wave model
+        kernel (every mode), or "staged", the batch pipeline's partitioned kernels (``near`` 0, ``effort`` 1 only; raises
+        ``RuntimeError`` for any other mode).  Stream, checkpoints and index are the same bytes under both, and a
+        checkpoint of one resumes under the other.  The context closes the object before it is destroyed itself."""
+        s = BandStream(self, img, near, effort, band_rows, checkpoint, index_every, front)
         self._objects.add(s)
         return s
 
@@ -706,13 +711,18 @@ class Context:
         return out[:cnt].copy()
 
 
+FRONTS = {"serial": 0, "staged": 1}       # nblic_amd_stream_set_front
+
+
 class BandStream:
     """An encode in progress (``nblic_amd_stream``).  ``run(budget_seconds)`` returns (finished, bytes of this call);
-    ``checkpoint()`` the state to hand to ``Context.stream(..., checkpoint=...)`` in another call or process."""
+    ``checkpoint()`` the state to hand to ``Context.stream(..., checkpoint=...)`` in another call or process;
+    ``front`` is the front its bands run on ("serial" or "staged")."""
 
     def __init__(self, ctx: Context, img: np.ndarray, near: int, effort: int, band_rows: int = 0, checkpoint: Optional[bytes] = None,
-                 index_every: int = 0):
+                 index_every: int = 0, front: str = "serial"):
         self.ctx, self.lib = ctx, ctx.lib
+        self.front = front
         self.img = np.ascontiguousarray(img, np.uint8)
         h, w = self.img.shape
         if checkpoint is None:
@@ -725,6 +735,9 @@ class BandStream:
         if index_every and self.lib.nblic_amd_stream_set_index(self.handle, int(index_every)) != 0:
             self.close()
             raise RuntimeError("nblic_amd_stream_set_index: every_rows outside [1, height), or a resumed encoder")
+        if front != "serial" and (front not in FRONTS or self.lib.nblic_amd_stream_set_front(self.handle, FRONTS[front]) != 0):
+            self.close()
+            raise RuntimeError(f"nblic_amd_stream_set_front: front {front!r} is not one of {sorted(FRONTS)}, or does not take this mode (staged: near 0, effort 1)")
         self.out = np.empty(h * w + h * w // 8 + 65536, np.uint8)
 
     def run(self, budget_seconds: float = 0.0) -> Tuple[bool, bytes]:

@@ -64,6 +64,8 @@ struct E1Job {
     int dbg;             // timing experiments only (NBLIC_AMD_DBG); 0 in normal operation
     int near, k_step;    // serial modes only (the staged -e1 kernels use the lossless constants 0 and 3)
     uint64_t ktab;       // model.h level_shift_table(k_step)
+    int row0;            // the image row at index 0 of b.img / b.rec1: 0 for a whole image; a row band of the band encoder
+                         // (e1_launch_front_band) has h = its rows, b.img = plane + row0 * w, and the plane goes on above b.img
 };
 
 // One HIP event before every kernel launch (and one after the last): interval k is exactly
@@ -89,6 +91,11 @@ static const char *const kE1StageNames[kE1Kernels] = {
 int e1_selftest(hipStream_t s);     // 0 = DPP wave scan agrees with the shuffle scan
 // d_jobs: device copy of h_jobs[0..n_jobs).  The host copy is only read to size the grids.
 void e1_launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s, E1Timers *tm);
+// The same sequence for ROW BANDS of -n0 -e1 images (E1Job::row0): no k_init_state -- ctx_state, map_state and cnt_state hold
+// what the rows above left, every chain kernel starts from them and writes its end state back -- and S1 takes a pixel's
+// fall-backs from its row in the image, reading the two rows above a band from the plane.  Untimed; `model_done`, if
+// given, is recorded behind k_bias_fixup (S1 .. S2 is what replaces the serial model stage).
+void e1_launch_front_band(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s, hipEvent_t model_done = nullptr);
 void e1_launch_back(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s, E1Timers *tm, bool general = false);
 // serial modes (near > 0, efforts 2/3): model state init, then -- after the caller has run the serial
 // model stage (serial_engine.h) that leaves rec1 and px | sign per pixel -- the re-mapper partition,

@@ -244,6 +244,9 @@ typedef uint32_t u32x4_dw __attribute__((ext_vector_type(4), aligned(4)));
 
 __device__ __forceinline__ int interior_runs(int w) { return w >= 20 ? (w - 12) / 8 : 0; }   // runs of 8 columns from column 8; taps reach j0-4 .. j0+11
 
+// BAND (a row band of the band encoder, e1_launch_front_band): b.img / b.rec1 start at image row J.row0, the plane goes
+// on above b.img, and what decides a pixel's fall-backs is its row in the IMAGE.  The batch pipeline launches <false>.
+template <bool BAND>
 __global__ void __launch_bounds__(256) k_predict_rows(const E1Job *__restrict__ jobs) {
     __shared__ uint16_t qlut[208];                                        // activity (clipped to 200) -> qu | qv << 4 | qw << 8
     if (threadIdx.x < 208) {
@@ -253,8 +256,11 @@ __global__ void __launch_bounds__(256) k_predict_rows(const E1Job *__restrict__ 
     __syncthreads();
     const E1Job &J = jobs[blockIdx.z];
     const int w = J.w;
-    const int run = int(blockIdx.x) * 256 + int(threadIdx.x), i = int(blockIdx.y) + 2;
+    // i: the row's index in b.img / b.rec1.  A band visits its rows 0 and 1 too: they are interior rows when two image
+    // rows lie above them, and the three loads below then reach above b.img, into the plane.
+    const int run = int(blockIdx.x) * 256 + int(threadIdx.x), i = BAND ? int(blockIdx.y) : int(blockIdx.y) + 2;
     if (i >= J.h || run >= interior_runs(w)) return;
+    if (BAND && J.row0 + i < 2) return;
     const int j0 = 8 + 8 * run;
     const auto at = gptr(J.b.img) + (size_t(i) * size_t(w) + size_t(j0 - 4));
     const u32x4 r0 = *(NB_GLOBAL const u32x4_any *)at;
@@ -285,11 +291,16 @@ __global__ void __launch_bounds__(256) k_predict_rows(const E1Job *__restrict__ 
     *(NB_GLOBAL u32x4_dw *)(out + 4) = u32x4{rec[4], rec[5], rec[6], rec[7]};
 }
 
-// top == 1: rows 0 and 1, every column (grid.y = 2);  top == 0: rows 2.., the columns k_predict_rows leaves out
+// top == 1: rows 0 and 1, every column (grid.y = 2);  top == 0: rows 2.., the columns k_predict_rows leaves out.
+// BAND: `top` takes the band's rows that are image rows 0 / 1 (none when row0 >= 2), the other launch (grid.y = the band's
+// rows) the rest; sample_taps sees the row in the image, and reads relative to the plane.
+template <bool BAND>
 __global__ void __launch_bounds__(64) k_predict_border(const E1Job *__restrict__ jobs, int top) {
     const E1Job &J = jobs[blockIdx.z];
     const int w = J.w;
-    const int i = top ? int(blockIdx.y) : int(blockIdx.y) + 2;
+    const int i = top || BAND ? int(blockIdx.y) : int(blockIdx.y) + 2;   // the row's index in b.img / b.rec1
+    const int row0 = BAND ? J.row0 : 0;
+    if (BAND && (row0 + i < 2) != (top != 0)) return;
     int j = int(blockIdx.x) * 64 + int(threadIdx.x);
     if (!top) {
         const int first_right = 8 + 8 * interior_runs(w);                 // == w when there is no interior at all
@@ -298,12 +309,15 @@ __global__ void __launch_bounds__(64) k_predict_border(const E1Job *__restrict__
     }
     if (i >= J.h || j >= w) return;
     const auto img = gptr(J.b.img);
-    auto pix = [&](int r, int c) { return int(img[size_t(r) * size_t(w) + size_t(c)]); };
-    Taps n = sample_taps(pix, w, i, j);
+    auto pix = [&](int r, int c) {                                        // r: row in the image
+        if (BAND) return int(img[(ptrdiff_t(r) - ptrdiff_t(row0)) * ptrdiff_t(w) + ptrdiff_t(c)]);
+        return int(img[size_t(r) * size_t(w) + size_t(c)]);
+    };
+    Taps n = sample_taps(pix, w, row0 + i, j);
     int px0 = predict(n);
     int err_prev = 0;
     if (j > 0) {
-        Taps m = sample_taps(pix, w, i, j - 1);
+        Taps m = sample_taps(pix, w, row0 + i, j - 1);
         err_prev = clip_err(n.a, predict(m));
     }
     Level L = quantise(activity(n, err_prev));
@@ -1448,7 +1462,11 @@ SegPlan make_plan(uint32_t n_items, uint32_t max_segments) {
 
 // Front half for a group of jobs: everything up to the per-pixel bin counts and their scan
 // (the event totals are needed on the host before the event buffers can be sized).  18 launches.
-void e1_launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s, E1Timers *tm) {
+// BAND: the jobs are row bands of images whose earlier rows have been coded (E1Job::row0): the model tables are the
+// caller's, so nothing is initialised -- every chain kernel starts from the table entry of its key and writes the end
+// state back -- and S1 is the band variant.  `model_done` (BAND only) is recorded behind k_bias_fixup.
+template <bool BAND>
+static void launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s, E1Timers *tm, hipEvent_t model_done) {
     int max_w = 0, max_h = 0, max_nseg = 0; uint32_t max_n = 0;
     for (int k = 0; k < n_jobs; k++) {
         max_w = h_jobs[k].w > max_w ? h_jobs[k].w : max_w; max_h = h_jobs[k].h > max_h ? h_jobs[k].h : max_h;
@@ -1456,11 +1474,22 @@ void e1_launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipSt
     }
     const dim3 seg_grid(pad8(cdiv(max_nseg, 4)), n_jobs), px_grid(pad8(cdiv(max_n, 256)), n_jobs);
     Marker mark{tm, s, 0};
-    mark(); hipLaunchKernelGGL(k_init_state, dim3(16, n_jobs), dim3(256), 0, s, d_jobs);
+    if (!BAND) { mark(); hipLaunchKernelGGL(k_init_state, dim3(16, n_jobs), dim3(256), 0, s, d_jobs); }   // (a band launch is not timed by stage: tm is null)
     mark();                                                     // one timed stage "k_predict": interior rows + the two border launches
-    if (max_h > 2 && max_w >= 20) hipLaunchKernelGGL(k_predict_rows, dim3(cdiv((max_w - 12) / 8, 256), max_h - 2, n_jobs), dim3(256), 0, s, d_jobs);
-    hipLaunchKernelGGL(k_predict_border, dim3(cdiv(max_w, 64), max_h < 2 ? max_h : 2, n_jobs), dim3(64), 0, s, d_jobs, 1);
-    if (max_h > 2) hipLaunchKernelGGL(k_predict_border, dim3(1, max_h - 2, n_jobs), dim3(64), 0, s, d_jobs, 0);
+    if (BAND) {                                                 // which of a band's rows are top rows is the kernels' business (row0)
+        int top_rows = 0;                                       // local rows below which some job has an image row 0 / 1: none for every band but an image's first one or two
+        for (int k = 0; k < n_jobs; k++) {
+            const int t = 2 - h_jobs[k].row0 < h_jobs[k].h ? 2 - h_jobs[k].row0 : h_jobs[k].h;
+            top_rows = t > top_rows ? t : top_rows;
+        }
+        if (max_h > 0 && max_w >= 20) hipLaunchKernelGGL(k_predict_rows<true>, dim3(cdiv((max_w - 12) / 8, 256), max_h, n_jobs), dim3(256), 0, s, d_jobs);
+        if (top_rows > 0) hipLaunchKernelGGL(k_predict_border<true>, dim3(cdiv(max_w, 64), top_rows, n_jobs), dim3(64), 0, s, d_jobs, 1);
+        hipLaunchKernelGGL(k_predict_border<true>, dim3(1, max_h, n_jobs), dim3(64), 0, s, d_jobs, 0);
+    } else {
+        if (max_h > 2 && max_w >= 20) hipLaunchKernelGGL(k_predict_rows<false>, dim3(cdiv((max_w - 12) / 8, 256), max_h - 2, n_jobs), dim3(256), 0, s, d_jobs);
+        hipLaunchKernelGGL(k_predict_border<false>, dim3(cdiv(max_w, 64), max_h < 2 ? max_h : 2, n_jobs), dim3(64), 0, s, d_jobs, 1);
+        if (max_h > 2) hipLaunchKernelGGL(k_predict_border<false>, dim3(1, max_h - 2, n_jobs), dim3(64), 0, s, d_jobs, 0);
+    }
     mark(); hipLaunchKernelGGL(k_adr_count<NbModel>, seg_grid, dim3(256), 0, s, d_jobs);
     scan_exclusive<0>(d_jobs, n_jobs, uint32_t(kContexts) * max_nseg, s, mark);
     mark(); hipLaunchKernelGGL(k_adr_scatter<NbModel>, seg_grid, dim3(256), 0, s, d_jobs);
@@ -1468,6 +1497,7 @@ void e1_launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipSt
     const unsigned max_blocks = max_n / kBiasBlock + unsigned(kContexts);
     mark(); hipLaunchKernelGGL(k_bias_blocks<NbModel>, dim3(cdiv(max_blocks, 64), n_jobs), dim3(64), 0, s, d_jobs);
     mark(); hipLaunchKernelGGL(k_bias_fixup<NbModel>, dim3(kContexts / 64, n_jobs), dim3(64), 0, s, d_jobs);
+    if (BAND && model_done) hipEventRecord(model_done, s);
     mark(); hipLaunchKernelGGL(k_map_count, seg_grid, dim3(256), 0, s, d_jobs);
     scan_exclusive<1>(d_jobs, n_jobs, 512u * max_nseg, s, mark);
     mark(); hipLaunchKernelGGL(k_map_scatter<false>, seg_grid, dim3(256), 0, s, d_jobs);
@@ -1475,6 +1505,14 @@ void e1_launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipSt
     mark(); hipLaunchKernelGGL(k_count_bins<false>, px_grid, dim3(256), 0, s, d_jobs);
     scan_exclusive<2>(d_jobs, n_jobs, max_n, s, mark);
     mark();                                                     // start of the host gap (index 20)
+}
+
+void e1_launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s, E1Timers *tm) {
+    launch_front<false>(d_jobs, h_jobs, n_jobs, s, tm, nullptr);
+}
+
+void e1_launch_front_band(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s, hipEvent_t model_done) {
+    launch_front<true>(d_jobs, h_jobs, n_jobs, s, nullptr, model_done);
 }
 
 // Front half of the serial modes: rec1 and px | sign per pixel come from the serial model stage

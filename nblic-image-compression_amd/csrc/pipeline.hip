@@ -36,6 +36,7 @@
 #include "device_coder.h"
 #include "hip_owned.h"
 #include "kernels_e1.h"
+#include "lsq_f64.h"
 #include "model.h"
 #include "range_coder.h"
 #include "serial_engine.h"
@@ -1548,6 +1549,8 @@ struct nblic_amd_stream {
     unsigned long long bytes_total = 0;
     nblic::Sha256 sha;
     bool finished = false, failed = false;
+    bool ran = false;                                                   // this object's first _run has been called
+    int front = 0;                                                      // nblic_amd_stream_set_front: 0 serial model stage, 1 staged kernels (-n0 -e1 only)
     long bands = 0;
     double model_ms = 0;
     // seek index (nblic_amd_stream_set_index): an entry in front of every row index_every, 2 index_every, ...  An entry
@@ -1602,7 +1605,37 @@ static E1Buffers stream_band_buffers(const nblic_amd_stream *s, const Slot &sl, 
 static void stream_band_jobs(nblic_amd_stream *s, Group &g, int i0, int rows) {
     const Slot &sl = g.slots[0];
     g.h_jobs[0] = e1_job_front(stream_band_buffers(s, sl, i0), rows, s->w, s->near, 0);
+    g.h_jobs[0].row0 = i0;
     g.h_sjobs[0] = model_job(s->d_img, s->d_recon, sl.b, s->d_stats, sl.d_state, s->h, s->w, s->near, s->effort, rows, i0, g.ctx->d_redo);
+}
+
+// ---- the STAGED front of a band (nblic_amd_stream_set_front, -n0 -e1) ------------------------------------------------
+// Lossless -e1 has no prediction chain (kernels_e1.hip S1), so a band's model stage can run on the key-partitioned
+// kernels instead of the one wave of k_serial_model.  The model state record stays what the encoder carries from band
+// to band -- checkpoints and index entries are read from it -- so a staged band takes the record's biases into
+// ctx_state, runs S1 .. S2 .. on its rows (e1_launch_front_band: every chain starts from its table entry and writes
+// its end state back), and leaves the record as k_serial_model<0, 1> leaves it after the same rows: next_row, status,
+// `bias` (never moved at effort 1: lsq::kBiasInit), and the biases -- which the model kernel does not write back after
+// the image's last row.
+__global__ void __launch_bounds__(256) k_band_record_out(SerialState *__restrict__ st, const int *__restrict__ ctx_state, int next_row, int done) {
+    const int k = int(blockIdx.x) * 256 + int(threadIdx.x);
+    if (!done && k < kContexts) reinterpret_cast<int *>(st + 1)[k] = ctx_state[k];
+    if (k == 0) { st->next_row = next_row; st->bias = lsq::kBiasInit; st->status = done ? kDone : kRunning; }
+}
+
+// The front half of the band [i0, i0 + rows) on the staged kernels; e_model is recorded behind the last launch of S2.
+static bool stream_front_staged(nblic_amd_stream *s, Group &g, int i0, int rows, hipEvent_t e_model) {
+    Slot &sl = g.slots[0];
+    const hipStream_t st = g.stream;
+    // row 0: k_init_state has zeroed ctx_state, and the record's table is not written yet (the model kernel starts from zeros too)
+    if (i0 > 0 && hipMemcpyAsync(sl.b.ctx_state, reinterpret_cast<const int *>(sl.d_state + 1), size_t(kContexts) * sizeof(int),
+                                 hipMemcpyDeviceToDevice, st) != hipSuccess) return false;
+    e1_launch_front_band(g.d_jobs, g.h_jobs, 1, st, e_model);
+    hipLaunchKernelGGL(k_band_record_out, dim3(kContexts / 256), dim3(256), 0, st, sl.d_state, sl.b.ctx_state, i0 + rows, int(i0 + rows >= s->h));
+    // rows too wide for the model kernel's LDS: the encoder keeps a reconstruction, which the checkpoint's two rows come from
+    const size_t at = size_t(i0) * size_t(s->w);
+    if (s->d_recon.get() && hipMemcpyAsync(s->d_recon.get() + at, s->d_img + at, size_t(rows) * size_t(s->w), hipMemcpyDeviceToDevice, st) != hipSuccess) return false;
+    return hipGetLastError() == hipSuccess;
 }
 
 static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8_t *out, const uint8_t *end, uint32_t lo, uint32_t hi);
@@ -1615,6 +1648,8 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
     if (s->finished) return 1;
     nblic_amd_ctx *c = s->c;
     if (hipSetDevice(c->device) != hipSuccess) return -1;
+    s->ran = true;
+    const bool staged = s->front == 1;
     Group &g = c->groups[size_t(s->gid)];
     Slot &sl = g.slots[0];
     const auto t0 = std::chrono::steady_clock::now();
@@ -1639,11 +1674,15 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
         stream_band_jobs(s, g, i0, rows);
         hipEvent_t e0 = g.tm.ev[0], e1 = g.tm.ev[1];
         if (hipMemcpyAsync(g.d_jobs, g.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, g.stream) != hipSuccess ||
-            hipMemcpyAsync(g.d_sjobs, g.h_sjobs, sizeof(SerialJob), hipMemcpyHostToDevice, g.stream) != hipSuccess) return fail("upload");
+            (!staged && hipMemcpyAsync(g.d_sjobs, g.h_sjobs, sizeof(SerialJob), hipMemcpyHostToDevice, g.stream) != hipSuccess)) return fail("upload");
         hipEventRecord(e0, g.stream);
-        if (!serial_model_launch(g.d_sjobs, g.h_sjobs, 1, g.stream)) return fail("model launch");
-        hipEventRecord(e1, g.stream);
-        e1_launch_front_pre(g.d_jobs, g.h_jobs, 1, g.stream);
+        if (staged) {
+            if (!stream_front_staged(s, g, i0, rows, e1)) return fail("staged front");
+        } else {
+            if (!serial_model_launch(g.d_sjobs, g.h_sjobs, 1, g.stream)) return fail("model launch");
+            hipEventRecord(e1, g.stream);
+            e1_launch_front_pre(g.d_jobs, g.h_jobs, 1, g.stream);
+        }
         if (hipMemcpyAsync(g.h_totals, g.d_totals, kTotalsStride * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
             hipStreamSynchronize(g.stream) != hipSuccess) return fail("front half");
         { float ms = 0.f; if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) s->model_ms += ms; }
@@ -1662,7 +1701,7 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
         rc.feed(s->h_coded, n_ev);
         if (rc.overflow) return fail("output buffer too small");
         s->next_row = i0 + rows; s->bands++;
-        { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count++; }
+        if (!staged) { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count++; }
         if (s->index_every > 0 && !stream_index_band(s, i0, rows, out, rc.p, rc.lo, rc.hi)) return fail("index entry");
         if (budget_s > 0 && s->next_row < s->h && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= budget_s) break;
     }
@@ -2278,6 +2317,14 @@ static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8
     return true;
 }
 
+// Which front the object's bands run on; before its first _run.  The staged one is -n0 -e1 alone.
+static int stream_set_front(nblic_amd_stream *s, int front) {
+    if (!s || s->ran || s->failed || front < 0 || front > 1) return -1;
+    if (front == 1 && (s->near != 0 || s->effort != 1)) return -1;
+    s->front = front;
+    return 0;
+}
+
 static int stream_set_index(nblic_amd_stream *s, int every) {
     if (!s || s->bytes_total != 0 || s->first_row != 0 || every < 1 || every >= s->h) return -1;
     s->index_every = every;
@@ -2831,6 +2878,7 @@ int nblic_amd_stream_recon(nblic_amd_stream *s, unsigned char *plane, int *first
 void nblic_amd_stream_end(nblic_amd_stream *s) { stream_free(s); }
 int nblic_amd_stream_set_index(nblic_amd_stream *s, int every_rows) { return stream_set_index(s, every_rows); }
 size_t nblic_amd_stream_index(nblic_amd_stream *s, void *buf, size_t cap) { return stream_index(s, buf, cap); }
+int nblic_amd_stream_set_front(nblic_amd_stream *s, int front) { return stream_set_front(s, front); }
 
 nblic_amd_dstream *nblic_amd_dstream_begin(nblic_amd_ctx *c, int band_rows) { return dstream_new(c, band_rows); }
 nblic_amd_dstream *nblic_amd_dstream_resume(nblic_amd_ctx *c, const void *checkpoint, size_t bytes) { return dstream_resume(c, checkpoint, bytes); }
