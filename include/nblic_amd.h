@@ -348,6 +348,17 @@ long nblic_amd_debug_stage(nblic_amd_ctx *ctx, const unsigned char *img, int hei
  * and band encoders, [3] streams + events.  Needs no context and makes no GPU call.                                  */
 void nblic_amd_debug_live(long counts[4]);
 
+/* Debug hook used by the hand-over tests: takes[k] = how many times a host coder thread took k images together since
+ * the last batch began (k = 0..24; 1 = an image on its own, the scalar coder; more = whole packs).               */
+void nblic_amd_debug_takes(nblic_amd_ctx *ctx, long takes[25]);
+
+/* Debug hook used by the hand-over tests: runs 2..8 host images as ONE pack of one group launch (the context's groups
+ * must have that many slots) and copies the pack's device rows back -- rows[(13 g + j) * 8 + lane], 13-bit groups of
+ * lane `lane`, PackRows in csrc/hip_owned.h -- then runs the same images unpacked and copies every image's u16 records
+ * to coded[k] (n_bins[k]: capacity in, count out).  Returns the 64-bit words written to rows, or -1.                 */
+long nblic_amd_debug_pack_rows(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *imgs, const int *heights, const int *widths,
+                               unsigned long long *rows, size_t rows_words, unsigned short *const *coded, unsigned int *n_bins);
+
 /* Device self-test of the wave primitives the chain kernels rely on (DPP prefix sum against the
  * shuffle formulation).  Returns the number of mismatching lanes (0 = pass) or -1.           */
 int nblic_amd_selftest(nblic_amd_ctx *ctx);
@@ -369,11 +380,22 @@ int nblic_amd_range_code_multi(const uint16_t *const *coded, const size_t *n, in
                                const size_t *caps, size_t *lens);
 
 /* The same streams fed `chunk` bins at a time through the RESUMABLE coders, exactly as the coder
- * threads do when they stream an image's bins from HBM (one stream: scalar coder; more: two
- * AVX-512 packs in lock-step, up to 16 streams).  Host function; exists so that the chunked path
- * can be checked without a GPU.  Returns 0, or -1 for count outside 1..16 or chunk == 0.        */
+ * threads do when they stream an image's bins from HBM (one stream: scalar coder; more: consecutive
+ * eights are AVX-512 packs, one to three in lock-step; any chunk length).  Host function; exists so that the
+ * chunked path can be checked without a GPU.  Returns 0, or -1 for count outside 1..24 or chunk == 0.           */
 int nblic_amd_range_code_chunked(const uint16_t *const *coded, const size_t *n, int count, unsigned char *const *outs,
                                  const size_t *caps, size_t *lens, size_t chunk);
+
+/* The layout's reference: ORs the 13-bit codes of one lane's n records into zeroed 8-lane rows,
+ * rows[(13 g + j) * 8 + lane] (csrc/range_coder.h).  Host function.                                               */
+void nblic_amd_pack_groups_host(uint64_t *rows, int lane, const uint16_t *coded, size_t n);
+
+/* The coder threads' pack feed, minus the GPU: n_packs (1..3) packs of pack_n[p] (1..8) streams each, coded in
+ * lock-step from 8-lane rows of 13-bit groups, `chunk` bins (a multiple of 64) at a time.  Every array is indexed
+ * 8 p + lane: stream `lane` of pack p.  lens[8 p + lane] = byte count or (size_t)-1.  Returns 0; 1 on a host without
+ * AVX-512 (every stream through the scalar coder, as the coder threads do there); -1 for arguments out of range.   */
+int nblic_amd_range_code_packs(int n_packs, const int *pack_n, const uint16_t *const *coded, const size_t *n, unsigned char *const *outs,
+                               const size_t *caps, size_t *lens, size_t chunk);
 
 /* ---- 3. front end: image files and the reference tool's command line (host only) ----------------- */
 

@@ -37,7 +37,7 @@ _lib = None
 EXPORTS = (
     "NBLICcompress", "NBLICdecompress", "QNBLICcompress", "QNBLICdecompress", "QNBLICcompressMultiThread",
     "nblic_amd_create", "nblic_amd_create_ex", "nblic_amd_destroy", "nblic_amd_encode_batch", "nblic_amd_encode_batch_begin", "nblic_amd_encode_batch_end", "nblic_amd_qencode_batch", "nblic_amd_set_max_pixels",
-    "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage", "nblic_amd_debug_live",
+    "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage", "nblic_amd_debug_live", "nblic_amd_debug_takes", "nblic_amd_debug_pack_rows",
     "nblic_amd_encode_batch_modes", "nblic_amd_decode_batch", "nblic_amd_serial_selftest",
     "nblic_amd_set_serial_rows", "nblic_amd_serial_launches", "nblic_amd_lsq_redo_counts", "nblic_amd_serial_plan", "nblic_amd_lsq_probe", "nblic_amd_set_feed_chunk", "nblic_amd_last_fed_bytes",
     "nblic_amd_stream_begin", "nblic_amd_stream_resume", "nblic_amd_stream_run", "nblic_amd_stream_checkpoint", "nblic_amd_stream_progress",
@@ -48,7 +48,7 @@ EXPORTS = (
     "nblic_amd_stream_set_index", "nblic_amd_stream_index", "nblic_amd_set_index_round", "nblic_amd_stream_set_front",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats",
-    "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
+    "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
 )
 
 
@@ -208,6 +208,17 @@ def load_library() -> C.CDLL:
     lib.nblic_amd_range_code_chunked.restype = C.c_int
     lib.nblic_amd_range_code_chunked.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p),
                                                  C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t]
+    if hasattr(lib, "nblic_amd_range_code_packs"):                 # (a library of an older build, loaded through NBLIC_AMD_LIB for an A/B run, has neither)
+        lib.nblic_amd_range_code_packs.restype = C.c_int
+        lib.nblic_amd_range_code_packs.argtypes = [C.c_int, ip, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                                   C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t]
+        lib.nblic_amd_pack_groups_host.restype = None
+        lib.nblic_amd_pack_groups_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        lib.nblic_amd_debug_takes.restype = None
+        lib.nblic_amd_debug_takes.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+        lib.nblic_amd_debug_pack_rows.restype = C.c_long
+        lib.nblic_amd_debug_pack_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), ip, ip, C.c_void_p, C.c_size_t,
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_uint)]
     lib.nblic_amd_selftest.restype = C.c_int
     lib.nblic_amd_selftest.argtypes = [C.c_void_p]
     lib.nblic_amd_syn1.restype = None
@@ -430,6 +441,39 @@ def range_code_chunked(streams: Sequence[np.ndarray], chunk: int, caps: Optional
         raise ValueError("nblic_amd_range_code_chunked: 1..16 streams, chunk > 0")
     bad = C.c_size_t(-1).value
     return [None if ln[i] == bad else outs[i][: ln[i]].tobytes() for i in range(k)]
+
+
+def range_code_packs(packs: Sequence[Sequence[np.ndarray]], chunk: int, caps: Optional[Sequence[Sequence[int]]] = None):
+    """One to three packs of one to eight bin streams each through the coder threads' pack feed, ``chunk`` bins at a time
+    (``nblic_amd_range_code_packs``).  Returns (a list per pack of lists of bytes or None (did not fit), used_simd):
+    used_simd is False on a host without AVX-512, where every stream went through the scalar coder instead."""
+    lib = load_library()
+    np_ = len(packs)
+    arrs = [[np.ascontiguousarray(a, np.uint16) for a in p] for p in packs]
+    caps = [[a.size * 4 + 16 for a in p] for p in arrs] if caps is None else [list(c) for c in caps]
+    outs = [[np.empty(max(c, 1), np.uint8) for c in cp] for cp in caps]
+    cp, nn, op, cc = (C.c_void_p * (8 * np_))(), (C.c_size_t * (8 * np_))(), (C.c_void_p * (8 * np_))(), (C.c_size_t * (8 * np_))()
+    for p in range(np_):
+        for l, a in enumerate(arrs[p]):
+            cp[8 * p + l], nn[8 * p + l], op[8 * p + l], cc[8 * p + l] = a.ctypes.data, a.size, outs[p][l].ctypes.data, caps[p][l]
+    ln = (C.c_size_t * (8 * np_))()
+    rc = lib.nblic_amd_range_code_packs(np_, (C.c_int * np_)(*[len(p) for p in arrs]), cp, nn, op, cc, ln, C.c_size_t(chunk))
+    if rc < 0:
+        raise ValueError("nblic_amd_range_code_packs: 1..3 packs of 1..8 streams, chunk a multiple of 64")
+    bad = C.c_size_t(-1).value
+    return [[None if ln[8 * p + l] == bad else outs[p][l][: ln[8 * p + l]].tobytes() for l in range(len(arrs[p]))] for p in range(np_)], rc == 0
+
+
+def pack_groups_host(lanes: Sequence[np.ndarray]) -> np.ndarray:
+    """The 8-lane rows of 13-bit groups of up to eight u16 record streams, rows[(13 g + j) * 8 + lane], laid out by the
+    library's host reference (``nblic_amd_pack_groups_host``: pack_groups_host in csrc/range_coder_x8.cpp)."""
+    lib = load_library()
+    groups = max((len(a) + 63) // 64 for a in lanes)
+    rows = np.zeros(groups * 13 * 8, np.uint64)
+    for lane, rec in enumerate(lanes):
+        rec = np.ascontiguousarray(rec, np.uint16)
+        lib.nblic_amd_pack_groups_host(C.c_void_p(rows.ctypes.data), lane, C.c_void_p(rec.ctypes.data), C.c_size_t(rec.size))
+    return rows
 
 
 # ---------------------------------------------------------------------------------------------
@@ -709,6 +753,29 @@ class Context:
         if cnt < 0:
             raise RuntimeError("nblic_amd_debug_stage failed")
         return out[:cnt].copy()
+
+    def takes(self) -> dict:
+        """{k: how many times a host coder thread took k images together} since the last batch began (``nblic_amd_debug_takes``)."""
+        v = (C.c_long * 25)()
+        self.lib.nblic_amd_debug_takes(self.handle, v)
+        return {k: int(v[k]) for k in range(25) if v[k]}
+
+    def debug_pack_rows(self, imgs: Sequence[np.ndarray]):
+        """2..8 images as one pack of one group launch (``nblic_amd_debug_pack_rows``): (the pack's device rows as
+        uint64, [every image's u16 records])."""
+        arrs = [np.ascontiguousarray(a, np.uint8) for a in imgs]
+        k = len(arrs)
+        cap = [40 * a.size + 64 for a in arrs]                    # bins per image at the most (as debug_stage)
+        rows = np.zeros((max(cap) // 64 + 2) * 13 * 8, np.uint64)
+        coded = [np.empty(c, np.uint16) for c in cap]
+        nb = (C.c_uint * k)(*cap)
+        words = self.lib.nblic_amd_debug_pack_rows(
+            self.handle, k, (C.c_void_p * k)(*[C.c_void_p(a.ctypes.data) for a in arrs]), (C.c_int * k)(*[a.shape[0] for a in arrs]),
+            (C.c_int * k)(*[a.shape[1] for a in arrs]), C.c_void_p(rows.ctypes.data), rows.size,
+            (C.c_void_p * k)(*[C.c_void_p(c.ctypes.data) for c in coded]), nb)
+        if words < 0:
+            raise RuntimeError("nblic_amd_debug_pack_rows failed")
+        return rows[:words].copy(), [coded[i][: nb[i]].copy() for i in range(k)]
 
 
 FRONTS = {"serial": 0, "staged": 1}       # nblic_amd_stream_set_front

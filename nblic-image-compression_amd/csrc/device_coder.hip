@@ -16,6 +16,10 @@
 // walk is bank-conflict free), and every lane walks its own row; the next round's 64 requests are in
 // flight while the current one is walked.  Emitted bytes go straight to the lane's output (consecutive
 // bytes of a lane share a line; the L2 merges them).
+// An image that is a lane of a PACK has no u16 records: its 256 bins of a round are the 52 words of four 13-bit groups,
+// every eighth word of the pack's rows (range_coder.h).  Threads 0..51 fetch them (one 64-byte line each: eight times
+// the requests of a u16 window, and the coder's speed is not what this path is for), they are parked in the same LDS
+// row, and the walk takes its four records per step from the words' 13-bit fields instead of 16-bit ones.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -48,12 +52,20 @@ __global__ void __launch_bounds__(64) k_range_code_lanes(const RcJob *__restrict
     const uint32_t my_rounds = (n + 255u) >> 8;
 
     // the pointers of the 64 streams, fetched per stream with readlane (wave-uniform addresses, coalesced 8-byte loads)
-    const uint32_t p_lo = uint32_t(uintptr_t(J.coded)), p_hi = uint32_t(uintptr_t(J.coded) >> 32);
+    const bool packed = J.coded == nullptr;
+    const uintptr_t src = packed ? uintptr_t(J.rows) : uintptr_t(J.coded);
+    const uint32_t p_lo = uint32_t(src), p_hi = uint32_t(src >> 32);
+    const int pack_lane = packed ? int(J.lane) : -1;
+    const uint32_t word_rows = ((n + 63u) >> 6) * 13u;             // of a pack lane: rows of the groups that hold its bins
     auto window = [&](int l, uint32_t round) {
         const uint64_t base = (uint64_t(uint32_t(__builtin_amdgcn_readlane(int(p_hi), l))) << 32) | uint32_t(__builtin_amdgcn_readlane(int(p_lo), l));
         const uint32_t r_l = uint32_t(__builtin_amdgcn_readlane(int(my_rounds), l));
         const uint32_t rr = r_l == 0u ? 0u : (round < r_l ? round : r_l - 1u);                 // finished streams re-read their last window
-        return ((NB_GLOBAL const u32x2 *)base)[size_t(rr) * 64u + uint32_t(lane)];
+        const int pl = __builtin_amdgcn_readlane(pack_lane, l);
+        if (pl < 0) return ((NB_GLOBAL const u32x2 *)base)[size_t(rr) * 64u + uint32_t(lane)];
+        const uint32_t row = rr * 52u + uint32_t(lane), rows_l = uint32_t(__builtin_amdgcn_readlane(int(word_rows), l));
+        if (lane >= 52 || row >= rows_l) return u32x2{0u, 0u};
+        return ((NB_GLOBAL const u32x2 *)base)[size_t(row) * 8u + uint32_t(pl)];
     };
     (void)in;
     u32x2 regs[64];
@@ -74,8 +86,23 @@ __global__ void __launch_bounds__(64) k_range_code_lanes(const RcJob *__restrict
         for (uint32_t wi = 0; wi < 64u; wi++) {
             if (__ballot(wi * 4u < mine) == 0ull) break;
             if (wi * 4u < mine) {
-                const u32x2 wv = stage[lane * kRowWords + int(wi)];
-                const uint32_t rec[4] = {wv.x & 0xFFFFu, wv.x >> 16, wv.y & 0xFFFFu, wv.y >> 16};
+                uint32_t rec[4];                                   // prob | bin << 15
+                if (!packed) {
+                    const u32x2 wv = stage[lane * kRowWords + int(wi)];
+                    rec[0] = wv.x & 0xFFFFu; rec[1] = wv.x >> 16; rec[2] = wv.y & 0xFFFFu; rec[3] = wv.y >> 16;
+                } else {                                           // bins 4 wi .. 4 wi + 3 of the round: codes 4 q .. 4 q + 3 of group wi / 16
+                    const int g0 = lane * kRowWords + 13 * int(wi >> 4), q = int(wi & 15u);
+                    if (q < 13) {
+                        const u32x2 wv = stage[g0 + q];
+                        const uint64_t w = uint64_t(wv.x) | (uint64_t(wv.y) << 32);
+#pragma unroll
+                        for (int k = 0; k < 4; k++) { const uint32_t c = uint32_t(w >> (13 * k)) & 0x1FFFu; rec[k] = (c & 0xFFFu) | ((c >> 12) << 15); }
+                    } else {                                       // codes 52 .. 63: probabilities on top of words 0 .. 11, their bins on top of word 12
+                        const uint32_t bins = stage[g0 + 12].y >> 20;
+#pragma unroll
+                        for (int k = 0; k < 4; k++) { const int e = 4 * (q - 13) + k; rec[k] = (stage[g0 + e].y >> 20) | (((bins >> e) & 1u) << 15); }
+                    }
+                }
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     if (wi * 4u + uint32_t(k) < mine) {

@@ -62,6 +62,22 @@ public:
 template <class T> using DevBuf = Buf<T, DeviceMem>;
 template <class T> using Pinned = Buf<T, PinnedMem>;
 
+// The rows of one PACK in device memory: the 13-bit groups of up to eight images of a group launch, eight lanes side by
+// side, rows[(13 g + j) * 8 + lane] (kernels_e1.h E1Job::pack_rows) -- what k_pack_rows writes and a coder thread copies
+// chunk by chunk.  Counted as device memory.  Grow-only; sized in bins of the pack's longest lane.
+class PackRows {
+    DevBuf<uint64_t> rows_;
+public:
+    static constexpr size_t kLanes = 8, kWordsPerGroup = 13, kBinsPerGroup = 64;
+    static constexpr size_t words(size_t bins) { return (bins + kBinsPerGroup - 1) / kBinsPerGroup * kWordsPerGroup * kLanes; }
+    hipError_t reserve_bins(size_t bins) {                           // an eighth of slack: the next pack is rarely much longer
+        const size_t need = words(bins ? bins : 1);                  // never null: the kernels read a null pack_rows as "not packed"
+        return need <= rows_.capacity() ? hipSuccess : rows_.alloc(need + need / 8 + kWordsPerGroup * kLanes);
+    }
+    uint64_t *get() const { return rows_.get(); }
+    size_t capacity_words() const { return rows_.capacity(); }
+};
+
 // Device buffers that die together.  The pool owns; the raw pointers it hands out are views (E1Buffers, the band
 // decoder's workspace).
 class DevPool {

@@ -66,6 +66,14 @@ struct E1Job {
     uint64_t ktab;       // model.h level_shift_table(k_step)
     int row0;            // the image row at index 0 of b.img / b.rec1: 0 for a whole image; a row band of the band encoder
                          // (e1_launch_front_band) has h = its rows, b.img = plane + row0 * w, and the plane goes on above b.img
+    // Where the coded bins go.  pack_rows == nullptr: b.coded, one u16 (prob | bin << 15) per bin, for an image that is
+    // coded on its own.  Otherwise the image is lane pack_lane (0..7) of a PACK: up to eight consecutive jobs of the launch
+    // that share pack_rows and that one AVX-512 register of a host coder thread codes together.  k_mix leaves such an
+    // image's bins as 13-bit groups (range_coder.h: thirteen 64-bit words per 64 bins) back to back in b.tin, whose touch
+    // payloads are dead by then, and k_pack_rows lays the pack's streams side by side:
+    // pack_rows[(13 * g + j) * 8 + pack_lane] = word j of bins 64 g .. 64 g + 63 (zero where a lane has no bin).
+    uint64_t *pack_rows;
+    int pack_lane;
 };
 
 // One HIP event before every kernel launch (and one after the last): interval k is exactly
@@ -86,7 +94,7 @@ static const char *const kE1StageNames[kE1Kernels] = {
     "k_emit_bins",
     "k_touch_count", "scan_reduce.touch", "scan_sums.touch", "scan_apply.touch", "k_touch_scatter",
     "k_plan_windows", "k_counter_epochs", "k_counter_probs",
-    "k_mix"};
+    "k_mix+k_pack_rows"};      // one interval: k_mix, and k_pack_rows behind it when the launch has packs
 
 int e1_selftest(hipStream_t s);     // 0 = DPP wave scan agrees with the shuffle scan
 // d_jobs: device copy of h_jobs[0..n_jobs).  The host copy is only read to size the grids.

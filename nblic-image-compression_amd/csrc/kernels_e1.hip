@@ -687,6 +687,7 @@ __device__ __forceinline__ void perm_set(Perm20 &p, int i, int v) {
     if (up) p.hi = w; else p.lo = w;
 }
 
+constexpr int kPackWords = 13, kPackLanes = 8;     // 64-bit words per lane per group of 64 bins (range_coder.h kGroupWords); lanes of a pack
 constexpr int kMapLanes = 16;
 __global__ void __launch_bounds__(64) k_mapper_chains(const E1Job *__restrict__ jobs) {
     __shared__ int count[kMapSyms][64];
@@ -1253,16 +1254,15 @@ __global__ void __launch_bounds__(256) k_counter_probs(const E1Job *__restrict__
 // without a second touch (both trees equal, or weight 0) mixes its one P with itself.  The two position words also
 // carry qw, the bin and qu's parity in their top four bits (pack_pos), so the event itself is not read again
 // (4 of 12 bytes per event) -- unless the image has too many touches for 28-bit positions (flag set by the scan).
-__global__ void __launch_bounds__(256) k_mix(const E1Job *__restrict__ jobs) {
-    const E1Job &J = jobs[blockIdx.y];
-    const auto tout = gptr(J.b.tout); const auto coded = gptr(J.b.coded);
+// P(bin == 1) | bin << 12 of bin r of job J (0 beyond the image's last bin)
+__device__ __forceinline__ uint32_t mixed_code(const E1Job &J, uint32_t r, bool wide) {
+    if (r >= J.n_ev) return 0u;
+    const auto tout = gptr(J.b.tout);
     const auto pos0 = (NB_GLOBAL const uint32_t *)gptr(J.b.tpos);
     const auto pos1 = pos0 + ((size_t(J.n_ev) + 63) & ~size_t(63));
-    const uint32_t r = xcd_block() * 256u + threadIdx.x;
-    if (r >= J.n_ev) return;
     uint32_t p0 = pos0[r], p1 = pos1[r];
     int qw, bin; bool odd;
-    if (gptr(J.b.totals)[kWideTouchFlag] != 0u) {
+    if (wide) {
         const uint32_t e = gptr(J.b.events)[r];
         qw = ev_qw(e); bin = ev_bin(e); odd = (ev_qu(e) & 1) != 0;
     } else {
@@ -1273,7 +1273,57 @@ __global__ void __launch_bounds__(256) k_mix(const E1Job *__restrict__ jobs) {
     }
     const uint32_t at_u = odd ? p1 : p0, other = odd ? p0 : p1, at_v = other == kNoTouch ? at_u : other;
     const int pu = tout[at_u], pv = tout[at_v];
-    coded[r] = pack_coded(mix_prob(pu, pv, qw), bin);
+    return uint32_t(mix_prob(pu, pv, qw)) | (uint32_t(bin) << 12);
+}
+
+// An image that is coded on its own: one u16 (prob | bin << 15) per bin into b.coded.
+// A lane of a PACK (E1Job::pack_rows set): the wave holds the 64 bins of one group, a bin per lane; lanes 0..12 assemble
+// the group's thirteen 64-bit words (range_coder.h: codes 4j .. 4j+3 in the low 52 bits; on top the probability of code
+// 52 + j or, word 12, the twelve bins of codes 52 .. 63, a slice of the wave's ballot) and store them back to back
+// -- 104 contiguous bytes -- into the image's OWN stream of groups in b.tin.  k_pack_rows then lays the streams of a
+// pack side by side.  Every group that holds a bin is written whole (zero codes past the last bin).
+__global__ void __launch_bounds__(256) k_mix(const E1Job *__restrict__ jobs) {
+    const E1Job &J = jobs[blockIdx.y];
+    const uint32_t r = xcd_block() * 256u + threadIdx.x;
+    if ((r & ~63u) >= J.n_ev) return;                                  // the whole wave is beyond the image's bins
+    const uint32_t code = mixed_code(J, r, gptr(J.b.totals)[kWideTouchFlag] != 0u);
+    if (!J.pack_rows) {
+        if (r < J.n_ev) gptr(J.b.coded)[r] = pack_coded(int(code & 0xFFFu), int(code >> 12));
+        return;
+    }
+    const int lane = int(threadIdx.x) & 63;
+    const int j = lane < kPackWords ? lane : kPackWords - 1;
+    const uint32_t c0 = uint32_t(__builtin_amdgcn_ds_bpermute((4 * j + 0) << 2, int(code)));
+    const uint32_t c1 = uint32_t(__builtin_amdgcn_ds_bpermute((4 * j + 1) << 2, int(code)));
+    const uint32_t c2 = uint32_t(__builtin_amdgcn_ds_bpermute((4 * j + 2) << 2, int(code)));
+    const uint32_t c3 = uint32_t(__builtin_amdgcn_ds_bpermute((4 * j + 3) << 2, int(code)));
+    const uint32_t top_prob = uint32_t(__builtin_amdgcn_ds_bpermute((52 + (j < 12 ? j : 0)) << 2, int(code))) & 0xFFFu;
+    const uint64_t ones = __ballot((code >> 12) != 0u);
+    const uint64_t top = j < 12 ? uint64_t(top_prob) : ((ones >> 52) & 0xFFFull);
+    const uint64_t word = uint64_t(c0) | (uint64_t(c1) << 13) | (uint64_t(c2) << 26) | (uint64_t(c3) << 39) | (top << 52);
+    if (lane < kPackWords) ((NB_GLOBAL uint64_t *)gptr(J.b.tin))[size_t(r >> 6) * kPackWords + size_t(lane)] = word;
+}
+
+// The transposition, once per group launch on the group's own stream: blockIdx.y is a pack (jobs 8 y .. 8 y + 7 of the
+// launch, as many of them as share the first one's pack_rows); thread t writes output word t = (13 g + j) * 8 + lane,
+// read from word 13 g + j of that lane's stream (zero where the lane has no such group).  A wave reads eight runs of
+// contiguous words and writes 512 contiguous bytes: pure streaming, 1.625 bytes per bin in and out.
+// (k_mix must walk ONE image at a time, and must not store between the other images' words itself: DESIGN.md 9-1.)
+__global__ void __launch_bounds__(256) k_pack_rows(const E1Job *__restrict__ jobs, int n_jobs) {
+    const int first = int(blockIdx.y) * kPackLanes;
+    const E1Job &J0 = jobs[first];
+    if (!J0.pack_rows) return;
+    uint32_t most = 0;
+    int cnt = 0;
+    for (int k = 0; k < kPackLanes && first + k < n_jobs && jobs[first + k].pack_rows == J0.pack_rows; k++) { cnt = k + 1; most = max(most, jobs[first + k].n_ev); }
+    const uint32_t groups = (most + 63u) / 64u;
+    const size_t t = size_t(xcd_block()) * 256u + threadIdx.x;
+    if (t >= size_t(groups) * (kPackWords * kPackLanes)) return;
+    const uint32_t g = uint32_t(t / (kPackWords * kPackLanes)), w = uint32_t(t % (kPackWords * kPackLanes));
+    const int k = int(w % kPackLanes), j = int(w / kPackLanes);
+    uint64_t v = 0;
+    if (k < cnt && g * 64u < jobs[first + k].n_ev) v = ((NB_GLOBAL const uint64_t *)gptr(jobs[first + k].b.tin))[size_t(g) * kPackWords + size_t(j)];
+    gptr(J0.pack_rows)[t] = v;
 }
 
 // ---- model state init (NBLIC.c:797-804) ---------------------------------------------------
@@ -1559,6 +1609,9 @@ void e1_launch_back(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStr
     const unsigned max_windows = unsigned(2ull * max_ev / kWin) + 4096u;          // every touch list has <= 2 touches per bin
     mark(); hipLaunchKernelGGL(k_counter_probs, dim3(cdiv(max_windows, 4), n_jobs), dim3(256), 0, s, d_jobs);
     mark(); hipLaunchKernelGGL(k_mix, dim3(pad8(cdiv(max_ev, 256) ? cdiv(max_ev, 256) : 1), n_jobs), dim3(256), 0, s, d_jobs);
+    uint32_t pack_ev = 0;                                       // the longest image that sits in a pack
+    for (int k = 0; k < n_jobs; k++) if (h_jobs[k].pack_rows && h_jobs[k].n_ev > pack_ev) pack_ev = h_jobs[k].n_ev;
+    if (pack_ev) hipLaunchKernelGGL(k_pack_rows, dim3(pad8(cdiv(cdiv(pack_ev, 64) * unsigned(kPackWords * kPackLanes), 256)), cdiv(unsigned(n_jobs), unsigned(kPackLanes))), dim3(256), 0, s, d_jobs, n_jobs);
     mark();                                                     // index 31: end
 }
 

@@ -2,9 +2,9 @@
 // stage (S6) on host threads, and the C ABI declared in include/nblic_amd.h.
 //
 // Images in flight are split into GROUPS that share every kernel launch (a driver thread and a HIP
-// stream per group).  A finished image's coded bins (u16 per bin) stay in an HBM buffer of a pool
-// until a coder thread streams them to the host chunk by chunk (packed to 13 bits per bin and laid
-// out for its AVX-512 lanes by k_pack_groups, up to 24 images at a time) through its own pinned ring
+// stream per group).  A finished image's coded bins stay in an HBM buffer of a pool -- a pack's rows (13 bits per bin,
+// laid out for the AVX-512 lanes inside the group launch: up to eight images of a launch are a pack), or u16 per
+// bin for an image on its own -- until a coder thread streams them to the host chunk by chunk through its own pinned ring
 // and turns them into the byte-exact range-coder stream (NBLIC.c:552-586), while the GPU is already
 // working on the next groups.  The rank's CPU share is what bounds the pipeline, so nothing here spins:
 // drivers sleep on a condition variable, coder threads poll for a chunk with 100 us sleeps.  Three kinds of group: staged -n0 -e1 encode, QNBLIC (effort 0) encode,
@@ -62,7 +62,6 @@ enum DbgFlag : int {
     kDbgReport = 32,          // coder / driver accounting on stderr when a batch ends
     kDbgTrace = 64,           // timeline of groups and coder takes on stderr
     kDbgFeedOnly = 128,       // bins reach the host but are not coded
-    kDbgNoPackKernel = 512,   // (with kDbgFeedOnly) no pack kernel
     kDbgNoCopy = 1024,        // (with kDbgFeedOnly) no copy
 };
 static int dbg_flags() {
@@ -127,14 +126,15 @@ bool size_ok(int h, int w, long max_px) {                                       
 // thread streams them to the host chunk by chunk (its own small pinned ring), so the pinned host
 // memory is per THREAD, not per image, and the GPU never waits for host buffers.
 using CodedBuf = DevBuf<uint16_t>;                                 // device; one image's coded bins (QNBLIC: pairs + histograms)
-// Bins per lane per chunk of the host ring.  Every chunk costs the GPU two dispatches per thread (the
-// interleave kernel and the copy, which the runtime performs with a blit kernel) that have to find
-// room between the encoder's own kernels: with 1 Mbin chunks the coder threads waited for their
+// Bins per lane per chunk of the host ring.  Every chunk costs the GPU a copy per pack (which the runtime
+// performs with a blit kernel) that has to find room between the encoder's own kernels: with 1 Mbin
+// chunks the coder threads waited for their
 // next chunk 15-20 % of the time (4.7 Gpx/s), with 4 Mbin chunks 3 % (5.2 Gpx/s).
 constexpr size_t kChunkBins = size_t(1) << 22;
 constexpr int kCopyStreams = 8;
 constexpr int kRingDepth = 3;                                      // ring slots per coder thread: the chunk being coded + the next two on their way (two slots: 6.14-6.30 Gpx/s, three: 6.35-6.38)
 constexpr int kMaxTake = 24;                                       // images one coder thread codes together (three AVX-512 packs; NBLIC_AMD_MAX_TAKE=16: two)
+constexpr int kMaxPacks = kMaxTake / int(kPackLanes);
 
 }  // namespace nblic
 // One submitted batch (nblic_amd_encode_batch_begin .. _end); `remaining` is guarded by ctx->fm.
@@ -148,6 +148,7 @@ struct ReadyImage {                                                  // everythi
     int kind;                                                        // 0 / 2 = NBLIC range coder, 1 = QNBLIC entropy stage
     ::nblic_amd_batch *batch;                                        // whose completion this image counts towards
     int near, k_step, effort;                                        // header fields (NBLIC.c:682-694)
+    int pack_n, pack_lane;                                           // pack_n >= 2: lane pack_lane of a pack of pack_n images whose rows are in pbufs[cb]; 1: on its own, u16 records in cbufs[cb]
 };
 
 // ---- one image in flight -------------------------------------------------------------------
@@ -160,6 +161,7 @@ struct Slot {
     int job = -1, h = 0, w = 0;       // current image
     int near = 0, effort = 1;         // its mode (kind 2 groups; 0 / 1 otherwise)
     uint32_t n_ev = 0;
+    int pack_n = 1, pack_lane = 0;    // its place in a pack of the current launch (launch_back); cb is then the PACK's buffer, shared by its lanes
     // serial modes: reconstruction (near > 0) and least-squares statistics (efforts 2/3)
     DevBuf<uint8_t> d_recon; DevBuf<double> d_stats;
     SerialState *d_state = nullptr;   // what the model stage carries from launch to launch (serial_engine.h); in `mem`
@@ -215,8 +217,10 @@ struct nblic_amd_ctx {
     int max_take = kMaxTake;                 // images a coder thread takes together: 24 = three AVX-512 packs (NBLIC_AMD_MAX_TAKE=16: two, for A/B runs)
     std::vector<Stream> copy_streams;        // shared by the coder threads (device -> host chunk copies)
     size_t chunk_bins = kChunkBins;          // bins per lane per chunk (NBLIC_AMD_CHUNK_BINS shrinks it, for tests of the chunk boundaries)
-    std::vector<CodedBuf> cbufs;
-    std::deque<int> free_cbufs;
+    std::vector<CodedBuf> cbufs;             // one image's u16 records (images coded on their own; QNBLIC: pairs + histograms)
+    std::deque<int> free_cbufs;              // both pools hand out the buffer returned last: memory is allocated for the backlog there is, not for the pool's size
+    std::vector<PackRows> pbufs;             // one pack's rows (k_pack_rows writes them)
+    std::deque<int> free_pbufs;
     int coding = 0;                       // images handed to the GPU whose streams are not finished yet
     // coder threads
     std::vector<std::thread> coders;
@@ -298,9 +302,13 @@ static bool nothing_outstanding(nblic_amd_ctx *c) {
 // The coded-bin buffer a slot took for an image that will not reach a coder goes back to the pool.
 static void return_coded(nblic_amd_ctx *c, Slot &s) {
     if (s.cb < 0) return;
-    std::lock_guard<std::mutex> l(c->fm);
-    c->free_cbufs.push_back(s.cb);
-    s.cb = -1;
+    {
+        std::lock_guard<std::mutex> l(c->fm);
+        if (s.pack_n <= 1) c->free_cbufs.push_front(s.cb);
+        else if (s.pack_lane == 0) c->free_pbufs.push_front(s.cb);       // a pack's buffer goes back once, with its first lane
+    }
+    s.cb = -1; s.pack_n = 1; s.pack_lane = 0;
+    c->fcv.notify_all();
 }
 
 // n images are finished (lens written): their coded-bin buffers go back, and they are counted off their batches and
@@ -308,7 +316,11 @@ static void return_coded(nblic_amd_ctx *c, Slot &s) {
 static void finish_images(nblic_amd_ctx *c, const ReadyImage *im, int n) {
     {
         std::lock_guard<std::mutex> l(c->fm);
-        for (int k = 0; k < n; k++) { c->free_cbufs.push_back(im[k].cb); im[k].batch->remaining -= 1; }
+        for (int k = 0; k < n; k++) {
+            if (im[k].pack_n <= 1) c->free_cbufs.push_front(im[k].cb);
+            else if (im[k].pack_lane == 0) c->free_pbufs.push_front(im[k].cb);   // whole packs are taken and finished together
+            im[k].batch->remaining -= 1;
+        }
         c->coding -= n;
     }
     c->fcv.notify_all();
@@ -376,8 +388,9 @@ static bool ensure_pixels(Slot &s, size_t n, bool with_events = true) {
 // ---- job records: the only code that fills an E1Job, or a SerialJob for the encoders' model stage -------------------
 // The back half's view of a job: the buffers as they are now (the event-sized ones may have grown, `coded` is known)
 // and the bin count with its partition plan.
-static void e1_job_back(E1Job &J, const E1Buffers &b, uint32_t n_ev) {
+static void e1_job_back(E1Job &J, const E1Buffers &b, uint32_t n_ev, uint64_t *pack_rows = nullptr, int pack_lane = 0) {
     J.b = b; J.n_ev = n_ev; J.pe = make_plan(n_ev, kTouchSegments);
+    J.pack_rows = pack_rows; J.pack_lane = pack_lane;
 }
 
 // The job of `rows` x w pixels in workspace b as a front half sees it: no bins yet (their count is its result).
@@ -415,7 +428,7 @@ static bool slot_begin(Group &g, int k, const uint8_t *const *imgs, bool on_devi
         HIP_OK(hipMemcpyAsync(s.d_img, imgs[s.job], n, hipMemcpyHostToDevice, g.stream));
         s.b.img = s.d_img;
     }
-    s.n_ev = 0;
+    s.n_ev = 0; s.pack_n = 1; s.pack_lane = 0;                     // (a pack is made in launch_back, for that launch only)
     g.h_jobs[k] = e1_job_front(s.b, s.h, s.w, s.near, dbg);
     return true;
 }
@@ -480,60 +493,27 @@ static bool launch_front_serial(nblic_amd_ctx *c, Group &g, const uint8_t *const
 }
 
 // ---- bins leave HBM in the layout the host coder wants ---------------------------------------
-// A chunk of up to sixteen images becomes ONE contiguous device->host copy of 13-bit groups (range_coder.h,
-// layout in range_coder_x8.cpp): rows[(13 * g + j) * 16 + lane] = word j of the thirteen 64-bit words that hold
-// bins 64g .. 64g+63 of lane `lane` (zero past the lane's end).  On the host a pack's word is one aligned
-// 64-byte load, and the link -- which bounds the pipeline -- carries 13 bits per bin instead of 16.
-// One thread produces one WORD: it reads the four records the word's low 52 bits hold (8 bytes) and the record
-// whose probability rides in its top field (2 bytes; word 12 reads the twelve records whose bins it collects) -- all
-// thirteen threads of a group read inside the same 128-byte line, the sixteen lanes of a word sit side by side, and a
-// wave stores four words x sixteen lanes = 512 contiguous bytes.  No LDS and a handful of registers ON PURPOSE: this
-// kernel runs on the coder threads' streams underneath the encoder's own kernels, and what it costs is the time its
-// workgroups wait for a slot, not its memory efficiency.  (Measured in the pipeline, per 4 Mbin chunk: a thread per
-// group fetching its own 128-byte line 3.5 ms; the same with the lines staged through 33 KB of LDS by coalesced
-// loads 5.9 ms -- the big workgroups find a CU late; the 16-bit interleave this replaces 2.8 ms.)
-// (Measured and rejected: letting this kernel store straight into the mapped host ring.  The
-// PCIe-bound waves crowd the encoder's own kernels off the GPU: 4.6 -> 2.4 Gpx/s.)
-struct InterleaveArgs { const uint16_t *src[kMaxTake]; uint32_t len[kMaxTake]; };
-__global__ void __launch_bounds__(256) k_pack_groups(InterleaveArgs a, uint64_t *__restrict__ rows, uint32_t n_words, uint32_t lanes) {
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t word = t / lanes, lane = t - word * lanes;   // word = 13 * group + j; lanes = 16 (a pack pair) or 24 (three packs)
-    if (word >= n_words) return;
-    const uint32_t g = word / uint32_t(kGroupWords), j = word - g * uint32_t(kGroupWords);
-    const uint32_t pos = g * uint32_t(kGroupBins), len = a.len[lane];
-    const uint16_t *src = a.src[lane] + pos;                     // chunk starts are multiples of 64 bins in 256-byte aligned buffers
-    auto rec = [&](uint32_t k) { return pos + k < len ? uint64_t(code13(src[k])) : uint64_t(0); };
-    uint64_t v;
-    if (pos + uint32_t(kGroupBins) <= len) {
-        const uint64_t q = *reinterpret_cast<const uint64_t *>(src + 4u * j);
-        v = uint64_t(code13(uint32_t(q) & 0xFFFFu)) | uint64_t(code13(uint32_t(q >> 16) & 0xFFFFu)) << 13 |
-            uint64_t(code13(uint32_t(q >> 32) & 0xFFFFu)) << 26 | uint64_t(code13(uint32_t(q >> 48))) << 39;
-        if (j < 12u) {
-            v |= uint64_t(src[52u + j] & 0xFFFu) << 52;
-        } else {
-            const uint64_t *tail = reinterpret_cast<const uint64_t *>(src + 52);
-            const uint64_t m = 0x8000800080008000ull;
-            // the four bins of each 8-byte load sit at bits 15, 31, 47, 63: gather them to bits 0..3
-            auto bins4 = [&](uint64_t x) { x &= m; return ((x >> 15) | (x >> 30) | (x >> 45) | (x >> 60)) & 0xFull; };
-            v |= (bins4(tail[0]) | bins4(tail[1]) << 4 | bins4(tail[2]) << 8) << 52;
-        }
-    } else {                                                     // the lane's last group of the chunk (or nothing at all)
-        v = rec(4u * j) | rec(4u * j + 1u) << 13 | rec(4u * j + 2u) << 26 | rec(4u * j + 3u) << 39;
-        if (j < 12u) v |= (rec(52u + j) & 0xFFFu) << 52;
-        else for (uint32_t e = 0; e < 12u; e++) v |= (rec(52u + e) >> 12) << (52u + e);
-    }
-    rows[t] = v;
-}
+// A host coder thread codes up to 24 images at once: three AVX-512 registers of eight 64-bit lanes in lock-step
+// (range_coder_x8.cpp).  What a register consumes is a PACK: 64 bins of each of its eight lanes as thirteen 64-bit words
+// of 13-bit codes, the eight lanes of a word side by side -- one aligned 64-byte load per four steps, and the link
+// carries 13 bits per bin instead of 16.  The pack is fixed when a group is LAUNCHED (launch_back: up to eight
+// consecutive jobs, the job's place is the lane) and its rows are written inside that launch, on the group's own stream
+// (kernels_e1.hip: k_mix leaves every image's groups in a stream of its own, k_pack_rows transposes a pack's streams
+// into its PackRows buffer).  A chunk of a pack is then ONE contiguous copy from the pack buffer into the thread's ring:
+// the copy streams carry nothing but copies and event records.  A coder thread takes one to three whole packs.
+// Images that are coded on their own (a group of one, the tail of a batch, the band encoder, QNBLIC) keep the plain u16 records and the scalar coder.
+// (Measured and rejected: a kernel that stores the rows straight into the mapped host ring.  The PCIe-bound waves crowd
+// the encoder's own kernels off the GPU: 4.6 -> 2.4 Gpx/s chip-wide, 3.34 / 2.68 / 2.46 Gpx/s with 16 / 48 / 128
+// workgroups per chunk against 5.5 with a staging pass + runtime copy.)
 
-// What a coder thread owns: a pinned ring of two half-buffers x sixteen lanes x kChunkBins, so chunk
-// c+1 lands while chunk c is coded.  Its device->host copies go through one of the context's few
-// copy streams: a stream per thread would outnumber the hardware queues, and streams that share a
-// hardware queue with a group's kernels have their copies stuck behind those kernels.
+// What a coder thread owns: page-locked rings, so chunks c+1 and c+2 land while chunk c is coded.  Its device->host
+// copies go through one of the context's few copy streams: a stream per thread would outnumber the hardware queues,
+// and streams that share a hardware queue with a group's kernels have their copies stuck behind those kernels.
 struct CoderThread {
     hipStream_t stream = nullptr;                        // one of the context's copy streams
     Event ev[kRingDepth];
-    Locked ring;
-    DevBuf<uint64_t> d_rows;                             // device: two halves of 13-bit groups (k_pack_groups' output)
+    Locked ring;                                         // a lone image's u16 chunks: kRingDepth slots of ring_chunk bins
+    Locked pring;                                        // packs: kRingDepth slots of kMaxPacks x pring_groups groups x 13 words x 8 lanes
     Locked whole;                                        // one whole QNBLIC image (its rANS runs last pixel first)
     RangeX8 x8, x8b, x8c;
     RangeScalar x1;
@@ -544,147 +524,151 @@ struct CoderThread {
         for (auto &e : ev) HIP_OK(e.create(hipEventDisableTiming | hipEventBlockingSync));
         return true;
     }
-    // The ring holds kRingDepth slots of ring_lanes x ring_chunk bins; it is sized by what the thread has actually been
-    // asked to code (one lane for an image coded alone, sixteen for a pack pair; the chunk no longer than the longest
-    // image) and only grows: a context that codes one small image through the drop-in entry points pins kilobytes,
-    // the bench's threads end up at 3 x 24 x 4 Mbin x 1.625 B = 491 MB each.
-    size_t ring_lanes = 0, ring_chunk = 0;
-    // 16-bit words per ring slot: a lone image's chunk as it is, or the 13-bit groups of ring_lanes lanes
-    size_t slot_words() const { return ring_lanes > 1 ? group_words(ring_chunk, ring_lanes) * 4 : ring_chunk; }
-    bool ensure_ring(size_t lanes, size_t chunk, bool need_rows) {
+    // The rings are sized by what the thread has actually been asked to code and only grow: a context that codes one
+    // small image through the drop-in entry points pins kilobytes, the bench's threads end up at
+    // 3 slots x 3 packs x 64 Ki groups x 832 B = 491 MB each.
+    size_t ring_chunk = 0, pring_groups = 0;
+    bool ensure_ring(size_t chunk) {
         chunk = (chunk + 4095) & ~size_t(4095);
-        if (lanes > ring_lanes || chunk > ring_chunk) {
-            const size_t nl = lanes > ring_lanes ? lanes : ring_lanes, nc = chunk > ring_chunk ? chunk : ring_chunk;
-            ring_lanes = nl; ring_chunk = nc;
-            if (!ring.alloc(kRingDepth * slot_words())) { ring_lanes = ring_chunk = 0; fprintf(stderr, "[nblic_amd] cannot allocate the coder thread's ring\n"); return false; }
+        if (chunk > ring_chunk) {
+            ring_chunk = chunk;
+            if (!ring.alloc(kRingDepth * ring_chunk)) { ring_chunk = 0; fprintf(stderr, "[nblic_amd] cannot allocate the coder thread's ring\n"); return false; }
         }
-        HIP_OK(d_rows.reserve(need_rows ? kRingDepth * group_words(ring_chunk, ring_lanes) : 0));
         return true;
     }
-    uint16_t *slot(size_t chunk) { return ring + size_t(chunk % kRingDepth) * slot_words(); }            // a lone image's chunk
-    uint64_t *rows(size_t chunk) { return reinterpret_cast<uint64_t *>(slot(chunk)); }
-    uint64_t *dev_rows(size_t chunk) { return d_rows + size_t(chunk % kRingDepth) * group_words(ring_chunk, ring_lanes); }
-};
-
-// How `take` images go to the AVX-512 packs (the coder threads, and nblic_amd_range_code_chunked that tests them).
-// More than one image: packs in lock-step -- a lone pack is bound by the latency of its own dependent chain, a second
-// one rides along almost for free, a third on what the core's ports have left (+20 % bins per CPU-second on the
-// records of real frames, and the rank's CPU quota is what bounds the pipeline).  Up to sixteen images make two packs
-// (16 lanes per word-row), more make three (24 lanes); the images are dealt to the packs in order, as evenly as they
-// go: pack p owns lanes 8p .. 8p + pack_n[p] - 1.  One image: no pack, the scalar coder.
-struct PackDeal {
-    int n_packs, pack_n[3] = {0, 0, 0}, pack_first[3] = {0, 0, 0};
-    explicit PackDeal(int take) : n_packs(take > 16 ? 3 : (take > 1 ? 2 : 0)) {
-        for (int p = 0, at = 0; p < n_packs; p++) { pack_n[p] = take / n_packs + (p < take % n_packs ? 1 : 0); pack_first[p] = at; at += pack_n[p]; }
-    }
-    size_t lanes() const { return size_t(8 * n_packs); }
-    int lane_of(int k) const { int p = 0; while (p + 1 < n_packs && k >= pack_first[p + 1]) p++; return 8 * p + (k - pack_first[p]); }
-};
-
-// Streams `take` images' bins from HBM and codes them: one image with the scalar coder, up to
-// eight in the lanes of the AVX-512 coder, up to sixteen as two packs in lock-step.
-// lens[k] = coder bytes or SIZE_MAX.
-static bool code_streamed(CoderThread &t, const uint16_t *const *dev, const size_t *n, int take, uint8_t *const *dst,
-                          const size_t *caps, size_t *lens, size_t chunk_bins) {
-    size_t n_max = 0;
-    for (int k = 0; k < take; k++) n_max = n[k] > n_max ? n[k] : n_max;
-    const PackDeal deal(take);
-    const int n_packs = deal.n_packs;
-    const size_t lanes = deal.lanes();
-    if (!t.ensure_ring(take > 1 ? lanes : 1, n_max < chunk_bins ? n_max + 4 : chunk_bins, take > 1)) return false;
-    const size_t chunks = (n_max + chunk_bins - 1) / chunk_bins;                     // chunk_bins <= kChunkBins, the ring's slot size
-    auto chunk_len = [&](size_t c, int k) { const size_t off = c * chunk_bins; return off >= n[k] ? size_t(0) : (n[k] - off < chunk_bins ? n[k] - off : chunk_bins); };
-    auto issue = [&](size_t c) -> bool {
-        if (take == 1) {                                      // one image: its bins as they are, for the scalar coder
-            HIP_OK(hipMemcpyAsync(t.slot(c), dev[0] + c * chunk_bins, chunk_len(c, 0) * sizeof(uint16_t), hipMemcpyDeviceToHost, t.stream));
-        } else {                                              // a pack pair: interleaved on the GPU, one copy
-            InterleaveArgs a{};
-            size_t longest = 0;
-            for (int k = 0; k < take; k++) {
-                const size_t len = chunk_len(c, k);
-                a.src[deal.lane_of(k)] = dev[k] + c * chunk_bins; a.len[deal.lane_of(k)] = uint32_t(len);
-                longest = len > longest ? len : longest;
-            }
-            const uint32_t n_groups = uint32_t((longest + kGroupBins - 1) / kGroupBins);
-            // (Measured and rejected, twice: letting this kernel store straight into the mapped host ring.  Round 1, chip-wide
-            // grid: 4.6 -> 2.4 Gpx/s.  Round 2, small grids so that few CUs wait on the link: 3.34 / 2.68 / 2.46 Gpx/s with
-            // 16 / 48 / 128 workgroups per chunk against 5.5 with the staging pass + runtime copy.)
-            uint64_t *d = t.dev_rows(c);
-            if (n_groups) {
-                if (!(dbg_flags() & kDbgNoPackKernel)) hipLaunchKernelGGL(k_pack_groups, dim3((n_groups * uint32_t(kGroupWords) * uint32_t(lanes) + 255u) / 256u), dim3(256), 0, t.stream, a, d, n_groups * uint32_t(kGroupWords), uint32_t(lanes));
-                HIP_OK(hipGetLastError());
-                // (In this pipeline the runtime performs the copy with its blit kernel -- four 32 MB dispatches per 128 MB chunk --
-                // whatever was tried: ring from hipHostMalloc instead of hipHostRegister, 2 / 4 / 8 copy streams, the copy cut
-                // into 8 or 16 MB pieces; the same copy from a bare test program goes through SDMA.  DESIGN.md section 4.)
-                if (!(dbg_flags() & kDbgNoCopy)) HIP_OK(hipMemcpyAsync(t.rows(c), d, group_words(longest, lanes) * sizeof(uint64_t), hipMemcpyDeviceToHost, t.stream));
-            }
+    size_t pack_words() const { return pring_groups * kGroupWords * kPackLanes; }                 // 64-bit words of one pack in one slot
+    bool ensure_pack_ring(size_t groups) {
+        groups = (groups + 63) & ~size_t(63);
+        if (groups > pring_groups) {
+            pring_groups = groups;
+            if (!pring.alloc(kRingDepth * size_t(kMaxPacks) * pack_words() * 4)) { pring_groups = 0; fprintf(stderr, "[nblic_amd] cannot allocate the coder thread's pack ring\n"); return false; }
         }
-        // (Measured and rejected: sleeping on a condition variable woken by a host function behind the copy, as the
-        // driver threads do.  A host function holds its stream until it has run, two threads share a copy stream,
-        // and the chunks arrived so much later that the threads fell back to packs of eight: 6.1 -> 4.0 Gpx/s.
-        // The threads wait for chunks for < 10 % of their time, so what the event wait burns is small.)
-        HIP_OK(hipEventRecord(t.ev[c % kRingDepth], t.stream));
         return true;
-    };
-    RangeX8 *const packs[3] = {&t.x8, &t.x8b, &t.x8c};
-    if (take > 1) { for (int p = 0; p < n_packs; p++) packs[p]->begin(deal.pack_n[p], dst + deal.pack_first[p], caps + deal.pack_first[p]); }
-    else t.x1.begin(dst[0], caps[0]);
-    for (size_t c = 0; c + 1 < size_t(kRingDepth) && c < chunks; c++) if (!issue(c)) return false;
-    for (size_t c = 0; c < chunks; c++) {
-        auto i0 = std::chrono::steady_clock::now();
-        if (c + kRingDepth - 1 < chunks && !issue(c + kRingDepth - 1)) return false;      // its ring slot was consumed one chunk ago
-        auto w0 = std::chrono::steady_clock::now();
-        t.issue_s += std::chrono::duration<double>(w0 - i0).count();
-        // a sleeping poll: hipEventSynchronize spins through the wait (see GroupWait), and CPU time is what the rank is
-        // short of; a chunk is ~30 ms of coding, so 100 us of extra latency on its arrival is nothing
-        for (;;) {
-            const hipError_t q = hipEventQuery(t.ev[c % kRingDepth]);
-            if (q == hipSuccess) break;
-            if (q != hipErrorNotReady) { fprintf(stderr, "[nblic_amd] HIP error: %s\n", hipGetErrorString(q)); return false; }
-            std::this_thread::sleep_for(std::chrono::microseconds(100));
-        }
-        t.wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
-        if (take > 1) {
-            size_t len[kMaxTake] = {0};
-            for (int k = 0; k < take; k++) len[deal.lane_of(k)] = chunk_len(c, k);
-            if (dbg_flags() & kDbgFeedOnly) {}
-            else if (n_packs == 3) feed_triple_groups(t.x8, t.x8b, t.x8c, t.rows(c), len);
-            else feed_pair_groups(t.x8, t.x8b, t.rows(c), len);
-        } else {
-            t.x1.feed(t.slot(c), chunk_len(c, 0));
-        }
     }
-    if (take > 1) { for (int p = 0; p < n_packs; p++) packs[p]->end(lens + deal.pack_first[p]); }
-    else lens[0] = t.x1.finish();
+    uint16_t *slot(size_t chunk) { return ring + size_t(chunk % kRingDepth) * ring_chunk; }
+    uint64_t *pack_slot(size_t chunk, int pack) { return reinterpret_cast<uint64_t *>(static_cast<uint16_t *>(pring)) + (size_t(chunk % kRingDepth) * size_t(kMaxPacks) + size_t(pack)) * pack_words(); }
+};
+
+// A sleeping poll: hipEventSynchronize spins through the wait (see GroupWait), and CPU time is what the rank is
+// short of; a chunk is ~30 ms of coding, so 100 us of extra latency on its arrival is nothing.
+// (Measured and rejected: sleeping on a condition variable woken by a host function behind the copy, as the
+// driver threads do.  A host function holds its stream until it has run, two threads share a copy stream,
+// and the chunks arrived so much later that the threads fell back to packs of eight: 6.1 -> 4.0 Gpx/s.)
+static bool wait_chunk(CoderThread &t, hipEvent_t e) {
+    const auto w0 = std::chrono::steady_clock::now();
+    for (;;) {
+        const hipError_t q = hipEventQuery(e);
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady) { fprintf(stderr, "[nblic_amd] HIP error: %s\n", hipGetErrorString(q)); return false; }
+        std::this_thread::sleep_for(std::chrono::microseconds(100));
+    }
+    t.wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
     return true;
 }
 
-// Coder thread.  Measured on the GPU box (EPYC 9575F), per thread: one stream alone 400-510
-// Mbins/s; packs always run as two AVX-512 registers in lock-step: 2 x 4 images 1300 Mbins/s,
-// 2 x 8 images 1950 Mbins/s -- at 2.5x / 3.4x the latency of a stream coded alone.  The host's
-// CPU share (16 cores, enforced as a quota), not the GPU, bounds the pipeline, so what counts is
-// bins per CPU-second: mid-batch, once every other thread is busy, a thread waits the ~30 ms it
-// takes for sixteen images to be queued rather than start a smaller pack (while others are idle --
-// the start of a batch -- it takes what is there, so all threads are at work within 0.4 s);
-// towards the end it takes whatever is there; and only
-// when at most two images per thread are left -- a short batch, or the very tail of a long one --
-// does each image go to a thread of its own.  (Alternatives ranked with a
-// discrete-event model of arrivals and coder speeds, tools/coder_policy_sim.py, then in situ.)
-static int coder_take(const nblic_amd_ctx *c) {                  // call with c->rm held; 0 = nothing to take
+// One image on its own: its u16 records stream from HBM chunk by chunk into the scalar coder.  *len = coder bytes or SIZE_MAX.
+static bool code_single(CoderThread &t, const uint16_t *dev, size_t n, uint8_t *dst, size_t cap, size_t *len, size_t chunk_bins) {
+    if (!t.ensure_ring(n < chunk_bins ? n + 4 : chunk_bins)) return false;
+    const size_t chunks = (n + chunk_bins - 1) / chunk_bins;                         // chunk_bins <= kChunkBins, the ring's slot size
+    auto chunk_len = [&](size_t c) { const size_t off = c * chunk_bins; return off >= n ? size_t(0) : std::min(n - off, chunk_bins); };
+    auto issue = [&](size_t c) -> bool {
+        HIP_OK(hipMemcpyAsync(t.slot(c), dev + c * chunk_bins, chunk_len(c) * sizeof(uint16_t), hipMemcpyDeviceToHost, t.stream));
+        HIP_OK(hipEventRecord(t.ev[c % kRingDepth], t.stream));
+        return true;
+    };
+    t.x1.begin(dst, cap);
+    for (size_t c = 0; c + 1 < size_t(kRingDepth) && c < chunks; c++) if (!issue(c)) return false;
+    for (size_t c = 0; c < chunks; c++) {
+        const auto i0 = std::chrono::steady_clock::now();
+        if (c + kRingDepth - 1 < chunks && !issue(c + kRingDepth - 1)) return false;      // its ring slot was consumed one chunk ago
+        t.issue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - i0).count();
+        if (!wait_chunk(t, t.ev[c % kRingDepth])) return false;
+        t.x1.feed(t.slot(c), chunk_len(c));
+    }
+    *len = t.x1.finish();
+    return true;
+}
+
+// One to three PACKS: chunk by chunk -- one contiguous copy per pack -- through the AVX-512 coders in lock-step (a lone
+// pack is bound by the latency of its own dependent chain, a second one rides along almost for free, a third on what
+// the core's ports have left).  n[8 p + lane] = bins of the image in lane `lane` of pack p (0 = no image); dst, caps and
+// lens likewise.  pack_n[p] = images of pack p, in lanes 0 .. pack_n[p] - 1.
+static bool code_packs(CoderThread &t, int n_packs, const uint64_t *const *dev_rows, const int *pack_n, const size_t *n, uint8_t *const *dst,
+                       const size_t *caps, size_t *lens, size_t chunk_bins) {
+    size_t groups[kMaxPacks] = {0}, most = 0;
+    for (int p = 0; p < n_packs; p++) {
+        for (int k = 0; k < pack_n[p]; k++) groups[p] = std::max(groups[p], (n[kPackLanes * p + k] + kGroupBins - 1) / kGroupBins);
+        most = std::max(most, groups[p]);
+    }
+    const size_t chunk_groups = std::min(chunk_bins / kGroupBins, most ? most : size_t(1));
+    if (!t.ensure_pack_ring(chunk_groups)) return false;
+    const size_t chunks = (most + chunk_groups - 1) / chunk_groups, chunk = chunk_groups * kGroupBins;
+    auto issue = [&](size_t c) -> bool {
+        for (int p = 0; p < n_packs; p++) {
+            const size_t g0 = c * chunk_groups;
+            if (g0 >= groups[p]) continue;
+            const size_t words = std::min(chunk_groups, groups[p] - g0) * kGroupWords * kPackLanes;
+            // (In this pipeline the runtime performs the copy with its blit kernel whatever was tried: ring from hipHostMalloc
+            // instead of hipHostRegister, 2 / 4 / 8 copy streams, the copy cut into 8 or 16 MB pieces; the same copy from a
+            // bare test program goes through SDMA.  DESIGN.md section 4.)
+            if (!(dbg_flags() & kDbgNoCopy)) HIP_OK(hipMemcpyAsync(t.pack_slot(c, p), dev_rows[p] + g0 * kGroupWords * kPackLanes, words * sizeof(uint64_t), hipMemcpyDeviceToHost, t.stream));
+        }
+        HIP_OK(hipEventRecord(t.ev[c % kRingDepth], t.stream));
+        return true;
+    };
+    RangeX8 *const packs[kMaxPacks] = {&t.x8, &t.x8b, &t.x8c};
+    for (int p = 0; p < n_packs; p++) packs[p]->begin(pack_n[p], dst + kPackLanes * p, caps + kPackLanes * p);
+    for (size_t c = 0; c + 1 < size_t(kRingDepth) && c < chunks; c++) if (!issue(c)) return false;
+    for (size_t c = 0; c < chunks; c++) {
+        const auto i0 = std::chrono::steady_clock::now();
+        if (c + kRingDepth - 1 < chunks && !issue(c + kRingDepth - 1)) return false;      // its ring slot was consumed one chunk ago
+        t.issue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - i0).count();
+        if (!wait_chunk(t, t.ev[c % kRingDepth])) return false;
+        size_t len[kMaxTake] = {0};
+        const uint64_t *rows_p[kMaxPacks] = {nullptr};
+        for (int p = 0; p < n_packs; p++) {
+            rows_p[p] = t.pack_slot(c, p);
+            for (int k = 0; k < pack_n[p]; k++) {
+                const size_t all = n[kPackLanes * p + k], off = c * chunk;
+                len[kPackLanes * p + k] = off >= all ? 0 : std::min(chunk, all - off);
+            }
+        }
+        if (!(dbg_flags() & kDbgFeedOnly)) feed_packs(packs, n_packs, rows_p, len);
+    }
+    for (int p = 0; p < n_packs; p++) packs[p]->end(lens + kPackLanes * p);
+    return true;
+}
+
+// Coder thread.  Measured on the GPU box (EPYC 9575F), per thread: one stream alone 400-510 Mbins/s; one pack of eight
+// 1300, two packs in lock-step 1950-2000, three 2200-2400 -- at 2.5x / 3.4x the latency of a stream coded alone.  The
+// host's CPU share (16 cores, enforced as a quota) is dear, so what counts is bins per CPU-second.  What a thread takes:
+//   packs at the front of the queue: as many whole packs as are there, up to three (max_take / 8).  Mid-batch (images
+//       still to come, and at least four per thread outstanding) it waits for a full set -- the ~30-45 ms it takes for
+//       three to be queued -- when every other thread is busy, and for at least two while others are idle too (the
+//       start of a batch, or the GPU side not keeping up): a lone pack costs twice the CPU time per bin.  At the tail it
+//       takes what is there.  A wait ends when something that is not a pack follows the packs at the front.
+//   an image on its own: that image (the scalar coder).  Whether an image is packed is decided when its group is
+//       launched (launch_back).
+// (Alternatives ranked with a discrete-event model of arrivals and coder speeds, tools/coder_policy_sim.py, then in situ.)
+static int coder_take(const nblic_amd_ctx *c) {                  // call with c->rm held; 0 = nothing to take; else the number of IMAGES
     const size_t q = c->ready.size();
     if (q == 0) return 0;
-    if (c->ready.front().kind == 1 || !c->simd) return 1;
-    const size_t left = q + size_t(c->batch_to_come), threads = c->coders.size();
-    if (left <= 2 * threads) return 1;                           // two rounds of singles beat one small pack
-    const size_t full = size_t(c->max_take);
-    if (c->batch_to_come > 0 && left >= 4 * threads) {
-        // mid-batch: with every other thread busy wait (~30-45 ms) for a full set; with others idle too -- the start of a
-        // batch, or the GPU side not keeping up -- at least for two full packs: packs of four lanes cost twice the CPU
-        // time per bin, and CPU time is what the rank is short of
-        const size_t want = c->idle_coders <= 1 ? full : (full < 16 ? full : size_t(16));
-        if (q < want) return 0;
+    const ReadyImage &f = c->ready.front();
+    if (f.kind == 1 || f.pack_n <= 1) return 1;
+    const int max_packs = std::max(1, c->max_take / int(kPackLanes));
+    int packs = 0; size_t imgs = 0;
+    bool more_may_join = true;
+    for (size_t i = 0; i < q && packs < max_packs;) {            // whole packs at the front (a pack is queued in one piece, lane 0 first)
+        const ReadyImage &r = c->ready[i];
+        if (r.kind == 1 || r.pack_n <= 1) { more_may_join = false; break; }
+        imgs += size_t(r.pack_n); i += size_t(r.pack_n); packs++;
     }
-    return int(q < full ? q : full);
+    const size_t left = q + size_t(c->batch_to_come), threads = c->coders.size();
+    if (more_may_join && c->batch_to_come > 0 && left >= 4 * threads) {
+        const int want = c->idle_coders <= 1 ? max_packs : std::min(max_packs, 2);
+        if (packs < want) return 0;
+    }
+    return int(imgs);
 }
 
 // One logical CPU per physical core of the process's affinity mask (the lowest-numbered sibling that is allowed).
@@ -742,10 +726,7 @@ static void coder_main(nblic_amd_ctx *c, int index) {
             take = coder_take(c);
             if (take == 0) break;                                // shutdown while waiting for a pack to fill
             c->idle_coders--;
-            for (int k = 0; k < take; k++) {
-                if (k > 0 && c->ready.front().kind == 1) { take = k; break; }
-                im[k] = c->ready.front(); c->ready.pop_front();
-            }
+            for (int k = 0; k < take; k++) { im[k] = c->ready.front(); c->ready.pop_front(); }
         }
         if (im[0].kind == 1) {                               // QNBLIC: histogram normalisation + rANS, one image per thread
             const ReadyImage &q = im[0];
@@ -766,20 +747,29 @@ static void coder_main(nblic_amd_ctx *c, int index) {
         }
         auto t0 = std::chrono::steady_clock::now();
         if (c->trace) fprintf(stderr, "[trace] %.3f coder %d takes %d\n", c->now(), index, take);
-        const uint16_t *src[kMaxTake]; size_t n[kMaxTake], caps[kMaxTake], lens[kMaxTake]; uint8_t *dst[kMaxTake];
+        size_t n[kMaxTake] = {0}, caps[kMaxTake] = {0}, lens[kMaxTake] = {0}; uint8_t *dst[kMaxTake] = {nullptr};
+        int at[kMaxTake];                                        // image k of the take sits at at[k] of the arrays above: 8 p + lane for packs, 0 for an image on its own
+        const uint64_t *rows[kMaxPacks] = {nullptr}; int pack_n[kMaxPacks] = {0};
+        int n_packs = 0;
         double bins = 0;
         for (int k = 0; k < take; k++) {
-            src[k] = c->cbufs[size_t(im[k].cb)]; n[k] = im[k].n_ev; bins += double(im[k].n_ev);
-            dst[k] = begin_stream_out(im[k], &caps[k]);
+            if (im[k].pack_n > 1 && im[k].pack_lane == 0) { rows[n_packs] = c->pbufs[size_t(im[k].cb)].get(); pack_n[n_packs] = im[k].pack_n; n_packs++; }
+            at[k] = im[k].pack_n > 1 ? int(kPackLanes) * (n_packs - 1) + im[k].pack_lane : 0;
+            n[at[k]] = im[k].n_ev; bins += double(im[k].n_ev);
+            dst[at[k]] = begin_stream_out(im[k], &caps[at[k]]);
         }
-        if (dbg_flags() & kDbgDeviceOnly) { for (int k = 0; k < take; k++) lens[k] = 0; }
-        else if (!code_streamed(t, src, n, take, dst, caps, lens, c->chunk_bins)) {
+        bool ok = true;
+        if (dbg_flags() & kDbgDeviceOnly) {}
+        else if (n_packs > 0) ok = code_packs(t, n_packs, rows, pack_n, n, dst, caps, lens, c->chunk_bins);
+        else ok = code_single(t, c->cbufs[size_t(im[0].cb)], n[0], dst[0], caps[0], &lens[0], c->chunk_bins);
+        if (!ok) {
             hipDeviceSynchronize();
-            for (int k = 0; k < take; k++) lens[k] = SIZE_MAX;
+            for (int k = 0; k < take; k++) lens[at[k]] = SIZE_MAX;
         }
         for (int k = 0; k < take; k++) {
-            if (lens[k] == SIZE_MAX) fprintf(stderr, "[nblic_amd] image %d: output buffer of %zu bytes is too small\n", im[k].job, im[k].caps[im[k].job]);
-            im[k].lens[im[k].job] = lens[k] == SIZE_MAX ? -1 : long(kHeaderBytes + lens[k]);
+            const size_t l = lens[at[k]];
+            if (l == SIZE_MAX) fprintf(stderr, "[nblic_amd] image %d: output buffer of %zu bytes is too small\n", im[k].job, im[k].caps[im[k].job]);
+            im[k].lens[im[k].job] = l == SIZE_MAX ? -1 : long(kHeaderBytes + l);
         }
         double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (c->trace) fprintf(stderr, "[trace] %.3f coder %d finished %d in %.3f s\n", c->now(), index, take, dt);
@@ -801,8 +791,17 @@ static int dev_take(const nblic_amd_ctx *c) {                  // call with c->r
     const size_t reserve = c->simd ? c->coders.size() * size_t(kMaxTake) / 2 : c->coders.size();
     if (q < size_t(kDevPack) + reserve) return 0;
     if (int(q) + c->batch_to_come + c->queued_images < c->dev_min_outstanding) return 0;
-    for (size_t k = 0; k < size_t(kDevPack); k++) if (c->ready[q - 1 - k].kind == 1) return 0;   // QNBLIC images are host work
-    return kDevPack;
+    // whole units from the back of the queue -- an image on its own, or a pack, which is queued in one piece and whose
+    // buffer goes back with all of its lanes -- as many as fit a wave's 64 lanes
+    size_t i = q; int n = 0;
+    while (i > 0) {
+        const ReadyImage &r = c->ready[i - 1];
+        if (r.kind == 1) return 0;                               // QNBLIC images are host work
+        const int unit = r.pack_n > 1 ? r.pack_n : 1;
+        if (n + unit > kDevPack) break;
+        n += unit; i -= size_t(unit);
+    }
+    return n;
 }
 
 static void dev_coder_main(nblic_amd_ctx *c, int index) {
@@ -840,7 +839,9 @@ static void dev_coder_main(nblic_amd_ctx *c, int index) {
             size_t room;
             dst[k] = begin_stream_out(im[k], &room);
             const size_t cap = std::min(room, (k + 1 < take ? off[k + 1] : need) - off[k]);
-            h_jobs[k] = RcJob{c->cbufs[size_t(im[k].cb)], d_out + off[k], d_lens + k, im[k].n_ev, uint32_t(cap < 0xFFFFFFF0u ? cap : 0xFFFFFFF0u)};
+            const bool packed = im[k].pack_n > 1;                // a lane of a pack: read from the pack's rows
+            h_jobs[k] = RcJob{packed ? nullptr : c->cbufs[size_t(im[k].cb)].get(), packed ? c->pbufs[size_t(im[k].cb)].get() : nullptr, uint32_t(im[k].pack_lane),
+                              d_out + off[k], d_lens + k, im[k].n_ev, uint32_t(cap < 0xFFFFFFF0u ? cap : 0xFFFFFFF0u)};
             bins += double(im[k].n_ev);
         }
         good = good && hipMemcpyAsync(d_jobs, h_jobs, size_t(take) * sizeof(RcJob), hipMemcpyHostToDevice, st) == hipSuccess &&
@@ -876,6 +877,17 @@ static bool acquire_coded(nblic_amd_ctx *c, Slot &s, size_t words) {
     return true;
 }
 
+// Takes a buffer for the rows of one pack whose longest image has max_ev bins (waits like acquire_coded).
+static bool acquire_pack(nblic_amd_ctx *c, int *id, size_t max_ev) {
+    {
+        std::unique_lock<std::mutex> l(c->fm);
+        c->fcv.wait(l, [c] { return !c->free_pbufs.empty(); });
+        *id = c->free_pbufs.front(); c->free_pbufs.pop_front();
+    }
+    HIP_OK(c->pbufs[size_t(*id)].reserve_bins(max_ev));
+    return true;
+}
+
 // Runs on a HIP runtime thread when the group's kernels have finished: queues the images for the
 // coder threads and hands the device workspace back.  (No HIP calls in here.)
 static void on_group_done(void *vp) {
@@ -886,7 +898,7 @@ static void on_group_done(void *vp) {
         std::lock_guard<std::mutex> l(c->rm);
         for (int k = 0; k < gp->n_jobs; k++) {
             const Slot &s = gp->slots[size_t(k)];
-            c->ready.push_back(ReadyImage{s.cb, s.job, s.h, s.w, s.n_ev, gp->outs, gp->caps, gp->lens, gp->kind, gp->batch, s.near, k_step_for_near(s.near), s.effort});
+            c->ready.push_back(ReadyImage{s.cb, s.job, s.h, s.w, s.n_ev, gp->outs, gp->caps, gp->lens, gp->kind, gp->batch, s.near, k_step_for_near(s.near), s.effort, s.pack_n, s.pack_lane});
         }
         c->batch_to_come -= gp->n_jobs;
     }
@@ -895,7 +907,7 @@ static void on_group_done(void *vp) {
 }
 
 static double thread_cpu_s();
-static bool launch_back(nblic_amd_ctx *c, Group &g, bool with_coders, bool general = false) {
+static bool launch_back(nblic_amd_ctx *c, Group &g, bool with_coders, bool general = false, bool force_pack = false) {
     // a BLOCKING wait: a spinning one per driver thread would take cores from the coder threads
     const double w0 = thread_cpu_s();
     { std::lock_guard<std::mutex> l(g.front->m); g.front->ready = false; }
@@ -917,12 +929,42 @@ static bool launch_back(nblic_amd_ctx *c, Group &g, bool with_coders, bool gener
     for (int k = 0; k < g.n_jobs; k++) {
         Slot &s = g.slots[size_t(k)];
         s.n_ev = g.h_totals[size_t(k) * kTotalsStride + 2];
+        s.pack_n = 1; s.pack_lane = 0;
         if (s.n_ev >= 0x7FFFFFFFu) { fprintf(stderr, "[nblic_amd] event count overflow\n"); return false; }
         if (!ensure_events(s, s.n_ev)) return false;
-        // the coded bins go straight into a pool buffer that outlives this group's turn on the slot
-        if (!acquire_coded(c, s, size_t(s.n_ev) + 8)) return false;
-        s.b.coded = c->cbufs[size_t(s.cb)];
-        e1_job_back(g.h_jobs[k], s.b, s.n_ev);
+    }
+    // Packs: up to eight consecutive jobs of the launch are coded together by one AVX-512 register of a coder thread
+    // (E1Job::pack_rows).  Not packed: a job on its own; hosts without AVX-512; and everything launched while at most two images per coder thread are outstanding -- queued,
+    // in flight on the GPU (this launch included) or still to be submitted: the tail of a batch or a short batch, where
+    // an image per thread finishes sooner than a pack per thread.
+    bool packing = force_pack || (with_coders && c->simd && g.n_jobs >= 2);      // force_pack: the layout hook (nblic_amd_debug_pack_rows)
+    if (packing && !force_pack) {
+        std::lock_guard<std::mutex> l(c->rm);
+        packing = c->ready.size() + size_t(c->batch_to_come) + size_t(c->queued_images) > 2 * c->coders.size();
+    }
+    for (int k0 = 0; k0 < g.n_jobs; k0 += int(kPackLanes)) {
+        const int cnt = std::min(int(kPackLanes), g.n_jobs - k0);
+        int pack_id = -1;
+        if (packing && cnt >= 2) {
+            size_t max_ev = 0;
+            for (int k = k0; k < k0 + cnt; k++) max_ev = std::max(max_ev, size_t(g.slots[size_t(k)].n_ev));
+            if (!acquire_pack(c, &pack_id, max_ev)) {            // the buffer is taken, its memory is not there: hand it back
+                if (pack_id >= 0) { std::lock_guard<std::mutex> l(c->fm); c->free_pbufs.push_front(pack_id); }
+                return false;
+            }
+        }
+        for (int k = k0; k < k0 + cnt; k++) {
+            Slot &s = g.slots[size_t(k)];
+            if (pack_id >= 0) {
+                s.cb = pack_id; s.pack_n = cnt; s.pack_lane = k - k0;
+                s.b.coded = nullptr;
+            } else {
+                // the coded bins go straight into a pool buffer that outlives this group's turn on the slot
+                if (!acquire_coded(c, s, size_t(s.n_ev) + 8)) return false;
+                s.b.coded = c->cbufs[size_t(s.cb)];
+            }
+            e1_job_back(g.h_jobs[k], s.b, s.n_ev, pack_id >= 0 ? c->pbufs[size_t(pack_id)].get() : nullptr, s.pack_lane);
+        }
     }
     HIP_OK(hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(g.n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, g.stream));
     e1_launch_back(g.d_jobs, g.h_jobs, g.n_jobs, g.stream, (c->timing && !general) ? &g.tm : nullptr, general);
@@ -1032,7 +1074,7 @@ static void encode_submit(nblic_amd_ctx *c, const nblic_amd_ctx::SubmitItem &it)
         while (next < order.size() && g.n_jobs < int(g.slots.size()) && kind_of(order[next]) == kind) {
             const int k = order[next++];
             Slot &s = g.slots[size_t(g.n_jobs++)];
-            s.job = k; s.h = it.hs[k]; s.w = it.ws[k]; s.cb = -1; s.near = near_of(k); s.effort = effort_of(k);
+            s.job = k; s.h = it.hs[k]; s.w = it.ws[k]; s.cb = -1; s.pack_n = 1; s.pack_lane = 0; s.near = near_of(k); s.effort = effort_of(k);
             unsigned char *const rec = it.recons ? it.recons[k] : nullptr;
             if (kind == 0 && rec) {                       // -n0 -e1: the reconstruction IS the input (NBLIC.c:876 rewrites the same bytes)
                 const size_t n = size_t(s.h) * size_t(s.w);
@@ -1084,6 +1126,7 @@ static void report_coders(nblic_amd_ctx *c) {                        // NBLIC_AM
     for (int k = 2; k <= 7; k++) t2 += c->takes[k];
     for (int k = 9; k <= 15; k++) t9 += c->takes[k];
     for (int k = 17; k < kMaxTake; k++) t17 += c->takes[k];
+    // (a take is whole packs now: 2-8 images are one pack, 9-16 two, 17-24 three)
     fprintf(stderr, "[nblic_amd] coder: %.2f thread-s of that waiting for chunks; takes of 1/2-7/8/9-15/16/17-23/24 images: %ld/%ld/%ld/%ld/%ld/%ld/%ld\n", c->wait_s,
             c->takes[1], t2, c->takes[8], t9, c->takes[16], t17, c->takes[kMaxTake]);
 }
@@ -2589,13 +2632,41 @@ int nblic_amd_range_code_multi(const uint16_t *const *coded, const size_t *n, in
     return 0;
 }
 
+// The coder threads' walk over chunks of packs, minus the GPU: every pack's chunk laid out by pack_groups_host (the
+// layout's reference) in a 64-byte aligned buffer of its own and fed through feed_packs.
+static int code_packs_host(int n_packs, const int *pack_n, const uint16_t *const *coded, const size_t *n, unsigned char *const *outs,
+                           const size_t *caps, size_t *lens, size_t chunk) {
+    RangeX8 x[kMaxPacks];
+    RangeX8 *packs[kMaxPacks] = {&x[0], &x[1], &x[2]};
+    size_t n_max = 0;
+    for (int p = 0; p < n_packs; p++) {
+        x[p].begin(pack_n[p], outs + kPackLanes * p, caps + kPackLanes * p);
+        for (int k = 0; k < pack_n[p]; k++) n_max = std::max(n_max, n[kPackLanes * p + k]);
+    }
+    const size_t rows_words = group_words(chunk);
+    uint64_t *rows[kMaxPacks] = {nullptr};
+    for (int p = 0; p < n_packs; p++)
+        if (!(rows[p] = static_cast<uint64_t *>(aligned_alloc(64, (rows_words * sizeof(uint64_t) + 63) & ~size_t(63))))) { for (int q = 0; q < p; q++) free(rows[q]); return -1; }
+    for (size_t off = 0; off < n_max; off += chunk) {
+        size_t len[kMaxTake] = {0};
+        for (int p = 0; p < n_packs; p++) {
+            memset(rows[p], 0, rows_words * sizeof(uint64_t));
+            for (int k = 0; k < pack_n[p]; k++) {
+                const size_t at = kPackLanes * p + k;
+                len[at] = off >= n[at] ? 0 : std::min(n[at] - off, chunk);
+                pack_groups_host(rows[p], k, coded[at] + off, len[at]);
+            }
+        }
+        feed_packs(packs, n_packs, rows, len);
+    }
+    for (int p = 0; p < n_packs; p++) { free(rows[p]); x[p].end(lens + kPackLanes * p); }
+    return 0;
+}
+
 int nblic_amd_range_code_chunked(const uint16_t *const *coded, const size_t *n, int count, unsigned char *const *outs,
                                  const size_t *caps, size_t *lens, size_t chunk) {
     if (count < 1 || count > kMaxTake || chunk == 0) return -1;
-    size_t n_max = 0;
-    for (int k = 0; k < count; k++) n_max = n[k] > n_max ? n[k] : n_max;
-    const bool packs = count > 1 && have_avx512();
-    if (!packs) {                                              // one after the other through the scalar coder
+    if (!(count > 1 && have_avx512())) {                       // one after the other through the scalar coder
         for (int k = 0; k < count; k++) {
             RangeScalar r;
             r.begin(outs[k], caps[k]);
@@ -2604,30 +2675,31 @@ int nblic_amd_range_code_chunked(const uint16_t *const *coded, const size_t *n, 
         }
         return 0;
     }
-    // the coder threads' deal (PackDeal), each chunk laid out as 13-bit groups (here on the host, in the pipeline by
-    // k_pack_groups on the GPU) and fed through feed_pair_groups / feed_triple_groups
-    RangeX8 x[3];
-    const PackDeal deal(count);
-    const int n_packs = deal.n_packs;
-    const size_t lanes = deal.lanes();
-    for (int p = 0; p < n_packs; p++) x[p].begin(deal.pack_n[p], outs + deal.pack_first[p], caps + deal.pack_first[p]);
-    const size_t rows_cap = group_words(chunk, lanes);
-    uint64_t *rows = static_cast<uint64_t *>(aligned_alloc(64, (rows_cap * sizeof(uint64_t) + 63) & ~size_t(63)));
-    if (!rows) return -1;
-    for (size_t off = 0; off < n_max; off += chunk) {
-        size_t len[kMaxTake] = {0};
-        memset(rows, 0, rows_cap * sizeof(uint64_t));
-        for (int k = 0; k < count; k++) {
-            const int lane = deal.lane_of(k);
-            len[lane] = off >= n[k] ? 0 : (n[k] - off < chunk ? n[k] - off : chunk);
-            pack_groups_host(rows, lane, coded[k] + off, len[lane], int(lanes));
-        }
-        if (n_packs == 3) feed_triple_groups(x[0], x[1], x[2], rows, len);
-        else feed_pair_groups(x[0], x[1], rows, len);
+    // consecutive eights are packs, as the groups' launches make them; any chunk length goes (every chunk is laid out from its own group 0)
+    const int n_packs = (count + int(kPackLanes) - 1) / int(kPackLanes);
+    int pack_n[kMaxPacks] = {0};
+    for (int p = 0; p < n_packs; p++) pack_n[p] = std::min(int(kPackLanes), count - int(kPackLanes) * p);
+    return code_packs_host(n_packs, pack_n, coded, n, outs, caps, lens, chunk);   // stream k is lane k % 8 of pack k / 8: the arrays are already indexed 8 p + lane
+}
+
+void nblic_amd_pack_groups_host(uint64_t *rows, int lane, const uint16_t *coded, size_t n) { pack_groups_host(rows, lane, coded, n); }
+
+int nblic_amd_range_code_packs(int n_packs, const int *pack_n, const uint16_t *const *coded, const size_t *n, unsigned char *const *outs,
+                               const size_t *caps, size_t *lens, size_t chunk) {
+    if (n_packs < 1 || n_packs > kMaxPacks || chunk < kGroupBins || chunk % kGroupBins != 0) return -1;
+    for (int p = 0; p < n_packs; p++) if (pack_n[p] < 1 || pack_n[p] > int(kPackLanes)) return -1;
+    if (!have_avx512()) {                                      // what the coder threads do on such a host: every image on its own
+        for (int p = 0; p < n_packs; p++)
+            for (int k = 0; k < pack_n[p]; k++) {
+                const size_t at = kPackLanes * size_t(p) + size_t(k);
+                RangeScalar r;
+                r.begin(outs[at], caps[at]);
+                for (size_t off = 0; off < n[at]; off += chunk) r.feed(coded[at] + off, std::min(n[at] - off, chunk));
+                lens[at] = r.finish();
+            }
+        return 1;
     }
-    free(rows);
-    for (int p = 0; p < n_packs; p++) x[p].end(lens + deal.pack_first[p]);
-    return 0;
+    return code_packs_host(n_packs, pack_n, coded, n, outs, caps, lens, chunk);
 }
 
 int nblic_amd_selftest(nblic_amd_ctx *c) {
@@ -2673,6 +2745,13 @@ nblic_amd_ctx *nblic_amd_create_ex(int device, int n_groups, int group_size, int
     }
     c->cbufs.resize(size_t(n_host_buffers));
     for (int i = 0; i < n_host_buffers; i++) c->free_cbufs.push_back(i);
+    // the same backlog counted in packs: n_host_buffers images' worth of bins, a pack per group in flight at the least.
+    // An image takes a buffer of ONE of the two pools, and no more images are in flight than before, so the backlog in
+    // HBM is what it was: both pools hand out the buffer returned last (push_front on return; the u16 pool used to
+    // rotate), and a buffer's memory is allocated at its first use, so neither pool allocates beyond the backlog there is.
+    const int n_pack_buffers = std::max(n_groups * ((group_size + int(kPackLanes) - 1) / int(kPackLanes)) + kMaxPacks, n_host_buffers / int(kPackLanes));
+    c->pbufs.resize(size_t(n_pack_buffers));
+    for (int i = 0; i < n_pack_buffers; i++) c->free_pbufs.push_back(i);
     if (c->dec_stream.create(hipStreamNonBlocking) != hipSuccess || c->d_redo.alloc(2) != hipSuccess || hipMemset(c->d_redo, 0, 2 * sizeof(unsigned long long)) != hipSuccess ||
         c->dec_stream2.create(hipStreamNonBlocking) != hipSuccess) { nblic_amd_destroy(c); return nullptr; }
     // (Measured and rejected: creating the copy streams with the highest stream priority, so that the
@@ -2718,6 +2797,52 @@ void nblic_amd_destroy(nblic_amd_ctx *c) {
     for (auto &t : c->drivers) t.join();
     if (c->feed_pipe[0] >= 0) { close(c->feed_pipe[0]); close(c->feed_pipe[1]); }
     delete c;                                                                // every thread has ended: the members release what they own
+}
+
+void nblic_amd_debug_takes(nblic_amd_ctx *c, long takes[25]) {
+    static_assert(kMaxTake == 24, "the header says 25 counts");
+    std::lock_guard<std::mutex> l(c->stat_m);
+    for (int k = 0; k <= kMaxTake; k++) takes[k] = c->takes[k];
+}
+
+long nblic_amd_debug_pack_rows(nblic_amd_ctx *c, int n_images, const unsigned char *const *imgs, const int *heights, const int *widths,
+                               unsigned long long *rows, size_t rows_words, unsigned short *const *coded, unsigned int *n_bins) {
+    if (!c || n_images < 2 || n_images > int(kPackLanes)) return -1;
+    for (int k = 0; k < n_images; k++) if (!size_ok(heights[k], widths[k], c->max_px)) return -1;
+    std::lock_guard<std::mutex> g(c->api);
+    if (hipSetDevice(c->device) != hipSuccess) return -1;
+    const int id = take_group(c);
+    Group &grp = c->groups[size_t(id)];
+    long words = -1;
+    auto run = [&](bool packed) -> bool {                      // the group's two halves as a driver runs them, packing forced or off
+        grp.n_jobs = n_images;
+        for (int k = 0; k < n_images; k++) { Slot &s = grp.slots[size_t(k)]; s.job = k; s.h = heights[k]; s.w = widths[k]; s.cb = -1; s.near = 0; s.effort = 1; }
+        const bool ok = launch_front(c, grp, imgs, false) && launch_back(c, grp, false, false, packed) && hipStreamSynchronize(grp.stream) == hipSuccess;
+        grp.tm_pending = false;
+        return ok;
+    };
+    auto give_back = [&] { for (int k = 0; k < n_images; k++) return_coded(c, grp.slots[size_t(k)]); };
+    if (int(grp.slots.size()) >= n_images) {
+        bool ok = run(true) && grp.slots[0].pack_n == n_images;
+        if (ok) {
+            size_t max_ev = 0;
+            for (int k = 0; k < n_images; k++) max_ev = std::max(max_ev, size_t(grp.slots[size_t(k)].n_ev));
+            const size_t w = PackRows::words(max_ev);
+            ok = w <= rows_words && hipMemcpy(rows, c->pbufs[size_t(grp.slots[0].cb)].get(), w * sizeof(uint64_t), hipMemcpyDeviceToHost) == hipSuccess;
+            if (ok) words = long(w);
+        }
+        give_back();
+        ok = ok && run(false);
+        for (int k = 0; k < n_images && ok; k++) {
+            const Slot &s = grp.slots[size_t(k)];
+            ok = s.cb >= 0 && s.n_ev <= n_bins[k] && hipMemcpy(coded[k], c->cbufs[size_t(s.cb)].get(), size_t(s.n_ev) * sizeof(uint16_t), hipMemcpyDeviceToHost) == hipSuccess;
+            n_bins[k] = s.n_ev;
+        }
+        give_back();
+        if (!ok) words = -1;
+    }
+    release_group(c, id);
+    return words;
 }
 
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
@@ -2803,7 +2928,7 @@ long nblic_amd_debug_stage(nblic_amd_ctx *c, const unsigned char *img, int h, in
     const int id = take_group(c);
     Group &grp = c->groups[size_t(id)];
     Slot &s = grp.slots[0];
-    grp.n_jobs = 1; s.job = 0; s.h = h; s.w = w; s.cb = -1; s.near = 0; s.effort = 1;
+    grp.n_jobs = 1; s.job = 0; s.h = h; s.w = w; s.cb = -1; s.pack_n = 1; s.pack_lane = 0; s.near = 0; s.effort = 1;
     const uint8_t *imgs[1] = {img};
     long count = -1;
     size_t n = size_t(h) * size_t(w);

@@ -36,18 +36,15 @@ struct RangeX8 {
 // two packs (sixteen streams) advanced in lock-step by one thread
 void feed_pair(RangeX8 &a, const uint16_t *const *src_a, const size_t *len_a, RangeX8 &b, const uint16_t *const *src_b, const size_t *len_b);
 
-// the same from row-interleaved bins: rows[16 * i + lane] = bins 4i..4i+3 of lane `lane` as one 64-bit word
-// (64-byte aligned; lanes 0-7 pack a, 8-15 pack b); len[lane] = the lane's bins in this chunk
-void feed_pair_rows(RangeX8 &a, RangeX8 &b, const uint64_t *rows, const size_t *len);
-
-// the form in which a pack pair's bins cross PCIe: 64 records of a lane as 64 x 13 bits = thirteen 64-bit words,
-// rows[(13 * g + j) * 16 + lane] = word j of the lane's group g (range_coder_x8.cpp, k_pack_groups in pipeline.hip)
-constexpr size_t kGroupBins = 64, kGroupWords = 13;
+// The form in which a pack's bins cross PCIe: 64 records of a lane as 64 x 13 bits = thirteen 64-bit words, the eight
+// lanes of a word side by side: rows[(13 * g + j) * 8 + lane] = word j of the lane's group g (range_coder_x8.cpp; k_mix
+// and k_pack_rows in kernels_e1.hip write it per pack of a group launch).
+constexpr size_t kGroupBins = 64, kGroupWords = 13, kPackLanes = 8;
 constexpr uint32_t code13(uint32_t rec) { return (rec & 0xFFFu) | ((rec >> 3) & 0x1000u); }           // prob | bin << 12
-constexpr size_t group_words(size_t bins, size_t lanes = 16) { return (bins + kGroupBins - 1) / kGroupBins * kGroupWords * lanes; }   // words of `bins` bins x `lanes` lanes
-void feed_pair_groups(RangeX8 &a, RangeX8 &b, const uint64_t *rows, const size_t *len);                    // 16 lanes
-void feed_triple_groups(RangeX8 &a, RangeX8 &b, RangeX8 &c, const uint64_t *rows, const size_t *len);      // 24 lanes: rows[(13 g + j) * 24 + lane]
-void pack_groups_host(uint64_t *rows, int lane, const uint16_t *coded, size_t len, int lanes = 16);   // ORs one lane's records into zeroed rows (tests, the chunked self-check)
+constexpr size_t group_words(size_t bins, size_t lanes = kPackLanes) { return (bins + kGroupBins - 1) / kGroupBins * kGroupWords * lanes; }   // words of `bins` bins x `lanes` lanes
+// one to three packs in lock-step, each from its own 64-byte aligned row stream; len[8 p + lane] = the lane's bins in this chunk (0 = idle)
+void feed_packs(RangeX8 *const *packs, int n_packs, const uint64_t *const *rows_p, const size_t *len);
+void pack_groups_host(uint64_t *rows, int lane, const uint16_t *coded, size_t len, int lanes = int(kPackLanes));   // ORs one lane's records into zeroed rows: the layout's reference (tests, the chunked self-check)
 
 bool have_avx512();
 size_t range_code(const uint16_t *coded, size_t n, uint8_t *out, size_t cap);

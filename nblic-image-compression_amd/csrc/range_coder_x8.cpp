@@ -247,52 +247,10 @@ NB_TARGET void feed_pair(RangeX8 &A, const uint16_t *const *src_a, const size_t 
     B.feed(rb, lb);
 }
 
-// The same pair fed from ROW-INTERLEAVED bins: rows[16 * i + lane] holds, as one 64-bit word, bins
-// 4i .. 4i+3 of lane `lane` (lanes 0-7 = pack A, 8-15 = pack B; zero where a lane has no bin).  That is
-// exactly what the gathers above assemble, so with this layout -- which a GPU kernel produces for the
-// coder threads before the bins leave HBM (k_interleave16) -- a pack's next four steps are ONE
-// aligned 64-byte load, and a chunk of sixteen images is one contiguous copy.  len[lane] = bins of
-// the lane in this chunk (0 = idle).
-NB_TARGET void feed_pair_rows(RangeX8 &A, RangeX8 &B, const uint64_t *rows, const size_t *len) {
-    Regs RA = A.st->L.r, RB = B.st->L.r;
-    Outs &OA = A.st->L.o, &OB = B.st->L.o;
-    const int ca = A.st->count, cb = B.st->count;
-    unsigned act_a = 0, act_b = 0;
-    size_t m = SIZE_MAX, longest = 0;
-    alignas(64) uint64_t lv[16];
-    for (int k = 0; k < 16; k++) {
-        const bool on = (k < 8 ? k < ca : k - 8 < cb) && len[k];
-        lv[k] = on ? len[k] : 0;
-        if (on) { (k < 8 ? act_a : act_b) |= 1u << (k & 7); if (len[k] < m) m = len[k]; if (len[k] > longest) longest = len[k]; }
-    }
-    size_t pos = 0;
-    if (act_a == (1u << ca) - 1u && act_b == (1u << cb) - 1u && (act_a | act_b)) {
-        for (; pos + 4 <= m; pos += 4) {
-            const uint64_t *row = rows + 4 * pos;                // 16 words per four bins
-            _mm_prefetch((const char *)(row + 16 * 16), _MM_HINT_T0);
-            const __m512i ga = _mm512_load_si512((const void *)row), gb = _mm512_load_si512((const void *)(row + 8));
-            step_all(RA, OA, ga);                         step_all(RB, OB, gb);
-            step_all(RA, OA, _mm512_srli_epi64(ga, 16));  step_all(RB, OB, _mm512_srli_epi64(gb, 16));
-            step_all(RA, OA, _mm512_srli_epi64(ga, 32));  step_all(RB, OB, _mm512_srli_epi64(gb, 32));
-            step_all(RA, OA, _mm512_srli_epi64(ga, 48));  step_all(RB, OB, _mm512_srli_epi64(gb, 48));
-        }
-    }
-    // whatever is left (lanes of different length, a pack with idle lanes): one bin at a time, lanes masked by their length
-    const __m512i la = _mm512_load_si512((const void *)lv), lb = _mm512_load_si512((const void *)(lv + 8));
-    for (; pos < longest; pos++) {
-        const uint64_t *row = rows + 16 * (pos >> 2);
-        const __m512i sh = _mm512_set1_epi64((long long)(16 * (pos & 3))), p = _mm512_set1_epi64((long long)pos);
-        const __mmask8 ka = _mm512_cmplt_epu64_mask(p, la), kb = _mm512_cmplt_epu64_mask(p, lb);
-        if (ka) step(RA, OA, _mm512_srlv_epi64(_mm512_load_si512((const void *)row), sh), ka);
-        if (kb) step(RB, OB, _mm512_srlv_epi64(_mm512_load_si512((const void *)(row + 8)), sh), kb);
-    }
-    A.st->L.r = RA;
-    B.st->L.r = RB;
-}
-
-// The pair fed from 13-BIT GROUPS -- the form in which bins cross PCIe.  A record is 12 bits of probability and the
-// bin: 13 bits as code13(), and 64 of them are exactly thirteen 64-bit words.  rows[(13 * g + j) * 16 + lane] is word j
-// of lane `lane`'s group g (bins 64g .. 64g+63; zero where the lane has no bin):
+// Packs fed from 13-BIT GROUPS -- the form in which bins cross PCIe.  A record is 12 bits of probability and the
+// bin: 13 bits as code13(), and 64 of them are exactly thirteen 64-bit words.  A pack has a row stream of its own, eight
+// lanes wide: rows[(13 * g + j) * 8 + lane] is word j of lane `lane`'s group g (bins 64g .. 64g+63; zero where the lane
+// has no bin):
 //     bits  0..51 of word j            codes 4j .. 4j+3 of the group, 13 bits each            (52 codes in 13 words)
 //     bits 52..63 of word j, j < 12    the probability of code 52+j
 //     bits 52..63 of word 12           bit e = the bin of code 52+e
@@ -301,7 +259,8 @@ NB_TARGET void feed_pair_rows(RangeX8 &A, RangeX8 &B, const uint64_t *rows, cons
 // 13k .. 13k+12 of the 832 bits, the 64 x 2 steps fully unrolled since every one has its own shift -- the compiler kept
 // the coder state on the stack there, and the walk ran 9-15 % slower than from 16-bit rows.)  A pack's word is still ONE
 // aligned 64-byte load, and the link -- which bounds the pipeline -- carries 18.75 % fewer
-// bytes.  k_pack_groups (pipeline.hip) writes the layout; pack_groups_host is the same on the host, for tests.
+// bytes.  k_mix and k_pack_rows (kernels_e1.hip) write the layout; pack_groups_host with lanes = 8 is the same on the
+// host, the layout's reference for the tests.
 void pack_groups_host(uint64_t *rows, int lane, const uint16_t *coded, size_t len, int lanes) {
     const size_t L = size_t(lanes);
     for (size_t i = 0; i < len; i++) {
@@ -313,17 +272,18 @@ void pack_groups_host(uint64_t *rows, int lane, const uint16_t *coded, size_t le
     }
 }
 
-// NP packs (8 * NP lanes, a word-row is NP aligned 64-byte loads) advanced in lock-step: two are a pack pair, three
-// ride a third pack along on whatever the core's ports have left (EPYC 9575F, one thread alone: 2150 -> 2380 Mbins/s).
+// NP packs (a word-row is one aligned 64-byte load from each pack's stream) advanced in lock-step: two are a pack pair,
+// three ride a third pack along on whatever the core's ports have left (EPYC 9575F, one thread alone: 2150 -> 2380
+// Mbins/s).  rows_p[p] = pack p's rows; len[8 p + lane] = the lane's bins in this chunk.
 template <int NP>
-NB_TARGET NB_INLINE void feed_groups_np(RangeX8 *const *P, const uint64_t *rows, const size_t *len) {
-    constexpr size_t L = 8 * NP;
+NB_TARGET NB_INLINE void feed_groups_np(RangeX8 *const *P, const uint64_t *const *rows_p, const size_t *len) {
+    constexpr size_t L = 8;                                       // words between consecutive rows of one pack
     Regs R[NP];
     Outs *O[NP];
     unsigned act[NP], full[NP];
     bool all_on = true, any = false;
     size_t m = SIZE_MAX, longest = 0;
-    alignas(64) uint64_t lv[L];
+    alignas(64) uint64_t lv[8 * NP];
     for (int p = 0; p < NP; p++) {
         R[p] = P[p]->st->L.r; O[p] = &P[p]->st->L.o;
         act[p] = 0; full[p] = (1u << P[p]->st->count) - 1u;
@@ -338,17 +298,17 @@ NB_TARGET NB_INLINE void feed_groups_np(RangeX8 *const *P, const uint64_t *rows,
     }
     size_t pos = 0;
     static const size_t ahead_groups = getenv("NBLIC_AMD_PREFETCH_GROUPS") ? size_t(atoi(getenv("NBLIC_AMD_PREFETCH_GROUPS"))) : 2;
-    const size_t ahead = ahead_groups * kGroupWords * L;          // words; 2 groups = 3.3 KB per pack pair
+    const size_t ahead = ahead_groups * kGroupWords * L;          // words; 2 groups = 1.7 KB per pack
     if (all_on && any) {
         for (; pos + kGroupBins <= m; pos += kGroupBins) {
-            const uint64_t *grp = rows + (pos >> 6) * (kGroupWords * L);
+            const size_t grp = (pos >> 6) * (kGroupWords * L);            // word offset of the group in every pack's stream
             for (int j = 0; j < int(kGroupWords); j++) {
-                const uint64_t *row = grp + L * j;
+                const size_t row = grp + L * j;
                 __m512i g[NP];
 #pragma GCC unroll 3
                 for (int p = 0; p < NP; p++) {
-                    _mm_prefetch((const char *)(row + ahead + 8 * p), _MM_HINT_T0);
-                    g[p] = _mm512_load_si512((const void *)(row + 8 * p));
+                    _mm_prefetch((const char *)(rows_p[p] + row + ahead), _MM_HINT_T0);
+                    g[p] = _mm512_load_si512((const void *)(rows_p[p] + row));
                 }
 #pragma GCC unroll 3
                 for (int p = 0; p < NP; p++) step_all<0x1000>(R[p], *O[p], g[p]);
@@ -361,31 +321,32 @@ NB_TARGET NB_INLINE void feed_groups_np(RangeX8 *const *P, const uint64_t *rows,
             }
             __m512i bins[NP];
 #pragma GCC unroll 3
-            for (int p = 0; p < NP; p++) bins[p] = _mm512_load_si512((const void *)(grp + L * 12 + 8 * p));
+            for (int p = 0; p < NP; p++) bins[p] = _mm512_load_si512((const void *)(rows_p[p] + grp + L * 12));
             __m512i bit = _mm512_set1_epi64(1ll << 52);
             for (int e = 0; e < 12; e++) {
-                const uint64_t *row = grp + L * e;
+                const size_t row = grp + L * e;
 #pragma GCC unroll 3
                 for (int p = 0; p < NP; p++)
-                    step_core(R[p], *O[p], _mm512_srli_epi64(_mm512_load_si512((const void *)(row + 8 * p)), 52), _mm512_testn_epi64_mask(bins[p], bit));
+                    step_core(R[p], *O[p], _mm512_srli_epi64(_mm512_load_si512((const void *)(rows_p[p] + row)), 52), _mm512_testn_epi64_mask(bins[p], bit));
                 bit = _mm512_slli_epi64(bit, 1);
             }
         }
     }
     // whatever is left (lanes of different length, a pack with idle lanes): one bin at a time, lanes masked by their length
     for (; pos < longest; pos++) {
-        const uint64_t *grp = rows + (pos >> 6) * (kGroupWords * L);
+        const size_t grp0 = (pos >> 6) * (kGroupWords * L);
         const size_t k = pos & 63;
         const __m512i at = _mm512_set1_epi64((long long)pos);
         for (int p = 0; p < NP; p++) {
             const __mmask8 kk = _mm512_cmplt_epu64_mask(at, _mm512_load_si512((const void *)(lv + 8 * p)));
             if (!kk) continue;
+            const uint64_t *grp = rows_p[p] + grp0;
             __m512i ev;
             if (k < 52) {
-                ev = _mm512_srl_epi64(_mm512_load_si512((const void *)(grp + L * (k >> 2) + 8 * p)), _mm_cvtsi64_si128((long long)(13 * (k & 3))));
+                ev = _mm512_srl_epi64(_mm512_load_si512((const void *)(grp + L * (k >> 2))), _mm_cvtsi64_si128((long long)(13 * (k & 3))));
             } else {
-                const __m512i bin = _mm512_srl_epi64(_mm512_load_si512((const void *)(grp + L * 12 + 8 * p)), _mm_cvtsi64_si128((long long)(52 + (k - 52))));
-                ev = _mm512_or_si512(_mm512_srli_epi64(_mm512_load_si512((const void *)(grp + L * (k - 52) + 8 * p)), 52),
+                const __m512i bin = _mm512_srl_epi64(_mm512_load_si512((const void *)(grp + L * 12)), _mm_cvtsi64_si128((long long)(52 + (k - 52))));
+                ev = _mm512_or_si512(_mm512_srli_epi64(_mm512_load_si512((const void *)(grp + L * (k - 52))), 52),
                                      _mm512_and_si512(_mm512_slli_epi64(bin, 12), _mm512_set1_epi64(0x1000)));
             }
             step<0x1000>(R[p], *O[p], ev, kk);
@@ -394,13 +355,11 @@ NB_TARGET NB_INLINE void feed_groups_np(RangeX8 *const *P, const uint64_t *rows,
     for (int p = 0; p < NP; p++) P[p]->st->L.r = R[p];
 }
 
-NB_TARGET void feed_pair_groups(RangeX8 &A, RangeX8 &B, const uint64_t *rows, const size_t *len) {
-    RangeX8 *const P[2] = {&A, &B};
-    feed_groups_np<2>(P, rows, len);
-}
-NB_TARGET void feed_triple_groups(RangeX8 &A, RangeX8 &B, RangeX8 &C, const uint64_t *rows, const size_t *len) {
-    RangeX8 *const P[3] = {&A, &B, &C};
-    feed_groups_np<3>(P, rows, len);
+// one, two or three packs, each from a row stream of its own
+NB_TARGET void feed_packs(RangeX8 *const *P, int n_packs, const uint64_t *const *rows_p, const size_t *len) {
+    if (n_packs == 1) feed_groups_np<1>(P, rows_p, len);
+    else if (n_packs == 2) feed_groups_np<2>(P, rows_p, len);
+    else if (n_packs == 3) feed_groups_np<3>(P, rows_p, len);
 }
 
 // leftovers of the byte accumulators, then the 4-byte flush of lo (NBLIC.c:576-586)

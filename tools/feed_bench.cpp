@@ -1,4 +1,4 @@
-// feed_bench.cpp -- host range-coder pack pair fed from 16-bit rows and from 13-bit groups (no GPU).
+// feed_bench.cpp -- host range-coder packs fed from 8-lane rows of 13-bit groups, one / two / three packs in lock-step (no GPU).
 //   g++ -O2 -std=c++17 tools/feed_bench.cpp nblic-image-compression_amd/csrc/build/range_coder_x8.o -o /tmp/feed_bench
 #include <chrono>
 #include <cstdio>
@@ -25,41 +25,28 @@ int main(int argc, char **argv) {
         }
         printf("records from %s* (%d files)\n", argv[2], have);
     }
-    uint64_t *r16 = (uint64_t *)aligned_alloc(64, n / 4 * 16 * 8), *r13 = (uint64_t *)aligned_alloc(64, group_words(n) * 8);
-    memset(r16, 0, n / 4 * 16 * 8); memset(r13, 0, group_words(n) * 8);
-    size_t len[16];
-    for (int l = 0; l < 16; l++) {
-        len[l] = n;
-        for (size_t i = 0; i < n; i++) r16[16 * (i >> 2) + l] |= uint64_t(s[l][i]) << (16 * (i & 3));
-        pack_groups_host(r13, l, s[l].data(), n);
+    uint64_t *rows[3];
+    size_t len[24];
+    for (int p = 0; p < 3; p++) {
+        rows[p] = (uint64_t *)aligned_alloc(64, group_words(n) * 8);
+        memset(rows[p], 0, group_words(n) * 8);
+        for (int l = 0; l < 8; l++) { len[8 * p + l] = n; pack_groups_host(rows[p], l, s[8 * p + l].data(), n); }
     }
-    uint64_t *r24 = (uint64_t *)aligned_alloc(64, group_words(n, 24) * 8);
-    memset(r24, 0, group_words(n, 24) * 8);
-    size_t len24[24];
-    for (int l = 0; l < 24; l++) { len24[l] = n; pack_groups_host(r24, l, s[l].data(), n, 24); }
     std::vector<std::vector<uint8_t>> out(24, std::vector<uint8_t>(2 * n + 64));
-    uint8_t *outs[24]; size_t caps[24], la[24], lb[24], lc[24];
+    uint8_t *outs[24]; size_t caps[24], lens[3][24];
     for (int l = 0; l < 24; l++) { outs[l] = out[l].data(); caps[l] = out[l].size(); }
     for (int rep = 0; rep < 3; rep++) {
-        for (int form = 0; form < 2; form++) {
-            RangeX8 a, b;
-            a.begin(8, outs, caps); b.begin(8, outs + 8, caps + 8);
+        for (int np = 1; np <= 3; np++) {
+            RangeX8 x[3];
+            RangeX8 *packs[3] = {&x[0], &x[1], &x[2]};
+            for (int p = 0; p < np; p++) x[p].begin(8, outs + 8 * p, caps + 8 * p);
             auto t0 = std::chrono::steady_clock::now();
-            if (form == 0) feed_pair_rows(a, b, r16, len); else feed_pair_groups(a, b, r13, len);
+            feed_packs(packs, np, rows, len);
             const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            a.end(form ? lb : la); b.end((form ? lb : la) + 8);
-            printf("%s: %.0f Mbins/s\n", form ? "13-bit groups" : "16-bit rows  ", 16.0 * n / dt / 1e6);
+            for (int p = 0; p < np; p++) x[p].end(lens[np - 1] + 8 * p);
+            printf("%d pack%s: %.0f Mbins/s\n", np, np > 1 ? "s" : " ", 8.0 * np * n / dt / 1e6);
         }
-        {
-            RangeX8 a, b, c;
-            a.begin(8, outs, caps); b.begin(8, outs + 8, caps + 8); c.begin(8, outs + 16, caps + 16);
-            auto t0 = std::chrono::steady_clock::now();
-            feed_triple_groups(a, b, c, r24, len24);
-            const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            a.end(lc); b.end(lc + 8); c.end(lc + 16);
-            printf("13-bit groups, three packs: %.0f Mbins/s\n", 24.0 * n / dt / 1e6);
-        }
-        printf("same lengths: %d %d\n", !memcmp(la, lb, 16 * sizeof(size_t)), !memcmp(la, lc, 16 * sizeof(size_t)));
+        printf("same lengths: %d %d\n", !memcmp(lens[0], lens[1], 8 * sizeof(size_t)), !memcmp(lens[1], lens[2], 16 * sizeof(size_t)));
     }
     return 0;
 }
