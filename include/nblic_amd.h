@@ -359,6 +359,24 @@ void nblic_amd_debug_takes(nblic_amd_ctx *ctx, long takes[25]);
 long nblic_amd_debug_pack_rows(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *imgs, const int *heights, const int *widths,
                                unsigned long long *rows, size_t rows_words, unsigned short *const *coded, unsigned int *n_bins);
 
+/* Debug hook used by the device coder's tests: ONE launch of the range coder's kernel (csrc/device_coder.hip, one wave
+ * lane per job) on jobs the caller supplies, 1..4096 of them.  Job k is
+ *   an image on its own  (records[k] != NULL): record_words[k] u16 records, prob | bin << 15, which the caller has padded
+ *     to the end of the last 512-byte window of its n_bins[k] bins (an empty stream: to one whole window);
+ *   a lane of a pack     (records[k] == NULL): lane lane_of[k] (0..7) of pack pack_of[k] (0..n_packs-1); pack p is
+ *     pack_words[p] 64-bit words, a multiple of 104, rows[(13 g + j) * 8 + lane] as above, and holds at least the
+ *     13 * ceil(n_bins[k] / 64) word rows of the job's groups.
+ * Records and rows are uploaded verbatim (256-byte aligned): every word the kernel reads is the caller's.  Job k codes
+ * n_bins[k] bins into a device buffer of caps[k] bytes that is followed by a guard of at least 64 patterned bytes;
+ * lens[k] is the byte count (flush included) and outs[k], caps[k] bytes, receives them -- or lens[k] is -1: caps[k] was
+ * too small.  Returns 0; -1 for arguments it refuses (a null pointer, a lane above 7, a pack index out of range, rows or
+ * records shorter than stated above; nothing is launched); -2 when a HIP call failed; -3 when a byte outside what the
+ * kernel may write -- a guard, or an output's bytes beyond the length it reported -- has changed.                      */
+int nblic_amd_debug_device_code(nblic_amd_ctx *ctx, int n_jobs, const unsigned short *const *records, const size_t *record_words,
+                                const int *pack_of, const int *lane_of, int n_packs, const unsigned long long *const *pack_rows,
+                                const size_t *pack_words, const unsigned int *n_bins, const unsigned int *caps,
+                                unsigned char *const *outs, long *lens);
+
 /* Device self-test of the wave primitives the chain kernels rely on (DPP prefix sum against the
  * shuffle formulation).  Returns the number of mismatching lanes (0 = pass) or -1.           */
 int nblic_amd_selftest(nblic_amd_ctx *ctx);

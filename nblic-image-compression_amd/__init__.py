@@ -37,7 +37,7 @@ _lib = None
 EXPORTS = (
     "NBLICcompress", "NBLICdecompress", "QNBLICcompress", "QNBLICdecompress", "QNBLICcompressMultiThread",
     "nblic_amd_create", "nblic_amd_create_ex", "nblic_amd_destroy", "nblic_amd_encode_batch", "nblic_amd_encode_batch_begin", "nblic_amd_encode_batch_end", "nblic_amd_qencode_batch", "nblic_amd_set_max_pixels",
-    "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage", "nblic_amd_debug_live", "nblic_amd_debug_takes", "nblic_amd_debug_pack_rows",
+    "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage", "nblic_amd_debug_live", "nblic_amd_debug_takes", "nblic_amd_debug_pack_rows", "nblic_amd_debug_device_code",
     "nblic_amd_encode_batch_modes", "nblic_amd_decode_batch", "nblic_amd_serial_selftest",
     "nblic_amd_set_serial_rows", "nblic_amd_serial_launches", "nblic_amd_lsq_redo_counts", "nblic_amd_serial_plan", "nblic_amd_lsq_probe", "nblic_amd_set_feed_chunk", "nblic_amd_last_fed_bytes",
     "nblic_amd_stream_begin", "nblic_amd_stream_resume", "nblic_amd_stream_run", "nblic_amd_stream_checkpoint", "nblic_amd_stream_progress",
@@ -219,6 +219,10 @@ def load_library() -> C.CDLL:
         lib.nblic_amd_debug_pack_rows.restype = C.c_long
         lib.nblic_amd_debug_pack_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), ip, ip, C.c_void_p, C.c_size_t,
                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_uint)]
+    if hasattr(lib, "nblic_amd_debug_device_code"):
+        lib.nblic_amd_debug_device_code.restype = C.c_int
+        lib.nblic_amd_debug_device_code.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), ip, ip, C.c_int, C.POINTER(C.c_void_p),
+                                                    C.POINTER(C.c_size_t), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_void_p), C.POINTER(C.c_long)]
     lib.nblic_amd_selftest.restype = C.c_int
     lib.nblic_amd_selftest.argtypes = [C.c_void_p]
     lib.nblic_amd_syn1.restype = None
@@ -776,6 +780,42 @@ class Context:
         if words < 0:
             raise RuntimeError("nblic_amd_debug_pack_rows failed")
         return rows[:words].copy(), [coded[i][: nb[i]].copy() for i in range(k)]
+
+    def debug_device_code(self, jobs: Sequence[tuple], packs: Sequence[np.ndarray] = ()) -> List[Optional[bytes]]:
+        """One launch of the device range coder on the caller's own jobs (``nblic_amd_debug_device_code``).  A job is
+        ``(records, n, cap)`` -- an image on its own: u16 records the caller has padded to the end of the last 512-byte
+        window of its ``n`` bins -- or ``((pack, lane), n, cap)``: lane ``lane`` of ``packs[pack]``, uint64 rows as
+        ``pack_groups_host`` lays them out.  Everything is handed over as it is: the library does the refusing
+        (``ValueError``).  Returns per job the coder's bytes, or None where ``cap`` was too small; raises
+        ``DeviceCoderGuardError`` when the kernel wrote a byte it may not write."""
+        k = len(jobs)
+        rows = [np.ascontiguousarray(p, np.uint64) for p in packs]
+        recs, rp, rw, po, lo = [], (C.c_void_p * k)(), (C.c_size_t * k)(), (C.c_int * k)(), (C.c_int * k)()
+        for i, (src, _, _) in enumerate(jobs):
+            po[i], lo[i] = -1, -1
+            if isinstance(src, tuple):
+                po[i], lo[i] = int(src[0]), int(src[1])
+            elif src is not None:
+                recs.append(np.ascontiguousarray(src, np.uint16))
+                rp[i], rw[i] = recs[-1].ctypes.data, recs[-1].size
+        nn = (C.c_uint * k)(*[int(j[1]) for j in jobs])
+        caps = (C.c_uint * k)(*[int(j[2]) for j in jobs])
+        outs = [np.empty(max(int(j[2]), 1), np.uint8) for j in jobs]
+        lens = (C.c_long * k)()
+        rc = self.lib.nblic_amd_debug_device_code(
+            self.handle, k, rp, rw, po, lo, len(rows), (C.c_void_p * len(rows))(*[C.c_void_p(r.ctypes.data) for r in rows]),
+            (C.c_size_t * len(rows))(*[r.size for r in rows]), nn, caps, (C.c_void_p * k)(*[C.c_void_p(o.ctypes.data) for o in outs]), lens)
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_device_code refused its arguments")
+        if rc == -3:
+            raise DeviceCoderGuardError("nblic_amd_debug_device_code: the kernel wrote outside its outputs, or beyond a length it reported")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_device_code failed")
+        return [None if lens[i] < 0 else outs[i][: lens[i]].tobytes() for i in range(k)]
+
+
+class DeviceCoderGuardError(RuntimeError):
+    """``Context.debug_device_code``: a byte outside what the device coder may write has changed."""
 
 
 FRONTS = {"serial": 0, "staged": 1}       # nblic_amd_stream_set_front

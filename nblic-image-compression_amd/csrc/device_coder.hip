@@ -8,7 +8,10 @@
 // only the 0.12 bytes per bin it produces do).  The pipeline (pipeline.hip) therefore uses it as a
 // high-latency SUPPLEMENT to the host coder threads: when the backlog of finished images is deep
 // enough that the host would need longer than a pack's latency to work through it, 64 images are
-// handed to a wave.  Same bytes either way (tests/test_gpu_parity.py::test_device_coder_*).
+// handed to a wave.  Same bytes either way: tests/test_device_coder.py runs this kernel alone, on jobs of its own
+// making, through nblic_amd_debug_device_code, and compares every lane with the host coder (lengths around the unroll,
+// the group and the round, every pack size and lane, ragged and partial waves, capacities that fit exactly and miss by
+// a byte); which images the pipeline deals to a wave is a race (tests/test_gpu_parity.py::test_device_coder_*).
 //
 // Memory traffic is staged exactly like the chain kernels' (kernels_e1.hip run_lane_streams): per round
 // the wave fetches, for each of its 64 streams, the aligned 512-byte window holding that stream's next

@@ -2845,6 +2845,87 @@ long nblic_amd_debug_pack_rows(nblic_amd_ctx *c, int n_images, const unsigned ch
     return words;
 }
 
+int nblic_amd_debug_device_code(nblic_amd_ctx *c, int n_jobs, const unsigned short *const *records, const size_t *record_words,
+                                const int *pack_of, const int *lane_of, int n_packs, const unsigned long long *const *pack_rows,
+                                const size_t *pack_words, const unsigned int *n_bins, const unsigned int *caps,
+                                unsigned char *const *outs, long *lens) {
+    constexpr int kMaxJobs = 4096;
+    constexpr size_t kMaxBytes = size_t(1) << 30, kGuard = 64, kGroupWords = PackRows::kWordsPerGroup * PackRows::kLanes;
+    constexpr uint8_t kPattern = 0xA5;
+    if (!c || n_jobs < 1 || n_jobs > kMaxJobs || n_packs < 0 || n_packs > kMaxJobs) return -1;
+    if (!records || !record_words || !pack_of || !lane_of || !n_bins || !caps || !outs || !lens) return -1;
+    if (n_packs > 0 && (!pack_rows || !pack_words)) return -1;
+    auto align = [](size_t v) { return (v + 255) & ~size_t(255); };
+    // the input arena: every pack's rows, then every single image's records, each 256-byte aligned
+    const size_t nj = size_t(n_jobs);
+    std::vector<size_t> pack_at(size_t(n_packs) + 1), in_at(nj), out_at(nj);
+    size_t in_bytes = 0, out_bytes = kGuard;                                  // a guard in front of the first output too
+    for (int p = 0; p < n_packs; p++) {
+        if (!pack_rows[p] || pack_words[p] % kGroupWords != 0 || pack_words[p] > kMaxBytes / 8) return -1;
+        pack_at[size_t(p)] = in_bytes;
+        in_bytes += align(pack_words[p] * sizeof(uint64_t) + 1);              // (+ 1: an empty pack still has an address of its own)
+    }
+    for (int k = 0; k < n_jobs; k++) {
+        const size_t n = n_bins[k];
+        if (records[k]) {
+            const size_t need = std::max<size_t>((n + 255) / 256, 1) * 256;   // whole 512-byte windows; an empty stream has one
+            if (record_words[k] < need || record_words[k] > kMaxBytes / 2) return -1;
+            in_at[size_t(k)] = in_bytes;
+            in_bytes += align(record_words[k] * sizeof(uint16_t));
+        } else {
+            if (pack_of[k] < 0 || pack_of[k] >= n_packs || lane_of[k] < 0 || lane_of[k] >= int(PackRows::kLanes)) return -1;
+            if (pack_words[pack_of[k]] < PackRows::words(n)) return -1;
+        }
+        if (caps[k] > 0 && !outs[k]) return -1;
+        out_at[size_t(k)] = out_bytes;
+        out_bytes += (size_t(caps[k]) + kGuard + 63) & ~size_t(63);           // the output, then 64..127 bytes of guard
+        if (in_bytes > kMaxBytes || out_bytes > kMaxBytes) return -1;
+    }
+    std::lock_guard<std::mutex> g(c->api);
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    Stream st;
+    DevBuf<uint8_t> d_in, d_out; DevBuf<RcJob> d_jobs; DevBuf<uint32_t> d_lens;
+    Pinned<RcJob> h_jobs; Pinned<uint32_t> h_lens;
+    std::vector<uint8_t> h_in(std::max<size_t>(in_bytes, 256), 0), h_out(out_bytes, kPattern);
+    for (int p = 0; p < n_packs; p++) memcpy(h_in.data() + pack_at[size_t(p)], pack_rows[p], pack_words[p] * sizeof(uint64_t));
+    for (int k = 0; k < n_jobs; k++) if (records[k]) memcpy(h_in.data() + in_at[size_t(k)], records[k], record_words[k] * sizeof(uint16_t));
+    bool ok = st.create(hipStreamNonBlocking) == hipSuccess && d_in.alloc(h_in.size()) == hipSuccess && d_out.alloc(out_bytes) == hipSuccess &&
+              d_jobs.alloc(size_t(n_jobs)) == hipSuccess && d_lens.alloc(size_t(n_jobs)) == hipSuccess &&
+              h_jobs.alloc(size_t(n_jobs)) == hipSuccess && h_lens.alloc(size_t(n_jobs)) == hipSuccess;
+    if (ok) {
+        for (int k = 0; k < n_jobs; k++) {
+            const bool packed = !records[k];
+            h_jobs[k] = RcJob{packed ? nullptr : reinterpret_cast<const uint16_t *>(d_in.get() + in_at[size_t(k)]),
+                              packed ? reinterpret_cast<const uint64_t *>(d_in.get() + pack_at[size_t(pack_of[k])]) : nullptr, packed ? uint32_t(lane_of[k]) : 0u,
+                              d_out.get() + out_at[size_t(k)], d_lens.get() + k, n_bins[k], caps[k]};
+            h_lens[k] = 0xFFFFFFFEu;                                          // neither a length nor "did not fit": the kernel must write every one
+        }
+        ok = hipMemcpyAsync(d_in, h_in.data(), h_in.size(), hipMemcpyHostToDevice, st) == hipSuccess &&
+             hipMemcpyAsync(d_out, h_out.data(), out_bytes, hipMemcpyHostToDevice, st) == hipSuccess &&
+             hipMemcpyAsync(d_lens, h_lens, size_t(n_jobs) * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
+             hipMemcpyAsync(d_jobs, h_jobs, size_t(n_jobs) * sizeof(RcJob), hipMemcpyHostToDevice, st) == hipSuccess &&
+             device_range_code(d_jobs, n_jobs, st) &&
+             hipMemcpyAsync(h_lens, d_lens, size_t(n_jobs) * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(h_out.data(), d_out, out_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+        ok = hipStreamSynchronize(st) == hipSuccess && ok;
+    }
+    if (!ok) return -2;
+    // everything the kernel may not have written still holds the pattern: guards, and an output beyond its reported length
+    bool intact = true;
+    size_t at = 0;
+    auto pattern_to = [&](size_t end) { for (; at < end; at++) intact = intact && h_out[at] == kPattern; };
+    for (int k = 0; k < n_jobs; k++) {
+        const uint32_t len = h_lens[k];
+        if (len != 0xFFFFFFFFu && len > caps[k]) { intact = false; lens[k] = -1; continue; }      // a length beyond cap (or none written)
+        pattern_to(out_at[size_t(k)]);
+        lens[k] = len == 0xFFFFFFFFu ? -1 : long(len);
+        if (len != 0xFFFFFFFFu) { memcpy(outs[k], h_out.data() + at, len); at += len; }
+        else at += caps[k];                                                   // did not fit: the kernel wrote what it liked below cap
+    }
+    pattern_to(out_bytes);
+    return intact ? 0 : -3;
+}
+
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
 
 void nblic_amd_set_max_pixels(nblic_amd_ctx *c, long max_pixels) {

@@ -608,7 +608,7 @@ def test_device_coder_supplements_host_threads(pkg, oracle):
     """The range-coder stage on the GPU (one lane per image, 64 images per wave) next to ONE host coder
     thread: with a deep queue of finished images the pack threads take the newest 64 at a time.  Every
     stream -- host-coded or device-coded, all sizes and contents, images that end at very different bins
-    inside one wave, an output buffer that is too small -- must be the oracle's, byte for byte."""
+    inside one wave -- must be the oracle's, byte for byte; and an output buffer that is too small fails its own image alone."""
     rng = np.random.default_rng(41)
     imgs = []
     for k in range(420):
@@ -622,11 +622,23 @@ def test_device_coder_supplements_host_threads(pkg, oracle):
         got = ctx.encode_batch(imgs)
         stats = ctx.device_coder_stats()
         modes = ctx.encode_modes(imgs[:200], [2] * 200, [1] * 200)[0]      # serial-mode images go through the same queue
+        # the same batch again, image 333's buffer one byte short (whether a host thread or the wave gets it is a race: the
+        # kernel's own capacity checks are in test_device_coder.py): the call fails, that image has no length, every
+        # other stream is whole, and the context goes on
+        short = 333
+        outs = [np.empty(pkg.out_capacity(*i.shape) if k != short else len(want[k]) - 1, np.uint8) for k, i in enumerate(imgs)]
+        args = pkg._batch_args([i.ctypes.data for i in imgs], [i.shape for i in imgs], outs)
+        rc = ctx.lib.nblic_amd_encode_batch(ctx.handle, len(imgs), args[0], 0, *args[1:])
+        lens = list(args[5])
+        after = ctx.encode_batch(imgs[300:364])
     finally:
         ctx.close()
     assert got == want
     assert modes == [oracle.encode(i, 2, 1)[0] for i in imgs[:200]]
     assert stats["images"] >= 64 and stats["packs"] >= 1, stats           # the device coder did take part
+    assert rc != 0 and lens[short] < 0
+    assert [o[:n].tobytes() for k, (o, n) in enumerate(zip(outs, lens)) if k != short] == want[:short] + want[short + 1:]
+    assert after == want[300:364]
 
 
 def test_serial_paths_at_extreme_widths_and_bad_streams(gpu_ctx, pkg, oracle):      # gpu_ctx first: torch must initialise HIP before the library does

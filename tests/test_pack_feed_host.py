@@ -4,12 +4,10 @@ records."""
 import numpy as np
 import pytest
 
+from coder_inputs import records as _records, runs
+
 CHUNK = 4096
 LENGTHS = (1, 51, 52, 53, 63, 64, 65, 4095, 4096, 4097)
-
-
-def _records(rng, n):
-    return rng.integers(1, 4096, n).astype(np.uint16) | (rng.integers(0, 2, n).astype(np.uint16) << 15)
 
 
 def _deal(streams, n_packs):
@@ -74,18 +72,6 @@ def test_lanes_end_in_different_groups_and_chunks(feed):
 
 def test_long_runs_of_extreme_probabilities(feed):
     """Probabilities 1 and 4095 in long runs: several bytes leave the coder per step."""
-    def runs(seed, n):
-        r = np.random.default_rng(seed)
-        out = np.empty(n, np.uint16)
-        at = 0
-        while at < n:
-            k = int(r.integers(40, 900))
-            p, b = (1, 1) if r.integers(0, 2) else (4095, 0)
-            if r.integers(0, 4) == 0:
-                b ^= 1                                     # the unlikely bin now and then: long carries of renormalisation
-            out[at:at + k] = p | (b << 15)
-            at += k
-        return out
     packs = [[np.full(5000, 1 | (1 << 15), np.uint16), np.full(4097, 4095, np.uint16), runs(1, 9000), runs(2, 4096), np.full(6000, 1, np.uint16)],
              [runs(3, 12000), np.full(3000, 4095 | (1 << 15), np.uint16), runs(4, 65)]]
     got, want = feed(packs)
