@@ -308,6 +308,42 @@ int nblic_amd_decode_indexed(nblic_amd_ctx *ctx, const unsigned char *stream, si
 int nblic_amd_decode_rows(nblic_amd_ctx *ctx, const unsigned char *stream, size_t stream_bytes, const void *index, size_t index_bytes,
                           int row0, int row1, unsigned char *out, size_t cap);
 
+/* INDEXED BATCH ENCODE: many lossless -n0 -e1 images AND their seek indexes in one call.  Image k gets its byte-exact
+ * .nblic stream and, when 1 <= every_rows[k] < heights[k], the seek index nblic_amd_index_build(every_rows[k]) would make
+ * for that stream, byte for byte -- without the serial decode index_build costs.  A group of images is stepped through
+ * row bands together: each launch sequence carries one band of every image of the group (images of different heights,
+ * widths and every_rows, at different rows), a slot whose image has ended takes the next image of the batch, and the
+ * bins of a step are range-coded on worker threads (as many as the context has coder threads) while the next step is on
+ * the GPU.  The device workspace is one band per slot, whatever the heights; it belongs to the context and only grows.
+ *   every_rows[k]   0, or >= heights[k]: the image is encoded with no index and index_lens[k] = 0 (index_build refuses
+ *                   that geometry too).  A negative value refuses the whole call.
+ *   indexes         NULL, or an array whose entries may be NULL: that image's index is not wanted (index_lens[k] = 0).
+ *                   index_caps and index_lens are required unless indexes is NULL.  nblic_amd_index_bytes gives the size.
+ *   band_rows       rows per band; <= 0 sizes it as nblic_amd_stream_begin does.  A band never crosses a multiple of the
+ *                   image's every_rows while its index is being written.  No choice of band_rows shows in the bytes.
+ *   per image       out_lens[k] = -1 when out_caps[k] is too small or the size is refused (limits above);
+ *                   index_lens[k] = -1 when index_caps[k] is too small -- the stream is still delivered -- or the stream
+ *                   failed.  The call returns -1 if any entry is -1, 0 otherwise; the other images are unaffected.
+ *   whole call      -1, nothing launched: n_images < 1, a null array or image or output, a negative every_rows, a context
+ *                   without a usable device.
+ * Lossless -e1 only: near-lossless and efforts 2 / 3 need the serial model stage, a reconstruction and the least-squares
+ * statistics per image (nblic_amd_stream_* writes their indexes, one image per object).
+ * The call takes groups of the context as a band encoder does -- up to min(groups, ceil(n_images / group size)) of them,
+ * each for the whole call -- so it runs next to batches, band coders and decoders of the same context, and blocks while
+ * no group is free.  imgs_on_device as for nblic_amd_encode_batch; host planes are hashed where they are (lossless: the
+ * reconstruction is the input), device planes have each band's rows copied back for the index's row hash.
+ * nblic_amd_index_bytes: the size of the index of a stream of this geometry; host only, no device, no context.  kind 0
+ * NBLIC (effort 1..3), 1 QNBLIC (effort 0).  -1 for every_rows < 1 or >= height, or fields out of range.
+ * nblic_amd_indexed_batch_split (reporting): the context's last indexed batch summed over its group steps -- ms[0] front
+ * halves, [1] totals read-back, [2] back halves and entry records, [3] copies to the host (GPU time, milliseconds),
+ * [4] the drivers' wait for the coder threads (host milliseconds); returns the number of group steps, -1 without a context. */
+int nblic_amd_encode_batch_indexed(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *imgs, int imgs_on_device,
+                                   const int *heights, const int *widths, const int *every_rows, int band_rows,
+                                   unsigned char *const *outs, const size_t *out_caps, long *out_lens,
+                                   unsigned char *const *indexes, const size_t *index_caps, long *index_lens);
+long nblic_amd_index_bytes(int kind, int height, int width, int effort, int every_rows);
+long nblic_amd_indexed_batch_split(nblic_amd_ctx *ctx, double ms[5]);
+
 /* The reference's decoders take no stream length (src/NBLIC.h:72, src/QNBLIC.h:16).  NBLICdecompress / QNBLICdecompress
  * therefore run a band decoder (nblic_amd_dstream above, band_rows as set by nblic_amd_set_serial_rows) and fetch the
  * caller's stream ON DEMAND in steps of `bytes` (default 1 MiB, at least 4096): the decoder stops in front of a row when

@@ -46,6 +46,7 @@ EXPORTS = (
     "nblic_amd_dstream_run", "nblic_amd_dstream_progress", "nblic_amd_dstream_checkpoint", "nblic_amd_dstream_end",
     "nblic_amd_index_check", "nblic_amd_index_build", "nblic_amd_decode_indexed", "nblic_amd_decode_rows",
     "nblic_amd_stream_set_index", "nblic_amd_stream_index", "nblic_amd_set_index_round", "nblic_amd_stream_set_front",
+    "nblic_amd_encode_batch_indexed", "nblic_amd_index_bytes", "nblic_amd_indexed_batch_split",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -188,6 +189,15 @@ def load_library() -> C.CDLL:
     lib.nblic_amd_decode_indexed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     lib.nblic_amd_decode_rows.restype = C.c_int
     lib.nblic_amd_decode_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    if hasattr(lib, "nblic_amd_encode_batch_indexed"):             # (an older build loaded through NBLIC_AMD_LIB has none of the three)
+        lib.nblic_amd_encode_batch_indexed.restype = C.c_int
+        lib.nblic_amd_encode_batch_indexed.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_int, ip, ip, ip, C.c_int,
+                                                       C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_long),
+                                                       C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_long)]
+        lib.nblic_amd_index_bytes.restype = C.c_long
+        lib.nblic_amd_index_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.nblic_amd_indexed_batch_split.restype = C.c_long
+        lib.nblic_amd_indexed_batch_split.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.nblic_amd_enable_timing.restype = None
     lib.nblic_amd_enable_timing.argtypes = [C.c_void_p, C.c_int]
     lib.nblic_amd_stage_times.restype = C.c_int
@@ -230,6 +240,22 @@ def load_library() -> C.CDLL:
     lib.nblic_amd_version.restype = C.c_char_p
     _lib = lib
     return lib
+
+
+def index_bytes(kind: int, h: int, w: int, effort: int, every_rows: int) -> int:
+    """Size of the seek index of a stream of this geometry (``nblic_amd_index_bytes``; kind 0 NBLIC, 1 QNBLIC); host only.
+    -1: ``every_rows`` outside [1, h), or a field out of range."""
+    return int(load_library().nblic_amd_index_bytes(int(kind), int(h), int(w), int(effort), int(every_rows)))
+
+
+def _every_rows_list(every_rows, k: int) -> List[int]:
+    """``every_rows`` of an indexed batch of k images as a list: an int for all, or one per image; no negative value."""
+    every = [int(every_rows)] * k if np.isscalar(every_rows) else [int(r) for r in every_rows]
+    if len(every) != k:
+        raise ValueError(f"every_rows names {len(every)} images, the batch has {k}")
+    if any(r < 0 for r in every):
+        raise ValueError("every_rows must not be negative (0: no index for that image)")
+    return every
 
 
 def out_capacity(h: int, w: int) -> int:
@@ -705,6 +731,51 @@ class Context:
         if rc != 0:
             raise RuntimeError(f"nblic_amd_encode_batch_end failed (lengths {list(lens[:8])}...)")
         return ticket["outs"], lens
+
+    def encode_indexed_ptrs(self, ptrs: Sequence[int], shapes: Sequence[Tuple[int, int]], on_device: bool, every_rows, band_rows: int = 0,
+                            out_caps: Optional[Sequence[int]] = None, index_caps: Optional[Sequence[int]] = None):
+        """``nblic_amd_encode_batch_indexed`` on planes given as raw addresses (host or device), with explicit buffer
+        capacities if wanted (default: enough).  Returns (rc, streams, indexes): per image the stream and the index as
+        bytes, ``None`` where the library reported -1; an image that gets no index (``every_rows`` 0 or >= its height)
+        has ``None`` for its index too."""
+        k = len(ptrs)
+        every = _every_rows_list(every_rows, k)
+        need = [index_bytes(0, h, w, 1, r) for (h, w), r in zip(shapes, every)]
+        outs = [np.empty(out_capacity(h, w) if out_caps is None else int(out_caps[i]), np.uint8) for i, (h, w) in enumerate(shapes)]
+        idxs = [np.empty(max(n, 1) if index_caps is None else max(int(index_caps[i]), 1), np.uint8) for i, n in enumerate(need)]
+        imgs, hs, ws, op, caps, lens = _batch_args(ptrs, shapes, outs)
+        xp = (C.c_void_p * k)(*[C.c_void_p(x.ctypes.data) for x in idxs])
+        xcaps = (C.c_size_t * k)(*[x.size if index_caps is None else int(index_caps[i]) for i, x in enumerate(idxs)])
+        xlens = (C.c_long * k)()
+        rc = int(self.lib.nblic_amd_encode_batch_indexed(self.handle, k, imgs, int(on_device), hs, ws, (C.c_int * k)(*every), int(band_rows),
+                                                         op, caps, lens, xp, xcaps, xlens))
+        streams = [o[:n].tobytes() if n >= 0 else None for o, n in zip(outs, lens)]
+        indexes = [x[:n].tobytes() if n > 0 else None for x, n in zip(idxs, xlens)]
+        return rc, streams, indexes
+
+    def encode_batch_indexed(self, imgs, every_rows, band_rows: int = 0) -> List[Tuple[Optional[bytes], Optional[bytes]]]:
+        """-n0 -e1 encode of a batch AND the seek index of every stream (``nblic_amd_encode_batch_indexed``): per image
+        (stream, index), the index byte-identical to ``build_index(stream, every_rows)`` and ``None`` where ``every_rows``
+        is 0 or not below the image's height.  ``imgs``: numpy planes, or device tensors (anything with ``data_ptr()``
+        and a 2-D ``shape``, uint8, contiguous); ``every_rows``: an int, or one per image.  Raises if any image failed."""
+        imgs = list(imgs)
+        on_device = bool(imgs) and hasattr(imgs[0], "data_ptr")
+        every = _every_rows_list(every_rows, len(imgs))
+        if on_device:
+            ptrs, shapes = [int(t.data_ptr()) for t in imgs], [(int(t.shape[0]), int(t.shape[1])) for t in imgs]
+        else:
+            planes = [np.ascontiguousarray(i, np.uint8) for i in imgs]
+            ptrs, shapes = [p.ctypes.data for p in planes], [p.shape for p in planes]
+        rc, streams, indexes = self.encode_indexed_ptrs(ptrs, shapes, on_device, every, band_rows)
+        if rc != 0:
+            raise RuntimeError("nblic_amd_encode_batch_indexed failed")
+        return list(zip(streams, indexes))
+
+    def indexed_batch_split(self) -> dict:
+        """Where the last indexed batch's group steps spent their time (``nblic_amd_indexed_batch_split``)."""
+        ms = (C.c_double * 5)()
+        steps = int(self.lib.nblic_amd_indexed_batch_split(self.handle, ms))
+        return dict(zip(("front_ms", "readback_ms", "back_ms", "copies_ms", "coder_wait_ms"), [float(v) for v in ms]), steps=steps)
 
     def encode_batch(self, imgs: Sequence[np.ndarray]) -> List[bytes]:
         """-n0 -e1 encode of host planes; returns the .nblic streams."""

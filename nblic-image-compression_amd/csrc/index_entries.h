@@ -1,0 +1,90 @@
+// index_entries.h -- the host-only part of writing a seek index while encoding (pipeline.hip: the band encoder and the
+// indexed batch): how large an index is, where its entries sit, and the entries that WAIT.  An entry written down at
+// an entry row lacks one field, the decoder's 4-byte window: the four stream bytes behind the entry's position, which
+// the coder has not emitted yet (the final flush always provides them).  PendingEntries hands every emitted stream
+// byte to the entries that wait for it and seals an entry once its window is complete.  No HIP, no device: the
+// stand-alone check (tools/index_entries_check.cpp) compiles this file alone, under the sanitizers.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <vector>
+
+#include "sha256.h"
+
+namespace nblic {
+
+inline void sha256_of(const void *p, size_t n, uint8_t out[32]) {
+    Sha256 s;
+    s.update(static_cast<const uint8_t *>(p), n);
+    s.digest(out);
+}
+// A sealed record: a head (magic, format version, ...), a body, and the SHA-256 of both in its last 32 bytes.
+inline void seal(uint8_t *buf, size_t n) { sha256_of(buf, n - 32, buf + n - 32); }
+
+// ---- sizes (pipeline.hip asserts them against the structs and constants they stand for) --------------------------------
+constexpr size_t kIndexHeadBytes = 96, kCheckpointHeadBytes = 168;                   // IndexHead, DecodeCheckpoint
+constexpr size_t kNblicRecordBytes = 86080, kQnblicRecordBytes = 12352, kQnblicTableBytes = 24576;   // kDecodeStateBytes, kQDecodeStateBytes, kQTab
+constexpr int kIndexMaxSide = 65535;                                                 // NBLIC_MAX_HEIGHT / _WIDTH, and QNBLIC's
+
+// The body of one entry: the decoder's state record, B (efforts 2 / 3: 512 / 1024 bytes per column), the two rows above
+// the entry row, the QNBLIC tables.  0 = kind / effort out of range.
+inline size_t index_record_bytes(int kind, int w, int effort) {
+    if (kind == 0 && effort >= 1 && effort <= 3) return kNblicRecordBytes + 2 * size_t(w) + (effort == 3 ? 1024 : effort == 2 ? 512 : 0) * size_t(w);
+    if (kind == 1 && effort == 0) return kQnblicRecordBytes + 2 * size_t(w) + kQnblicTableBytes;
+    return 0;
+}
+// One sealed entry: checkpoint head, body, SHA-256.
+inline size_t index_entry_bytes(int kind, int w, int effort) { return kCheckpointHeadBytes + index_record_bytes(kind, w, effort) + 32; }
+// Layout of an index: head | count x (uint64 length | entry) | SHA-256.
+inline size_t index_entry_at(int k, size_t entry_bytes) { return kIndexHeadBytes + size_t(k) * (8 + entry_bytes) + 8; }   // entry k, 0-based (its length sits in the 8 bytes before)
+inline size_t index_total_bytes(int count, size_t entry_bytes) { return kIndexHeadBytes + size_t(count) * (8 + entry_bytes) + 32; }
+
+// nblic_amd_index_bytes: the one place that knows the size of an index.
+inline long index_bytes(int kind, int h, int w, int effort, int every_rows) {
+    if (h < 1 || w < 1 || h > kIndexMaxSide || w > kIndexMaxSide || every_rows < 1 || every_rows >= h) return -1;
+    if (index_record_bytes(kind, w, effort) == 0) return -1;
+    return long(index_total_bytes((h - 1) / every_rows, index_entry_bytes(kind, w, effort)));
+}
+
+// Head and entry lengths around `count` entries that already sit at index_entry_at(k), then the seal.
+inline void index_close(uint8_t *p, const void *head, int count, size_t entry_bytes) {
+    memcpy(p, head, kIndexHeadBytes);
+    const unsigned long long n = entry_bytes;
+    for (int k = 0; k < count; k++) memcpy(p + index_entry_at(k, entry_bytes) - 8, &n, 8);
+    seal(p, index_total_bytes(count, entry_bytes));
+}
+
+// ---- entries that wait for their window ----------------------------------------------------------------------------------
+struct PendingEntries {
+    struct Entry {
+        uint8_t *ck; size_t bytes;      // the entry (head | body | room for the seal); the memory is the caller's and stays where it is
+        size_t window_at;               // where its 32-bit window goes, in bytes from ck
+        unsigned long long at;          // the window is stream bytes [at, at + 4)
+        int got; uint32_t window;
+    };
+    std::vector<Entry> waiting;         // in row order
+    unsigned long long fed = 0;         // stream bytes handed to the waiting entries so far
+    int sealed = 0;
+
+    void add(uint8_t *ck, size_t bytes, size_t window_at, unsigned long long at) { waiting.push_back(Entry{ck, bytes, window_at, at, 0, 0u}); }
+
+    // Stream bytes [base, base + (end - out)) have been emitted and lie at [out, end).  Bytes handed over before are skipped.
+    void bytes(unsigned long long base, const uint8_t *out, const uint8_t *end) {
+        const unsigned long long stop = base + (unsigned long long)(end - out);
+        for (unsigned long long a = fed > base ? fed : base; a < stop && !waiting.empty(); a++)
+            for (auto &e : waiting)
+                if (a >= e.at && a < e.at + 4) { e.window = (e.window << 8) | out[a - base]; e.got++; }
+        fed = fed > stop ? fed : stop;
+        while (!waiting.empty() && waiting.front().got == 4) {
+            const Entry &e = waiting.front();
+            memcpy(e.ck + e.window_at, &e.window, 4);
+            seal(e.ck, e.bytes);
+            waiting.erase(waiting.begin());
+            sealed++;
+        }
+    }
+};
+
+}  // namespace nblic

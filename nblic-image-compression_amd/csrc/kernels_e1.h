@@ -109,6 +109,13 @@ void e1_launch_back(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStr
 // model stage (serial_engine.h) that leaves rec1 and px | sign per pixel -- the re-mapper partition,
 // the re-mapper chains and the bin counts; e1_launch_back(..., general = true) finishes the job
 void e1_launch_init(const E1Job *d_jobs, int n_jobs, hipStream_t s);
+// Seek-index entry records of row bands (the indexed batch, pipeline.hip).  For every task, one workgroup converts the model
+// tables of job `job` -- as its band's front and back halves left them -- into the DECODER's state record (serial_engine.h:
+// SerialState, the 2048 context biases, the 4096 counters c0 | c1 << 16 tree-major, the re-mappers' hit counts, symbol -> rank
+// and rank -> symbol bytes) followed by the two image rows above the row behind the band, at out + `out`.  The header is
+// zero but for `bias`; the coder fields are the host's, which knows them once the band is coded.
+struct IndexRecordTask { int job, reserved; unsigned long long out; };     // out: byte offset of the record, a multiple of 4
+void e1_launch_index_records(const E1Job *d_jobs, const IndexRecordTask *d_tasks, int n_tasks, uint8_t *d_out, hipStream_t s);
 void e1_launch_front_pre(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s);
 // QNBLIC (effort 0) model stage for a group: leaves level | symbol << 8 per pixel in `pxs` and the
 // 12 x 256 histograms in `qhist`; the entropy stage (normalise, histogram code, rANS) is host work.

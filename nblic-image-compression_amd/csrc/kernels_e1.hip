@@ -27,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include "model.h"
 #include "kernels_e1.h"
+#include "lsq_f64.h"
+#include "serial_engine.h"
 
 namespace nblic {
 
@@ -1326,6 +1328,51 @@ __global__ void __launch_bounds__(256) k_pack_rows(const E1Job *__restrict__ job
     gptr(J0.pack_rows)[t] = v;
 }
 
+// ---- seek-index entry records (kernels_e1.h IndexRecordTask) --------------------------------
+// One workgroup per entry.  Every global access is a run of consecutive words or bytes over consecutive lanes: the
+// counters keep their 256-node runs (a tree's nodes are consecutive keys), and the re-mappers' 60-int records go through
+// LDS, 64 re-mappers at a time, so that the three tables they are split into are written as dense streams.
+__global__ void __launch_bounds__(256) k_index_records(const E1Job *__restrict__ jobs, const IndexRecordTask *__restrict__ tasks, uint8_t *__restrict__ out) {
+    constexpr int kTile = 64;                                             // re-mappers per LDS tile
+    __shared__ int tile[kTile * 60];
+    const IndexRecordTask T = tasks[blockIdx.x];
+    const E1Job &J = jobs[T.job];
+    const int t = int(threadIdx.x);
+    const auto rec = gptr(out) + T.out;
+    const auto words = (NB_GLOBAL uint32_t *)rec;
+    constexpr int kHeadWords = int(sizeof(SerialState) / 4), kBiasWord = int(offsetof(SerialState, bias) / 4);
+    if (t < kHeadWords) words[t] = t == kBiasWord ? uint32_t(lsq::kBiasInit) : 0u;
+    const auto tab = words + kHeadWords;
+    const auto ctx_state = gptr(J.b.ctx_state);
+    for (int k = t; k < kContexts; k += 256) tab[k] = uint32_t(ctx_state[k]);
+    const auto cnt_state = (NB_GLOBAL const i32x2 *)gptr(J.b.cnt_state);
+    for (int key = t; key < 4096; key += 256) {
+        const i32x2 c = cnt_state[key];
+        const int tree = ((key >> 8) & 7) * 2 + (key >> 11), node = key & 255;
+        tab[kContexts + tree * kTreeNodes + node] = uint32_t(c.x) | (uint32_t(c.y) << 16);
+    }
+    const auto map_state = gptr(J.b.map_state);
+    const auto rank = rec + sizeof(SerialState) + size_t(kRecRank) * 4, sym = rec + sizeof(SerialState) + size_t(kRecSym) * 4;
+    for (int m0 = 0; m0 < 512; m0 += kTile) {
+        for (int k = t; k < kTile * 60; k += 256) tile[k] = map_state[m0 * 60 + k];
+        __syncthreads();
+        for (int k = t; k < kTile * kMapSyms; k += 256) {
+            const int m = k / kMapSyms, q = k - m * kMapSyms;
+            rank[m0 * kMapSyms + k] = uint8_t(tile[m * 60 + q]);
+            sym[m0 * kMapSyms + k] = uint8_t(tile[m * 60 + 20 + q]);
+            tab[kRecCount + m0 * kMapSyms + k] = uint32_t(tile[m * 60 + 40 + q]);
+        }
+        __syncthreads();
+    }
+    // rows [r - n, r) of the image, n = min(r, 2), behind (2 - n) w zero bytes; r = the row behind the band.  b.img is the
+    // band's first row and the plane goes on above it.
+    const int w = J.w, r = J.row0 + J.h, n = r < 2 ? r : 2;
+    const auto rows = rec + kDecodeStateBytes;
+    const auto img = gptr(J.b.img);
+    const ptrdiff_t zeros = ptrdiff_t(2 - n) * w, from = ptrdiff_t(J.h - n) * w;
+    for (ptrdiff_t k = t; k < 2 * ptrdiff_t(w); k += 256) rows[k] = k < zeros ? uint8_t(0) : img[from + (k - zeros)];
+}
+
 // ---- model state init (NBLIC.c:797-804) ---------------------------------------------------
 __global__ void k_init_state(const E1Job *__restrict__ jobs) {
     const E1Job &J = jobs[blockIdx.y];
@@ -1585,6 +1632,10 @@ void e1_launch_front_pre(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, h
 
 void e1_launch_init(const E1Job *d_jobs, int n_jobs, hipStream_t s) {
     hipLaunchKernelGGL(k_init_state, dim3(16, n_jobs), dim3(256), 0, s, d_jobs);
+}
+
+void e1_launch_index_records(const E1Job *d_jobs, const IndexRecordTask *d_tasks, int n_tasks, uint8_t *d_out, hipStream_t s) {
+    if (n_tasks > 0) hipLaunchKernelGGL(k_index_records, dim3(unsigned(n_tasks)), dim3(256), 0, s, d_jobs, d_tasks, d_out);
 }
 
 // Back half: needs n_ev / pe filled in the job records and event-sized buffers.  10 launches.

@@ -35,6 +35,7 @@
 #include "../../include/nblic_amd.h"
 #include "device_coder.h"
 #include "hip_owned.h"
+#include "index_entries.h"
 #include "kernels_e1.h"
 #include "lsq_f64.h"
 #include "model.h"
@@ -271,6 +272,7 @@ struct nblic_amd_ctx {
     int index_round_segments = 0;         // > 0: at most this many segments per round of decode_indexed (nblic_amd_set_index_round)
     int serial_rows = 0;                  // rows per launch of the serial kernels; 0 = sized for a few seconds per launch (nblic_amd_set_serial_rows)
     DevBuf<unsigned long long> d_redo;          // device: pixels whose least-squares system 0 / 1 was redone with integers (SerialJob::redo of every job of the context)
+    double idx_split[5] = {0}; long idx_steps = 0;   // the last indexed batch, summed over its group steps: front, totals read-back, back half + entry records, copies (GPU ms); coder wait (host ms).  Guarded by stat_m
     long serial_launch_count = 0;         // launches of the serial model / decode kernels since the context was created (reporting, tests)
     size_t feed_chunk = size_t(1) << 20;  // bytes per step in which the drop-in decoders fetch a stream of unknown length (nblic_amd_set_feed_chunk)
     long fed_bytes = 0;                   // bytes the last drop-in decode read from the caller's stream
@@ -1265,14 +1267,8 @@ static bool upload_stream(uint8_t *d, const unsigned char *src, size_t n, hipStr
     return hipMemsetAsync(d + z, 0, stream_buf_bytes(n) - z, st) == hipSuccess && hipMemcpyAsync(d, src, n, hipMemcpyHostToDevice, st) == hipSuccess;
 }
 
-static void sha256_of(const void *p, size_t n, uint8_t out[32]) {
-    Sha256 s;
-    s.update(static_cast<const uint8_t *>(p), n);
-    s.digest(out);
-}
-
-// A sealed record: a head (magic, format version, ...), a body, and the SHA-256 of both in its last 32 bytes.
-static void seal(uint8_t *buf, size_t n) { sha256_of(buf, n - 32, buf + n - 32); }
+// A sealed record (index_entries.h: sha256_of, seal): a head (magic, format version, ...), a body, and the SHA-256 of both
+// in its last 32 bytes.
 // The head (into H) and the body of the len bytes at p if they are a sealed record of this magic and version; else null.
 template <class Head> static const uint8_t *sealed_body(const void *p, size_t len, const char *magic, uint32_t version, Head &H) {
     uint8_t d[32];
@@ -1296,6 +1292,8 @@ struct DecodeCheckpoint {              // followed by: state record | B | two ro
     Sha256 rows_sha;                   // of rows [0, next_row)
 };
 static_assert(std::is_trivially_copyable<DecodeCheckpoint>::value, "written and read as bytes");
+static_assert(sizeof(DecodeCheckpoint) == kCheckpointHeadBytes && kDecodeStateBytes == kNblicRecordBytes && kQDecodeStateBytes == kQnblicRecordBytes &&
+              kQTab == kQnblicTableBytes && NBLIC_MAX_HEIGHT == kIndexMaxSide && NBLIC_MAX_WIDTH == kIndexMaxSide, "index_entries.h states these sizes for host-only code");
 constexpr unsigned long long kMaxStreamPos = 1ull << 48;   // no stream this library decodes comes near it
 
 // Where the parts of a decoder record's body are, in bytes from its start (the state record is at 0).
@@ -1599,10 +1597,8 @@ struct nblic_amd_stream {
     // seek index (nblic_amd_stream_set_index): an entry in front of every row index_every, 2 index_every, ...  An entry
     // waits for the four stream bytes that follow its position (the decoder's window) before it is sealed.
     int index_every = 0;
-    struct PendingEntry { std::vector<uint8_t> ck; unsigned long long at; int got; uint32_t window; };
-    std::vector<PendingEntry> pending;
-    std::vector<std::vector<uint8_t>> entries;                          // sealed, in row order
-    unsigned long long index_fed = 0;                                   // stream bytes handed to the pending entries so far
+    nblic::PendingEntries pending;                                      // (index_entries.h) views of the entries below that still wait
+    std::vector<std::vector<uint8_t>> entries;                          // in row order; sealed unless `pending` still names it
     nblic::Sha256 rows_sha;                                             // of the reconstruction rows coded so far
     std::vector<uint8_t> band_rows_host;
 };
@@ -2161,7 +2157,7 @@ struct IndexHead {
     unsigned long long stream_len;
     uint8_t stream_sha[32];
 };
-static_assert(sizeof(IndexHead) == 96, "written and read as bytes");
+static_assert(sizeof(IndexHead) == kIndexHeadBytes, "written and read as bytes");
 
 static IndexHead index_head(const DecodeItem &it, int every, int count, unsigned long long stream_len) {     // all but stream_sha
     IndexHead H{};
@@ -2240,8 +2236,9 @@ static long index_build(nblic_amd_ctx *c, const unsigned char *stream, size_t sl
     if (describe_stream(stream, slen, false, c ? c->max_px : kMaxPixels, it, qtab) != Described::ok) return -1;
     if (every < 1 || every >= it.h) return -1;
     const int count = (it.h - 1) / every;
-    const size_t eb = sizeof(DecodeCheckpoint) + record_layout(it.kind, it.w, it.effort).bytes + 32;
-    const size_t need = sizeof(IndexHead) + size_t(count) * (8 + eb) + 32;
+    const size_t eb = index_entry_bytes(it.kind, it.w, it.effort);
+    const size_t need = index_total_bytes(count, eb);
+    if (eb != sizeof(DecodeCheckpoint) + record_layout(it.kind, it.w, it.effort).bytes + 32) return -1;     // (the two descriptions of an entry agree)
     if (!out || cap < need) return long(need);
     if (!c) return -1;
     IndexHead H = index_head(it, every, count, slen);
@@ -2288,22 +2285,9 @@ static long index_build(nblic_amd_ctx *c, const unsigned char *stream, size_t sl
 
 // The stream bytes emitted by this call so far, [out, end): what the pending entries are waiting for.
 static void stream_index_bytes(nblic_amd_stream *s, const uint8_t *out, const uint8_t *end) {
-    const unsigned long long base = s->bytes_total, stop = base + (unsigned long long)(end - out);
-    for (unsigned long long a = std::max(s->index_fed, base); a < stop; a++)
-        for (auto &e : s->pending)
-            if (a >= e.at && a < e.at + 4) { e.window = (e.window << 8) | out[a - base]; e.got++; }
-    s->index_fed = std::max(s->index_fed, stop);
-    while (!s->pending.empty() && s->pending.front().got == 4) {
-        auto &e = s->pending.front();
-        SerialState S;
-        memcpy(&S, e.ck.data() + sizeof(DecodeCheckpoint), sizeof S);
-        S.window = e.window;
-        memcpy(e.ck.data() + sizeof(DecodeCheckpoint), &S, sizeof S);
-        seal(e.ck.data(), e.ck.size());
-        s->entries.push_back(std::move(e.ck));
-        s->pending.erase(s->pending.begin());
-    }
+    s->pending.bytes(s->bytes_total, out, end);
 }
+constexpr size_t kEntryWindowAt = sizeof(DecodeCheckpoint) + offsetof(SerialState, window);     // where an entry's window goes
 
 // After the band [i0, i0 + rows) has been coded: the bytes it emitted go to the pending entries, its rows into the row
 // hash, and at an entry row the entry is written down (all but its window).
@@ -2356,7 +2340,8 @@ static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8
         }
     const DecodeCheckpoint H = decode_head(it, R, r, S.pos & ~511ull, canonical_sha(s->rows_sha));
     memcpy(ck.data(), &H, sizeof H);
-    s->pending.push_back(nblic_amd_stream::PendingEntry{std::move(ck), emitted, 0, 0u});
+    s->entries.push_back(std::move(ck));                               // (moving the vector leaves its bytes where they are)
+    s->pending.add(s->entries.back().data(), s->entries.back().size(), kEntryWindowAt, emitted);
     return true;
 }
 
@@ -2376,24 +2361,17 @@ static int stream_set_index(nblic_amd_stream *s, int every) {
 
 // The index of a finished image whose every band this object coded; 0 otherwise.  Same layout as index_build.
 static size_t stream_index(nblic_amd_stream *s, void *buf, size_t cap) {
-    if (!s || s->index_every <= 0 || s->first_row != 0 || !s->finished || !s->pending.empty()) return 0;
+    if (!s || s->index_every <= 0 || s->first_row != 0 || !s->finished || !s->pending.waiting.empty()) return 0;
     const int count = (s->h - 1) / s->index_every;
     if (int(s->entries.size()) != count) return 0;
-    size_t need = sizeof(IndexHead) + 32;
-    for (const auto &e : s->entries) need += 8 + e.size();
+    const size_t eb = index_entry_bytes(0, s->w, s->effort), need = index_total_bytes(count, eb);
+    for (const auto &e : s->entries) if (e.size() != eb) return 0;
     if (!buf || cap < need) return need;
     IndexHead H = index_head(DecodeItem{0, s->h, s->w, s->near, s->k_step, s->effort, 0, 0, -1, -1}, s->index_every, count, s->bytes_total);
     s->sha.digest(H.stream_sha);
     uint8_t *p = static_cast<uint8_t *>(buf);
-    memcpy(p, &H, sizeof H);
-    size_t at = sizeof H;
-    for (const auto &e : s->entries) {
-        const unsigned long long n = e.size();
-        memcpy(p + at, &n, 8);
-        memcpy(p + at + 8, e.data(), e.size());
-        at += 8 + e.size();
-    }
-    seal(p, need);
+    for (int k = 0; k < count; k++) memcpy(p + index_entry_at(k, eb), s->entries[size_t(k)].data(), eb);
+    index_close(p, &H, count, eb);
     return need;
 }
 
@@ -2598,6 +2576,309 @@ static int decode_rows(nblic_amd_ctx *c, const unsigned char *stream, size_t sle
 }
 
 // ---- default context behind the drop-in entry points ---------------------------------------
+// ---- the INDEXED BATCH: many -n0 -e1 images and their seek indexes, a group of images stepped through row bands together ----
+// What the band encoder does for one image per object (staged front, an entry record at every entry row), done for a
+// whole group per launch sequence: every live slot of a group holds one image in progress, a STEP carries one band of each
+// -- the jobs differ in row0, in height and in width -- and a slot whose image has ended takes the batch's next image at
+// the next step.  Nothing in a band's front or back half depends on the range coder, so the bins and entry records of step t
+// are coded by worker threads, one task per image and band, while the GPU runs step t + 1; a step's bins, records and (for
+// device inputs) rows land in one of two sets of page-locked buffers.  The model tables are the slot's three tables and stay
+// on the device from band to band; an entry's decoder record is made there (k_index_records).
+struct IdxPool {                                                         // worker threads of one call
+    std::mutex m; std::condition_variable cv; std::deque<std::function<void()>> q; bool stop = false;
+    std::vector<std::thread> th;
+    void start(int n) {
+        for (int i = 0; i < n; i++)
+            th.emplace_back([this] {
+                for (;;) {
+                    std::function<void()> f;
+                    {
+                        std::unique_lock<std::mutex> l(m);
+                        cv.wait(l, [this] { return stop || !q.empty(); });
+                        if (q.empty()) return;
+                        f = std::move(q.front()); q.pop_front();
+                    }
+                    f();
+                }
+            });
+    }
+    void post(std::function<void()> f) { { std::lock_guard<std::mutex> l(m); q.push_back(std::move(f)); } cv.notify_one(); }
+    ~IdxPool() { { std::lock_guard<std::mutex> l(m); stop = true; } cv.notify_all(); for (auto &t : th) t.join(); }
+};
+struct IdxPendingTasks {                                                 // the tasks of one group's step that have not ended
+    std::mutex m; std::condition_variable cv; int left = 0;
+    void add(int n) { std::lock_guard<std::mutex> l(m); left += n; }
+    void done() { { std::lock_guard<std::mutex> l(m); left--; } cv.notify_all(); }
+    void wait() { std::unique_lock<std::mutex> l(m); cv.wait(l, [this] { return left == 0; }); }
+};
+
+// One image of the batch between its first band and its last: the resumable coder (interval, bytes emitted, the running
+// SHA-256 of the stream and of the rows) and the index being written into the caller's buffer.  Touched by one task at a time.
+struct IdxImage {
+    int k = 0, h = 0, w = 0, every = 0;                                  // every: 0 = no index wanted (or none possible)
+    const uint8_t *host_plane = nullptr;                                 // host input: the rows are hashed from it
+    uint8_t *out = nullptr; size_t cap = 0;
+    RangeScalar rc;
+    unsigned long long emitted = 0;                                      // stream bytes so far, header included
+    Sha256 stream_sha, rows_sha;
+    uint8_t *index = nullptr; size_t entry_bytes = 0; int count = 0, made = 0;
+    PendingEntries pending;
+    std::atomic<bool> failed{false};                                     // out of room: the driver drops the image at its next step
+};
+struct IdxBand {                                                         // what a task codes: one band of one image
+    IdxImage *im; int i0, rows; const uint16_t *bins; uint32_t n_ev; const uint8_t *rows_host, *rec; bool last;
+};
+struct IdxCall {
+    nblic_amd_ctx *c; int n; const unsigned char *const *imgs; bool on_device; const int *hs, *ws, *every; int band_rows;
+    unsigned char *const *outs; const size_t *caps; long *lens; unsigned char *const *indexes; const size_t *icaps; long *ilens;
+    std::atomic<int> next{0};
+    std::atomic<bool> failed{false};                                     // a device-side failure: the call is over
+    IdxPool pool;
+    std::mutex m; double split[5] = {0}; long steps = 0;                 // summed over the groups (guarded by m)
+};
+
+// The band [i0, i0 + rows) of an image has been coded on the device: range-code its bins, hash its rows, hand the new stream
+// bytes to the waiting entries, write down the entry in front of row i0 + rows if there is one, and end the image with its
+// last band.
+static void idx_code_band(IdxCall &q, const IdxBand &b) {
+    IdxImage &I = *b.im;
+    if (I.failed) return;
+    auto fail = [&] { I.failed = true; q.lens[I.k] = -1; if (I.every) q.ilens[I.k] = -1; };
+    if (b.i0 == 0) {
+        write_header(I.out, I.h, I.w, 0, k_step_for_near(0), 1);
+        I.rc.begin(I.out + kHeaderBytes, I.cap - kHeaderBytes);
+        I.stream_sha.update(I.out, kHeaderBytes);
+        I.emitted = kHeaderBytes;
+    }
+    const uint8_t *const from = I.rc.p;
+    I.rc.feed(b.bins, b.n_ev);
+    if (I.rc.overflow || (b.last && I.rc.finish() == SIZE_MAX)) return fail();
+    I.pending.bytes(I.emitted, from, I.rc.p);
+    I.stream_sha.update(from, size_t(I.rc.p - from));
+    I.emitted += (unsigned long long)(I.rc.p - from);
+    if (I.every) I.rows_sha.update(b.rows_host, size_t(b.rows) * size_t(I.w));
+    if (b.rec) {                                                         // an entry row: everything but the window, which waits
+        const int r = b.i0 + b.rows;
+        const DecodeItem it{0, I.h, I.w, 0, k_step_for_near(0), 1, 0, 0, -1, -1};
+        uint8_t *ck = I.index + index_entry_at(I.made, I.entry_bytes), *rec = ck + sizeof(DecodeCheckpoint);
+        memcpy(rec, b.rec, kDecodeStateBytes + 2 * size_t(I.w));
+        SerialState S;
+        memcpy(&S, rec, sizeof S);                                       // zero but for `bias` (k_index_records)
+        S.next_row = r; S.status = kRunning; S.pos = I.emitted + 4; S.lo = I.rc.lo; S.hi = I.rc.hi;
+        memcpy(rec, &S, sizeof S);
+        const DecodeCheckpoint H = decode_head(it, I.every, r, S.pos & ~511ull, canonical_sha(I.rows_sha));
+        memcpy(ck, &H, sizeof H);
+        I.pending.add(ck, I.entry_bytes, kEntryWindowAt, I.emitted);
+        I.made++;
+    }
+    if (!b.last) return;
+    q.lens[I.k] = long(I.emitted);
+    if (!I.every) return;
+    if (I.made != I.count || !I.pending.waiting.empty()) { q.ilens[I.k] = -1; return; }     // (cannot happen: the flush provides every window)
+    IndexHead H = index_head(DecodeItem{0, I.h, I.w, 0, k_step_for_near(0), 1, 0, 0, -1, -1}, I.every, I.count, I.emitted);
+    I.stream_sha.digest(H.stream_sha);
+    index_close(I.index, &H, I.count, I.entry_bytes);
+    q.ilens[I.k] = long(index_total_bytes(I.count, I.entry_bytes));
+}
+
+// The rows per band of an image of the batch: stream_open's rule.
+static int idx_band_rows(const IdxCall &q, int h, int w) { return q.band_rows > 0 ? std::min(q.band_rows, h) : serial_rows_per_launch(h, w, 1, 0); }
+
+// One driver: holds one group for the whole call and steps its slots through the batch's images.
+static void idx_driver(IdxCall &q, std::vector<std::unique_ptr<IdxImage>> &images) {
+    nblic_amd_ctx *c = q.c;
+    if (hipSetDevice(c->device) != hipSuccess) { q.failed = true; return; }
+    const int gid = take_group(c);
+    {                                                                    // (everything the driver owns goes before the group is released)
+        Group &g = c->groups[size_t(gid)];
+        const hipStream_t st = g.stream;
+        const int n_slots = int(g.slots.size());
+        struct Live { IdxImage *im = nullptr; int row0 = 0, band = 0; const uint8_t *plane = nullptr; };
+        std::vector<Live> live{size_t(n_slots)};
+        struct Set { Locked bins, recs, rows; } sets[2];                 // what a step's tasks read (Locked counts 16-bit words)
+        DevBuf<uint16_t> d_bins; DevBuf<uint8_t> d_recs;
+        Pinned<IndexRecordTask> h_tasks; DevBuf<IndexRecordTask> d_tasks;
+        IdxPendingTasks tasks_left;
+        std::vector<int> slot_of(size_t(n_slots), 0);
+        std::vector<size_t> bins_at(size_t(n_slots), 0), rec_at(size_t(n_slots), 0), rows_at(size_t(n_slots), 0);
+        double split[5] = {0}; long steps = 0;
+        bool ok = h_tasks.alloc(size_t(n_slots)) == hipSuccess && d_tasks.alloc(size_t(n_slots)) == hipSuccess;
+        auto grow = [](Locked &b, size_t bytes) { return bytes <= b.capacity() * 2 || b.alloc((bytes + bytes / 4 + 4096) / 2); };
+        for (long t = 0; ok && !q.failed; t++) {
+            // ---- which image each slot works on
+            for (int k = 0; k < n_slots; k++) {
+                Live &L = live[size_t(k)];
+                if (L.im && (L.row0 >= L.im->h || L.im->failed)) L.im = nullptr;
+                while (!L.im) {
+                    const int j = q.next.fetch_add(1);
+                    if (j >= q.n) break;
+                    IdxImage *I = images[size_t(j)].get();
+                    if (!I) continue;                                    // refused before the call started (idx_prepare)
+                    Slot &s = g.slots[size_t(k)];
+                    L.band = idx_band_rows(q, I->h, I->w);
+                    const size_t n = size_t(I->h) * size_t(I->w);
+                    if (!(ok = ensure_pixels(s, size_t(L.band) * size_t(I->w)))) break;
+                    if (q.on_device) L.plane = q.imgs[j];
+                    else {
+                        if (!(ok = s.d_img.reserve(n) == hipSuccess && hipMemcpyAsync(s.d_img, q.imgs[j], n, hipMemcpyHostToDevice, st) == hipSuccess)) break;
+                        L.plane = s.d_img;
+                    }
+                    L.im = I; L.row0 = 0;
+                }
+                if (!ok) break;
+            }
+            if (!ok) break;
+            // ---- 1. job records of the live slots
+            int n_jobs = 0;
+            for (int k = 0; k < n_slots; k++) {
+                Live &L = live[size_t(k)];
+                if (!L.im) continue;
+                const IdxImage &I = *L.im;
+                int rows = std::min(L.band, I.h - L.row0);
+                if (I.every) rows = std::min(rows, I.every - L.row0 % I.every);           // a band never crosses an entry row
+                E1Buffers b = g.slots[size_t(k)].b;
+                b.img = L.plane + size_t(L.row0) * size_t(I.w);
+                g.h_jobs[n_jobs] = e1_job_front(b, rows, I.w, 0, 0);
+                g.h_jobs[n_jobs].row0 = L.row0;
+                slot_of[size_t(n_jobs++)] = k;
+            }
+            if (n_jobs == 0) break;
+            hipEvent_t *ev = g.tm.ev;                                    // marks of the step's five parts
+            ok = hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, st) == hipSuccess;
+            if (!ok) break;
+            hipEventRecord(ev[0], st);
+            // ---- 2. / 3. fresh tables for the jobs that start an image, then the front half of every band
+            for (int j = 0; j < n_jobs; j++) if (g.h_jobs[j].row0 == 0) e1_launch_init(g.d_jobs + j, 1, st);
+            e1_launch_front_band(g.d_jobs, g.h_jobs, n_jobs, st);
+            hipEventRecord(ev[1], st);
+            // ---- 4. totals
+            ok = hipMemcpyAsync(g.h_totals, g.d_totals, size_t(n_slots) * kTotalsStride * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+            hipEventRecord(ev[2], st);
+            if (!ok || hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { ok = false; break; }
+            // ---- 5. the back half: bins of all jobs side by side in one buffer
+            size_t n_bins = 0, rec_bytes = 0, rows_bytes = 0; int n_tasks = 0;
+            for (int j = 0; j < n_jobs && ok; j++) {
+                const int k = slot_of[size_t(j)];
+                const uint32_t n_ev = g.h_totals[size_t(k) * kTotalsStride + 2];
+                ok = n_ev < 0x7FFFFFFFu && ensure_events(g.slots[size_t(k)], n_ev);
+                bins_at[size_t(j)] = n_bins;
+                n_bins += (size_t(n_ev) + 64 + 63) & ~size_t(63);
+                const IdxImage &I = *live[size_t(k)].im;
+                const int r = g.h_jobs[j].row0 + g.h_jobs[j].h;
+                rec_at[size_t(j)] = SIZE_MAX;
+                if (I.every && r % I.every == 0 && r < I.h) {
+                    rec_at[size_t(j)] = rec_bytes;
+                    h_tasks[n_tasks++] = IndexRecordTask{j, 0, (unsigned long long)(rec_bytes)};
+                    rec_bytes += up256(kDecodeStateBytes + 2 * size_t(I.w));
+                }
+                rows_at[size_t(j)] = rows_bytes;
+                if (q.on_device && I.every) rows_bytes += size_t(g.h_jobs[j].n);
+            }
+            if (!ok) break;
+            Set &S = sets[t & 1];                                        // free: the tasks of step t - 2 ended before step t - 1 was handed over
+            ok = (n_bins <= d_bins.capacity() || d_bins.alloc(n_bins + n_bins / 4 + 4096) == hipSuccess) &&
+                 (rec_bytes <= d_recs.capacity() || d_recs.alloc(rec_bytes) == hipSuccess) &&
+                 grow(S.bins, n_bins * 2) && grow(S.recs, rec_bytes) && grow(S.rows, rows_bytes);
+            if (!ok) break;
+            for (int j = 0; j < n_jobs; j++) {
+                E1Buffers b = g.slots[size_t(slot_of[size_t(j)])].b;
+                b.img = g.h_jobs[j].b.img; b.coded = d_bins + bins_at[size_t(j)];
+                e1_job_back(g.h_jobs[j], b, g.h_totals[size_t(slot_of[size_t(j)]) * kTotalsStride + 2]);
+            }
+            ok = hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, st) == hipSuccess &&
+                 (!n_tasks || hipMemcpyAsync(d_tasks, h_tasks, size_t(n_tasks) * sizeof(IndexRecordTask), hipMemcpyHostToDevice, st) == hipSuccess);
+            if (!ok) break;
+            hipEventRecord(ev[3], st);
+            e1_launch_back(g.d_jobs, g.h_jobs, n_jobs, st, nullptr, true);
+            // ---- 6. the decoder records of the jobs whose band ends on an entry row
+            e1_launch_index_records(g.d_jobs, d_tasks, n_tasks, d_recs, st);
+            hipEventRecord(ev[4], st);
+            // ---- 7. one copy of the step's bins, one of its records (and the rows of device inputs, for the row hash)
+            ok = hipMemcpyAsync(static_cast<uint16_t *>(S.bins), d_bins, n_bins * sizeof(uint16_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                 (!rec_bytes || hipMemcpyAsync(static_cast<uint16_t *>(S.recs), d_recs, rec_bytes, hipMemcpyDeviceToHost, st) == hipSuccess);
+            uint8_t *const rows_host = reinterpret_cast<uint8_t *>(static_cast<uint16_t *>(S.rows));
+            for (int j = 0; j < n_jobs && ok && q.on_device; j++)
+                if (live[size_t(slot_of[size_t(j)])].im->every)
+                    ok = hipMemcpyAsync(rows_host + rows_at[size_t(j)], g.h_jobs[j].b.img, size_t(g.h_jobs[j].n), hipMemcpyDeviceToHost, st) == hipSuccess;
+            hipEventRecord(ev[5], st);
+            if (!ok || hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { ok = false; break; }
+            for (int k = 0; k < 4; k++) {
+                float ms = 0.f;
+                const int a = k < 2 ? k : k + 1;                         // (2 -> 3 is the host's sizing of the back half)
+                if (hipEventElapsedTime(&ms, ev[a], ev[a + 1]) == hipSuccess) split[k] += ms;
+            }
+            const auto w0 = std::chrono::steady_clock::now();
+            tasks_left.wait();                                           // step t - 1 is coded: an image's bands are coded in order
+            split[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+            steps++;
+            tasks_left.add(n_jobs);
+            const uint8_t *const recs_host = reinterpret_cast<const uint8_t *>(static_cast<uint16_t *>(S.recs));
+            for (int j = 0; j < n_jobs; j++) {
+                Live &L = live[size_t(slot_of[size_t(j)])];
+                IdxImage *I = L.im;
+                const int rows = g.h_jobs[j].h;
+                const uint8_t *rows_src = !I->every ? nullptr : q.on_device ? rows_host + rows_at[size_t(j)] : I->host_plane + size_t(L.row0) * size_t(I->w);
+                const IdxBand b{I, L.row0, rows, static_cast<uint16_t *>(S.bins) + bins_at[size_t(j)], g.h_jobs[j].n_ev, rows_src,
+                                rec_at[size_t(j)] == SIZE_MAX ? nullptr : recs_host + rec_at[size_t(j)], L.row0 + rows >= I->h};
+                q.pool.post([&q, &tasks_left, b] { idx_code_band(q, b); tasks_left.done(); });
+                L.row0 += rows;
+            }
+        }
+        if (!ok) { q.failed = true; fprintf(stderr, "[nblic_amd] indexed batch: a device step failed\n"); }
+        hipStreamSynchronize(st);
+        tasks_left.wait();
+        std::lock_guard<std::mutex> l(q.m);
+        for (int k = 0; k < 5; k++) q.split[k] += split[k];
+        q.steps += steps;
+    }
+    release_group(c, gid);
+}
+
+static int encode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *const *imgs, bool on_device, const int *hs, const int *ws, const int *every,
+                                int band_rows, unsigned char *const *outs, const size_t *caps, long *lens, unsigned char *const *indexes, const size_t *icaps, long *ilens) {
+    if (!c || c->broken || n < 1 || !imgs || !hs || !ws || !every || !outs || !caps || !lens || (indexes && (!icaps || !ilens))) return -1;
+    for (int k = 0; k < n; k++) if (every[k] < 0 || !imgs[k] || !outs[k]) return -1;
+    if (hipSetDevice(c->device) != hipSuccess) return -1;
+    IdxCall q{c, n, imgs, on_device, hs, ws, every, band_rows, outs, caps, lens, indexes, icaps, ilens};
+    std::vector<std::unique_ptr<IdxImage>> images{size_t(n)};
+    int n_live = 0;
+    for (int k = 0; k < n; k++) {                                        // what can be refused is refused before anything is launched
+        lens[k] = -1;
+        if (ilens) ilens[k] = 0;
+        const size_t cap = std::min(caps[k], size_t(1) << 46);
+        if (!size_ok(hs[k], ws[k], c->max_px) || cap < size_t(kHeaderBytes) + 4) continue;
+        auto I = std::make_unique<IdxImage>();
+        I->k = k; I->h = hs[k]; I->w = ws[k]; I->out = outs[k]; I->cap = cap;
+        I->host_plane = on_device ? nullptr : imgs[k];
+        if (indexes && indexes[k] && every[k] >= 1 && every[k] < hs[k]) {
+            const long need = index_bytes(0, hs[k], ws[k], 1, every[k]);
+            if (need < 0 || icaps[k] < size_t(need)) ilens[k] = -1;                       // the stream is still delivered
+            else { I->every = every[k]; I->index = indexes[k]; I->entry_bytes = index_entry_bytes(0, ws[k], 1); I->count = (hs[k] - 1) / every[k]; }
+        }
+        images[size_t(k)] = std::move(I);
+        n_live++;
+    }
+    if (n_live) {
+        const int group_size = int(c->groups[0].slots.size());
+        const int n_drivers = std::min(int(c->groups.size()), (n_live + group_size - 1) / group_size);
+        q.pool.start(std::max(1, c->coders_wanted));
+        std::vector<std::thread> drivers;
+        for (int i = 0; i < n_drivers; i++) drivers.emplace_back([&] { idx_driver(q, images); });
+        for (auto &t : drivers) t.join();
+    }
+    {
+        std::lock_guard<std::mutex> l(c->stat_m);
+        for (int k = 0; k < 5; k++) c->idx_split[k] = q.split[k];
+        c->idx_steps = q.steps;
+    }
+    bool all = !q.failed;
+    for (int k = 0; k < n; k++) {
+        if (q.failed && images[size_t(k)]) { lens[k] = -1; if (ilens && images[size_t(k)]->every) ilens[k] = -1; }
+        all = all && lens[k] >= 0 && (!ilens || ilens[k] >= 0);
+    }
+    return all ? 0 : -1;
+}
+
 static nblic_amd_ctx *g_default = nullptr;
 static std::mutex g_default_m;
 
@@ -3136,6 +3417,19 @@ int nblic_amd_index_check(nblic_amd_ctx *c, const void *index, size_t index_byte
 }
 long nblic_amd_index_build(nblic_amd_ctx *c, const unsigned char *stream, size_t stream_bytes, int every_rows, unsigned char *out, size_t cap) {
     return index_build(c, stream, stream_bytes, every_rows, out, cap);
+}
+int nblic_amd_encode_batch_indexed(nblic_amd_ctx *c, int n_images, const unsigned char *const *imgs, int imgs_on_device,
+                                   const int *heights, const int *widths, const int *every_rows, int band_rows,
+                                   unsigned char *const *outs, const size_t *out_caps, long *out_lens,
+                                   unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
+    return encode_batch_indexed(c, n_images, imgs, imgs_on_device != 0, heights, widths, every_rows, band_rows, outs, out_caps, out_lens, indexes, index_caps, index_lens);
+}
+long nblic_amd_index_bytes(int kind, int height, int width, int effort, int every_rows) { return index_bytes(kind, height, width, effort, every_rows); }
+long nblic_amd_indexed_batch_split(nblic_amd_ctx *c, double ms[5]) {
+    if (!c || !ms) return -1;
+    std::lock_guard<std::mutex> l(c->stat_m);
+    for (int k = 0; k < 5; k++) ms[k] = c->idx_split[k];
+    return c->idx_steps;
 }
 int nblic_amd_decode_indexed(nblic_amd_ctx *c, const unsigned char *stream, size_t stream_bytes, const void *index, size_t index_bytes,
                              unsigned char *img, size_t img_cap) {
