@@ -413,6 +413,47 @@ int nblic_amd_debug_device_code(nblic_amd_ctx *ctx, int n_jobs, const unsigned s
                                 const size_t *pack_words, const unsigned int *n_bins, const unsigned int *caps,
                                 unsigned char *const *outs, long *lens);
 
+/* Debug hook used by the chain kernels' tests: ONE launch sequence of the staged model stages BEHIND S1 on n records the
+ * caller supplies (1 .. 1 << 22), as one job.  x[n] are the pixel values, rec1[n] the S1 records, both uploaded verbatim.
+ *   model 0 (NBLIC -e1): rec1 is csrc/model.h pack_s1 (px0 | adr << 8 | qw << 19 | qu's low bit << 24 | qv_rel << 25).  Runs
+ *     k_adr_count -> scan -> k_adr_scatter -> k_plan_blocks -> k_bias_blocks -> k_bias_fixup -> k_map_count -> scan ->
+ *     k_map_scatter -> k_mapper_chains -> k_count_bins -> scan: what the front half runs behind k_predict.  Writes
+ *     pxs[n] (px | sign << 8), z[n], cnt[n], blk_base[2049], ctx_state_out[2048], map_state_out[512 * 60]; qhist is unused.
+ *   model 1 (QNBLIC): rec1 is px0 | adr << 8 with adr < 3072.  Runs k_adr_count -> scan -> k_adr_scatter -> k_plan_blocks ->
+ *     k_bias_blocks -> k_bias_fixup -> k_q_symbols: what the model stage runs behind k_q_predict.  Writes pxs[n]
+ *     (level | symbol << 8), qhist[12 * 256], blk_base[3073], ctx_state_out[3072]; z, cnt and map_state_out are unused and
+ *     map_state_in must be NULL.
+ * Both write blk_ok[blk_base[keys]], one byte per 4096-record block of every context chain in key order: 1 = the block's
+ * warm-up copies met (or it is the chain's first block).  blk_ok_cap, its capacity, must be at least n / 4096 + keys.
+ * ctx_state_in / map_state_in: NULL = the tables of an image's first row (k_init_state); otherwise they are uploaded
+ * and the chains start from them, as a row band's do (when every table the model has is given, k_init_state is not
+ * launched).  Buffers are the workspace of a group slot of the context (counted by nblic_amd_debug_live).
+ * Returns 0; -1, with nothing launched or allocated, for what it refuses: a null pointer, n outside the range, blk_ok_cap
+ * too small, a record S1 cannot write (model 0: a bit above 26, qv_rel 3, qw > 16, qv outside 0..15; model 1: an address
+ * >= 3072 or a bit above it), a table no sequence of records leaves (|bias| > 32576, model 1: > 1 << 20; re-mapper tables
+ * that are not inverse permutations of 0..19, a negative hit count); -2 when a HIP call failed.                          */
+int nblic_amd_debug_model_stages(nblic_amd_ctx *ctx, int model, size_t n, const unsigned char *x, const unsigned int *rec1,
+                                 const int *ctx_state_in, const int *map_state_in, unsigned short *pxs, unsigned char *z,
+                                 unsigned char *cnt, unsigned int *qhist, unsigned int *blk_base, unsigned char *blk_ok,
+                                 size_t blk_ok_cap, int *ctx_state_out, int *map_state_out);
+
+/* Debug hook used by the chain kernels' tests: ONE launch sequence of the back half BEHIND k_emit_bins on n_ev bin events
+ * the caller supplies (1 .. 1 << 22; csrc/model.h pack_event: qu | qv << 4 | node << 8 | qw << 16 | bin << 21), uploaded
+ * verbatim, as one job on its own (not packed): k_touch_count -> scan -> k_touch_scatter -> k_plan_windows ->
+ * k_counter_epochs -> k_counter_probs -> k_mix.  Writes coded[n_ev] (prob | bin << 15), cnt_state_out[4096 * 2]
+ * (c0, c1 per counter, counter = parity * 2048 + (tree >> 1) * 256 + node) and totals[8] (the job's totals words:
+ * [3] the touch count, [4] 1 = 32-bit touch positions were used).  cnt_state_in: NULL = every counter (32, 32);
+ * otherwise uploaded, k_init_state is not launched.
+ * Equal trees with a non-zero qw are accepted: the binarisation walk (model.h walk_symbol) sets qv = qu when the two
+ * levels fall into different groups of k_step levels, and again after every escalation, while the event keeps the
+ * pixel's qw -- such an event touches its one counter twice, with 32 - qw and then qw.  quantise() also gives
+ * qv = qu + 1 with qw 0 (the second touch is dropped).
+ * Returns 0; -1, with nothing launched or allocated, for a null pointer, n_ev outside the range, an event the walk cannot
+ * emit (|qu - qv| > 1, qw > 16, a bit above 21 -- where a level above 15 would end up) or a counter no sequence of
+ * touches leaves (c0 or c1 < 1, c0 + c1 > 8192); -2 when a HIP call failed.                                            */
+int nblic_amd_debug_back_half(nblic_amd_ctx *ctx, size_t n_ev, const unsigned int *events, const int *cnt_state_in,
+                              unsigned short *coded, int *cnt_state_out, unsigned int *totals);
+
 /* Device self-test of the wave primitives the chain kernels rely on (DPP prefix sum against the
  * shuffle formulation).  Returns the number of mismatching lanes (0 = pass) or -1.           */
 int nblic_amd_selftest(nblic_amd_ctx *ctx);

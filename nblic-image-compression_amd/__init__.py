@@ -37,7 +37,7 @@ _lib = None
 EXPORTS = (
     "NBLICcompress", "NBLICdecompress", "QNBLICcompress", "QNBLICdecompress", "QNBLICcompressMultiThread",
     "nblic_amd_create", "nblic_amd_create_ex", "nblic_amd_destroy", "nblic_amd_encode_batch", "nblic_amd_encode_batch_begin", "nblic_amd_encode_batch_end", "nblic_amd_qencode_batch", "nblic_amd_set_max_pixels",
-    "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage", "nblic_amd_debug_live", "nblic_amd_debug_takes", "nblic_amd_debug_pack_rows", "nblic_amd_debug_device_code",
+    "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage", "nblic_amd_debug_live", "nblic_amd_debug_takes", "nblic_amd_debug_pack_rows", "nblic_amd_debug_device_code", "nblic_amd_debug_model_stages", "nblic_amd_debug_back_half",
     "nblic_amd_encode_batch_modes", "nblic_amd_decode_batch", "nblic_amd_serial_selftest",
     "nblic_amd_set_serial_rows", "nblic_amd_serial_launches", "nblic_amd_lsq_redo_counts", "nblic_amd_serial_plan", "nblic_amd_lsq_probe", "nblic_amd_set_feed_chunk", "nblic_amd_last_fed_bytes",
     "nblic_amd_stream_begin", "nblic_amd_stream_resume", "nblic_amd_stream_run", "nblic_amd_stream_checkpoint", "nblic_amd_stream_progress",
@@ -233,6 +233,11 @@ def load_library() -> C.CDLL:
         lib.nblic_amd_debug_device_code.restype = C.c_int
         lib.nblic_amd_debug_device_code.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), ip, ip, C.c_int, C.POINTER(C.c_void_p),
                                                     C.POINTER(C.c_size_t), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_void_p), C.POINTER(C.c_long)]
+    if hasattr(lib, "nblic_amd_debug_model_stages"):
+        lib.nblic_amd_debug_model_stages.restype = C.c_int
+        lib.nblic_amd_debug_model_stages.argtypes = [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p, C.c_void_p]
+        lib.nblic_amd_debug_back_half.restype = C.c_int
+        lib.nblic_amd_debug_back_half.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
     lib.nblic_amd_selftest.restype = C.c_int
     lib.nblic_amd_selftest.argtypes = [C.c_void_p]
     lib.nblic_amd_syn1.restype = None
@@ -883,6 +888,56 @@ class Context:
         if rc != 0:
             raise RuntimeError("nblic_amd_debug_device_code failed")
         return [None if lens[i] < 0 else outs[i][: lens[i]].tobytes() for i in range(k)]
+
+    def debug_model_stages(self, model: int, x, rec1, ctx_state=None, map_state=None) -> dict:
+        """One launch sequence of the staged model stages behind S1 on the caller's own records
+        (``nblic_amd_debug_model_stages``): ``model`` 0 NBLIC -e1 (``rec1`` = ``pack_s1`` words), 1 QNBLIC
+        (``px0 | adr << 8``); ``x`` the pixel values; ``ctx_state`` / ``map_state`` the tables to start from (None: an
+        image's first).  Everything is handed over as it is: the library does the refusing (``ValueError``).  Returns
+        the arrays the header names, ``blk_ok`` cut to ``blk_base[-1]``."""
+        x = None if x is None else np.ascontiguousarray(x, np.uint8)
+        rec1 = None if rec1 is None else np.ascontiguousarray(rec1, np.uint32)
+        n = 0 if rec1 is None else int(rec1.size)
+        keys = 3072 if model == 1 else 2048
+        cs = None if ctx_state is None else np.ascontiguousarray(ctx_state, np.int32)
+        ms = None if map_state is None else np.ascontiguousarray(map_state, np.int32)
+        out = dict(pxs=np.zeros(max(n, 1), np.uint16), blk_base=np.zeros(keys + 1, np.uint32), blk_ok=np.zeros(n // 4096 + keys, np.uint8),
+                   ctx_state=np.zeros(keys, np.int32))
+        if model == 1:
+            out["qhist"] = np.zeros(12 * 256, np.uint32)
+        else:
+            out.update(z=np.zeros(max(n, 1), np.uint8), cnt=np.zeros(max(n, 1), np.uint8), map_state=np.zeros(512 * 60, np.int32))
+        p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        rc = self.lib.nblic_amd_debug_model_stages(
+            self.handle, int(model), n, p(x), p(rec1), p(cs), p(ms), p(out["pxs"]), p(out.get("z")), p(out.get("cnt")), p(out.get("qhist")),
+            p(out["blk_base"]), p(out["blk_ok"]), out["blk_ok"].size, p(out["ctx_state"]), p(out.get("map_state")))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_model_stages refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_model_stages failed")
+        for k in ("pxs", "z", "cnt"):
+            if k in out:
+                out[k] = out[k][:n]
+        out["blk_ok"] = out["blk_ok"][: int(out["blk_base"][keys])]
+        return out
+
+    def debug_back_half(self, events, cnt_state=None) -> dict:
+        """One launch sequence of the back half behind ``k_emit_bins`` on the caller's own bin events
+        (``nblic_amd_debug_back_half``; ``pack_event`` words), from ``cnt_state`` (None: every counter (32, 32)).
+        Returns ``coded``, ``cnt_state`` and ``totals``; raises ``ValueError`` for what the library refuses."""
+        ev = None if events is None else np.ascontiguousarray(events, np.uint32)
+        n = 0 if ev is None else int(ev.size)
+        cs = None if cnt_state is None else np.ascontiguousarray(cnt_state, np.int32)
+        out = dict(coded=np.zeros(max(n, 1), np.uint16), cnt_state=np.zeros(4096 * 2, np.int32), totals=np.zeros(8, np.uint32))
+        p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        rc = self.lib.nblic_amd_debug_back_half(self.handle, n, p(ev), p(cs), p(out["coded"]), p(out["cnt_state"]), p(out["totals"]))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_back_half refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_back_half failed")
+        out["coded"] = out["coded"][:n]
+        return out
+
 
 
 class DeviceCoderGuardError(RuntimeError):

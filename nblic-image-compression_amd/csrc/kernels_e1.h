@@ -120,5 +120,13 @@ void e1_launch_front_pre(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, h
 // QNBLIC (effort 0) model stage for a group: leaves level | symbol << 8 per pixel in `pxs` and the
 // 12 x 256 histograms in `qhist`; the entropy stage (normalise, histogram code, rANS) is host work.
 void q_launch_model(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s);
+// The same launch sequences from caller-made records instead of an image (the debug entries of pipeline.hip,
+// tests/test_chain_kernels.py): the front half behind S1 from b.rec1 (model.h pack_s1) and b.img (h * w = n values, read as
+// a flat array), QNBLIC's model stage behind k_q_predict from b.rec1 (px0 | adr << 8), the back half behind k_emit_bins
+// from b.events and n_ev.  Nothing is initialised: the model tables are the caller's (band semantics; e1_launch_init writes
+// an image's first ones).
+void e1_launch_model_stages(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s);
+void q_launch_model_stages(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s);
+void e1_launch_back_stages(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s);
 
 }  // namespace nblic

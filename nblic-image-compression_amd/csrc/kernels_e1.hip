@@ -1557,6 +1557,28 @@ SegPlan make_plan(uint32_t n_items, uint32_t max_segments) {
     return p;
 }
 
+// The front half behind S1, from the S1 records in b.rec1: partition by context, the context chains, partition by
+// re-mapper, the re-mapper chains, the bin counts and their scan.  19 launches.  `model_done`, if given, is recorded
+// behind k_bias_fixup.
+static void front_behind_s1(const E1Job *d_jobs, int n_jobs, int max_nseg, uint32_t max_n, hipStream_t s, Marker &mark, hipEvent_t model_done) {
+    const dim3 seg_grid(pad8(cdiv(max_nseg, 4)), n_jobs), px_grid(pad8(cdiv(max_n, 256)), n_jobs);
+    mark(); hipLaunchKernelGGL(k_adr_count<NbModel>, seg_grid, dim3(256), 0, s, d_jobs);
+    scan_exclusive<0>(d_jobs, n_jobs, uint32_t(kContexts) * max_nseg, s, mark);
+    mark(); hipLaunchKernelGGL(k_adr_scatter<NbModel>, seg_grid, dim3(256), 0, s, d_jobs);
+    mark(); hipLaunchKernelGGL(k_plan_blocks<NbModel>, dim3(1, n_jobs), dim3(1024), 0, s, d_jobs);
+    const unsigned max_blocks = max_n / kBiasBlock + unsigned(kContexts);
+    mark(); hipLaunchKernelGGL(k_bias_blocks<NbModel>, dim3(cdiv(max_blocks, 64), n_jobs), dim3(64), 0, s, d_jobs);
+    mark(); hipLaunchKernelGGL(k_bias_fixup<NbModel>, dim3(kContexts / 64, n_jobs), dim3(64), 0, s, d_jobs);
+    if (model_done) hipEventRecord(model_done, s);
+    mark(); hipLaunchKernelGGL(k_map_count, seg_grid, dim3(256), 0, s, d_jobs);
+    scan_exclusive<1>(d_jobs, n_jobs, 512u * max_nseg, s, mark);
+    mark(); hipLaunchKernelGGL(k_map_scatter<false>, seg_grid, dim3(256), 0, s, d_jobs);
+    mark(); hipLaunchKernelGGL(k_mapper_chains, dim3(512 / kMapLanes, n_jobs), dim3(64), 0, s, d_jobs);
+    mark(); hipLaunchKernelGGL(k_count_bins<false>, px_grid, dim3(256), 0, s, d_jobs);
+    scan_exclusive<2>(d_jobs, n_jobs, max_n, s, mark);
+    mark();                                                     // start of the host gap (index 20)
+}
+
 // Front half for a group of jobs: everything up to the per-pixel bin counts and their scan
 // (the event totals are needed on the host before the event buffers can be sized).  18 launches.
 // BAND: the jobs are row bands of images whose earlier rows have been coded (E1Job::row0): the model tables are the
@@ -1569,7 +1591,6 @@ static void launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, h
         max_w = h_jobs[k].w > max_w ? h_jobs[k].w : max_w; max_h = h_jobs[k].h > max_h ? h_jobs[k].h : max_h;
         max_n = h_jobs[k].n > max_n ? h_jobs[k].n : max_n; max_nseg = h_jobs[k].pp.nseg > max_nseg ? h_jobs[k].pp.nseg : max_nseg;
     }
-    const dim3 seg_grid(pad8(cdiv(max_nseg, 4)), n_jobs), px_grid(pad8(cdiv(max_n, 256)), n_jobs);
     Marker mark{tm, s, 0};
     if (!BAND) { mark(); hipLaunchKernelGGL(k_init_state, dim3(16, n_jobs), dim3(256), 0, s, d_jobs); }   // (a band launch is not timed by stage: tm is null)
     mark();                                                     // one timed stage "k_predict": interior rows + the two border launches
@@ -1587,21 +1608,7 @@ static void launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, h
         hipLaunchKernelGGL(k_predict_border<false>, dim3(cdiv(max_w, 64), max_h < 2 ? max_h : 2, n_jobs), dim3(64), 0, s, d_jobs, 1);
         if (max_h > 2) hipLaunchKernelGGL(k_predict_border<false>, dim3(1, max_h - 2, n_jobs), dim3(64), 0, s, d_jobs, 0);
     }
-    mark(); hipLaunchKernelGGL(k_adr_count<NbModel>, seg_grid, dim3(256), 0, s, d_jobs);
-    scan_exclusive<0>(d_jobs, n_jobs, uint32_t(kContexts) * max_nseg, s, mark);
-    mark(); hipLaunchKernelGGL(k_adr_scatter<NbModel>, seg_grid, dim3(256), 0, s, d_jobs);
-    mark(); hipLaunchKernelGGL(k_plan_blocks<NbModel>, dim3(1, n_jobs), dim3(1024), 0, s, d_jobs);
-    const unsigned max_blocks = max_n / kBiasBlock + unsigned(kContexts);
-    mark(); hipLaunchKernelGGL(k_bias_blocks<NbModel>, dim3(cdiv(max_blocks, 64), n_jobs), dim3(64), 0, s, d_jobs);
-    mark(); hipLaunchKernelGGL(k_bias_fixup<NbModel>, dim3(kContexts / 64, n_jobs), dim3(64), 0, s, d_jobs);
-    if (BAND && model_done) hipEventRecord(model_done, s);
-    mark(); hipLaunchKernelGGL(k_map_count, seg_grid, dim3(256), 0, s, d_jobs);
-    scan_exclusive<1>(d_jobs, n_jobs, 512u * max_nseg, s, mark);
-    mark(); hipLaunchKernelGGL(k_map_scatter<false>, seg_grid, dim3(256), 0, s, d_jobs);
-    mark(); hipLaunchKernelGGL(k_mapper_chains, dim3(512 / kMapLanes, n_jobs), dim3(64), 0, s, d_jobs);
-    mark(); hipLaunchKernelGGL(k_count_bins<false>, px_grid, dim3(256), 0, s, d_jobs);
-    scan_exclusive<2>(d_jobs, n_jobs, max_n, s, mark);
-    mark();                                                     // start of the host gap (index 20)
+    front_behind_s1(d_jobs, n_jobs, max_nseg, max_n, s, mark, BAND ? model_done : nullptr);
 }
 
 void e1_launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s, E1Timers *tm) {
@@ -1610,6 +1617,15 @@ void e1_launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipSt
 
 void e1_launch_front_band(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s, hipEvent_t model_done) {
     launch_front<true>(d_jobs, h_jobs, n_jobs, s, nullptr, model_done);
+}
+
+void e1_launch_model_stages(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s) {
+    int max_nseg = 0; uint32_t max_n = 0;
+    for (int k = 0; k < n_jobs; k++) {
+        max_n = h_jobs[k].n > max_n ? h_jobs[k].n : max_n; max_nseg = h_jobs[k].pp.nseg > max_nseg ? h_jobs[k].pp.nseg : max_nseg;
+    }
+    Marker mark{nullptr, s, 0};
+    front_behind_s1(d_jobs, n_jobs, max_nseg, max_n, s, mark, nullptr);
 }
 
 // Front half of the serial modes: rec1 and px | sign per pixel come from the serial model stage
@@ -1638,18 +1654,10 @@ void e1_launch_index_records(const E1Job *d_jobs, const IndexRecordTask *d_tasks
     if (n_tasks > 0) hipLaunchKernelGGL(k_index_records, dim3(unsigned(n_tasks)), dim3(256), 0, s, d_jobs, d_tasks, d_out);
 }
 
-// Back half: needs n_ev / pe filled in the job records and event-sized buffers.  10 launches.
-void e1_launch_back(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s, E1Timers *tm, bool general) {
-    int max_nseg = 0; uint32_t max_n = 0, max_ev = 0;
-    for (int k = 0; k < n_jobs; k++) {
-        max_n = h_jobs[k].n > max_n ? h_jobs[k].n : max_n; max_ev = h_jobs[k].n_ev > max_ev ? h_jobs[k].n_ev : max_ev;
-        max_nseg = h_jobs[k].pe.nseg > max_nseg ? h_jobs[k].pe.nseg : max_nseg;
-    }
+// The back half behind k_emit_bins, from the bin events in b.events: partition the counter touches, the counter
+// chains, the mix; k_pack_rows behind it when the launch has packs.  9 launches (10 with packs).
+static void back_behind_emit(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, int max_nseg, uint32_t max_ev, hipStream_t s, Marker &mark) {
     const dim3 seg_grid(pad8(cdiv(max_nseg, 4)), n_jobs);
-    Marker mark{tm, s, 21};
-    mark();
-    if (general) hipLaunchKernelGGL(k_emit_bins<true>, dim3(pad8(cdiv(max_n, 256)), n_jobs), dim3(256), 0, s, d_jobs);
-    else hipLaunchKernelGGL(k_emit_bins<false>, dim3(pad8(cdiv(max_n, 256)), n_jobs), dim3(256), 0, s, d_jobs);
     mark(); hipLaunchKernelGGL(k_touch_count, seg_grid, dim3(256), 0, s, d_jobs);
     scan_exclusive<3>(d_jobs, n_jobs, 4096u * max_nseg, s, mark);
     mark();
@@ -1666,16 +1674,34 @@ void e1_launch_back(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStr
     mark();                                                     // index 31: end
 }
 
-void q_launch_model(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s) {
-    int max_w = 0, max_h = 0, max_nseg = 0; uint32_t max_n = 0;
+// Back half: needs n_ev / pe filled in the job records and event-sized buffers.  10 launches.
+void e1_launch_back(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s, E1Timers *tm, bool general) {
+    int max_nseg = 0; uint32_t max_n = 0, max_ev = 0;
     for (int k = 0; k < n_jobs; k++) {
-        max_w = h_jobs[k].w > max_w ? h_jobs[k].w : max_w; max_h = h_jobs[k].h > max_h ? h_jobs[k].h : max_h;
-        max_n = h_jobs[k].n > max_n ? h_jobs[k].n : max_n; max_nseg = h_jobs[k].pp.nseg > max_nseg ? h_jobs[k].pp.nseg : max_nseg;
+        max_n = h_jobs[k].n > max_n ? h_jobs[k].n : max_n; max_ev = h_jobs[k].n_ev > max_ev ? h_jobs[k].n_ev : max_ev;
+        max_nseg = h_jobs[k].pe.nseg > max_nseg ? h_jobs[k].pe.nseg : max_nseg;
     }
+    Marker mark{tm, s, 21};
+    mark();
+    if (general) hipLaunchKernelGGL(k_emit_bins<true>, dim3(pad8(cdiv(max_n, 256)), n_jobs), dim3(256), 0, s, d_jobs);
+    else hipLaunchKernelGGL(k_emit_bins<false>, dim3(pad8(cdiv(max_n, 256)), n_jobs), dim3(256), 0, s, d_jobs);
+    back_behind_emit(d_jobs, h_jobs, n_jobs, max_nseg, max_ev, s, mark);
+}
+
+void e1_launch_back_stages(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s) {
+    int max_nseg = 0; uint32_t max_ev = 0;
+    for (int k = 0; k < n_jobs; k++) {
+        max_ev = h_jobs[k].n_ev > max_ev ? h_jobs[k].n_ev : max_ev; max_nseg = h_jobs[k].pe.nseg > max_nseg ? h_jobs[k].pe.nseg : max_nseg;
+    }
+    Marker mark{nullptr, s, 22};
+    back_behind_emit(d_jobs, h_jobs, n_jobs, max_nseg, max_ev, s, mark);
+}
+
+// QNBLIC's model stage behind k_q_predict, from px0 | adr << 8 in b.rec1: partition by context, the context chains, the
+// symbols and their histograms.  9 launches.
+static void q_behind_predict(const E1Job *d_jobs, int n_jobs, int max_nseg, uint32_t max_n, hipStream_t s) {
     const dim3 seg_grid(pad8(cdiv(max_nseg, 4)), n_jobs);
     Marker mark{nullptr, s, 0};
-    hipLaunchKernelGGL(k_init_state, dim3(16, n_jobs), dim3(256), 0, s, d_jobs);
-    hipLaunchKernelGGL(k_q_predict, dim3(cdiv(max_w, 256), max_h, n_jobs), dim3(256), 0, s, d_jobs);
     hipLaunchKernelGGL(k_adr_count<QModel>, seg_grid, dim3(256), 0, s, d_jobs);
     scan_exclusive<4>(d_jobs, n_jobs, 3072u * max_nseg, s, mark);
     hipLaunchKernelGGL(k_adr_scatter<QModel>, seg_grid, dim3(256), 0, s, d_jobs);
@@ -1685,6 +1711,25 @@ void q_launch_model(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStr
     hipLaunchKernelGGL(k_bias_fixup<QModel>, dim3(3072 / 64, n_jobs), dim3(64), 0, s, d_jobs);
     unsigned sym_blocks = cdiv(max_n, 256 * 16);                      // 16 pixels per thread: fewer global histogram merges
     hipLaunchKernelGGL(k_q_symbols, dim3(pad8(sym_blocks ? sym_blocks : 1), n_jobs), dim3(256), 0, s, d_jobs);
+}
+
+void q_launch_model(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s) {
+    int max_w = 0, max_h = 0, max_nseg = 0; uint32_t max_n = 0;
+    for (int k = 0; k < n_jobs; k++) {
+        max_w = h_jobs[k].w > max_w ? h_jobs[k].w : max_w; max_h = h_jobs[k].h > max_h ? h_jobs[k].h : max_h;
+        max_n = h_jobs[k].n > max_n ? h_jobs[k].n : max_n; max_nseg = h_jobs[k].pp.nseg > max_nseg ? h_jobs[k].pp.nseg : max_nseg;
+    }
+    hipLaunchKernelGGL(k_init_state, dim3(16, n_jobs), dim3(256), 0, s, d_jobs);
+    hipLaunchKernelGGL(k_q_predict, dim3(cdiv(max_w, 256), max_h, n_jobs), dim3(256), 0, s, d_jobs);
+    q_behind_predict(d_jobs, n_jobs, max_nseg, max_n, s);
+}
+
+void q_launch_model_stages(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s) {
+    int max_nseg = 0; uint32_t max_n = 0;
+    for (int k = 0; k < n_jobs; k++) {
+        max_n = h_jobs[k].n > max_n ? h_jobs[k].n : max_n; max_nseg = h_jobs[k].pp.nseg > max_nseg ? h_jobs[k].pp.nseg : max_nseg;
+    }
+    q_behind_predict(d_jobs, n_jobs, max_nseg, max_n, s);
 }
 
 }  // namespace nblic

@@ -3207,6 +3207,133 @@ int nblic_amd_debug_device_code(nblic_amd_ctx *c, int n_jobs, const unsigned sho
     return intact ? 0 : -3;
 }
 
+// ---- the staged pipeline behind S1 on caller-made records (tests/test_chain_kernels.py) --------------------------------
+// A carried-in table is accepted when some sequence of records can have left it there.
+static bool ctx_table_ok(const int *v, int keys, int extreme) {
+    for (int k = 0; k < keys; k++) if (v[k] < -extreme || v[k] > extreme) return false;
+    return true;
+}
+static bool map_table_ok(const int *t) {             // per re-mapper: symbol -> rank, rank -> symbol (inverse permutations of 0..19), hit counts by rank
+    for (int key = 0; key < 512; key++) {
+        const int *rank_of = t + key * 3 * kMapSyms, *sym_at = rank_of + kMapSyms, *count = sym_at + kMapSyms;
+        for (int k = 0; k < kMapSyms; k++) {
+            if (rank_of[k] < 0 || rank_of[k] >= kMapSyms || sym_at[rank_of[k]] != k) return false;
+            if (count[k] < 0 || count[k] > (1 << 30)) return false;
+        }
+    }
+    return true;
+}
+static bool cnt_table_ok(const int *t) {
+    for (int k = 0; k < 4096; k++) if (!counter_ok(t[2 * k], t[2 * k + 1])) return false;
+    return true;
+}
+constexpr size_t kDebugMaxRecords = size_t(1) << 22;
+
+int nblic_amd_debug_model_stages(nblic_amd_ctx *c, int model, size_t n, const unsigned char *x, const unsigned int *rec1,
+                                 const int *ctx_state_in, const int *map_state_in, unsigned short *pxs, unsigned char *z,
+                                 unsigned char *cnt, unsigned int *qhist, unsigned int *blk_base, unsigned char *blk_ok,
+                                 size_t blk_ok_cap, int *ctx_state_out, int *map_state_out) {
+    if (!c || (model != 0 && model != 1) || n < 1 || n > kDebugMaxRecords) return -1;
+    const bool q = model == 1;
+    const int keys = q ? 3072 : kContexts;
+    if (!x || !rec1 || !pxs || !blk_base || !blk_ok || !ctx_state_out) return -1;
+    if (q ? (!qhist || map_state_in) : (!z || !cnt || !map_state_out)) return -1;
+    if (blk_ok_cap < n / 4096 + size_t(keys)) return -1;                    // every chain has one partial block at the most
+    for (size_t t = 0; t < n; t++) {
+        const uint32_t r = rec1[t];
+        if (q) { if ((r >> 8) >= 3072u) return -1; continue; }              // (the level is the address's high bits: 0..11)
+        const Level L = s1_level(r);
+        if ((r >> 27) != 0u || ((r >> 25) & 3u) == 3u || L.qw > kWeightOne / 2 || L.qv < 0 || L.qv >= kLevels) return -1;
+    }
+    if (ctx_state_in && !ctx_table_ok(ctx_state_in, keys, q ? (1 << 20) : 32576)) return -1;
+    if (map_state_in && !map_table_ok(map_state_in)) return -1;
+    std::lock_guard<std::mutex> g(c->api);
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    const int id = take_group(c);
+    Group &grp = c->groups[size_t(id)];
+    Slot &s = grp.slots[0];
+    const bool ok = [&]() -> bool {
+        grp.n_jobs = 1; s.job = 0; s.h = 1; s.w = int(n); s.near = 0; s.effort = q ? 0 : 1; s.n_ev = 0;
+        if (!ensure_pixels(s, n, false)) return false;
+        HIP_OK(s.d_img.reserve(n));
+        s.b.img = s.d_img;
+        grp.h_jobs[0] = e1_job_front(s.b, 1, int(n), 0, q ? 0 : dbg_flags());
+        hipStream_t st = grp.stream;
+        HIP_OK(hipMemcpyAsync(s.d_img, x, n, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(s.b.rec1, rec1, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(grp.d_jobs, grp.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, st));
+        // a table that is not given is k_init_state's; a given one goes in behind it, or instead of it
+        if (!ctx_state_in || (!q && !map_state_in)) e1_launch_init(grp.d_jobs, 1, st);
+        else if (q) HIP_OK(hipMemsetAsync(s.b.qhist, 0, 12 * 256 * sizeof(uint32_t), st));
+        if (ctx_state_in) HIP_OK(hipMemcpyAsync(s.b.ctx_state, ctx_state_in, size_t(keys) * sizeof(int), hipMemcpyHostToDevice, st));
+        if (map_state_in) HIP_OK(hipMemcpyAsync(s.b.map_state, map_state_in, size_t(512) * 60 * sizeof(int), hipMemcpyHostToDevice, st));
+        if (q) q_launch_model_stages(grp.d_jobs, grp.h_jobs, 1, st); else e1_launch_model_stages(grp.d_jobs, grp.h_jobs, 1, st);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(pxs, s.b.pxs, n * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(blk_base, s.b.blk_base, size_t(keys + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(ctx_state_out, s.b.ctx_state, size_t(keys) * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (q) {
+            HIP_OK(hipMemcpyAsync(qhist, s.b.qhist, 12 * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        } else {
+            HIP_OK(hipMemcpyAsync(z, s.b.z, n, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(cnt, s.b.cnt, n, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(map_state_out, s.b.map_state, size_t(512) * 60 * sizeof(int), hipMemcpyDeviceToHost, st));
+        }
+        HIP_OK(hipStreamSynchronize(st));
+        const size_t blocks = blk_base[keys];
+        if (blocks > blk_ok_cap) return false;
+        HIP_OK(hipMemcpy(blk_ok, s.b.blk_ok, blocks, hipMemcpyDeviceToHost));
+        return true;
+    }();
+    grp.tm_pending = false;
+    release_group(c, id);
+    return ok ? 0 : -2;
+}
+
+int nblic_amd_debug_back_half(nblic_amd_ctx *c, size_t n_ev, const unsigned int *events, const int *cnt_state_in,
+                              unsigned short *coded, int *cnt_state_out, unsigned int *totals) {
+    if (!c || n_ev < 1 || n_ev > kDebugMaxRecords || !events || !coded || !cnt_state_out || !totals) return -1;
+    for (size_t r = 0; r < n_ev; r++) {
+        const uint32_t e = events[r];
+        const int d = ev_qu(e) - ev_qv(e);
+        if ((e >> 22) != 0u || d < -1 || d > 1 || ev_qw(e) > kWeightOne / 2) return -1;
+    }
+    if (cnt_state_in && !cnt_table_ok(cnt_state_in)) return -1;
+    std::lock_guard<std::mutex> g(c->api);
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    const int id = take_group(c);
+    Group &grp = c->groups[size_t(id)];
+    Slot &s = grp.slots[0];
+    DevBuf<uint16_t> d_coded;                                               // (a production image's comes from the context's pool and goes to a coder thread)
+    const bool ok = [&]() -> bool {
+        grp.n_jobs = 1; s.job = 0; s.h = 0; s.w = 0; s.near = 0; s.effort = 1; s.n_ev = uint32_t(n_ev);
+        if (!ensure_events(s, n_ev)) return false;
+        HIP_OK(d_coded.alloc(n_ev));
+        E1Job J = e1_job_front(s.b, 0, 0, 0, dbg_flags());
+        E1Buffers b = s.b;
+        b.coded = d_coded;
+        e1_job_back(J, b, uint32_t(n_ev));
+        grp.h_jobs[0] = J;
+        hipStream_t st = grp.stream;
+        HIP_OK(hipMemcpyAsync(s.b.events, events, n_ev * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(grp.d_jobs, grp.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(s.b.totals, 0, kTotalsStride * sizeof(uint32_t), st));
+        if (cnt_state_in) HIP_OK(hipMemcpyAsync(s.b.cnt_state, cnt_state_in, size_t(4096) * 2 * sizeof(int), hipMemcpyHostToDevice, st));
+        else e1_launch_init(grp.d_jobs, 1, st);
+        e1_launch_back_stages(grp.d_jobs, grp.h_jobs, 1, st);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(coded, d_coded, n_ev * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(cnt_state_out, s.b.cnt_state, size_t(4096) * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(totals, s.b.totals, kTotalsStride * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    s.n_ev = 0;
+    grp.tm_pending = false;
+    release_group(c, id);
+    return ok ? 0 : -2;
+}
+
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
 
 void nblic_amd_set_max_pixels(nblic_amd_ctx *c, long max_pixels) {

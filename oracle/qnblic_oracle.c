@@ -269,6 +269,30 @@ void orc_q_model(const uint8_t *img, int h, int w, uint8_t *px0_out, uint16_t *a
     free(ctx);
 }
 
+/* The context stage on arrays, for the chain kernels' tests: the bias correction, the symbol and the bias update
+ * (QNBLIC.c:176-202) replayed ONE CONTEXT AT A TIME over a stable partition by address, never in raster order -- what
+ * orc_s2 is for NBLIC.  adr[t] < 3072, px0[t] and x[t] are any bytes (they need not come from an image); ctx_end_out
+ * (optional) receives the 3072 biases after the last record.  Equal to orc_q_model's y on an image's own arrays
+ * (tests/test_oracle_q.py), which proves the decomposition. */
+void orc_q_s2(size_t n, const uint16_t *adr, const uint8_t *px0, const uint8_t *x, uint8_t *y_out, int *ctx_end_out) {
+    size_t *start = (size_t *)calloc(Q_NCTX + 1, sizeof(size_t)), *cur = (size_t *)malloc(sizeof(size_t) * Q_NCTX);
+    size_t *order = (size_t *)malloc(sizeof(size_t) * (n ? n : 1));
+    for (size_t t = 0; t < n; t++) start[adr[t] + 1]++;
+    for (int k = 0; k < Q_NCTX; k++) { start[k + 1] += start[k]; cur[k] = start[k]; }
+    for (size_t t = 0; t < n; t++) order[cur[adr[t]]++] = t;
+    for (int k = 0; k < Q_NCTX; k++) {
+        int v = 0;
+        for (size_t r = start[k]; r < start[k + 1]; r++) {
+            size_t t = order[r]; int sign;
+            int px = q_ctx_correct(v, px0[t], &sign);
+            y_out[t] = (uint8_t)q_x_to_y(x[t], px, sign);
+            v = q_ctx_update(v, (int)x[t] - (int)px0[t]);
+        }
+        if (ctx_end_out) ctx_end_out[k] = v;
+    }
+    free(order); free(cur); free(start);
+}
+
 /* QNBLICcompress (QNBLIC.c:562-655): returns the length in 16-bit words, or -1 */
 long orc_qnblic_encode(uint16_t *out, const uint8_t *img, int h, int w, long max_px) {
     if (max_px <= 0) max_px = 100000000L;

@@ -68,3 +68,40 @@ def test_q_vs_live_reference(oracle):
         assert a == b, img.shape
         if k < len(cases) - 1:
             assert np.array_equal(reference.qdecode(a), img) and np.array_equal(oracle.qdecode(b), img)
+
+
+def _q_model(oracle, img):
+    h, w = img.shape
+    n = h * w
+    u8p, u16p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)
+    px0 = np.empty(n, np.uint8); adr = np.empty(n, np.uint16); qd = np.empty(n, np.uint8); y = np.empty(n, np.uint8)
+    hist = np.zeros(12 * 256, np.uint32)
+    oracle.lib.orc_q_model(img.ctypes.data_as(u8p), h, w, px0.ctypes.data_as(u8p), adr.ctypes.data_as(u16p), qd.ctypes.data_as(u8p),
+                           y.ctypes.data_as(u8p), hist.ctypes.data_as(C.POINTER(C.c_uint32)))
+    return px0, adr, qd, y, hist
+
+
+def test_q_context_stage_on_arrays_equals_the_raster_model(oracle, golden):
+    """orc_q_s2 -- the context stage replayed one context at a time over arrays, the chain kernels' expected output
+    (tests/test_chain_kernels.py) -- gives orc_q_model's symbols on every random case and every small golden image, and
+    the histogram of (level, symbol) pairs it leads to gives the golden / stored stream through orc_q_entropy_stage."""
+    import chain_inputs
+    _, streams = golden
+    _, stored = inputs.fixtures()
+    cases = [(img, stored[f"q_case_{k}"].tobytes()) for k, img in enumerate(inputs.random_q_cases())]
+    cases += [(inputs.make(c, h, w), streams[f"q_{c}_{h}x{w}"].tobytes()) for (h, w) in inputs.SMALL_SHAPES for c in inputs.CONTENTS]
+    u8p = C.POINTER(C.c_uint8)
+    oracle.lib.orc_q_entropy_stage.restype = C.c_long
+    for img, want in cases:
+        img = np.ascontiguousarray(img, np.uint8)
+        h, w = img.shape
+        px0, adr, qd, y, hist = _q_model(oracle, img)
+        got_y, _ = chain_inputs.orc_q_s2(oracle, adr, px0, img.reshape(-1))
+        assert np.array_equal(got_y, y), img.shape
+        assert np.array_equal(qd, adr >> 8), img.shape
+        pairs = np.bincount(qd.astype(np.int64) * 256 + got_y, minlength=12 * 256).astype(np.uint32)
+        assert np.array_equal(pairs, hist), img.shape
+        out = np.empty(2 * h * w + 4096, np.uint16)
+        words = oracle.lib.orc_q_entropy_stage(out.ctypes.data_as(C.POINTER(C.c_uint16)), h, w, qd.ctypes.data_as(u8p), got_y.ctypes.data_as(u8p),
+                                               pairs.ctypes.data_as(C.POINTER(C.c_uint32)))
+        assert out[:words].tobytes() == want, img.shape
