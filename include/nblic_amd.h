@@ -454,6 +454,32 @@ int nblic_amd_debug_model_stages(nblic_amd_ctx *ctx, int model, size_t n, const 
 int nblic_amd_debug_back_half(nblic_amd_ctx *ctx, size_t n_ev, const unsigned int *events, const int *cnt_state_in,
                               unsigned short *coded, int *cnt_state_out, unsigned int *totals);
 
+/* Debug hook used by the entropy front's tests: ONE launch sequence of what a serial-mode band of the band encoder runs
+ * between k_serial_model and the host coder, on n records the caller supplies (1 .. 1 << 22), as one job of 1 x n pixels.
+ * x[n] are the pixel values, rec1[n] the S1 records (csrc/model.h pack_s1; only the levels and qw are read), pxs[n] the
+ * corrected predictions px | sign << 8 -- what k_serial_model leaves per pixel -- all uploaded verbatim; near is 0..9.
+ * The job record is filled as the encoders fill it, which pairs k_step = clip(3 + 2 near, 3, 16) and its level table
+ * with near; then k_map_count_pre -> scan -> k_map_scatter<general> -> k_mapper_chains -> k_count_bins<general> -> scan,
+ * the event total is read, the event-sized buffers are sized, and k_emit_bins<general> -> k_touch_count -> scan ->
+ * k_touch_scatter -> k_plan_windows -> k_counter_epochs -> k_counter_probs -> k_mix (unpacked) follow.
+ * Writes z[n], cnt[n] (bins per record), pos3[n] (the record's place in the re-mapper partition, or 0x80000000 | y for a
+ * symbol >= 20), ev_off[n] (exclusive scan of cnt), events[total] (pack_event words), coded[total] (prob | bin << 15),
+ * map_state_out[512 * 60], cnt_state_out[4096 * 2] and totals[8] (the job's totals words: [1] records in the re-mapper
+ * partition, [2] events, [3] touches, [4] 1 = 32-bit touch positions).  events_cap is the capacity of events and coded.
+ * map_state_in / cnt_state_in: NULL = the tables of an image's first row (k_init_state); otherwise uploaded, and the
+ * chains start from them, as a later band's do (when both are given k_init_state is not launched).
+ * There is no free k_step: the encoder kernels are valid for the paired step only -- near 0 with k_step 16 would need 256
+ * bins for symbol 255, and cnt is a byte.  (The decoders take any pair; tests/test_foreign_streams.py.)
+ * Returns 0; -1, with nothing launched or allocated, for what it refuses: a null pointer, n outside the range, near
+ * outside 0..9, a pxs word >= 512, a record nblic_amd_debug_model_stages refuses, a table it or nblic_amd_debug_back_half
+ * refuses; -2 when a HIP call failed; -3 when the event total (then in totals[2]) exceeds events_cap: the back half was
+ * not launched and no other output is written.                                                                        */
+int nblic_amd_debug_entropy_front(nblic_amd_ctx *ctx, size_t n, const unsigned char *x, const unsigned int *rec1,
+                                  const unsigned short *pxs, int near, const int *map_state_in, const int *cnt_state_in,
+                                  unsigned char *z, unsigned char *cnt, unsigned int *pos3, unsigned int *ev_off,
+                                  unsigned int *events, size_t events_cap, unsigned short *coded, int *map_state_out,
+                                  int *cnt_state_out, unsigned int *totals);
+
 /* Device self-test of the wave primitives the chain kernels rely on (DPP prefix sum against the
  * shuffle formulation).  Returns the number of mismatching lanes (0 = pass) or -1.           */
 int nblic_amd_selftest(nblic_amd_ctx *ctx);

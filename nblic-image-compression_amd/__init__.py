@@ -37,7 +37,7 @@ _lib = None
 EXPORTS = (
     "NBLICcompress", "NBLICdecompress", "QNBLICcompress", "QNBLICdecompress", "QNBLICcompressMultiThread",
     "nblic_amd_create", "nblic_amd_create_ex", "nblic_amd_destroy", "nblic_amd_encode_batch", "nblic_amd_encode_batch_begin", "nblic_amd_encode_batch_end", "nblic_amd_qencode_batch", "nblic_amd_set_max_pixels",
-    "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage", "nblic_amd_debug_live", "nblic_amd_debug_takes", "nblic_amd_debug_pack_rows", "nblic_amd_debug_device_code", "nblic_amd_debug_model_stages", "nblic_amd_debug_back_half",
+    "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage", "nblic_amd_debug_live", "nblic_amd_debug_takes", "nblic_amd_debug_pack_rows", "nblic_amd_debug_device_code", "nblic_amd_debug_model_stages", "nblic_amd_debug_back_half", "nblic_amd_debug_entropy_front",
     "nblic_amd_encode_batch_modes", "nblic_amd_decode_batch", "nblic_amd_serial_selftest",
     "nblic_amd_set_serial_rows", "nblic_amd_serial_launches", "nblic_amd_lsq_redo_counts", "nblic_amd_serial_plan", "nblic_amd_lsq_probe", "nblic_amd_set_feed_chunk", "nblic_amd_last_fed_bytes",
     "nblic_amd_stream_begin", "nblic_amd_stream_resume", "nblic_amd_stream_run", "nblic_amd_stream_checkpoint", "nblic_amd_stream_progress",
@@ -238,6 +238,9 @@ def load_library() -> C.CDLL:
         lib.nblic_amd_debug_model_stages.argtypes = [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p, C.c_void_p]
         lib.nblic_amd_debug_back_half.restype = C.c_int
         lib.nblic_amd_debug_back_half.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 5
+    if hasattr(lib, "nblic_amd_debug_entropy_front"):
+        lib.nblic_amd_debug_entropy_front.restype = C.c_int
+        lib.nblic_amd_debug_entropy_front.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 7 + [C.c_size_t] + [C.c_void_p] * 4
     lib.nblic_amd_selftest.restype = C.c_int
     lib.nblic_amd_selftest.argtypes = [C.c_void_p]
     lib.nblic_amd_syn1.restype = None
@@ -936,6 +939,38 @@ class Context:
         if rc != 0:
             raise RuntimeError("nblic_amd_debug_back_half failed")
         out["coded"] = out["coded"][:n]
+        return out
+
+    def debug_entropy_front(self, x, rec1, pxs, near: int, map_state=None, cnt_state=None) -> dict:
+        """One launch sequence of a serial-mode band's entropy front and back half on the caller's own records
+        (``nblic_amd_debug_entropy_front``): ``x`` the pixel values, ``rec1`` ``pack_s1`` words, ``pxs``
+        ``px | sign << 8``, ``near`` 0..9 (k_step is the library's pairing); ``map_state`` / ``cnt_state`` the tables to
+        start from (None: an image's first).  Everything is handed over as it is: the library does the refusing
+        (``ValueError``).  Returns ``z``, ``cnt``, ``pos3``, ``ev_off``, ``n_ev``, ``events``, ``coded``,
+        ``map_state``, ``cnt_state`` and ``totals``."""
+        x = None if x is None else np.ascontiguousarray(x, np.uint8)
+        rec1 = None if rec1 is None else np.ascontiguousarray(rec1, np.uint32)
+        pxs = None if pxs is None else np.ascontiguousarray(pxs, np.uint16)
+        n = 0 if rec1 is None else int(rec1.size)
+        ms = None if map_state is None else np.ascontiguousarray(map_state, np.int32)
+        cs = None if cnt_state is None else np.ascontiguousarray(cnt_state, np.int32)
+        cap = 64 * max(n, 1)                                   # no paired (near, k_step) walk has more than 56 bins
+        out = dict(z=np.zeros(max(n, 1), np.uint8), cnt=np.zeros(max(n, 1), np.uint8), pos3=np.zeros(max(n, 1), np.uint32),
+                   ev_off=np.zeros(max(n, 1), np.uint32), events=np.empty(cap, np.uint32), coded=np.empty(cap, np.uint16),
+                   map_state=np.zeros(512 * 60, np.int32), cnt_state=np.zeros(4096 * 2, np.int32), totals=np.zeros(8, np.uint32))
+        p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        rc = self.lib.nblic_amd_debug_entropy_front(
+            self.handle, n, p(x), p(rec1), p(pxs), int(near), p(ms), p(cs), p(out["z"]), p(out["cnt"]), p(out["pos3"]), p(out["ev_off"]),
+            p(out["events"]), cap, p(out["coded"]), p(out["map_state"]), p(out["cnt_state"]), p(out["totals"]))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_entropy_front refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_entropy_front failed (%d)" % rc)
+        out["n_ev"] = int(out["totals"][2])
+        for k in ("z", "cnt", "pos3", "ev_off"):
+            out[k] = out[k][:n]
+        for k in ("events", "coded"):
+            out[k] = out[k][: out["n_ev"]].copy()
         return out
 
 

@@ -3334,6 +3334,80 @@ int nblic_amd_debug_back_half(nblic_amd_ctx *c, size_t n_ev, const unsigned int 
     return ok ? 0 : -2;
 }
 
+// ---- the entropy front of the serial modes on caller-made records (tests/test_entropy_front.py) -----------------------
+// What stream_run does for a serial-mode band between k_serial_model and the host coder, once, on arrays the caller owns.
+int nblic_amd_debug_entropy_front(nblic_amd_ctx *c, size_t n, const unsigned char *x, const unsigned int *rec1, const unsigned short *pxs,
+                                  int near, const int *map_state_in, const int *cnt_state_in, unsigned char *z, unsigned char *cnt,
+                                  unsigned int *pos3, unsigned int *ev_off, unsigned int *events, size_t events_cap,
+                                  unsigned short *coded, int *map_state_out, int *cnt_state_out, unsigned int *totals) {
+    if (!c || n < 1 || n > kDebugMaxRecords || near < 0 || near > kMaxNear) return -1;
+    if (!x || !rec1 || !pxs || !z || !cnt || !pos3 || !ev_off || !events || !coded || !map_state_out || !cnt_state_out || !totals) return -1;
+    for (size_t t = 0; t < n; t++) {
+        const uint32_t r = rec1[t];
+        const Level L = s1_level(r);
+        if ((r >> 27) != 0u || ((r >> 25) & 3u) == 3u || L.qw > kWeightOne / 2 || L.qv < 0 || L.qv >= kLevels) return -1;
+        if (pxs[t] >= 512u) return -1;                                      // px | sign << 8: the re-mapper's key is 2 px + sign
+    }
+    if (map_state_in && !map_table_ok(map_state_in)) return -1;
+    if (cnt_state_in && !cnt_table_ok(cnt_state_in)) return -1;
+    std::lock_guard<std::mutex> g(c->api);
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    const int id = take_group(c);
+    Group &grp = c->groups[size_t(id)];
+    Slot &s = grp.slots[0];
+    DevBuf<uint16_t> d_coded;
+    int rc = 0;
+    const bool ok = [&]() -> bool {
+        grp.n_jobs = 1; s.job = 0; s.h = 1; s.w = int(n); s.near = near; s.effort = 1; s.n_ev = 0;
+        if (!ensure_pixels(s, n, false)) return false;
+        HIP_OK(s.d_img.reserve(n));
+        s.b.img = s.d_img;
+        grp.h_jobs[0] = e1_job_front(s.b, 1, int(n), near, 0);              // the one place that pairs k_step and ktab with near
+        hipStream_t st = grp.stream;
+        HIP_OK(hipMemcpyAsync(s.d_img, x, n, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(s.b.rec1, rec1, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(s.b.pxs, pxs, n * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(grp.d_jobs, grp.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(s.b.totals, 0, kTotalsStride * sizeof(uint32_t), st));
+        // a table that is not given is k_init_state's; a given one goes in behind it, or instead of it
+        if (!map_state_in || !cnt_state_in) e1_launch_init(grp.d_jobs, 1, st);
+        if (map_state_in) HIP_OK(hipMemcpyAsync(s.b.map_state, map_state_in, size_t(512) * 60 * sizeof(int), hipMemcpyHostToDevice, st));
+        if (cnt_state_in) HIP_OK(hipMemcpyAsync(s.b.cnt_state, cnt_state_in, size_t(4096) * 2 * sizeof(int), hipMemcpyHostToDevice, st));
+        e1_launch_front_pre(grp.d_jobs, grp.h_jobs, 1, st);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(grp.h_totals, grp.d_totals, kTotalsStride * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        const uint32_t n_ev = grp.h_totals[2];
+        totals[2] = n_ev;
+        if (size_t(n_ev) > events_cap) { rc = -3; return true; }
+        if (n_ev >= 0x7FFFFFFFu || !ensure_events(s, n_ev)) return false;
+        HIP_OK(d_coded.alloc(size_t(n_ev) + 8));
+        E1Buffers b = s.b;
+        b.coded = d_coded;
+        e1_job_back(grp.h_jobs[0], b, n_ev);
+        HIP_OK(hipMemcpyAsync(grp.d_jobs, grp.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, st));
+        e1_launch_back(grp.d_jobs, grp.h_jobs, 1, st, nullptr, true);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(z, s.b.z, n, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(cnt, s.b.cnt, n, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(pos3, s.b.pos3, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(ev_off, s.b.ev_off, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (n_ev) {
+            HIP_OK(hipMemcpyAsync(events, s.b.events, size_t(n_ev) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(coded, d_coded, size_t(n_ev) * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+        }
+        HIP_OK(hipMemcpyAsync(map_state_out, s.b.map_state, size_t(512) * 60 * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(cnt_state_out, s.b.cnt_state, size_t(4096) * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(totals, s.b.totals, kTotalsStride * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    s.n_ev = 0; s.near = 0;
+    grp.tm_pending = false;
+    release_group(c, id);
+    return ok ? rc : -2;
+}
+
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
 
 void nblic_amd_set_max_pixels(nblic_amd_ctx *c, long max_pixels) {

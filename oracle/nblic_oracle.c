@@ -150,6 +150,11 @@ static void walk_count(walk_cov *c, int k_step, int qu, int z) {
     if (ones >= reach) c->beyond_lanes++;
 }
 
+/* Per pixel (raster order, h * w entries each) what the model stage hands to the entropy front, and what that front
+ * makes of it: the prediction and context address, the two levels and their weight, the corrected prediction and its
+ * sign; the symbol y, its rank z and the number of bins it was coded with.  (The reconstruction goes to the image.) */
+struct orc_trace { uint8_t *px0; uint16_t *adr; uint8_t *qu, *qv, *qw, *px, *sign, *y, *z, *bins; };
+
 typedef struct {
     int        near, k_step, effort, n, m, w, h;
     int        ctx[NB_NCTX];
@@ -163,6 +168,7 @@ typedef struct {
     /* statistics, filled when non-NULL */
     long       n_bins;
     walk_cov   cov;                  /* encoder only: which parts of the binarisation walk the image visits */
+    const struct orc_trace *trace;   /* encoder only, optional: per pixel what the model stage hands to the entropy front */
 } engine;
 
 static int engine_bin(void *vp, int qu, int qv, int node, int qw, int bin) {
@@ -229,7 +235,15 @@ static void engine_pixel(engine *en, uint8_t *recon, int i, int j, int decoding,
         int x = recon[(size_t)i * w + j];
         y = nb_x_to_y(x, px, sign, en->near);
         walk_count(&en->cov, en->k_step, qu, nb_mapper_y2z(mp, y));
+        const long bins_before = en->n_bins;
         nb_walk_symbol(en->k_step, qu, qv, qw, nb_mapper_y2z(mp, y), engine_bin, en);
+        if (en->trace) {
+            const struct orc_trace *tr = en->trace; const size_t t = (size_t)i * w + j;
+            tr->px0[t] = (uint8_t)px0; tr->adr[t] = (uint16_t)adr;
+            tr->qu[t] = (uint8_t)qu; tr->qv[t] = (uint8_t)qv; tr->qw[t] = (uint8_t)qw;
+            tr->px[t] = (uint8_t)px; tr->sign[t] = (uint8_t)sign;
+            tr->y[t] = (uint8_t)y; tr->z[t] = (uint8_t)nb_mapper_y2z(mp, y); tr->bins[t] = (uint8_t)(en->n_bins - bins_before);
+        }
     } else {
         y = nb_mapper_z2y(mp, nb_walk_symbol(en->k_step, qu, qv, qw, -1, engine_bin, en));
     }
@@ -271,7 +285,8 @@ static int size_ok(int h, int w, long max_px) {          /* NBLIC.c:717-729 */
  * ---------------------------------------------------------------------- */
 
 /* Header, then the body, with the k_step given: what both encode entry points do once their arguments are settled. */
-static long encode_with(uint8_t *out, uint8_t *img, int h, int w, int near, int k_step, int effort, long max_px, long *n_bins) {
+static long encode_with(uint8_t *out, uint8_t *img, int h, int w, int near, int k_step, int effort, long max_px, long *n_bins,
+                        const struct orc_trace *trace) {
     uint8_t *p = out;
     memcpy(p, NB_MAGIC, 8); p += 8;
     *p++ = 1;
@@ -281,6 +296,7 @@ static long encode_with(uint8_t *out, uint8_t *img, int h, int w, int near, int 
     if (!size_ok(h, w, max_px)) return -1;
     engine *en = (engine *)malloc(sizeof(engine));
     if (!en || engine_init(en, h, w, near, k_step, effort, p, 0)) { free(en); return -1; }
+    en->trace = trace;
     engine_run(en, img, 0);
     long len = (long)(en->rc.p - out);
     if (n_bins) *n_bins = en->n_bins;
@@ -297,7 +313,7 @@ long orc_nblic_encode(uint8_t *out, uint8_t *img, int h, int w, int *near, int *
     *near   = nb_clip(*near, 0, NB_MAX_NEAR);
     *effort = nb_clip(*effort, 1, 3);
     int k_step = nb_clip(NB_MIN_KSTEP + 2 * *near, NB_MIN_KSTEP, NB_NQD);
-    return encode_with(out, img, h, w, *near, k_step, *effort, max_px, n_bins);
+    return encode_with(out, img, h, w, *near, k_step, *effort, max_px, n_bins, NULL);
 }
 
 /* Encode with the k_step given instead of derived from near: the streams the reference's decoder accepts
@@ -306,7 +322,19 @@ long orc_nblic_encode(uint8_t *out, uint8_t *img, int h, int w, int *near, int *
 long orc_nblic_encode_kstep(uint8_t *out, uint8_t *img, int h, int w, int near, int k_step, int effort) {
     if (near < 0 || near > NB_MAX_NEAR || k_step < NB_MIN_KSTEP || k_step > NB_NQD || effort < 1 || effort > 3 ||
         !size_ok(h, w, 100000000L)) return -1;
-    return encode_with(out, img, h, w, near, k_step, effort, 100000000L, NULL);
+    return encode_with(out, img, h, w, near, k_step, effort, 100000000L, NULL, NULL);
+}
+
+/* The fused encoder of any (near, effort) with the k_step the encoders pair with near, which also writes, per pixel, what
+ * its model stage hands to the entropy front (struct orc_trace; every array h * w entries).  `img` is overwritten with
+ * the reconstruction.  Nothing is clamped: -1 for arguments outside near 0..9, effort 1..3.  Returns stream bytes. */
+long orc_nblic_trace(uint8_t *out, uint8_t *img, int h, int w, int near, int effort,
+                     uint8_t *px0, uint16_t *adr, uint8_t *qu, uint8_t *qv, uint8_t *qw,
+                     uint8_t *px, uint8_t *sign, uint8_t *y, uint8_t *z, uint8_t *bins) {
+    if (near < 0 || near > NB_MAX_NEAR || effort < 1 || effort > 3 || !size_ok(h, w, 100000000L)) return -1;
+    const struct orc_trace tr = { px0, adr, qu, qv, qw, px, sign, y, z, bins };
+    const int k_step = nb_clip(NB_MIN_KSTEP + 2 * near, NB_MIN_KSTEP, NB_NQD);
+    return encode_with(out, img, h, w, near, k_step, effort, 100000000L, NULL, &tr);
 }
 
 /* The walk coverage of the last encode of this library: qu[16], k[8], escalations, beyond_lanes. */

@@ -14,6 +14,10 @@
  *   S5  4096 chains by counter: probability of every event          (NBLIC.c:589-637)
  *   S6  one serial chain    : range coder                           (NBLIC.c:552-586)
  *
+ * S3 and S4 also exist for every other mode (orc_s3_near, orc_s4_kstep): behind the model stage -- which at near > 0 or
+ * efforts 2 / 3 is a serial chain through the reconstruction, nblic_oracle.c orc_nblic_trace -- the entropy front is
+ * the same decomposition with the mode's near and k_step.
+ *
  * S2, S3 and S5 deliberately run "all of key 0, then all of key 1, ..." over a
  * stable partition, never in raster order, so a passing byte-compare against
  * the fused engine / the reference is a proof of the decomposition.
@@ -79,7 +83,8 @@ void orc_s2(size_t n, const uint16_t *adr, const uint8_t *px0, const int8_t *err
 }
 
 /* ---- S3 ---------------------------------------------------------------- */
-void orc_s3(size_t n, const uint8_t *img, const uint8_t *px, const uint8_t *sign, uint8_t *y_out, uint8_t *z_out) {
+/* any near: the symbol is the quantised residual (NBLIC.c:431-466); the chains are the same */
+void orc_s3_near(size_t n, const uint8_t *img, const uint8_t *px, const uint8_t *sign, int near, uint8_t *y_out, uint8_t *z_out) {
     uint32_t *key = (uint32_t *)malloc(sizeof(uint32_t) * (n ? n : 1));
     size_t start[512 + 1];
     for (size_t t = 0; t < n; t++) key[t] = (uint32_t)px[t] * 2 + sign[t];
@@ -88,13 +93,17 @@ void orc_s3(size_t n, const uint8_t *img, const uint8_t *px, const uint8_t *sign
         nb_mapper m; nb_mapper_init(&m);
         for (size_t r = start[k]; r < start[k + 1]; r++) {
             size_t t = order[r];
-            int y = nb_x_to_y(img[t], px[t], sign[t], 0);
+            int y = nb_x_to_y(img[t], px[t], sign[t], near);
             y_out[t] = (uint8_t)y;
             z_out[t] = (uint8_t)nb_mapper_y2z(&m, y);
             nb_mapper_observe(&m, y);
         }
     }
     free(order); free(key);
+}
+
+void orc_s3(size_t n, const uint8_t *img, const uint8_t *px, const uint8_t *sign, uint8_t *y_out, uint8_t *z_out) {
+    orc_s3_near(n, img, px, sign, 0, y_out, z_out);
 }
 
 /* ---- S4 ---------------------------------------------------------------- */
@@ -111,16 +120,22 @@ static int ev_emit(void *vp, int qu, int qv, int node, int qw, int bin) {
     return bin;
 }
 
-/* first call with cu==NULL to size, then again to fill.  ev_count[t] (optional) = events of pixel t */
-size_t orc_s4(size_t n, const uint8_t *qu, const uint8_t *qv, const uint8_t *qw, const uint8_t *z,
-              uint16_t *cu, uint16_t *cv, uint8_t *ev_qw, uint8_t *ev_bin, uint8_t *ev_count) {
+/* first call with cu==NULL to size, then again to fill.  ev_count[t] (optional) = events of pixel t.
+ * Any k_step 3..16: the walk of a near-lossless mode is the walk with that mode's step. */
+size_t orc_s4_kstep(size_t n, int k_step, const uint8_t *qu, const uint8_t *qv, const uint8_t *qw, const uint8_t *z,
+                    uint16_t *cu, uint16_t *cv, uint8_t *ev_qw, uint8_t *ev_bin, uint8_t *ev_count) {
     ev_sink s = { cu, cv, ev_qw, ev_bin, 0, cu == NULL };
     for (size_t t = 0; t < n; t++) {
         size_t before = s.n;
-        nb_walk_symbol(KSTEP_LOSSLESS, qu[t], qv[t], qw[t], z[t], ev_emit, &s);
+        nb_walk_symbol(k_step, qu[t], qv[t], qw[t], z[t], ev_emit, &s);
         if (ev_count) ev_count[t] = (uint8_t)(s.n - before);
     }
     return s.n;
+}
+
+size_t orc_s4(size_t n, const uint8_t *qu, const uint8_t *qv, const uint8_t *qw, const uint8_t *z,
+              uint16_t *cu, uint16_t *cv, uint8_t *ev_qw, uint8_t *ev_bin, uint8_t *ev_count) {
+    return orc_s4_kstep(n, KSTEP_LOSSLESS, qu, qv, qw, z, cu, cv, ev_qw, ev_bin, ev_count);
 }
 
 /* ---- S5 ----------------------------------------------------------------

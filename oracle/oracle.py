@@ -156,6 +156,62 @@ class Oracle:
         return dict(px0=px0, err=err, qu=qu, qv=qv, qw=qw, adr=adr, px=px, sign=sign, y=y, z=z,
                     ev_count=cnt, cu=cu, cv=cv, ev_qw=eqw, ev_bin=ebin, prob=prob, body=out[:nbody].tobytes())
 
+    # -- the staged entropy front of every mode ---------------------------
+    def trace(self, img: np.ndarray, near: int = 0, effort: int = 1) -> dict:
+        """The fused encoder of (near, effort), k_step paired with near (orc_nblic_trace): ``stream``, ``recon`` and, per
+        pixel in raster order, what the model stage hands to the entropy front (``px0``, ``adr``, ``qu``, ``qv``,
+        ``qw``, ``px``, ``sign``) and what the front makes of it (``y``, ``z``, ``bins``)."""
+        img = np.ascontiguousarray(img, np.uint8)
+        h, w = img.shape
+        rec = img.copy()
+        out = np.empty(out_capacity(h, w), np.uint8)
+        names = ("px0", "adr", "qu", "qv", "qw", "px", "sign", "y", "z", "bins")
+        t = {k: np.empty(h * w, np.uint16 if k == "adr" else np.uint8) for k in names}
+        fn = self.lib.orc_nblic_trace
+        fn.restype = C.c_long
+        ln = fn(_ptr(out), _ptr(rec), h, w, int(near), int(effort), *[C.c_void_p(t[k].ctypes.data) for k in names])
+        if ln < 0:
+            raise ValueError("orc_nblic_trace refused its arguments")
+        t.update(stream=out[:ln].tobytes(), recon=rec)
+        return t
+
+    def s3_near(self, x, px, sign, near: int):
+        """orc_s3_near on flat arrays: (y, z)."""
+        x, px, sign = (np.ascontiguousarray(a, np.uint8).reshape(-1) for a in (x, px, sign))
+        y, z = np.empty(x.size, np.uint8), np.empty(x.size, np.uint8)
+        self.lib.orc_s3_near(C.c_size_t(x.size), _ptr(x), _ptr(px), _ptr(sign), int(near), _ptr(y), _ptr(z))
+        return y, z
+
+    def s4_kstep(self, k_step: int, qu, qv, qw, z) -> dict:
+        """orc_s4_kstep on flat arrays: ``cnt`` (bins per record) and the events ``cu``, ``cv``, ``qw``, ``bin``."""
+        qu, qv, qw, z = (np.ascontiguousarray(a, np.uint8).reshape(-1) for a in (qu, qv, qw, z))
+        n = qu.size
+        u16p = C.POINTER(C.c_uint16)
+        fn = self.lib.orc_s4_kstep
+        fn.restype = C.c_size_t
+        ne = fn(C.c_size_t(n), int(k_step), _ptr(qu), _ptr(qv), _ptr(qw), _ptr(z), None, None, None, None, None)
+        cu, cv = np.empty(ne, np.uint16), np.empty(ne, np.uint16)
+        eqw, ebin, cnt = np.empty(ne, np.uint8), np.empty(ne, np.uint8), np.empty(n, np.uint8)
+        fn(C.c_size_t(n), int(k_step), _ptr(qu), _ptr(qv), _ptr(qw), _ptr(z), _ptr(cu, u16p), _ptr(cv, u16p), _ptr(eqw), _ptr(ebin), _ptr(cnt))
+        return dict(cnt=cnt, cu=cu, cv=cv, qw=eqw, bin=ebin)
+
+    def s5(self, cu, cv, qw, bin_) -> np.ndarray:
+        """orc_s5: the probability of every event."""
+        cu, cv = np.ascontiguousarray(cu, np.uint16), np.ascontiguousarray(cv, np.uint16)
+        qw, bin_ = np.ascontiguousarray(qw, np.uint8), np.ascontiguousarray(bin_, np.uint8)
+        u16p = C.POINTER(C.c_uint16)
+        prob = np.empty(cu.size, np.uint16)
+        self.lib.orc_s5(C.c_size_t(cu.size), _ptr(cu, u16p), _ptr(cv, u16p), _ptr(qw), _ptr(bin_), _ptr(prob, u16p))
+        return prob
+
+    def s6(self, prob, bin_) -> bytes:
+        """orc_s6: the range coder's bytes (flush included, no header)."""
+        prob, bin_ = np.ascontiguousarray(prob, np.uint16), np.ascontiguousarray(bin_, np.uint8)
+        out = np.empty(2 * prob.size + 64, np.uint8)
+        self.lib.orc_s6.restype = C.c_size_t
+        n = self.lib.orc_s6(C.c_size_t(prob.size), _ptr(prob, C.POINTER(C.c_uint16)), _ptr(bin_), _ptr(out))
+        return out[:n].tobytes()
+
     # -- QNBLIC (effort 0) ------------------------------------------------
     def qencode(self, img: np.ndarray):
         img = np.ascontiguousarray(img, np.uint8)

@@ -219,11 +219,11 @@ def map_init():
     return t.reshape(-1)
 
 
-def mapper_replay(x, px, sign, state=None):
+def mapper_replay(x, px, sign, state=None, y=None):
     """The re-mapper chains one key (2 px + sign) at a time: z in raster order (a symbol >= 20 codes as itself), the end
     tables (512 x [symbol -> rank, rank -> symbol, hits by rank]), and per key its first position in the partitioned
-    stream, its length and its number of overtakes."""
-    y = x_to_y(x, px, sign)
+    stream, its length and its number of overtakes.  y: the symbols, where they are not the lossless ones of x."""
+    y = x_to_y(x, px, sign) if y is None else np.asarray(y).astype(np.int64)
     key = np.asarray(px).astype(np.int64) * 2 + np.asarray(sign).astype(np.int64)
     tab = (map_init() if state is None else np.asarray(state, np.int32).copy()).reshape(512, 60)
     z = y.copy()

@@ -216,3 +216,41 @@ def test_oracle_on_kodak_matches_reference_and_readme(oracle, golden):
         assert (len(s), sha(s)) == (k[name]["len"], k[name]["sha256"]), name
         q = oracle.qencode(img)
         assert (len(q), sha(q)) == (k[name]["q_len"], k[name]["q_sha256"]), name
+
+
+@pytest.mark.parametrize("name", ["kodak05", "blocks", "noise", "syn1", "spikes", "checker"])
+def test_staged_entropy_front_equals_fused_in_every_mode(oracle, name):
+    """The decomposition test_staged_equals_fused proves for lossless -e1, for the modes whose model stage is a serial
+    chain: the fused encoder's own records per pixel (orc_nblic_trace) through the general S3 (one re-mapper key at a
+    time) -> general S4 -> S5 (one counter at a time) -> S6 give the fused stream's body, at near 0..9 x efforts 1..3
+    with the k_step the encoders pair with near."""
+    plane = inputs.foreign_planes()[name]
+    for effort in (1, 2, 3):
+        for near in range(10):
+            case = (name, near, effort)
+            s, rec, *_ = oracle.encode(plane, near, effort)
+            t = oracle.trace(plane, near, effort)
+            assert t["stream"] == s and np.array_equal(t["recon"], rec), case
+            assert s[14] == inputs.paired_k_step(near), case
+            assert np.array_equal(t["adr"] >> 8, t["qu"] >> 1) and int(t["qw"].max()) <= 16, case      # what pack_s1 relies on
+            assert int(np.abs(t["qv"].astype(int) - t["qu"].astype(int)).max()) <= 1, case
+            y, z = oracle.s3_near(plane, t["px"], t["sign"], near)
+            assert np.array_equal(y, t["y"]) and np.array_equal(z, t["z"]), case
+            ev = oracle.s4_kstep(s[14], t["qu"], t["qv"], t["qw"], z)
+            assert np.array_equal(ev["cnt"], t["bins"]), case
+            prob = oracle.s5(ev["cu"], ev["cv"], ev["qw"], ev["bin"])
+            assert oracle.s6(prob, ev["bin"]) == s[16:], case
+
+
+def test_general_stages_at_the_lossless_constants_are_the_lossless_stages(oracle):
+    """orc_s3_near at near 0 and orc_s4_kstep at k_step 3 are orc_s3 and orc_s4."""
+    for plane in inputs.foreign_planes().values():
+        st = oracle.stages(plane)
+        y, z = oracle.s3_near(plane, st["px"], st["sign"], 0)
+        assert np.array_equal(y, st["y"]) and np.array_equal(z, st["z"])
+        ev = oracle.s4_kstep(3, st["qu"], st["qv"], st["qw"], z)
+        for a, b in (("cnt", "ev_count"), ("cu", "cu"), ("cv", "cv"), ("qw", "ev_qw"), ("bin", "ev_bin")):
+            assert np.array_equal(ev[a], st[b]), a
+        t = oracle.trace(plane, 0, 1)                        # and the fused engine's records at -n0 -e1 are S1 / S2's
+        for k in ("px0", "adr", "qu", "qv", "qw", "px", "sign", "y", "z"):
+            assert np.array_equal(t[k], st[k]), k
