@@ -344,6 +344,51 @@ int nblic_amd_encode_batch_indexed(nblic_amd_ctx *ctx, int n_images, const unsig
 long nblic_amd_index_bytes(int kind, int height, int width, int effort, int every_rows);
 long nblic_amd_indexed_batch_split(nblic_amd_ctx *ctx, double ms[5]);
 
+/* INDEXED BATCH DECODE: the segments of many streams, or one row range of each, in one call.  Image k is a stream and its
+ * seek index; NBLIC in any mode and QNBLIC, any geometry and any R may share a call.  row0 and row1 both NULL: whole
+ * planes; otherwise rows [row0[k], row1[k]) of image k.  outs[k] is a host buffer of out_caps[k] bytes.
+ *   host check      nblic_amd_index_check(index, stream) and the stream's description, on worker threads of the call (as
+ *                   many as the context has coder threads).  No byte of an image reaches the device before it has passed.
+ *   segments        with k0 = row0 / R and k1 the segment that holds row1 - 1, segments k0 .. k1 all run side by side,
+ *                   segment 0 from the stream's start and segment s from entry s; the last one stops in front of row1.
+ *                   The stream goes up once per image (a row range: from the first entry's feed_from on) and the index
+ *                   verbatim, in one copy; a kernel sets every segment up from the uploaded entry (its record, B, the two
+ *                   rows above) wherever that entry happens to lie.
+ *   job list        all segments of all accepted images form one list (nblic_amd_indexed_decode_plan); the segments of a
+ *                   (codec, effort) class share a launch, so a call with many segments takes the decoders' lean image.
+ *   rounds          at most 1 GiB of per-segment state per round, and nblic_amd_set_index_round(ctx, n) caps a round at n
+ *                   segments here too.  Within an image a higher segment never runs in a later round than a lower one.
+ *   verification    every inner boundary of an image is checked ON THE DEVICE: the segment's final record, B and last two
+ *                   rows against the next entry, as nblic_amd_decode_indexed compares them on the host.  The last segment of
+ *                   a whole plane must end the image, that of a range must stand in front of row1.  Only one word per
+ *                   boundary and one 64-byte header per image are read back.
+ *   per image       status[k] = 0, or -1: the host check refused it, a row range outside 0 <= row0 < row1 <= height,
+ *                   out_caps[k] below (row1 - row0) x width (height x width for a whole plane) -- such an image takes no
+ *                   further part in the call and its buffer is not written -- or a boundary differs or a segment fails:
+ *                   then outs[k] is zeroed over the bytes that would have been written.  Nothing else is written to outs[k].
+ *                   heights / widths / nears / efforts [k] are filled in for every image that passed the host check.
+ *   whole call      0 when every status is 0, else -1.  -1 with nothing launched or allocated and status untouched:
+ *                   n_images < 1, a null array, stream, index or output, exactly one of row0 / row1 NULL, a context without
+ *                   a usable device.
+ * The call has a HIP stream and a workspace of its own: the streams, indexes and planes (or row ranges) of all accepted
+ * images are in device memory together, so a caller with more than the device holds splits its batch.
+ * nblic_amd_indexed_decode_split (reporting): the context's last call as host milliseconds -- ms[0] the host checks,
+ * [1] allocation and uploads, [2] the rounds with their chain check, [3] the copies to the host; 0, -1 without a context.
+ * nblic_amd_indexed_decode_plan: the job list alone; host only, no device, no context.  Image k is kinds[k] (0 NBLIC,
+ * 1 QNBLIC), efforts[k], heights[k] x widths[k], an entry every every_rows[k] rows, rows [row0[k], row1[k]) (both NULL:
+ * whole planes); round_segments <= 0: one round.  Job j is the six ints jobs[6 j ..]: image, segment, first row, end_row
+ * (0: the image's last row), class (kind * 4 + effort) and round; jobs are listed round by round, class by class within
+ * a round, and an image's segments from the last to the first.  Returns the number of jobs (jobs is filled when it is
+ * not NULL and jobs_cap, in jobs, suffices), -1 for fields out of range. */
+int nblic_amd_decode_batch_indexed(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                   const void *const *indexes, const size_t *index_lens, const int *row0, const int *row1,
+                                   unsigned char *const *outs, const size_t *out_caps, int *heights, int *widths, int *nears,
+                                   int *efforts, int *status);
+int nblic_amd_indexed_decode_split(nblic_amd_ctx *ctx, double ms[4]);
+long nblic_amd_indexed_decode_plan(int n_images, const int *kinds, const int *efforts, const int *heights, const int *widths,
+                                   const int *every_rows, const int *row0, const int *row1, int round_segments, int *jobs,
+                                   size_t jobs_cap);
+
 /* The reference's decoders take no stream length (src/NBLIC.h:72, src/QNBLIC.h:16).  NBLICdecompress / QNBLICdecompress
  * therefore run a band decoder (nblic_amd_dstream above, band_rows as set by nblic_amd_set_serial_rows) and fetch the
  * caller's stream ON DEMAND in steps of `bytes` (default 1 MiB, at least 4096): the decoder stops in front of a row when
@@ -479,6 +524,25 @@ int nblic_amd_debug_entropy_front(nblic_amd_ctx *ctx, size_t n, const unsigned c
                                   unsigned char *z, unsigned char *cnt, unsigned int *pos3, unsigned int *ev_off,
                                   unsigned int *events, size_t events_cap, unsigned short *coded, int *map_state_out,
                                   int *cnt_state_out, unsigned int *totals);
+
+/* Debug hook used by the indexed batch decode's tests: ONE launch of k_index_seed, or of k_index_chain, on caller-made
+ * bytes.  `index` (one nblic_amd_index_check accepts) is uploaded at byte base_offset (0 .. 4096) of a larger zeroed
+ * buffer, so the caller chooses the residue of every entry's address; `entry` is 1-based, 0 = segment 0 (seed only).
+ *   seed (final_rec, final_b, final_rows and verdict all NULL): the task of segment `entry` with SerialState::avail =
+ *       avail and, for entry 0, pos = first_pos.  Writes rec_out (the record: 86,080 bytes, QNBLIC 12,352), stats_out
+ *       ([B | F]: 2 x (512 / 1024 x width) bytes at -e2 / -e3, else nothing) and rows_out: the 2 x width bytes of a plane
+ *       that holds rows [r - 2, r) of the entry's row r, filled with 0xA7 before the launch.
+ *   chain (verdict != NULL): final_rec, final_b (may be NULL when the mode has no B) and final_rows -- the plane rows
+ *       [r - n, r), n = min(r, 2) -- are uploaded as a segment's final state and compared with `entry`; *verdict = 0, or
+ *       the OR of 1 (record), 2 (B), 4 (rows).  Nothing else is written.
+ * Every device output is followed by a patterned guard.  Returns 0; -1, with nothing launched or allocated: a null
+ * pointer, an index that is refused, entry outside the index, a final_* buffer shorter than the kernel reads; -2 when a
+ * HIP call failed; -3 when a byte behind an output has changed. */
+int nblic_amd_debug_index_kernels(nblic_amd_ctx *ctx, const void *index, size_t index_bytes, size_t base_offset, int entry,
+                                  unsigned long long avail, unsigned long long first_pos, unsigned char *rec_out,
+                                  unsigned char *stats_out, unsigned char *rows_out, const unsigned char *final_rec,
+                                  size_t final_rec_bytes, const unsigned char *final_b, size_t final_b_bytes,
+                                  const unsigned char *final_rows, size_t final_rows_bytes, unsigned int *verdict);
 
 /* Device self-test of the wave primitives the chain kernels rely on (DPP prefix sum against the
  * shuffle formulation).  Returns the number of mismatching lanes (0 = pass) or -1.           */

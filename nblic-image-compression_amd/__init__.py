@@ -47,6 +47,7 @@ EXPORTS = (
     "nblic_amd_index_check", "nblic_amd_index_build", "nblic_amd_decode_indexed", "nblic_amd_decode_rows",
     "nblic_amd_stream_set_index", "nblic_amd_stream_index", "nblic_amd_set_index_round", "nblic_amd_stream_set_front",
     "nblic_amd_encode_batch_indexed", "nblic_amd_index_bytes", "nblic_amd_indexed_batch_split",
+    "nblic_amd_decode_batch_indexed", "nblic_amd_indexed_decode_split", "nblic_amd_indexed_decode_plan", "nblic_amd_debug_index_kernels",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -198,6 +199,17 @@ def load_library() -> C.CDLL:
         lib.nblic_amd_index_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         lib.nblic_amd_indexed_batch_split.restype = C.c_long
         lib.nblic_amd_indexed_batch_split.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    if hasattr(lib, "nblic_amd_decode_batch_indexed"):
+        vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
+        lib.nblic_amd_decode_batch_indexed.restype = C.c_int
+        lib.nblic_amd_decode_batch_indexed.argtypes = [C.c_void_p, C.c_int, vpp, szp, vpp, szp, ip, ip, vpp, szp, ip, ip, ip, ip, ip]
+        lib.nblic_amd_indexed_decode_split.restype = C.c_int
+        lib.nblic_amd_indexed_decode_split.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        lib.nblic_amd_indexed_decode_plan.restype = C.c_long
+        lib.nblic_amd_indexed_decode_plan.argtypes = [C.c_int, ip, ip, ip, ip, ip, ip, ip, C.c_int, ip, C.c_size_t]
+        lib.nblic_amd_debug_index_kernels.restype = C.c_int
+        lib.nblic_amd_debug_index_kernels.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_ulonglong, C.c_ulonglong] + [C.c_void_p] * 3 + \
+                                                     [C.c_void_p, C.c_size_t] * 3 + [C.c_void_p]
     lib.nblic_amd_enable_timing.restype = None
     lib.nblic_amd_enable_timing.argtypes = [C.c_void_p, C.c_int]
     lib.nblic_amd_stage_times.restype = C.c_int
@@ -254,6 +266,32 @@ def index_bytes(kind: int, h: int, w: int, effort: int, every_rows: int) -> int:
     """Size of the seek index of a stream of this geometry (``nblic_amd_index_bytes``; kind 0 NBLIC, 1 QNBLIC); host only.
     -1: ``every_rows`` outside [1, h), or a field out of range."""
     return int(load_library().nblic_amd_index_bytes(int(kind), int(h), int(w), int(effort), int(every_rows)))
+
+
+def indexed_decode_plan(images, rows=None, round_segments: int = 0) -> List[dict]:
+    """The job list of ``Context.decode_batch_indexed`` (``nblic_amd_indexed_decode_plan``); host only.  ``images`` is a
+    list of ``(kind, effort, h, w, R)`` (kind 0 NBLIC, 1 QNBLIC), ``rows`` None (whole planes) or one ``(r0, r1)`` per
+    image, ``round_segments`` the cap of a round (0: one round).  Returns one dict per segment -- ``image``, ``segment``,
+    ``first_row``, ``end_row`` (0: the image's last row), ``cls`` and ``round`` -- in the order the call runs them.
+    Raises ``ValueError`` for fields out of range."""
+    lib = load_library()
+    n = len(images)
+    cols = [np.ascontiguousarray([int(im[f]) for im in images], np.int32) for f in range(5)]
+    ip = C.POINTER(C.c_int)
+    q = lambda a: a.ctypes.data_as(ip)
+    r0 = r1 = None
+    if rows is not None:
+        r0 = np.ascontiguousarray([int(r[0]) for r in rows], np.int32)
+        r1 = np.ascontiguousarray([int(r[1]) for r in rows], np.int32)
+    args = [n] + [q(c) for c in cols] + [None if r0 is None else q(r0), None if r1 is None else q(r1), int(round_segments)]
+    count = lib.nblic_amd_indexed_decode_plan(*args, None, 0)
+    if count < 0:
+        raise ValueError("nblic_amd_indexed_decode_plan refused its arguments")
+    jobs = np.zeros((count, 6), np.int32)
+    if lib.nblic_amd_indexed_decode_plan(*args, q(jobs), count) != count:
+        raise RuntimeError("nblic_amd_indexed_decode_plan failed")
+    names = ("image", "segment", "first_row", "end_row", "cls", "round")
+    return [dict(zip(names, (int(v) for v in row))) for row in jobs]
 
 
 def _every_rows_list(every_rows, k: int) -> List[int]:
@@ -672,6 +710,78 @@ class Context:
         if self.lib.nblic_amd_decode_rows(self.handle, _ptr(s), s.size, _ptr(x), x.size, int(r0), int(r1), _ptr(out), out.size) != 0:
             raise RuntimeError("nblic_amd_decode_rows failed (index refused, rows outside the image, or a damaged stream)")
         return out
+
+    def decode_batch_indexed(self, pairs, rows=None, info: Optional[dict] = None) -> List[Optional[np.ndarray]]:
+        """Many streams' segments, or one row range of each, in one call (``nblic_amd_decode_batch_indexed``).  ``pairs``
+        is ``[(stream, index), ...]``, ``rows`` None (whole planes) or ``[(r0, r1), ...]``.  Returns per image the plane,
+        the rows, or None (refused, or index and stream disagree); the others are unaffected.  ``info``, when given,
+        receives ``status`` and ``rc``."""
+        n = len(pairs)
+        ss = [_bytes_arg(s if s is not None else b"") for s, _ in pairs]
+        xs = [_bytes_arg(x if x is not None else b"") for _, x in pairs]      # (no index: that image alone is refused)
+        nothing = np.zeros(1, np.uint8)                         # an empty stream or index still gets a pointer: the library refuses the image, not the call
+        ip = C.POINTER(C.c_int)
+        dims = []
+        for k in range(n):                                      # the head of an index names the geometry; the library checks all of it
+            h = w = 0
+            if xs[k].size >= INDEX_HEAD_BYTES:
+                h, w = (int(v) for v in np.frombuffer(xs[k][16:24].tobytes(), "<i4"))
+            if not (0 < h <= 65535 and 0 < w <= 65535):
+                h = w = 0
+            dims.append((h, w))
+        if rows is not None:
+            r0 = np.ascontiguousarray([int(r[0]) for r in rows], np.int32)
+            r1 = np.ascontiguousarray([int(r[1]) for r in rows], np.int32)
+            shapes = [(max(0, min(int(b), dims[k][0]) - max(int(a), 0)), dims[k][1]) for k, (a, b) in enumerate(rows)]
+        else:
+            r0 = r1 = None
+            shapes = dims
+        outs = [np.empty(max(1, sh[0] * sh[1]), np.uint8) for sh in shapes]
+        vp = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data if a.size else nothing.ctypes.data for a in arrs])
+        sz = lambda arrs: (C.c_size_t * n)(*[a.size for a in arrs])
+        caps = (C.c_size_t * n)(*[sh[0] * sh[1] for sh in shapes])
+        meta = [np.full(max(n, 1), -1, np.int32) for _ in range(5)]
+        q = lambda a: None if a is None else a.ctypes.data_as(ip)
+        rc = self.lib.nblic_amd_decode_batch_indexed(self.handle, n, vp(ss), sz(ss), vp(xs), sz(xs), q(r0), q(r1), vp(outs), caps, *[q(m) for m in meta])
+        status = meta[4][:n] if n else np.zeros(0, np.int32)
+        if info is not None:
+            info["status"], info["rc"] = [int(v) for v in status], int(rc)
+        return [outs[k][: shapes[k][0] * shapes[k][1]].reshape(shapes[k]) if status[k] == 0 else None for k in range(n)]
+
+    def indexed_decode_split(self) -> dict:
+        """Host milliseconds of the last ``decode_batch_indexed`` (``nblic_amd_indexed_decode_split``)."""
+        ms = (C.c_double * 4)()
+        self.lib.nblic_amd_indexed_decode_split(self.handle, ms)
+        return dict(zip(("check", "upload", "rounds", "copy_out"), (float(v) for v in ms)))
+
+    def debug_index_kernels(self, index, base_offset: int, entry: int, avail: int = 0, first_pos: int = 0, final=None):
+        """``nblic_amd_debug_index_kernels``: k_index_seed (``final`` None; returns ``(record, stats, rows)``) or
+        k_index_chain (``final = (record, B, rows)``; returns the verdict word) on caller-made bytes, the index uploaded
+        at ``base_offset``.  ``ValueError`` when refused, ``DeviceCoderGuardError`` when a guard byte has changed."""
+        x = _bytes_arg(index)
+        kind, h, w, _, _, effort, R, count = (int(v) for v in np.frombuffer(x[12:44].tobytes(), "<i4")) if x.size >= 44 else (0,) * 8
+        rec_b = 12352 if kind == 1 else 86080
+        b_b = (1024 if effort == 3 else 512 if effort == 2 else 0) * max(w, 0) if kind == 0 else 0
+        rec, stats, rows = np.zeros(rec_b, np.uint8), np.zeros(max(2 * b_b, 1), np.uint8), np.zeros(max(2 * w, 1), np.uint8)
+        p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        verdict = None
+        fin = [None, None, None]
+        if final is not None:
+            fin = [None if f is None else np.ascontiguousarray(f, np.uint8).reshape(-1) for f in final]
+            verdict = np.zeros(1, np.uint32)
+        size = lambda a: 0 if a is None else int(a.size)
+        rc = self.lib.nblic_amd_debug_index_kernels(self.handle, _ptr(x), x.size, int(base_offset), int(entry), int(avail), int(first_pos),
+                                                    p(rec), p(stats), p(rows), p(fin[0]), size(fin[0]), p(fin[1]), size(fin[1]),
+                                                    p(fin[2]), size(fin[2]), p(verdict))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_index_kernels refused its arguments")
+        if rc == -3:
+            raise DeviceCoderGuardError("nblic_amd_debug_index_kernels: a byte behind an output has changed")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_index_kernels failed (%d)" % rc)
+        if final is not None:
+            return int(verdict[0])
+        return rec, stats[: 2 * b_b], rows[: 2 * w]
 
     def set_index_round(self, segments: int):
         """At most ``segments`` segments per round of ``decode_indexed`` (``nblic_amd_set_index_round``); 0 = bounded by

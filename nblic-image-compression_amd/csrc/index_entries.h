@@ -56,6 +56,45 @@ inline void index_close(uint8_t *p, const void *head, int count, size_t entry_by
     seal(p, index_total_bytes(count, entry_bytes));
 }
 
+// ---- the job list of an indexed batch decode (nblic_amd_indexed_decode_plan; pipeline.hip decode_batch_indexed) ----------
+// Image k of a call wants rows [row0, row1) of an h-row image whose index has an entry every R rows: its segments
+// row0 / R .. (row1 - 1) / R all run, each from its entry (segment 0 from the stream's start), the last one stopping in
+// front of row1.  The segments of all images form ONE list, cut into rounds of at most `cap` segments (cap <= 0: one
+// round).  Two rules fix the order.  Images are taken class by class (cls = kind * 4 + effort, what one launch can
+// carry), so a round's jobs of one class are neighbours and share a launch.  Within an image the segments are listed from
+// the last to the first: the rows above a segment come from its entry and lie in the plane BEFORE the segment that owns
+// them decodes, so a higher segment must never run in a later round than a lower one.
+struct IndexedJob { int image, segment, first_row, end_row, cls, round; };   // end_row 0: the job runs to the image's last row
+struct IndexedPlanImage { int kind, effort, h, w, every, row0, row1; };
+inline int indexed_class(int kind, int effort) { return kind * 4 + effort; }
+// false: an image whose fields are out of range (nothing is appended then).
+inline bool indexed_decode_plan(const IndexedPlanImage *im, int n, int cap, std::vector<IndexedJob> &jobs) {
+    jobs.clear();
+    if (n < 1 || !im) return false;
+    std::vector<int> order;
+    for (int k = 0; k < n; k++) {
+        const IndexedPlanImage &I = im[k];
+        if (index_record_bytes(I.kind, I.w, I.effort) == 0 || I.h < 1 || I.w < 1 || I.h > kIndexMaxSide || I.w > kIndexMaxSide || I.every < 1 ||
+            I.row0 < 0 || I.row1 <= I.row0 || I.row1 > I.h) return false;
+        order.push_back(k);
+    }
+    for (int a = 1; a < n; a++)                                          // stable, by class
+        for (int b = a; b > 0 && indexed_class(im[order[size_t(b)]].kind, im[order[size_t(b)]].effort) <
+                                     indexed_class(im[order[size_t(b - 1)]].kind, im[order[size_t(b - 1)]].effort); b--) {
+            const int t = order[size_t(b)]; order[size_t(b)] = order[size_t(b - 1)]; order[size_t(b - 1)] = t;
+        }
+    for (int k : order) {
+        const IndexedPlanImage &I = im[k];
+        const int s0 = I.row0 / I.every, s1 = (I.row1 - 1) / I.every;
+        for (int s = s1; s >= s0; s--) {
+            const int end = s == s1 ? (I.row1 < I.h ? I.row1 : 0) : (s + 1) * I.every;
+            const int round = cap > 0 ? int(jobs.size() / size_t(cap)) : 0;
+            jobs.push_back(IndexedJob{k, s, s * I.every, end, indexed_class(I.kind, I.effort), round});
+        }
+    }
+    return true;
+}
+
 // ---- entries that wait for their window ----------------------------------------------------------------------------------
 struct PendingEntries {
     struct Entry {

@@ -273,6 +273,7 @@ struct nblic_amd_ctx {
     int serial_rows = 0;                  // rows per launch of the serial kernels; 0 = sized for a few seconds per launch (nblic_amd_set_serial_rows)
     DevBuf<unsigned long long> d_redo;          // device: pixels whose least-squares system 0 / 1 was redone with integers (SerialJob::redo of every job of the context)
     double idx_split[5] = {0}; long idx_steps = 0;   // the last indexed batch, summed over its group steps: front, totals read-back, back half + entry records, copies (GPU ms); coder wait (host ms).  Guarded by stat_m
+    double idxdec_split[4] = {0};         // the last indexed batch decode: host checks, uploads, rounds and chain check, copy-out (host ms).  Guarded by stat_m
     long serial_launch_count = 0;         // launches of the serial model / decode kernels since the context was created (reporting, tests)
     size_t feed_chunk = size_t(1) << 20;  // bytes per step in which the drop-in decoders fetch a stream of unknown length (nblic_amd_set_feed_chunk)
     long fed_bytes = 0;                   // bytes the last drop-in decode read from the caller's stream
@@ -2879,6 +2880,249 @@ static int encode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
     return all ? 0 : -1;
 }
 
+// ---- the INDEXED BATCH DECODE: the segments and row ranges of many streams in one call ----------------------------------
+// What decode_indexed and decode_rows do for one stream per call, for many: the host checks run on worker threads, every
+// accepted image's stream (or, for a row range, its tail from the first entry's feed_from) and its index go up ONCE, the
+// index verbatim, and all segments of all images form one job list (indexed_decode_plan: rounds that bound the per-segment
+// memory, classes that share a launch).  A round's segments are set up by k_index_seed straight from the uploaded index and
+// their final records and B are compared with the next entries by k_index_chain before the round's buffers are reused; the
+// rows part of that comparison runs once, after the last round -- at R = 1 the two rows above an entry belong to two
+// segments that may run in different rounds.  Only the verdict words and one SerialState per image come back.
+struct IdxDecImage {
+    int k = 0;                          // the caller's image
+    bool ok = false;
+    IndexView V;
+    DecodeItem it{};
+    std::vector<uint8_t> qtab;
+    int row0 = 0, row1 = 0, base = 0, seg0 = 0, seg1 = 0;       // rows wanted, first row of the device plane, first and last segment
+    unsigned long long stream_off = 0;
+    size_t out_bytes = 0;
+    uint8_t *d_stream = nullptr, *d_index = nullptr, *d_plane = nullptr, *d_tab = nullptr;
+    uint32_t *d_verdict = nullptr;      // one word per inner boundary, from boundary seg0 | seg0 + 1 on
+    SerialState last{};                 // the last segment's final header
+};
+
+static bool idxdec_upload_tasks(std::vector<IndexTask> &tasks, bool seed, IndexTask *d_tasks, uint32_t &chunks, hipStream_t st) {
+    chunks = 0;
+    for (auto &t : tasks) { t.first_chunk = chunks; chunks += index_task_chunks(t, seed); }
+    return tasks.empty() || hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(IndexTask), hipMemcpyHostToDevice, st) == hipSuccess;
+}
+
+static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *const *streams, const size_t *slens, const void *const *indexes,
+                                const size_t *ilens, const int *row0, const int *row1, unsigned char *const *outs, const size_t *caps,
+                                int *hs, int *ws, int *nears, int *efforts, int *status) {
+    if (!c || c->broken || n < 1 || !streams || !slens || !indexes || !ilens || !outs || !caps || !hs || !ws || !nears || !efforts || !status) return -1;
+    if ((row0 == nullptr) != (row1 == nullptr)) return -1;
+    for (int k = 0; k < n; k++) if (!streams[k] || !indexes[k] || !outs[k]) return -1;
+    if (hipSetDevice(c->device) != hipSuccess) return -1;
+    using Clock = std::chrono::steady_clock;
+    auto ms_since = [](Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); };
+    double split[4] = {0, 0, 0, 0};
+    auto t0 = Clock::now();
+    // the host half: index against stream, the stream's description -- nothing of an image goes up before it has passed
+    std::vector<IdxDecImage> all{size_t(n)};
+    {
+        IdxPool pool;
+        IdxPendingTasks pending;
+        pending.add(n);
+        pool.start(std::max(1, std::min(n, c->coders_wanted)));
+        for (int k = 0; k < n; k++)
+            pool.post([&, k] {
+                IdxDecImage &I = all[size_t(k)];
+                I.k = k;
+                I.it = DecodeItem{k, 0, 0, 0, 0, 0, 0, 0, -1, -1};
+                I.ok = index_check(indexes[k], ilens[k], streams[k], slens[k], c->max_px, I.V) == 0 &&
+                       describe_stream(streams[k], slens[k], false, c->max_px, I.it, I.qtab) == Described::ok;
+                pending.done();
+            });
+        pending.wait();
+    }
+    split[0] = ms_since(t0);
+    std::vector<IdxDecImage *> live;
+    std::vector<IndexedPlanImage> plan_in;
+    size_t per_seg_max = 1;
+    for (int k = 0; k < n; k++) {
+        IdxDecImage &I = all[size_t(k)];
+        status[k] = -1; hs[k] = ws[k] = 0; nears[k] = efforts[k] = 0;
+        if (!I.ok) continue;
+        const DecodeItem &it = I.it;
+        hs[k] = it.h; ws[k] = it.w; nears[k] = it.near; efforts[k] = it.effort;
+        I.row0 = row0 ? row0[k] : 0; I.row1 = row1 ? row1[k] : it.h;
+        if (I.row0 < 0 || I.row1 <= I.row0 || I.row1 > it.h) continue;
+        I.out_bytes = size_t(I.row1 - I.row0) * size_t(it.w);
+        if (caps[k] < I.out_bytes) continue;
+        const int R = I.V.H.every_rows;
+        I.seg0 = I.row0 / R; I.seg1 = (I.row1 - 1) / R;
+        I.base = std::max(0, I.seg0 * R - 2);
+        if (I.seg0 > 0) {                                                // <= slen (index_check)
+            DecodeCheckpoint E;
+            memcpy(&E, I.V.ent[size_t(I.seg0 - 1)], sizeof E);
+            I.stream_off = E.feed_from;
+        }
+        per_seg_max = std::max(per_seg_max, up256(I.V.L.b) + up256(2 * I.V.L.b_bytes));
+        plan_in.push_back(IndexedPlanImage{it.kind, it.effort, it.h, it.w, R, I.row0, I.row1});
+        live.push_back(&I);
+    }
+    if (live.empty()) return -1;
+    size_t cap = std::max<size_t>(1, kIndexedRoundBytes / per_seg_max);
+    if (c->index_round_segments > 0) cap = std::min(cap, size_t(c->index_round_segments));
+    std::vector<IndexedJob> plan;
+    if (!indexed_decode_plan(plan_in.data(), int(plan_in.size()), int(std::min<size_t>(cap, size_t(1) << 30)), plan)) return -1;
+
+    // from here on a failure is the device's: every accepted image fails, and nothing unverified stays in its buffer
+    Stream st;                                                           // declared before the buffers: they go first
+    DevPool mem;
+    auto fail = [&](const char *what) {
+        fprintf(stderr, "[nblic_amd] indexed batch decode: %s\n", what);
+        if (st) hipStreamSynchronize(st);
+        for (IdxDecImage *I : live) { status[I->k] = -1; memset(outs[I->k], 0, I->out_bytes); }
+        return -1;
+    };
+    if (st.create(hipStreamNonBlocking) != hipSuccess) return fail("cannot create a stream");
+    t0 = Clock::now();
+    size_t n_bounds = 0;
+    for (IdxDecImage *I : live) n_bounds += size_t(I->seg1 - I->seg0);
+    uint32_t *d_verdicts = mem.make<uint32_t>(std::max<size_t>(1, n_bounds));
+    if (!d_verdicts || hipMemsetAsync(d_verdicts, 0, std::max<size_t>(1, n_bounds) * sizeof(uint32_t), st) != hipSuccess) return fail("cannot allocate the workspace");
+    {
+        size_t at = 0;
+        for (IdxDecImage *I : live) {
+            const DecodeItem &it = I->it;
+            const size_t win = size_t(it.len - I->stream_off), ilen = ilens[I->k];
+            I->d_verdict = d_verdicts + at; at += size_t(I->seg1 - I->seg0);
+            I->d_stream = mem.make<uint8_t>(stream_buf_bytes(win));
+            I->d_index = mem.make<uint8_t>(up256(ilen + 16));               // (the kernels read whole aligned words around an entry)
+            I->d_plane = mem.make<uint8_t>(size_t(I->row1 - I->base) * size_t(it.w));
+            if (it.kind) I->d_tab = mem.make<uint8_t>(kQTab);
+            if (!I->d_stream || !I->d_index || !I->d_plane || (it.kind && !I->d_tab)) return fail("cannot allocate the workspace");
+            if (!upload_stream(I->d_stream, streams[I->k] + I->stream_off, win, st) ||
+                hipMemcpyAsync(I->d_index, indexes[I->k], ilen, hipMemcpyHostToDevice, st) != hipSuccess ||
+                (it.kind && hipMemcpyAsync(I->d_tab, I->qtab.data(), kQTab, hipMemcpyHostToDevice, st) != hipSuccess)) return fail("upload");
+        }
+    }
+    // the rounds' shared buffers: records and statistics, jobs, tasks
+    const int n_rounds = plan.back().round + 1;
+    std::vector<size_t> round_begin(size_t(n_rounds) + 1, plan.size());
+    size_t rec_bytes_max = 0, jobs_max = 0;
+    for (size_t j = plan.size(); j-- > 0;) round_begin[size_t(plan[j].round)] = j;
+    for (int r = 0; r < n_rounds; r++) {
+        size_t bytes = 0;
+        for (size_t j = round_begin[size_t(r)]; j < round_begin[size_t(r) + 1]; j++) {
+            const RecordLayout &L = live[size_t(plan[j].image)]->V.L;
+            bytes += up256(L.b) + up256(2 * L.b_bytes);
+        }
+        rec_bytes_max = std::max(rec_bytes_max, bytes);
+        jobs_max = std::max(jobs_max, round_begin[size_t(r) + 1] - round_begin[size_t(r)]);
+    }
+    uint8_t *d_recs = mem.make<uint8_t>(rec_bytes_max);
+    SerialJob *d_jobs = mem.make<SerialJob>(jobs_max);
+    IndexTask *d_tasks = mem.make<IndexTask>(std::max(jobs_max, n_bounds));
+    IndexTask *d_tasks2 = mem.make<IndexTask>(jobs_max);
+    if (!d_recs || !d_jobs || !d_tasks || !d_tasks2) return fail("cannot allocate the workspace");
+    if (hipStreamSynchronize(st) != hipSuccess) return fail("upload");
+    split[1] = ms_since(t0);
+    t0 = Clock::now();
+    // the part of an entry a task names: record, B, rows above row r of image I
+    auto entry_task = [&](const IdxDecImage &I, int e, uint8_t *rec, uint8_t *stats, uint32_t parts) {
+        const RecordLayout &L = I.V.L;
+        const int r = e * I.V.H.every_rows;
+        const RowsAbove A = rows_above(r, I.it.w);
+        IndexTask T{};
+        T.entry = e > 0 ? I.d_index + size_t(I.V.body(e) - static_cast<const uint8_t *>(indexes[I.k])) : nullptr;
+        T.rec = rec; T.stats = stats;
+        T.rows = I.d_plane + size_t(A.first - I.base) * size_t(I.it.w);
+        T.avail = I.it.len; T.first_pos = first_pos(I.it);
+        T.rec_bytes = (parts & kChainRecord) ? uint32_t(L.b) : 0u;
+        T.b_bytes = (parts & kChainB) ? uint32_t(L.b_bytes) : 0u;
+        T.rows_bytes = (parts & kChainRows) && e > 0 ? uint32_t(size_t(A.n) * size_t(I.it.w)) : 0u;
+        T.b_at = uint32_t(L.b); T.rows_at = uint32_t(L.rows + A.at);
+        T.kind = uint32_t(I.it.kind);
+        return T;
+    };
+    std::vector<SerialJob> jobs(jobs_max);
+    std::vector<IndexTask> seeds, chains;
+    long launches_total = 0;
+    for (int r = 0; r < n_rounds; r++) {
+        const size_t j0 = round_begin[size_t(r)], j1 = round_begin[size_t(r) + 1];
+        seeds.clear(); chains.clear();
+        size_t at = 0;
+        for (size_t j = j0; j < j1; j++) {
+            const IndexedJob &P = plan[j];
+            IdxDecImage &I = *live[size_t(P.image)];
+            const RecordLayout &L = I.V.L;
+            uint8_t *rec = d_recs + at; at += up256(L.b);
+            uint8_t *stats = L.b_bytes ? d_recs + at : nullptr; at += up256(2 * L.b_bytes);
+            jobs[j - j0] = decode_job(I.it, I.d_plane, I.base, I.d_stream, I.stream_off, reinterpret_cast<SerialState *>(rec), reinterpret_cast<double *>(stats),
+                                      I.d_tab, rows_per_launch(I.it, c->serial_rows), P.end_row, c->d_redo);
+            seeds.push_back(entry_task(I, P.segment, rec, stats, kChainRecord | kChainB | kChainRows));
+            if (P.segment < I.seg1) {                                    // its end is an inner boundary: record and B now, the rows after the last round
+                IndexTask T = entry_task(I, P.segment + 1, rec, stats, kChainRecord | kChainB);
+                T.verdict = I.d_verdict + (P.segment - I.seg0);
+                chains.push_back(T);
+            }
+        }
+        uint32_t seed_chunks = 0, chain_chunks = 0;
+        if (!idxdec_upload_tasks(seeds, true, d_tasks, seed_chunks, st) || !idxdec_upload_tasks(chains, false, d_tasks2, chain_chunks, st) ||
+            hipMemcpyAsync(d_jobs, jobs.data(), (j1 - j0) * sizeof(SerialJob), hipMemcpyHostToDevice, st) != hipSuccess) return fail("upload");
+        if (!index_seed_launch(d_tasks, int(seeds.size()), seed_chunks, st)) return fail("launch");
+        for (size_t a = j0; a < j1;) {                                   // one launch sequence per class present
+            size_t b = a + 1;
+            int launches = 1;
+            while (b < j1 && plan[b].cls == plan[a].cls) b++;
+            for (size_t j = a; j < b; j++) {
+                const IndexedJob &P = plan[j];
+                const SerialJob &J = jobs[j - j0];
+                launches = std::max(launches, serial_launches((P.end_row ? P.end_row : J.h) - P.first_row, J.rows));
+            }
+            for (int l = 0; l < launches; l++)
+                if (!decode_launch(live[size_t(plan[a].image)]->it, d_jobs + (a - j0), jobs.data() + (a - j0), int(b - a), st, true)) return fail("launch");
+            launches_total += launches;
+            a = b;
+        }
+        if (!index_chain_launch(d_tasks2, int(chains.size()), chain_chunks, st)) return fail("launch");
+        for (size_t j = j0; j < j1; j++) {
+            IdxDecImage &I = *live[size_t(plan[j].image)];
+            if (plan[j].segment == I.seg1 && hipMemcpyAsync(&I.last, jobs[j - j0].state, sizeof(SerialState), hipMemcpyDeviceToHost, st) != hipSuccess) return fail("state");
+        }
+        if (hipStreamSynchronize(st) != hipSuccess) return fail("a round");       // the records, `jobs` and the task arrays are reused by the next round
+    }
+    { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count += launches_total; }
+    // every row is final now: the rows part of every boundary, then the verdicts
+    chains.clear();
+    for (IdxDecImage *I : live)
+        for (int s = I->seg0; s < I->seg1; s++) {
+            IndexTask T = entry_task(*I, s + 1, nullptr, nullptr, kChainRows);
+            T.verdict = I->d_verdict + (s - I->seg0);
+            if (T.rows_bytes) chains.push_back(T);
+        }
+    uint32_t chain_chunks = 0;
+    std::vector<uint32_t> verdicts(std::max<size_t>(1, n_bounds));
+    if (!idxdec_upload_tasks(chains, false, d_tasks, chain_chunks, st) || !index_chain_launch(d_tasks, int(chains.size()), chain_chunks, st) ||
+        hipMemcpyAsync(verdicts.data(), d_verdicts, verdicts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) return fail("the chain check");
+    split[2] = ms_since(t0);
+    t0 = Clock::now();
+    bool every = true;
+    for (IdxDecImage *I : live) {
+        uint32_t bad = 0;
+        for (int s = I->seg0; s < I->seg1; s++) bad |= verdicts[size_t(I->d_verdict - d_verdicts) + size_t(s - I->seg0)];
+        const bool ended = I->row1 == I->it.h ? I->last.status == kDone : (I->last.status == kRunning && I->last.next_row == I->row1);
+        if (bad || !ended) {
+            fprintf(stderr, "[nblic_amd] indexed batch decode: image %d: %s\n", I->k,
+                    bad ? "a segment does not end where the next entry starts (index and stream disagree)" : "the stream is damaged or ends too early");
+            memset(outs[I->k], 0, I->out_bytes);
+            continue;
+        }
+        if (hipMemcpyAsync(outs[I->k], I->d_plane + size_t(I->row0 - I->base) * size_t(I->it.w), I->out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return fail("rows");
+        status[I->k] = 0;
+    }
+    if (hipStreamSynchronize(st) != hipSuccess) return fail("rows");
+    split[3] = ms_since(t0);
+    { std::lock_guard<std::mutex> l(c->stat_m); for (int k = 0; k < 4; k++) c->idxdec_split[k] = split[k]; }
+    for (int k = 0; k < n; k++) every = every && status[k] == 0;
+    return every ? 0 : -1;
+}
+
 static nblic_amd_ctx *g_default = nullptr;
 static std::mutex g_default_m;
 
@@ -3408,6 +3652,80 @@ int nblic_amd_debug_entropy_front(nblic_amd_ctx *c, size_t n, const unsigned cha
     return ok ? rc : -2;
 }
 
+// ---- k_index_seed and k_index_chain on caller-made bytes (tests/test_indexed_batch_decode.py) ----------------------------
+// The index goes up at byte `base_offset` of a larger buffer, so the tests choose the residue of every entry's address.
+int nblic_amd_debug_index_kernels(nblic_amd_ctx *c, const void *index, size_t index_bytes, size_t base_offset, int entry, unsigned long long avail,
+                                  unsigned long long first_pos, unsigned char *rec_out, unsigned char *stats_out, unsigned char *rows_out,
+                                  const unsigned char *final_rec, size_t final_rec_bytes, const unsigned char *final_b, size_t final_b_bytes,
+                                  const unsigned char *final_rows, size_t final_rows_bytes, unsigned int *verdict) {
+    IndexView V;
+    if (!c || !index || !rec_out || !stats_out || !rows_out || base_offset > 4096 || index_check(index, index_bytes, nullptr, 0, c->max_px, V) != 0) return -1;
+    if (entry < 0 || entry > V.H.count) return -1;
+    const bool chain = final_rec || final_b || final_rows || verdict;
+    const RecordLayout &L = V.L;
+    const size_t w = size_t(V.H.w);
+    const RowsAbove A = rows_above(entry * V.H.every_rows, V.H.w);
+    const size_t rows_bytes = size_t(A.n) * w;
+    if (chain && (entry < 1 || !final_rec || !verdict || (L.b_bytes && !final_b) || (rows_bytes && !final_rows) || final_rec_bytes < L.b ||
+                  final_b_bytes < L.b_bytes || final_rows_bytes < rows_bytes)) return -1;
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    constexpr size_t kGuard = 256;
+    constexpr uint8_t kPattern = 0xA7;
+    Stream st;
+    DevPool mem;
+    const size_t rec_b = up256(L.b), stats_b = up256(2 * L.b_bytes), plane_b = up256(2 * w), word_b = 256;
+    const size_t out_bytes = rec_b + stats_b + plane_b + word_b + 4 * kGuard;
+    uint8_t *d_index = mem.make<uint8_t>(up256(base_offset + index_bytes + 16));
+    uint8_t *d_out = mem.make<uint8_t>(out_bytes);
+    IndexTask *d_task = mem.make<IndexTask>(1);
+    if (!d_index || !d_out || !d_task || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    uint8_t *d_rec = d_out, *d_stats = d_rec + rec_b + kGuard, *d_plane = d_stats + stats_b + kGuard, *d_word = d_plane + plane_b + kGuard;
+    const size_t used[4] = {L.b, 2 * L.b_bytes, 2 * w, chain ? sizeof(uint32_t) : 0};
+    uint8_t *const parts[4] = {d_rec, d_stats, d_plane, d_word};
+    const size_t room[4] = {rec_b + kGuard, stats_b + kGuard, plane_b + kGuard, word_b + kGuard};
+    std::vector<uint8_t> back(out_bytes);
+    const bool ok = [&]() -> bool {
+        HIP_OK(hipMemsetAsync(d_index, 0, up256(base_offset + index_bytes + 16), st));
+        HIP_OK(hipMemcpyAsync(d_index + base_offset, index, index_bytes, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(d_out, kPattern, out_bytes, st));
+        IndexTask T{};
+        T.entry = entry > 0 ? d_index + base_offset + size_t(V.body(entry) - static_cast<const uint8_t *>(index)) : nullptr;
+        T.rec = d_rec; T.stats = L.b_bytes ? d_stats : nullptr;
+        T.rows = d_plane + A.at;                                         // the plane here is the 2 w bytes of rows [r - 2, r)
+        T.avail = avail; T.first_pos = first_pos;
+        T.rec_bytes = uint32_t(L.b); T.b_bytes = uint32_t(L.b_bytes); T.rows_bytes = entry > 0 ? uint32_t(rows_bytes) : 0u;
+        T.b_at = uint32_t(L.b); T.rows_at = uint32_t(L.rows + A.at);
+        T.kind = uint32_t(V.H.kind);
+        T.verdict = reinterpret_cast<uint32_t *>(d_word);
+        if (chain) {
+            HIP_OK(hipMemcpyAsync(d_rec, final_rec, L.b, hipMemcpyHostToDevice, st));
+            if (L.b_bytes) HIP_OK(hipMemcpyAsync(d_stats, final_b, L.b_bytes, hipMemcpyHostToDevice, st));
+            if (rows_bytes) HIP_OK(hipMemcpyAsync(d_plane + A.at, final_rows, rows_bytes, hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemsetAsync(d_word, 0, sizeof(uint32_t), st));
+        }
+        HIP_OK(hipMemcpyAsync(d_task, &T, sizeof T, hipMemcpyHostToDevice, st));
+        if (!(chain ? index_chain_launch(d_task, 1, index_task_chunks(T, false), st) : index_seed_launch(d_task, 1, index_task_chunks(T, true), st))) return false;
+        HIP_OK(hipMemcpyAsync(back.data(), d_out, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    if (!ok) return -2;
+    for (int k = 0; k < 4; k++) {                                        // everything behind what a part may hold is still the pattern
+        const size_t at = size_t(parts[k] - d_out);
+        for (size_t i = used[k]; i < room[k]; i++)
+            if (back[at + i] != kPattern) return -3;
+    }
+    if (chain) {
+        memcpy(verdict, back.data() + (d_word - d_out), sizeof(uint32_t));
+        return 0;
+    }
+    memcpy(rec_out, back.data(), L.b);
+    memcpy(stats_out, back.data() + (d_stats - d_out), 2 * L.b_bytes);
+    memcpy(rows_out, back.data() + (d_plane - d_out), 2 * w);
+    return 0;
+}
+
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
 
 void nblic_amd_set_max_pixels(nblic_amd_ctx *c, long max_pixels) {
@@ -3635,6 +3953,33 @@ long nblic_amd_indexed_batch_split(nblic_amd_ctx *c, double ms[5]) {
 int nblic_amd_decode_indexed(nblic_amd_ctx *c, const unsigned char *stream, size_t stream_bytes, const void *index, size_t index_bytes,
                              unsigned char *img, size_t img_cap) {
     return decode_indexed(c, stream, stream_bytes, index, index_bytes, img, img_cap);
+}
+int nblic_amd_decode_batch_indexed(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                   const void *const *indexes, const size_t *index_lens, const int *row0, const int *row1,
+                                   unsigned char *const *outs, const size_t *out_caps, int *heights, int *widths, int *nears, int *efforts, int *status) {
+    return decode_batch_indexed(c, n_images, streams, stream_lens, indexes, index_lens, row0, row1, outs, out_caps, heights, widths, nears, efforts, status);
+}
+int nblic_amd_indexed_decode_split(nblic_amd_ctx *c, double ms[4]) {
+    if (!c || !ms) return -1;
+    std::lock_guard<std::mutex> l(c->stat_m);
+    for (int k = 0; k < 4; k++) ms[k] = c->idxdec_split[k];
+    return 0;
+}
+long nblic_amd_indexed_decode_plan(int n_images, const int *kinds, const int *efforts, const int *heights, const int *widths, const int *every_rows,
+                                   const int *row0, const int *row1, int round_segments, int *jobs, size_t jobs_cap) {
+    if (n_images < 1 || !kinds || !efforts || !heights || !widths || !every_rows || (row0 == nullptr) != (row1 == nullptr)) return -1;
+    std::vector<IndexedPlanImage> im;
+    for (int k = 0; k < n_images; k++)
+        im.push_back(IndexedPlanImage{kinds[k], efforts[k], heights[k], widths[k], every_rows[k], row0 ? row0[k] : 0, row1 ? row1[k] : heights[k]});
+    std::vector<IndexedJob> plan;
+    if (!indexed_decode_plan(im.data(), n_images, round_segments, plan)) return -1;
+    if (jobs && jobs_cap >= plan.size())
+        for (size_t j = 0; j < plan.size(); j++) {
+            const IndexedJob &P = plan[j];
+            const int v[6] = {P.image, P.segment, P.first_row, P.end_row, P.cls, P.round};
+            memcpy(jobs + 6 * j, v, sizeof v);
+        }
+    return long(plan.size());
 }
 int nblic_amd_decode_rows(nblic_amd_ctx *c, const unsigned char *stream, size_t stream_bytes, const void *index, size_t index_bytes, int row0,
                           int row1, unsigned char *out, size_t cap) {

@@ -110,6 +110,42 @@ int serial_decode_plan(int n, int max_w, bool whole_streams);
 bool serial_model_launch(const SerialJob *d_jobs, const SerialJob *h_jobs, int n, hipStream_t s);
 bool serial_decode_launch(const SerialJob *d_jobs, const SerialJob *h_jobs, int n, hipStream_t s, bool whole_streams);   // whole_streams: every job's stream is final (SerialState::final_)
 bool serial_qdecode_launch(const SerialJob *d_jobs, const SerialJob *h_jobs, int n, hipStream_t s);
+// ---- an indexed batch decode's segment set-up and chain check, on the device ----------------------------------------------
+// The index of an image is uploaded as it is, so an entry's body -- state record | B | the two rows above -- lies at ANY
+// address: an entry is 8 + 168 + body + 32 bytes and the body holds 2 w bytes of rows, so at odd w successive records sit
+// at 2 mod 4 and at w = 2 mod 4 the doubles of B sit at 4 mod 8.  Both kernels read the entry as aligned 32-bit words
+// shifted into place (or byte by byte, for the rows); what they write is the library's own and aligned, except the rows
+// of the plane.  A task's bytes are cut into chunks of kIndexChunkBytes, one workgroup each (a 4 MB B and its F are 512 of them).
+//   k_index_seed   one task per segment: the record the segment starts from (the entry's, or zeros with pos = first_pos
+//                  for segment 0; status kRunning, avail, final_ = 1), B into the first half of [B | F], zeros into F, and
+//                  the rows above into the plane.
+//   k_index_chain  one task per inner boundary: the segment's final record, B and plane rows against the next entry, as
+//                  the host's chain check compares them -- for NBLIC without the words [kRecRank, kRecSym), which the
+//                  lean decoder never writes back, and with hi and window.  A part that differs ORs its bit into the
+//                  boundary's verdict word (kChainRecord / kChainB / kChainRows); a part whose byte count is 0 is skipped.
+struct IndexTask {
+    const uint8_t *entry;                  // the entry's body inside the uploaded index; seed: null = segment 0
+    uint8_t *rec;                          // the segment's state record
+    uint8_t *stats;                        // [B | F]; null when the mode has none
+    uint8_t *rows;                         // the plane byte of the first row rows_above names (rows_bytes of them follow)
+    uint32_t *verdict;                     // chain: the boundary's verdict word (zeroed by the host)
+    unsigned long long avail, first_pos;   // seed: SerialState::avail, and pos of segment 0
+    uint32_t rec_bytes, b_bytes, rows_bytes;   // of the record and of B (multiples of 16), of the rows (any)
+    uint32_t b_at, rows_at;                // where B and the rows lie in the entry's body
+    uint32_t kind;                         // 0 NBLIC, 1 QNBLIC
+    uint32_t first_chunk;                  // chunks of the tasks in front of this one
+    uint32_t pad;
+};
+static_assert(sizeof(IndexTask) == 88, "uploaded as bytes");
+enum : uint32_t { kChainRecord = 1, kChainB = 2, kChainRows = 4 };
+constexpr uint32_t kIndexChunkBytes = 16384;
+// Chunks of one task: record | B (seed: and F behind it) | rows, in 16-byte units.
+inline uint32_t index_task_units(const IndexTask &t, bool seed) { return t.rec_bytes / 16 + (seed ? 2 : 1) * (t.b_bytes / 16) + (t.rows_bytes + 15) / 16; }
+inline uint32_t index_task_chunks(const IndexTask &t, bool seed) { return (index_task_units(t, seed) + kIndexChunkBytes / 16 - 1) / (kIndexChunkBytes / 16); }
+// d_tasks[0..n) with first_chunk filled in, `chunks` their sum.  false: the launch failed.
+bool index_seed_launch(const IndexTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
+bool index_chain_launch(const IndexTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
+
 // Both least-squares solvers of the serial kernels on `count` given systems, no image and no coder (tests): stats = count x vec_len(n)
 // integer-valued statistics [s | b | A], vn = count x 10 regressors, bias = the regularisation strength the pixel starts from (the two
 // systems of an item are the ones bias_pair makes of it).  n = 6 or 10; waves = 2 (n = 10 only) runs the two-wave hand-over.  Per item

@@ -1617,4 +1617,112 @@ bool serial_qdecode_launch(const SerialJob *d_jobs, const SerialJob *h_jobs, int
     return launch_rows(k_serial_qdecode, sizeof(QDecodeLds), d_jobs, h_jobs, n, s, 64, kRowPad);
 }
 
+// ---- indexed batch decode: segment set-up and chain check (serial_engine.h IndexTask) --------------------------------------
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));          // (a plain vector: HIP's uint4 has no address-space-qualified assignment)
+constexpr int kIndexThreads = 256;
+constexpr uint32_t kIndexChunkUnits = kIndexChunkBytes / 16;
+// the header of a record is units 0..3; NBLIC's rank -> symbol words are whole units too
+constexpr uint32_t kRankUnit0 = uint32_t(sizeof(SerialState) + size_t(kRecRank) * 4) / 16, kRankUnit1 = uint32_t(sizeof(SerialState) + size_t(kRecSym) * 4) / 16;
+static_assert((sizeof(SerialState) + size_t(kRecRank) * 4) % 16 == 0 && (sizeof(SerialState) + size_t(kRecSym) * 4) % 16 == 0 &&
+              kDecodeStateBytes % 16 == 0 && kQDecodeStateBytes % 16 == 0, "the kernels work in 16-byte units");
+
+// Sixteen bytes from any address: the aligned words around them, shifted into place.  The fifth word is read only when
+// the address is not a multiple of four -- it then holds the last of the sixteen bytes, so no word is read that holds
+// none of them.
+__device__ __forceinline__ u32x4 load16_any(const NB_GLOBAL uint8_t *p) {
+    const uintptr_t a = uintptr_t(p);
+    const NB_GLOBAL uint32_t *q = (const NB_GLOBAL uint32_t *)(a & ~uintptr_t(3));
+    const uint32_t sh = uint32_t(a & 3) * 8;
+    const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3], w4 = sh ? q[4] : 0u;
+    return u32x4{__builtin_amdgcn_alignbit(w1, w0, sh), __builtin_amdgcn_alignbit(w2, w1, sh), __builtin_amdgcn_alignbit(w3, w2, sh),
+                 __builtin_amdgcn_alignbit(w4, w3, sh)};
+}
+
+// The task a chunk belongs to: the last one whose first_chunk is not behind it (every lane reads the same words).
+__device__ __forceinline__ int index_task_of(const IndexTask *__restrict__ tasks, int n, uint32_t chunk) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tasks[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(kIndexThreads) k_index_seed(const IndexTask *__restrict__ tasks, int n) {
+    const IndexTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
+    const NB_GLOBAL uint8_t *entry = gp(T.entry);
+    NB_GLOBAL u32x4 *rec = (NB_GLOBAL u32x4 *)gp(T.rec), *stats = (NB_GLOBAL u32x4 *)gp(T.stats);
+    NB_GLOBAL uint8_t *rows = gp(T.rows);
+    const uint32_t ru = T.rec_bytes / 16, bu = T.b_bytes / 16, su = 2 * bu, wu = (T.rows_bytes + 15) / 16;
+    const uint32_t u0 = (blockIdx.x - T.first_chunk) * kIndexChunkUnits;
+    for (uint32_t j = threadIdx.x; j < kIndexChunkUnits; j += kIndexThreads) {
+        const uint32_t u = u0 + j;
+        if (u < ru) {
+            u32x4 v = entry ? load16_any(entry + size_t(u) * 16) : u32x4{0u, 0u, 0u, 0u};
+            if (u == 0) {                                                // next_row, status, pos
+                v.y = uint32_t(kRunning);
+                if (!entry) { v.z = uint32_t(T.first_pos); v.w = uint32_t(T.first_pos >> 32); }
+            } else if (u == 2) {                                         // avail, final_
+                v.x = uint32_t(T.avail); v.y = uint32_t(T.avail >> 32); v.z = 1u;
+            }
+            rec[u] = v;
+        } else if (u < ru + su) {
+            const uint32_t k = u - ru;
+            stats[k] = entry && k < bu ? load16_any(entry + T.b_at + size_t(k) * 16) : u32x4{0u, 0u, 0u, 0u};
+        } else if (u < ru + su + wu) {
+            const uint32_t o0 = (u - ru - su) * 16, o1 = min(o0 + 16, T.rows_bytes);
+            for (uint32_t o = o0; o < o1; o++) rows[o] = entry[T.rows_at + o];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kIndexThreads) k_index_chain(const IndexTask *__restrict__ tasks, int n) {
+    const IndexTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
+    const NB_GLOBAL uint8_t *entry = gp(T.entry);
+    const NB_GLOBAL u32x4 *rec = (const NB_GLOBAL u32x4 *)gp(T.rec), *stats = (const NB_GLOBAL u32x4 *)gp(T.stats);
+    const NB_GLOBAL uint8_t *rows = gp(T.rows);
+    const uint32_t ru = T.rec_bytes / 16, bu = T.b_bytes / 16, wu = (T.rows_bytes + 15) / 16;
+    const uint32_t u0 = (blockIdx.x - T.first_chunk) * kIndexChunkUnits;
+    const bool nblic = T.kind == 0;
+    uint32_t bad = 0;
+    for (uint32_t j = threadIdx.x; j < kIndexChunkUnits; j += kIndexThreads) {
+        const uint32_t u = u0 + j;
+        if (u < ru) {
+            if (u == 2 || u == 3 || (nblic && u >= kRankUnit0 && u < kRankUnit1)) continue;      // avail, final_, pad; the stale rank words
+            const u32x4 got = rec[u];
+            u32x4 want = load16_any(entry + size_t(u) * 16);
+            bool same;
+            if (u == 0) {                                                // next_row, status (must be kRunning), pos
+                want.y = uint32_t(kRunning);
+                same = got.x == want.x && got.y == want.y && got.z == want.z && got.w == want.w;
+            } else if (u == 1) {                                         // lo, hi, window, bias: QNBLIC keeps its state in lo alone
+                same = got.x == want.x && got.w == want.w && (!nblic || (got.y == want.y && got.z == want.z));
+            } else {
+                same = got.x == want.x && got.y == want.y && got.z == want.z && got.w == want.w;
+            }
+            if (!same) bad |= kChainRecord;
+        } else if (u < ru + bu) {
+            const uint32_t k = u - ru;
+            const u32x4 got = stats[k], want = load16_any(entry + T.b_at + size_t(k) * 16);
+            if (got.x != want.x || got.y != want.y || got.z != want.z || got.w != want.w) bad |= kChainB;
+        } else if (u < ru + bu + wu) {
+            const uint32_t o0 = (u - ru - bu) * 16, o1 = min(o0 + 16, T.rows_bytes);
+            for (uint32_t o = o0; o < o1; o++)
+                if (rows[o] != entry[T.rows_at + o]) bad |= kChainRows;
+        }
+    }
+    if (bad) atomicOr(T.verdict, bad);                              // only where something differs
+}
+
+bool index_seed_launch(const IndexTask *d_tasks, int n, uint32_t chunks, hipStream_t s) {
+    if (n <= 0 || chunks == 0) return true;
+    hipLaunchKernelGGL(k_index_seed, dim3(chunks), dim3(kIndexThreads), 0, s, d_tasks, n);
+    return hipGetLastError() == hipSuccess;
+}
+bool index_chain_launch(const IndexTask *d_tasks, int n, uint32_t chunks, hipStream_t s) {
+    if (n <= 0 || chunks == 0) return true;
+    hipLaunchKernelGGL(k_index_chain, dim3(chunks), dim3(kIndexThreads), 0, s, d_tasks, n);
+    return hipGetLastError() == hipSuccess;
+}
+
 }  // namespace nblic

@@ -1,5 +1,6 @@
 // Stand-alone check of index_entries.h (host only): the size of an index, entries that wait for their window while the
-// stream is emitted in pieces of every size, and the assembly of the index around them.  Build with the sanitizers and run:
+// stream is emitted in pieces of every size, the assembly of the index around them, and the job list of an indexed batch
+// decode.  Build with the sanitizers and run:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o index_entries_check tools/index_entries_check.cpp && ./index_entries_check
 #include <cstdio>
 #include <cstdlib>
@@ -65,6 +66,45 @@ static int run(size_t len, size_t piece, size_t gap, int w, unsigned seed) {
     return 0;
 }
 
+// The job list of an indexed batch decode on random mixes: every wanted row in exactly one job, rounds within the cap, an
+// image's segments in rounds that never increase with the segment number.
+static int plan_runs(unsigned seed) {
+    std::mt19937 rng(seed);
+    const int n = 1 + int(rng() % 12);
+    std::vector<IndexedPlanImage> im;
+    for (int k = 0; k < n; k++) {
+        const int kind = int(rng() % 4) == 3, h = 2 + int(rng() % 70), every = 1 + int(rng() % unsigned(h - 1));
+        const int r0 = int(rng() % unsigned(h)), r1 = r0 + 1 + int(rng() % unsigned(h - r0));
+        im.push_back(IndexedPlanImage{kind, kind ? 0 : 1 + int(rng() % 3), h, 1 + int(rng() % 300), every, (rng() & 1) ? 0 : r0, (rng() & 1) ? h : r1});
+        if (im.back().row1 <= im.back().row0) im.back().row1 = h;
+    }
+    for (int cap : {0, 1, 2, 3, 7}) {
+        std::vector<IndexedJob> jobs;
+        CHECK(indexed_decode_plan(im.data(), n, cap, jobs) && !jobs.empty());
+        std::vector<std::vector<int>> hits(static_cast<size_t>(n));
+        for (int k = 0; k < n; k++) hits[size_t(k)].assign(size_t(im[size_t(k)].h), 0);
+        std::vector<int> per_round(jobs.size(), 0), last_round(size_t(n), -1), last_seg(size_t(n), 1 << 30);
+        for (size_t j = 0; j < jobs.size(); j++) {
+            const IndexedJob &J = jobs[j];
+            const IndexedPlanImage &I = im[size_t(J.image)];
+            const int end = J.end_row ? J.end_row : I.h;
+            CHECK(J.first_row == J.segment * I.every && end > J.first_row && end <= I.h && (J.end_row == 0) == (end == I.h));
+            CHECK(J.cls == indexed_class(I.kind, I.effort) && J.round >= 0 && size_t(J.round) < jobs.size());
+            CHECK(j == 0 || J.round >= jobs[j - 1].round);
+            CHECK(J.segment < last_seg[size_t(J.image)] && J.round >= last_round[size_t(J.image)]);      // listed last to first, rounds never decrease
+            last_seg[size_t(J.image)] = J.segment; last_round[size_t(J.image)] = J.round;
+            CHECK(++per_round[size_t(J.round)] <= (cap > 0 ? cap : int(jobs.size())) && (cap > 0 || J.round == 0));
+            for (int r = J.first_row; r < end; r++) hits[size_t(J.image)][size_t(r)]++;
+        }
+        for (int k = 0; k < n; k++)
+            for (int r = 0; r < im[size_t(k)].h; r++) {
+                const bool wanted = r >= im[size_t(k)].row0 && r < im[size_t(k)].row1;
+                CHECK(hits[size_t(k)][size_t(r)] <= 1 && (!wanted || hits[size_t(k)][size_t(r)] == 1));
+            }
+    }
+    return 0;
+}
+
 int main() {
     // sizes: head 96 | count x (8 | 168 + body + 32) | 32
     CHECK(index_bytes(0, 40, 37, 1, 5) == long(96 + 32 + 7 * (8 + 200 + 86080 + 74)));
@@ -85,6 +125,11 @@ int main() {
                 if (run(len, piece, gap, 1 + int(seed % 40), seed)) return 1;
                 seed++;
             }
-    printf("index_entries_check ok: %u runs\n", seed - 1);
+    for (unsigned p = 1; p <= 200; p++)
+        if (plan_runs(p)) return 1;
+    std::vector<IndexedJob> none;
+    const IndexedPlanImage bad[2] = {{0, 1, 20, 30, 4, 0, 20}, {0, 1, 20, 30, 4, 5, 21}};
+    CHECK(!indexed_decode_plan(bad, 2, 0, none) && none.empty() && !indexed_decode_plan(bad, 0, 0, none) && indexed_decode_plan(bad, 1, 0, none) && none.size() == 5);
+    printf("index_entries_check ok: %u runs, 200 plans\n", seed - 1);
     return 0;
 }
