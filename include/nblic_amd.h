@@ -389,6 +389,52 @@ long nblic_amd_indexed_decode_plan(int n_images, const int *kinds, const int *ef
                                    const int *every_rows, const int *row0, const int *row1, int round_segments, int *jobs,
                                    size_t jobs_cap);
 
+/* BATCH INDEX BUILD: the seek indexes of many streams from ONE decode pass.  nblic_amd_index_build takes one stream per
+ * call and pays a host round trip at every band and every entry; this call takes n streams -- NBLIC in any mode and QNBLIC,
+ * written by this library or by the reference; any mix of geometries and of R = every_rows[k] -- and writes into
+ * indexes[k] (index_caps[k] bytes; nblic_amd_index_bytes gives the size) byte for byte what
+ * nblic_amd_index_build(stream k, every_rows[k]) writes.  planes (may be NULL, and so may its entries) receives the decoded
+ * planes, so decoding an archive and indexing it costs one pass; plane_caps is required unless planes is NULL.
+ *   host check      the stream's description, on worker threads of the call (as many as the context has coder threads).
+ *                   No byte of an image reaches the device before it has passed.
+ *   decode pass     every accepted stream goes up once and is decoded whole, the images of a (codec, effort) class side
+ *                   by side in the same launches (more than 256 of a class: the decoders' lean image).  A job stops in
+ *                   front of each of its entry rows; after every decode launch a capture kernel turns the device state of
+ *                   the jobs that stand there into the entries' bodies (record, B, the two rows above) and lets them go on.
+ *   schedule        a job's progress is known beforehand while it does not fail, so the launches of the whole call are
+ *                   laid out on the host first (nblic_amd_index_build_plan), uploaded once and queued back to back: the
+ *                   host waits once.  nblic_amd_set_serial_rows bounds the rows of a launch here too, and shows in no byte.
+ *   finish          worker threads fetch each image's staged bodies and its plane in one copy each and write the index:
+ *                   heads, the canonical running SHA-256 of the rows above every entry, the QNBLIC tables, the seals.
+ *   per image       status[k] = 0 and index_lens[k] = the index's size, or status[k] = -1 and index_lens[k] = -1: not a
+ *                   stream this library decodes, every_rows[k] < 1 or >= height (as nblic_amd_index_build refuses it),
+ *                   index_caps[k] or plane_caps[k] too small -- such an image takes no further part in the call and its
+ *                   buffers are not written -- or the stream does not decode to its end: then indexes[k] (and planes[k])
+ *                   are zeroed over the bytes that would have been written.  Nothing else is written to them.
+ *                   heights / widths / nears / efforts [k] are filled in for every stream whose description passed.
+ *   whole call      0 when every status is 0, else -1.  -1 with nothing launched or allocated and status untouched:
+ *                   n_images < 1, a null array (planes excepted), stream or index buffer, a context without a usable device.
+ * The call has a HIP stream of its own for the uploads and launches, up to four more for the finish's copies, and one
+ * workspace, so it runs next to everything else of its context.  All accepted
+ * images are in device memory together -- per image its stream, its whole plane, one decoder record, [B | F] and a staging
+ * buffer for its entries' bodies -- so a caller with more than the device holds splits its batch.
+ * nblic_amd_index_build_split (reporting): the context's last call as host milliseconds -- ms[0] the host checks,
+ * [1] allocation, uploads and seeding, [2] the decode and capture launches, [3] the finish; 0, -1 without a context.
+ * nblic_amd_index_build_plan: the schedule alone; host only, no device, no context.  Image k is kinds[k] (0 NBLIC,
+ * 1 QNBLIC), efforts[k], heights[k] x widths[k], an entry every every_rows[k] rows; serial_rows as
+ * nblic_amd_set_serial_rows (0: automatic).  class_launches (may be NULL) receives eight ints: the decode launches of class
+ * kind * 4 + effort.  Entry j is the four ints entries[4 j ..]: image, entry row, class, and the 0-based decode launch of
+ * that class behind which it is captured; entries are listed class by class and, within a class, by that launch.
+ * Returns the number of entries (entries is filled when it is not NULL and entries_cap, in entries, suffices), -1 for
+ * fields out of range. */
+int nblic_amd_index_build_batch(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                const int *every_rows, unsigned char *const *indexes, const size_t *index_caps, long *index_lens,
+                                unsigned char *const *planes, const size_t *plane_caps, int *heights, int *widths, int *nears,
+                                int *efforts, int *status);
+int nblic_amd_index_build_split(nblic_amd_ctx *ctx, double ms[4]);
+long nblic_amd_index_build_plan(int n_images, const int *kinds, const int *efforts, const int *heights, const int *widths,
+                                const int *every_rows, int serial_rows, int *class_launches, int *entries, size_t entries_cap);
+
 /* The reference's decoders take no stream length (src/NBLIC.h:72, src/QNBLIC.h:16).  NBLICdecompress / QNBLICdecompress
  * therefore run a band decoder (nblic_amd_dstream above, band_rows as set by nblic_amd_set_serial_rows) and fetch the
  * caller's stream ON DEMAND in steps of `bytes` (default 1 MiB, at least 4096): the decoder stops in front of a row when
@@ -543,6 +589,20 @@ int nblic_amd_debug_index_kernels(nblic_amd_ctx *ctx, const void *index, size_t 
                                   unsigned char *stats_out, unsigned char *rows_out, const unsigned char *final_rec,
                                   size_t final_rec_bytes, const unsigned char *final_b, size_t final_b_bytes,
                                   const unsigned char *final_rows, size_t final_rows_bytes, unsigned int *verdict);
+
+/* Debug hook used by the batch index build's tests: ONE launch of k_index_capture, one task, on caller-made bytes.
+ * `record` (86,080 bytes; QNBLIC 12,352), `b` (512 / 1024 x width bytes at -e2 / -e3, else none) and `rows` -- the plane rows
+ * [row - n, row), n = min(row, 2), uploaded at byte plane_offset (0 .. 4096) of a zeroed buffer -- are the state of a job
+ * whose end_row is `row`.  body_out receives the staged body, record | B | the 2 x width row slot; *end_row_out the job's
+ * end_row after the launch (next_end when the task acted).  A record whose status is not 0 or whose next_row is not `row`
+ * makes the task write nothing: body_out is then all 0xA7, the pattern the output held before, and *end_row_out = row.
+ * The output is followed by a patterned guard.  Returns 0; -1, with nothing launched or allocated: a null pointer, kind /
+ * effort / width / row out of range, a buffer whose size is not what the geometry says, body_cap too small; -2 when a HIP
+ * call failed; -3 when a byte behind the output has changed. */
+int nblic_amd_debug_index_capture(nblic_amd_ctx *ctx, int kind, int effort, int width, int row, int next_end,
+                                  const unsigned char *record, size_t record_bytes, const unsigned char *b, size_t b_bytes,
+                                  const unsigned char *rows, size_t rows_bytes, size_t plane_offset, unsigned char *body_out,
+                                  size_t body_cap, int *end_row_out);
 
 /* Device self-test of the wave primitives the chain kernels rely on (DPP prefix sum against the
  * shuffle formulation).  Returns the number of mismatching lanes (0 = pass) or -1.           */

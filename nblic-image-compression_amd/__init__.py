@@ -48,6 +48,7 @@ EXPORTS = (
     "nblic_amd_stream_set_index", "nblic_amd_stream_index", "nblic_amd_set_index_round", "nblic_amd_stream_set_front",
     "nblic_amd_encode_batch_indexed", "nblic_amd_index_bytes", "nblic_amd_indexed_batch_split",
     "nblic_amd_decode_batch_indexed", "nblic_amd_indexed_decode_split", "nblic_amd_indexed_decode_plan", "nblic_amd_debug_index_kernels",
+    "nblic_amd_index_build_batch", "nblic_amd_index_build_split", "nblic_amd_index_build_plan", "nblic_amd_debug_index_capture",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -210,6 +211,16 @@ def load_library() -> C.CDLL:
         lib.nblic_amd_debug_index_kernels.restype = C.c_int
         lib.nblic_amd_debug_index_kernels.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_ulonglong, C.c_ulonglong] + [C.c_void_p] * 3 + \
                                                      [C.c_void_p, C.c_size_t] * 3 + [C.c_void_p]
+    if hasattr(lib, "nblic_amd_index_build_batch"):
+        vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
+        lib.nblic_amd_index_build_batch.restype = C.c_int
+        lib.nblic_amd_index_build_batch.argtypes = [C.c_void_p, C.c_int, vpp, szp, ip, vpp, szp, C.POINTER(C.c_long), vpp, szp, ip, ip, ip, ip, ip]
+        lib.nblic_amd_index_build_split.restype = C.c_int
+        lib.nblic_amd_index_build_split.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        lib.nblic_amd_index_build_plan.restype = C.c_long
+        lib.nblic_amd_index_build_plan.argtypes = [C.c_int, ip, ip, ip, ip, ip, C.c_int, ip, ip, C.c_size_t]
+        lib.nblic_amd_debug_index_capture.restype = C.c_int
+        lib.nblic_amd_debug_index_capture.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_size_t] * 3 + [C.c_size_t, C.c_void_p, C.c_size_t, ip]
     lib.nblic_amd_enable_timing.restype = None
     lib.nblic_amd_enable_timing.argtypes = [C.c_void_p, C.c_int]
     lib.nblic_amd_stage_times.restype = C.c_int
@@ -292,6 +303,39 @@ def indexed_decode_plan(images, rows=None, round_segments: int = 0) -> List[dict
         raise RuntimeError("nblic_amd_indexed_decode_plan failed")
     names = ("image", "segment", "first_row", "end_row", "cls", "round")
     return [dict(zip(names, (int(v) for v in row))) for row in jobs]
+
+
+def index_build_plan(images, serial_rows: int = 0) -> Tuple[dict, List[dict]]:
+    """The launch schedule of ``Context.build_index_batch`` (``nblic_amd_index_build_plan``); host only.  ``images`` is a
+    list of ``(kind, effort, h, w, R)`` (kind 0 NBLIC, 1 QNBLIC), ``serial_rows`` as ``Context.set_serial_rows``.  Returns
+    ``(launches, entries)``: the decode launches of every class present (``kind * 4 + effort``), and one dict per entry --
+    ``image``, ``row``, ``cls`` and ``launch``, the 0-based decode launch of its class behind which it is captured -- class
+    by class and, within a class, by that launch.  Raises ``ValueError`` for fields out of range."""
+    lib = load_library()
+    n = len(images)
+    cols = [np.ascontiguousarray([int(im[f]) for im in images], np.int32) for f in range(5)]
+    ip = C.POINTER(C.c_int)
+    q = lambda a: a.ctypes.data_as(ip)
+    per_class = np.zeros(8, np.int32)
+    args = [n] + [q(c) for c in cols] + [int(serial_rows), q(per_class)]
+    count = lib.nblic_amd_index_build_plan(*args, None, 0)
+    if count < 0:
+        raise ValueError("nblic_amd_index_build_plan refused its arguments")
+    entries = np.zeros((max(count, 1), 4), np.int32)
+    if lib.nblic_amd_index_build_plan(*args, q(entries), count) != count:
+        raise RuntimeError("nblic_amd_index_build_plan failed")
+    names = ("image", "row", "cls", "launch")
+    return ({c: int(v) for c, v in enumerate(per_class) if v}, [dict(zip(names, (int(v) for v in row))) for row in entries[:count]])
+
+
+def _stream_dims(b: np.ndarray) -> Optional[Tuple[int, int]]:
+    """(height, width) as the first bytes of a stream name them, to size a plane buffer; None when they are no header.  The
+    library parses and checks the header itself: a plane buffer that does not fit costs that image alone."""
+    if b.size >= 16 and bytes(b[:8]) == b"NBLIC0.3":
+        return (int(b[9]) << 8) | int(b[10]), (int(b[11]) << 8) | int(b[12])
+    if b.size >= 8 and bytes(b[:4]) == b"Q0.2":
+        return int(b[4]) | (int(b[5]) << 8), int(b[6]) | (int(b[7]) << 8)
+    return None
 
 
 def _every_rows_list(every_rows, k: int) -> List[int]:
@@ -629,14 +673,7 @@ class Context:
         (image, near, effort) or None per stream."""
         k = len(streams)
         bufs = [np.frombuffer(bytes(s), np.uint8).copy() for s in streams]
-        dims = []
-        for b in bufs:
-            if b.size >= 16 and bytes(b[:8]) == b"NBLIC0.3":
-                dims.append(((int(b[9]) << 8) | int(b[10]), (int(b[11]) << 8) | int(b[12])))
-            elif b.size >= 8 and bytes(b[:4]) == b"Q0.2":
-                dims.append((int(b[4]) | (int(b[5]) << 8), int(b[6]) | (int(b[7]) << 8)))
-            else:
-                dims.append((1, 1))
+        dims = [_stream_dims(b) or (1, 1) for b in bufs]
         imgs = [np.zeros((max(h, 1), max(w, 1)), np.uint8) for (h, w) in dims]
         sp = (C.c_void_p * k)(*[C.c_void_p(b.ctypes.data) for b in bufs])
         sl = (C.c_size_t * k)(*[b.size for b in bufs])
@@ -691,6 +728,73 @@ class Context:
         if self.lib.nblic_amd_index_build(self.handle, _ptr(s), s.size, int(every_rows), _ptr(out), out.size) != need:
             raise RuntimeError("nblic_amd_index_build failed (the stream does not decode)")
         return out.tobytes()
+
+    def build_index_batch(self, streams, every_rows, planes: bool = False, info: Optional[dict] = None):
+        """The seek indexes of many streams from one decode pass (``nblic_amd_index_build_batch``): NBLIC in any mode and
+        QNBLIC, any mix of sizes.  ``every_rows`` is an int for all or one per stream.  Returns per stream the index --
+        byte for byte ``build_index(stream, R)`` -- or None (not a stream this library decodes, R outside [1, height), or
+        the stream does not decode to its end); the others are unaffected.  With ``planes=True`` returns
+        ``(indexes, planes)``, the decoded planes of the same pass.  ``info``, when given, receives ``rc``, ``status`` and
+        the parsed ``heights`` / ``widths`` / ``nears`` / ``efforts``."""
+        n = len(streams)
+        ss = [_bytes_arg(s if s is not None else b"") for s in streams]
+        every = [int(every_rows)] * n if np.isscalar(every_rows) else [int(r) for r in every_rows]
+        if len(every) != n:
+            raise ValueError(f"every_rows names {len(every)} streams, the batch has {n}")
+        nothing = np.zeros(1, np.uint8)                         # an empty stream still gets a pointer: the library refuses the image, not the call
+        geom = []
+        for s, r in zip(ss, every):                             # the library sizes the index from its own description of the stream
+            need = int(self.lib.nblic_amd_index_build(self.handle, _ptr(s), s.size, r, None, 0)) if s.size else -1
+            h, w = (_stream_dims(s) or (0, 0)) if planes else (0, 0)
+            geom.append((h, w, max(need, 0)))
+        xs = [np.empty(max(g[2], 1), np.uint8) for g in geom]
+        ps = [np.empty(max(g[0] * g[1], 1), np.uint8) for g in geom] if planes else None
+        ip = C.POINTER(C.c_int)
+        vp = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data if a.size else nothing.ctypes.data for a in arrs])
+        sz = lambda vals: (C.c_size_t * n)(*vals)
+        lens = (C.c_long * max(n, 1))(*([-1] * max(n, 1)))
+        meta = [np.full(max(n, 1), -1, np.int32) for _ in range(5)]
+        ev = np.ascontiguousarray(every if n else [0], np.int32)
+        rc = self.lib.nblic_amd_index_build_batch(self.handle, n, vp(ss), sz([a.size for a in ss]), ev.ctypes.data_as(ip), vp(xs), sz([g[2] for g in geom]), lens,
+                                                  vp(ps) if planes else None, sz([g[0] * g[1] for g in geom]) if planes else None,
+                                                  *[m.ctypes.data_as(ip) for m in meta])
+        status = [int(v) for v in meta[4][:n]]
+        if info is not None:
+            info["rc"], info["status"] = int(rc), status
+            for name, m in zip(("heights", "widths", "nears", "efforts"), meta):
+                info[name] = [int(v) for v in m[:n]]
+        ok = [rc in (0, -1) and status[k] == 0 and lens[k] == geom[k][2] for k in range(n)]
+        out = [xs[k][:geom[k][2]].tobytes() if ok[k] else None for k in range(n)]
+        if not planes:
+            return out
+        return out, [ps[k][:geom[k][0] * geom[k][1]].reshape(geom[k][0], geom[k][1]) if ok[k] else None for k in range(n)]
+
+    def index_build_split(self) -> dict:
+        """Host milliseconds of the last ``build_index_batch`` (``nblic_amd_index_build_split``)."""
+        ms = (C.c_double * 4)()
+        self.lib.nblic_amd_index_build_split(self.handle, ms)
+        return dict(zip(("check", "upload", "launches", "finish"), (float(v) for v in ms)))
+
+    def debug_index_capture(self, kind: int, effort: int, w: int, row: int, next_end: int, record, b, rows, plane_offset: int = 0):
+        """``nblic_amd_debug_index_capture``: ONE launch of k_index_capture on a caller-made record, B and plane rows
+        (uploaded at ``plane_offset``).  Returns ``(body, end_row)``: the staged body (record | B | the 2 w-byte row slot;
+        all 0xA7 when the task did not act) and the job's end_row after the launch.  ``ValueError`` when refused,
+        ``DeviceCoderGuardError`` when a guard byte has changed."""
+        arr = lambda a: None if a is None else np.ascontiguousarray(a, np.uint8).reshape(-1)
+        rec, bb, rr = arr(record), arr(b), arr(rows)
+        p = lambda a: None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)
+        size = lambda a: 0 if a is None else int(a.size)
+        body = np.zeros(size(rec) + size(bb) + 2 * max(int(w), 0) + 16, np.uint8)
+        end = C.c_int(-1)
+        rc = self.lib.nblic_amd_debug_index_capture(self.handle, int(kind), int(effort), int(w), int(row), int(next_end), p(rec), size(rec), p(bb), size(bb),
+                                                    p(rr), size(rr), int(plane_offset), p(body), body.size - 16, C.byref(end))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_index_capture refused its arguments")
+        if rc == -3:
+            raise DeviceCoderGuardError("nblic_amd_debug_index_capture: a byte behind the output has changed")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_index_capture failed (%d)" % rc)
+        return body[:body.size - 16], int(end.value)
 
     def decode_indexed(self, stream: bytes, index: bytes) -> np.ndarray:
         """The whole plane, every segment of the index side by side (``nblic_amd_decode_indexed``); raises when the index

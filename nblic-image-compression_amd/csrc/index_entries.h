@@ -2,8 +2,9 @@
 // indexed batch): how large an index is, where its entries sit, and the entries that WAIT.  An entry written down at
 // an entry row lacks one field, the decoder's 4-byte window: the four stream bytes behind the entry's position, which
 // the coder has not emitted yet (the final flush always provides them).  PendingEntries hands every emitted stream
-// byte to the entries that wait for it and seals an entry once its window is complete.  No HIP, no device: the
-// stand-alone check (tools/index_entries_check.cpp) compiles this file alone, under the sanitizers.
+// byte to the entries that wait for it and seals an entry once its window is complete.  The job list of an indexed batch
+// decode and the launch schedule of a batch index build are laid out here too.  No HIP, no device: the stand-alone
+// checks (tools/index_entries_check.cpp, tools/index_build_plan_check.cpp) compile this file alone, under the sanitizers.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -91,6 +92,48 @@ inline bool indexed_decode_plan(const IndexedPlanImage *im, int n, int cap, std:
             const int round = cap > 0 ? int(jobs.size() / size_t(cap)) : 0;
             jobs.push_back(IndexedJob{k, s, s * I.every, end, indexed_class(I.kind, I.effort), round});
         }
+    }
+    return true;
+}
+
+// ---- the launch schedule of a batch index build (nblic_amd_index_build_plan; pipeline.hip index_build_batch) --------------
+// Image k of a call is decoded from its first row to its last, `rows` rows per launch at most, and stops in front of every
+// entry row R, 2R, ... below h (SerialJob::end_row): a launch advances it by min(rows, next entry row - row), and by
+// min(rows, h - row) behind the last entry.  While no stream fails that is all there is to know, so the whole call is laid
+// out here before anything runs: the images of a class (indexed_class: what one launch can carry) share its launches, a
+// class needs as many as its slowest image, and an entry is captured behind the launch in which its image reaches its row.
+// Entries are listed class by class, within a class by that launch, so the entries one capture launch takes are neighbours.
+struct BuildPlanImage { int kind, effort, h, w, every, rows; };           // rows: what one launch covers (>= 1)
+struct BuildEntry { int image, row, cls, launch; };                       // launch: 0-based, counted within the class
+constexpr int kBuildClasses = 8;
+struct BuildPlan { int launches[kBuildClasses]; std::vector<BuildEntry> entries; };
+// false: an image whose fields are out of range (the plan is empty then).
+inline bool index_build_plan(const BuildPlanImage *im, int n, BuildPlan &P) {
+    P.entries.clear();
+    for (int c = 0; c < kBuildClasses; c++) P.launches[c] = 0;
+    if (n < 1 || !im) return false;
+    for (int k = 0; k < n; k++) {
+        const BuildPlanImage &I = im[k];
+        if (index_bytes(I.kind, I.h, I.w, I.effort, I.every) < 0 || I.rows < 1 || indexed_class(I.kind, I.effort) >= kBuildClasses) return false;
+    }
+    for (int c = 0; c < kBuildClasses; c++) {
+        const size_t first = P.entries.size();
+        for (int k = 0; k < n; k++) {
+            const BuildPlanImage &I = im[k];
+            if (indexed_class(I.kind, I.effort) != c) continue;
+            const int count = (I.h - 1) / I.every;
+            const int per_segment = (I.every + I.rows - 1) / I.rows;                 // launches from one entry row to the next
+            const int tail = (I.h - count * I.every + I.rows - 1) / I.rows;          // and from the last one to the end (>= 1)
+            for (int e = 1; e <= count; e++) P.entries.push_back(BuildEntry{k, e * I.every, c, e * per_segment - 1});
+            const long total = long(count) * per_segment + tail;                     // <= 65534 + 65535
+            if (total > P.launches[c]) P.launches[c] = int(total);
+        }
+        // by launch, stable: images stay in the caller's order within a launch (counting sort over the class's launches)
+        std::vector<BuildEntry> part(P.entries.begin() + ptrdiff_t(first), P.entries.end());
+        std::vector<size_t> at(size_t(P.launches[c]) + 1, 0);
+        for (const BuildEntry &e : part) at[size_t(e.launch) + 1]++;
+        for (size_t l = 1; l < at.size(); l++) at[l] += at[l - 1];
+        for (const BuildEntry &e : part) P.entries[first + at[size_t(e.launch)]++] = e;
     }
     return true;
 }

@@ -273,6 +273,7 @@ struct nblic_amd_ctx {
     int serial_rows = 0;                  // rows per launch of the serial kernels; 0 = sized for a few seconds per launch (nblic_amd_set_serial_rows)
     DevBuf<unsigned long long> d_redo;          // device: pixels whose least-squares system 0 / 1 was redone with integers (SerialJob::redo of every job of the context)
     double idx_split[5] = {0}; long idx_steps = 0;   // the last indexed batch, summed over its group steps: front, totals read-back, back half + entry records, copies (GPU ms); coder wait (host ms).  Guarded by stat_m
+    double idxbuild_split[4] = {0};       // the last batch index build: host checks, uploads and seeding, the decode-and-capture launches, the finish (host ms).  Guarded by stat_m
     double idxdec_split[4] = {0};         // the last indexed batch decode: host checks, uploads, rounds and chain check, copy-out (host ms).  Guarded by stat_m
     long serial_launch_count = 0;         // launches of the serial model / decode kernels since the context was created (reporting, tests)
     size_t feed_chunk = size_t(1) << 20;  // bytes per step in which the drop-in decoders fetch a stream of unknown length (nblic_amd_set_feed_chunk)
@@ -3123,6 +3124,254 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
     return every ? 0 : -1;
 }
 
+// ---- the BATCH INDEX BUILD: the seek indexes of many streams from one decode pass -----------------------------------------
+// What index_build does for one stream per call -- one wave of the band decoder, a host round trip at every band and every
+// entry -- done for many: every accepted stream goes up once and is decoded whole, side by side with the others of its
+// class, and stops in front of each of its entry rows (SerialJob::end_row), where k_index_capture turns the device state
+// into the entry's body and moves end_row on.  While no stream fails a job's progress is known beforehand, so the launches
+// of the whole call and the capture tasks behind each are laid out on the host (index_entries.h index_build_plan), uploaded
+// once and queued back to back; the host waits once, then worker threads put the indexes together -- heads, row hashes,
+// seals -- from one copy of each image's staged bodies and one of its plane.
+struct IdxBuildImage {
+    int k = 0;                          // the caller's image
+    bool ok = false;                    // described
+    DecodeItem it{};
+    std::vector<uint8_t> qtab;
+    int every = 0, count = 0;
+    RecordLayout L{};
+    size_t entry_bytes = 0, need = 0, stride = 0, plane_bytes = 0;      // stride: of one staged body
+    uint8_t *d_stream = nullptr, *d_plane = nullptr, *d_rec = nullptr, *d_stats = nullptr, *d_tab = nullptr, *d_stage = nullptr;
+    SerialState last{};                 // the record's header after the last launch
+    bool good = false;
+};
+static size_t build_stage_stride(const RecordLayout &L) { return (L.tab + 15) & ~size_t(15); }      // record | B | the row slot
+
+static IndexCaptureTask capture_task(const DecodeItem &it, const RecordLayout &L, int row, int next_end, const uint8_t *rec, const uint8_t *stats,
+                                     const uint8_t *plane, int plane_row0, uint8_t *out, SerialJob *job) {
+    const RowsAbove A = rows_above(row, it.w);
+    IndexCaptureTask T{};
+    T.rec = rec; T.stats = L.b_bytes ? stats : nullptr;
+    T.rows = plane + size_t(A.first - plane_row0) * size_t(it.w);
+    T.out = out; T.job = job;
+    T.row = row; T.next_end = next_end;
+    T.rec_bytes = uint32_t(L.b); T.b_bytes = uint32_t(L.b_bytes);
+    T.rows_lead = uint32_t(A.at); T.rows_bytes = uint32_t(size_t(A.n) * size_t(it.w));
+    T.kind = uint32_t(it.kind);
+    return T;
+}
+
+static int index_build_batch(nblic_amd_ctx *c, int n, const unsigned char *const *streams, const size_t *slens, const int *every_rows,
+                             unsigned char *const *indexes, const size_t *icaps, long *ilens, unsigned char *const *planes, const size_t *pcaps,
+                             int *hs, int *ws, int *nears, int *efforts, int *status) {
+    if (!c || c->broken || n < 1 || !streams || !slens || !every_rows || !indexes || !icaps || !ilens || (planes && !pcaps) || !hs || !ws || !nears ||
+        !efforts || !status) return -1;
+    for (int k = 0; k < n; k++) if (!streams[k] || !indexes[k]) return -1;
+    if (hipSetDevice(c->device) != hipSuccess) return -1;
+    using Clock = std::chrono::steady_clock;
+    auto ms_since = [](Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); };
+    double split[4] = {0, 0, 0, 0};
+    auto t0 = Clock::now();
+    std::vector<IdxBuildImage> all{size_t(n)};
+    IdxPool pool;
+    IdxPendingTasks pending;
+    const int n_workers = std::max(1, std::min(n, c->coders_wanted));
+    pool.start(n_workers);
+    pending.add(n);
+    for (int k = 0; k < n; k++)
+        pool.post([&, k] {
+            IdxBuildImage &I = all[size_t(k)];
+            I.k = k;
+            I.it = DecodeItem{k, 0, 0, 0, 0, 0, 0, 0, -1, -1};
+            I.ok = describe_stream(streams[k], slens[k], false, c->max_px, I.it, I.qtab) == Described::ok;
+            pending.done();
+        });
+    pending.wait();
+    split[0] = ms_since(t0);
+    std::vector<IdxBuildImage *> live;
+    for (int k = 0; k < n; k++) {
+        IdxBuildImage &I = all[size_t(k)];
+        status[k] = -1; ilens[k] = -1; hs[k] = ws[k] = 0; nears[k] = efforts[k] = 0;
+        if (!I.ok) continue;
+        const DecodeItem &it = I.it;
+        hs[k] = it.h; ws[k] = it.w; nears[k] = it.near; efforts[k] = it.effort;
+        const long need = index_bytes(it.kind, it.h, it.w, it.effort, every_rows[k]);     // -1: every_rows < 1 or >= h, as index_build refuses it
+        I.plane_bytes = size_t(it.h) * size_t(it.w);
+        if (need < 0 || icaps[k] < size_t(need) || (planes && planes[k] && pcaps[k] < I.plane_bytes)) continue;
+        I.every = every_rows[k]; I.count = (it.h - 1) / I.every;
+        I.L = record_layout(it.kind, it.w, it.effort);
+        I.entry_bytes = index_entry_bytes(it.kind, it.w, it.effort); I.need = size_t(need);
+        I.stride = build_stage_stride(I.L);
+        if (I.entry_bytes != sizeof(DecodeCheckpoint) + I.L.bytes + 32) continue;        // (the two descriptions of an entry agree)
+        live.push_back(&I);
+    }
+    if (live.empty()) return -1;
+    std::stable_sort(live.begin(), live.end(), [](const IdxBuildImage *a, const IdxBuildImage *b) {
+        return indexed_class(a->it.kind, a->it.effort) < indexed_class(b->it.kind, b->it.effort); });
+    const size_t m = live.size();
+    std::vector<BuildPlanImage> plan_in;
+    for (const IdxBuildImage *I : live) plan_in.push_back(BuildPlanImage{I->it.kind, I->it.effort, I->it.h, I->it.w, I->every, rows_per_launch(I->it, c->serial_rows)});
+    BuildPlan plan;
+    if (!index_build_plan(plan_in.data(), int(m), plan)) return -1;
+
+    // from here on a failure is the device's: every accepted image fails, and nothing unverified stays in its buffers
+    Stream st;                                                           // declared before the buffers: they go first
+    std::vector<Stream> copy_st{size_t(std::min(n_workers, 4))};        // the finish: the workers' copies share these (a stream costs milliseconds to make)
+    std::vector<std::mutex> copy_m{copy_st.size()};
+    DevPool mem;
+    auto drop = [&](const IdxBuildImage &I) {
+        status[I.k] = -1; ilens[I.k] = -1;
+        memset(indexes[I.k], 0, I.need);
+        if (planes && planes[I.k]) memset(planes[I.k], 0, I.plane_bytes);
+    };
+    auto fail = [&](const char *what) {
+        fprintf(stderr, "[nblic_amd] batch index build: %s\n", what);
+        if (st) hipStreamSynchronize(st);
+        for (const IdxBuildImage *I : live) drop(*I);
+        return -1;
+    };
+    if (st.create(hipStreamNonBlocking) != hipSuccess) return fail("cannot create a stream");
+    for (Stream &s : copy_st) if (s.create(hipStreamNonBlocking) != hipSuccess) return fail("cannot create a stream");
+    t0 = Clock::now();
+    std::vector<SerialJob> jobs(m);
+    std::vector<IndexTask> seeds;
+    SerialJob *d_jobs = mem.make<SerialJob>(m);
+    IndexTask *d_seeds = mem.make<IndexTask>(m);
+    IndexCaptureTask *d_caps = mem.make<IndexCaptureTask>(std::max<size_t>(1, plan.entries.size()));
+    if (!d_jobs || !d_seeds || !d_caps) return fail("cannot allocate the workspace");
+    size_t arena_bytes = 0;                                              // one block for all images: stream, plane, record, [B | F], tables, staged bodies
+    for (const IdxBuildImage *I : live)
+        arena_bytes += stream_buf_bytes(I->it.len) + up256(I->plane_bytes) + up256(I->L.b) + up256(2 * I->L.b_bytes) + (I->it.kind ? up256(kQTab) : 0) +
+                       up256(size_t(I->count) * I->stride);
+    uint8_t *arena = mem.make<uint8_t>(arena_bytes);
+    if (!arena) return fail("cannot allocate the workspace");
+    for (size_t i = 0, at = 0; i < m; i++) {
+        IdxBuildImage &I = *live[i];
+        const DecodeItem &it = I.it;
+        I.d_stream = arena + at; at += stream_buf_bytes(it.len);
+        I.d_plane = arena + at; at += up256(I.plane_bytes);
+        I.d_rec = arena + at; at += up256(I.L.b);
+        if (I.L.b_bytes) { I.d_stats = arena + at; at += up256(2 * I.L.b_bytes); }
+        if (it.kind) { I.d_tab = arena + at; at += up256(kQTab); }
+        I.d_stage = arena + at; at += up256(size_t(I.count) * I.stride);
+        // a body that was never captured must not pass for one: the finish tells by its header
+        if (hipMemsetAsync(I.d_stage, 0xFF, size_t(I.count) * I.stride, st) != hipSuccess) return fail("upload");
+        if (!upload_stream(I.d_stream, streams[I.k], it.len, st) ||
+            (it.kind && hipMemcpyAsync(I.d_tab, I.qtab.data(), kQTab, hipMemcpyHostToDevice, st) != hipSuccess)) return fail("upload");
+        jobs[i] = decode_job(it, I.d_plane, 0, I.d_stream, 0, reinterpret_cast<SerialState *>(I.d_rec), reinterpret_cast<double *>(I.d_stats), I.d_tab,
+                             plan_in[i].rows, I.every, c->d_redo);
+        IndexTask T{};                                                   // segment 0 of an indexed decode: zeros, pos, avail, final_ = 1; zeros in [B | F]
+        T.rec = I.d_rec; T.stats = I.d_stats;
+        T.avail = it.len; T.first_pos = first_pos(it);
+        T.rec_bytes = uint32_t(I.L.b); T.b_bytes = uint32_t(I.L.b_bytes);
+        T.kind = uint32_t(it.kind);
+        seeds.push_back(T);
+    }
+    // the capture tasks, in the plan's order; first_chunk counts from the first task of the same launch
+    std::vector<IndexCaptureTask> caps;
+    struct CaptureRun { size_t first; int n; uint32_t chunks; };
+    std::vector<std::vector<CaptureRun>> runs(kBuildClasses);
+    for (int cls = 0; cls < kBuildClasses; cls++) runs[size_t(cls)].assign(size_t(plan.launches[cls]), CaptureRun{0, 0, 0u});
+    for (const BuildEntry &E : plan.entries) {
+        IdxBuildImage &I = *live[size_t(E.image)];
+        const int e = E.row / I.every;                                   // 1-based
+        IndexCaptureTask T = capture_task(I.it, I.L, E.row, e < I.count ? E.row + I.every : 0, I.d_rec, I.d_stats, I.d_plane, 0,
+                                          I.d_stage + size_t(e - 1) * I.stride, d_jobs + E.image);
+        CaptureRun &R = runs[size_t(E.cls)][size_t(E.launch)];
+        if (R.n == 0) R.first = caps.size();
+        T.first_chunk = R.chunks;
+        R.n++; R.chunks += index_capture_chunks(T);
+        caps.push_back(T);
+    }
+    uint32_t seed_chunks = 0;
+    if (!idxdec_upload_tasks(seeds, true, d_seeds, seed_chunks, st) ||
+        hipMemcpyAsync(d_jobs, jobs.data(), m * sizeof(SerialJob), hipMemcpyHostToDevice, st) != hipSuccess ||
+        (!caps.empty() && hipMemcpyAsync(d_caps, caps.data(), caps.size() * sizeof(IndexCaptureTask), hipMemcpyHostToDevice, st) != hipSuccess) ||
+        !index_seed_launch(d_seeds, int(m), seed_chunks, st)) return fail("upload");
+    if (hipStreamSynchronize(st) != hipSuccess) return fail("upload");
+    split[1] = ms_since(t0);
+    t0 = Clock::now();
+    long launches_total = 0;
+    for (size_t a = 0; a < m;) {                                         // class by class: decode launch, capture launch, ... -- no wait in between
+        size_t b = a + 1;
+        const int cls = indexed_class(live[a]->it.kind, live[a]->it.effort);
+        while (b < m && indexed_class(live[b]->it.kind, live[b]->it.effort) == cls) b++;
+        for (int l = 0; l < plan.launches[cls]; l++) {
+            const CaptureRun &R = runs[size_t(cls)][size_t(l)];
+            if (!decode_launch(live[a]->it, d_jobs + a, jobs.data() + a, int(b - a), st, true) ||
+                !index_capture_launch(d_caps + R.first, R.n, R.chunks, st)) return fail("launch");
+        }
+        launches_total += plan.launches[cls];
+        a = b;
+    }
+    for (size_t i = 0; i < m; i++)
+        if (hipMemcpyAsync(&live[i]->last, live[i]->d_rec, sizeof(SerialState), hipMemcpyDeviceToHost, st) != hipSuccess) return fail("state");
+    if (hipStreamSynchronize(st) != hipSuccess) return fail("the launches");
+    { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count += launches_total; }
+    split[2] = ms_since(t0);
+    t0 = Clock::now();
+    // the finish, one task per image on the workers (its two copies on one of the call's copy streams, one image at a time per stream)
+    std::atomic<bool> device_failed{false};
+    pending.add(int(m));
+    for (size_t i = 0; i < m; i++)
+        pool.post([&, i] {
+            IdxBuildImage &I = *live[i];
+            const DecodeItem &it = I.it;
+            [&] {
+                if (I.last.status != kDone) {
+                    fprintf(stderr, "[nblic_amd] batch index build: image %d: the stream is damaged or ends too early\n", I.k);
+                    return;
+                }
+                std::vector<uint8_t> stage(size_t(I.count) * I.stride), own_plane;
+                uint8_t *plane = planes && planes[I.k] ? planes[I.k] : nullptr;
+                if (!plane) { own_plane.resize(I.plane_bytes); plane = own_plane.data(); }
+                bool copied;
+                {
+                    const size_t sid = i % copy_st.size();
+                    std::lock_guard<std::mutex> l(copy_m[sid]);
+                    hipStream_t cs = copy_st[sid];
+                    copied = hipSetDevice(c->device) == hipSuccess &&
+                             hipMemcpyAsync(stage.data(), I.d_stage, stage.size(), hipMemcpyDeviceToHost, cs) == hipSuccess &&
+                             hipMemcpyAsync(plane, I.d_plane, I.plane_bytes, hipMemcpyDeviceToHost, cs) == hipSuccess &&
+                             hipStreamSynchronize(cs) == hipSuccess;
+                }
+                if (!copied) { device_failed = true; return; }
+                uint8_t *out = indexes[I.k];
+                IndexHead H = index_head(it, I.every, I.count, it.len);
+                sha256_of(streams[I.k], it.len, H.stream_sha);
+                Sha256 rows_sha;
+                const size_t w = size_t(it.w);
+                for (int e = 1; e <= I.count; e++) {
+                    const int row = e * I.every;
+                    rows_sha.update(plane + size_t(row - I.every) * w, size_t(I.every) * w);
+                    const uint8_t *body = stage.data() + size_t(e - 1) * I.stride;
+                    SerialState S;
+                    memcpy(&S, body, sizeof S);
+                    if (S.next_row != row || S.status != kRunning) return;           // (an entry that was not captured: the plan and the device disagree)
+                    uint8_t *ck = out + index_entry_at(e - 1, I.entry_bytes);
+                    const DecodeCheckpoint C = decode_head(it, I.every, row, S.pos & ~511ull, canonical_sha(rows_sha));
+                    memcpy(ck, &C, sizeof C);
+                    memcpy(ck + sizeof C, body, I.L.tab);
+                    if (it.kind) memcpy(ck + sizeof C + I.L.tab, I.qtab.data(), kQTab);
+                    seal(ck, I.entry_bytes);
+                }
+                index_close(out, &H, I.count, I.entry_bytes);
+                I.good = true;
+            }();
+            pending.done();
+        });
+    pending.wait();
+    if (device_failed) return fail("copies to the host");
+    bool every = true;
+    for (IdxBuildImage *I : live) {
+        if (!I->good) { drop(*I); continue; }
+        status[I->k] = 0; ilens[I->k] = long(I->need);
+    }
+    split[3] = ms_since(t0);
+    { std::lock_guard<std::mutex> l(c->stat_m); for (int k = 0; k < 4; k++) c->idxbuild_split[k] = split[k]; }
+    for (int k = 0; k < n; k++) every = every && status[k] == 0;
+    return every ? 0 : -1;
+}
+
 static nblic_amd_ctx *g_default = nullptr;
 static std::mutex g_default_m;
 
@@ -3726,6 +3975,64 @@ int nblic_amd_debug_index_kernels(nblic_amd_ctx *c, const void *index, size_t in
     return 0;
 }
 
+// ---- k_index_capture on caller-made bytes (tests/test_index_build_batch.py) ------------------------------------------------
+// ONE launch, one task: the record, B and the rows above `row` go up verbatim (the rows at byte plane_offset of a zeroed
+// buffer, so the tests choose the residue of the plane's address) and the staged body comes back.
+int nblic_amd_debug_index_capture(nblic_amd_ctx *c, int kind, int effort, int width, int row, int next_end, const unsigned char *record, size_t record_bytes,
+                                  const unsigned char *b, size_t b_bytes, const unsigned char *rows, size_t rows_bytes, size_t plane_offset,
+                                  unsigned char *body_out, size_t body_cap, int *end_row_out) {
+    if (!c || !record || !rows || !body_out || !end_row_out || index_record_bytes(kind, width, effort) == 0 || width < 1 || width > kIndexMaxSide ||
+        row < 1 || row > kIndexMaxSide || next_end < 0 || plane_offset > 4096) return -1;
+    const DecodeItem it{0, kIndexMaxSide, width, 0, kMinKStep, effort, kind, 0, -1, -1};
+    const RecordLayout L = record_layout(kind, width, effort);
+    const RowsAbove A = rows_above(row, width);
+    if (record_bytes != L.b || b_bytes != L.b_bytes || (b_bytes && !b) || rows_bytes != size_t(A.n) * size_t(width) || body_cap < L.tab) return -1;
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    constexpr size_t kGuard = 256;
+    constexpr uint8_t kPattern = 0xA7;
+    const size_t used = build_stage_stride(L), out_bytes = used + kGuard, plane_bytes = up256(plane_offset + rows_bytes + 16);
+    Stream st;
+    DevPool mem;
+    uint8_t *d_rec = mem.make<uint8_t>(up256(L.b)), *d_stats = mem.make<uint8_t>(up256(2 * L.b_bytes)), *d_plane = mem.make<uint8_t>(plane_bytes);
+    uint8_t *d_out = mem.make<uint8_t>(out_bytes);
+    SerialJob *d_job = mem.make<SerialJob>(1);
+    IndexCaptureTask *d_task = mem.make<IndexCaptureTask>(1);
+    if (!d_rec || !d_stats || !d_plane || !d_out || !d_job || !d_task || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    std::vector<uint8_t> back(out_bytes);
+    SerialJob J{};
+    J.end_row = row;
+    bool acted = false;
+    const bool ok = [&]() -> bool {
+        HIP_OK(hipMemcpyAsync(d_rec, record, L.b, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(d_stats, 0, up256(2 * L.b_bytes), st));
+        if (L.b_bytes) HIP_OK(hipMemcpyAsync(d_stats, b, L.b_bytes, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(d_plane, 0, plane_bytes, st));
+        HIP_OK(hipMemcpyAsync(d_plane + plane_offset, rows, rows_bytes, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(d_out, kPattern, out_bytes, st));
+        HIP_OK(hipMemcpyAsync(d_job, &J, sizeof J, hipMemcpyHostToDevice, st));
+        // the plane here holds rows [row - n, row) alone, from plane_offset on
+        IndexCaptureTask T = capture_task(it, L, row, next_end, d_rec, d_stats, d_plane + plane_offset, A.first, d_out, d_job);
+        HIP_OK(hipMemcpyAsync(d_task, &T, sizeof T, hipMemcpyHostToDevice, st));
+        if (!index_capture_launch(d_task, 1, index_capture_chunks(T), st)) return false;
+        HIP_OK(hipMemcpyAsync(back.data(), d_out, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(&J, d_job, sizeof J, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    if (!ok) return -2;
+    SerialState S;
+    memcpy(&S, record, sizeof S);
+    acted = S.status == kRunning && S.next_row == row;
+    for (size_t i = acted ? used : 0; i < out_bytes; i++)
+        if (back[i] != kPattern) return -3;
+    for (size_t i = L.tab; acted && i < used; i++)                        // the last unit is filled up with zeros
+        if (back[i] != 0) return -3;
+    memcpy(body_out, back.data(), L.tab);
+    *end_row_out = J.end_row;
+    return 0;
+}
+
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
 
 void nblic_amd_set_max_pixels(nblic_amd_ctx *c, long max_pixels) {
@@ -3980,6 +4287,37 @@ long nblic_amd_indexed_decode_plan(int n_images, const int *kinds, const int *ef
             memcpy(jobs + 6 * j, v, sizeof v);
         }
     return long(plan.size());
+}
+int nblic_amd_index_build_batch(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens, const int *every_rows,
+                                unsigned char *const *indexes, const size_t *index_caps, long *index_lens, unsigned char *const *planes,
+                                const size_t *plane_caps, int *heights, int *widths, int *nears, int *efforts, int *status) {
+    return index_build_batch(c, n_images, streams, stream_lens, every_rows, indexes, index_caps, index_lens, planes, plane_caps, heights, widths, nears, efforts, status);
+}
+int nblic_amd_index_build_split(nblic_amd_ctx *c, double ms[4]) {
+    if (!c || !ms) return -1;
+    std::lock_guard<std::mutex> l(c->stat_m);
+    for (int k = 0; k < 4; k++) ms[k] = c->idxbuild_split[k];
+    return 0;
+}
+long nblic_amd_index_build_plan(int n_images, const int *kinds, const int *efforts, const int *heights, const int *widths, const int *every_rows,
+                                int serial_rows, int *class_launches, int *entries, size_t entries_cap) {
+    if (n_images < 1 || !kinds || !efforts || !heights || !widths || !every_rows || serial_rows < 0) return -1;
+    std::vector<BuildPlanImage> im;
+    for (int k = 0; k < n_images; k++) {
+        if (index_bytes(kinds[k], heights[k], widths[k], efforts[k], every_rows[k]) < 0) return -1;
+        const DecodeItem it{k, heights[k], widths[k], 0, kMinKStep, efforts[k], kinds[k], 0, -1, -1};
+        im.push_back(BuildPlanImage{kinds[k], efforts[k], heights[k], widths[k], every_rows[k], rows_per_launch(it, serial_rows)});
+    }
+    BuildPlan plan;
+    if (!index_build_plan(im.data(), n_images, plan)) return -1;
+    if (class_launches) memcpy(class_launches, plan.launches, sizeof plan.launches);
+    if (entries && entries_cap >= plan.entries.size())
+        for (size_t j = 0; j < plan.entries.size(); j++) {
+            const BuildEntry &E = plan.entries[j];
+            const int v[4] = {E.image, E.row, E.cls, E.launch};
+            memcpy(entries + 4 * j, v, sizeof v);
+        }
+    return long(plan.entries.size());
 }
 int nblic_amd_decode_rows(nblic_amd_ctx *c, const unsigned char *stream, size_t stream_bytes, const void *index, size_t index_bytes, int row0,
                           int row1, unsigned char *out, size_t cap) {

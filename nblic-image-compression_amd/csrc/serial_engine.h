@@ -146,6 +146,38 @@ inline uint32_t index_task_chunks(const IndexTask &t, bool seed) { return (index
 bool index_seed_launch(const IndexTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
 bool index_chain_launch(const IndexTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
 
+// ---- a batch index build's entry capture, on the device: the inverse of k_index_seed -------------------------------------
+// A decode job that has stopped in front of an entry row (SerialJob::end_row) holds everything that entry's body is made
+// of: its record, B in the first half of [B | F], the two rows above in the plane.  k_index_capture, one task per (job,
+// entry), writes that body -- record | B | the 2 w-byte row slot -- to a 16-byte-aligned place in the image's staging buffer,
+// from where the host moves it to its place in the index (any address) while it hashes it; the kernel stores whole
+// aligned 16-byte units only, the slot's last one filled up with zeros.  A task ACTS only when the job's record says
+// status kRunning and next_row == row, and writes nothing otherwise: a job that failed, or has not arrived, captures nothing.
+//   the record   the header as a checkpoint holds it (pipeline.hip dstream_checkpoint): status kRunning, avail, final_ and the
+//                padding zero, the rest verbatim; the tables verbatim -- except NBLIC's symbol -> rank bytes [kRecRank,
+//                kRecSym), which the lean decoder never writes back: they are rebuilt as the inverse of the rank -> symbol
+//                bytes, rank[m][sym[m][i]] = i, for either decoder image (0 for a symbol the rank -> symbol bytes do not name)
+//   the rows     read byte by byte: the plane lies at any address
+// The workgroup of a task's chunk 0 then sets the job's end_row to next_end (the next entry row; 0 behind the last), which
+// nothing else in the launch reads.
+struct IndexCaptureTask {
+    const uint8_t *rec;                    // the job's state record
+    const uint8_t *stats;                  // [B | F]; null when the mode has none
+    const uint8_t *rows;                   // the plane byte of the first row rows_above names (rows_bytes of them follow)
+    uint8_t *out;                          // the staged body (a multiple of 16)
+    SerialJob *job;                        // the job in the launches' job array
+    int row, next_end;
+    uint32_t rec_bytes, b_bytes;           // of the record and of B (multiples of 16)
+    uint32_t rows_lead, rows_bytes;        // the slot: rows_lead zeros, then rows_bytes from the plane (together 2 w)
+    uint32_t kind;                         // 0 NBLIC, 1 QNBLIC
+    uint32_t first_chunk;                  // chunks of the launch's tasks in front of this one
+};
+static_assert(sizeof(IndexCaptureTask) == 72, "uploaded as bytes");
+inline uint32_t index_capture_units(const IndexCaptureTask &t) { return t.rec_bytes / 16 + t.b_bytes / 16 + (t.rows_lead + t.rows_bytes + 15) / 16; }
+inline uint32_t index_capture_chunks(const IndexCaptureTask &t) { return (index_capture_units(t) + kIndexChunkBytes / 16 - 1) / (kIndexChunkBytes / 16); }
+// d_tasks[0..n) with first_chunk filled in (from 0), `chunks` their sum.  false: the launch failed.
+bool index_capture_launch(const IndexCaptureTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
+
 // Both least-squares solvers of the serial kernels on `count` given systems, no image and no coder (tests): stats = count x vec_len(n)
 // integer-valued statistics [s | b | A], vn = count x 10 regressors, bias = the regularisation strength the pixel starts from (the two
 // systems of an item are the ones bias_pair makes of it).  n = 6 or 10; waves = 2 (n = 10 only) runs the two-wave hand-over.  Per item

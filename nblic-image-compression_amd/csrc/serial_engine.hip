@@ -1639,7 +1639,8 @@ __device__ __forceinline__ u32x4 load16_any(const NB_GLOBAL uint8_t *p) {
 }
 
 // The task a chunk belongs to: the last one whose first_chunk is not behind it (every lane reads the same words).
-__device__ __forceinline__ int index_task_of(const IndexTask *__restrict__ tasks, int n, uint32_t chunk) {
+template <class Task>
+__device__ __forceinline__ int index_task_of(const Task *__restrict__ tasks, int n, uint32_t chunk) {
     int lo = 0, hi = n - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -1722,6 +1723,76 @@ bool index_seed_launch(const IndexTask *d_tasks, int n, uint32_t chunks, hipStre
 bool index_chain_launch(const IndexTask *d_tasks, int n, uint32_t chunks, hipStream_t s) {
     if (n <= 0 || chunks == 0) return true;
     hipLaunchKernelGGL(k_index_chain, dim3(chunks), dim3(kIndexThreads), 0, s, d_tasks, n);
+    return hipGetLastError() == hipSuccess;
+}
+
+// ---- batch index build: entry capture (serial_engine.h IndexCaptureTask) ----------------------------------------------------
+// The symbol -> rank bytes [16 unit, 16 unit + 16) of the re-mappers, from the rank -> symbol bytes at `sym`: byte b belongs
+// to re-mapper b / 20 and symbol b % 20, and holds the rank i at which that re-mapper's rank -> symbol bytes name the symbol.
+// Sixteen bytes touch two re-mappers at most; each one's twenty bytes are five aligned words, searched in registers.
+__device__ __forceinline__ u32x4 rank_unit(const NB_GLOBAL uint32_t *sym, uint32_t unit) {
+    constexpr uint32_t kSyms = uint32_t(kMapSyms);
+    const uint32_t b0 = unit * 16, m0 = b0 / kSyms, m1 = (b0 + 15) / kSyms;       // m1 <= 511: the last unit ends the last re-mapper
+    uint32_t w0[5], w1[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) { w0[k] = sym[m0 * 5 + k]; w1[k] = sym[m1 * 5 + k]; }
+    uint32_t out[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        const uint32_t b = b0 + uint32_t(j);
+        const bool second = b >= (m0 + 1) * kSyms;
+        const uint32_t s = b - (second ? m1 : m0) * kSyms;
+        uint32_t rank = 0;
+#pragma unroll
+        for (int i = 0; i < kMapSyms; i++) {
+            const uint32_t word = second ? w1[i >> 2] : w0[i >> 2];
+            if (((word >> ((i & 3) * 8)) & 0xFFu) == s) rank = uint32_t(i);
+        }
+        out[j >> 2] |= rank << ((j & 3) * 8);
+    }
+    return u32x4{out[0], out[1], out[2], out[3]};
+}
+static_assert(kMapSyms == 20 && (512 * kMapSyms) % 16 == 0, "rank_unit: five words per re-mapper, whole units");
+
+__global__ void __launch_bounds__(kIndexThreads) k_index_capture(const IndexCaptureTask *__restrict__ tasks, int n) {
+    const IndexCaptureTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
+    const NB_GLOBAL SerialState *st = (const NB_GLOBAL SerialState *)gp(T.rec);
+    if (st->status != kRunning || st->next_row != T.row) return;     // the job failed, or is not there: nothing is written
+    const NB_GLOBAL u32x4 *rec = (const NB_GLOBAL u32x4 *)gp(T.rec), *stats = (const NB_GLOBAL u32x4 *)gp(T.stats);
+    const NB_GLOBAL uint32_t *sym = (const NB_GLOBAL uint32_t *)gp(T.rec) + sizeof(SerialState) / 4 + kRecSym;
+    const NB_GLOBAL uint8_t *rows = gp(T.rows);
+    NB_GLOBAL u32x4 *out = (NB_GLOBAL u32x4 *)gp(T.out);
+    const uint32_t ru = T.rec_bytes / 16, bu = T.b_bytes / 16, slot = T.rows_lead + T.rows_bytes, wu = (slot + 15) / 16;
+    const uint32_t u0 = (blockIdx.x - T.first_chunk) * kIndexChunkUnits;
+    const bool nblic = T.kind == 0;
+    for (uint32_t j = threadIdx.x; j < kIndexChunkUnits; j += kIndexThreads) {
+        const uint32_t u = u0 + j;
+        if (u < ru) {
+            u32x4 v;
+            if (u == 2 || u == 3) v = u32x4{0u, 0u, 0u, 0u};                // avail, final_, pad
+            else if (nblic && u >= kRankUnit0 && u < kRankUnit1) v = rank_unit(sym, u - kRankUnit0);
+            else v = rec[u];
+            if (u == 0) v.y = uint32_t(kRunning);
+            out[u] = v;
+        } else if (u < ru + bu) {
+            out[u] = stats[u - ru];
+        } else if (u < ru + bu + wu) {
+            const uint32_t o0 = (u - ru - bu) * 16;
+            uint32_t word[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const uint32_t o = o0 + uint32_t(k);
+                if (o >= T.rows_lead && o < slot) word[k >> 2] |= uint32_t(rows[o - T.rows_lead]) << ((k & 3) * 8);
+            }
+            out[u] = u32x4{word[0], word[1], word[2], word[3]};
+        }
+    }
+    if (blockIdx.x == T.first_chunk && threadIdx.x == 0) gp(T.job)->end_row = T.next_end;
+}
+
+bool index_capture_launch(const IndexCaptureTask *d_tasks, int n, uint32_t chunks, hipStream_t s) {
+    if (n <= 0 || chunks == 0) return true;
+    hipLaunchKernelGGL(k_index_capture, dim3(chunks), dim3(kIndexThreads), 0, s, d_tasks, n);
     return hipGetLastError() == hipSuccess;
 }
 
