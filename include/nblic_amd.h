@@ -161,6 +161,33 @@ void nblic_amd_set_max_pixels(nblic_amd_ctx *ctx, long max_pixels);
 void nblic_amd_set_serial_rows(nblic_amd_ctx *ctx, int rows);
 long nblic_amd_serial_launches(nblic_amd_ctx *ctx);
 
+/* Long chains.  The staged kernels (-n0 -e1, QNBLIC's model stage, the staged band front, the indexed batch) replay each
+ * table entry's records as one chain, and on flat, saturated or document-like content one entry holds nearly all of
+ * them.  The context-bias chains are cut into blocks of 4096 records whose start state is found by running two copies
+ * from the extreme states over the 3072 records before the block; where the copies do not meet (a constant error parks
+ * them up to 127 apart) the block is replayed from each of the at most 128 states between them, which leaves a table
+ * "start state -> end state", the chain's blocks are then walked with one look-up each, and the outputs are written
+ * a lane per block.  No output byte depends on any of this.
+ * The re-mapper chains' hit counts never decay and belong to symbols, so the counts by symbol at any record are the chain's
+ * start counts plus a histogram prefix; only the permutation at a block's first record is unknown.  A chain of at least
+ * min_records records is cut into blocks of block_records: every block is replayed from a GUESSED permutation (symbols by
+ * descending count, ties in the chain's starting order, refined over the block before), and accepted, in order, only if
+ * the guess is the block before's true end permutation -- otherwise it is replayed from the true state.  A wrong guess
+ * costs time, never a byte.
+ *   min_records, block_records: 0 = the defaults (65536, 4096); block_records is at least 128.
+ *   min_records < 0  turns both parts off: blocks whose copies did not meet are replayed in order by one lane per chain
+ *   and no re-mapper chain is cut -- the launch sequence before either existed (A/B runs, an escape hatch).
+ * Both values travel in every job record.  No output byte depends on either.
+ * nblic_amd_long_chain_stats: blocks since the context was created or last reset (reset != 0 clears after reading):
+ *   counts[0] context-chain blocks whose copies met      counts[3] re-mapper chains cut into blocks
+ *   counts[1] ... resolved through a table                counts[4] re-mapper blocks whose guessed start was right
+ *   counts[2] ... replayed serially, in order             counts[5] re-mapper blocks replayed after a wrong guess
+ *   counts[6], counts[7] are 0.  counts[2] is 0 on every input unless min_records < 0.  The device words ride in the
+ * totals record every front half already reads back.  ctx == NULL addresses the context behind the drop-in entry points.
+ * Returns 0, -1 for bad arguments.                                                                              */
+void nblic_amd_set_long_chains(nblic_amd_ctx *ctx, int min_records, int block_records);
+int nblic_amd_long_chain_stats(nblic_amd_ctx *ctx, long counts[8], int reset);
+
 /* Efforts 2 / 3 carry the reference's int64 least squares in doubles and redo a pixel with plain 64-bit integers when
  * one of its two systems leaves the range in which the doubles are exact.  counts[0] / counts[1]: the pixels
  * whose system 0 / system 1 did, over every encode and decode of the context since it was created or last reset

@@ -39,7 +39,7 @@ EXPORTS = (
     "nblic_amd_create", "nblic_amd_create_ex", "nblic_amd_destroy", "nblic_amd_encode_batch", "nblic_amd_encode_batch_begin", "nblic_amd_encode_batch_end", "nblic_amd_qencode_batch", "nblic_amd_set_max_pixels",
     "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage", "nblic_amd_debug_live", "nblic_amd_debug_takes", "nblic_amd_debug_pack_rows", "nblic_amd_debug_device_code", "nblic_amd_debug_model_stages", "nblic_amd_debug_back_half", "nblic_amd_debug_entropy_front",
     "nblic_amd_encode_batch_modes", "nblic_amd_decode_batch", "nblic_amd_serial_selftest",
-    "nblic_amd_set_serial_rows", "nblic_amd_serial_launches", "nblic_amd_lsq_redo_counts", "nblic_amd_serial_plan", "nblic_amd_lsq_probe", "nblic_amd_set_feed_chunk", "nblic_amd_last_fed_bytes",
+    "nblic_amd_set_serial_rows", "nblic_amd_serial_launches", "nblic_amd_set_long_chains", "nblic_amd_long_chain_stats", "nblic_amd_lsq_redo_counts", "nblic_amd_serial_plan", "nblic_amd_lsq_probe", "nblic_amd_set_feed_chunk", "nblic_amd_last_fed_bytes",
     "nblic_amd_stream_begin", "nblic_amd_stream_resume", "nblic_amd_stream_run", "nblic_amd_stream_checkpoint", "nblic_amd_stream_progress",
     "nblic_amd_stream_recon", "nblic_amd_stream_end", "nblic_amd_stream_check",
     "nblic_amd_dstream_begin", "nblic_amd_dstream_resume", "nblic_amd_dstream_check", "nblic_amd_dstream_feed", "nblic_amd_dstream_info",
@@ -130,6 +130,11 @@ def load_library() -> C.CDLL:
     lib.nblic_amd_set_serial_rows.argtypes = [C.c_void_p, C.c_int]
     lib.nblic_amd_serial_launches.restype = C.c_long
     lib.nblic_amd_serial_launches.argtypes = [C.c_void_p]
+    if hasattr(lib, "nblic_amd_set_long_chains"):                  # (an older build loaded through NBLIC_AMD_LIB has neither)
+        lib.nblic_amd_set_long_chains.restype = None
+        lib.nblic_amd_set_long_chains.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        lib.nblic_amd_long_chain_stats.restype = C.c_int
+        lib.nblic_amd_long_chain_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.c_int]
     lib.nblic_amd_lsq_redo_counts.restype = C.c_int
     lib.nblic_amd_lsq_redo_counts.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
     lib.nblic_amd_serial_plan.restype = C.c_int
@@ -898,6 +903,21 @@ class Context:
 
     def serial_launches(self) -> int:
         return int(self.lib.nblic_amd_serial_launches(self.handle))
+
+    LONG_CHAIN_COUNTS = ("s2_met", "s2_table", "s2_serial", "s3_split", "s3_accepted", "s3_missed")
+
+    def set_long_chains(self, min_records: int = 0, block_records: int = 0):
+        """How the staged kernels treat chains that hold most of an image (``nblic_amd_set_long_chains``): 0 = the
+        defaults, ``min_records < 0`` = off (context-chain blocks whose copies did not meet are replayed in order).
+        Shows in no output byte."""
+        self.lib.nblic_amd_set_long_chains(self.handle, min_records, block_records)
+
+    def long_chain_stats(self, reset: bool = False) -> dict:
+        """Blocks by how they were resolved since the last reset (``nblic_amd_long_chain_stats``)."""
+        v = (C.c_long * 8)()
+        if self.lib.nblic_amd_long_chain_stats(self.handle, v, int(reset)) != 0:
+            raise RuntimeError("nblic_amd_long_chain_stats failed")
+        return dict(zip(self.LONG_CHAIN_COUNTS, (int(x) for x in v)))
 
     def lsq_redo_counts(self, reset: bool = False) -> Tuple[int, int]:
         """Pixels (efforts 2 / 3) whose least-squares system 0 / 1 left the exact range of the doubles and was redone with

@@ -11,6 +11,13 @@ constexpr uint32_t kMaxSegments = 1024;   // waves per partition pass (pixel par
 // 9x write amplification.  256 waves per image keep the open lines of a launch resident.
 constexpr uint32_t kTouchSegments = 256;
 constexpr int kTotalsStride = 8, kWideTouchFlag = 4;      // words per image in the totals array; index of the wide-position flag
+// The spare words of an image's totals count the S2 blocks of its last front half (kernels_e1.hip k_bias_blocks ..
+// k_bias_replay): warm-up copies met / resolved through a candidate table / replayed serially in order.
+constexpr int kLongS2Met = 5, kLongS2Table = 6, kLongS2Serial = 7;
+// The device array has kTotalsSlot words per image: the totals record, then the re-mapper chains' counts (k_map_plan ..
+// k_map_check): chains cut into blocks / blocks whose guessed start permutation was right / blocks replayed after a miss.
+constexpr int kTotalsSlot = 16, kLongS3Split = 8, kLongS3Accepted = 9, kLongS3Missed = 10;
+constexpr int kLongBlockMin = 128;         // records per block of a cut re-mapper chain, at least (sizes mblk_cnt / mblk_perm)
 
 struct SegPlan { int nseg; uint32_t seg_len; };
 SegPlan make_plan(uint32_t n_items, uint32_t max_segments = kMaxSegments);
@@ -34,7 +41,7 @@ struct E1Buffers {
     uint32_t *ev_off;        // n      exclusive scan of cnt
     uint32_t *table;         // 4096 * kMaxSegments   partition histogram / offsets
     uint32_t *scan_sums;     // scan scratch
-    uint32_t *totals;        // [kTotalsStride] item totals: adr, mapper, events, touches; [kWideTouchFlag] 1 = this image needs 32-bit touch positions
+    uint32_t *totals;        // [kTotalsSlot] item totals: adr, mapper, events, touches; [kWideTouchFlag] 1 = this image needs 32-bit touch positions; [kLongS2Met ..] block counts of S2
     int      *ctx_state;     // 2048
     int      *map_state;     // 512 * 60
     int      *cnt_state;     // 4096 * 2
@@ -45,6 +52,13 @@ struct E1Buffers {
     uint32_t *blk_base;      // 2049          first block of every context chain (+ total)
     int      *blk_end;       // n/4096+2048   context state at the end of each block
     uint8_t  *blk_ok;        // n/4096+2048   1 = the block's warm-up copies met (its output is exact)
+    int      *blk_cand;      // 2 * (n/4096+2048)  per block whose copies did not meet: the lower copy at its first record (after k_bias_fixup: the exact state there), its table (-1 = none)
+    uint32_t *blk_item;      // n/4096+64     table -> block
+    int      *blk_tab;       // 128 * (n/4096+64)  per table: the block's end state from each of the 128 candidate start states
+    uint32_t *mblk_base;     // 513           first block of every cut re-mapper chain (+ total); a chain that is not cut has none
+    uint32_t *mblk_cnt;      // 20 * (n/128+512)   per block: hits by SYMBOL at its first record (k_map_hist leaves the block's own histogram, k_map_prefix the sums)
+    uint32_t *mend_cnt;      // 512 * 20      hits by symbol behind a cut chain's last record
+    uint64_t *mblk_perm;     // 4 * (n/128+512)    per block: symbol -> rank (Perm20) it was started with, and at its end
     uint32_t *qhist;         // 12 * 256      QNBLIC symbol histograms per activity level
     unsigned long long *dbg_out;   // 4096 words of in-kernel cycle stamps, written only when E1Job::dbg & 8
     uint32_t *win_base;      // 4097 + 4096   first window record of every counter chain (+ total); chain keys, longest first
@@ -64,6 +78,8 @@ struct E1Job {
     int dbg;             // timing experiments only (NBLIC_AMD_DBG); 0 in normal operation
     int near, k_step;    // serial modes only (the staged -e1 kernels use the lossless constants 0 and 3)
     uint64_t ktab;       // model.h level_shift_table(k_step)
+    int long_min, long_block;   // long chains (nblic_amd_set_long_chains): a re-mapper chain of >= long_min records is cut into blocks of long_block;
+                                // long_min < 0 = none is, and context-chain blocks whose copies did not meet are replayed serially, in order
     int row0;            // the image row at index 0 of b.img / b.rec1: 0 for a whole image; a row band of the band encoder
                          // (e1_launch_front_band) has h = its rows, b.img = plane + row0 * w, and the plane goes on above b.img
     // Where the coded bins go.  pack_rows == nullptr: b.coded, one u16 (prob | bin << 15) per bin, for an image that is

@@ -7,9 +7,11 @@
 //
 //   k_predict            S1  stateless, one lane per pixel        -> rec1[t]
 //   partition by adr     (count -> scan -> scatter)               -> s2in[]  grouped by context, pos2[t]
-//   k_bias_blocks/_fixup S2  one LANE per 4096-record block of a context chain (monotone coupling) -> s2out[] (state >> 7)
+//   k_bias_blocks/_fixup S2  one LANE per 4096-record block of a context chain (monotone coupling; blocks whose copies
+//                            did not meet: k_bias_tabulate / k_bias_replay)                  -> s2out[] (state >> 7)
 //   partition by px|sign (gathers s2out through pos2)             -> s3in[]  grouped by re-mapper, pos3[t]
-//   k_mapper_chains      S3  one LANE per re-mapper chain (16 per wave), counts in LDS -> s3out[] (z, same order)
+//   k_mapper_chains      S3  one LANE per re-mapper chain (16 per wave), counts in LDS -> s3out[] (z, same order);
+//                            a chain that holds most of an image is cut into blocks (k_map_plan .. k_map_check)
 //   k_count_bins/k_emit_bins  S4 stateless (gathers z through pos3)     -> events[r]
 //   partition by counter (even / odd trees; hot chains staged in LDS) -> tin[] grouped by counter, two position arrays
 //   k_counter_epochs     S5a one WAVE per counter chain: resolves the halvings        -> win_recs[]
@@ -438,9 +440,20 @@ __global__ void __launch_bounds__(256) k_adr_scatter(const E1Job *__restrict__ j
 // within ~2100 records (the error dithers the floor).  Each chain is therefore cut into blocks
 // of kBiasBlock records; a lane warms both copies up over the kBiasWarm records before its
 // block, takes the common state if they met, and replays its block.  Blocks whose copies did
-// not meet (flat regions: a constant error parks them 127 apart) are replayed afterwards from
-// their predecessor's end state by k_bias_fixup, in order -- still exact, just serial.
+// not meet (flat regions: a constant error parks them 127 apart) are resolved through TABLES:
+//
+// The gap of the two copies obeys g' <= ceil(127 g / 128), so after kBiasWarm records it is below kBiasCands
+// whatever the errors were (from 2 * kExtreme: 869 steps for NbModel, 1311 for QModel), and by monotonicity
+// the true state at the block's first record is one of the <= 128 values [va, vb].  k_bias_tabulate replays the
+// block from every candidate -- a lane each, all lanes on the same record -- and keeps only the end states; k_bias_fixup
+// then walks a chain's blocks with ONE look-up per block (a candidate's image lies inside the next block's
+// [va, vb]: a copy started earlier at an extreme stays inside one started later), which leaves every such block's exact
+// start state, and k_bias_replay writes their outputs, a lane per block.  With E1Job::long_min < 0 none of this runs
+// and such blocks are replayed from their predecessor's end state by k_bias_fixup, in order -- exact too, but serial.
 constexpr uint32_t kBiasBlock = 4096, kBiasWarm = 3072;
+constexpr int kBiasCands = 128;
+// tables of an image: only a chain's blocks behind its first can fail to meet
+__device__ __forceinline__ uint32_t bias_table_cap(const E1Job &J) { return J.n / kBiasBlock + 1u; }
 
 // blocks per chain -> exclusive scan -> blk_base[kKeys + 1]; one 1024-thread block per job
 template <class M>
@@ -465,6 +478,15 @@ __global__ void __launch_bounds__(1024) k_plan_blocks(const E1Job *__restrict__ 
     for (int wv = 0; wv < int(threadIdx.x >> 6); wv++) pre += part[wv];
     for (int k = 0; k < kPer; k++) { blk_base[threadIdx.x * kPer + k] = pre; pre += cnt[k]; }
     if (threadIdx.x == 1023) blk_base[M::kKeys] = pre;
+    if (threadIdx.x < 3) { gptr(J.b.totals)[kLongS2Met + threadIdx.x] = 0u; gptr(J.b.totals)[kLongS3Split + threadIdx.x] = 0u; }   // the block counts of this front half
+}
+
+// which chain owns block `item`?  the largest key with blk_base[key] <= item
+template <class M>
+__device__ __forceinline__ int chain_of_block(NB_GLOBAL const uint32_t *blk_base, uint32_t item) {
+    int lo = 0, hi = M::kKeys;                                        // invariant: blk_base[lo] <= item < blk_base[hi]
+    while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (blk_base[mid] <= item) lo = mid; else hi = mid; }
+    return lo;
 }
 
 // one LANE per block of any chain; grid.x is an upper bound on the block count
@@ -478,13 +500,7 @@ __global__ void __launch_bounds__(64) k_bias_blocks(const E1Job *__restrict__ jo
     const uint32_t item = blockIdx.x * 64u + threadIdx.x;
     if (blockIdx.x * 64u >= n_items) return;                          // whole wave idle
     const bool have = item < n_items;
-    // which chain?  largest key with blk_base[key] <= item
-    int key = 0;
-    if (have) {
-        int lo = 0, hi = M::kKeys;                                    // invariant: blk_base[lo] <= item < blk_base[hi]
-        while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (blk_base[mid] <= item) lo = mid; else hi = mid; }
-        key = lo;
-    }
+    const int key = have ? chain_of_block<M>(blk_base, item) : 0;
     const int nseg = J.pp.nseg;
     const uint32_t c_start = table[size_t(key) * nseg];
     const uint32_t c_end = key + 1 < M::kKeys ? table[size_t(key + 1) * nseg] : J.n;
@@ -497,18 +513,61 @@ __global__ void __launch_bounds__(64) k_bias_blocks(const E1Job *__restrict__ jo
     const int v0 = gptr(J.b.ctx_state)[key];
     int va = exact ? v0 : -M::kExtreme, vb = exact ? v0 : M::kExtreme;
     bool met = false;
+    int va0 = 0, vb0 = 0;                                             // the copies at the block's first record
     run_lane_streams(s2in, s2out, have ? w_start : 0u, b_end, b_start, stage, [&](uint32_t rec, uint32_t idx) {
         const int e = M::err_of(rec);
-        if (idx == b_start) met = va == vb;                           // did the two copies meet during the warm-up?
+        if (idx == b_start) { met = va == vb; va0 = va; vb0 = vb; }   // did the two copies meet during the warm-up?
         uint32_t o = uint32_t(va >> M::kOutShift);
         va = M::update(va, e);
         if (idx < b_start) vb = M::update(vb, e);                     // warm-up: carry the second copy too
         return o;
     });
     if (have) { blk_end[item] = va; gptr(J.b.blk_ok)[item] = uint8_t(met); }
+    const uint64_t n_met = __ballot(have && met);
+    if (lane_id() == 0 && n_met) atomicAdd(J.b.totals + kLongS2Met, uint32_t(__popcll(n_met)));
+    if (have && !met && J.long_min >= 0) {
+        int table = -1;                                               // (the gap bound and the table count cannot fail; a block without a table is replayed in order)
+        if (vb0 - va0 < kBiasCands) {
+            const uint32_t t = atomicAdd(J.b.totals + kLongS2Table, 1u);
+            if (t < bias_table_cap(J)) { table = int(t); gptr(J.b.blk_item)[t] = item; }
+        }
+        gptr(J.b.blk_cand)[2 * size_t(item)] = va0; gptr(J.b.blk_cand)[2 * size_t(item) + 1] = table;
+    }
 }
 
-// one lane per chain: replays, in order, the blocks whose warm-up did not meet; publishes the final state
+// one 128-lane workgroup per table: lane k replays the block from va + k and keeps the end state
+template <class M>
+__global__ void __launch_bounds__(kBiasCands) k_bias_tabulate(const E1Job *__restrict__ jobs) {
+    __shared__ u32x2 recs[kBiasBlock / 4];
+    const E1Job &J = jobs[blockIdx.y];
+    const uint32_t t = blockIdx.x;
+    if (t >= min(gptr(J.b.totals)[kLongS2Table], bias_table_cap(J))) return;
+    const auto s2in = gptr(J.b.s2in); const auto table = gptr(J.b.table); const auto blk_base = gptr(J.b.blk_base);
+    const uint32_t item = gptr(J.b.blk_item)[t];
+    const int key = chain_of_block<M>(blk_base, item);
+    const int nseg = J.pp.nseg;
+    const uint32_t c_start = table[size_t(key) * nseg];
+    const uint32_t c_end = key + 1 < M::kKeys ? table[size_t(key + 1) * nseg] : J.n;
+    const uint32_t b_start = c_start + (item - blk_base[key]) * kBiasBlock;
+    const uint32_t len = min(c_end, b_start + kBiasBlock) - b_start;
+    const auto rec16 = reinterpret_cast<uint16_t *>(recs);
+    for (uint32_t i = threadIdx.x; i < len; i += uint32_t(kBiasCands)) rec16[i] = s2in[b_start + i];
+    __syncthreads();
+    int v = min(gptr(J.b.blk_cand)[2 * size_t(item)] + int(threadIdx.x), M::kExtreme);
+    uint32_t q = 0;                                                   // every lane reads the same word: an LDS broadcast
+#pragma unroll 4
+    for (; q < len / 4u; q++) {
+        const u32x2 w = recs[q];
+        v = M::update(v, M::err_of(w.x & 0xFFFFu)); v = M::update(v, M::err_of(w.x >> 16));
+        v = M::update(v, M::err_of(w.y & 0xFFFFu)); v = M::update(v, M::err_of(w.y >> 16));
+    }
+    for (uint32_t i = q * 4u; i < len; i++) v = M::update(v, M::err_of(rec16[i]));
+    gptr(J.b.blk_tab)[size_t(t) * kBiasCands + threadIdx.x] = v;
+}
+
+// one lane per chain: walks its blocks in order -- a met block's end state is known, a block with a table takes it from
+// there (and leaves its exact start state for k_bias_replay), a block with neither is replayed here -- and publishes the
+// final state
 template <class M>
 __global__ void __launch_bounds__(64) k_bias_fixup(const E1Job *__restrict__ jobs) {
     const E1Job &J = jobs[blockIdx.y];
@@ -519,9 +578,20 @@ __global__ void __launch_bounds__(64) k_bias_fixup(const E1Job *__restrict__ job
     const uint32_t c_start = table[size_t(key) * nseg];
     const uint32_t c_end = key + 1 < M::kKeys ? table[size_t(key + 1) * nseg] : J.n;
     const uint32_t first = blk_base[key], count = blk_base[key + 1] - first;
+    const auto blk_cand = gptr(J.b.blk_cand); const auto blk_tab = gptr(J.b.blk_tab);
     int v = gptr(J.b.ctx_state)[key];
+    uint32_t serial = 0;
     for (uint32_t b = 0; b < count; b++) {
         if (blk_ok[first + b]) { v = blk_end[first + b]; continue; }
+        const int tab = J.long_min >= 0 ? blk_cand[2 * size_t(first + b) + 1] : -1;
+        if (tab >= 0) {
+            const int va = blk_cand[2 * size_t(first + b)];
+            blk_cand[2 * size_t(first + b)] = v;
+            v = blk_tab[size_t(tab) * kBiasCands + size_t(iclip(v - va, 0, kBiasCands - 1))];
+            blk_end[first + b] = v;
+            continue;
+        }
+        serial++;
         const uint32_t lo = c_start + b * kBiasBlock, hi = min(c_end, lo + kBiasBlock);
         for (uint32_t r = lo; r < hi; r++) {
             s2out[r] = uint16_t(v >> M::kOutShift);
@@ -530,6 +600,33 @@ __global__ void __launch_bounds__(64) k_bias_fixup(const E1Job *__restrict__ job
         blk_end[first + b] = v;
     }
     gptr(J.b.ctx_state)[key] = v;
+    if (serial) atomicAdd(J.b.totals + kLongS2Serial, serial);
+}
+
+// one lane per table: the block's outputs from its exact start state
+template <class M>
+__global__ void __launch_bounds__(64) k_bias_replay(const E1Job *__restrict__ jobs) {
+    __shared__ u32x2 stage[64 * kRowWords];
+    const E1Job &J = jobs[blockIdx.y];
+    const uint32_t n_tabs = min(gptr(J.b.totals)[kLongS2Table], bias_table_cap(J));
+    const uint32_t t = blockIdx.x * 64u + threadIdx.x;
+    if (blockIdx.x * 64u >= n_tabs) return;                           // whole wave idle
+    const bool have = t < n_tabs;
+    const auto s2in = gptr(J.b.s2in); const auto s2out = gptr(J.b.s2out); const auto table = gptr(J.b.table);
+    const auto blk_base = gptr(J.b.blk_base);
+    const uint32_t item = have ? gptr(J.b.blk_item)[t] : 0u;
+    const int key = have ? chain_of_block<M>(blk_base, item) : 0;
+    const int nseg = J.pp.nseg;
+    const uint32_t c_start = table[size_t(key) * nseg];
+    const uint32_t c_end = key + 1 < M::kKeys ? table[size_t(key + 1) * nseg] : J.n;
+    const uint32_t b_start = have ? c_start + (item - blk_base[key]) * kBiasBlock : 0u;
+    const uint32_t b_end = have ? min(c_end, b_start + kBiasBlock) : 0u;
+    int v = have ? gptr(J.b.blk_cand)[2 * size_t(item)] : 0;
+    run_lane_streams(s2in, s2out, b_start, b_end, b_start, stage, [&](uint32_t rec, uint32_t) {
+        const uint32_t o = uint32_t(v >> M::kOutShift);
+        v = M::update(v, M::err_of(rec));
+        return o;
+    });
 }
 
 // ---- partition 2: pixels by (px, sign) (512 keys); symbols >= 20 bypass the re-mapper -----
@@ -607,6 +704,7 @@ __global__ void __launch_bounds__(256) k_map_count_pre(const E1Job *__restrict__
     if (seg >= plan.nseg) return;
     // the scan that follows raises this flag for an image with too many touches for 28-bit positions (k_touch_scatter)
     if (seg == 0 && lane_id() == 0) gptr(J.b.totals)[kWideTouchFlag] = (J.dbg & 256) ? 1u : 0u;   // (NBLIC_AMD_DBG & 256: plain 32-bit positions for every image -- tests, A/B runs)
+    if (seg == 0 && lane_id() < 3) { gptr(J.b.totals)[kLongS2Met + lane_id()] = 0u; gptr(J.b.totals)[kLongS3Split + lane_id()] = 0u; }   // no S2 on this path; the re-mapper chains count from zero
     uint32_t *hist = lds[threadIdx.x >> 6];
     lds_fill<512>(hist, 0);
     uint32_t lo = uint32_t(seg) * plan.seg_len, hi = min(n, lo + plan.seg_len);
@@ -691,6 +789,8 @@ __device__ __forceinline__ void perm_set(Perm20 &p, int i, int v) {
 
 constexpr int kPackWords = 13, kPackLanes = 8;     // 64-bit words per lane per group of 64 bins (range_coder.h kGroupWords); lanes of a pack
 constexpr int kMapLanes = 16;
+// a chain of at least E1Job::long_min records is cut into blocks (k_map_plan .. k_map_check below) and empty here
+__device__ __forceinline__ bool map_chain_cut(const E1Job &J, uint32_t len) { return J.long_min >= 0 && len >= uint32_t(max(J.long_min, 1)); }
 __global__ void __launch_bounds__(64) k_mapper_chains(const E1Job *__restrict__ jobs) {
     __shared__ int count[kMapSyms][64];
     __shared__ u32x2 stage[64 * kRowWords];
@@ -709,7 +809,8 @@ __global__ void __launch_bounds__(64) k_mapper_chains(const E1Job *__restrict__ 
         perm_set(rank_of, k, st[k]); perm_set(sym_at, k, st[kMapSyms + k]); count[k][lane] = st[2 * kMapSyms + k];
     }
     const uint32_t start = active ? table[size_t(key) * plan.nseg] : 0u;
-    const uint32_t end = !active ? 0u : (key + 1 < 512 ? table[size_t(key + 1) * plan.nseg] : *total);
+    uint32_t end = !active ? 0u : (key + 1 < 512 ? table[size_t(key + 1) * plan.nseg] : *total);
+    if (map_chain_cut(J, end - start)) end = start;                   // k_map_blocks / k_map_check have it (its table entry is written back as it is)
     run_lane_streams(s3in, s3out, start, end, start, stage, [&](uint32_t y, uint32_t) {
         const int zz = perm_get(rank_of, int(y));
         const int up = zz > 0 ? zz - 1 : 0;
@@ -727,6 +828,200 @@ __global__ void __launch_bounds__(64) k_mapper_chains(const E1Job *__restrict__ 
         for (int k = 0; k < kMapSyms; k++) {
             st[k] = perm_get(rank_of, k); st[kMapSyms + k] = perm_get(sym_at, k); st[2 * kMapSyms + k] = count[k][lane];
         }
+}
+
+// ---- S3 for a chain that holds most of an image: cut into blocks ---------------------------------------------------
+// The hit counts never decay and belong to symbols, so the counts BY SYMBOL at any record are the chain's start counts
+// plus a histogram prefix -- exact and parallel.  What is not known at a block's first record is the permutation.  So a
+// chain of at least E1Job::long_min records is left out of k_mapper_chains (which sees it as empty) and cut into blocks
+// of long_block records:
+//   k_map_plan    blocks per chain -> mblk_base
+//   k_map_hist    a wave per block: its histogram of the 20 symbols
+//   k_map_prefix  a wave per chain: counts by symbol at every block's first record, and behind the chain
+//   k_map_blocks  a LANE per block: guesses the permutation one block EARLIER -- symbols by descending count, ties in the
+//                 order the chain started with (exact for symbols not yet touched) -- refines it over that block's
+//                 records, notes what it holds at its own first record and replays its block from there: s3out, the
+//                 end permutation.  Blocks 0 and 1 start from the chain's table: exact.
+//   k_map_check   a lane per chain, in order: block b stands if what it started with is block b - 1's true end
+//                 permutation; otherwise it is replayed here from the true state.  Publishes the chain's end.
+// Nothing depends on the guess being right but the time: a tie between symbols that have been hit is decided by which
+// of them got there first, which the counts do not say.
+__device__ __forceinline__ uint32_t map_block_records(const E1Job &J) { return uint32_t(max(J.long_block, kLongBlockMin)); }
+__device__ __forceinline__ void map_chain_range(const E1Job &J, int key, uint32_t &start, uint32_t &end) {
+    const auto table = gptr(J.b.table);
+    start = table[size_t(key) * J.pp.nseg];
+    end = key + 1 < 512 ? table[size_t(key + 1) * J.pp.nseg] : gptr(J.b.totals)[1];
+}
+__device__ __forceinline__ int map_chain_of_block(NB_GLOBAL const uint32_t *base, uint32_t item) {
+    int lo = 0, hi = 512;                                             // invariant: base[lo] <= item < base[hi]
+    while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (base[mid] <= item) lo = mid; else hi = mid; }
+    return lo;
+}
+
+__global__ void __launch_bounds__(512) k_map_plan(const E1Job *__restrict__ jobs) {
+    __shared__ uint32_t part[8];
+    const E1Job &J = jobs[blockIdx.y];
+    const int key = int(threadIdx.x);
+    uint32_t start, end;
+    map_chain_range(J, key, start, end);
+    const uint32_t B = map_block_records(J);
+    const uint32_t nb = map_chain_cut(J, end - start) ? (end - start + B - 1) / B : 0u;
+    const uint32_t incl = wave_scan_incl(nb);
+    if (lane_id() == 63) part[threadIdx.x >> 6] = incl;
+    __syncthreads();
+    uint32_t pre = incl - nb;
+    for (int wv = 0; wv < int(threadIdx.x >> 6); wv++) pre += part[wv];
+    gptr(J.b.mblk_base)[key] = pre;
+    if (key == 511) gptr(J.b.mblk_base)[512] = pre + nb;
+    const uint64_t cut = __ballot(nb != 0u);
+    if (lane_id() == 0 && cut) atomicAdd(J.b.totals + kLongS3Split, uint32_t(__popcll(cut)));
+}
+
+__global__ void __launch_bounds__(64) k_map_hist(const E1Job *__restrict__ jobs) {
+    const E1Job &J = jobs[blockIdx.y];
+    const auto base = gptr(J.b.mblk_base); const auto s3in = gptr(J.b.s3in);
+    const uint32_t item = blockIdx.x;
+    if (item >= base[512]) return;
+    const int key = map_chain_of_block(base, item);
+    uint32_t c_start, c_end;
+    map_chain_range(J, key, c_start, c_end);
+    const uint32_t B = map_block_records(J);
+    const uint32_t b_start = c_start + (item - base[key]) * B, b_end = min(c_end, b_start + B);
+    const int lane = lane_id();
+    uint32_t mine = 0;                                                // lane s counts symbol s
+    for (uint32_t r = b_start; r < b_end; r += 64u) {
+        const uint32_t y = r + uint32_t(lane) < b_end ? uint32_t(s3in[r + uint32_t(lane)]) : 0xFFFFu;
+#pragma unroll
+        for (int s = 0; s < kMapSyms; s++) {
+            const uint64_t m = __ballot(y == uint32_t(s));
+            if (lane == s) mine += uint32_t(__popcll(m));
+        }
+    }
+    if (lane < kMapSyms) gptr(J.b.mblk_cnt)[size_t(item) * kMapSyms + lane] = mine;
+}
+
+__global__ void __launch_bounds__(64) k_map_prefix(const E1Job *__restrict__ jobs) {
+    const E1Job &J = jobs[blockIdx.y];
+    const auto base = gptr(J.b.mblk_base); const auto cnt = gptr(J.b.mblk_cnt);
+    const int key = int(blockIdx.x), s = lane_id();
+    const uint32_t first = base[key], nb = base[key + 1] - first;
+    if (nb == 0u || s >= kMapSyms) return;
+    const auto st = gptr(J.b.map_state) + size_t(key) * (3 * kMapSyms);
+    uint32_t acc = uint32_t(st[2 * kMapSyms + st[s]]);                // the table keeps hits by rank
+    for (uint32_t b = 0; b < nb; b++) {
+        const size_t at = size_t(first + b) * kMapSyms + s;
+        const uint32_t h = cnt[at];
+        cnt[at] = acc; acc += h;
+    }
+    gptr(J.b.mend_cnt)[key * kMapSyms + s] = acc;
+}
+
+// one step of a re-mapper chain (NBLIC.c:470-523): the rank of symbol y, then its hit; count[rank][lane] in LDS
+__device__ __forceinline__ int mapper_step(Perm20 &rank_of, Perm20 &sym_at, int (*count)[64], int lane, int y) {
+    const int zz = perm_get(rank_of, y);
+    const int up = zz > 0 ? zz - 1 : 0;
+    const int c = count[zz][lane] + 1, c_up = count[up][lane];
+    count[zz][lane] = c;
+    if (zz > 0 && c_up < c) {
+        const int other = perm_get(sym_at, up);
+        count[zz][lane] = c_up;  count[up][lane] = c;
+        perm_set(sym_at, zz, other); perm_set(sym_at, up, y);
+        perm_set(rank_of, y, up); perm_set(rank_of, other, zz);
+    }
+    return zz;
+}
+
+__global__ void __launch_bounds__(64) k_map_blocks(const E1Job *__restrict__ jobs) {
+    __shared__ int count[kMapSyms][64];
+    __shared__ u32x2 stage[64 * kRowWords];
+    const E1Job &J = jobs[blockIdx.y];
+    const auto base = gptr(J.b.mblk_base); const auto s3in = gptr(J.b.s3in); const auto s3out = gptr(J.b.s3out);
+    const uint32_t n_items = base[512];
+    if (blockIdx.x * uint32_t(kMapLanes) >= n_items) return;         // whole wave idle
+    const int lane = int(threadIdx.x);
+    const uint32_t item = blockIdx.x * uint32_t(kMapLanes) + uint32_t(lane);
+    const bool active = lane < kMapLanes && item < n_items;           // kMapLanes blocks per wave: see k_mapper_chains
+    const int key = active ? map_chain_of_block(base, item) : 0;
+    uint32_t c_start, c_end;
+    map_chain_range(J, key, c_start, c_end);
+    const uint32_t B = map_block_records(J);
+    const uint32_t blk = active ? item - base[key] : 0u;
+    const uint32_t b_start = active ? c_start + blk * B : 0u, b_end = active ? min(c_end, b_start + B) : 0u;
+    const uint32_t w_start = blk == 0u ? b_start : b_start - B;      // the guess is made a block early
+    const uint32_t w_item = blk == 0u ? item : item - 1u;
+    const auto st = gptr(J.b.map_state) + size_t(key) * (3 * kMapSyms);
+    Perm20 rank_of{0, 0}, sym_at{0, 0};
+    {
+        uint32_t cs[kMapSyms]; int r0[kMapSyms];
+#pragma unroll
+        for (int s = 0; s < kMapSyms; s++) { cs[s] = active ? gptr(J.b.mblk_cnt)[size_t(w_item) * kMapSyms + s] : 0u; r0[s] = st[s]; }
+#pragma unroll
+        for (int s = 0; s < kMapSyms; s++) {
+            int r = 0;
+            if (blk <= 1u) r = r0[s];                                 // the chain's own table
+            else {
+#pragma unroll
+                for (int t = 0; t < kMapSyms; t++) r += int(cs[t] > cs[s] || (cs[t] == cs[s] && r0[t] < r0[s]));
+            }
+            perm_set(rank_of, s, r); perm_set(sym_at, r, s);
+            count[r][lane] = int(cs[s]);
+        }
+    }
+    Perm20 held = rank_of;                                            // what the lane holds at its block's first record
+    run_lane_streams(s3in, s3out, w_start, b_end, b_start, stage, [&](uint32_t y, uint32_t idx) {
+        if (idx == b_start) held = rank_of;
+        return uint32_t(mapper_step(rank_of, sym_at, count, lane, int(y)));
+    });
+    if (active) {
+        const auto perm = gptr(J.b.mblk_perm) + size_t(item) * 4;
+        perm[0] = held.lo; perm[1] = held.hi; perm[2] = rank_of.lo; perm[3] = rank_of.hi;
+    }
+}
+
+__global__ void __launch_bounds__(64) k_map_check(const E1Job *__restrict__ jobs) {
+    __shared__ int count[kMapSyms][64];
+    const E1Job &J = jobs[blockIdx.y];
+    const auto base = gptr(J.b.mblk_base); const auto s3in = gptr(J.b.s3in); const auto s3out = gptr(J.b.s3out);
+    const auto perm = gptr(J.b.mblk_perm); const auto cnt = gptr(J.b.mblk_cnt);
+    const int lane = int(threadIdx.x);
+    const int key = int(blockIdx.x) * kMapLanes + (lane < kMapLanes ? lane : 0);
+    const uint32_t first = base[key], nb = lane < kMapLanes ? base[key + 1] - first : 0u;
+    if (nb == 0u) return;
+    uint32_t c_start, c_end;
+    map_chain_range(J, key, c_start, c_end);
+    const uint32_t B = map_block_records(J);
+    Perm20 rank_of{perm[size_t(first) * 4 + 2], perm[size_t(first) * 4 + 3]};          // block 0 started from the table: its end is true
+    uint32_t accepted = 0, missed = 0;
+    for (uint32_t b = 1; b < nb; b++) {
+        const size_t it = size_t(first + b);
+        if (perm[it * 4] == rank_of.lo && perm[it * 4 + 1] == rank_of.hi) {
+            accepted++;
+            rank_of = Perm20{perm[it * 4 + 2], perm[it * 4 + 3]};
+            continue;
+        }
+        missed++;
+        Perm20 sym_at{0, 0};
+        for (int s = 0; s < kMapSyms; s++) {
+            const int r = perm_get(rank_of, s);
+            perm_set(sym_at, r, s); count[r][lane] = int(cnt[it * kMapSyms + s]);
+        }
+        const uint32_t lo = c_start + b * B, hi = min(c_end, lo + B);
+        for (uint32_t r = lo; r < hi; r += 8u) {                      // eight loads ahead of the eight dependent steps
+            uint32_t y[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) y[k] = s3in[min(r + uint32_t(k), hi - 1u)];
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                if (r + uint32_t(k) < hi) s3out[r + uint32_t(k)] = uint16_t(mapper_step(rank_of, sym_at, count, lane, int(y[k])));
+        }
+    }
+    const auto st = gptr(J.b.map_state) + size_t(key) * (3 * kMapSyms);
+    for (int s = 0; s < kMapSyms; s++) {
+        const int r = perm_get(rank_of, s);
+        st[s] = r; st[kMapSyms + r] = s; st[2 * kMapSyms + r] = int(gptr(J.b.mend_cnt)[key * kMapSyms + s]);
+    }
+    if (accepted) atomicAdd(J.b.totals + kLongS3Accepted, accepted);
+    if (missed) atomicAdd(J.b.totals + kLongS3Missed, missed);
 }
 
 // ---- S4: binarisation (NBLIC.c:640-679); path depends on (qu,qv,qw,z) only ----------------
@@ -1557,10 +1852,25 @@ SegPlan make_plan(uint32_t n_items, uint32_t max_segments) {
     return p;
 }
 
+// S3: the chains short enough for one lane each, then those that are cut into blocks (6 launches; 1 with long chains off)
+static void launch_mapper_chains(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, uint32_t max_n, hipStream_t s) {
+    hipLaunchKernelGGL(k_mapper_chains, dim3(512 / kMapLanes, n_jobs), dim3(64), 0, s, d_jobs);
+    if (h_jobs[0].long_min < 0) return;
+    const unsigned B = unsigned(h_jobs[0].long_block > kLongBlockMin ? h_jobs[0].long_block : kLongBlockMin);
+    const unsigned most = max_n / unsigned(h_jobs[0].long_min > 1 ? h_jobs[0].long_min : 1) + 1u;      // cut chains of a job, at most
+    const unsigned max_blocks = max_n / B + (most < 512u ? most : 512u);                               // one partial block per chain
+    hipLaunchKernelGGL(k_map_plan, dim3(1, n_jobs), dim3(512), 0, s, d_jobs);
+    hipLaunchKernelGGL(k_map_hist, dim3(max_blocks, n_jobs), dim3(64), 0, s, d_jobs);
+    hipLaunchKernelGGL(k_map_prefix, dim3(512, n_jobs), dim3(64), 0, s, d_jobs);
+    hipLaunchKernelGGL(k_map_blocks, dim3(cdiv(max_blocks, kMapLanes), n_jobs), dim3(64), 0, s, d_jobs);
+    hipLaunchKernelGGL(k_map_check, dim3(512 / kMapLanes, n_jobs), dim3(64), 0, s, d_jobs);
+}
+
 // The front half behind S1, from the S1 records in b.rec1: partition by context, the context chains, partition by
 // re-mapper, the re-mapper chains, the bin counts and their scan.  19 launches.  `model_done`, if given, is recorded
 // behind k_bias_fixup.
-static void front_behind_s1(const E1Job *d_jobs, int n_jobs, int max_nseg, uint32_t max_n, hipStream_t s, Marker &mark, hipEvent_t model_done) {
+static void front_behind_s1(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, int max_nseg, uint32_t max_n, hipStream_t s, Marker &mark, hipEvent_t model_done) {
+    const bool long_chains = h_jobs[0].long_min >= 0;
     const dim3 seg_grid(pad8(cdiv(max_nseg, 4)), n_jobs), px_grid(pad8(cdiv(max_n, 256)), n_jobs);
     mark(); hipLaunchKernelGGL(k_adr_count<NbModel>, seg_grid, dim3(256), 0, s, d_jobs);
     scan_exclusive<0>(d_jobs, n_jobs, uint32_t(kContexts) * max_nseg, s, mark);
@@ -1568,12 +1878,16 @@ static void front_behind_s1(const E1Job *d_jobs, int n_jobs, int max_nseg, uint3
     mark(); hipLaunchKernelGGL(k_plan_blocks<NbModel>, dim3(1, n_jobs), dim3(1024), 0, s, d_jobs);
     const unsigned max_blocks = max_n / kBiasBlock + unsigned(kContexts);
     mark(); hipLaunchKernelGGL(k_bias_blocks<NbModel>, dim3(cdiv(max_blocks, 64), n_jobs), dim3(64), 0, s, d_jobs);
-    mark(); hipLaunchKernelGGL(k_bias_fixup<NbModel>, dim3(kContexts / 64, n_jobs), dim3(64), 0, s, d_jobs);
+    mark();                                                     // one timed stage "k_bias_fixup": tables, the walk, the replay
+    const unsigned max_tabs = max_n / kBiasBlock + 1u;
+    if (long_chains) hipLaunchKernelGGL(k_bias_tabulate<NbModel>, dim3(max_tabs, n_jobs), dim3(kBiasCands), 0, s, d_jobs);
+    hipLaunchKernelGGL(k_bias_fixup<NbModel>, dim3(kContexts / 64, n_jobs), dim3(64), 0, s, d_jobs);
+    if (long_chains) hipLaunchKernelGGL(k_bias_replay<NbModel>, dim3(cdiv(max_tabs, 64), n_jobs), dim3(64), 0, s, d_jobs);
     if (model_done) hipEventRecord(model_done, s);
     mark(); hipLaunchKernelGGL(k_map_count, seg_grid, dim3(256), 0, s, d_jobs);
     scan_exclusive<1>(d_jobs, n_jobs, 512u * max_nseg, s, mark);
     mark(); hipLaunchKernelGGL(k_map_scatter<false>, seg_grid, dim3(256), 0, s, d_jobs);
-    mark(); hipLaunchKernelGGL(k_mapper_chains, dim3(512 / kMapLanes, n_jobs), dim3(64), 0, s, d_jobs);
+    mark(); launch_mapper_chains(d_jobs, h_jobs, n_jobs, max_n, s);       // one timed stage "k_mapper_chains": the cut chains' kernels too
     mark(); hipLaunchKernelGGL(k_count_bins<false>, px_grid, dim3(256), 0, s, d_jobs);
     scan_exclusive<2>(d_jobs, n_jobs, max_n, s, mark);
     mark();                                                     // start of the host gap (index 20)
@@ -1608,7 +1922,7 @@ static void launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, h
         hipLaunchKernelGGL(k_predict_border<false>, dim3(cdiv(max_w, 64), max_h < 2 ? max_h : 2, n_jobs), dim3(64), 0, s, d_jobs, 1);
         if (max_h > 2) hipLaunchKernelGGL(k_predict_border<false>, dim3(1, max_h - 2, n_jobs), dim3(64), 0, s, d_jobs, 0);
     }
-    front_behind_s1(d_jobs, n_jobs, max_nseg, max_n, s, mark, BAND ? model_done : nullptr);
+    front_behind_s1(d_jobs, h_jobs, n_jobs, max_nseg, max_n, s, mark, BAND ? model_done : nullptr);
 }
 
 void e1_launch_front(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s, E1Timers *tm) {
@@ -1625,7 +1939,7 @@ void e1_launch_model_stages(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs
         max_n = h_jobs[k].n > max_n ? h_jobs[k].n : max_n; max_nseg = h_jobs[k].pp.nseg > max_nseg ? h_jobs[k].pp.nseg : max_nseg;
     }
     Marker mark{nullptr, s, 0};
-    front_behind_s1(d_jobs, n_jobs, max_nseg, max_n, s, mark, nullptr);
+    front_behind_s1(d_jobs, h_jobs, n_jobs, max_nseg, max_n, s, mark, nullptr);
 }
 
 // Front half of the serial modes: rec1 and px | sign per pixel come from the serial model stage
@@ -1641,7 +1955,7 @@ void e1_launch_front_pre(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, h
     hipLaunchKernelGGL(k_map_count_pre, seg_grid, dim3(256), 0, s, d_jobs);
     scan_exclusive<1>(d_jobs, n_jobs, 512u * max_nseg, s, mark);
     hipLaunchKernelGGL(k_map_scatter<true>, seg_grid, dim3(256), 0, s, d_jobs);
-    hipLaunchKernelGGL(k_mapper_chains, dim3(512 / kMapLanes, n_jobs), dim3(64), 0, s, d_jobs);
+    launch_mapper_chains(d_jobs, h_jobs, n_jobs, max_n, s);
     hipLaunchKernelGGL(k_count_bins<true>, px_grid, dim3(256), 0, s, d_jobs);
     scan_exclusive<2>(d_jobs, n_jobs, max_n, s, mark);
 }
@@ -1699,7 +2013,7 @@ void e1_launch_back_stages(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs,
 
 // QNBLIC's model stage behind k_q_predict, from px0 | adr << 8 in b.rec1: partition by context, the context chains, the
 // symbols and their histograms.  9 launches.
-static void q_behind_predict(const E1Job *d_jobs, int n_jobs, int max_nseg, uint32_t max_n, hipStream_t s) {
+static void q_behind_predict(const E1Job *d_jobs, int n_jobs, int max_nseg, uint32_t max_n, bool long_chains, hipStream_t s) {
     const dim3 seg_grid(pad8(cdiv(max_nseg, 4)), n_jobs);
     Marker mark{nullptr, s, 0};
     hipLaunchKernelGGL(k_adr_count<QModel>, seg_grid, dim3(256), 0, s, d_jobs);
@@ -1708,7 +2022,10 @@ static void q_behind_predict(const E1Job *d_jobs, int n_jobs, int max_nseg, uint
     hipLaunchKernelGGL(k_plan_blocks<QModel>, dim3(1, n_jobs), dim3(1024), 0, s, d_jobs);
     const unsigned max_blocks = max_n / kBiasBlock + 3072u;
     hipLaunchKernelGGL(k_bias_blocks<QModel>, dim3(cdiv(max_blocks, 64), n_jobs), dim3(64), 0, s, d_jobs);
+    const unsigned max_tabs = max_n / kBiasBlock + 1u;
+    if (long_chains) hipLaunchKernelGGL(k_bias_tabulate<QModel>, dim3(max_tabs, n_jobs), dim3(kBiasCands), 0, s, d_jobs);
     hipLaunchKernelGGL(k_bias_fixup<QModel>, dim3(3072 / 64, n_jobs), dim3(64), 0, s, d_jobs);
+    if (long_chains) hipLaunchKernelGGL(k_bias_replay<QModel>, dim3(cdiv(max_tabs, 64), n_jobs), dim3(64), 0, s, d_jobs);
     unsigned sym_blocks = cdiv(max_n, 256 * 16);                      // 16 pixels per thread: fewer global histogram merges
     hipLaunchKernelGGL(k_q_symbols, dim3(pad8(sym_blocks ? sym_blocks : 1), n_jobs), dim3(256), 0, s, d_jobs);
 }
@@ -1721,7 +2038,7 @@ void q_launch_model(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStr
     }
     hipLaunchKernelGGL(k_init_state, dim3(16, n_jobs), dim3(256), 0, s, d_jobs);
     hipLaunchKernelGGL(k_q_predict, dim3(cdiv(max_w, 256), max_h, n_jobs), dim3(256), 0, s, d_jobs);
-    q_behind_predict(d_jobs, n_jobs, max_nseg, max_n, s);
+    q_behind_predict(d_jobs, n_jobs, max_nseg, max_n, h_jobs[0].long_min >= 0, s);
 }
 
 void q_launch_model_stages(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s) {
@@ -1729,7 +2046,7 @@ void q_launch_model_stages(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs,
     for (int k = 0; k < n_jobs; k++) {
         max_n = h_jobs[k].n > max_n ? h_jobs[k].n : max_n; max_nseg = h_jobs[k].pp.nseg > max_nseg ? h_jobs[k].pp.nseg : max_nseg;
     }
-    q_behind_predict(d_jobs, n_jobs, max_nseg, max_n, s);
+    q_behind_predict(d_jobs, n_jobs, max_nseg, max_n, h_jobs[0].long_min >= 0, s);
 }
 
 }  // namespace nblic

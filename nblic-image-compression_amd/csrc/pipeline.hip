@@ -275,6 +275,8 @@ struct nblic_amd_ctx {
     double idx_split[5] = {0}; long idx_steps = 0;   // the last indexed batch, summed over its group steps: front, totals read-back, back half + entry records, copies (GPU ms); coder wait (host ms).  Guarded by stat_m
     double idxbuild_split[4] = {0};       // the last batch index build: host checks, uploads and seeding, the decode-and-capture launches, the finish (host ms).  Guarded by stat_m
     double idxdec_split[4] = {0};         // the last indexed batch decode: host checks, uploads, rounds and chain check, copy-out (host ms).  Guarded by stat_m
+    int long_min = 0, long_block = 0;     // nblic_amd_set_long_chains as given (0: the default); what a job record carries is long_chains_of()
+    long long_counts[8] = {0};            // nblic_amd_long_chain_stats: summed from the totals records the front halves leave.  Guarded by stat_m
     long serial_launch_count = 0;         // launches of the serial model / decode kernels since the context was created (reporting, tests)
     size_t feed_chunk = size_t(1) << 20;  // bytes per step in which the drop-in decoders fetch a stream of unknown length (nblic_amd_set_feed_chunk)
     long fed_bytes = 0;                   // bytes the last drop-in decode read from the caller's stream
@@ -347,15 +349,15 @@ static bool group_init(Group &g, int id, int n_slots, nblic_amd_ctx *c) {
     for (int k = 0; k < kE1Marks; k++) { HIP_OK(g.tm_ev[k].create(hipEventDefault)); g.tm.ev[k] = g.tm_ev[k]; }
     HIP_OK(g.h_jobs.alloc(size_t(n_slots))); HIP_OK(g.d_jobs.alloc(size_t(n_slots)));
     HIP_OK(g.h_sjobs.alloc(size_t(n_slots))); HIP_OK(g.d_sjobs.alloc(size_t(n_slots)));
-    HIP_OK(g.h_totals.alloc(size_t(n_slots) * kTotalsStride)); HIP_OK(g.d_totals.alloc(size_t(n_slots) * kTotalsStride));
+    HIP_OK(g.h_totals.alloc(size_t(n_slots) * kTotalsSlot)); HIP_OK(g.d_totals.alloc(size_t(n_slots) * kTotalsSlot));
     for (int k = 0; k < n_slots; k++) {
         Slot &s = g.slots[size_t(k)];
         DevPool &m = s.mem;
         HIP_OK(m.renew(s.b.table, size_t(4096) * kMaxSegments)); HIP_OK(m.renew(s.b.scan_sums, (size_t(1) << 20) / sizeof(uint32_t)));
-        s.b.totals = g.d_totals + size_t(k) * kTotalsStride;
+        s.b.totals = g.d_totals + size_t(k) * kTotalsSlot;
         HIP_OK(m.renew(s.b.ctx_state, 4096));                                        // 2048 (NBLIC) or 3072 (QNBLIC) contexts
         HIP_OK(m.renew(s.b.qhist, 12 * 256)); HIP_OK(m.renew(s.b.map_state, 512 * 60)); HIP_OK(m.renew(s.b.cnt_state, 4096 * 2));
-        HIP_OK(m.renew(s.b.win_base, 4097 + 4096)); HIP_OK(m.renew(s.b.blk_base, 4097)); HIP_OK(m.renew(s.b.dbg_out, 4096));
+        HIP_OK(m.renew(s.b.win_base, 4097 + 4096)); HIP_OK(m.renew(s.b.blk_base, 4097)); HIP_OK(m.renew(s.b.mblk_base, 513)); HIP_OK(m.renew(s.b.mend_cnt, 512 * 20)); HIP_OK(m.renew(s.b.dbg_out, 4096));
         HIP_OK(hipMemset(s.b.dbg_out, 0, 4096 * sizeof(unsigned long long)));
         uint8_t *state = nullptr;
         HIP_OK(m.renew(state, kModelStateBytes));
@@ -384,6 +386,8 @@ static bool ensure_pixels(Slot &s, size_t n, bool with_events = true) {
         HIP_OK(m.renew(s.b.pxs, n)); HIP_OK(m.renew(s.b.s3in, n + kStreamPad)); HIP_OK(m.renew(s.b.pos3, n)); HIP_OK(m.renew(s.b.s3out, n + kStreamPad));
         HIP_OK(m.renew(s.b.z, n)); HIP_OK(m.renew(s.b.cnt, n)); HIP_OK(m.renew(s.b.ev_off, n));
         HIP_OK(m.renew(s.b.blk_end, n / 4096 + 4096 + 64)); HIP_OK(m.renew(s.b.blk_ok, n / 4096 + 4096 + 64));
+        HIP_OK(m.renew(s.b.blk_cand, 2 * (n / 4096 + 4096 + 64))); HIP_OK(m.renew(s.b.blk_item, n / 4096 + 64)); HIP_OK(m.renew(s.b.blk_tab, 128 * (n / 4096 + 64)));
+        HIP_OK(m.renew(s.b.mblk_cnt, 20 * (n / kLongBlockMin + 512))); HIP_OK(m.renew(s.b.mblk_perm, 4 * (n / kLongBlockMin + 512)));
         s.px_cap = n;
     }
     return with_events ? ensure_events(s, 5 * n) : true;   // typical images need 4.3-4.5 bins/px (ensure_events adds 1/8); grown on demand
@@ -400,9 +404,24 @@ static void e1_job_back(E1Job &J, const E1Buffers &b, uint32_t n_ev, uint64_t *p
 // The job of `rows` x w pixels in workspace b as a front half sees it: no bins yet (their count is its result).
 // near is 0 for the staged -e1 and the QNBLIC kernels, which use the lossless constants whatever the record says;
 // dbg is NBLIC_AMD_DBG for the staged -e1 kernels and 0 for everything else.
-static E1Job e1_job_front(const E1Buffers &b, int rows, int w, int near, int dbg) {
+// Long chains: what nblic_amd_set_long_chains left in the context, as a job record carries it.
+constexpr int kLongMinDefault = 65536, kLongBlockDefault = 4096;
+struct LongChains { int min_records, block_records; };
+static LongChains long_chains_of(const nblic_amd_ctx *c) {
+    if (c->long_min < 0) return LongChains{-1, 0};
+    return LongChains{c->long_min ? c->long_min : kLongMinDefault, std::max(c->long_block ? c->long_block : kLongBlockDefault, kLongBlockMin)};
+}
+// the block counts of one image's front half, from its totals record
+static void count_long_chains(nblic_amd_ctx *c, const uint32_t *totals) {
+    std::lock_guard<std::mutex> l(c->stat_m);
+    c->long_counts[0] += totals[kLongS2Met]; c->long_counts[1] += totals[kLongS2Table]; c->long_counts[2] += totals[kLongS2Serial];
+    c->long_counts[3] += totals[kLongS3Split]; c->long_counts[4] += totals[kLongS3Accepted]; c->long_counts[5] += totals[kLongS3Missed];
+}
+
+static E1Job e1_job_front(const E1Buffers &b, int rows, int w, int near, int dbg, LongChains lc) {
     E1Job J{};
     J.h = rows; J.w = w; J.n = uint32_t(size_t(rows) * size_t(w)); J.pp = make_plan(J.n); J.dbg = dbg;
+    J.long_min = lc.min_records; J.long_block = lc.block_records;
     J.near = near; J.k_step = k_step_for_near(near); J.ktab = level_shift_table(J.k_step);
     e1_job_back(J, b, 0);
     return J;
@@ -433,7 +452,7 @@ static bool slot_begin(Group &g, int k, const uint8_t *const *imgs, bool on_devi
         s.b.img = s.d_img;
     }
     s.n_ev = 0; s.pack_n = 1; s.pack_lane = 0;                     // (a pack is made in launch_back, for that launch only)
-    g.h_jobs[k] = e1_job_front(s.b, s.h, s.w, s.near, dbg);
+    g.h_jobs[k] = e1_job_front(s.b, s.h, s.w, s.near, dbg, long_chains_of(g.ctx));
     return true;
 }
 
@@ -444,7 +463,7 @@ static bool launch_front(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs,
     HIP_OK(hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(g.n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, g.stream));
     g.tm.mask = c->timing_mask;
     e1_launch_front(g.d_jobs, g.h_jobs, g.n_jobs, g.stream, c->timing ? &g.tm : nullptr);
-    HIP_OK(hipMemcpyAsync(g.h_totals, g.d_totals, size_t(g.n_jobs) * kTotalsStride * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
+    HIP_OK(hipMemcpyAsync(g.h_totals, g.d_totals, size_t(g.n_jobs) * kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
     return true;
 }
 
@@ -492,7 +511,7 @@ static bool launch_front_serial(nblic_amd_ctx *c, Group &g, const uint8_t *const
         else if (on_device) HIP_OK(hipMemcpyAsync(dst, imgs[s.job], n, hipMemcpyDeviceToHost, g.stream));
     }
     e1_launch_front_pre(g.d_jobs, g.h_jobs, g.n_jobs, g.stream);
-    HIP_OK(hipMemcpyAsync(g.h_totals, g.d_totals, size_t(g.n_jobs) * kTotalsStride * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
+    HIP_OK(hipMemcpyAsync(g.h_totals, g.d_totals, size_t(g.n_jobs) * kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
     return true;
 }
 
@@ -898,6 +917,7 @@ static void on_group_done(void *vp) {
     Group *gp = static_cast<Group *>(vp);
     nblic_amd_ctx *c = gp->ctx;
     if (c->trace) fprintf(stderr, "[trace] %.3f group %d done (%d images)\n", c->now(), gp->id, gp->n_jobs);
+    if (gp->kind == 1) for (int k = 0; k < gp->n_jobs; k++) count_long_chains(c, gp->h_totals + size_t(k) * kTotalsSlot);   // (NBLIC: launch_back has)
     {
         std::lock_guard<std::mutex> l(c->rm);
         for (int k = 0; k < gp->n_jobs; k++) {
@@ -932,7 +952,8 @@ static bool launch_back(nblic_amd_ctx *c, Group &g, bool with_coders, bool gener
     { std::lock_guard<std::mutex> l(c->stat_m); c->driver_wait_cpu_s += thread_cpu_s() - w0; }
     for (int k = 0; k < g.n_jobs; k++) {
         Slot &s = g.slots[size_t(k)];
-        s.n_ev = g.h_totals[size_t(k) * kTotalsStride + 2];
+        s.n_ev = g.h_totals[size_t(k) * kTotalsSlot + 2];
+        count_long_chains(c, g.h_totals + size_t(k) * kTotalsSlot);
         s.pack_n = 1; s.pack_lane = 0;
         if (s.n_ev >= 0x7FFFFFFFu) { fprintf(stderr, "[nblic_amd] event count overflow\n"); return false; }
         if (!ensure_events(s, s.n_ev)) return false;
@@ -1170,6 +1191,8 @@ static bool launch_q(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, boo
         HIP_OK(hipMemcpyAsync(dst, s.b.pxs, n * sizeof(uint16_t), hipMemcpyDeviceToDevice, g.stream));
         HIP_OK(hipMemcpyAsync(dst + n_pad, s.b.qhist, 12 * 256 * sizeof(uint32_t), hipMemcpyDeviceToDevice, g.stream));
     }
+    // the block counts of the context chains (nblic_amd_long_chain_stats); on_group_done adds them up
+    HIP_OK(hipMemcpyAsync(g.h_totals, g.d_totals, size_t(g.n_jobs) * kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
     HIP_OK(hipLaunchHostFunc(g.stream, on_group_done, &g));
     return true;
 }
@@ -1645,7 +1668,7 @@ static E1Buffers stream_band_buffers(const nblic_amd_stream *s, const Slot &sl, 
 // the front-half job records of the band that starts at row i0
 static void stream_band_jobs(nblic_amd_stream *s, Group &g, int i0, int rows) {
     const Slot &sl = g.slots[0];
-    g.h_jobs[0] = e1_job_front(stream_band_buffers(s, sl, i0), rows, s->w, s->near, 0);
+    g.h_jobs[0] = e1_job_front(stream_band_buffers(s, sl, i0), rows, s->w, s->near, 0, long_chains_of(g.ctx));
     g.h_jobs[0].row0 = i0;
     g.h_sjobs[0] = model_job(s->d_img, s->d_recon, sl.b, s->d_stats, sl.d_state, s->h, s->w, s->near, s->effort, rows, i0, g.ctx->d_redo);
 }
@@ -1724,10 +1747,11 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
             hipEventRecord(e1, g.stream);
             e1_launch_front_pre(g.d_jobs, g.h_jobs, 1, g.stream);
         }
-        if (hipMemcpyAsync(g.h_totals, g.d_totals, kTotalsStride * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
+        if (hipMemcpyAsync(g.h_totals, g.d_totals, kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream) != hipSuccess ||
             hipStreamSynchronize(g.stream) != hipSuccess) return fail("front half");
         { float ms = 0.f; if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) s->model_ms += ms; }
         const uint32_t n_ev = g.h_totals[2];
+        count_long_chains(g.ctx, g.h_totals);
         if (n_ev >= 0x7FFFFFFFu || !ensure_events(sl, n_ev)) return fail("bin count");
         if (size_t(n_ev) + 8 > std::min(s->d_coded.capacity(), s->h_coded.capacity())) {
             const size_t cap = size_t(n_ev) + size_t(n_ev) / 4 + 4096;
@@ -2740,7 +2764,7 @@ static void idx_driver(IdxCall &q, std::vector<std::unique_ptr<IdxImage>> &image
                 if (I.every) rows = std::min(rows, I.every - L.row0 % I.every);           // a band never crosses an entry row
                 E1Buffers b = g.slots[size_t(k)].b;
                 b.img = L.plane + size_t(L.row0) * size_t(I.w);
-                g.h_jobs[n_jobs] = e1_job_front(b, rows, I.w, 0, 0);
+                g.h_jobs[n_jobs] = e1_job_front(b, rows, I.w, 0, 0, long_chains_of(c));
                 g.h_jobs[n_jobs].row0 = L.row0;
                 slot_of[size_t(n_jobs++)] = k;
             }
@@ -2754,14 +2778,15 @@ static void idx_driver(IdxCall &q, std::vector<std::unique_ptr<IdxImage>> &image
             e1_launch_front_band(g.d_jobs, g.h_jobs, n_jobs, st);
             hipEventRecord(ev[1], st);
             // ---- 4. totals
-            ok = hipMemcpyAsync(g.h_totals, g.d_totals, size_t(n_slots) * kTotalsStride * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+            ok = hipMemcpyAsync(g.h_totals, g.d_totals, size_t(n_slots) * kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
             hipEventRecord(ev[2], st);
             if (!ok || hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { ok = false; break; }
             // ---- 5. the back half: bins of all jobs side by side in one buffer
             size_t n_bins = 0, rec_bytes = 0, rows_bytes = 0; int n_tasks = 0;
             for (int j = 0; j < n_jobs && ok; j++) {
                 const int k = slot_of[size_t(j)];
-                const uint32_t n_ev = g.h_totals[size_t(k) * kTotalsStride + 2];
+                const uint32_t n_ev = g.h_totals[size_t(k) * kTotalsSlot + 2];
+                count_long_chains(c, g.h_totals + size_t(k) * kTotalsSlot);
                 ok = n_ev < 0x7FFFFFFFu && ensure_events(g.slots[size_t(k)], n_ev);
                 bins_at[size_t(j)] = n_bins;
                 n_bins += (size_t(n_ev) + 64 + 63) & ~size_t(63);
@@ -2785,7 +2810,7 @@ static void idx_driver(IdxCall &q, std::vector<std::unique_ptr<IdxImage>> &image
             for (int j = 0; j < n_jobs; j++) {
                 E1Buffers b = g.slots[size_t(slot_of[size_t(j)])].b;
                 b.img = g.h_jobs[j].b.img; b.coded = d_bins + bins_at[size_t(j)];
-                e1_job_back(g.h_jobs[j], b, g.h_totals[size_t(slot_of[size_t(j)]) * kTotalsStride + 2]);
+                e1_job_back(g.h_jobs[j], b, g.h_totals[size_t(slot_of[size_t(j)]) * kTotalsSlot + 2]);
             }
             ok = hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, st) == hipSuccess &&
                  (!n_tasks || hipMemcpyAsync(d_tasks, h_tasks, size_t(n_tasks) * sizeof(IndexRecordTask), hipMemcpyHostToDevice, st) == hipSuccess);
@@ -3750,7 +3775,7 @@ int nblic_amd_debug_model_stages(nblic_amd_ctx *c, int model, size_t n, const un
         if (!ensure_pixels(s, n, false)) return false;
         HIP_OK(s.d_img.reserve(n));
         s.b.img = s.d_img;
-        grp.h_jobs[0] = e1_job_front(s.b, 1, int(n), 0, q ? 0 : dbg_flags());
+        grp.h_jobs[0] = e1_job_front(s.b, 1, int(n), 0, q ? 0 : dbg_flags(), long_chains_of(c));
         hipStream_t st = grp.stream;
         HIP_OK(hipMemcpyAsync(s.d_img, x, n, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(s.b.rec1, rec1, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -3765,6 +3790,7 @@ int nblic_amd_debug_model_stages(nblic_amd_ctx *c, int model, size_t n, const un
         HIP_OK(hipMemcpyAsync(pxs, s.b.pxs, n * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(blk_base, s.b.blk_base, size_t(keys + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(ctx_state_out, s.b.ctx_state, size_t(keys) * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(grp.h_totals, grp.d_totals, kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         if (q) {
             HIP_OK(hipMemcpyAsync(qhist, s.b.qhist, 12 * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         } else {
@@ -3773,6 +3799,7 @@ int nblic_amd_debug_model_stages(nblic_amd_ctx *c, int model, size_t n, const un
             HIP_OK(hipMemcpyAsync(map_state_out, s.b.map_state, size_t(512) * 60 * sizeof(int), hipMemcpyDeviceToHost, st));
         }
         HIP_OK(hipStreamSynchronize(st));
+        count_long_chains(c, grp.h_totals);
         const size_t blocks = blk_base[keys];
         if (blocks > blk_ok_cap) return false;
         HIP_OK(hipMemcpy(blk_ok, s.b.blk_ok, blocks, hipMemcpyDeviceToHost));
@@ -3802,7 +3829,7 @@ int nblic_amd_debug_back_half(nblic_amd_ctx *c, size_t n_ev, const unsigned int 
         grp.n_jobs = 1; s.job = 0; s.h = 0; s.w = 0; s.near = 0; s.effort = 1; s.n_ev = uint32_t(n_ev);
         if (!ensure_events(s, n_ev)) return false;
         HIP_OK(d_coded.alloc(n_ev));
-        E1Job J = e1_job_front(s.b, 0, 0, 0, dbg_flags());
+        E1Job J = e1_job_front(s.b, 0, 0, 0, dbg_flags(), long_chains_of(c));
         E1Buffers b = s.b;
         b.coded = d_coded;
         e1_job_back(J, b, uint32_t(n_ev));
@@ -3810,7 +3837,7 @@ int nblic_amd_debug_back_half(nblic_amd_ctx *c, size_t n_ev, const unsigned int 
         hipStream_t st = grp.stream;
         HIP_OK(hipMemcpyAsync(s.b.events, events, n_ev * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(grp.d_jobs, grp.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemsetAsync(s.b.totals, 0, kTotalsStride * sizeof(uint32_t), st));
+        HIP_OK(hipMemsetAsync(s.b.totals, 0, kTotalsSlot * sizeof(uint32_t), st));
         if (cnt_state_in) HIP_OK(hipMemcpyAsync(s.b.cnt_state, cnt_state_in, size_t(4096) * 2 * sizeof(int), hipMemcpyHostToDevice, st));
         else e1_launch_init(grp.d_jobs, 1, st);
         e1_launch_back_stages(grp.d_jobs, grp.h_jobs, 1, st);
@@ -3855,22 +3882,23 @@ int nblic_amd_debug_entropy_front(nblic_amd_ctx *c, size_t n, const unsigned cha
         if (!ensure_pixels(s, n, false)) return false;
         HIP_OK(s.d_img.reserve(n));
         s.b.img = s.d_img;
-        grp.h_jobs[0] = e1_job_front(s.b, 1, int(n), near, 0);              // the one place that pairs k_step and ktab with near
+        grp.h_jobs[0] = e1_job_front(s.b, 1, int(n), near, 0, long_chains_of(c));              // the one place that pairs k_step and ktab with near
         hipStream_t st = grp.stream;
         HIP_OK(hipMemcpyAsync(s.d_img, x, n, hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(s.b.rec1, rec1, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(s.b.pxs, pxs, n * sizeof(uint16_t), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(grp.d_jobs, grp.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemsetAsync(s.b.totals, 0, kTotalsStride * sizeof(uint32_t), st));
+        HIP_OK(hipMemsetAsync(s.b.totals, 0, kTotalsSlot * sizeof(uint32_t), st));
         // a table that is not given is k_init_state's; a given one goes in behind it, or instead of it
         if (!map_state_in || !cnt_state_in) e1_launch_init(grp.d_jobs, 1, st);
         if (map_state_in) HIP_OK(hipMemcpyAsync(s.b.map_state, map_state_in, size_t(512) * 60 * sizeof(int), hipMemcpyHostToDevice, st));
         if (cnt_state_in) HIP_OK(hipMemcpyAsync(s.b.cnt_state, cnt_state_in, size_t(4096) * 2 * sizeof(int), hipMemcpyHostToDevice, st));
         e1_launch_front_pre(grp.d_jobs, grp.h_jobs, 1, st);
         HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpyAsync(grp.h_totals, grp.d_totals, kTotalsStride * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(grp.h_totals, grp.d_totals, kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         const uint32_t n_ev = grp.h_totals[2];
+        count_long_chains(c, grp.h_totals);
         totals[2] = n_ev;
         if (size_t(n_ev) > events_cap) { rc = -3; return true; }
         if (n_ev >= 0x7FFFFFFFu || !ensure_events(s, n_ev)) return false;
@@ -4042,6 +4070,17 @@ void nblic_amd_set_max_pixels(nblic_amd_ctx *c, long max_pixels) {
 void nblic_amd_set_serial_rows(nblic_amd_ctx *c, int rows) {
     if (!c) c = default_ctx();
     if (c) { std::lock_guard<std::mutex> g(c->api); c->serial_rows = rows > 0 ? rows : 0; }
+}
+void nblic_amd_set_long_chains(nblic_amd_ctx *c, int min_records, int block_records) {
+    if (!c) c = default_ctx();
+    if (c) { std::lock_guard<std::mutex> g(c->api); c->long_min = min_records < 0 ? -1 : min_records; c->long_block = block_records > 0 ? block_records : 0; }
+}
+int nblic_amd_long_chain_stats(nblic_amd_ctx *c, long counts[8], int reset) {
+    if (!c) c = default_ctx();
+    if (!c || !counts) return -1;
+    std::lock_guard<std::mutex> l(c->stat_m);
+    for (int k = 0; k < 8; k++) { counts[k] = c->long_counts[k]; if (reset) c->long_counts[k] = 0; }
+    return 0;
 }
 long nblic_amd_serial_launches(nblic_amd_ctx *c) {
     if (!c) c = default_ctx();
