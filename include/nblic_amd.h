@@ -335,6 +335,27 @@ int nblic_amd_decode_indexed(nblic_amd_ctx *ctx, const unsigned char *stream, si
 int nblic_amd_decode_rows(nblic_amd_ctx *ctx, const unsigned char *stream, size_t stream_bytes, const void *index, size_t index_bytes,
                           int row0, int row1, unsigned char *out, size_t cap);
 
+/* PACKED SEEK INDEX: the same information as a seek index, delta-coded entry against entry and bit-packed (magic
+ * "NBLSIDXP"; the format: DESIGN.md section 6).  It converts to and from the index byte for byte, and every function that
+ * READS an index takes either form: index_check, decode_indexed, decode_rows (both unpack on the host) and
+ * decode_batch_indexed (packed and unpacked indexes in any mix; a packed one is checked in its packed form and expanded on
+ * the device only).  Everything that WRITES an index writes the unpacked form; packing is one host call on the result.
+ * All five are host only and need no context.
+ *   index_pack         `index` (one nblic_amd_index_check accepts) as a packed index into out.  Returns its size -- written
+ *                      only when cap is large enough (nblic_amd_index_pack_bound is) -- or -1: an index the check refuses.
+ *   index_pack_bound   no packed form of `index` (its head is read) is larger: its own size + 32 + 33 per entry.  0: not an
+ *                      index's head.
+ *   index_unpack       the index a packed one stands for into out (cap >= nblic_amd_index_unpacked_bytes).  Every entry is
+ *                      re-derived and sealed again; a seal that differs from the stored one is a refusal.  Returns the size
+ *                      (with out == NULL or cap too small: the size alone), or -1.
+ *   index_unpacked_bytes   from the packed index's head; 0: not a packed index's head.
+ *   index_is_packed    1 when the bytes start with the packed magic. */
+long nblic_amd_index_pack(const void *index, size_t index_bytes, unsigned char *out, size_t cap);
+size_t nblic_amd_index_pack_bound(const void *index, size_t index_bytes);
+long nblic_amd_index_unpack(const void *packed, size_t packed_bytes, unsigned char *out, size_t cap);
+size_t nblic_amd_index_unpacked_bytes(const void *packed, size_t packed_bytes);
+int nblic_amd_index_is_packed(const void *index, size_t index_bytes);
+
 /* INDEXED BATCH ENCODE: many lossless -n0 -e1 images AND their seek indexes in one call.  Image k gets its byte-exact
  * .nblic stream and, when 1 <= every_rows[k] < heights[k], the seek index nblic_amd_index_build(every_rows[k]) would make
  * for that stream, byte for byte -- without the serial decode index_build costs.  A group of images is stepped through

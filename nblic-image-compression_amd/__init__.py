@@ -49,6 +49,7 @@ EXPORTS = (
     "nblic_amd_encode_batch_indexed", "nblic_amd_index_bytes", "nblic_amd_indexed_batch_split",
     "nblic_amd_decode_batch_indexed", "nblic_amd_indexed_decode_split", "nblic_amd_indexed_decode_plan", "nblic_amd_debug_index_kernels",
     "nblic_amd_index_build_batch", "nblic_amd_index_build_split", "nblic_amd_index_build_plan", "nblic_amd_debug_index_capture",
+    "nblic_amd_index_pack", "nblic_amd_index_pack_bound", "nblic_amd_index_unpack", "nblic_amd_index_unpacked_bytes", "nblic_amd_index_is_packed",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -216,6 +217,17 @@ def load_library() -> C.CDLL:
         lib.nblic_amd_debug_index_kernels.restype = C.c_int
         lib.nblic_amd_debug_index_kernels.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_ulonglong, C.c_ulonglong] + [C.c_void_p] * 3 + \
                                                      [C.c_void_p, C.c_size_t] * 3 + [C.c_void_p]
+    if hasattr(lib, "nblic_amd_index_pack"):
+        lib.nblic_amd_index_pack.restype = C.c_long
+        lib.nblic_amd_index_pack.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        lib.nblic_amd_index_unpack.restype = C.c_long
+        lib.nblic_amd_index_unpack.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        lib.nblic_amd_index_pack_bound.restype = C.c_size_t
+        lib.nblic_amd_index_pack_bound.argtypes = [C.c_void_p, C.c_size_t]
+        lib.nblic_amd_index_unpacked_bytes.restype = C.c_size_t
+        lib.nblic_amd_index_unpacked_bytes.argtypes = [C.c_void_p, C.c_size_t]
+        lib.nblic_amd_index_is_packed.restype = C.c_int
+        lib.nblic_amd_index_is_packed.argtypes = [C.c_void_p, C.c_size_t]
     if hasattr(lib, "nblic_amd_index_build_batch"):
         vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
         lib.nblic_amd_index_build_batch.restype = C.c_int
@@ -802,7 +814,7 @@ class Context:
         return body[:body.size - 16], int(end.value)
 
     def decode_indexed(self, stream: bytes, index: bytes) -> np.ndarray:
-        """The whole plane, every segment of the index side by side (``nblic_amd_decode_indexed``); raises when the index
+        """The whole plane, every segment of the index (packed or not) side by side (``nblic_amd_decode_indexed``); raises when the index
         is refused or a segment does not end where the next entry starts."""
         s, x = _bytes_arg(stream), _bytes_arg(index)
         h, w = _checked_dims(self, s, x)
@@ -822,7 +834,8 @@ class Context:
 
     def decode_batch_indexed(self, pairs, rows=None, info: Optional[dict] = None) -> List[Optional[np.ndarray]]:
         """Many streams' segments, or one row range of each, in one call (``nblic_amd_decode_batch_indexed``).  ``pairs``
-        is ``[(stream, index), ...]``, ``rows`` None (whole planes) or ``[(r0, r1), ...]``.  Returns per image the plane,
+        is ``[(stream, index), ...]`` -- packed indexes (``pack_index``) and unpacked ones in any mix; a packed one is expanded
+        on the device -- ``rows`` None (whole planes) or ``[(r0, r1), ...]``.  Returns per image the plane,
         the rows, or None (refused, or index and stream disagree); the others are unaffected.  ``info``, when given,
         receives ``status`` and ``rc``."""
         n = len(pairs)
@@ -1334,8 +1347,8 @@ def _checked_dims(ctx, stream: np.ndarray, index: np.ndarray) -> Tuple[int, int]
 
 
 def check_index(index: bytes, stream: Optional[bytes] = None, ctx: Optional[Context] = None) -> bool:
-    """True when ``index`` is a valid seek index (``nblic_amd_index_check``: head, checksums, every entry) and, when
-    ``stream`` is given, the index of that stream.  Host only: needs no device."""
+    """True when ``index`` is a valid seek index, packed or not (``nblic_amd_index_check``: head, checksums, every entry)
+    and, when ``stream`` is given, the index of that stream.  Host only: needs no device."""
     lib = load_library()
     x = _bytes_arg(index)
     s = _bytes_arg(stream) if stream is not None else None       # (stream=None: the index alone)
@@ -1343,11 +1356,51 @@ def check_index(index: bytes, stream: Optional[bytes] = None, ctx: Optional[Cont
     return lib.nblic_amd_index_check(handle, _ptr(x), x.size, _ptr(s) if s is not None else None, s.size if s is not None else 0) == 0
 
 
+def index_is_packed(index: bytes) -> bool:
+    """True when ``index`` starts with the packed index's magic (``nblic_amd_index_is_packed``)."""
+    x = _bytes_arg(index)
+    return bool(load_library().nblic_amd_index_is_packed(_ptr(x), x.size))
+
+
+def pack_index_bound(index: bytes) -> int:
+    """No packed form of ``index`` is larger (``nblic_amd_index_pack_bound``; 0: not an index's head)."""
+    x = _bytes_arg(index)
+    return int(load_library().nblic_amd_index_pack_bound(_ptr(x), x.size))
+
+
+def pack_index(index: bytes) -> bytes:
+    """``index`` as a packed index (``nblic_amd_index_pack``): delta-coded entry against entry and bit-packed, it unpacks to
+    the same bytes, and everything that reads an index takes it as it is.  Host only.  ``ValueError``: not a valid index."""
+    lib = load_library()
+    x = _bytes_arg(index)
+    out = np.empty(max(1, int(lib.nblic_amd_index_pack_bound(_ptr(x), x.size))), np.uint8)
+    n = int(lib.nblic_amd_index_pack(_ptr(x), x.size, _ptr(out), out.size))
+    if n < 0 or n > out.size:
+        raise ValueError("pack_index: not a valid (unpacked) seek index")
+    return out[:n].tobytes()
+
+
+def unpack_index(packed: bytes) -> bytes:
+    """The index a packed one stands for, byte for byte (``nblic_amd_index_unpack``).  Host only.  ``ValueError``: not a
+    packed index, damaged, or its entries do not re-derive to the seals it carries."""
+    lib = load_library()
+    x = _bytes_arg(packed)
+    need = int(lib.nblic_amd_index_unpacked_bytes(_ptr(x), x.size))
+    if need <= 0 or int(lib.nblic_amd_index_unpack(_ptr(x), x.size, None, 0)) != need:      # (the structural walk, before anything is allocated)
+        raise ValueError("unpack_index: not a valid packed seek index")
+    out = np.empty(need, np.uint8)
+    if int(lib.nblic_amd_index_unpack(_ptr(x), x.size, _ptr(out), out.size)) != need:
+        raise ValueError("unpack_index: the packed index does not unpack to the index it names")
+    return out.tobytes()
+
+
 def index_entries(index: bytes) -> List[bytes]:
-    """The entries of a valid seek index: band-decoder checkpoints for ``Context.decoder(checkpoint=...)``, in row order
-    (the decoder is then fed from its ``progress()["feed_from"]`` on)."""
+    """The entries of a valid seek index, packed or not: band-decoder checkpoints for ``Context.decoder(checkpoint=...)``,
+    in row order (the decoder is then fed from its ``progress()["feed_from"]`` on)."""
     if not check_index(index):
         raise ValueError("index_entries: not a valid seek index")
+    if index_is_packed(index):
+        index = unpack_index(index)
     b = bytes(index)
     count = int.from_bytes(b[40:44], "little")
     at, out = INDEX_HEAD_BYTES, []

@@ -36,6 +36,7 @@
 #include "device_coder.h"
 #include "hip_owned.h"
 #include "index_entries.h"
+#include "index_pack.h"
 #include "kernels_e1.h"
 #include "lsq_f64.h"
 #include "model.h"
@@ -1857,42 +1858,53 @@ static nblic_amd_stream *stream_resume(nblic_amd_ctx *c, const unsigned char *im
 // or, when the window was what ran out, the window grows: the only case in which the workspace grows).
 // The checkpoint: DecodeCheckpoint (the record layer above).
 // Every field of a checkpoint, before anything of it reaches the device.  0 = valid (head filled in), -1 = refused.
+// The parts of that check, which a packed index entry (index_pack.h) goes through piece by piece: the head's fields and the
+// record's header; the NBLIC tables a resumed launch loads (every value an index can come from); the QNBLIC tables.
+static bool checkpoint_fields_ok(const DecodeCheckpoint &H, const SerialState &S, long max_px) {
+    if (!codec_fields_ok(H.kind, H.h, H.w, H.near, H.k_step, H.effort, max_px)) return false;
+    if (H.band_rows < 1 || H.band_rows > H.h || H.next_row < 0 || H.next_row >= H.h) return false;
+    if (H.body_bytes != record_layout(H.kind, H.w, H.effort).bytes) return false;
+    if (H.rows_sha.total != (unsigned long long)(H.next_row) * (unsigned long long)(H.w)) return false;
+    const unsigned long long first = H.kind ? 8 : (unsigned long long)(kHeaderBytes);
+    return S.status == kRunning && S.next_row == H.next_row && S.pos >= first && S.pos < kMaxStreamPos && (S.pos & ~511ull) == H.feed_from;
+}
+static bool nblic_tables_ok(const uint8_t *cnt, const uint8_t *rank, const uint8_t *sym) {
+    for (int k = 0; k < kLevels * kTreeNodes; k++) {
+        uint32_t c;
+        memcpy(&c, cnt + size_t(k) * 4, 4);
+        if (!counter_ok(int(c & 0xFFFFu), int(c >> 16))) return false;
+    }
+    for (int m = 0; m < 512; m++)
+        if (!remapper_ok(rank + m * kMapSyms, sym + m * kMapSyms)) return false;
+    return true;
+}
+static bool qtab_ok(const uint8_t *tab) {                                 // the twelve frequency tables and their cumulative starts
+    std::vector<uint32_t> t(2 * 12 * 256);
+    memcpy(t.data(), tab, kQTab);
+    const uint32_t *freq = t.data(), *start = t.data() + 12 * 256;
+    for (int l = 0; l < 12; l++) {
+        uint32_t acc = 0;
+        for (int s = 0; s < 256; s++) {
+            if (start[l * 256 + s] != acc || freq[l * 256 + s] > 32768u) return false;
+            acc += freq[l * 256 + s];
+        }
+        if (acc != 32768u) return false;
+    }
+    return true;
+}
 static int dstream_check(const void *ck, size_t len, long max_px, DecodeCheckpoint &H) {
     const uint8_t *body = sealed_body(ck, len, "NBLDCKPT", kDecodeCheckpointVersion, H);
     if (!body || !codec_fields_ok(H.kind, H.h, H.w, H.near, H.k_step, H.effort, max_px)) return -1;
-    if (H.band_rows < 1 || H.band_rows > H.h || H.next_row < 0 || H.next_row >= H.h) return -1;
     const RecordLayout L = record_layout(H.kind, H.w, H.effort);
     if (H.body_bytes != L.bytes || len != sizeof H + H.body_bytes + 32) return -1;
-    if (H.rows_sha.total != (unsigned long long)(H.next_row) * (unsigned long long)(H.w)) return -1;
     SerialState S;
     memcpy(&S, body, sizeof S);
-    const unsigned long long first = H.kind ? 8 : (unsigned long long)(kHeaderBytes);
-    if (S.status != kRunning || S.next_row != H.next_row || S.pos < first || S.pos >= kMaxStreamPos || (S.pos & ~511ull) != H.feed_from) return -1;
+    if (!checkpoint_fields_ok(H, S, max_px)) return -1;
     const uint8_t *tab = body + sizeof S;
-    if (H.kind == 0 && H.next_row > 0) {                                 // the tables a resumed launch loads: every value an index can come from
-        const uint32_t *cnt = reinterpret_cast<const uint32_t *>(tab) + kContexts;
-        for (int k = 0; k < kLevels * kTreeNodes; k++) {
-            uint32_t c;
-            memcpy(&c, cnt + k, 4);
-            if (!counter_ok(int(c & 0xFFFFu), int(c >> 16))) return -1;
-        }
-        const uint8_t *rank = tab + size_t(kRecRank) * 4, *sym = tab + size_t(kRecSym) * 4;
-        for (int m = 0; m < 512; m++)
-            if (!remapper_ok(rank + m * kMapSyms, sym + m * kMapSyms)) return -1;
-    }
+    if (H.kind == 0 && H.next_row > 0 &&
+        !nblic_tables_ok(tab + size_t(kContexts) * 4, tab + size_t(kRecRank) * 4, tab + size_t(kRecSym) * 4)) return -1;
     if (!finite_doubles(body + L.b, L.b_bytes)) return -1;
-    if (H.kind == 1) {                                                   // the twelve frequency tables and their cumulative starts
-        uint32_t freq[12 * 256], start[12 * 256];
-        memcpy(freq, body + L.tab, sizeof freq); memcpy(start, body + L.tab + sizeof freq, sizeof start);
-        for (int l = 0; l < 12; l++) {
-            uint32_t acc = 0;
-            for (int s = 0; s < 256; s++) {
-                if (start[l * 256 + s] != acc || freq[l * 256 + s] > 32768u) return -1;
-                acc += freq[l * 256 + s];
-            }
-            if (acc != 32768u) return -1;
-        }
-    }
+    if (H.kind == 1 && !qtab_ok(body + L.tab)) return -1;
     return 0;
 }
 
@@ -2184,6 +2196,10 @@ struct IndexHead {
     uint8_t stream_sha[32];
 };
 static_assert(sizeof(IndexHead) == kIndexHeadBytes, "written and read as bytes");
+static_assert(offsetof(IndexHead, version) == kHeadVersionAt && offsetof(IndexHead, kind) == kHeadKindAt && offsetof(IndexHead, h) == kHeadHAt &&
+              offsetof(IndexHead, w) == kHeadWAt && offsetof(IndexHead, effort) == kHeadEffortAt && offsetof(IndexHead, every_rows) == kHeadEveryAt &&
+              offsetof(IndexHead, count) == kHeadCountAt && kIndexVersion == kUnpackedVersion && kMapSyms == int(kPackMapSyms) &&
+              kCodeRank == kUnpackCodeRank, "index_pack.h reads these fields by offset");
 
 static IndexHead index_head(const DecodeItem &it, int every, int count, unsigned long long stream_len) {     // all but stream_sha
     IndexHead H{};
@@ -2198,8 +2214,10 @@ static IndexHead index_head(const DecodeItem &it, int every, int count, unsigned
 struct IndexView {                     // a checked index: its head and where its entries are
     IndexHead H;
     RecordLayout L;                    // of every entry's body
-    std::vector<const uint8_t *> ent;  // entry k + 1 (the checkpoint in front of row (k + 1) R) at ent[k]
-    const uint8_t *body(int k) const { return ent[size_t(k - 1)] + sizeof(DecodeCheckpoint); }     // entry k, 1-based
+    std::vector<const uint8_t *> ent;  // entry k + 1 (the checkpoint in front of row (k + 1) R) at ent[k]: its head (verbatim in a packed index too)
+    const uint8_t *body(int k) const { return ent[size_t(k - 1)] + sizeof(DecodeCheckpoint); }     // entry k, 1-based; an unpacked index only
+    bool packed = false;               // a packed index (index_pack.h): P says where the parts of its entries' bodies lie
+    PackedView P;
 };
 
 // A checkpoint's running row hash, written canonically: the bytes of the partial block past total % 64 are whatever
@@ -2212,13 +2230,72 @@ static Sha256 canonical_sha(Sha256 s) {
 
 // Every field of an index, every entry (dstream_check), and -- when `stream` is given -- that it is the stream the index
 // was made for.  Host only.  0 = valid (V filled in), -1 = refused.
-static int index_check(const void *idx, size_t ilen, const void *stream, size_t slen, long max_px, IndexView &V) {
+static bool index_head_ok(const IndexHead &H, long max_px) {
+    if (!codec_fields_ok(H.kind, H.h, H.w, H.near, H.k_step, H.effort, max_px) || H.reserved[0] != 0 || H.reserved[1] != 0 || H.reserved[2] != 0) return false;
+    if (H.every_rows < 1 || H.every_rows >= H.h || H.count != (H.h - 1) / H.every_rows) return false;
+    return H.stream_len < kMaxStreamPos;
+}
+static bool index_entry_head_ok(const IndexHead &H, const DecodeCheckpoint &C, const SerialState &S, int k) {     // entry k, 0-based
+    return C.kind == H.kind && C.h == H.h && C.w == H.w && C.near == H.near && C.k_step == H.k_step && C.effort == H.effort &&
+           C.band_rows == H.every_rows && C.next_row == (k + 1) * H.every_rows && C.feed_from <= H.stream_len && S.pos <= H.stream_len;
+}
+static bool index_stream_ok(const IndexHead &H, const void *stream, size_t slen, long max_px) {
+    if (slen != H.stream_len) return false;
+    DecodeItem it{0, 0, 0, 0, 0, 0, 0, slen, -1, -1};
+    if (!parse_stream_header(static_cast<const uint8_t *>(stream), slen, max_px, it)) return false;
+    if (it.kind != H.kind || it.h != H.h || it.w != H.w || it.near != H.near || it.k_step != H.k_step || it.effort != H.effort) return false;
+    uint8_t d[32];
+    sha256_of(stream, slen, d);
+    return memcmp(d, H.stream_sha, 32) == 0;
+}
+
+// The same for a PACKED index, in its packed form: the structural walk (every length, flag and width byte, every packed
+// entry's hash), the head, every entry's head and record header, and the table values a resumed launch depends on -- the
+// counters, the re-mappers, a raw B, the QNBLIC tables -- each re-derived from its own part alone, entry after entry.  The
+// entries' own seals and the final seal are NOT re-derived here: unpack_index does that.
+static int packed_index_check(const void *idx, size_t ilen, const void *stream, size_t slen, long max_px, IndexView &V) {
+    const uint8_t *p = static_cast<const uint8_t *>(idx);
+    V.ent.clear();
+    V.packed = true;
+    if (!packed_walk(idx, ilen, V.P)) return -1;
     IndexHead &H = V.H;
+    memcpy(&H, p, sizeof H);
+    if (!index_head_ok(H, max_px)) return -1;
+    V.L = record_layout(H.kind, H.w, H.effort);
+    const PackedView &P = V.P;
+    if (P.body_bytes != V.L.bytes) return -1;
+    std::vector<uint8_t> tab[2][3];                                      // this entry's and the previous one's: counters | rank | syms, or the QNBLIC tables
+    const int want[3] = {H.kind ? kQPartTab : kPartCounters, H.kind ? -1 : kPartRank, H.kind ? -1 : kPartSyms};
+    for (int k = 0; k < H.count; k++) {
+        const PackedEntry &E = P.ent[size_t(k)];
+        DecodeCheckpoint C;
+        SerialState S;
+        memcpy(&C, p + E.head_at, sizeof C);
+        memcpy(&S, p + E.part_at[0], sizeof S);                          // (a part that is not coded is always stored raw)
+        if (memcmp(C.magic, "NBLDCKPT", 8) != 0 || C.version != kDecodeCheckpointVersion || !checkpoint_fields_ok(C, S, max_px) ||
+            !index_entry_head_ok(H, C, S, k)) return -1;
+        auto &cur = tab[k & 1], &prev = tab[(k & 1) ^ 1];
+        for (int t : {0, 2, 1}) {                                        // the rank bytes last: left out, they come from the syms
+            const int j = want[t];
+            if (j < 0) continue;
+            cur[t].resize(P.parts[j].bytes);
+            unpack_part(p, P, k, j, k ? prev[t].data() : nullptr, t == 1 ? cur[2].data() : nullptr, cur[t].data());
+        }
+        if (H.kind ? !qtab_ok(cur[0].data()) : !nblic_tables_ok(cur[0].data(), cur[1].data(), cur[2].data())) return -1;
+        for (int j = 0; j < P.n_parts; j++)
+            if (P.parts[j].code == kCodeInt64 && E.part_flag[j] == kPartRaw && !finite_doubles(p + E.part_at[j], P.parts[j].bytes)) return -1;
+        V.ent.push_back(p + E.head_at);
+    }
+    return stream && !index_stream_ok(H, stream, slen, max_px) ? -1 : 0;
+}
+
+static int index_check(const void *idx, size_t ilen, const void *stream, size_t slen, long max_px, IndexView &V) {
+    if (index_is_packed(idx, ilen)) return packed_index_check(idx, ilen, stream, slen, max_px, V);
+    IndexHead &H = V.H;
+    V.packed = false;
     if (!sealed_body(idx, ilen, "NBLSIDX1", kIndexVersion, H)) return -1;
     const uint8_t *p = static_cast<const uint8_t *>(idx);
-    if (!codec_fields_ok(H.kind, H.h, H.w, H.near, H.k_step, H.effort, max_px) || H.reserved[0] != 0 || H.reserved[1] != 0 || H.reserved[2] != 0) return -1;
-    if (H.every_rows < 1 || H.every_rows >= H.h || H.count != (H.h - 1) / H.every_rows) return -1;
-    if (H.stream_len >= kMaxStreamPos) return -1;
+    if (!index_head_ok(H, max_px)) return -1;
     V.L = record_layout(H.kind, H.w, H.effort);
     V.ent.clear();
     size_t at = sizeof H;
@@ -2231,25 +2308,14 @@ static int index_check(const void *idx, size_t ilen, const void *stream, size_t 
         if (n > end - at) return -1;
         DecodeCheckpoint C;
         if (dstream_check(p + at, size_t(n), max_px, C) != 0) return -1;
-        if (C.kind != H.kind || C.h != H.h || C.w != H.w || C.near != H.near || C.k_step != H.k_step || C.effort != H.effort ||
-            C.band_rows != H.every_rows || C.next_row != (k + 1) * H.every_rows || C.feed_from > H.stream_len) return -1;
         SerialState S;
         memcpy(&S, p + at + sizeof C, sizeof S);
-        if (S.pos > H.stream_len) return -1;
+        if (!index_entry_head_ok(H, C, S, k)) return -1;
         V.ent.push_back(p + at);
         at += size_t(n);
     }
     if (at != end) return -1;
-    if (stream) {
-        if (slen != H.stream_len) return -1;
-        DecodeItem it{0, 0, 0, 0, 0, 0, 0, slen, -1, -1};
-        if (!parse_stream_header(static_cast<const uint8_t *>(stream), slen, max_px, it)) return -1;
-        if (it.kind != H.kind || it.h != H.h || it.w != H.w || it.near != H.near || it.k_step != H.k_step || it.effort != H.effort) return -1;
-        uint8_t d[32];
-        sha256_of(stream, slen, d);
-        if (memcmp(d, H.stream_sha, 32) != 0) return -1;
-    }
-    return 0;
+    return stream && !index_stream_ok(H, stream, slen, max_px) ? -1 : 0;
 }
 
 // One band-decoder pass with band_rows = R, a checkpoint in front of every row R, 2R, ...; the pass runs to the end of the
@@ -2405,6 +2471,7 @@ static size_t stream_index(nblic_amd_stream *s, void *buf, size_t cap) {
 // buffers (mem), released on every path out: the stream synchronised, then the buffers, then the stream.
 struct IndexedRun {
     IndexView V;
+    std::vector<uint8_t> unpacked;     // a packed index is unpacked here, on the host, and V is a view of this
     DecodeItem it{};
     std::vector<uint8_t> qtab;
     size_t slen = 0;
@@ -2418,7 +2485,12 @@ struct IndexedRun {
 
 // The host half of an indexed decode: the index against the stream, the stream's description.  false: refused.
 static bool indexed_check(IndexedRun &run, nblic_amd_ctx *c, const unsigned char *stream, size_t slen, const void *idx, size_t ilen) {
-    if (!c || !stream || index_check(idx, ilen, stream, slen, c->max_px, run.V) != 0) return false;
+    if (!c || !stream) return false;
+    if (index_is_packed(idx, ilen)) {                                    // one image: unpacked on the host, then as ever
+        if (!unpack_index(idx, ilen, run.unpacked)) return false;
+        idx = run.unpacked.data(); ilen = run.unpacked.size();
+    }
+    if (index_check(idx, ilen, stream, slen, c->max_px, run.V) != 0) return false;
     run.it = DecodeItem{0, 0, 0, 0, 0, 0, 0, 0, -1, -1};
     if (describe_stream(stream, slen, false, c->max_px, run.it, run.qtab) != Described::ok) return false;
     run.slen = slen;
@@ -2926,7 +2998,32 @@ struct IdxDecImage {
     uint8_t *d_stream = nullptr, *d_index = nullptr, *d_plane = nullptr, *d_tab = nullptr;
     uint32_t *d_verdict = nullptr;      // one word per inner boundary, from boundary seg0 | seg0 + 1 on
     SerialState last{};                 // the last segment's final header
+    // a packed index: where its parts lie (for the device), the payload offsets, and this round's unpacked entries
+    unsigned long long *d_desc = nullptr; uint32_t *d_offs = nullptr;
+    IndexUnpackTask unpack{};           // all but the round's fields
+    uint8_t *d_unpacked = nullptr; int unpacked_first = 0;       // entry unpacked_first (1-based) lies at d_unpacked, the next ones unpack.out_stride apart
 };
+
+// The device's view of a checked packed index: its parts without the QNBLIC tables (nothing on the device reads an entry's),
+// and where every part of entries 0 .. walk - 1 lies.
+static void idxdec_unpack_task(const IndexView &V, int walk, IndexUnpackTask &T, std::vector<unsigned long long> &desc) {
+    const PackedView &P = V.P;
+    T = IndexUnpackTask{};
+    std::vector<int> parts;
+    for (int j = 0; j < P.n_parts; j++) {
+        const PackPart &p = P.parts[j];
+        if (p.at >= V.L.tab) continue;
+        T.part[parts.size()] = IndexUnpackPart{p.at, p.bytes, p.unit, p.code, p.init, T.blocks};
+        T.blocks += part_blocks(p);
+        parts.push_back(j);
+    }
+    T.n_parts = uint32_t(parts.size());
+    T.walk = uint32_t(walk);
+    T.out_stride = uint32_t((V.L.tab + 15) & ~size_t(15));
+    desc.clear();
+    for (int e = 0; e < walk; e++)
+        for (int j : parts) desc.push_back((unsigned long long)(P.ent[size_t(e)].part_at[j]) | ((unsigned long long)(P.ent[size_t(e)].part_flag[j]) << 56));
+}
 
 static bool idxdec_upload_tasks(std::vector<IndexTask> &tasks, bool seed, IndexTask *d_tasks, uint32_t &chunks, hipStream_t st) {
     chunks = 0;
@@ -2985,7 +3082,8 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
             memcpy(&E, I.V.ent[size_t(I.seg0 - 1)], sizeof E);
             I.stream_off = E.feed_from;
         }
-        per_seg_max = std::max(per_seg_max, up256(I.V.L.b) + up256(2 * I.V.L.b_bytes));
+        // (a round's segments s .. t of an image need its entries s .. t + 1 unpacked: no more than two per segment)
+        per_seg_max = std::max(per_seg_max, up256(I.V.L.b) + up256(2 * I.V.L.b_bytes) + (I.V.packed ? 2 * up256(I.V.L.tab + 15) : 0));
         plan_in.push_back(IndexedPlanImage{it.kind, it.effort, it.h, it.w, R, I.row0, I.row1});
         live.push_back(&I);
     }
@@ -3026,25 +3124,64 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
                 (it.kind && hipMemcpyAsync(I->d_tab, I->qtab.data(), kQTab, hipMemcpyHostToDevice, st) != hipSuccess)) return fail("upload");
         }
     }
+    // the packed indexes among them: where their parts lie, and every block's payload offset (one scan launch for the call)
+    std::vector<std::vector<unsigned long long>> descs(live.size());
+    std::vector<IndexUnpackTask> unpacks;
+    IndexUnpackTask *d_unpacks = mem.make<IndexUnpackTask>(live.size());
+    if (!d_unpacks) return fail("cannot allocate the workspace");
+    {
+        uint32_t scan_waves = 0;
+        for (size_t i = 0; i < live.size(); i++) {
+            IdxDecImage *I = live[i];
+            if (!I->V.packed) continue;
+            const int walk = I->seg1;                                    // entries 1 .. seg1, 0-based 0 .. walk - 1, are all this call reads
+            idxdec_unpack_task(I->V, walk, I->unpack, descs[i]);
+            I->d_desc = mem.make<unsigned long long>(std::max<size_t>(1, descs[i].size()));
+            I->d_offs = mem.make<uint32_t>(std::max<size_t>(1, size_t(walk) * I->unpack.blocks));
+            if (!I->d_desc || !I->d_offs) return fail("cannot allocate the workspace");
+            if (!descs[i].empty() && hipMemcpyAsync(I->d_desc, descs[i].data(), descs[i].size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st) != hipSuccess) return fail("upload");
+            I->unpack.packed = I->d_index; I->unpack.desc = I->d_desc; I->unpack.offs = I->d_offs;
+            if (walk == 0) continue;
+            IndexUnpackTask T = I->unpack;
+            T.first_scan_wave = scan_waves; scan_waves += index_unpack_scan_waves(T);
+            unpacks.push_back(T);
+        }
+        if (!unpacks.empty() && (hipMemcpyAsync(d_unpacks, unpacks.data(), unpacks.size() * sizeof(IndexUnpackTask), hipMemcpyHostToDevice, st) != hipSuccess ||
+                                 !index_unpack_scan_launch(d_unpacks, int(unpacks.size()), scan_waves, st))) return fail("launch");
+    }
     // the rounds' shared buffers: records and statistics, jobs, tasks
     const int n_rounds = plan.back().round + 1;
     std::vector<size_t> round_begin(size_t(n_rounds) + 1, plan.size());
-    size_t rec_bytes_max = 0, jobs_max = 0;
+    size_t rec_bytes_max = 0, jobs_max = 0, unpacked_max = 0;
     for (size_t j = plan.size(); j-- > 0;) round_begin[size_t(plan[j].round)] = j;
+    // the entries (1-based) of image I that a round's segments [s_lo, s_hi] read: every seed but segment 0's, the one behind each
+    auto round_entries = [](const IdxDecImage &I, int s_lo, int s_hi, int &first, int &last) {
+        first = std::max(1, s_lo); last = std::min(s_hi + 1, I.seg1);    // (the last segment of the range ends at no boundary; seg1 <= count)
+    };
     for (int r = 0; r < n_rounds; r++) {
-        size_t bytes = 0;
+        size_t bytes = 0, unpacked = 0;
         for (size_t j = round_begin[size_t(r)]; j < round_begin[size_t(r) + 1]; j++) {
-            const RecordLayout &L = live[size_t(plan[j].image)]->V.L;
+            const IdxDecImage &I = *live[size_t(plan[j].image)];
+            const RecordLayout &L = I.V.L;
             bytes += up256(L.b) + up256(2 * L.b_bytes);
+            if (I.V.packed && (j + 1 == round_begin[size_t(r) + 1] || plan[j + 1].image != plan[j].image)) {     // the image's last job of the round: its lowest segment
+                size_t a = j;
+                while (a > round_begin[size_t(r)] && plan[a - 1].image == plan[j].image) a--;
+                int first, last;
+                round_entries(I, plan[j].segment, plan[a].segment, first, last);
+                if (last >= first) unpacked += up256(size_t(last - first + 1) * I.unpack.out_stride);
+            }
         }
         rec_bytes_max = std::max(rec_bytes_max, bytes);
+        unpacked_max = std::max(unpacked_max, unpacked);
         jobs_max = std::max(jobs_max, round_begin[size_t(r) + 1] - round_begin[size_t(r)]);
     }
     uint8_t *d_recs = mem.make<uint8_t>(rec_bytes_max);
     SerialJob *d_jobs = mem.make<SerialJob>(jobs_max);
     IndexTask *d_tasks = mem.make<IndexTask>(std::max(jobs_max, n_bounds));
     IndexTask *d_tasks2 = mem.make<IndexTask>(jobs_max);
-    if (!d_recs || !d_jobs || !d_tasks || !d_tasks2) return fail("cannot allocate the workspace");
+    uint8_t *d_unpacked = mem.make<uint8_t>(std::max<size_t>(1, unpacked_max));
+    if (!d_recs || !d_jobs || !d_tasks || !d_tasks2 || !d_unpacked) return fail("cannot allocate the workspace");
     if (hipStreamSynchronize(st) != hipSuccess) return fail("upload");
     split[1] = ms_since(t0);
     t0 = Clock::now();
@@ -3054,14 +3191,27 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
         const int r = e * I.V.H.every_rows;
         const RowsAbove A = rows_above(r, I.it.w);
         IndexTask T{};
-        T.entry = e > 0 ? I.d_index + size_t(I.V.body(e) - static_cast<const uint8_t *>(indexes[I.k])) : nullptr;
+        bool rows_direct = false;                                        // T.entry is the row slot itself, not the body
+        if (e > 0 && I.V.packed) {
+            if (parts == kChainRows) {                                   // after the last round: the rows lie raw in the packed index
+                const PackedEntry &E = I.V.P.ent[size_t(e - 1)];
+                int j = 0;
+                while (I.V.P.parts[j].at != L.rows) j++;
+                T.entry = I.d_index + E.part_at[j];
+                rows_direct = true;
+            } else {
+                T.entry = I.d_unpacked + size_t(e - I.unpacked_first) * I.unpack.out_stride;
+            }
+        } else {
+            T.entry = e > 0 ? I.d_index + size_t(I.V.body(e) - static_cast<const uint8_t *>(indexes[I.k])) : nullptr;
+        }
         T.rec = rec; T.stats = stats;
         T.rows = I.d_plane + size_t(A.first - I.base) * size_t(I.it.w);
         T.avail = I.it.len; T.first_pos = first_pos(I.it);
         T.rec_bytes = (parts & kChainRecord) ? uint32_t(L.b) : 0u;
         T.b_bytes = (parts & kChainB) ? uint32_t(L.b_bytes) : 0u;
         T.rows_bytes = (parts & kChainRows) && e > 0 ? uint32_t(size_t(A.n) * size_t(I.it.w)) : 0u;
-        T.b_at = uint32_t(L.b); T.rows_at = uint32_t(L.rows + A.at);
+        T.b_at = uint32_t(L.b); T.rows_at = uint32_t((rows_direct ? 0 : L.rows) + A.at);
         T.kind = uint32_t(I.it.kind);
         return T;
     };
@@ -3070,7 +3220,31 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
     long launches_total = 0;
     for (int r = 0; r < n_rounds; r++) {
         const size_t j0 = round_begin[size_t(r)], j1 = round_begin[size_t(r) + 1];
-        seeds.clear(); chains.clear();
+        seeds.clear(); chains.clear(); unpacks.clear();
+        // the packed images of the round: their entries, unpacked
+        {
+            size_t at = 0;
+            uint32_t waves = 0, groups = 0;
+            for (size_t j = j0; j < j1;) {
+                size_t b = j + 1;
+                while (b < j1 && plan[b].image == plan[j].image) b++;
+                IdxDecImage &I = *live[size_t(plan[j].image)];
+                int first = 1, last = 0;
+                if (I.V.packed) round_entries(I, plan[b - 1].segment, plan[j].segment, first, last);
+                if (last >= first) {
+                    I.d_unpacked = d_unpacked + at; I.unpacked_first = first;
+                    at += up256(size_t(last - first + 1) * I.unpack.out_stride);
+                    IndexUnpackTask T = I.unpack;
+                    T.out = I.d_unpacked; T.walk = uint32_t(last); T.first_out = uint32_t(first - 1);
+                    T.first_wave = waves; waves += index_unpack_waves(T);
+                    T.first_rank_group = groups; groups += index_unpack_rank_groups(T);
+                    unpacks.push_back(T);
+                }
+                j = b;
+            }
+            if (!unpacks.empty() && (hipMemcpyAsync(d_unpacks, unpacks.data(), unpacks.size() * sizeof(IndexUnpackTask), hipMemcpyHostToDevice, st) != hipSuccess ||
+                                     !index_unpack_launch(d_unpacks, int(unpacks.size()), waves, groups, st))) return fail("launch");
+        }
         size_t at = 0;
         for (size_t j = j0; j < j1; j++) {
             const IndexedJob &P = plan[j];
@@ -3936,7 +4110,7 @@ int nblic_amd_debug_index_kernels(nblic_amd_ctx *c, const void *index, size_t in
                                   const unsigned char *final_rec, size_t final_rec_bytes, const unsigned char *final_b, size_t final_b_bytes,
                                   const unsigned char *final_rows, size_t final_rows_bytes, unsigned int *verdict) {
     IndexView V;
-    if (!c || !index || !rec_out || !stats_out || !rows_out || base_offset > 4096 || index_check(index, index_bytes, nullptr, 0, c->max_px, V) != 0) return -1;
+    if (!c || !index || !rec_out || !stats_out || !rows_out || base_offset > 4096 || index_check(index, index_bytes, nullptr, 0, c->max_px, V) != 0 || V.packed) return -1;
     if (entry < 0 || entry > V.H.count) return -1;
     const bool chain = final_rec || final_b || final_rows || verdict;
     const RecordLayout &L = V.L;
@@ -4279,6 +4453,32 @@ void nblic_amd_set_index_round(nblic_amd_ctx *c, int segments) { if (c) c->index
 int nblic_amd_index_check(nblic_amd_ctx *c, const void *index, size_t index_bytes, const unsigned char *stream, size_t stream_bytes) {
     IndexView V;
     return index_check(index, index_bytes, stream, stream_bytes, c ? c->max_px : kMaxPixels, V);
+}
+int nblic_amd_index_is_packed(const void *index, size_t index_bytes) { return index_is_packed(index, index_bytes) ? 1 : 0; }
+size_t nblic_amd_index_unpacked_bytes(const void *packed, size_t packed_bytes) { return index_unpacked_bytes(packed, packed_bytes); }
+size_t nblic_amd_index_pack_bound(const void *index, size_t index_bytes) {
+    PackHead H;
+    if (!pack_head(static_cast<const uint8_t *>(index), index_bytes, "NBLSIDX1", kUnpackedVersion, H)) return 0;
+    return index_pack_bound(H.count, index_entry_bytes(H.kind, H.w, H.effort));
+}
+long nblic_amd_index_pack(const void *index, size_t index_bytes, unsigned char *out, size_t cap) {
+    IndexView V;
+    std::vector<uint8_t> packed;
+    if (index_is_packed(index, index_bytes) || index_check(index, index_bytes, nullptr, 0, kMaxPixels, V) != 0 || !pack_index(index, index_bytes, packed)) return -1;
+    if (out && cap >= packed.size()) memcpy(out, packed.data(), packed.size());
+    return long(packed.size());
+}
+long nblic_amd_index_unpack(const void *packed, size_t packed_bytes, unsigned char *out, size_t cap) {
+    const size_t need = index_unpacked_bytes(packed, packed_bytes);
+    if (need == 0) return -1;
+    if (!out || cap < need) {                                            // the size alone -- of a packed index that passes its structural walk
+        PackedView V;
+        return packed_walk(packed, packed_bytes, V) ? long(need) : -1;
+    }
+    std::vector<uint8_t> index;
+    if (!unpack_index(packed, packed_bytes, index) || index.size() != need) return -1;
+    memcpy(out, index.data(), need);
+    return long(need);
 }
 long nblic_amd_index_build(nblic_amd_ctx *c, const unsigned char *stream, size_t stream_bytes, int every_rows, unsigned char *out, size_t cap) {
     return index_build(c, stream, stream_bytes, every_rows, out, cap);

@@ -178,6 +178,44 @@ inline uint32_t index_capture_chunks(const IndexCaptureTask &t) { return (index_
 // d_tasks[0..n) with first_chunk filled in (from 0), `chunks` their sum.  false: the launch failed.
 bool index_capture_launch(const IndexCaptureTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
 
+// ---- a packed index (index_pack.h), expanded on the device ------------------------------------------------------------------
+// A packed index is uploaded as it is (any address).  The bodies of the entries a round needs are written, unpacked, into an
+// aligned buffer -- record | B | the row slot, `out_stride` apart; the QNBLIC tables are not: nothing on the device reads an
+// entry's -- and the IndexTask::entry pointers of k_index_seed and k_index_chain point there.  Three launches:
+//   k_index_unpack_scan  one wave per (image, entry, coded part): the payload offset of every block, an exclusive scan of the
+//                        part's width bytes, 64 blocks per step across the lanes.  Once per call: `offs` serves every round.
+//   k_index_unpack       one wave per (image, part, block), one unit per lane.  The differences chain from entry to entry, so
+//                        the wave walks entries 0 .. walk - 1 in order with each lane's running value in a register, reads
+//                        the block's width byte b and takes its b bits out of the aligned 32-bit words around them, and
+//                        stores the unit -- one aligned 2-, 4- or 8-byte store -- for the entries from `first_out` on.
+//   k_index_unpack_rank  the symbol -> rank bytes a packed entry leaves out, from the unpacked rank -> symbol bytes, as
+//                        k_index_capture rebuilds them; one workgroup per (image, stored entry).
+// desc[e * n_parts + j] = where part j of entry e lies in the packed index (its data, behind its flag byte) | flag << 56, from
+// the host's check, which has walked every width byte: nothing the kernels read lies outside the packed index.
+struct IndexUnpackPart { uint32_t out_at, bytes, unit, code, init, first_block; };       // index_pack.h PackPart, and the blocks in front
+struct IndexUnpackTask {
+    const uint8_t *packed;
+    const unsigned long long *desc;
+    uint32_t *offs;                        // [entry][blocks]: a block's payload, in bytes from its part's data
+    uint8_t *out;                          // entries first_out .. walk - 1 (0-based), out_stride apart (a multiple of 16)
+    uint32_t walk, first_out, out_stride, n_parts;
+    uint32_t blocks;                       // of all parts together
+    uint32_t first_wave, first_scan_wave, first_rank_group;   // waves / workgroups of the tasks in front of this one
+    IndexUnpackPart part[8];
+};
+static_assert(sizeof(IndexUnpackTask) == 256, "uploaded as bytes");
+constexpr unsigned long long kUnpackDescAt = (1ull << 56) - 1;
+inline uint32_t index_unpack_waves(const IndexUnpackTask &t) { return t.blocks; }
+inline uint32_t index_unpack_scan_waves(const IndexUnpackTask &t) { return t.walk * t.n_parts; }
+constexpr uint32_t kUnpackCodeRank = 4;                                                  // index_pack.h kCodeRank (pipeline.hip asserts it)
+inline uint32_t index_unpack_rank_groups(const IndexUnpackTask &t) {                     // one per stored entry of a mode that has re-mappers
+    for (uint32_t j = 0; j < t.n_parts; j++) if (t.part[j].code == kUnpackCodeRank) return t.walk - t.first_out;
+    return 0;
+}
+// d_tasks[0..n) with the first_* fields filled in; the totals of each.  false: the launch failed.
+bool index_unpack_scan_launch(const IndexUnpackTask *d_tasks, int n, uint32_t scan_waves, hipStream_t s);
+bool index_unpack_launch(const IndexUnpackTask *d_tasks, int n, uint32_t waves, uint32_t rank_groups, hipStream_t s);
+
 // Both least-squares solvers of the serial kernels on `count` given systems, no image and no coder (tests): stats = count x vec_len(n)
 // integer-valued statistics [s | b | A], vn = count x 10 regressors, bias = the regularisation strength the pixel starts from (the two
 // systems of an item are the ones bias_pair makes of it).  n = 6 or 10; waves = 2 (n = 10 only) runs the two-wave hand-over.  Per item

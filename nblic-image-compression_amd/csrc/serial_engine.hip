@@ -1796,4 +1796,134 @@ bool index_capture_launch(const IndexCaptureTask *d_tasks, int n, uint32_t chunk
     return hipGetLastError() == hipSuccess;
 }
 
+
+// ---- a packed index, expanded on the device (serial_engine.h IndexUnpackTask; the format: index_pack.h) --------------------
+constexpr uint32_t kUnpackWaves = kIndexThreads / 64;
+enum : uint32_t { kUnpackRaw = 0, kUnpackCoded = 1, kUnpackLeftOut = 2 };                 // a part's flag byte
+enum : uint32_t { kUnpackDiff = 1, kUnpackXor = 2, kUnpackInt64 = 3 };                    // PackPart::code (0: a raw part; kUnpackCodeRank)
+
+// The task a wave (or workgroup) belongs to: the last one whose FIRST is not behind it.
+template <uint32_t IndexUnpackTask::*FIRST>
+__device__ __forceinline__ int unpack_task_of(const IndexUnpackTask *__restrict__ tasks, int n, uint32_t at) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tasks[mid].*FIRST <= at) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// Unit i of the table a fresh decoder starts from (index_pack.h pack_initial; k_serial_decode at i0 == 0).
+__device__ __forceinline__ uint64_t unpack_initial(uint32_t init, uint32_t i) {
+    constexpr uint32_t kSyms = uint32_t(kMapSyms);
+    return init == 1 ? 32u : init == 2 ? 2u * (kSyms - 1u - i % kSyms) : init == 3 ? 0x03020100u + 0x04040404u * (i % (kSyms / 4u)) : 0u;
+}
+
+// `bits` bits (0 .. 64) at bit `bit` behind p, p at any address: the aligned words that hold them, shifted into place.  A
+// field of more than 32 bits may straddle three words; no word is read that holds none of its bits, and none for bits == 0.
+__device__ __forceinline__ uint64_t load_bits_any(const NB_GLOBAL uint8_t *p, uint32_t bit, uint32_t bits) {
+    if (bits == 0) return 0;
+    const uintptr_t a = uintptr_t(p);
+    const NB_GLOBAL uint32_t *q = (const NB_GLOBAL uint32_t *)(a & ~uintptr_t(3));
+    const uint32_t at = uint32_t(a & 3) * 8 + bit, k = at >> 5, sh = at & 31;
+    const uint32_t w0 = q[k], w1 = sh + bits > 32 ? q[k + 1] : 0u, w2 = sh + bits > 64 ? q[k + 2] : 0u;
+    const uint64_t v = uint64_t(__builtin_amdgcn_alignbit(w1, w0, sh)) | (uint64_t(__builtin_amdgcn_alignbit(w2, w1, sh)) << 32);
+    return bits >= 64 ? v : v & ((1ull << bits) - 1);
+}
+
+__global__ void __launch_bounds__(kIndexThreads) k_index_unpack_scan(const IndexUnpackTask *__restrict__ tasks, int n) {
+    const uint32_t wave = blockIdx.x * kUnpackWaves + threadIdx.x / 64, lane = threadIdx.x & 63;
+    const IndexUnpackTask &T = tasks[unpack_task_of<&IndexUnpackTask::first_scan_wave>(tasks, n, wave)];
+    const uint32_t r = wave - T.first_scan_wave;
+    if (r >= T.walk * T.n_parts) return;
+    const uint32_t e = r / T.n_parts, j = r % T.n_parts;
+    const unsigned long long d = gp(T.desc)[r];
+    if (uint32_t(d >> 56) != kUnpackCoded) return;
+    const IndexUnpackPart P = T.part[j];
+    const uint32_t nb = ((P.bytes + P.unit - 1) / P.unit + 63) / 64;
+    const NB_GLOBAL uint8_t *widths = gp(T.packed) + size_t(d & kUnpackDescAt);
+    NB_GLOBAL uint32_t *offs = gp(T.offs) + size_t(e) * T.blocks + P.first_block;
+    uint32_t carry = nb;                                                // the payloads follow the width bytes
+    for (uint32_t b0 = 0; b0 < nb; b0 += 64) {
+        const uint32_t b = b0 + lane, v = b < nb ? 8u * widths[b] : 0u;
+        uint32_t incl = v;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const uint32_t t = uint32_t(__shfl_up(int(incl), s, 64));
+            if (int(lane) >= s) incl += t;
+        }
+        if (b < nb) offs[b] = carry + incl - v;
+        carry += uint32_t(__builtin_amdgcn_readlane(int(incl), 63));
+    }
+}
+
+__global__ void __launch_bounds__(kIndexThreads) k_index_unpack(const IndexUnpackTask *__restrict__ tasks, int n) {
+    const uint32_t wave = blockIdx.x * kUnpackWaves + threadIdx.x / 64, lane = threadIdx.x & 63;
+    const IndexUnpackTask &T = tasks[unpack_task_of<&IndexUnpackTask::first_wave>(tasks, n, wave)];
+    const uint32_t r = wave - T.first_wave;
+    if (r >= T.blocks) return;
+    uint32_t j = 0;
+    while (j + 1 < T.n_parts && T.part[j + 1].first_block <= r) j++;
+    const IndexUnpackPart P = T.part[j];
+    const uint32_t blk = r - P.first_block, u = blk * 64 + lane, units = (P.bytes + P.unit - 1) / P.unit, ubits = 8 * P.unit;
+    const bool active = u < units;
+    const uint32_t raw_bits = active ? min(ubits, 8u * (P.bytes - u * P.unit)) : 0u;       // (the last unit of a raw part may be short)
+    const uint64_t umask = ubits >= 64 ? ~0ull : (1ull << ubits) - 1;
+    const NB_GLOBAL uint8_t *packed = gp(T.packed);
+    const NB_GLOBAL unsigned long long *desc = gp(T.desc) + j;
+    const NB_GLOBAL uint32_t *offs = gp(T.offs) + r;
+    NB_GLOBAL uint8_t *out = gp(T.out) + P.out_at + size_t(u) * P.unit;
+    uint64_t run = unpack_initial(P.init, u);
+    for (uint32_t e = 0; e < T.walk; e++) {
+        const unsigned long long d = desc[size_t(e) * T.n_parts];
+        const uint32_t flag = uint32_t(d >> 56);
+        if (flag == kUnpackLeftOut) continue;                           // k_index_unpack_rank
+        const NB_GLOBAL uint8_t *data = packed + size_t(d & kUnpackDescAt);
+        uint64_t x;
+        if (flag == kUnpackRaw) {
+            x = load_bits_any(data + size_t(blk) * 64 * P.unit, lane * ubits, raw_bits);
+        } else {
+            const uint32_t b = data[blk];
+            const uint64_t v = load_bits_any(data + offs[size_t(e) * T.blocks], lane * b, active ? b : 0u);
+            const uint64_t z = (v >> 1) ^ (0ull - (v & 1));             // zig-zag undone
+            if (P.code == kUnpackDiff) x = (run + z) & umask;
+            else if (P.code == kUnpackXor) x = run ^ v;
+            else x = uint64_t(__double_as_longlong(double((long long)z)));
+        }
+        run = x;
+        if (!active || e < T.first_out) continue;
+        NB_GLOBAL uint8_t *o = out + size_t(e - T.first_out) * T.out_stride;
+        if (P.unit == 8) *(NB_GLOBAL uint64_t *)o = x;
+        else if (P.unit == 4) *(NB_GLOBAL uint32_t *)o = uint32_t(x);
+        else *(NB_GLOBAL uint16_t *)o = uint16_t(x);
+    }
+}
+
+__global__ void __launch_bounds__(kIndexThreads) k_index_unpack_rank(const IndexUnpackTask *__restrict__ tasks, int n) {
+    const IndexUnpackTask &T = tasks[unpack_task_of<&IndexUnpackTask::first_rank_group>(tasks, n, blockIdx.x)];
+    const uint32_t e = T.first_out + (blockIdx.x - T.first_rank_group);
+    if (e >= T.walk) return;
+    uint32_t j = 0;
+    while (j < T.n_parts && T.part[j].code != kUnpackCodeRank) j++;
+    if (j + 1 >= T.n_parts || uint32_t(gp(T.desc)[size_t(e) * T.n_parts + j] >> 56) != kUnpackLeftOut) return;
+    NB_GLOBAL uint8_t *body = gp(T.out) + size_t(e - T.first_out) * T.out_stride;
+    const NB_GLOBAL uint32_t *sym = (const NB_GLOBAL uint32_t *)(body + T.part[j + 1].out_at);
+    NB_GLOBAL u32x4 *rank = (NB_GLOBAL u32x4 *)(body + T.part[j].out_at);
+    for (uint32_t k = threadIdx.x; k < T.part[j].bytes / 16; k += kIndexThreads) rank[k] = rank_unit(sym, k);
+}
+
+bool index_unpack_scan_launch(const IndexUnpackTask *d_tasks, int n, uint32_t scan_waves, hipStream_t s) {
+    if (n <= 0 || scan_waves == 0) return true;
+    hipLaunchKernelGGL(k_index_unpack_scan, dim3((scan_waves + kUnpackWaves - 1) / kUnpackWaves), dim3(kIndexThreads), 0, s, d_tasks, n);
+    return hipGetLastError() == hipSuccess;
+}
+bool index_unpack_launch(const IndexUnpackTask *d_tasks, int n, uint32_t waves, uint32_t rank_groups, hipStream_t s) {
+    if (n <= 0 || waves == 0) return true;
+    hipLaunchKernelGGL(k_index_unpack, dim3((waves + kUnpackWaves - 1) / kUnpackWaves), dim3(kIndexThreads), 0, s, d_tasks, n);
+    if (hipGetLastError() != hipSuccess) return false;
+    if (rank_groups == 0) return true;
+    hipLaunchKernelGGL(k_index_unpack_rank, dim3(rank_groups), dim3(kIndexThreads), 0, s, d_tasks, n);
+    return hipGetLastError() == hipSuccess;
+}
+
 }  // namespace nblic
