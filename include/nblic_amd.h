@@ -652,6 +652,26 @@ int nblic_amd_debug_index_capture(nblic_amd_ctx *ctx, int kind, int effort, int 
                                   const unsigned char *rows, size_t rows_bytes, size_t plane_offset, unsigned char *body_out,
                                   size_t body_cap, int *end_row_out);
 
+/* Debug hook used by the packed index's device tests: ONE launch of k_index_unpack_scan and ONE unpack launch
+ * (k_index_unpack, then k_index_unpack_rank) over n packed indexes (1 .. 8) as n tasks, set up and placed in the launches as
+ * nblic_amd_decode_batch_indexed does it.  Index k is uploaded at byte base_offsets[k] (0 .. 4096) of a zeroed, larger
+ * buffer, so the caller chooses the residue of its address; its entries 0 .. walks[k] - 1 (0-based; 1 <= walk <= count) are
+ * walked and those from first_outs[k] (0 <= first_out < walk) on are stored, out_strides[k] bytes apart: each the entry's
+ * body without the QNBLIC tables, record | B | the row slot; the bytes between its end and the stride are not defined.
+ * outs[k] receives these (walk - first_out) x out_stride bytes and, behind them, the first 256 bytes of the patterned
+ * guard as they were read back; caps[k] must hold both.  The device buffer holds 0xA7 everywhere before the launch.
+ *
+ * The hook accepts EXACTLY what the kernels' memory safety rests on: the structural walk of the packed form (every length,
+ * flag, width byte and hash) and a sound index head.  It does NOT apply the checks nblic_amd_index_check makes on the
+ * values of the tables (counter ranges, re-mapper bytes, finite B, the QNBLIC tables): the tests feed the kernels packings
+ * of values those checks refuse -- full-range differences, NaN, rank bytes that are no inverse.  Nothing of its output is
+ * decoded from.
+ * Returns 0; -1, with nothing launched or allocated: a null pointer, n out of range, an index the walk or the head check
+ * refuses, walk or first_out out of range, a cap too small; -2 when a HIP call failed; -3 when a guard byte has changed. */
+int nblic_amd_debug_index_unpack(nblic_amd_ctx *ctx, int n, const void *const *packed, const size_t *packed_bytes,
+                                 const size_t *base_offsets, const int *walks, const int *first_outs,
+                                 unsigned char *const *outs, const size_t *caps, size_t *out_strides);
+
 /* Device self-test of the wave primitives the chain kernels rely on (DPP prefix sum against the
  * shuffle formulation).  Returns the number of mismatching lanes (0 = pass) or -1.           */
 int nblic_amd_selftest(nblic_amd_ctx *ctx);

@@ -49,7 +49,7 @@ EXPORTS = (
     "nblic_amd_encode_batch_indexed", "nblic_amd_index_bytes", "nblic_amd_indexed_batch_split",
     "nblic_amd_decode_batch_indexed", "nblic_amd_indexed_decode_split", "nblic_amd_indexed_decode_plan", "nblic_amd_debug_index_kernels",
     "nblic_amd_index_build_batch", "nblic_amd_index_build_split", "nblic_amd_index_build_plan", "nblic_amd_debug_index_capture",
-    "nblic_amd_index_pack", "nblic_amd_index_pack_bound", "nblic_amd_index_unpack", "nblic_amd_index_unpacked_bytes", "nblic_amd_index_is_packed",
+    "nblic_amd_index_pack", "nblic_amd_index_pack_bound", "nblic_amd_index_unpack", "nblic_amd_index_unpacked_bytes", "nblic_amd_index_is_packed", "nblic_amd_debug_index_unpack",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -228,6 +228,10 @@ def load_library() -> C.CDLL:
         lib.nblic_amd_index_unpacked_bytes.argtypes = [C.c_void_p, C.c_size_t]
         lib.nblic_amd_index_is_packed.restype = C.c_int
         lib.nblic_amd_index_is_packed.argtypes = [C.c_void_p, C.c_size_t]
+    if hasattr(lib, "nblic_amd_debug_index_unpack"):
+        vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
+        lib.nblic_amd_debug_index_unpack.restype = C.c_int
+        lib.nblic_amd_debug_index_unpack.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, ip, ip, vpp, szp, szp]
     if hasattr(lib, "nblic_amd_index_build_batch"):
         vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
         lib.nblic_amd_index_build_batch.restype = C.c_int
@@ -904,6 +908,40 @@ class Context:
         if final is not None:
             return int(verdict[0])
         return rec, stats[: 2 * b_b], rows[: 2 * w]
+
+    def debug_index_unpack(self, tasks):
+        """``nblic_amd_debug_index_unpack``: one scan launch and one unpack launch (k_index_unpack, k_index_unpack_rank)
+        over ``tasks = [(packed, base_offset, walk, first_out), ...]`` (1 .. 8 of them), each packed index uploaded at its
+        ``base_offset``.  Accepted is what the structural walk and the head check accept; the tables' values are not
+        looked at.  Returns per task ``(bodies, guard)``: ``bodies[e - first_out]`` is the ``out_stride`` bytes stored for
+        entry ``e`` (0-based), ``guard`` the 256 bytes behind the last one as read back (all 0xA7).  ``ValueError`` when
+        refused, ``DeviceCoderGuardError`` when a guard byte has changed."""
+        n = len(tasks)
+        xs = [_bytes_arg(t[0]) for t in tasks]
+        nothing = np.zeros(1, np.uint8)
+        caps = []
+        for x, (_, _, walk, first_out) in zip(xs, tasks):       # the stride is at most the body and 15; the library says what it is
+            kind, _, w, _, _, effort = (int(v) for v in np.frombuffer(x[12:36].tobytes(), "<i4")) if x.size >= 36 else (0,) * 6
+            body = (12352 if kind == 1 else 86080 + (1024 if effort == 3 else 512 if effort == 2 else 0) * max(min(w, 65535), 0)) + 2 * max(min(w, 65535), 0)
+            caps.append(max(min(int(walk) - int(first_out), 64), 1) * (body + 15) + 256)
+        outs = [np.zeros(cap, np.uint8) for cap in caps]
+        vp = lambda arrs: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else nothing.ctypes.data for a in arrs])
+        sz = lambda vals: (C.c_size_t * max(n, 1))(*[int(v) for v in vals])
+        iv = lambda vals: (C.c_int * max(n, 1))(*[int(v) for v in vals])
+        strides = (C.c_size_t * max(n, 1))()
+        rc = self.lib.nblic_amd_debug_index_unpack(self.handle, n, vp(xs), sz(x.size for x in xs), sz(t[1] for t in tasks), iv(t[2] for t in tasks),
+                                                   iv(t[3] for t in tasks), vp(outs), sz(caps), strides)
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_index_unpack refused its arguments")
+        if rc == -3:
+            raise DeviceCoderGuardError("nblic_amd_debug_index_unpack: a byte behind an output has changed")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_index_unpack failed (%d)" % rc)
+        res = []
+        for out, stride, (_, _, walk, first_out) in zip(outs, strides, tasks):
+            used = (int(walk) - int(first_out)) * int(stride)
+            res.append((out[:used].reshape(-1, int(stride)), out[used:used + 256]))
+        return res
 
     def set_index_round(self, segments: int):
         """At most ``segments`` segments per round of ``decode_indexed`` (``nblic_amd_set_index_round``); 0 = bounded by

@@ -3025,6 +3025,19 @@ static void idxdec_unpack_task(const IndexView &V, int walk, IndexUnpackTask &T,
         for (int j : parts) desc.push_back((unsigned long long)(P.ent[size_t(e)].part_at[j]) | ((unsigned long long)(P.ent[size_t(e)].part_flag[j]) << 56));
 }
 
+// A task's place in a launch: the waves and workgroups of the tasks in front of it (serial_engine.h first_*).  The scan launch
+// takes the task as idxdec_unpack_task made it; a round's launch the entries it stores, [first_out, walk), and where.
+static void idxdec_place_scan(IndexUnpackTask T, uint32_t &scan_waves, std::vector<IndexUnpackTask> &tasks) {
+    T.first_scan_wave = scan_waves; scan_waves += index_unpack_scan_waves(T);
+    tasks.push_back(T);
+}
+static void idxdec_place_round(IndexUnpackTask T, uint8_t *out, int walk, int first_out, uint32_t &waves, uint32_t &groups, std::vector<IndexUnpackTask> &tasks) {
+    T.out = out; T.walk = uint32_t(walk); T.first_out = uint32_t(first_out);
+    T.first_wave = waves; waves += index_unpack_waves(T);
+    T.first_rank_group = groups; groups += index_unpack_rank_groups(T);
+    tasks.push_back(T);
+}
+
 static bool idxdec_upload_tasks(std::vector<IndexTask> &tasks, bool seed, IndexTask *d_tasks, uint32_t &chunks, hipStream_t st) {
     chunks = 0;
     for (auto &t : tasks) { t.first_chunk = chunks; chunks += index_task_chunks(t, seed); }
@@ -3142,9 +3155,7 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
             if (!descs[i].empty() && hipMemcpyAsync(I->d_desc, descs[i].data(), descs[i].size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st) != hipSuccess) return fail("upload");
             I->unpack.packed = I->d_index; I->unpack.desc = I->d_desc; I->unpack.offs = I->d_offs;
             if (walk == 0) continue;
-            IndexUnpackTask T = I->unpack;
-            T.first_scan_wave = scan_waves; scan_waves += index_unpack_scan_waves(T);
-            unpacks.push_back(T);
+            idxdec_place_scan(I->unpack, scan_waves, unpacks);
         }
         if (!unpacks.empty() && (hipMemcpyAsync(d_unpacks, unpacks.data(), unpacks.size() * sizeof(IndexUnpackTask), hipMemcpyHostToDevice, st) != hipSuccess ||
                                  !index_unpack_scan_launch(d_unpacks, int(unpacks.size()), scan_waves, st))) return fail("launch");
@@ -3234,11 +3245,7 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
                 if (last >= first) {
                     I.d_unpacked = d_unpacked + at; I.unpacked_first = first;
                     at += up256(size_t(last - first + 1) * I.unpack.out_stride);
-                    IndexUnpackTask T = I.unpack;
-                    T.out = I.d_unpacked; T.walk = uint32_t(last); T.first_out = uint32_t(first - 1);
-                    T.first_wave = waves; waves += index_unpack_waves(T);
-                    T.first_rank_group = groups; groups += index_unpack_rank_groups(T);
-                    unpacks.push_back(T);
+                    idxdec_place_round(I.unpack, I.d_unpacked, last, first - 1, waves, groups, unpacks);
                 }
                 j = b;
             }
@@ -4232,6 +4239,86 @@ int nblic_amd_debug_index_capture(nblic_amd_ctx *c, int kind, int effort, int wi
         if (back[i] != 0) return -3;
     memcpy(body_out, back.data(), L.tab);
     *end_row_out = J.end_row;
+    return 0;
+}
+
+// ---- k_index_unpack_scan, k_index_unpack and k_index_unpack_rank on caller-made bytes (tests/test_index_unpack_kernels.py) --
+// ONE scan launch and ONE unpack launch (the rank kernel with it) over n packed indexes as n tasks, made by idxdec_unpack_task
+// and placed as decode_batch_indexed places them.  What is accepted is what the kernels' memory safety rests on -- packed_walk,
+// which has read every length, flag and width byte, and a sound head -- and NOT the table checks of packed_index_check: the
+// tests feed the kernels values those refuse.
+int nblic_amd_debug_index_unpack(nblic_amd_ctx *c, int n, const void *const *packed, const size_t *packed_bytes, const size_t *base_offsets,
+                                 const int *walks, const int *first_outs, unsigned char *const *outs, const size_t *caps, size_t *out_strides) {
+    constexpr int kMaxTasks = 8;
+    constexpr size_t kGuard = 256;
+    constexpr uint8_t kPattern = 0xA7;
+    if (!c || n < 1 || n > kMaxTasks || !packed || !packed_bytes || !base_offsets || !walks || !first_outs || !outs || !caps || !out_strides) return -1;
+    const size_t count = size_t(n);
+    std::vector<IndexView> views(count);
+    std::vector<IndexUnpackTask> made(count);
+    std::vector<std::vector<unsigned long long>> descs(count);
+    std::vector<size_t> used(count), out_at(count), index_at(count), desc_at(count), offs_at(count);
+    size_t out_bytes = 0, index_bytes = 0, desc_words = 0, offs_words = 0;
+    for (int k = 0; k < n; k++) {
+        IndexView &V = views[size_t(k)];
+        if (!packed[k] || !outs[k] || base_offsets[k] > 4096 || !packed_walk(packed[k], packed_bytes[k], V.P)) return -1;
+        memcpy(&V.H, packed[k], sizeof V.H);
+        if (!index_head_ok(V.H, c->max_px)) return -1;
+        V.packed = true;
+        V.L = record_layout(V.H.kind, V.H.w, V.H.effort);
+        if (V.P.body_bytes != V.L.bytes || walks[k] < 1 || walks[k] > V.H.count || first_outs[k] < 0 || first_outs[k] >= walks[k]) return -1;
+        idxdec_unpack_task(V, walks[k], made[size_t(k)], descs[size_t(k)]);
+        used[size_t(k)] = size_t(walks[k] - first_outs[k]) * made[size_t(k)].out_stride;
+        if (caps[k] < used[size_t(k)] + kGuard) return -1;
+        out_at[size_t(k)] = out_bytes; out_bytes += up256(used[size_t(k)]) + kGuard;
+        index_at[size_t(k)] = index_bytes; index_bytes += up256(base_offsets[k] + packed_bytes[k] + 16);      // (the kernels read whole aligned words)
+        desc_at[size_t(k)] = desc_words; desc_words += descs[size_t(k)].size();
+        offs_at[size_t(k)] = offs_words; offs_words += size_t(walks[k]) * made[size_t(k)].blocks;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    Stream st;
+    DevPool mem;
+    uint8_t *d_index = mem.make<uint8_t>(index_bytes), *d_out = mem.make<uint8_t>(out_bytes);
+    unsigned long long *d_desc = mem.make<unsigned long long>(desc_words);
+    uint32_t *d_offs = mem.make<uint32_t>(offs_words);
+    IndexUnpackTask *d_tasks = mem.make<IndexUnpackTask>(size_t(n));
+    if (!d_index || !d_out || !d_desc || !d_offs || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    std::vector<uint8_t> back(out_bytes);
+    const bool ok = [&]() -> bool {
+        HIP_OK(hipMemsetAsync(d_index, 0, index_bytes, st));
+        HIP_OK(hipMemsetAsync(d_offs, 0, offs_words * sizeof(uint32_t), st));
+        HIP_OK(hipMemsetAsync(d_out, kPattern, out_bytes, st));
+        std::vector<IndexUnpackTask> scans, rounds;
+        uint32_t scan_waves = 0, waves = 0, groups = 0;
+        for (int k = 0; k < n; k++) {
+            const size_t i = size_t(k);
+            IndexUnpackTask &T = made[i];
+            T.packed = d_index + index_at[i] + base_offsets[k]; T.desc = d_desc + desc_at[i]; T.offs = d_offs + offs_at[i];
+            HIP_OK(hipMemcpyAsync(d_index + index_at[i] + base_offsets[k], packed[k], packed_bytes[k], hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemcpyAsync(d_desc + desc_at[i], descs[i].data(), descs[i].size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+            idxdec_place_scan(T, scan_waves, scans);
+            idxdec_place_round(T, d_out + out_at[i], walks[k], first_outs[k], waves, groups, rounds);
+        }
+        HIP_OK(hipMemcpyAsync(d_tasks, scans.data(), scans.size() * sizeof(IndexUnpackTask), hipMemcpyHostToDevice, st));
+        if (!index_unpack_scan_launch(d_tasks, n, scan_waves, st)) return false;
+        HIP_OK(hipStreamSynchronize(st));                                // (the task array is reused)
+        HIP_OK(hipMemcpyAsync(d_tasks, rounds.data(), rounds.size() * sizeof(IndexUnpackTask), hipMemcpyHostToDevice, st));
+        if (!index_unpack_launch(d_tasks, n, waves, groups, st)) return false;
+        HIP_OK(hipMemcpyAsync(back.data(), d_out, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    if (!ok) return -2;
+    for (int k = 0; k < n; k++) {                                        // everything behind the stored entries is still the pattern
+        const size_t i = size_t(k), room = up256(used[i]) + kGuard;
+        for (size_t at = used[i]; at < room; at++)
+            if (back[out_at[i] + at] != kPattern) return -3;
+    }
+    for (int k = 0; k < n; k++) {
+        memcpy(outs[k], back.data() + out_at[size_t(k)], used[size_t(k)] + kGuard);
+        out_strides[k] = made[size_t(k)].out_stride;
+    }
     return 0;
 }
 
