@@ -324,9 +324,14 @@ void nblic_amd_dstream_end(nblic_amd_dstream *d);
  *                   entry: any difference refuses the result (-1, img zeroed: no unverified pixel is left there).  0 on
  *                   success.  Segments run in rounds of at most 1 GiB of per-segment state;
  *                   nblic_amd_set_index_round(ctx, n > 0) caps a round at n segments (0: the memory bound alone).
- *   decode_rows     rows [row0, row1) alone into out (cap >= (row1 - row0) x width), from the last entry at or above row0;
- *                   nothing else is written.  0 / -1.
- * Each call has a HIP stream and a workspace of its own, so it can run next to batches and band coders of its context. */
+ *   decode_rows     rows [row0, row1) alone into out (cap >= (row1 - row0) x width): the segments row0 / R .. (row1 - 1) / R
+ *                   side by side, the first from the last entry at or above row0, and every entry strictly inside the
+ *                   range compared with the end of the segment in front of it as decode_indexed compares them (-1, the
+ *                   (row1 - row0) x width bytes zeroed).  Nothing else is written.  0 / -1.
+ * Both are nblic_amd_decode_batch_indexed (below) with one image: its host check, its rules for a refused image (-1, nothing
+ * launched, the buffer untouched) and its verification on the device are theirs, and a context without a usable device
+ * refuses them.  Each call has a HIP stream and a workspace of its own, so it can run next to batches and band coders of
+ * its context. */
 void nblic_amd_set_index_round(nblic_amd_ctx *ctx, int segments);
 int nblic_amd_index_check(nblic_amd_ctx *ctx, const void *index, size_t index_bytes, const unsigned char *stream, size_t stream_bytes);
 long nblic_amd_index_build(nblic_amd_ctx *ctx, const unsigned char *stream, size_t stream_bytes, int every_rows, unsigned char *out, size_t cap);
@@ -337,10 +342,10 @@ int nblic_amd_decode_rows(nblic_amd_ctx *ctx, const unsigned char *stream, size_
 
 /* PACKED SEEK INDEX: the same information as a seek index, delta-coded entry against entry and bit-packed (magic
  * "NBLSIDXP"; the format: DESIGN.md section 6).  It converts to and from the index byte for byte, and every function that
- * READS an index takes either form: index_check, decode_indexed, decode_rows (both unpack on the host) and
- * decode_batch_indexed (packed and unpacked indexes in any mix; a packed one is checked in its packed form and expanded on
- * the device only).  Everything that WRITES an index writes the unpacked form; packing is one host call on the result.
- * All five are host only and need no context.
+ * READS an index takes either form: index_check, decode_indexed, decode_rows and decode_batch_indexed (packed and
+ * unpacked indexes in any mix; a packed one is checked in its packed form, as index_check checks it, and expanded on the
+ * device only; the seals of the unpacked form it stores are re-derived by index_unpack alone).  Everything that WRITES an
+ * index writes the unpacked form; packing is one host call on the result.  All five are host only and need no context.
  *   index_pack         `index` (one nblic_amd_index_check accepts) as a packed index into out.  Returns its size -- written
  *                      only when cap is large enough (nblic_amd_index_pack_bound is) -- or -1: an index the check refuses.
  *   index_pack_bound   no packed form of `index` (its head is read) is larger: its own size + 32 + 33 per entry.  0: not an
@@ -407,7 +412,7 @@ long nblic_amd_indexed_batch_split(nblic_amd_ctx *ctx, double ms[5]);
  *   rounds          at most 1 GiB of per-segment state per round, and nblic_amd_set_index_round(ctx, n) caps a round at n
  *                   segments here too.  Within an image a higher segment never runs in a later round than a lower one.
  *   verification    every inner boundary of an image is checked ON THE DEVICE: the segment's final record, B and last two
- *                   rows against the next entry, as nblic_amd_decode_indexed compares them on the host.  The last segment of
+ *                   rows against the next entry (k_index_chain, has the fields).  The last segment of
  *                   a whole plane must end the image, that of a range must stand in front of row1.  Only one word per
  *                   boundary and one 64-byte header per image are read back.
  *   per image       status[k] = 0, or -1: the host check refused it, a row range outside 0 <= row0 < row1 <= height,

@@ -270,7 +270,7 @@ struct nblic_amd_ctx {
     Stream dec_stream, dec_stream2;                                    // decode_batch alternates its chunks between the two
     DevBuf<uint8_t> dec_arena;
     DevBuf<SerialJob> dec_jobs;
-    int index_round_segments = 0;         // > 0: at most this many segments per round of decode_indexed (nblic_amd_set_index_round)
+    int index_round_segments = 0;         // > 0: at most this many segments per round of the indexed decode (nblic_amd_set_index_round)
     int serial_rows = 0;                  // rows per launch of the serial kernels; 0 = sized for a few seconds per launch (nblic_amd_set_serial_rows)
     DevBuf<unsigned long long> d_redo;          // device: pixels whose least-squares system 0 / 1 was redone with integers (SerialJob::redo of every job of the context)
     double idx_split[5] = {0}; long idx_steps = 0;   // the last indexed batch, summed over its group steps: front, totals read-back, back half + entry records, copies (GPU ms); coder wait (host ms).  Guarded by stat_m
@@ -2467,212 +2467,6 @@ static size_t stream_index(nblic_amd_stream *s, void *buf, size_t cap) {
     return need;
 }
 
-// One indexed decode call: the checked index, the described stream, and the device side -- its own HIP stream and
-// buffers (mem), released on every path out: the stream synchronised, then the buffers, then the stream.
-struct IndexedRun {
-    IndexView V;
-    std::vector<uint8_t> unpacked;     // a packed index is unpacked here, on the host, and V is a view of this
-    DecodeItem it{};
-    std::vector<uint8_t> qtab;
-    size_t slen = 0;
-    int rows = 0;                      // rows per launch
-    unsigned long long *redo = nullptr; // the context's redo counters (SerialJob::redo)
-    Stream st;
-    DevPool mem;
-    uint8_t *d_tab = nullptr;          // QNBLIC tables
-    ~IndexedRun() { if (st) hipStreamSynchronize(st); }
-};
-
-// The host half of an indexed decode: the index against the stream, the stream's description.  false: refused.
-static bool indexed_check(IndexedRun &run, nblic_amd_ctx *c, const unsigned char *stream, size_t slen, const void *idx, size_t ilen) {
-    if (!c || !stream) return false;
-    if (index_is_packed(idx, ilen)) {                                    // one image: unpacked on the host, then as ever
-        if (!unpack_index(idx, ilen, run.unpacked)) return false;
-        idx = run.unpacked.data(); ilen = run.unpacked.size();
-    }
-    if (index_check(idx, ilen, stream, slen, c->max_px, run.V) != 0) return false;
-    run.it = DecodeItem{0, 0, 0, 0, 0, 0, 0, 0, -1, -1};
-    if (describe_stream(stream, slen, false, c->max_px, run.it, run.qtab) != Described::ok) return false;
-    run.slen = slen;
-    run.rows = rows_per_launch(run.it, c->serial_rows);
-    run.redo = c->d_redo;
-    return true;
-}
-
-// The device half: the call's HIP stream, and the QNBLIC tables on the device.
-static bool indexed_begin(IndexedRun &run, nblic_amd_ctx *c) {
-    if (hipSetDevice(c->device) != hipSuccess) return false;
-    if (run.st.create(hipStreamNonBlocking) != hipSuccess) return false;
-    if (!run.it.kind) return true;
-    run.d_tab = run.mem.make<uint8_t>(kQTab);
-    return run.d_tab && hipMemcpyAsync(run.d_tab, run.qtab.data(), kQTab, hipMemcpyHostToDevice, run.st) == hipSuccess;
-}
-
-// Segment k of an indexed decode, set up on run.st: its job, the record it starts from -- the stream's start (k = 0) or
-// entry k, staged in `stage` (L.b host bytes that live until run.st is synchronised) -- zeroed statistics, and from
-// entry k its B and the two rows above row kR into the plane `recon` (recon_row0: the image row at its index 0).
-static bool segment_start(IndexedRun &run, int k, uint8_t *d_rec, double *d_stats, uint8_t *recon, int recon_row0, const uint8_t *d_stream,
-                          unsigned long long stream_off, int end_row, uint8_t *stage, SerialJob &J) {
-    const RecordLayout &L = run.V.L;
-    SerialState S{};
-    if (k > 0) {
-        memcpy(stage, run.V.body(k), L.b);
-        memcpy(&S, stage, sizeof S);
-    } else {
-        memset(stage, 0, L.b);
-        S.pos = first_pos(run.it);
-    }
-    S.status = kRunning; S.avail = run.slen; S.final_ = 1;               // the whole stream is in device memory
-    memcpy(stage, &S, sizeof S);
-    J = decode_job(run.it, recon, recon_row0, d_stream, stream_off, reinterpret_cast<SerialState *>(d_rec), d_stats, run.d_tab, run.rows, end_row, run.redo);
-    bool ok = hipMemcpyAsync(d_rec, stage, L.b, hipMemcpyHostToDevice, run.st) == hipSuccess;
-    if (d_stats) ok = ok && hipMemsetAsync(d_stats, 0, 2 * L.b_bytes, run.st) == hipSuccess;
-    if (k > 0) {
-        const uint8_t *E = run.V.body(k);
-        if (d_stats) ok = ok && hipMemcpyAsync(d_stats, E + L.b, L.b_bytes, hipMemcpyHostToDevice, run.st) == hipSuccess;
-        ok = ok && rows_above_in(recon, recon_row0, E + L.rows, k * run.V.H.every_rows, run.it.w, run.st);
-    }
-    return ok;
-}
-
-// Segment k of an indexed decode ends in front of entry k + 1's row; its final record, B and rows must be that entry.
-// The record's header fields and tables are compared except the rank -> symbol words (kRecRank): the lean decoder never
-// writes them back, and dstream_check has verified that the entry's are the inverse of its sym_at, which IS compared.
-static bool chain_matches(const IndexView &V, int k, const uint8_t *rec, const uint8_t *b, const uint8_t *plane) {
-    const uint8_t *E = V.body(k + 1);
-    SerialState got, want;
-    memcpy(&got, rec, sizeof got); memcpy(&want, E, sizeof want);
-    if (got.status != kRunning || got.next_row != want.next_row || got.pos != want.pos || got.lo != want.lo || got.bias != want.bias) return false;
-    if (V.H.kind == 0 && (got.hi != want.hi || got.window != want.window)) return false;
-    const uint8_t *tg = rec + sizeof(SerialState), *tw = E + sizeof(SerialState);
-    const size_t tab = V.L.b - sizeof(SerialState);
-    if (V.H.kind == 0) {
-        const size_t rank0 = size_t(kRecRank) * 4, sym0 = size_t(kRecSym) * 4;
-        if (memcmp(tg, tw, rank0) != 0 || memcmp(tg + sym0, tw + sym0, tab - sym0) != 0) return false;
-    } else if (memcmp(tg, tw, tab) != 0) {
-        return false;
-    }
-    if (V.L.b_bytes && memcmp(b, E + V.L.b, V.L.b_bytes) != 0) return false;
-    const size_t w = size_t(V.H.w);
-    const RowsAbove A = rows_above(want.next_row, V.H.w);
-    return memcmp(plane + size_t(A.first) * w, E + V.L.rows + A.at, size_t(A.n) * w) == 0;
-}
-
-constexpr size_t kIndexedRoundBytes = size_t(1) << 30;   // device memory of one round's per-segment records and statistics
-
-// Every segment of the image side by side, one wave each (serial_decode_launch with whole streams: more segments than
-// CUs take the lean image), in rounds that bound the per-segment memory; the plane is copied out once, then the chain
-// check (chain_matches) refuses the result on any difference.  0 / -1.
-static int decode_indexed(nblic_amd_ctx *c, const unsigned char *stream, size_t slen, const void *idx, size_t ilen, unsigned char *img, size_t img_cap) {
-    IndexedRun run;
-    if (!img || !indexed_check(run, c, stream, slen, idx, ilen)) return -1;
-    const DecodeItem &it = run.it;
-    const RecordLayout &L = run.V.L;
-    const size_t plane_bytes = size_t(it.h) * size_t(it.w);
-    if (img_cap < plane_bytes) return -1;
-    auto fail = [&](const char *what) { fprintf(stderr, "[nblic_amd] indexed decode: %s\n", what); return -1; };
-    if (!indexed_begin(run, c)) return fail("cannot set up the workspace");
-    const int R = run.V.H.every_rows, nseg = run.V.H.count + 1;
-    const size_t rec_bytes = up256(L.b), stats_bytes = 2 * L.b_bytes;
-    const size_t per_seg = rec_bytes + up256(stats_bytes);
-    int per_round = int(std::max<size_t>(1, std::min<size_t>(size_t(nseg), kIndexedRoundBytes / per_seg)));
-    if (c->index_round_segments > 0) per_round = std::min(per_round, c->index_round_segments);
-    uint8_t *d_stream = run.mem.make<uint8_t>(stream_buf_bytes(slen)), *d_plane = run.mem.make<uint8_t>(plane_bytes);
-    uint8_t *d_recs = run.mem.make<uint8_t>(size_t(per_round) * per_seg);
-    SerialJob *d_jobs = run.mem.make<SerialJob>(size_t(per_round));
-    if (!d_stream || !d_plane || !d_recs || !d_jobs) return fail("cannot allocate the workspace");
-    const hipStream_t st = run.st;
-    if (!upload_stream(d_stream, stream, slen, st)) return fail("upload");
-    std::vector<uint8_t> host_recs(size_t(nseg) * L.b), host_b(size_t(nseg) * L.b_bytes), stage(size_t(per_round) * L.b);
-    std::vector<SerialJob> jobs(static_cast<size_t>(per_round));
-    long launches_total = 0;
-    // rounds from the last segments to the first: the rows above a segment (from its entry) are written into the plane
-    // before the segment that owns them decodes, so every row of the plane ends as its own segment decoded it
-    for (int s1 = nseg; s1 > 0;) {
-        const int s0 = std::max(0, s1 - per_round), n = s1 - s0;
-        int launches = 1;
-        for (int k = s0; k < s1; k++) {
-            const int j = k - s0, r1 = k + 1 < nseg ? (k + 1) * R : it.h;
-            uint8_t *rec = d_recs + size_t(j) * per_seg;
-            double *stats = stats_bytes ? reinterpret_cast<double *>(rec + rec_bytes) : nullptr;
-            if (!segment_start(run, k, rec, stats, d_plane, 0, d_stream, 0, r1 < it.h ? r1 : 0, stage.data() + size_t(j) * L.b, jobs[size_t(j)]))
-                return fail("upload");
-            launches = std::max(launches, serial_launches(r1 - k * R, run.rows));
-        }
-        if (hipMemcpyAsync(d_jobs, jobs.data(), size_t(n) * sizeof(SerialJob), hipMemcpyHostToDevice, st) != hipSuccess) return fail("upload");
-        for (int l = 0; l < launches; l++)
-            if (!decode_launch(it, d_jobs, jobs.data(), n, st, true)) return fail("launch");
-        launches_total += launches;
-        for (int k = s0; k < s1; k++) {
-            const uint8_t *rec = d_recs + size_t(k - s0) * per_seg;
-            bool ok = hipMemcpyAsync(host_recs.data() + size_t(k) * L.b, rec, L.b, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (L.b_bytes) ok = ok && hipMemcpyAsync(host_b.data() + size_t(k) * L.b_bytes, rec + rec_bytes, L.b_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
-            if (!ok) return fail("state");
-        }
-        if (hipStreamSynchronize(st) != hipSuccess) return fail("a round");       // `stage` and `jobs` are reused by the next round
-        s1 = s0;
-    }
-    { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count += launches_total; }
-    if (hipMemcpyAsync(img, d_plane, plane_bytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-        memset(img, 0, plane_bytes);
-        return fail("plane");
-    }
-    for (int k = 0; k < nseg; k++) {
-        const uint8_t *rec = host_recs.data() + size_t(k) * L.b;
-        if (k + 1 == nseg) {
-            SerialState S;
-            memcpy(&S, rec, sizeof S);
-            if (S.status != kDone) { memset(img, 0, plane_bytes); return fail("the stream is damaged or ends too early"); }
-        } else if (!chain_matches(run.V, k, rec, host_b.data() + size_t(k) * L.b_bytes, img)) {
-            memset(img, 0, plane_bytes);                                 // nothing unverified is left in the caller's buffer
-            return fail("a segment does not end where the next entry starts (index and stream disagree)");
-        }
-    }
-    return 0;
-}
-
-// Rows [row0, row1) alone: the one segment from the last entry at or before row0 (the stream's start for row0 < R), fed
-// from the entry's feed_from, ending in front of row1.  Writes only out[0, (row1 - row0) w).  0 / -1.
-static int decode_rows(nblic_amd_ctx *c, const unsigned char *stream, size_t slen, const void *idx, size_t ilen, int row0, int row1,
-                       unsigned char *out, size_t cap) {
-    IndexedRun run;
-    if (!out || !indexed_check(run, c, stream, slen, idx, ilen)) return -1;
-    const DecodeItem &it = run.it;
-    if (row0 < 0 || row1 <= row0 || row1 > it.h) return -1;
-    const size_t w = size_t(it.w);
-    if (cap < size_t(row1 - row0) * w) return -1;
-    auto fail = [&](const char *what) { fprintf(stderr, "[nblic_amd] row-range decode: %s\n", what); return -1; };
-    if (!indexed_begin(run, c)) return fail("cannot set up the workspace");
-    const int k = row0 / run.V.H.every_rows, r0 = k * run.V.H.every_rows, base = std::max(0, r0 - 2);
-    unsigned long long off = 0;
-    if (k > 0) {                                                         // <= slen (index_check)
-        DecodeCheckpoint E;
-        memcpy(&E, run.V.ent[size_t(k - 1)], sizeof E);
-        off = E.feed_from;
-    }
-    const size_t win = size_t(slen - off), stats_bytes = 2 * run.V.L.b_bytes;
-    uint8_t *d_win = run.mem.make<uint8_t>(stream_buf_bytes(win)), *d_rows = run.mem.make<uint8_t>(size_t(row1 - base) * w);
-    uint8_t *d_rec = run.mem.make<uint8_t>(up256(run.V.L.b));
-    double *d_stats = stats_bytes ? run.mem.make<double>(stats_bytes / sizeof(double)) : nullptr;
-    SerialJob *d_job = run.mem.make<SerialJob>(1);
-    if (!d_win || !d_rows || !d_rec || !d_job || (stats_bytes && !d_stats)) return fail("cannot allocate the workspace");
-    const hipStream_t st = run.st;
-    std::vector<uint8_t> stage(run.V.L.b);
-    SerialJob J;
-    if (!upload_stream(d_win, stream + off, win, st) || !segment_start(run, k, d_rec, d_stats, d_rows, base, d_win, off, row1 < it.h ? row1 : 0, stage.data(), J) ||
-        hipMemcpyAsync(d_job, &J, sizeof J, hipMemcpyHostToDevice, st) != hipSuccess) return fail("upload");
-    const int launches = serial_launches(row1 - r0, J.rows);
-    for (int l = 0; l < launches; l++)
-        if (!decode_launch(it, d_job, &J, 1, st, false)) return fail("launch");
-    { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count += launches; }
-    SerialState S;
-    if (hipMemcpyAsync(&S, d_rec, sizeof S, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail("state");
-    if (row1 == it.h ? S.status != kDone : (S.status != kRunning || S.next_row != row1)) return fail("the stream is damaged or ends too early");
-    if (hipMemcpyAsync(out, d_rows + size_t(row0 - base) * w, size_t(row1 - row0) * w, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) return fail("rows");
-    return 0;
-}
-
 // ---- default context behind the drop-in entry points ---------------------------------------
 // ---- the INDEXED BATCH: many -n0 -e1 images and their seek indexes, a group of images stepped through row bands together ----
 // What the band encoder does for one image per object (staged front, an entry record at every entry row), done for a
@@ -2979,13 +2773,16 @@ static int encode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
 }
 
 // ---- the INDEXED BATCH DECODE: the segments and row ranges of many streams in one call ----------------------------------
-// What decode_indexed and decode_rows do for one stream per call, for many: the host checks run on worker threads, every
-// accepted image's stream (or, for a row range, its tail from the first entry's feed_from) and its index go up ONCE, the
-// index verbatim, and all segments of all images form one job list (indexed_decode_plan: rounds that bound the per-segment
-// memory, classes that share a launch).  A round's segments are set up by k_index_seed straight from the uploaded index and
-// their final records and B are compared with the next entries by k_index_chain before the round's buffers are reused; the
-// rows part of that comparison runs once, after the last round -- at R = 1 the two rows above an entry belong to two
-// segments that may run in different rounds.  Only the verdict words and one SerialState per image come back.
+// The one indexed decode (nblic_amd_decode_indexed and nblic_amd_decode_rows are calls of it with one image): the host
+// checks run on worker threads (one image: on the calling thread), every accepted image's stream (or, for a row range, its tail from the first entry's
+// feed_from) and its index go up ONCE, the index verbatim, and all segments of all images form one job list
+// (indexed_decode_plan: rounds that bound the per-segment memory, classes that share a launch; more segments than CUs take
+// the lean image).  A round's segments are set up by k_index_seed straight from the uploaded index and their final records
+// and B are compared with the next entries by k_index_chain before the round's buffers are reused; the rows part of that
+// comparison runs once, after the last round -- at R = 1 the two rows above an entry belong to two segments that may run
+// in different rounds.  Only the verdict words and one SerialState per image come back.
+constexpr size_t kIndexedRoundBytes = size_t(1) << 30;   // device memory of one round's per-segment records and statistics
+
 struct IdxDecImage {
     int k = 0;                          // the caller's image
     bool ok = false;
@@ -3057,20 +2854,21 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
     auto t0 = Clock::now();
     // the host half: index against stream, the stream's description -- nothing of an image goes up before it has passed
     std::vector<IdxDecImage> all{size_t(n)};
-    {
+    auto host_check = [&](int k) {
+        IdxDecImage &I = all[size_t(k)];
+        I.k = k;
+        I.it = DecodeItem{k, 0, 0, 0, 0, 0, 0, 0, -1, -1};
+        I.ok = index_check(indexes[k], ilens[k], streams[k], slens[k], c->max_px, I.V) == 0 &&
+               describe_stream(streams[k], slens[k], false, c->max_px, I.it, I.qtab) == Described::ok;
+    };
+    if (n == 1) {
+        host_check(0);                                                   // (the single calls: no thread is worth starting for one image)
+    } else {
         IdxPool pool;
         IdxPendingTasks pending;
         pending.add(n);
         pool.start(std::max(1, std::min(n, c->coders_wanted)));
-        for (int k = 0; k < n; k++)
-            pool.post([&, k] {
-                IdxDecImage &I = all[size_t(k)];
-                I.k = k;
-                I.it = DecodeItem{k, 0, 0, 0, 0, 0, 0, 0, -1, -1};
-                I.ok = index_check(indexes[k], ilens[k], streams[k], slens[k], c->max_px, I.V) == 0 &&
-                       describe_stream(streams[k], slens[k], false, c->max_px, I.it, I.qtab) == Described::ok;
-                pending.done();
-            });
+        for (int k = 0; k < n; k++) pool.post([&, k] { host_check(k); pending.done(); });
         pending.wait();
     }
     split[0] = ms_since(t0);
@@ -3119,7 +2917,10 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
     t0 = Clock::now();
     size_t n_bounds = 0;
     for (IdxDecImage *I : live) n_bounds += size_t(I->seg1 - I->seg0);
-    uint32_t *d_verdicts = mem.make<uint32_t>(std::max<size_t>(1, n_bounds));
+    // (device blocks are carved out of few allocations, every part at a multiple of 256 bytes: a call with one image makes three)
+    const size_t verdict_bytes = up256(std::max<size_t>(1, n_bounds) * sizeof(uint32_t));
+    uint8_t *d_call = mem.make<uint8_t>(verdict_bytes + live.size() * sizeof(IndexUnpackTask));
+    uint32_t *d_verdicts = reinterpret_cast<uint32_t *>(d_call);
     if (!d_verdicts || hipMemsetAsync(d_verdicts, 0, std::max<size_t>(1, n_bounds) * sizeof(uint32_t), st) != hipSuccess) return fail("cannot allocate the workspace");
     {
         size_t at = 0;
@@ -3127,11 +2928,13 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
             const DecodeItem &it = I->it;
             const size_t win = size_t(it.len - I->stream_off), ilen = ilens[I->k];
             I->d_verdict = d_verdicts + at; at += size_t(I->seg1 - I->seg0);
-            I->d_stream = mem.make<uint8_t>(stream_buf_bytes(win));
-            I->d_index = mem.make<uint8_t>(up256(ilen + 16));               // (the kernels read whole aligned words around an entry)
-            I->d_plane = mem.make<uint8_t>(size_t(I->row1 - I->base) * size_t(it.w));
-            if (it.kind) I->d_tab = mem.make<uint8_t>(kQTab);
-            if (!I->d_stream || !I->d_index || !I->d_plane || (it.kind && !I->d_tab)) return fail("cannot allocate the workspace");
+            const size_t index_bytes = up256(ilen + 16);                    // (the kernels read whole aligned words around an entry)
+            const size_t plane_bytes = up256(size_t(I->row1 - I->base) * size_t(it.w));
+            I->d_stream = mem.make<uint8_t>(stream_buf_bytes(win) + index_bytes + plane_bytes + (it.kind ? kQTab : 0));
+            if (!I->d_stream) return fail("cannot allocate the workspace");
+            I->d_index = I->d_stream + stream_buf_bytes(win);
+            I->d_plane = I->d_index + index_bytes;
+            if (it.kind) I->d_tab = I->d_plane + plane_bytes;
             if (!upload_stream(I->d_stream, streams[I->k] + I->stream_off, win, st) ||
                 hipMemcpyAsync(I->d_index, indexes[I->k], ilen, hipMemcpyHostToDevice, st) != hipSuccess ||
                 (it.kind && hipMemcpyAsync(I->d_tab, I->qtab.data(), kQTab, hipMemcpyHostToDevice, st) != hipSuccess)) return fail("upload");
@@ -3140,8 +2943,7 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
     // the packed indexes among them: where their parts lie, and every block's payload offset (one scan launch for the call)
     std::vector<std::vector<unsigned long long>> descs(live.size());
     std::vector<IndexUnpackTask> unpacks;
-    IndexUnpackTask *d_unpacks = mem.make<IndexUnpackTask>(live.size());
-    if (!d_unpacks) return fail("cannot allocate the workspace");
+    IndexUnpackTask *d_unpacks = reinterpret_cast<IndexUnpackTask *>(d_call + verdict_bytes);
     {
         uint32_t scan_waves = 0;
         for (size_t i = 0; i < live.size(); i++) {
@@ -3187,12 +2989,14 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
         unpacked_max = std::max(unpacked_max, unpacked);
         jobs_max = std::max(jobs_max, round_begin[size_t(r) + 1] - round_begin[size_t(r)]);
     }
-    uint8_t *d_recs = mem.make<uint8_t>(rec_bytes_max);
-    SerialJob *d_jobs = mem.make<SerialJob>(jobs_max);
-    IndexTask *d_tasks = mem.make<IndexTask>(std::max(jobs_max, n_bounds));
-    IndexTask *d_tasks2 = mem.make<IndexTask>(jobs_max);
-    uint8_t *d_unpacked = mem.make<uint8_t>(std::max<size_t>(1, unpacked_max));
-    if (!d_recs || !d_jobs || !d_tasks || !d_tasks2 || !d_unpacked) return fail("cannot allocate the workspace");
+    const size_t round_part[5] = {up256(rec_bytes_max), up256(jobs_max * sizeof(SerialJob)), up256(std::max(jobs_max, n_bounds) * sizeof(IndexTask)),
+                                  up256(jobs_max * sizeof(IndexTask)), up256(unpacked_max)};
+    uint8_t *d_recs = mem.make<uint8_t>(round_part[0] + round_part[1] + round_part[2] + round_part[3] + round_part[4]);
+    if (!d_recs) return fail("cannot allocate the workspace");
+    SerialJob *d_jobs = reinterpret_cast<SerialJob *>(d_recs + round_part[0]);
+    IndexTask *d_tasks = reinterpret_cast<IndexTask *>(d_recs + round_part[0] + round_part[1]);
+    IndexTask *d_tasks2 = reinterpret_cast<IndexTask *>(d_recs + round_part[0] + round_part[1] + round_part[2]);
+    uint8_t *d_unpacked = d_recs + round_part[0] + round_part[1] + round_part[2] + round_part[3];
     if (hipStreamSynchronize(st) != hipSuccess) return fail("upload");
     split[1] = ms_since(t0);
     t0 = Clock::now();
@@ -4585,7 +4389,8 @@ long nblic_amd_indexed_batch_split(nblic_amd_ctx *c, double ms[5]) {
 }
 int nblic_amd_decode_indexed(nblic_amd_ctx *c, const unsigned char *stream, size_t stream_bytes, const void *index, size_t index_bytes,
                              unsigned char *img, size_t img_cap) {
-    return decode_indexed(c, stream, stream_bytes, index, index_bytes, img, img_cap);
+    int h, w, near, effort, status;                                      // one image of the batch call, the whole plane
+    return decode_batch_indexed(c, 1, &stream, &stream_bytes, &index, &index_bytes, nullptr, nullptr, &img, &img_cap, &h, &w, &near, &effort, &status);
 }
 int nblic_amd_decode_batch_indexed(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
                                    const void *const *indexes, const size_t *index_lens, const int *row0, const int *row1,
@@ -4647,7 +4452,8 @@ long nblic_amd_index_build_plan(int n_images, const int *kinds, const int *effor
 }
 int nblic_amd_decode_rows(nblic_amd_ctx *c, const unsigned char *stream, size_t stream_bytes, const void *index, size_t index_bytes, int row0,
                           int row1, unsigned char *out, size_t cap) {
-    return decode_rows(c, stream, stream_bytes, index, index_bytes, row0, row1, out, cap);
+    int h, w, near, effort, status;                                      // one image of the batch call, one range
+    return decode_batch_indexed(c, 1, &stream, &stream_bytes, &index, &index_bytes, &row0, &row1, &out, &cap, &h, &w, &near, &effort, &status);
 }
 
 int nblic_amd_set_device_coder(nblic_amd_ctx *c, int n_packs, int min_outstanding) {

@@ -119,10 +119,13 @@ bool serial_qdecode_launch(const SerialJob *d_jobs, const SerialJob *h_jobs, int
 //   k_index_seed   one task per segment: the record the segment starts from (the entry's, or zeros with pos = first_pos
 //                  for segment 0; status kRunning, avail, final_ = 1), B into the first half of [B | F], zeros into F, and
 //                  the rows above into the plane.
-//   k_index_chain  one task per inner boundary: the segment's final record, B and plane rows against the next entry, as
-//                  the host's chain check compares them -- for NBLIC without the words [kRecRank, kRecSym), which the
-//                  lean decoder never writes back, and with hi and window.  A part that differs ORs its bit into the
-//                  boundary's verdict word (kChainRecord / kChainB / kChainRows); a part whose byte count is 0 is skipped.
+//   k_index_chain  one task per inner boundary: the segment's final record, B and plane rows against the next entry.  Of the
+//                  record's header next_row, pos, lo and bias must be the entry's and status kRunning (NBLIC: hi and window
+//                  too; QNBLIC keeps its state in lo alone); avail, final_ and the padding are the host's and skipped.  The
+//                  tables must be the entry's, for NBLIC without the words [kRecRank, kRecSym): the lean decoder never
+//                  writes them back, and the index check has verified that the entry's are the inverse of its rank ->
+//                  symbol bytes, which ARE compared.  A part that differs ORs its bit into the boundary's verdict word
+//                  (kChainRecord / kChainB / kChainRows); a part whose byte count is 0 is skipped.
 struct IndexTask {
     const uint8_t *entry;                  // the entry's body inside the uploaded index; seed: null = segment 0
     uint8_t *rec;                          // the segment's state record

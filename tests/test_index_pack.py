@@ -109,8 +109,8 @@ def test_row_ranges_and_rounds_that_start_above_segment_0(gpu_ctx, pkg, oracle):
             last = ((h - 1) // R) * R                                          # the last segment's first row
             mid = ((h - 1) // R // 2) * R
             for r in ((0, 1), (1, min(h, 2 * R + 1)), (mid, mid + 1), (mid - 1, min(h, mid + R + 1)), (last, h), (last - 1, h), (0, h)):
-                pairs.append((s, p)); rows.append(r); want.append(gpu_ctx.decode_rows(s, ix, *r))
-                assert np.array_equal(want[-1], rec[r[0]:r[1]])
+                pairs.append((s, p)); rows.append(r); want.append(rec[r[0]:r[1]])          # the oracle's rows
+                assert np.array_equal(gpu_ctx.decode_rows(s, ix, *r), want[-1])
     gpu_ctx.set_index_round(3)                                                 # rounds start at s0 > 0: the walk from entry 0 stores from s0 on
     try:
         with _live(pkg):

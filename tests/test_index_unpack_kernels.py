@@ -182,8 +182,8 @@ def test_public_calls_take_non_canonical_packings(gpu_ctx, pkg, oracle, packing)
     for key in keys:
         s, ix, rec = made[key]
         for r in _ranges(key[1][0], key[1][2]):
-            pairs.append((s, packed[key])); rows.append(r); want.append(gpu_ctx.decode_rows(s, ix, *r))
-            assert np.array_equal(want[-1], rec[r[0]:r[1]]), (key, r)
+            pairs.append((s, packed[key])); rows.append(r); want.append(rec[r[0]:r[1]])              # the oracle's rows
+            assert np.array_equal(gpu_ctx.decode_rows(s, ix, *r), want[-1]), (key, r)
     mixed = []
     for k, key in enumerate(keys):                                             # non-canonical, canonical and unpacked in one call
         s, ix, _ = made[key]

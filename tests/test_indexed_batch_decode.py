@@ -84,8 +84,8 @@ def test_mixed_batch_matches_the_oracle(gpu_ctx, pkg, oracle):
     assert gpu_ctx.serial_launches() > before
     for (s, ix, rec, case), plane, single in zip(made, planes, singles):
         assert plane is not None and plane.shape == rec.shape, case
-        assert np.array_equal(plane, rec), case
-        assert np.array_equal(plane, single), case
+        assert np.array_equal(plane, rec), case                                # the oracle's plane: what the test rests on
+        assert np.array_equal(plane, single), case                             # (the same path called with one image)
     split = gpu_ctx.indexed_decode_split()
     assert all(v >= 0 for v in split.values()) and split["rounds"] > 0
 

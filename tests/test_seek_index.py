@@ -117,8 +117,8 @@ def test_band_encoder_index_refusals(gpu_ctx, oracle):
 
 
 def test_indexed_decode_in_several_rounds(gpu_ctx, oracle):
-    """Rounds of 2 and 3 segments: the rounds run from the last segments to the first, and each segment's rows must end
-    as that segment decoded them."""
+    """Rounds of 2 and 3 segments: the job list (indexed_decode_plan) names an image's segments from the last to the first
+    and is cut into rounds in that order, and each segment's rows must end as that segment decoded them."""
     try:
         for kind, near, effort in CASES:
             s, rec = _stream(oracle, kind, near, effort, 67, 150)
@@ -130,7 +130,7 @@ def test_indexed_decode_in_several_rounds(gpu_ctx, oracle):
             e = bytearray(ents[5])
             e[len(e) - 32 - 2 * 150 - (24576 if kind == "q" else 0) + 3] ^= 0x04      # a row above entry 6 (row 42), resealed
             forged = _join(ix[:96], ents[:5] + [_reseal_entry(bytes(e))] + ents[6:])
-            gpu_ctx.set_index_round(2)                      # rounds [8, 10), [6, 8), [4, 6), ...: segment 6 starts a round, segment 5 ends the next
+            gpu_ctx.set_index_round(2)                      # the plan's rounds: segments 9 8 | 7 6 | 5 4 | ...: the boundary in front of row 42 lies between two rounds
             with pytest.raises(RuntimeError):
                 gpu_ctx.decode_indexed(s, forged)
     finally:
@@ -314,3 +314,49 @@ def test_integer_redo_on_each_side_of_a_segment_cut(gpu_ctx, pkg, oracle):
         own = st.index()
         st.close()
         assert done and whole == s and own == ix
+
+
+def _c_rows(ctx, s, ix, r0, r1, w, slack=40):
+    """nblic_amd_decode_rows through the C entry into a buffer of 0x5A with `slack` bytes behind the range, cap exact:
+    (rc, the range's bytes, the slack)."""
+    sb, xb = np.frombuffer(s, np.uint8).copy(), np.frombuffer(ix, np.uint8).copy()
+    n = (r1 - r0) * w
+    out = np.full(n + slack, 0x5A, np.uint8)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    rc = ctx.lib.nblic_amd_decode_rows(ctx.handle, p(sb), sb.size, p(xb), xb.size, r0, r1, p(out), n)
+    return rc, out[:n], out[n:]
+
+
+def test_row_range_checks_the_boundaries_it_crosses(gpu_ctx, pkg, oracle):
+    """Three segments, entry 2 (in front of row 20) forged in its rows above and resealed: a range that crosses that
+    boundary is refused and zeroed, nothing behind it touched; a range inside segment 0 and one seeded from the honest
+    entry 1 that ends before row 20 decode."""
+    h, w = 30, 100
+    s, rec = _stream(oracle, "n", 0, 1, h, w, seed=9)
+    ix = gpu_ctx.build_index(s, 10)
+    head, ents = _split(ix)
+    e = bytearray(ents[1])
+    e[len(e) - 32 - 2 * w + 150] ^= 0x01
+    forged = _join(head, [ents[0], _reseal_entry(bytes(e))])
+    assert pkg.check_index(forged, s)
+    live = pkg.live_resources()
+    rc, rows, slack = _c_rows(gpu_ctx, s, forged, 5, 25, w)
+    assert rc == -1 and rows.size == 2000 and not rows.any() and (slack == 0x5A).all()
+    assert pkg.live_resources() == live
+    for r0, r1 in ((3, 9), (12, 18)):
+        rc, rows, slack = _c_rows(gpu_ctx, s, forged, r0, r1, w)
+        assert rc == 0 and np.array_equal(rows.reshape(r1 - r0, w), rec[r0:r1]) and (slack == 0x5A).all(), (r0, r1)
+        assert pkg.live_resources() == live
+
+
+@pytest.mark.parametrize("kind,near,effort", [("n", 2, 2), ("q", 0, 0)])
+def test_row_range_writes_only_its_bytes(gpu_ctx, pkg, oracle, kind, near, effort):
+    """Odd width, unaligned entries, a range over four segments, the unpacked and the packed index: the oracle's rows, and
+    the bytes behind them untouched."""
+    h, w = 23, 149
+    s, rec = _stream(oracle, kind, near, effort, h, w)
+    ix = gpu_ctx.build_index(s, 3)
+    for x in (ix, pkg.pack_index(ix)):
+        rc, rows, slack = _c_rows(gpu_ctx, s, x, 2, 11, w)
+        assert rc == 0 and np.array_equal(rows.reshape(9, w), rec[2:11]), (kind, len(x))
+        assert (slack == 0x5A).all(), (kind, len(x))

@@ -1,5 +1,5 @@
-"""Same-box A/B of the band decoder against the indexed decode (seek index, Context.decode_indexed) on one large image
-per case.  Per case: the band decoder (decompress_bands), build_index, decode_indexed (best of --repeat calls), a
+"""Same-box A/B of the band decoder against the indexed decode (seek index, Context.decode_indexed: the indexed batch
+decode with one image) on one large image per case.  Per case: the band decoder (decompress_bands), build_index, decode_indexed (best of --repeat calls), a
 row-range decode of R rows from the middle, the segment count and index bytes / stream bytes.  Every plane is checked
 bit-exact against the input (lossless).  Writes one JSON document.
 

@@ -1,8 +1,12 @@
 """Same-box A/B of three ways to read a batch of indexed streams back, in one process on one GPU:
 
   a        Context.decode_indexed for each image in turn;
-  a_thr    one thread per image (at most 16 at a time), one decode_indexed call each: the most a caller could overlap before;
+  a_thr    one thread per image (at most 16 at a time), one decode_indexed call each;
   b        one Context.decode_batch_indexed call.
+
+decode_indexed and decode_rows are decode_batch_indexed with one image, so a, a_thr and rows_a measure what a call of
+that path costs per image against one call for all of them.  (In profiles/r14_indexed_batch_decode_ab.json, and with an
+older library behind NBLIC_AMD_LIB, they measure the single calls' former host-side path.)
 
 Streams and indexes come from Context.encode_batch_indexed.  One warm-up per leg, then --repeat runs per leg, alternating;
 wall time per run; every plane of every run is compared with its input.  Leg b also reports where the call spent its time
