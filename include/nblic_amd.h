@@ -146,6 +146,14 @@ int nblic_amd_set_device_coder(nblic_amd_ctx *ctx, int n_packs, int min_outstand
 /* What the device coder did since the context was last idle: bins coded, packs launched, images coded. */
 void nblic_amd_device_coder_stats(nblic_amd_ctx *ctx, double *bins, long *packs, long *images);
 
+/* Who moved the chunks of coded bins of this context's PACKS to the host since it was created.  While the HSA runtime
+ * loaded in the process offers its copy entry points (and NBLIC_AMD_COPY_ENGINE is not 0) a chunk travels on a DMA
+ * engine, which occupies no compute queue; otherwise, and from the first engine error on, through hipMemcpyAsync.
+ *   out[0] chunks that arrived by the engine            out[2] chunks handed to the runtime because the engine failed on them
+ *   out[1] chunks handed to the runtime                 out[3] 1 when the engine is available to this context, else 0
+ * No output byte depends on the path.  Returns 0, -1 for bad arguments.                                          */
+int nblic_amd_copy_stats(nblic_amd_ctx *ctx, long out[4]);
+
 /* Opt-in: raise the pixel-count limit above NBLIC_MAX_IMG_SIZE for this context (config 5 of
  * BASELINE.json exceeds the reference's own limit, src/NBLIC.h:31).  0 restores the reference limit.
  * ctx == NULL addresses the context behind the drop-in entry points of section 1.                   */

@@ -51,7 +51,7 @@ EXPORTS = (
     "nblic_amd_index_build_batch", "nblic_amd_index_build_split", "nblic_amd_index_build_plan", "nblic_amd_debug_index_capture",
     "nblic_amd_index_pack", "nblic_amd_index_pack_bound", "nblic_amd_index_unpack", "nblic_amd_index_unpacked_bytes", "nblic_amd_index_is_packed", "nblic_amd_debug_index_unpack",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
-    "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats",
+    "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats", "nblic_amd_copy_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
 )
 
@@ -136,6 +136,9 @@ def load_library() -> C.CDLL:
         lib.nblic_amd_set_long_chains.argtypes = [C.c_void_p, C.c_int, C.c_int]
         lib.nblic_amd_long_chain_stats.restype = C.c_int
         lib.nblic_amd_long_chain_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.c_int]
+    if hasattr(lib, "nblic_amd_copy_stats"):                       # (an older build loaded through NBLIC_AMD_LIB has none)
+        lib.nblic_amd_copy_stats.restype = C.c_int
+        lib.nblic_amd_copy_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
     lib.nblic_amd_lsq_redo_counts.restype = C.c_int
     lib.nblic_amd_lsq_redo_counts.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
     lib.nblic_amd_serial_plan.restype = C.c_int
@@ -969,6 +972,15 @@ class Context:
         if self.lib.nblic_amd_long_chain_stats(self.handle, v, int(reset)) != 0:
             raise RuntimeError("nblic_amd_long_chain_stats failed")
         return dict(zip(self.LONG_CHAIN_COUNTS, (int(x) for x in v)))
+
+    def copy_stats(self) -> dict:
+        """Who moved the chunks of this context's packs to the host (``nblic_amd_copy_stats``): ``engine`` chunks that
+        arrived by a DMA engine, ``runtime`` chunks handed to hipMemcpyAsync, ``fallbacks`` chunks handed to it because
+        the engine failed on them, ``available`` whether the engine can be used by this context."""
+        v = (C.c_long * 4)()
+        if self.lib.nblic_amd_copy_stats(self.handle, v) != 0:
+            raise RuntimeError("nblic_amd_copy_stats failed")
+        return {"engine": int(v[0]), "runtime": int(v[1]), "fallbacks": int(v[2]), "available": bool(v[3])}
 
     def lsq_redo_counts(self, reset: bool = False) -> Tuple[int, int]:
         """Pixels (efforts 2 / 3) whose least-squares system 0 / 1 left the exact range of the doubles and was redone with

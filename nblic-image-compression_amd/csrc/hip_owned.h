@@ -3,9 +3,11 @@
 // each one counts itself in g_live (nblic_amd_debug_live), so "nothing leaks" can be checked on a card that other
 // processes share.  Members are destroyed in reverse order of declaration: an object declares its stream first, so
 // its buffers go before the stream does; what has to happen before that (joining threads, synchronising the stream,
-// hipSetDevice) stays with the object.
+// hipSetDevice) stays with the object.  The completion signals of the copy engine (copy_engine.h) are owned here too.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "copy_engine.h"
 
 #include <algorithm>
 #include <atomic>
@@ -18,7 +20,7 @@
 
 namespace nblic {
 
-enum Live { kLiveDevice, kLivePinned, kLiveLocked, kLiveSync };      // sync: streams + events
+enum Live { kLiveDevice, kLivePinned, kLiveLocked, kLiveSync };      // sync: streams + events + completion signals
 inline std::atomic<long> g_live[4];
 inline void live_add(Live k, long d) { g_live[k].fetch_add(d, std::memory_order_relaxed); }
 
@@ -113,10 +115,10 @@ public:
         live_add(kLiveLocked, -1);
         p_ = nullptr; words_ = 0;
     }
-    bool alloc(size_t words) {                                       // releases what it holds first
+    bool alloc(size_t words, bool from_runtime = false) {            // releases what it holds first.  from_runtime: hipHostMalloc at once (a ring the copy engine writes)
         reset();
         const size_t bytes = (words * sizeof(uint16_t) + (size_t(2) << 20) - 1) & ~((size_t(2) << 20) - 1);
-        void *p = getenv("NBLIC_AMD_HOSTMALLOC") ? nullptr : aligned_alloc(size_t(2) << 20, bytes);
+        void *p = from_runtime || getenv("NBLIC_AMD_HOSTMALLOC") ? nullptr : aligned_alloc(size_t(2) << 20, bytes);
         if (p) {
             madvise(p, bytes, MADV_HUGEPAGE);
             memset(p, 0, bytes);
@@ -151,5 +153,23 @@ public:
 };
 using Stream = Sync<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
 using Event = Sync<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
+
+// A completion signal of the HSA runtime, created and destroyed through the copy engine's table (which outlives it).
+// Counted with the streams and events.
+class HsaSignal {
+    const HsaApi *api_ = nullptr; uint64_t h_ = 0;
+public:
+    HsaSignal() = default;
+    HsaSignal(HsaSignal &&o) noexcept : api_(std::exchange(o.api_, nullptr)), h_(std::exchange(o.h_, 0)) {}
+    HsaSignal &operator=(HsaSignal &&o) noexcept { std::swap(api_, o.api_); std::swap(h_, o.h_); return *this; }
+    ~HsaSignal() { if (h_) { api_->signal_destroy(h_); live_add(kLiveSync, -1); } }
+    bool create(const HsaApi &api, int64_t initial) {                // once
+        if (h_ || api.signal_create(initial, 0, nullptr, &h_) != 0) return false;
+        if (!h_) return false;
+        api_ = &api; live_add(kLiveSync, 1);
+        return true;
+    }
+    uint64_t handle() const { return h_; }
+};
 
 }  // namespace nblic

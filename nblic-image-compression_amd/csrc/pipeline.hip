@@ -137,6 +137,7 @@ constexpr int kCopyStreams = 8;
 constexpr int kRingDepth = 3;                                      // ring slots per coder thread: the chunk being coded + the next two on their way (two slots: 6.14-6.30 Gpx/s, three: 6.35-6.38)
 constexpr int kMaxTake = 24;                                       // images one coder thread codes together (three AVX-512 packs; NBLIC_AMD_MAX_TAKE=16: two)
 constexpr int kMaxPacks = kMaxTake / int(kPackLanes);
+static_assert(kRingDepth == kChunkSlots && kMaxPacks == kChunkPieces, "copy_engine.h carries the ring's shape for its stand-alone check");
 
 }  // namespace nblic
 // One submitted batch (nblic_amd_encode_batch_begin .. _end); `remaining` is guarded by ctx->fm.
@@ -180,6 +181,7 @@ struct Group {
     std::unique_ptr<GroupWait> front = std::make_unique<GroupWait>();
     Stream stream;
     Event done, tm_ev[kE1Marks];
+    Event released;                                    // hipEventReleaseToSystem, recorded behind the back half: what the copy engine reads has left L2 (launch_back)
     E1Timers tm{};                                     // its events are tm_ev's
     std::vector<Slot> slots;
     Pinned<E1Job> h_jobs; DevBuf<E1Job> d_jobs;        // pinned host / device job records
@@ -218,6 +220,7 @@ struct nblic_amd_ctx {
     int coders_wanted = 0;                   // coder threads of this context (set before they start: pinning needs it)
     int max_take = kMaxTake;                 // images a coder thread takes together: 24 = three AVX-512 packs (NBLIC_AMD_MAX_TAKE=16: two, for A/B runs)
     std::vector<Stream> copy_streams;        // shared by the coder threads (device -> host chunk copies)
+    CopyEngine engine;                       // the chunks of packs on a DMA engine instead (NBLIC_AMD_COPY_ENGINE=0: never opened); outlives the coder threads' signals
     size_t chunk_bins = kChunkBins;          // bins per lane per chunk (NBLIC_AMD_CHUNK_BINS shrinks it, for tests of the chunk boundaries)
     std::vector<CodedBuf> cbufs;             // one image's u16 records (images coded on their own; QNBLIC: pairs + histograms)
     std::deque<int> free_cbufs;              // both pools hand out the buffer returned last: memory is allocated for the backlog there is, not for the pool's size
@@ -347,6 +350,7 @@ static bool group_init(Group &g, int id, int n_slots, nblic_amd_ctx *c) {
     g.slots.resize(size_t(n_slots));
     HIP_OK(g.stream.create(hipStreamNonBlocking));
     HIP_OK(g.done.create(hipEventDisableTiming | hipEventBlockingSync));
+    if (c->engine.available()) HIP_OK(g.released.create(hipEventDisableTiming | hipEventReleaseToSystem));
     for (int k = 0; k < kE1Marks; k++) { HIP_OK(g.tm_ev[k].create(hipEventDefault)); g.tm.ev[k] = g.tm_ev[k]; }
     HIP_OK(g.h_jobs.alloc(size_t(n_slots))); HIP_OK(g.d_jobs.alloc(size_t(n_slots)));
     HIP_OK(g.h_sjobs.alloc(size_t(n_slots))); HIP_OK(g.d_sjobs.alloc(size_t(n_slots)));
@@ -542,10 +546,20 @@ struct CoderThread {
     RangeX8 x8, x8b, x8c;
     RangeScalar x1;
     double wait_s = 0, issue_s = 0;                      // time spent waiting for chunks / inside the runtime calls that queue a chunk (reporting)
-    bool init(int device, hipStream_t copy_stream) {
+    CopyEngine *engine = nullptr;                        // the context's, when the chunks of packs may travel on a DMA engine (copy_engine.h)
+    HsaSignal sig[kRingDepth];                           // ... then one completion signal per slot of pring
+    EngineLane lane;
+    bool init(int device, hipStream_t copy_stream, CopyEngine *eng) {
         HIP_OK(hipSetDevice(device));
         stream = copy_stream;
         for (auto &e : ev) HIP_OK(e.create(hipEventDisableTiming | hipEventBlockingSync));
+        if (eng && eng->on()) {
+            engine = eng;
+            for (int k = 0; k < kRingDepth; k++) {
+                if (!sig[k].create(eng->api(), 0)) { eng->fail("hsa_signal_create", -1); break; }
+                lane.sig[k] = sig[k].handle();
+            }
+        }
         return true;
     }
     // The rings are sized by what the thread has actually been asked to code and only grow: a context that codes one
@@ -565,7 +579,9 @@ struct CoderThread {
         groups = (groups + 63) & ~size_t(63);
         if (groups > pring_groups) {
             pring_groups = groups;
-            if (!pring.alloc(kRingDepth * size_t(kMaxPacks) * pack_words() * 4)) { pring_groups = 0; fprintf(stderr, "[nblic_amd] cannot allocate the coder thread's pack ring\n"); return false; }
+            // (with the engine the ring is the runtime's own pinned memory: the engine is given the agent that owns an allocation,
+            // and pages registered in place have none -- hip_owned.h Locked on what that costs the reading thread)
+            if (!pring.alloc(kRingDepth * size_t(kMaxPacks) * pack_words() * 4, engine != nullptr)) { pring_groups = 0; fprintf(stderr, "[nblic_amd] cannot allocate the coder thread's pack ring\n"); return false; }
         }
         return true;
     }
@@ -627,27 +643,28 @@ static bool code_packs(CoderThread &t, int n_packs, const uint64_t *const *dev_r
     const size_t chunk_groups = std::min(chunk_bins / kGroupBins, most ? most : size_t(1));
     if (!t.ensure_pack_ring(chunk_groups)) return false;
     const size_t chunks = (most + chunk_groups - 1) / chunk_groups, chunk = chunk_groups * kGroupBins;
-    auto issue = [&](size_t c) -> bool {
-        for (int p = 0; p < n_packs; p++) {
-            const size_t g0 = c * chunk_groups;
-            if (g0 >= groups[p]) continue;
-            const size_t words = std::min(chunk_groups, groups[p] - g0) * kGroupWords * kPackLanes;
-            // (In this pipeline the runtime performs the copy with its blit kernel whatever was tried: ring from hipHostMalloc
-            // instead of hipHostRegister, 2 / 4 / 8 copy streams, the copy cut into 8 or 16 MB pieces; the same copy from a
-            // bare test program goes through SDMA.  DESIGN.md section 4.)
-            if (!(dbg_flags() & kDbgNoCopy)) HIP_OK(hipMemcpyAsync(t.pack_slot(c, p), dev_rows[p] + g0 * kGroupWords * kPackLanes, words * sizeof(uint64_t), hipMemcpyDeviceToHost, t.stream));
+    // Who carries a chunk (copy_engine.h run_chunk_ring): a DMA engine while the context's is on -- one
+    // hsa_amd_memory_async_copy per pack, the slot's signal counting them down -- and otherwise, or after an engine
+    // error, the runtime on the thread's copy stream, which in this pipeline means its blit kernel whatever was tried:
+    // ring from hipHostMalloc instead of hipHostRegister, 2 / 4 / 8 copy streams, the copy cut into 8 or 16 MB pieces
+    // (DESIGN.md section 4).  The engine reads memory, not L2: the rows were released to the system by the event the
+    // group's stream records behind its back half (launch_back).
+    struct RuntimeCopies {
+        CoderThread &t;
+        bool issue(size_t c, const CopyPiece *pc, int n) {
+            for (int k = 0; k < n; k++) HIP_OK(hipMemcpyAsync(pc[k].dst, pc[k].src, pc[k].bytes, hipMemcpyDeviceToHost, t.stream));
+            HIP_OK(hipEventRecord(t.ev[c % kRingDepth], t.stream));
+            return true;
         }
-        HIP_OK(hipEventRecord(t.ev[c % kRingDepth], t.stream));
-        return true;
+        bool wait(size_t c) { return wait_chunk(t, t.ev[c % kRingDepth]); }
+    } runtime{t};
+    auto pieces = [&](size_t c, CopyPiece *out) -> int {
+        if (dbg_flags() & kDbgNoCopy) return 0;
+        return chunk_pieces(c, n_packs, groups, chunk_groups, kGroupWords * kPackLanes, dev_rows, [&](size_t cc, int p) { return t.pack_slot(cc, p); }, out);
     };
     RangeX8 *const packs[kMaxPacks] = {&t.x8, &t.x8b, &t.x8c};
     for (int p = 0; p < n_packs; p++) packs[p]->begin(pack_n[p], dst + kPackLanes * p, caps + kPackLanes * p);
-    for (size_t c = 0; c + 1 < size_t(kRingDepth) && c < chunks; c++) if (!issue(c)) return false;
-    for (size_t c = 0; c < chunks; c++) {
-        const auto i0 = std::chrono::steady_clock::now();
-        if (c + kRingDepth - 1 < chunks && !issue(c + kRingDepth - 1)) return false;      // its ring slot was consumed one chunk ago
-        t.issue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - i0).count();
-        if (!wait_chunk(t, t.ev[c % kRingDepth])) return false;
+    auto consume = [&](size_t c) {
         size_t len[kMaxTake] = {0};
         const uint64_t *rows_p[kMaxPacks] = {nullptr};
         for (int p = 0; p < n_packs; p++) {
@@ -658,7 +675,8 @@ static bool code_packs(CoderThread &t, int n_packs, const uint64_t *const *dev_r
             }
         }
         if (!(dbg_flags() & kDbgFeedOnly)) feed_packs(packs, n_packs, rows_p, len);
-    }
+    };
+    if (!run_chunk_ring(t.engine, t.lane, chunks, runtime, pieces, consume, &t.issue_s, &t.wait_s)) return false;
     for (int p = 0; p < n_packs; p++) packs[p]->end(lens + kPackLanes * p);
     return true;
 }
@@ -738,7 +756,7 @@ static void coder_main(nblic_amd_ctx *c, int index) {
         }
     }
     CoderThread t;
-    if (!t.init(c->device, c->copy_streams[size_t(index) % c->copy_streams.size()])) c->broken = true;
+    if (!t.init(c->device, c->copy_streams[size_t(index) % c->copy_streams.size()], &c->engine)) c->broken = true;
     for (;;) {
         ReadyImage im[kMaxTake];
         int take = 0;
@@ -995,6 +1013,9 @@ static bool launch_back(nblic_amd_ctx *c, Group &g, bool with_coders, bool gener
     HIP_OK(hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(g.n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, g.stream));
     e1_launch_back(g.d_jobs, g.h_jobs, g.n_jobs, g.stream, (c->timing && !general) ? &g.tm : nullptr, general);
     g.tm_pending = c->timing && !general;
+    // A pack becomes takeable in on_group_done.  Its reader may be a DMA engine, which reads memory and not L2: the rows
+    // k_mix and k_pack_rows wrote are released at system scope HERE, by this event, not by whatever the host function does.
+    if (with_coders && c->engine.available()) HIP_OK(hipEventRecord(g.released, g.stream));
     if (with_coders) HIP_OK(hipLaunchHostFunc(g.stream, on_group_done, &g));       // the caller has counted the images in ctx->coding
     return true;
 }
@@ -3522,6 +3543,10 @@ nblic_amd_ctx *nblic_amd_create_ex(int device, int n_groups, int group_size, int
     auto *c = new nblic_amd_ctx;
     c->device = device;
     c->simd = have_avx512() && !getenv("NBLIC_AMD_NO_SIMD");
+    {   // NBLIC_AMD_COPY_ENGINE=0 leaves every copy with the runtime; so does a process without the HSA runtime's entry points
+        const char *ce = getenv("NBLIC_AMD_COPY_ENGINE");
+        if (!ce || atoi(ce) != 0) c->engine.open();
+    }
     c->groups.resize(size_t(n_groups));
     for (int i = 0; i < n_groups; i++) {
         if (!group_init(c->groups[size_t(i)], i, group_size, c)) { nblic_amd_destroy(c); return nullptr; }
@@ -4127,6 +4152,12 @@ int nblic_amd_debug_index_unpack(nblic_amd_ctx *c, int n, const void *const *pac
 }
 
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
+
+int nblic_amd_copy_stats(nblic_amd_ctx *c, long out[4]) {
+    if (!c || !out) return -1;
+    c->engine.stats(out);
+    return 0;
+}
 
 void nblic_amd_set_max_pixels(nblic_amd_ctx *c, long max_pixels) {
     if (!c) c = default_ctx();                                               // NULL: the context behind the drop-in entry points
