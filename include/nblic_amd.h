@@ -395,15 +395,46 @@ int nblic_amd_index_is_packed(const void *index, size_t index_bytes);
  * reconstruction is the input), device planes have each band's rows copied back for the index's row hash.
  * nblic_amd_index_bytes: the size of the index of a stream of this geometry; host only, no device, no context.  kind 0
  * NBLIC (effort 1..3), 1 QNBLIC (effort 0).  -1 for every_rows < 1 or >= height, or fields out of range.
- * nblic_amd_indexed_batch_split (reporting): the context's last indexed batch summed over its group steps -- ms[0] front
- * halves, [1] totals read-back, [2] back halves and entry records, [3] copies to the host (GPU time, milliseconds),
- * [4] the drivers' wait for the coder threads (host milliseconds); returns the number of group steps, -1 without a context. */
+ * nblic_amd_indexed_batch_split (reporting): the context's last indexed batch of either kind (this call or
+ * nblic_amd_qencode_batch_indexed) summed over its group steps -- ms[0] front halves (effort 0: the model stage), [1] totals
+ * read-back, [2] back halves and entry records, [3] copies to the host (GPU time, milliseconds), [4] the drivers' wait for
+ * the coder threads (host milliseconds); returns the number of group steps, -1 without a context.  The effort-0 batch has no
+ * totals read-back and no back half: there [1] reads 0, [2] is the entry records alone, and [4] is the drivers' wait for
+ * a free image buffer, which is how its workers hold a driver back. */
 int nblic_amd_encode_batch_indexed(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *imgs, int imgs_on_device,
                                    const int *heights, const int *widths, const int *every_rows, int band_rows,
                                    unsigned char *const *outs, const size_t *out_caps, long *out_lens,
                                    unsigned char *const *indexes, const size_t *index_caps, long *index_lens);
 long nblic_amd_index_bytes(int kind, int height, int width, int effort, int every_rows);
 long nblic_amd_indexed_batch_split(nblic_amd_ctx *ctx, double ms[5]);
+
+/* INDEXED EFFORT-0 BATCH ENCODE: many QNBLIC images AND their seek indexes in one call.  Image k gets the stream
+ * nblic_amd_qencode_batch and QNBLICcompress write for it, byte for byte (outs[k] are uint16_t buffers; capacities and
+ * lengths in 16-bit WORDS), and, when 1 <= every_rows[k] < heights[k], the seek index nblic_amd_index_build(every_rows[k])
+ * would make for that stream, byte for byte -- nblic_amd_index_bytes(1, h, w, 0, every_rows[k]) bytes -- without the serial
+ * decode index_build costs.  A group of images is stepped through row bands together as in nblic_amd_encode_batch_indexed:
+ * a launch sequence carries the model stage of one band of every image of the group and the decoder records of the bands
+ * that end on an entry row; nothing on the host sizes anything in between, so a group's steps are queued ahead (eight at
+ * most) without a wait.  every_rows, indexes, band_rows, the per-image results and what refuses the whole call are exactly
+ * nblic_amd_encode_batch_indexed's (above); a stream buffer of fewer than 6 words is refused like a refused size.
+ *   per image in flight   an image's histograms are final only with its last band, so its entropy stage -- normalisation,
+ *                   histogram code and the rANS pass, on a worker thread of the call (as many as the context has coder
+ *                   threads) -- starts when all its level | symbol words are on the host: the call holds 2 bytes per pixel
+ *                   of page-locked memory per image in flight, plus 12,352 + 2 x width bytes per entry, plus 1 byte per
+ *                   pixel for a device-resident input whose index is wanted (the rows the index hashes).  A group has
+ *                   2 x (its slots) such buffers: one per image being stepped and as many for images being coded; a
+ *                   slot whose image has ended takes the next image only when a buffer is free.  They belong to the
+ *                   context and only grow, as the device workspace (one band per slot) does.
+ *   the entries     the rANS pass runs last pixel first, so its state once pixel every_rows x width x j has been coded is
+ *                   the state the decoder holds in front of that row; the worker reads state and position off the pass.
+ * Lossless effort 0 only: it is the one other mode whose model stage runs on the partitioned kernels and whose
+ * reconstruction is the input (near-lossless and efforts 2 / 3: see above).  No choice of band_rows shows in any byte.
+ * The call takes groups of the context as nblic_amd_encode_batch_indexed does, each for the whole call, and runs next to
+ * batches, band coders and decoders of the same context.  nblic_amd_indexed_batch_split reports it (above). */
+int nblic_amd_qencode_batch_indexed(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *imgs, int imgs_on_device,
+                                    const int *heights, const int *widths, const int *every_rows, int band_rows,
+                                    uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words,
+                                    unsigned char *const *indexes, const size_t *index_caps, long *index_lens);
 
 /* INDEXED BATCH DECODE: the segments of many streams, or one row range of each, in one call.  Image k is a stream and its
  * seek index; NBLIC in any mode and QNBLIC, any geometry and any R may share a call.  row0 and row1 both NULL: whole
@@ -684,6 +715,20 @@ int nblic_amd_debug_index_capture(nblic_amd_ctx *ctx, int kind, int effort, int 
 int nblic_amd_debug_index_unpack(nblic_amd_ctx *ctx, int n, const void *const *packed, const size_t *packed_bytes,
                                  const size_t *base_offsets, const int *walks, const int *first_outs,
                                  unsigned char *const *outs, const size_t *caps, size_t *out_strides);
+
+/* Debug hook used by the indexed effort-0 batch's host tests: QNBLIC's entropy stage (histogram normalisation, histogram
+ * code, the rANS pass) on caller-made records, reporting the coder in front of entry rows as the batch's workers read it.
+ * Host only: no context, no device.  words[height x width] = level | symbol << 8 per pixel, hist[12 x 256] the counts
+ * per level and symbol; entry_rows[n_entries] rows 0 < r < height in ascending order (n_entries may be 0).  Writes the
+ * stream into out (cap_words 16-bit words) and per entry row r: states[k] = the rANS state once pixel r x width has been
+ * coded (the pass runs last pixel first), words_emitted[k] = the renormalisation words emitted by then.  With W such words
+ * in all -- the stream's rANS part is W + 2 words -- a decoder in front of row r holds states[k] and has consumed
+ * 2 + W - words_emitted[k] words of it.  Returns the stream's length in words; -1 when cap_words is too small; -2, with
+ * nothing written, for a null pointer, a size out of range, entry rows out of range or order, a word whose level is
+ * above 11 or whose symbol its level's histogram does not count. */
+long nblic_amd_debug_q_entropy(int height, int width, const uint16_t *words, const unsigned int *hist, const int *entry_rows,
+                               int n_entries, uint16_t *out, size_t cap_words, unsigned int *states,
+                               unsigned long long *words_emitted);
 
 /* Device self-test of the wave primitives the chain kernels rely on (DPP prefix sum against the
  * shuffle formulation).  Returns the number of mismatching lanes (0 = pass) or -1.           */

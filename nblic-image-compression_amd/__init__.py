@@ -47,6 +47,7 @@ EXPORTS = (
     "nblic_amd_index_check", "nblic_amd_index_build", "nblic_amd_decode_indexed", "nblic_amd_decode_rows",
     "nblic_amd_stream_set_index", "nblic_amd_stream_index", "nblic_amd_set_index_round", "nblic_amd_stream_set_front",
     "nblic_amd_encode_batch_indexed", "nblic_amd_index_bytes", "nblic_amd_indexed_batch_split",
+    "nblic_amd_qencode_batch_indexed", "nblic_amd_debug_q_entropy",
     "nblic_amd_decode_batch_indexed", "nblic_amd_indexed_decode_split", "nblic_amd_indexed_decode_plan", "nblic_amd_debug_index_kernels",
     "nblic_amd_index_build_batch", "nblic_amd_index_build_split", "nblic_amd_index_build_plan", "nblic_amd_debug_index_capture",
     "nblic_amd_index_pack", "nblic_amd_index_pack_bound", "nblic_amd_index_unpack", "nblic_amd_index_unpacked_bytes", "nblic_amd_index_is_packed", "nblic_amd_debug_index_unpack",
@@ -209,6 +210,11 @@ def load_library() -> C.CDLL:
         lib.nblic_amd_index_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         lib.nblic_amd_indexed_batch_split.restype = C.c_long
         lib.nblic_amd_indexed_batch_split.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    if hasattr(lib, "nblic_amd_qencode_batch_indexed"):
+        lib.nblic_amd_qencode_batch_indexed.restype = C.c_int
+        lib.nblic_amd_qencode_batch_indexed.argtypes = lib.nblic_amd_encode_batch_indexed.argtypes
+        lib.nblic_amd_debug_q_entropy.restype = C.c_long
+        lib.nblic_amd_debug_q_entropy.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, ip, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     if hasattr(lib, "nblic_amd_decode_batch_indexed"):
         vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
         lib.nblic_amd_decode_batch_indexed.restype = C.c_int
@@ -370,6 +376,36 @@ def _every_rows_list(every_rows, k: int) -> List[int]:
     if any(r < 0 for r in every):
         raise ValueError("every_rows must not be negative (0: no index for that image)")
     return every
+
+
+def q_entropy_entries(words: np.ndarray, entry_rows=(), hist: Optional[np.ndarray] = None, cap_words: Optional[int] = None):
+    """QNBLIC's entropy stage on caller-made records (``nblic_amd_debug_q_entropy``; host only, no device): ``words`` is a
+    2-D uint16 array of ``level | symbol << 8``, ``hist`` the 12 x 256 counts (default: counted from ``words``),
+    ``entry_rows`` ascending rows ``0 < r < h``.  Returns (stream bytes, [(rANS state, words emitted) per entry row]);
+    the stream is ``None`` when ``cap_words`` is too small.  Raises ``ValueError`` for what the library refuses."""
+    words = np.ascontiguousarray(words, np.uint16)
+    if words.ndim != 2 or words.size == 0:
+        raise ValueError("words must be a non-empty 2-D array")
+    h, w = words.shape
+    if hist is None:
+        hist = np.bincount((words & 0xFF).astype(np.int64).ravel() * 256 + (words >> 8).astype(np.int64).ravel(), minlength=12 * 256)
+        if hist.size != 12 * 256:
+            raise ValueError("a word names a level above 11")
+    hist = np.ascontiguousarray(hist, np.uint32).reshape(-1)
+    if hist.size != 12 * 256:
+        raise ValueError("hist must hold 12 x 256 counts")
+    rows = [int(r) for r in entry_rows]
+    k = len(rows)
+    cap = 2 * h * w + 4096 if cap_words is None else int(cap_words)
+    out = np.empty(max(cap, 1), np.uint16)
+    states, emitted = np.zeros(max(k, 1), np.uint32), np.zeros(max(k, 1), np.uint64)
+    n = int(load_library().nblic_amd_debug_q_entropy(h, w, words.ctypes.data, hist.ctypes.data, (C.c_int * max(k, 1))(*rows), k, out.ctypes.data, cap,
+                                                     states.ctypes.data, emitted.ctypes.data))
+    if n == -2:
+        raise ValueError("nblic_amd_debug_q_entropy refused its arguments")
+    if n < 0:
+        return None, []
+    return out[:n].tobytes(), [(int(s), int(e)) for s, e in zip(states[:k], emitted[:k])]
 
 
 def out_capacity(h: int, w: int) -> int:
@@ -1081,6 +1117,45 @@ class Context:
         ms = (C.c_double * 5)()
         steps = int(self.lib.nblic_amd_indexed_batch_split(self.handle, ms))
         return dict(zip(("front_ms", "readback_ms", "back_ms", "copies_ms", "coder_wait_ms"), [float(v) for v in ms]), steps=steps)
+
+    def qencode_indexed_ptrs(self, ptrs: Sequence[int], shapes: Sequence[Tuple[int, int]], on_device: bool, every_rows, band_rows: int = 0,
+                             want_index: bool = True):
+        """``nblic_amd_qencode_batch_indexed`` on planes given as raw addresses (host or device).  ``want_index`` False
+        passes no index buffers at all.  Returns (rc, streams, indexes) as :meth:`encode_indexed_ptrs` does."""
+        k = len(ptrs)
+        every = _every_rows_list(every_rows, k)
+        outs = [np.empty(out_capacity(h, w) // 2, np.uint16) for h, w in shapes]
+        imgs, hs, ws, op, caps, lens = _batch_args(ptrs, shapes, outs)
+        if want_index:
+            idxs = [np.empty(max(index_bytes(1, h, w, 0, r), 1), np.uint8) for (h, w), r in zip(shapes, every)]
+            xp = (C.c_void_p * k)(*[C.c_void_p(x.ctypes.data) for x in idxs])
+            xcaps, xlens = (C.c_size_t * k)(*[x.size for x in idxs]), (C.c_long * k)()
+        else:
+            idxs, xp, xcaps, xlens = [None] * k, None, None, [0] * k
+        rc = int(self.lib.nblic_amd_qencode_batch_indexed(self.handle, k, imgs, int(on_device), hs, ws, (C.c_int * k)(*every), int(band_rows),
+                                                          op, caps, lens, xp, xcaps, xlens if want_index else None))
+        streams = [o[:n].tobytes() if n >= 0 else None for o, n in zip(outs, lens)]
+        indexes = [x[:n].tobytes() if n > 0 else None for x, n in zip(idxs, xlens)]
+        return rc, streams, indexes
+
+    def qencode_batch_indexed(self, imgs, every_rows, band_rows: int = 0) -> List[Tuple[Optional[bytes], Optional[bytes]]]:
+        """Effort-0 (QNBLIC) encode of a batch AND the seek index of every stream (``nblic_amd_qencode_batch_indexed``): per
+        image (stream, index), the stream what :meth:`qencode_batch` returns, the index byte-identical to
+        ``build_index(stream, every_rows)`` and ``None`` where ``every_rows`` is 0 or not below the image's height.
+        ``imgs``: numpy planes, or device tensors (anything with ``data_ptr()`` and a 2-D ``shape``, uint8, contiguous);
+        ``every_rows``: an int, or one per image.  Raises if any image failed."""
+        imgs = list(imgs)
+        on_device = bool(imgs) and hasattr(imgs[0], "data_ptr")
+        every = _every_rows_list(every_rows, len(imgs))
+        if on_device:
+            ptrs, shapes = [int(t.data_ptr()) for t in imgs], [(int(t.shape[0]), int(t.shape[1])) for t in imgs]
+        else:
+            planes = [np.ascontiguousarray(i, np.uint8) for i in imgs]
+            ptrs, shapes = [p.ctypes.data for p in planes], [p.shape for p in planes]
+        rc, streams, indexes = self.qencode_indexed_ptrs(ptrs, shapes, on_device, every, band_rows)
+        if rc != 0:
+            raise RuntimeError("nblic_amd_qencode_batch_indexed failed")
+        return list(zip(streams, indexes))
 
     def encode_batch(self, imgs: Sequence[np.ndarray]) -> List[bytes]:
         """-n0 -e1 encode of host planes; returns the .nblic streams."""

@@ -136,6 +136,16 @@ void e1_launch_front_pre(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, h
 // QNBLIC (effort 0) model stage for a group: leaves level | symbol << 8 per pixel in `pxs` and the
 // 12 x 256 histograms in `qhist`; the entropy stage (normalise, histogram code, rANS) is host work.
 void q_launch_model(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s);
+// The same for ROW BANDS of effort-0 images (E1Job::row0; the indexed effort-0 batch, pipeline.hip), the counterpart of
+// e1_launch_front_band: k_init_state runs for the jobs with row0 == 0 alone, the context chains start from the slot's
+// ctx_state and leave their end state there, the window's rows 0 / 1 rules follow the row in the IMAGE and the rows above a
+// band are read from the plane, and k_q_symbols adds the band's counts to the slot's qhist; pxs holds level | symbol << 8
+// of the band's pixels.  The jobs of a launch differ in row0, height and width.
+void q_launch_model_band(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s);
+// QNBLIC's sibling of e1_launch_index_records: per task the decoder record of job `job` -- a zero SerialState (all of it
+// is the host's), then the 3072 contexts as its band's chains left them, which is how the decoder keeps them -- followed by
+// the two image rows above the row behind the band, at out + `out`: kQDecodeStateBytes + 2 w bytes.
+void q_launch_index_records(const E1Job *d_jobs, const IndexRecordTask *d_tasks, int n_tasks, uint8_t *d_out, hipStream_t s);
 // The same launch sequences from caller-made records instead of an image (the debug entries of pipeline.hip,
 // tests/test_chain_kernels.py): the front half behind S1 from b.rec1 (model.h pack_s1) and b.img (h * w = n values, read as
 // a flat array), QNBLIC's model stage behind k_q_predict from b.rec1 (px0 | adr << 8), the back half behind k_emit_bins

@@ -1776,6 +1776,27 @@ __global__ void __launch_bounds__(256) k_q_predict(const E1Job *__restrict__ job
     gptr(J.b.rec1)[size_t(i) * size_t(w) + size_t(j)] = uint32_t(px0) | (uint32_t(context_address_q(n, qd, px0)) << 8);
 }
 
+// The same for a ROW BAND (E1Job::row0; q_launch_model_band): b.img / b.rec1 start at image row row0, and the window's
+// closed form sees the row in the IMAGE -- rows 0 and 1 are special wherever the band starts -- and reads the one or two
+// rows above the band from the plane, which goes on above b.img.  A kernel of its own: the whole-image grid above keeps
+// its unsigned addressing.
+__global__ void __launch_bounds__(256) k_q_predict_band(const E1Job *__restrict__ jobs) {
+    const E1Job &J = jobs[blockIdx.z];
+    const int w = J.w, row0 = J.row0;
+    int j = int(blockIdx.x) * 256 + int(threadIdx.x);
+    int i = int(blockIdx.y);                                             // the row's index in b.img / b.rec1
+    if (i >= J.h || j >= w) return;
+    const auto img = gptr(J.b.img);
+    auto pix = [&](int r, int c) { return int(img[(ptrdiff_t(r) - ptrdiff_t(row0)) * ptrdiff_t(w) + ptrdiff_t(c)]); };   // r: row in the image
+    Taps n = sample_taps_q(pix, w, row0 + i, j);
+    int px0 = predict_q(n);
+    int err_prev = 0;
+    if (j > 0) err_prev = pix(row0 + i, j - 1) - predict_q(sample_taps_q(pix, w, row0 + i, j - 1));
+    int qd = level_q(n, err_prev);
+    gptr(J.b.rec1)[size_t(i) * size_t(w) + size_t(j)] = uint32_t(px0) | (uint32_t(context_address_q(n, qd, px0)) << 8);
+}
+
+// A band adds its counts to the slot's qhist, which k_init_state zeroes at an image's first band alone.
 __global__ void __launch_bounds__(256) k_q_symbols(const E1Job *__restrict__ jobs) {
     __shared__ uint32_t hist[12 * 256];
     const E1Job &J = jobs[blockIdx.y];
@@ -1797,6 +1818,27 @@ __global__ void __launch_bounds__(256) k_q_symbols(const E1Job *__restrict__ job
     }
     __syncthreads();
     for (int k = int(threadIdx.x); k < 12 * 256; k += 256) if (hist[k]) atomicAdd(J.b.qhist + k, hist[k]);
+}
+
+// QNBLIC's seek-index entry records (kernels_e1.h q_launch_index_records): one workgroup per entry.  The decoder keeps its
+// 3072 contexts as the chains keep them (the same v, read as v >> 10), so the record is a zero header, ctx_state verbatim
+// and the two rows above the row behind the band -- the layout k_index_capture leaves for kind 1.
+__global__ void __launch_bounds__(256) k_q_index_records(const E1Job *__restrict__ jobs, const IndexRecordTask *__restrict__ tasks, uint8_t *__restrict__ out) {
+    const IndexRecordTask T = tasks[blockIdx.x];
+    const E1Job &J = jobs[T.job];
+    const int t = int(threadIdx.x);
+    const auto rec = gptr(out) + T.out;
+    const auto words = (NB_GLOBAL uint32_t *)rec;
+    constexpr int kHeadWords = int(sizeof(SerialState) / 4);
+    if (t < kHeadWords) words[t] = 0u;
+    const auto ctx_state = gptr(J.b.ctx_state);
+    for (int k = t; k < 3072; k += 256) words[kHeadWords + k] = uint32_t(ctx_state[k]);
+    // rows [r - n, r) of the image, n = min(r, 2), behind (2 - n) w zero bytes (k_index_records)
+    const int w = J.w, r = J.row0 + J.h, n = r < 2 ? r : 2;
+    const auto rows = rec + kQDecodeStateBytes;
+    const auto img = gptr(J.b.img);
+    const ptrdiff_t zeros = ptrdiff_t(2 - n) * w, from = ptrdiff_t(J.h - n) * w;
+    for (ptrdiff_t k = t; k < 2 * ptrdiff_t(w); k += 256) rows[k] = k < zeros ? uint8_t(0) : img[from + (k - zeros)];
 }
 
 // self-test: the DPP scan must equal the shuffle scan on arbitrary data
@@ -2039,6 +2081,22 @@ void q_launch_model(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStr
     hipLaunchKernelGGL(k_init_state, dim3(16, n_jobs), dim3(256), 0, s, d_jobs);
     hipLaunchKernelGGL(k_q_predict, dim3(cdiv(max_w, 256), max_h, n_jobs), dim3(256), 0, s, d_jobs);
     q_behind_predict(d_jobs, n_jobs, max_nseg, max_n, h_jobs[0].long_min >= 0, s);
+}
+
+void q_launch_model_band(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s) {
+    int max_w = 0, max_h = 0, max_nseg = 0; uint32_t max_n = 0;
+    for (int k = 0; k < n_jobs; k++) {
+        max_w = h_jobs[k].w > max_w ? h_jobs[k].w : max_w; max_h = h_jobs[k].h > max_h ? h_jobs[k].h : max_h;
+        max_n = h_jobs[k].n > max_n ? h_jobs[k].n : max_n; max_nseg = h_jobs[k].pp.nseg > max_nseg ? h_jobs[k].pp.nseg : max_nseg;
+    }
+    for (int k = 0; k < n_jobs; k++)                                  // fresh contexts and histograms for the jobs that start an image
+        if (h_jobs[k].row0 == 0) hipLaunchKernelGGL(k_init_state, dim3(16, 1), dim3(256), 0, s, d_jobs + k);
+    hipLaunchKernelGGL(k_q_predict_band, dim3(cdiv(max_w, 256), max_h, n_jobs), dim3(256), 0, s, d_jobs);
+    q_behind_predict(d_jobs, n_jobs, max_nseg, max_n, h_jobs[0].long_min >= 0, s);
+}
+
+void q_launch_index_records(const E1Job *d_jobs, const IndexRecordTask *d_tasks, int n_tasks, uint8_t *d_out, hipStream_t s) {
+    if (n_tasks > 0) hipLaunchKernelGGL(k_q_index_records, dim3(unsigned(n_tasks)), dim3(256), 0, s, d_jobs, d_tasks, d_out);
 }
 
 void q_launch_model_stages(const E1Job *d_jobs, const E1Job *h_jobs, int n_jobs, hipStream_t s) {

@@ -40,6 +40,7 @@
 #include "kernels_e1.h"
 #include "lsq_f64.h"
 #include "model.h"
+#include "q_entropy.h"
 #include "range_coder.h"
 #include "serial_engine.h"
 #include "sha256.h"
@@ -109,7 +110,6 @@ size_t range_code(const uint16_t *coded, size_t n, uint8_t *out, size_t cap) {
     return r.finish();
 }
 
-long q_entropy_encode(uint16_t *out, size_t cap_words, int h, int w, const uint16_t *qy, const uint32_t *hist_in);
 
 void write_header(uint8_t *p, int h, int w, int near, int k_step, int effort) {   // NBLIC.c:682-694
     memcpy(p, "NBLIC0.3", 8);
@@ -197,6 +197,12 @@ struct Group {
     ::nblic_amd_batch *batch = nullptr;
     // hand-over to the group's driver thread (guarded by ctx->dm)
     const uint8_t *const *imgs = nullptr; bool on_device = false; bool has_work = false;
+    // the indexed effort-0 batch (qidx_driver), whose driver holds the group: page-locked buffers of the images in flight
+    // (words | histograms | entry records | rows), the ring of queued steps' job records, tasks and totals, the staged
+    // records.  Grow-only; allocated by the first such call
+    std::vector<Locked> qidx_bufs; std::vector<Event> qidx_ready;
+    Pinned<E1Job> qidx_jobs; Pinned<IndexRecordTask> qidx_tasks; Pinned<uint32_t> qidx_totals;
+    DevBuf<IndexRecordTask> qidx_d_tasks; DevBuf<uint8_t> qidx_d_recs;
 };
 
 }  // namespace nblic
@@ -1220,7 +1226,6 @@ static bool launch_q(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, boo
 }
 
 // ---- decoders: every stream of a batch side by side, one wave per image (serial_engine.hip) -----
-long q_decode_tables(const uint16_t *in, size_t n_words, int *h, int *w, uint32_t *freq, uint32_t *start, uint8_t *slot);
 
 struct DecodeItem { int k, h, w, near, k_step, effort, kind; size_t len; long q_pos; int qtab; };      // kind 0 NBLIC, 1 QNBLIC; q_pos: first rANS word; qtab: which parsed table set
 
@@ -2778,6 +2783,288 @@ static int encode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
         q.pool.start(std::max(1, c->coders_wanted));
         std::vector<std::thread> drivers;
         for (int i = 0; i < n_drivers; i++) drivers.emplace_back([&] { idx_driver(q, images); });
+        for (auto &t : drivers) t.join();
+    }
+    {
+        std::lock_guard<std::mutex> l(c->stat_m);
+        for (int k = 0; k < 5; k++) c->idx_split[k] = q.split[k];
+        c->idx_steps = q.steps;
+    }
+    bool all = !q.failed;
+    for (int k = 0; k < n; k++) {
+        if (q.failed && images[size_t(k)]) { lens[k] = -1; if (ilens && images[size_t(k)]->every) ilens[k] = -1; }
+        all = all && lens[k] >= 0 && (!ilens || ilens[k] >= 0);
+    }
+    return all ? 0 : -1;
+}
+
+// ---- the INDEXED effort-0 BATCH: QNBLIC streams and their seek indexes, a group of images stepped through row bands -------
+// The indexed batch above for effort 0.  QNBLIC's model stage is parallel already (q_launch_model), it is lossless, and its
+// decoder record is 64 bytes and 3072 contexts, so a step is one launch sequence -- q_launch_model_band, then the records
+// of the jobs whose band ends on an entry row -- and three kinds of copies: the band's level | symbol words into the
+// IMAGE's page-locked buffer, its entry record, and at the image's last band the histograms (and, for a device input, the
+// rows the index hashes).  Nothing on the host sizes anything in between, so a driver does not wait for a step: it queues
+// up to kQIdxDepth steps ahead (the ring of job records the queued copies still read, and four timing marks a step) and
+// otherwise stops only for a free image buffer.  An image's entropy stage cannot start before its last word is on the
+// host -- the histograms are final only then -- so every image in flight holds 2 bytes per pixel of page-locked memory
+// (plus its records: 12,352 + 2 w bytes an entry, and 1 byte per pixel more for a device input whose index is wanted); a
+// group has 2 x its slots of them, one per slot that is being stepped and as many again for the images the workers are
+// coding.  The stage runs on a worker thread: q_entropy_encode_entries, then the entries -- the rANS pass runs last pixel
+// first, so what it holds once pixel r w is coded is what the decoder holds in front of row r (q_entropy.cpp).
+constexpr int kQIdxDepth = 8;
+static_assert(kQIdxDepth * 4 <= kE1Marks, "a queued step's four marks are timing events of the group");
+
+struct QIdxImage {
+    int k = 0, h = 0, w = 0, every = 0, count = 0;                       // every: 0 = no index wanted (or none possible); count: its entries
+    const uint8_t *host_plane = nullptr;                                 // host input: the rows are hashed from it
+    uint16_t *out = nullptr; size_t cap = 0;                             // in words
+    uint8_t *index = nullptr; size_t entry_bytes = 0;
+};
+// An image's page-locked buffer, in bytes: words | histograms | entry records | rows [0, count * every) of a device input.
+struct QIdxLayout { size_t hist, recs, rec_stride, rows, bytes; };
+static QIdxLayout qidx_layout(const QIdxImage &I, bool on_device) {
+    QIdxLayout L;
+    L.hist = up256(2 * size_t(I.h) * size_t(I.w));
+    L.recs = L.hist + 12 * 256 * sizeof(uint32_t);
+    L.rec_stride = up256(kQDecodeStateBytes + 2 * size_t(I.w));
+    L.rows = L.recs + size_t(I.count) * L.rec_stride;
+    L.bytes = L.rows + (on_device ? size_t(I.count) * size_t(I.every) * size_t(I.w) : 0);
+    return L;
+}
+struct QIdxCall {
+    nblic_amd_ctx *c; int n; const unsigned char *const *imgs; bool on_device; const int *hs, *ws; int band_rows;
+    long *lens, *ilens;
+    std::atomic<int> next{0};
+    std::atomic<bool> failed{false};                                     // a device-side failure: the call is over
+    IdxPool pool;
+    std::mutex m; double split[5] = {0}; long steps = 0;                 // summed over the groups (guarded by m)
+};
+struct QIdxFree {                                                        // a driver's image buffers: taken when an image starts, given back by its worker.  Shared (shared_ptr) by the driver and the tasks it posts: whoever lets go last destroys it
+    std::mutex m; std::condition_variable cv; std::vector<int> free; int out = 0;
+    int take() { std::unique_lock<std::mutex> l(m); cv.wait(l, [this] { return !free.empty(); }); const int b = free.back(); free.pop_back(); out++; return b; }
+    void give(int b) { { std::lock_guard<std::mutex> l(m); free.push_back(b); out--; } cv.notify_all(); }
+    void wait_all() { std::unique_lock<std::mutex> l(m); cv.wait(l, [this] { return out == 0; }); }
+};
+
+// An image's last band has been queued; `ready` is recorded behind its copies.  The entropy stage, then the index.
+static void qidx_finish(QIdxCall &q, const QIdxImage &I, const uint8_t *base, const QIdxLayout &L, hipEvent_t ready) {
+    auto fail = [&] { q.lens[I.k] = -1; if (I.every) q.ilens[I.k] = -1; };
+    if (hipSetDevice(q.c->device) != hipSuccess || hipEventSynchronize(ready) != hipSuccess) { q.failed = true; return fail(); }
+    std::vector<int> rows(size_t(I.count));
+    std::vector<QEntryState> at(size_t(I.count));
+    for (int e = 0; e < I.count; e++) rows[size_t(e)] = (e + 1) * I.every;
+    const long words = q_entropy_encode_entries(I.out, I.cap, I.h, I.w, reinterpret_cast<const uint16_t *>(base),
+                                                reinterpret_cast<const uint32_t *>(base + L.hist), rows.data(), I.count, at.data());
+    if (words < 0) {
+        fprintf(stderr, "[nblic_amd] image %d: output buffer of %zu words is too small\n", I.k, I.cap);
+        return fail();
+    }
+    q.lens[I.k] = words;
+    if (!I.every) return;
+    const size_t stream_bytes = size_t(words) * 2;
+    std::vector<uint8_t> tab(kQTab);
+    const long q_pos = q_parse_tables(reinterpret_cast<const unsigned char *>(I.out), stream_bytes, tab.data());
+    if (q_pos < 0) { q.ilens[I.k] = -1; return; }                        // (cannot happen: the tables were written a moment ago)
+    const unsigned long long emitted = (unsigned long long)(words - q_pos - 2);       // renormalisation words of the whole pass
+    const DecodeItem it{0, I.h, I.w, 0, kMinKStep, 0, 1, stream_bytes, q_pos, -1};
+    const RecordLayout R = record_layout(1, I.w, 0);
+    const uint8_t *plane = I.host_plane ? I.host_plane : base + L.rows;
+    Sha256 rows_sha;
+    for (int e = 0; e < I.count; e++) {
+        const int r = (e + 1) * I.every;
+        rows_sha.update(plane + size_t(e) * size_t(I.every) * size_t(I.w), size_t(I.every) * size_t(I.w));
+        uint8_t *ck = I.index + index_entry_at(e, I.entry_bytes), *rec = ck + sizeof(DecodeCheckpoint);
+        memcpy(rec, base + L.recs + size_t(e) * L.rec_stride, kQDecodeStateBytes + 2 * size_t(I.w));
+        SerialState S{};                                                 // every other field as the band decoder's checkpoint leaves it: zero
+        S.next_row = r; S.status = kRunning; S.lo = at[size_t(e)].state;
+        S.pos = first_pos(it) + 4 + 2 * (emitted - at[size_t(e)].words);  // the two words of the initial state, then one per renormalisation of the pixels above
+        memcpy(rec, &S, sizeof S);
+        memcpy(rec + R.tab, tab.data(), kQTab);
+        const DecodeCheckpoint H = decode_head(it, I.every, r, S.pos & ~511ull, canonical_sha(rows_sha));
+        memcpy(ck, &H, sizeof H);
+        seal(ck, I.entry_bytes);
+    }
+    IndexHead H = index_head(it, I.every, I.count, stream_bytes);
+    sha256_of(I.out, stream_bytes, H.stream_sha);
+    index_close(I.index, &H, I.count, I.entry_bytes);
+    q.ilens[I.k] = long(index_total_bytes(I.count, I.entry_bytes));
+}
+
+// One driver: holds one group for the whole call and steps its slots through the batch's images.
+static void qidx_driver(QIdxCall &q, std::vector<std::unique_ptr<QIdxImage>> &images) {
+    nblic_amd_ctx *c = q.c;
+    if (hipSetDevice(c->device) != hipSuccess) { q.failed = true; return; }
+    const int gid = take_group(c);
+    {
+        Group &g = c->groups[size_t(gid)];
+        const hipStream_t st = g.stream;
+        const int n_slots = int(g.slots.size()), n_bufs = 2 * n_slots;
+        struct Live { QIdxImage *im = nullptr; int row0 = 0, band = 0, buf = -1; const uint8_t *plane = nullptr; QIdxLayout lay{}; };
+        std::vector<Live> live{size_t(n_slots)};
+        const auto bufs = std::make_shared<QIdxFree>();
+        std::vector<int> slot_of(size_t(n_slots), 0), ring_jobs(size_t(kQIdxDepth), 0), ring_slot(size_t(kQIdxDepth) * size_t(n_slots), 0);
+        std::vector<size_t> rec_at(size_t(n_slots), 0);
+        const size_t rec_room = up256(kQDecodeStateBytes + 2 * size_t(NBLIC_MAX_WIDTH));
+        double split[5] = {0}; long steps = 0;
+        bool ok = true;
+        if (g.qidx_bufs.empty()) {                                       // the group's first call of this kind
+            g.qidx_bufs.resize(size_t(n_bufs));
+            g.qidx_ready.resize(size_t(n_bufs));
+            for (auto &e : g.qidx_ready) ok = ok && e.create(hipEventDisableTiming | hipEventBlockingSync) == hipSuccess;
+            ok = ok && g.qidx_jobs.alloc(size_t(kQIdxDepth) * size_t(n_slots)) == hipSuccess && g.qidx_tasks.alloc(size_t(kQIdxDepth) * size_t(n_slots)) == hipSuccess &&
+                 g.qidx_totals.alloc(size_t(kQIdxDepth) * size_t(n_slots) * kTotalsSlot) == hipSuccess && g.qidx_d_tasks.alloc(size_t(n_slots)) == hipSuccess &&
+                 g.qidx_d_recs.alloc(size_t(n_slots) * rec_room) == hipSuccess;
+            if (!ok) { g.qidx_bufs.clear(); g.qidx_ready.clear(); }
+        }
+        for (int b = 0; ok && b < n_bufs; b++) bufs->free.push_back(b);
+        hipEvent_t *ev = g.tm.ev;                                        // four marks a queued step
+        // Step t - kQIdxDepth has left the GPU: its ring entry is free, its marks and its block counts are read.
+        auto retire = [&](int e) {
+            if (ring_jobs[size_t(e)] == 0) return true;
+            if (hipEventSynchronize(ev[4 * e + 3]) != hipSuccess) return false;
+            for (int k = 0; k < 3; k++) {
+                float ms = 0.f;
+                if (hipEventElapsedTime(&ms, ev[4 * e + k], ev[4 * e + k + 1]) == hipSuccess) split[k == 0 ? 0 : k + 1] += ms;
+            }
+            for (int j = 0; j < ring_jobs[size_t(e)]; j++)
+                count_long_chains(c, g.qidx_totals + (size_t(e) * size_t(n_slots) + size_t(ring_slot[size_t(e) * size_t(n_slots) + size_t(j)])) * kTotalsSlot);
+            ring_jobs[size_t(e)] = 0;
+            return true;
+        };
+        for (long t = 0; ok && !q.failed; t++) {
+            const int e = int(t % kQIdxDepth);
+            if (!(ok = retire(e))) break;
+            // ---- which image each slot works on
+            for (int k = 0; k < n_slots && ok; k++) {
+                Live &L = live[size_t(k)];
+                if (L.im && L.row0 >= L.im->h) L.im = nullptr;           // (its worker has the buffer)
+                while (!L.im) {
+                    const int j = q.next.fetch_add(1);
+                    if (j >= q.n) break;
+                    QIdxImage *I = images[size_t(j)].get();
+                    if (!I) continue;                                    // refused before the call started
+                    Slot &s = g.slots[size_t(k)];
+                    const auto w0 = std::chrono::steady_clock::now();
+                    L.buf = bufs->take();                                 // every buffer out: the workers are behind
+                    split[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+                    L.im = I; L.row0 = 0;
+                    L.lay = qidx_layout(*I, q.on_device && I->every);
+                    Locked &B = g.qidx_bufs[size_t(L.buf)];
+                    L.band = q.band_rows > 0 ? std::min(q.band_rows, I->h) : serial_rows_per_launch(I->h, I->w, 1, 0);      // stream_open's rule
+                    const size_t n = size_t(I->h) * size_t(I->w), band_px = size_t(L.band) * size_t(I->w);
+                    // a workspace that has to grow is still read by the steps in the queue
+                    if ((band_px > s.px_cap || (!q.on_device && n > s.d_img.capacity())) && hipStreamSynchronize(st) != hipSuccess) { ok = false; break; }
+                    if (!(ok = (L.lay.bytes <= B.capacity() * 2 || B.alloc((L.lay.bytes + L.lay.bytes / 8 + 4096) / 2)) && ensure_pixels(s, band_px, false))) break;
+                    if (q.on_device) L.plane = q.imgs[j];
+                    else {
+                        if (!(ok = s.d_img.reserve(n) == hipSuccess && hipMemcpyAsync(s.d_img, q.imgs[j], n, hipMemcpyHostToDevice, st) == hipSuccess)) break;
+                        L.plane = s.d_img;
+                    }
+                }
+            }
+            if (!ok) break;
+            // ---- 1. job records of the live slots, and the tasks of the bands that end on an entry row
+            E1Job *const hj = g.qidx_jobs + size_t(e) * size_t(n_slots);
+            IndexRecordTask *const ht = g.qidx_tasks + size_t(e) * size_t(n_slots);
+            int n_jobs = 0, n_tasks = 0;
+            for (int k = 0; k < n_slots; k++) {
+                Live &L = live[size_t(k)];
+                if (!L.im) continue;
+                const QIdxImage &I = *L.im;
+                int rows = std::min(L.band, I.h - L.row0);
+                if (I.every) rows = std::min(rows, I.every - L.row0 % I.every);           // a band never crosses an entry row
+                E1Buffers b = g.slots[size_t(k)].b;
+                b.img = L.plane + size_t(L.row0) * size_t(I.w);
+                hj[n_jobs] = e1_job_front(b, rows, I.w, 0, 0, long_chains_of(c));
+                hj[n_jobs].row0 = L.row0;
+                const int r = L.row0 + rows;
+                rec_at[size_t(n_jobs)] = SIZE_MAX;
+                if (I.every && r % I.every == 0 && r < I.h) {
+                    rec_at[size_t(n_jobs)] = size_t(n_tasks) * rec_room;
+                    ht[n_tasks++] = IndexRecordTask{n_jobs, 0, (unsigned long long)(rec_at[size_t(n_jobs)])};
+                }
+                ring_slot[size_t(e) * size_t(n_slots) + size_t(n_jobs)] = k;
+                slot_of[size_t(n_jobs++)] = k;
+            }
+            if (n_jobs == 0) break;
+            ok = hipMemcpyAsync(g.d_jobs, hj, size_t(n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, st) == hipSuccess &&
+                 (!n_tasks || hipMemcpyAsync(g.qidx_d_tasks, ht, size_t(n_tasks) * sizeof(IndexRecordTask), hipMemcpyHostToDevice, st) == hipSuccess);
+            if (!ok) break;
+            hipEventRecord(ev[4 * e], st);
+            // ---- 2. the model stage of every band, 3. the decoder records
+            q_launch_model_band(g.d_jobs, hj, n_jobs, st);
+            hipEventRecord(ev[4 * e + 1], st);
+            q_launch_index_records(g.d_jobs, g.qidx_d_tasks, n_tasks, g.qidx_d_recs, st);
+            hipEventRecord(ev[4 * e + 2], st);
+            // ---- 4. the band's words and its record into the image's buffer; behind an image's last band its histograms
+            //         (and a device input's rows), and the image goes to a worker
+            ok = hipMemcpyAsync(g.qidx_totals + size_t(e) * size_t(n_slots) * kTotalsSlot, g.d_totals, size_t(n_slots) * kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+            for (int j = 0; j < n_jobs && ok; j++) {
+                const int k = slot_of[size_t(j)];
+                Live &L = live[size_t(k)];
+                QIdxImage *I = L.im;
+                const Slot &s = g.slots[size_t(k)];
+                uint8_t *const base = reinterpret_cast<uint8_t *>(static_cast<uint16_t *>(g.qidx_bufs[size_t(L.buf)]));
+                const int rows = hj[j].h, r = L.row0 + rows;
+                ok = hipMemcpyAsync(base + 2 * size_t(L.row0) * size_t(I->w), s.b.pxs, size_t(hj[j].n) * sizeof(uint16_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+                if (ok && rec_at[size_t(j)] != SIZE_MAX)
+                    ok = hipMemcpyAsync(base + L.lay.recs + size_t(r / I->every - 1) * L.lay.rec_stride, g.qidx_d_recs + rec_at[size_t(j)],
+                                        kQDecodeStateBytes + 2 * size_t(I->w), hipMemcpyDeviceToHost, st) == hipSuccess;
+                L.row0 = r;
+                if (!ok || r < I->h) continue;
+                const hipEvent_t ready = g.qidx_ready[size_t(L.buf)];
+                ok = hipMemcpyAsync(base + L.lay.hist, s.b.qhist, 12 * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                     (L.lay.bytes == L.lay.rows || hipMemcpyAsync(base + L.lay.rows, L.plane, L.lay.bytes - L.lay.rows, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+                     hipEventRecord(ready, st) == hipSuccess;
+                if (!ok) { L.row0 = 0; continue; }                       // (not handed over: the driver gives the buffer back below)
+                const QIdxLayout lay = L.lay; const int buf = L.buf;
+                q.pool.post([&q, bufs, I, base, lay, ready, buf] { qidx_finish(q, *I, base, lay, ready); bufs->give(buf); });
+            }
+            hipEventRecord(ev[4 * e + 3], st);
+            ring_jobs[size_t(e)] = n_jobs;
+            steps++;
+        }
+        if (!ok) { q.failed = true; fprintf(stderr, "[nblic_amd] indexed effort-0 batch: a device step failed\n"); }
+        const bool drained = hipStreamSynchronize(st) == hipSuccess;
+        for (int e = 0; e < kQIdxDepth && ok && drained; e++) retire(e);
+        for (auto &L : live) if (L.im && L.row0 < L.im->h && L.buf >= 0) bufs->give(L.buf);    // images the call ended under
+        bufs->wait_all();
+        std::lock_guard<std::mutex> l(q.m);
+        for (int k = 0; k < 5; k++) q.split[k] += split[k];
+        q.steps += steps;
+    }
+    release_group(c, gid);
+}
+
+static int qencode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *const *imgs, bool on_device, const int *hs, const int *ws, const int *every,
+                                 int band_rows, uint16_t *const *outs, const size_t *caps, long *lens, unsigned char *const *indexes, const size_t *icaps, long *ilens) {
+    if (!c || c->broken || n < 1 || !imgs || !hs || !ws || !every || !outs || !caps || !lens || (indexes && (!icaps || !ilens))) return -1;
+    for (int k = 0; k < n; k++) if (every[k] < 0 || !imgs[k] || !outs[k]) return -1;
+    if (hipSetDevice(c->device) != hipSuccess) return -1;
+    QIdxCall q{c, n, imgs, on_device, hs, ws, band_rows, lens, ilens};
+    std::vector<std::unique_ptr<QIdxImage>> images{size_t(n)};
+    int n_live = 0;
+    for (int k = 0; k < n; k++) {                                        // what can be refused is refused before anything is launched
+        lens[k] = -1;
+        if (ilens) ilens[k] = 0;
+        if (!size_ok(hs[k], ws[k], c->max_px) || caps[k] < 6) continue;
+        auto I = std::make_unique<QIdxImage>();
+        I->k = k; I->h = hs[k]; I->w = ws[k]; I->out = outs[k]; I->cap = std::min(caps[k], size_t(1) << 45);
+        I->host_plane = on_device ? nullptr : imgs[k];
+        if (indexes && indexes[k] && every[k] >= 1 && every[k] < hs[k]) {
+            const long need = index_bytes(1, hs[k], ws[k], 0, every[k]);
+            if (need < 0 || icaps[k] < size_t(need)) ilens[k] = -1;                       // the stream is still delivered
+            else { I->every = every[k]; I->index = indexes[k]; I->entry_bytes = index_entry_bytes(1, ws[k], 0); I->count = (hs[k] - 1) / every[k]; }
+        }
+        images[size_t(k)] = std::move(I);
+        n_live++;
+    }
+    if (n_live) {
+        const int group_size = int(c->groups[0].slots.size());
+        const int n_drivers = std::min(int(c->groups.size()), (n_live + group_size - 1) / group_size);
+        q.pool.start(std::max(1, c->coders_wanted));
+        std::vector<std::thread> drivers;
+        for (int i = 0; i < n_drivers; i++) drivers.emplace_back([&] { qidx_driver(q, images); });
         for (auto &t : drivers) t.join();
     }
     {
@@ -4410,6 +4697,23 @@ int nblic_amd_encode_batch_indexed(nblic_amd_ctx *c, int n_images, const unsigne
                                    unsigned char *const *outs, const size_t *out_caps, long *out_lens,
                                    unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
     return encode_batch_indexed(c, n_images, imgs, imgs_on_device != 0, heights, widths, every_rows, band_rows, outs, out_caps, out_lens, indexes, index_caps, index_lens);
+}
+int nblic_amd_qencode_batch_indexed(nblic_amd_ctx *c, int n_images, const unsigned char *const *imgs, int imgs_on_device,
+                                    const int *heights, const int *widths, const int *every_rows, int band_rows,
+                                    uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words,
+                                    unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
+    return qencode_batch_indexed(c, n_images, imgs, imgs_on_device != 0, heights, widths, every_rows, band_rows, outs, out_caps_words, out_len_words, indexes, index_caps, index_lens);
+}
+long nblic_amd_debug_q_entropy(int height, int width, const uint16_t *words, const unsigned int *hist, const int *entry_rows, int n_entries,
+                               uint16_t *out, size_t cap_words, unsigned int *states, unsigned long long *words_emitted) {
+    if (!words || !hist || !out || n_entries < 0 || (n_entries > 0 && (!entry_rows || !states || !words_emitted))) return -2;
+    if (height < 1 || width < 1 || height > kIndexMaxSide || width > kIndexMaxSide) return -2;
+    if (!q_words_ok(words, size_t(height) * size_t(width), hist)) return -2;
+    std::vector<QEntryState> at;
+    at.resize(size_t(n_entries));
+    const long n = q_entropy_encode_entries(out, cap_words, height, width, words, hist, entry_rows, n_entries, at.data());
+    for (int k = 0; n >= 0 && k < n_entries; k++) { states[k] = at[size_t(k)].state; words_emitted[k] = at[size_t(k)].words; }
+    return n;
 }
 long nblic_amd_index_bytes(int kind, int height, int width, int effort, int every_rows) { return index_bytes(kind, height, width, effort, every_rows); }
 long nblic_amd_indexed_batch_split(nblic_amd_ctx *c, double ms[5]) {

@@ -4,7 +4,8 @@
 // histograms.  What is left (QNBLIC.c:625-655) is small or serial: scale every histogram to a sum
 // of 2^15, write them in the reference's compact 16-bit code, then push the symbols through one
 // 32-bit rANS coder LAST PIXEL FIRST and reverse the emitted words.  The decoder side builds the
-// per-level slot tables for the device engine.
+// per-level slot tables for the device engine.  The pass can report the coder in front of given
+// rows (q_entropy_encode_entries): what a seek index's entries hold of it.
 //
 // The histogram scaling is the only floating point on any NBLIC path and it decides bits of the
 // stream, so this file is compiled by the host compiler with contraction off (csrc/Makefile):
@@ -12,6 +13,8 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+
+#include "q_entropy.h"
 
 namespace nblic {
 
@@ -83,11 +86,25 @@ static const uint16_t *q_read_hist(const uint16_t *p, const uint16_t *end, uint3
     return p;
 }
 
+// true when every word names a level below 12 and a symbol its level's histogram counts: what the pass below divides by.
+bool q_words_ok(const uint16_t *qy, size_t n, const uint32_t *hist) {
+    for (size_t t = 0; t < n; t++)
+        if ((qy[t] & 0xFF) >= kQLevels || hist[(qy[t] & 0xFF) * kQSyms + (qy[t] >> 8)] == 0) return false;
+    return true;
+}
+
 // Entropy stage of QNBLICcompress.  qy[t] = level | symbol << 8; hist = 12 x 256 raw counts.
-// Returns the stream length in 16-bit words (header included) or -1 if cap_words is too small.
-long q_entropy_encode(uint16_t *out, size_t cap_words, int h, int w, const uint16_t *qy, const uint32_t *hist_in) {
+// entry_rows[0 .. n_entries): rows 0 < r < h in ascending order; entries[k] receives the coder in front of row
+// entry_rows[k] (above).  The stream does not depend on them.
+// Returns the stream length in 16-bit words (header included), -1 if cap_words is too small, -2 for entry rows that are
+// out of range or out of order (nothing is written then).
+long q_entropy_encode_entries(uint16_t *out, size_t cap_words, int h, int w, const uint16_t *qy, const uint32_t *hist_in,
+                              const int *entry_rows, int n_entries, QEntryState *entries) {
     uint32_t freq[kQLevels][kQSyms], start[kQLevels][kQSyms];
     const size_t n = (size_t)h * (size_t)w;
+    if (n_entries < 0 || (n_entries > 0 && (!entry_rows || !entries))) return -2;
+    for (int k = 0; k < n_entries; k++)
+        if (entry_rows[k] < 1 || entry_rows[k] >= h || (k > 0 && entry_rows[k] <= entry_rows[k - 1])) return -2;
     if (cap_words < 6) return -1;
     uint16_t *p = out, *const end = out + cap_words;
     *p++ = (uint16_t)('Q' | ('0' << 8)); *p++ = (uint16_t)('.' | ('2' << 8));            // QNBLIC.c:463-473, host byte order
@@ -102,19 +119,29 @@ long q_entropy_encode(uint16_t *out, size_t cap_words, int h, int w, const uint1
     }
     uint16_t *const body = p;
     uint32_t x = 1u << kQAnsBits;                                                       // QNBLIC.c:238-253
-    for (size_t t = n; t-- > 0;) {
-        const uint32_t e = qy[t], f = freq[e & 0xFF][e >> 8], s0 = start[e & 0xFF][e >> 8];
-        uint32_t q = x / f;
-        if (q > (1u << (2 * kQAnsBits - kQNormBits)) - 1) {
-            if (p >= end) return -1;
-            *p++ = (uint16_t)x; x >>= kQAnsBits; q = x / f;
+    size_t t = n;
+    for (int k = n_entries; k >= 0; k--) {                                              // pixels down to the entry row's first, then the entry
+        const size_t stop = k > 0 ? (size_t)entry_rows[k - 1] * (size_t)w : 0;
+        while (t-- > stop) {
+            const uint32_t e = qy[t], f = freq[e & 0xFF][e >> 8], s0 = start[e & 0xFF][e >> 8];
+            uint32_t q = x / f;
+            if (q > (1u << (2 * kQAnsBits - kQNormBits)) - 1) {
+                if (p >= end) return -1;
+                *p++ = (uint16_t)x; x >>= kQAnsBits; q = x / f;
+            }
+            x = (x - q * f) + (q << kQNormBits) + s0;
         }
-        x = (x - q * f) + (q << kQNormBits) + s0;
+        t = stop;
+        if (k > 0) entries[k - 1] = QEntryState{x, 0u, (unsigned long long)(p - body)};
     }
     if (p + 2 > end) return -1;
     *p++ = (uint16_t)x; *p++ = (uint16_t)(x >> kQAnsBits);
     for (uint16_t *a = body, *b = p - 1; a < b; a++, b--) { uint16_t t = *a; *a = *b; *b = t; }   // decoder reads forwards
     return (long)(p - out);
+}
+
+long q_entropy_encode(uint16_t *out, size_t cap_words, int h, int w, const uint16_t *qy, const uint32_t *hist_in) {
+    return q_entropy_encode_entries(out, cap_words, h, w, qy, hist_in, nullptr, 0, nullptr);
 }
 
 // Decoder front matter (QNBLIC.c:505-518): parses the header and the twelve histograms, builds

@@ -1,0 +1,29 @@
+// q_entropy.h -- the host half of the QNBLIC (effort 0) path as the pipeline calls it (q_entropy.cpp).  No HIP, no device.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace nblic {
+
+// What the coder holds in front of an entry row r (the indexed effort-0 batch, pipeline.hip): the rANS pass runs LAST PIXEL
+// FIRST, so its state once pixel r * w has been coded -- and before pixel r * w - 1 is looked at -- is the state a decoder
+// holds when it has decoded (and renormalised after) pixel r * w - 1: the decoder undoes the pass step by step.  `words`
+// counts the renormalisation words emitted up to that moment, the one pixel r * w itself may have cost included; the
+// decoder has then consumed all the others, so with W words in all (the two final ones aside) it stands
+// 2 * (2 + W - words) bytes behind the first rANS word of the reversed stream.
+struct QEntryState { uint32_t state, reserved; unsigned long long words; };
+
+// Entropy stage of QNBLICcompress.  qy[t] = level | symbol << 8; hist = 12 x 256 raw counts.
+// Returns the stream length in 16-bit words (header included) or -1 if cap_words is too small.
+long q_entropy_encode(uint16_t *out, size_t cap_words, int h, int w, const uint16_t *qy, const uint32_t *hist_in);
+// The same stage.  entry_rows[0 .. n_entries): rows 0 < r < h in ascending order; entries[k] receives the coder in front
+// of row entry_rows[k] (above).  The stream does not depend on them.  Also -2: entry rows that are out of range or out of
+// order (nothing is written then).
+long q_entropy_encode_entries(uint16_t *out, size_t cap_words, int h, int w, const uint16_t *qy, const uint32_t *hist_in,
+                              const int *entry_rows, int n_entries, QEntryState *entries);
+// true when every word names a level below 12 and a symbol its level's histogram counts: what the pass divides by.
+bool q_words_ok(const uint16_t *qy, size_t n, const uint32_t *hist);
+// Decoder front matter (q_entropy.cpp).
+long q_decode_tables(const uint16_t *in, size_t n_words, int *h, int *w, uint32_t *freq, uint32_t *start, uint8_t *slot);
+
+}  // namespace nblic
