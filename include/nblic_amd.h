@@ -596,6 +596,58 @@ int nblic_amd_debug_device_code(nblic_amd_ctx *ctx, int n_jobs, const unsigned s
                                 const size_t *pack_words, const unsigned int *n_bins, const unsigned int *caps,
                                 unsigned char *const *outs, long *lens);
 
+/* The device rANS stage of effort 0 (csrc/q_device_coder.hip, k_q_rans_lanes: one wave lane per image, launches that
+ * resume from a record in device memory; the lane's arithmetic and resumption are csrc/q_rans.h, shared with the host).
+ *
+ * nblic_amd_set_device_qcoder puts it into the batch pipeline.  ctx == NULL addresses the drop-in context.  mode:
+ *   0  host (the default): effort-0 images are coded by the host coder threads, as without this call; the thread sleeps
+ *   1  device: every effort-0 image of nblic_amd_qencode_batch and of the QNBLIC*compress drop-ins goes to the device
+ *      stage; the coder threads take none
+ *   2  shared: the device thread takes the newest waiting effort-0 images, all but one per host coder thread, and only
+ *      while no host coder thread is idle.  Bytes are identical; who codes which image is a race
+ * One thread per context (started by the first call that names mode 1 or 2) keeps a rolling list of jobs on one stream;
+ * every launch advances every job by at most symbols_per_launch symbols (0: the default), and two launches are queued
+ * per wait while no image waits to be admitted.  Returns the mode set, or -1.  To be called between batches.
+ * Sizing n_host_buffers (nblic_amd_create_ex) for mode 1: an image being coded on the device holds its coded-bin buffer,
+ * 2 bytes per pixel of HBM, for as long as its lane takes -- pixels / lane rate, seconds for a large frame -- and the
+ * model stage waits for a free buffer before it launches an image.  So n_host_buffers is the number of lanes that can
+ * be in flight: give it the batch size (or as many images as the HBM left over holds) or the model stage is throttled
+ * to the lanes' pace.  nblic_amd_qencode_batch_indexed does not use the device stage.
+ * nblic_amd_device_qcoder_stats: totals since the context was created -- symbols coded by retired jobs, kernel launches,
+ * images, and the GPU time between the first and the last launch of every wait, in ms.  Returns 0, or -1.
+ *
+ * The three calls below run the stage on its own.
+ *
+ * nblic_amd_qcoder_selftest: the kernel's quotient routines (floor(x / f) without a divide) on the device against 64-bit
+ * division, for every f in 1 .. 32767 crossed with 1 << 16, 2^32 - 1, the powers of two and their neighbours, 4096
+ * xorshift values and (1 << 17) * f with its two neighbours.  ctx == NULL: the drop-in context.  Returns the number of
+ * mismatches, or -1.
+ *
+ * nblic_amd_debug_q_rans_host: host only, no context.  QNBLIC's entropy stage on height x width caller-made words
+ * (level | symbol << 8) and their 12 x 256 raw counts, with the pass run by ONE lane of csrc/q_rans.h that stops every
+ * symbols_per_launch symbols (<= 0: never) and resumes from its record.  Returns the stream's words (front matter
+ * included; the bytes of nblic_amd_debug_q_entropy), -1 when cap_words is too small, -2 for arguments it refuses.
+ *
+ * nblic_amd_debug_device_q_entropy: a resumed launch sequence of k_q_rans_lanes on 1 .. 4096 caller-made jobs.  Job k is
+ * n_symbols[k] words (1 .. 1 << 24), which the caller has padded to the end of the last 512-byte window -- words[k] holds
+ * ceil(n / 256) * 256 of them and all are uploaded verbatim, 256-byte aligned; the kernel fetches the padding and must
+ * not use it -- and the 12 x 256 raw counts hists[k].  outs[k] has room for caps_words[k] words.  The front matter is
+ * written there by the host (its header names the image of n pixels whose width is the largest divisor of n below
+ * 65536; an n without two sides below 65536, such as a prime above 65535, is refused with -1); the lane gets a device region of what is left, followed by a guard of at least 64 patterned bytes, and every
+ * launch advances every unfinished job by symbols_per_launch symbols (0: the default).  lens[k] is the stream's words,
+ * or -1: caps_words[k] was too small (a job without room for its front matter is not launched at all).
+ * Returns 0; -1 for arguments it refuses (a null pointer, a word that names a level above 11 or a symbol its histogram
+ * does not count, sizes out of range, more than 8192 launches; nothing is launched); -2 when a HIP call failed; -3 when
+ * a guard byte, or a byte of a region in front of the words it reported, has changed.                                   */
+int nblic_amd_set_device_qcoder(nblic_amd_ctx *ctx, int mode, long symbols_per_launch);
+int nblic_amd_device_qcoder_stats(nblic_amd_ctx *ctx, double *symbols, long *launches, long *images, double *kernel_ms);
+int nblic_amd_qcoder_selftest(nblic_amd_ctx *ctx);
+long nblic_amd_debug_q_rans_host(int height, int width, const uint16_t *words, const unsigned int *hist, long symbols_per_launch,
+                                 uint16_t *out, size_t cap_words);
+int nblic_amd_debug_device_q_entropy(nblic_amd_ctx *ctx, int n_jobs, const uint16_t *const *words, const unsigned int *n_symbols,
+                                     const unsigned int *const *hists, const size_t *caps_words, long symbols_per_launch,
+                                     uint16_t *const *outs, long *lens);
+
 /* Debug hook used by the chain kernels' tests: ONE launch sequence of the staged model stages BEHIND S1 on n records the
  * caller supplies (1 .. 1 << 22), as one job.  x[n] are the pixel values, rec1[n] the S1 records, both uploaded verbatim.
  *   model 0 (NBLIC -e1): rec1 is csrc/model.h pack_s1 (px0 | adr << 8 | qw << 19 | qu's low bit << 24 | qv_rel << 25).  Runs

@@ -48,6 +48,7 @@ EXPORTS = (
     "nblic_amd_stream_set_index", "nblic_amd_stream_index", "nblic_amd_set_index_round", "nblic_amd_stream_set_front",
     "nblic_amd_encode_batch_indexed", "nblic_amd_index_bytes", "nblic_amd_indexed_batch_split",
     "nblic_amd_qencode_batch_indexed", "nblic_amd_debug_q_entropy",
+    "nblic_amd_set_device_qcoder", "nblic_amd_device_qcoder_stats", "nblic_amd_qcoder_selftest", "nblic_amd_debug_q_rans_host", "nblic_amd_debug_device_q_entropy",
     "nblic_amd_decode_batch_indexed", "nblic_amd_indexed_decode_split", "nblic_amd_indexed_decode_plan", "nblic_amd_debug_index_kernels",
     "nblic_amd_index_build_batch", "nblic_amd_index_build_split", "nblic_amd_index_build_plan", "nblic_amd_debug_index_capture",
     "nblic_amd_index_pack", "nblic_amd_index_pack_bound", "nblic_amd_index_unpack", "nblic_amd_index_unpacked_bytes", "nblic_amd_index_is_packed", "nblic_amd_debug_index_unpack",
@@ -286,6 +287,18 @@ def load_library() -> C.CDLL:
         lib.nblic_amd_debug_device_code.restype = C.c_int
         lib.nblic_amd_debug_device_code.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), ip, ip, C.c_int, C.POINTER(C.c_void_p),
                                                     C.POINTER(C.c_size_t), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_void_p), C.POINTER(C.c_long)]
+    if hasattr(lib, "nblic_amd_qcoder_selftest"):                  # (an older build loaded through NBLIC_AMD_LIB has none of the three)
+        lib.nblic_amd_set_device_qcoder.restype = C.c_int
+        lib.nblic_amd_set_device_qcoder.argtypes = [C.c_void_p, C.c_int, C.c_long]
+        lib.nblic_amd_device_qcoder_stats.restype = C.c_int
+        lib.nblic_amd_device_qcoder_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_double)]
+        lib.nblic_amd_qcoder_selftest.restype = C.c_int
+        lib.nblic_amd_qcoder_selftest.argtypes = [C.c_void_p]
+        lib.nblic_amd_debug_q_rans_host.restype = C.c_long
+        lib.nblic_amd_debug_q_rans_host.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_size_t]
+        lib.nblic_amd_debug_device_q_entropy.restype = C.c_int
+        lib.nblic_amd_debug_device_q_entropy.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint), C.POINTER(C.c_void_p),
+                                                         C.POINTER(C.c_size_t), C.c_long, C.POINTER(C.c_void_p), C.POINTER(C.c_long)]
     if hasattr(lib, "nblic_amd_debug_model_stages"):
         lib.nblic_amd_debug_model_stages.restype = C.c_int
         lib.nblic_amd_debug_model_stages.argtypes = [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p, C.c_void_p]
@@ -387,13 +400,7 @@ def q_entropy_entries(words: np.ndarray, entry_rows=(), hist: Optional[np.ndarra
     if words.ndim != 2 or words.size == 0:
         raise ValueError("words must be a non-empty 2-D array")
     h, w = words.shape
-    if hist is None:
-        hist = np.bincount((words & 0xFF).astype(np.int64).ravel() * 256 + (words >> 8).astype(np.int64).ravel(), minlength=12 * 256)
-        if hist.size != 12 * 256:
-            raise ValueError("a word names a level above 11")
-    hist = np.ascontiguousarray(hist, np.uint32).reshape(-1)
-    if hist.size != 12 * 256:
-        raise ValueError("hist must hold 12 x 256 counts")
+    hist = _q_hist(words, hist)
     rows = [int(r) for r in entry_rows]
     k = len(rows)
     cap = 2 * h * w + 4096 if cap_words is None else int(cap_words)
@@ -406,6 +413,54 @@ def q_entropy_entries(words: np.ndarray, entry_rows=(), hist: Optional[np.ndarra
     if n < 0:
         return None, []
     return out[:n].tobytes(), [(int(s), int(e)) for s, e in zip(states[:k], emitted[:k])]
+
+
+def _q_hist(words: np.ndarray, hist) -> np.ndarray:
+    """The 12 x 256 counts of ``level | symbol << 8`` words as the library takes them (counted from ``words`` when None)."""
+    if hist is None:
+        hist = np.bincount((words & 0xFF).astype(np.int64).ravel() * 256 + (words >> 8).astype(np.int64).ravel(), minlength=12 * 256)
+        if hist.size != 12 * 256:
+            raise ValueError("a word names a level above 11")
+    hist = np.ascontiguousarray(hist, np.uint32).reshape(-1)
+    if hist.size != 12 * 256:
+        raise ValueError("hist must hold 12 x 256 counts")
+    return hist
+
+
+def q_rans_host(words: np.ndarray, hist: Optional[np.ndarray] = None, symbols_per_launch: int = 0, cap_words: Optional[int] = None) -> Optional[bytes]:
+    """QNBLIC's entropy stage with the pass run the way a lane of the device stage runs it (``nblic_amd_debug_q_rans_host``;
+    host only, no device): ``words`` is a 2-D uint16 array of ``level | symbol << 8``, ``hist`` the 12 x 256 counts (default:
+    counted from ``words``); the lane stops every ``symbols_per_launch`` symbols (0: never) and resumes from its record.
+    Returns the stream, or None when ``cap_words`` is too small.  Raises ``ValueError`` for what the library refuses."""
+    words = np.ascontiguousarray(words, np.uint16)
+    if words.ndim != 2 or words.size == 0:
+        raise ValueError("words must be a non-empty 2-D array")
+    h, w = words.shape
+    hist = _q_hist(words, hist)
+    cap = 2 * h * w + 4096 if cap_words is None else int(cap_words)
+    out = np.empty(max(cap, 1), np.uint16)
+    n = int(load_library().nblic_amd_debug_q_rans_host(h, w, words.ctypes.data, hist.ctypes.data, int(symbols_per_launch), out.ctypes.data, cap))
+    if n == -2:
+        raise ValueError("nblic_amd_debug_q_rans_host refused its arguments")
+    return None if n < 0 else out[:n].tobytes()
+
+
+def set_device_qcoder(ctx, mode: int, symbols_per_launch: int = 0) -> int:
+    """Where effort-0 images are entropy coded (``nblic_amd_set_device_qcoder``): 0 host coder threads, 1 the device stage,
+    2 shared.  ``ctx`` is a ``Context``, or None for the context behind the drop-in operators.  Returns the mode set."""
+    r = int(load_library().nblic_amd_set_device_qcoder(None if ctx is None else ctx.handle, int(mode), int(symbols_per_launch)))
+    if r < 0:
+        raise ValueError("nblic_amd_set_device_qcoder refused its arguments")
+    return r
+
+
+def q_hook_shape(n: int) -> Tuple[int, int]:
+    """(height, width) that ``Context.debug_device_q_entropy`` writes into the header of a job of ``n`` symbols: the width
+    is the largest divisor of ``n`` below 65536."""
+    w = min(int(n), 65535)
+    while n % w:
+        w -= 1
+    return n // w, w
 
 
 def out_capacity(h: int, w: int) -> int:
@@ -1262,6 +1317,51 @@ class Context:
             raise DeviceCoderGuardError("nblic_amd_debug_device_code: the kernel wrote outside its outputs, or beyond a length it reported")
         if rc != 0:
             raise RuntimeError("nblic_amd_debug_device_code failed")
+        return [None if lens[i] < 0 else outs[i][: lens[i]].tobytes() for i in range(k)]
+
+    def set_device_qcoder(self, mode: int, symbols_per_launch: int = 0) -> int:
+        """0: effort 0 is coded by the host coder threads; 1: by the device stage; 2: shared (``nblic_amd_set_device_qcoder``)."""
+        return set_device_qcoder(self, mode, symbols_per_launch)
+
+    def device_qcoder_stats(self) -> dict:
+        """Totals of the device rANS stage since the context was created (``nblic_amd_device_qcoder_stats``)."""
+        s, k = C.c_double(), C.c_double()
+        n, i = C.c_long(), C.c_long()
+        if self.lib.nblic_amd_device_qcoder_stats(self.handle, C.byref(s), C.byref(n), C.byref(i), C.byref(k)) != 0:
+            raise RuntimeError("nblic_amd_device_qcoder_stats failed")
+        return {"symbols": s.value, "launches": int(n.value), "images": int(i.value), "kernel_ms": k.value}
+
+    def qcoder_selftest(self) -> int:
+        """The device rANS stage's quotient routines against 64-bit division (``nblic_amd_qcoder_selftest``): mismatches."""
+        return int(self.lib.nblic_amd_qcoder_selftest(self.handle))
+
+    def debug_device_q_entropy(self, jobs: Sequence[tuple], symbols_per_launch: int = 0) -> List[Optional[bytes]]:
+        """A resumed launch sequence of the device rANS stage on the caller's own jobs (``nblic_amd_debug_device_q_entropy``).
+        A job is ``(words, n, hist, cap_words)``: 1-D uint16 ``level | symbol << 8`` words which the caller has padded to
+        the end of the last 512-byte window of its ``n`` symbols, the 12 x 256 raw counts of the first ``n``, and the room
+        for the stream in words.  Everything is handed over as it is: the library does the refusing (``ValueError``).
+        Returns per job the stream (its header names ``q_hook_shape(n)``), or None where ``cap_words`` was too small;
+        raises ``DeviceCoderGuardError`` when the kernel wrote a word it may not write."""
+        k = len(jobs)
+        words = [None if j[0] is None else np.ascontiguousarray(j[0], np.uint16) for j in jobs]
+        hists = [None if j[2] is None else np.ascontiguousarray(j[2], np.uint32).reshape(-1) for j in jobs]
+        for wd, j, hs in zip(words, jobs, hists):
+            if wd is not None and wd.size < (int(j[1]) + 255) // 256 * 256:
+                raise ValueError("a job's words must reach the end of its last 512-byte window")
+            if hs is not None and hs.size != 12 * 256:
+                raise ValueError("hist must hold 12 x 256 counts")
+        outs = [np.empty(max(int(j[3]), 1), np.uint16) for j in jobs]
+        lens = (C.c_long * k)()
+        vp = lambda arrs: (C.c_void_p * k)(*[None if a is None else C.c_void_p(a.ctypes.data) for a in arrs])
+        rc = self.lib.nblic_amd_debug_device_q_entropy(
+            self.handle, k, vp(words), (C.c_uint * k)(*[int(j[1]) for j in jobs]), vp(hists), (C.c_size_t * k)(*[int(j[3]) for j in jobs]),
+            int(symbols_per_launch), vp(outs), lens)
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_device_q_entropy refused its arguments")
+        if rc == -3:
+            raise DeviceCoderGuardError("nblic_amd_debug_device_q_entropy: the kernel wrote outside its regions, or in front of the words it reported")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_device_q_entropy failed")
         return [None if lens[i] < 0 else outs[i][: lens[i]].tobytes() for i in range(k)]
 
     def debug_model_stages(self, model: int, x, rec1, ctx_state=None, map_state=None) -> dict:

@@ -40,6 +40,7 @@
 #include "kernels_e1.h"
 #include "lsq_f64.h"
 #include "model.h"
+#include "q_device_coder.h"
 #include "q_entropy.h"
 #include "range_coder.h"
 #include "serial_engine.h"
@@ -275,6 +276,11 @@ struct nblic_amd_ctx {
     std::vector<std::thread> dev_coders;
     int dev_min_outstanding = 0;          // a pack is taken only while at least this many images of the submitted batches are unfinished
     double dev_bins = 0; long dev_packs = 0, dev_images = 0;
+    // device rANS stage of effort 0 (q_device_coder.hip): ONE thread with one stream and a rolling job list (qdev_main)
+    std::thread qdev;                     // started by the first nblic_amd_set_device_qcoder that names mode 1 or 2; sleeps in mode 0
+    int qmode = 0;                        // 0 host, 1 device, 2 shared (guarded by rm)
+    uint32_t q_budget = 0;                // symbols per launch (guarded by rm); 0 until the first set call
+    double qdev_symbols = 0, qdev_kernel_ms = 0; long qdev_launches = 0, qdev_images = 0;   // guarded by stat_m
     // decode batches (nblic_amd_decode_batch): a stream of their own and grow-only device / pinned arenas
     Stream dec_stream, dec_stream2;                                    // decode_batch alternates its chunks between the two
     DevBuf<uint8_t> dec_arena;
@@ -702,7 +708,8 @@ static int coder_take(const nblic_amd_ctx *c) {                  // call with c-
     const size_t q = c->ready.size();
     if (q == 0) return 0;
     const ReadyImage &f = c->ready.front();
-    if (f.kind == 1 || f.pack_n <= 1) return 1;
+    if (f.kind == 1) return c->qmode == 1 ? 0 : 1;               // device mode: the device-qcoder thread takes it (and wakes the coders when it has)
+    if (f.pack_n <= 1) return 1;
     const int max_packs = std::max(1, c->max_take / int(kPackLanes));
     int packs = 0; size_t imgs = 0;
     bool more_may_join = true;
@@ -833,6 +840,10 @@ static void coder_main(nblic_amd_ctx *c, int index) {
 // then it hands up to 64 images to one wave, sleeps in a blocking stream wait, copies the coder bytes
 // to the callers' buffers and completes the images exactly as a host coder thread does.
 constexpr int kDevPack = 64;
+// Symbols a launch of the device rANS stage (q_device_coder.hip) advances a job by when the caller names none: what a
+// lane codes in about 10 ms.  Measured (profiles/r21_device_qcoder_ab.json): 2.9-3.3 M symbols/s per lane, 20-22 ms per
+// launch of 65536 symbols, whether 64 or 2048 lanes are live.
+constexpr uint32_t kQSymbolsPerLaunch = 1u << 15;
 
 static int dev_take(const nblic_amd_ctx *c) {                  // call with c->rm held
     const size_t q = c->ready.size();
@@ -909,6 +920,135 @@ static void dev_coder_main(nblic_amd_ctx *c, int index) {
         if (!good) { for (int k = 0; k < take; k++) im[k].lens[im[k].job] = -1; }
         { std::lock_guard<std::mutex> l(c->stat_m); c->dev_bins += bins; c->dev_packs++; c->dev_images += take; }
         finish_images(c, im, take);
+    }
+}
+
+// ---- device-qcoder thread: QNBLIC's rANS pass on the GPU (q_device_coder.hip) ---------------------------------------------
+// One thread per context, one stream.  Every launch of k_q_rans_lanes holds a wave per 64 images for its whole
+// duration, so launches are bounded (q_budget symbols per job) and there is no hand-out of packs: the thread keeps a
+// ROLLING list of job slots whose records stay in device memory.  Per turn it admits what its mode lets it take, reads
+// each newcomer's raw histogram back (12 KB), runs the front matter on the host straight into the caller's buffer,
+// uploads the table and the record, launches over all slots up to the highest live one, reads one word per slot back,
+// retires the finished jobs (their words are copied behind the front matter, the coded-bin buffer goes back) and goes
+// round again.  While nobody waits to be admitted TWO launches are queued per wait (kQAhead): the job set is the same
+// for both, and a job that the first one finishes is an idle lane in the second.
+// The words are written IN PLACE, downwards from the end of the image's coded-bin buffer (pairs | pad | raw histogram):
+// a pass never emits more words than it has consumed symbols, so the words stay above every symbol still to be read,
+// and the histogram they overwrite was read back before the first launch.
+constexpr int kQAhead = 2;
+constexpr size_t kQHistWords = 2 * 12 * 256;                     // the raw histogram in 16-bit words (launch_q)
+
+static int qdev_take(const nblic_amd_ctx *c) {                  // call with c->rm held: how many QNBLIC images the thread may take now
+    int q = 0;
+    if (c->qmode == 1) { for (const ReadyImage &r : c->ready) q += r.kind == 1; return q; }
+    if (c->qmode != 2 || c->idle_coders > 0) return 0;          // shared: only while no host coder thread is idle,
+    size_t i = c->ready.size();                                  //   the newest ones, and one image per host thread stays
+    while (i > c->coders.size() && c->ready[i - 1].kind == 1) { i--; q++; }
+    return q;
+}
+
+static void qdev_main(nblic_amd_ctx *c) {
+    pthread_setname_np(pthread_self(), "nblic-qdevcoder");
+    struct LiveJob { ReadyImage im; long front = 0; bool used = false; };
+    const size_t slots = (c->cbufs.size() + 63) & ~size_t(63);  // an image in flight holds a coded-bin buffer: never more jobs than buffers
+    Stream st; Event t0, t1;
+    DevBuf<QRansJob> d_jobs; DevBuf<uint32_t> d_tables, d_results;
+    Pinned<QRansJob> h_jobs; Pinned<uint32_t> h_tables, h_results, h_hist;
+    std::vector<LiveJob> live(slots);
+    std::vector<uint32_t> freq(kQRansTable), start(kQRansTable);
+    bool ok = hipSetDevice(c->device) == hipSuccess && st.create(hipStreamNonBlocking) == hipSuccess &&
+              t0.create(hipEventDefault) == hipSuccess && t1.create(hipEventDefault) == hipSuccess &&
+              d_jobs.alloc(slots) == hipSuccess && d_tables.alloc(slots * kQRansTable) == hipSuccess && d_results.alloc(slots) == hipSuccess &&
+              h_jobs.alloc(slots) == hipSuccess && h_tables.alloc(slots * kQRansTable) == hipSuccess && h_results.alloc(slots) == hipSuccess &&
+              h_hist.alloc(slots * kQRansTable) == hipSuccess &&
+              hipMemset(d_jobs, 0, slots * sizeof(QRansJob)) == hipSuccess;          // live == 0: every slot empty
+    if (!ok) { fprintf(stderr, "[nblic_amd] device qcoder: could not set itself up (%s)\n", hipGetErrorString(hipGetLastError())); c->broken = true; }
+    size_t n_live = 0;
+    for (;;) {
+        std::vector<size_t> fresh;
+        bool more_waiting = false;
+        uint32_t budget;
+        {
+            std::unique_lock<std::mutex> l(c->rm);
+            if (n_live == 0) c->rcv.wait(l, [c] { return c->stop || qdev_take(c) > 0; });
+            if (c->stop && n_live == 0) break;
+            int take = qdev_take(c);
+            budget = c->q_budget ? c->q_budget : kQSymbolsPerLaunch;
+            size_t slot = 0;
+            for (size_t i = c->ready.size(); i-- > 0 && take > 0;) {            // from the back: the newest
+                if (c->ready[i].kind != 1) continue;
+                while (slot < slots && live[slot].used) slot++;
+                if (slot == slots) break;
+                live[slot].im = c->ready[i]; live[slot].used = true; live[slot].front = 0;
+                c->ready.erase(c->ready.begin() + long(i));
+                fresh.push_back(slot); take--;
+            }
+            more_waiting = c->batch_to_come > 0 || c->queued_images > 0;       // newcomers may arrive during the next launch
+        }
+        if (!fresh.empty()) c->rcv.notify_all();                                 // a coder thread may find its kind of image at the front now
+        n_live += fresh.size();
+        bool good = ok;
+        // front matter of the newcomers: raw histograms back, scaled and coded on the host, tables and records up
+        for (size_t slot : fresh) {
+            const ReadyImage &q = live[slot].im;
+            const size_t n = size_t(q.h) * size_t(q.w), n_pad = (n + 1) & ~size_t(1);
+            good = good && hipMemcpyAsync(h_hist + slot * kQRansTable, c->cbufs[size_t(q.cb)] + n_pad, kQRansTable * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+        }
+        if (!fresh.empty()) good = hipStreamSynchronize(st) == hipSuccess && good;
+        for (size_t slot : fresh) {
+            LiveJob &L = live[slot];
+            const ReadyImage &q = L.im;
+            const size_t n = size_t(q.h) * size_t(q.w), n_pad = (n + 1) & ~size_t(1);
+            L.front = good ? q_entropy_front(reinterpret_cast<uint16_t *>(q.outs[q.job]), q.caps[q.job], q.h, q.w, h_hist + slot * kQRansTable, freq.data(), start.data()) : -1;
+            if (L.front < 0) continue;                                           // no room for the front matter (or a failure): retired below, never launched
+            q_rans_table(freq.data(), start.data(), h_tables + slot * kQRansTable);
+            QRansJob &J = h_jobs[slot];
+            uint16_t *const buf = c->cbufs[size_t(q.cb)];
+            J.words = buf; J.table = d_tables + slot * kQRansTable; J.out_end = buf + n_pad + kQHistWords; J.result = d_results + slot;
+            J.cap = uint32_t(std::min<size_t>(q.caps[q.job] - size_t(L.front), 0xFFFFFFF0u));
+            J.live = 1u;
+            q_rans_begin(J.st, uint32_t(n), J.cap);
+            h_results[slot] = 0u;
+            good = good && hipMemcpyAsync(d_tables + slot * kQRansTable, h_tables + slot * kQRansTable, kQRansTable * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
+                   hipMemcpyAsync(d_results + slot, h_results + slot, sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
+                   hipMemcpyAsync(d_jobs + slot, h_jobs + slot, sizeof(QRansJob), hipMemcpyHostToDevice, st) == hipSuccess;
+        }
+        size_t top = 0;
+        for (size_t k = 0; k < slots; k++) if (live[k].used) top = k + 1;
+        const int launches = more_waiting ? 1 : kQAhead;
+        float ms = 0.f;
+        good = good && hipEventRecord(t0, st) == hipSuccess;
+        for (int k = 0; good && k < launches; k++) good = device_q_rans(d_jobs, int(top), budget, st);
+        good = good && hipEventRecord(t1, st) == hipSuccess &&
+               hipMemcpyAsync(h_results, d_results, top * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+        good = hipStreamSynchronize(st) == hipSuccess && good;
+        if (good && hipEventElapsedTime(&ms, t0, t1) != hipSuccess) ms = 0.f;
+        // retire: finished jobs, jobs without room for their front matter, and after a failure every job
+        std::vector<size_t> gone;
+        double symbols = 0;
+        for (size_t k = 0; k < top; k++) {
+            LiveJob &L = live[k];
+            if (!L.used) continue;
+            const ReadyImage &q = L.im;
+            const uint32_t r = good && L.front >= 0 ? h_results[k] : 0xFFFFFFFFu;
+            if (r == 0u) continue;                                               // still coding
+            const size_t n = size_t(q.h) * size_t(q.w), n_pad = (n + 1) & ~size_t(1);
+            long len = -1;
+            if (r != 0xFFFFFFFFu && hipMemcpyAsync(reinterpret_cast<uint16_t *>(q.outs[q.job]) + L.front, c->cbufs[size_t(q.cb)] + n_pad + kQHistWords - r,
+                                                   size_t(r) * sizeof(uint16_t), hipMemcpyDeviceToHost, st) == hipSuccess) len = L.front + long(r);
+            else if (good) fprintf(stderr, "[nblic_amd] image %d: output buffer of %zu words is too small\n", q.job, q.caps[q.job]);
+            q.lens[q.job] = len;
+            symbols += double(n);
+            gone.push_back(k);
+        }
+        if (!gone.empty() && hipStreamSynchronize(st) != hipSuccess) { for (size_t k : gone) live[k].im.lens[live[k].im.job] = -1; good = false; }
+        if (!good) fprintf(stderr, "[nblic_amd] device qcoder: a turn failed (%s): %zu images report -1\n", hipGetErrorString(hipGetLastError()), gone.size());
+        if (!good && ok) {                                                      // the slots' records on the device are of no use any more
+            if (hipMemset(d_jobs, 0, slots * sizeof(QRansJob)) != hipSuccess) { ok = false; c->broken = true; }
+        }
+        { std::lock_guard<std::mutex> l(c->stat_m); c->qdev_symbols += symbols; c->qdev_launches += good ? launches : 0; c->qdev_images += long(gone.size()); c->qdev_kernel_ms += double(ms); }
+        for (size_t k : gone) { finish_images(c, &live[k].im, 1); live[k].used = false; }
+        n_live -= gone.size();
     }
 }
 
@@ -3888,6 +4028,7 @@ void nblic_amd_destroy(nblic_amd_ctx *c) {
     c->rcv.notify_all();
     for (auto &t : c->coders) t.join();
     for (auto &t : c->dev_coders) t.join();
+    if (c->qdev.joinable()) c->qdev.join();
     { std::lock_guard<std::mutex> l(c->dm); c->stop_drivers = true; }
     c->dcv.notify_all();
     for (auto &t : c->drivers) t.join();
@@ -4821,6 +4962,142 @@ int nblic_amd_lsq_probe(nblic_amd_ctx *c, int n, int waves, int count, const dou
     if (!c || !stats || !regressors || !bias || !out_f64 || !out_i64 || hipSetDevice(c->device) != hipSuccess) return -1;
     std::lock_guard<std::mutex> g(c->api);
     return serial_lsq_probe(c->dec_stream, n, waves, count, stats, reinterpret_cast<const int8_t *>(regressors), bias, out_f64, out_i64) ? 0 : -1;
+}
+
+// ---- the device rANS stage of effort 0 (q_device_coder.hip) on its own ----------------------------------------------------
+int nblic_amd_set_device_qcoder(nblic_amd_ctx *c, int mode, long symbols_per_launch) {
+    if (!c) c = default_ctx();
+    if (!c || mode < 0 || mode > 2 || symbols_per_launch < 0) return -1;
+    std::lock_guard<std::mutex> g(c->api);
+    if (mode != 0 && !c->qdev.joinable()) c->qdev = std::thread(qdev_main, c);
+    {
+        std::lock_guard<std::mutex> l(c->rm);
+        c->qmode = mode;
+        c->q_budget = symbols_per_launch == 0 ? kQSymbolsPerLaunch : uint32_t(std::min<long>(symbols_per_launch, 1L << 30));
+    }
+    c->rcv.notify_all();
+    return mode;
+}
+
+int nblic_amd_device_qcoder_stats(nblic_amd_ctx *c, double *symbols, long *launches, long *images, double *kernel_ms) {
+    if (!c) c = default_ctx();
+    if (!c) return -1;
+    std::lock_guard<std::mutex> l(c->stat_m);
+    if (symbols) *symbols = c->qdev_symbols;
+    if (launches) *launches = c->qdev_launches;
+    if (images) *images = c->qdev_images;
+    if (kernel_ms) *kernel_ms = c->qdev_kernel_ms;
+    return 0;
+}
+
+int nblic_amd_qcoder_selftest(nblic_amd_ctx *c) {
+    if (!c) c = default_ctx();
+    if (!c || hipSetDevice(c->device) != hipSuccess) return -1;
+    std::lock_guard<std::mutex> g(c->api);
+    const long bad = device_q_quot_selftest(c->dec_stream);
+    return bad < 0 ? -1 : int(std::min<long>(bad, 0x7FFFFFFF));
+}
+
+long nblic_amd_debug_q_rans_host(int height, int width, const uint16_t *words, const unsigned int *hist, long symbols_per_launch,
+                                 uint16_t *out, size_t cap_words) {
+    if (!words || !hist || !out) return -2;
+    if (height < 1 || width < 1 || height > kIndexMaxSide || width > kIndexMaxSide) return -2;
+    if (!q_words_ok(words, size_t(height) * size_t(width), hist)) return -2;
+    return q_rans_encode_host(out, cap_words, height, width, words, hist, symbols_per_launch);
+}
+
+int nblic_amd_debug_device_q_entropy(nblic_amd_ctx *c, int n_jobs, const uint16_t *const *words, const unsigned int *n_symbols,
+                                     const unsigned int *const *hists, const size_t *caps_words, long symbols_per_launch,
+                                     uint16_t *const *outs, long *lens) {
+    constexpr int kMaxJobs = 4096;
+    constexpr size_t kMaxBytes = size_t(1) << 30, kGuard = 64, kMaxSymbols = size_t(1) << 24, kMaxLaunches = 8192;
+    constexpr uint8_t kPattern = 0xA5;
+    if (!c || n_jobs < 1 || n_jobs > kMaxJobs || !words || !n_symbols || !hists || !caps_words || !outs || !lens || symbols_per_launch < 0) return -1;
+    auto align = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t nj = size_t(n_jobs);
+    const uint32_t budget = symbols_per_launch == 0 ? kQSymbolsPerLaunch : uint32_t(std::min<long>(symbols_per_launch, long(kMaxSymbols)));
+    std::vector<size_t> in_at(nj), out_at(nj), cap_body(nj);
+    std::vector<long> front(nj);
+    std::vector<uint32_t> tables(nj * kQRansTable), freq(kQRansTable), start(kQRansTable);
+    size_t in_bytes = 0, out_bytes = kGuard, n_max = 0;                         // a guard in front of the first region too
+    for (int k = 0; k < n_jobs; k++) {
+        const size_t n = n_symbols[k];
+        if (!words[k] || !hists[k] || n < 1 || n > kMaxSymbols || (caps_words[k] > 0 && !outs[k]) || caps_words[k] > kMaxBytes / 2) return -1;
+        if (!q_words_ok(words[k], n, hists[k])) return -1;
+        n_max = std::max(n_max, n);
+        in_at[size_t(k)] = in_bytes;
+        in_bytes += align((n + kQRansWindow - 1) / kQRansWindow * kQRansWindow * sizeof(uint16_t));       // whole 512-byte windows, the caller's padding included
+        if (in_bytes > kMaxBytes) return -1;
+    }
+    if ((n_max + budget - 1) / budget > kMaxLaunches) return -1;
+    // the front matter, on the host and straight into the caller's buffers: a region's capacity is what it leaves
+    for (int k = 0; k < n_jobs; k++) {
+        // the header names the widest image of n pixels (the pass does not look at it): w the largest divisor of n below 65536
+        const size_t n = n_symbols[k];
+        size_t w = std::min<size_t>(n, 65535);
+        while (n % w != 0) w--;
+        if (n / w > 65535) return -1;
+        const int h = int(n / w);
+        front[size_t(k)] = q_entropy_front(outs[k], caps_words[k], h, int(w), hists[k], freq.data(), start.data());
+        q_rans_table(freq.data(), start.data(), tables.data() + size_t(k) * kQRansTable);
+        cap_body[size_t(k)] = front[size_t(k)] < 0 ? 0 : caps_words[k] - size_t(front[size_t(k)]);
+        out_at[size_t(k)] = out_bytes;
+        out_bytes += (cap_body[size_t(k)] * sizeof(uint16_t) + kGuard + 63) & ~size_t(63);                // the region, then 64 .. 127 bytes of guard
+        if (out_bytes > kMaxBytes) return -1;
+    }
+    std::lock_guard<std::mutex> g(c->api);
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    Stream st;
+    DevBuf<uint8_t> d_in, d_out; DevBuf<uint32_t> d_tables, d_results; DevBuf<QRansJob> d_jobs;
+    Pinned<QRansJob> h_jobs; Pinned<uint32_t> h_results;
+    std::vector<uint8_t> h_in(std::max<size_t>(in_bytes, 256), 0), h_out(out_bytes, kPattern);
+    for (int k = 0; k < n_jobs; k++)
+        memcpy(h_in.data() + in_at[size_t(k)], words[k], (size_t(n_symbols[k]) + kQRansWindow - 1) / kQRansWindow * kQRansWindow * sizeof(uint16_t));
+    bool ok = st.create(hipStreamNonBlocking) == hipSuccess && d_in.alloc(h_in.size()) == hipSuccess && d_out.alloc(out_bytes) == hipSuccess &&
+              d_tables.alloc(tables.size()) == hipSuccess && d_results.alloc(nj) == hipSuccess && d_jobs.alloc(nj) == hipSuccess &&
+              h_jobs.alloc(nj) == hipSuccess && h_results.alloc(nj) == hipSuccess;
+    if (ok) {
+        for (int k = 0; k < n_jobs; k++) {
+            QRansJob &J = h_jobs[k];
+            J.words = reinterpret_cast<const uint16_t *>(d_in.get() + in_at[size_t(k)]);
+            J.table = d_tables.get() + size_t(k) * kQRansTable;
+            J.out_end = reinterpret_cast<uint16_t *>(d_out.get() + out_at[size_t(k)]) + cap_body[size_t(k)];
+            J.result = d_results.get() + k;
+            J.cap = uint32_t(cap_body[size_t(k)]);
+            J.live = front[size_t(k)] < 0 ? 0u : 1u;                             // no room for the front matter: never launched, reports -1
+            q_rans_begin(J.st, n_symbols[k], J.cap);
+            h_results[k] = 0u;
+        }
+        ok = hipMemcpyAsync(d_in, h_in.data(), h_in.size(), hipMemcpyHostToDevice, st) == hipSuccess &&
+             hipMemcpyAsync(d_out, h_out.data(), out_bytes, hipMemcpyHostToDevice, st) == hipSuccess &&
+             hipMemcpyAsync(d_tables, tables.data(), tables.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
+             hipMemcpyAsync(d_results, h_results, nj * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
+             hipMemcpyAsync(d_jobs, h_jobs, nj * sizeof(QRansJob), hipMemcpyHostToDevice, st) == hipSuccess;
+        for (size_t done = 0; ok && done < n_max; done += budget) ok = device_q_rans(d_jobs, n_jobs, budget, st);   // the resumed sequence: every record stays on the device
+        ok = ok && hipMemcpyAsync(h_results, d_results, nj * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(h_out.data(), d_out, out_bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+        ok = hipStreamSynchronize(st) == hipSuccess && ok;
+    }
+    if (!ok) return -2;
+    // everything the kernel may not have written still holds the pattern: the guards, and a region in front of its reported words
+    bool intact = true;
+    size_t at = 0;
+    auto pattern_to = [&](size_t end) { for (; at < end; at++) intact = intact && h_out[at] == kPattern; };
+    for (int k = 0; k < n_jobs; k++) {
+        const uint32_t r = h_results[k];
+        const size_t region = cap_body[size_t(k)] * sizeof(uint16_t);
+        pattern_to(out_at[size_t(k)]);
+        lens[k] = -1;
+        if (front[size_t(k)] < 0) { if (r != 0u) intact = false; pattern_to(out_at[size_t(k)] + region); continue; }
+        if (r == 0xFFFFFFFFu) { at += region; continue; }                      // did not fit: the kernel wrote what it liked inside the region
+        if (r < 2u || size_t(r) > cap_body[size_t(k)]) { intact = false; at += region; continue; }       // no length written, or one beyond the region
+        pattern_to(out_at[size_t(k)] + region - size_t(r) * sizeof(uint16_t));
+        memcpy(outs[k] + front[size_t(k)], h_out.data() + at, size_t(r) * sizeof(uint16_t));
+        at += size_t(r) * sizeof(uint16_t);
+        lens[k] = front[size_t(k)] + long(r);
+    }
+    pattern_to(out_bytes);
+    return intact ? 0 : -3;
 }
 
 // ---- drop-in entry points --------------------------------------------------------------------

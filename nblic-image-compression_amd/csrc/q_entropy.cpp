@@ -14,7 +14,10 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <vector>
+
 #include "q_entropy.h"
+#include "q_rans.h"
 
 namespace nblic {
 
@@ -98,6 +101,26 @@ bool q_words_ok(const uint16_t *qy, size_t n, const uint32_t *hist) {
 // entry_rows[k] (above).  The stream does not depend on them.
 // Returns the stream length in 16-bit words (header included), -1 if cap_words is too small, -2 for entry rows that are
 // out of range or out of order (nothing is written then).
+// The front matter of a stream, on its own: the four header words, then per level the histogram scaled to a sum of 2^15
+// (q_normalise) and its code (q_write_hist); freq / start (12 x 256 each) receive the scaled counts and their running
+// sums, what the pass codes with.  Returns the words written, or -1 if cap_words is too small.
+long q_entropy_front(uint16_t *out, size_t cap_words, int h, int w, const uint32_t *hist_in, uint32_t *freq, uint32_t *start) {
+    if (cap_words < 6) return -1;
+    uint16_t *p = out, *const end = out + cap_words;
+    *p++ = (uint16_t)('Q' | ('0' << 8)); *p++ = (uint16_t)('.' | ('2' << 8));            // QNBLIC.c:463-473, host byte order
+    *p++ = (uint16_t)h; *p++ = (uint16_t)w;
+    memcpy(freq, hist_in, sizeof(uint32_t) * kQLevels * kQSyms);
+    for (int k = 0; k < kQLevels; k++) {
+        uint32_t *f = freq + k * kQSyms, *s0 = start + k * kQSyms;
+        q_normalise(f);
+        uint32_t acc = 0;
+        for (int s = 0; s < kQSyms; s++) { s0[s] = acc; acc += f[s]; }
+        p = q_write_hist(p, end, f);
+        if (!p) return -1;
+    }
+    return (long)(p - out);
+}
+
 long q_entropy_encode_entries(uint16_t *out, size_t cap_words, int h, int w, const uint16_t *qy, const uint32_t *hist_in,
                               const int *entry_rows, int n_entries, QEntryState *entries) {
     uint32_t freq[kQLevels][kQSyms], start[kQLevels][kQSyms];
@@ -105,18 +128,9 @@ long q_entropy_encode_entries(uint16_t *out, size_t cap_words, int h, int w, con
     if (n_entries < 0 || (n_entries > 0 && (!entry_rows || !entries))) return -2;
     for (int k = 0; k < n_entries; k++)
         if (entry_rows[k] < 1 || entry_rows[k] >= h || (k > 0 && entry_rows[k] <= entry_rows[k - 1])) return -2;
-    if (cap_words < 6) return -1;
-    uint16_t *p = out, *const end = out + cap_words;
-    *p++ = (uint16_t)('Q' | ('0' << 8)); *p++ = (uint16_t)('.' | ('2' << 8));            // QNBLIC.c:463-473, host byte order
-    *p++ = (uint16_t)h; *p++ = (uint16_t)w;
-    memcpy(freq, hist_in, sizeof freq);
-    for (int k = 0; k < kQLevels; k++) {
-        q_normalise(freq[k]);
-        uint32_t acc = 0;
-        for (int s = 0; s < kQSyms; s++) { start[k][s] = acc; acc += freq[k][s]; }
-        p = q_write_hist(p, end, freq[k]);
-        if (!p) return -1;
-    }
+    const long front = q_entropy_front(out, cap_words, h, w, hist_in, &freq[0][0], &start[0][0]);
+    if (front < 0) return -1;
+    uint16_t *p = out + front, *const end = out + cap_words;
     uint16_t *const body = p;
     uint32_t x = 1u << kQAnsBits;                                                       // QNBLIC.c:238-253
     size_t t = n;
@@ -138,6 +152,49 @@ long q_entropy_encode_entries(uint16_t *out, size_t cap_words, int h, int w, con
     *p++ = (uint16_t)x; *p++ = (uint16_t)(x >> kQAnsBits);
     for (uint16_t *a = body, *b = p - 1; a < b; a++, b--) { uint16_t t = *a; *a = *b; *b = t; }   // decoder reads forwards
     return (long)(p - out);
+}
+
+// The packed (f, start) table a lane codes with (q_rans.h), from what q_entropy_front leaves.  An unused symbol has f = 0.
+void q_rans_table(const uint32_t *freq, const uint32_t *start, uint32_t *table) {
+    for (uint32_t i = 0; i < kQRansTable; i++) table[i] = freq[i] ? q_rans_entry(freq[i], start[i]) : 0u;
+}
+
+// The same stream as q_entropy_encode, made the way the device stage makes it (q_device_coder.hip): the front matter,
+// then one lane of q_rans.h advanced by at most symbols_per_launch symbols at a time (<= 0: all at once) and resumed from
+// its record until the job is done, its words written downwards from the end of `out` and moved behind the front matter
+// at the end.  Returns the stream length in words, or -1 if cap_words is too small.
+long q_rans_encode_host(uint16_t *out, size_t cap_words, int h, int w, const uint16_t *qy, const uint32_t *hist_in, long symbols_per_launch) {
+    std::vector<uint32_t> freq(kQRansTable), start(kQRansTable), table(kQRansTable);
+    const size_t n = (size_t)h * (size_t)w;
+    if (n == 0 || n > 0xFFFFFFF0u) return -1;
+    const long front = q_entropy_front(out, cap_words, h, w, hist_in, freq.data(), start.data());
+    if (front < 0) return -1;
+    q_rans_table(freq.data(), start.data(), table.data());
+    const size_t room = cap_words - (size_t)front;
+    const uint32_t cap = room < 0xFFFFFFF0u ? (uint32_t)room : 0xFFFFFFF0u;
+    uint16_t *const out_end = out + cap_words;
+    const uint32_t budget = symbols_per_launch <= 0 || (size_t)symbols_per_launch > n ? (uint32_t)n : (uint32_t)symbols_per_launch;
+    QRansState record;
+    q_rans_begin(record, (uint32_t)n, cap);
+    uint32_t result = 0;
+    while (result == 0) {                                                               // one turn: one launch of one lane
+        QRansState s = record;                                                          // (the kernel's lanes load and store theirs the same way)
+        const uint32_t take = q_rans_take(s.left, budget), rounds = q_rans_rounds(s.left, take);
+        for (uint32_t r = 0; r < rounds; r++) {
+            const QRansSpan sp = q_rans_span(s.left, take, r);
+            const uint16_t *win = qy + (size_t)sp.window * kQRansWindow;
+            for (uint32_t i = sp.hi; i-- > sp.lo;) {
+                const uint32_t e = table[q_rans_index(win[i])];
+                q_rans_put(s, e, q_rans_rcp(e & 0xFFFFu), out_end, cap);
+            }
+        }
+        s.left -= take;
+        if (s.left == 0) result = q_rans_flush(s, out_end, cap);
+        record = s;
+    }
+    if (result == 0xFFFFFFFFu) return -1;
+    memmove(out + front, out_end - result, sizeof(uint16_t) * result);
+    return front + (long)result;
 }
 
 long q_entropy_encode(uint16_t *out, size_t cap_words, int h, int w, const uint16_t *qy, const uint32_t *hist_in) {

@@ -21,6 +21,13 @@ long q_entropy_encode(uint16_t *out, size_t cap_words, int h, int w, const uint1
 // order (nothing is written then).
 long q_entropy_encode_entries(uint16_t *out, size_t cap_words, int h, int w, const uint16_t *qy, const uint32_t *hist_in,
                               const int *entry_rows, int n_entries, QEntryState *entries);
+// The front matter alone: header words, then per level the scaled histogram's code; freq / start (12 x 256 each) receive
+// the tables the pass codes with.  Returns the words written, or -1 if cap_words is too small.
+long q_entropy_front(uint16_t *out, size_t cap_words, int h, int w, const uint32_t *hist_in, uint32_t *freq, uint32_t *start);
+// freq / start as the packed table of q_rans.h (12 x 256 entries of f | start << 16; 0 for a symbol never coded).
+void q_rans_table(const uint32_t *freq, const uint32_t *start, uint32_t *table);
+// q_entropy_encode's stream, made by one lane of q_rans.h that is resumed every symbols_per_launch symbols (<= 0: never).
+long q_rans_encode_host(uint16_t *out, size_t cap_words, int h, int w, const uint16_t *qy, const uint32_t *hist_in, long symbols_per_launch);
 // true when every word names a level below 12 and a symbol its level's histogram counts: what the pass divides by.
 bool q_words_ok(const uint16_t *qy, size_t n, const uint32_t *hist);
 // Decoder front matter (q_entropy.cpp).
