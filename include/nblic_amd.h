@@ -481,6 +481,51 @@ long nblic_amd_indexed_decode_plan(int n_images, const int *kinds, const int *ef
                                    const int *every_rows, const int *row0, const int *row1, int round_segments, int *jobs,
                                    size_t jobs_cap);
 
+/* DECODE TO DEVICE MEMORY: a window of every image of a batch straight into caller-owned device memory, as pixels or as
+ * normalised floats.  The encoders take device pointers; these two calls are the decoders' counterpart for a consumer on
+ * the GPU (a loader that wants a crop of each frame in a batch tensor): no pixel crosses the bus, only the verdict words and
+ * one 64-byte header per image reach the host.
+ *   the window      rows [row0, row1) x columns [col0, col1) of image k; row1 == 0 / col1 == 0 stand for the image's
+ *                   height / width.  The ROWS choose the segments an indexed decode runs, as row0 / row1 of
+ *                   nblic_amd_decode_batch_indexed do; the COLUMNS do not shorten the decode (the model needs whole rows),
+ *                   they only choose what is delivered.
+ *   the destination element (r, c) of the window goes to ptr + r x pitch_bytes + c x element size.  ptr is device memory of
+ *                   the context's device and, like pitch_bytes, a multiple of the element size; cap_bytes is what may be
+ *                   written from ptr on.  Nothing outside the window's rows is written: pitch gaps stay as they were.
+ *   format          0 uint8 (a copy; scale must be 1 and bias 0), 1 float16, 2 bfloat16, 3 float32: float(px) x scale, rounded
+ *                   to float, + bias, rounded to float -- never fused -- then rounded to nearest even into the format, so
+ *                   numpy's float32(px) * float32(scale) + float32(bias), converted, is the same bits.
+ *   delivery        ONE kernel launch (k_deliver) per call (decode_batch_to: per chunk of 64 images)
+ *                   delivers every window, after the verification that nblic_amd_decode_batch_indexed makes on the device.
+ *   per image       status[k] = 0, or -1.  REFUSED on the host, before anything of it is launched, with its destination not
+ *                   written and the other images unaffected: what the host call refuses, and a destination whose ptr the
+ *                   runtime (hipPointerGetAttributes) does not report as device memory of the context's device, whose ptr or
+ *                   pitch_bytes is no multiple of the element size, whose pitch_bytes is below the window's row, whose window
+ *                   is empty or outside the image, or with (rows - 1) x pitch_bytes + cols x element size > cap_bytes or
+ *                   beyond the end of the allocation ptr lies in.  FAILED on the device (a boundary differs, the stream is
+ *                   damaged or ends early): the window is filled with zero bytes (+0.0, not bias).
+ *   whole call      0 when every status is 0, else -1.  -1 with nothing launched: what the host call refuses, a NULL dests,
+ *                   an unknown format, a scale or bias that is not finite, uint8 with scale != 1 or bias != 0.  If the device
+ *                   fails, every accepted image's window is zeroed where the stream still works and every status is -1.
+ * Overlapping destinations are the caller's business: the windows are written in no defined order.  The calls return when
+ * the data is complete (they synchronise their own stream), and they order themselves against NOTHING the caller has queued
+ * on streams of its own: a destination must not be in use by pending work when the call is made.
+ * nblic_amd_decode_batch_indexed_to is nblic_amd_decode_batch_indexed with that delivery in place of the copies to the
+ * host (nblic_amd_indexed_decode_split's ms[3] is then the delivery); nblic_amd_decode_batch_to is nblic_amd_decode_batch
+ * likewise, each window gated ON THE DEVICE by its image's decoder record: a stream that fails there leaves zeros. */
+typedef struct nblic_amd_dest {
+    void  *ptr;          /* device memory on the context's device                          */
+    size_t pitch_bytes;  /* between rows; >= (col1 - col0) x element size, a multiple of it */
+    size_t cap_bytes;    /* readable / writable bytes from ptr                             */
+    int    row0, row1, col0, col1;   /* the window; row1 == 0 / col1 == 0: to the image's last row / column */
+} nblic_amd_dest;
+int nblic_amd_decode_batch_indexed_to(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                      const void *const *indexes, const size_t *index_lens, const nblic_amd_dest *dests, int format,
+                                      float scale, float bias, int *heights, int *widths, int *nears, int *efforts, int *status);
+int nblic_amd_decode_batch_to(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                              const nblic_amd_dest *dests, int format, float scale, float bias, int *heights, int *widths,
+                              int *nears, int *efforts, int *status);
+
 /* BATCH INDEX BUILD: the seek indexes of many streams from ONE decode pass.  nblic_amd_index_build takes one stream per
  * call and pays a host round trip at every band and every entry; this call takes n streams -- NBLIC in any mode and QNBLIC,
  * written by this library or by the reference; any mix of geometries and of R = every_rows[k] -- and writes into
@@ -767,6 +812,31 @@ int nblic_amd_debug_index_capture(nblic_amd_ctx *ctx, int kind, int effort, int 
 int nblic_amd_debug_index_unpack(nblic_amd_ctx *ctx, int n, const void *const *packed, const size_t *packed_bytes,
                                  const size_t *base_offsets, const int *walks, const int *first_outs,
                                  unsigned char *const *outs, const size_t *caps, size_t *out_strides);
+
+/* Debug hooks used by the delivery's tests (nblic_amd_decode_batch_indexed_to).  A task is a plane of plane_rows x width
+ * bytes, a window of four ints (row0, row1, col0, col1: 0 <= row0 < row1 <= plane_rows, 0 <= col0 < col1 <= width -- no 0
+ * stands for "to the end" here), a format with its scale and bias, a `zero` flag (zero bytes instead of pixels) and a
+ * destination: a byte offset into an output buffer and a row pitch.
+ * nblic_amd_debug_deliver_host: host only, no context, no device.  It runs the unit walk the kernel shares with the host
+ * (csrc/deliver.h) over the caller's plane into out + dst_offset, one unit after the other; the unit grid follows the
+ * destination's address modulo 16, as on the device.  gate_status: -1 or 1 deliver, anything else writes zeros.  units /
+ * chunks (may be NULL) receive what a launch counts for the task: rows x ((cols + 16 / elem - 1 + 15) / 16) units, 1024
+ * to a chunk.
+ * nblic_amd_debug_deliver: ONE k_deliver launch over n tasks (1 .. 65536).  Plane k is uploaded at byte base_offsets[k]
+ * (0 .. 15) of a zeroed, larger device buffer, and the kernel may read up256(plane_rows x width) bytes from there -- what
+ * the decoders' planes allow it.  Destination k lies at byte dst_offsets[k] of a device buffer of out_bytes[k] bytes (at a
+ * multiple of 256) that holds 0x5A everywhere before the launch and comes back whole in outs[k].  gate_status[k] != -1 is
+ * put into a decoder record's header on the device, which the task is gated by: 1 (done) delivers, anything else zeros.
+ * Both return 0; -1, with nothing launched or written, for a null pointer, a window outside the plane, a format, scale or
+ * bias the calls refuse, a destination or pitch that is no multiple of the element size, a pitch below the window's row,
+ * or a window that does not fit the output buffer from its offset on; nblic_amd_debug_deliver -2 when a HIP call failed. */
+int nblic_amd_debug_deliver_host(const unsigned char *plane, int plane_rows, int width, const int *window, int format, float scale,
+                                 float bias, int zero, int gate_status, unsigned char *out, size_t out_bytes, size_t dst_offset,
+                                 size_t pitch_bytes, unsigned long long *units, unsigned long long *chunks);
+int nblic_amd_debug_deliver(nblic_amd_ctx *ctx, int n, const unsigned char *const *planes, const size_t *plane_bytes,
+                            const size_t *base_offsets, const int *plane_rows, const int *widths, const int *windows,
+                            const int *formats, const float *scales, const float *biases, const int *zeros, const size_t *pitches,
+                            const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs, const int *gate_status);
 
 /* Debug hook used by the indexed effort-0 batch's host tests: QNBLIC's entropy stage (histogram normalisation, histogram
  * code, the rANS pass) on caller-made records, reporting the coder in front of entry rows as the batch's workers read it.

@@ -52,6 +52,7 @@ EXPORTS = (
     "nblic_amd_decode_batch_indexed", "nblic_amd_indexed_decode_split", "nblic_amd_indexed_decode_plan", "nblic_amd_debug_index_kernels",
     "nblic_amd_index_build_batch", "nblic_amd_index_build_split", "nblic_amd_index_build_plan", "nblic_amd_debug_index_capture",
     "nblic_amd_index_pack", "nblic_amd_index_pack_bound", "nblic_amd_index_unpack", "nblic_amd_index_unpacked_bytes", "nblic_amd_index_is_packed", "nblic_amd_debug_index_unpack",
+    "nblic_amd_decode_batch_indexed_to", "nblic_amd_decode_batch_to", "nblic_amd_debug_deliver_host", "nblic_amd_debug_deliver",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats", "nblic_amd_copy_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -242,6 +243,17 @@ def load_library() -> C.CDLL:
         vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
         lib.nblic_amd_debug_index_unpack.restype = C.c_int
         lib.nblic_amd_debug_index_unpack.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, ip, ip, vpp, szp, szp]
+    if hasattr(lib, "nblic_amd_decode_batch_indexed_to"):           # (an older build loaded through NBLIC_AMD_LIB has none of the four)
+        vpp, szp, fp, dp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(Dest)
+        lib.nblic_amd_decode_batch_indexed_to.restype = C.c_int
+        lib.nblic_amd_decode_batch_indexed_to.argtypes = [C.c_void_p, C.c_int, vpp, szp, vpp, szp, dp, C.c_int, C.c_float, C.c_float, ip, ip, ip, ip, ip]
+        lib.nblic_amd_decode_batch_to.restype = C.c_int
+        lib.nblic_amd_decode_batch_to.argtypes = [C.c_void_p, C.c_int, vpp, szp, dp, C.c_int, C.c_float, C.c_float, ip, ip, ip, ip, ip]
+        lib.nblic_amd_debug_deliver_host.restype = C.c_int
+        lib.nblic_amd_debug_deliver_host.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                     C.c_size_t, C.c_size_t, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+        lib.nblic_amd_debug_deliver.restype = C.c_int
+        lib.nblic_amd_debug_deliver.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, ip, ip, ip, ip, fp, fp, ip, szp, szp, szp, vpp, ip]
     if hasattr(lib, "nblic_amd_index_build_batch"):
         vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
         lib.nblic_amd_index_build_batch.restype = C.c_int
@@ -314,6 +326,128 @@ def load_library() -> C.CDLL:
     lib.nblic_amd_version.restype = C.c_char_p
     _lib = lib
     return lib
+
+
+class Dest(C.Structure):
+    """``nblic_amd_dest``: where one image's window goes in device memory."""
+    _fields_ = [("ptr", C.c_void_p), ("pitch_bytes", C.c_size_t), ("cap_bytes", C.c_size_t),
+                ("row0", C.c_int), ("row1", C.c_int), ("col0", C.c_int), ("col1", C.c_int)]
+
+
+DELIVER_FORMATS = {"uint8": 0, "float16": 1, "bfloat16": 2, "float32": 3}       # the `format` of the _to calls, by dtype name
+DELIVER_ELEM = (1, 2, 2, 4)
+DELIVER_PATTERN = 0x5A                                                          # what the debug hooks' output buffers hold before a delivery
+
+
+def deliver_format(dtype) -> int:
+    """The ``format`` a dtype stands for (``torch.float16``, ``np.float16``, ``"float16"`` ...); ``ValueError`` for any other."""
+    name = str(getattr(dtype, "name", dtype)).split(".")[-1]
+    if name not in DELIVER_FORMATS:
+        raise ValueError(f"no delivery format for dtype {dtype}: uint8, float16, bfloat16 or float32")
+    return DELIVER_FORMATS[name]
+
+
+def deliver_units(rows: int, cols: int, fmt: int) -> Tuple[int, int]:
+    """Units and chunks one delivery task counts (csrc/deliver.h): every row has ``(cols + 16 / elem - 1 + 15) // 16``
+    units of at most sixteen pixels, 1024 units go to a chunk (one workgroup)."""
+    units = rows * ((cols + 16 // DELIVER_ELEM[fmt] - 1 + 15) // 16)
+    return units, (units + 1023) // 1024
+
+
+def deliver_host(plane: np.ndarray, window, fmt, scale: float = 1.0, bias: float = 0.0, pitch: Optional[int] = None, offset: int = 0,
+                 out_bytes: Optional[int] = None, zero: bool = False, gate_status: int = -1, info: Optional[dict] = None) -> np.ndarray:
+    """The delivery kernel's unit walk on the host (``nblic_amd_debug_deliver_host``; no device): the window
+    ``(row0, row1, col0, col1)`` of the 2-D uint8 ``plane`` in format ``fmt`` (0 .. 3 or a dtype) goes to byte ``offset`` of
+    a buffer of ``out_bytes`` bytes that holds 0x5A, rows ``pitch`` bytes apart (default: the window's row).  The buffer
+    starts at a multiple of 16, so ``offset`` is the destination's residue as on the device.  Returns the buffer (uint8);
+    ``info`` receives ``units`` and ``chunks``.  ``ValueError`` when refused."""
+    plane = np.ascontiguousarray(plane, np.uint8)
+    fmt = fmt if isinstance(fmt, int) else deliver_format(fmt)
+    r0, r1, c0, c1 = (int(v) for v in window)
+    elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
+    if pitch is None:
+        pitch = (c1 - c0) * elem
+    if out_bytes is None:
+        out_bytes = offset + max(r1 - r0 - 1, 0) * pitch + max(c1 - c0, 0) * elem
+    raw = np.full(int(out_bytes) + 16, DELIVER_PATTERN, np.uint8)
+    lead = (-raw.ctypes.data) % 16
+    out = raw[lead: lead + int(out_bytes)]
+    win = (C.c_int * 4)(r0, r1, c0, c1)
+    units, chunks = C.c_ulonglong(0), C.c_ulonglong(0)
+    rc = load_library().nblic_amd_debug_deliver_host(plane.ctypes.data if plane.size else None, plane.shape[0], plane.shape[1] if plane.ndim == 2 else 0, win,
+                                                     int(fmt), float(scale), float(bias), int(bool(zero)), int(gate_status), out.ctypes.data, out.size,
+                                                     int(offset), int(pitch), C.byref(units), C.byref(chunks))
+    if rc != 0:
+        raise ValueError("nblic_amd_debug_deliver_host refused its arguments")
+    if info is not None:
+        info["units"], info["chunks"] = int(units.value), int(chunks.value)
+    return out
+
+
+def _pairs_for(arg, n: int, what: str):
+    """None, one ``(a, b)`` for every image, or one pair per image -> a list of n pairs; None stands for (0, 0): all of it."""
+    if arg is None:
+        return [(0, 0)] * n
+    arg = list(arg)
+    if len(arg) == 2 and not hasattr(arg[0], "__len__"):
+        return [(int(arg[0]), int(arg[1]))] * n
+    if len(arg) != n:
+        raise ValueError(f"{what}: one pair, or one pair per image")
+    return [(0, 0) if a is None else (int(a[0]), int(a[1])) for a in arg]
+
+
+def _dest_tensors(out, n: int):
+    """The 2-D tensor of every image: ``out`` is one tensor [N, H', W'] or [N, 1, H', W'], or a list of 2-D tensors."""
+    if isinstance(out, (list, tuple)):
+        views = list(out)
+    else:
+        shape = tuple(out.shape)
+        if len(shape) == 4 and shape[1] == 1:
+            views = [out[k][0] for k in range(shape[0])]
+        elif len(shape) == 3:
+            views = [out[k] for k in range(shape[0])]
+        else:
+            raise ValueError("out: a tensor [N, H', W'] or [N, 1, H', W'], or a list of 2-D tensors")
+    if len(views) != n or any(len(tuple(v.shape)) != 2 for v in views):
+        raise ValueError("out: one 2-D tensor per image")
+    return views
+
+
+def _dests_of(views, dims, rows, cols) -> Tuple[list, int]:
+    """One ``(ptr, pitch, cap, row0, row1, col0, col1)`` per image and the calls' format, from tensors used duck-typed
+    (``data_ptr()``, ``stride()``, ``element_size()``, ``shape``, ``dtype``).  A tensor whose shape is not its image's window
+    gets a null pointer: the library refuses that image alone."""
+    n = len(views)
+    fmts = {deliver_format(v.dtype) for v in views}
+    if len(fmts) > 1:
+        raise ValueError("out: one dtype per call")
+    fmt = fmts.pop() if fmts else 0
+    rows, cols = _pairs_for(rows, n, "rows"), _pairs_for(cols, n, "cols")
+    dests = []
+    for k, v in enumerate(views):
+        elem = int(v.element_size())
+        hh, ww = (int(x) for x in v.shape)
+        s0, s1 = (int(x) for x in v.stride())
+        if (ww > 1 and s1 != 1) or s0 < 0 or elem != DELIVER_ELEM[fmt]:
+            raise ValueError("out: the last stride must be 1 and the row stride not negative")
+        (r0, r1), (c0, c1) = rows[k], cols[k]
+        h, w = dims[k]
+        fits = h > 0 and w > 0 and (r1 or h) - r0 == hh and (c1 or w) - c0 == ww
+        ptr = int(v.data_ptr())
+        try:                                                    # what the storage holds from data_ptr() on, when the tensor tells
+            st = v.untyped_storage()
+            cap = int(st.data_ptr()) + int(st.nbytes()) - ptr
+        except AttributeError:                                  # otherwise the view's own extent
+            cap = (max(hh - 1, 0) * s0 + ww) * elem
+        dests.append((ptr if fits and hh > 0 and ww > 0 else 0, s0 * elem if hh > 1 else max(s0, ww) * elem, max(cap, 0), r0, r1, c0, c1))
+    return dests, fmt
+
+
+def _dest_array(dests):
+    arr = (Dest * max(len(dests), 1))()
+    for k, d in enumerate(dests):
+        arr[k] = Dest(*[int(x) if i else (int(x) or None) for i, x in enumerate(d)])
+    return arr
 
 
 def index_bytes(kind: int, h: int, w: int, effort: int, every_rows: int) -> int:
@@ -967,6 +1101,104 @@ class Context:
         if info is not None:
             info["status"], info["rc"] = [int(v) for v in status], int(rc)
         return [outs[k][: shapes[k][0] * shapes[k][1]].reshape(shapes[k]) if status[k] == 0 else None for k in range(n)]
+
+    def decode_batch_indexed_to(self, pairs, dests, fmt: int, scale: float = 1.0, bias: float = 0.0, info: Optional[dict] = None) -> List[int]:
+        """``nblic_amd_decode_batch_indexed_to`` as it is: ``dests`` is one ``(ptr, pitch_bytes, cap_bytes, row0, row1, col0,
+        col1)`` per image, ``ptr`` an address in device memory.  Returns the status list; ``info`` receives ``status``,
+        ``rc`` and ``dims`` (the (height, width) of every image whose host check passed)."""
+        n = len(pairs)
+        ss = [_bytes_arg(s if s is not None else b"") for s, _ in pairs]
+        xs = [_bytes_arg(x if x is not None else b"") for _, x in pairs]
+        nothing = np.zeros(1, np.uint8)
+        ip = C.POINTER(C.c_int)
+        vp = lambda arrs: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else nothing.ctypes.data for a in arrs])
+        sz = lambda arrs: (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        meta = [np.full(max(n, 1), -1, np.int32) for _ in range(5)]
+        rc = self.lib.nblic_amd_decode_batch_indexed_to(self.handle, n, vp(ss), sz(ss), vp(xs), sz(xs), _dest_array(dests), int(fmt), float(scale), float(bias),
+                                                        *[m.ctypes.data_as(ip) for m in meta])
+        status = [int(v) for v in meta[4][:n]]
+        if info is not None:
+            info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
+        return status
+
+    def decode_batch_indexed_into(self, pairs, out, rows=None, cols=None, scale: float = 1.0, bias: float = 0.0, info: Optional[dict] = None) -> List[int]:
+        """A window of every image of ``decode_batch_indexed`` straight into device tensors: no pixel crosses the bus.
+        ``out`` is one tensor [N, H', W'] or [N, 1, H', W'] on this context's device, or a list of 2-D tensors -- views
+        with any batch and row stride, last stride 1; the dtype chooses the format: uint8 (a copy), float16, bfloat16 or
+        float32 (``px * scale + bias`` in float32, two roundings, then round-to-nearest-even).  ``rows`` / ``cols``: None
+        (all), one ``(a, b)`` for every image, or one per image; the rows choose the segments that run, the columns only
+        what is delivered.  A tensor whose shape is not its window's is refused for that image.  Returns the status list
+        (0, or -1: refused -- the tensor is not written -- or failed -- its window is zeros); ``info`` as
+        ``decode_batch_indexed`` fills it.  The call returns when the data is there, and orders itself against nothing queued
+        on the caller's streams: synchronise those first if they still use ``out``."""
+        n = len(pairs)
+        dims = []
+        for _, x in pairs:                                      # the head of an index names the geometry; the library checks all of it
+            x = _bytes_arg(x if x is not None else b"")
+            h, w = (int(v) for v in np.frombuffer(x[16:24].tobytes(), "<i4")) if x.size >= INDEX_HEAD_BYTES else (0, 0)
+            dims.append((h, w) if 0 < h <= 65535 and 0 < w <= 65535 else (0, 0))
+        dests, fmt = _dests_of(_dest_tensors(out, n), dims, rows, cols)
+        return self.decode_batch_indexed_to(pairs, dests, fmt, scale, bias, info)
+
+    def decode_batch_to(self, streams, dests, fmt: int, scale: float = 1.0, bias: float = 0.0, info: Optional[dict] = None) -> List[int]:
+        """``nblic_amd_decode_batch_to`` as it is; arguments and result as ``decode_batch_indexed_to``."""
+        n = len(streams)
+        ss = [_bytes_arg(s if s is not None else b"") for s in streams]
+        nothing = np.zeros(1, np.uint8)
+        ip = C.POINTER(C.c_int)
+        sp = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else nothing.ctypes.data for a in ss])
+        sl = (C.c_size_t * max(n, 1))(*[a.size for a in ss])
+        meta = [np.full(max(n, 1), -1, np.int32) for _ in range(5)]
+        rc = self.lib.nblic_amd_decode_batch_to(self.handle, n, sp, sl, _dest_array(dests), int(fmt), float(scale), float(bias), *[m.ctypes.data_as(ip) for m in meta])
+        status = [int(v) for v in meta[4][:n]]
+        if info is not None:
+            info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
+        return status
+
+    def decode_batch_into(self, streams, out, rows=None, cols=None, scale: float = 1.0, bias: float = 0.0, info: Optional[dict] = None) -> List[int]:
+        """``decode_batch`` with a window of every plane delivered into device tensors (no index: every stream is decoded
+        whole, from its start).  ``out``, ``rows``, ``cols``, ``scale``, ``bias``, the result and ``info`` as
+        ``decode_batch_indexed_into``; a stream that fails on the device leaves zeros."""
+        dims = [_stream_dims(_bytes_arg(s if s is not None else b"")) or (0, 0) for s in streams]
+        dests, fmt = _dests_of(_dest_tensors(out, len(streams)), dims, rows, cols)
+        return self.decode_batch_to(streams, dests, fmt, scale, bias, info)
+
+    def debug_deliver(self, tasks) -> List[np.ndarray]:
+        """``nblic_amd_debug_deliver``: ONE k_deliver launch over ``tasks``, each a dict with ``plane`` (2-D uint8),
+        ``window`` (row0, row1, col0, col1) and ``fmt``, and optionally ``scale``, ``bias``, ``pitch`` (default: the window's
+        row), ``offset`` (of the destination in its 0x5A-filled buffer), ``out_bytes`` (default: what the window needs from
+        ``offset`` on), ``base_offset`` (0 .. 15, of the plane in its device buffer), ``zero`` and ``gate_status`` (-1: no
+        gate).  Returns every task's whole buffer (uint8).  ``ValueError`` when refused."""
+        n = len(tasks)
+        planes, wins, fmts, scales, biases, zeros, pitches, offsets, sizes, bases, gates = ([] for _ in range(11))
+        for t in tasks:
+            plane = np.ascontiguousarray(t["plane"], np.uint8)
+            fmt = t["fmt"] if isinstance(t["fmt"], int) else deliver_format(t["fmt"])
+            r0, r1, c0, c1 = (int(v) for v in t["window"])
+            elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
+            pitch = int(t.get("pitch", (c1 - c0) * elem))
+            offset = int(t.get("offset", 0))
+            planes.append(plane); wins += [r0, r1, c0, c1]; fmts.append(fmt)
+            scales.append(float(t.get("scale", 1.0))); biases.append(float(t.get("bias", 0.0))); zeros.append(int(bool(t.get("zero", False))))
+            pitches.append(pitch); offsets.append(offset)
+            sizes.append(int(t.get("out_bytes", offset + max(r1 - r0 - 1, 0) * pitch + max(c1 - c0, 0) * elem)))
+            bases.append(int(t.get("base_offset", 0))); gates.append(int(t.get("gate_status", -1)))
+        if any(p.ndim != 2 or p.size == 0 for p in planes):
+            raise ValueError("debug_deliver: every plane is a 2-D uint8 array")
+        outs = [np.zeros(max(b, 1), np.uint8) for b in sizes]
+        m = max(n, 1)
+        vp = lambda arrs: (C.c_void_p * m)(*[a.ctypes.data for a in arrs])
+        sz = lambda vals: (C.c_size_t * m)(*[int(v) for v in vals])
+        iv = lambda vals, k=1: (C.c_int * (m * k))(*[int(v) for v in vals])
+        fv = lambda vals: (C.c_float * m)(*vals)
+        rc = self.lib.nblic_amd_debug_deliver(self.handle, n, vp(planes), sz(p.size for p in planes), sz(bases), iv(p.shape[0] for p in planes),
+                                              iv(p.shape[1] for p in planes), iv(wins, 4), iv(fmts), fv(scales), fv(biases), iv(zeros), sz(pitches),
+                                              sz(offsets), sz(sizes), vp(outs), iv(gates))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_deliver refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_deliver failed (%d)" % rc)
+        return [o[:b] for o, b in zip(outs, sizes)]
 
     def indexed_decode_split(self) -> dict:
         """Host milliseconds of the last ``decode_batch_indexed`` (``nblic_amd_indexed_decode_split``)."""

@@ -297,6 +297,7 @@ struct nblic_amd_ctx {
     size_t feed_chunk = size_t(1) << 20;  // bytes per step in which the drop-in decoders fetch a stream of unknown length (nblic_amd_set_feed_chunk)
     long fed_bytes = 0;                   // bytes the last drop-in decode read from the caller's stream
     int feed_pipe[2] = {-1, -1};          // safe_copy: the kernel does the reading
+    DevBuf<DeliverTask> dec_deliver;      // nblic_amd_decode_batch_to: the chunks' delivery tasks (grow-only, like dec_jobs)
 };
 
 namespace nblic {
@@ -1553,13 +1554,70 @@ static bool decode_launch(const DecodeItem &first, const SerialJob *d_jobs, cons
     return first.kind == 1 ? serial_qdecode_launch(d_jobs, h_jobs, n, st) : serial_decode_launch(d_jobs, h_jobs, n, st, whole_streams);
 }
 
+// ---- delivery to caller-owned device memory (deliver.h, serial_engine.h k_deliver) ----------------------------------------
+// What the _to calls hand down: one destination per image, one format and one normalisation per call.
+struct DeliverTo { const nblic_amd_dest *dests; uint32_t format; float scale, bias; };
+
+static bool deliver_args_ok(int format, float scale, float bias) {
+    if (format < 0 || format >= int(kDeliverFormats)) return false;
+    if (!(scale - scale == 0.0f) || !(bias - bias == 0.0f)) return false;                // NaN, infinite
+    return format != int(kDeliverU8) || (scale == 1.0f && bias == 0.0f);
+}
+
+// The window destination k names in an image of h x w, and the task that fills it -- all but src, src_bytes, gate and zero,
+// which are the caller's.  false: refused, on the host, before anything of the image is launched: the window is empty or
+// outside the image, the pointer or the pitch is no multiple of the element size, the pitch is too small, the window does
+// not fit cap_bytes, or the runtime does not know the pointer as memory of this context's device that holds the whole extent.
+static bool deliver_dest_task(const nblic_amd_ctx *c, const DeliverTo &to, int k, int h, int w, DeliverTask &T) {
+    const nblic_amd_dest &D = to.dests[k];
+    T = DeliverTask{};
+    T.row0 = D.row0; T.row1 = D.row1 ? D.row1 : h; T.col0 = D.col0; T.col1 = D.col1 ? D.col1 : w;
+    if (T.row0 < 0 || T.row1 <= T.row0 || T.row1 > h || T.col0 < 0 || T.col1 <= T.col0 || T.col1 > w) return false;
+    const size_t elem = deliver_elem(to.format), rows = size_t(T.row1 - T.row0), cols = size_t(T.col1 - T.col0);
+    if (!D.ptr || uintptr_t(D.ptr) % elem || D.pitch_bytes % elem || D.pitch_bytes < cols * elem || D.pitch_bytes > (size_t(1) << 40)) return false;
+    const unsigned long long extent = deliver_extent(uint32_t(rows), uint32_t(cols), to.format, D.pitch_bytes);
+    if (extent > D.cap_bytes) return false;
+    hipPointerAttribute_t A;
+    void *base = nullptr;
+    size_t size = 0;
+    if (hipPointerGetAttributes(&A, D.ptr) != hipSuccess || hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t *>(&base), &size, D.ptr) != hipSuccess) {
+        (void)hipGetLastError();                                         // (a pointer the runtime does not know is an error to it, not to this context)
+        return false;
+    }
+    if (A.type != hipMemoryTypeDevice || A.device != c->device) return false;
+    if (uintptr_t(D.ptr) < uintptr_t(base) || uintptr_t(D.ptr) - uintptr_t(base) + extent > size) return false;
+    T.dst = static_cast<uint8_t *>(D.ptr); T.dst_pitch = D.pitch_bytes;
+    T.src_pitch = uint32_t(w);
+    T.format = to.format; T.scale = to.scale; T.bias = to.bias;
+    return deliver_task_chunks(T) < (1ull << 31) / kDeliverChunkUnits;
+}
+
+// The tasks' places in ONE k_deliver launch, their upload to d_tasks and the launch, queued on st.
+static bool deliver_queue(DeliverTask *tasks, size_t n, DeliverTask *d_tasks, hipStream_t st) {
+    unsigned long long chunks = 0;
+    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(chunks); chunks += deliver_task_chunks(tasks[i]); }
+    if (n == 0) return true;
+    if (chunks >= (1ull << 31) || n >= (size_t(1) << 30)) return false;
+    return hipMemcpyAsync(d_tasks, tasks, n * sizeof(DeliverTask), hipMemcpyHostToDevice, st) == hipSuccess && deliver_launch(d_tasks, int(n), uint32_t(chunks), st);
+}
+
+// After a device failure: zero bytes into every window, by the same kernel, as far as the stream still works.
+static void deliver_zeros(std::vector<DeliverTask> &tasks, hipStream_t st) {
+    if (tasks.empty() || !st) return;
+    DevBuf<DeliverTask> d_tasks;
+    for (DeliverTask &T : tasks) { T.zero = 1; T.gate = nullptr; }
+    if (d_tasks.alloc(tasks.size()) == hipSuccess && deliver_queue(tasks.data(), tasks.size(), d_tasks, st)) hipStreamSynchronize(st);
+}
+
 // Parses and validates the headers, uploads the streams (their lengths are known here: running dry is an error),
 // works every (codec, effort) class present through its launches -- `rows` rows of every image per launch, the
 // state records carry the images from one launch to the next -- and copies the planes back.  status[k] = 0 / -1.
 static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *streams, const size_t *lens,
-                         unsigned char *const *imgs, const size_t *img_caps, int *hs, int *ws, int *nears, int *efforts, int *status) {
+                         unsigned char *const *imgs, const size_t *img_caps, int *hs, int *ws, int *nears, int *efforts, int *status,
+                         const DeliverTo *to = nullptr) {
     if (hipSetDevice(c->device) != hipSuccess) return false;
     std::vector<DecodeItem> items;
+    std::vector<DeliverTask> deliveries;                                // `to`: one per item, in the items' order (below)
     std::vector<std::vector<uint8_t>> qtabs;                            // per QNBLIC item, alive until the copies have been made
     size_t arena = 0;
     for (int k = 0; k < n; k++) {
@@ -1568,7 +1626,13 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         std::vector<uint8_t> tab;                                        // QNBLIC: histogram tables parsed on the host; a stream whose tables
         const Described r = describe_stream(streams[k], lens[k], false, c->max_px, it, tab);     // do not parse never reaches the GPU
         if (it.h > 0) { hs[k] = it.h; ws[k] = it.w; nears[k] = it.near; efforts[k] = it.effort; }     // the header parsed
-        if (r != Described::ok || size_t(it.h) * size_t(it.w) > img_caps[k]) continue;
+        if (r != Described::ok) continue;
+        if (to) {                                                        // the planes stay on the device: a window of each goes to the caller's memory there
+            DeliverTask T;
+            if (!deliver_dest_task(c, *to, k, it.h, it.w, T)) continue;
+            T.first_chunk = uint32_t(k);                                 // (until the sort below: the image it belongs to)
+            deliveries.push_back(T);
+        } else if (size_t(it.h) * size_t(it.w) > img_caps[k]) continue;
         if (it.kind == 1) {
             it.qtab = int(qtabs.size());
             qtabs.push_back(std::move(tab));
@@ -1581,6 +1645,13 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
     std::stable_sort(items.begin(), items.end(), [](const DecodeItem &a, const DecodeItem &b) { return a.kind * 4 + a.effort < b.kind * 4 + b.effort; });
     const int m = int(items.size());
     HIP_OK(c->dec_arena.reserve(arena)); HIP_OK(c->dec_jobs.reserve(size_t(m)));      // grow-only, like every workspace
+    if (to) {
+        HIP_OK(c->dec_deliver.reserve(size_t(m)));
+        std::vector<DeliverTask> sorted;
+        for (const DecodeItem &it : items)
+            sorted.push_back(*std::find_if(deliveries.begin(), deliveries.end(), [&](const DeliverTask &T) { return T.first_chunk == uint32_t(it.k); }));
+        deliveries.swap(sorted);
+    }
     std::vector<SerialJob> jobs(static_cast<size_t>(m));
     std::vector<SerialState> heads(static_cast<size_t>(m));
     std::vector<uint8_t *> d_streams(static_cast<size_t>(m)), d_tabs(static_cast<size_t>(m), nullptr);
@@ -1597,6 +1668,10 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         SerialState &H = heads[size_t(i)];
         H = SerialState{};
         H.pos = first_pos(it); H.avail = it.len; H.final_ = 1;
+        if (to) {                                                        // gated by the job's record: a stream that fails on the device leaves zeros
+            DeliverTask &T = deliveries[size_t(i)];
+            T.src = recon; T.src_bytes = up256(size_t(it.h) * size_t(it.w)); T.gate = state;
+        }
     }
     // Chunks of one (codec, effort) class, at most kDecodeChunk images each, alternate between two streams: a chunk's uploads,
     // its launches (`rows` rows of every image per launch) and its copies back are all on ITS stream, and the host issues
@@ -1613,6 +1688,7 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
     auto fail = [&](const char *what) {
         fprintf(stderr, "[nblic_amd] decode: %s failed\n", what);
         hipStreamSynchronize(c->dec_stream); hipStreamSynchronize(c->dec_stream2);
+        if (to) deliver_zeros(deliveries, c->dec_stream);
         return false;
     };
     auto upload_and_launch = [&](const Chunk &ch) {
@@ -1637,9 +1713,10 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         for (int i = ch.i0; i < ch.i1; i++) {
             const DecodeItem &it = items[size_t(i)];
             if (hipMemcpyAsync(&heads[size_t(i)], jobs[size_t(i)].state, sizeof(SerialState), hipMemcpyDeviceToHost, ch.st) != hipSuccess) return false;
-            if (hipMemcpyAsync(imgs[it.k], jobs[size_t(i)].recon, size_t(it.h) * size_t(it.w), hipMemcpyDeviceToHost, ch.st) != hipSuccess) return false;
+            if (!to && hipMemcpyAsync(imgs[it.k], jobs[size_t(i)].recon, size_t(it.h) * size_t(it.w), hipMemcpyDeviceToHost, ch.st) != hipSuccess) return false;
         }
-        return true;
+        // the chunk's windows: ONE launch on its stream, behind its decode launches
+        return !to || deliver_queue(deliveries.data() + ch.i0, size_t(ch.i1 - ch.i0), c->dec_deliver + ch.i0, ch.st);
     };
     for (size_t n = 0; n < chunks.size(); n++) {
         if (n >= 2 && hipStreamSynchronize(chunks[n].st) != hipSuccess) return fail("a chunk");      // heads[] of chunk n - 2 have landed before its stream is reused (its H2D reads heads of chunk n)
@@ -3243,6 +3320,7 @@ struct IdxDecImage {
     uint8_t *d_stream = nullptr, *d_index = nullptr, *d_plane = nullptr, *d_tab = nullptr;
     uint32_t *d_verdict = nullptr;      // one word per inner boundary, from boundary seg0 | seg0 + 1 on
     SerialState last{};                 // the last segment's final header
+    DeliverTask deliver{};              // decode_batch_indexed_to: the image's window and destination
     // a packed index: where its parts lie (for the device), the payload offsets, and this round's unpacked entries
     unsigned long long *d_desc = nullptr; uint32_t *d_offs = nullptr;
     IndexUnpackTask unpack{};           // all but the round's fields
@@ -3291,10 +3369,11 @@ static bool idxdec_upload_tasks(std::vector<IndexTask> &tasks, bool seed, IndexT
 
 static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *const *streams, const size_t *slens, const void *const *indexes,
                                 const size_t *ilens, const int *row0, const int *row1, unsigned char *const *outs, const size_t *caps,
-                                int *hs, int *ws, int *nears, int *efforts, int *status) {
-    if (!c || c->broken || n < 1 || !streams || !slens || !indexes || !ilens || !outs || !caps || !hs || !ws || !nears || !efforts || !status) return -1;
+                                int *hs, int *ws, int *nears, int *efforts, int *status, const DeliverTo *to = nullptr) {
+    // `to`: the rows go to the caller's device memory (k_deliver) instead of outs; row0 / row1 / outs / caps are not read
+    if (!c || c->broken || n < 1 || !streams || !slens || !indexes || !ilens || (!to && (!outs || !caps)) || !hs || !ws || !nears || !efforts || !status) return -1;
     if ((row0 == nullptr) != (row1 == nullptr)) return -1;
-    for (int k = 0; k < n; k++) if (!streams[k] || !indexes[k] || !outs[k]) return -1;
+    for (int k = 0; k < n; k++) if (!streams[k] || !indexes[k] || (!to && !outs[k])) return -1;
     if (hipSetDevice(c->device) != hipSuccess) return -1;
     using Clock = std::chrono::steady_clock;
     auto ms_since = [](Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); };
@@ -3329,10 +3408,15 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
         if (!I.ok) continue;
         const DecodeItem &it = I.it;
         hs[k] = it.h; ws[k] = it.w; nears[k] = it.near; efforts[k] = it.effort;
-        I.row0 = row0 ? row0[k] : 0; I.row1 = row1 ? row1[k] : it.h;
+        if (to) {                                                        // the window's rows choose the segments; its columns do not shorten the decode
+            if (!deliver_dest_task(c, *to, k, it.h, it.w, I.deliver)) continue;
+            I.row0 = I.deliver.row0; I.row1 = I.deliver.row1;
+        } else {
+            I.row0 = row0 ? row0[k] : 0; I.row1 = row1 ? row1[k] : it.h;
+        }
         if (I.row0 < 0 || I.row1 <= I.row0 || I.row1 > it.h) continue;
         I.out_bytes = size_t(I.row1 - I.row0) * size_t(it.w);
-        if (caps[k] < I.out_bytes) continue;
+        if (!to && caps[k] < I.out_bytes) continue;
         const int R = I.V.H.every_rows;
         I.seg0 = I.row0 / R; I.seg1 = (I.row1 - 1) / R;
         I.base = std::max(0, I.seg0 * R - 2);
@@ -3358,7 +3442,12 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
     auto fail = [&](const char *what) {
         fprintf(stderr, "[nblic_amd] indexed batch decode: %s\n", what);
         if (st) hipStreamSynchronize(st);
-        for (IdxDecImage *I : live) { status[I->k] = -1; memset(outs[I->k], 0, I->out_bytes); }
+        for (IdxDecImage *I : live) { status[I->k] = -1; if (!to) memset(outs[I->k], 0, I->out_bytes); }
+        if (to) {
+            std::vector<DeliverTask> zeros;
+            for (IdxDecImage *I : live) zeros.push_back(I->deliver);
+            deliver_zeros(zeros, st);
+        }
         return -1;
     };
     if (st.create(hipStreamNonBlocking) != hipSuccess) return fail("cannot create a stream");
@@ -3367,7 +3456,8 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
     for (IdxDecImage *I : live) n_bounds += size_t(I->seg1 - I->seg0);
     // (device blocks are carved out of few allocations, every part at a multiple of 256 bytes: a call with one image makes three)
     const size_t verdict_bytes = up256(std::max<size_t>(1, n_bounds) * sizeof(uint32_t));
-    uint8_t *d_call = mem.make<uint8_t>(verdict_bytes + live.size() * sizeof(IndexUnpackTask));
+    const size_t unpack_task_bytes = up256(live.size() * sizeof(IndexUnpackTask));
+    uint8_t *d_call = mem.make<uint8_t>(verdict_bytes + unpack_task_bytes + (to ? live.size() * sizeof(DeliverTask) : 0));
     uint32_t *d_verdicts = reinterpret_cast<uint32_t *>(d_call);
     if (!d_verdicts || hipMemsetAsync(d_verdicts, 0, std::max<size_t>(1, n_bounds) * sizeof(uint32_t), st) != hipSuccess) return fail("cannot allocate the workspace");
     {
@@ -3382,6 +3472,10 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
             if (!I->d_stream) return fail("cannot allocate the workspace");
             I->d_index = I->d_stream + stream_buf_bytes(win);
             I->d_plane = I->d_index + index_bytes;
+            if (to) {                                                    // the window's rows count from the plane's first: row `base` of the image
+                I->deliver.src = I->d_plane; I->deliver.src_bytes = plane_bytes;
+                I->deliver.row0 -= I->base; I->deliver.row1 -= I->base;
+            }
             if (it.kind) I->d_tab = I->d_plane + plane_bytes;
             if (!upload_stream(I->d_stream, streams[I->k] + I->stream_off, win, st) ||
                 hipMemcpyAsync(I->d_index, indexes[I->k], ilen, hipMemcpyHostToDevice, st) != hipSuccess ||
@@ -3562,6 +3656,7 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
     split[2] = ms_since(t0);
     t0 = Clock::now();
     bool every = true;
+    std::vector<DeliverTask> deliveries;
     for (IdxDecImage *I : live) {
         uint32_t bad = 0;
         for (int s = I->seg0; s < I->seg1; s++) bad |= verdicts[size_t(I->d_verdict - d_verdicts) + size_t(s - I->seg0)];
@@ -3569,12 +3664,16 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
         if (bad || !ended) {
             fprintf(stderr, "[nblic_amd] indexed batch decode: image %d: %s\n", I->k,
                     bad ? "a segment does not end where the next entry starts (index and stream disagree)" : "the stream is damaged or ends too early");
-            memset(outs[I->k], 0, I->out_bytes);
+            if (to) { I->deliver.zero = 1; deliveries.push_back(I->deliver); }
+            else memset(outs[I->k], 0, I->out_bytes);
             continue;
         }
-        if (hipMemcpyAsync(outs[I->k], I->d_plane + size_t(I->row0 - I->base) * size_t(I->it.w), I->out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return fail("rows");
+        if (to) deliveries.push_back(I->deliver);
+        else if (hipMemcpyAsync(outs[I->k], I->d_plane + size_t(I->row0 - I->base) * size_t(I->it.w), I->out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return fail("rows");
         status[I->k] = 0;
     }
+    // `to`: ONE launch delivers every live image's window -- zeros for the images that failed above
+    if (to && !deliver_queue(deliveries.data(), deliveries.size(), reinterpret_cast<DeliverTask *>(d_call + verdict_bytes + unpack_task_bytes), st)) return fail("delivery");
     if (hipStreamSynchronize(st) != hipSuccess) return fail("rows");
     split[3] = ms_since(t0);
     { std::lock_guard<std::mutex> l(c->stat_m); for (int k = 0; k < 4; k++) c->idxdec_split[k] = split[k]; }
@@ -4579,6 +4678,98 @@ int nblic_amd_debug_index_unpack(nblic_amd_ctx *c, int n, const void *const *pac
     return 0;
 }
 
+// ---- k_deliver on caller-made planes (tests/test_decode_to_device.py), and its host walk (tests/test_deliver_host.py) -------
+static bool debug_deliver_task(DeliverTask &T, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero, size_t pitch) {
+    if (plane_rows < 1 || width < 1 || !window || !deliver_args_ok(format, scale, bias)) return false;
+    T = DeliverTask{};
+    T.src_pitch = uint32_t(width);
+    T.row0 = window[0]; T.row1 = window[1]; T.col0 = window[2]; T.col1 = window[3];
+    T.format = uint32_t(format); T.scale = scale; T.bias = bias; T.zero = zero ? 1u : 0u;
+    T.dst_pitch = pitch;
+    return pitch <= (size_t(1) << 40);
+}
+
+// Host only: the shared unit walk (deliver.h deliver_host) over the caller's plane of plane_rows x width into out + dst_offset,
+// one unit after the other.  The unit grid follows the destination's address as the kernel's does, so a caller that wants
+// the grid of a device buffer hands in `out` at the same residue of 16.  units / chunks: what a launch would count for the task.
+int nblic_amd_debug_deliver_host(const unsigned char *plane, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero,
+                                 int gate_status, unsigned char *out, size_t out_bytes, size_t dst_offset, size_t pitch_bytes,
+                                 unsigned long long *units, unsigned long long *chunks) {
+    DeliverTask T;
+    if (!plane || !out || !debug_deliver_task(T, plane_rows, width, window, format, scale, bias, zero, pitch_bytes)) return -1;
+    T.src = plane; T.src_bytes = size_t(plane_rows) * size_t(width);
+    T.dst = out + dst_offset;
+    if (dst_offset > out_bytes || !deliver_task_ok(T, uint32_t(plane_rows))) return -1;
+    if (deliver_extent(uint32_t(T.row1 - T.row0), uint32_t(T.col1 - T.col0), T.format, pitch_bytes) > out_bytes - dst_offset) return -1;
+    if (units) *units = deliver_task_units(T);
+    if (chunks) *chunks = deliver_task_chunks(T);
+    deliver_host(T, gate_status == -1 ? int(kDone) : gate_status);
+    return 0;
+}
+
+// ONE k_deliver launch over n caller-made planes as n tasks.  Plane k (plane_rows[k] x widths[k]) is uploaded at byte
+// base_offsets[k] (0 .. 15) of a zeroed buffer that is larger; the task may read up256(rows * width) bytes from there, as the
+// decoders' planes allow.  Destination k lies at byte dst_offsets[k] of a buffer of out_bytes[k] bytes filled with 0x5A, which
+// comes back whole in outs[k].  gate_status[k] != -1 is put into a SerialState on the device, the task's gate.  windows: four
+// ints per task (row0, row1, col0, col1).  -1: refused; -2: a HIP call failed.
+int nblic_amd_debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const *planes, const size_t *plane_bytes, const size_t *base_offsets,
+                            const int *plane_rows, const int *widths, const int *windows, const int *formats, const float *scales, const float *biases,
+                            const int *zeros, const size_t *pitches, const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs,
+                            const int *gate_status) {
+    constexpr int kMaxTasks = 65536;
+    constexpr uint8_t kPattern = 0x5A;
+    if (!c || n < 1 || n > kMaxTasks || !planes || !plane_bytes || !base_offsets || !plane_rows || !widths || !windows || !formats || !scales || !biases ||
+        !zeros || !pitches || !dst_offsets || !out_bytes || !outs || !gate_status) return -1;
+    const size_t count = size_t(n);
+    std::vector<DeliverTask> tasks(count);
+    std::vector<size_t> plane_at(count), out_at(count);
+    size_t planes_total = 0, outs_total = 0;
+    for (int k = 0; k < n; k++) {
+        const size_t i = size_t(k);
+        DeliverTask &T = tasks[i];
+        if (!planes[k] || !outs[k] || base_offsets[k] > 15 || !debug_deliver_task(T, plane_rows[k], widths[k], windows + 4 * i, formats[k], scales[k], biases[k], zeros[k], pitches[k]))
+            return -1;
+        if (plane_bytes[k] != size_t(plane_rows[k]) * size_t(widths[k]) || plane_bytes[k] > (size_t(1) << 30) || out_bytes[k] > (size_t(1) << 30) || dst_offsets[k] > out_bytes[k]) return -1;
+        T.src_bytes = up256(plane_bytes[k]);
+        plane_at[i] = planes_total; planes_total += up256(base_offsets[k] + T.src_bytes + 16);
+        out_at[i] = outs_total; outs_total += up256(out_bytes[k]);
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    Stream st;
+    DevPool mem;
+    uint8_t *d_planes = mem.make<uint8_t>(planes_total), *d_outs = mem.make<uint8_t>(outs_total);
+    SerialState *d_gates = mem.make<SerialState>(count);
+    DeliverTask *d_tasks = mem.make<DeliverTask>(count);
+    if (!d_planes || !d_outs || !d_gates || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    for (int k = 0; k < n; k++) {                                        // the addresses are known now: the rest of the checks
+        const size_t i = size_t(k);
+        DeliverTask &T = tasks[i];
+        T.src = d_planes + plane_at[i] + base_offsets[k];
+        T.dst = d_outs + out_at[i] + dst_offsets[k];
+        if (gate_status[k] != -1) T.gate = d_gates + i;
+        if (!deliver_task_ok(T, uint32_t(plane_rows[k])) ||
+            deliver_extent(uint32_t(T.row1 - T.row0), uint32_t(T.col1 - T.col0), T.format, T.dst_pitch) > out_bytes[k] - dst_offsets[k]) return -1;
+    }
+    std::vector<uint8_t> back(outs_total);
+    std::vector<SerialState> gates(count);
+    for (int k = 0; k < n; k++) gates[size_t(k)].status = gate_status[k];
+    const bool ok = [&]() -> bool {
+        HIP_OK(hipMemsetAsync(d_planes, 0, planes_total, st));
+        HIP_OK(hipMemsetAsync(d_outs, kPattern, outs_total, st));
+        HIP_OK(hipMemcpyAsync(d_gates, gates.data(), count * sizeof(SerialState), hipMemcpyHostToDevice, st));
+        for (int k = 0; k < n; k++)
+            HIP_OK(hipMemcpyAsync(d_planes + plane_at[size_t(k)] + base_offsets[k], planes[k], plane_bytes[k], hipMemcpyHostToDevice, st));
+        if (!deliver_queue(tasks.data(), count, d_tasks, st)) return false;
+        HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    if (!ok) return -2;
+    for (int k = 0; k < n; k++) memcpy(outs[k], back.data() + out_at[size_t(k)], out_bytes[k]);
+    return 0;
+}
+
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
 
 int nblic_amd_copy_stats(nblic_amd_ctx *c, long out[4]) {
@@ -4717,6 +4908,17 @@ int nblic_amd_decode_batch(nblic_amd_ctx *c, int n_images, const unsigned char *
     if (!c || n_images < 0) return -1;
     std::lock_guard<std::mutex> g(c->api);
     if (!decode_batch(c, n_images, streams, stream_lens, imgs, img_caps, heights, widths, nears, efforts, status)) return -1;
+    for (int k = 0; k < n_images; k++) if (status[k] != 0) return -1;
+    return 0;
+}
+
+int nblic_amd_decode_batch_to(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens, const nblic_amd_dest *dests,
+                              int format, float scale, float bias, int *heights, int *widths, int *nears, int *efforts, int *status) {
+    if (!c || c->broken || n_images < 0 || !streams || !stream_lens || !dests || !heights || !widths || !nears || !efforts || !status || !deliver_args_ok(format, scale, bias)) return -1;
+    for (int k = 0; k < n_images; k++) if (!streams[k]) return -1;
+    const DeliverTo to{dests, uint32_t(format), scale, bias};
+    std::lock_guard<std::mutex> g(c->api);
+    if (!decode_batch(c, n_images, streams, stream_lens, nullptr, nullptr, heights, widths, nears, efforts, status, &to)) return -1;
     for (int k = 0; k < n_images; k++) if (status[k] != 0) return -1;
     return 0;
 }
@@ -4872,6 +5074,13 @@ int nblic_amd_decode_batch_indexed(nblic_amd_ctx *c, int n_images, const unsigne
                                    const void *const *indexes, const size_t *index_lens, const int *row0, const int *row1,
                                    unsigned char *const *outs, const size_t *out_caps, int *heights, int *widths, int *nears, int *efforts, int *status) {
     return decode_batch_indexed(c, n_images, streams, stream_lens, indexes, index_lens, row0, row1, outs, out_caps, heights, widths, nears, efforts, status);
+}
+int nblic_amd_decode_batch_indexed_to(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                      const void *const *indexes, const size_t *index_lens, const nblic_amd_dest *dests, int format, float scale, float bias,
+                                      int *heights, int *widths, int *nears, int *efforts, int *status) {
+    if (!dests || !deliver_args_ok(format, scale, bias)) return -1;
+    const DeliverTo to{dests, uint32_t(format), scale, bias};
+    return decode_batch_indexed(c, n_images, streams, stream_lens, indexes, index_lens, nullptr, nullptr, nullptr, nullptr, heights, widths, nears, efforts, status, &to);
 }
 int nblic_amd_indexed_decode_split(nblic_amd_ctx *c, double ms[4]) {
     if (!c || !ms) return -1;

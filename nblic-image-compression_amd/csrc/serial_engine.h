@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "deliver.h"
+
 namespace nblic {
 
 // ---- resumable launches ---------------------------------------------------------------------------
@@ -180,6 +182,15 @@ inline uint32_t index_capture_units(const IndexCaptureTask &t) { return t.rec_by
 inline uint32_t index_capture_chunks(const IndexCaptureTask &t) { return (index_capture_units(t) + kIndexChunkBytes / 16 - 1) / (kIndexChunkBytes / 16); }
 // d_tasks[0..n) with first_chunk filled in (from 0), `chunks` their sum.  false: the launch failed.
 bool index_capture_launch(const IndexCaptureTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
+
+// ---- delivery: a window of each decoded plane into caller-owned device memory (deliver.h) ------------------------------------
+// k_deliver, in the family of the kernels above: tasks with first_chunk, one workgroup per chunk of kDeliverChunkUnits units,
+// a unit = at most sixteen pixels of one row whose destination starts at a multiple of 16 bytes.  The source row starts at
+// any byte (odd widths, any col0) and is read as aligned words shifted into place; the destination gets 16-byte stores but
+// for a row's head and tail.  uint8 is a copy; float16 / bfloat16 / float32 are float(px) * scale + bias, two roundings, then
+// round-to-nearest-even into the format.  A task with `zero`, or whose gate record is not kDone, writes zero bytes.
+// d_tasks[0..n) with first_chunk filled in (from 0), `chunks` their sum.  false: the launch failed.
+bool deliver_launch(const DeliverTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
 
 // ---- a packed index (index_pack.h), expanded on the device ------------------------------------------------------------------
 // A packed index is uploaded as it is (any address).  The bodies of the entries a round needs are written, unpacked, into an

@@ -1796,6 +1796,79 @@ bool index_capture_launch(const IndexCaptureTask *d_tasks, int n, uint32_t chunk
     return hipGetLastError() == hipSuccess;
 }
 
+// ---- delivery: windows of decoded planes into caller-owned device memory (deliver.h DeliverTask) -----------------------------
+static_assert(kDeliverChunkUnits == kIndexChunkUnits && kDone == 1, "deliver.h states both for host-only code");
+
+// The sixteen source bytes of a unit, slot k in byte k.  The aligned words around them when all of those lie inside the
+// readable bytes [lo, hi) -- nearly always; otherwise (a plane at an odd address, the last bytes of the last row) only the
+// bytes of slots [k_lo, k_hi), one by one.
+__device__ __forceinline__ u32x4 deliver_load(const NB_GLOBAL uint8_t *p, uintptr_t lo, uintptr_t hi, uint32_t k_lo, uint32_t k_hi) {
+    const uintptr_t a = uintptr_t(p) & ~uintptr_t(3);
+    if (a >= lo && a + ((uintptr_t(p) & 3) ? 20 : 16) <= hi) return load16_any(p);
+    uint32_t word[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++)
+        if (k >= k_lo && k < k_hi) word[k >> 2] |= uint32_t(p[k]) << ((k & 3) * 8);
+    return u32x4{word[0], word[1], word[2], word[3]};
+}
+
+// A unit's slots [k_lo, k_hi) to the destination, `d` the (16-byte-aligned) place of slot 0: ELEM blocks of 16 bytes, each
+// one store when all its slots are inside, element by element otherwise (a row's head and tail).
+template <uint32_t ELEM, class Value>
+__device__ __forceinline__ void deliver_store(NB_GLOBAL uint8_t *d, uint32_t k_lo, uint32_t k_hi, Value value) {
+    constexpr uint32_t kPer = 16 / ELEM;                              // elements of a block
+    typedef typename std::conditional<ELEM == 1, uint8_t, typename std::conditional<ELEM == 2, uint16_t, uint32_t>::type>::type Elem;
+#pragma unroll
+    for (uint32_t b = 0; b < ELEM; b++) {
+        const uint32_t k0 = b * kPer;
+        if (k_lo >= k0 + kPer || k_hi <= k0) continue;
+        if (k_lo <= k0 && k0 + kPer <= k_hi) {
+            uint32_t word[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (uint32_t e = 0; e < kPer; e++) word[e * ELEM / 4] |= value(k0 + e) << ((e * ELEM % 4) * 8);
+            ((NB_GLOBAL u32x4 *)d)[b] = u32x4{word[0], word[1], word[2], word[3]};
+        } else {
+#pragma unroll
+            for (uint32_t e = 0; e < kPer; e++)
+                if (k0 + e >= k_lo && k0 + e < k_hi) ((NB_GLOBAL Elem *)d)[k0 + e] = Elem(value(k0 + e));
+        }
+    }
+}
+
+// One workgroup per chunk of kDeliverChunkUnits units, one unit per lane and step: sixteen pixels of one row (deliver.h).
+// No LDS, no atomics; nothing is read outside the task's readable bytes and nothing written outside the window's rows.
+__global__ void __launch_bounds__(kIndexThreads) k_deliver(const DeliverTask *__restrict__ tasks, int n) {
+    const DeliverTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
+    const bool zero = T.zero != 0 || (T.gate && gp(T.gate)->status != kDone);
+    const uint32_t units = uint32_t(deliver_task_units(T)), u0 = (blockIdx.x - T.first_chunk) * kDeliverChunkUnits;
+    const uint32_t elem = deliver_elem(T.format);
+    const uintptr_t lo = uintptr_t(T.src), hi = lo + T.src_bytes;
+    for (uint32_t j = threadIdx.x; j < kDeliverChunkUnits; j += kIndexThreads) {
+        const uint32_t u = u0 + j;
+        if (u >= units) break;
+        const DeliverUnit U = deliver_unit_of(T, u);
+        if (U.c_lo == U.c_hi) continue;
+        const uint32_t k_lo = uint32_t(int(U.c_lo) - U.c0), k_hi = uint32_t(int(U.c_hi) - U.c0);
+        NB_GLOBAL uint8_t *d = gp(T.dst) + size_t(U.row) * size_t(T.dst_pitch) + ptrdiff_t(U.c0) * ptrdiff_t(elem);
+        u32x4 px = u32x4{0u, 0u, 0u, 0u};
+        if (!zero) px = deliver_load(gp(T.src) + size_t(uint32_t(T.row0) + U.row) * T.src_pitch + size_t(T.col0) + ptrdiff_t(U.c0), lo, hi, k_lo, k_hi);
+        const uint32_t w[4] = {px.x, px.y, px.z, px.w};
+        auto pixel = [&](uint32_t k) { return (w[k >> 2] >> ((k & 3) * 8)) & 0xFFu; };
+        switch (T.format) {                                              // (zero: +0.0 is zero bytes in every format)
+            case kDeliverU8: deliver_store<1>(d, k_lo, k_hi, pixel); break;
+            case kDeliverF16: deliver_store<2>(d, k_lo, k_hi, [&](uint32_t k) { return zero ? 0u : deliver_value(pixel(k), kDeliverF16, T.scale, T.bias); }); break;
+            case kDeliverBF16: deliver_store<2>(d, k_lo, k_hi, [&](uint32_t k) { return zero ? 0u : deliver_value(pixel(k), kDeliverBF16, T.scale, T.bias); }); break;
+            default: deliver_store<4>(d, k_lo, k_hi, [&](uint32_t k) { return zero ? 0u : deliver_value(pixel(k), kDeliverF32, T.scale, T.bias); }); break;
+        }
+    }
+}
+
+bool deliver_launch(const DeliverTask *d_tasks, int n, uint32_t chunks, hipStream_t s) {
+    if (n <= 0 || chunks == 0) return true;
+    hipLaunchKernelGGL(k_deliver, dim3(chunks), dim3(kIndexThreads), 0, s, d_tasks, n);
+    return hipGetLastError() == hipSuccess;
+}
+
 
 // ---- a packed index, expanded on the device (serial_engine.h IndexUnpackTask; the format: index_pack.h) --------------------
 constexpr uint32_t kUnpackWaves = kIndexThreads / 64;

@@ -1,0 +1,139 @@
+// Stand-alone check of csrc/deliver.h (host only): the unit walk of the delivery kernel on random windows, formats,
+// pitches and destination residues.  Plane and destination are heap blocks of EXACTLY the bytes the task may touch -- a
+// read or a store outside them is an overrun the sanitizer reports -- and every byte is compared with a plain
+// element-by-element loop that knows nothing of units; the units of a row must tile its columns in order, each one's
+// slot 0 at a multiple of 16 bytes; float16 is compared with a conversion through doubles (half_ref).  Build and run:
+//   g++ -std=c++17 -O2 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -o deliver_check tools/deliver_check.cpp && ./deliver_check
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <random>
+#include <vector>
+
+#include "../nblic-image-compression_amd/csrc/deliver.h"
+
+using namespace nblic;
+
+#define CHECK(x) do { if (!(x)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); return 1; } } while (0)
+
+// float -> binary16, round to nearest even, through doubles: the value in units of its quantum 2^(E - 10), E >= -14,
+// rounded by nearbyint (exact: a double has room for it).
+static uint16_t half_ref(float f) {
+    uint32_t bits;
+    memcpy(&bits, &f, 4);
+    const uint16_t sign = uint16_t((bits >> 16) & 0x8000u);
+    if (f != f) return sign | 0x7E00;
+    const double a = std::fabs(double(f));
+    if (a == 0.0) return sign;
+    if (std::isinf(a)) return sign | 0x7C00;
+    int e;
+    std::frexp(a, &e);
+    int E = e - 1 < -14 ? -14 : e - 1;
+    double q = std::nearbyint(std::ldexp(a, 10 - E));
+    if (q >= 2048.0) { q = 1024.0; E++; }
+    if (E > 15) return sign | 0x7C00;
+    if (q < 1024.0) return sign | uint16_t(q);                       // subnormal (E == -14), or zero
+    return sign | uint16_t(((E + 15) << 10) | (int(q) - 1024));
+}
+
+static int one_task(std::mt19937 &rng, uint32_t format, int rows_total, int width, int row0, int row1, int col0, int col1, size_t slack, size_t residue,
+                    float scale, float bias, bool zero) {
+    const uint32_t elem = deliver_elem(format), rows = uint32_t(row1 - row0), cols = uint32_t(col1 - col0);
+    const size_t pitch = size_t(cols) * elem + slack * elem;
+    const size_t extent = size_t(deliver_extent(rows, cols, format, pitch));
+    uint8_t *plane = static_cast<uint8_t *>(malloc(size_t(rows_total) * size_t(width)));
+    void *aligned = nullptr;
+    CHECK(posix_memalign(&aligned, 16, residue + extent) == 0);
+    uint8_t *block = static_cast<uint8_t *>(aligned);
+    CHECK(plane && block);
+    for (size_t i = 0; i < size_t(rows_total) * size_t(width); i++) plane[i] = uint8_t(rng());
+    // the destination ends where the block's usable bytes end: [block + residue, block + residue + extent)
+    uint8_t *dst = block + residue;
+    memset(block, 0x5A, residue + extent);
+    DeliverTask T{};
+    T.src = plane; T.src_bytes = size_t(rows_total) * size_t(width); T.src_pitch = uint32_t(width);
+    T.dst = dst; T.dst_pitch = pitch;
+    T.row0 = row0; T.row1 = row1; T.col0 = col0; T.col1 = col1;
+    T.format = format; T.scale = scale; T.bias = bias; T.zero = zero ? 1u : 0u;
+    CHECK(deliver_task_ok(T, uint32_t(rows_total)));
+    // the units of every row tile [0, cols) in order
+    const uint32_t per_row = deliver_row_units(cols, format);
+    CHECK(deliver_task_units(T) == (unsigned long long)(rows) * per_row);
+    for (uint32_t r = 0; r < rows; r++) {
+        uint32_t at = 0;
+        for (uint32_t j = 0; j < per_row; j++) {
+            const DeliverUnit U = deliver_unit_of(T, r * per_row + j);
+            CHECK(U.row == r && U.c_lo <= U.c_hi && U.c_hi - U.c_lo <= kDeliverUnitPixels);
+            CHECK((uintptr_t(dst) + size_t(r) * pitch + size_t(ptrdiff_t(U.c0) * ptrdiff_t(elem))) % 16 == 0);
+            if (U.c_lo == U.c_hi) continue;
+            CHECK(U.c_lo == at && int(U.c_lo) >= U.c0 && int(U.c_hi) <= U.c0 + 16);
+            at = U.c_hi;
+        }
+        CHECK(at == cols);
+    }
+    deliver_host(T, 1);
+    for (size_t i = 0; i < residue; i++) CHECK(block[i] == 0x5A);
+    for (uint32_t r = 0; r < rows; r++) {
+        for (uint32_t c = 0; c < cols; c++) {
+            const uint8_t px = plane[size_t(row0 + int(r)) * size_t(width) + size_t(col0) + c];
+            uint32_t want = 0;
+            if (!zero) {
+                if (format == kDeliverU8) want = px;
+                else {
+                    volatile float prod = float(px) * scale;
+                    const float v = prod + bias;
+                    uint32_t bits;
+                    memcpy(&bits, &v, 4);
+                    if (format == kDeliverF32) want = bits;
+                    else if (format == kDeliverBF16) want = (bits + 0x7FFFu + ((bits >> 16) & 1u)) >> 16;
+                    else want = half_ref(v);
+                }
+            }
+            uint32_t got = 0;
+            memcpy(&got, dst + size_t(r) * pitch + size_t(c) * elem, elem);
+            CHECK(got == want);
+        }
+        if (r + 1 < rows)
+            for (size_t g = size_t(cols) * elem; g < pitch; g++) CHECK(dst[size_t(r) * pitch + g] == 0x5A);
+    }
+    free(plane); free(block);
+    return 0;
+}
+
+int main() {
+    std::mt19937 rng(22);
+    const float norms[][2] = {{1.0f, 0.0f}, {1.0f / 255.0f, -0.5f}, {0.0078125f, -1.0f}, {1e-7f, 0.0f}, {300.0f, -1.0f}, {5.9604645e-8f, 0.0f}};
+    const int widths[] = {1, 15, 16, 17, 33, 131, 149, 150};
+    long tasks = 0;
+    for (uint32_t format = 0; format < kDeliverFormats; format++)
+        for (int width : widths)
+            for (int rep = 0; rep < 300; rep++) {
+                const int rows_total = 1 + int(rng() % 6);
+                const int row0 = int(rng() % uint32_t(rows_total)), row1 = row0 + 1 + int(rng() % uint32_t(rows_total - row0));
+                const int col0 = int(rng() % uint32_t(width)), col1 = col0 + 1 + int(rng() % uint32_t(width - col0));
+                const uint32_t elem = deliver_elem(format);
+                const float *nb = format == kDeliverU8 ? norms[0] : norms[rng() % 6];
+                if (one_task(rng, format, rows_total, width, row0, row1, col0, col1, rng() % 4, size_t(rng() % (16 / elem)) * elem, nb[0], nb[1], rng() % 8 == 0)) return 1;
+                tasks++;
+            }
+    // every float32 exponent around the halves' range, both signs, ties included: the integer conversion against half_ref
+    for (uint32_t e = 90; e < 150; e++)
+        for (uint32_t m = 0; m < (1u << 23); m += 0x3FF) {
+            for (uint32_t low : {0u, 1u, 0x0FFFu, 0x1000u, 0x1001u, 0x1FFFu}) {
+                const uint32_t bits = (e << 23) | ((m & ~0x1FFFu) | low);
+                for (uint32_t sign : {0u, 0x80000000u}) {
+                    float f;
+                    const uint32_t b = bits | sign;
+                    memcpy(&f, &b, 4);
+                    CHECK(deliver_f16_bits(b) == half_ref(f));
+                }
+            }
+        }
+    for (uint32_t b : {0x7F800000u, 0xFF800000u, 0u, 0x80000000u, 1u, 0x007FFFFFu, 0x33000000u, 0x33000001u, 0x477FEFFFu, 0x477FF000u}) {
+        float f;
+        memcpy(&f, &b, 4);
+        CHECK(deliver_f16_bits(b) == half_ref(f));
+    }
+    printf("deliver_check: %ld tasks, all bytes as expected\n", tasks);
+    return 0;
+}
