@@ -1,5 +1,6 @@
 // index_entries.h -- the host-only part of writing a seek index while encoding (pipeline.hip: the band encoder and the
-// indexed batch): how large an index is, where its entries sit, and the entries that WAIT.  An entry written down at
+// indexed batch): how large an index is, where its entries sit, which rows they stand in front of and how an encoder's
+// bands are cut there, which image of a batch gets an index, and the entries that WAIT.  An entry written down at
 // an entry row lacks one field, the decoder's 4-byte window: the four stream bytes behind the entry's position, which
 // the coder has not emitted yet (the final flush always provides them).  PendingEntries hands every emitted stream
 // byte to the entries that wait for it and seals an entry once its window is complete.  The job list of an indexed batch
@@ -47,6 +48,27 @@ inline long index_bytes(int kind, int h, int w, int effort, int every_rows) {
     if (h < 1 || w < 1 || h > kIndexMaxSide || w > kIndexMaxSide || every_rows < 1 || every_rows >= h) return -1;
     if (index_record_bytes(kind, w, effort) == 0) return -1;
     return long(index_total_bytes((h - 1) / every_rows, index_entry_bytes(kind, w, effort)));
+}
+
+// ---- where the entries are: the one statement of the rule every index writer follows -------------------------------------
+// An entry stands in front of row r when r is a multiple of R and r < h, and an encoder's band never crosses such a row.
+// The next band of an image that has coded rows [0, row0) (row0 < h), `band` rows at most; every < 1: no index, no cut.
+struct BandCut { int rows; bool entry; };                                // entry: an entry is written behind this band
+inline BandCut index_band_cut(int row0, int band, int h, int every) {
+    int rows = band < h - row0 ? band : h - row0;
+    if (every < 1) return BandCut{rows, false};
+    const int to_entry = every - row0 % every;                           // rows up to the next multiple of R
+    if (to_entry < rows) rows = to_entry;
+    return BandCut{rows, rows == to_entry && row0 + rows < h};
+}
+// Whether an image whose caller offers `cap` bytes for an index every R rows gets one: every = 0 when none is possible
+// (R < 1 or R >= h; index_bytes refuses the same), too_small when there is one and it does not fit (or the codec has none).
+struct IndexAdmission { int every, count; size_t entry_bytes; bool too_small; };
+inline IndexAdmission index_admit(int kind, int effort, int h, int w, int every_rows, size_t cap) {
+    if (every_rows < 1 || every_rows >= h) return IndexAdmission{0, 0, 0, false};
+    const long need = index_bytes(kind, h, w, effort, every_rows);
+    if (need < 0 || cap < size_t(need)) return IndexAdmission{0, 0, 0, true};
+    return IndexAdmission{every_rows, (h - 1) / every_rows, index_entry_bytes(kind, w, effort), false};
 }
 
 // Head and entry lengths around `count` entries that already sit at index_entry_at(k), then the seal.

@@ -445,6 +445,15 @@ static E1Job e1_job_front(const E1Buffers &b, int rows, int w, int near, int dbg
     return J;
 }
 
+// The front job of the band [row0, row0 + rows) of a w-wide plane on the device, in workspace b: the band encoder's and the
+// indexed batches'.
+static E1Job band_job_front(const nblic_amd_ctx *c, E1Buffers b, const uint8_t *plane, int row0, int rows, int w, int near) {
+    b.img = plane + size_t(row0) * size_t(w);
+    E1Job J = e1_job_front(b, rows, w, near, 0, long_chains_of(c));
+    J.row0 = row0;
+    return J;
+}
+
 // The job of k_serial_model for an image of h x w: `rows` rows per launch, whose records go to b.rec1 / b.pxs from
 // index 0 on (out_row0: the image row that sits there -- 0, or the first row of a band).
 static SerialJob model_job(const uint8_t *img, uint8_t *recon, const E1Buffers &b, double *stats, SerialState *state, int h, int w,
@@ -1882,11 +1891,14 @@ static void stream_free(nblic_amd_stream *s) {
     if (c && gid >= 0) release_group(c, gid);
 }
 
+// The rows per band of an encoder: what its caller asks for, or what one launch covers.
+static int encoder_band_rows(int band_rows, int h, int w, int effort) { return band_rows > 0 ? std::min(band_rows, h) : serial_rows_per_launch(h, w, effort, 0); }
+
 static nblic_amd_stream *stream_open(nblic_amd_ctx *c, const unsigned char *img, bool on_device, int h, int w, int near, int effort, int band_rows) {
     if (!c || !img || !size_ok(h, w, c->max_px) || hipSetDevice(c->device) != hipSuccess) return nullptr;
     auto *s = new nblic_amd_stream;
     s->c = c; s->h = h; s->w = w; s->near = iclip(near, 0, kMaxNear); s->effort = iclip(effort, 1, 3); s->k_step = k_step_for_near(s->near);
-    s->band_rows = band_rows > 0 ? (band_rows < h ? band_rows : h) : serial_rows_per_launch(h, w, s->effort, 0);
+    s->band_rows = encoder_band_rows(band_rows, h, w, s->effort);
     s->gid = take_group(c);   // for as long as the stream lives: its first slot's band workspace, its stream, its pinned job records
     Group &g = c->groups[size_t(s->gid)];
     const size_t n = size_t(h) * size_t(w);
@@ -1912,8 +1924,7 @@ static E1Buffers stream_band_buffers(const nblic_amd_stream *s, const Slot &sl, 
 // the front-half job records of the band that starts at row i0
 static void stream_band_jobs(nblic_amd_stream *s, Group &g, int i0, int rows) {
     const Slot &sl = g.slots[0];
-    g.h_jobs[0] = e1_job_front(stream_band_buffers(s, sl, i0), rows, s->w, s->near, 0, long_chains_of(g.ctx));
-    g.h_jobs[0].row0 = i0;
+    g.h_jobs[0] = band_job_front(g.ctx, stream_band_buffers(s, sl, i0), s->d_img, i0, rows, s->w, s->near);
     g.h_sjobs[0] = model_job(s->d_img, s->d_recon, sl.b, s->d_stats, sl.d_state, s->h, s->w, s->near, s->effort, rows, i0, g.ctx->d_redo);
 }
 
@@ -1946,7 +1957,7 @@ static bool stream_front_staged(nblic_amd_stream *s, Group &g, int i0, int rows,
     return hipGetLastError() == hipSuccess;
 }
 
-static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8_t *out, const uint8_t *end, uint32_t lo, uint32_t hi);
+static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, bool entry, const uint8_t *out, const uint8_t *end, uint32_t lo, uint32_t hi);
 static void stream_index_bytes(nblic_amd_stream *s, const uint8_t *out, const uint8_t *end);
 
 // Runs bands until the image is finished or the budget is spent.  1 finished, 0 suspended between two bands, -1 error.
@@ -1976,9 +1987,9 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
     rc.begin(p, cap - size_t(p - out));
     rc.lo = s->lo; rc.hi = s->hi;
     while (s->next_row < s->h) {
-        int rows = std::min(s->band_rows, s->h - s->next_row);
         const int i0 = s->next_row;
-        if (s->index_every > 0) rows = std::min(rows, s->index_every - i0 % s->index_every);     // a band never crosses an entry row
+        const BandCut cut = index_band_cut(i0, s->band_rows, s->h, s->index_every);      // a band never crosses an entry row
+        const int rows = cut.rows;
         stream_band_jobs(s, g, i0, rows);
         hipEvent_t e0 = g.tm.ev[0], e1 = g.tm.ev[1];
         if (hipMemcpyAsync(g.d_jobs, g.h_jobs, sizeof(E1Job), hipMemcpyHostToDevice, g.stream) != hipSuccess ||
@@ -2011,7 +2022,7 @@ static int stream_run(nblic_amd_stream *s, double budget_s, unsigned char *out, 
         if (rc.overflow) return fail("output buffer too small");
         s->next_row = i0 + rows; s->bands++;
         if (!staged) { std::lock_guard<std::mutex> l(c->stat_m); c->serial_launch_count++; }
-        if (s->index_every > 0 && !stream_index_band(s, i0, rows, out, rc.p, rc.lo, rc.hi)) return fail("index entry");
+        if (s->index_every > 0 && !stream_index_band(s, i0, rows, cut.entry, out, rc.p, rc.lo, rc.hi)) return fail("index entry");
         if (budget_s > 0 && s->next_row < s->h && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() >= budget_s) break;
     }
     s->lo = rc.lo; s->hi = rc.hi;
@@ -2471,6 +2482,16 @@ static Sha256 canonical_sha(Sha256 s) {
     return s;
 }
 
+// The head of the index entry in front of row `row` at ck, and behind it the header of its record: S as the coder stands
+// there (pos, interval or rANS state, and whatever else of the header the writer holds), rows_sha over rows [0, row).  The
+// rest of the body and the seal are the caller's.  Every encoder's index and index_build_batch's go through here.
+static void index_entry_head(uint8_t *ck, const DecodeItem &it, int every, int row, SerialState S, const Sha256 &rows_sha) {
+    S.next_row = row; S.status = kRunning;
+    const DecodeCheckpoint H = decode_head(it, every, row, S.pos & ~511ull, canonical_sha(rows_sha));
+    memcpy(ck, &H, sizeof H);
+    memcpy(ck + sizeof H, &S, sizeof S);
+}
+
 // Every field of an index, every entry (dstream_check), and -- when `stream` is given -- that it is the stream the index
 // was made for.  Host only.  0 = valid (V filled in), -1 = refused.
 static bool index_head_ok(const IndexHead &H, long max_px) {
@@ -2625,8 +2646,8 @@ static void stream_index_bytes(nblic_amd_stream *s, const uint8_t *out, const ui
 constexpr size_t kEntryWindowAt = sizeof(DecodeCheckpoint) + offsetof(SerialState, window);     // where an entry's window goes
 
 // After the band [i0, i0 + rows) has been coded: the bytes it emitted go to the pending entries, its rows into the row
-// hash, and at an entry row the entry is written down (all but its window).
-static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8_t *out, const uint8_t *end, uint32_t lo, uint32_t hi) {
+// hash, and behind a band that ends on an entry row (`entry`: index_band_cut) the entry is written down (all but its window).
+static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, bool entry, const uint8_t *out, const uint8_t *end, uint32_t lo, uint32_t hi) {
     stream_index_bytes(s, out, end);
     const size_t w = size_t(s->w), at = size_t(i0) * w;
     const uint8_t *plane = s->near > 0 ? s->d_recon : s->d_img;       // lossless: the reconstruction is the input
@@ -2637,7 +2658,7 @@ static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8
         hipStreamSynchronize(g.stream) != hipSuccess) return false;
     s->rows_sha.update(s->band_rows_host.data(), s->band_rows_host.size());
     const int r = i0 + rows, R = s->index_every;
-    if (r % R != 0 || r >= s->h) return true;
+    if (!entry) return true;
     const DecodeItem it{0, s->h, s->w, s->near, s->k_step, s->effort, 0, 0, -1, -1};
     const RecordLayout L = record_layout(0, s->w, s->effort);
     std::vector<uint8_t> ck(sizeof(DecodeCheckpoint) + L.bytes + 32, 0);
@@ -2653,10 +2674,9 @@ static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8
     SerialState M;
     memcpy(&M, model.data(), sizeof M);
     SerialState S{};
-    S.next_row = r; S.status = kRunning;
     const unsigned long long emitted = s->bytes_total + (unsigned long long)(end - out);
     S.pos = emitted + 4; S.lo = lo; S.hi = hi; S.bias = M.bias;
-    memcpy(rec, &S, sizeof S);
+    index_entry_head(ck.data(), it, R, r, S, s->rows_sha);
     uint8_t *tab = rec + sizeof S;
     memcpy(tab, model.data() + sizeof M, size_t(kContexts) * 4);                       // context biases
     uint32_t *dcnt = reinterpret_cast<uint32_t *>(tab) + kContexts;                   // counters, tree-major
@@ -2673,8 +2693,6 @@ static bool stream_index_band(nblic_amd_stream *s, int i0, int rows, const uint8
             sym[m * kMapSyms + k] = uint8_t(map[size_t(m) * 60 + 20 + k]);
             memcpy(hits + m * kMapSyms + k, &map[size_t(m) * 60 + 40 + k], 4);
         }
-    const DecodeCheckpoint H = decode_head(it, R, r, S.pos & ~511ull, canonical_sha(s->rows_sha));
-    memcpy(ck.data(), &H, sizeof H);
     s->entries.push_back(std::move(ck));                               // (moving the vector leaves its bytes where they are)
     s->pending.add(s->entries.back().data(), s->entries.back().size(), kEntryWindowAt, emitted);
     return true;
@@ -2710,7 +2728,6 @@ static size_t stream_index(nblic_amd_stream *s, void *buf, size_t cap) {
     return need;
 }
 
-// ---- default context behind the drop-in entry points ---------------------------------------
 // ---- the INDEXED BATCH: many -n0 -e1 images and their seek indexes, a group of images stepped through row bands together ----
 // What the band encoder does for one image per object (staged front, an entry record at every entry row), done for a
 // whole group per launch sequence: every live slot of a group holds one image in progress, a STEP carries one band of each
@@ -2747,29 +2764,87 @@ struct IdxPendingTasks {                                                 // the 
     void wait() { std::unique_lock<std::mutex> l(m); cv.wait(l, [this] { return left == 0; }); }
 };
 
-// One image of the batch between its first band and its last: the resumable coder (interval, bytes emitted, the running
-// SHA-256 of the stream and of the rows) and the index being written into the caller's buffer.  Touched by one task at a time.
-struct IdxImage {
-    int k = 0, h = 0, w = 0, every = 0;                                  // every: 0 = no index wanted (or none possible)
-    const uint8_t *host_plane = nullptr;                                 // host input: the rows are hashed from it
-    uint8_t *out = nullptr; size_t cap = 0;
+// The FRAME of a call, for this codec and for effort 0 below (indexed_batch): the arguments are checked and every image that
+// can be refused is refused before anything is launched, the admitted ones are handed out one by one to the drivers -- one
+// thread per group the call uses, each holding its group for the whole call (idx_run_driver) -- and the results are closed
+// once the drivers have ended.  What a codec adds is its IdxCodec: five facts and the step loop of its driver.
+struct IdxCall;
+struct IdxSplit { double ms[5] = {0}; long steps = 0; };                 // nblic_amd_indexed_batch_split's figures, of one driver or summed
+struct IdxCodec {
+    int kind, effort;
+    size_t min_out, max_out;                                             // in elements of `outs` (bytes; effort 0: 16-bit words): below min_out the image is refused, the capacity is clamped to max_out
+    void (*driver)(IdxCall &, Group &, IdxSplit &);                      // steps the group's slots through the batch's images
+};
+// The NBLIC coder of an image between its first band and its last (-e1 alone): interval, bytes emitted, the running SHA-256 of
+// the stream and of the rows, the entries that wait for their window.  Touched by one task at a time.
+struct IdxCoder {
     RangeScalar rc;
     unsigned long long emitted = 0;                                      // stream bytes so far, header included
     Sha256 stream_sha, rows_sha;
-    uint8_t *index = nullptr; size_t entry_bytes = 0; int count = 0, made = 0;
     PendingEntries pending;
+    int made = 0;
     std::atomic<bool> failed{false};                                     // out of room: the driver drops the image at its next step
 };
-struct IdxBand {                                                         // what a task codes: one band of one image
-    IdxImage *im; int i0, rows; const uint16_t *bins; uint32_t n_ev; const uint8_t *rows_host, *rec; bool last;
+struct IdxImage {                                                        // one admitted image and the index being written into the caller's buffer
+    int k = 0, h = 0, w = 0, every = 0, count = 0;                       // every: 0 = no index wanted (or none possible); count: its entries
+    const uint8_t *host_plane = nullptr;                                 // host input: the rows are hashed from it
+    void *out = nullptr; size_t cap = 0;                                 // in the codec's elements
+    uint8_t *index = nullptr; size_t entry_bytes = 0;
+    IdxCoder nb;
 };
 struct IdxCall {
-    nblic_amd_ctx *c; int n; const unsigned char *const *imgs; bool on_device; const int *hs, *ws, *every; int band_rows;
-    unsigned char *const *outs; const size_t *caps; long *lens; unsigned char *const *indexes; const size_t *icaps; long *ilens;
+    const IdxCodec &codec; nblic_amd_ctx *c; int n; const unsigned char *const *imgs; bool on_device; int band_rows; long *lens, *ilens;
+    std::vector<std::unique_ptr<IdxImage>> images;                       // by position in the batch; empty: refused before the call started
     std::atomic<int> next{0};
     std::atomic<bool> failed{false};                                     // a device-side failure: the call is over
     IdxPool pool;
-    std::mutex m; double split[5] = {0}; long steps = 0;                 // summed over the groups (guarded by m)
+    std::mutex m; IdxSplit split;                                        // summed over the groups (guarded by m)
+    void fail(const IdxImage &I) { lens[I.k] = -1; if (I.every) ilens[I.k] = -1; }
+    IdxImage *next_image() {                                             // the batch's next admitted image; nullptr: all are taken
+        for (;;) {
+            const int j = next.fetch_add(1);
+            if (j >= n) return nullptr;
+            if (images[size_t(j)]) return images[size_t(j)].get();
+        }
+    }
+};
+struct IdxLive { IdxImage *im = nullptr; int row0 = 0, band = 0; const uint8_t *plane = nullptr; };     // the image a slot works on, rows [0, row0) queued
+
+// Image I's plane where slot s's kernels read it: a device input as it is, a host input copied into the slot on st.
+// nullptr: the copy could not be queued.
+static const uint8_t *idx_plane(const IdxCall &q, const IdxImage &I, Slot &s, hipStream_t st) {
+    if (q.on_device) return q.imgs[I.k];
+    const size_t n = size_t(I.h) * size_t(I.w);
+    if (s.d_img.reserve(n) != hipSuccess || hipMemcpyAsync(s.d_img, q.imgs[I.k], n, hipMemcpyHostToDevice, st) != hipSuccess) return nullptr;
+    return s.d_img;
+}
+
+// jobs[j]: the front job of the next band of live slot L (workspace s), cut by the band rule.  true: an entry stands behind
+// the band, and the task that makes its decoder record at byte rec_at of the step's records has been appended.
+static bool idx_band_job(nblic_amd_ctx *c, const IdxLive &L, const Slot &s, E1Job *jobs, int j, IndexRecordTask *tasks, int &n_tasks, size_t rec_at) {
+    const BandCut cut = index_band_cut(L.row0, L.band, L.im->h, L.im->every);
+    jobs[j] = band_job_front(c, s.b, L.plane, L.row0, cut.rows, L.im->w, 0);
+    if (cut.entry) tasks[n_tasks++] = IndexRecordTask{j, 0, (unsigned long long)(rec_at)};
+    return cut.entry;
+}
+
+// One driver thread: takes a group, runs the codec's driver on it, adds its figures to the call's.
+static void idx_run_driver(IdxCall &q) {
+    nblic_amd_ctx *c = q.c;
+    if (hipSetDevice(c->device) != hipSuccess) { q.failed = true; return; }
+    const int gid = take_group(c);
+    IdxSplit sp;
+    q.codec.driver(q, c->groups[size_t(gid)], sp);                       // (everything the driver owns goes before the group is released)
+    {
+        std::lock_guard<std::mutex> l(q.m);
+        for (int k = 0; k < 5; k++) q.split.ms[k] += sp.ms[k];
+        q.split.steps += sp.steps;
+    }
+    release_group(c, gid);
+}
+
+struct IdxBand {                                                         // what a task codes: one band of one image
+    IdxImage *im; int i0, rows; const uint16_t *bins; uint32_t n_ev; const uint8_t *rows_host, *rec; bool last;
 };
 
 // The band [i0, i0 + rows) of an image has been coded on the device: range-code its bins, hash its rows, hand the new stream
@@ -2777,242 +2852,159 @@ struct IdxCall {
 // last band.
 static void idx_code_band(IdxCall &q, const IdxBand &b) {
     IdxImage &I = *b.im;
-    if (I.failed) return;
-    auto fail = [&] { I.failed = true; q.lens[I.k] = -1; if (I.every) q.ilens[I.k] = -1; };
+    IdxCoder &C = I.nb;
+    if (C.failed) return;
+    auto fail = [&] { C.failed = true; q.fail(I); };
+    uint8_t *const out = static_cast<uint8_t *>(I.out);
+    const DecodeItem it{0, I.h, I.w, 0, k_step_for_near(0), 1, 0, 0, -1, -1};
     if (b.i0 == 0) {
-        write_header(I.out, I.h, I.w, 0, k_step_for_near(0), 1);
-        I.rc.begin(I.out + kHeaderBytes, I.cap - kHeaderBytes);
-        I.stream_sha.update(I.out, kHeaderBytes);
-        I.emitted = kHeaderBytes;
+        write_header(out, I.h, I.w, 0, k_step_for_near(0), 1);
+        C.rc.begin(out + kHeaderBytes, I.cap - kHeaderBytes);
+        C.stream_sha.update(out, kHeaderBytes);
+        C.emitted = kHeaderBytes;
     }
-    const uint8_t *const from = I.rc.p;
-    I.rc.feed(b.bins, b.n_ev);
-    if (I.rc.overflow || (b.last && I.rc.finish() == SIZE_MAX)) return fail();
-    I.pending.bytes(I.emitted, from, I.rc.p);
-    I.stream_sha.update(from, size_t(I.rc.p - from));
-    I.emitted += (unsigned long long)(I.rc.p - from);
-    if (I.every) I.rows_sha.update(b.rows_host, size_t(b.rows) * size_t(I.w));
+    const uint8_t *const from = C.rc.p;
+    C.rc.feed(b.bins, b.n_ev);
+    if (C.rc.overflow || (b.last && C.rc.finish() == SIZE_MAX)) return fail();
+    C.pending.bytes(C.emitted, from, C.rc.p);
+    C.stream_sha.update(from, size_t(C.rc.p - from));
+    C.emitted += (unsigned long long)(C.rc.p - from);
+    if (I.every) C.rows_sha.update(b.rows_host, size_t(b.rows) * size_t(I.w));
     if (b.rec) {                                                         // an entry row: everything but the window, which waits
-        const int r = b.i0 + b.rows;
-        const DecodeItem it{0, I.h, I.w, 0, k_step_for_near(0), 1, 0, 0, -1, -1};
-        uint8_t *ck = I.index + index_entry_at(I.made, I.entry_bytes), *rec = ck + sizeof(DecodeCheckpoint);
+        uint8_t *ck = I.index + index_entry_at(C.made, I.entry_bytes), *rec = ck + sizeof(DecodeCheckpoint);
         memcpy(rec, b.rec, kDecodeStateBytes + 2 * size_t(I.w));
         SerialState S;
         memcpy(&S, rec, sizeof S);                                       // zero but for `bias` (k_index_records)
-        S.next_row = r; S.status = kRunning; S.pos = I.emitted + 4; S.lo = I.rc.lo; S.hi = I.rc.hi;
-        memcpy(rec, &S, sizeof S);
-        const DecodeCheckpoint H = decode_head(it, I.every, r, S.pos & ~511ull, canonical_sha(I.rows_sha));
-        memcpy(ck, &H, sizeof H);
-        I.pending.add(ck, I.entry_bytes, kEntryWindowAt, I.emitted);
-        I.made++;
+        S.pos = C.emitted + 4; S.lo = C.rc.lo; S.hi = C.rc.hi;
+        index_entry_head(ck, it, I.every, b.i0 + b.rows, S, C.rows_sha);
+        C.pending.add(ck, I.entry_bytes, kEntryWindowAt, C.emitted);
+        C.made++;
     }
     if (!b.last) return;
-    q.lens[I.k] = long(I.emitted);
+    q.lens[I.k] = long(C.emitted);
     if (!I.every) return;
-    if (I.made != I.count || !I.pending.waiting.empty()) { q.ilens[I.k] = -1; return; }     // (cannot happen: the flush provides every window)
-    IndexHead H = index_head(DecodeItem{0, I.h, I.w, 0, k_step_for_near(0), 1, 0, 0, -1, -1}, I.every, I.count, I.emitted);
-    I.stream_sha.digest(H.stream_sha);
+    if (C.made != I.count || !C.pending.waiting.empty()) { q.ilens[I.k] = -1; return; }     // (cannot happen: the flush provides every window)
+    IndexHead H = index_head(it, I.every, I.count, C.emitted);
+    C.stream_sha.digest(H.stream_sha);
     index_close(I.index, &H, I.count, I.entry_bytes);
     q.ilens[I.k] = long(index_total_bytes(I.count, I.entry_bytes));
 }
 
-// The rows per band of an image of the batch: stream_open's rule.
-static int idx_band_rows(const IdxCall &q, int h, int w) { return q.band_rows > 0 ? std::min(q.band_rows, h) : serial_rows_per_launch(h, w, 1, 0); }
-
-// One driver: holds one group for the whole call and steps its slots through the batch's images.
-static void idx_driver(IdxCall &q, std::vector<std::unique_ptr<IdxImage>> &images) {
+// The step loop of -e1: a step waits for its totals in the middle, and for the tasks of the step before at its end.
+static void idx_driver(IdxCall &q, Group &g, IdxSplit &sp) {
     nblic_amd_ctx *c = q.c;
-    if (hipSetDevice(c->device) != hipSuccess) { q.failed = true; return; }
-    const int gid = take_group(c);
-    {                                                                    // (everything the driver owns goes before the group is released)
-        Group &g = c->groups[size_t(gid)];
-        const hipStream_t st = g.stream;
-        const int n_slots = int(g.slots.size());
-        struct Live { IdxImage *im = nullptr; int row0 = 0, band = 0; const uint8_t *plane = nullptr; };
-        std::vector<Live> live{size_t(n_slots)};
-        struct Set { Locked bins, recs, rows; } sets[2];                 // what a step's tasks read (Locked counts 16-bit words)
-        DevBuf<uint16_t> d_bins; DevBuf<uint8_t> d_recs;
-        Pinned<IndexRecordTask> h_tasks; DevBuf<IndexRecordTask> d_tasks;
-        IdxPendingTasks tasks_left;
-        std::vector<int> slot_of(size_t(n_slots), 0);
-        std::vector<size_t> bins_at(size_t(n_slots), 0), rec_at(size_t(n_slots), 0), rows_at(size_t(n_slots), 0);
-        double split[5] = {0}; long steps = 0;
-        bool ok = h_tasks.alloc(size_t(n_slots)) == hipSuccess && d_tasks.alloc(size_t(n_slots)) == hipSuccess;
-        auto grow = [](Locked &b, size_t bytes) { return bytes <= b.capacity() * 2 || b.alloc((bytes + bytes / 4 + 4096) / 2); };
-        for (long t = 0; ok && !q.failed; t++) {
-            // ---- which image each slot works on
-            for (int k = 0; k < n_slots; k++) {
-                Live &L = live[size_t(k)];
-                if (L.im && (L.row0 >= L.im->h || L.im->failed)) L.im = nullptr;
-                while (!L.im) {
-                    const int j = q.next.fetch_add(1);
-                    if (j >= q.n) break;
-                    IdxImage *I = images[size_t(j)].get();
-                    if (!I) continue;                                    // refused before the call started (idx_prepare)
-                    Slot &s = g.slots[size_t(k)];
-                    L.band = idx_band_rows(q, I->h, I->w);
-                    const size_t n = size_t(I->h) * size_t(I->w);
-                    if (!(ok = ensure_pixels(s, size_t(L.band) * size_t(I->w)))) break;
-                    if (q.on_device) L.plane = q.imgs[j];
-                    else {
-                        if (!(ok = s.d_img.reserve(n) == hipSuccess && hipMemcpyAsync(s.d_img, q.imgs[j], n, hipMemcpyHostToDevice, st) == hipSuccess)) break;
-                        L.plane = s.d_img;
-                    }
-                    L.im = I; L.row0 = 0;
-                }
-                if (!ok) break;
-            }
-            if (!ok) break;
-            // ---- 1. job records of the live slots
-            int n_jobs = 0;
-            for (int k = 0; k < n_slots; k++) {
-                Live &L = live[size_t(k)];
-                if (!L.im) continue;
-                const IdxImage &I = *L.im;
-                int rows = std::min(L.band, I.h - L.row0);
-                if (I.every) rows = std::min(rows, I.every - L.row0 % I.every);           // a band never crosses an entry row
-                E1Buffers b = g.slots[size_t(k)].b;
-                b.img = L.plane + size_t(L.row0) * size_t(I.w);
-                g.h_jobs[n_jobs] = e1_job_front(b, rows, I.w, 0, 0, long_chains_of(c));
-                g.h_jobs[n_jobs].row0 = L.row0;
-                slot_of[size_t(n_jobs++)] = k;
-            }
-            if (n_jobs == 0) break;
-            hipEvent_t *ev = g.tm.ev;                                    // marks of the step's five parts
-            ok = hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, st) == hipSuccess;
-            if (!ok) break;
-            hipEventRecord(ev[0], st);
-            // ---- 2. / 3. fresh tables for the jobs that start an image, then the front half of every band
-            for (int j = 0; j < n_jobs; j++) if (g.h_jobs[j].row0 == 0) e1_launch_init(g.d_jobs + j, 1, st);
-            e1_launch_front_band(g.d_jobs, g.h_jobs, n_jobs, st);
-            hipEventRecord(ev[1], st);
-            // ---- 4. totals
-            ok = hipMemcpyAsync(g.h_totals, g.d_totals, size_t(n_slots) * kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
-            hipEventRecord(ev[2], st);
-            if (!ok || hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { ok = false; break; }
-            // ---- 5. the back half: bins of all jobs side by side in one buffer
-            size_t n_bins = 0, rec_bytes = 0, rows_bytes = 0; int n_tasks = 0;
-            for (int j = 0; j < n_jobs && ok; j++) {
-                const int k = slot_of[size_t(j)];
-                const uint32_t n_ev = g.h_totals[size_t(k) * kTotalsSlot + 2];
-                count_long_chains(c, g.h_totals + size_t(k) * kTotalsSlot);
-                ok = n_ev < 0x7FFFFFFFu && ensure_events(g.slots[size_t(k)], n_ev);
-                bins_at[size_t(j)] = n_bins;
-                n_bins += (size_t(n_ev) + 64 + 63) & ~size_t(63);
-                const IdxImage &I = *live[size_t(k)].im;
-                const int r = g.h_jobs[j].row0 + g.h_jobs[j].h;
-                rec_at[size_t(j)] = SIZE_MAX;
-                if (I.every && r % I.every == 0 && r < I.h) {
-                    rec_at[size_t(j)] = rec_bytes;
-                    h_tasks[n_tasks++] = IndexRecordTask{j, 0, (unsigned long long)(rec_bytes)};
-                    rec_bytes += up256(kDecodeStateBytes + 2 * size_t(I.w));
-                }
-                rows_at[size_t(j)] = rows_bytes;
-                if (q.on_device && I.every) rows_bytes += size_t(g.h_jobs[j].n);
-            }
-            if (!ok) break;
-            Set &S = sets[t & 1];                                        // free: the tasks of step t - 2 ended before step t - 1 was handed over
-            ok = (n_bins <= d_bins.capacity() || d_bins.alloc(n_bins + n_bins / 4 + 4096) == hipSuccess) &&
-                 (rec_bytes <= d_recs.capacity() || d_recs.alloc(rec_bytes) == hipSuccess) &&
-                 grow(S.bins, n_bins * 2) && grow(S.recs, rec_bytes) && grow(S.rows, rows_bytes);
-            if (!ok) break;
-            for (int j = 0; j < n_jobs; j++) {
-                E1Buffers b = g.slots[size_t(slot_of[size_t(j)])].b;
-                b.img = g.h_jobs[j].b.img; b.coded = d_bins + bins_at[size_t(j)];
-                e1_job_back(g.h_jobs[j], b, g.h_totals[size_t(slot_of[size_t(j)]) * kTotalsSlot + 2]);
-            }
-            ok = hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, st) == hipSuccess &&
-                 (!n_tasks || hipMemcpyAsync(d_tasks, h_tasks, size_t(n_tasks) * sizeof(IndexRecordTask), hipMemcpyHostToDevice, st) == hipSuccess);
-            if (!ok) break;
-            hipEventRecord(ev[3], st);
-            e1_launch_back(g.d_jobs, g.h_jobs, n_jobs, st, nullptr, true);
-            // ---- 6. the decoder records of the jobs whose band ends on an entry row
-            e1_launch_index_records(g.d_jobs, d_tasks, n_tasks, d_recs, st);
-            hipEventRecord(ev[4], st);
-            // ---- 7. one copy of the step's bins, one of its records (and the rows of device inputs, for the row hash)
-            ok = hipMemcpyAsync(static_cast<uint16_t *>(S.bins), d_bins, n_bins * sizeof(uint16_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                 (!rec_bytes || hipMemcpyAsync(static_cast<uint16_t *>(S.recs), d_recs, rec_bytes, hipMemcpyDeviceToHost, st) == hipSuccess);
-            uint8_t *const rows_host = reinterpret_cast<uint8_t *>(static_cast<uint16_t *>(S.rows));
-            for (int j = 0; j < n_jobs && ok && q.on_device; j++)
-                if (live[size_t(slot_of[size_t(j)])].im->every)
-                    ok = hipMemcpyAsync(rows_host + rows_at[size_t(j)], g.h_jobs[j].b.img, size_t(g.h_jobs[j].n), hipMemcpyDeviceToHost, st) == hipSuccess;
-            hipEventRecord(ev[5], st);
-            if (!ok || hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { ok = false; break; }
-            for (int k = 0; k < 4; k++) {
-                float ms = 0.f;
-                const int a = k < 2 ? k : k + 1;                         // (2 -> 3 is the host's sizing of the back half)
-                if (hipEventElapsedTime(&ms, ev[a], ev[a + 1]) == hipSuccess) split[k] += ms;
-            }
-            const auto w0 = std::chrono::steady_clock::now();
-            tasks_left.wait();                                           // step t - 1 is coded: an image's bands are coded in order
-            split[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-            steps++;
-            tasks_left.add(n_jobs);
-            const uint8_t *const recs_host = reinterpret_cast<const uint8_t *>(static_cast<uint16_t *>(S.recs));
-            for (int j = 0; j < n_jobs; j++) {
-                Live &L = live[size_t(slot_of[size_t(j)])];
-                IdxImage *I = L.im;
-                const int rows = g.h_jobs[j].h;
-                const uint8_t *rows_src = !I->every ? nullptr : q.on_device ? rows_host + rows_at[size_t(j)] : I->host_plane + size_t(L.row0) * size_t(I->w);
-                const IdxBand b{I, L.row0, rows, static_cast<uint16_t *>(S.bins) + bins_at[size_t(j)], g.h_jobs[j].n_ev, rows_src,
-                                rec_at[size_t(j)] == SIZE_MAX ? nullptr : recs_host + rec_at[size_t(j)], L.row0 + rows >= I->h};
-                q.pool.post([&q, &tasks_left, b] { idx_code_band(q, b); tasks_left.done(); });
-                L.row0 += rows;
-            }
+    const hipStream_t st = g.stream;
+    const int n_slots = int(g.slots.size());
+    std::vector<IdxLive> live{size_t(n_slots)};
+    struct Set { Locked bins, recs, rows; } sets[2];                     // what a step's tasks read (Locked counts 16-bit words)
+    DevBuf<uint16_t> d_bins; DevBuf<uint8_t> d_recs;
+    Pinned<IndexRecordTask> h_tasks; DevBuf<IndexRecordTask> d_tasks;
+    IdxPendingTasks tasks_left;
+    std::vector<int> slot_of(size_t(n_slots), 0);
+    std::vector<size_t> bins_at(size_t(n_slots), 0), rec_at(size_t(n_slots), 0), rows_at(size_t(n_slots), 0);
+    bool ok = h_tasks.alloc(size_t(n_slots)) == hipSuccess && d_tasks.alloc(size_t(n_slots)) == hipSuccess;
+    auto grow = [](Locked &b, size_t bytes) { return bytes <= b.capacity() * 2 || b.alloc((bytes + bytes / 4 + 4096) / 2); };
+    for (long t = 0; ok && !q.failed; t++) {
+        // ---- which image each slot works on
+        for (int k = 0; k < n_slots; k++) {
+            IdxLive &L = live[size_t(k)];
+            if (L.im && (L.row0 >= L.im->h || L.im->nb.failed)) L.im = nullptr;
+            IdxImage *I = L.im ? nullptr : q.next_image();
+            if (!I) continue;
+            Slot &s = g.slots[size_t(k)];
+            L.band = encoder_band_rows(q.band_rows, I->h, I->w, 1);
+            if (!(ok = ensure_pixels(s, size_t(L.band) * size_t(I->w)) && (L.plane = idx_plane(q, *I, s, st)) != nullptr)) break;
+            L.im = I; L.row0 = 0;
         }
-        if (!ok) { q.failed = true; fprintf(stderr, "[nblic_amd] indexed batch: a device step failed\n"); }
-        hipStreamSynchronize(st);
-        tasks_left.wait();
-        std::lock_guard<std::mutex> l(q.m);
-        for (int k = 0; k < 5; k++) q.split[k] += split[k];
-        q.steps += steps;
-    }
-    release_group(c, gid);
-}
-
-static int encode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *const *imgs, bool on_device, const int *hs, const int *ws, const int *every,
-                                int band_rows, unsigned char *const *outs, const size_t *caps, long *lens, unsigned char *const *indexes, const size_t *icaps, long *ilens) {
-    if (!c || c->broken || n < 1 || !imgs || !hs || !ws || !every || !outs || !caps || !lens || (indexes && (!icaps || !ilens))) return -1;
-    for (int k = 0; k < n; k++) if (every[k] < 0 || !imgs[k] || !outs[k]) return -1;
-    if (hipSetDevice(c->device) != hipSuccess) return -1;
-    IdxCall q{c, n, imgs, on_device, hs, ws, every, band_rows, outs, caps, lens, indexes, icaps, ilens};
-    std::vector<std::unique_ptr<IdxImage>> images{size_t(n)};
-    int n_live = 0;
-    for (int k = 0; k < n; k++) {                                        // what can be refused is refused before anything is launched
-        lens[k] = -1;
-        if (ilens) ilens[k] = 0;
-        const size_t cap = std::min(caps[k], size_t(1) << 46);
-        if (!size_ok(hs[k], ws[k], c->max_px) || cap < size_t(kHeaderBytes) + 4) continue;
-        auto I = std::make_unique<IdxImage>();
-        I->k = k; I->h = hs[k]; I->w = ws[k]; I->out = outs[k]; I->cap = cap;
-        I->host_plane = on_device ? nullptr : imgs[k];
-        if (indexes && indexes[k] && every[k] >= 1 && every[k] < hs[k]) {
-            const long need = index_bytes(0, hs[k], ws[k], 1, every[k]);
-            if (need < 0 || icaps[k] < size_t(need)) ilens[k] = -1;                       // the stream is still delivered
-            else { I->every = every[k]; I->index = indexes[k]; I->entry_bytes = index_entry_bytes(0, ws[k], 1); I->count = (hs[k] - 1) / every[k]; }
+        if (!ok) break;
+        // ---- 1. job records of the live slots, and the tasks of the bands that end on an entry row
+        int n_jobs = 0, n_tasks = 0; size_t rec_bytes = 0;
+        for (int k = 0; k < n_slots; k++) {
+            const IdxLive &L = live[size_t(k)];
+            if (!L.im) continue;
+            const bool entry = idx_band_job(c, L, g.slots[size_t(k)], g.h_jobs, n_jobs, h_tasks, n_tasks, rec_bytes);
+            rec_at[size_t(n_jobs)] = entry ? rec_bytes : SIZE_MAX;
+            if (entry) rec_bytes += up256(kDecodeStateBytes + 2 * size_t(L.im->w));
+            slot_of[size_t(n_jobs++)] = k;
         }
-        images[size_t(k)] = std::move(I);
-        n_live++;
+        if (n_jobs == 0) break;
+        hipEvent_t *ev = g.tm.ev;                                        // marks of the step's five parts
+        ok = hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, st) == hipSuccess;
+        if (!ok) break;
+        hipEventRecord(ev[0], st);
+        // ---- 2. / 3. fresh tables for the jobs that start an image, then the front half of every band
+        for (int j = 0; j < n_jobs; j++) if (g.h_jobs[j].row0 == 0) e1_launch_init(g.d_jobs + j, 1, st);
+        e1_launch_front_band(g.d_jobs, g.h_jobs, n_jobs, st);
+        hipEventRecord(ev[1], st);
+        // ---- 4. totals
+        ok = hipMemcpyAsync(g.h_totals, g.d_totals, size_t(n_slots) * kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+        hipEventRecord(ev[2], st);
+        if (!ok || hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { ok = false; break; }
+        // ---- 5. the back half: bins of all jobs side by side in one buffer
+        size_t n_bins = 0, rows_bytes = 0;
+        for (int j = 0; j < n_jobs && ok; j++) {
+            const int k = slot_of[size_t(j)];
+            const uint32_t n_ev = g.h_totals[size_t(k) * kTotalsSlot + 2];
+            count_long_chains(c, g.h_totals + size_t(k) * kTotalsSlot);
+            ok = n_ev < 0x7FFFFFFFu && ensure_events(g.slots[size_t(k)], n_ev);
+            bins_at[size_t(j)] = n_bins;
+            n_bins += (size_t(n_ev) + 64 + 63) & ~size_t(63);
+            rows_at[size_t(j)] = rows_bytes;
+            if (q.on_device && live[size_t(k)].im->every) rows_bytes += size_t(g.h_jobs[j].n);
+        }
+        if (!ok) break;
+        Set &S = sets[t & 1];                                            // free: the tasks of step t - 2 ended before step t - 1 was handed over
+        ok = (n_bins <= d_bins.capacity() || d_bins.alloc(n_bins + n_bins / 4 + 4096) == hipSuccess) &&
+             (rec_bytes <= d_recs.capacity() || d_recs.alloc(rec_bytes) == hipSuccess) &&
+             grow(S.bins, n_bins * 2) && grow(S.recs, rec_bytes) && grow(S.rows, rows_bytes);
+        if (!ok) break;
+        for (int j = 0; j < n_jobs; j++) {
+            E1Buffers b = g.slots[size_t(slot_of[size_t(j)])].b;
+            b.img = g.h_jobs[j].b.img; b.coded = d_bins + bins_at[size_t(j)];
+            e1_job_back(g.h_jobs[j], b, g.h_totals[size_t(slot_of[size_t(j)]) * kTotalsSlot + 2]);
+        }
+        ok = hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, st) == hipSuccess &&
+             (!n_tasks || hipMemcpyAsync(d_tasks, h_tasks, size_t(n_tasks) * sizeof(IndexRecordTask), hipMemcpyHostToDevice, st) == hipSuccess);
+        if (!ok) break;
+        hipEventRecord(ev[3], st);
+        e1_launch_back(g.d_jobs, g.h_jobs, n_jobs, st, nullptr, true);
+        // ---- 6. the decoder records of the jobs whose band ends on an entry row
+        e1_launch_index_records(g.d_jobs, d_tasks, n_tasks, d_recs, st);
+        hipEventRecord(ev[4], st);
+        // ---- 7. one copy of the step's bins, one of its records (and the rows of device inputs, for the row hash)
+        ok = hipMemcpyAsync(static_cast<uint16_t *>(S.bins), d_bins, n_bins * sizeof(uint16_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             (!rec_bytes || hipMemcpyAsync(static_cast<uint16_t *>(S.recs), d_recs, rec_bytes, hipMemcpyDeviceToHost, st) == hipSuccess);
+        uint8_t *const rows_host = reinterpret_cast<uint8_t *>(static_cast<uint16_t *>(S.rows));
+        for (int j = 0; j < n_jobs && ok && q.on_device; j++)
+            if (live[size_t(slot_of[size_t(j)])].im->every)
+                ok = hipMemcpyAsync(rows_host + rows_at[size_t(j)], g.h_jobs[j].b.img, size_t(g.h_jobs[j].n), hipMemcpyDeviceToHost, st) == hipSuccess;
+        hipEventRecord(ev[5], st);
+        if (!ok || hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { ok = false; break; }
+        for (int k = 0; k < 4; k++) {
+            float ms = 0.f;
+            const int a = k < 2 ? k : k + 1;                             // (2 -> 3 is the host's sizing of the back half)
+            if (hipEventElapsedTime(&ms, ev[a], ev[a + 1]) == hipSuccess) sp.ms[k] += ms;
+        }
+        const auto w0 = std::chrono::steady_clock::now();
+        tasks_left.wait();                                               // step t - 1 is coded: an image's bands are coded in order
+        sp.ms[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+        sp.steps++;
+        tasks_left.add(n_jobs);
+        const uint8_t *const recs_host = reinterpret_cast<const uint8_t *>(static_cast<uint16_t *>(S.recs));
+        for (int j = 0; j < n_jobs; j++) {
+            IdxLive &L = live[size_t(slot_of[size_t(j)])];
+            IdxImage *I = L.im;
+            const int rows = g.h_jobs[j].h;
+            const uint8_t *rows_src = !I->every ? nullptr : q.on_device ? rows_host + rows_at[size_t(j)] : I->host_plane + size_t(L.row0) * size_t(I->w);
+            const IdxBand b{I, L.row0, rows, static_cast<uint16_t *>(S.bins) + bins_at[size_t(j)], g.h_jobs[j].n_ev, rows_src,
+                            rec_at[size_t(j)] == SIZE_MAX ? nullptr : recs_host + rec_at[size_t(j)], L.row0 + rows >= I->h};
+            q.pool.post([&q, &tasks_left, b] { idx_code_band(q, b); tasks_left.done(); });
+            L.row0 += rows;
+        }
     }
-    if (n_live) {
-        const int group_size = int(c->groups[0].slots.size());
-        const int n_drivers = std::min(int(c->groups.size()), (n_live + group_size - 1) / group_size);
-        q.pool.start(std::max(1, c->coders_wanted));
-        std::vector<std::thread> drivers;
-        for (int i = 0; i < n_drivers; i++) drivers.emplace_back([&] { idx_driver(q, images); });
-        for (auto &t : drivers) t.join();
-    }
-    {
-        std::lock_guard<std::mutex> l(c->stat_m);
-        for (int k = 0; k < 5; k++) c->idx_split[k] = q.split[k];
-        c->idx_steps = q.steps;
-    }
-    bool all = !q.failed;
-    for (int k = 0; k < n; k++) {
-        if (q.failed && images[size_t(k)]) { lens[k] = -1; if (ilens && images[size_t(k)]->every) ilens[k] = -1; }
-        all = all && lens[k] >= 0 && (!ilens || ilens[k] >= 0);
-    }
-    return all ? 0 : -1;
+    if (!ok) { q.failed = true; fprintf(stderr, "[nblic_amd] indexed batch: a device step failed\n"); }
+    hipStreamSynchronize(st);
+    tasks_left.wait();
 }
 
 // ---- the INDEXED effort-0 BATCH: QNBLIC streams and their seek indexes, a group of images stepped through row bands -------
@@ -3031,15 +3023,9 @@ static int encode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
 constexpr int kQIdxDepth = 8;
 static_assert(kQIdxDepth * 4 <= kE1Marks, "a queued step's four marks are timing events of the group");
 
-struct QIdxImage {
-    int k = 0, h = 0, w = 0, every = 0, count = 0;                       // every: 0 = no index wanted (or none possible); count: its entries
-    const uint8_t *host_plane = nullptr;                                 // host input: the rows are hashed from it
-    uint16_t *out = nullptr; size_t cap = 0;                             // in words
-    uint8_t *index = nullptr; size_t entry_bytes = 0;
-};
 // An image's page-locked buffer, in bytes: words | histograms | entry records | rows [0, count * every) of a device input.
 struct QIdxLayout { size_t hist, recs, rec_stride, rows, bytes; };
-static QIdxLayout qidx_layout(const QIdxImage &I, bool on_device) {
+static QIdxLayout qidx_layout(const IdxImage &I, bool on_device) {
     QIdxLayout L;
     L.hist = up256(2 * size_t(I.h) * size_t(I.w));
     L.recs = L.hist + 12 * 256 * sizeof(uint32_t);
@@ -3048,14 +3034,6 @@ static QIdxLayout qidx_layout(const QIdxImage &I, bool on_device) {
     L.bytes = L.rows + (on_device ? size_t(I.count) * size_t(I.every) * size_t(I.w) : 0);
     return L;
 }
-struct QIdxCall {
-    nblic_amd_ctx *c; int n; const unsigned char *const *imgs; bool on_device; const int *hs, *ws; int band_rows;
-    long *lens, *ilens;
-    std::atomic<int> next{0};
-    std::atomic<bool> failed{false};                                     // a device-side failure: the call is over
-    IdxPool pool;
-    std::mutex m; double split[5] = {0}; long steps = 0;                 // summed over the groups (guarded by m)
-};
 struct QIdxFree {                                                        // a driver's image buffers: taken when an image starts, given back by its worker.  Shared (shared_ptr) by the driver and the tasks it posts: whoever lets go last destroys it
     std::mutex m; std::condition_variable cv; std::vector<int> free; int out = 0;
     int take() { std::unique_lock<std::mutex> l(m); cv.wait(l, [this] { return !free.empty(); }); const int b = free.back(); free.pop_back(); out++; return b; }
@@ -3064,23 +3042,23 @@ struct QIdxFree {                                                        // a dr
 };
 
 // An image's last band has been queued; `ready` is recorded behind its copies.  The entropy stage, then the index.
-static void qidx_finish(QIdxCall &q, const QIdxImage &I, const uint8_t *base, const QIdxLayout &L, hipEvent_t ready) {
-    auto fail = [&] { q.lens[I.k] = -1; if (I.every) q.ilens[I.k] = -1; };
-    if (hipSetDevice(q.c->device) != hipSuccess || hipEventSynchronize(ready) != hipSuccess) { q.failed = true; return fail(); }
+static void qidx_finish(IdxCall &q, const IdxImage &I, const uint8_t *base, const QIdxLayout &L, hipEvent_t ready) {
+    if (hipSetDevice(q.c->device) != hipSuccess || hipEventSynchronize(ready) != hipSuccess) { q.failed = true; return q.fail(I); }
+    uint16_t *const out = static_cast<uint16_t *>(I.out);
     std::vector<int> rows(size_t(I.count));
     std::vector<QEntryState> at(size_t(I.count));
     for (int e = 0; e < I.count; e++) rows[size_t(e)] = (e + 1) * I.every;
-    const long words = q_entropy_encode_entries(I.out, I.cap, I.h, I.w, reinterpret_cast<const uint16_t *>(base),
+    const long words = q_entropy_encode_entries(out, I.cap, I.h, I.w, reinterpret_cast<const uint16_t *>(base),
                                                 reinterpret_cast<const uint32_t *>(base + L.hist), rows.data(), I.count, at.data());
     if (words < 0) {
         fprintf(stderr, "[nblic_amd] image %d: output buffer of %zu words is too small\n", I.k, I.cap);
-        return fail();
+        return q.fail(I);
     }
     q.lens[I.k] = words;
     if (!I.every) return;
     const size_t stream_bytes = size_t(words) * 2;
     std::vector<uint8_t> tab(kQTab);
-    const long q_pos = q_parse_tables(reinterpret_cast<const unsigned char *>(I.out), stream_bytes, tab.data());
+    const long q_pos = q_parse_tables(reinterpret_cast<const unsigned char *>(out), stream_bytes, tab.data());
     if (q_pos < 0) { q.ilens[I.k] = -1; return; }                        // (cannot happen: the tables were written a moment ago)
     const unsigned long long emitted = (unsigned long long)(words - q_pos - 2);       // renormalisation words of the whole pass
     const DecodeItem it{0, I.h, I.w, 0, kMinKStep, 0, 1, stream_bytes, q_pos, -1};
@@ -3088,192 +3066,165 @@ static void qidx_finish(QIdxCall &q, const QIdxImage &I, const uint8_t *base, co
     const uint8_t *plane = I.host_plane ? I.host_plane : base + L.rows;
     Sha256 rows_sha;
     for (int e = 0; e < I.count; e++) {
-        const int r = (e + 1) * I.every;
         rows_sha.update(plane + size_t(e) * size_t(I.every) * size_t(I.w), size_t(I.every) * size_t(I.w));
         uint8_t *ck = I.index + index_entry_at(e, I.entry_bytes), *rec = ck + sizeof(DecodeCheckpoint);
         memcpy(rec, base + L.recs + size_t(e) * L.rec_stride, kQDecodeStateBytes + 2 * size_t(I.w));
         SerialState S{};                                                 // every other field as the band decoder's checkpoint leaves it: zero
-        S.next_row = r; S.status = kRunning; S.lo = at[size_t(e)].state;
+        S.lo = at[size_t(e)].state;
         S.pos = first_pos(it) + 4 + 2 * (emitted - at[size_t(e)].words);  // the two words of the initial state, then one per renormalisation of the pixels above
-        memcpy(rec, &S, sizeof S);
+        index_entry_head(ck, it, I.every, rows[size_t(e)], S, rows_sha);
         memcpy(rec + R.tab, tab.data(), kQTab);
-        const DecodeCheckpoint H = decode_head(it, I.every, r, S.pos & ~511ull, canonical_sha(rows_sha));
-        memcpy(ck, &H, sizeof H);
         seal(ck, I.entry_bytes);
     }
     IndexHead H = index_head(it, I.every, I.count, stream_bytes);
-    sha256_of(I.out, stream_bytes, H.stream_sha);
+    sha256_of(out, stream_bytes, H.stream_sha);
     index_close(I.index, &H, I.count, I.entry_bytes);
     q.ilens[I.k] = long(index_total_bytes(I.count, I.entry_bytes));
 }
 
-// One driver: holds one group for the whole call and steps its slots through the batch's images.
-static void qidx_driver(QIdxCall &q, std::vector<std::unique_ptr<QIdxImage>> &images) {
+// The step loop of effort 0: queues kQIdxDepth steps ahead and stops only for a free image buffer.
+static void qidx_driver(IdxCall &q, Group &g, IdxSplit &sp) {
     nblic_amd_ctx *c = q.c;
-    if (hipSetDevice(c->device) != hipSuccess) { q.failed = true; return; }
-    const int gid = take_group(c);
-    {
-        Group &g = c->groups[size_t(gid)];
-        const hipStream_t st = g.stream;
-        const int n_slots = int(g.slots.size()), n_bufs = 2 * n_slots;
-        struct Live { QIdxImage *im = nullptr; int row0 = 0, band = 0, buf = -1; const uint8_t *plane = nullptr; QIdxLayout lay{}; };
-        std::vector<Live> live{size_t(n_slots)};
-        const auto bufs = std::make_shared<QIdxFree>();
-        std::vector<int> slot_of(size_t(n_slots), 0), ring_jobs(size_t(kQIdxDepth), 0), ring_slot(size_t(kQIdxDepth) * size_t(n_slots), 0);
-        std::vector<size_t> rec_at(size_t(n_slots), 0);
-        const size_t rec_room = up256(kQDecodeStateBytes + 2 * size_t(NBLIC_MAX_WIDTH));
-        double split[5] = {0}; long steps = 0;
-        bool ok = true;
-        if (g.qidx_bufs.empty()) {                                       // the group's first call of this kind
-            g.qidx_bufs.resize(size_t(n_bufs));
-            g.qidx_ready.resize(size_t(n_bufs));
-            for (auto &e : g.qidx_ready) ok = ok && e.create(hipEventDisableTiming | hipEventBlockingSync) == hipSuccess;
-            ok = ok && g.qidx_jobs.alloc(size_t(kQIdxDepth) * size_t(n_slots)) == hipSuccess && g.qidx_tasks.alloc(size_t(kQIdxDepth) * size_t(n_slots)) == hipSuccess &&
-                 g.qidx_totals.alloc(size_t(kQIdxDepth) * size_t(n_slots) * kTotalsSlot) == hipSuccess && g.qidx_d_tasks.alloc(size_t(n_slots)) == hipSuccess &&
-                 g.qidx_d_recs.alloc(size_t(n_slots) * rec_room) == hipSuccess;
-            if (!ok) { g.qidx_bufs.clear(); g.qidx_ready.clear(); }
-        }
-        for (int b = 0; ok && b < n_bufs; b++) bufs->free.push_back(b);
-        hipEvent_t *ev = g.tm.ev;                                        // four marks a queued step
-        // Step t - kQIdxDepth has left the GPU: its ring entry is free, its marks and its block counts are read.
-        auto retire = [&](int e) {
-            if (ring_jobs[size_t(e)] == 0) return true;
-            if (hipEventSynchronize(ev[4 * e + 3]) != hipSuccess) return false;
-            for (int k = 0; k < 3; k++) {
-                float ms = 0.f;
-                if (hipEventElapsedTime(&ms, ev[4 * e + k], ev[4 * e + k + 1]) == hipSuccess) split[k == 0 ? 0 : k + 1] += ms;
-            }
-            for (int j = 0; j < ring_jobs[size_t(e)]; j++)
-                count_long_chains(c, g.qidx_totals + (size_t(e) * size_t(n_slots) + size_t(ring_slot[size_t(e) * size_t(n_slots) + size_t(j)])) * kTotalsSlot);
-            ring_jobs[size_t(e)] = 0;
-            return true;
-        };
-        for (long t = 0; ok && !q.failed; t++) {
-            const int e = int(t % kQIdxDepth);
-            if (!(ok = retire(e))) break;
-            // ---- which image each slot works on
-            for (int k = 0; k < n_slots && ok; k++) {
-                Live &L = live[size_t(k)];
-                if (L.im && L.row0 >= L.im->h) L.im = nullptr;           // (its worker has the buffer)
-                while (!L.im) {
-                    const int j = q.next.fetch_add(1);
-                    if (j >= q.n) break;
-                    QIdxImage *I = images[size_t(j)].get();
-                    if (!I) continue;                                    // refused before the call started
-                    Slot &s = g.slots[size_t(k)];
-                    const auto w0 = std::chrono::steady_clock::now();
-                    L.buf = bufs->take();                                 // every buffer out: the workers are behind
-                    split[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-                    L.im = I; L.row0 = 0;
-                    L.lay = qidx_layout(*I, q.on_device && I->every);
-                    Locked &B = g.qidx_bufs[size_t(L.buf)];
-                    L.band = q.band_rows > 0 ? std::min(q.band_rows, I->h) : serial_rows_per_launch(I->h, I->w, 1, 0);      // stream_open's rule
-                    const size_t n = size_t(I->h) * size_t(I->w), band_px = size_t(L.band) * size_t(I->w);
-                    // a workspace that has to grow is still read by the steps in the queue
-                    if ((band_px > s.px_cap || (!q.on_device && n > s.d_img.capacity())) && hipStreamSynchronize(st) != hipSuccess) { ok = false; break; }
-                    if (!(ok = (L.lay.bytes <= B.capacity() * 2 || B.alloc((L.lay.bytes + L.lay.bytes / 8 + 4096) / 2)) && ensure_pixels(s, band_px, false))) break;
-                    if (q.on_device) L.plane = q.imgs[j];
-                    else {
-                        if (!(ok = s.d_img.reserve(n) == hipSuccess && hipMemcpyAsync(s.d_img, q.imgs[j], n, hipMemcpyHostToDevice, st) == hipSuccess)) break;
-                        L.plane = s.d_img;
-                    }
-                }
-            }
-            if (!ok) break;
-            // ---- 1. job records of the live slots, and the tasks of the bands that end on an entry row
-            E1Job *const hj = g.qidx_jobs + size_t(e) * size_t(n_slots);
-            IndexRecordTask *const ht = g.qidx_tasks + size_t(e) * size_t(n_slots);
-            int n_jobs = 0, n_tasks = 0;
-            for (int k = 0; k < n_slots; k++) {
-                Live &L = live[size_t(k)];
-                if (!L.im) continue;
-                const QIdxImage &I = *L.im;
-                int rows = std::min(L.band, I.h - L.row0);
-                if (I.every) rows = std::min(rows, I.every - L.row0 % I.every);           // a band never crosses an entry row
-                E1Buffers b = g.slots[size_t(k)].b;
-                b.img = L.plane + size_t(L.row0) * size_t(I.w);
-                hj[n_jobs] = e1_job_front(b, rows, I.w, 0, 0, long_chains_of(c));
-                hj[n_jobs].row0 = L.row0;
-                const int r = L.row0 + rows;
-                rec_at[size_t(n_jobs)] = SIZE_MAX;
-                if (I.every && r % I.every == 0 && r < I.h) {
-                    rec_at[size_t(n_jobs)] = size_t(n_tasks) * rec_room;
-                    ht[n_tasks++] = IndexRecordTask{n_jobs, 0, (unsigned long long)(rec_at[size_t(n_jobs)])};
-                }
-                ring_slot[size_t(e) * size_t(n_slots) + size_t(n_jobs)] = k;
-                slot_of[size_t(n_jobs++)] = k;
-            }
-            if (n_jobs == 0) break;
-            ok = hipMemcpyAsync(g.d_jobs, hj, size_t(n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, st) == hipSuccess &&
-                 (!n_tasks || hipMemcpyAsync(g.qidx_d_tasks, ht, size_t(n_tasks) * sizeof(IndexRecordTask), hipMemcpyHostToDevice, st) == hipSuccess);
-            if (!ok) break;
-            hipEventRecord(ev[4 * e], st);
-            // ---- 2. the model stage of every band, 3. the decoder records
-            q_launch_model_band(g.d_jobs, hj, n_jobs, st);
-            hipEventRecord(ev[4 * e + 1], st);
-            q_launch_index_records(g.d_jobs, g.qidx_d_tasks, n_tasks, g.qidx_d_recs, st);
-            hipEventRecord(ev[4 * e + 2], st);
-            // ---- 4. the band's words and its record into the image's buffer; behind an image's last band its histograms
-            //         (and a device input's rows), and the image goes to a worker
-            ok = hipMemcpyAsync(g.qidx_totals + size_t(e) * size_t(n_slots) * kTotalsSlot, g.d_totals, size_t(n_slots) * kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
-            for (int j = 0; j < n_jobs && ok; j++) {
-                const int k = slot_of[size_t(j)];
-                Live &L = live[size_t(k)];
-                QIdxImage *I = L.im;
-                const Slot &s = g.slots[size_t(k)];
-                uint8_t *const base = reinterpret_cast<uint8_t *>(static_cast<uint16_t *>(g.qidx_bufs[size_t(L.buf)]));
-                const int rows = hj[j].h, r = L.row0 + rows;
-                ok = hipMemcpyAsync(base + 2 * size_t(L.row0) * size_t(I->w), s.b.pxs, size_t(hj[j].n) * sizeof(uint16_t), hipMemcpyDeviceToHost, st) == hipSuccess;
-                if (ok && rec_at[size_t(j)] != SIZE_MAX)
-                    ok = hipMemcpyAsync(base + L.lay.recs + size_t(r / I->every - 1) * L.lay.rec_stride, g.qidx_d_recs + rec_at[size_t(j)],
-                                        kQDecodeStateBytes + 2 * size_t(I->w), hipMemcpyDeviceToHost, st) == hipSuccess;
-                L.row0 = r;
-                if (!ok || r < I->h) continue;
-                const hipEvent_t ready = g.qidx_ready[size_t(L.buf)];
-                ok = hipMemcpyAsync(base + L.lay.hist, s.b.qhist, 12 * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                     (L.lay.bytes == L.lay.rows || hipMemcpyAsync(base + L.lay.rows, L.plane, L.lay.bytes - L.lay.rows, hipMemcpyDeviceToHost, st) == hipSuccess) &&
-                     hipEventRecord(ready, st) == hipSuccess;
-                if (!ok) { L.row0 = 0; continue; }                       // (not handed over: the driver gives the buffer back below)
-                const QIdxLayout lay = L.lay; const int buf = L.buf;
-                q.pool.post([&q, bufs, I, base, lay, ready, buf] { qidx_finish(q, *I, base, lay, ready); bufs->give(buf); });
-            }
-            hipEventRecord(ev[4 * e + 3], st);
-            ring_jobs[size_t(e)] = n_jobs;
-            steps++;
-        }
-        if (!ok) { q.failed = true; fprintf(stderr, "[nblic_amd] indexed effort-0 batch: a device step failed\n"); }
-        const bool drained = hipStreamSynchronize(st) == hipSuccess;
-        for (int e = 0; e < kQIdxDepth && ok && drained; e++) retire(e);
-        for (auto &L : live) if (L.im && L.row0 < L.im->h && L.buf >= 0) bufs->give(L.buf);    // images the call ended under
-        bufs->wait_all();
-        std::lock_guard<std::mutex> l(q.m);
-        for (int k = 0; k < 5; k++) q.split[k] += split[k];
-        q.steps += steps;
+    const hipStream_t st = g.stream;
+    const int n_slots = int(g.slots.size()), n_bufs = 2 * n_slots;
+    struct Live : IdxLive { int buf = -1; QIdxLayout lay{}; };
+    std::vector<Live> live{size_t(n_slots)};
+    const auto bufs = std::make_shared<QIdxFree>();
+    std::vector<int> slot_of(size_t(n_slots), 0), ring_jobs(size_t(kQIdxDepth), 0), ring_slot(size_t(kQIdxDepth) * size_t(n_slots), 0);
+    std::vector<size_t> rec_at(size_t(n_slots), 0);
+    const size_t rec_room = up256(kQDecodeStateBytes + 2 * size_t(NBLIC_MAX_WIDTH));
+    bool ok = true;
+    if (g.qidx_bufs.empty()) {                                           // the group's first call of this kind
+        g.qidx_bufs.resize(size_t(n_bufs));
+        g.qidx_ready.resize(size_t(n_bufs));
+        for (auto &e : g.qidx_ready) ok = ok && e.create(hipEventDisableTiming | hipEventBlockingSync) == hipSuccess;
+        ok = ok && g.qidx_jobs.alloc(size_t(kQIdxDepth) * size_t(n_slots)) == hipSuccess && g.qidx_tasks.alloc(size_t(kQIdxDepth) * size_t(n_slots)) == hipSuccess &&
+             g.qidx_totals.alloc(size_t(kQIdxDepth) * size_t(n_slots) * kTotalsSlot) == hipSuccess && g.qidx_d_tasks.alloc(size_t(n_slots)) == hipSuccess &&
+             g.qidx_d_recs.alloc(size_t(n_slots) * rec_room) == hipSuccess;
+        if (!ok) { g.qidx_bufs.clear(); g.qidx_ready.clear(); }
     }
-    release_group(c, gid);
+    for (int b = 0; ok && b < n_bufs; b++) bufs->free.push_back(b);
+    hipEvent_t *ev = g.tm.ev;                                            // four marks a queued step
+    // Step t - kQIdxDepth has left the GPU: its ring entry is free, its marks and its block counts are read.
+    auto retire = [&](int e) {
+        if (ring_jobs[size_t(e)] == 0) return true;
+        if (hipEventSynchronize(ev[4 * e + 3]) != hipSuccess) return false;
+        for (int k = 0; k < 3; k++) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, ev[4 * e + k], ev[4 * e + k + 1]) == hipSuccess) sp.ms[k == 0 ? 0 : k + 1] += ms;
+        }
+        for (int j = 0; j < ring_jobs[size_t(e)]; j++)
+            count_long_chains(c, g.qidx_totals + (size_t(e) * size_t(n_slots) + size_t(ring_slot[size_t(e) * size_t(n_slots) + size_t(j)])) * kTotalsSlot);
+        ring_jobs[size_t(e)] = 0;
+        return true;
+    };
+    for (long t = 0; ok && !q.failed; t++) {
+        const int e = int(t % kQIdxDepth);
+        if (!(ok = retire(e))) break;
+        // ---- which image each slot works on
+        for (int k = 0; k < n_slots; k++) {
+            Live &L = live[size_t(k)];
+            if (L.im && L.row0 >= L.im->h) L.im = nullptr;               // (its worker has the buffer)
+            IdxImage *I = L.im ? nullptr : q.next_image();
+            if (!I) continue;
+            Slot &s = g.slots[size_t(k)];
+            const auto w0 = std::chrono::steady_clock::now();
+            L.buf = bufs->take();                                         // every buffer out: the workers are behind
+            sp.ms[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+            L.im = I; L.row0 = 0;
+            L.lay = qidx_layout(*I, q.on_device && I->every);
+            Locked &B = g.qidx_bufs[size_t(L.buf)];
+            L.band = encoder_band_rows(q.band_rows, I->h, I->w, 1);
+            const size_t n = size_t(I->h) * size_t(I->w), band_px = size_t(L.band) * size_t(I->w);
+            // a workspace that has to grow is still read by the steps in the queue
+            if ((band_px > s.px_cap || (!q.on_device && n > s.d_img.capacity())) && hipStreamSynchronize(st) != hipSuccess) { ok = false; break; }
+            if (!(ok = (L.lay.bytes <= B.capacity() * 2 || B.alloc((L.lay.bytes + L.lay.bytes / 8 + 4096) / 2)) && ensure_pixels(s, band_px, false) &&
+                       (L.plane = idx_plane(q, *I, s, st)) != nullptr)) break;
+        }
+        if (!ok) break;
+        // ---- 1. job records of the live slots, and the tasks of the bands that end on an entry row
+        E1Job *const hj = g.qidx_jobs + size_t(e) * size_t(n_slots);
+        IndexRecordTask *const ht = g.qidx_tasks + size_t(e) * size_t(n_slots);
+        int n_jobs = 0, n_tasks = 0;
+        for (int k = 0; k < n_slots; k++) {
+            const Live &L = live[size_t(k)];
+            if (!L.im) continue;
+            const size_t at = size_t(n_tasks) * rec_room;
+            rec_at[size_t(n_jobs)] = idx_band_job(c, L, g.slots[size_t(k)], hj, n_jobs, ht, n_tasks, at) ? at : SIZE_MAX;
+            ring_slot[size_t(e) * size_t(n_slots) + size_t(n_jobs)] = k;
+            slot_of[size_t(n_jobs++)] = k;
+        }
+        if (n_jobs == 0) break;
+        ok = hipMemcpyAsync(g.d_jobs, hj, size_t(n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, st) == hipSuccess &&
+             (!n_tasks || hipMemcpyAsync(g.qidx_d_tasks, ht, size_t(n_tasks) * sizeof(IndexRecordTask), hipMemcpyHostToDevice, st) == hipSuccess);
+        if (!ok) break;
+        hipEventRecord(ev[4 * e], st);
+        // ---- 2. the model stage of every band, 3. the decoder records
+        q_launch_model_band(g.d_jobs, hj, n_jobs, st);
+        hipEventRecord(ev[4 * e + 1], st);
+        q_launch_index_records(g.d_jobs, g.qidx_d_tasks, n_tasks, g.qidx_d_recs, st);
+        hipEventRecord(ev[4 * e + 2], st);
+        // ---- 4. the band's words and its record into the image's buffer; behind an image's last band its histograms
+        //         (and a device input's rows), and the image goes to a worker
+        ok = hipMemcpyAsync(g.qidx_totals + size_t(e) * size_t(n_slots) * kTotalsSlot, g.d_totals, size_t(n_slots) * kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+        for (int j = 0; j < n_jobs && ok; j++) {
+            const int k = slot_of[size_t(j)];
+            Live &L = live[size_t(k)];
+            IdxImage *I = L.im;
+            const Slot &s = g.slots[size_t(k)];
+            uint8_t *const base = reinterpret_cast<uint8_t *>(static_cast<uint16_t *>(g.qidx_bufs[size_t(L.buf)]));
+            const int rows = hj[j].h, r = L.row0 + rows;
+            ok = hipMemcpyAsync(base + 2 * size_t(L.row0) * size_t(I->w), s.b.pxs, size_t(hj[j].n) * sizeof(uint16_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+            if (ok && rec_at[size_t(j)] != SIZE_MAX)
+                ok = hipMemcpyAsync(base + L.lay.recs + size_t(r / I->every - 1) * L.lay.rec_stride, g.qidx_d_recs + rec_at[size_t(j)],
+                                    kQDecodeStateBytes + 2 * size_t(I->w), hipMemcpyDeviceToHost, st) == hipSuccess;
+            L.row0 = r;
+            if (!ok || r < I->h) continue;
+            const hipEvent_t ready = g.qidx_ready[size_t(L.buf)];
+            ok = hipMemcpyAsync(base + L.lay.hist, s.b.qhist, 12 * 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                 (L.lay.bytes == L.lay.rows || hipMemcpyAsync(base + L.lay.rows, L.plane, L.lay.bytes - L.lay.rows, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+                 hipEventRecord(ready, st) == hipSuccess;
+            if (!ok) { L.row0 = 0; continue; }                           // (not handed over: the driver gives the buffer back below)
+            const QIdxLayout lay = L.lay; const int buf = L.buf;
+            q.pool.post([&q, bufs, I, base, lay, ready, buf] { qidx_finish(q, *I, base, lay, ready); bufs->give(buf); });
+        }
+        hipEventRecord(ev[4 * e + 3], st);
+        ring_jobs[size_t(e)] = n_jobs;
+        sp.steps++;
+    }
+    if (!ok) { q.failed = true; fprintf(stderr, "[nblic_amd] indexed effort-0 batch: a device step failed\n"); }
+    const bool drained = hipStreamSynchronize(st) == hipSuccess;
+    for (int e = 0; e < kQIdxDepth && ok && drained; e++) retire(e);
+    for (auto &L : live) if (L.im && L.row0 < L.im->h && L.buf >= 0) bufs->give(L.buf);    // images the call ended under
+    bufs->wait_all();
 }
 
-static int qencode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *const *imgs, bool on_device, const int *hs, const int *ws, const int *every,
-                                 int band_rows, uint16_t *const *outs, const size_t *caps, long *lens, unsigned char *const *indexes, const size_t *icaps, long *ilens) {
+// ---- the frame itself ------------------------------------------------------------------------------------------------------
+static const IdxCodec kIdxNblic{0, 1, size_t(kHeaderBytes) + 4, size_t(1) << 46, idx_driver};      // lossless -e1: `outs` in bytes
+static const IdxCodec kIdxQnblic{1, 0, 6, size_t(1) << 45, qidx_driver};                           // effort 0: `outs` in 16-bit words
+
+template <class Out>                                                     // unsigned char or uint16_t: what the codec's lengths count
+static int indexed_batch(const IdxCodec &F, nblic_amd_ctx *c, int n, const unsigned char *const *imgs, bool on_device, const int *hs, const int *ws, const int *every,
+                         int band_rows, Out *const *outs, const size_t *caps, long *lens, unsigned char *const *indexes, const size_t *icaps, long *ilens) {
     if (!c || c->broken || n < 1 || !imgs || !hs || !ws || !every || !outs || !caps || !lens || (indexes && (!icaps || !ilens))) return -1;
     for (int k = 0; k < n; k++) if (every[k] < 0 || !imgs[k] || !outs[k]) return -1;
     if (hipSetDevice(c->device) != hipSuccess) return -1;
-    QIdxCall q{c, n, imgs, on_device, hs, ws, band_rows, lens, ilens};
-    std::vector<std::unique_ptr<QIdxImage>> images{size_t(n)};
+    IdxCall q{F, c, n, imgs, on_device, band_rows, lens, ilens};
+    q.images.resize(size_t(n));
     int n_live = 0;
     for (int k = 0; k < n; k++) {                                        // what can be refused is refused before anything is launched
         lens[k] = -1;
         if (ilens) ilens[k] = 0;
-        if (!size_ok(hs[k], ws[k], c->max_px) || caps[k] < 6) continue;
-        auto I = std::make_unique<QIdxImage>();
-        I->k = k; I->h = hs[k]; I->w = ws[k]; I->out = outs[k]; I->cap = std::min(caps[k], size_t(1) << 45);
+        if (!size_ok(hs[k], ws[k], c->max_px) || caps[k] < F.min_out) continue;
+        auto I = std::make_unique<IdxImage>();
+        I->k = k; I->h = hs[k]; I->w = ws[k]; I->out = outs[k]; I->cap = std::min(caps[k], F.max_out);
         I->host_plane = on_device ? nullptr : imgs[k];
-        if (indexes && indexes[k] && every[k] >= 1 && every[k] < hs[k]) {
-            const long need = index_bytes(1, hs[k], ws[k], 0, every[k]);
-            if (need < 0 || icaps[k] < size_t(need)) ilens[k] = -1;                       // the stream is still delivered
-            else { I->every = every[k]; I->index = indexes[k]; I->entry_bytes = index_entry_bytes(1, ws[k], 0); I->count = (hs[k] - 1) / every[k]; }
+        if (indexes && indexes[k]) {
+            const IndexAdmission A = index_admit(F.kind, F.effort, hs[k], ws[k], every[k], icaps[k]);
+            if (A.too_small) ilens[k] = -1;                              // the stream is still delivered
+            else { I->every = A.every; I->count = A.count; I->entry_bytes = A.entry_bytes; I->index = indexes[k]; }
         }
-        images[size_t(k)] = std::move(I);
+        q.images[size_t(k)] = std::move(I);
         n_live++;
     }
     if (n_live) {
@@ -3281,17 +3232,17 @@ static int qencode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *c
         const int n_drivers = std::min(int(c->groups.size()), (n_live + group_size - 1) / group_size);
         q.pool.start(std::max(1, c->coders_wanted));
         std::vector<std::thread> drivers;
-        for (int i = 0; i < n_drivers; i++) drivers.emplace_back([&] { qidx_driver(q, images); });
+        for (int i = 0; i < n_drivers; i++) drivers.emplace_back([&q] { idx_run_driver(q); });
         for (auto &t : drivers) t.join();
     }
     {
         std::lock_guard<std::mutex> l(c->stat_m);
-        for (int k = 0; k < 5; k++) c->idx_split[k] = q.split[k];
-        c->idx_steps = q.steps;
+        for (int k = 0; k < 5; k++) c->idx_split[k] = q.split.ms[k];
+        c->idx_steps = q.split.steps;
     }
     bool all = !q.failed;
     for (int k = 0; k < n; k++) {
-        if (q.failed && images[size_t(k)]) { lens[k] = -1; if (ilens && images[size_t(k)]->every) ilens[k] = -1; }
+        if (q.failed && q.images[size_t(k)]) q.fail(*q.images[size_t(k)]);
         all = all && lens[k] >= 0 && (!ilens || ilens[k] >= 0);
     }
     return all ? 0 : -1;
@@ -3904,11 +3855,10 @@ static int index_build_batch(nblic_amd_ctx *c, int n, const unsigned char *const
                     SerialState S;
                     memcpy(&S, body, sizeof S);
                     if (S.next_row != row || S.status != kRunning) return;           // (an entry that was not captured: the plan and the device disagree)
-                    uint8_t *ck = out + index_entry_at(e - 1, I.entry_bytes);
-                    const DecodeCheckpoint C = decode_head(it, I.every, row, S.pos & ~511ull, canonical_sha(rows_sha));
-                    memcpy(ck, &C, sizeof C);
-                    memcpy(ck + sizeof C, body, I.L.tab);
-                    if (it.kind) memcpy(ck + sizeof C + I.L.tab, I.qtab.data(), kQTab);
+                    uint8_t *ck = out + index_entry_at(e - 1, I.entry_bytes), *rec = ck + sizeof(DecodeCheckpoint);
+                    memcpy(rec, body, I.L.tab);
+                    index_entry_head(ck, it, I.every, row, S, rows_sha);
+                    if (it.kind) memcpy(rec + I.L.tab, I.qtab.data(), kQTab);
                     seal(ck, I.entry_bytes);
                 }
                 index_close(out, &H, I.count, I.entry_bytes);
@@ -3929,6 +3879,7 @@ static int index_build_batch(nblic_amd_ctx *c, int n, const unsigned char *const
     return every ? 0 : -1;
 }
 
+// ---- default context behind the drop-in entry points ---------------------------------------
 static nblic_amd_ctx *g_default = nullptr;
 static std::mutex g_default_m;
 
@@ -5039,13 +4990,13 @@ int nblic_amd_encode_batch_indexed(nblic_amd_ctx *c, int n_images, const unsigne
                                    const int *heights, const int *widths, const int *every_rows, int band_rows,
                                    unsigned char *const *outs, const size_t *out_caps, long *out_lens,
                                    unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
-    return encode_batch_indexed(c, n_images, imgs, imgs_on_device != 0, heights, widths, every_rows, band_rows, outs, out_caps, out_lens, indexes, index_caps, index_lens);
+    return indexed_batch(kIdxNblic, c, n_images, imgs, imgs_on_device != 0, heights, widths, every_rows, band_rows, outs, out_caps, out_lens, indexes, index_caps, index_lens);
 }
 int nblic_amd_qencode_batch_indexed(nblic_amd_ctx *c, int n_images, const unsigned char *const *imgs, int imgs_on_device,
                                     const int *heights, const int *widths, const int *every_rows, int band_rows,
                                     uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words,
                                     unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
-    return qencode_batch_indexed(c, n_images, imgs, imgs_on_device != 0, heights, widths, every_rows, band_rows, outs, out_caps_words, out_len_words, indexes, index_caps, index_lens);
+    return indexed_batch(kIdxQnblic, c, n_images, imgs, imgs_on_device != 0, heights, widths, every_rows, band_rows, outs, out_caps_words, out_len_words, indexes, index_caps, index_lens);
 }
 long nblic_amd_debug_q_entropy(int height, int width, const uint16_t *words, const unsigned int *hist, const int *entry_rows, int n_entries,
                                uint16_t *out, size_t cap_words, unsigned int *states, unsigned long long *words_emitted) {

@@ -1,6 +1,7 @@
 // Stand-alone check of index_entries.h (host only): the size of an index, entries that wait for their window while the
-// stream is emitted in pieces of every size, the assembly of the index around them, and the job list of an indexed batch
-// decode.  Build with the sanitizers and run:
+// stream is emitted in pieces of every size, the assembly of the index around them, the job list of an indexed batch
+// decode, the rule that cuts an encoder's bands at the entry rows, and which image of a batch gets an index.  Build with the
+// sanitizers and run (tests/test_index_entries_host.py does):
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o index_entries_check tools/index_entries_check.cpp && ./index_entries_check
 #include <cstdio>
 #include <cstdlib>
@@ -105,7 +106,54 @@ static int plan_runs(unsigned seed) {
     return 0;
 }
 
+// The band rule, exhaustively: the cuts of an h-row image in bands of at most `band` rows with an entry every `every` rows
+// tile [0, h) in order, no cut has a multiple of `every` strictly inside it, and the cuts flagged "an entry behind this
+// band" are exactly those that end at R, 2R, ..., ((h - 1) / R) R.
+static int band_rule(int h, int band, int every) {
+    std::vector<int> flagged;
+    int row0 = 0, cuts = 0;
+    while (row0 < h) {
+        const BandCut c = index_band_cut(row0, band, h, every);
+        CHECK(c.rows >= 1 && c.rows <= band && row0 + c.rows <= h && ++cuts <= h);
+        if (every >= 1)
+            for (int r = row0 + 1; r < row0 + c.rows; r++) CHECK(r % every != 0);
+        if (c.entry) flagged.push_back(row0 + c.rows);
+        row0 += c.rows;
+    }
+    CHECK(row0 == h);
+    const int count = every >= 1 ? (h - 1) / every : 0;
+    CHECK(int(flagged.size()) == count);
+    for (int e = 0; e < count; e++) CHECK(flagged[size_t(e)] == (e + 1) * every);
+    return 0;
+}
+
+// The admission rule against index_bytes: no index when R < 1 or R >= h, otherwise (h - 1) / R entries of
+// index_entry_bytes each when the buffer holds index_bytes, and "too small" below that or for a codec without an index.
+static int admission(int kind, int effort, int h, int w, int every) {
+    const long need = index_bytes(kind, h, w, effort, every);
+    const bool possible = every >= 1 && every < h;
+    const IndexAdmission none = index_admit(kind, effort, h, w, every, 0);
+    CHECK(none.every == 0 && none.count == 0 && none.entry_bytes == 0 && none.too_small == possible);
+    if (!possible) { CHECK(need < 0 && !index_admit(kind, effort, h, w, every, ~size_t(0)).too_small); return 0; }
+    const IndexAdmission all = index_admit(kind, effort, h, w, every, ~size_t(0));
+    if (need < 0) { CHECK(all.every == 0 && all.too_small); return 0; }
+    CHECK(index_admit(kind, effort, h, w, every, size_t(need) - 1).too_small);
+    for (const IndexAdmission &a : {all, index_admit(kind, effort, h, w, every, size_t(need))}) {
+        CHECK(!a.too_small && a.every == every && a.count == (h - 1) / every && a.entry_bytes == index_entry_bytes(kind, w, effort));
+        CHECK(long(index_total_bytes(a.count, a.entry_bytes)) == need);
+    }
+    return 0;
+}
+
 int main() {
+    for (int h = 1; h <= 40; h++)
+        for (int band = 1; band <= h; band++)
+            for (int every = 0; every <= h + 1; every++)
+                if (band_rule(h, band, every)) return 1;
+    for (int h : {1, 2, 3, 7, 40, 65535})
+        for (int every : {-1, 0, 1, 2, 3, 6, 7, 39, 40, 41, 65534, 65535})
+            for (int mode : {1, 2, 3, 4, 16, 17})                        // kind * 16 + effort: NBLIC -e1 .. -e3, -e4 (none), QNBLIC, QNBLIC effort 1 (none)
+                if (admission(mode / 16, mode % 16, h, 37, every)) return 1;
     // sizes: head 96 | count x (8 | 168 + body + 32) | 32
     CHECK(index_bytes(0, 40, 37, 1, 5) == long(96 + 32 + 7 * (8 + 200 + 86080 + 74)));
     CHECK(index_bytes(0, 40, 37, 1, 39) == long(96 + 32 + 1 * (8 + 200 + 86080 + 74)));
@@ -122,6 +170,7 @@ int main() {
         for (size_t piece : {1u, 2u, 3u, 5u, 64u, 5000u})
             for (size_t gap : {1u, 2u, 4u, 7u, 100u}) {
                 if (gap + 4 > len) continue;
+                if ((len - 4) / gap > 64) continue;                      // hundreds of 86 KB entries a few bytes apart: len 64's cases again, minutes under the sanitizers
                 if (run(len, piece, gap, 1 + int(seed % 40), seed)) return 1;
                 seed++;
             }
