@@ -210,6 +210,7 @@ int nblic_amd_lsq_redo_counts(nblic_amd_ctx *ctx, unsigned long long counts[2], 
  * model stage of an encode; decode != 0: the NBLIC decoder (whole_streams: every stream is there in full, as in
  * nblic_amd_decode_batch).  Bits: 1 = two waves per image (effort-3 encodes of few images), 2 = the lean decoder image
  * (many streams side by side), 4 = the rows of the widest image are kept in LDS (otherwise its taps come from memory).
+ * decode != 0 with effort 0: the QNBLIC decoder, which has one LDS image for any number of streams -- bit 4 alone.
  * Returns -1 for arguments out of range.                                                                             */
 int nblic_amd_serial_plan(int decode, int effort, int images, int width, int whole_streams);
 

@@ -669,7 +669,8 @@ PLAN_TWO_WAVES, PLAN_LEAN, PLAN_ROWS_IN_LDS = 1, 2, 4
 
 
 def serial_plan(decode: bool, effort: int, images: int, width: int, whole_streams: bool = True) -> int:
-    """The serial kernel variant a launch gets (``nblic_amd_serial_plan``): PLAN_* bits.  Needs no device."""
+    """The serial kernel variant a launch gets (``nblic_amd_serial_plan``): PLAN_* bits; ``effort`` 0 is the QNBLIC decoder
+    (``decode`` only).  Needs no device."""
     r = load_library().nblic_amd_serial_plan(int(decode), effort, images, width, int(whole_streams))
     if r < 0:
         raise ValueError("serial_plan: arguments out of range")

@@ -5113,7 +5113,8 @@ int nblic_amd_serial_selftest(nblic_amd_ctx *c) {
 }
 
 int nblic_amd_serial_plan(int decode, int effort, int images, int width, int whole_streams) {
-    if (images < 1 || width < 1 || effort < 1 || effort > 3) return -1;
+    if (images < 1 || width < 1 || effort < 0 || effort > 3 || (effort == 0 && !decode)) return -1;
+    if (effort == 0) return serial_qdecode_plan(width);
     return decode ? serial_decode_plan(images, width, whole_streams != 0) : serial_model_plan(effort, images, width);
 }
 

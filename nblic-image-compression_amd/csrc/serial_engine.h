@@ -106,6 +106,7 @@ bool serial_model_rows_fit(int w);
 enum : int { kPlanTwoWaves = 1, kPlanLean = 2, kPlanRowsInLds = 4 };
 int serial_model_plan(int effort, int n, int max_w);
 int serial_decode_plan(int n, int max_w, bool whole_streams);
+int serial_qdecode_plan(int max_w);                                  // the QNBLIC decoder: one LDS image, kPlanRowsInLds or 0
 
 // d_jobs[0..n): all of one effort (1, 2 or 3); h_jobs: host copy, read to size the launch.  ONE launch: every job
 // advances by its `rows`; call serial_launches(h, rows) times (maximum over the jobs) to finish them.

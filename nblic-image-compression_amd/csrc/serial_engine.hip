@@ -1356,7 +1356,10 @@ __global__ void __launch_bounds__(64) k_serial_qdecode(const SerialJob *__restri
     if (i0 >= end) return;
     const bool final_ = st->final_ != 0;
     const size_t avail = size_t(st->avail) & ~size_t(1), row_need = size_t(2) * size_t(w) + 8;
-    if (!final_ && (avail < size_t(st->pos) || avail - size_t(st->pos) < row_need)) { if (lane == 0) st->status = kStarved; return; }
+    // a fresh image reads the four bytes of the rANS state before row 0: they count here, or the row loop would starve in
+    // front of row 0 with the state consumed, and the next launch (next_row still 0) would read it again four bytes on
+    const size_t launch_need = row_need + (i0 == 0 ? 4 : 0);
+    if (!final_ && (avail < size_t(st->pos) || avail - size_t(st->pos) < launch_need)) { if (lane == 0) st->status = kStarved; return; }
     for (int k = lane; k < 3072; k += 64) {
         const uint32_t s0 = gp(J.q_start)[k], f = gp(J.q_freq)[k];
         S.ctx[k] = i0 ? st_ctx[k] : 0;
@@ -1564,6 +1567,7 @@ int serial_decode_plan(int n, int max_w, bool whole_streams) {
     const bool fit = 3 * ((max_w + kRowPad + 15) & ~15) + 4 <= lds_room(lean ? sizeof(DecodeLdsLean) : sizeof(DecodeLds));
     return (lean ? kPlanLean : 0) | (fit ? kPlanRowsInLds : 0);
 }
+int serial_qdecode_plan(int max_w) { return 3 * ((max_w + kRowPad + 15) & ~15) + 4 <= lds_room(sizeof(QDecodeLds)) ? kPlanRowsInLds : 0; }
 
 template <class K>
 static bool launch_rows(K kernel, size_t static_lds, const SerialJob *d_jobs, const SerialJob *h_jobs, int n, hipStream_t s, int threads = 64,

@@ -230,6 +230,43 @@ class Oracle:
         rc = self.lib.orc_qnblic_decode(buf.ctypes.data_as(C.POINTER(C.c_uint16)), _ptr(img), C.byref(hh), C.byref(ww), C.c_long(0))
         return None if rc != 0 else img
 
+    def q_model(self, img: np.ndarray):
+        """orc_q_model: per pixel in raster order the level ``qd`` and the symbol ``y`` the entropy stage codes, and the
+        12 x 256 counts ``hist`` of the symbols per level.  Returns (qd, y, hist)."""
+        img = np.ascontiguousarray(img, np.uint8)
+        h, w = img.shape
+        qd, y = np.empty(h * w, np.uint8), np.empty(h * w, np.uint8)
+        hist = np.zeros((12, 256), np.uint32)
+        self.lib.orc_q_model.restype = None
+        self.lib.orc_q_model(_ptr(img), h, w, None, None, _ptr(qd), _ptr(y), C.c_void_p(hist.ctypes.data))
+        return qd, y, hist
+
+    def q_norm_hist(self, hist) -> np.ndarray:
+        """orc_q_norm_hist on one 256-entry histogram: its scaling to a sum of 2^15 (a copy; the argument is left alone)."""
+        out = np.ascontiguousarray(hist, np.uint32).reshape(256).copy()
+        self.lib.orc_q_norm_hist.restype = None
+        self.lib.orc_q_norm_hist(C.c_void_p(out.ctypes.data))
+        return out
+
+    def qencode_tables(self, img: np.ndarray, tables, model=None) -> bytes:
+        """The QNBLIC stream of ``img`` coded with the caller's 12 x 256 ``tables`` in place of the image's own counts
+        (orc_q_entropy_stage with hist_in = tables).  The stage scales what it is given (orc_q_norm_hist), so the stream
+        carries ``tables`` themselves only where every level is a fixed point of that scaling; every symbol the image
+        codes needs a nonzero entry (ValueError otherwise: the coder would divide by zero).  ``model``: the
+        ``q_model(img)`` triple when the caller has it already."""
+        img = np.ascontiguousarray(img, np.uint8)
+        h, w = img.shape
+        qd, y, _ = self.q_model(img) if model is None else model
+        tables = np.ascontiguousarray(tables, np.uint32).reshape(12, 256)
+        if (tables[qd, y] == 0).any():
+            raise ValueError("a coded symbol has no entry in the tables")
+        out = np.empty(h * w + 4 + 12 * 256 + 2, np.uint16)              # header, 12 x 256 codes, a word per pixel, the state
+        fn = self.lib.orc_q_entropy_stage
+        fn.restype = C.c_long
+        words = fn(C.c_void_p(out.ctypes.data), h, w, _ptr(qd), _ptr(y), C.c_void_p(tables.ctypes.data))
+        assert 0 < words <= out.size
+        return out[:words].tobytes()
+
 
 class Reference:
     """The unmodified reference library compiled into oracle/_ref (never shipped in git)."""
