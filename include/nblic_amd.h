@@ -527,6 +527,68 @@ int nblic_amd_decode_batch_to(nblic_amd_ctx *ctx, int n_images, const unsigned c
                               const nblic_amd_dest *dests, int format, float scale, float bias, int *heights, int *widths,
                               int *nears, int *efforts, int *status);
 
+/* ENCODE FROM DEVICE MEMORY: the batch encoders on images that lie in caller-owned device memory in ANY layout -- a crop
+ * of a larger frame, a pitched surface, one channel of an [N, C, H, W] tensor, one colour of an interleaved H x W x 3 frame
+ * -- as pixels or as floats that are quantised to 8 bits on the way.  The counterpart of the two calls above: a batch goes
+ * device memory -> streams (+ seek indexes) -> device memory without a pixel in host memory of the caller's.
+ *   the source      element (r, c) of image k is read at ptr + r x pitch_bytes + c x step_bytes.  The image IS the window: a
+ *                   crop offsets ptr.  ptr is device memory of the context's device; ptr, pitch_bytes and step_bytes are
+ *                   multiples of the element size and not below it; cap_bytes is what may be read from ptr on.  Nothing
+ *                   outside the elements of the image is read: pitch gaps and the bytes between the pixels are not touched.
+ *   format          0 uint8 (the pixel is the element; scale must be 1 and bias 0), 1 float16, 2 bfloat16, 3 float32: the
+ *                   pixel is float(x) x scale, rounded to float, + bias, rounded to float -- never fused -- NaN to 0,
+ *                   everything else clamped to [0, 255] and rounded to nearest, ties to even: numpy's
+ *                   clip(rint(float32(x) * float32(scale) + float32(bias)), 0, 255) with NaN as 0 is the same bits.
+ *                   "Lossless" means lossless with respect to this collected plane.
+ *   collection      a uint8 source with step_bytes == 1 and pitch_bytes == cols is used where it lies, at the cost of
+ *                   imgs_on_device = 1.  Every other one is written into the workspace of the slot that encodes it -- the
+ *                   buffer a host plane is uploaded into -- by k_collect: ONE launch for the images of
+ *                   a group's front half, and in the indexed calls one per group step, for the rows of the step's bands.
+ *   per image       REFUSED on the host, before anything of it is launched, with the other images unaffected -- out_lens[k]
+ *                   = -1 and, in the indexed calls, index_lens[k] = -1: rows or cols the encoder does not take; a ptr,
+ *                   pitch_bytes or step_bytes that is no multiple of the element size or is below it; step_bytes > 2^20 or
+ *                   pitch_bytes > 2^40; (rows - 1) x pitch_bytes + (cols - 1) x step_bytes + element size > cap_bytes or
+ *                   beyond the end of the allocation ptr lies in; a ptr the runtime (hipPointerGetAttributes) does not
+ *                   report as device memory of the context's device.
+ *   whole call      -1 with nothing launched: what the parent call refuses, a NULL srcs, an unknown format, a scale or bias
+ *                   that is not finite, uint8 with scale != 1 or bias != 0.
+ * Sources may overlap: they are only read.  The calls return when the streams are complete, and they order themselves
+ * against NOTHING the caller has queued on streams of its own: a source must not be in use by pending work when the call is
+ * made, and must stay valid and unchanged until it returns.
+ * Each call is its parent -- nblic_amd_encode_batch_modes (NULL nears / efforts: -n0 -e1 on the staged pipeline; recons stay
+ * host buffers), nblic_amd_qencode_batch, nblic_amd_encode_batch_indexed, nblic_amd_qencode_batch_indexed -- with srcs,
+ * format, scale, bias in place of imgs, imgs_on_device, heights, widths, and returns byte for byte what the parent returns
+ * for the collected planes, indexes included.  There is no asynchronous _begin / _end pair and no nblic_amd_stream_* on
+ * sources, and reconstructions are not delivered to device memory.
+ * nblic_amd_collect_stats: since the context was created, out[0] images used in place, [1] images collected, [2] k_collect
+ * launches, [3] pixels collected.  Returns 0, -1 for a null pointer.
+ * nblic_amd_collect_ms: while nblic_amd_enable_timing is on, a k_collect launch stands between two events of its group;
+ * *ms is the GPU time of the launches timed since the context was created and *timed_launches their number (a group has
+ * one pair of events, so of the steps that an indexed effort-0 batch queues ahead only those that find it free are
+ * timed).  Call it when no batch is outstanding.  Returns 0, -1 for a null pointer. */
+typedef struct nblic_amd_src {
+    const void *ptr;        /* element (0, 0) of the image, device memory of the context's device */
+    size_t pitch_bytes;     /* between rows                                                        */
+    size_t step_bytes;      /* between neighbouring pixels of a row (element size: contiguous)     */
+    size_t cap_bytes;       /* readable bytes from ptr                                             */
+    int    rows, cols;      /* the image: height and width of what is encoded                      */
+} nblic_amd_src;
+int nblic_amd_encode_batch_modes_from(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                      const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps,
+                                      long *out_lens, unsigned char *const *recons);
+int nblic_amd_qencode_batch_from(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                 uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words);
+int nblic_amd_encode_batch_indexed_from(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale,
+                                        float bias, const int *every_rows, int band_rows, unsigned char *const *outs,
+                                        const size_t *out_caps, long *out_lens, unsigned char *const *indexes,
+                                        const size_t *index_caps, long *index_lens);
+int nblic_amd_qencode_batch_indexed_from(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale,
+                                         float bias, const int *every_rows, int band_rows, uint16_t *const *outs,
+                                         const size_t *out_caps_words, long *out_len_words, unsigned char *const *indexes,
+                                         const size_t *index_caps, long *index_lens);
+int nblic_amd_collect_stats(nblic_amd_ctx *ctx, long out[4]);
+int nblic_amd_collect_ms(nblic_amd_ctx *ctx, double *ms, long *timed_launches);
+
 /* BATCH INDEX BUILD: the seek indexes of many streams from ONE decode pass.  nblic_amd_index_build takes one stream per
  * call and pays a host round trip at every band and every entry; this call takes n streams -- NBLIC in any mode and QNBLIC,
  * written by this library or by the reference; any mix of geometries and of R = every_rows[k] -- and writes into
@@ -838,6 +900,29 @@ int nblic_amd_debug_deliver(nblic_amd_ctx *ctx, int n, const unsigned char *cons
                             const size_t *base_offsets, const int *plane_rows, const int *widths, const int *windows,
                             const int *formats, const float *scales, const float *biases, const int *zeros, const size_t *pitches,
                             const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs, const int *gate_status);
+
+/* Debug hooks used by the collection's tests (the _from encoders), the twins of the two above.  A task is a source -- its
+ * bytes, the image's rows x cols, a pitch and a step in bytes, a format with its scale and bias -- and optionally a range of
+ * two ints (px0, px1): the pixels of the flat rows x cols plane it writes (px1 == 0: to the end; NULL: all of it), as the
+ * indexed batch collects the rows of a band.
+ * nblic_amd_debug_collect_host: host only, no context, no device.  It runs the unit walk the kernel shares with the host
+ * (csrc/collect.h) over the source at src (cap_bytes readable) into out, which must be a multiple of 16 and hold rows x cols
+ * bytes.  units / chunks (may be NULL) receive what a launch counts for the task: (px1 + 15) / 16 - px0 / 16 units, 1024
+ * to a chunk.
+ * nblic_amd_debug_collect: ONE k_collect launch over n tasks (1 .. 65536).  The src_bytes[k] bytes of source k are uploaded
+ * at byte base_offsets[k] (0 .. 255) of a larger device buffer that holds 0xFF everywhere else (NaN in every float format);
+ * element (0, 0) is the first of them, and the task is refused unless the image's extent fits src_bytes[k].  Plane k lies at
+ * byte 256 of a device buffer of out_bytes[k] = 256 + rows x cols rounded up to 256 + 256 bytes that holds 0x5A everywhere
+ * before the launch and comes back whole in outs[k].
+ * Both return 0; -1, with nothing launched or written, for a null pointer or anything the _from calls refuse of a source,
+ * a range outside the plane or a buffer of the wrong size; nblic_amd_debug_collect -2 when a HIP call failed. */
+int nblic_amd_debug_collect_host(const void *src, size_t cap_bytes, int rows, int cols, size_t pitch_bytes, size_t step_bytes, int format,
+                                 float scale, float bias, const int *range, unsigned char *out, size_t out_bytes,
+                                 unsigned long long *units, unsigned long long *chunks);
+int nblic_amd_debug_collect(nblic_amd_ctx *ctx, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets,
+                            const int *rows, const int *cols, const size_t *pitches, const size_t *steps, const int *formats,
+                            const float *scales, const float *biases, const int *ranges, unsigned char *const *outs,
+                            const size_t *out_bytes);
 
 /* Debug hook used by the indexed effort-0 batch's host tests: QNBLIC's entropy stage (histogram normalisation, histogram
  * code, the rANS pass) on caller-made records, reporting the coder in front of entry rows as the batch's workers read it.

@@ -53,6 +53,8 @@ EXPORTS = (
     "nblic_amd_index_build_batch", "nblic_amd_index_build_split", "nblic_amd_index_build_plan", "nblic_amd_debug_index_capture",
     "nblic_amd_index_pack", "nblic_amd_index_pack_bound", "nblic_amd_index_unpack", "nblic_amd_index_unpacked_bytes", "nblic_amd_index_is_packed", "nblic_amd_debug_index_unpack",
     "nblic_amd_decode_batch_indexed_to", "nblic_amd_decode_batch_to", "nblic_amd_debug_deliver_host", "nblic_amd_debug_deliver",
+    "nblic_amd_encode_batch_modes_from", "nblic_amd_qencode_batch_from", "nblic_amd_encode_batch_indexed_from", "nblic_amd_qencode_batch_indexed_from",
+    "nblic_amd_collect_stats", "nblic_amd_collect_ms", "nblic_amd_debug_collect_host", "nblic_amd_debug_collect",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats", "nblic_amd_copy_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -254,6 +256,26 @@ def load_library() -> C.CDLL:
                                                      C.c_size_t, C.c_size_t, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
         lib.nblic_amd_debug_deliver.restype = C.c_int
         lib.nblic_amd_debug_deliver.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, ip, ip, ip, ip, fp, fp, ip, szp, szp, szp, vpp, ip]
+    if hasattr(lib, "nblic_amd_encode_batch_modes_from"):           # (an older build loaded through NBLIC_AMD_LIB has none of the seven)
+        vpp, szp, fp, sp, lp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(Src), C.POINTER(C.c_long)
+        head = [C.c_void_p, C.c_int, sp, C.c_int, C.c_float, C.c_float]
+        lib.nblic_amd_encode_batch_modes_from.restype = C.c_int
+        lib.nblic_amd_encode_batch_modes_from.argtypes = head + [ip, ip, vpp, szp, lp, vpp]
+        lib.nblic_amd_qencode_batch_from.restype = C.c_int
+        lib.nblic_amd_qencode_batch_from.argtypes = head + [vpp, szp, lp]
+        lib.nblic_amd_encode_batch_indexed_from.restype = C.c_int
+        lib.nblic_amd_encode_batch_indexed_from.argtypes = head + [ip, C.c_int, vpp, szp, lp, vpp, szp, lp]
+        lib.nblic_amd_qencode_batch_indexed_from.restype = C.c_int
+        lib.nblic_amd_qencode_batch_indexed_from.argtypes = lib.nblic_amd_encode_batch_indexed_from.argtypes
+        lib.nblic_amd_collect_stats.restype = C.c_int
+        lib.nblic_amd_collect_stats.argtypes = [C.c_void_p, lp]
+        lib.nblic_amd_collect_ms.restype = C.c_int
+        lib.nblic_amd_collect_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), lp]
+        lib.nblic_amd_debug_collect_host.restype = C.c_int
+        lib.nblic_amd_debug_collect_host.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_float, ip,
+                                                     C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+        lib.nblic_amd_debug_collect.restype = C.c_int
+        lib.nblic_amd_debug_collect.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, ip, ip, szp, szp, ip, fp, fp, ip, vpp, szp]
     if hasattr(lib, "nblic_amd_index_build_batch"):
         vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
         lib.nblic_amd_index_build_batch.restype = C.c_int
@@ -448,6 +470,139 @@ def _dest_array(dests):
     for k, d in enumerate(dests):
         arr[k] = Dest(*[int(x) if i else (int(x) or None) for i, x in enumerate(d)])
     return arr
+
+
+class Src(C.Structure):
+    """``nblic_amd_src``: where one image lies in device memory."""
+    _fields_ = [("ptr", C.c_void_p), ("pitch_bytes", C.c_size_t), ("step_bytes", C.c_size_t), ("cap_bytes", C.c_size_t),
+                ("rows", C.c_int), ("cols", C.c_int)]
+
+
+COLLECT_PATTERN = 0x5A                                                          # what nblic_amd_debug_collect's output buffers hold before the launch
+COLLECT_GUARD = 256                                                             # bytes of it in front of a plane and behind it
+
+
+def collect_format(dtype) -> int:
+    """The ``format`` of the _from calls a dtype stands for: the delivery's numbers (:func:`deliver_format`)."""
+    return deliver_format(dtype)
+
+
+def collect_units(rows: int, cols: int, px0: int = 0, px1: int = 0) -> Tuple[int, int]:
+    """Units and chunks one collect task counts (csrc/collect.h): sixteen consecutive bytes of the flat plane at a
+    multiple of 16 are a unit, 1024 units go to a chunk (one workgroup)."""
+    px1 = px1 or rows * cols
+    units = (px1 + 15) // 16 - px0 // 16
+    return units, (units + 1023) // 1024
+
+
+def collect_numpy(values: np.ndarray, fmt, scale: float = 1.0, bias: float = 0.0) -> np.ndarray:
+    """The collected plane of a 2-D array of source elements, in numpy alone: what the _from calls encode.  ``values`` holds
+    uint8, float16 or float32 elements, or -- format 2 -- the uint16 bit patterns of bfloat16 ones."""
+    fmt = fmt if isinstance(fmt, int) else collect_format(fmt)
+    values = np.asarray(values)
+    if fmt == 0:
+        return np.ascontiguousarray(values, np.uint8)
+    if fmt == 2:
+        x = (np.ascontiguousarray(values, np.uint16).astype(np.uint32) << 16).view(np.float32)
+    else:
+        x = np.asarray(values, np.float16 if fmt == 1 else np.float32).astype(np.float32)
+    with np.errstate(all="ignore"):
+        t = x * np.float32(scale) + np.float32(bias)
+        px = np.clip(np.rint(t), 0, 255)
+    return np.where(np.isnan(t), np.float32(0), px).astype(np.uint8)
+
+
+def collect_host(array: np.ndarray, fmt, scale: float = 1.0, bias: float = 0.0, pitch: Optional[int] = None, step: Optional[int] = None,
+                 offset: int = 0, rows: Optional[int] = None, cols: Optional[int] = None, cap: Optional[int] = None, px_range=None,
+                 info: Optional[dict] = None) -> np.ndarray:
+    """The collect kernel's unit walk on the host (``nblic_amd_debug_collect_host``; no device).  With ``rows`` and ``cols``,
+    ``array`` is a buffer of raw bytes in which element (0, 0) of the image lies at byte ``offset``, rows ``pitch`` bytes and
+    the pixels of a row ``step`` bytes apart, ``cap`` bytes readable from there (default: to the buffer's end).  Without
+    them ``array`` is a 2-D view whose shape and strides say all of that.  ``px_range``: the pixels (px0, px1) of the flat
+    plane to write; the rest keeps 0x5A.  Returns the plane (rows x cols, uint8); ``info`` receives ``units`` and
+    ``chunks``.  ``ValueError`` when refused."""
+    fmt = fmt if isinstance(fmt, int) else collect_format(fmt)
+    if rows is None or cols is None:
+        if array.ndim != 2 or any(s < 0 for s in array.strides):
+            raise ValueError("collect_host: a 2-D view with non-negative strides, or raw bytes with rows and cols")
+        rows, cols = array.shape
+        pitch, step = (array.strides[0] if rows > 1 else max(array.strides[0], cols * array.strides[1])), array.strides[1] if cols > 1 else array.itemsize
+        base, cap = array.ctypes.data, max(rows - 1, 0) * pitch + max(cols - 1, 0) * step + array.itemsize
+    else:
+        raw = array.reshape(-1).view(np.uint8)
+        elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
+        pitch = cols * elem if pitch is None else pitch
+        step = elem if step is None else step
+        base, cap = raw.ctypes.data + int(offset), (raw.size - int(offset) if cap is None else int(cap))
+    store = np.full(max(int(rows) * int(cols), 1) + 16, COLLECT_PATTERN, np.uint8)
+    lead = (-store.ctypes.data) % 16
+    out = store[lead: lead + max(int(rows) * int(cols), 0)]
+    rng = None if px_range is None else (C.c_int * 2)(int(px_range[0]), int(px_range[1]))
+    units, chunks = C.c_ulonglong(0), C.c_ulonglong(0)
+    rc = load_library().nblic_amd_debug_collect_host(base, max(int(cap), 0), int(rows), int(cols), int(pitch), int(step), int(fmt), float(scale), float(bias),
+                                                     rng, out.ctypes.data if out.size else None, out.size, C.byref(units), C.byref(chunks))
+    if rc != 0:
+        raise ValueError("nblic_amd_debug_collect_host refused its arguments")
+    if info is not None:
+        info["units"], info["chunks"] = int(units.value), int(chunks.value)
+    return out.reshape(int(rows), int(cols))
+
+
+def _src_views(src):
+    """The 2-D view of every image: ``src`` is one tensor [N, H, W] or [N, C, H, W] (every channel an image, n-major), or
+    a list of 2-D tensors or views."""
+    if isinstance(src, (list, tuple)):
+        views = list(src)
+    else:
+        shape = tuple(src.shape)
+        if len(shape) == 4:
+            views = [src[n][c] for n in range(shape[0]) for c in range(shape[1])]
+        elif len(shape) == 3:
+            views = [src[n] for n in range(shape[0])]
+        else:
+            raise ValueError("src: a tensor [N, H, W] or [N, C, H, W], or a list of 2-D tensors")
+    if any(len(tuple(v.shape)) != 2 for v in views):
+        raise ValueError("src: one 2-D tensor per image")
+    return views
+
+
+def _srcs_of(views, rows, cols) -> Tuple[list, int]:
+    """One ``(ptr, pitch, step, cap, rows, cols)`` per image and the call's format, from tensors used duck-typed
+    (``data_ptr()``, ``stride()``, ``element_size()``, ``shape``, ``dtype``): any non-negative strides.  ``rows`` / ``cols``
+    crop -- ``(a, b)`` with b == 0 for "to the end", as :func:`_pairs_for` takes them -- by offsetting the pointer."""
+    n = len(views)
+    fmts = {collect_format(v.dtype) for v in views}
+    if len(fmts) > 1:
+        raise ValueError("src: one dtype per call")
+    fmt = fmts.pop() if fmts else 0
+    rows, cols = _pairs_for(rows, n, "rows"), _pairs_for(cols, n, "cols")
+    srcs = []
+    for k, v in enumerate(views):
+        elem = int(v.element_size())
+        hh, ww = (int(x) for x in v.shape)
+        s0, s1 = (int(x) for x in v.stride())
+        if s0 < 0 or s1 < 0:
+            raise ValueError("src: strides must not be negative")
+        (r0, r1), (c0, c1) = rows[k], cols[k]
+        r1, c1 = r1 or hh, c1 or ww
+        if not (0 <= r0 <= r1 <= hh and 0 <= c0 <= c1 <= ww):
+            raise ValueError(f"src: the crop of image {k} is outside its tensor")
+        ptr = int(v.data_ptr()) + (r0 * s0 + c0 * s1) * elem
+        h, w = r1 - r0, c1 - c0
+        try:                                                    # what the storage holds from the crop's first element on, when the tensor tells
+            st = v.untyped_storage()
+            cap = int(st.data_ptr()) + int(st.nbytes()) - ptr
+        except AttributeError:                                  # otherwise the crop's own extent
+            cap = (max(h - 1, 0) * s0 + max(w - 1, 0) * s1 + 1) * elem
+        srcs.append((ptr, (s0 if h > 1 else max(s0, 1)) * elem, (s1 if w > 1 else max(s1, 1)) * elem, max(cap, 0), h, w))
+    return srcs, fmt
+
+
+def _per_image(arg, n: int, what: str) -> List[int]:
+    vals = [int(arg)] * n if np.isscalar(arg) else [int(v) for v in arg]
+    if len(vals) != n:
+        raise ValueError(f"{what}: one value, or one per image")
+    return vals
 
 
 def index_bytes(kind: int, h: int, w: int, effort: int, every_rows: int) -> int:
@@ -1200,6 +1355,136 @@ class Context:
         if rc != 0:
             raise RuntimeError("nblic_amd_debug_deliver failed (%d)" % rc)
         return [o[:b] for o, b in zip(outs, sizes)]
+
+    def collect_stats(self) -> Tuple[int, int, int, int]:
+        """Since the context was created (``nblic_amd_collect_stats``): images of the _from calls used in place, images
+        collected, k_collect launches, pixels collected."""
+        v = (C.c_long * 4)()
+        if self.lib.nblic_amd_collect_stats(self.handle, v) != 0:
+            raise RuntimeError("nblic_amd_collect_stats failed")
+        return tuple(int(x) for x in v)
+
+    def collect_ms(self) -> Tuple[float, int]:
+        """GPU milliseconds of the k_collect launches timed while ``enable_timing`` was on, and how many were timed
+        (``nblic_amd_collect_ms``).  Call it when no batch is outstanding."""
+        ms, k = C.c_double(0), C.c_long(0)
+        if self.lib.nblic_amd_collect_ms(self.handle, C.byref(ms), C.byref(k)) != 0:
+            raise RuntimeError("nblic_amd_collect_ms failed")
+        return float(ms.value), int(k.value)
+
+    def encode_from_srcs(self, srcs, fmt: int, scale: float = 1.0, bias: float = 0.0, near=0, effort=1, every_rows=None, band_rows: int = 0,
+                         info: Optional[dict] = None):
+        """The four _from calls on ``srcs``, one ``(ptr, pitch_bytes, step_bytes, cap_bytes, rows, cols)`` per image (device
+        memory), in format ``fmt`` (0 .. 3).  ``effort`` 0 (for every image) takes the QNBLIC calls, ``every_rows`` the
+        indexed ones.  Returns the streams -- ``None`` for a refused or failed image -- or (stream, index) pairs when
+        ``every_rows`` is given; ``info`` receives ``rc`` and, for the mode call, ``recons`` (the host reconstructions).
+        ``ValueError`` when the library refuses the whole call."""
+        n = len(srcs)
+        nears, efforts = _per_image(near, n, "near"), _per_image(effort, n, "effort")
+        q = n > 0 and all(e == 0 for e in efforts)
+        if (not q and any(e == 0 for e in efforts)) or (q and any(nears)):
+            raise ValueError("effort 0 (QNBLIC) is lossless and takes a whole call")
+        if every_rows is not None and not q and (any(nears) or any(e != 1 for e in efforts)):
+            raise ValueError("the indexed calls are lossless -e1 or effort 0")
+        arr = (Src * max(n, 1))()
+        for k, s in enumerate(srcs):
+            arr[k] = Src(*[int(x) if i else (int(x) or None) for i, x in enumerate(s)])
+        shapes = [(max(int(s[4]), 1), max(int(s[5]), 1)) for s in srcs]
+        outs = [np.empty(out_capacity(h, w) // (2 if q else 1), np.uint16 if q else np.uint8) for h, w in shapes]
+        m = max(n, 1)
+        op = (C.c_void_p * m)(*[C.c_void_p(o.ctypes.data) for o in outs])
+        caps = (C.c_size_t * m)(*[o.size for o in outs])
+        lens = (C.c_long * m)(*([-2] * m))                      # (the library writes every length once it has accepted the call)
+        head = (self.handle, n, arr, int(fmt), float(scale), float(bias))
+        recs = idxs = xlens = None
+        if every_rows is not None:
+            every = _every_rows_list(every_rows, n)
+            idxs = [np.empty(max(index_bytes(1 if q else 0, h, w, 0 if q else 1, r), 1), np.uint8) for (h, w), r in zip(shapes, every)]
+            xp = (C.c_void_p * m)(*[C.c_void_p(x.ctypes.data) for x in idxs])
+            xcaps, xlens = (C.c_size_t * m)(*[x.size for x in idxs]), (C.c_long * m)()
+            call = self.lib.nblic_amd_qencode_batch_indexed_from if q else self.lib.nblic_amd_encode_batch_indexed_from
+            rc = call(*head, (C.c_int * m)(*every), int(band_rows), op, caps, lens, xp, xcaps, xlens)
+        elif q:
+            rc = self.lib.nblic_amd_qencode_batch_from(*head, op, caps, lens)
+        else:
+            if info is not None:
+                recs = [np.zeros(s, np.uint8) for s in shapes]
+            rp = (C.c_void_p * m)(*[C.c_void_p(r.ctypes.data) for r in recs]) if recs is not None else None
+            rc = self.lib.nblic_amd_encode_batch_modes_from(*head, (C.c_int * m)(*nears), (C.c_int * m)(*efforts), op, caps, lens, rp)
+        if rc != 0 and n > 0 and all(v == -2 for v in lens[:n]):
+            raise ValueError("the library refused the whole call")
+        if info is not None:
+            info["rc"] = int(rc)
+            if recs is not None:
+                info["recons"] = recs
+        streams = [o[:v].tobytes() if v >= 0 else None for o, v in zip(outs, lens[:n])]
+        if every_rows is None:
+            return streams
+        return list(zip(streams, [x[:v].tobytes() if v > 0 else None for x, v in zip(idxs, xlens[:n])]))
+
+    def encode_src_ptrs(self, srcs, fmt: int, scale: float = 1.0, bias: float = 0.0,
+                        outs: Optional[List[np.ndarray]] = None) -> Tuple[List[np.ndarray], np.ndarray]:
+        """-n0 -e1 encode of sources given as ``(ptr, pitch_bytes, step_bytes, cap_bytes, rows, cols)`` (device memory), as
+        :meth:`encode_ptrs` encodes planes: returns (out buffers, lengths) and raises if any image failed."""
+        k = len(srcs)
+        arr = (Src * max(k, 1))()
+        for i, s in enumerate(srcs):
+            arr[i] = Src(*[int(x) if j else (int(x) or None) for j, x in enumerate(s)])
+        if outs is None:
+            outs = [np.empty(out_capacity(int(s[4]), int(s[5])), np.uint8) for s in srcs]
+        op = (C.c_void_p * k)(*[C.c_void_p(o.ctypes.data) for o in outs])
+        caps, lens = (C.c_size_t * k)(*[o.size for o in outs]), (C.c_long * k)()
+        rc = self.lib.nblic_amd_encode_batch_modes_from(self.handle, k, arr, int(fmt), float(scale), float(bias), None, None, op, caps, lens, None)
+        got = np.array(list(lens), dtype=np.int64)
+        if rc != 0:
+            raise RuntimeError(f"nblic_amd_encode_batch_modes_from failed (lengths {got.tolist()})")
+        return outs, got
+
+    def encode_batch_from(self, src, rows=None, cols=None, scale: float = 1.0, bias: float = 0.0, near=0, effort=1, every_rows=None,
+                          band_rows: int = 0, info: Optional[dict] = None):
+        """Encode images that lie in device memory in any layout, as pixels or as floats quantised on the way (the _from
+        calls; include/nblic_amd.h says what the pixel of an element is).  ``src``: one tensor [N, H, W], one tensor
+        [N, C, H, W] -- every channel is an image, n-major -- or a list of 2-D tensors or views, of ONE dtype (uint8,
+        float16, bfloat16, float32) and with any non-negative strides: a channels-last tensor and an H x W x 3 frame seen
+        as three [H, W] views work as they are.  Tensors are used duck-typed (``data_ptr()``, ``stride()``,
+        ``element_size()``, ``shape``, ``dtype``).  ``rows`` / ``cols`` crop every image, or one pair per image.
+        ``near`` / ``effort``: one value or one per image; ``effort`` 0 takes the QNBLIC calls, ``every_rows`` the indexed
+        ones (lossless -e1 or effort 0).  Returns the streams (``None`` for a refused or failed image), or
+        (stream, index) pairs when ``every_rows`` is given.  The caller makes sure that the tensors' producers have
+        finished (``torch.cuda.synchronize()``): the call orders itself against no stream of the caller's."""
+        srcs, fmt = _srcs_of(_src_views(src), rows, cols)
+        return self.encode_from_srcs(srcs, fmt, scale, bias, near, effort, every_rows, band_rows, info)
+
+    def debug_collect(self, tasks) -> List[np.ndarray]:
+        """``nblic_amd_debug_collect``: ONE k_collect launch over ``tasks``, each a dict with ``raw`` (the source's bytes, any
+        array; element (0, 0) is its first byte), ``rows``, ``cols`` and ``fmt``, and optionally ``pitch`` and ``step`` in
+        bytes (default: contiguous), ``scale``, ``bias``, ``base_offset`` (0 .. 255, of the bytes in their 0xFF-filled device
+        buffer) and ``px_range`` (px0, px1).  Returns every task's whole buffer (uint8): 256 bytes of 0x5A, the plane
+        rounded up to 256 bytes, 256 bytes of 0x5A.  ``ValueError`` when refused."""
+        n = len(tasks)
+        raws, hs, ws, pitches, steps, fmts, scales, biases, bases, ranges = ([] for _ in range(10))
+        for t in tasks:
+            fmt = t["fmt"] if isinstance(t["fmt"], int) else collect_format(t["fmt"])
+            elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
+            raws.append(np.ascontiguousarray(t["raw"]).reshape(-1).view(np.uint8))
+            hs.append(int(t["rows"])); ws.append(int(t["cols"])); fmts.append(fmt)
+            pitches.append(int(t.get("pitch", int(t["cols"]) * elem))); steps.append(int(t.get("step", elem)))
+            scales.append(float(t.get("scale", 1.0))); biases.append(float(t.get("bias", 0.0))); bases.append(int(t.get("base_offset", 0)))
+            ranges += [int(v) for v in t.get("px_range", (0, 0))]
+        sizes = [2 * COLLECT_GUARD + ((max(h * w, 0) + 255) & ~255) for h, w in zip(hs, ws)]
+        outs = [np.zeros(b, np.uint8) for b in sizes]
+        m = max(n, 1)
+        vp = lambda arrs: (C.c_void_p * m)(*[a.ctypes.data for a in arrs])
+        sz = lambda vals: (C.c_size_t * m)(*[int(v) for v in vals])
+        iv = lambda vals, k=1: (C.c_int * (m * k))(*[int(v) for v in vals])
+        fv = lambda vals: (C.c_float * m)(*vals)
+        rc = self.lib.nblic_amd_debug_collect(self.handle, n, vp(raws), sz(r.size for r in raws), sz(bases), iv(hs), iv(ws), sz(pitches), sz(steps),
+                                              iv(fmts), fv(scales), fv(biases), iv(ranges, 2), vp(outs), sz(sizes))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_collect refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_collect failed (%d)" % rc)
+        return outs
 
     def indexed_decode_split(self) -> dict:
         """Host milliseconds of the last ``decode_batch_indexed`` (``nblic_amd_indexed_decode_split``)."""

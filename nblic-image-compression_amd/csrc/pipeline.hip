@@ -175,6 +175,8 @@ struct Slot {
 // What a driver thread sleeps on while its group's front half runs (a host function queued behind the front half
 // sets `ready`).  hipEventSynchronize is NOT a sleep here, whatever the event's flags say: measured, a driver burnt
 // 35 ms of CPU per 55 ms wait, 1.1 of the rank's 16 CPUs between the six of them -- quota the coder threads need.
+struct CollectFrom;                                    // below: what the _from calls hand down
+
 struct GroupWait { std::mutex m; std::condition_variable cv; bool ready = false; };
 
 struct Group {
@@ -204,6 +206,13 @@ struct Group {
     std::vector<Locked> qidx_bufs; std::vector<Event> qidx_ready;
     Pinned<E1Job> qidx_jobs; Pinned<IndexRecordTask> qidx_tasks; Pinned<uint32_t> qidx_totals;
     DevBuf<IndexRecordTask> qidx_d_tasks; DevBuf<uint8_t> qidx_d_recs;
+    // the _from calls (at the end: no member that existed before has moved).  Where the images lie, handed over with imgs /
+    // on_device (guarded by ctx->dm; null: imgs / on_device say it)
+    const CollectFrom *from = nullptr;
+    // collection (collect.h): the tasks of the launch that is being put together, and their device copy.  Allocated by the
+    // first call that collects; an indexed effort-0 batch uses one stretch of them per queued step
+    Pinned<CollectTask> h_ctasks; DevBuf<CollectTask> d_ctasks; int n_ctasks = 0;
+    Event ct_ev[2]; bool ct_pending = false;           // nblic_amd_enable_timing: the marks around a k_collect launch that nobody has read yet
 };
 
 }  // namespace nblic
@@ -265,6 +274,7 @@ struct nblic_amd_ctx {
         ::nblic_amd_batch *b; int kind;       // 0 NBLIC (per image near / effort), 1 QNBLIC (outs are uint16_t streams, caps / lens in words)
         int n; const uint8_t *const *imgs; bool on_device; const int *hs, *ws;
         uint8_t *const *outs; const size_t *caps; long *lens; const int *nears, *efforts; unsigned char *const *recons;
+        const CollectFrom *from = nullptr;    // the _from calls: imgs / on_device / hs / ws are its own (collect_plan)
     };
     std::thread submitter;
     std::mutex sm;
@@ -298,6 +308,8 @@ struct nblic_amd_ctx {
     long fed_bytes = 0;                   // bytes the last drop-in decode read from the caller's stream
     int feed_pipe[2] = {-1, -1};          // safe_copy: the kernel does the reading
     DevBuf<DeliverTask> dec_deliver;      // nblic_amd_decode_batch_to: the chunks' delivery tasks (grow-only, like dec_jobs)
+    std::atomic<long> collect_counts[4] = {};   // nblic_amd_collect_stats: images in place, images collected, k_collect launches, pixels collected
+    double collect_ms = 0; long collect_timed = 0;   // nblic_amd_collect_ms: GPU time of the k_collect launches that were timed, and how many.  Guarded by stat_m
 };
 
 namespace nblic {
@@ -465,13 +477,82 @@ static SerialJob model_job(const uint8_t *img, uint8_t *recon, const E1Buffers &
     return Q;
 }
 
+// ---- collection from caller-owned device memory (collect.h, serial_engine.h k_collect) ------------------------------------
+// What the _from calls hand down: one source per image, one format and one quantisation per call, and what collect_plan
+// (below, beside the delivery's checks) made of them on the host: per image refused, used where it lies, or collected
+// by a task; and the arguments of the parent call -- plane pointers (in place: the source; else null), heights, widths
+// (a refused image: 0 x 0, which the parent refuses).
+enum : uint8_t { kSrcRefused = 0, kSrcInPlace = 1, kSrcCollect = 2 };
+struct CollectFrom {
+    const nblic_amd_src *srcs; uint32_t format; float scale, bias;
+    std::vector<uint8_t> how;
+    std::vector<CollectTask> tasks;                                      // kSrcCollect: all but dst, px0, px1 and first_chunk
+    std::vector<const uint8_t *> imgs; std::vector<int> hs, ws;
+};
+
+// Room for n tasks in group g.
+static bool collect_room(Group &g, size_t n) {
+    if (g.h_ctasks.capacity() >= n) return true;
+    HIP_OK(hipStreamSynchronize(g.stream));                              // (a queued upload may still read the old block)
+    HIP_OK(g.h_ctasks.alloc(n)); HIP_OK(g.d_ctasks.alloc(n));
+    return true;
+}
+static void collect_begin(Group &g) { g.n_ctasks = 0; }
+// Appends the task that collects pixels [px0, px1) of image k's flat plane into the plane at dst (16-byte aligned).
+static bool collect_add(Group &g, const CollectFrom &from, int k, uint8_t *dst, uint32_t px0, uint32_t px1, size_t at = 0) {
+    if (at + size_t(g.n_ctasks) >= g.h_ctasks.capacity()) return false;
+    CollectTask &T = g.h_ctasks[at + size_t(g.n_ctasks++)];
+    T = from.tasks[size_t(k)];
+    T.dst = dst; T.px0 = px0; T.px1 = px1;
+    if (px0 == 0) { g.ctx->collect_counts[1]++; g.ctx->collect_counts[3] += long(T.rows) * long(T.cols); }
+    return true;
+}
+// The marks of group g's last timed k_collect launch, added to the context's figures.  wait: for a launch still running
+// (else it is left for later).  false: the marks are still in use.
+static bool collect_timing_read(Group &g, bool wait) {
+    if (!g.ct_pending) return true;
+    if (!wait && hipEventQuery(g.ct_ev[1]) != hipSuccess) { (void)hipGetLastError(); return false; }
+    float ms = 0.f;
+    if (hipEventSynchronize(g.ct_ev[1]) == hipSuccess && hipEventElapsedTime(&ms, g.ct_ev[0], g.ct_ev[1]) == hipSuccess) {
+        std::lock_guard<std::mutex> l(g.ctx->stat_m);
+        g.ctx->collect_ms += ms; g.ctx->collect_timed++;
+    }
+    g.ct_pending = false;
+    return true;
+}
+
+// ONE k_collect launch over the tasks appended since collect_begin, queued on st (none: nothing is queued).  With
+// nblic_amd_enable_timing the launch stands between two marks of the group, when the pair is free: the steps an indexed
+// effort-0 batch queues ahead are not all timed (nblic_amd_collect_ms says how many were).
+static bool collect_flush(Group &g, hipStream_t st, size_t at = 0) {
+    if (g.n_ctasks == 0) return true;
+    const bool timed = g.ctx->timing && collect_timing_read(g, false) && (g.ct_ev[0] || (g.ct_ev[0].create(hipEventDefault) == hipSuccess && g.ct_ev[1].create(hipEventDefault) == hipSuccess));
+    CollectTask *h = g.h_ctasks + at, *d = g.d_ctasks + at;
+    unsigned long long chunks = 0;
+    for (int i = 0; i < g.n_ctasks; i++) { h[i].first_chunk = uint32_t(chunks); chunks += collect_task_chunks(h[i]); }
+    if (chunks >= (1ull << 31)) return false;
+    HIP_OK(hipMemcpyAsync(d, h, size_t(g.n_ctasks) * sizeof(CollectTask), hipMemcpyHostToDevice, st));
+    if (timed) HIP_OK(hipEventRecord(g.ct_ev[0], st));
+    if (!collect_launch(d, g.n_ctasks, uint32_t(chunks), st)) return false;
+    if (timed) { HIP_OK(hipEventRecord(g.ct_ev[1], st)); g.ct_pending = true; }
+    g.ctx->collect_counts[2]++;
+    g.n_ctasks = 0;
+    return true;
+}
+
 // What every front half starts with for slot k of group g (which already carries job / h / w / near): its workspace,
-// its input plane on the device -- the caller's, or a copy on the group's stream -- and its job record.
-static bool slot_begin(Group &g, int k, const uint8_t *const *imgs, bool on_device, bool with_events, int dbg) {
+// its input plane on the device -- the caller's, a copy on the group's stream, or a source that the group's k_collect
+// launch (collect_flush, once the slots have begun) writes into the slot's d_img -- and its job record.
+static bool slot_begin(Group &g, int k, const uint8_t *const *imgs, bool on_device, bool with_events, int dbg, const CollectFrom *from = nullptr) {
     Slot &s = g.slots[size_t(k)];
     const size_t n = size_t(s.h) * size_t(s.w);
     if (!ensure_pixels(s, n, with_events)) return false;
-    if (on_device) {
+    if (from && from->how[size_t(s.job)] == kSrcCollect) {
+        HIP_OK(s.d_img.reserve(n));
+        if (!collect_add(g, *from, s.job, s.d_img, 0, uint32_t(n))) return false;
+        s.b.img = s.d_img;
+    } else if (on_device) {
+        if (from) g.ctx->collect_counts[0]++;
         s.b.img = imgs[s.job];
     } else {
         HIP_OK(s.d_img.reserve(n));
@@ -484,9 +565,17 @@ static bool slot_begin(Group &g, int k, const uint8_t *const *imgs, bool on_devi
 }
 
 // Front half for the images assigned to group g (slots 0..n_jobs-1 already carry job/h/w).
-static bool launch_front(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device) {
+static bool launch_front(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device, const CollectFrom *from = nullptr) {
+    collect_begin(g);
+    if (from && !collect_room(g, g.slots.size())) return false;
     for (int k = 0; k < g.n_jobs; k++)
-        if (!slot_begin(g, k, imgs, on_device, true, dbg_flags())) return false;
+        if (!slot_begin(g, k, imgs, on_device, true, dbg_flags(), from)) return false;
+    if (!collect_flush(g, g.stream)) return false;
+    for (int k = 0; k < g.n_jobs && from && g.recons; k++) {             // -n0 -e1: the reconstruction IS the collected plane
+        const Slot &s = g.slots[size_t(k)];
+        if (from->how[size_t(s.job)] == kSrcCollect && g.recons[s.job])
+            HIP_OK(hipMemcpyAsync(g.recons[s.job], s.d_img, size_t(s.h) * size_t(s.w), hipMemcpyDeviceToHost, g.stream));
+    }
     HIP_OK(hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(g.n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, g.stream));
     g.tm.mask = c->timing_mask;
     e1_launch_front(g.d_jobs, g.h_jobs, g.n_jobs, g.stream, c->timing ? &g.tm : nullptr);
@@ -498,9 +587,11 @@ static bool launch_front(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs,
 // model stage (one wave per image, all images of the group side by side; the slots are ordered by
 // effort, one launch per effort present), the reconstructions on their way back to the host, then
 // the re-mapper partition and chains and the bin counts.
-static bool launch_front_serial(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device) {
+static bool launch_front_serial(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device, const CollectFrom *from = nullptr) {
+    collect_begin(g);
+    if (from && !collect_room(g, g.slots.size())) return false;
     for (int k = 0; k < g.n_jobs; k++) {
-        if (!slot_begin(g, k, imgs, on_device, true, 0)) return false;
+        if (!slot_begin(g, k, imgs, on_device, true, 0, from)) return false;
         Slot &s = g.slots[size_t(k)];
         const size_t n = size_t(s.h) * size_t(s.w);
         const bool wide = !serial_model_rows_fit(s.w);                   // rows do not fit in LDS: taps come from the reconstruction in memory
@@ -513,6 +604,7 @@ static bool launch_front_serial(nblic_amd_ctx *c, Group &g, const uint8_t *const
                                  serial_rows_per_launch(s.h, s.w, s.effort, c->serial_rows), 0, c->d_redo);
         HIP_OK(hipMemsetAsync(s.d_state, 0, sizeof(SerialState), g.stream));               // a fresh image: row 0, running
     }
+    if (!collect_flush(g, g.stream)) return false;
     HIP_OK(hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(g.n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, g.stream));
     HIP_OK(hipMemcpyAsync(g.d_sjobs, g.h_sjobs, size_t(g.n_jobs) * sizeof(SerialJob), hipMemcpyHostToDevice, g.stream));
     e1_launch_init(g.d_jobs, g.n_jobs, g.stream);
@@ -535,7 +627,7 @@ static bool launch_front_serial(nblic_amd_ctx *c, Group &g, const uint8_t *const
         const size_t n = size_t(s.h) * size_t(s.w);
         if (s.near > 0) HIP_OK(hipMemcpyAsync(dst, s.d_recon, n, hipMemcpyDeviceToHost, g.stream));
         else if (!on_device && dst != imgs[s.job]) memcpy(dst, imgs[s.job], n);
-        else if (on_device) HIP_OK(hipMemcpyAsync(dst, imgs[s.job], n, hipMemcpyDeviceToHost, g.stream));
+        else if (on_device) HIP_OK(hipMemcpyAsync(dst, s.b.img, n, hipMemcpyDeviceToHost, g.stream));      // (the caller's plane, or the collected one)
     }
     e1_launch_front_pre(g.d_jobs, g.h_jobs, g.n_jobs, g.stream);
     HIP_OK(hipMemcpyAsync(g.h_totals, g.d_totals, size_t(g.n_jobs) * kTotalsSlot * sizeof(uint32_t), hipMemcpyDeviceToHost, g.stream));
@@ -1189,7 +1281,7 @@ static void collect_timing(nblic_amd_ctx *c, Group &g) {
     c->stage_launches++;
 }
 
-static bool launch_q(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device);
+static bool launch_q(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device, const CollectFrom *from);
 
 static double thread_cpu_s() {
     timespec ts;
@@ -1209,9 +1301,9 @@ static void driver_main(nblic_amd_ctx *c, int id) {
             g.has_work = false;
         }
         const double cpu0 = thread_cpu_s();
-        const bool ok = g.kind == 0 ? (launch_front(c, g, g.imgs, g.on_device) && launch_back(c, g, true))
-                      : g.kind == 2 ? (launch_front_serial(c, g, g.imgs, g.on_device) && launch_back(c, g, true, true))
-                                    : launch_q(c, g, g.imgs, g.on_device);
+        const bool ok = g.kind == 0 ? (launch_front(c, g, g.imgs, g.on_device, g.from) && launch_back(c, g, true))
+                      : g.kind == 2 ? (launch_front_serial(c, g, g.imgs, g.on_device, g.from) && launch_back(c, g, true, true))
+                                    : launch_q(c, g, g.imgs, g.on_device, g.from);
         { std::lock_guard<std::mutex> l(c->stat_m); c->driver_cpu_s += thread_cpu_s() - cpu0; c->driver_launches++; }
         if (!ok) {
             hipStreamSynchronize(g.stream);
@@ -1226,9 +1318,9 @@ static void driver_main(nblic_amd_ctx *c, int id) {
 
 // The images are counted as outstanding BEFORE the driver thread is woken, so the batch's final
 // wait cannot slip through between the hand-over and the launch.
-static void start_group(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device) {
+static void start_group(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device, const CollectFrom *from) {
     { std::lock_guard<std::mutex> l(c->fm); c->coding += g.n_jobs; g.batch->remaining += g.n_jobs; }
-    { std::lock_guard<std::mutex> l(c->dm); g.imgs = imgs; g.on_device = on_device; g.has_work = true; }
+    { std::lock_guard<std::mutex> l(c->dm); g.imgs = imgs; g.on_device = on_device; g.from = from; g.has_work = true; }
     c->dcv.notify_all();
 }
 
@@ -1279,13 +1371,14 @@ static void encode_submit(nblic_amd_ctx *c, const nblic_amd_ctx::SubmitItem &it)
             Slot &s = g.slots[size_t(g.n_jobs++)];
             s.job = k; s.h = it.hs[k]; s.w = it.ws[k]; s.cb = -1; s.pack_n = 1; s.pack_lane = 0; s.near = near_of(k); s.effort = effort_of(k);
             unsigned char *const rec = it.recons ? it.recons[k] : nullptr;
-            if (kind == 0 && rec) {                       // -n0 -e1: the reconstruction IS the input (NBLIC.c:876 rewrites the same bytes)
+            const bool collected = it.from && it.from->how[size_t(k)] == kSrcCollect;      // (launch_front copies the collected plane)
+            if (kind == 0 && rec && !collected) {         // -n0 -e1: the reconstruction IS the input (NBLIC.c:876 rewrites the same bytes)
                 const size_t n = size_t(s.h) * size_t(s.w);
                 if (it.on_device) { if (hipMemcpy(rec, it.imgs[k], n, hipMemcpyDeviceToHost) != hipSuccess) b->ok = false; }
                 else if (rec != it.imgs[k]) memcpy(rec, it.imgs[k], n);
             }
         }
-        start_group(c, g, it.imgs, it.on_device);
+        start_group(c, g, it.imgs, it.on_device, it.from);
     }
 }
 
@@ -1355,9 +1448,12 @@ static bool run_batch(nblic_amd_ctx *c, nblic_amd_ctx::SubmitItem it) {
 }
 
 // ---- QNBLIC (effort 0): model on the GPU, entropy stage on a coder thread ---------------------
-static bool launch_q(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device) {
+static bool launch_q(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs, bool on_device, const CollectFrom *from) {
+    collect_begin(g);
+    if (from && !collect_room(g, g.slots.size())) return false;
     for (int k = 0; k < g.n_jobs; k++)
-        if (!slot_begin(g, k, imgs, on_device, false, 0)) return false;
+        if (!slot_begin(g, k, imgs, on_device, false, 0, from)) return false;
+    if (!collect_flush(g, g.stream)) return false;
     HIP_OK(hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(g.n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, g.stream));
     q_launch_model(g.d_jobs, g.h_jobs, g.n_jobs, g.stream);
     g.tm_pending = false;
@@ -1573,6 +1669,21 @@ static bool deliver_args_ok(int format, float scale, float bias) {
     return format != int(kDeliverU8) || (scale == 1.0f && bias == 0.0f);
 }
 
+// Does the runtime report [ptr, ptr + extent) as device memory of this context's device, inside ONE allocation?  What the
+// delivery asks of a destination and the collection of a source.
+static bool device_range_ok(const nblic_amd_ctx *c, const void *ptr, unsigned long long extent) {
+    hipPointerAttribute_t A;
+    void *base = nullptr;
+    size_t size = 0;
+    if (hipPointerGetAttributes(&A, ptr) != hipSuccess ||
+        hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t *>(&base), &size, const_cast<void *>(ptr)) != hipSuccess) {
+        (void)hipGetLastError();                                         // (a pointer the runtime does not know is an error to it, not to this context)
+        return false;
+    }
+    if (A.type != hipMemoryTypeDevice || A.device != c->device) return false;
+    return uintptr_t(ptr) >= uintptr_t(base) && uintptr_t(ptr) - uintptr_t(base) + extent <= size;
+}
+
 // The window destination k names in an image of h x w, and the task that fills it -- all but src, src_bytes, gate and zero,
 // which are the caller's.  false: refused, on the host, before anything of the image is launched: the window is empty or
 // outside the image, the pointer or the pitch is no multiple of the element size, the pitch is too small, the window does
@@ -1585,17 +1696,8 @@ static bool deliver_dest_task(const nblic_amd_ctx *c, const DeliverTo &to, int k
     const size_t elem = deliver_elem(to.format), rows = size_t(T.row1 - T.row0), cols = size_t(T.col1 - T.col0);
     if (!D.ptr || uintptr_t(D.ptr) % elem || D.pitch_bytes % elem || D.pitch_bytes < cols * elem || D.pitch_bytes > (size_t(1) << 40)) return false;
     const unsigned long long extent = deliver_extent(uint32_t(rows), uint32_t(cols), to.format, D.pitch_bytes);
-    if (extent > D.cap_bytes) return false;
-    hipPointerAttribute_t A;
-    void *base = nullptr;
-    size_t size = 0;
-    if (hipPointerGetAttributes(&A, D.ptr) != hipSuccess || hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t *>(&base), &size, D.ptr) != hipSuccess) {
-        (void)hipGetLastError();                                         // (a pointer the runtime does not know is an error to it, not to this context)
-        return false;
-    }
-    if (A.type != hipMemoryTypeDevice || A.device != c->device) return false;
-    if (uintptr_t(D.ptr) < uintptr_t(base) || uintptr_t(D.ptr) - uintptr_t(base) + extent > size) return false;
-    T.dst = static_cast<uint8_t *>(D.ptr); T.dst_pitch = D.pitch_bytes;
+    if (extent > D.cap_bytes || !device_range_ok(c, D.ptr, extent)) return false;
+    T.dst =static_cast<uint8_t *>(D.ptr); T.dst_pitch = D.pitch_bytes;
     T.src_pitch = uint32_t(w);
     T.format = to.format; T.scale = to.scale; T.bias = to.bias;
     return deliver_task_chunks(T) < (1ull << 31) / kDeliverChunkUnits;
@@ -1616,6 +1718,37 @@ static void deliver_zeros(std::vector<DeliverTask> &tasks, hipStream_t st) {
     DevBuf<DeliverTask> d_tasks;
     for (DeliverTask &T : tasks) { T.zero = 1; T.gate = nullptr; }
     if (d_tasks.alloc(tasks.size()) == hipSuccess && deliver_queue(tasks.data(), tasks.size(), d_tasks, st)) hipStreamSynchronize(st);
+}
+
+// ---- the sources of the _from calls, checked on the host (CollectFrom, above slot_begin) ------------------------------------
+// Source k as a task -- all but dst, px0, px1 and first_chunk, which are the launch's -- and what becomes of it.  Refused,
+// before anything of the image is launched: rows or cols the encoder does not take, a pointer, pitch or step that is no
+// multiple of the element size or is below it, a step above 2^20 or a pitch above 2^40 bytes, an extent that cap_bytes
+// does not hold, or that the runtime does not know as memory of this context's device inside one allocation.
+static uint8_t collect_src_task(const nblic_amd_ctx *c, const CollectFrom &from, int k, CollectTask &T) {
+    const nblic_amd_src &S = from.srcs[k];
+    T = CollectTask{};
+    if (!size_ok(S.rows, S.cols, c->max_px) || S.pitch_bytes > kCollectMaxPitch || S.step_bytes > kCollectMaxStep) return kSrcRefused;
+    T.src = static_cast<const uint8_t *>(S.ptr);
+    T.pitch = S.pitch_bytes; T.step = uint32_t(S.step_bytes);
+    T.rows = uint32_t(S.rows); T.cols = uint32_t(S.cols); T.px0 = 0; T.px1 = T.rows * T.cols;
+    T.format = from.format; T.scale = from.scale; T.bias = from.bias;
+    if (!collect_source_ok(T, S.cap_bytes) || !device_range_ok(c, S.ptr, collect_extent(T.rows, T.cols, T.format, T.pitch, T.step))) return kSrcRefused;
+    return collect_in_place(T.format, T.pitch, T.step, T.cols) ? kSrcInPlace : kSrcCollect;
+}
+
+// Every source of a call: how it is taken, its task, and the parent call's imgs / heights / widths.
+static void collect_plan(const nblic_amd_ctx *c, CollectFrom &from, int n) {
+    const size_t count = size_t(n);
+    from.how.assign(count, kSrcRefused); from.tasks.assign(count, CollectTask{});
+    from.imgs.assign(count, nullptr); from.hs.assign(count, 0); from.ws.assign(count, 0);
+    for (int k = 0; k < n; k++) {
+        const size_t i = size_t(k);
+        from.how[i] = collect_src_task(c, from, k, from.tasks[i]);
+        if (from.how[i] == kSrcRefused) continue;
+        from.hs[i] = from.srcs[k].rows; from.ws[i] = from.srcs[k].cols;
+        if (from.how[i] == kSrcInPlace) from.imgs[i] = from.tasks[i].src;
+    }
 }
 
 // Parses and validates the headers, uploads the streams (their lengths are known here: running dry is an error),
@@ -2788,12 +2921,14 @@ struct IdxCoder {
 struct IdxImage {                                                        // one admitted image and the index being written into the caller's buffer
     int k = 0, h = 0, w = 0, every = 0, count = 0;                       // every: 0 = no index wanted (or none possible); count: its entries
     const uint8_t *host_plane = nullptr;                                 // host input: the rows are hashed from it
+    bool on_device = false, collect = false;                             // its rows are on the device alone; a source that k_collect writes into the slot's d_img, band by band
     void *out = nullptr; size_t cap = 0;                                 // in the codec's elements
     uint8_t *index = nullptr; size_t entry_bytes = 0;
     IdxCoder nb;
 };
 struct IdxCall {
     const IdxCodec &codec; nblic_amd_ctx *c; int n; const unsigned char *const *imgs; bool on_device; int band_rows; long *lens, *ilens;
+    const CollectFrom *from;                                             // the _from calls: imgs / on_device are its own; null otherwise
     std::vector<std::unique_ptr<IdxImage>> images;                       // by position in the batch; empty: refused before the call started
     std::atomic<int> next{0};
     std::atomic<bool> failed{false};                                     // a device-side failure: the call is over
@@ -2810,11 +2945,13 @@ struct IdxCall {
 };
 struct IdxLive { IdxImage *im = nullptr; int row0 = 0, band = 0; const uint8_t *plane = nullptr; };     // the image a slot works on, rows [0, row0) queued
 
-// Image I's plane where slot s's kernels read it: a device input as it is, a host input copied into the slot on st.
+// Image I's plane where slot s's kernels read it: a device input as it is, a host input copied into the slot on st, a
+// source in the slot's d_img, where every step collects the rows of its band (idx_collect_band).
 // nullptr: the copy could not be queued.
 static const uint8_t *idx_plane(const IdxCall &q, const IdxImage &I, Slot &s, hipStream_t st) {
-    if (q.on_device) return q.imgs[I.k];
     const size_t n = size_t(I.h) * size_t(I.w);
+    if (I.collect) return s.d_img.reserve(n) == hipSuccess ? s.d_img.get() : nullptr;
+    if (I.on_device) { if (q.from) q.c->collect_counts[0]++; return q.imgs[I.k]; }
     if (s.d_img.reserve(n) != hipSuccess || hipMemcpyAsync(s.d_img, q.imgs[I.k], n, hipMemcpyHostToDevice, st) != hipSuccess) return nullptr;
     return s.d_img;
 }
@@ -2826,6 +2963,13 @@ static bool idx_band_job(nblic_amd_ctx *c, const IdxLive &L, const Slot &s, E1Jo
     jobs[j] = band_job_front(c, s.b, L.plane, L.row0, cut.rows, L.im->w, 0);
     if (cut.entry) tasks[n_tasks++] = IndexRecordTask{j, 0, (unsigned long long)(rec_at)};
     return cut.entry;
+}
+
+// The rows of job J's band, of a source, into their place in the slot's plane: a task of the step's ONE k_collect launch.
+static bool idx_collect_band(const IdxCall &q, Group &g, const IdxLive &L, const E1Job &J, size_t at) {
+    if (!L.im->collect) return true;
+    const uint32_t w = uint32_t(L.im->w), px0 = uint32_t(L.row0) * w;
+    return collect_add(g, *q.from, L.im->k, const_cast<uint8_t *>(L.plane), px0, px0 + uint32_t(J.h) * w, at);
 }
 
 // One driver thread: takes a group, runs the codec's driver on it, adds its figures to the call's.
@@ -2902,7 +3046,7 @@ static void idx_driver(IdxCall &q, Group &g, IdxSplit &sp) {
     IdxPendingTasks tasks_left;
     std::vector<int> slot_of(size_t(n_slots), 0);
     std::vector<size_t> bins_at(size_t(n_slots), 0), rec_at(size_t(n_slots), 0), rows_at(size_t(n_slots), 0);
-    bool ok = h_tasks.alloc(size_t(n_slots)) == hipSuccess && d_tasks.alloc(size_t(n_slots)) == hipSuccess;
+    bool ok = h_tasks.alloc(size_t(n_slots)) == hipSuccess && d_tasks.alloc(size_t(n_slots)) == hipSuccess && (!q.from || collect_room(g, size_t(n_slots)));
     auto grow = [](Locked &b, size_t bytes) { return bytes <= b.capacity() * 2 || b.alloc((bytes + bytes / 4 + 4096) / 2); };
     for (long t = 0; ok && !q.failed; t++) {
         // ---- which image each slot works on
@@ -2919,19 +3063,22 @@ static void idx_driver(IdxCall &q, Group &g, IdxSplit &sp) {
         if (!ok) break;
         // ---- 1. job records of the live slots, and the tasks of the bands that end on an entry row
         int n_jobs = 0, n_tasks = 0; size_t rec_bytes = 0;
-        for (int k = 0; k < n_slots; k++) {
+        collect_begin(g);
+        for (int k = 0; k < n_slots && ok; k++) {
             const IdxLive &L = live[size_t(k)];
             if (!L.im) continue;
             const bool entry = idx_band_job(c, L, g.slots[size_t(k)], g.h_jobs, n_jobs, h_tasks, n_tasks, rec_bytes);
+            ok = idx_collect_band(q, g, L, g.h_jobs[n_jobs], 0);
             rec_at[size_t(n_jobs)] = entry ? rec_bytes : SIZE_MAX;
             if (entry) rec_bytes += up256(kDecodeStateBytes + 2 * size_t(L.im->w));
             slot_of[size_t(n_jobs++)] = k;
         }
-        if (n_jobs == 0) break;
+        if (n_jobs == 0 || !ok) break;
         hipEvent_t *ev = g.tm.ev;                                        // marks of the step's five parts
         ok = hipMemcpyAsync(g.d_jobs, g.h_jobs, size_t(n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, st) == hipSuccess;
         if (!ok) break;
         hipEventRecord(ev[0], st);
+        if (!(ok = collect_flush(g, st))) break;                         // the bands of the sources: one launch
         // ---- 2. / 3. fresh tables for the jobs that start an image, then the front half of every band
         for (int j = 0; j < n_jobs; j++) if (g.h_jobs[j].row0 == 0) e1_launch_init(g.d_jobs + j, 1, st);
         e1_launch_front_band(g.d_jobs, g.h_jobs, n_jobs, st);
@@ -2950,7 +3097,7 @@ static void idx_driver(IdxCall &q, Group &g, IdxSplit &sp) {
             bins_at[size_t(j)] = n_bins;
             n_bins += (size_t(n_ev) + 64 + 63) & ~size_t(63);
             rows_at[size_t(j)] = rows_bytes;
-            if (q.on_device && live[size_t(k)].im->every) rows_bytes += size_t(g.h_jobs[j].n);
+            if (live[size_t(k)].im->on_device && live[size_t(k)].im->every) rows_bytes += size_t(g.h_jobs[j].n);
         }
         if (!ok) break;
         Set &S = sets[t & 1];                                            // free: the tasks of step t - 2 ended before step t - 1 was handed over
@@ -2975,8 +3122,8 @@ static void idx_driver(IdxCall &q, Group &g, IdxSplit &sp) {
         ok = hipMemcpyAsync(static_cast<uint16_t *>(S.bins), d_bins, n_bins * sizeof(uint16_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
              (!rec_bytes || hipMemcpyAsync(static_cast<uint16_t *>(S.recs), d_recs, rec_bytes, hipMemcpyDeviceToHost, st) == hipSuccess);
         uint8_t *const rows_host = reinterpret_cast<uint8_t *>(static_cast<uint16_t *>(S.rows));
-        for (int j = 0; j < n_jobs && ok && q.on_device; j++)
-            if (live[size_t(slot_of[size_t(j)])].im->every)
+        for (int j = 0; j < n_jobs && ok; j++)
+            if (live[size_t(slot_of[size_t(j)])].im->on_device && live[size_t(slot_of[size_t(j)])].im->every)
                 ok = hipMemcpyAsync(rows_host + rows_at[size_t(j)], g.h_jobs[j].b.img, size_t(g.h_jobs[j].n), hipMemcpyDeviceToHost, st) == hipSuccess;
         hipEventRecord(ev[5], st);
         if (!ok || hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) { ok = false; break; }
@@ -2995,7 +3142,7 @@ static void idx_driver(IdxCall &q, Group &g, IdxSplit &sp) {
             IdxLive &L = live[size_t(slot_of[size_t(j)])];
             IdxImage *I = L.im;
             const int rows = g.h_jobs[j].h;
-            const uint8_t *rows_src = !I->every ? nullptr : q.on_device ? rows_host + rows_at[size_t(j)] : I->host_plane + size_t(L.row0) * size_t(I->w);
+            const uint8_t *rows_src = !I->every ? nullptr : I->on_device ? rows_host + rows_at[size_t(j)] : I->host_plane + size_t(L.row0) * size_t(I->w);
             const IdxBand b{I, L.row0, rows, static_cast<uint16_t *>(S.bins) + bins_at[size_t(j)], g.h_jobs[j].n_ev, rows_src,
                             rec_at[size_t(j)] == SIZE_MAX ? nullptr : recs_host + rec_at[size_t(j)], L.row0 + rows >= I->h};
             q.pool.post([&q, &tasks_left, b] { idx_code_band(q, b); tasks_left.done(); });
@@ -3103,6 +3250,7 @@ static void qidx_driver(IdxCall &q, Group &g, IdxSplit &sp) {
              g.qidx_d_recs.alloc(size_t(n_slots) * rec_room) == hipSuccess;
         if (!ok) { g.qidx_bufs.clear(); g.qidx_ready.clear(); }
     }
+    ok = ok && (!q.from || collect_room(g, size_t(kQIdxDepth) * size_t(n_slots)));
     for (int b = 0; ok && b < n_bufs; b++) bufs->free.push_back(b);
     hipEvent_t *ev = g.tm.ev;                                            // four marks a queued step
     // Step t - kQIdxDepth has left the GPU: its ring entry is free, its marks and its block counts are read.
@@ -3132,12 +3280,12 @@ static void qidx_driver(IdxCall &q, Group &g, IdxSplit &sp) {
             L.buf = bufs->take();                                         // every buffer out: the workers are behind
             sp.ms[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
             L.im = I; L.row0 = 0;
-            L.lay = qidx_layout(*I, q.on_device && I->every);
+            L.lay = qidx_layout(*I, I->on_device && I->every);
             Locked &B = g.qidx_bufs[size_t(L.buf)];
             L.band = encoder_band_rows(q.band_rows, I->h, I->w, 1);
             const size_t n = size_t(I->h) * size_t(I->w), band_px = size_t(L.band) * size_t(I->w);
             // a workspace that has to grow is still read by the steps in the queue
-            if ((band_px > s.px_cap || (!q.on_device && n > s.d_img.capacity())) && hipStreamSynchronize(st) != hipSuccess) { ok = false; break; }
+            if ((band_px > s.px_cap || ((!I->on_device || I->collect) && n > s.d_img.capacity())) && hipStreamSynchronize(st) != hipSuccess) { ok = false; break; }
             if (!(ok = (L.lay.bytes <= B.capacity() * 2 || B.alloc((L.lay.bytes + L.lay.bytes / 8 + 4096) / 2)) && ensure_pixels(s, band_px, false) &&
                        (L.plane = idx_plane(q, *I, s, st)) != nullptr)) break;
         }
@@ -3146,19 +3294,23 @@ static void qidx_driver(IdxCall &q, Group &g, IdxSplit &sp) {
         E1Job *const hj = g.qidx_jobs + size_t(e) * size_t(n_slots);
         IndexRecordTask *const ht = g.qidx_tasks + size_t(e) * size_t(n_slots);
         int n_jobs = 0, n_tasks = 0;
-        for (int k = 0; k < n_slots; k++) {
+        const size_t ct_at = size_t(e) * size_t(n_slots);                // the step's stretch of the group's collect tasks
+        collect_begin(g);
+        for (int k = 0; k < n_slots && ok; k++) {
             const Live &L = live[size_t(k)];
             if (!L.im) continue;
             const size_t at = size_t(n_tasks) * rec_room;
             rec_at[size_t(n_jobs)] = idx_band_job(c, L, g.slots[size_t(k)], hj, n_jobs, ht, n_tasks, at) ? at : SIZE_MAX;
+            ok = idx_collect_band(q, g, L, hj[n_jobs], ct_at);
             ring_slot[size_t(e) * size_t(n_slots) + size_t(n_jobs)] = k;
             slot_of[size_t(n_jobs++)] = k;
         }
-        if (n_jobs == 0) break;
+        if (n_jobs == 0 || !ok) break;
         ok = hipMemcpyAsync(g.d_jobs, hj, size_t(n_jobs) * sizeof(E1Job), hipMemcpyHostToDevice, st) == hipSuccess &&
              (!n_tasks || hipMemcpyAsync(g.qidx_d_tasks, ht, size_t(n_tasks) * sizeof(IndexRecordTask), hipMemcpyHostToDevice, st) == hipSuccess);
         if (!ok) break;
         hipEventRecord(ev[4 * e], st);
+        if (!(ok = collect_flush(g, st, ct_at))) break;                  // the bands of the sources: one launch
         // ---- 2. the model stage of every band, 3. the decoder records
         q_launch_model_band(g.d_jobs, hj, n_jobs, st);
         hipEventRecord(ev[4 * e + 1], st);
@@ -3205,20 +3357,23 @@ static const IdxCodec kIdxQnblic{1, 0, 6, size_t(1) << 45, qidx_driver};        
 
 template <class Out>                                                     // unsigned char or uint16_t: what the codec's lengths count
 static int indexed_batch(const IdxCodec &F, nblic_amd_ctx *c, int n, const unsigned char *const *imgs, bool on_device, const int *hs, const int *ws, const int *every,
-                         int band_rows, Out *const *outs, const size_t *caps, long *lens, unsigned char *const *indexes, const size_t *icaps, long *ilens) {
+                         int band_rows, Out *const *outs, const size_t *caps, long *lens, unsigned char *const *indexes, const size_t *icaps, long *ilens,
+                         const CollectFrom *from = nullptr) {
+    // `from`: imgs / on_device / hs / ws are collect_plan's (an image it refused is 0 x 0 and has no plane)
     if (!c || c->broken || n < 1 || !imgs || !hs || !ws || !every || !outs || !caps || !lens || (indexes && (!icaps || !ilens))) return -1;
-    for (int k = 0; k < n; k++) if (every[k] < 0 || !imgs[k] || !outs[k]) return -1;
+    for (int k = 0; k < n; k++) if (every[k] < 0 || (!from && !imgs[k]) || !outs[k]) return -1;
     if (hipSetDevice(c->device) != hipSuccess) return -1;
-    IdxCall q{F, c, n, imgs, on_device, band_rows, lens, ilens};
+    IdxCall q{F, c, n, imgs, on_device, band_rows, lens, ilens, from};
     q.images.resize(size_t(n));
     int n_live = 0;
     for (int k = 0; k < n; k++) {                                        // what can be refused is refused before anything is launched
         lens[k] = -1;
-        if (ilens) ilens[k] = 0;
+        if (ilens) ilens[k] = from && from->how[size_t(k)] == kSrcRefused ? -1 : 0;       // (a refused source: no stream and no index)
         if (!size_ok(hs[k], ws[k], c->max_px) || caps[k] < F.min_out) continue;
         auto I = std::make_unique<IdxImage>();
         I->k = k; I->h = hs[k]; I->w = ws[k]; I->out = outs[k]; I->cap = std::min(caps[k], F.max_out);
         I->host_plane = on_device ? nullptr : imgs[k];
+        I->on_device = on_device; I->collect = from && from->how[size_t(k)] == kSrcCollect;
         if (indexes && indexes[k]) {
             const IndexAdmission A = index_admit(F.kind, F.effort, hs[k], ws[k], every[k], icaps[k]);
             if (A.too_small) ilens[k] = -1;                              // the stream is still delivered
@@ -4721,6 +4876,107 @@ int nblic_amd_debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const 
     return 0;
 }
 
+// ---- k_collect on caller-made sources (tests/test_encode_from_device.py), and its host walk (tests/test_collect_host.py) ------
+static bool debug_collect_task(CollectTask &T, const void *src, int rows, int cols, int format, float scale, float bias, size_t pitch, size_t step, const int *range) {
+    if (!deliver_args_ok(format, scale, bias) || rows < 1 || cols < 1 || rows > int(kCollectMaxSide) || cols > int(kCollectMaxSide) || step > kCollectMaxStep) return false;
+    T = CollectTask{};
+    T.src = static_cast<const uint8_t *>(src);
+    T.pitch = pitch; T.step = uint32_t(step);
+    T.rows = uint32_t(rows); T.cols = uint32_t(cols);
+    T.px0 = range ? uint32_t(range[0]) : 0u; T.px1 = range && range[1] ? uint32_t(range[1]) : T.rows * T.cols;
+    T.format = uint32_t(format); T.scale = scale; T.bias = bias;
+    return !range || (range[0] >= 0 && range[1] >= 0);
+}
+
+// Host only: the shared unit walk (collect.h collect_host) over the source at src -- cap_bytes readable from there -- into
+// the plane at out, which must be a multiple of 16 and hold rows x cols bytes.  range: the pixels [px0, px1) of the flat plane
+// (NULL: all of it; px1 == 0: to the end).  -1: refused.
+int nblic_amd_debug_collect_host(const void *src, size_t cap_bytes, int rows, int cols, size_t pitch_bytes, size_t step_bytes, int format, float scale,
+                                 float bias, const int *range, unsigned char *out, size_t out_bytes, unsigned long long *units, unsigned long long *chunks) {
+    CollectTask T;
+    if (!src || !out || !debug_collect_task(T, src, rows, cols, format, scale, bias, pitch_bytes, step_bytes, range)) return -1;
+    T.dst = out;
+    if (!collect_task_ok(T, cap_bytes) || size_t(T.rows) * size_t(T.cols) > out_bytes) return -1;
+    if (units) *units = collect_task_units(T);
+    if (chunks) *chunks = collect_task_chunks(T);
+    collect_host(T);
+    return 0;
+}
+
+// ONE k_collect launch over n caller-made sources as n tasks.  The bytes of source k (src_bytes[k] of them) are uploaded at
+// byte base_offsets[k] (0 .. 255) of a region filled with 0xFF -- NaN in every float format, 255 as a pixel -- that is larger;
+// the image's element (0, 0) is the first of them.  Plane k (rows x cols bytes) lies at byte 256 of a region filled with
+// 0x5A, which comes back whole in outs[k]: out_bytes[k] = 256 + up256(rows x cols) + 256.  ranges: two ints per task
+// (px0, px1; px1 == 0: to the end) or NULL.  -1: refused; -2: a HIP call failed.
+int nblic_amd_debug_collect(nblic_amd_ctx *c, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets, const int *rows,
+                            const int *cols, const size_t *pitches, const size_t *steps, const int *formats, const float *scales, const float *biases,
+                            const int *ranges, unsigned char *const *outs, const size_t *out_bytes) {
+    constexpr int kMaxTasks = 65536;
+    constexpr size_t kGuard = 256;
+    if (!c || n < 1 || n > kMaxTasks || !srcs || !src_bytes || !base_offsets || !rows || !cols || !pitches || !steps || !formats || !scales || !biases || !outs || !out_bytes) return -1;
+    const size_t count = size_t(n);
+    std::vector<CollectTask> tasks(count);
+    std::vector<size_t> src_at(count), out_at(count);
+    size_t srcs_total = 0, outs_total = 0;
+    for (int k = 0; k < n; k++) {
+        const size_t i = size_t(k);
+        if (!srcs[k] || !outs[k] || base_offsets[k] > 255 || src_bytes[k] > (size_t(1) << 30) ||
+            !debug_collect_task(tasks[i], nullptr, rows[k], cols[k], formats[k], scales[k], biases[k], pitches[k], steps[k], ranges ? ranges + 2 * i : nullptr)) return -1;
+        const size_t plane = size_t(rows[k]) * size_t(cols[k]);
+        if (plane > (size_t(1) << 30) || out_bytes[k] != kGuard + up256(plane) + kGuard) return -1;
+        src_at[i] = srcs_total; srcs_total += up256(base_offsets[k] + src_bytes[k] + 256);
+        out_at[i] = outs_total; outs_total += out_bytes[k];
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    Stream st;
+    DevPool mem;
+    uint8_t *d_srcs = mem.make<uint8_t>(srcs_total), *d_outs = mem.make<uint8_t>(outs_total);
+    CollectTask *d_tasks = mem.make<CollectTask>(count);
+    if (!d_srcs || !d_outs || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    unsigned long long chunks = 0;
+    for (int k = 0; k < n; k++) {                                        // the addresses are known now: the rest of the checks
+        const size_t i = size_t(k);
+        CollectTask &T = tasks[i];
+        T.src = d_srcs + src_at[i] + base_offsets[k];
+        T.dst = d_outs + out_at[i] + kGuard;
+        if (!collect_task_ok(T, src_bytes[k])) return -1;                // nothing outside the uploaded bytes is the task's to read
+        T.first_chunk = uint32_t(chunks); chunks += collect_task_chunks(T);
+    }
+    if (chunks >= (1ull << 31)) return -1;
+    std::vector<uint8_t> back(outs_total);
+    const bool ok = [&]() -> bool {
+        HIP_OK(hipMemsetAsync(d_srcs, 0xFF, srcs_total, st));
+        HIP_OK(hipMemsetAsync(d_outs, 0x5A, outs_total, st));
+        for (int k = 0; k < n; k++)
+            HIP_OK(hipMemcpyAsync(d_srcs + src_at[size_t(k)] + base_offsets[k], srcs[k], src_bytes[k], hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_tasks, tasks.data(), count * sizeof(CollectTask), hipMemcpyHostToDevice, st));
+        if (!collect_launch(d_tasks, n, uint32_t(chunks), st)) return false;
+        HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    if (!ok) return -2;
+    for (int k = 0; k < n; k++) memcpy(outs[k], back.data() + out_at[size_t(k)], out_bytes[k]);
+    return 0;
+}
+
+// Call it when nothing is outstanding on the context: it reads the groups' marks.
+int nblic_amd_collect_ms(nblic_amd_ctx *c, double *ms, long *timed_launches) {
+    if (!c || !ms || !timed_launches || hipSetDevice(c->device) != hipSuccess) return -1;
+    std::lock_guard<std::mutex> g(c->api);
+    for (auto &grp : c->groups) collect_timing_read(grp, true);
+    std::lock_guard<std::mutex> l(c->stat_m);
+    *ms = c->collect_ms; *timed_launches = c->collect_timed;
+    return 0;
+}
+
+int nblic_amd_collect_stats(nblic_amd_ctx *c, long out[4]) {
+    if (!c || !out) return -1;
+    for (int k = 0; k < 4; k++) out[k] = c->collect_counts[k].load();
+    return 0;
+}
+
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
 
 int nblic_amd_copy_stats(nblic_amd_ctx *c, long out[4]) {
@@ -4998,6 +5254,50 @@ int nblic_amd_qencode_batch_indexed(nblic_amd_ctx *c, int n_images, const unsign
                                     unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
     return indexed_batch(kIdxQnblic, c, n_images, imgs, imgs_on_device != 0, heights, widths, every_rows, band_rows, outs, out_caps_words, out_len_words, indexes, index_caps, index_lens);
 }
+
+// ---- ENCODE FROM DEVICE MEMORY: the four batch encoders on sources instead of planes ------------------------------------------
+// What every _from call starts with: the whole-call refusals, then the sources checked one by one (collect_plan).
+static bool collect_from_begin(nblic_amd_ctx *c, int n, const nblic_amd_src *srcs, int format, float scale, float bias, CollectFrom &from) {
+    if (!c || c->broken || n < 0 || !srcs || !deliver_args_ok(format, scale, bias) || hipSetDevice(c->device) != hipSuccess) return false;
+    from.srcs = srcs; from.format = uint32_t(format); from.scale = scale; from.bias = bias;
+    collect_plan(c, from, n);
+    return true;
+}
+
+int nblic_amd_encode_batch_modes_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                      const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
+                                      unsigned char *const *recons) {
+    CollectFrom from{};
+    if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from)) return -1;
+    const bool ok = run_batch(c, nblic_amd_ctx::SubmitItem{nullptr, 0, n_images, from.imgs.data(), true, from.hs.data(), from.ws.data(), outs, out_caps, out_lens, nears, efforts, recons, &from});
+    if (nothing_outstanding(c)) for (auto &g : c->groups) collect_timing(c, g);       // (nblic_amd_stage_times, as nblic_amd_encode_batch leaves them)
+    return ok ? 0 : -1;
+}
+int nblic_amd_qencode_batch_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                 uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words) {
+    CollectFrom from{};
+    if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from)) return -1;
+    return run_batch(c, nblic_amd_ctx::SubmitItem{nullptr, 1, n_images, from.imgs.data(), true, from.hs.data(), from.ws.data(), reinterpret_cast<unsigned char *const *>(outs),
+                                                  out_caps_words, out_len_words, nullptr, nullptr, nullptr, &from}) ? 0 : -1;
+}
+extern "C++" template <class Out>
+static int indexed_batch_from(const IdxCodec &F, nblic_amd_ctx *c, int n, const nblic_amd_src *srcs, int format, float scale, float bias, const int *every, int band_rows,
+                              Out *const *outs, const size_t *caps, long *lens, unsigned char *const *indexes, const size_t *icaps, long *ilens) {
+    CollectFrom from{};
+    if (n < 1 || !collect_from_begin(c, n, srcs, format, scale, bias, from)) return -1;
+    return indexed_batch(F, c, n, from.imgs.data(), true, from.hs.data(), from.ws.data(), every, band_rows, outs, caps, lens, indexes, icaps, ilens, &from);
+}
+int nblic_amd_encode_batch_indexed_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                        const int *every_rows, int band_rows, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
+                                        unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
+    return indexed_batch_from(kIdxNblic, c, n_images, srcs, format, scale, bias, every_rows, band_rows, outs, out_caps, out_lens, indexes, index_caps, index_lens);
+}
+int nblic_amd_qencode_batch_indexed_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                         const int *every_rows, int band_rows, uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words,
+                                         unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
+    return indexed_batch_from(kIdxQnblic, c, n_images, srcs, format, scale, bias, every_rows, band_rows, outs, out_caps_words, out_len_words, indexes, index_caps, index_lens);
+}
+
 long nblic_amd_debug_q_entropy(int height, int width, const uint16_t *words, const unsigned int *hist, const int *entry_rows, int n_entries,
                                uint16_t *out, size_t cap_words, unsigned int *states, unsigned long long *words_emitted) {
     if (!words || !hist || !out || n_entries < 0 || (n_entries > 0 && (!entry_rows || !states || !words_emitted))) return -2;

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "deliver.h"
+#include "collect.h"
 
 namespace nblic {
 
@@ -192,6 +193,14 @@ bool index_capture_launch(const IndexCaptureTask *d_tasks, int n, uint32_t chunk
 // round-to-nearest-even into the format.  A task with `zero`, or whose gate record is not kDone, writes zero bytes.
 // d_tasks[0..n) with first_chunk filled in (from 0), `chunks` their sum.  false: the launch failed.
 bool deliver_launch(const DeliverTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
+
+// ---- collection: images out of caller-owned device memory into the encoders' contiguous planes (collect.h) -------------------
+// k_collect, the delivery's twin: tasks with first_chunk, one workgroup per chunk of kCollectChunkUnits units, a unit =
+// sixteen consecutive bytes of the flat plane at a multiple of 16.  The source has any pitch and any step between the pixels
+// of a row; uint8 is a copy, float16 / bfloat16 / float32 are float(x) * scale + bias, two roundings, NaN to 0, clamped to
+// [0, 255] and rounded to nearest even.  d_tasks[0..n) with first_chunk filled in (from 0), `chunks` their sum.
+// false: the launch failed.
+bool collect_launch(const CollectTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
 
 // ---- a packed index (index_pack.h), expanded on the device ------------------------------------------------------------------
 // A packed index is uploaded as it is (any address).  The bodies of the entries a round needs are written, unpacked, into an

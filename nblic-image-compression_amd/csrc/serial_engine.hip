@@ -1873,6 +1873,73 @@ bool deliver_launch(const DeliverTask *d_tasks, int n, uint32_t chunks, hipStrea
     return hipGetLastError() == hipSuccess;
 }
 
+// ---- collection: images out of caller-owned device memory into the encoders' planes (collect.h CollectTask) ------------------
+static_assert(kCollectChunkUnits == kIndexChunkUnits, "collect.h states it for host-only code");
+
+// One workgroup per chunk of kCollectChunkUnits units, one unit per lane and step: sixteen consecutive bytes of the flat
+// plane (collect.h).  A unit whose sixteen source elements are neighbours in one row at a multiple of four bytes is read
+// in aligned words, every other one element by element: no byte is read that is not part of an element of the image.  A
+// whole unit is one 16-byte store; the shorter first and last units of a task are written in words and bytes.  No LDS, no
+// atomics; nothing is written outside the task's pixels [px0, px1).
+__global__ void __launch_bounds__(kIndexThreads) k_collect(const CollectTask *__restrict__ tasks, int n) {
+    const CollectTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
+    const uint32_t units = collect_task_units(T), u0 = (blockIdx.x - T.first_chunk) * kCollectChunkUnits;
+    const uint32_t elem = collect_elem(T.format);
+    const NB_GLOBAL uint8_t *src = gp(T.src);
+    for (uint32_t j = threadIdx.x; j < kCollectChunkUnits; j += kIndexThreads) {
+        const uint32_t u = u0 + j;
+        if (u >= units) break;
+        const CollectUnit U = collect_unit_of(T, u);
+        const uint32_t k_lo = U.p_lo - U.p0, k_hi = U.p_hi - U.p0;
+        uint32_t row = U.p_lo / T.cols, col = U.p_lo - row * T.cols;
+        const NB_GLOBAL uint8_t *s = src + collect_src_at(T, row, col);
+        uint32_t word[4] = {0u, 0u, 0u, 0u};
+        if (T.step == elem && k_hi - k_lo == 16 && T.cols - col >= 16 && !(uintptr_t(s) & 3)) {
+            const NB_GLOBAL uint32_t *q = (const NB_GLOBAL uint32_t *)s;
+            if (elem == 1) {
+#pragma unroll
+                for (int i = 0; i < 4; i++) word[i] = q[i];
+            } else if (elem == 2) {
+#pragma unroll
+                for (uint32_t i = 0; i < 8; i++) {
+                    const uint32_t x = q[i];
+                    word[i >> 1] |= (collect_value(x & 0xFFFFu, T.format, T.scale, T.bias) | (collect_value(x >> 16, T.format, T.scale, T.bias) << 8)) << ((i & 1) * 16);
+                }
+            } else {
+#pragma unroll
+                for (uint32_t i = 0; i < 16; i++) word[i >> 2] |= collect_value(q[i], kCollectF32, T.scale, T.bias) << ((i & 3) * 8);
+            }
+            *(NB_GLOBAL u32x4 *)(gp(T.dst) + U.p0) = u32x4{word[0], word[1], word[2], word[3]};
+            continue;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 16; k++) {
+            if (k < k_lo || k >= k_hi) continue;
+            uint32_t x;
+            if (elem == 1) x = *s;
+            else if (elem == 2) x = *(const NB_GLOBAL uint16_t *)s;
+            else x = *(const NB_GLOBAL uint32_t *)s;
+            word[k >> 2] |= collect_value(x, T.format, T.scale, T.bias) << ((k & 3) * 8);
+            if (++col == T.cols) { col = 0; row++; s = src + collect_src_at(T, row, 0); } else s += T.step;
+        }
+        NB_GLOBAL uint8_t *d = gp(T.dst) + U.p0;
+        if (k_hi - k_lo == 16) { *(NB_GLOBAL u32x4 *)d = u32x4{word[0], word[1], word[2], word[3]}; continue; }
+#pragma unroll
+        for (uint32_t b = 0; b < 4; b++) {
+            if (k_lo <= 4 * b && 4 * b + 4 <= k_hi) { ((NB_GLOBAL uint32_t *)d)[b] = word[b]; continue; }
+#pragma unroll
+            for (uint32_t k = 4 * b; k < 4 * b + 4; k++)
+                if (k >= k_lo && k < k_hi) d[k] = uint8_t(word[b] >> ((k & 3) * 8));
+        }
+    }
+}
+
+bool collect_launch(const CollectTask *d_tasks, int n, uint32_t chunks, hipStream_t s) {
+    if (n <= 0 || chunks == 0) return true;
+    hipLaunchKernelGGL(k_collect, dim3(chunks), dim3(kIndexThreads), 0, s, d_tasks, n);
+    return hipGetLastError() == hipSuccess;
+}
+
 
 // ---- a packed index, expanded on the device (serial_engine.h IndexUnpackTask; the format: index_pack.h) --------------------
 constexpr uint32_t kUnpackWaves = kIndexThreads / 64;
