@@ -527,6 +527,41 @@ int nblic_amd_decode_batch_to(nblic_amd_ctx *ctx, int n_images, const unsigned c
                               const nblic_amd_dest *dests, int format, float scale, float bias, int *heights, int *widths,
                               int *nears, int *efforts, int *status);
 
+/* DECODE TO ANY DEVICE LAYOUT: the two calls above with a destination that has, like a source of the _from calls below, a
+ * step between the elements of a row, and its own normalisation -- the colours of a uint8 [N, H, W, 3] batch, or the
+ * channels of a channels-last float16 tensor with a mean and a std per channel, are written where they lie.
+ *   the destination element (r, c) of the window goes to ptr + r x pitch_bytes + c x step_bytes, as float(px) x scale + bias
+ *                   in the call's format (above).  Nothing else is written: the bytes between the elements and the pitch
+ *                   gaps keep their contents.  step_bytes == element size is the destination of the calls above, with their
+ *                   rule (pitch_bytes >= the window's row).  step_bytes > element size is a STRIDED destination: it may
+ *                   have any pitch_bytes, so a transposed view works.
+ *   per image       REFUSED, with its destination not written and the other images unaffected: what the calls above
+ *                   refuse, and a destination whose ptr, pitch_bytes or step_bytes is no multiple of the element size or is
+ *                   below it; step_bytes > 2^20 or pitch_bytes > 2^40; (rows - 1) x pitch_bytes + (cols - 1) x step_bytes
+ *                   + element size > cap_bytes or beyond the end of the allocation ptr lies in; a scale or bias that is
+ *                   not finite; uint8 with scale != 1 or bias != 0.
+ *   whole call      -1 with nothing launched: what the host call refuses, a NULL dests, an unknown format.
+ * The two calls above ARE these calls, with step_bytes = element size and the call's scale / bias in every destination
+ * (their whole-call -1 for a scale or bias they refuse stays).  One k_deliver launch carries contiguous and strided
+ * destinations mixed.
+ * nblic_amd_deliver_stats: out[0] the delivery tasks that the last call on this context that delivers (the four _to calls,
+ * nblic_amd_encode_batch_modes_from_to, nblic_amd_debug_deliver, nblic_amd_debug_deliver_ex) queued, out[1] the strided ones among them.  0, -1 for a null pointer. */
+typedef struct nblic_amd_dest_ex {
+    void  *ptr;          /* device memory on the context's device                              */
+    size_t pitch_bytes;  /* between rows                                                       */
+    size_t step_bytes;   /* between neighbouring elements of a row (element size: contiguous)  */
+    size_t cap_bytes;    /* writable bytes from ptr                                            */
+    int    row0, row1, col0, col1;   /* the window; row1 == 0 / col1 == 0: to the image's last row / column */
+    float  scale, bias;  /* float formats: float(px) x scale + bias; uint8: 1 and 0            */
+} nblic_amd_dest_ex;
+int nblic_amd_decode_batch_indexed_to_ex(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                         const void *const *indexes, const size_t *index_lens, const nblic_amd_dest_ex *dests, int format,
+                                         int *heights, int *widths, int *nears, int *efforts, int *status);
+int nblic_amd_decode_batch_to_ex(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                 const nblic_amd_dest_ex *dests, int format, int *heights, int *widths, int *nears, int *efforts,
+                                 int *status);
+int nblic_amd_deliver_stats(nblic_amd_ctx *ctx, long out[2]);
+
 /* ENCODE FROM DEVICE MEMORY: the batch encoders on images that lie in caller-owned device memory in ANY layout -- a crop
  * of a larger frame, a pitched surface, one channel of an [N, C, H, W] tensor, one colour of an interleaved H x W x 3 frame
  * -- as pixels or as floats that are quantised to 8 bits on the way.  The counterpart of the two calls above: a batch goes
@@ -559,7 +594,7 @@ int nblic_amd_decode_batch_to(nblic_amd_ctx *ctx, int n_images, const unsigned c
  * host buffers), nblic_amd_qencode_batch, nblic_amd_encode_batch_indexed, nblic_amd_qencode_batch_indexed -- with srcs,
  * format, scale, bias in place of imgs, imgs_on_device, heights, widths, and returns byte for byte what the parent returns
  * for the collected planes, indexes included.  There is no asynchronous _begin / _end pair and no nblic_amd_stream_* on
- * sources, and reconstructions are not delivered to device memory.
+ * sources; reconstructions go to device memory by nblic_amd_encode_batch_modes_from_to.
  * nblic_amd_collect_stats: since the context was created, out[0] images used in place, [1] images collected, [2] k_collect
  * launches, [3] pixels collected.  Returns 0, -1 for a null pointer.
  * nblic_amd_collect_ms: while nblic_amd_enable_timing is on, a k_collect launch stands between two events of its group;
@@ -578,6 +613,25 @@ int nblic_amd_encode_batch_modes_from(nblic_amd_ctx *ctx, int n_images, const nb
                                       long *out_lens, unsigned char *const *recons);
 int nblic_amd_qencode_batch_from(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
                                  uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words);
+/* RECONSTRUCTIONS TO DEVICE MEMORY: nblic_amd_encode_batch_modes_from with, in place of the host recons, one
+ * nblic_amd_dest_ex per image (above: window, pitch, step, scale and bias as for a decode) and their format: the plane a
+ * decoder of the stream produces goes to the caller's device memory next to the source, and no plane reaches the host.
+ * A destination with a NULL ptr asks for no reconstruction of its image.
+ *   what is delivered  near > 0: the reconstruction the model stage keeps on the device.  near == 0: the plane that was
+ *                   encoded -- the collected one, or the source where it lies.
+ *   delivery        after the model stage of a group's images, ONE k_deliver launch on the group's own stream.  In the serial
+ *                   modes (near > 0, or effort 2 / 3) a task is gated by the model's record: an image that fails there
+ *                   leaves zeros in its window.
+ *   per image       a destination that the _to_ex calls would refuse costs THAT IMAGE'S RECONSTRUCTION ONLY: it is not
+ *                   written, and the image's stream is written as if none had been asked for.  A refused source has neither.
+ *   whole call      -1 with nothing launched: what nblic_amd_encode_batch_modes_from refuses, a NULL recons, an unknown
+ *                   recon_format.
+ * The streams are byte for byte those of nblic_amd_encode_batch_modes_from.  nblic_amd_deliver_stats counts the call's
+ * tasks.  There is no such call for QNBLIC (lossless: the reconstruction is the source), the indexed encoders or
+ * _begin / _end. */
+int nblic_amd_encode_batch_modes_from_to(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                         const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps,
+                                         long *out_lens, const nblic_amd_dest_ex *recons, int recon_format);
 int nblic_amd_encode_batch_indexed_from(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale,
                                         float bias, const int *every_rows, int band_rows, unsigned char *const *outs,
                                         const size_t *out_caps, long *out_lens, unsigned char *const *indexes,
@@ -900,6 +954,20 @@ int nblic_amd_debug_deliver(nblic_amd_ctx *ctx, int n, const unsigned char *cons
                             const size_t *base_offsets, const int *plane_rows, const int *widths, const int *windows,
                             const int *formats, const float *scales, const float *biases, const int *zeros, const size_t *pitches,
                             const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs, const int *gate_status);
+/* The two hooks above with a destination step: step_bytes / steps[k] are the bytes between neighbouring elements of a
+ * destination row.  The element size is the task of the hooks above, byte for byte; anything larger is a strided task
+ * (csrc/deliver.h): element (r, c) of the window goes to r x pitch + c x step from the destination's offset, units are
+ * sixteen consecutive pixels of a row -- rows x ((cols + 15) / 16) of them -- and the pitch may be anything from the element
+ * size up.  They refuse (-1) as above, and a step that is no multiple of the element size, is below it or above 2^20, and
+ * a window whose last element, at (rows - 1) x pitch + (cols - 1) x step, does not fit the output buffer. */
+int nblic_amd_debug_deliver_host_ex(const unsigned char *plane, int plane_rows, int width, const int *window, int format, float scale,
+                                    float bias, int zero, int gate_status, unsigned char *out, size_t out_bytes, size_t dst_offset,
+                                    size_t pitch_bytes, size_t step_bytes, unsigned long long *units, unsigned long long *chunks);
+int nblic_amd_debug_deliver_ex(nblic_amd_ctx *ctx, int n, const unsigned char *const *planes, const size_t *plane_bytes,
+                               const size_t *base_offsets, const int *plane_rows, const int *widths, const int *windows,
+                               const int *formats, const float *scales, const float *biases, const int *zeros, const size_t *pitches,
+                               const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs,
+                               const int *gate_status);
 
 /* Debug hooks used by the collection's tests (the _from encoders), the twins of the two above.  A task is a source -- its
  * bytes, the image's rows x cols, a pitch and a step in bytes, a format with its scale and bias -- and optionally a range of

@@ -53,6 +53,8 @@ EXPORTS = (
     "nblic_amd_index_build_batch", "nblic_amd_index_build_split", "nblic_amd_index_build_plan", "nblic_amd_debug_index_capture",
     "nblic_amd_index_pack", "nblic_amd_index_pack_bound", "nblic_amd_index_unpack", "nblic_amd_index_unpacked_bytes", "nblic_amd_index_is_packed", "nblic_amd_debug_index_unpack",
     "nblic_amd_decode_batch_indexed_to", "nblic_amd_decode_batch_to", "nblic_amd_debug_deliver_host", "nblic_amd_debug_deliver",
+    "nblic_amd_decode_batch_indexed_to_ex", "nblic_amd_decode_batch_to_ex", "nblic_amd_deliver_stats", "nblic_amd_debug_deliver_host_ex", "nblic_amd_debug_deliver_ex",
+    "nblic_amd_encode_batch_modes_from_to",
     "nblic_amd_encode_batch_modes_from", "nblic_amd_qencode_batch_from", "nblic_amd_encode_batch_indexed_from", "nblic_amd_qencode_batch_indexed_from",
     "nblic_amd_collect_stats", "nblic_amd_collect_ms", "nblic_amd_debug_collect_host", "nblic_amd_debug_collect",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
@@ -256,6 +258,22 @@ def load_library() -> C.CDLL:
                                                      C.c_size_t, C.c_size_t, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
         lib.nblic_amd_debug_deliver.restype = C.c_int
         lib.nblic_amd_debug_deliver.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, ip, ip, ip, ip, fp, fp, ip, szp, szp, szp, vpp, ip]
+    if hasattr(lib, "nblic_amd_decode_batch_to_ex"):
+        ip = C.POINTER(C.c_int)
+        vpp, szp, fp, xp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(DestEx)
+        lib.nblic_amd_decode_batch_indexed_to_ex.restype = C.c_int
+        lib.nblic_amd_decode_batch_indexed_to_ex.argtypes = [C.c_void_p, C.c_int, vpp, szp, vpp, szp, xp, C.c_int] + [ip] * 5
+        lib.nblic_amd_decode_batch_to_ex.restype = C.c_int
+        lib.nblic_amd_decode_batch_to_ex.argtypes = [C.c_void_p, C.c_int, vpp, szp, xp, C.c_int] + [ip] * 5
+        lib.nblic_amd_deliver_stats.restype = C.c_int
+        lib.nblic_amd_deliver_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+        lib.nblic_amd_debug_deliver_host_ex.restype = C.c_int
+        lib.nblic_amd_debug_deliver_host_ex.argtypes = [C.c_void_p, C.c_int, C.c_int, ip, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                        C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+        lib.nblic_amd_encode_batch_modes_from_to.restype = C.c_int
+        lib.nblic_amd_encode_batch_modes_from_to.argtypes = [C.c_void_p, C.c_int, C.POINTER(Src), C.c_int, C.c_float, C.c_float, ip, ip, vpp, szp, C.POINTER(C.c_long), xp, C.c_int]
+        lib.nblic_amd_debug_deliver_ex.restype = C.c_int
+        lib.nblic_amd_debug_deliver_ex.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, ip, ip, ip, ip, fp, fp, ip, szp, szp, szp, szp, vpp, ip]
     if hasattr(lib, "nblic_amd_encode_batch_modes_from"):           # (an older build loaded through NBLIC_AMD_LIB has none of the seven)
         vpp, szp, fp, sp, lp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(Src), C.POINTER(C.c_long)
         head = [C.c_void_p, C.c_int, sp, C.c_int, C.c_float, C.c_float]
@@ -356,6 +374,13 @@ class Dest(C.Structure):
                 ("row0", C.c_int), ("row1", C.c_int), ("col0", C.c_int), ("col1", C.c_int)]
 
 
+class DestEx(C.Structure):
+    """``nblic_amd_dest_ex``: where one image's window goes in device memory, with the step between the elements of a row
+    and the image's own normalisation."""
+    _fields_ = [("ptr", C.c_void_p), ("pitch_bytes", C.c_size_t), ("step_bytes", C.c_size_t), ("cap_bytes", C.c_size_t),
+                ("row0", C.c_int), ("row1", C.c_int), ("col0", C.c_int), ("col1", C.c_int), ("scale", C.c_float), ("bias", C.c_float)]
+
+
 DELIVER_FORMATS = {"uint8": 0, "float16": 1, "bfloat16": 2, "float32": 3}       # the `format` of the _to calls, by dtype name
 DELIVER_ELEM = (1, 2, 2, 4)
 DELIVER_PATTERN = 0x5A                                                          # what the debug hooks' output buffers hold before a delivery
@@ -369,36 +394,47 @@ def deliver_format(dtype) -> int:
     return DELIVER_FORMATS[name]
 
 
-def deliver_units(rows: int, cols: int, fmt: int) -> Tuple[int, int]:
+def deliver_units(rows: int, cols: int, fmt: int, step: Optional[int] = None) -> Tuple[int, int]:
     """Units and chunks one delivery task counts (csrc/deliver.h): every row has ``(cols + 16 / elem - 1 + 15) // 16``
-    units of at most sixteen pixels, 1024 units go to a chunk (one workgroup)."""
-    units = rows * ((cols + 16 // DELIVER_ELEM[fmt] - 1 + 15) // 16)
+    units of at most sixteen pixels, 1024 units go to a chunk (one workgroup).  ``step``: the bytes between the elements of
+    a destination row; with more than the element size the task is strided and a row has ``(cols + 15) // 16`` units."""
+    if step is None or step == DELIVER_ELEM[fmt]:
+        units = rows * ((cols + 16 // DELIVER_ELEM[fmt] - 1 + 15) // 16)
+    else:
+        units = rows * ((cols + 15) // 16)
     return units, (units + 1023) // 1024
 
 
 def deliver_host(plane: np.ndarray, window, fmt, scale: float = 1.0, bias: float = 0.0, pitch: Optional[int] = None, offset: int = 0,
-                 out_bytes: Optional[int] = None, zero: bool = False, gate_status: int = -1, info: Optional[dict] = None) -> np.ndarray:
+                 out_bytes: Optional[int] = None, zero: bool = False, gate_status: int = -1, info: Optional[dict] = None,
+                 step: Optional[int] = None) -> np.ndarray:
     """The delivery kernel's unit walk on the host (``nblic_amd_debug_deliver_host``; no device): the window
     ``(row0, row1, col0, col1)`` of the 2-D uint8 ``plane`` in format ``fmt`` (0 .. 3 or a dtype) goes to byte ``offset`` of
     a buffer of ``out_bytes`` bytes that holds 0x5A, rows ``pitch`` bytes apart (default: the window's row).  The buffer
     starts at a multiple of 16, so ``offset`` is the destination's residue as on the device.  Returns the buffer (uint8);
-    ``info`` receives ``units`` and ``chunks``.  ``ValueError`` when refused."""
+    ``info`` receives ``units`` and ``chunks``.  ``step`` (``nblic_amd_debug_deliver_host_ex``): the bytes between the
+    elements of a destination row; the default pitch is then ``cols * step``.  ``ValueError`` when refused."""
     plane = np.ascontiguousarray(plane, np.uint8)
     fmt = fmt if isinstance(fmt, int) else deliver_format(fmt)
     r0, r1, c0, c1 = (int(v) for v in window)
     elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
     if pitch is None:
-        pitch = (c1 - c0) * elem
+        pitch = (c1 - c0) * (elem if step is None else int(step))
     if out_bytes is None:
-        out_bytes = offset + max(r1 - r0 - 1, 0) * pitch + max(c1 - c0, 0) * elem
+        out_bytes = offset + max(r1 - r0 - 1, 0) * pitch + max(c1 - c0 - 1, 0) * (elem if step is None else int(step)) + elem
     raw = np.full(int(out_bytes) + 16, DELIVER_PATTERN, np.uint8)
     lead = (-raw.ctypes.data) % 16
     out = raw[lead: lead + int(out_bytes)]
     win = (C.c_int * 4)(r0, r1, c0, c1)
     units, chunks = C.c_ulonglong(0), C.c_ulonglong(0)
-    rc = load_library().nblic_amd_debug_deliver_host(plane.ctypes.data if plane.size else None, plane.shape[0], plane.shape[1] if plane.ndim == 2 else 0, win,
-                                                     int(fmt), float(scale), float(bias), int(bool(zero)), int(gate_status), out.ctypes.data, out.size,
-                                                     int(offset), int(pitch), C.byref(units), C.byref(chunks))
+    head = (plane.ctypes.data if plane.size else None, plane.shape[0], plane.shape[1] if plane.ndim == 2 else 0, win, int(fmt), float(scale), float(bias),
+            int(bool(zero)), int(gate_status), out.ctypes.data, out.size, int(offset), int(pitch))
+    if step is None:
+        rc = load_library().nblic_amd_debug_deliver_host(*head, C.byref(units), C.byref(chunks))
+    else:
+        if int(step) < 0:
+            raise ValueError("deliver_host: a negative step")
+        rc = load_library().nblic_amd_debug_deliver_host_ex(*head, int(step), C.byref(units), C.byref(chunks))
     if rc != 0:
         raise ValueError("nblic_amd_debug_deliver_host refused its arguments")
     if info is not None:
@@ -463,6 +499,56 @@ def _dests_of(views, dims, rows, cols) -> Tuple[list, int]:
             cap = (max(hh - 1, 0) * s0 + ww) * elem
         dests.append((ptr if fits and hh > 0 and ww > 0 else 0, s0 * elem if hh > 1 else max(s0, ww) * elem, max(cap, 0), r0, r1, c0, c1))
     return dests, fmt
+
+
+def _per_image_floats(arg, n: int, what: str) -> List[float]:
+    """One float for every image, or one per image -> a list of n floats."""
+    if hasattr(arg, "__len__"):
+        vals = [float(v) for v in arg]
+        if len(vals) != n:
+            raise ValueError(f"{what}: one value, or one per image")
+        return vals
+    return [float(arg)] * n
+
+
+def _dests_ex_of(views, dims, rows, cols, scale, bias) -> Tuple[list, int]:
+    """One ``(ptr, pitch, step, cap, row0, row1, col0, col1, scale, bias)`` per image and the call's format, from tensors
+    used duck-typed as :func:`_dests_of` uses them, with any non-negative strides (``layout="any"``).  A tensor whose shape
+    is not its image's window gets a null pointer: the library refuses that image alone."""
+    n = len(views)
+    fmts = {deliver_format(v.dtype) for v in views}
+    if len(fmts) > 1:
+        raise ValueError("out: one dtype per call")
+    fmt = fmts.pop() if fmts else 0
+    rows, cols = _pairs_for(rows, n, "rows"), _pairs_for(cols, n, "cols")
+    scales, biases = _per_image_floats(scale, n, "scale"), _per_image_floats(bias, n, "bias")
+    dests = []
+    for k, v in enumerate(views):
+        elem = int(v.element_size())
+        hh, ww = (int(x) for x in v.shape)
+        s0, s1 = (int(x) for x in v.stride())
+        if s0 < 0 or s1 < 0 or elem != DELIVER_ELEM[fmt]:
+            raise ValueError("out: strides must not be negative")
+        (r0, r1), (c0, c1) = rows[k], cols[k]
+        h, w = dims[k]
+        fits = h > 0 and w > 0 and (r1 or h) - r0 == hh and (c1 or w) - c0 == ww and hh > 0 and ww > 0
+        ptr = int(v.data_ptr())
+        step = (s1 if ww > 1 else max(s1, 1)) * elem
+        pitch = (s0 if hh > 1 else max(s0, ww if step == elem else 1)) * elem
+        try:                                                    # what the storage holds from data_ptr() on, when the tensor tells
+            st = v.untyped_storage()
+            cap = int(st.data_ptr()) + int(st.nbytes()) - ptr
+        except AttributeError:                                  # otherwise the view's own extent
+            cap = max(hh - 1, 0) * pitch + max(ww - 1, 0) * step + elem
+        dests.append((ptr if fits else 0, pitch, step, max(cap, 0), r0, r1, c0, c1, scales[k], biases[k]))
+    return dests, fmt
+
+
+def _dest_ex_array(dests):
+    arr = (DestEx * max(len(dests), 1))()
+    for k, d in enumerate(dests):
+        arr[k] = DestEx(int(d[0]) or None, *[int(x) for x in d[1:8]], float(d[8]), float(d[9]))
+    return arr
 
 
 def _dest_array(dests):
@@ -1277,7 +1363,62 @@ class Context:
             info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
         return status
 
-    def decode_batch_indexed_into(self, pairs, out, rows=None, cols=None, scale: float = 1.0, bias: float = 0.0, info: Optional[dict] = None) -> List[int]:
+    def decode_batch_indexed_to_ex(self, pairs, dests, fmt: int, info: Optional[dict] = None) -> List[int]:
+        """``nblic_amd_decode_batch_indexed_to_ex`` as it is: ``dests`` is one ``(ptr, pitch_bytes, step_bytes, cap_bytes,
+        row0, row1, col0, col1, scale, bias)`` per image.  Result and ``info`` as ``decode_batch_indexed_to``."""
+        n = len(pairs)
+        ss = [_bytes_arg(s if s is not None else b"") for s, _ in pairs]
+        xs = [_bytes_arg(x if x is not None else b"") for _, x in pairs]
+        nothing = np.zeros(1, np.uint8)
+        ip = C.POINTER(C.c_int)
+        vp = lambda arrs: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else nothing.ctypes.data for a in arrs])
+        sz = lambda arrs: (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        meta = [np.full(max(n, 1), -1, np.int32) for _ in range(5)]
+        rc = self.lib.nblic_amd_decode_batch_indexed_to_ex(self.handle, n, vp(ss), sz(ss), vp(xs), sz(xs), _dest_ex_array(dests), int(fmt),
+                                                           *[m.ctypes.data_as(ip) for m in meta])
+        status = [int(v) for v in meta[4][:n]]
+        if info is not None:
+            info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
+        return status
+
+    def decode_batch_to_ex(self, streams, dests, fmt: int, info: Optional[dict] = None) -> List[int]:
+        """``nblic_amd_decode_batch_to_ex`` as it is; arguments and result as ``decode_batch_indexed_to_ex``."""
+        n = len(streams)
+        ss = [_bytes_arg(s if s is not None else b"") for s in streams]
+        nothing = np.zeros(1, np.uint8)
+        ip = C.POINTER(C.c_int)
+        sp = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else nothing.ctypes.data for a in ss])
+        sl = (C.c_size_t * max(n, 1))(*[a.size for a in ss])
+        meta = [np.full(max(n, 1), -1, np.int32) for _ in range(5)]
+        rc = self.lib.nblic_amd_decode_batch_to_ex(self.handle, n, sp, sl, _dest_ex_array(dests), int(fmt), *[m.ctypes.data_as(ip) for m in meta])
+        status = [int(v) for v in meta[4][:n]]
+        if info is not None:
+            info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
+        return status
+
+    def deliver_stats(self) -> Tuple[int, int]:
+        """Delivery tasks of the last call that delivered, and the strided ones among them (``nblic_amd_deliver_stats``)."""
+        v = (C.c_long * 2)()
+        if self.lib.nblic_amd_deliver_stats(self.handle, v) != 0:
+            raise RuntimeError("nblic_amd_deliver_stats failed")
+        return int(v[0]), int(v[1])
+
+    def _dests_for(self, out, n, dims, rows, cols, scale, bias, layout):
+        """What the two _into calls make of ``out``: ("ex", dests, fmt) or ("plain", dests, fmt, scale, bias)."""
+        if layout not in ("rows", "any"):
+            raise ValueError('layout: "rows" or "any"')
+        if layout == "any":
+            views = _src_views(out)
+            if len(views) != n:
+                raise ValueError("out: one 2-D tensor per image")
+            return ("ex",) + _dests_ex_of(views, dims, rows, cols, scale, bias)
+        dests, fmt = _dests_of(_dest_tensors(out, n), dims, rows, cols)
+        if not hasattr(scale, "__len__") and not hasattr(bias, "__len__"):
+            return ("plain", dests, fmt, scale, bias)
+        scales, biases = _per_image_floats(scale, n, "scale"), _per_image_floats(bias, n, "bias")
+        return ("ex", [(d[0], d[1], DELIVER_ELEM[fmt]) + tuple(d[2:]) + (scales[k], biases[k]) for k, d in enumerate(dests)], fmt)
+
+    def decode_batch_indexed_into(self, pairs, out, rows=None, cols=None, scale=1.0, bias=0.0, info: Optional[dict] = None, layout: str = "rows") -> List[int]:
         """A window of every image of ``decode_batch_indexed`` straight into device tensors: no pixel crosses the bus.
         ``out`` is one tensor [N, H', W'] or [N, 1, H', W'] on this context's device, or a list of 2-D tensors -- views
         with any batch and row stride, last stride 1; the dtype chooses the format: uint8 (a copy), float16, bfloat16 or
@@ -1286,15 +1427,20 @@ class Context:
         what is delivered.  A tensor whose shape is not its window's is refused for that image.  Returns the status list
         (0, or -1: refused -- the tensor is not written -- or failed -- its window is zeros); ``info`` as
         ``decode_batch_indexed`` fills it.  The call returns when the data is there, and orders itself against nothing queued
-        on the caller's streams: synchronise those first if they still use ``out``."""
+        on the caller's streams: synchronise those first if they still use ``out``.
+
+        ``layout="any"``: ``out`` is one tensor [N, H', W'] or [N, C, H', W'] -- every channel is an image, n-major, as
+        ``encode_batch_from`` reads them -- or a list of 2-D views, with any non-negative strides: a channels-last tensor and
+        ``t.permute(0, 3, 1, 2)`` of a [N, H, W, C] batch are written where they lie, and the bytes between the elements
+        keep their contents.  ``scale`` / ``bias``: one value, or one per image (a mean and std per channel), in either layout."""
         n = len(pairs)
         dims = []
         for _, x in pairs:                                      # the head of an index names the geometry; the library checks all of it
             x = _bytes_arg(x if x is not None else b"")
             h, w = (int(v) for v in np.frombuffer(x[16:24].tobytes(), "<i4")) if x.size >= INDEX_HEAD_BYTES else (0, 0)
             dims.append((h, w) if 0 < h <= 65535 and 0 < w <= 65535 else (0, 0))
-        dests, fmt = _dests_of(_dest_tensors(out, n), dims, rows, cols)
-        return self.decode_batch_indexed_to(pairs, dests, fmt, scale, bias, info)
+        how = self._dests_for(out, n, dims, rows, cols, scale, bias, layout)
+        return self.decode_batch_indexed_to(pairs, *how[1:], info) if how[0] == "plain" else self.decode_batch_indexed_to_ex(pairs, how[1], how[2], info)
 
     def decode_batch_to(self, streams, dests, fmt: int, scale: float = 1.0, bias: float = 0.0, info: Optional[dict] = None) -> List[int]:
         """``nblic_amd_decode_batch_to`` as it is; arguments and result as ``decode_batch_indexed_to``."""
@@ -1311,33 +1457,38 @@ class Context:
             info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
         return status
 
-    def decode_batch_into(self, streams, out, rows=None, cols=None, scale: float = 1.0, bias: float = 0.0, info: Optional[dict] = None) -> List[int]:
+    def decode_batch_into(self, streams, out, rows=None, cols=None, scale=1.0, bias=0.0, info: Optional[dict] = None, layout: str = "rows") -> List[int]:
         """``decode_batch`` with a window of every plane delivered into device tensors (no index: every stream is decoded
-        whole, from its start).  ``out``, ``rows``, ``cols``, ``scale``, ``bias``, the result and ``info`` as
+        whole, from its start).  ``out``, ``layout``, ``rows``, ``cols``, ``scale``, ``bias``, the result and ``info`` as
         ``decode_batch_indexed_into``; a stream that fails on the device leaves zeros."""
         dims = [_stream_dims(_bytes_arg(s if s is not None else b"")) or (0, 0) for s in streams]
-        dests, fmt = _dests_of(_dest_tensors(out, len(streams)), dims, rows, cols)
-        return self.decode_batch_to(streams, dests, fmt, scale, bias, info)
+        how = self._dests_for(out, len(streams), dims, rows, cols, scale, bias, layout)
+        return self.decode_batch_to(streams, *how[1:], info) if how[0] == "plain" else self.decode_batch_to_ex(streams, how[1], how[2], info)
 
     def debug_deliver(self, tasks) -> List[np.ndarray]:
         """``nblic_amd_debug_deliver``: ONE k_deliver launch over ``tasks``, each a dict with ``plane`` (2-D uint8),
         ``window`` (row0, row1, col0, col1) and ``fmt``, and optionally ``scale``, ``bias``, ``pitch`` (default: the window's
         row), ``offset`` (of the destination in its 0x5A-filled buffer), ``out_bytes`` (default: what the window needs from
         ``offset`` on), ``base_offset`` (0 .. 15, of the plane in its device buffer), ``zero`` and ``gate_status`` (-1: no
-        gate).  Returns every task's whole buffer (uint8).  ``ValueError`` when refused."""
+        gate), and ``step`` (the bytes between the elements of a destination row; default: the element size.  When any task
+        names one the launch goes through ``nblic_amd_debug_deliver_ex``, and a task's default pitch is ``cols * step``).
+        Returns every task's whole buffer (uint8).  ``ValueError`` when refused."""
         n = len(tasks)
-        planes, wins, fmts, scales, biases, zeros, pitches, offsets, sizes, bases, gates = ([] for _ in range(11))
+        planes, wins, fmts, scales, biases, zeros, pitches, offsets, sizes, bases, gates, steps = ([] for _ in range(12))
+        ex = any("step" in t for t in tasks)
         for t in tasks:
             plane = np.ascontiguousarray(t["plane"], np.uint8)
             fmt = t["fmt"] if isinstance(t["fmt"], int) else deliver_format(t["fmt"])
             r0, r1, c0, c1 = (int(v) for v in t["window"])
             elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
-            pitch = int(t.get("pitch", (c1 - c0) * elem))
+            step = int(t.get("step", elem))
+            pitch = int(t.get("pitch", (c1 - c0) * step))
             offset = int(t.get("offset", 0))
+            steps.append(step)
             planes.append(plane); wins += [r0, r1, c0, c1]; fmts.append(fmt)
             scales.append(float(t.get("scale", 1.0))); biases.append(float(t.get("bias", 0.0))); zeros.append(int(bool(t.get("zero", False))))
             pitches.append(pitch); offsets.append(offset)
-            sizes.append(int(t.get("out_bytes", offset + max(r1 - r0 - 1, 0) * pitch + max(c1 - c0, 0) * elem)))
+            sizes.append(int(t.get("out_bytes", offset + max(r1 - r0 - 1, 0) * pitch + max(c1 - c0 - 1, 0) * step + elem)))
             bases.append(int(t.get("base_offset", 0))); gates.append(int(t.get("gate_status", -1)))
         if any(p.ndim != 2 or p.size == 0 for p in planes):
             raise ValueError("debug_deliver: every plane is a 2-D uint8 array")
@@ -1347,9 +1498,14 @@ class Context:
         sz = lambda vals: (C.c_size_t * m)(*[int(v) for v in vals])
         iv = lambda vals, k=1: (C.c_int * (m * k))(*[int(v) for v in vals])
         fv = lambda vals: (C.c_float * m)(*vals)
-        rc = self.lib.nblic_amd_debug_deliver(self.handle, n, vp(planes), sz(p.size for p in planes), sz(bases), iv(p.shape[0] for p in planes),
-                                              iv(p.shape[1] for p in planes), iv(wins, 4), iv(fmts), fv(scales), fv(biases), iv(zeros), sz(pitches),
-                                              sz(offsets), sz(sizes), vp(outs), iv(gates))
+        head = (self.handle, n, vp(planes), sz(p.size for p in planes), sz(bases), iv(p.shape[0] for p in planes), iv(p.shape[1] for p in planes), iv(wins, 4),
+                iv(fmts), fv(scales), fv(biases), iv(zeros), sz(pitches))
+        if ex:
+            if any(v < 0 for v in steps):
+                raise ValueError("debug_deliver: a negative step")
+            rc = self.lib.nblic_amd_debug_deliver_ex(*head, sz(steps), sz(offsets), sz(sizes), vp(outs), iv(gates))
+        else:
+            rc = self.lib.nblic_amd_debug_deliver(*head, sz(offsets), sz(sizes), vp(outs), iv(gates))
         if rc == -1:
             raise ValueError("nblic_amd_debug_deliver refused its arguments")
         if rc != 0:
@@ -1373,14 +1529,19 @@ class Context:
         return float(ms.value), int(k.value)
 
     def encode_from_srcs(self, srcs, fmt: int, scale: float = 1.0, bias: float = 0.0, near=0, effort=1, every_rows=None, band_rows: int = 0,
-                         info: Optional[dict] = None):
+                         info: Optional[dict] = None, recon_dests=None, recon_fmt: int = 0):
         """The four _from calls on ``srcs``, one ``(ptr, pitch_bytes, step_bytes, cap_bytes, rows, cols)`` per image (device
         memory), in format ``fmt`` (0 .. 3).  ``effort`` 0 (for every image) takes the QNBLIC calls, ``every_rows`` the
         indexed ones.  Returns the streams -- ``None`` for a refused or failed image -- or (stream, index) pairs when
         ``every_rows`` is given; ``info`` receives ``rc`` and, for the mode call, ``recons`` (the host reconstructions).
+        ``recon_dests`` (the mode call only): one ``(ptr, pitch_bytes, step_bytes, cap_bytes, row0, row1, col0, col1, scale,
+        bias)`` per image, ptr 0 for none -- the reconstructions go to device memory in format ``recon_fmt``
+        (``nblic_amd_encode_batch_modes_from_to``) and there are no host ``recons``.
         ``ValueError`` when the library refuses the whole call."""
         n = len(srcs)
         nears, efforts = _per_image(near, n, "near"), _per_image(effort, n, "effort")
+        if recon_dests is not None and (every_rows is not None or (n > 0 and all(e == 0 for e in efforts))):
+            raise ValueError("reconstructions go to device memory from the mode call only: no effort 0, no every_rows")
         q = n > 0 and all(e == 0 for e in efforts)
         if (not q and any(e == 0 for e in efforts)) or (q and any(nears)):
             raise ValueError("effort 0 (QNBLIC) is lossless and takes a whole call")
@@ -1406,6 +1567,10 @@ class Context:
             rc = call(*head, (C.c_int * m)(*every), int(band_rows), op, caps, lens, xp, xcaps, xlens)
         elif q:
             rc = self.lib.nblic_amd_qencode_batch_from(*head, op, caps, lens)
+        elif recon_dests is not None:
+            if len(recon_dests) != n:
+                raise ValueError("recon_dests: one per image")
+            rc = self.lib.nblic_amd_encode_batch_modes_from_to(*head, (C.c_int * m)(*nears), (C.c_int * m)(*efforts), op, caps, lens, _dest_ex_array(recon_dests), int(recon_fmt))
         else:
             if info is not None:
                 recs = [np.zeros(s, np.uint8) for s in shapes]
@@ -1441,7 +1606,7 @@ class Context:
         return outs, got
 
     def encode_batch_from(self, src, rows=None, cols=None, scale: float = 1.0, bias: float = 0.0, near=0, effort=1, every_rows=None,
-                          band_rows: int = 0, info: Optional[dict] = None):
+                          band_rows: int = 0, info: Optional[dict] = None, recon_out=None, recon_scale=1.0, recon_bias=0.0):
         """Encode images that lie in device memory in any layout, as pixels or as floats quantised on the way (the _from
         calls; include/nblic_amd.h says what the pixel of an element is).  ``src``: one tensor [N, H, W], one tensor
         [N, C, H, W] -- every channel is an image, n-major -- or a list of 2-D tensors or views, of ONE dtype (uint8,
@@ -1451,9 +1616,21 @@ class Context:
         ``near`` / ``effort``: one value or one per image; ``effort`` 0 takes the QNBLIC calls, ``every_rows`` the indexed
         ones (lossless -e1 or effort 0).  Returns the streams (``None`` for a refused or failed image), or
         (stream, index) pairs when ``every_rows`` is given.  The caller makes sure that the tensors' producers have
-        finished (``torch.cuda.synchronize()``): the call orders itself against no stream of the caller's."""
+        finished (``torch.cuda.synchronize()``): the call orders itself against no stream of the caller's.
+
+        ``recon_out``: where the reconstructions go on the device -- what a decoder of each stream produces -- as one tensor
+        or a list like ``src``, of any of the four dtypes and with any non-negative strides (``decode_batch_into`` with
+        ``layout="any"`` takes the same), every image's the shape of what is encoded; ``recon_scale`` / ``recon_bias``
+        normalise a float one, one value or one per image.  A destination the library refuses costs that reconstruction
+        only.  Not with effort 0 or ``every_rows``."""
         srcs, fmt = _srcs_of(_src_views(src), rows, cols)
-        return self.encode_from_srcs(srcs, fmt, scale, bias, near, effort, every_rows, band_rows, info)
+        if recon_out is None:
+            return self.encode_from_srcs(srcs, fmt, scale, bias, near, effort, every_rows, band_rows, info)
+        views = _src_views(recon_out)
+        if len(views) != len(srcs):
+            raise ValueError("recon_out: one 2-D tensor per image")
+        dests, rfmt = _dests_ex_of(views, [(s[4], s[5]) for s in srcs], None, None, recon_scale, recon_bias)
+        return self.encode_from_srcs(srcs, fmt, scale, bias, near, effort, every_rows, band_rows, info, recon_dests=dests, recon_fmt=rfmt)
 
     def debug_collect(self, tasks) -> List[np.ndarray]:
         """``nblic_amd_debug_collect``: ONE k_collect launch over ``tasks``, each a dict with ``raw`` (the source's bytes, any

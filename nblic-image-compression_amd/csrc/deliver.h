@@ -8,6 +8,11 @@
 // first unit of a row begins up to 16 / elem - 1 elements in front of the window (it has a head: fewer than sixteen
 // pixels) and the last one may end behind it (a tail).  Every row has the same number of units -- the most any row
 // alignment needs -- and a unit that no column falls into does nothing.
+//
+// A STRIDED task (dst_step > the element size: the elements of a destination row lie dst_step bytes apart, as the colours
+// of an interleaved frame or the channels of a channels-last tensor do) knows no 16-byte rule: nothing is stored that is
+// wider than one element.  Its unit is sixteen consecutive pixels of one row, counted from col0; element (r, c) of the
+// window goes to dst + r * dst_pitch + c * dst_step and no other byte is written.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -31,24 +36,33 @@ struct DeliverTask {
     uint8_t *dst;                          // element (row0, col0) goes here; a multiple of the element size
     const SerialState *gate;               // not null: deliver only if its status is kDone, zeros otherwise
     unsigned long long src_bytes;          // readable bytes from src: nothing outside [src, src + src_bytes) is read
-    unsigned long long dst_pitch;          // bytes between destination rows: a multiple of the element size, >= cols * elem
+    unsigned long long dst_pitch;          // bytes between destination rows: a multiple of the element size; contiguous: >= cols * elem
     uint32_t src_pitch;                    // bytes between source rows: the image's width
     int row0, row1, col0, col1;            // the window [row0, row1) x [col0, col1)
     uint32_t format;                       // kDeliverU8 .. kDeliverF32
     float scale, bias;                     // float formats: float(px) * scale, rounded, + bias, rounded, then to the format
     uint32_t zero;                         // != 0: zero bytes instead of pixels
     uint32_t first_chunk;                  // chunks of the launch's tasks in front of this one
+    uint32_t dst_step;                     // bytes between neighbouring elements of a destination row: the element size, or more (strided)
+    uint32_t pad_;
 };
-static_assert(sizeof(DeliverTask) == 80, "uploaded as bytes");
+static_assert(sizeof(DeliverTask) == 88, "uploaded as bytes");
 
 constexpr uint32_t kDeliverUnitPixels = 16;
 constexpr uint32_t kDeliverChunkUnits = 1024;                        // one workgroup: kIndexChunkBytes / 16 (serial_engine.hip asserts it)
+constexpr uint32_t kDeliverMaxStep = 1u << 20;                       // bytes; the sources' limit (collect.h kCollectMaxStep)
+constexpr unsigned long long kDeliverMaxPitch = 1ull << 40;
 
 DL_HD uint32_t deliver_elem(uint32_t format) { return format == kDeliverU8 ? 1u : (format == kDeliverF32 ? 4u : 2u); }
 // Units of one row: cols pixels behind a head gap of at most 16 / elem - 1 elements, sixteen to a unit.
 DL_HD uint32_t deliver_row_units(uint32_t cols, uint32_t format) { return (cols + 16u / deliver_elem(format) - 1u + 15u) / 16u; }
+// The same for a row whose elements lie `step` bytes apart: a strided row has no head gap.
+DL_HD uint32_t deliver_row_units(uint32_t cols, uint32_t format, uint32_t step) {
+    return step == deliver_elem(format) ? deliver_row_units(cols, format) : (cols + 15u) / 16u;
+}
+DL_HD bool deliver_strided(const DeliverTask &t) { return t.dst_step != deliver_elem(t.format); }
 DL_HD unsigned long long deliver_task_units(const DeliverTask &t) {
-    return (unsigned long long)(uint32_t(t.row1 - t.row0)) * deliver_row_units(uint32_t(t.col1 - t.col0), t.format);
+    return (unsigned long long)(uint32_t(t.row1 - t.row0)) * deliver_row_units(uint32_t(t.col1 - t.col0), t.format, t.dst_step);
 }
 DL_HD unsigned long long deliver_task_chunks(const DeliverTask &t) { return (deliver_task_units(t) + kDeliverChunkUnits - 1) / kDeliverChunkUnits; }
 
@@ -66,6 +80,17 @@ DL_HD DeliverUnit deliver_unit_of(const DeliverTask &t, uint32_t u) {
     U.c_lo = U.c0 < 0 ? 0u : uint32_t(U.c0);
     U.c_hi = uint32_t(U.c0 + 16) < cols ? uint32_t(U.c0 + 16) : cols;
     if (U.c_lo > U.c_hi) U.c_lo = U.c_hi;
+    return U;
+}
+
+// Unit u of a strided task: columns [16 j, 16 j + 16) of its row, cut at the window's end.  No head: c0 is never negative.
+DL_HD DeliverUnit deliver_strided_unit_of(const DeliverTask &t, uint32_t u) {
+    const uint32_t cols = uint32_t(t.col1 - t.col0), per_row = (cols + 15u) / 16u;
+    DeliverUnit U;
+    U.row = u / per_row;
+    U.c_lo = 16u * (u - U.row * per_row);
+    U.c0 = int(U.c_lo);
+    U.c_hi = U.c_lo + 16u < cols ? U.c_lo + 16u : cols;
     return U;
 }
 
@@ -110,14 +135,16 @@ DL_HD uint32_t deliver_value(uint32_t px, uint32_t format, float scale, float bi
 }
 
 // What a task must satisfy before a kernel or the host walk may run it: a sound window inside a plane of src_rows rows
-// that the readable bytes hold, a destination pitch and pointer that are multiples of the element size, rows that do
-// not overlap, no more units than 32 bits count, and uint8 as a plain copy.
+// that the readable bytes hold, a destination pitch, step and pointer that are multiples of the element size and not
+// below it, contiguous rows that do not overlap (a strided task may have any pitch: a transposed view is one), no more
+// units than 32 bits count, and uint8 as a plain copy.
 inline bool deliver_task_ok(const DeliverTask &t, uint32_t src_rows) {
     if (!t.src || !t.dst || t.format >= kDeliverFormats || t.src_pitch == 0) return false;
     if (t.row0 < 0 || t.row1 <= t.row0 || uint32_t(t.row1) > src_rows || t.col0 < 0 || t.col1 <= t.col0 || uint32_t(t.col1) > t.src_pitch) return false;
     if ((unsigned long long)(src_rows) * t.src_pitch > t.src_bytes) return false;
     const uint32_t elem = deliver_elem(t.format);
-    if (uintptr_t(t.dst) % elem || t.dst_pitch % elem || t.dst_pitch < (unsigned long long)(uint32_t(t.col1 - t.col0)) * elem) return false;
+    if (uintptr_t(t.dst) % elem || t.dst_pitch % elem || t.dst_step % elem || t.dst_step < elem || t.dst_step > kDeliverMaxStep || t.dst_pitch > kDeliverMaxPitch) return false;
+    if (t.dst_pitch < (deliver_strided(t) ? (unsigned long long)(elem) : (unsigned long long)(uint32_t(t.col1 - t.col0)) * elem)) return false;
     if (!(t.scale - t.scale == 0.0f) || !(t.bias - t.bias == 0.0f)) return false;          // NaN, infinite
     if (t.format == kDeliverU8 && (t.scale != 1.0f || t.bias != 0.0f)) return false;
     return deliver_task_chunks(t) < (1ull << 31) / kDeliverChunkUnits;
@@ -127,6 +154,10 @@ inline bool deliver_task_ok(const DeliverTask &t, uint32_t src_rows) {
 inline unsigned long long deliver_extent(uint32_t rows, uint32_t cols, uint32_t format, unsigned long long pitch) {
     return (unsigned long long)(rows - 1) * pitch + (unsigned long long)(cols) * deliver_elem(format);
 }
+// The same with the row's elements `step` bytes apart: from the first byte written to the one behind the last.
+inline unsigned long long deliver_extent(uint32_t rows, uint32_t cols, uint32_t format, unsigned long long pitch, unsigned long long step) {
+    return (unsigned long long)(rows - 1) * pitch + (unsigned long long)(cols - 1) * step + deliver_elem(format);
+}
 
 // The host walk: every unit of the task, one after the other, element by element.  `gate_status` stands for the gate
 // record's status (the task's own gate pointer is not followed); pass 1 (kDone) for none.
@@ -134,13 +165,14 @@ inline void deliver_host(const DeliverTask &t, int gate_status) {
     const uint32_t elem = deliver_elem(t.format);
     const bool zero = t.zero != 0 || gate_status != 1;
     const unsigned long long units = deliver_task_units(t);
+    const bool strided = deliver_strided(t);
     for (unsigned long long u = 0; u < units; u++) {
-        const DeliverUnit U = deliver_unit_of(t, uint32_t(u));
+        const DeliverUnit U = strided ? deliver_strided_unit_of(t, uint32_t(u)) : deliver_unit_of(t, uint32_t(u));
         const uint8_t *s = t.src + size_t(uint32_t(t.row0) + U.row) * t.src_pitch + uint32_t(t.col0);
         uint8_t *d = t.dst + size_t(U.row) * size_t(t.dst_pitch);
         for (uint32_t c = U.c_lo; c < U.c_hi; c++) {
             const uint32_t v = zero ? 0u : deliver_value(s[c], t.format, t.scale, t.bias);
-            memcpy(d + size_t(c) * elem, &v, elem);                  // (little endian: the low elem bytes)
+            memcpy(d + size_t(c) * t.dst_step, &v, elem);            // (little endian: the low elem bytes)
         }
     }
 }

@@ -213,6 +213,9 @@ struct Group {
     // first call that collects; an indexed effort-0 batch uses one stretch of them per queued step
     Pinned<CollectTask> h_ctasks; DevBuf<CollectTask> d_ctasks; int n_ctasks = 0;
     Event ct_ev[2]; bool ct_pending = false;           // nblic_amd_enable_timing: the marks around a k_collect launch that nobody has read yet
+    // reconstructions to device memory (nblic_amd_encode_batch_modes_from_to): the delivery tasks of the group's images and
+    // their device copy.  Grow-only; allocated by the first call that delivers one
+    Pinned<DeliverTask> h_dtasks; DevBuf<DeliverTask> d_dtasks;
 };
 
 }  // namespace nblic
@@ -310,6 +313,7 @@ struct nblic_amd_ctx {
     DevBuf<DeliverTask> dec_deliver;      // nblic_amd_decode_batch_to: the chunks' delivery tasks (grow-only, like dec_jobs)
     std::atomic<long> collect_counts[4] = {};   // nblic_amd_collect_stats: images in place, images collected, k_collect launches, pixels collected
     double collect_ms = 0; long collect_timed = 0;   // nblic_amd_collect_ms: GPU time of the k_collect launches that were timed, and how many.  Guarded by stat_m
+    long deliver_tasks = 0, deliver_strided = 0;     // nblic_amd_deliver_stats: of the last call that delivers.  Guarded by stat_m (at the end: no member has moved)
 };
 
 namespace nblic {
@@ -488,6 +492,9 @@ struct CollectFrom {
     std::vector<uint8_t> how;
     std::vector<CollectTask> tasks;                                      // kSrcCollect: all but dst, px0, px1 and first_chunk
     std::vector<const uint8_t *> imgs; std::vector<int> hs, ws;
+    // nblic_amd_encode_batch_modes_from_to: where image k's reconstruction goes (recon_ok[k]) -- a task that lacks only src,
+    // src_bytes and gate, which the group that encodes the image knows.  Empty: no reconstruction leaves by this door
+    std::vector<DeliverTask> recon_tasks; std::vector<uint8_t> recon_ok;
 };
 
 // Room for n tasks in group g.
@@ -540,6 +547,38 @@ static bool collect_flush(Group &g, hipStream_t st, size_t at = 0) {
     return true;
 }
 
+// The reconstructions of group g's images into the caller's device memory: ONE k_deliver launch on the group's stream,
+// behind the launches that made the planes.  An image's plane is its reconstruction (near > 0), or what was encoded -- the
+// collected plane, or the source where it lies.  gated: by the serial model's record, so an image that failed there leaves
+// zeros.  Their tasks count for nblic_amd_deliver_stats.
+static bool recon_deliver(Group &g, const CollectFrom *from, bool gated) {
+    if (!from || from->recon_tasks.empty()) return true;
+    if (g.h_dtasks.capacity() < g.slots.size()) {
+        HIP_OK(hipStreamSynchronize(g.stream));                          // (a queued upload may still read the old block)
+        HIP_OK(g.h_dtasks.alloc(g.slots.size())); HIP_OK(g.d_dtasks.alloc(g.slots.size()));
+    }
+    int n = 0;
+    long strided = 0;
+    unsigned long long chunks = 0;
+    for (int k = 0; k < g.n_jobs; k++) {
+        const Slot &s = g.slots[size_t(k)];
+        if (!from->recon_ok[size_t(s.job)]) continue;
+        DeliverTask &T = g.h_dtasks[n++];
+        T = from->recon_tasks[size_t(s.job)];
+        T.src = s.near > 0 ? s.d_recon.get() : s.b.img; T.src_bytes = size_t(s.h) * size_t(s.w);
+        T.gate = gated ? s.d_state : nullptr;
+        T.first_chunk = uint32_t(chunks); chunks += deliver_task_chunks(T);
+        strided += deliver_strided(T) ? 1 : 0;
+    }
+    if (n == 0) return true;
+    if (chunks >= (1ull << 31)) return false;
+    HIP_OK(hipMemcpyAsync(g.d_dtasks, g.h_dtasks, size_t(n) * sizeof(DeliverTask), hipMemcpyHostToDevice, g.stream));
+    if (!deliver_launch(g.d_dtasks, n, uint32_t(chunks), g.stream)) return false;
+    std::lock_guard<std::mutex> l(g.ctx->stat_m);
+    g.ctx->deliver_tasks += n; g.ctx->deliver_strided += strided;
+    return true;
+}
+
 // What every front half starts with for slot k of group g (which already carries job / h / w / near): its workspace,
 // its input plane on the device -- the caller's, a copy on the group's stream, or a source that the group's k_collect
 // launch (collect_flush, once the slots have begun) writes into the slot's d_img -- and its job record.
@@ -571,6 +610,7 @@ static bool launch_front(nblic_amd_ctx *c, Group &g, const uint8_t *const *imgs,
     for (int k = 0; k < g.n_jobs; k++)
         if (!slot_begin(g, k, imgs, on_device, true, dbg_flags(), from)) return false;
     if (!collect_flush(g, g.stream)) return false;
+    if (!recon_deliver(g, from, false)) return false;
     for (int k = 0; k < g.n_jobs && from && g.recons; k++) {             // -n0 -e1: the reconstruction IS the collected plane
         const Slot &s = g.slots[size_t(k)];
         if (from->how[size_t(s.job)] == kSrcCollect && g.recons[s.job])
@@ -620,6 +660,7 @@ static bool launch_front_serial(nblic_amd_ctx *c, Group &g, const uint8_t *const
         { std::lock_guard<std::mutex> sl(c->stat_m); c->serial_launch_count += launches; }
         k0 = k1;
     }
+    if (!recon_deliver(g, from, true)) return false;
     for (int k = 0; k < g.n_jobs; k++) {                                 // the encoder leaves the reconstruction in the caller's plane (NBLIC.c:876)
         Slot &s = g.slots[size_t(k)];
         unsigned char *dst = g.recons ? g.recons[s.job] : nullptr;
@@ -1660,8 +1701,18 @@ static bool decode_launch(const DecodeItem &first, const SerialJob *d_jobs, cons
 }
 
 // ---- delivery to caller-owned device memory (deliver.h, serial_engine.h k_deliver) ----------------------------------------
-// What the _to calls hand down: one destination per image, one format and one normalisation per call.
-struct DeliverTo { const nblic_amd_dest *dests; uint32_t format; float scale, bias; };
+// What the _to calls hand down: one destination per image with its step and normalisation, one format per call.  The
+// calls without a step make theirs here (dests_ex): the element size, and the call's scale / bias in every image.
+struct DeliverTo { const nblic_amd_dest_ex *dests; uint32_t format; };
+
+static std::vector<nblic_amd_dest_ex> dests_ex(const nblic_amd_dest *dests, int n, int format, float scale, float bias) {
+    std::vector<nblic_amd_dest_ex> ex(size_t(std::max(n, 0)));
+    for (size_t k = 0; k < ex.size(); k++) {
+        const nblic_amd_dest &D = dests[k];
+        ex[k] = nblic_amd_dest_ex{D.ptr, D.pitch_bytes, deliver_elem(uint32_t(format)), D.cap_bytes, D.row0, D.row1, D.col0, D.col1, scale, bias};
+    }
+    return ex;
+}
 
 static bool deliver_args_ok(int format, float scale, float bias) {
     if (format < 0 || format >= int(kDeliverFormats)) return false;
@@ -1686,30 +1737,43 @@ static bool device_range_ok(const nblic_amd_ctx *c, const void *ptr, unsigned lo
 
 // The window destination k names in an image of h x w, and the task that fills it -- all but src, src_bytes, gate and zero,
 // which are the caller's.  false: refused, on the host, before anything of the image is launched: the window is empty or
-// outside the image, the pointer or the pitch is no multiple of the element size, the pitch is too small, the window does
-// not fit cap_bytes, or the runtime does not know the pointer as memory of this context's device that holds the whole extent.
+// outside the image, the pointer, the pitch or the step is no multiple of the element size or is below it, the step or the
+// pitch is beyond its limit, a contiguous destination's pitch is below its row, the scale or the bias is not finite (or not
+// 1 / 0 for uint8), the window does not fit cap_bytes, or the runtime does not know the pointer as memory of this context's
+// device that holds the whole extent.
 static bool deliver_dest_task(const nblic_amd_ctx *c, const DeliverTo &to, int k, int h, int w, DeliverTask &T) {
-    const nblic_amd_dest &D = to.dests[k];
+    const nblic_amd_dest_ex &D = to.dests[k];
     T = DeliverTask{};
     T.row0 = D.row0; T.row1 = D.row1 ? D.row1 : h; T.col0 = D.col0; T.col1 = D.col1 ? D.col1 : w;
     if (T.row0 < 0 || T.row1 <= T.row0 || T.row1 > h || T.col0 < 0 || T.col1 <= T.col0 || T.col1 > w) return false;
+    if (!deliver_args_ok(int(to.format), D.scale, D.bias)) return false;
     const size_t elem = deliver_elem(to.format), rows = size_t(T.row1 - T.row0), cols = size_t(T.col1 - T.col0);
-    if (!D.ptr || uintptr_t(D.ptr) % elem || D.pitch_bytes % elem || D.pitch_bytes < cols * elem || D.pitch_bytes > (size_t(1) << 40)) return false;
-    const unsigned long long extent = deliver_extent(uint32_t(rows), uint32_t(cols), to.format, D.pitch_bytes);
+    if (!D.ptr || uintptr_t(D.ptr) % elem || D.pitch_bytes % elem || D.step_bytes % elem || D.step_bytes < elem || D.step_bytes > kDeliverMaxStep) return false;
+    if (D.pitch_bytes < (D.step_bytes == elem ? cols * elem : elem) || D.pitch_bytes > kDeliverMaxPitch) return false;
+    const unsigned long long extent = deliver_extent(uint32_t(rows), uint32_t(cols), to.format, D.pitch_bytes, D.step_bytes);
     if (extent > D.cap_bytes || !device_range_ok(c, D.ptr, extent)) return false;
-    T.dst =static_cast<uint8_t *>(D.ptr); T.dst_pitch = D.pitch_bytes;
+    T.dst =static_cast<uint8_t *>(D.ptr); T.dst_pitch = D.pitch_bytes; T.dst_step = uint32_t(D.step_bytes);
     T.src_pitch = uint32_t(w);
-    T.format = to.format; T.scale = to.scale; T.bias = to.bias;
+    T.format = to.format; T.scale = D.scale; T.bias = D.bias;
     return deliver_task_chunks(T) < (1ull << 31) / kDeliverChunkUnits;
 }
 
-// The tasks' places in ONE k_deliver launch, their upload to d_tasks and the launch, queued on st.
-static bool deliver_queue(DeliverTask *tasks, size_t n, DeliverTask *d_tasks, hipStream_t st) {
+// The tasks' places in ONE k_deliver launch, their upload to d_tasks and the launch, queued on st.  `c`: the context whose
+// nblic_amd_deliver_stats count them (null: the zeros after a failure are not counted).
+static bool deliver_queue(DeliverTask *tasks, size_t n, DeliverTask *d_tasks, hipStream_t st, nblic_amd_ctx *c = nullptr) {
     unsigned long long chunks = 0;
-    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(chunks); chunks += deliver_task_chunks(tasks[i]); }
+    long strided = 0;
+    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(chunks); chunks += deliver_task_chunks(tasks[i]); strided += deliver_strided(tasks[i]) ? 1 : 0; }
     if (n == 0) return true;
+    if (c) { std::lock_guard<std::mutex> l(c->stat_m); c->deliver_tasks += long(n); c->deliver_strided += strided; }
     if (chunks >= (1ull << 31) || n >= (size_t(1) << 30)) return false;
     return hipMemcpyAsync(d_tasks, tasks, n * sizeof(DeliverTask), hipMemcpyHostToDevice, st) == hipSuccess && deliver_launch(d_tasks, int(n), uint32_t(chunks), st);
+}
+
+static void deliver_stats_reset(nblic_amd_ctx *c) {
+    if (!c) return;
+    std::lock_guard<std::mutex> l(c->stat_m);
+    c->deliver_tasks = c->deliver_strided = 0;
 }
 
 // After a device failure: zero bytes into every window, by the same kernel, as far as the stream still works.
@@ -1858,7 +1922,7 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
             if (!to && hipMemcpyAsync(imgs[it.k], jobs[size_t(i)].recon, size_t(it.h) * size_t(it.w), hipMemcpyDeviceToHost, ch.st) != hipSuccess) return false;
         }
         // the chunk's windows: ONE launch on its stream, behind its decode launches
-        return !to || deliver_queue(deliveries.data() + ch.i0, size_t(ch.i1 - ch.i0), c->dec_deliver + ch.i0, ch.st);
+        return !to || deliver_queue(deliveries.data() + ch.i0, size_t(ch.i1 - ch.i0), c->dec_deliver + ch.i0, ch.st, c);
     };
     for (size_t n = 0; n < chunks.size(); n++) {
         if (n >= 2 && hipStreamSynchronize(chunks[n].st) != hipSuccess) return fail("a chunk");      // heads[] of chunk n - 2 have landed before its stream is reused (its H2D reads heads of chunk n)
@@ -3779,7 +3843,7 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
         status[I->k] = 0;
     }
     // `to`: ONE launch delivers every live image's window -- zeros for the images that failed above
-    if (to && !deliver_queue(deliveries.data(), deliveries.size(), reinterpret_cast<DeliverTask *>(d_call + verdict_bytes + unpack_task_bytes), st)) return fail("delivery");
+    if (to && !deliver_queue(deliveries.data(), deliveries.size(), reinterpret_cast<DeliverTask *>(d_call + verdict_bytes + unpack_task_bytes), st, c)) return fail("delivery");
     if (hipStreamSynchronize(st) != hipSuccess) return fail("rows");
     split[3] = ms_since(t0);
     { std::lock_guard<std::mutex> l(c->stat_m); for (int k = 0; k < 4; k++) c->idxdec_split[k] = split[k]; }
@@ -4785,15 +4849,22 @@ int nblic_amd_debug_index_unpack(nblic_amd_ctx *c, int n, const void *const *pac
 }
 
 // ---- k_deliver on caller-made planes (tests/test_decode_to_device.py), and its host walk (tests/test_deliver_host.py) -------
-static bool debug_deliver_task(DeliverTask &T, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero, size_t pitch) {
-    if (plane_rows < 1 || width < 1 || !window || !deliver_args_ok(format, scale, bias)) return false;
+// (step 0 stands for the element size: the hooks without a step)
+static bool debug_deliver_task(DeliverTask &T, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero, size_t pitch, size_t step) {
+    if (plane_rows < 1 || width < 1 || !window || !deliver_args_ok(format, scale, bias) || step > kDeliverMaxStep) return false;
     T = DeliverTask{};
     T.src_pitch = uint32_t(width);
     T.row0 = window[0]; T.row1 = window[1]; T.col0 = window[2]; T.col1 = window[3];
     T.format = uint32_t(format); T.scale = scale; T.bias = bias; T.zero = zero ? 1u : 0u;
-    T.dst_pitch = pitch;
+    T.dst_pitch = pitch; T.dst_step = step ? uint32_t(step) : deliver_elem(T.format);
     return pitch <= (size_t(1) << 40);
 }
+
+static int debug_deliver_host(const unsigned char *plane, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero, int gate_status,
+                              unsigned char *out, size_t out_bytes, size_t dst_offset, size_t pitch_bytes, size_t step_bytes, unsigned long long *units, unsigned long long *chunks);
+static int debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const *planes, const size_t *plane_bytes, const size_t *base_offsets, const int *plane_rows,
+                         const int *widths, const int *windows, const int *formats, const float *scales, const float *biases, const int *zeros, const size_t *pitches,
+                         const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs, const int *gate_status);
 
 // Host only: the shared unit walk (deliver.h deliver_host) over the caller's plane of plane_rows x width into out + dst_offset,
 // one unit after the other.  The unit grid follows the destination's address as the kernel's does, so a caller that wants
@@ -4801,12 +4872,23 @@ static bool debug_deliver_task(DeliverTask &T, int plane_rows, int width, const 
 int nblic_amd_debug_deliver_host(const unsigned char *plane, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero,
                                  int gate_status, unsigned char *out, size_t out_bytes, size_t dst_offset, size_t pitch_bytes,
                                  unsigned long long *units, unsigned long long *chunks) {
+    return debug_deliver_host(plane, plane_rows, width, window, format, scale, bias, zero, gate_status, out, out_bytes, dst_offset, pitch_bytes, 0, units, chunks);
+}
+int nblic_amd_debug_deliver_host_ex(const unsigned char *plane, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero,
+                                    int gate_status, unsigned char *out, size_t out_bytes, size_t dst_offset, size_t pitch_bytes, size_t step_bytes,
+                                    unsigned long long *units, unsigned long long *chunks) {
+    if (step_bytes == 0) return -1;
+    return debug_deliver_host(plane, plane_rows, width, window, format, scale, bias, zero, gate_status, out, out_bytes, dst_offset, pitch_bytes, step_bytes, units, chunks);
+}
+static int debug_deliver_host(const unsigned char *plane, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero,
+                              int gate_status, unsigned char *out, size_t out_bytes, size_t dst_offset, size_t pitch_bytes, size_t step_bytes,
+                              unsigned long long *units, unsigned long long *chunks) {
     DeliverTask T;
-    if (!plane || !out || !debug_deliver_task(T, plane_rows, width, window, format, scale, bias, zero, pitch_bytes)) return -1;
+    if (!plane || !out || !debug_deliver_task(T, plane_rows, width, window, format, scale, bias, zero, pitch_bytes, step_bytes)) return -1;
     T.src = plane; T.src_bytes = size_t(plane_rows) * size_t(width);
     T.dst = out + dst_offset;
     if (dst_offset > out_bytes || !deliver_task_ok(T, uint32_t(plane_rows))) return -1;
-    if (deliver_extent(uint32_t(T.row1 - T.row0), uint32_t(T.col1 - T.col0), T.format, pitch_bytes) > out_bytes - dst_offset) return -1;
+    if (deliver_extent(uint32_t(T.row1 - T.row0), uint32_t(T.col1 - T.col0), T.format, pitch_bytes, T.dst_step) > out_bytes - dst_offset) return -1;
     if (units) *units = deliver_task_units(T);
     if (chunks) *chunks = deliver_task_chunks(T);
     deliver_host(T, gate_status == -1 ? int(kDone) : gate_status);
@@ -4822,6 +4904,20 @@ int nblic_amd_debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const 
                             const int *plane_rows, const int *widths, const int *windows, const int *formats, const float *scales, const float *biases,
                             const int *zeros, const size_t *pitches, const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs,
                             const int *gate_status) {
+    return debug_deliver(c, n, planes, plane_bytes, base_offsets, plane_rows, widths, windows, formats, scales, biases, zeros, pitches, nullptr, dst_offsets, out_bytes, outs, gate_status);
+}
+int nblic_amd_debug_deliver_ex(nblic_amd_ctx *c, int n, const unsigned char *const *planes, const size_t *plane_bytes, const size_t *base_offsets,
+                               const int *plane_rows, const int *widths, const int *windows, const int *formats, const float *scales, const float *biases,
+                               const int *zeros, const size_t *pitches, const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes,
+                               unsigned char *const *outs, const int *gate_status) {
+    if (!steps) return -1;
+    for (int k = 0; k < n; k++) if (steps[k] == 0) return -1;
+    return debug_deliver(c, n, planes, plane_bytes, base_offsets, plane_rows, widths, windows, formats, scales, biases, zeros, pitches, steps, dst_offsets, out_bytes, outs, gate_status);
+}
+static int debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const *planes, const size_t *plane_bytes, const size_t *base_offsets,
+                         const int *plane_rows, const int *widths, const int *windows, const int *formats, const float *scales, const float *biases,
+                         const int *zeros, const size_t *pitches, const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs,
+                         const int *gate_status) {
     constexpr int kMaxTasks = 65536;
     constexpr uint8_t kPattern = 0x5A;
     if (!c || n < 1 || n > kMaxTasks || !planes || !plane_bytes || !base_offsets || !plane_rows || !widths || !windows || !formats || !scales || !biases ||
@@ -4833,7 +4929,7 @@ int nblic_amd_debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const 
     for (int k = 0; k < n; k++) {
         const size_t i = size_t(k);
         DeliverTask &T = tasks[i];
-        if (!planes[k] || !outs[k] || base_offsets[k] > 15 || !debug_deliver_task(T, plane_rows[k], widths[k], windows + 4 * i, formats[k], scales[k], biases[k], zeros[k], pitches[k]))
+        if (!planes[k] || !outs[k] || base_offsets[k] > 15 || !debug_deliver_task(T, plane_rows[k], widths[k], windows + 4 * i, formats[k], scales[k], biases[k], zeros[k], pitches[k], steps ? steps[k] : 0))
             return -1;
         if (plane_bytes[k] != size_t(plane_rows[k]) * size_t(widths[k]) || plane_bytes[k] > (size_t(1) << 30) || out_bytes[k] > (size_t(1) << 30) || dst_offsets[k] > out_bytes[k]) return -1;
         T.src_bytes = up256(plane_bytes[k]);
@@ -4854,7 +4950,7 @@ int nblic_amd_debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const 
         T.dst = d_outs + out_at[i] + dst_offsets[k];
         if (gate_status[k] != -1) T.gate = d_gates + i;
         if (!deliver_task_ok(T, uint32_t(plane_rows[k])) ||
-            deliver_extent(uint32_t(T.row1 - T.row0), uint32_t(T.col1 - T.col0), T.format, T.dst_pitch) > out_bytes[k] - dst_offsets[k]) return -1;
+            deliver_extent(uint32_t(T.row1 - T.row0), uint32_t(T.col1 - T.col0), T.format, T.dst_pitch, T.dst_step) > out_bytes[k] - dst_offsets[k]) return -1;
     }
     std::vector<uint8_t> back(outs_total);
     std::vector<SerialState> gates(count);
@@ -4865,7 +4961,8 @@ int nblic_amd_debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const 
         HIP_OK(hipMemcpyAsync(d_gates, gates.data(), count * sizeof(SerialState), hipMemcpyHostToDevice, st));
         for (int k = 0; k < n; k++)
             HIP_OK(hipMemcpyAsync(d_planes + plane_at[size_t(k)] + base_offsets[k], planes[k], plane_bytes[k], hipMemcpyHostToDevice, st));
-        if (!deliver_queue(tasks.data(), count, d_tasks, st)) return false;
+        deliver_stats_reset(c);
+        if (!deliver_queue(tasks.data(), count, d_tasks, st, c)) return false;
         HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         return true;
@@ -5121,12 +5218,25 @@ int nblic_amd_decode_batch(nblic_amd_ctx *c, int n_images, const unsigned char *
 
 int nblic_amd_decode_batch_to(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens, const nblic_amd_dest *dests,
                               int format, float scale, float bias, int *heights, int *widths, int *nears, int *efforts, int *status) {
-    if (!c || c->broken || n_images < 0 || !streams || !stream_lens || !dests || !heights || !widths || !nears || !efforts || !status || !deliver_args_ok(format, scale, bias)) return -1;
+    if (!dests || n_images < 0 || !deliver_args_ok(format, scale, bias)) return -1;
+    const std::vector<nblic_amd_dest_ex> ex = dests_ex(dests, n_images, format, scale, bias);
+    return nblic_amd_decode_batch_to_ex(c, n_images, streams, stream_lens, ex.data(), format, heights, widths, nears, efforts, status);
+}
+int nblic_amd_decode_batch_to_ex(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens, const nblic_amd_dest_ex *dests,
+                                 int format, int *heights, int *widths, int *nears, int *efforts, int *status) {
+    if (!c || c->broken || n_images < 0 || !streams || !stream_lens || !dests || !heights || !widths || !nears || !efforts || !status || format < 0 || format >= int(kDeliverFormats)) return -1;
     for (int k = 0; k < n_images; k++) if (!streams[k]) return -1;
-    const DeliverTo to{dests, uint32_t(format), scale, bias};
+    const DeliverTo to{dests, uint32_t(format)};
     std::lock_guard<std::mutex> g(c->api);
+    deliver_stats_reset(c);
     if (!decode_batch(c, n_images, streams, stream_lens, nullptr, nullptr, heights, widths, nears, efforts, status, &to)) return -1;
     for (int k = 0; k < n_images; k++) if (status[k] != 0) return -1;
+    return 0;
+}
+int nblic_amd_deliver_stats(nblic_amd_ctx *c, long out[2]) {
+    if (!c || !out) return -1;
+    std::lock_guard<std::mutex> l(c->stat_m);
+    out[0] = c->deliver_tasks; out[1] = c->deliver_strided;
     return 0;
 }
 
@@ -5273,6 +5383,21 @@ int nblic_amd_encode_batch_modes_from(nblic_amd_ctx *c, int n_images, const nbli
     if (nothing_outstanding(c)) for (auto &g : c->groups) collect_timing(c, g);       // (nblic_amd_stage_times, as nblic_amd_encode_batch leaves them)
     return ok ? 0 : -1;
 }
+int nblic_amd_encode_batch_modes_from_to(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                         const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
+                                         const nblic_amd_dest_ex *recons, int recon_format) {
+    CollectFrom from{};
+    if (!recons || recon_format < 0 || recon_format >= int(kDeliverFormats)) return -1;
+    if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from)) return -1;
+    const DeliverTo to{recons, uint32_t(recon_format)};
+    from.recon_tasks.assign(size_t(n_images), DeliverTask{}); from.recon_ok.assign(size_t(n_images), 0);
+    for (int k = 0; k < n_images; k++)                                   // a refused destination costs the reconstruction, not the stream
+        from.recon_ok[size_t(k)] = from.how[size_t(k)] != kSrcRefused && recons[k].ptr && deliver_dest_task(c, to, k, from.hs[size_t(k)], from.ws[size_t(k)], from.recon_tasks[size_t(k)]);
+    deliver_stats_reset(c);
+    const bool ok = run_batch(c, nblic_amd_ctx::SubmitItem{nullptr, 0, n_images, from.imgs.data(), true, from.hs.data(), from.ws.data(), outs, out_caps, out_lens, nears, efforts, nullptr, &from});
+    if (nothing_outstanding(c)) for (auto &g : c->groups) collect_timing(c, g);
+    return ok ? 0 : -1;
+}
 int nblic_amd_qencode_batch_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
                                  uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words) {
     CollectFrom from{};
@@ -5329,8 +5454,16 @@ int nblic_amd_decode_batch_indexed(nblic_amd_ctx *c, int n_images, const unsigne
 int nblic_amd_decode_batch_indexed_to(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
                                       const void *const *indexes, const size_t *index_lens, const nblic_amd_dest *dests, int format, float scale, float bias,
                                       int *heights, int *widths, int *nears, int *efforts, int *status) {
-    if (!dests || !deliver_args_ok(format, scale, bias)) return -1;
-    const DeliverTo to{dests, uint32_t(format), scale, bias};
+    if (!dests || n_images < 0 || !deliver_args_ok(format, scale, bias)) return -1;
+    const std::vector<nblic_amd_dest_ex> ex = dests_ex(dests, n_images, format, scale, bias);
+    return nblic_amd_decode_batch_indexed_to_ex(c, n_images, streams, stream_lens, indexes, index_lens, ex.data(), format, heights, widths, nears, efforts, status);
+}
+int nblic_amd_decode_batch_indexed_to_ex(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                         const void *const *indexes, const size_t *index_lens, const nblic_amd_dest_ex *dests, int format,
+                                         int *heights, int *widths, int *nears, int *efforts, int *status) {
+    if (!dests || format < 0 || format >= int(kDeliverFormats)) return -1;
+    const DeliverTo to{dests, uint32_t(format)};
+    deliver_stats_reset(c);
     return decode_batch_indexed(c, n_images, streams, stream_lens, indexes, index_lens, nullptr, nullptr, nullptr, nullptr, heights, widths, nears, efforts, status, &to);
 }
 int nblic_amd_indexed_decode_split(nblic_amd_ctx *c, double ms[4]) {

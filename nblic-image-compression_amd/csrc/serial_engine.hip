@@ -1839,7 +1839,31 @@ __device__ __forceinline__ void deliver_store(NB_GLOBAL uint8_t *d, uint32_t k_l
     }
 }
 
-// One workgroup per chunk of kDeliverChunkUnits units, one unit per lane and step: sixteen pixels of one row (deliver.h).
+// A chunk of a STRIDED task (deliver.h): the elements of a destination row lie dst_step bytes apart, so nothing wider than
+// an element can be stored.  Sixteen pixels per lane would make every store instruction write 64 places that lie sixteen
+// steps apart -- 64 cache lines at a step of 3 or 6 bytes.  The lanes lie ALONG the row instead: slot p of the chunk's
+// 16 * kDeliverChunkUnits pixel slots is pixel p % 16 of unit u0 + p / 16, and lane l takes the slots l, l + 256, ...:
+// a wave's 64 lanes read 64 neighbouring source bytes (four units; one row, but where a row ends) and one store
+// instruction writes 64 neighbouring elements.  Only pixels of the window are read, so nothing outside the plane is.
+__device__ __forceinline__ void deliver_strided_chunk(const DeliverTask &T, bool zero, uint32_t units, uint32_t u0) {
+    const uint32_t elem = deliver_elem(T.format);
+    for (uint32_t p = threadIdx.x; p < kDeliverChunkUnits * kDeliverUnitPixels; p += kIndexThreads) {
+        const uint32_t u = u0 + p / kDeliverUnitPixels;
+        if (u >= units) break;
+        const DeliverUnit U = deliver_strided_unit_of(T, u);
+        const uint32_t c = U.c_lo + p % kDeliverUnitPixels;
+        if (c >= U.c_hi) continue;
+        uint32_t v = 0u;
+        if (!zero) v = deliver_value(gp(T.src)[size_t(uint32_t(T.row0) + U.row) * T.src_pitch + size_t(T.col0) + c], T.format, T.scale, T.bias);
+        NB_GLOBAL uint8_t *d = gp(T.dst) + size_t(U.row) * size_t(T.dst_pitch) + size_t(c) * size_t(T.dst_step);
+        if (elem == 1) *d = uint8_t(v);
+        else if (elem == 2) *(NB_GLOBAL uint16_t *)d = uint16_t(v);
+        else *(NB_GLOBAL uint32_t *)d = v;
+    }
+}
+
+// One workgroup per chunk of kDeliverChunkUnits units, one unit per lane and step: sixteen pixels of one row (deliver.h);
+// a strided task's chunk has its lanes along the row (above), and one launch carries both kinds mixed.
 // No LDS, no atomics; nothing is read outside the task's readable bytes and nothing written outside the window's rows.
 __global__ void __launch_bounds__(kIndexThreads) k_deliver(const DeliverTask *__restrict__ tasks, int n) {
     const DeliverTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
@@ -1847,6 +1871,7 @@ __global__ void __launch_bounds__(kIndexThreads) k_deliver(const DeliverTask *__
     const uint32_t units = uint32_t(deliver_task_units(T)), u0 = (blockIdx.x - T.first_chunk) * kDeliverChunkUnits;
     const uint32_t elem = deliver_elem(T.format);
     const uintptr_t lo = uintptr_t(T.src), hi = lo + T.src_bytes;
+    if (deliver_strided(T)) { deliver_strided_chunk(T, zero, units, u0); return; }
     for (uint32_t j = threadIdx.x; j < kDeliverChunkUnits; j += kIndexThreads) {
         const uint32_t u = u0 + j;
         if (u >= units) break;

@@ -2,7 +2,10 @@
 // pitches and destination residues.  Plane and destination are heap blocks of EXACTLY the bytes the task may touch -- a
 // read or a store outside them is an overrun the sanitizer reports -- and every byte is compared with a plain
 // element-by-element loop that knows nothing of units; the units of a row must tile its columns in order, each one's
-// slot 0 at a multiple of 16 bytes; float16 is compared with a conversion through doubles (half_ref).  Build and run:
+// slot 0 at a multiple of 16 bytes; float16 is compared with a conversion through doubles (half_ref).  The same for
+// strided tasks (a step of 2 .. 7 elements between the elements of a row, any pitch from the row's up, and transposed:
+// pitch = one element, step = rows elements): the block ends with the last element's last byte, and every byte between
+// the elements must keep its pattern.  Build and run:
 //   g++ -std=c++17 -O2 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -o deliver_check tools/deliver_check.cpp && ./deliver_check
 #include <cmath>
 #include <cstdio>
@@ -52,7 +55,7 @@ static int one_task(std::mt19937 &rng, uint32_t format, int rows_total, int widt
     memset(block, 0x5A, residue + extent);
     DeliverTask T{};
     T.src = plane; T.src_bytes = size_t(rows_total) * size_t(width); T.src_pitch = uint32_t(width);
-    T.dst = dst; T.dst_pitch = pitch;
+    T.dst = dst; T.dst_pitch = pitch; T.dst_step = elem;
     T.row0 = row0; T.row1 = row1; T.col0 = col0; T.col1 = col1;
     T.format = format; T.scale = scale; T.bias = bias; T.zero = zero ? 1u : 0u;
     CHECK(deliver_task_ok(T, uint32_t(rows_total)));
@@ -100,6 +103,55 @@ static int one_task(std::mt19937 &rng, uint32_t format, int rows_total, int widt
     return 0;
 }
 
+// The walk's value for one pixel, by the plain arithmetic above.
+static uint32_t value_ref(uint8_t px, uint32_t format, float scale, float bias) {
+    if (format == kDeliverU8) return px;
+    volatile float prod = float(px) * scale;
+    const float v = prod + bias;
+    uint32_t bits;
+    memcpy(&bits, &v, 4);
+    if (format == kDeliverF32) return bits;
+    if (format == kDeliverBF16) return (bits + 0x7FFFu + ((bits >> 16) & 1u)) >> 16;
+    return half_ref(v);
+}
+
+// A strided task: elements `step` bytes apart, rows `pitch` bytes apart (transposed: pitch == elem, step == rows * elem).
+static int one_strided_task(std::mt19937 &rng, uint32_t format, int rows_total, int width, int row0, int row1, int col0, int col1, size_t step, size_t pitch,
+                            size_t residue, float scale, float bias, bool zero) {
+    const uint32_t elem = deliver_elem(format), rows = uint32_t(row1 - row0), cols = uint32_t(col1 - col0);
+    const size_t extent = size_t(deliver_extent(rows, cols, format, pitch, step));
+    CHECK(extent == size_t(rows - 1) * pitch + size_t(cols - 1) * step + elem);
+    uint8_t *plane = static_cast<uint8_t *>(malloc(size_t(rows_total) * size_t(width)));
+    uint8_t *block = static_cast<uint8_t *>(malloc(residue + extent));       // (no alignment rule: malloc's is more than enough)
+    CHECK(plane && block);
+    for (size_t i = 0; i < size_t(rows_total) * size_t(width); i++) plane[i] = uint8_t(rng());
+    uint8_t *dst = block + residue;
+    memset(block, 0x5A, residue + extent);
+    DeliverTask T{};
+    T.src = plane; T.src_bytes = size_t(rows_total) * size_t(width); T.src_pitch = uint32_t(width);
+    T.dst = dst; T.dst_pitch = pitch; T.dst_step = uint32_t(step);
+    T.row0 = row0; T.row1 = row1; T.col0 = col0; T.col1 = col1;
+    T.format = format; T.scale = scale; T.bias = bias; T.zero = zero ? 1u : 0u;
+    CHECK(deliver_strided(T) && deliver_task_ok(T, uint32_t(rows_total)));
+    const uint32_t per_row = deliver_row_units(cols, format, uint32_t(step));
+    CHECK(per_row == (cols + 15) / 16 && deliver_task_units(T) == (unsigned long long)(rows) * per_row);
+    for (uint32_t r = 0; r < rows; r++)                                      // sixteen consecutive pixels, counted from col0
+        for (uint32_t j = 0; j < per_row; j++) {
+            const DeliverUnit U = deliver_strided_unit_of(T, r * per_row + j);
+            CHECK(U.row == r && U.c0 == int(16 * j) && U.c_lo == 16 * j && U.c_hi == (16 * j + 16 < cols ? 16 * j + 16 : cols));
+        }
+    deliver_host(T, 1);
+    std::vector<uint8_t> want(residue + extent, 0x5A);
+    for (uint32_t r = 0; r < rows; r++)
+        for (uint32_t c = 0; c < cols; c++) {
+            const uint32_t v = zero ? 0u : value_ref(plane[size_t(row0 + int(r)) * size_t(width) + size_t(col0) + c], format, scale, bias);
+            memcpy(want.data() + residue + size_t(r) * pitch + size_t(c) * step, &v, elem);
+        }
+    CHECK(memcmp(block, want.data(), residue + extent) == 0);
+    free(plane); free(block);
+    return 0;
+}
+
 int main() {
     std::mt19937 rng(22);
     const float norms[][2] = {{1.0f, 0.0f}, {1.0f / 255.0f, -0.5f}, {0.0078125f, -1.0f}, {1e-7f, 0.0f}, {300.0f, -1.0f}, {5.9604645e-8f, 0.0f}};
@@ -116,6 +168,48 @@ int main() {
                 if (one_task(rng, format, rows_total, width, row0, row1, col0, col1, rng() % 4, size_t(rng() % (16 / elem)) * elem, nb[0], nb[1], rng() % 8 == 0)) return 1;
                 tasks++;
             }
+    long strided = 0;
+    for (uint32_t format = 0; format < kDeliverFormats; format++)
+        for (int width : widths)
+            for (int rep = 0; rep < 300; rep++) {
+                const int rows_total = 1 + int(rng() % 6);
+                const int row0 = int(rng() % uint32_t(rows_total)), row1 = row0 + 1 + int(rng() % uint32_t(rows_total - row0));
+                const int col0 = int(rng() % uint32_t(width)), col1 = col0 + 1 + int(rng() % uint32_t(width - col0));
+                const uint32_t elem = deliver_elem(format), rows = uint32_t(row1 - row0), cols = uint32_t(col1 - col0);
+                const float *nb = format == kDeliverU8 ? norms[0] : norms[rng() % 6];
+                size_t step = size_t(2 + rng() % 6) * elem, pitch = size_t(cols) * step + size_t(rng() % 4) * elem;
+                if (rows > 1 && rep % 5 == 0) { step = size_t(rows) * elem; pitch = elem; }          // transposed
+                if (one_strided_task(rng, format, rows_total, width, row0, row1, col0, col1, step, pitch, size_t(rng() % (16 / elem)) * elem, nb[0], nb[1], rng() % 8 == 0)) return 1;
+                strided++;
+            }
+    // three tasks interleave into one rows x cols x 3 frame of exactly its size: every byte written, none beyond
+    for (uint32_t format = 0; format < kDeliverFormats; format++) {
+        const uint32_t elem = deliver_elem(format), rows = 3, cols = 33;
+        std::vector<uint8_t> planes[3];
+        uint8_t *frame = static_cast<uint8_t *>(malloc(size_t(rows) * cols * 3 * elem));
+        CHECK(frame);
+        memset(frame, 0x5A, size_t(rows) * cols * 3 * elem);
+        for (uint32_t ch = 0; ch < 3; ch++) {
+            planes[ch].resize(rows * cols);
+            for (uint8_t &b : planes[ch]) b = uint8_t(rng());
+            DeliverTask T{};
+            T.src = planes[ch].data(); T.src_bytes = rows * cols; T.src_pitch = cols;
+            T.dst = frame + ch * elem; T.dst_pitch = size_t(cols) * 3 * elem; T.dst_step = 3 * elem;
+            T.row1 = int(rows); T.col1 = int(cols);
+            T.format = format; T.scale = format ? norms[ch + 1][0] : 1.0f; T.bias = format ? norms[ch + 1][1] : 0.0f;
+            CHECK(deliver_task_ok(T, rows));
+            CHECK(deliver_extent(rows, cols, format, T.dst_pitch, T.dst_step) == size_t(rows) * cols * 3 * elem - (2 - ch) * elem - ch * elem);
+            deliver_host(T, 1);
+        }
+        for (uint32_t i = 0; i < rows * cols; i++)
+            for (uint32_t ch = 0; ch < 3; ch++) {
+                uint32_t got = 0;
+                memcpy(&got, frame + (size_t(i) * 3 + ch) * elem, elem);
+                CHECK(got == value_ref(planes[ch][i], format, format ? norms[ch + 1][0] : 1.0f, format ? norms[ch + 1][1] : 0.0f));
+            }
+        free(frame);
+        strided += 3;
+    }
     // every float32 exponent around the halves' range, both signs, ties included: the integer conversion against half_ref
     for (uint32_t e = 90; e < 150; e++)
         for (uint32_t m = 0; m < (1u << 23); m += 0x3FF) {
@@ -134,6 +228,6 @@ int main() {
         memcpy(&f, &b, 4);
         CHECK(deliver_f16_bits(b) == half_ref(f));
     }
-    printf("deliver_check: %ld tasks, all bytes as expected\n", tasks);
+    printf("deliver_check: %ld contiguous and %ld strided tasks, all bytes as expected\n", tasks, strided);
     return 0;
 }
