@@ -514,6 +514,36 @@ long nblic_amd_indexed_decode_plan(int n_images, const int *kinds, const int *ef
  * nblic_amd_decode_batch_indexed_to is nblic_amd_decode_batch_indexed with that delivery in place of the copies to the
  * host (nblic_amd_indexed_decode_split's ms[3] is then the delivery); nblic_amd_decode_batch_to is nblic_amd_decode_batch
  * likewise, each window gated ON THE DEVICE by its image's decoder record: a stream that fails there leaves zeros. */
+/* REVERSIBLE COLOUR TRANSFORM: RGB frames in the _from encoders and the _to_ex decoders.  OR'ed into their `format` argument,
+ * NBLIC_AMD_FORMAT_RCT makes images 3f, 3f + 1, 3f + 2 of the call the R, G, B of frame f, and the three streams of a
+ * frame those of the planes
+ *     t_R = (R - G + 128) mod 256,    t_G = G,    t_B = (B - G + 128) mod 256
+ * (JPEG-LS's transform; 8-bit wrap-around arithmetic, the offset keeps small differences in mid-range), which the decoders
+ * undo on the way out: R = (t_R + G - 128) mod 256, B = (t_B + G - 128) mod 256, then the destination's scale and bias.
+ * There is no container and no change to a stream: each of the three is an ordinary .nblic / QNBLIC stream, byte for byte
+ * what the same call without the flag returns for the transformed plane, seek index included -- so a decoder that knows
+ * nothing of the transform (the reference tool, the calls here without the flag) yields the TRANSFORMED planes.  The
+ * transform happens inside k_collect and k_deliver: R and B are collected with the caller's G source
+ * as their reference, and delivered with the decoded G plane as theirs.  Lossless only: with near > 0 an error of +-near
+ * on a difference plane can wrap to +-255 on R or B.
+ *   accepted by     nblic_amd_encode_batch_modes_from (near = 0 for every image), nblic_amd_qencode_batch_from,
+ *                   nblic_amd_encode_batch_indexed_from, nblic_amd_qencode_batch_indexed_from, nblic_amd_decode_batch_to_ex,
+ *                   nblic_amd_decode_batch_indexed_to_ex.  Every other call takes the flag for an unknown format.
+ *   whole call      -1 with nothing launched or written: n_images % 3 != 0; an image with near > 0;
+ *                   nblic_amd_encode_batch_modes_from_to (there is no reconstruction of a lossless frame to deliver).
+ *   encode          the three sources of a frame have equal rows and cols and one format, scale and bias; the pixel of a
+ *                   source element is what it is without the flag, and the differences are taken of those pixels.  A frame
+ *                   with a source that is refused, or with sources of unequal size, is refused AS A WHOLE: three empty
+ *                   results, nothing launched for it.  R and B are always collected (never used in place); a contiguous
+ *                   uint8 G still is.
+ *   decode          the three streams of a frame have equal height and width and near = 0; they may differ in codec, effort
+ *                   and index.  The three destinations name the same window.  A frame with a refused image or destination
+ *                   is refused as a whole and not written; a frame with a plane that fails on the device gets zeros in all
+ *                   three windows; either way its three statuses are -1.  nblic_amd_decode_batch_to_ex delivers the colour
+ *                   frames of a call in ONE launch behind the work of both of its streams (an event wait), since the
+ *                   planes of a frame may be of different (codec, effort) classes.
+ * The gain on photographs is UNMEASURED: no colour photograph was at hand (README.md says what was measured instead). */
+#define NBLIC_AMD_FORMAT_RCT 0x100
 typedef struct nblic_amd_dest {
     void  *ptr;          /* device memory on the context's device                          */
     size_t pitch_bytes;  /* between rows; >= (col1 - col0) x element size, a multiple of it */
@@ -991,6 +1021,37 @@ int nblic_amd_debug_collect(nblic_amd_ctx *ctx, int n, const void *const *srcs, 
                             const int *rows, const int *cols, const size_t *pitches, const size_t *steps, const int *formats,
                             const float *scales, const float *biases, const int *ranges, unsigned char *const *outs,
                             const size_t *out_bytes);
+
+/* Debug hooks used by the colour transform's tests (REVERSIBLE COLOUR TRANSFORM, above): the four hooks above on tasks that
+ * may have a REFERENCE (csrc/collect.h, csrc/deliver.h), each ONE launch or one host walk; a task without one is the
+ * task of the hooks above, byte for byte, and both kinds go into the same launch.
+ * nblic_amd_debug_collect_ref_host / nblic_amd_debug_collect_ref: ref / refs[k] (NULL: none) is a second source of the
+ * task's rows x cols and format with its own pitch and step in bytes -- ref_cap_bytes / ref_bytes[k] readable, uploaded at
+ * byte ref_base_offsets[k] (0 .. 255) of a region of its own -- and a pixel is (own - ref + 128) mod 256 of the two
+ * quantised elements.  They refuse (-1) what the hooks above refuse, and a reference that a source would be refused for.
+ * nblic_amd_debug_deliver_ref_host / nblic_amd_debug_deliver_ref: ref / refs[k] (NULL: none) is a plane of ref_rows x width
+ * bytes (uploaded at byte ref_base_offsets[k], 0 .. 15, of a zeroed region), and an element is made of
+ * (plane + ref - 128) mod 256.  gate_status: THREE ints per task, each as in nblic_amd_debug_deliver; a task delivers
+ * when none of them says otherwise.  step_bytes / steps: as in the _ex hooks; 0 or a NULL steps: the element size.  They
+ * refuse (-1) what the hooks above refuse, and a reference that does not hold the window's rows. */
+int nblic_amd_debug_collect_ref_host(const void *src, size_t cap_bytes, const void *ref, size_t ref_cap_bytes, size_t ref_pitch_bytes,
+                                     size_t ref_step_bytes, int rows, int cols, size_t pitch_bytes, size_t step_bytes, int format,
+                                     float scale, float bias, const int *range, unsigned char *out, size_t out_bytes,
+                                     unsigned long long *units, unsigned long long *chunks);
+int nblic_amd_debug_collect_ref(nblic_amd_ctx *ctx, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets,
+                                const void *const *refs, const size_t *ref_bytes, const size_t *ref_base_offsets,
+                                const size_t *ref_pitches, const size_t *ref_steps, const int *rows, const int *cols,
+                                const size_t *pitches, const size_t *steps, const int *formats, const float *scales,
+                                const float *biases, const int *ranges, unsigned char *const *outs, const size_t *out_bytes);
+int nblic_amd_debug_deliver_ref_host(const unsigned char *plane, int plane_rows, int width, const unsigned char *ref, int ref_rows,
+                                     const int *window, int format, float scale, float bias, int zero, const int *gate_status,
+                                     unsigned char *out, size_t out_bytes, size_t dst_offset, size_t pitch_bytes, size_t step_bytes,
+                                     unsigned long long *units, unsigned long long *chunks);
+int nblic_amd_debug_deliver_ref(nblic_amd_ctx *ctx, int n, const unsigned char *const *planes, const size_t *plane_bytes,
+                                const size_t *base_offsets, const unsigned char *const *refs, const size_t *ref_base_offsets,
+                                const int *ref_rows, const int *plane_rows, const int *widths, const int *windows, const int *formats,
+                                const float *scales, const float *biases, const int *zeros, const size_t *pitches, const size_t *steps,
+                                const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs, const int *gate_status);
 
 /* Debug hook used by the indexed effort-0 batch's host tests: QNBLIC's entropy stage (histogram normalisation, histogram
  * code, the rANS pass) on caller-made records, reporting the coder in front of entry rows as the batch's workers read it.

@@ -57,6 +57,7 @@ EXPORTS = (
     "nblic_amd_encode_batch_modes_from_to",
     "nblic_amd_encode_batch_modes_from", "nblic_amd_qencode_batch_from", "nblic_amd_encode_batch_indexed_from", "nblic_amd_qencode_batch_indexed_from",
     "nblic_amd_collect_stats", "nblic_amd_collect_ms", "nblic_amd_debug_collect_host", "nblic_amd_debug_collect",
+    "nblic_amd_debug_collect_ref_host", "nblic_amd_debug_collect_ref", "nblic_amd_debug_deliver_ref_host", "nblic_amd_debug_deliver_ref",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats", "nblic_amd_copy_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -294,6 +295,18 @@ def load_library() -> C.CDLL:
                                                      C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
         lib.nblic_amd_debug_collect.restype = C.c_int
         lib.nblic_amd_debug_collect.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, ip, ip, szp, szp, ip, fp, fp, ip, vpp, szp]
+    if hasattr(lib, "nblic_amd_debug_collect_ref"):                 # (an older build loaded through NBLIC_AMD_LIB has none of the four)
+        vpp, szp, fp, ullp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(C.c_ulonglong)
+        lib.nblic_amd_debug_collect_ref_host.restype = C.c_int
+        lib.nblic_amd_debug_collect_ref_host.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
+                                                         C.c_int, C.c_float, C.c_float, ip, C.c_void_p, C.c_size_t, ullp, ullp]
+        lib.nblic_amd_debug_collect_ref.restype = C.c_int
+        lib.nblic_amd_debug_collect_ref.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, vpp, szp, szp, szp, szp, ip, ip, szp, szp, ip, fp, fp, ip, vpp, szp]
+        lib.nblic_amd_debug_deliver_ref_host.restype = C.c_int
+        lib.nblic_amd_debug_deliver_ref_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, ip, C.c_int, C.c_float, C.c_float, C.c_int, ip, C.c_void_p,
+                                                         C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, ullp, ullp]
+        lib.nblic_amd_debug_deliver_ref.restype = C.c_int
+        lib.nblic_amd_debug_deliver_ref.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, vpp, szp, ip, ip, ip, ip, ip, fp, fp, ip, szp, szp, szp, szp, vpp, ip]
     if hasattr(lib, "nblic_amd_index_build_batch"):
         vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
         lib.nblic_amd_index_build_batch.restype = C.c_int
@@ -406,15 +419,21 @@ def deliver_units(rows: int, cols: int, fmt: int, step: Optional[int] = None) ->
 
 
 def deliver_host(plane: np.ndarray, window, fmt, scale: float = 1.0, bias: float = 0.0, pitch: Optional[int] = None, offset: int = 0,
-                 out_bytes: Optional[int] = None, zero: bool = False, gate_status: int = -1, info: Optional[dict] = None,
-                 step: Optional[int] = None) -> np.ndarray:
+                 out_bytes: Optional[int] = None, zero: bool = False, gate_status=-1, info: Optional[dict] = None,
+                 step: Optional[int] = None, ref: Optional[np.ndarray] = None) -> np.ndarray:
     """The delivery kernel's unit walk on the host (``nblic_amd_debug_deliver_host``; no device): the window
     ``(row0, row1, col0, col1)`` of the 2-D uint8 ``plane`` in format ``fmt`` (0 .. 3 or a dtype) goes to byte ``offset`` of
     a buffer of ``out_bytes`` bytes that holds 0x5A, rows ``pitch`` bytes apart (default: the window's row).  The buffer
     starts at a multiple of 16, so ``offset`` is the destination's residue as on the device.  Returns the buffer (uint8);
     ``info`` receives ``units`` and ``chunks``.  ``step`` (``nblic_amd_debug_deliver_host_ex``): the bytes between the
-    elements of a destination row; the default pitch is then ``cols * step``.  ``ValueError`` when refused."""
+    elements of a destination row; the default pitch is then ``cols * step``.  ``ref`` (``nblic_amd_debug_deliver_ref_host``):
+    the reference plane of a colour frame, 2-D uint8 of the plane's width -- the element is made of
+    ``(plane + ref - 128) & 255`` -- and ``gate_status`` may then be three statuses, one per plane of the frame.
+    ``ValueError`` when refused."""
     plane = np.ascontiguousarray(plane, np.uint8)
+    gates = [int(g) for g in gate_status] if hasattr(gate_status, "__len__") else None
+    if gates is not None and len(gates) != 3:
+        raise ValueError("deliver_host: one gate status, or three")
     fmt = fmt if isinstance(fmt, int) else deliver_format(fmt)
     r0, r1, c0, c1 = (int(v) for v in window)
     elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
@@ -427,6 +446,22 @@ def deliver_host(plane: np.ndarray, window, fmt, scale: float = 1.0, bias: float
     out = raw[lead: lead + int(out_bytes)]
     win = (C.c_int * 4)(r0, r1, c0, c1)
     units, chunks = C.c_ulonglong(0), C.c_ulonglong(0)
+    if ref is not None or gates is not None:
+        if step is not None and int(step) < 0:
+            raise ValueError("deliver_host: a negative step")
+        r = None if ref is None else np.ascontiguousarray(ref, np.uint8)
+        if r is not None and (r.ndim != 2 or plane.ndim != 2 or r.shape[1] != plane.shape[1]):
+            raise ValueError("deliver_host: the reference is a 2-D uint8 plane of the plane's width")
+        g3 = (C.c_int * 3)(*(gates if gates is not None else [int(gate_status), -1, -1]))
+        rc = load_library().nblic_amd_debug_deliver_ref_host(plane.ctypes.data if plane.size else None, plane.shape[0], plane.shape[1] if plane.ndim == 2 else 0,
+                                                             r.ctypes.data if r is not None and r.size else None, r.shape[0] if r is not None else 0, win, int(fmt),
+                                                             float(scale), float(bias), int(bool(zero)), g3, out.ctypes.data, out.size, int(offset), int(pitch),
+                                                             0 if step is None else int(step), C.byref(units), C.byref(chunks))
+        if rc != 0:
+            raise ValueError("nblic_amd_debug_deliver_ref_host refused its arguments")
+        if info is not None:
+            info["units"], info["chunks"] = int(units.value), int(chunks.value)
+        return out
     head = (plane.ctypes.data if plane.size else None, plane.shape[0], plane.shape[1] if plane.ndim == 2 else 0, win, int(fmt), float(scale), float(bias),
             int(bool(zero)), int(gate_status), out.ctypes.data, out.size, int(offset), int(pitch))
     if step is None:
@@ -600,13 +635,17 @@ def collect_numpy(values: np.ndarray, fmt, scale: float = 1.0, bias: float = 0.0
 
 def collect_host(array: np.ndarray, fmt, scale: float = 1.0, bias: float = 0.0, pitch: Optional[int] = None, step: Optional[int] = None,
                  offset: int = 0, rows: Optional[int] = None, cols: Optional[int] = None, cap: Optional[int] = None, px_range=None,
-                 info: Optional[dict] = None) -> np.ndarray:
+                 info: Optional[dict] = None, ref: Optional[np.ndarray] = None, ref_pitch: Optional[int] = None, ref_step: Optional[int] = None,
+                 ref_offset: int = 0, ref_cap: Optional[int] = None) -> np.ndarray:
     """The collect kernel's unit walk on the host (``nblic_amd_debug_collect_host``; no device).  With ``rows`` and ``cols``,
     ``array`` is a buffer of raw bytes in which element (0, 0) of the image lies at byte ``offset``, rows ``pitch`` bytes and
     the pixels of a row ``step`` bytes apart, ``cap`` bytes readable from there (default: to the buffer's end).  Without
     them ``array`` is a 2-D view whose shape and strides say all of that.  ``px_range``: the pixels (px0, px1) of the flat
     plane to write; the rest keeps 0x5A.  Returns the plane (rows x cols, uint8); ``info`` receives ``units`` and
-    ``chunks``.  ``ValueError`` when refused."""
+    ``chunks``.  ``ref`` (``nblic_amd_debug_collect_ref_host``): the reference source of a colour frame's difference
+    plane, of the same format -- a 2-D view of the image's shape whose strides say where its elements lie, or, with
+    ``ref_pitch`` or ``ref_step``, raw bytes with element (0, 0) at byte ``ref_offset`` and ``ref_cap`` bytes readable from
+    there; a pixel is then ``(own - ref + 128) & 255`` of the two quantised elements.  ``ValueError`` when refused."""
     fmt = fmt if isinstance(fmt, int) else collect_format(fmt)
     if rows is None or cols is None:
         if array.ndim != 2 or any(s < 0 for s in array.strides):
@@ -625,13 +664,70 @@ def collect_host(array: np.ndarray, fmt, scale: float = 1.0, bias: float = 0.0, 
     out = store[lead: lead + max(int(rows) * int(cols), 0)]
     rng = None if px_range is None else (C.c_int * 2)(int(px_range[0]), int(px_range[1]))
     units, chunks = C.c_ulonglong(0), C.c_ulonglong(0)
-    rc = load_library().nblic_amd_debug_collect_host(base, max(int(cap), 0), int(rows), int(cols), int(pitch), int(step), int(fmt), float(scale), float(bias),
-                                                     rng, out.ctypes.data if out.size else None, out.size, C.byref(units), C.byref(chunks))
+    if ref is not None:
+        elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
+        if ref_pitch is None and ref_step is None:
+            if ref.ndim != 2 or tuple(ref.shape) != (int(rows), int(cols)) or any(v < 0 for v in ref.strides):
+                raise ValueError("collect_host: the reference is a 2-D view of the image's shape, or raw bytes with ref_pitch / ref_step")
+            ref_pitch = ref.strides[0] if rows > 1 else max(ref.strides[0], cols * ref.strides[1])
+            ref_step = ref.strides[1] if cols > 1 else ref.itemsize
+            rbase, rcap = ref.ctypes.data, max(rows - 1, 0) * ref_pitch + max(cols - 1, 0) * ref_step + ref.itemsize
+        else:
+            rraw = ref.reshape(-1).view(np.uint8)
+            ref_pitch = cols * elem if ref_pitch is None else ref_pitch
+            ref_step = elem if ref_step is None else ref_step
+            rbase, rcap = rraw.ctypes.data + int(ref_offset), (rraw.size - int(ref_offset) if ref_cap is None else int(ref_cap))
+        if int(ref_pitch) < 0 or int(ref_step) < 0:
+            raise ValueError("collect_host: a negative pitch or step")
+        rc = load_library().nblic_amd_debug_collect_ref_host(base, max(int(cap), 0), rbase, max(int(rcap), 0), int(ref_pitch), int(ref_step), int(rows), int(cols),
+                                                             int(pitch), int(step), int(fmt), float(scale), float(bias), rng,
+                                                             out.ctypes.data if out.size else None, out.size, C.byref(units), C.byref(chunks))
+    else:
+        rc = load_library().nblic_amd_debug_collect_host(base, max(int(cap), 0), int(rows), int(cols), int(pitch), int(step), int(fmt), float(scale), float(bias),
+                                                         rng, out.ctypes.data if out.size else None, out.size, C.byref(units), C.byref(chunks))
     if rc != 0:
         raise ValueError("nblic_amd_debug_collect_host refused its arguments")
     if info is not None:
         info["units"], info["chunks"] = int(units.value), int(chunks.value)
     return out.reshape(int(rows), int(cols))
+
+
+FORMAT_RCT = 0x100                                                              # NBLIC_AMD_FORMAT_RCT: a flag bit in a call's format
+
+
+def rct_forward(r: np.ndarray, g: np.ndarray, b: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The reversible colour transform of three uint8 planes of one shape, on the host: ``(r - g + 128) mod 256``, ``g``,
+    ``(b - g + 128) mod 256`` -- the planes whose streams ``color="rct"`` writes, and what a decoder that knows nothing of
+    the transform gets back from them."""
+    r, g, b = (np.asarray(v) for v in (r, g, b))
+    if any(v.dtype != np.uint8 for v in (r, g, b)) or r.shape != g.shape or b.shape != g.shape:
+        raise ValueError("rct_forward: three uint8 arrays of one shape")
+    off = np.uint8(128)
+    return r - g + off, g.copy(), b - g + off                  # (uint8 arithmetic wraps)
+
+
+def rct_inverse(tr: np.ndarray, g: np.ndarray, tb: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The inverse of :func:`rct_forward`: ``(tr + g - 128) mod 256``, ``g``, ``(tb + g - 128) mod 256``."""
+    tr, g, tb = (np.asarray(v) for v in (tr, g, tb))
+    if any(v.dtype != np.uint8 for v in (tr, g, tb)) or tr.shape != g.shape or tb.shape != g.shape:
+        raise ValueError("rct_inverse: three uint8 arrays of one shape")
+    off = np.uint8(128)
+    return tr + g - off, g.copy(), tb + g - off
+
+
+def _color_flag(color, arg) -> int:
+    """The format flag ``color`` stands for.  With ``"rct"``, ``arg`` -- the sources or the destinations -- is a tensor
+    [N, 3, H, W] or a list of 3 F views, the R, G, B of frame f at 3 f, 3 f + 1, 3 f + 2."""
+    if color is None:
+        return 0
+    if color != "rct":
+        raise ValueError('color: None or "rct"')
+    if isinstance(arg, (list, tuple)):
+        if len(arg) % 3 != 0:
+            raise ValueError('color="rct": a list holds three views per frame')
+    elif len(tuple(arg.shape)) != 4 or int(arg.shape[1]) != 3:
+        raise ValueError('color="rct": a tensor [N, 3, H, W] (NHWC: permute it), or a list of three views per frame')
+    return FORMAT_RCT
 
 
 def _src_views(src):
@@ -1403,8 +1499,8 @@ class Context:
             raise RuntimeError("nblic_amd_deliver_stats failed")
         return int(v[0]), int(v[1])
 
-    def _dests_for(self, out, n, dims, rows, cols, scale, bias, layout):
-        """What the two _into calls make of ``out``: ("ex", dests, fmt) or ("plain", dests, fmt, scale, bias)."""
+    def _dests_for(self, out, n, dims, rows, cols, scale, bias, layout, ex: bool = False):
+        """What the two _into calls make of ``out``: ("ex", dests, fmt) or ("plain", dests, fmt, scale, bias); ``ex``: never the latter."""
         if layout not in ("rows", "any"):
             raise ValueError('layout: "rows" or "any"')
         if layout == "any":
@@ -1413,12 +1509,13 @@ class Context:
                 raise ValueError("out: one 2-D tensor per image")
             return ("ex",) + _dests_ex_of(views, dims, rows, cols, scale, bias)
         dests, fmt = _dests_of(_dest_tensors(out, n), dims, rows, cols)
-        if not hasattr(scale, "__len__") and not hasattr(bias, "__len__"):
+        if not ex and not hasattr(scale, "__len__") and not hasattr(bias, "__len__"):
             return ("plain", dests, fmt, scale, bias)
         scales, biases = _per_image_floats(scale, n, "scale"), _per_image_floats(bias, n, "bias")
         return ("ex", [(d[0], d[1], DELIVER_ELEM[fmt]) + tuple(d[2:]) + (scales[k], biases[k]) for k, d in enumerate(dests)], fmt)
 
-    def decode_batch_indexed_into(self, pairs, out, rows=None, cols=None, scale=1.0, bias=0.0, info: Optional[dict] = None, layout: str = "rows") -> List[int]:
+    def decode_batch_indexed_into(self, pairs, out, rows=None, cols=None, scale=1.0, bias=0.0, info: Optional[dict] = None, layout: str = "rows",
+                                  color: Optional[str] = None) -> List[int]:
         """A window of every image of ``decode_batch_indexed`` straight into device tensors: no pixel crosses the bus.
         ``out`` is one tensor [N, H', W'] or [N, 1, H', W'] on this context's device, or a list of 2-D tensors -- views
         with any batch and row stride, last stride 1; the dtype chooses the format: uint8 (a copy), float16, bfloat16 or
@@ -1432,15 +1529,22 @@ class Context:
         ``layout="any"``: ``out`` is one tensor [N, H', W'] or [N, C, H', W'] -- every channel is an image, n-major, as
         ``encode_batch_from`` reads them -- or a list of 2-D views, with any non-negative strides: a channels-last tensor and
         ``t.permute(0, 3, 1, 2)`` of a [N, H, W, C] batch are written where they lie, and the bytes between the elements
-        keep their contents.  ``scale`` / ``bias``: one value, or one per image (a mean and std per channel), in either layout."""
+        keep their contents.  ``scale`` / ``bias``: one value, or one per image (a mean and std per channel), in either layout.
+
+        ``color="rct"``: the streams are those of ``encode_batch_from(..., color="rct")`` -- 3 f, 3 f + 1, 3 f + 2 hold the
+        R - G, G and B - G planes of frame f -- and R and B are put together again on the way out, before ``scale`` and
+        ``bias``.  ``out`` is a tensor [N, 3, H', W'] (``layout="any"``) or a list of three views per frame (``ValueError``
+        otherwise); the three planes of a frame have one size and one window.  A frame stands or falls as a whole: all
+        three statuses are -1 when one of its planes or destinations is refused (nothing is written) or fails (zeros)."""
         n = len(pairs)
+        flag = _color_flag(color, out)
         dims = []
         for _, x in pairs:                                      # the head of an index names the geometry; the library checks all of it
             x = _bytes_arg(x if x is not None else b"")
             h, w = (int(v) for v in np.frombuffer(x[16:24].tobytes(), "<i4")) if x.size >= INDEX_HEAD_BYTES else (0, 0)
             dims.append((h, w) if 0 < h <= 65535 and 0 < w <= 65535 else (0, 0))
-        how = self._dests_for(out, n, dims, rows, cols, scale, bias, layout)
-        return self.decode_batch_indexed_to(pairs, *how[1:], info) if how[0] == "plain" else self.decode_batch_indexed_to_ex(pairs, how[1], how[2], info)
+        how = self._dests_for(out, n, dims, rows, cols, scale, bias, layout, ex=bool(flag))
+        return self.decode_batch_indexed_to(pairs, *how[1:], info) if how[0] == "plain" else self.decode_batch_indexed_to_ex(pairs, how[1], how[2] | flag, info)
 
     def decode_batch_to(self, streams, dests, fmt: int, scale: float = 1.0, bias: float = 0.0, info: Optional[dict] = None) -> List[int]:
         """``nblic_amd_decode_batch_to`` as it is; arguments and result as ``decode_batch_indexed_to``."""
@@ -1457,13 +1561,16 @@ class Context:
             info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
         return status
 
-    def decode_batch_into(self, streams, out, rows=None, cols=None, scale=1.0, bias=0.0, info: Optional[dict] = None, layout: str = "rows") -> List[int]:
+    def decode_batch_into(self, streams, out, rows=None, cols=None, scale=1.0, bias=0.0, info: Optional[dict] = None, layout: str = "rows",
+                          color: Optional[str] = None) -> List[int]:
         """``decode_batch`` with a window of every plane delivered into device tensors (no index: every stream is decoded
         whole, from its start).  ``out``, ``layout``, ``rows``, ``cols``, ``scale``, ``bias``, the result and ``info`` as
-        ``decode_batch_indexed_into``; a stream that fails on the device leaves zeros."""
+        ``decode_batch_indexed_into``; a stream that fails on the device leaves zeros.  ``color="rct"`` as there: the three
+        planes of a frame may be of different codecs and efforts."""
+        flag = _color_flag(color, out)
         dims = [_stream_dims(_bytes_arg(s if s is not None else b"")) or (0, 0) for s in streams]
-        how = self._dests_for(out, len(streams), dims, rows, cols, scale, bias, layout)
-        return self.decode_batch_to(streams, *how[1:], info) if how[0] == "plain" else self.decode_batch_to_ex(streams, how[1], how[2], info)
+        how = self._dests_for(out, len(streams), dims, rows, cols, scale, bias, layout, ex=bool(flag))
+        return self.decode_batch_to(streams, *how[1:], info) if how[0] == "plain" else self.decode_batch_to_ex(streams, how[1], how[2] | flag, info)
 
     def debug_deliver(self, tasks) -> List[np.ndarray]:
         """``nblic_amd_debug_deliver``: ONE k_deliver launch over ``tasks``, each a dict with ``plane`` (2-D uint8),
@@ -1606,7 +1713,7 @@ class Context:
         return outs, got
 
     def encode_batch_from(self, src, rows=None, cols=None, scale: float = 1.0, bias: float = 0.0, near=0, effort=1, every_rows=None,
-                          band_rows: int = 0, info: Optional[dict] = None, recon_out=None, recon_scale=1.0, recon_bias=0.0):
+                          band_rows: int = 0, info: Optional[dict] = None, recon_out=None, recon_scale=1.0, recon_bias=0.0, color: Optional[str] = None):
         """Encode images that lie in device memory in any layout, as pixels or as floats quantised on the way (the _from
         calls; include/nblic_amd.h says what the pixel of an element is).  ``src``: one tensor [N, H, W], one tensor
         [N, C, H, W] -- every channel is an image, n-major -- or a list of 2-D tensors or views, of ONE dtype (uint8,
@@ -1622,10 +1729,20 @@ class Context:
         or a list like ``src``, of any of the four dtypes and with any non-negative strides (``decode_batch_into`` with
         ``layout="any"`` takes the same), every image's the shape of what is encoded; ``recon_scale`` / ``recon_bias``
         normalise a float one, one value or one per image.  A destination the library refuses costs that reconstruction
-        only.  Not with effort 0 or ``every_rows``."""
+        only.  Not with effort 0 or ``every_rows``.
+
+        ``color="rct"``: ``src`` holds colour frames -- a tensor [N, 3, H, W] (an NHWC batch: ``permute(0, 3, 1, 2)``) or a
+        list of three views per frame, R, G, B -- and the streams 3 f, 3 f + 1, 3 f + 2 are those of the planes
+        ``(R - G + 128) mod 256``, ``G`` and ``(B - G + 128) mod 256`` (:func:`rct_forward` of the collected planes): ordinary
+        streams, which any decoder turns into those planes and ``decode_batch_into(..., color="rct")`` into the frame.
+        Lossless only (``near`` 0; no ``recon_out``): ``ValueError`` otherwise, and for any other channel count.  The three
+        sources of a frame have one size; a frame with a refused source has three ``None``."""
+        flag = _color_flag(color, src)
+        if flag and recon_out is not None:
+            raise ValueError('color="rct" is lossless: there is no reconstruction to deliver')
         srcs, fmt = _srcs_of(_src_views(src), rows, cols)
         if recon_out is None:
-            return self.encode_from_srcs(srcs, fmt, scale, bias, near, effort, every_rows, band_rows, info)
+            return self.encode_from_srcs(srcs, fmt | flag, scale, bias, near, effort, every_rows, band_rows, info)
         views = _src_views(recon_out)
         if len(views) != len(srcs):
             raise ValueError("recon_out: one 2-D tensor per image")
@@ -1662,6 +1779,82 @@ class Context:
         if rc != 0:
             raise RuntimeError("nblic_amd_debug_collect failed (%d)" % rc)
         return outs
+
+    def debug_collect_ref(self, tasks) -> List[np.ndarray]:
+        """``nblic_amd_debug_collect_ref``: :meth:`debug_collect` over tasks that may have a reference source -- ``ref`` (its
+        bytes, like ``raw``), ``ref_pitch`` and ``ref_step`` in bytes (default: contiguous) and ``ref_base_offset`` (0 .. 255).
+        Tasks with and without one go into the same launch."""
+        n = len(tasks)
+        raws, refs, hs, ws, pitches, steps, rpitches, rsteps, fmts, scales, biases, bases, rbases, ranges = ([] for _ in range(14))
+        for t in tasks:
+            fmt = t["fmt"] if isinstance(t["fmt"], int) else collect_format(t["fmt"])
+            elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
+            raws.append(np.ascontiguousarray(t["raw"]).reshape(-1).view(np.uint8))
+            refs.append(np.ascontiguousarray(t["ref"]).reshape(-1).view(np.uint8) if t.get("ref") is not None else None)
+            hs.append(int(t["rows"])); ws.append(int(t["cols"])); fmts.append(fmt)
+            pitches.append(int(t.get("pitch", int(t["cols"]) * elem))); steps.append(int(t.get("step", elem)))
+            rpitches.append(int(t.get("ref_pitch", int(t["cols"]) * elem))); rsteps.append(int(t.get("ref_step", elem)))
+            scales.append(float(t.get("scale", 1.0))); biases.append(float(t.get("bias", 0.0)))
+            bases.append(int(t.get("base_offset", 0))); rbases.append(int(t.get("ref_base_offset", 0)))
+            ranges += [int(v) for v in t.get("px_range", (0, 0))]
+        sizes = [2 * COLLECT_GUARD + ((max(h * w, 0) + 255) & ~255) for h, w in zip(hs, ws)]
+        outs = [np.zeros(b, np.uint8) for b in sizes]
+        m = max(n, 1)
+        vp = lambda arrs: (C.c_void_p * m)(*[a.ctypes.data if a is not None else None for a in arrs])
+        sz = lambda vals: (C.c_size_t * m)(*[int(v) for v in vals])
+        iv = lambda vals, k=1: (C.c_int * (m * k))(*[int(v) for v in vals])
+        fv = lambda vals: (C.c_float * m)(*vals)
+        rc = self.lib.nblic_amd_debug_collect_ref(self.handle, n, vp(raws), sz(r.size for r in raws), sz(bases),
+                                                  vp(refs), sz(r.size if r is not None else 0 for r in refs), sz(rbases), sz(rpitches), sz(rsteps),
+                                                  iv(hs), iv(ws), sz(pitches), sz(steps), iv(fmts), fv(scales), fv(biases), iv(ranges, 2), vp(outs), sz(sizes))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_collect_ref refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_collect_ref failed (%d)" % rc)
+        return outs
+
+    def debug_deliver_ref(self, tasks) -> List[np.ndarray]:
+        """``nblic_amd_debug_deliver_ref``: :meth:`debug_deliver` over tasks that may have a reference plane -- ``ref`` (2-D
+        uint8, the plane's width) with ``ref_base_offset`` (0 .. 15) -- and whose ``gate_status`` may be three statuses, one
+        per plane of the frame (one: the other two gates are not set).  Tasks with and without a reference go into the same
+        launch."""
+        n = len(tasks)
+        planes, refs, wins, fmts, scales, biases, zeros, pitches, offsets, sizes, bases, rbases, gates, steps = ([] for _ in range(14))
+        for t in tasks:
+            plane = np.ascontiguousarray(t["plane"], np.uint8)
+            ref = np.ascontiguousarray(t["ref"], np.uint8) if t.get("ref") is not None else None
+            fmt = t["fmt"] if isinstance(t["fmt"], int) else deliver_format(t["fmt"])
+            r0, r1, c0, c1 = (int(v) for v in t["window"])
+            elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
+            step = int(t.get("step", elem))
+            pitch = int(t.get("pitch", (c1 - c0) * step))
+            offset = int(t.get("offset", 0))
+            if step < 0 or plane.ndim != 2 or plane.size == 0 or (ref is not None and (ref.ndim != 2 or ref.size == 0 or ref.shape[1] != plane.shape[1])):
+                raise ValueError("debug_deliver_ref: 2-D uint8 planes, a reference of its plane's width, a step that is not negative")
+            g = t.get("gate_status", -1)
+            g = [int(v) for v in g] if hasattr(g, "__len__") else [int(g), -1, -1]
+            if len(g) != 3:
+                raise ValueError("debug_deliver_ref: one gate status, or three")
+            steps.append(step); planes.append(plane); refs.append(ref); wins += [r0, r1, c0, c1]; fmts.append(fmt)
+            scales.append(float(t.get("scale", 1.0))); biases.append(float(t.get("bias", 0.0))); zeros.append(int(bool(t.get("zero", False))))
+            pitches.append(pitch); offsets.append(offset)
+            sizes.append(int(t.get("out_bytes", offset + max(r1 - r0 - 1, 0) * pitch + max(c1 - c0 - 1, 0) * step + elem)))
+            bases.append(int(t.get("base_offset", 0))); rbases.append(int(t.get("ref_base_offset", 0))); gates += g
+        outs = [np.zeros(max(b, 1), np.uint8) for b in sizes]
+        m = max(n, 1)
+        vp = lambda arrs: (C.c_void_p * m)(*[a.ctypes.data if a is not None else None for a in arrs])
+        sz = lambda vals: (C.c_size_t * m)(*[int(v) for v in vals])
+        iv = lambda vals, k=1: (C.c_int * (m * k))(*[int(v) for v in vals])
+        fv = lambda vals: (C.c_float * m)(*vals)
+        rc = self.lib.nblic_amd_debug_deliver_ref(self.handle, n, vp(planes), sz(p.size for p in planes), sz(bases), vp(refs), sz(rbases),
+                                                  iv(r.shape[0] if r is not None else 0 for r in refs), iv(p.shape[0] for p in planes), iv(p.shape[1] for p in planes),
+                                                  iv(wins, 4), iv(fmts), fv(scales), fv(biases), iv(zeros), sz(pitches), sz(steps), sz(offsets), sz(sizes), vp(outs),
+                                                  iv(gates, 3))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_deliver_ref refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_deliver_ref failed (%d)" % rc)
+        return [o[:b] for o, b in zip(outs, sizes)]
 
     def indexed_decode_split(self) -> dict:
         """Host milliseconds of the last ``decode_batch_indexed`` (``nblic_amd_indexed_decode_split``)."""

@@ -8,6 +8,12 @@
 // one lane's work -- is sixteen consecutive bytes of the FLAT plane at a multiple of 16: it runs across row ends whenever
 // cols is no multiple of 16.  A task covers the pixels [px0, px1) of the flat plane (a whole image: [0, rows * cols); the
 // indexed batch: the rows of one band), so its first and its last unit may be shorter than sixteen pixels.
+//
+// A task with a REFERENCE writes the difference plane of the reversible colour transform (R - G, B - G of a frame whose
+// three colours are three sources): the reference is a second source of the same rows x cols, format, scale and bias --
+// the caller's G -- with a pitch and a step of its own, and pixel (row, col) is (own - ref + 128) & 255 of the two
+// elements there, each quantised as without a reference.  The reference is read where the caller keeps it, never from
+// another task's plane, so the tasks of a launch stay independent of each other.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -34,9 +40,11 @@ struct CollectTask {
     uint32_t format;                       // kCollectU8 .. kCollectF32
     float scale, bias;                     // float formats: float(x) * scale, rounded, + bias, rounded, then to a pixel
     uint32_t first_chunk;                  // chunks of the launch's tasks in front of this one
-    uint32_t pad;
+    uint32_t ref_step;                     // bytes between neighbouring pixels of a row of the reference
+    const uint8_t *ref;                    // not null: element (0, 0) of the REFERENCE source (below); a multiple of the element size
+    unsigned long long ref_pitch;          // bytes between the reference's rows
 };
-static_assert(sizeof(CollectTask) == 64, "uploaded as bytes");
+static_assert(sizeof(CollectTask) == 80, "uploaded as bytes");
 
 constexpr uint32_t kCollectUnitPixels = 16;
 constexpr uint32_t kCollectChunkUnits = 1024;                        // one workgroup: kIndexChunkBytes / 16 (serial_engine.hip asserts it)
@@ -75,6 +83,10 @@ CL_HD uint32_t collect_f16_to_f32_bits(uint32_t h) {
     return sign | ((113u - k) << 23) | ((mm & 0x3FFu) << 13);
 }
 
+CL_HD unsigned long long collect_ref_at(const CollectTask &t, uint32_t row, uint32_t col) {
+    return (unsigned long long)(row) * t.ref_pitch + (unsigned long long)(col) * t.ref_step;
+}
+
 // The pixel of one source element whose bits are in the low elem bytes of x: the element itself, or
 // float(x) * scale + bias with both operations rounded to float -- never fused -- NaN to 0, everything else clamped to
 // [0, 255] and rounded to nearest, ties to even.
@@ -99,6 +111,9 @@ CL_HD uint32_t collect_value(uint32_t x, uint32_t format, float scale, float bia
 #endif
 }
 
+// The pixel of a task with a reference: own and ref are collect_value of the two elements.
+CL_HD uint32_t collect_rct(uint32_t own, uint32_t ref) { return (own - ref + 128u) & 255u; }
+
 // Bytes from src that an image of rows x cols spans: its last element ends it.
 inline unsigned long long collect_extent(uint32_t rows, uint32_t cols, uint32_t format, unsigned long long pitch, unsigned long long step) {
     return (unsigned long long)(rows - 1) * pitch + (unsigned long long)(cols - 1) * step + collect_elem(format);
@@ -106,21 +121,27 @@ inline unsigned long long collect_extent(uint32_t rows, uint32_t cols, uint32_t 
 
 // What a task's SOURCE must satisfy: an image the encoders take, a pointer, pitch and step that are multiples of the
 // element size and not below it, a step and a pitch within their limits, an extent that cap_bytes holds, finite scale
-// and bias, and uint8 as a plain copy.
-inline bool collect_source_ok(const CollectTask &t, unsigned long long cap_bytes) {
+// and bias, and uint8 as a plain copy.  A reference is a source of its own: the same rules for its pointer, pitch and
+// step, and its extent inside ref_cap_bytes.
+inline bool collect_source_ok(const CollectTask &t, unsigned long long cap_bytes, unsigned long long ref_cap_bytes = 0) {
     if (!t.src || t.format >= kCollectFormats) return false;
     if (t.rows < 1 || t.cols < 1 || t.rows > kCollectMaxSide || t.cols > kCollectMaxSide) return false;
     const uint32_t elem = collect_elem(t.format);
     if (uintptr_t(t.src) % elem || t.pitch % elem || t.step % elem || t.step < elem || t.pitch < elem) return false;
     if (t.step > kCollectMaxStep || t.pitch > kCollectMaxPitch) return false;
     if (collect_extent(t.rows, t.cols, t.format, t.pitch, t.step) > cap_bytes) return false;
+    if (t.ref) {
+        if (uintptr_t(t.ref) % elem || t.ref_pitch % elem || t.ref_step % elem || t.ref_step < elem || t.ref_pitch < elem) return false;
+        if (t.ref_step > kCollectMaxStep || t.ref_pitch > kCollectMaxPitch) return false;
+        if (collect_extent(t.rows, t.cols, t.format, t.ref_pitch, t.ref_step) > ref_cap_bytes) return false;
+    }
     if (!(t.scale - t.scale == 0.0f) || !(t.bias - t.bias == 0.0f)) return false;          // NaN, infinite
     return t.format != kCollectU8 || (t.scale == 1.0f && t.bias == 0.0f);
 }
 // What a task must satisfy before a kernel or the host walk may run it: such a source, a pixel range inside the plane
 // and an aligned destination.
-inline bool collect_task_ok(const CollectTask &t, unsigned long long cap_bytes) {
-    return collect_source_ok(t, cap_bytes) && t.dst && uintptr_t(t.dst) % 16 == 0 && t.px0 < t.px1 && t.px1 <= t.rows * t.cols;
+inline bool collect_task_ok(const CollectTask &t, unsigned long long cap_bytes, unsigned long long ref_cap_bytes = 0) {
+    return collect_source_ok(t, cap_bytes, ref_cap_bytes) && t.dst && uintptr_t(t.dst) % 16 == 0 && t.px0 < t.px1 && t.px1 <= t.rows * t.cols;
 }
 
 // A source that is the collected plane already: nothing has to run for it.
@@ -137,7 +158,13 @@ inline void collect_host(const CollectTask &t) {
         for (uint32_t p = U.p_lo; p < U.p_hi; p++) {
             uint32_t x = 0;
             memcpy(&x, t.src + collect_src_at(t, row, col), elem);   // (little endian: the low elem bytes)
-            t.dst[p] = uint8_t(collect_value(x, t.format, t.scale, t.bias));
+            uint32_t v = collect_value(x, t.format, t.scale, t.bias);
+            if (t.ref) {
+                uint32_t y = 0;
+                memcpy(&y, t.ref + collect_ref_at(t, row, col), elem);
+                v = collect_rct(v, collect_value(y, t.format, t.scale, t.bias));
+            }
+            t.dst[p] = uint8_t(v);
             if (++col == t.cols) { col = 0; row++; }
         }
     }

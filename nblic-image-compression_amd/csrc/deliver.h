@@ -13,6 +13,11 @@
 // of an interleaved frame or the channels of a channels-last tensor do) knows no 16-byte rule: nothing is stored that is
 // wider than one element.  Its unit is sixteen consecutive pixels of one row, counted from col0; element (r, c) of the
 // window goes to dst + r * dst_pitch + c * dst_step and no other byte is written.
+//
+// A task with a REFERENCE undoes the reversible colour transform: its plane holds differences (R - G or B - G, + 128,
+// mod 256), the reference is the G plane of the same frame -- same width, given from the window's first row on -- and
+// the pixel of window position (r, c) is (src + ref - 128) & 255 of the two planes' bytes there; scale, bias and format
+// apply to that pixel.  The three planes of a frame stand or fall together: each of its tasks names all three gates.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -44,9 +49,12 @@ struct DeliverTask {
     uint32_t zero;                         // != 0: zero bytes instead of pixels
     uint32_t first_chunk;                  // chunks of the launch's tasks in front of this one
     uint32_t dst_step;                     // bytes between neighbouring elements of a destination row: the element size, or more (strided)
-    uint32_t pad_;
+    uint32_t ref_pitch;                    // bytes between the reference's rows: the image's width (= src_pitch)
+    const uint8_t *ref;                    // not null: the REFERENCE plane (below) at row row0, column 0
+    unsigned long long ref_bytes;          // readable bytes from ref: nothing outside [ref, ref + ref_bytes) is read
+    const SerialState *gate2, *gate3;      // further gates, like `gate`: every one that is not null must be kDone
 };
-static_assert(sizeof(DeliverTask) == 88, "uploaded as bytes");
+static_assert(sizeof(DeliverTask) == 120, "uploaded as bytes");
 
 constexpr uint32_t kDeliverUnitPixels = 16;
 constexpr uint32_t kDeliverChunkUnits = 1024;                        // one workgroup: kIndexChunkBytes / 16 (serial_engine.hip asserts it)
@@ -134,14 +142,19 @@ DL_HD uint32_t deliver_value(uint32_t px, uint32_t format, float scale, float bi
 #endif
 }
 
+// The pixel of a task with a reference: px and ref are the two planes' bytes.
+DL_HD uint32_t deliver_rct(uint32_t px, uint32_t ref) { return (px + ref - 128u) & 255u; }
+
 // What a task must satisfy before a kernel or the host walk may run it: a sound window inside a plane of src_rows rows
 // that the readable bytes hold, a destination pitch, step and pointer that are multiples of the element size and not
 // below it, contiguous rows that do not overlap (a strided task may have any pitch: a transposed view is one), no more
-// units than 32 bits count, and uint8 as a plain copy.
+// units than 32 bits count, and uint8 as a plain copy.  A reference has the plane's width as its pitch and holds the
+// window's rows inside its readable bytes.
 inline bool deliver_task_ok(const DeliverTask &t, uint32_t src_rows) {
     if (!t.src || !t.dst || t.format >= kDeliverFormats || t.src_pitch == 0) return false;
     if (t.row0 < 0 || t.row1 <= t.row0 || uint32_t(t.row1) > src_rows || t.col0 < 0 || t.col1 <= t.col0 || uint32_t(t.col1) > t.src_pitch) return false;
     if ((unsigned long long)(src_rows) * t.src_pitch > t.src_bytes) return false;
+    if (t.ref && (t.ref_pitch != t.src_pitch || (unsigned long long)(uint32_t(t.row1 - t.row0 - 1)) * t.ref_pitch + uint32_t(t.col1) > t.ref_bytes)) return false;
     const uint32_t elem = deliver_elem(t.format);
     if (uintptr_t(t.dst) % elem || t.dst_pitch % elem || t.dst_step % elem || t.dst_step < elem || t.dst_step > kDeliverMaxStep || t.dst_pitch > kDeliverMaxPitch) return false;
     if (t.dst_pitch < (deliver_strided(t) ? (unsigned long long)(elem) : (unsigned long long)(uint32_t(t.col1 - t.col0)) * elem)) return false;
@@ -160,18 +173,20 @@ inline unsigned long long deliver_extent(uint32_t rows, uint32_t cols, uint32_t 
 }
 
 // The host walk: every unit of the task, one after the other, element by element.  `gate_status` stands for the gate
-// record's status (the task's own gate pointer is not followed); pass 1 (kDone) for none.
-inline void deliver_host(const DeliverTask &t, int gate_status) {
+// record's status (the task's own gate pointers are not followed); pass 1 (kDone) for none.  gate2_status / gate3_status:
+// the same for the second and the third gate.
+inline void deliver_host(const DeliverTask &t, int gate_status, int gate2_status = 1, int gate3_status = 1) {
     const uint32_t elem = deliver_elem(t.format);
-    const bool zero = t.zero != 0 || gate_status != 1;
+    const bool zero = t.zero != 0 || gate_status != 1 || gate2_status != 1 || gate3_status != 1;
     const unsigned long long units = deliver_task_units(t);
     const bool strided = deliver_strided(t);
     for (unsigned long long u = 0; u < units; u++) {
         const DeliverUnit U = strided ? deliver_strided_unit_of(t, uint32_t(u)) : deliver_unit_of(t, uint32_t(u));
         const uint8_t *s = t.src + size_t(uint32_t(t.row0) + U.row) * t.src_pitch + uint32_t(t.col0);
+        const uint8_t *r = t.ref ? t.ref + size_t(U.row) * t.ref_pitch + uint32_t(t.col0) : nullptr;
         uint8_t *d = t.dst + size_t(U.row) * size_t(t.dst_pitch);
         for (uint32_t c = U.c_lo; c < U.c_hi; c++) {
-            const uint32_t v = zero ? 0u : deliver_value(s[c], t.format, t.scale, t.bias);
+            const uint32_t v = zero ? 0u : deliver_value(r ? deliver_rct(s[c], r[c]) : uint32_t(s[c]), t.format, t.scale, t.bias);
             memcpy(d + size_t(c) * t.dst_step, &v, elem);            // (little endian: the low elem bytes)
         }
     }

@@ -489,6 +489,7 @@ static SerialJob model_job(const uint8_t *img, uint8_t *recon, const E1Buffers &
 enum : uint8_t { kSrcRefused = 0, kSrcInPlace = 1, kSrcCollect = 2 };
 struct CollectFrom {
     const nblic_amd_src *srcs; uint32_t format; float scale, bias;
+    bool rct = false;                                                    // NBLIC_AMD_FORMAT_RCT: sources 3f, 3f + 1, 3f + 2 are R, G, B of frame f
     std::vector<uint8_t> how;
     std::vector<CollectTask> tasks;                                      // kSrcCollect: all but dst, px0, px1 and first_chunk
     std::vector<const uint8_t *> imgs; std::vector<int> hs, ws;
@@ -1703,7 +1704,19 @@ static bool decode_launch(const DecodeItem &first, const SerialJob *d_jobs, cons
 // ---- delivery to caller-owned device memory (deliver.h, serial_engine.h k_deliver) ----------------------------------------
 // What the _to calls hand down: one destination per image with its step and normalisation, one format per call.  The
 // calls without a step make theirs here (dests_ex): the element size, and the call's scale / bias in every image.
-struct DeliverTo { const nblic_amd_dest_ex *dests; uint32_t format; };
+// rct (NBLIC_AMD_FORMAT_RCT): images 3f, 3f + 1, 3f + 2 are the R - G, G and B - G planes of frame f, and R and B are put
+// together again on the way out (deliver.h: a task with a reference).
+struct DeliverTo { const nblic_amd_dest_ex *dests; uint32_t format; bool rct = false; };
+
+// NBLIC_AMD_FORMAT_RCT in a format argument of a _from or a _to_ex call: is it there?  It is taken off.
+static bool format_rct(int &format) {
+    const bool rct = format >= 0 && (format & NBLIC_AMD_FORMAT_RCT) != 0;
+    if (rct) format &= ~NBLIC_AMD_FORMAT_RCT;
+    return rct;
+}
+
+// Do the three tasks of a colour frame name the same window (in rows and columns of the image)?
+static bool same_window(const DeliverTask &a, const DeliverTask &b) { return a.row0 == b.row0 && a.row1 == b.row1 && a.col0 == b.col0 && a.col1 == b.col1; }
 
 static std::vector<nblic_amd_dest_ex> dests_ex(const nblic_amd_dest *dests, int n, int format, float scale, float bias) {
     std::vector<nblic_amd_dest_ex> ex(size_t(std::max(n, 0)));
@@ -1813,6 +1826,22 @@ static void collect_plan(const nblic_amd_ctx *c, CollectFrom &from, int n) {
         from.hs[i] = from.srcs[k].rows; from.ws[i] = from.srcs[k].cols;
         if (from.how[i] == kSrcInPlace) from.imgs[i] = from.tasks[i].src;
     }
+    if (!from.rct) return;
+    // Colour frames: R and B become tasks with the frame's G SOURCE as their reference (collect.h) -- collected even where
+    // they could be used in place -- and G stays what it was.  A frame with a refused source, or sources of unequal size, is
+    // refused as a whole.
+    for (size_t f = 0; f + 2 < count; f += 3) {
+        const CollectTask &G = from.tasks[f + 1];
+        bool ok = true;
+        for (size_t i = f; i < f + 3; i++) ok = ok && from.how[i] != kSrcRefused && from.hs[i] == from.hs[f] && from.ws[i] == from.ws[f];
+        for (size_t i = f; i < f + 3; i++) {
+            if (!ok) { from.how[i] = kSrcRefused; from.imgs[i] = nullptr; from.hs[i] = from.ws[i] = 0; continue; }
+            if (i == f + 1) continue;
+            CollectTask &T = from.tasks[i];
+            T.ref = G.src; T.ref_pitch = G.pitch; T.ref_step = G.step;
+            from.how[i] = kSrcCollect; from.imgs[i] = nullptr;
+        }
+    }
 }
 
 // Parses and validates the headers, uploads the streams (their lengths are known here: running dry is an error),
@@ -1847,6 +1876,29 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         arena += stream_buf_bytes(it.len) + up256(size_t(it.h) * size_t(it.w)) + up256(lsq_stats_bytes(it.kind, it.effort, it.w)) +
                  up256(record_state_bytes(it.kind)) + (it.kind ? up256(kQTab) : 0);
     }
+    if (to && to->rct) {
+        // a colour frame stands or falls as a whole: three lossless planes of one size, three destinations of one window
+        auto bytes_of = [](const DecodeItem &it) {
+            return stream_buf_bytes(it.len) + up256(size_t(it.h) * size_t(it.w)) + up256(lsq_stats_bytes(it.kind, it.effort, it.w)) + up256(record_state_bytes(it.kind)) + (it.kind ? up256(kQTab) : 0);
+        };
+        std::vector<int> at(size_t(n), -1);
+        for (size_t i = 0; i < items.size(); i++) at[size_t(items[i].k)] = int(i);
+        std::vector<uint8_t> keep(items.size(), 0);
+        for (int f = 0; f + 2 < n; f += 3) {
+            const int a = at[size_t(f)], b = at[size_t(f) + 1], d = at[size_t(f) + 2];
+            if (a < 0 || b < 0 || d < 0) continue;
+            const DecodeItem &A = items[size_t(a)], &B = items[size_t(b)], &D = items[size_t(d)];
+            if (A.h != B.h || A.h != D.h || A.w != B.w || A.w != D.w || A.near || B.near || D.near) continue;
+            if (!same_window(deliveries[size_t(a)], deliveries[size_t(b)]) || !same_window(deliveries[size_t(a)], deliveries[size_t(d)])) continue;
+            keep[size_t(a)] = keep[size_t(b)] = keep[size_t(d)] = 1;
+        }
+        std::vector<DecodeItem> kept_items; std::vector<DeliverTask> kept_tasks;
+        for (size_t i = 0; i < items.size(); i++) {
+            if (keep[i]) { kept_items.push_back(items[i]); kept_tasks.push_back(deliveries[i]); }
+            else arena -= bytes_of(items[i]);
+        }
+        items.swap(kept_items); deliveries.swap(kept_tasks);
+    }
     if (items.empty()) return true;
     std::stable_sort(items.begin(), items.end(), [](const DecodeItem &a, const DecodeItem &b) { return a.kind * 4 + a.effort < b.kind * 4 + b.effort; });
     const int m = int(items.size());
@@ -1877,6 +1929,20 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         if (to) {                                                        // gated by the job's record: a stream that fails on the device leaves zeros
             DeliverTask &T = deliveries[size_t(i)];
             T.src = recon; T.src_bytes = up256(size_t(it.h) * size_t(it.w)); T.gate = state;
+        }
+    }
+    const bool rct = to && to->rct;
+    if (rct) {                                                           // every task of a frame is gated by its three records; R and B refer to G's plane
+        std::vector<int> at(size_t(n), -1);
+        for (int i = 0; i < m; i++) at[size_t(items[size_t(i)].k)] = i;
+        for (int i = 0; i < m; i++) {
+            const int k = items[size_t(i)].k, f = k - k % 3;
+            const DeliverTask &G = deliveries[size_t(at[size_t(f) + 1])];
+            DeliverTask &T = deliveries[size_t(i)];
+            T.gate = jobs[size_t(at[size_t(f)])].state; T.gate2 = jobs[size_t(at[size_t(f) + 1])].state; T.gate3 = jobs[size_t(at[size_t(f) + 2])].state;
+            if (k % 3 == 1) continue;
+            const size_t skip = size_t(T.row0) * size_t(T.src_pitch);
+            T.ref = G.src + skip; T.ref_bytes = G.src_bytes - skip; T.ref_pitch = T.src_pitch;
         }
     }
     // Chunks of one (codec, effort) class, at most kDecodeChunk images each, alternate between two streams: a chunk's uploads,
@@ -1921,8 +1987,8 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
             if (hipMemcpyAsync(&heads[size_t(i)], jobs[size_t(i)].state, sizeof(SerialState), hipMemcpyDeviceToHost, ch.st) != hipSuccess) return false;
             if (!to && hipMemcpyAsync(imgs[it.k], jobs[size_t(i)].recon, size_t(it.h) * size_t(it.w), hipMemcpyDeviceToHost, ch.st) != hipSuccess) return false;
         }
-        // the chunk's windows: ONE launch on its stream, behind its decode launches
-        return !to || deliver_queue(deliveries.data() + ch.i0, size_t(ch.i1 - ch.i0), c->dec_deliver + ch.i0, ch.st, c);
+        // the chunk's windows: ONE launch on its stream, behind its decode launches (colour frames: one for the call, below)
+        return !to || rct || deliver_queue(deliveries.data() + ch.i0, size_t(ch.i1 - ch.i0), c->dec_deliver + ch.i0, ch.st, c);
     };
     for (size_t n = 0; n < chunks.size(); n++) {
         if (n >= 2 && hipStreamSynchronize(chunks[n].st) != hipSuccess) return fail("a chunk");      // heads[] of chunk n - 2 have landed before its stream is reused (its H2D reads heads of chunk n)
@@ -1930,8 +1996,20 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         if (n >= 1 && !download(chunks[n - 1])) return fail("a copy");
     }
     if (!download(chunks.back())) return fail("a copy");
+    if (rct) {
+        // The planes of a frame may lie in chunks of both streams, and the arena keeps them all: ONE delivery launch for the
+        // call on the first stream, behind an event that marks the end of the second one's work.
+        Event done2;
+        if (done2.create(hipEventDisableTiming) != hipSuccess || hipEventRecord(done2, c->dec_stream2) != hipSuccess ||
+            hipStreamWaitEvent(c->dec_stream, done2, 0) != hipSuccess ||
+            !deliver_queue(deliveries.data(), deliveries.size(), c->dec_deliver, c->dec_stream, c)) return fail("the colour delivery");
+        if (hipStreamSynchronize(c->dec_stream) != hipSuccess) return fail("the colour delivery");      // (done2 goes when this block ends)
+    }
     if (hipStreamSynchronize(c->dec_stream) != hipSuccess || hipStreamSynchronize(c->dec_stream2) != hipSuccess) return fail("the last chunk");
     for (int i = 0; i < m; i++) status[items[size_t(i)].k] = heads[size_t(i)].status == kDone ? 0 : -1;
+    if (rct)                                                             // what the gates did on the device: a frame with a failed plane has none
+        for (int f = 0; f + 2 < n; f += 3)
+            if (status[f] != 0 || status[f + 1] != 0 || status[f + 2] != 0) status[f] = status[f + 1] = status[f + 2] = -1;
     return true;
 }
 
@@ -3491,6 +3569,8 @@ struct IdxDecImage {
     uint32_t *d_verdict = nullptr;      // one word per inner boundary, from boundary seg0 | seg0 + 1 on
     SerialState last{};                 // the last segment's final header
     DeliverTask deliver{};              // decode_batch_indexed_to: the image's window and destination
+    bool live = false, bad = false;     // accepted by the host checks; found damaged after the decode
+    size_t plane_bytes = 0;             // readable from d_plane
     // a packed index: where its parts lie (for the device), the payload offsets, and this round's unpacked entries
     unsigned long long *d_desc = nullptr; uint32_t *d_offs = nullptr;
     IndexUnpackTask unpack{};           // all but the round's fields
@@ -3597,7 +3677,19 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
         }
         // (a round's segments s .. t of an image need its entries s .. t + 1 unpacked: no more than two per segment)
         per_seg_max = std::max(per_seg_max, up256(I.V.L.b) + up256(2 * I.V.L.b_bytes) + (I.V.packed ? 2 * up256(I.V.L.tab + 15) : 0));
-        plan_in.push_back(IndexedPlanImage{it.kind, it.effort, it.h, it.w, R, I.row0, I.row1});
+        I.live = true;
+    }
+    if (to && to->rct)                                                   // a colour frame stands or falls as a whole: three lossless planes of one size, one window
+        for (int f = 0; f + 2 < n; f += 3) {
+            IdxDecImage &A = all[size_t(f)], &B = all[size_t(f) + 1], &D = all[size_t(f) + 2];
+            const bool ok = A.live && B.live && D.live && A.it.h == B.it.h && A.it.h == D.it.h && A.it.w == B.it.w && A.it.w == D.it.w &&
+                            !A.it.near && !B.it.near && !D.it.near && same_window(A.deliver, B.deliver) && same_window(A.deliver, D.deliver);
+            if (!ok) A.live = B.live = D.live = false;
+        }
+    for (int k = 0; k < n; k++) {
+        IdxDecImage &I = all[size_t(k)];
+        if (!I.live) continue;
+        plan_in.push_back(IndexedPlanImage{I.it.kind, I.it.effort, I.it.h, I.it.w, I.V.H.every_rows, I.row0, I.row1});
         live.push_back(&I);
     }
     if (live.empty()) return -1;
@@ -3643,7 +3735,7 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
             I->d_index = I->d_stream + stream_buf_bytes(win);
             I->d_plane = I->d_index + index_bytes;
             if (to) {                                                    // the window's rows count from the plane's first: row `base` of the image
-                I->deliver.src = I->d_plane; I->deliver.src_bytes = plane_bytes;
+                I->deliver.src = I->d_plane; I->deliver.src_bytes = plane_bytes; I->plane_bytes = plane_bytes;
                 I->deliver.row0 -= I->base; I->deliver.row1 -= I->base;
             }
             if (it.kind) I->d_tab = I->d_plane + plane_bytes;
@@ -3831,9 +3923,23 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
         uint32_t bad = 0;
         for (int s = I->seg0; s < I->seg1; s++) bad |= verdicts[size_t(I->d_verdict - d_verdicts) + size_t(s - I->seg0)];
         const bool ended = I->row1 == I->it.h ? I->last.status == kDone : (I->last.status == kRunning && I->last.next_row == I->row1);
-        if (bad || !ended) {
+        I->bad = bad || !ended;
+        if (I->bad)
             fprintf(stderr, "[nblic_amd] indexed batch decode: image %d: %s\n", I->k,
                     bad ? "a segment does not end where the next entry starts (index and stream disagree)" : "the stream is damaged or ends too early");
+    }
+    if (to && to->rct)                                                   // a frame with a damaged plane has none; R and B refer to G's plane, whose first row may be another
+        for (IdxDecImage *I : live) {
+            const size_t f = size_t(I->k - I->k % 3);
+            IdxDecImage &G = all[f + 1];
+            if (all[f].bad || G.bad || all[f + 2].bad) continue;
+            if (I->k % 3 == 1) continue;
+            const size_t skip = size_t(I->row0 - G.base) * size_t(I->it.w);
+            I->deliver.ref = G.d_plane + skip; I->deliver.ref_bytes = G.plane_bytes - skip; I->deliver.ref_pitch = uint32_t(I->it.w);
+        }
+    for (IdxDecImage *I : live) {
+        const size_t f = size_t(I->k - I->k % 3);
+        if (I->bad || (to && to->rct && (all[f].bad || all[f + 1].bad || all[f + 2].bad))) {
             if (to) { I->deliver.zero = 1; deliveries.push_back(I->deliver); }
             else memset(outs[I->k], 0, I->out_bytes);
             continue;
@@ -4860,11 +4966,22 @@ static bool debug_deliver_task(DeliverTask &T, int plane_rows, int width, const 
     return pitch <= (size_t(1) << 40);
 }
 
+// (ref / refs: the reference planes of the _ref hooks, ref_rows x width bytes each; gates: statuses per task -- one without, three with refs)
 static int debug_deliver_host(const unsigned char *plane, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero, int gate_status,
-                              unsigned char *out, size_t out_bytes, size_t dst_offset, size_t pitch_bytes, size_t step_bytes, unsigned long long *units, unsigned long long *chunks);
+                              unsigned char *out, size_t out_bytes, size_t dst_offset, size_t pitch_bytes, size_t step_bytes, unsigned long long *units, unsigned long long *chunks,
+                              const unsigned char *ref = nullptr, int ref_rows = 0, int gate2_status = -1, int gate3_status = -1);
 static int debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const *planes, const size_t *plane_bytes, const size_t *base_offsets, const int *plane_rows,
                          const int *widths, const int *windows, const int *formats, const float *scales, const float *biases, const int *zeros, const size_t *pitches,
-                         const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs, const int *gate_status);
+                         const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs, const int *gate_status,
+                         const unsigned char *const *refs = nullptr, const size_t *ref_base_offsets = nullptr, const int *ref_rows = nullptr);
+
+// The reference of a debug task: the plane at `ref` has ref_rows rows of the task's width; the task names it from its
+// window's first row on.  false: it does not reach that row.
+static bool debug_deliver_ref(DeliverTask &T, const uint8_t *ref, int ref_rows, size_t readable) {
+    if (ref_rows <= T.row0 || size_t(T.row0) * T.src_pitch > readable) return false;
+    T.ref = ref + size_t(T.row0) * T.src_pitch; T.ref_pitch = T.src_pitch; T.ref_bytes = readable - size_t(T.row0) * T.src_pitch;
+    return true;
+}
 
 // Host only: the shared unit walk (deliver.h deliver_host) over the caller's plane of plane_rows x width into out + dst_offset,
 // one unit after the other.  The unit grid follows the destination's address as the kernel's does, so a caller that wants
@@ -4882,17 +4999,27 @@ int nblic_amd_debug_deliver_host_ex(const unsigned char *plane, int plane_rows, 
 }
 static int debug_deliver_host(const unsigned char *plane, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero,
                               int gate_status, unsigned char *out, size_t out_bytes, size_t dst_offset, size_t pitch_bytes, size_t step_bytes,
-                              unsigned long long *units, unsigned long long *chunks) {
+                              unsigned long long *units, unsigned long long *chunks, const unsigned char *ref, int ref_rows, int gate2_status, int gate3_status) {
     DeliverTask T;
     if (!plane || !out || !debug_deliver_task(T, plane_rows, width, window, format, scale, bias, zero, pitch_bytes, step_bytes)) return -1;
     T.src = plane; T.src_bytes = size_t(plane_rows) * size_t(width);
     T.dst = out + dst_offset;
+    if (ref && (ref_rows < 1 || !debug_deliver_ref(T, ref, ref_rows, size_t(ref_rows) * size_t(width)))) return -1;
     if (dst_offset > out_bytes || !deliver_task_ok(T, uint32_t(plane_rows))) return -1;
     if (deliver_extent(uint32_t(T.row1 - T.row0), uint32_t(T.col1 - T.col0), T.format, pitch_bytes, T.dst_step) > out_bytes - dst_offset) return -1;
     if (units) *units = deliver_task_units(T);
     if (chunks) *chunks = deliver_task_chunks(T);
-    deliver_host(T, gate_status == -1 ? int(kDone) : gate_status);
+    deliver_host(T, gate_status == -1 ? int(kDone) : gate_status, gate2_status == -1 ? int(kDone) : gate2_status, gate3_status == -1 ? int(kDone) : gate3_status);
     return 0;
+}
+// The host walk of a task with a reference plane (ref_rows x width bytes; NULL: none) and three gate statuses; step_bytes 0
+// stands for the element size.
+int nblic_amd_debug_deliver_ref_host(const unsigned char *plane, int plane_rows, int width, const unsigned char *ref, int ref_rows, const int *window, int format,
+                                     float scale, float bias, int zero, const int *gate_status, unsigned char *out, size_t out_bytes, size_t dst_offset,
+                                     size_t pitch_bytes, size_t step_bytes, unsigned long long *units, unsigned long long *chunks) {
+    if (!gate_status) return -1;
+    return debug_deliver_host(plane, plane_rows, width, window, format, scale, bias, zero, gate_status[0], out, out_bytes, dst_offset, pitch_bytes, step_bytes, units, chunks,
+                              ref, ref_rows, gate_status[1], gate_status[2]);
 }
 
 // ONE k_deliver launch over n caller-made planes as n tasks.  Plane k (plane_rows[k] x widths[k]) is uploaded at byte
@@ -4914,17 +5041,30 @@ int nblic_amd_debug_deliver_ex(nblic_amd_ctx *c, int n, const unsigned char *con
     for (int k = 0; k < n; k++) if (steps[k] == 0) return -1;
     return debug_deliver(c, n, planes, plane_bytes, base_offsets, plane_rows, widths, windows, formats, scales, biases, zeros, pitches, steps, dst_offsets, out_bytes, outs, gate_status);
 }
+// ONE k_deliver launch like nblic_amd_debug_deliver_ex (steps may be NULL: the element size) over tasks that may have a
+// reference: refs[k] (NULL: none) is a plane of ref_rows[k] x widths[k] bytes, uploaded at byte ref_base_offsets[k] (0 .. 15)
+// of a zeroed region like the planes.  gate_status: THREE ints per task, each as in nblic_amd_debug_deliver.
+int nblic_amd_debug_deliver_ref(nblic_amd_ctx *c, int n, const unsigned char *const *planes, const size_t *plane_bytes, const size_t *base_offsets,
+                                const unsigned char *const *refs, const size_t *ref_base_offsets, const int *ref_rows,
+                                const int *plane_rows, const int *widths, const int *windows, const int *formats, const float *scales, const float *biases,
+                                const int *zeros, const size_t *pitches, const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes,
+                                unsigned char *const *outs, const int *gate_status) {
+    if (!refs || !ref_base_offsets || !ref_rows) return -1;
+    return debug_deliver(c, n, planes, plane_bytes, base_offsets, plane_rows, widths, windows, formats, scales, biases, zeros, pitches, steps, dst_offsets, out_bytes, outs, gate_status,
+                         refs, ref_base_offsets, ref_rows);
+}
 static int debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const *planes, const size_t *plane_bytes, const size_t *base_offsets,
                          const int *plane_rows, const int *widths, const int *windows, const int *formats, const float *scales, const float *biases,
                          const int *zeros, const size_t *pitches, const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs,
-                         const int *gate_status) {
+                         const int *gate_status, const unsigned char *const *refs, const size_t *ref_base_offsets, const int *ref_rows) {
     constexpr int kMaxTasks = 65536;
     constexpr uint8_t kPattern = 0x5A;
     if (!c || n < 1 || n > kMaxTasks || !planes || !plane_bytes || !base_offsets || !plane_rows || !widths || !windows || !formats || !scales || !biases ||
         !zeros || !pitches || !dst_offsets || !out_bytes || !outs || !gate_status) return -1;
     const size_t count = size_t(n);
     std::vector<DeliverTask> tasks(count);
-    std::vector<size_t> plane_at(count), out_at(count);
+    std::vector<size_t> plane_at(count), out_at(count), ref_at(count, 0);
+    const size_t n_gates = refs ? 3 : 1;                                 // statuses, and records on the device, per task
     size_t planes_total = 0, outs_total = 0;
     for (int k = 0; k < n; k++) {
         const size_t i = size_t(k);
@@ -4934,13 +5074,17 @@ static int debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const *pl
         if (plane_bytes[k] != size_t(plane_rows[k]) * size_t(widths[k]) || plane_bytes[k] > (size_t(1) << 30) || out_bytes[k] > (size_t(1) << 30) || dst_offsets[k] > out_bytes[k]) return -1;
         T.src_bytes = up256(plane_bytes[k]);
         plane_at[i] = planes_total; planes_total += up256(base_offsets[k] + T.src_bytes + 16);
+        if (refs && refs[k]) {
+            if (ref_base_offsets[k] > 15 || ref_rows[k] < 1 || size_t(ref_rows[k]) * size_t(widths[k]) > (size_t(1) << 30)) return -1;
+            ref_at[i] = planes_total; planes_total += up256(ref_base_offsets[k] + up256(size_t(ref_rows[k]) * size_t(widths[k])) + 16);
+        }
         out_at[i] = outs_total; outs_total += up256(out_bytes[k]);
     }
     if (hipSetDevice(c->device) != hipSuccess) return -2;
     Stream st;
     DevPool mem;
     uint8_t *d_planes = mem.make<uint8_t>(planes_total), *d_outs = mem.make<uint8_t>(outs_total);
-    SerialState *d_gates = mem.make<SerialState>(count);
+    SerialState *d_gates = mem.make<SerialState>(count * n_gates);
     DeliverTask *d_tasks = mem.make<DeliverTask>(count);
     if (!d_planes || !d_outs || !d_gates || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
     for (int k = 0; k < n; k++) {                                        // the addresses are known now: the rest of the checks
@@ -4948,19 +5092,27 @@ static int debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const *pl
         DeliverTask &T = tasks[i];
         T.src = d_planes + plane_at[i] + base_offsets[k];
         T.dst = d_outs + out_at[i] + dst_offsets[k];
-        if (gate_status[k] != -1) T.gate = d_gates + i;
-        if (!deliver_task_ok(T, uint32_t(plane_rows[k])) ||
+        if (gate_status[n_gates * i] != -1) T.gate = d_gates + n_gates * i;
+        if (refs) {
+            if (gate_status[3 * i + 1] != -1) T.gate2 = d_gates + 3 * i + 1;
+            if (gate_status[3 * i + 2] != -1) T.gate3 = d_gates + 3 * i + 2;
+            if (refs[k] && !debug_deliver_ref(T, d_planes + ref_at[i] + ref_base_offsets[k], ref_rows[k], up256(size_t(ref_rows[k]) * size_t(widths[k])))) return -1;
+        }
+        if (!deliver_task_ok(T, uint32_t(plane_rows[k])) || (T.ref && uint32_t(ref_rows[k]) < uint32_t(T.row1)) ||
             deliver_extent(uint32_t(T.row1 - T.row0), uint32_t(T.col1 - T.col0), T.format, T.dst_pitch, T.dst_step) > out_bytes[k] - dst_offsets[k]) return -1;
     }
     std::vector<uint8_t> back(outs_total);
-    std::vector<SerialState> gates(count);
-    for (int k = 0; k < n; k++) gates[size_t(k)].status = gate_status[k];
+    std::vector<SerialState> gates(count * n_gates);
+    for (size_t k = 0; k < gates.size(); k++) gates[k].status = gate_status[k];
     const bool ok = [&]() -> bool {
         HIP_OK(hipMemsetAsync(d_planes, 0, planes_total, st));
         HIP_OK(hipMemsetAsync(d_outs, kPattern, outs_total, st));
-        HIP_OK(hipMemcpyAsync(d_gates, gates.data(), count * sizeof(SerialState), hipMemcpyHostToDevice, st));
-        for (int k = 0; k < n; k++)
+        HIP_OK(hipMemcpyAsync(d_gates, gates.data(), gates.size() * sizeof(SerialState), hipMemcpyHostToDevice, st));
+        for (int k = 0; k < n; k++) {
             HIP_OK(hipMemcpyAsync(d_planes + plane_at[size_t(k)] + base_offsets[k], planes[k], plane_bytes[k], hipMemcpyHostToDevice, st));
+            if (refs && refs[k])
+                HIP_OK(hipMemcpyAsync(d_planes + ref_at[size_t(k)] + ref_base_offsets[k], refs[k], size_t(ref_rows[k]) * size_t(widths[k]), hipMemcpyHostToDevice, st));
+        }
         deliver_stats_reset(c);
         if (!deliver_queue(tasks.data(), count, d_tasks, st, c)) return false;
         HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
@@ -4984,16 +5136,40 @@ static bool debug_collect_task(CollectTask &T, const void *src, int rows, int co
     T.format = uint32_t(format); T.scale = scale; T.bias = bias;
     return !range || (range[0] >= 0 && range[1] >= 0);
 }
+static bool debug_collect_ref(CollectTask &T, const void *ref, size_t pitch, size_t step) {
+    if (step > 0xFFFFFFFFull) return false;                              // (collect_source_ok holds it against its limit)
+    T.ref = static_cast<const uint8_t *>(ref); T.ref_pitch = pitch; T.ref_step = uint32_t(step);
+    return true;
+}
+static int debug_collect_host(const void *src, size_t cap_bytes, const void *ref, size_t ref_cap_bytes, size_t ref_pitch_bytes, size_t ref_step_bytes, int rows, int cols,
+                              size_t pitch_bytes, size_t step_bytes, int format, float scale, float bias, const int *range, unsigned char *out, size_t out_bytes,
+                              unsigned long long *units, unsigned long long *chunks);
+static int debug_collect(nblic_amd_ctx *c, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets,
+                         const void *const *refs, const size_t *ref_bytes, const size_t *ref_base_offsets, const size_t *ref_pitches, const size_t *ref_steps,
+                         const int *rows, const int *cols, const size_t *pitches, const size_t *steps, const int *formats, const float *scales, const float *biases,
+                         const int *ranges, unsigned char *const *outs, const size_t *out_bytes);
 
 // Host only: the shared unit walk (collect.h collect_host) over the source at src -- cap_bytes readable from there -- into
 // the plane at out, which must be a multiple of 16 and hold rows x cols bytes.  range: the pixels [px0, px1) of the flat plane
 // (NULL: all of it; px1 == 0: to the end).  -1: refused.
 int nblic_amd_debug_collect_host(const void *src, size_t cap_bytes, int rows, int cols, size_t pitch_bytes, size_t step_bytes, int format, float scale,
                                  float bias, const int *range, unsigned char *out, size_t out_bytes, unsigned long long *units, unsigned long long *chunks) {
+    return debug_collect_host(src, cap_bytes, nullptr, 0, 0, 0, rows, cols, pitch_bytes, step_bytes, format, scale, bias, range, out, out_bytes, units, chunks);
+}
+// The same with a reference source (NULL: none): ref_cap_bytes readable from ref, its own pitch and step.
+int nblic_amd_debug_collect_ref_host(const void *src, size_t cap_bytes, const void *ref, size_t ref_cap_bytes, size_t ref_pitch_bytes, size_t ref_step_bytes,
+                                     int rows, int cols, size_t pitch_bytes, size_t step_bytes, int format, float scale, float bias, const int *range,
+                                     unsigned char *out, size_t out_bytes, unsigned long long *units, unsigned long long *chunks) {
+    return debug_collect_host(src, cap_bytes, ref, ref_cap_bytes, ref_pitch_bytes, ref_step_bytes, rows, cols, pitch_bytes, step_bytes, format, scale, bias, range, out, out_bytes, units, chunks);
+}
+static int debug_collect_host(const void *src, size_t cap_bytes, const void *ref, size_t ref_cap_bytes, size_t ref_pitch_bytes, size_t ref_step_bytes, int rows, int cols,
+                              size_t pitch_bytes, size_t step_bytes, int format, float scale, float bias, const int *range, unsigned char *out, size_t out_bytes,
+                              unsigned long long *units, unsigned long long *chunks) {
     CollectTask T;
     if (!src || !out || !debug_collect_task(T, src, rows, cols, format, scale, bias, pitch_bytes, step_bytes, range)) return -1;
     T.dst = out;
-    if (!collect_task_ok(T, cap_bytes) || size_t(T.rows) * size_t(T.cols) > out_bytes) return -1;
+    if (ref && !debug_collect_ref(T, ref, ref_pitch_bytes, ref_step_bytes)) return -1;
+    if (!collect_task_ok(T, cap_bytes, ref_cap_bytes) || size_t(T.rows) * size_t(T.cols) > out_bytes) return -1;
     if (units) *units = collect_task_units(T);
     if (chunks) *chunks = collect_task_chunks(T);
     collect_host(T);
@@ -5008,12 +5184,27 @@ int nblic_amd_debug_collect_host(const void *src, size_t cap_bytes, int rows, in
 int nblic_amd_debug_collect(nblic_amd_ctx *c, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets, const int *rows,
                             const int *cols, const size_t *pitches, const size_t *steps, const int *formats, const float *scales, const float *biases,
                             const int *ranges, unsigned char *const *outs, const size_t *out_bytes) {
+    return debug_collect(c, n, srcs, src_bytes, base_offsets, nullptr, nullptr, nullptr, nullptr, nullptr, rows, cols, pitches, steps, formats, scales, biases, ranges, outs, out_bytes);
+}
+// The same launch over tasks that may have a reference: refs[k] (NULL: none) is a second source of ref_bytes[k] bytes with
+// its own pitch and step, uploaded at byte ref_base_offsets[k] (0 .. 255) of a region of its own like the sources'.
+int nblic_amd_debug_collect_ref(nblic_amd_ctx *c, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets,
+                                const void *const *refs, const size_t *ref_bytes, const size_t *ref_base_offsets, const size_t *ref_pitches, const size_t *ref_steps,
+                                const int *rows, const int *cols, const size_t *pitches, const size_t *steps, const int *formats, const float *scales, const float *biases,
+                                const int *ranges, unsigned char *const *outs, const size_t *out_bytes) {
+    if (!refs || !ref_bytes || !ref_base_offsets || !ref_pitches || !ref_steps) return -1;
+    return debug_collect(c, n, srcs, src_bytes, base_offsets, refs, ref_bytes, ref_base_offsets, ref_pitches, ref_steps, rows, cols, pitches, steps, formats, scales, biases, ranges, outs, out_bytes);
+}
+static int debug_collect(nblic_amd_ctx *c, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets,
+                         const void *const *refs, const size_t *ref_bytes, const size_t *ref_base_offsets, const size_t *ref_pitches, const size_t *ref_steps,
+                         const int *rows, const int *cols, const size_t *pitches, const size_t *steps, const int *formats, const float *scales, const float *biases,
+                         const int *ranges, unsigned char *const *outs, const size_t *out_bytes) {
     constexpr int kMaxTasks = 65536;
     constexpr size_t kGuard = 256;
     if (!c || n < 1 || n > kMaxTasks || !srcs || !src_bytes || !base_offsets || !rows || !cols || !pitches || !steps || !formats || !scales || !biases || !outs || !out_bytes) return -1;
     const size_t count = size_t(n);
     std::vector<CollectTask> tasks(count);
-    std::vector<size_t> src_at(count), out_at(count);
+    std::vector<size_t> src_at(count), out_at(count), ref_at(count, 0);
     size_t srcs_total = 0, outs_total = 0;
     for (int k = 0; k < n; k++) {
         const size_t i = size_t(k);
@@ -5022,6 +5213,10 @@ int nblic_amd_debug_collect(nblic_amd_ctx *c, int n, const void *const *srcs, co
         const size_t plane = size_t(rows[k]) * size_t(cols[k]);
         if (plane > (size_t(1) << 30) || out_bytes[k] != kGuard + up256(plane) + kGuard) return -1;
         src_at[i] = srcs_total; srcs_total += up256(base_offsets[k] + src_bytes[k] + 256);
+        if (refs && refs[k]) {
+            if (ref_base_offsets[k] > 255 || ref_bytes[k] > (size_t(1) << 30)) return -1;
+            ref_at[i] = srcs_total; srcs_total += up256(ref_base_offsets[k] + ref_bytes[k] + 256);
+        }
         out_at[i] = outs_total; outs_total += out_bytes[k];
     }
     if (hipSetDevice(c->device) != hipSuccess) return -2;
@@ -5036,7 +5231,8 @@ int nblic_amd_debug_collect(nblic_amd_ctx *c, int n, const void *const *srcs, co
         CollectTask &T = tasks[i];
         T.src = d_srcs + src_at[i] + base_offsets[k];
         T.dst = d_outs + out_at[i] + kGuard;
-        if (!collect_task_ok(T, src_bytes[k])) return -1;                // nothing outside the uploaded bytes is the task's to read
+        if (refs && refs[k] && !debug_collect_ref(T, d_srcs + ref_at[i] + ref_base_offsets[k], ref_pitches[k], ref_steps[k])) return -1;
+        if (!collect_task_ok(T, src_bytes[k], T.ref ? ref_bytes[k] : 0)) return -1;                // nothing outside the uploaded bytes is the task's to read
         T.first_chunk = uint32_t(chunks); chunks += collect_task_chunks(T);
     }
     if (chunks >= (1ull << 31)) return -1;
@@ -5046,6 +5242,8 @@ int nblic_amd_debug_collect(nblic_amd_ctx *c, int n, const void *const *srcs, co
         HIP_OK(hipMemsetAsync(d_outs, 0x5A, outs_total, st));
         for (int k = 0; k < n; k++)
             HIP_OK(hipMemcpyAsync(d_srcs + src_at[size_t(k)] + base_offsets[k], srcs[k], src_bytes[k], hipMemcpyHostToDevice, st));
+        for (int k = 0; k < n; k++)
+            if (refs && refs[k]) HIP_OK(hipMemcpyAsync(d_srcs + ref_at[size_t(k)] + ref_base_offsets[k], refs[k], ref_bytes[k], hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d_tasks, tasks.data(), count * sizeof(CollectTask), hipMemcpyHostToDevice, st));
         if (!collect_launch(d_tasks, n, uint32_t(chunks), st)) return false;
         HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
@@ -5224,9 +5422,11 @@ int nblic_amd_decode_batch_to(nblic_amd_ctx *c, int n_images, const unsigned cha
 }
 int nblic_amd_decode_batch_to_ex(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens, const nblic_amd_dest_ex *dests,
                                  int format, int *heights, int *widths, int *nears, int *efforts, int *status) {
+    const bool rct = format_rct(format);
     if (!c || c->broken || n_images < 0 || !streams || !stream_lens || !dests || !heights || !widths || !nears || !efforts || !status || format < 0 || format >= int(kDeliverFormats)) return -1;
+    if (rct && n_images % 3 != 0) return -1;
     for (int k = 0; k < n_images; k++) if (!streams[k]) return -1;
-    const DeliverTo to{dests, uint32_t(format)};
+    const DeliverTo to{dests, uint32_t(format), rct};
     std::lock_guard<std::mutex> g(c->api);
     deliver_stats_reset(c);
     if (!decode_batch(c, n_images, streams, stream_lens, nullptr, nullptr, heights, widths, nears, efforts, status, &to)) return -1;
@@ -5368,6 +5568,8 @@ int nblic_amd_qencode_batch_indexed(nblic_amd_ctx *c, int n_images, const unsign
 // ---- ENCODE FROM DEVICE MEMORY: the four batch encoders on sources instead of planes ------------------------------------------
 // What every _from call starts with: the whole-call refusals, then the sources checked one by one (collect_plan).
 static bool collect_from_begin(nblic_amd_ctx *c, int n, const nblic_amd_src *srcs, int format, float scale, float bias, CollectFrom &from) {
+    from.rct = format_rct(format);
+    if (from.rct && n % 3 != 0) return false;
     if (!c || c->broken || n < 0 || !srcs || !deliver_args_ok(format, scale, bias) || hipSetDevice(c->device) != hipSuccess) return false;
     from.srcs = srcs; from.format = uint32_t(format); from.scale = scale; from.bias = bias;
     collect_plan(c, from, n);
@@ -5378,6 +5580,8 @@ int nblic_amd_encode_batch_modes_from(nblic_amd_ctx *c, int n_images, const nbli
                                       const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
                                       unsigned char *const *recons) {
     CollectFrom from{};
+    if (format >= 0 && (format & NBLIC_AMD_FORMAT_RCT) && nears)         // a difference plane off by +-near wraps to +-255 in R or B
+        for (int k = 0; k < n_images; k++) if (nears[k] > 0) return -1;
     if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from)) return -1;
     const bool ok = run_batch(c, nblic_amd_ctx::SubmitItem{nullptr, 0, n_images, from.imgs.data(), true, from.hs.data(), from.ws.data(), outs, out_caps, out_lens, nears, efforts, recons, &from});
     if (nothing_outstanding(c)) for (auto &g : c->groups) collect_timing(c, g);       // (nblic_amd_stage_times, as nblic_amd_encode_batch leaves them)
@@ -5387,7 +5591,7 @@ int nblic_amd_encode_batch_modes_from_to(nblic_amd_ctx *c, int n_images, const n
                                          const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
                                          const nblic_amd_dest_ex *recons, int recon_format) {
     CollectFrom from{};
-    if (!recons || recon_format < 0 || recon_format >= int(kDeliverFormats)) return -1;
+    if (!recons || recon_format < 0 || recon_format >= int(kDeliverFormats) || format < 0 || format >= int(kCollectFormats)) return -1;      // (no colour frames here)
     if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from)) return -1;
     const DeliverTo to{recons, uint32_t(recon_format)};
     from.recon_tasks.assign(size_t(n_images), DeliverTask{}); from.recon_ok.assign(size_t(n_images), 0);
@@ -5461,8 +5665,9 @@ int nblic_amd_decode_batch_indexed_to(nblic_amd_ctx *c, int n_images, const unsi
 int nblic_amd_decode_batch_indexed_to_ex(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
                                          const void *const *indexes, const size_t *index_lens, const nblic_amd_dest_ex *dests, int format,
                                          int *heights, int *widths, int *nears, int *efforts, int *status) {
-    if (!dests || format < 0 || format >= int(kDeliverFormats)) return -1;
-    const DeliverTo to{dests, uint32_t(format)};
+    const bool rct = format_rct(format);
+    if (!dests || format < 0 || format >= int(kDeliverFormats) || (rct && n_images % 3 != 0)) return -1;
+    const DeliverTo to{dests, uint32_t(format), rct};
     deliver_stats_reset(c);
     return decode_batch_indexed(c, n_images, streams, stream_lens, indexes, index_lens, nullptr, nullptr, nullptr, nullptr, heights, widths, nears, efforts, status, &to);
 }

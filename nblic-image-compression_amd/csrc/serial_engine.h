@@ -190,7 +190,8 @@ bool index_capture_launch(const IndexCaptureTask *d_tasks, int n, uint32_t chunk
 // a unit = at most sixteen pixels of one row whose destination starts at a multiple of 16 bytes.  The source row starts at
 // any byte (odd widths, any col0) and is read as aligned words shifted into place; the destination gets 16-byte stores but
 // for a row's head and tail.  uint8 is a copy; float16 / bfloat16 / float32 are float(px) * scale + bias, two roundings, then
-// round-to-nearest-even into the format.  A task with `zero`, or whose gate record is not kDone, writes zero bytes.
+// round-to-nearest-even into the format.  A task with `zero`, or with a gate record that is not kDone, writes zero bytes.
+// A task with a reference plane (a colour frame's R - G or B - G) delivers (px + ref - 128) & 255 in place of px.
 // d_tasks[0..n) with first_chunk filled in (from 0), `chunks` their sum.  false: the launch failed.
 bool deliver_launch(const DeliverTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
 
@@ -198,7 +199,8 @@ bool deliver_launch(const DeliverTask *d_tasks, int n, uint32_t chunks, hipStrea
 // k_collect, the delivery's twin: tasks with first_chunk, one workgroup per chunk of kCollectChunkUnits units, a unit =
 // sixteen consecutive bytes of the flat plane at a multiple of 16.  The source has any pitch and any step between the pixels
 // of a row; uint8 is a copy, float16 / bfloat16 / float32 are float(x) * scale + bias, two roundings, NaN to 0, clamped to
-// [0, 255] and rounded to nearest even.  d_tasks[0..n) with first_chunk filled in (from 0), `chunks` their sum.
+// [0, 255] and rounded to nearest even.  A task with a reference source writes (own - ref + 128) & 255 of the two pixels.
+// d_tasks[0..n) with first_chunk filled in (from 0), `chunks` their sum.
 // false: the launch failed.
 bool collect_launch(const CollectTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
 

@@ -1854,7 +1854,11 @@ __device__ __forceinline__ void deliver_strided_chunk(const DeliverTask &T, bool
         const uint32_t c = U.c_lo + p % kDeliverUnitPixels;
         if (c >= U.c_hi) continue;
         uint32_t v = 0u;
-        if (!zero) v = deliver_value(gp(T.src)[size_t(uint32_t(T.row0) + U.row) * T.src_pitch + size_t(T.col0) + c], T.format, T.scale, T.bias);
+        if (!zero) {
+            uint32_t px = gp(T.src)[size_t(uint32_t(T.row0) + U.row) * T.src_pitch + size_t(T.col0) + c];
+            if (T.ref) px = deliver_rct(px, gp(T.ref)[size_t(U.row) * T.ref_pitch + size_t(T.col0) + c]);
+            v = deliver_value(px, T.format, T.scale, T.bias);
+        }
         NB_GLOBAL uint8_t *d = gp(T.dst) + size_t(U.row) * size_t(T.dst_pitch) + size_t(c) * size_t(T.dst_step);
         if (elem == 1) *d = uint8_t(v);
         else if (elem == 2) *(NB_GLOBAL uint16_t *)d = uint16_t(v);
@@ -1867,7 +1871,8 @@ __device__ __forceinline__ void deliver_strided_chunk(const DeliverTask &T, bool
 // No LDS, no atomics; nothing is read outside the task's readable bytes and nothing written outside the window's rows.
 __global__ void __launch_bounds__(kIndexThreads) k_deliver(const DeliverTask *__restrict__ tasks, int n) {
     const DeliverTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
-    const bool zero = T.zero != 0 || (T.gate && gp(T.gate)->status != kDone);
+    const bool zero = T.zero != 0 || (T.gate && gp(T.gate)->status != kDone) || (T.gate2 && gp(T.gate2)->status != kDone) ||
+                      (T.gate3 && gp(T.gate3)->status != kDone);
     const uint32_t units = uint32_t(deliver_task_units(T)), u0 = (blockIdx.x - T.first_chunk) * kDeliverChunkUnits;
     const uint32_t elem = deliver_elem(T.format);
     const uintptr_t lo = uintptr_t(T.src), hi = lo + T.src_bytes;
@@ -1881,7 +1886,18 @@ __global__ void __launch_bounds__(kIndexThreads) k_deliver(const DeliverTask *__
         NB_GLOBAL uint8_t *d = gp(T.dst) + size_t(U.row) * size_t(T.dst_pitch) + ptrdiff_t(U.c0) * ptrdiff_t(elem);
         u32x4 px = u32x4{0u, 0u, 0u, 0u};
         if (!zero) px = deliver_load(gp(T.src) + size_t(uint32_t(T.row0) + U.row) * T.src_pitch + size_t(T.col0) + ptrdiff_t(U.c0), lo, hi, k_lo, k_hi);
-        const uint32_t w[4] = {px.x, px.y, px.z, px.w};
+        uint32_t w[4] = {px.x, px.y, px.z, px.w};
+        if (!zero && T.ref) {                                            // the same sixteen slots of the reference: the inverse transform, byte by byte
+            const u32x4 rf = deliver_load(gp(T.ref) + size_t(U.row) * T.ref_pitch + size_t(T.col0) + ptrdiff_t(U.c0), uintptr_t(T.ref), uintptr_t(T.ref) + T.ref_bytes, k_lo, k_hi);
+            const uint32_t r[4] = {rf.x, rf.y, rf.z, rf.w};
+#pragma unroll
+            for (uint32_t b = 0; b < 4; b++) {
+                uint32_t x = 0u;
+#pragma unroll
+                for (uint32_t k = 0; k < 4; k++) x |= deliver_rct((w[b] >> (8 * k)) & 0xFFu, (r[b] >> (8 * k)) & 0xFFu) << (8 * k);
+                w[b] = x;
+            }
+        }
         auto pixel = [&](uint32_t k) { return (w[k >> 2] >> ((k & 3) * 8)) & 0xFFu; };
         switch (T.format) {                                              // (zero: +0.0 is zero bytes in every format)
             case kDeliverU8: deliver_store<1>(d, k_lo, k_hi, pixel); break;
@@ -1901,51 +1917,70 @@ bool deliver_launch(const DeliverTask *d_tasks, int n, uint32_t chunks, hipStrea
 // ---- collection: images out of caller-owned device memory into the encoders' planes (collect.h CollectTask) ------------------
 static_assert(kCollectChunkUnits == kIndexChunkUnits, "collect.h states it for host-only code");
 
+// The sixteen pixels of a unit out of ONE source (the task's own, or its reference): slot k in byte k of word[], the slots
+// outside [k_lo, k_hi) zero.  (row, col): the image position of slot k_lo.  Sixteen source elements that are neighbours in
+// one row at a multiple of four bytes are read in aligned words, every other unit element by element: no byte is read
+// that is not part of an element of the image.
+__device__ __forceinline__ void collect_unit_load(const CollectTask &T, const NB_GLOBAL uint8_t *src, unsigned long long pitch, uint32_t step,
+                                                  uint32_t row, uint32_t col, uint32_t k_lo, uint32_t k_hi, uint32_t word[4]) {
+    const uint32_t elem = collect_elem(T.format);
+    const NB_GLOBAL uint8_t *s = src + (unsigned long long)(row) * pitch + (unsigned long long)(col) * step;
+    word[0] = word[1] = word[2] = word[3] = 0u;
+    if (step == elem && k_hi - k_lo == 16 && T.cols - col >= 16 && !(uintptr_t(s) & 3)) {
+        const NB_GLOBAL uint32_t *q = (const NB_GLOBAL uint32_t *)s;
+        if (elem == 1) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) word[i] = q[i];
+        } else if (elem == 2) {
+#pragma unroll
+            for (uint32_t i = 0; i < 8; i++) {
+                const uint32_t x = q[i];
+                word[i >> 1] |= (collect_value(x & 0xFFFFu, T.format, T.scale, T.bias) | (collect_value(x >> 16, T.format, T.scale, T.bias) << 8)) << ((i & 1) * 16);
+            }
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 16; i++) word[i >> 2] |= collect_value(q[i], kCollectF32, T.scale, T.bias) << ((i & 3) * 8);
+        }
+        return;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++) {
+        if (k < k_lo || k >= k_hi) continue;
+        uint32_t x;
+        if (elem == 1) x = *s;
+        else if (elem == 2) x = *(const NB_GLOBAL uint16_t *)s;
+        else x = *(const NB_GLOBAL uint32_t *)s;
+        word[k >> 2] |= collect_value(x, T.format, T.scale, T.bias) << ((k & 3) * 8);
+        if (++col == T.cols) { col = 0; row++; s = src + (unsigned long long)(row) * pitch; } else s += step;
+    }
+}
+
 // One workgroup per chunk of kCollectChunkUnits units, one unit per lane and step: sixteen consecutive bytes of the flat
-// plane (collect.h).  A unit whose sixteen source elements are neighbours in one row at a multiple of four bytes is read
-// in aligned words, every other one element by element: no byte is read that is not part of an element of the image.  A
-// whole unit is one 16-byte store; the shorter first and last units of a task are written in words and bytes.  No LDS, no
-// atomics; nothing is written outside the task's pixels [px0, px1).
+// plane (collect.h), loaded by collect_unit_load.  A task with a reference loads the same sixteen positions of the
+// reference too and stores (own - ref + 128) & 255 (collect.h collect_rct).  A whole unit is one 16-byte store; the
+// shorter first and last units of a task are written in words and bytes.  No LDS, no atomics; nothing is written outside
+// the task's pixels [px0, px1).
 __global__ void __launch_bounds__(kIndexThreads) k_collect(const CollectTask *__restrict__ tasks, int n) {
     const CollectTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
     const uint32_t units = collect_task_units(T), u0 = (blockIdx.x - T.first_chunk) * kCollectChunkUnits;
-    const uint32_t elem = collect_elem(T.format);
-    const NB_GLOBAL uint8_t *src = gp(T.src);
     for (uint32_t j = threadIdx.x; j < kCollectChunkUnits; j += kIndexThreads) {
         const uint32_t u = u0 + j;
         if (u >= units) break;
         const CollectUnit U = collect_unit_of(T, u);
         const uint32_t k_lo = U.p_lo - U.p0, k_hi = U.p_hi - U.p0;
-        uint32_t row = U.p_lo / T.cols, col = U.p_lo - row * T.cols;
-        const NB_GLOBAL uint8_t *s = src + collect_src_at(T, row, col);
-        uint32_t word[4] = {0u, 0u, 0u, 0u};
-        if (T.step == elem && k_hi - k_lo == 16 && T.cols - col >= 16 && !(uintptr_t(s) & 3)) {
-            const NB_GLOBAL uint32_t *q = (const NB_GLOBAL uint32_t *)s;
-            if (elem == 1) {
+        const uint32_t row = U.p_lo / T.cols, col = U.p_lo - row * T.cols;
+        uint32_t word[4];
+        collect_unit_load(T, gp(T.src), T.pitch, T.step, row, col, k_lo, k_hi, word);
+        if (T.ref) {
+            uint32_t ref[4];
+            collect_unit_load(T, gp(T.ref), T.ref_pitch, T.ref_step, row, col, k_lo, k_hi, ref);
 #pragma unroll
-                for (int i = 0; i < 4; i++) word[i] = q[i];
-            } else if (elem == 2) {
+            for (uint32_t b = 0; b < 4; b++) {
+                uint32_t w = 0u;
 #pragma unroll
-                for (uint32_t i = 0; i < 8; i++) {
-                    const uint32_t x = q[i];
-                    word[i >> 1] |= (collect_value(x & 0xFFFFu, T.format, T.scale, T.bias) | (collect_value(x >> 16, T.format, T.scale, T.bias) << 8)) << ((i & 1) * 16);
-                }
-            } else {
-#pragma unroll
-                for (uint32_t i = 0; i < 16; i++) word[i >> 2] |= collect_value(q[i], kCollectF32, T.scale, T.bias) << ((i & 3) * 8);
+                for (uint32_t k = 0; k < 4; k++) w |= collect_rct((word[b] >> (8 * k)) & 0xFFu, (ref[b] >> (8 * k)) & 0xFFu) << (8 * k);
+                word[b] = w;
             }
-            *(NB_GLOBAL u32x4 *)(gp(T.dst) + U.p0) = u32x4{word[0], word[1], word[2], word[3]};
-            continue;
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < 16; k++) {
-            if (k < k_lo || k >= k_hi) continue;
-            uint32_t x;
-            if (elem == 1) x = *s;
-            else if (elem == 2) x = *(const NB_GLOBAL uint16_t *)s;
-            else x = *(const NB_GLOBAL uint32_t *)s;
-            word[k >> 2] |= collect_value(x, T.format, T.scale, T.bias) << ((k & 3) * 8);
-            if (++col == T.cols) { col = 0; row++; s = src + collect_src_at(T, row, 0); } else s += T.step;
         }
         NB_GLOBAL uint8_t *d = gp(T.dst) + U.p0;
         if (k_hi - k_lo == 16) { *(NB_GLOBAL u32x4 *)d = u32x4{word[0], word[1], word[2], word[3]}; continue; }

@@ -3,7 +3,9 @@
 // the image's extent and the plane one of exactly rows x cols bytes -- a read or a store outside them is an overrun the
 // sanitizer reports -- gaps between the elements hold NaN (0xFF), and every byte is compared with a plain loop that knows
 // nothing of units and rounds through doubles; the units of a task must tile its pixels in order, each at a multiple of
-// 16.  Build and run:
+// 16.  Tasks with a reference (the colour transform's difference planes) have a second block of exactly the reference's
+// extent, in a layout of its own, and are compared with (own - ref + 128) mod 256 of the two plain loops' pixels.
+// Build and run:
 //   g++ -std=c++17 -O2 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -o collect_check tools/collect_check.cpp && ./collect_check
 #include <cmath>
 #include <cstdio>
@@ -92,6 +94,44 @@ static int one_task(std::mt19937 &rng, uint32_t format, uint32_t rows, uint32_t 
     return 0;
 }
 
+// A task with a reference: the own source and the reference in layouts of their own (step and slack in elements), each a
+// block of exactly its extent.
+static int one_ref_task(std::mt19937 &rng, uint32_t format, uint32_t rows, uint32_t cols, uint32_t step_elems, size_t slack_elems, uint32_t ref_step_elems,
+                        size_t ref_slack_elems, size_t residue, size_t ref_residue, float scale, float bias, uint32_t px0, uint32_t px1) {
+    const uint32_t elem = collect_elem(format);
+    const size_t step = size_t(step_elems) * elem, pitch = (size_t(cols - 1) * step_elems + 1 + slack_elems) * elem;
+    const size_t ref_step = size_t(ref_step_elems) * elem, ref_pitch = (size_t(cols - 1) * ref_step_elems + 1 + ref_slack_elems) * elem;
+    const size_t extent = size_t(collect_extent(rows, cols, format, pitch, step)), ref_extent = size_t(collect_extent(rows, cols, format, ref_pitch, ref_step));
+    void *own_mem = nullptr, *ref_mem = nullptr, *plane_mem = nullptr;
+    CHECK(posix_memalign(&own_mem, 16, residue + extent) == 0 && posix_memalign(&ref_mem, 16, ref_residue + ref_extent) == 0 &&
+          posix_memalign(&plane_mem, 16, size_t(rows) * cols) == 0);
+    uint8_t *src = static_cast<uint8_t *>(own_mem) + residue, *ref = static_cast<uint8_t *>(ref_mem) + ref_residue, *plane = static_cast<uint8_t *>(plane_mem);
+    memset(own_mem, 0xFF, residue + extent);
+    memset(ref_mem, 0xFF, ref_residue + ref_extent);
+    memset(plane, 0x5A, size_t(rows) * cols);
+    std::vector<uint32_t> elems(size_t(rows) * cols), ref_elems(size_t(rows) * cols);
+    for (uint32_t r = 0; r < rows; r++)
+        for (uint32_t c = 0; c < cols; c++) {
+            const uint32_t x = element_bits(rng, format), y = element_bits(rng, format);
+            elems[size_t(r) * cols + c] = x; ref_elems[size_t(r) * cols + c] = y;
+            memcpy(src + size_t(r) * pitch + size_t(c) * step, &x, elem);
+            memcpy(ref + size_t(r) * ref_pitch + size_t(c) * ref_step, &y, elem);
+        }
+    CollectTask T{};
+    T.src = src; T.dst = plane; T.pitch = pitch; T.step = uint32_t(step); T.rows = rows; T.cols = cols; T.px0 = px0; T.px1 = px1;
+    T.format = format; T.scale = scale; T.bias = bias;
+    T.ref = ref; T.ref_pitch = ref_pitch; T.ref_step = uint32_t(ref_step);
+    CHECK(collect_task_ok(T, extent, ref_extent));
+    CHECK(!collect_task_ok(T, extent, ref_extent - 1) && !collect_task_ok(T, extent - 1, ref_extent) && !collect_task_ok(T, extent));
+    collect_host(T);
+    for (uint32_t p = 0; p < rows * cols; p++) {
+        const uint8_t want = uint8_t((int(pixel_ref(elems[p], format, scale, bias)) - int(pixel_ref(ref_elems[p], format, scale, bias)) + 128 + 256) % 256);
+        CHECK(plane[p] == (p >= px0 && p < px1 ? want : 0x5A));
+    }
+    free(own_mem); free(ref_mem); free(plane);
+    return 0;
+}
+
 static int refusals() {
     alignas(16) static uint8_t src[4096], dst[256];
     CollectTask S{};
@@ -124,6 +164,22 @@ static int refusals() {
     T = S; T.dst = nullptr; CHECK(!collect_task_ok(T, cap));
     T = S; T.px1 = 33; CHECK(!collect_task_ok(T, cap));
     T = S; T.px0 = 32; CHECK(!collect_task_ok(T, cap));
+    // a reference is checked like a source, against its own readable bytes
+    CollectTask R = S;
+    R.ref = src + 2048; R.ref_pitch = 32; R.ref_step = 4;
+    const unsigned long long rcap = collect_extent(4, 8, kCollectF16, 32, 4);
+    CHECK(collect_task_ok(R, cap, rcap) && !collect_task_ok(R, cap, rcap - 1) && !collect_task_ok(R, cap) && !collect_task_ok(R, cap - 1, rcap));
+    T = R; T.ref = src + 2049; CHECK(!collect_task_ok(T, cap, rcap));
+    T = R; T.ref_pitch = 33; CHECK(!collect_task_ok(T, cap, ~0ull));
+    T = R; T.ref_step = 3; CHECK(!collect_task_ok(T, cap, ~0ull));
+    T = R; T.ref_step = 0; CHECK(!collect_task_ok(T, cap, rcap));
+    T = R; T.ref_pitch = 0; CHECK(!collect_task_ok(T, cap, rcap));
+    T = R; T.ref_step = kCollectMaxStep + 2; CHECK(!collect_task_ok(T, cap, ~0ull));
+    T = R; T.ref_step = kCollectMaxStep; CHECK(collect_task_ok(T, cap, ~0ull));
+    T = R; T.ref_pitch = kCollectMaxPitch + 2; CHECK(!collect_task_ok(T, cap, ~0ull));
+    T = R; T.ref_pitch = kCollectMaxPitch; CHECK(collect_task_ok(T, cap, ~0ull));
+    for (uint32_t a = 0; a < 256; a++)
+        for (uint32_t b = 0; b < 256; b++) CHECK(collect_rct(a, b) == uint32_t((int(a) - int(b) + 128 + 256) % 256));
     CHECK(collect_in_place(kCollectU8, 8, 1, 8) && !collect_in_place(kCollectU8, 9, 1, 8) && !collect_in_place(kCollectU8, 8, 2, 8) && !collect_in_place(kCollectF16, 8, 1, 8));
     return 0;
 }
@@ -152,6 +208,25 @@ int main() {
     if (one_task(rng, kCollectF16, 130, 129, 1, 3, false, 2, 255.0f, 0.0f, 0, 130 * 129)) return 1;
     if (one_task(rng, kCollectU8, 130, 129, 3, 1, false, 5, 1.0f, 0.0f, 129 * 7, 129 * 100)) return 1;
     tasks += 2;
+    // tasks with a reference: own source and reference in every pair of steps, other slack and residue each; pixel ranges;
+    // rows that end inside units (17 x 33) and the chunk crossed (129 x 129)
+    long referenced = 0;
+    for (uint32_t format = 0; format < kCollectFormats; format++) {
+        const uint32_t elem = collect_elem(format);
+        const uint32_t shapes[][2] = {{1, 1}, {1, 17}, {3, 5}, {17, 33}, {2, 16}, {129, 129}};
+        for (auto &hw : shapes)
+            for (uint32_t own_step : steps)
+                for (uint32_t ref_step : steps) {
+                    if (hw[0] == 129 && own_step == 3) continue;
+                    const float *nb = format == kCollectU8 ? norms[0] : norms[rng() % 6];
+                    const uint32_t n = hw[0] * hw[1];
+                    uint32_t px0 = 0, px1 = n;
+                    if (rng() % 2 == 0) { px0 = rng() % n; px1 = px0 + 1 + rng() % (n - px0); }
+                    if (one_ref_task(rng, format, hw[0], hw[1], own_step, rng() % 4, ref_step, rng() % 4, size_t(rng() % (16 / elem)) * elem,
+                                     size_t(rng() % (16 / elem)) * elem, nb[0], nb[1], px0, px1)) return 1;
+                    referenced++;
+                }
+    }
     // every float16 and every bfloat16 pattern, and float32 around every k + 0.5
     for (const float *nb : {norms[0], norms[1], norms[2]})
         for (uint32_t x = 0; x < 65536; x++) {
@@ -172,6 +247,6 @@ int main() {
         memcpy(&b, &t[0], 4);
         CHECK(collect_value(b, kCollectF32, 1.0f, 0.0f) == uint32_t(t[1]));
     }
-    printf("collect_check: %ld tasks, the refusals, 2 x 3 x 65536 values, all bytes as expected\n", tasks);
+    printf("collect_check: %ld tasks and %ld with a reference, the refusals, 2 x 3 x 65536 values, all bytes as expected\n", tasks, referenced);
     return 0;
 }

@@ -5,7 +5,9 @@
 // slot 0 at a multiple of 16 bytes; float16 is compared with a conversion through doubles (half_ref).  The same for
 // strided tasks (a step of 2 .. 7 elements between the elements of a row, any pitch from the row's up, and transposed:
 // pitch = one element, step = rows elements): the block ends with the last element's last byte, and every byte between
-// the elements must keep its pattern.  Build and run:
+// the elements must keep its pattern.  Tasks with a reference plane (the colour transform's inverse) have a reference
+// block of EXACTLY the window's rows from column 0 to the window's last column, and are compared with the plain loop over
+// (px + ref - 128) mod 256; three gate statuses decide together.  Build and run:
 //   g++ -std=c++17 -O2 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -o deliver_check tools/deliver_check.cpp && ./deliver_check
 #include <cmath>
 #include <cstdio>
@@ -152,6 +154,46 @@ static int one_strided_task(std::mt19937 &rng, uint32_t format, int rows_total, 
     return 0;
 }
 
+// A task with a reference, contiguous (step == 0) or strided: the reference block starts at the window's first row and
+// ends with the last byte the window needs.  gates: three statuses, all 1 delivers.
+static int one_ref_task(std::mt19937 &rng, uint32_t format, int rows_total, int width, int row0, int row1, int col0, int col1, size_t step, size_t slack,
+                        size_t residue, float scale, float bias, const int gates[3]) {
+    const uint32_t elem = deliver_elem(format), rows = uint32_t(row1 - row0), cols = uint32_t(col1 - col0);
+    const size_t stp = step ? step : elem, pitch = size_t(cols) * stp + slack * elem;
+    const size_t extent = size_t(deliver_extent(rows, cols, format, pitch, stp));
+    const size_t ref_bytes = size_t(rows - 1) * size_t(width) + size_t(col1);
+    uint8_t *plane = static_cast<uint8_t *>(malloc(size_t(rows_total) * size_t(width))), *ref = static_cast<uint8_t *>(malloc(ref_bytes));
+    void *aligned = nullptr;
+    CHECK(posix_memalign(&aligned, 16, residue + extent) == 0);
+    uint8_t *block = static_cast<uint8_t *>(aligned), *dst = block + residue;
+    CHECK(plane && ref && block);
+    for (size_t i = 0; i < size_t(rows_total) * size_t(width); i++) plane[i] = uint8_t(rng());
+    for (size_t i = 0; i < ref_bytes; i++) ref[i] = uint8_t(rng());
+    memset(block, 0x5A, residue + extent);
+    DeliverTask T{};
+    T.src = plane; T.src_bytes = size_t(rows_total) * size_t(width); T.src_pitch = uint32_t(width);
+    T.dst = dst; T.dst_pitch = pitch; T.dst_step = uint32_t(stp);
+    T.row0 = row0; T.row1 = row1; T.col0 = col0; T.col1 = col1;
+    T.format = format; T.scale = scale; T.bias = bias;
+    T.ref = ref; T.ref_bytes = ref_bytes; T.ref_pitch = uint32_t(width);
+    CHECK(deliver_task_ok(T, uint32_t(rows_total)));
+    T.ref_bytes = ref_bytes - 1; CHECK(!deliver_task_ok(T, uint32_t(rows_total)));
+    T.ref_bytes = ref_bytes; T.ref_pitch = uint32_t(width) + 1; CHECK(!deliver_task_ok(T, uint32_t(rows_total)));
+    T.ref_pitch = uint32_t(width);
+    deliver_host(T, gates[0], gates[1], gates[2]);
+    const bool zero = gates[0] != 1 || gates[1] != 1 || gates[2] != 1;
+    std::vector<uint8_t> want(residue + extent, 0x5A);
+    for (uint32_t r = 0; r < rows; r++)
+        for (uint32_t c = 0; c < cols; c++) {
+            const int px = plane[size_t(row0 + int(r)) * size_t(width) + size_t(col0) + c], g = ref[size_t(r) * size_t(width) + size_t(col0) + c];
+            const uint32_t v = zero ? 0u : value_ref(uint8_t((px + g - 128 + 256) % 256), format, scale, bias);
+            memcpy(want.data() + residue + size_t(r) * pitch + size_t(c) * stp, &v, elem);
+        }
+    CHECK(memcmp(block, want.data(), residue + extent) == 0);
+    free(plane); free(ref); free(block);
+    return 0;
+}
+
 int main() {
     std::mt19937 rng(22);
     const float norms[][2] = {{1.0f, 0.0f}, {1.0f / 255.0f, -0.5f}, {0.0078125f, -1.0f}, {1e-7f, 0.0f}, {300.0f, -1.0f}, {5.9604645e-8f, 0.0f}};
@@ -210,6 +252,23 @@ int main() {
         free(frame);
         strided += 3;
     }
+    // tasks with a reference plane, contiguous and strided, and every way one of three gates is not done
+    long referenced = 0;
+    for (uint32_t a = 0; a < 256; a++)
+        for (uint32_t b = 0; b < 256; b++) CHECK(deliver_rct(a, b) == uint32_t((int(a) + int(b) - 128 + 256) % 256));
+    for (uint32_t format = 0; format < kDeliverFormats; format++)
+        for (int width : widths)
+            for (int rep = 0; rep < 200; rep++) {
+                const int rows_total = 1 + int(rng() % 6);
+                const int row0 = int(rng() % uint32_t(rows_total)), row1 = row0 + 1 + int(rng() % uint32_t(rows_total - row0));
+                const int col0 = int(rng() % uint32_t(width)), col1 = col0 + 1 + int(rng() % uint32_t(width - col0));
+                const uint32_t elem = deliver_elem(format);
+                const float *nb = format == kDeliverU8 ? norms[0] : norms[rng() % 6];
+                const int all[][3] = {{1, 1, 1}, {1, 1, 1}, {1, 1, 1}, {0, 1, 1}, {1, 2, 1}, {1, 1, -7}};
+                if (one_ref_task(rng, format, rows_total, width, row0, row1, col0, col1, rep % 2 ? size_t(2 + rng() % 6) * elem : 0, rng() % 4,
+                                 size_t(rng() % (16 / elem)) * elem, nb[0], nb[1], all[rng() % 6])) return 1;
+                referenced++;
+            }
     // every float32 exponent around the halves' range, both signs, ties included: the integer conversion against half_ref
     for (uint32_t e = 90; e < 150; e++)
         for (uint32_t m = 0; m < (1u << 23); m += 0x3FF) {
@@ -228,6 +287,6 @@ int main() {
         memcpy(&f, &b, 4);
         CHECK(deliver_f16_bits(b) == half_ref(f));
     }
-    printf("deliver_check: %ld contiguous and %ld strided tasks, all bytes as expected\n", tasks, strided);
+    printf("deliver_check: %ld contiguous, %ld strided and %ld referenced tasks, all bytes as expected\n", tasks, strided, referenced);
     return 0;
 }
