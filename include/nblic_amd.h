@@ -542,7 +542,8 @@ long nblic_amd_indexed_decode_plan(int n_images, const int *kinds, const int *ef
  *                   three windows; either way its three statuses are -1.  nblic_amd_decode_batch_to_ex delivers the colour
  *                   frames of a call in ONE launch behind the work of both of its streams (an event wait), since the
  *                   planes of a frame may be of different (codec, effort) classes.
- * The gain on photographs is UNMEASURED: no colour photograph was at hand (README.md says what was measured instead). */
+ * The gain on photographs is UNMEASURED: no colour photograph was at hand (README.md says what was measured instead).
+ * The calls with the flag are the _color calls (PER-FRAME COLOUR MODES, below) with every frame's mode NBLIC_AMD_COLOR_RCT. */
 #define NBLIC_AMD_FORMAT_RCT 0x100
 typedef struct nblic_amd_dest {
     void  *ptr;          /* device memory on the context's device                          */
@@ -1052,6 +1053,82 @@ int nblic_amd_debug_deliver_ref(nblic_amd_ctx *ctx, int n, const unsigned char *
                                 const int *ref_rows, const int *plane_rows, const int *widths, const int *windows, const int *formats,
                                 const float *scales, const float *biases, const int *zeros, const size_t *pitches, const size_t *steps,
                                 const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs, const int *gate_status);
+
+/* PER-FRAME COLOUR MODES: the transform chosen frame by frame from costs measured on the device.
+ * A frame's MODE is one byte.  Bits 0..1: the base channel b (0 = R, 1 = G, 2 = B).  Bit 2: the lower-numbered of the two
+ * other channels is coded as (c - b + 128) mod 256.  Bit 3: the same for the higher-numbered one.  The base, and a channel
+ * whose bit is clear, are coded as they are.  Valid: 0 (plain, the only spelling of "no difference") and b | 4, b | 8,
+ * b | 12 for b = 0 .. 2 -- ten modes; NBLIC_AMD_COLOR_RCT (base G, both differences) is what NBLIC_AMD_FORMAT_RCT does.
+ * The reference of a difference is always the caller's SOURCE of the base channel on encode and the DECODED base plane on
+ * decode; there are no chains of differences.  Nothing in a stream says which mode it was coded in: the caller keeps the
+ * byte with the frame's three streams.
+ *
+ * nblic_amd_color_plan measures and chooses.  Images 3f .. 3f + 2 of srcs are R, G, B of frame f (sources as the _from
+ * calls take them, one format, scale and bias).  ONE launch of k_color_cost computes, per frame, the COST of nine planes --
+ * R, G, B, R-G, R-B, G-R, G-B, B-R, B-G in this order, X-Y being (X - Y + 128) mod 256 of the pixels k_collect would write:
+ * the sum over the pixels of 2 * bitlen(|e|) + 1, e the residual (wrapped to -128 .. 127) of the MED prediction from W, N
+ * and NW of the same plane (row 0: W; column 0: N; (0, 0): 128), integers only, unsigned 64-bit sums that depend on nothing
+ * but the pixels -- the table comes back in one copy, and the host chooses by nblic_amd_color_choose:
+ *     with base b, channel c takes its difference only if 64 * cost(c - b) < 63 * cost(c) (a design margin: a difference
+ *     that does not clearly win should not cost the frame its readability by plain decoders);
+ *     total(b) = cost(b) + the cheaper alternative, under that rule, of each other channel; the smallest total wins,
+ *     ties go to G, then R, then B; a winner without a difference is mode 0.
+ * The rule is part of the interface: two builds plan alike.
+ *   frame_modes   n_images / 3 bytes; 0xFF for a frame with a source the _from calls refuse or with sources of unequal size
+ *                 (nothing is launched for it, its costs are zero, the other frames are unaffected)
+ *   costs         NULL, or nine sums per frame
+ *   -1            nothing launched: n_images % 3 != 0, a null srcs or frame_modes, an unknown format (NBLIC_AMD_FORMAT_RCT
+ *                 included), a scale or bias the _from calls refuse; or a HIP call failed.
+ * nblic_amd_color_plan_stats: out[0] launches of k_color_cost, out[1] source elements read, since the context was made;
+ * last_plan_ms (may be NULL): GPU milliseconds of the last nblic_amd_color_plan's launch.
+ *
+ * The six _color calls are the four _from encoders and the two _to_ex decoders with `frame_modes` (one byte per frame,
+ * n_images / 3 of them) in place of NBLIC_AMD_FORMAT_RCT, which they do not take; the calls with the flag are these with
+ * every mode NBLIC_AMD_COLOR_RCT.  Each plane of a frame takes its reference from the mode; a plane that is no difference
+ * and is contiguous uint8 is still used in place.  A frame with a difference follows the flag's frame rules (a refused
+ * member refuses the frame; every delivery task of the frame is gated by all three planes; a plane that fails leaves
+ * zeros in all three windows); a frame of mode 0 is three independent images, exactly as without the flag.
+ *   -1, nothing launched or written: an invalid mode byte (0xFF is one); n_images % 3 != 0; in
+ *   nblic_amd_encode_batch_modes_from_color, near > 0 on an image of a frame whose mode is not 0.
+ * nblic_amd_encode_batch_modes_from_to has no sibling. */
+#define NBLIC_AMD_COLOR_PLAIN 0
+#define NBLIC_AMD_COLOR_RCT 0x0D
+int nblic_amd_color_plan(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                         unsigned char *frame_modes, unsigned long long *costs);
+unsigned char nblic_amd_color_choose(const unsigned long long costs[9]);     /* host only, pure; NULL: 0xFF */
+int nblic_amd_color_mode_valid(int mode);                                    /* 1 / 0 */
+int nblic_amd_color_mode_ref(int mode, int channel);                         /* the channel plane `channel` is taken against; -1: none; -2: invalid */
+int nblic_amd_color_plan_stats(nblic_amd_ctx *ctx, long out[2], double *last_plan_ms);
+int nblic_amd_encode_batch_modes_from_color(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                            const unsigned char *frame_modes, const int *nears, const int *efforts, unsigned char *const *outs,
+                                            const size_t *out_caps, long *out_lens, unsigned char *const *recons);
+int nblic_amd_qencode_batch_from_color(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                       const unsigned char *frame_modes, uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words);
+int nblic_amd_encode_batch_indexed_from_color(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                              const unsigned char *frame_modes, const int *every_rows, int band_rows, unsigned char *const *outs,
+                                              const size_t *out_caps, long *out_lens, unsigned char *const *indexes, const size_t *index_caps, long *index_lens);
+int nblic_amd_qencode_batch_indexed_from_color(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                               const unsigned char *frame_modes, const int *every_rows, int band_rows, uint16_t *const *outs,
+                                               const size_t *out_caps_words, long *out_len_words, unsigned char *const *indexes, const size_t *index_caps,
+                                               long *index_lens);
+int nblic_amd_decode_batch_to_ex_color(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                       const nblic_amd_dest_ex *dests, int format, const unsigned char *frame_modes, int *heights, int *widths,
+                                       int *nears, int *efforts, int *status);
+int nblic_amd_decode_batch_indexed_to_ex_color(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                               const void *const *indexes, const size_t *index_lens, const nblic_amd_dest_ex *dests, int format,
+                                               const unsigned char *frame_modes, int *heights, int *widths, int *nears, int *efforts, int *status);
+/* Debug hooks used by the colour plan's tests: the cost kernel and its host walk alone (csrc/color_plan.h).
+ * nblic_amd_debug_color_cost_host: ONE frame, host only: srcs / cap_bytes / pitches / steps have three entries (R, G, B),
+ * cap_bytes[ch] readable from srcs[ch]; costs receives the nine sums, tiles (may be NULL) the kernel's workgroups.
+ * nblic_amd_debug_color_cost: ONE k_color_cost launch over n frames: srcs / src_bytes / base_offsets / pitches / steps have
+ * three entries per frame (3 k + channel), each source uploaded at byte base_offsets[] (0 .. 255) of a region of its own
+ * filled with 0xFF; costs receives nine sums per frame.  -1: refused (what a source of nblic_amd_debug_collect is refused
+ * for); -2: a HIP call failed. */
+int nblic_amd_debug_color_cost_host(const void *const *srcs, const size_t *cap_bytes, const size_t *pitches, const size_t *steps, int rows, int cols,
+                                    int format, float scale, float bias, unsigned long long *costs, unsigned long long *tiles);
+int nblic_amd_debug_color_cost(nblic_amd_ctx *ctx, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets,
+                               const size_t *pitches, const size_t *steps, const int *rows, const int *cols, const int *formats,
+                               const float *scales, const float *biases, unsigned long long *costs);
 
 /* Debug hook used by the indexed effort-0 batch's host tests: QNBLIC's entropy stage (histogram normalisation, histogram
  * code, the rANS pass) on caller-made records, reporting the coder in front of entry rows as the batch's workers read it.

@@ -58,6 +58,10 @@ EXPORTS = (
     "nblic_amd_encode_batch_modes_from", "nblic_amd_qencode_batch_from", "nblic_amd_encode_batch_indexed_from", "nblic_amd_qencode_batch_indexed_from",
     "nblic_amd_collect_stats", "nblic_amd_collect_ms", "nblic_amd_debug_collect_host", "nblic_amd_debug_collect",
     "nblic_amd_debug_collect_ref_host", "nblic_amd_debug_collect_ref", "nblic_amd_debug_deliver_ref_host", "nblic_amd_debug_deliver_ref",
+    "nblic_amd_color_plan", "nblic_amd_color_choose", "nblic_amd_color_mode_valid", "nblic_amd_color_mode_ref", "nblic_amd_color_plan_stats",
+    "nblic_amd_encode_batch_modes_from_color", "nblic_amd_qencode_batch_from_color", "nblic_amd_encode_batch_indexed_from_color",
+    "nblic_amd_qencode_batch_indexed_from_color", "nblic_amd_decode_batch_to_ex_color", "nblic_amd_decode_batch_indexed_to_ex_color",
+    "nblic_amd_debug_color_cost_host", "nblic_amd_debug_color_cost",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats", "nblic_amd_copy_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -307,6 +311,36 @@ def load_library() -> C.CDLL:
                                                          C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, ullp, ullp]
         lib.nblic_amd_debug_deliver_ref.restype = C.c_int
         lib.nblic_amd_debug_deliver_ref.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, vpp, szp, ip, ip, ip, ip, ip, fp, fp, ip, szp, szp, szp, szp, vpp, ip]
+    if hasattr(lib, "nblic_amd_color_plan"):                        # (an older build loaded through NBLIC_AMD_LIB has none of these)
+        vpp, szp, fp, ullp, lp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(C.c_ulonglong), C.POINTER(C.c_long)
+        xp, ubp = C.POINTER(DestEx), C.POINTER(C.c_ubyte)
+        head = [C.c_void_p, C.c_int, C.POINTER(Src), C.c_int, C.c_float, C.c_float]
+        lib.nblic_amd_color_plan.restype = C.c_int
+        lib.nblic_amd_color_plan.argtypes = head + [ubp, ullp]
+        lib.nblic_amd_color_choose.restype = C.c_ubyte
+        lib.nblic_amd_color_choose.argtypes = [ullp]
+        lib.nblic_amd_color_mode_valid.restype = C.c_int
+        lib.nblic_amd_color_mode_valid.argtypes = [C.c_int]
+        lib.nblic_amd_color_mode_ref.restype = C.c_int
+        lib.nblic_amd_color_mode_ref.argtypes = [C.c_int, C.c_int]
+        lib.nblic_amd_color_plan_stats.restype = C.c_int
+        lib.nblic_amd_color_plan_stats.argtypes = [C.c_void_p, lp, C.POINTER(C.c_double)]
+        lib.nblic_amd_encode_batch_modes_from_color.restype = C.c_int
+        lib.nblic_amd_encode_batch_modes_from_color.argtypes = head + [ubp, ip, ip, vpp, szp, lp, vpp]
+        lib.nblic_amd_qencode_batch_from_color.restype = C.c_int
+        lib.nblic_amd_qencode_batch_from_color.argtypes = head + [ubp, vpp, szp, lp]
+        lib.nblic_amd_encode_batch_indexed_from_color.restype = C.c_int
+        lib.nblic_amd_encode_batch_indexed_from_color.argtypes = head + [ubp, ip, C.c_int, vpp, szp, lp, vpp, szp, lp]
+        lib.nblic_amd_qencode_batch_indexed_from_color.restype = C.c_int
+        lib.nblic_amd_qencode_batch_indexed_from_color.argtypes = lib.nblic_amd_encode_batch_indexed_from_color.argtypes
+        lib.nblic_amd_decode_batch_to_ex_color.restype = C.c_int
+        lib.nblic_amd_decode_batch_to_ex_color.argtypes = [C.c_void_p, C.c_int, vpp, szp, xp, C.c_int, ubp] + [ip] * 5
+        lib.nblic_amd_decode_batch_indexed_to_ex_color.restype = C.c_int
+        lib.nblic_amd_decode_batch_indexed_to_ex_color.argtypes = [C.c_void_p, C.c_int, vpp, szp, vpp, szp, xp, C.c_int, ubp] + [ip] * 5
+        lib.nblic_amd_debug_color_cost_host.restype = C.c_int
+        lib.nblic_amd_debug_color_cost_host.argtypes = [vpp, szp, szp, szp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, ullp, ullp]
+        lib.nblic_amd_debug_color_cost.restype = C.c_int
+        lib.nblic_amd_debug_color_cost.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, szp, szp, ip, ip, ip, fp, fp, ullp]
     if hasattr(lib, "nblic_amd_index_build_batch"):
         vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
         lib.nblic_amd_index_build_batch.restype = C.c_int
@@ -695,39 +729,144 @@ def collect_host(array: np.ndarray, fmt, scale: float = 1.0, bias: float = 0.0, 
 FORMAT_RCT = 0x100                                                              # NBLIC_AMD_FORMAT_RCT: a flag bit in a call's format
 
 
-def rct_forward(r: np.ndarray, g: np.ndarray, b: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """The reversible colour transform of three uint8 planes of one shape, on the host: ``(r - g + 128) mod 256``, ``g``,
-    ``(b - g + 128) mod 256`` -- the planes whose streams ``color="rct"`` writes, and what a decoder that knows nothing of
-    the transform gets back from them."""
-    r, g, b = (np.asarray(v) for v in (r, g, b))
-    if any(v.dtype != np.uint8 for v in (r, g, b)) or r.shape != g.shape or b.shape != g.shape:
-        raise ValueError("rct_forward: three uint8 arrays of one shape")
+COLOR_PLAIN, COLOR_RCT, COLOR_REFUSED = 0, 0x0D, 0xFF                           # NBLIC_AMD_COLOR_PLAIN / _RCT; what color_plan gives a refused frame
+COLOR_MODES = (0, 4, 8, 12, 5, 9, 13, 6, 10, 14)                                # the ten valid mode bytes
+COLOR_PLANES = ("R", "G", "B", "R-G", "R-B", "G-R", "G-B", "B-R", "B-G")        # the order of a frame's nine costs
+
+
+def color_mode_valid(mode: int) -> bool:
+    """Is ``mode`` one of the ten colour mode bytes (``nblic_amd_color_mode_valid``)?"""
+    return bool(load_library().nblic_amd_color_mode_valid(int(mode)))
+
+
+def color_mode_ref(mode: int, channel: int) -> Optional[int]:
+    """The channel (0 = R, 1 = G, 2 = B) that plane ``channel`` of a frame of ``mode`` is coded against, ``None`` when it is
+    coded as it is (``nblic_amd_color_mode_ref``).  ``ValueError`` for an invalid mode or channel."""
+    r = int(load_library().nblic_amd_color_mode_ref(int(mode), int(channel)))
+    if r == -2:
+        raise ValueError("color_mode_ref: an invalid mode or channel")
+    return None if r < 0 else r
+
+
+def color_choose(costs) -> int:
+    """The mode the rule chooses from a frame's nine costs (``nblic_amd_color_choose``; include/nblic_amd.h states the
+    rule)."""
+    v = np.ascontiguousarray(costs, np.uint64).reshape(-1)
+    if v.size != 9:
+        raise ValueError("color_choose: nine costs")
+    return int(load_library().nblic_amd_color_choose(v.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+
+
+def _three_planes(planes, what):
+    planes = tuple(np.asarray(v) for v in planes)
+    if any(v.dtype != np.uint8 for v in planes) or any(v.shape != planes[0].shape for v in planes):
+        raise ValueError(what + ": three uint8 arrays of one shape")
+    return planes
+
+
+def rct_forward(r: np.ndarray, g: np.ndarray, b: np.ndarray, mode: int = COLOR_RCT) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The planes whose streams a frame of colour ``mode`` has, on the host: a channel the mode codes as a difference is
+    ``(c - base + 128) mod 256``, every other one a copy.  The default is the fixed transform of ``color="rct"``:
+    ``(r - g + 128) mod 256``, ``g``, ``(b - g + 128) mod 256``.  A decoder that knows nothing of the transform gets these
+    planes back."""
+    planes = _three_planes((r, g, b), "rct_forward")
     off = np.uint8(128)
-    return r - g + off, g.copy(), b - g + off                  # (uint8 arithmetic wraps)
+    refs = [color_mode_ref(mode, c) for c in range(3)]
+    return tuple(planes[c].copy() if refs[c] is None else planes[c] - planes[refs[c]] + off for c in range(3))      # (uint8 arithmetic wraps)
 
 
-def rct_inverse(tr: np.ndarray, g: np.ndarray, tb: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """The inverse of :func:`rct_forward`: ``(tr + g - 128) mod 256``, ``g``, ``(tb + g - 128) mod 256``."""
-    tr, g, tb = (np.asarray(v) for v in (tr, g, tb))
-    if any(v.dtype != np.uint8 for v in (tr, g, tb)) or tr.shape != g.shape or tb.shape != g.shape:
-        raise ValueError("rct_inverse: three uint8 arrays of one shape")
+def rct_inverse(tr: np.ndarray, g: np.ndarray, tb: np.ndarray, mode: int = COLOR_RCT) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The inverse of :func:`rct_forward` for the same ``mode``: a difference plane becomes ``(t + base - 128) mod 256``."""
+    planes = _three_planes((tr, g, tb), "rct_inverse")
     off = np.uint8(128)
-    return tr + g - off, g.copy(), tb + g - off
+    refs = [color_mode_ref(mode, c) for c in range(3)]
+    return tuple(planes[c].copy() if refs[c] is None else planes[c] + planes[refs[c]] - off for c in range(3))
 
 
-def _color_flag(color, arg) -> int:
-    """The format flag ``color`` stands for.  With ``"rct"``, ``arg`` -- the sources or the destinations -- is a tensor
+def _plane_cost_numpy(p: np.ndarray) -> int:
+    """The cost of one uint8 plane, restated with whole-array numpy: MED prediction, residual wrapped to -128 .. 127,
+    2 * bitlen(|e|) + 1 a pixel."""
+    p = np.asarray(p).astype(np.int64)
+    pred = np.empty_like(p)
+    pred[0, 0] = 128
+    pred[0, 1:] = p[0, :-1]
+    pred[1:, 0] = p[:-1, 0]
+    w, n, nw = p[1:, :-1], p[:-1, 1:], p[:-1, :-1]
+    lo, hi = np.minimum(w, n), np.maximum(w, n)
+    pred[1:, 1:] = np.where(nw >= hi, lo, np.where(nw <= lo, hi, w + n - nw))
+    e = (p - pred + 128) % 256 - 128
+    a = np.abs(e)
+    bitlen = np.zeros_like(a)
+    for k in range(8):
+        bitlen += (a >> k) > 0
+    return int((2 * bitlen + 1).sum())
+
+
+def color_cost_numpy(r: np.ndarray, g: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """The nine costs of a frame of three 2-D uint8 planes (``COLOR_PLANES`` says which), restated in numpy -- what
+    ``Context.color_plan(..., costs=True)`` reports for the collected planes."""
+    ch = _three_planes((r, g, b), "color_cost_numpy")
+    if ch[0].ndim != 2 or ch[0].size == 0:
+        raise ValueError("color_cost_numpy: 2-D planes")
+    off = np.uint8(128)
+    planes = list(ch) + [ch[x] - ch[y] + off for x, y in ((0, 1), (0, 2), (1, 0), (1, 2), (2, 0), (2, 1))]
+    return np.array([_plane_cost_numpy(p) for p in planes], np.uint64)
+
+
+def color_cost_host(raws, rows: int, cols: int, fmt, pitches=None, steps=None, scale: float = 1.0, bias: float = 0.0, offsets=(0, 0, 0),
+                    caps=None, info: Optional[dict] = None) -> np.ndarray:
+    """The cost kernel's tile walk on the host (``nblic_amd_debug_color_cost_host``; no device) over ONE frame: ``raws`` are
+    the raw bytes of the R, G and B sources, element (0, 0) of each at byte ``offsets[ch]``, rows ``pitches[ch]`` and the
+    pixels of a row ``steps[ch]`` bytes apart (default: contiguous), ``caps[ch]`` bytes readable from there (default: to the
+    buffer's end).  Returns the nine sums (uint64); ``info`` receives ``tiles``.  ``ValueError`` when refused."""
+    fmt = fmt if isinstance(fmt, int) else collect_format(fmt)
+    elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
+    raws = [np.ascontiguousarray(v).reshape(-1).view(np.uint8) for v in raws]
+    if len(raws) != 3:
+        raise ValueError("color_cost_host: three sources")
+    pitches = [int(cols) * elem] * 3 if pitches is None else [int(v) for v in pitches]
+    steps = [elem] * 3 if steps is None else [int(v) for v in steps]
+    caps = [r.size - int(o) for r, o in zip(raws, offsets)] if caps is None else [int(v) for v in caps]
+    if min(pitches + steps) < 0:
+        raise ValueError("color_cost_host: a negative pitch or step")
+    out, tiles = np.zeros(9, np.uint64), C.c_ulonglong(0)
+    rc = load_library().nblic_amd_debug_color_cost_host((C.c_void_p * 3)(*[r.ctypes.data + int(o) for r, o in zip(raws, offsets)]),
+                                                        (C.c_size_t * 3)(*[max(v, 0) for v in caps]), (C.c_size_t * 3)(*pitches), (C.c_size_t * 3)(*steps),
+                                                        int(rows), int(cols), int(fmt), float(scale), float(bias),
+                                                        out.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(tiles))
+    if rc != 0:
+        raise ValueError("nblic_amd_debug_color_cost_host refused its arguments")
+    if info is not None:
+        info["tiles"] = int(tiles.value)
+    return out
+
+
+def _color_arg(color, arg):
+    """What ``color`` stands for: (format flag, mode bytes or None).  ``"rct"`` is the flag; a sequence or array is one mode
+    byte per frame for the _color calls.  With either, ``arg`` -- the sources or the destinations -- is a tensor
     [N, 3, H, W] or a list of 3 F views, the R, G, B of frame f at 3 f, 3 f + 1, 3 f + 2."""
     if color is None:
-        return 0
-    if color != "rct":
-        raise ValueError('color: None or "rct"')
+        return 0, None
+    if isinstance(color, str) and color != "rct":
+        raise ValueError('color: None, "rct", or one mode byte per frame')
     if isinstance(arg, (list, tuple)):
         if len(arg) % 3 != 0:
-            raise ValueError('color="rct": a list holds three views per frame')
+            raise ValueError("color: a list holds three views per frame")
+        frames = len(arg) // 3
     elif len(tuple(arg.shape)) != 4 or int(arg.shape[1]) != 3:
-        raise ValueError('color="rct": a tensor [N, 3, H, W] (NHWC: permute it), or a list of three views per frame')
-    return FORMAT_RCT
+        raise ValueError("color: a tensor [N, 3, H, W] (NHWC: permute it), or a list of three views per frame")
+    else:
+        frames = int(arg.shape[0])
+    if isinstance(color, str):
+        return FORMAT_RCT, None
+    modes = np.array([int(v) for v in color], np.int64)
+    if modes.shape != (frames,) or modes.min(initial=0) < 0 or modes.max(initial=0) > 255:
+        raise ValueError("color: one mode byte per frame")
+    return 0, modes.astype(np.uint8)
+
+
+def _modes_ptr(modes):
+    return np.ascontiguousarray(modes, np.uint8).ctypes.data_as(C.POINTER(C.c_ubyte))
 
 
 def _src_views(src):
@@ -1459,9 +1598,10 @@ class Context:
             info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
         return status
 
-    def decode_batch_indexed_to_ex(self, pairs, dests, fmt: int, info: Optional[dict] = None) -> List[int]:
+    def decode_batch_indexed_to_ex(self, pairs, dests, fmt: int, info: Optional[dict] = None, modes=None) -> List[int]:
         """``nblic_amd_decode_batch_indexed_to_ex`` as it is: ``dests`` is one ``(ptr, pitch_bytes, step_bytes, cap_bytes,
-        row0, row1, col0, col1, scale, bias)`` per image.  Result and ``info`` as ``decode_batch_indexed_to``."""
+        row0, row1, col0, col1, scale, bias)`` per image.  Result and ``info`` as ``decode_batch_indexed_to``.  ``modes``:
+        one colour mode byte per frame (``nblic_amd_decode_batch_indexed_to_ex_color``)."""
         n = len(pairs)
         ss = [_bytes_arg(s if s is not None else b"") for s, _ in pairs]
         xs = [_bytes_arg(x if x is not None else b"") for _, x in pairs]
@@ -1470,15 +1610,20 @@ class Context:
         vp = lambda arrs: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else nothing.ctypes.data for a in arrs])
         sz = lambda arrs: (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
         meta = [np.full(max(n, 1), -1, np.int32) for _ in range(5)]
-        rc = self.lib.nblic_amd_decode_batch_indexed_to_ex(self.handle, n, vp(ss), sz(ss), vp(xs), sz(xs), _dest_ex_array(dests), int(fmt),
-                                                           *[m.ctypes.data_as(ip) for m in meta])
+        if modes is not None:
+            rc = self.lib.nblic_amd_decode_batch_indexed_to_ex_color(self.handle, n, vp(ss), sz(ss), vp(xs), sz(xs), _dest_ex_array(dests), int(fmt), _modes_ptr(modes),
+                                                                     *[m.ctypes.data_as(ip) for m in meta])
+        else:
+            rc = self.lib.nblic_amd_decode_batch_indexed_to_ex(self.handle, n, vp(ss), sz(ss), vp(xs), sz(xs), _dest_ex_array(dests), int(fmt),
+                                                               *[m.ctypes.data_as(ip) for m in meta])
         status = [int(v) for v in meta[4][:n]]
         if info is not None:
             info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
         return status
 
-    def decode_batch_to_ex(self, streams, dests, fmt: int, info: Optional[dict] = None) -> List[int]:
-        """``nblic_amd_decode_batch_to_ex`` as it is; arguments and result as ``decode_batch_indexed_to_ex``."""
+    def decode_batch_to_ex(self, streams, dests, fmt: int, info: Optional[dict] = None, modes=None) -> List[int]:
+        """``nblic_amd_decode_batch_to_ex`` as it is (``modes``: ``nblic_amd_decode_batch_to_ex_color``); arguments and result
+        as ``decode_batch_indexed_to_ex``."""
         n = len(streams)
         ss = [_bytes_arg(s if s is not None else b"") for s in streams]
         nothing = np.zeros(1, np.uint8)
@@ -1486,7 +1631,10 @@ class Context:
         sp = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else nothing.ctypes.data for a in ss])
         sl = (C.c_size_t * max(n, 1))(*[a.size for a in ss])
         meta = [np.full(max(n, 1), -1, np.int32) for _ in range(5)]
-        rc = self.lib.nblic_amd_decode_batch_to_ex(self.handle, n, sp, sl, _dest_ex_array(dests), int(fmt), *[m.ctypes.data_as(ip) for m in meta])
+        if modes is not None:
+            rc = self.lib.nblic_amd_decode_batch_to_ex_color(self.handle, n, sp, sl, _dest_ex_array(dests), int(fmt), _modes_ptr(modes), *[m.ctypes.data_as(ip) for m in meta])
+        else:
+            rc = self.lib.nblic_amd_decode_batch_to_ex(self.handle, n, sp, sl, _dest_ex_array(dests), int(fmt), *[m.ctypes.data_as(ip) for m in meta])
         status = [int(v) for v in meta[4][:n]]
         if info is not None:
             info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
@@ -1515,7 +1663,7 @@ class Context:
         return ("ex", [(d[0], d[1], DELIVER_ELEM[fmt]) + tuple(d[2:]) + (scales[k], biases[k]) for k, d in enumerate(dests)], fmt)
 
     def decode_batch_indexed_into(self, pairs, out, rows=None, cols=None, scale=1.0, bias=0.0, info: Optional[dict] = None, layout: str = "rows",
-                                  color: Optional[str] = None) -> List[int]:
+                                  color=None) -> List[int]:
         """A window of every image of ``decode_batch_indexed`` straight into device tensors: no pixel crosses the bus.
         ``out`` is one tensor [N, H', W'] or [N, 1, H', W'] on this context's device, or a list of 2-D tensors -- views
         with any batch and row stride, last stride 1; the dtype chooses the format: uint8 (a copy), float16, bfloat16 or
@@ -1535,16 +1683,21 @@ class Context:
         R - G, G and B - G planes of frame f -- and R and B are put together again on the way out, before ``scale`` and
         ``bias``.  ``out`` is a tensor [N, 3, H', W'] (``layout="any"``) or a list of three views per frame (``ValueError``
         otherwise); the three planes of a frame have one size and one window.  A frame stands or falls as a whole: all
-        three statuses are -1 when one of its planes or destinations is refused (nothing is written) or fails (zeros)."""
+        three statuses are -1 when one of its planes or destinations is refused (nothing is written) or fails (zeros).
+
+        ``color=modes``, a sequence or array of one colour mode byte per frame (``COLOR_MODES``; what ``color_plan`` chose
+        and ``encode_batch_from`` was given): each frame's differences are undone against its base plane; ``"rct"`` is
+        every mode ``COLOR_RCT``.  A frame of mode 0 is three independent images.  An invalid byte refuses the whole call:
+        every status is -1 and nothing is written."""
         n = len(pairs)
-        flag = _color_flag(color, out)
+        flag, modes = _color_arg(color, out)
         dims = []
         for _, x in pairs:                                      # the head of an index names the geometry; the library checks all of it
             x = _bytes_arg(x if x is not None else b"")
             h, w = (int(v) for v in np.frombuffer(x[16:24].tobytes(), "<i4")) if x.size >= INDEX_HEAD_BYTES else (0, 0)
             dims.append((h, w) if 0 < h <= 65535 and 0 < w <= 65535 else (0, 0))
-        how = self._dests_for(out, n, dims, rows, cols, scale, bias, layout, ex=bool(flag))
-        return self.decode_batch_indexed_to(pairs, *how[1:], info) if how[0] == "plain" else self.decode_batch_indexed_to_ex(pairs, how[1], how[2] | flag, info)
+        how = self._dests_for(out, n, dims, rows, cols, scale, bias, layout, ex=color is not None)
+        return self.decode_batch_indexed_to(pairs, *how[1:], info) if how[0] == "plain" else self.decode_batch_indexed_to_ex(pairs, how[1], how[2] | flag, info, modes)
 
     def decode_batch_to(self, streams, dests, fmt: int, scale: float = 1.0, bias: float = 0.0, info: Optional[dict] = None) -> List[int]:
         """``nblic_amd_decode_batch_to`` as it is; arguments and result as ``decode_batch_indexed_to``."""
@@ -1562,15 +1715,15 @@ class Context:
         return status
 
     def decode_batch_into(self, streams, out, rows=None, cols=None, scale=1.0, bias=0.0, info: Optional[dict] = None, layout: str = "rows",
-                          color: Optional[str] = None) -> List[int]:
+                          color=None) -> List[int]:
         """``decode_batch`` with a window of every plane delivered into device tensors (no index: every stream is decoded
         whole, from its start).  ``out``, ``layout``, ``rows``, ``cols``, ``scale``, ``bias``, the result and ``info`` as
-        ``decode_batch_indexed_into``; a stream that fails on the device leaves zeros.  ``color="rct"`` as there: the three
-        planes of a frame may be of different codecs and efforts."""
-        flag = _color_flag(color, out)
+        ``decode_batch_indexed_into``; a stream that fails on the device leaves zeros.  ``color="rct"`` or ``color=modes`` as
+        there: the three planes of a frame may be of different codecs and efforts."""
+        flag, modes = _color_arg(color, out)
         dims = [_stream_dims(_bytes_arg(s if s is not None else b"")) or (0, 0) for s in streams]
-        how = self._dests_for(out, len(streams), dims, rows, cols, scale, bias, layout, ex=bool(flag))
-        return self.decode_batch_to(streams, *how[1:], info) if how[0] == "plain" else self.decode_batch_to_ex(streams, how[1], how[2] | flag, info)
+        how = self._dests_for(out, len(streams), dims, rows, cols, scale, bias, layout, ex=color is not None)
+        return self.decode_batch_to(streams, *how[1:], info) if how[0] == "plain" else self.decode_batch_to_ex(streams, how[1], how[2] | flag, info, modes)
 
     def debug_deliver(self, tasks) -> List[np.ndarray]:
         """``nblic_amd_debug_deliver``: ONE k_deliver launch over ``tasks``, each a dict with ``plane`` (2-D uint8),
@@ -1635,15 +1788,79 @@ class Context:
             raise RuntimeError("nblic_amd_collect_ms failed")
         return float(ms.value), int(k.value)
 
+    def color_plan(self, src, scale: float = 1.0, bias: float = 0.0, costs: bool = False, rows=None, cols=None):
+        """Choose a colour mode per frame from costs measured on the device (``nblic_amd_color_plan``).  ``src`` as
+        ``encode_batch_from(..., color=...)`` takes it -- a tensor [N, 3, H, W] or a list of three views per frame, any
+        layout, one of the four dtypes -- with the same ``scale``, ``bias``, ``rows`` and ``cols``, so the costs are those of
+        the planes the encoder would collect.  Returns a uint8 array of one mode per frame for ``color=`` of the encoder
+        and the decoders; ``COLOR_REFUSED`` (0xFF) marks a frame with a source the library refuses or sources of unequal
+        size.  ``costs=True``: also the [F, 9] uint64 table (``COLOR_PLANES``; zeros for a refused frame).  ``ValueError``
+        when the library refuses the whole call."""
+        _color_arg("rct", src)
+        srcs, fmt = _srcs_of(_src_views(src), rows, cols)
+        n = len(srcs)
+        arr = (Src * max(n, 1))()
+        for k, s in enumerate(srcs):
+            arr[k] = Src(*[int(x) if i else (int(x) or None) for i, x in enumerate(s)])
+        modes, table = np.zeros(max(n // 3, 1), np.uint8), np.zeros((max(n // 3, 1), 9), np.uint64)
+        rc = self.lib.nblic_amd_color_plan(self.handle, n, arr, int(fmt), float(scale), float(bias), _modes_ptr(modes),
+                                           table.ctypes.data_as(C.POINTER(C.c_ulonglong)) if costs else None)
+        if rc != 0:
+            raise ValueError("nblic_amd_color_plan refused the call")
+        return (modes[:n // 3], table[:n // 3]) if costs else modes[:n // 3]
+
+    def color_plan_stats(self) -> Tuple[int, int, float]:
+        """k_color_cost launches and source elements read since the context was created, and the GPU milliseconds of the
+        last :meth:`color_plan`'s launch (``nblic_amd_color_plan_stats``)."""
+        v, ms = (C.c_long * 2)(), C.c_double(0)
+        if self.lib.nblic_amd_color_plan_stats(self.handle, v, C.byref(ms)) != 0:
+            raise RuntimeError("nblic_amd_color_plan_stats failed")
+        return int(v[0]), int(v[1]), float(ms.value)
+
+    def debug_color_cost(self, tasks) -> np.ndarray:
+        """``nblic_amd_debug_color_cost``: ONE k_color_cost launch over ``tasks``, each a dict with ``raws`` (the bytes of the
+        R, G and B sources), ``rows``, ``cols``, ``fmt`` and optionally ``pitches``, ``steps`` (three each, bytes; default:
+        contiguous), ``scale``, ``bias`` and ``base_offsets`` (three, 0 .. 255: where the device copies start).  Returns the
+        [n, 9] uint64 sums."""
+        n = len(tasks)
+        raws, pitches, steps, bases, hs, ws, fmts, scales, biases = ([] for _ in range(9))
+        for t in tasks:
+            fmt = t["fmt"] if isinstance(t["fmt"], int) else collect_format(t["fmt"])
+            elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
+            three = [np.ascontiguousarray(v).reshape(-1).view(np.uint8) for v in t["raws"]]
+            if len(three) != 3:
+                raise ValueError("debug_color_cost: three sources per task")
+            raws += three
+            pitches += [int(v) for v in t.get("pitches", [int(t["cols"]) * elem] * 3)]; steps += [int(v) for v in t.get("steps", [elem] * 3)]
+            bases += [int(v) for v in t.get("base_offsets", (0, 0, 0))]
+            hs.append(int(t["rows"])); ws.append(int(t["cols"])); fmts.append(fmt)
+            scales.append(float(t.get("scale", 1.0))); biases.append(float(t.get("bias", 0.0)))
+        if min(pitches + steps + bases + [0]) < 0:
+            raise ValueError("debug_color_cost: a negative pitch, step or offset")
+        m = max(n, 1)
+        out = np.zeros((m, 9), np.uint64)
+        vp = (C.c_void_p * (3 * m))(*[a.ctypes.data for a in raws])
+        sz = lambda vals: (C.c_size_t * (3 * m))(*[int(v) for v in vals])
+        iv = lambda vals: (C.c_int * m)(*[int(v) for v in vals])
+        fv = lambda vals: (C.c_float * m)(*vals)
+        rc = self.lib.nblic_amd_debug_color_cost(self.handle, n, vp, sz(r.size for r in raws), sz(bases), sz(pitches), sz(steps), iv(hs), iv(ws), iv(fmts),
+                                                 fv(scales), fv(biases), out.ctypes.data_as(C.POINTER(C.c_ulonglong)))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_color_cost refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_color_cost failed (%d)" % rc)
+        return out[:n]
+
     def encode_from_srcs(self, srcs, fmt: int, scale: float = 1.0, bias: float = 0.0, near=0, effort=1, every_rows=None, band_rows: int = 0,
-                         info: Optional[dict] = None, recon_dests=None, recon_fmt: int = 0):
+                         info: Optional[dict] = None, recon_dests=None, recon_fmt: int = 0, modes=None):
         """The four _from calls on ``srcs``, one ``(ptr, pitch_bytes, step_bytes, cap_bytes, rows, cols)`` per image (device
         memory), in format ``fmt`` (0 .. 3).  ``effort`` 0 (for every image) takes the QNBLIC calls, ``every_rows`` the
         indexed ones.  Returns the streams -- ``None`` for a refused or failed image -- or (stream, index) pairs when
         ``every_rows`` is given; ``info`` receives ``rc`` and, for the mode call, ``recons`` (the host reconstructions).
         ``recon_dests`` (the mode call only): one ``(ptr, pitch_bytes, step_bytes, cap_bytes, row0, row1, col0, col1, scale,
         bias)`` per image, ptr 0 for none -- the reconstructions go to device memory in format ``recon_fmt``
-        (``nblic_amd_encode_batch_modes_from_to``) and there are no host ``recons``.
+        (``nblic_amd_encode_batch_modes_from_to``) and there are no host ``recons``.  ``modes``: one colour mode byte per
+        frame of three sources -- the _color siblings of the four calls.
         ``ValueError`` when the library refuses the whole call."""
         n = len(srcs)
         nears, efforts = _per_image(near, n, "near"), _per_image(effort, n, "effort")
@@ -1665,15 +1882,20 @@ class Context:
         lens = (C.c_long * m)(*([-2] * m))                      # (the library writes every length once it has accepted the call)
         head = (self.handle, n, arr, int(fmt), float(scale), float(bias))
         recs = idxs = xlens = None
+        if modes is not None:
+            if recon_dests is not None:
+                raise ValueError("colour modes are lossless: there is no reconstruction to deliver")
+            head += (_modes_ptr(modes),)
+        pick = (lambda name: getattr(self.lib, name + "_color")) if modes is not None else (lambda name: getattr(self.lib, name))
         if every_rows is not None:
             every = _every_rows_list(every_rows, n)
             idxs = [np.empty(max(index_bytes(1 if q else 0, h, w, 0 if q else 1, r), 1), np.uint8) for (h, w), r in zip(shapes, every)]
             xp = (C.c_void_p * m)(*[C.c_void_p(x.ctypes.data) for x in idxs])
             xcaps, xlens = (C.c_size_t * m)(*[x.size for x in idxs]), (C.c_long * m)()
-            call = self.lib.nblic_amd_qencode_batch_indexed_from if q else self.lib.nblic_amd_encode_batch_indexed_from
+            call = pick("nblic_amd_qencode_batch_indexed_from" if q else "nblic_amd_encode_batch_indexed_from")
             rc = call(*head, (C.c_int * m)(*every), int(band_rows), op, caps, lens, xp, xcaps, xlens)
         elif q:
-            rc = self.lib.nblic_amd_qencode_batch_from(*head, op, caps, lens)
+            rc = pick("nblic_amd_qencode_batch_from")(*head, op, caps, lens)
         elif recon_dests is not None:
             if len(recon_dests) != n:
                 raise ValueError("recon_dests: one per image")
@@ -1682,7 +1904,7 @@ class Context:
             if info is not None:
                 recs = [np.zeros(s, np.uint8) for s in shapes]
             rp = (C.c_void_p * m)(*[C.c_void_p(r.ctypes.data) for r in recs]) if recs is not None else None
-            rc = self.lib.nblic_amd_encode_batch_modes_from(*head, (C.c_int * m)(*nears), (C.c_int * m)(*efforts), op, caps, lens, rp)
+            rc = pick("nblic_amd_encode_batch_modes_from")(*head, (C.c_int * m)(*nears), (C.c_int * m)(*efforts), op, caps, lens, rp)
         if rc != 0 and n > 0 and all(v == -2 for v in lens[:n]):
             raise ValueError("the library refused the whole call")
         if info is not None:
@@ -1713,7 +1935,7 @@ class Context:
         return outs, got
 
     def encode_batch_from(self, src, rows=None, cols=None, scale: float = 1.0, bias: float = 0.0, near=0, effort=1, every_rows=None,
-                          band_rows: int = 0, info: Optional[dict] = None, recon_out=None, recon_scale=1.0, recon_bias=0.0, color: Optional[str] = None):
+                          band_rows: int = 0, info: Optional[dict] = None, recon_out=None, recon_scale=1.0, recon_bias=0.0, color=None):
         """Encode images that lie in device memory in any layout, as pixels or as floats quantised on the way (the _from
         calls; include/nblic_amd.h says what the pixel of an element is).  ``src``: one tensor [N, H, W], one tensor
         [N, C, H, W] -- every channel is an image, n-major -- or a list of 2-D tensors or views, of ONE dtype (uint8,
@@ -1736,13 +1958,19 @@ class Context:
         ``(R - G + 128) mod 256``, ``G`` and ``(B - G + 128) mod 256`` (:func:`rct_forward` of the collected planes): ordinary
         streams, which any decoder turns into those planes and ``decode_batch_into(..., color="rct")`` into the frame.
         Lossless only (``near`` 0; no ``recon_out``): ``ValueError`` otherwise, and for any other channel count.  The three
-        sources of a frame have one size; a frame with a refused source has three ``None``."""
-        flag = _color_flag(color, src)
-        if flag and recon_out is not None:
+        sources of a frame have one size; a frame with a refused source has three ``None``.
+
+        ``color=modes``, a sequence or array of one colour mode byte per frame (``COLOR_MODES``; :meth:`color_plan` chooses
+        them): the streams of frame f are those of ``rct_forward(R, G, B, mode=modes[f])`` -- each difference is taken
+        against the frame's base channel.  ``"rct"`` is every mode ``COLOR_RCT``.  A frame of mode 0 is three independent
+        images, and only its images may have ``near`` > 0.  Nothing in a stream names the mode: keep the byte with the
+        frame's three streams.  An invalid byte refuses the whole call (``ValueError``)."""
+        flag, modes = _color_arg(color, src)
+        if color is not None and recon_out is not None:
             raise ValueError('color="rct" is lossless: there is no reconstruction to deliver')
         srcs, fmt = _srcs_of(_src_views(src), rows, cols)
         if recon_out is None:
-            return self.encode_from_srcs(srcs, fmt | flag, scale, bias, near, effort, every_rows, band_rows, info)
+            return self.encode_from_srcs(srcs, fmt | flag, scale, bias, near, effort, every_rows, band_rows, info, modes=modes)
         views = _src_views(recon_out)
         if len(views) != len(srcs):
             raise ValueError("recon_out: one 2-D tensor per image")

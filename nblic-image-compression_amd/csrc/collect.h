@@ -9,9 +9,10 @@
 // cols is no multiple of 16.  A task covers the pixels [px0, px1) of the flat plane (a whole image: [0, rows * cols); the
 // indexed batch: the rows of one band), so its first and its last unit may be shorter than sixteen pixels.
 //
-// A task with a REFERENCE writes the difference plane of the reversible colour transform (R - G, B - G of a frame whose
-// three colours are three sources): the reference is a second source of the same rows x cols, format, scale and bias --
-// the caller's G -- with a pitch and a step of its own, and pixel (row, col) is (own - ref + 128) & 255 of the two
+// A task with a REFERENCE writes a difference plane of a colour frame whose three colours are three sources (R - G and
+// B - G of the fixed transform; any channel against the base channel of the frame's colour mode, color_plan.h): the
+// reference is a second source of the same rows x cols, format, scale and bias -- the caller's base channel, G in the
+// fixed transform -- with a pitch and a step of its own, and pixel (row, col) is (own - ref + 128) & 255 of the two
 // elements there, each quantised as without a reference.  The reference is read where the caller keeps it, never from
 // another task's plane, so the tasks of a launch stay independent of each other.
 #pragma once

@@ -15,7 +15,8 @@
 // window goes to dst + r * dst_pitch + c * dst_step and no other byte is written.
 //
 // A task with a REFERENCE undoes the reversible colour transform: its plane holds differences (R - G or B - G, + 128,
-// mod 256), the reference is the G plane of the same frame -- same width, given from the window's first row on -- and
+// mod 256; with per-frame colour modes, color_plan.h: any channel against the frame's base channel), the reference is the
+// decoded plane of the base channel (G in the fixed transform) of the same frame -- same width, given from the window's first row on -- and
 // the pixel of window position (r, c) is (src + ref - 128) & 255 of the two planes' bytes there; scale, bias and format
 // apply to that pixel.  The three planes of a frame stand or fall together: each of its tasks names all three gates.
 #pragma once

@@ -313,6 +313,8 @@ struct nblic_amd_ctx {
     DevBuf<DeliverTask> dec_deliver;      // nblic_amd_decode_batch_to: the chunks' delivery tasks (grow-only, like dec_jobs)
     std::atomic<long> collect_counts[4] = {};   // nblic_amd_collect_stats: images in place, images collected, k_collect launches, pixels collected
     double collect_ms = 0; long collect_timed = 0;   // nblic_amd_collect_ms: GPU time of the k_collect launches that were timed, and how many.  Guarded by stat_m
+    std::atomic<long> color_counts[2] = {};     // nblic_amd_color_plan_stats: k_color_cost launches, pixels read (three per frame position)
+    double color_ms = 0;                        // nblic_amd_color_plan_stats: GPU time of the last nblic_amd_color_plan's launch.  Guarded by stat_m
     long deliver_tasks = 0, deliver_strided = 0;     // nblic_amd_deliver_stats: of the last call that delivers.  Guarded by stat_m (at the end: no member has moved)
 };
 
@@ -489,7 +491,7 @@ static SerialJob model_job(const uint8_t *img, uint8_t *recon, const E1Buffers &
 enum : uint8_t { kSrcRefused = 0, kSrcInPlace = 1, kSrcCollect = 2 };
 struct CollectFrom {
     const nblic_amd_src *srcs; uint32_t format; float scale, bias;
-    bool rct = false;                                                    // NBLIC_AMD_FORMAT_RCT: sources 3f, 3f + 1, 3f + 2 are R, G, B of frame f
+    std::vector<uint8_t> modes;                                          // not empty: sources 3f, 3f + 1, 3f + 2 are R, G, B of frame f, coded in colour mode modes[f] (color_plan.h)
     std::vector<uint8_t> how;
     std::vector<CollectTask> tasks;                                      // kSrcCollect: all but dst, px0, px1 and first_chunk
     std::vector<const uint8_t *> imgs; std::vector<int> hs, ws;
@@ -1704,15 +1706,28 @@ static bool decode_launch(const DecodeItem &first, const SerialJob *d_jobs, cons
 // ---- delivery to caller-owned device memory (deliver.h, serial_engine.h k_deliver) ----------------------------------------
 // What the _to calls hand down: one destination per image with its step and normalisation, one format per call.  The
 // calls without a step make theirs here (dests_ex): the element size, and the call's scale / bias in every image.
-// rct (NBLIC_AMD_FORMAT_RCT): images 3f, 3f + 1, 3f + 2 are the R - G, G and B - G planes of frame f, and R and B are put
-// together again on the way out (deliver.h: a task with a reference).
-struct DeliverTo { const nblic_amd_dest_ex *dests; uint32_t format; bool rct = false; };
+// modes (the _color calls; NBLIC_AMD_FORMAT_RCT: every one 0x0D): images 3f, 3f + 1, 3f + 2 are the three planes of frame f
+// in colour mode modes[f] (color_plan.h), and the channels coded as differences are put together again on the way out
+// (deliver.h: a task with a reference).  A frame of mode 0 is three images like any other.
+struct DeliverTo {
+    const nblic_amd_dest_ex *dests; uint32_t format; const uint8_t *modes = nullptr;
+    uint32_t mode_of(int k) const { return modes ? modes[k / 3] : 0u; }  // of the frame image k belongs to
+};
 
 // NBLIC_AMD_FORMAT_RCT in a format argument of a _from or a _to_ex call: is it there?  It is taken off.
 static bool format_rct(int &format) {
     const bool rct = format >= 0 && (format & NBLIC_AMD_FORMAT_RCT) != 0;
     if (rct) format &= ~NBLIC_AMD_FORMAT_RCT;
     return rct;
+}
+
+// Every frame's mode 0x0D: what the flag stands for in the _color calls' terms.
+static std::vector<uint8_t> rct_modes(int n) { return std::vector<uint8_t>(size_t(std::max(n, 0) / 3), uint8_t(kColorRct)); }
+// The modes of a _color call: n / 3 valid bytes?
+static bool color_modes_ok(int n, const unsigned char *modes) {
+    if (n < 0 || n % 3 != 0 || !modes) return false;
+    for (int f = 0; f < n / 3; f++) if (!color_mode_valid(modes[f])) return false;
+    return true;
 }
 
 // Do the three tasks of a colour frame name the same window (in rows and columns of the image)?
@@ -1826,19 +1841,23 @@ static void collect_plan(const nblic_amd_ctx *c, CollectFrom &from, int n) {
         from.hs[i] = from.srcs[k].rows; from.ws[i] = from.srcs[k].cols;
         if (from.how[i] == kSrcInPlace) from.imgs[i] = from.tasks[i].src;
     }
-    if (!from.rct) return;
-    // Colour frames: R and B become tasks with the frame's G SOURCE as their reference (collect.h) -- collected even where
-    // they could be used in place -- and G stays what it was.  A frame with a refused source, or sources of unequal size, is
-    // refused as a whole.
+    if (from.modes.empty()) return;
+    // Colour frames: a channel that the frame's mode codes as a difference becomes a task with the base channel's SOURCE as
+    // its reference (collect.h) -- collected even where it could be used in place -- and the others stay what they were.  A
+    // frame with a difference and a refused source, or sources of unequal size, is refused as a whole; a frame of mode 0 is
+    // three images like any other.
     for (size_t f = 0; f + 2 < count; f += 3) {
-        const CollectTask &G = from.tasks[f + 1];
+        const uint32_t mode = from.modes[f / 3];
+        if (mode == kColorPlain) continue;
         bool ok = true;
         for (size_t i = f; i < f + 3; i++) ok = ok && from.how[i] != kSrcRefused && from.hs[i] == from.hs[f] && from.ws[i] == from.ws[f];
         for (size_t i = f; i < f + 3; i++) {
             if (!ok) { from.how[i] = kSrcRefused; from.imgs[i] = nullptr; from.hs[i] = from.ws[i] = 0; continue; }
-            if (i == f + 1) continue;
+            const int ref = color_mode_ref(mode, uint32_t(i - f));
+            if (ref < 0) continue;
+            const CollectTask &B = from.tasks[f + size_t(ref)];
             CollectTask &T = from.tasks[i];
-            T.ref = G.src; T.ref_pitch = G.pitch; T.ref_step = G.step;
+            T.ref = B.src; T.ref_pitch = B.pitch; T.ref_step = B.step;
             from.how[i] = kSrcCollect; from.imgs[i] = nullptr;
         }
     }
@@ -1876,8 +1895,8 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         arena += stream_buf_bytes(it.len) + up256(size_t(it.h) * size_t(it.w)) + up256(lsq_stats_bytes(it.kind, it.effort, it.w)) +
                  up256(record_state_bytes(it.kind)) + (it.kind ? up256(kQTab) : 0);
     }
-    if (to && to->rct) {
-        // a colour frame stands or falls as a whole: three lossless planes of one size, three destinations of one window
+    if (to && to->modes) {
+        // a colour frame with a difference stands or falls as a whole: three lossless planes of one size, three destinations of one window
         auto bytes_of = [](const DecodeItem &it) {
             return stream_buf_bytes(it.len) + up256(size_t(it.h) * size_t(it.w)) + up256(lsq_stats_bytes(it.kind, it.effort, it.w)) + up256(record_state_bytes(it.kind)) + (it.kind ? up256(kQTab) : 0);
         };
@@ -1886,6 +1905,10 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         std::vector<uint8_t> keep(items.size(), 0);
         for (int f = 0; f + 2 < n; f += 3) {
             const int a = at[size_t(f)], b = at[size_t(f) + 1], d = at[size_t(f) + 2];
+            if (to->mode_of(f) == kColorPlain) {                         // three images like any other
+                for (int i : {a, b, d}) if (i >= 0) keep[size_t(i)] = 1;
+                continue;
+            }
             if (a < 0 || b < 0 || d < 0) continue;
             const DecodeItem &A = items[size_t(a)], &B = items[size_t(b)], &D = items[size_t(d)];
             if (A.h != B.h || A.h != D.h || A.w != B.w || A.w != D.w || A.near || B.near || D.near) continue;
@@ -1931,18 +1954,21 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
             T.src = recon; T.src_bytes = up256(size_t(it.h) * size_t(it.w)); T.gate = state;
         }
     }
-    const bool rct = to && to->rct;
-    if (rct) {                                                           // every task of a frame is gated by its three records; R and B refer to G's plane
+    const bool rct = to && to->modes;
+    if (rct) {                                                           // every task of a frame with a difference is gated by its three records; a difference refers to the base's plane
         std::vector<int> at(size_t(n), -1);
         for (int i = 0; i < m; i++) at[size_t(items[size_t(i)].k)] = i;
         for (int i = 0; i < m; i++) {
             const int k = items[size_t(i)].k, f = k - k % 3;
-            const DeliverTask &G = deliveries[size_t(at[size_t(f) + 1])];
+            const uint32_t mode = to->mode_of(k);
+            if (mode == kColorPlain) continue;
             DeliverTask &T = deliveries[size_t(i)];
             T.gate = jobs[size_t(at[size_t(f)])].state; T.gate2 = jobs[size_t(at[size_t(f) + 1])].state; T.gate3 = jobs[size_t(at[size_t(f) + 2])].state;
-            if (k % 3 == 1) continue;
+            const int ref = color_mode_ref(mode, uint32_t(k % 3));
+            if (ref < 0) continue;
+            const DeliverTask &B = deliveries[size_t(at[size_t(f) + size_t(ref)])];
             const size_t skip = size_t(T.row0) * size_t(T.src_pitch);
-            T.ref = G.src + skip; T.ref_bytes = G.src_bytes - skip; T.ref_pitch = T.src_pitch;
+            T.ref = B.src + skip; T.ref_bytes = B.src_bytes - skip; T.ref_pitch = T.src_pitch;
         }
     }
     // Chunks of one (codec, effort) class, at most kDecodeChunk images each, alternate between two streams: a chunk's uploads,
@@ -2009,7 +2035,7 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
     for (int i = 0; i < m; i++) status[items[size_t(i)].k] = heads[size_t(i)].status == kDone ? 0 : -1;
     if (rct)                                                             // what the gates did on the device: a frame with a failed plane has none
         for (int f = 0; f + 2 < n; f += 3)
-            if (status[f] != 0 || status[f + 1] != 0 || status[f + 2] != 0) status[f] = status[f + 1] = status[f + 2] = -1;
+            if (to->mode_of(f) != kColorPlain && (status[f] != 0 || status[f + 1] != 0 || status[f + 2] != 0)) status[f] = status[f + 1] = status[f + 2] = -1;
     return true;
 }
 
@@ -3679,8 +3705,9 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
         per_seg_max = std::max(per_seg_max, up256(I.V.L.b) + up256(2 * I.V.L.b_bytes) + (I.V.packed ? 2 * up256(I.V.L.tab + 15) : 0));
         I.live = true;
     }
-    if (to && to->rct)                                                   // a colour frame stands or falls as a whole: three lossless planes of one size, one window
+    if (to && to->modes)                                                 // a colour frame with a difference stands or falls as a whole: three lossless planes of one size, one window
         for (int f = 0; f + 2 < n; f += 3) {
+            if (to->mode_of(f) == kColorPlain) continue;
             IdxDecImage &A = all[size_t(f)], &B = all[size_t(f) + 1], &D = all[size_t(f) + 2];
             const bool ok = A.live && B.live && D.live && A.it.h == B.it.h && A.it.h == D.it.h && A.it.w == B.it.w && A.it.w == D.it.w &&
                             !A.it.near && !B.it.near && !D.it.near && same_window(A.deliver, B.deliver) && same_window(A.deliver, D.deliver);
@@ -3928,18 +3955,19 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
             fprintf(stderr, "[nblic_amd] indexed batch decode: image %d: %s\n", I->k,
                     bad ? "a segment does not end where the next entry starts (index and stream disagree)" : "the stream is damaged or ends too early");
     }
-    if (to && to->rct)                                                   // a frame with a damaged plane has none; R and B refer to G's plane, whose first row may be another
+    if (to && to->modes)                                                 // a frame with a damaged plane has none; a difference refers to the base's plane, whose first row may be another
         for (IdxDecImage *I : live) {
             const size_t f = size_t(I->k - I->k % 3);
-            IdxDecImage &G = all[f + 1];
-            if (all[f].bad || G.bad || all[f + 2].bad) continue;
-            if (I->k % 3 == 1) continue;
+            const int ref = color_mode_ref(to->mode_of(I->k), uint32_t(I->k % 3));
+            if (ref < 0) continue;
+            IdxDecImage &G = all[f + size_t(ref)];
+            if (all[f].bad || all[f + 1].bad || all[f + 2].bad) continue;
             const size_t skip = size_t(I->row0 - G.base) * size_t(I->it.w);
             I->deliver.ref = G.d_plane + skip; I->deliver.ref_bytes = G.plane_bytes - skip; I->deliver.ref_pitch = uint32_t(I->it.w);
         }
     for (IdxDecImage *I : live) {
         const size_t f = size_t(I->k - I->k % 3);
-        if (I->bad || (to && to->rct && (all[f].bad || all[f + 1].bad || all[f + 2].bad))) {
+        if (I->bad || (to && to->mode_of(I->k) != kColorPlain && (all[f].bad || all[f + 1].bad || all[f + 2].bad))) {
             if (to) { I->deliver.zero = 1; deliveries.push_back(I->deliver); }
             else memset(outs[I->k], 0, I->out_bytes);
             continue;
@@ -5272,6 +5300,160 @@ int nblic_amd_collect_stats(nblic_amd_ctx *c, long out[4]) {
     return 0;
 }
 
+// ---- the colour plan: costs on the device, the choice on the host (color_plan.h, serial_engine.h k_color_cost) --------------
+// The tasks' places in ONE k_color_cost launch, their upload and the launch, queued on st.  The costs are the caller's to zero.
+static bool color_cost_queue(nblic_amd_ctx *c, ColorCostTask *tasks, size_t n, ColorCostTask *d_tasks, hipStream_t st) {
+    unsigned long long tiles = 0, pixels = 0;
+    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(tiles); tiles += color_task_tiles(tasks[i]); pixels += 3ull * tasks[i].rows * tasks[i].cols; }
+    if (n == 0) return true;
+    if (tiles >= (1ull << 31) || n >= (size_t(1) << 30)) return false;
+    c->color_counts[0] += 1; c->color_counts[1] += long(pixels);
+    return hipMemcpyAsync(d_tasks, tasks, n * sizeof(ColorCostTask), hipMemcpyHostToDevice, st) == hipSuccess && color_cost_launch(d_tasks, int(n), uint32_t(tiles), st);
+}
+
+int nblic_amd_color_plan(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                         unsigned char *frame_modes, unsigned long long *costs) {
+    if (!c || c->broken || n_images < 0 || n_images % 3 != 0 || !srcs || !frame_modes || format >= int(kCollectFormats) || !deliver_args_ok(format, scale, bias) ||
+        hipSetDevice(c->device) != hipSuccess) return -1;
+    const size_t frames = size_t(n_images) / 3;
+    std::lock_guard<std::mutex> g(c->api);
+    CollectFrom from{};
+    from.srcs = srcs; from.format = uint32_t(format); from.scale = scale; from.bias = bias;
+    std::vector<ColorCostTask> tasks;
+    std::vector<size_t> frame_of;
+    for (size_t f = 0; f < frames; f++) {                                // a frame with a refused source, or sources of unequal size: 0xFF, and nothing is launched for it
+        ColorCostTask T{};
+        bool ok = true;
+        for (int ch = 0; ch < 3; ch++) {
+            CollectTask S;
+            ok = ok && collect_src_task(c, from, int(3 * f) + ch, S) != kSrcRefused && (ch == 0 || (S.rows == T.rows && S.cols == T.cols));
+            if (!ok) break;
+            T.src[ch] = S.src; T.pitch[ch] = S.pitch; T.step[ch] = S.step; T.rows = S.rows; T.cols = S.cols;
+        }
+        frame_modes[f] = uint8_t(kColorRefused);
+        if (!ok) continue;
+        T.format = uint32_t(format); T.scale = scale; T.bias = bias;
+        tasks.push_back(T); frame_of.push_back(f);
+    }
+    std::vector<unsigned long long> table(frames * kColorCosts, 0ull);
+    if (!tasks.empty()) {
+        Stream st;
+        Event t0, t1;
+        DevPool mem;
+        unsigned long long *d_costs = mem.make<unsigned long long>(tasks.size() * kColorCosts);
+        ColorCostTask *d_tasks = mem.make<ColorCostTask>(tasks.size());
+        std::vector<unsigned long long> back(tasks.size() * kColorCosts);
+        if (!d_costs || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess || t0.create(hipEventDefault) != hipSuccess || t1.create(hipEventDefault) != hipSuccess) return -1;
+        for (size_t i = 0; i < tasks.size(); i++) tasks[i].costs = d_costs + i * kColorCosts;
+        const bool ok = [&]() -> bool {                                  // the launch, then ONE copy of the whole table
+            HIP_OK(hipMemsetAsync(d_costs, 0, back.size() * sizeof(unsigned long long), st));
+            HIP_OK(hipEventRecord(t0, st));
+            if (!color_cost_queue(c, tasks.data(), tasks.size(), d_tasks, st)) return false;
+            HIP_OK(hipEventRecord(t1, st));
+            HIP_OK(hipMemcpyAsync(back.data(), d_costs, back.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            return true;
+        }();
+        if (st) hipStreamSynchronize(st);
+        if (!ok) return -1;
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, t0, t1) == hipSuccess) { std::lock_guard<std::mutex> l(c->stat_m); c->color_ms = double(ms); }
+        for (size_t i = 0; i < tasks.size(); i++) {
+            memcpy(&table[frame_of[i] * kColorCosts], &back[i * kColorCosts], kColorCosts * sizeof(unsigned long long));
+            frame_modes[frame_of[i]] = color_choose(&back[i * kColorCosts]);
+        }
+    }
+    if (costs) memcpy(costs, table.data(), table.size() * sizeof(unsigned long long));
+    return 0;
+}
+
+unsigned char nblic_amd_color_choose(const unsigned long long costs[9]) { return costs ? color_choose(costs) : uint8_t(kColorRefused); }
+int nblic_amd_color_mode_valid(int mode) { return mode >= 0 && mode < 256 && color_mode_valid(uint32_t(mode)) ? 1 : 0; }
+int nblic_amd_color_mode_ref(int mode, int channel) {
+    return nblic_amd_color_mode_valid(mode) && channel >= 0 && channel < 3 ? color_mode_ref(uint32_t(mode), uint32_t(channel)) : -2;
+}
+
+int nblic_amd_color_plan_stats(nblic_amd_ctx *c, long out[2], double *last_plan_ms) {
+    if (!c || !out) return -1;
+    for (int k = 0; k < 2; k++) out[k] = c->color_counts[k].load();
+    if (last_plan_ms) { std::lock_guard<std::mutex> l(c->stat_m); *last_plan_ms = c->color_ms; }
+    return 0;
+}
+
+// A debug frame's task: all but the sources' addresses and costs.  false: an argument no task can hold.
+static bool debug_color_task(ColorCostTask &T, const size_t *pitches, const size_t *steps, int rows, int cols, int format, float scale, float bias) {
+    T = ColorCostTask{};
+    if (rows < 1 || cols < 1 || format < 0 || format >= int(kCollectFormats)) return false;
+    for (int ch = 0; ch < 3; ch++) {
+        if (steps[ch] > 0xFFFFFFFFull) return false;                     // (collect_source_ok holds it against its limit)
+        T.pitch[ch] = pitches[ch]; T.step[ch] = uint32_t(steps[ch]);
+    }
+    T.rows = uint32_t(rows); T.cols = uint32_t(cols); T.format = uint32_t(format); T.scale = scale; T.bias = bias;
+    return true;
+}
+
+// Host only: the shared tile walk (color_plan.h color_cost_host) over the three sources of ONE frame, cap_bytes[ch] readable
+// from srcs[ch].  costs: the nine sums; tiles: how many the kernel would run.  -1: refused.
+int nblic_amd_debug_color_cost_host(const void *const *srcs, const size_t *cap_bytes, const size_t *pitches, const size_t *steps, int rows, int cols,
+                                    int format, float scale, float bias, unsigned long long *costs, unsigned long long *tiles) {
+    ColorCostTask T;
+    if (!srcs || !cap_bytes || !pitches || !steps || !costs || !debug_color_task(T, pitches, steps, rows, cols, format, scale, bias)) return -1;
+    unsigned long long caps[3];
+    for (int ch = 0; ch < 3; ch++) { T.src[ch] = static_cast<const uint8_t *>(srcs[ch]); caps[ch] = cap_bytes[ch]; }
+    T.costs = costs;
+    if (!color_task_ok(T, caps)) return -1;
+    if (tiles) *tiles = color_task_tiles(T);
+    for (uint32_t k = 0; k < kColorCosts; k++) costs[k] = 0;
+    color_cost_host(T);
+    return 0;
+}
+
+// ONE k_color_cost launch over n caller-made frames as n tasks.  Three sources per frame (index 3 k + channel), each uploaded
+// at byte base_offsets[] (0 .. 255) of a region of its own filled with 0xFF that is larger, as nblic_amd_debug_collect does.
+// costs: nine sums per frame.  -1: refused; -2: a HIP call failed.
+int nblic_amd_debug_color_cost(nblic_amd_ctx *c, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets,
+                               const size_t *pitches, const size_t *steps, const int *rows, const int *cols, const int *formats,
+                               const float *scales, const float *biases, unsigned long long *costs) {
+    constexpr int kMaxTasks = 65536;
+    if (!c || n < 1 || n > kMaxTasks || !srcs || !src_bytes || !base_offsets || !pitches || !steps || !rows || !cols || !formats || !scales || !biases || !costs) return -1;
+    const size_t count = size_t(n);
+    std::vector<ColorCostTask> tasks(count);
+    std::vector<size_t> src_at(3 * count);
+    size_t srcs_total = 0;
+    for (size_t i = 0; i < count; i++) {
+        if (!debug_color_task(tasks[i], pitches + 3 * i, steps + 3 * i, rows[i], cols[i], formats[i], scales[i], biases[i])) return -1;
+        for (size_t s = 3 * i; s < 3 * i + 3; s++) {
+            if (!srcs[s] || base_offsets[s] > 255 || src_bytes[s] > (size_t(1) << 30)) return -1;
+            src_at[s] = srcs_total; srcs_total += up256(base_offsets[s] + src_bytes[s] + 256);
+        }
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    Stream st;
+    DevPool mem;
+    uint8_t *d_srcs = mem.make<uint8_t>(srcs_total);
+    unsigned long long *d_costs = mem.make<unsigned long long>(count * kColorCosts);
+    ColorCostTask *d_tasks = mem.make<ColorCostTask>(count);
+    if (!d_srcs || !d_costs || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    for (size_t i = 0; i < count; i++) {                                 // the addresses are known now: the rest of the checks
+        ColorCostTask &T = tasks[i];
+        unsigned long long caps[3];
+        for (size_t ch = 0; ch < 3; ch++) { T.src[ch] = d_srcs + src_at[3 * i + ch] + base_offsets[3 * i + ch]; caps[ch] = src_bytes[3 * i + ch]; }
+        T.costs = d_costs + i * kColorCosts;
+        if (!color_task_ok(T, caps)) return -1;                          // nothing outside the uploaded bytes is the task's to read
+    }
+    const bool ok = [&]() -> bool {
+        HIP_OK(hipMemsetAsync(d_srcs, 0xFF, srcs_total, st));
+        HIP_OK(hipMemsetAsync(d_costs, 0, count * kColorCosts * sizeof(unsigned long long), st));
+        for (size_t s = 0; s < 3 * count; s++) HIP_OK(hipMemcpyAsync(d_srcs + src_at[s] + base_offsets[s], srcs[s], src_bytes[s], hipMemcpyHostToDevice, st));
+        if (!color_cost_queue(c, tasks.data(), count, d_tasks, st)) return false;
+        HIP_OK(hipMemcpyAsync(costs, d_costs, count * kColorCosts * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    return ok ? 0 : -2;
+}
+
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
 
 int nblic_amd_copy_stats(nblic_amd_ctx *c, long out[4]) {
@@ -5420,13 +5602,11 @@ int nblic_amd_decode_batch_to(nblic_amd_ctx *c, int n_images, const unsigned cha
     const std::vector<nblic_amd_dest_ex> ex = dests_ex(dests, n_images, format, scale, bias);
     return nblic_amd_decode_batch_to_ex(c, n_images, streams, stream_lens, ex.data(), format, heights, widths, nears, efforts, status);
 }
-int nblic_amd_decode_batch_to_ex(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens, const nblic_amd_dest_ex *dests,
-                                 int format, int *heights, int *widths, int *nears, int *efforts, int *status) {
-    const bool rct = format_rct(format);
+static int decode_batch_to_modes(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens, const nblic_amd_dest_ex *dests,
+                                 int format, const uint8_t *modes, int *heights, int *widths, int *nears, int *efforts, int *status) {
     if (!c || c->broken || n_images < 0 || !streams || !stream_lens || !dests || !heights || !widths || !nears || !efforts || !status || format < 0 || format >= int(kDeliverFormats)) return -1;
-    if (rct && n_images % 3 != 0) return -1;
     for (int k = 0; k < n_images; k++) if (!streams[k]) return -1;
-    const DeliverTo to{dests, uint32_t(format), rct};
+    const DeliverTo to{dests, uint32_t(format), modes};
     std::lock_guard<std::mutex> g(c->api);
     deliver_stats_reset(c);
     if (!decode_batch(c, n_images, streams, stream_lens, nullptr, nullptr, heights, widths, nears, efforts, status, &to)) return -1;
@@ -5565,27 +5745,60 @@ int nblic_amd_qencode_batch_indexed(nblic_amd_ctx *c, int n_images, const unsign
     return indexed_batch(kIdxQnblic, c, n_images, imgs, imgs_on_device != 0, heights, widths, every_rows, band_rows, outs, out_caps_words, out_len_words, indexes, index_caps, index_lens);
 }
 
+int nblic_amd_decode_batch_to_ex(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens, const nblic_amd_dest_ex *dests,
+                                 int format, int *heights, int *widths, int *nears, int *efforts, int *status) {
+    const bool rct = format_rct(format);
+    if (rct && (n_images < 0 || n_images % 3 != 0)) return -1;
+    const std::vector<uint8_t> modes = rct_modes(rct ? n_images : 0);
+    return decode_batch_to_modes(c, n_images, streams, stream_lens, dests, format, rct ? modes.data() : nullptr, heights, widths, nears, efforts, status);
+}
+int nblic_amd_decode_batch_to_ex_color(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens, const nblic_amd_dest_ex *dests,
+                                       int format, const unsigned char *frame_modes, int *heights, int *widths, int *nears, int *efforts, int *status) {
+    if (!color_modes_ok(n_images, frame_modes)) return -1;
+    return decode_batch_to_modes(c, n_images, streams, stream_lens, dests, format, frame_modes, heights, widths, nears, efforts, status);
+}
+
 // ---- ENCODE FROM DEVICE MEMORY: the four batch encoders on sources instead of planes ------------------------------------------
 // What every _from call starts with: the whole-call refusals, then the sources checked one by one (collect_plan).
-static bool collect_from_begin(nblic_amd_ctx *c, int n, const nblic_amd_src *srcs, int format, float scale, float bias, CollectFrom &from) {
-    from.rct = format_rct(format);
-    if (from.rct && n % 3 != 0) return false;
+// frame_modes: the _color calls' (one valid byte per frame); NULL: none but what NBLIC_AMD_FORMAT_RCT in `format` says.
+static bool collect_from_begin(nblic_amd_ctx *c, int n, const nblic_amd_src *srcs, int format, float scale, float bias, CollectFrom &from,
+                               const unsigned char *frame_modes = nullptr) {
+    if (frame_modes) {
+        if (!color_modes_ok(n, frame_modes)) return false;
+        from.modes.assign(frame_modes, frame_modes + n / 3);
+    } else if (format_rct(format)) {
+        if (n < 0 || n % 3 != 0) return false;
+        from.modes = rct_modes(n);
+    }
     if (!c || c->broken || n < 0 || !srcs || !deliver_args_ok(format, scale, bias) || hipSetDevice(c->device) != hipSuccess) return false;
     from.srcs = srcs; from.format = uint32_t(format); from.scale = scale; from.bias = bias;
     collect_plan(c, from, n);
     return true;
 }
 
-int nblic_amd_encode_batch_modes_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
-                                      const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
-                                      unsigned char *const *recons) {
+static int encode_batch_modes_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                   const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
+                                   unsigned char *const *recons, const unsigned char *frame_modes) {
     CollectFrom from{};
-    if (format >= 0 && (format & NBLIC_AMD_FORMAT_RCT) && nears)         // a difference plane off by +-near wraps to +-255 in R or B
+    if (format >= 0 && (format & NBLIC_AMD_FORMAT_RCT) && !frame_modes && nears)         // a difference plane off by +-near wraps to +-255 in R or B
         for (int k = 0; k < n_images; k++) if (nears[k] > 0) return -1;
-    if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from)) return -1;
+    if (frame_modes && nears && color_modes_ok(n_images, frame_modes))   // the same, frame by frame: mode 0 has no difference plane
+        for (int k = 0; k < n_images; k++) if (nears[k] > 0 && frame_modes[k / 3] != kColorPlain) return -1;
+    if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from, frame_modes)) return -1;
     const bool ok = run_batch(c, nblic_amd_ctx::SubmitItem{nullptr, 0, n_images, from.imgs.data(), true, from.hs.data(), from.ws.data(), outs, out_caps, out_lens, nears, efforts, recons, &from});
     if (nothing_outstanding(c)) for (auto &g : c->groups) collect_timing(c, g);       // (nblic_amd_stage_times, as nblic_amd_encode_batch leaves them)
     return ok ? 0 : -1;
+}
+int nblic_amd_encode_batch_modes_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                      const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
+                                      unsigned char *const *recons) {
+    return encode_batch_modes_from(c, n_images, srcs, format, scale, bias, nears, efforts, outs, out_caps, out_lens, recons, nullptr);
+}
+int nblic_amd_encode_batch_modes_from_color(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                            const unsigned char *frame_modes, const int *nears, const int *efforts, unsigned char *const *outs,
+                                            const size_t *out_caps, long *out_lens, unsigned char *const *recons) {
+    if (!frame_modes || format < 0 || format >= int(kCollectFormats)) return -1;
+    return encode_batch_modes_from(c, n_images, srcs, format, scale, bias, nears, efforts, outs, out_caps, out_lens, recons, frame_modes);
 }
 int nblic_amd_encode_batch_modes_from_to(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
                                          const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
@@ -5602,18 +5815,28 @@ int nblic_amd_encode_batch_modes_from_to(nblic_amd_ctx *c, int n_images, const n
     if (nothing_outstanding(c)) for (auto &g : c->groups) collect_timing(c, g);
     return ok ? 0 : -1;
 }
-int nblic_amd_qencode_batch_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
-                                 uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words) {
+static int qencode_batch_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                              uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words, const unsigned char *frame_modes) {
     CollectFrom from{};
-    if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from)) return -1;
+    if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from, frame_modes)) return -1;
     return run_batch(c, nblic_amd_ctx::SubmitItem{nullptr, 1, n_images, from.imgs.data(), true, from.hs.data(), from.ws.data(), reinterpret_cast<unsigned char *const *>(outs),
                                                   out_caps_words, out_len_words, nullptr, nullptr, nullptr, &from}) ? 0 : -1;
 }
+int nblic_amd_qencode_batch_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                 uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words) {
+    return qencode_batch_from(c, n_images, srcs, format, scale, bias, outs, out_caps_words, out_len_words, nullptr);
+}
+int nblic_amd_qencode_batch_from_color(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                       const unsigned char *frame_modes, uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words) {
+    if (!frame_modes || format < 0 || format >= int(kCollectFormats)) return -1;
+    return qencode_batch_from(c, n_images, srcs, format, scale, bias, outs, out_caps_words, out_len_words, frame_modes);
+}
 extern "C++" template <class Out>
 static int indexed_batch_from(const IdxCodec &F, nblic_amd_ctx *c, int n, const nblic_amd_src *srcs, int format, float scale, float bias, const int *every, int band_rows,
-                              Out *const *outs, const size_t *caps, long *lens, unsigned char *const *indexes, const size_t *icaps, long *ilens) {
+                              Out *const *outs, const size_t *caps, long *lens, unsigned char *const *indexes, const size_t *icaps, long *ilens,
+                              const unsigned char *frame_modes = nullptr) {
     CollectFrom from{};
-    if (n < 1 || !collect_from_begin(c, n, srcs, format, scale, bias, from)) return -1;
+    if (n < 1 || !collect_from_begin(c, n, srcs, format, scale, bias, from, frame_modes)) return -1;
     return indexed_batch(F, c, n, from.imgs.data(), true, from.hs.data(), from.ws.data(), every, band_rows, outs, caps, lens, indexes, icaps, ilens, &from);
 }
 int nblic_amd_encode_batch_indexed_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
@@ -5625,6 +5848,20 @@ int nblic_amd_qencode_batch_indexed_from(nblic_amd_ctx *c, int n_images, const n
                                          const int *every_rows, int band_rows, uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words,
                                          unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
     return indexed_batch_from(kIdxQnblic, c, n_images, srcs, format, scale, bias, every_rows, band_rows, outs, out_caps_words, out_len_words, indexes, index_caps, index_lens);
+}
+
+int nblic_amd_encode_batch_indexed_from_color(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                              const unsigned char *frame_modes, const int *every_rows, int band_rows, unsigned char *const *outs,
+                                              const size_t *out_caps, long *out_lens, unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
+    if (!frame_modes || format < 0 || format >= int(kCollectFormats)) return -1;
+    return indexed_batch_from(kIdxNblic, c, n_images, srcs, format, scale, bias, every_rows, band_rows, outs, out_caps, out_lens, indexes, index_caps, index_lens, frame_modes);
+}
+int nblic_amd_qencode_batch_indexed_from_color(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                               const unsigned char *frame_modes, const int *every_rows, int band_rows, uint16_t *const *outs,
+                                               const size_t *out_caps_words, long *out_len_words, unsigned char *const *indexes, const size_t *index_caps,
+                                               long *index_lens) {
+    if (!frame_modes || format < 0 || format >= int(kCollectFormats)) return -1;
+    return indexed_batch_from(kIdxQnblic, c, n_images, srcs, format, scale, bias, every_rows, band_rows, outs, out_caps_words, out_len_words, indexes, index_caps, index_lens, frame_modes);
 }
 
 long nblic_amd_debug_q_entropy(int height, int width, const uint16_t *words, const unsigned int *hist, const int *entry_rows, int n_entries,
@@ -5666,8 +5903,17 @@ int nblic_amd_decode_batch_indexed_to_ex(nblic_amd_ctx *c, int n_images, const u
                                          const void *const *indexes, const size_t *index_lens, const nblic_amd_dest_ex *dests, int format,
                                          int *heights, int *widths, int *nears, int *efforts, int *status) {
     const bool rct = format_rct(format);
-    if (!dests || format < 0 || format >= int(kDeliverFormats) || (rct && n_images % 3 != 0)) return -1;
-    const DeliverTo to{dests, uint32_t(format), rct};
+    if (!dests || format < 0 || format >= int(kDeliverFormats) || (rct && (n_images < 0 || n_images % 3 != 0))) return -1;
+    const std::vector<uint8_t> modes = rct_modes(rct ? n_images : 0);
+    const DeliverTo to{dests, uint32_t(format), rct ? modes.data() : nullptr};
+    deliver_stats_reset(c);
+    return decode_batch_indexed(c, n_images, streams, stream_lens, indexes, index_lens, nullptr, nullptr, nullptr, nullptr, heights, widths, nears, efforts, status, &to);
+}
+int nblic_amd_decode_batch_indexed_to_ex_color(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                               const void *const *indexes, const size_t *index_lens, const nblic_amd_dest_ex *dests, int format,
+                                               const unsigned char *frame_modes, int *heights, int *widths, int *nears, int *efforts, int *status) {
+    if (!dests || format < 0 || format >= int(kDeliverFormats) || !color_modes_ok(n_images, frame_modes)) return -1;
+    const DeliverTo to{dests, uint32_t(format), frame_modes};
     deliver_stats_reset(c);
     return decode_batch_indexed(c, n_images, streams, stream_lens, indexes, index_lens, nullptr, nullptr, nullptr, nullptr, heights, widths, nears, efforts, status, &to);
 }

@@ -20,6 +20,7 @@
 
 #include "deliver.h"
 #include "collect.h"
+#include "color_plan.h"
 
 namespace nblic {
 
@@ -203,6 +204,15 @@ bool deliver_launch(const DeliverTask *d_tasks, int n, uint32_t chunks, hipStrea
 // d_tasks[0..n) with first_chunk filled in (from 0), `chunks` their sum.
 // false: the launch failed.
 bool collect_launch(const CollectTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
+
+// ---- the cost of a colour frame's nine candidate planes (color_plan.h ColorCostTask) ------------------------------------------
+// k_color_cost, beside k_collect: tasks with first_chunk, one workgroup per tile of kColorTile x kColorTile pixels of one
+// frame.  The workgroup stages the tile's R, G, B pixels -- quantised by k_collect's loader, each source element once -- with
+// one row above and one column to the left in LDS, computes the nine residual costs of every pixel from there, and adds its
+// nine sums (lanes, then waves in LDS) to the task's costs with one 64-bit atomic each: integer adds, so the result does
+// not depend on the launch's geometry or order.  The costs are zeroed by the caller.  d_tasks[0..n) with first_chunk
+// filled in (from 0), `tiles` their sum.  false: the launch failed.
+bool color_cost_launch(const ColorCostTask *d_tasks, int n, uint32_t tiles, hipStream_t s);
 
 // ---- a packed index (index_pack.h), expanded on the device ------------------------------------------------------------------
 // A packed index is uploaded as it is (any address).  The bodies of the entries a round needs are written, unpacked, into an

@@ -2000,6 +2000,92 @@ bool collect_launch(const CollectTask *d_tasks, int n, uint32_t chunks, hipStrea
     return hipGetLastError() == hipSuccess;
 }
 
+// ---- the costs of a colour frame's nine candidate planes (color_plan.h ColorCostTask) ------------------------------------------
+static_assert(kColorTile == 64 && kIndexThreads == 4 * 64, "a lane per tile column, sixteen rows per wave");
+constexpr uint32_t kColorLdsRows = kColorTile + 1;                   // the row above the tile, then its rows
+constexpr uint32_t kColorLdsPitch = kColorTile + 4;                  // bytes: byte 3 is the column to the left, byte 4 tile column 0 -- units are whole words,
+                                                                     // and 17 words a row keep the words of neighbouring rows on different banks
+constexpr uint32_t kColorRowUnits = kColorTile / kCollectUnitPixels;
+
+// One workgroup per tile.  STAGE: the tile's rows and the row above, as units of sixteen pixels of one row (one unit per
+// lane and step, neighbouring lanes on neighbouring units, loaded by k_collect's collect_unit_load: aligned words where
+// the elements are neighbours, element by element where they are strided), and the column to the left element by element;
+// every source element is converted once and nothing outside the image is read.  COST: a lane per column, a wave per
+// sixteen rows, top down, so N and NW of a pixel are the lane's P and W of the row before; the nine planes' costs by
+// color_plan.h's own functions.  SUM: over the wave by shuffles, over the four waves in LDS, then nine 64-bit atomic adds.
+__global__ void __launch_bounds__(kIndexThreads) k_color_cost(const ColorCostTask *__restrict__ tasks, int n) {
+    __shared__ uint32_t lds[3 * kColorLdsRows * kColorLdsPitch / 4];
+    __shared__ uint32_t part[kIndexThreads / 64][kColorCosts];
+    const ColorCostTask *tp = tasks + index_task_of(tasks, n, blockIdx.x);
+    const uint32_t rows = tp->rows, cols = tp->cols;
+    CollectTask C{};                                                 // what the loader reads of a task: the format, the quantisation, the width
+    C.format = tp->format; C.scale = tp->scale; C.bias = tp->bias; C.rows = rows; C.cols = cols;
+    const uint32_t across = (cols + kColorTile - 1) / kColorTile, tile = blockIdx.x - tp->first_chunk;
+    const uint32_t y0 = (tile / across) * kColorTile, x0 = (tile % across) * kColorTile;
+    uint8_t *bytes = reinterpret_cast<uint8_t *>(lds);
+    // LDS row r of a channel holds image row y0 + r - 1
+    for (uint32_t j = threadIdx.x; j < 3 * kColorLdsRows * kColorRowUnits; j += kIndexThreads) {
+        const uint32_t ch = j / (kColorLdsRows * kColorRowUnits), r = (j / kColorRowUnits) % kColorLdsRows, q = j % kColorRowUnits;
+        const uint32_t y = y0 + r - 1u, x = x0 + q * kCollectUnitPixels;
+        if ((r == 0 && y0 == 0) || y >= rows || x >= cols) continue;
+        uint32_t word[4];
+        collect_unit_load(C, gp(tp->src[ch]), tp->pitch[ch], tp->step[ch], y, x, 0u, cols - x < 16u ? cols - x : 16u, word);
+        uint32_t *d = lds + ((ch * kColorLdsRows + r) * kColorLdsPitch + 4u + q * kCollectUnitPixels) / 4u;
+#pragma unroll
+        for (int i = 0; i < 4; i++) d[i] = word[i];
+    }
+    if (x0 > 0 && threadIdx.x < 3 * kColorLdsRows) {
+        const uint32_t ch = threadIdx.x / kColorLdsRows, r = threadIdx.x % kColorLdsRows, y = y0 + r - 1u;
+        if (!(r == 0 && y0 == 0) && y < rows) {
+            uint32_t word[4];
+            collect_unit_load(C, gp(tp->src[ch]), tp->pitch[ch], tp->step[ch], y, x0 - 1u, 0u, 1u, word);
+            bytes[(ch * kColorLdsRows + r) * kColorLdsPitch + 3u] = uint8_t(word[0]);
+        }
+    }
+    __syncthreads();
+    const uint32_t wave = threadIdx.x / 64u, lane = threadIdx.x % 64u, x = x0 + lane;
+    uint32_t sums[kColorCosts] = {};
+    if (x < cols) {
+        const uint32_t r0 = wave * 16u;                              // the wave's first tile row; LDS row r0 is the one above it
+        uint32_t nn[3], nw[3];
+#pragma unroll
+        for (uint32_t ch = 0; ch < 3; ch++) {
+            const uint8_t *row = bytes + (ch * kColorLdsRows + r0) * kColorLdsPitch + 3u + lane;
+            nw[ch] = row[0]; nn[ch] = row[1];                        // (row 0 or column 0 of the image: never looked at)
+        }
+        for (uint32_t r = r0; r < r0 + 16u && y0 + r < rows; r++) {
+            uint32_t p[3], w[3];
+#pragma unroll
+            for (uint32_t ch = 0; ch < 3; ch++) {
+                const uint8_t *row = bytes + (ch * kColorLdsRows + r + 1u) * kColorLdsPitch + 3u + lane;
+                w[ch] = row[0]; p[ch] = row[1];
+            }
+            color_pixel_costs(p, w, nn, nw, y0 + r, x, sums);
+#pragma unroll
+            for (uint32_t ch = 0; ch < 3; ch++) { nn[ch] = p[ch]; nw[ch] = w[ch]; }
+        }
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kColorCosts; k++) {
+        uint32_t v = sums[k];                                        // (at most 16 x 17 a lane)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0) part[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < kColorCosts) {
+        unsigned long long total = 0;
+        for (uint32_t wv = 0; wv < kIndexThreads / 64; wv++) total += part[wv][threadIdx.x];
+        atomicAdd(tp->costs + threadIdx.x, total);
+    }
+}
+
+bool color_cost_launch(const ColorCostTask *d_tasks, int n, uint32_t tiles, hipStream_t s) {
+    if (n <= 0 || tiles == 0) return true;
+    hipLaunchKernelGGL(k_color_cost, dim3(tiles), dim3(kIndexThreads), 0, s, d_tasks, n);
+    return hipGetLastError() == hipSuccess;
+}
+
 
 // ---- a packed index, expanded on the device (serial_engine.h IndexUnpackTask; the format: index_pack.h) --------------------
 constexpr uint32_t kUnpackWaves = kIndexThreads / 64;

@@ -1,0 +1,168 @@
+// Stand-alone check of csrc/color_plan.h (host only): the tile walk of the cost kernel over the test shapes in all four
+// formats and three layouts, the mode helpers and the choice rule.  Every source is a heap block of EXACTLY its extent -- a
+// read outside it is an overrun the sanitizer reports -- with NaN (0xFF) wherever no element lies, and the nine sums are
+// compared with a plain restatement that knows nothing of tiles: it makes the three planes with a pixel function that
+// rounds through doubles, then the nine planes, then walks each with its own MED and its own bit length.
+// Build and run:
+//   g++ -std=c++17 -O2 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -o color_plan_check tools/color_plan_check.cpp && ./color_plan_check
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <random>
+#include <vector>
+
+#include "../nblic-image-compression_amd/csrc/color_plan.h"
+
+using namespace nblic;
+
+#define CHECK(x) do { if (!(x)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); return 1; } } while (0)
+
+static double half_value(uint32_t h) {
+    const double sign = (h & 0x8000u) ? -1.0 : 1.0;
+    const int e = int((h >> 10) & 0x1Fu), m = int(h & 0x3FFu);
+    if (e == 0x1F) return m ? NAN : sign * INFINITY;
+    return sign * (e ? std::ldexp(1024.0 + m, e - 25) : std::ldexp(double(m), -24));
+}
+static uint8_t pixel_ref(uint32_t x, uint32_t format, float scale, float bias) {
+    if (format == kCollectU8) return uint8_t(x);
+    float f;
+    if (format == kCollectF16) f = float(half_value(x));
+    else { const uint32_t b = format == kCollectBF16 ? x << 16 : x; memcpy(&f, &b, 4); }
+    const float prod = float(double(f) * double(scale));
+    const float v = float(double(prod) + double(bias));
+    if (v != v) return 0;
+    const double r = std::nearbyint(double(v));
+    return uint8_t(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
+}
+static uint32_t element_bits(std::mt19937 &rng, uint32_t format) {
+    if (format == kCollectU8) return rng() & 0xFFu;
+    const uint32_t kind = rng() % 8;
+    float f = kind == 0 ? float(rng() % 512) * 0.5f - 0.5f : (kind == 1 ? float(int(rng() % 2000) - 1000) : float(rng() % 65536) / 65536.0f);
+    uint32_t bits;
+    memcpy(&bits, &f, 4);
+    if (kind == 4) bits = 0x7FC00000u | (rng() & 0x80000000u);
+    if (kind == 5) bits = rng();
+    if (format == kCollectF32) return bits;
+    if (format == kCollectBF16) return bits >> 16;
+    return rng() & 0xFFFFu;
+}
+
+// The cost of one plane, restated.
+static unsigned long long plane_cost(const std::vector<int> &p, int rows, int cols) {
+    unsigned long long sum = 0;
+    for (int y = 0; y < rows; y++)
+        for (int x = 0; x < cols; x++) {
+            int pred;
+            if (y == 0 && x == 0) pred = 128;
+            else if (y == 0) pred = p[size_t(x) - 1];
+            else if (x == 0) pred = p[size_t(y - 1) * cols];
+            else {
+                const int w = p[size_t(y) * cols + x - 1], n = p[size_t(y - 1) * cols + x], nw = p[size_t(y - 1) * cols + x - 1];
+                pred = nw >= std::max(w, n) ? std::min(w, n) : (nw <= std::min(w, n) ? std::max(w, n) : w + n - nw);
+            }
+            int e = p[size_t(y) * cols + x] - pred;
+            while (e < -128) e += 256;
+            while (e > 127) e -= 256;
+            int a = std::abs(e), len = 0;
+            while ((1 << len) <= a) len++;
+            sum += 2ull * len + 1;
+        }
+    return sum;
+}
+
+static int one_frame(std::mt19937 &rng, uint32_t format, uint32_t rows, uint32_t cols, int layout, float scale, float bias) {
+    const uint32_t elem = collect_elem(format);
+    ColorCostTask T{};
+    unsigned long long caps[3];
+    uint8_t *blocks[3];
+    std::vector<int> planes[3];
+    for (uint32_t ch = 0; ch < 3; ch++) {
+        const size_t step = (layout == 1 ? 3 : 1) * size_t(elem), residue = size_t(rng() % (16 / elem)) * elem;
+        const size_t pitch = layout == 1 ? size_t(cols) * 3 * elem : (size_t(cols) + (layout == 2 ? 1 + rng() % 3 : 0)) * elem;
+        const size_t extent = size_t(collect_extent(rows, cols, format, pitch, step));
+        void *mem = nullptr;
+        CHECK(posix_memalign(&mem, 16, residue + extent) == 0);
+        blocks[ch] = static_cast<uint8_t *>(mem);
+        memset(mem, 0xFF, residue + extent);
+        planes[ch].resize(size_t(rows) * cols);
+        for (uint32_t r = 0; r < rows; r++)
+            for (uint32_t c = 0; c < cols; c++) {
+                const uint32_t x = element_bits(rng, format);
+                memcpy(blocks[ch] + residue + size_t(r) * pitch + size_t(c) * step, &x, elem);
+                planes[ch][size_t(r) * cols + c] = pixel_ref(x, format, scale, bias);
+            }
+        T.src[ch] = blocks[ch] + residue; T.pitch[ch] = pitch; T.step[ch] = uint32_t(step); caps[ch] = extent;
+    }
+    T.rows = rows; T.cols = cols; T.format = format; T.scale = scale; T.bias = bias;
+    unsigned long long got[kColorCosts] = {};
+    T.costs = got;
+    CHECK(color_task_ok(T, caps));
+    for (uint32_t ch = 0; ch < 3; ch++) { caps[ch]--; CHECK(!color_task_ok(T, caps)); caps[ch]++; }
+    uint32_t covered = 0;                                            // the tiles cover the frame once
+    for (uint32_t k = 0; k < color_task_tiles(T); k++) {
+        const ColorTile t = color_tile_of(T, k);
+        CHECK(t.y0 % kColorTile == 0 && t.x0 % kColorTile == 0 && t.y0 < rows && t.x0 < cols);
+        covered += std::min(kColorTile, rows - t.y0) * std::min(kColorTile, cols - t.x0);
+    }
+    CHECK(covered == rows * cols);
+    color_cost_host(T);
+    const int pairs[6][2] = {{0, 1}, {0, 2}, {1, 0}, {1, 2}, {2, 0}, {2, 1}};
+    for (uint32_t k = 0; k < kColorCosts; k++) {
+        std::vector<int> p(size_t(rows) * cols);
+        for (size_t i = 0; i < p.size(); i++) p[i] = k < 3 ? planes[k][i] : ((planes[pairs[k - 3][0]][i] - planes[pairs[k - 3][1]][i] + 128) % 256 + 256) % 256;
+        CHECK(got[k] == plane_cost(p, int(rows), int(cols)));
+        if (k >= 3) CHECK(color_plane_own(k) == pairs[k - 3][0] && color_plane_ref(k) == pairs[k - 3][1] && color_diff_plane(uint32_t(pairs[k - 3][0]), uint32_t(pairs[k - 3][1])) == k);
+    }
+    for (auto b : blocks) free(b);
+    return 0;
+}
+
+static int modes_and_rule() {
+    int valid = 0;
+    for (uint32_t m = 0; m < 256; m++) {
+        const bool want = m == 0 || (m < 16 && (m & 3) != 3 && (m & 12) != 0);
+        CHECK(color_mode_valid(m) == want);
+        valid += want;
+        if (!want) continue;
+        const uint32_t b = m & 3, others[2] = {b == 0 ? 1u : 0u, b == 2 ? 1u : 2u};
+        CHECK(color_mode_ref(m, b) == -1);
+        CHECK(color_mode_ref(m, others[0]) == ((m & 4) ? int(b) : -1) && color_mode_ref(m, others[1]) == ((m & 8) ? int(b) : -1));
+    }
+    CHECK(valid == 10 && color_mode_valid(kColorRct) && !color_mode_valid(kColorRefused));
+    // the rule: each of the ten modes from a table that favours it, the tie order, the margin's boundary
+    for (uint32_t m = 0; m < 16; m++) {
+        if (!color_mode_valid(m)) continue;
+        unsigned long long t[kColorCosts] = {1000, 1000, 1000, 2000, 2000, 2000, 2000, 2000, 2000};
+        for (uint32_t c = 0; c < 3; c++) if (color_mode_ref(m, c) >= 0) t[color_diff_plane(c, m & 3)] = 100;
+        CHECK(color_choose(t) == m);
+    }
+    unsigned long long tie[kColorCosts] = {1000, 1000, 1000, 100, 100, 100, 100, 100, 100};
+    CHECK(color_choose(tie) == 0x0D);
+    tie[3] = tie[8] = 2000;                                          // nothing against G: R and B tie, R wins
+    CHECK(color_choose(tie) == 0x0C);
+    tie[5] = tie[7] = 2000;                                          // nothing against R either
+    CHECK(color_choose(tie) == 0x0E);
+    unsigned long long edge[kColorCosts] = {64000, 64000, 64000, 63000, 128000, 128000, 128000, 128000, 128000};
+    CHECK(color_choose(edge) == 0);
+    edge[3] = 62999;
+    CHECK(color_choose(edge) == 0x05);
+    return 0;
+}
+
+int main() {
+    if (modes_and_rule()) return 1;
+    std::mt19937 rng(26);
+    const float norms[][2] = {{1.0f, 0.0f}, {255.0f, 0.0f}, {127.5f, 127.5f}};
+    const uint32_t shapes[][2] = {{1, 1}, {1, 17}, {17, 1}, {3, 5}, {64, 64}, {65, 65}, {129, 129}, {2, 200}, {130, 3}};
+    long frames = 0;
+    for (uint32_t format = 0; format < kCollectFormats; format++)
+        for (auto &hw : shapes)
+            for (int layout = 0; layout < 3; layout++) {
+                const float *nb = format == kCollectU8 ? norms[0] : norms[rng() % 3];
+                if (one_frame(rng, format, hw[0], hw[1], layout, nb[0], nb[1])) return 1;
+                frames++;
+            }
+    printf("color_plan_check: %ld frames of nine sums, the ten modes and the rule, all as expected\n", frames);
+    return 0;
+}
