@@ -1130,6 +1130,109 @@ int nblic_amd_debug_color_cost(nblic_amd_ctx *ctx, int n, const void *const *src
                                const size_t *pitches, const size_t *steps, const int *rows, const int *cols, const int *formats,
                                const float *scales, const float *biases, unsigned long long *costs);
 
+/* SLICE STACKS: the images of a call as stacks of `depth` slices -- the slices of a CT or microscopy volume, the frames of a
+ * static camera, a burst -- a slice coded as it is or against the slice before it (csrc/stack.h).
+ *   depth         D >= 1, n_images % D == 0; image s * D + d is slice d of stack s (n-major, as a [N, D, H, W] tensor is read).
+ *                 The slices of a stack have one size.
+ *   slice_modes   one byte per image.  0 (NBLIC_AMD_SLICE_KEY): coded as it is.  1 (NBLIC_AMD_SLICE_DELTA): coded as
+ *                 (x_d - x_{d-1} + 128) mod 256, both the pixels k_collect would write.  Slice 0 of every stack must be 0.
+ *                 Every other byte is invalid; 0xFF is what nblic_amd_stack_plan gives the slices of a stack it refuses.
+ * A RUN is a key slice and the delta slices that follow it; restoring is x_d = (t_d + x_{d-1} - 128) mod 256 along the run.
+ * The streams are ordinary .nblic / QNBLIC streams of those planes: nothing in them names the mode, the caller keeps the
+ * bytes, and a decoder without them yields the difference planes.  LOSSLESS ONLY inside a run: near > 0 is
+ * allowed only on a key slice whose successor in the stack (if any) is a key slice too.
+ *
+ * ENCODE: the four _from_stack calls are the four _from encoders with depth and slice_modes.  A delta slice is collected
+ * with the caller's SOURCE of the slice before it as its reference (no new kernel; collected even where it could be used in
+ * place); key slices stay what they were.  A stack with a delta and a refused or unequal-size source is refused as a whole
+ * (every length -1); a stack of keys only is D images like any other.  Every stream and index is byte for byte what the call
+ * without _stack returns for the difference plane.
+ *   -1, nothing launched: an invalid byte, depth < 1, n_images % depth != 0, the near rule above, NBLIC_AMD_FORMAT_RCT in format.
+ *
+ * DECODE: the two _to_ex_stack calls are the two _to_ex decoders with depth and slice_modes.  A run with a delta is delivered
+ * by ONE task of a second kernel, k_deliver_stack, whose lanes carry the running pixels of sixteen window pixels from the
+ * key slice to the run's last one in registers; a key slice without a delta behind it goes through k_deliver as before: at
+ * most one launch of each kernel per call (in nblic_amd_decode_batch_to_ex_stack behind the work of both of its streams).
+ *   same window   the slices of a stack with a delta share ONE window after defaulting (with an index the window's rows
+ *                 choose the segments of every slice; the slices' indexes may differ)
+ *   refused       status -1 for every slice, nothing written, nothing launched, for a stack with a delta and: a member that
+ *                 does not parse, unequal sizes, near > 0 inside a run, unequal windows, or a refused destination
+ *   skipped       a destination with ptr == NULL and cap_bytes == 0: the slice is decoded as a reference only; its window
+ *                 fields still count for the "same window" rule; its status is that of its plane
+ *   failure       slice d is delivered only if every plane of its run from the key through d decoded: otherwise d and every
+ *                 later slice of the run get zeros and status -1; earlier slices, other runs and other stacks are unaffected
+ *   random access hand in the streams key .. target of one run with one destination (the others skipped)
+ *   -1 for the call: an invalid byte, depth < 1, n_images % depth != 0.
+ *
+ * PLAN: nblic_amd_stack_plan measures and chooses.  ONE launch of k_stack_cost computes two COSTS per slice (the cost of
+ * nblic_amd_color_plan: the sum of 2 * bitlen(|e|) + 1 over the MED residuals): INTRA, of the slice itself, and DELTA, of
+ * its difference plane against the slice before (0 for slice 0) -- against that slice's SOURCE whatever its own mode, so
+ * the choices are independent of each other and the exhaustive best of a stack is two encodes, all keys and all deltas.
+ * The host chooses by nblic_amd_stack_choose: 1 iff 64 * delta < 63 * intra (the colour plan's margin; equality gives 0).
+ * The rule is part of the interface.  key_every = K > 0 forces every slice with d % K == 0 to a key (0: only slice 0).
+ *   slice_modes   n_images bytes; 0xFF for all slices of a stack with a source the _from calls refuse or sources of unequal
+ *                 size (nothing is launched for it, its costs are zero, the other stacks are unaffected)
+ *   costs         NULL, or two sums per image (intra, delta)
+ *   -1            nothing launched: the call-level errors of nblic_amd_color_plan (but the count rule), depth < 1,
+ *                 n_images % depth != 0, key_every < 0; or a HIP call failed.
+ * nblic_amd_stack_plan_stats: out[0] launches of k_stack_cost, out[1] source elements read, out[2] launches of
+ * k_deliver_stack, out[3] runs delivered, since the context was made; last_ms (may be NULL), two values: GPU milliseconds
+ * of the last nblic_amd_stack_plan's launch, and of the delivery launches of the last _to_ex_stack call.
+ * The gain on real volumes and sequences is UNMEASURED: none was at hand (README.md says what was measured instead). */
+#define NBLIC_AMD_SLICE_KEY 0
+#define NBLIC_AMD_SLICE_DELTA 1
+int nblic_amd_stack_plan(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias, int depth, int key_every,
+                         unsigned char *slice_modes, unsigned long long *costs);
+int nblic_amd_stack_choose(unsigned long long intra, unsigned long long delta);      /* host only, pure: 1 / 0 */
+int nblic_amd_stack_slice_mode(int d, int key_every, unsigned long long intra, unsigned long long delta);     /* what the plan gives slice d: 1 / 0; -1: d or key_every < 0 */
+int nblic_amd_stack_mode_valid(int mode);                                            /* 1 / 0 */
+int nblic_amd_stack_modes_valid(int n_images, int depth, const unsigned char *slice_modes);     /* the bytes of a call: 1 / 0 */
+int nblic_amd_stack_plan_stats(nblic_amd_ctx *ctx, long out[4], double last_ms[2]);
+int nblic_amd_encode_batch_modes_from_stack(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                            int depth, const unsigned char *slice_modes, const int *nears, const int *efforts, unsigned char *const *outs,
+                                            const size_t *out_caps, long *out_lens, unsigned char *const *recons);
+int nblic_amd_qencode_batch_from_stack(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                       int depth, const unsigned char *slice_modes, uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words);
+int nblic_amd_encode_batch_indexed_from_stack(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                              int depth, const unsigned char *slice_modes, const int *every_rows, int band_rows, unsigned char *const *outs,
+                                              const size_t *out_caps, long *out_lens, unsigned char *const *indexes, const size_t *index_caps, long *index_lens);
+int nblic_amd_qencode_batch_indexed_from_stack(nblic_amd_ctx *ctx, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                               int depth, const unsigned char *slice_modes, const int *every_rows, int band_rows, uint16_t *const *outs,
+                                               const size_t *out_caps_words, long *out_len_words, unsigned char *const *indexes, const size_t *index_caps,
+                                               long *index_lens);
+int nblic_amd_decode_batch_to_ex_stack(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                       const nblic_amd_dest_ex *dests, int format, int depth, const unsigned char *slice_modes, int *heights, int *widths,
+                                       int *nears, int *efforts, int *status);
+int nblic_amd_decode_batch_indexed_to_ex_stack(nblic_amd_ctx *ctx, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                               const void *const *indexes, const size_t *index_lens, const nblic_amd_dest_ex *dests, int format,
+                                               int depth, const unsigned char *slice_modes, int *heights, int *widths, int *nears, int *efforts, int *status);
+/* Debug hooks used by the stacks' tests: the two kernels and their host walks alone (csrc/stack.h).
+ * nblic_amd_debug_stack_deliver_host: ONE run of `count` caller-made planes of plane_rows x width bytes, host only: window is
+ * row0, row1, col0, col1; slice d goes to outs[d] + dst_offsets[d] in out_bytes[d] bytes with pitches[d] and steps[d] (0: the
+ * element size), outs[d] NULL: a skipped slice; zeros[d] != 0: the plane is known to be bad; gate_status[d]: the status of its
+ * gate record (-1: none).  units / chunks (may be NULL): what a launch would count.
+ * nblic_amd_debug_stack_deliver: ONE k_deliver_stack launch over n runs; run k has counts[k] planes, and the per-plane
+ * arrays hold the runs' entries one after the other.  A plane is uploaded at byte base_offsets[] (0 .. 15) of a zeroed region
+ * of its own; a destination lies at byte dst_offsets[] of a buffer of out_bytes[] bytes filled with 0x5A, which comes back
+ * whole in outs[].
+ * nblic_amd_debug_stack_cost_host: ONE stack of `count` sources, host only; costs receives two sums per source, tiles (may be
+ * NULL) the kernel's workgroups.  nblic_amd_debug_stack_cost: ONE k_stack_cost launch over n stacks of counts[k] sources,
+ * each uploaded at byte base_offsets[] (0 .. 255) of a region of its own filled with 0xFF.
+ * -1: refused; -2: a HIP call failed. */
+int nblic_amd_debug_stack_deliver_host(int count, const unsigned char *const *planes, int plane_rows, int width, const int *window, int format,
+                                       const float *scales, const float *biases, const int *zeros, const int *gate_status, unsigned char *const *outs,
+                                       const size_t *out_bytes, const size_t *dst_offsets, const size_t *pitches, const size_t *steps,
+                                       unsigned long long *units, unsigned long long *chunks);
+int nblic_amd_debug_stack_deliver(nblic_amd_ctx *ctx, int n, const int *counts, const unsigned char *const *planes, const size_t *base_offsets,
+                                  const int *plane_rows, const int *widths, const int *windows, const int *formats, const float *scales, const float *biases,
+                                  const int *zeros, const size_t *pitches, const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes,
+                                  unsigned char *const *outs, const int *gate_status);
+int nblic_amd_debug_stack_cost_host(int count, const void *const *srcs, const size_t *cap_bytes, const size_t *pitches, const size_t *steps, int rows, int cols,
+                                    int format, float scale, float bias, unsigned long long *costs, unsigned long long *tiles);
+int nblic_amd_debug_stack_cost(nblic_amd_ctx *ctx, int n, const int *counts, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets,
+                               const size_t *pitches, const size_t *steps, const int *rows, const int *cols, const int *formats,
+                               const float *scales, const float *biases, unsigned long long *costs);
+
 /* Debug hook used by the indexed effort-0 batch's host tests: QNBLIC's entropy stage (histogram normalisation, histogram
  * code, the rANS pass) on caller-made records, reporting the coder in front of entry rows as the batch's workers read it.
  * Host only: no context, no device.  words[height x width] = level | symbol << 8 per pixel, hist[12 x 256] the counts

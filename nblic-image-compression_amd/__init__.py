@@ -62,6 +62,10 @@ EXPORTS = (
     "nblic_amd_encode_batch_modes_from_color", "nblic_amd_qencode_batch_from_color", "nblic_amd_encode_batch_indexed_from_color",
     "nblic_amd_qencode_batch_indexed_from_color", "nblic_amd_decode_batch_to_ex_color", "nblic_amd_decode_batch_indexed_to_ex_color",
     "nblic_amd_debug_color_cost_host", "nblic_amd_debug_color_cost",
+    "nblic_amd_stack_plan", "nblic_amd_stack_choose", "nblic_amd_stack_slice_mode", "nblic_amd_stack_mode_valid", "nblic_amd_stack_modes_valid", "nblic_amd_stack_plan_stats",
+    "nblic_amd_encode_batch_modes_from_stack", "nblic_amd_qencode_batch_from_stack", "nblic_amd_encode_batch_indexed_from_stack",
+    "nblic_amd_qencode_batch_indexed_from_stack", "nblic_amd_decode_batch_to_ex_stack", "nblic_amd_decode_batch_indexed_to_ex_stack",
+    "nblic_amd_debug_stack_deliver_host", "nblic_amd_debug_stack_deliver", "nblic_amd_debug_stack_cost_host", "nblic_amd_debug_stack_cost",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats", "nblic_amd_copy_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -341,6 +345,42 @@ def load_library() -> C.CDLL:
         lib.nblic_amd_debug_color_cost_host.argtypes = [vpp, szp, szp, szp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, ullp, ullp]
         lib.nblic_amd_debug_color_cost.restype = C.c_int
         lib.nblic_amd_debug_color_cost.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, szp, szp, ip, ip, ip, fp, fp, ullp]
+    if hasattr(lib, "nblic_amd_stack_plan"):                        # (an older build loaded through NBLIC_AMD_LIB has none of these)
+        vpp, szp, fp, ullp, lp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(C.c_ulonglong), C.POINTER(C.c_long)
+        xp, ubp = C.POINTER(DestEx), C.POINTER(C.c_ubyte)
+        head = [C.c_void_p, C.c_int, C.POINTER(Src), C.c_int, C.c_float, C.c_float, C.c_int]
+        lib.nblic_amd_stack_plan.restype = C.c_int
+        lib.nblic_amd_stack_plan.argtypes = head + [C.c_int, ubp, ullp]
+        lib.nblic_amd_stack_choose.restype = C.c_int
+        lib.nblic_amd_stack_choose.argtypes = [C.c_ulonglong, C.c_ulonglong]
+        lib.nblic_amd_stack_slice_mode.restype = C.c_int
+        lib.nblic_amd_stack_slice_mode.argtypes = [C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong]
+        lib.nblic_amd_stack_mode_valid.restype = C.c_int
+        lib.nblic_amd_stack_mode_valid.argtypes = [C.c_int]
+        lib.nblic_amd_stack_modes_valid.restype = C.c_int
+        lib.nblic_amd_stack_modes_valid.argtypes = [C.c_int, C.c_int, ubp]
+        lib.nblic_amd_stack_plan_stats.restype = C.c_int
+        lib.nblic_amd_stack_plan_stats.argtypes = [C.c_void_p, lp, C.POINTER(C.c_double)]
+        lib.nblic_amd_encode_batch_modes_from_stack.restype = C.c_int
+        lib.nblic_amd_encode_batch_modes_from_stack.argtypes = head + [ubp, ip, ip, vpp, szp, lp, vpp]
+        lib.nblic_amd_qencode_batch_from_stack.restype = C.c_int
+        lib.nblic_amd_qencode_batch_from_stack.argtypes = head + [ubp, vpp, szp, lp]
+        lib.nblic_amd_encode_batch_indexed_from_stack.restype = C.c_int
+        lib.nblic_amd_encode_batch_indexed_from_stack.argtypes = head + [ubp, ip, C.c_int, vpp, szp, lp, vpp, szp, lp]
+        lib.nblic_amd_qencode_batch_indexed_from_stack.restype = C.c_int
+        lib.nblic_amd_qencode_batch_indexed_from_stack.argtypes = lib.nblic_amd_encode_batch_indexed_from_stack.argtypes
+        lib.nblic_amd_decode_batch_to_ex_stack.restype = C.c_int
+        lib.nblic_amd_decode_batch_to_ex_stack.argtypes = [C.c_void_p, C.c_int, vpp, szp, xp, C.c_int, C.c_int, ubp] + [ip] * 5
+        lib.nblic_amd_decode_batch_indexed_to_ex_stack.restype = C.c_int
+        lib.nblic_amd_decode_batch_indexed_to_ex_stack.argtypes = [C.c_void_p, C.c_int, vpp, szp, vpp, szp, xp, C.c_int, C.c_int, ubp] + [ip] * 5
+        lib.nblic_amd_debug_stack_deliver_host.restype = C.c_int
+        lib.nblic_amd_debug_stack_deliver_host.argtypes = [C.c_int, vpp, C.c_int, C.c_int, ip, C.c_int, fp, fp, ip, ip, vpp, szp, szp, szp, szp, ullp, ullp]
+        lib.nblic_amd_debug_stack_deliver.restype = C.c_int
+        lib.nblic_amd_debug_stack_deliver.argtypes = [C.c_void_p, C.c_int, ip, vpp, szp, ip, ip, ip, ip, fp, fp, ip, szp, szp, szp, szp, vpp, ip]
+        lib.nblic_amd_debug_stack_cost_host.restype = C.c_int
+        lib.nblic_amd_debug_stack_cost_host.argtypes = [C.c_int, vpp, szp, szp, szp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, ullp, ullp]
+        lib.nblic_amd_debug_stack_cost.restype = C.c_int
+        lib.nblic_amd_debug_stack_cost.argtypes = [C.c_void_p, C.c_int, ip, vpp, szp, szp, szp, szp, ip, ip, ip, fp, fp, ullp]
     if hasattr(lib, "nblic_amd_index_build_batch"):
         vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
         lib.nblic_amd_index_build_batch.restype = C.c_int
@@ -585,7 +625,7 @@ def _dests_ex_of(views, dims, rows, cols, scale, bias) -> Tuple[list, int]:
     used duck-typed as :func:`_dests_of` uses them, with any non-negative strides (``layout="any"``).  A tensor whose shape
     is not its image's window gets a null pointer: the library refuses that image alone."""
     n = len(views)
-    fmts = {deliver_format(v.dtype) for v in views}
+    fmts = {deliver_format(v.dtype) for v in views if v is not None}
     if len(fmts) > 1:
         raise ValueError("out: one dtype per call")
     fmt = fmts.pop() if fmts else 0
@@ -593,6 +633,9 @@ def _dests_ex_of(views, dims, rows, cols, scale, bias) -> Tuple[list, int]:
     scales, biases = _per_image_floats(scale, n, "scale"), _per_image_floats(bias, n, "bias")
     dests = []
     for k, v in enumerate(views):
+        if v is None:                                           # a skipped slice of a stack: its window, and no destination
+            dests.append((0, 0, 0, 0) + rows[k] + cols[k] + (scales[k], biases[k]))
+            continue
         elem = int(v.element_size())
         hh, ww = (int(x) for x in v.shape)
         s0, s1 = (int(x) for x in v.stride())
@@ -867,6 +910,182 @@ def _color_arg(color, arg):
 
 def _modes_ptr(modes):
     return np.ascontiguousarray(modes, np.uint8).ctypes.data_as(C.POINTER(C.c_ubyte))
+
+
+STACK_KEY, STACK_DELTA, STACK_REFUSED = 0, 1, 0xFF                              # NBLIC_AMD_SLICE_KEY / _DELTA; what stack_plan gives the slices of a refused stack
+
+
+def stack_mode_valid(mode: int) -> bool:
+    """Is ``mode`` a slice mode byte (``nblic_amd_stack_mode_valid``): 0, a key slice, or 1, a delta slice?"""
+    return bool(load_library().nblic_amd_stack_mode_valid(int(mode)))
+
+
+def stack_choose(intra: int, delta: int) -> int:
+    """The mode the rule chooses for a slice from its two costs (``nblic_amd_stack_choose``): 1 iff
+    ``64 * delta < 63 * intra``."""
+    return int(load_library().nblic_amd_stack_choose(int(intra), int(delta)))
+
+
+def stack_modes_from_costs(costs, depth: int, key_every: int = 0) -> np.ndarray:
+    """The mode bytes ``stack_plan`` makes of a [n, 2] table of costs (intra, delta) of stacks of ``depth`` slices
+    (``nblic_amd_stack_slice_mode``): slice 0, and with ``key_every`` = K > 0 every slice ``d % K == 0``, is a key; every other
+    slice what :func:`stack_choose` says."""
+    costs = np.asarray(costs, np.uint64).reshape(-1, 2)
+    if depth < 1 or len(costs) % depth != 0 or key_every < 0:
+        raise ValueError("stack_modes_from_costs: a depth that divides the number of slices, and key_every >= 0")
+    lib = load_library()
+    return np.array([lib.nblic_amd_stack_slice_mode(k % depth, int(key_every), int(i), int(d)) for k, (i, d) in enumerate(costs)], np.uint8)
+
+
+def _stack_slices(slices, modes, what):
+    slices = [np.asarray(v) for v in slices]
+    modes = [int(m) for m in modes]
+    if not slices or len(modes) != len(slices) or any(v.dtype != np.uint8 or v.shape != slices[0].shape for v in slices):
+        raise ValueError(what + ": uint8 arrays of one shape, and one mode byte for each")
+    if modes[0] != STACK_KEY or not all(stack_mode_valid(m) for m in modes):
+        raise ValueError(what + ": mode bytes are 0 or 1, and slice 0 is a key (0)")
+    return slices, modes
+
+
+def stack_forward(slices, modes) -> List[np.ndarray]:
+    """The planes whose streams ONE stack of uint8 ``slices`` has under the slice ``modes``, on the host: a delta slice is
+    ``(x[d] - x[d - 1] + 128) mod 256``, a key slice a copy.  A decoder that knows nothing of the modes gets these back."""
+    slices, modes = _stack_slices(slices, modes, "stack_forward")
+    off = np.uint8(128)
+    return [x.copy() if m == STACK_KEY else x - slices[d - 1] + off for d, (x, m) in enumerate(zip(slices, modes))]      # (uint8 arithmetic wraps)
+
+
+def stack_inverse(planes, modes) -> List[np.ndarray]:
+    """The inverse of :func:`stack_forward`: along a run, ``x[d] = (t[d] + x[d - 1] - 128) mod 256``."""
+    planes, modes = _stack_slices(planes, modes, "stack_inverse")
+    off = np.uint8(128)
+    out = []
+    for t, m in zip(planes, modes):
+        out.append(t.copy() if m == STACK_KEY else t + out[-1] - off)
+    return out
+
+
+def stack_cost_numpy(slices) -> np.ndarray:
+    """The two costs of every slice of ONE stack of 2-D uint8 arrays, restated in numpy: [D, 2] uint64, column 0 the cost of
+    the slice itself, column 1 that of its difference against the slice before (0 for slice 0) -- what
+    ``Context.stack_plan(..., costs=True)`` reports for the collected planes."""
+    slices = [np.asarray(v) for v in slices]
+    if not slices or any(v.dtype != np.uint8 or v.ndim != 2 or v.size == 0 or v.shape != slices[0].shape for v in slices):
+        raise ValueError("stack_cost_numpy: 2-D uint8 arrays of one shape")
+    off = np.uint8(128)
+    return np.array([[_plane_cost_numpy(x), _plane_cost_numpy(x - slices[d - 1] + off) if d else 0] for d, x in enumerate(slices)], np.uint64)
+
+
+def stack_cost_host(raws, rows: int, cols: int, fmt, pitches=None, steps=None, scale: float = 1.0, bias: float = 0.0, offsets=None,
+                    caps=None, info: Optional[dict] = None) -> np.ndarray:
+    """The cost kernel's tile walk on the host (``nblic_amd_debug_stack_cost_host``; no device) over ONE stack: ``raws`` are
+    the raw bytes of the slices' sources, element (0, 0) of each at byte ``offsets[d]``, rows ``pitches[d]`` and the pixels of
+    a row ``steps[d]`` bytes apart (default: contiguous), ``caps[d]`` bytes readable from there (default: to the buffer's
+    end).  Returns the [D, 2] sums (uint64); ``info`` receives ``tiles``.  ``ValueError`` when refused."""
+    fmt = fmt if isinstance(fmt, int) else collect_format(fmt)
+    elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
+    raws = [np.ascontiguousarray(v).reshape(-1).view(np.uint8) for v in raws]
+    d = len(raws)
+    if d < 1:
+        raise ValueError("stack_cost_host: at least one source")
+    offsets = [0] * d if offsets is None else [int(v) for v in offsets]
+    pitches = [int(cols) * elem] * d if pitches is None else [int(v) for v in pitches]
+    steps = [elem] * d if steps is None else [int(v) for v in steps]
+    caps = [r.size - o for r, o in zip(raws, offsets)] if caps is None else [int(v) for v in caps]
+    if min(pitches + steps + offsets) < 0:
+        raise ValueError("stack_cost_host: a negative pitch, step or offset")
+    out, tiles = np.zeros((d, 2), np.uint64), C.c_ulonglong(0)
+    sz = lambda vals: (C.c_size_t * d)(*[max(int(v), 0) for v in vals])
+    rc = load_library().nblic_amd_debug_stack_cost_host(d, (C.c_void_p * d)(*[r.ctypes.data + o for r, o in zip(raws, offsets)]), sz(caps), sz(pitches), sz(steps),
+                                                        int(rows), int(cols), int(fmt), float(scale), float(bias),
+                                                        out.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(tiles))
+    if rc != 0:
+        raise ValueError("nblic_amd_debug_stack_cost_host refused its arguments")
+    if info is not None:
+        info["tiles"] = int(tiles.value)
+    return out
+
+
+def _stack_run_args(t):
+    """The per-slice lists of one run given as a dict (``Context.debug_stack_deliver`` says what it holds)."""
+    planes = [np.ascontiguousarray(p, np.uint8) for p in t["planes"]]
+    d = len(planes)
+    if d < 1 or any(p.ndim != 2 or p.size == 0 or p.shape != planes[0].shape for p in planes):
+        raise ValueError("a run: 2-D uint8 planes of one shape")
+    fmt = t["fmt"] if isinstance(t["fmt"], int) else deliver_format(t["fmt"])
+    elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
+    r0, r1, c0, c1 = (int(v) for v in t["window"])
+    per = lambda key, default: list(t[key]) if hasattr(t.get(key, default), "__len__") else [t.get(key, default)] * d
+    steps = [int(v) for v in per("steps", elem)]
+    pitches = [int(v) for v in t["pitches"]] if "pitches" in t else [(c1 - c0) * s for s in steps]
+    offsets = [int(v) for v in per("offsets", 0)]
+    skip = [bool(v) for v in per("skip", False)]
+    sizes = [int(v) for v in t["out_bytes"]] if "out_bytes" in t else [o + max(r1 - r0 - 1, 0) * p + max(c1 - c0 - 1, 0) * s + elem for o, p, s in zip(offsets, pitches, steps)]
+    lists = dict(planes=planes, steps=steps, pitches=pitches, offsets=offsets, skip=skip, sizes=sizes, scales=[float(v) for v in per("scales", 1.0)],
+                 biases=[float(v) for v in per("biases", 0.0)], zeros=[int(bool(v)) for v in per("zeros", False)], gates=[int(v) for v in per("gate_status", -1)],
+                 bases=[int(v) for v in per("base_offsets", 0)])
+    if any(len(v) != d for v in lists.values()) or min(steps + pitches + offsets + sizes + lists["bases"]) < 0:
+        raise ValueError("a run: one non-negative value per slice")
+    return fmt, (r0, r1, c0, c1), lists
+
+
+def stack_deliver_host(planes, window, fmt, scales=1.0, biases=0.0, pitches=None, steps=None, offsets=0, out_bytes=None, skip=False, zeros=False,
+                       gate_status=-1, fill: int = DELIVER_PATTERN, info: Optional[dict] = None) -> List[Optional[np.ndarray]]:
+    """The run delivery's walk on the host (``nblic_amd_debug_stack_deliver_host``; no device) over ONE run: ``planes`` are the
+    decoded planes -- the key slice's, then the difference planes -- ``window`` is (row0, row1, col0, col1), and every other
+    argument is one value for every slice or one per slice: ``steps`` (bytes between the elements of a destination row;
+    default: the element size), ``pitches`` (default: ``cols * step``), ``offsets`` (of the destination in its buffer),
+    ``out_bytes``, ``skip`` (the slice has no destination), ``zeros`` (its plane is known to be bad), ``gate_status`` (-1: no
+    gate).  Returns every slice's whole buffer, filled with ``fill`` where nothing was written; None for a skipped slice.
+    ``info`` receives ``units`` and ``chunks``.  ``ValueError`` when refused."""
+    t = dict(planes=planes, window=window, fmt=fmt, scales=scales, biases=biases, steps=steps, offsets=offsets, skip=skip, zeros=zeros, gate_status=gate_status)
+    if steps is None:
+        del t["steps"]
+    if pitches is not None:
+        t["pitches"] = pitches
+    if out_bytes is not None:
+        t["out_bytes"] = out_bytes
+    fmt, win, L = _stack_run_args(t)
+    d = len(L["planes"])
+    outs = [None if s else np.full(max(b, 1), fill, np.uint8) for s, b in zip(L["skip"], L["sizes"])]
+    units, chunks = C.c_ulonglong(0), C.c_ulonglong(0)
+    vp = lambda arrs: (C.c_void_p * d)(*[a.ctypes.data if a is not None else None for a in arrs])
+    sz = lambda vals: (C.c_size_t * d)(*vals)
+    iv = lambda vals: (C.c_int * len(vals))(*vals)
+    fv = lambda vals: (C.c_float * d)(*vals)
+    rc = load_library().nblic_amd_debug_stack_deliver_host(d, vp(L["planes"]), L["planes"][0].shape[0], L["planes"][0].shape[1], iv(list(win)), int(fmt), fv(L["scales"]),
+                                                           fv(L["biases"]), iv(L["zeros"]), iv(L["gates"]), vp(outs), sz(L["sizes"]), sz(L["offsets"]), sz(L["pitches"]),
+                                                           sz(L["steps"]), C.byref(units), C.byref(chunks))
+    if rc != 0:
+        raise ValueError("nblic_amd_debug_stack_deliver_host refused its arguments")
+    if info is not None:
+        info["units"], info["chunks"] = int(units.value), int(chunks.value)
+    return [None if o is None else o[:b] for o, b in zip(outs, L["sizes"])]
+
+
+def _stack_arg(stack, depth, arg, n: int):
+    """What ``stack`` and ``depth`` stand for: (depth, mode bytes), or (0, None) without ``stack``.  ``"delta"``: every slice
+    but the first of each stack is a delta; otherwise one mode byte per image.  ``depth`` defaults to dimension 1 of a 4-D
+    tensor ``arg`` -- the sources or the destinations -- and is required for lists."""
+    if stack is None:
+        if depth is not None:
+            raise ValueError("depth goes with stack")
+        return 0, None
+    if depth is None:
+        if isinstance(arg, (list, tuple)) or len(tuple(arg.shape)) != 4:
+            raise ValueError("stack: depth is required unless the tensor is [N, D, H, W]")
+        depth = int(arg.shape[1])
+    depth = int(depth)
+    if depth < 1 or n % depth != 0:
+        raise ValueError("stack: the depth divides the number of images")
+    if isinstance(stack, str):
+        if stack != "delta":
+            raise ValueError('stack: None, "delta", or one mode byte per image')
+        return depth, np.array([STACK_KEY if k % depth == 0 else STACK_DELTA for k in range(n)], np.uint8)
+    modes = np.array([int(v) for v in np.asarray(stack).reshape(-1)], np.int64)
+    if modes.shape != (n,) or modes.min(initial=0) < 0 or modes.max(initial=0) > 255:
+        raise ValueError("stack: one mode byte per image")
+    return depth, modes.astype(np.uint8)
 
 
 def _src_views(src):
@@ -1598,10 +1817,11 @@ class Context:
             info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
         return status
 
-    def decode_batch_indexed_to_ex(self, pairs, dests, fmt: int, info: Optional[dict] = None, modes=None) -> List[int]:
+    def decode_batch_indexed_to_ex(self, pairs, dests, fmt: int, info: Optional[dict] = None, modes=None, stack=None) -> List[int]:
         """``nblic_amd_decode_batch_indexed_to_ex`` as it is: ``dests`` is one ``(ptr, pitch_bytes, step_bytes, cap_bytes,
         row0, row1, col0, col1, scale, bias)`` per image.  Result and ``info`` as ``decode_batch_indexed_to``.  ``modes``:
-        one colour mode byte per frame (``nblic_amd_decode_batch_indexed_to_ex_color``)."""
+        one colour mode byte per frame (``nblic_amd_decode_batch_indexed_to_ex_color``).  ``stack``: (depth, one slice mode
+        byte per image) (``nblic_amd_decode_batch_indexed_to_ex_stack``)."""
         n = len(pairs)
         ss = [_bytes_arg(s if s is not None else b"") for s, _ in pairs]
         xs = [_bytes_arg(x if x is not None else b"") for _, x in pairs]
@@ -1610,7 +1830,10 @@ class Context:
         vp = lambda arrs: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else nothing.ctypes.data for a in arrs])
         sz = lambda arrs: (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
         meta = [np.full(max(n, 1), -1, np.int32) for _ in range(5)]
-        if modes is not None:
+        if stack is not None:
+            rc = self.lib.nblic_amd_decode_batch_indexed_to_ex_stack(self.handle, n, vp(ss), sz(ss), vp(xs), sz(xs), _dest_ex_array(dests), int(fmt), int(stack[0]),
+                                                                     _modes_ptr(stack[1]), *[m.ctypes.data_as(ip) for m in meta])
+        elif modes is not None:
             rc = self.lib.nblic_amd_decode_batch_indexed_to_ex_color(self.handle, n, vp(ss), sz(ss), vp(xs), sz(xs), _dest_ex_array(dests), int(fmt), _modes_ptr(modes),
                                                                      *[m.ctypes.data_as(ip) for m in meta])
         else:
@@ -1621,8 +1844,9 @@ class Context:
             info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
         return status
 
-    def decode_batch_to_ex(self, streams, dests, fmt: int, info: Optional[dict] = None, modes=None) -> List[int]:
-        """``nblic_amd_decode_batch_to_ex`` as it is (``modes``: ``nblic_amd_decode_batch_to_ex_color``); arguments and result
+    def decode_batch_to_ex(self, streams, dests, fmt: int, info: Optional[dict] = None, modes=None, stack=None) -> List[int]:
+        """``nblic_amd_decode_batch_to_ex`` as it is (``modes``: ``nblic_amd_decode_batch_to_ex_color``; ``stack``, a depth
+        and one slice mode byte per image: ``nblic_amd_decode_batch_to_ex_stack``); arguments and result
         as ``decode_batch_indexed_to_ex``."""
         n = len(streams)
         ss = [_bytes_arg(s if s is not None else b"") for s in streams]
@@ -1631,7 +1855,10 @@ class Context:
         sp = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else nothing.ctypes.data for a in ss])
         sl = (C.c_size_t * max(n, 1))(*[a.size for a in ss])
         meta = [np.full(max(n, 1), -1, np.int32) for _ in range(5)]
-        if modes is not None:
+        if stack is not None:
+            rc = self.lib.nblic_amd_decode_batch_to_ex_stack(self.handle, n, sp, sl, _dest_ex_array(dests), int(fmt), int(stack[0]), _modes_ptr(stack[1]),
+                                                             *[m.ctypes.data_as(ip) for m in meta])
+        elif modes is not None:
             rc = self.lib.nblic_amd_decode_batch_to_ex_color(self.handle, n, sp, sl, _dest_ex_array(dests), int(fmt), _modes_ptr(modes), *[m.ctypes.data_as(ip) for m in meta])
         else:
             rc = self.lib.nblic_amd_decode_batch_to_ex(self.handle, n, sp, sl, _dest_ex_array(dests), int(fmt), *[m.ctypes.data_as(ip) for m in meta])
@@ -1662,8 +1889,15 @@ class Context:
         scales, biases = _per_image_floats(scale, n, "scale"), _per_image_floats(bias, n, "bias")
         return ("ex", [(d[0], d[1], DELIVER_ELEM[fmt]) + tuple(d[2:]) + (scales[k], biases[k]) for k, d in enumerate(dests)], fmt)
 
+    def _stack_dests(self, out, n, dims, rows, cols, scale, bias):
+        """What the two _into calls make of ``out`` with ``stack``: (dests, fmt), any layout, ``None`` in a list a skipped slice."""
+        views = list(out) if isinstance(out, (list, tuple)) else _src_views(out)
+        if len(views) != n or any(v is not None and len(tuple(v.shape)) != 2 for v in views):
+            raise ValueError("out: one 2-D tensor (or None) per image")
+        return _dests_ex_of(views, dims, rows, cols, scale, bias)
+
     def decode_batch_indexed_into(self, pairs, out, rows=None, cols=None, scale=1.0, bias=0.0, info: Optional[dict] = None, layout: str = "rows",
-                                  color=None) -> List[int]:
+                                  color=None, stack=None, depth=None) -> List[int]:
         """A window of every image of ``decode_batch_indexed`` straight into device tensors: no pixel crosses the bus.
         ``out`` is one tensor [N, H', W'] or [N, 1, H', W'] on this context's device, or a list of 2-D tensors -- views
         with any batch and row stride, last stride 1; the dtype chooses the format: uint8 (a copy), float16, bfloat16 or
@@ -1688,14 +1922,28 @@ class Context:
         ``color=modes``, a sequence or array of one colour mode byte per frame (``COLOR_MODES``; what ``color_plan`` chose
         and ``encode_batch_from`` was given): each frame's differences are undone against its base plane; ``"rct"`` is
         every mode ``COLOR_RCT``.  A frame of mode 0 is three independent images.  An invalid byte refuses the whole call:
-        every status is -1 and nothing is written."""
+        every status is -1 and nothing is written.
+
+        ``stack="delta"`` or ``stack=modes`` (one slice mode byte per image; what ``stack_plan`` chose and
+        ``encode_batch_from`` was given) with ``depth`` (default: dimension 1 of a 4-D ``out``; required for a list): image
+        ``s * depth + d`` is slice d of stack s, and a run -- a key slice and the delta slices behind it -- is put together
+        again on the way out.  ``out`` is taken as with ``layout="any"``; a ``None`` in a list is a SKIPPED slice, decoded as a
+        reference only: for one slice of a volume hand in the streams of its run from the key to the target with one
+        destination.  The slices of a stack with a delta have one size and one window; such a stack is refused as a whole.
+        A plane that fails leaves zeros and -1 in its slice and the later ones of its run.  Not with ``color``
+        (``ValueError``); an invalid byte refuses the whole call."""
         n = len(pairs)
         flag, modes = _color_arg(color, out)
+        sdepth, smodes = _stack_arg(stack, depth, out, n)
+        if smodes is not None and color is not None:
+            raise ValueError("stack does not go with color")
         dims = []
         for _, x in pairs:                                      # the head of an index names the geometry; the library checks all of it
             x = _bytes_arg(x if x is not None else b"")
             h, w = (int(v) for v in np.frombuffer(x[16:24].tobytes(), "<i4")) if x.size >= INDEX_HEAD_BYTES else (0, 0)
             dims.append((h, w) if 0 < h <= 65535 and 0 < w <= 65535 else (0, 0))
+        if smodes is not None:
+            return self.decode_batch_indexed_to_ex(pairs, *self._stack_dests(out, n, dims, rows, cols, scale, bias), info, stack=(sdepth, smodes))
         how = self._dests_for(out, n, dims, rows, cols, scale, bias, layout, ex=color is not None)
         return self.decode_batch_indexed_to(pairs, *how[1:], info) if how[0] == "plain" else self.decode_batch_indexed_to_ex(pairs, how[1], how[2] | flag, info, modes)
 
@@ -1715,13 +1963,19 @@ class Context:
         return status
 
     def decode_batch_into(self, streams, out, rows=None, cols=None, scale=1.0, bias=0.0, info: Optional[dict] = None, layout: str = "rows",
-                          color=None) -> List[int]:
+                          color=None, stack=None, depth=None) -> List[int]:
         """``decode_batch`` with a window of every plane delivered into device tensors (no index: every stream is decoded
         whole, from its start).  ``out``, ``layout``, ``rows``, ``cols``, ``scale``, ``bias``, the result and ``info`` as
         ``decode_batch_indexed_into``; a stream that fails on the device leaves zeros.  ``color="rct"`` or ``color=modes`` as
-        there: the three planes of a frame may be of different codecs and efforts."""
+        there: the three planes of a frame may be of different codecs and efforts.  ``stack`` and ``depth`` as there: the
+        slices of a run may be of different codecs and efforts too."""
         flag, modes = _color_arg(color, out)
+        sdepth, smodes = _stack_arg(stack, depth, out, len(streams))
+        if smodes is not None and color is not None:
+            raise ValueError("stack does not go with color")
         dims = [_stream_dims(_bytes_arg(s if s is not None else b"")) or (0, 0) for s in streams]
+        if smodes is not None:
+            return self.decode_batch_to_ex(streams, *self._stack_dests(out, len(streams), dims, rows, cols, scale, bias), info, stack=(sdepth, smodes))
         how = self._dests_for(out, len(streams), dims, rows, cols, scale, bias, layout, ex=color is not None)
         return self.decode_batch_to(streams, *how[1:], info) if how[0] == "plain" else self.decode_batch_to_ex(streams, how[1], how[2] | flag, info, modes)
 
@@ -1809,6 +2063,114 @@ class Context:
             raise ValueError("nblic_amd_color_plan refused the call")
         return (modes[:n // 3], table[:n // 3]) if costs else modes[:n // 3]
 
+    def stack_plan(self, src, depth=None, key_every: int = 0, scale: float = 1.0, bias: float = 0.0, costs: bool = False, rows=None, cols=None):
+        """Choose a slice mode per image from costs measured on the device (``nblic_amd_stack_plan``).  ``src`` as
+        ``encode_batch_from(..., stack=...)`` takes it -- a tensor [N, D, H, W] or a list of ``depth`` views per stack, any
+        layout, one of the four dtypes -- with the same ``scale``, ``bias``, ``rows`` and ``cols``, so the costs are those of
+        the planes the encoder would collect.  Returns a uint8 array of one mode per image for ``stack=`` of the encoder and
+        the decoders: 1 where the difference against the slice before clearly wins (``stack_choose``), 0 otherwise and for
+        slice 0; ``key_every=K`` > 0 forces a key at every slice ``d % K == 0`` (random access in runs of at most K).
+        ``STACK_REFUSED`` (0xFF) marks the slices of a stack with a source the library refuses or sources of unequal size.
+        ``costs=True``: also the [n, 2] uint64 table (intra, delta; zeros for a refused stack).  ``ValueError`` when the
+        library refuses the whole call."""
+        srcs, fmt = _srcs_of(_src_views(src), rows, cols)
+        n = len(srcs)
+        if depth is None:
+            if isinstance(src, (list, tuple)) or len(tuple(src.shape)) != 4:
+                raise ValueError("stack_plan: depth is required unless the tensor is [N, D, H, W]")
+            depth = int(src.shape[1])
+        arr = (Src * max(n, 1))()
+        for k, s in enumerate(srcs):
+            arr[k] = Src(*[int(x) if i else (int(x) or None) for i, x in enumerate(s)])
+        modes, table = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 2), np.uint64)
+        rc = self.lib.nblic_amd_stack_plan(self.handle, n, arr, int(fmt), float(scale), float(bias), int(depth), int(key_every), _modes_ptr(modes),
+                                           table.ctypes.data_as(C.POINTER(C.c_ulonglong)) if costs else None)
+        if rc != 0:
+            raise ValueError("nblic_amd_stack_plan refused the call")
+        return (modes[:n], table[:n]) if costs else modes[:n]
+
+    def stack_plan_stats(self) -> dict:
+        """Since the context was created (``nblic_amd_stack_plan_stats``): ``cost_launches`` of k_stack_cost, ``elements``
+        read by them, ``deliver_launches`` of k_deliver_stack and ``runs`` delivered; ``plan_ms``: the GPU milliseconds of the
+        last :meth:`stack_plan`'s launch; ``deliver_ms``: those of the delivery launches of the last decode with ``stack``."""
+        v, ms = (C.c_long * 4)(), (C.c_double * 2)()
+        if self.lib.nblic_amd_stack_plan_stats(self.handle, v, ms) != 0:
+            raise RuntimeError("nblic_amd_stack_plan_stats failed")
+        return dict(cost_launches=int(v[0]), elements=int(v[1]), deliver_launches=int(v[2]), runs=int(v[3]), plan_ms=float(ms[0]), deliver_ms=float(ms[1]))
+
+    def debug_stack_cost(self, tasks) -> List[np.ndarray]:
+        """``nblic_amd_debug_stack_cost``: ONE k_stack_cost launch over ``tasks``, each a dict with ``raws`` (the bytes of the
+        slices' sources), ``rows``, ``cols``, ``fmt`` and optionally ``pitches``, ``steps`` (one per slice, bytes; default:
+        contiguous), ``scale``, ``bias`` and ``base_offsets`` (one per slice, 0 .. 255: where the device copies start).
+        Returns one [D, 2] uint64 array of sums per task."""
+        n = len(tasks)
+        counts, raws, pitches, steps, bases, hs, ws, fmts, scales, biases = ([] for _ in range(10))
+        for t in tasks:
+            fmt = t["fmt"] if isinstance(t["fmt"], int) else collect_format(t["fmt"])
+            elem = DELIVER_ELEM[fmt] if 0 <= fmt < 4 else 1
+            own = [np.ascontiguousarray(v).reshape(-1).view(np.uint8) for v in t["raws"]]
+            d = len(own)
+            if d < 1:
+                raise ValueError("debug_stack_cost: at least one source per task")
+            counts.append(d); raws += own
+            pitches += [int(v) for v in t.get("pitches", [int(t["cols"]) * elem] * d)]; steps += [int(v) for v in t.get("steps", [elem] * d)]
+            bases += [int(v) for v in t.get("base_offsets", [0] * d)]
+            hs.append(int(t["rows"])); ws.append(int(t["cols"])); fmts.append(fmt)
+            scales.append(float(t.get("scale", 1.0))); biases.append(float(t.get("bias", 0.0)))
+        total = len(raws)
+        if n < 1 or len(pitches) != total or len(steps) != total or len(bases) != total or min(pitches + steps + bases) < 0:
+            raise ValueError("debug_stack_cost: one non-negative pitch, step and offset per source")
+        out = np.zeros((total, 2), np.uint64)
+        sz = lambda vals: (C.c_size_t * total)(*[int(v) for v in vals])
+        iv = lambda vals: (C.c_int * n)(*[int(v) for v in vals])
+        fv = lambda vals: (C.c_float * n)(*vals)
+        rc = self.lib.nblic_amd_debug_stack_cost(self.handle, n, iv(counts), (C.c_void_p * total)(*[a.ctypes.data for a in raws]), sz(r.size for r in raws), sz(bases),
+                                                 sz(pitches), sz(steps), iv(hs), iv(ws), iv(fmts), fv(scales), fv(biases), out.ctypes.data_as(C.POINTER(C.c_ulonglong)))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_stack_cost refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_stack_cost failed (%d)" % rc)
+        ends = np.cumsum(counts)
+        return [out[e - c:e] for c, e in zip(counts, ends)]
+
+    def debug_stack_deliver(self, tasks) -> List[List[Optional[np.ndarray]]]:
+        """``nblic_amd_debug_stack_deliver``: ONE k_deliver_stack launch over ``tasks``, each ONE run as a dict with ``planes``
+        (2-D uint8, one shape: the key slice's plane, then the difference planes), ``window`` (row0, row1, col0, col1) and
+        ``fmt``, and optionally, one value for every slice or one per slice, ``scales``, ``biases``, ``steps`` (default: the
+        element size), ``offsets`` (of the destination in its 0x5A-filled buffer), ``skip`` (no destination), ``zeros`` (the
+        plane is known to be bad), ``gate_status`` (-1: no gate), ``base_offsets`` (0 .. 15, of the plane in its device
+        buffer), and one per slice ``pitches`` (default: ``cols * step``) and ``out_bytes``.  Returns, per task, every slice's
+        whole buffer (uint8), None for a skipped slice.  ``ValueError`` when refused."""
+        n = len(tasks)
+        counts, hs, ws, wins, fmts = [], [], [], [], []
+        keys = ("planes", "steps", "pitches", "offsets", "skip", "sizes", "scales", "biases", "zeros", "gates", "bases")
+        flat = {k: [] for k in keys}
+        for t in tasks:
+            fmt, win, L = _stack_run_args(t)
+            counts.append(len(L["planes"])); hs.append(L["planes"][0].shape[0]); ws.append(L["planes"][0].shape[1]); wins += list(win); fmts.append(fmt)
+            for k in keys:
+                flat[k] += L[k]
+        total = len(flat["planes"])
+        if n < 1:
+            raise ValueError("debug_stack_deliver: at least one task")
+        outs = [None if s else np.zeros(max(b, 1), np.uint8) for s, b in zip(flat["skip"], flat["sizes"])]
+        vp = lambda arrs: (C.c_void_p * total)(*[a.ctypes.data if a is not None else None for a in arrs])
+        sz = lambda vals: (C.c_size_t * total)(*[int(v) for v in vals])
+        iv = lambda vals: (C.c_int * len(vals))(*[int(v) for v in vals])
+        fv = lambda vals: (C.c_float * total)(*vals)
+        rc = self.lib.nblic_amd_debug_stack_deliver(self.handle, n, iv(counts), vp(flat["planes"]), sz(flat["bases"]), iv(hs), iv(ws), iv(wins), iv(fmts),
+                                                    fv(flat["scales"]), fv(flat["biases"]), iv(flat["zeros"]), sz(flat["pitches"]), sz(flat["steps"]),
+                                                    sz(flat["offsets"]), sz(flat["sizes"]), vp(outs), iv(flat["gates"]))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_stack_deliver refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_stack_deliver failed (%d)" % rc)
+        res, at = [], 0
+        for c in counts:
+            res.append([None if o is None else o[:b] for o, b in zip(outs[at:at + c], flat["sizes"][at:at + c])])
+            at += c
+        return res
+
     def color_plan_stats(self) -> Tuple[int, int, float]:
         """k_color_cost launches and source elements read since the context was created, and the GPU milliseconds of the
         last :meth:`color_plan`'s launch (``nblic_amd_color_plan_stats``)."""
@@ -1852,7 +2214,7 @@ class Context:
         return out[:n]
 
     def encode_from_srcs(self, srcs, fmt: int, scale: float = 1.0, bias: float = 0.0, near=0, effort=1, every_rows=None, band_rows: int = 0,
-                         info: Optional[dict] = None, recon_dests=None, recon_fmt: int = 0, modes=None):
+                         info: Optional[dict] = None, recon_dests=None, recon_fmt: int = 0, modes=None, stack=None):
         """The four _from calls on ``srcs``, one ``(ptr, pitch_bytes, step_bytes, cap_bytes, rows, cols)`` per image (device
         memory), in format ``fmt`` (0 .. 3).  ``effort`` 0 (for every image) takes the QNBLIC calls, ``every_rows`` the
         indexed ones.  Returns the streams -- ``None`` for a refused or failed image -- or (stream, index) pairs when
@@ -1860,7 +2222,8 @@ class Context:
         ``recon_dests`` (the mode call only): one ``(ptr, pitch_bytes, step_bytes, cap_bytes, row0, row1, col0, col1, scale,
         bias)`` per image, ptr 0 for none -- the reconstructions go to device memory in format ``recon_fmt``
         (``nblic_amd_encode_batch_modes_from_to``) and there are no host ``recons``.  ``modes``: one colour mode byte per
-        frame of three sources -- the _color siblings of the four calls.
+        frame of three sources -- the _color siblings of the four calls.  ``stack``: (depth, one slice mode byte per image) --
+        the _stack siblings.
         ``ValueError`` when the library refuses the whole call."""
         n = len(srcs)
         nears, efforts = _per_image(near, n, "near"), _per_image(effort, n, "effort")
@@ -1886,7 +2249,12 @@ class Context:
             if recon_dests is not None:
                 raise ValueError("colour modes are lossless: there is no reconstruction to deliver")
             head += (_modes_ptr(modes),)
-        pick = (lambda name: getattr(self.lib, name + "_color")) if modes is not None else (lambda name: getattr(self.lib, name))
+        if stack is not None:
+            if recon_dests is not None or modes is not None:
+                raise ValueError("slice stacks go neither with colour modes nor with reconstructions on the device")
+            head += (int(stack[0]), _modes_ptr(stack[1]))
+        suffix = "_stack" if stack is not None else ("_color" if modes is not None else "")
+        pick = lambda name: getattr(self.lib, name + suffix)
         if every_rows is not None:
             every = _every_rows_list(every_rows, n)
             idxs = [np.empty(max(index_bytes(1 if q else 0, h, w, 0 if q else 1, r), 1), np.uint8) for (h, w), r in zip(shapes, every)]
@@ -1935,7 +2303,8 @@ class Context:
         return outs, got
 
     def encode_batch_from(self, src, rows=None, cols=None, scale: float = 1.0, bias: float = 0.0, near=0, effort=1, every_rows=None,
-                          band_rows: int = 0, info: Optional[dict] = None, recon_out=None, recon_scale=1.0, recon_bias=0.0, color=None):
+                          band_rows: int = 0, info: Optional[dict] = None, recon_out=None, recon_scale=1.0, recon_bias=0.0, color=None,
+                          stack=None, depth=None):
         """Encode images that lie in device memory in any layout, as pixels or as floats quantised on the way (the _from
         calls; include/nblic_amd.h says what the pixel of an element is).  ``src``: one tensor [N, H, W], one tensor
         [N, C, H, W] -- every channel is an image, n-major -- or a list of 2-D tensors or views, of ONE dtype (uint8,
@@ -1964,11 +2333,31 @@ class Context:
         them): the streams of frame f are those of ``rct_forward(R, G, B, mode=modes[f])`` -- each difference is taken
         against the frame's base channel.  ``"rct"`` is every mode ``COLOR_RCT``.  A frame of mode 0 is three independent
         images, and only its images may have ``near`` > 0.  Nothing in a stream names the mode: keep the byte with the
-        frame's three streams.  An invalid byte refuses the whole call (``ValueError``)."""
+        frame's three streams.  An invalid byte refuses the whole call (``ValueError``).
+
+        ``stack="delta"`` or ``stack=modes`` with ``depth`` (default: dimension 1 of a 4-D ``src``; required for a list):
+        image ``s * depth + d`` is slice d of stack s -- the slices of a volume, the frames of a static camera -- and the
+        streams are those of ``stack_forward`` of each stack's collected planes: a slice of mode 1 is coded as
+        ``(x[d] - x[d - 1] + 128) mod 256``, one of mode 0 as it is; ``"delta"`` is mode 1 for every slice but the first, and
+        :meth:`stack_plan` chooses per slice.  Ordinary streams again, and nothing in them names the mode: keep the bytes.
+        The slices of a stack with a delta have one size; such a stack with a refused source has ``None`` everywhere.
+        ``near`` > 0 only on a key slice whose successor is a key slice; not with ``color`` or ``recon_out``
+        (``ValueError``, as for an invalid byte)."""
         flag, modes = _color_arg(color, src)
         if color is not None and recon_out is not None:
             raise ValueError('color="rct" is lossless: there is no reconstruction to deliver')
         srcs, fmt = _srcs_of(_src_views(src), rows, cols)
+        sdepth, smodes = _stack_arg(stack, depth, src, len(srcs))
+        if smodes is not None:
+            if color is not None or recon_out is not None:
+                raise ValueError("stack goes neither with color nor with recon_out")
+            nears = _per_image(near, len(srcs), "near")
+            if not self.lib.nblic_amd_stack_modes_valid(len(srcs), sdepth, _modes_ptr(smodes)):
+                raise ValueError("stack: mode bytes are 0 or 1, and slice 0 of every stack is a key (0)")
+            for k, v in enumerate(nears):
+                if v > 0 and (smodes[k] != STACK_KEY or ((k + 1) % sdepth != 0 and smodes[k + 1] != STACK_KEY)):
+                    raise ValueError("stack: near > 0 only on a key slice whose successor is a key slice")
+            return self.encode_from_srcs(srcs, fmt, scale, bias, near, effort, every_rows, band_rows, info, stack=(sdepth, smodes))
         if recon_out is None:
             return self.encode_from_srcs(srcs, fmt | flag, scale, bias, near, effort, every_rows, band_rows, info, modes=modes)
         views = _src_views(recon_out)

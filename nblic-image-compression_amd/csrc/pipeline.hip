@@ -311,10 +311,14 @@ struct nblic_amd_ctx {
     long fed_bytes = 0;                   // bytes the last drop-in decode read from the caller's stream
     int feed_pipe[2] = {-1, -1};          // safe_copy: the kernel does the reading
     DevBuf<DeliverTask> dec_deliver;      // nblic_amd_decode_batch_to: the chunks' delivery tasks (grow-only, like dec_jobs)
+    DevBuf<StackDeliverTask> dec_runs;    // nblic_amd_decode_batch_to_ex_stack: the runs of the call's k_deliver_stack launch and
+    DevBuf<StackSlice> dec_slices;        // their slice records (grow-only too)
     std::atomic<long> collect_counts[4] = {};   // nblic_amd_collect_stats: images in place, images collected, k_collect launches, pixels collected
     double collect_ms = 0; long collect_timed = 0;   // nblic_amd_collect_ms: GPU time of the k_collect launches that were timed, and how many.  Guarded by stat_m
     std::atomic<long> color_counts[2] = {};     // nblic_amd_color_plan_stats: k_color_cost launches, pixels read (three per frame position)
     double color_ms = 0;                        // nblic_amd_color_plan_stats: GPU time of the last nblic_amd_color_plan's launch.  Guarded by stat_m
+    std::atomic<long> stack_counts[4] = {};     // nblic_amd_stack_plan_stats: k_stack_cost launches, source elements read, k_deliver_stack launches, runs delivered
+    double stack_ms = 0, stack_deliver_ms = 0;  // GPU time of the last nblic_amd_stack_plan's launch / of the last timed k_deliver_stack launch.  Guarded by stat_m
     long deliver_tasks = 0, deliver_strided = 0;     // nblic_amd_deliver_stats: of the last call that delivers.  Guarded by stat_m (at the end: no member has moved)
 };
 
@@ -492,6 +496,7 @@ enum : uint8_t { kSrcRefused = 0, kSrcInPlace = 1, kSrcCollect = 2 };
 struct CollectFrom {
     const nblic_amd_src *srcs; uint32_t format; float scale, bias;
     std::vector<uint8_t> modes;                                          // not empty: sources 3f, 3f + 1, 3f + 2 are R, G, B of frame f, coded in colour mode modes[f] (color_plan.h)
+    std::vector<uint8_t> slice_modes; int depth = 0;                     // not empty: source s * depth + d is slice d of stack s, in slice mode slice_modes[s * depth + d] (stack.h)
     std::vector<uint8_t> how;
     std::vector<CollectTask> tasks;                                      // kSrcCollect: all but dst, px0, px1 and first_chunk
     std::vector<const uint8_t *> imgs; std::vector<int> hs, ws;
@@ -1709,10 +1714,23 @@ static bool decode_launch(const DecodeItem &first, const SerialJob *d_jobs, cons
 // modes (the _color calls; NBLIC_AMD_FORMAT_RCT: every one 0x0D): images 3f, 3f + 1, 3f + 2 are the three planes of frame f
 // in colour mode modes[f] (color_plan.h), and the channels coded as differences are put together again on the way out
 // (deliver.h: a task with a reference).  A frame of mode 0 is three images like any other.
+// slice_modes / depth (the _stack calls, stack.h): image s * depth + d is slice d of stack s; a run of differences is put
+// together again by ONE task of k_deliver_stack, a key slice without a delta behind it goes through k_deliver like any image.
 struct DeliverTo {
     const nblic_amd_dest_ex *dests; uint32_t format; const uint8_t *modes = nullptr;
+    const uint8_t *slice_modes = nullptr; int depth = 0;
     uint32_t mode_of(int k) const { return modes ? modes[k / 3] : 0u; }  // of the frame image k belongs to
+    bool skipped(int k) const { return slice_modes && !dests[k].ptr && dests[k].cap_bytes == 0; }      // a slice decoded as a reference only
+    bool stack_has_delta(int k) const {                                  // does the stack image k belongs to hold a delta slice?
+        if (!slice_modes) return false;
+        const int s = k - k % depth;
+        for (int i = s; i < s + depth; i++) if (slice_modes[i] == kStackDelta) return true;
+        return false;
+    }
 };
+
+// The depth and the slice modes of a _stack call (stack.h), as the entry points hand them down.
+struct StackArg { int depth; const unsigned char *modes; };
 
 // NBLIC_AMD_FORMAT_RCT in a format argument of a _from or a _to_ex call: is it there?  It is taken off.
 static bool format_rct(int &format) {
@@ -1774,6 +1792,10 @@ static bool deliver_dest_task(const nblic_amd_ctx *c, const DeliverTo &to, int k
     T = DeliverTask{};
     T.row0 = D.row0; T.row1 = D.row1 ? D.row1 : h; T.col0 = D.col0; T.col1 = D.col1 ? D.col1 : w;
     if (T.row0 < 0 || T.row1 <= T.row0 || T.row1 > h || T.col0 < 0 || T.col1 <= T.col0 || T.col1 > w) return false;
+    if (to.skipped(k)) {                                                 // a _stack call's slice that is decoded as a reference only: the window, and no destination
+        T.src_pitch = uint32_t(w); T.format = to.format; T.dst_step = deliver_elem(to.format);
+        return true;
+    }
     if (!deliver_args_ok(int(to.format), D.scale, D.bias)) return false;
     const size_t elem = deliver_elem(to.format), rows = size_t(T.row1 - T.row0), cols = size_t(T.col1 - T.col0);
     if (!D.ptr || uintptr_t(D.ptr) % elem || D.pitch_bytes % elem || D.step_bytes % elem || D.step_bytes < elem || D.step_bytes > kDeliverMaxStep) return false;
@@ -1788,13 +1810,19 @@ static bool deliver_dest_task(const nblic_amd_ctx *c, const DeliverTo &to, int k
 
 // The tasks' places in ONE k_deliver launch, their upload to d_tasks and the launch, queued on st.  `c`: the context whose
 // nblic_amd_deliver_stats count them (null: the zeros after a failure are not counted).
+// deliver_place: the places alone, counted and held against the limits of one launch.
+static bool deliver_place(DeliverTask *tasks, size_t n, nblic_amd_ctx *c, unsigned long long &chunks) {
+    long strided = 0;
+    chunks = 0;
+    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(chunks); chunks += deliver_task_chunks(tasks[i]); strided += deliver_strided(tasks[i]) ? 1 : 0; }
+    if (c && n) { std::lock_guard<std::mutex> l(c->stat_m); c->deliver_tasks += long(n); c->deliver_strided += strided; }
+    return chunks < (1ull << 31) && n < (size_t(1) << 30);
+}
 static bool deliver_queue(DeliverTask *tasks, size_t n, DeliverTask *d_tasks, hipStream_t st, nblic_amd_ctx *c = nullptr) {
     unsigned long long chunks = 0;
-    long strided = 0;
-    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(chunks); chunks += deliver_task_chunks(tasks[i]); strided += deliver_strided(tasks[i]) ? 1 : 0; }
+    const bool fits = deliver_place(tasks, n, c, chunks);
     if (n == 0) return true;
-    if (c) { std::lock_guard<std::mutex> l(c->stat_m); c->deliver_tasks += long(n); c->deliver_strided += strided; }
-    if (chunks >= (1ull << 31) || n >= (size_t(1) << 30)) return false;
+    if (!fits) return false;
     return hipMemcpyAsync(d_tasks, tasks, n * sizeof(DeliverTask), hipMemcpyHostToDevice, st) == hipSuccess && deliver_launch(d_tasks, int(n), uint32_t(chunks), st);
 }
 
@@ -1806,10 +1834,83 @@ static void deliver_stats_reset(nblic_amd_ctx *c) {
 
 // After a device failure: zero bytes into every window, by the same kernel, as far as the stream still works.
 static void deliver_zeros(std::vector<DeliverTask> &tasks, hipStream_t st) {
+    tasks.erase(std::remove_if(tasks.begin(), tasks.end(), [](const DeliverTask &T) { return !T.dst; }), tasks.end());      // (a _stack call's skipped slices have no window to zero)
     if (tasks.empty() || !st) return;
     DevBuf<DeliverTask> d_tasks;
     for (DeliverTask &T : tasks) { T.zero = 1; T.gate = nullptr; }
     if (d_tasks.alloc(tasks.size()) == hipSuccess && deliver_queue(tasks.data(), tasks.size(), d_tasks, st)) hipStreamSynchronize(st);
+}
+
+// ---- the delivery of a _stack call (stack.h, serial_engine.h k_deliver_stack) ---------------------------------------------------
+// What a _stack call launches: the tasks of k_deliver for its lone key slices, and the runs with their slice records.
+struct StackDelivery {
+    std::vector<DeliverTask> plain; std::vector<StackDeliverTask> runs; std::vector<StackSlice> slices;
+    Event t0, t1;                                                        // around the call's delivery launches (nblic_amd_stack_plan_stats)
+};
+
+// of[k]: image k's task as k_deliver would take it -- its window, its plane from row 0 on, its gate, zero for a plane known to
+// be bad, dst null for a skipped slice -- or null for an image that is not live (a stack with a delta is live as a whole).
+static void stack_delivery_plan(const DeliverTo &to, int n, const std::vector<const DeliverTask *> &of, StackDelivery &P) {
+    for (int s = 0; s + to.depth <= n; s += to.depth)
+        for (int d = 0; d < to.depth;) {
+            const int len = int(stack_run_len(to.slice_modes + s, uint32_t(d), uint32_t(to.depth)));
+            const DeliverTask *K = of[size_t(s + d)];
+            if (len == 1) {
+                if (K && K->dst) P.plain.push_back(*K);
+                d++;
+                continue;
+            }
+            bool live = true, wanted = false;
+            for (int i = 0; i < len; i++) { const DeliverTask *T = of[size_t(s + d + i)]; live = live && T; wanted = wanted || (T && T->dst); }
+            if (live && wanted) {
+                StackDeliverTask R{};
+                R.first_slice = uint32_t(P.slices.size()); R.count = uint32_t(len);
+                R.rows = uint32_t(K->row1 - K->row0); R.col0 = uint32_t(K->col0); R.col1 = uint32_t(K->col1); R.src_pitch = K->src_pitch; R.format = K->format;
+                for (int i = 0; i < len; i++) {
+                    const DeliverTask &T = *of[size_t(s + d + i)];
+                    const size_t skip = size_t(T.row0) * size_t(T.src_pitch);
+                    StackSlice S{};
+                    S.src = T.src + skip; S.src_bytes = T.src_bytes - skip; S.gate = T.gate;
+                    S.dst = T.dst; S.dst_pitch = T.dst_pitch; S.dst_step = T.dst_step; S.scale = T.scale; S.bias = T.bias; S.zero = T.zero;
+                    P.slices.push_back(S);
+                }
+                P.runs.push_back(R);
+            }
+            d += len;
+        }
+}
+
+// The runs' places in ONE k_deliver_stack launch, held against its limits, and the upload of the two tables, queued on st.
+static bool deliver_stack_upload(StackDeliverTask *runs, size_t n, const StackSlice *slices, size_t n_slices, StackDeliverTask *d_runs, StackSlice *d_slices,
+                                 hipStream_t st, unsigned long long &chunks) {
+    chunks = 0;
+    for (size_t i = 0; i < n; i++) { runs[i].first_chunk = uint32_t(chunks); chunks += stack_task_chunks(runs[i]); }
+    if (n == 0) return true;
+    if (chunks >= (1ull << 31) || n >= (size_t(1) << 30) || n_slices >= (size_t(1) << 30)) return false;
+    return hipMemcpyAsync(d_runs, runs, n * sizeof(StackDeliverTask), hipMemcpyHostToDevice, st) == hipSuccess &&
+           hipMemcpyAsync(d_slices, slices, n_slices * sizeof(StackSlice), hipMemcpyHostToDevice, st) == hipSuccess;
+}
+
+// At most one launch of each kernel for the call, queued on st: the three tables go up first (d_plain, d_runs, d_slices: room
+// for P's, the caller's, alive until the stream has been waited for), then the launches between the two events.
+static bool stack_delivery_queue(nblic_amd_ctx *c, StackDelivery &P, DeliverTask *d_plain, StackDeliverTask *d_runs, StackSlice *d_slices, hipStream_t st) {
+    if ((!P.plain.empty() && !d_plain) || (!P.runs.empty() && (!d_runs || !d_slices))) return false;
+    unsigned long long plain_chunks = 0, run_chunks = 0;
+    if (!deliver_place(P.plain.data(), P.plain.size(), c, plain_chunks)) return false;
+    if (!P.plain.empty() && hipMemcpyAsync(d_plain, P.plain.data(), P.plain.size() * sizeof(DeliverTask), hipMemcpyHostToDevice, st) != hipSuccess) return false;
+    if (!deliver_stack_upload(P.runs.data(), P.runs.size(), P.slices.data(), P.slices.size(), d_runs, d_slices, st, run_chunks)) return false;
+    if (P.t0.create(hipEventDefault) != hipSuccess || P.t1.create(hipEventDefault) != hipSuccess || hipEventRecord(P.t0, st) != hipSuccess) return false;
+    if (!deliver_launch(d_plain, int(P.plain.size()), uint32_t(plain_chunks), st)) return false;
+    if (!P.runs.empty()) {
+        c->stack_counts[2] += 1; c->stack_counts[3] += long(P.runs.size());
+        if (!deliver_stack_launch(d_runs, int(P.runs.size()), d_slices, uint32_t(run_chunks), st)) return false;
+    }
+    return hipEventRecord(P.t1, st) == hipSuccess;
+}
+// After the stream has been waited for: the GPU time of the call's delivery launches.
+static void stack_delivery_timed(nblic_amd_ctx *c, const StackDelivery &P) {
+    float ms = 0.0f;
+    if (P.t0 && P.t1 && hipEventElapsedTime(&ms, P.t0, P.t1) == hipSuccess) { std::lock_guard<std::mutex> l(c->stat_m); c->stack_deliver_ms = double(ms); }
 }
 
 // ---- the sources of the _from calls, checked on the host (CollectFrom, above slot_begin) ------------------------------------
@@ -1840,6 +1941,28 @@ static void collect_plan(const nblic_amd_ctx *c, CollectFrom &from, int n) {
         if (from.how[i] == kSrcRefused) continue;
         from.hs[i] = from.srcs[k].rows; from.ws[i] = from.srcs[k].cols;
         if (from.how[i] == kSrcInPlace) from.imgs[i] = from.tasks[i].src;
+    }
+    // Slice stacks: a delta slice becomes a task with the SOURCE of the slice before it as its reference (stack.h) --
+    // collected even where it could be used in place -- and a key slice stays what it was.  A stack with a delta and a
+    // refused source, or sources of unequal size, is refused as a whole; a stack of keys only is `depth` images like any other.
+    if (!from.slice_modes.empty()) {
+        const size_t D = size_t(from.depth);
+        for (size_t s = 0; s + D <= count; s += D) {
+            bool delta = false, ok = true;
+            for (size_t i = s; i < s + D; i++) {
+                delta = delta || from.slice_modes[i] == kStackDelta;
+                ok = ok && from.how[i] != kSrcRefused && from.hs[i] == from.hs[s] && from.ws[i] == from.ws[s];
+            }
+            if (!delta) continue;
+            for (size_t i = s; i < s + D; i++) {
+                if (!ok) { from.how[i] = kSrcRefused; from.imgs[i] = nullptr; from.hs[i] = from.ws[i] = 0; continue; }
+                if (from.slice_modes[i] != kStackDelta) continue;
+                const CollectTask &B = from.tasks[i - 1];
+                CollectTask &T = from.tasks[i];
+                T.ref = B.src; T.ref_pitch = B.pitch; T.ref_step = B.step;
+                from.how[i] = kSrcCollect; from.imgs[i] = nullptr;
+            }
+        }
     }
     if (from.modes.empty()) return;
     // Colour frames: a channel that the frame's mode codes as a difference becomes a task with the base channel's SOURCE as
@@ -1922,6 +2045,33 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         }
         items.swap(kept_items); deliveries.swap(kept_tasks);
     }
+    if (to && to->slice_modes) {
+        // a stack with a delta stands or falls as a whole: slices of one size and one window, lossless inside its runs
+        auto bytes_of = [](const DecodeItem &it) {
+            return stream_buf_bytes(it.len) + up256(size_t(it.h) * size_t(it.w)) + up256(lsq_stats_bytes(it.kind, it.effort, it.w)) + up256(record_state_bytes(it.kind)) + (it.kind ? up256(kQTab) : 0);
+        };
+        std::vector<int> at(size_t(n), -1);
+        for (size_t i = 0; i < items.size(); i++) at[size_t(items[i].k)] = int(i);
+        std::vector<uint8_t> keep(items.size(), 1);
+        for (int s = 0; s + to->depth <= n; s += to->depth) {
+            if (!to->stack_has_delta(s)) continue;                       // `depth` images like any other
+            bool ok = true;
+            for (int k = s; k < s + to->depth && ok; k++) {
+                const int i = at[size_t(k)], i0 = at[size_t(s)];
+                ok = i >= 0 && i0 >= 0 && items[size_t(i)].h == items[size_t(i0)].h && items[size_t(i)].w == items[size_t(i0)].w &&
+                     same_window(deliveries[size_t(i)], deliveries[size_t(i0)]);
+                const bool in_run = to->slice_modes[k] == kStackDelta || (k + 1 < s + to->depth && to->slice_modes[k + 1] == kStackDelta);
+                ok = ok && !(in_run && items[size_t(i)].near);
+            }
+            if (!ok) for (int k = s; k < s + to->depth; k++) if (at[size_t(k)] >= 0) keep[size_t(at[size_t(k)])] = 0;
+        }
+        std::vector<DecodeItem> kept_items; std::vector<DeliverTask> kept_tasks;
+        for (size_t i = 0; i < items.size(); i++) {
+            if (keep[i]) { kept_items.push_back(items[i]); kept_tasks.push_back(deliveries[i]); }
+            else arena -= bytes_of(items[i]);
+        }
+        items.swap(kept_items); deliveries.swap(kept_tasks);
+    }
     if (items.empty()) return true;
     std::stable_sort(items.begin(), items.end(), [](const DecodeItem &a, const DecodeItem &b) { return a.kind * 4 + a.effort < b.kind * 4 + b.effort; });
     const int m = int(items.size());
@@ -1954,7 +2104,7 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
             T.src = recon; T.src_bytes = up256(size_t(it.h) * size_t(it.w)); T.gate = state;
         }
     }
-    const bool rct = to && to->modes;
+    const bool rct = to && to->modes, stack = to && to->slice_modes;
     if (rct) {                                                           // every task of a frame with a difference is gated by its three records; a difference refers to the base's plane
         std::vector<int> at(size_t(n), -1);
         for (int i = 0; i < m; i++) at[size_t(items[size_t(i)].k)] = i;
@@ -2014,7 +2164,7 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
             if (!to && hipMemcpyAsync(imgs[it.k], jobs[size_t(i)].recon, size_t(it.h) * size_t(it.w), hipMemcpyDeviceToHost, ch.st) != hipSuccess) return false;
         }
         // the chunk's windows: ONE launch on its stream, behind its decode launches (colour frames: one for the call, below)
-        return !to || rct || deliver_queue(deliveries.data() + ch.i0, size_t(ch.i1 - ch.i0), c->dec_deliver + ch.i0, ch.st, c);
+        return !to || rct || stack || deliver_queue(deliveries.data() + ch.i0, size_t(ch.i1 - ch.i0), c->dec_deliver + ch.i0, ch.st, c);
     };
     for (size_t n = 0; n < chunks.size(); n++) {
         if (n >= 2 && hipStreamSynchronize(chunks[n].st) != hipSuccess) return fail("a chunk");      // heads[] of chunk n - 2 have landed before its stream is reused (its H2D reads heads of chunk n)
@@ -2031,8 +2181,30 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
             !deliver_queue(deliveries.data(), deliveries.size(), c->dec_deliver, c->dec_stream, c)) return fail("the colour delivery");
         if (hipStreamSynchronize(c->dec_stream) != hipSuccess) return fail("the colour delivery");      // (done2 goes when this block ends)
     }
+    if (stack) {
+        // As for colour frames: the planes of a run may lie in chunks of both streams.  ONE k_deliver launch for the lone key
+        // slices and ONE k_deliver_stack launch for the runs, on the first stream behind the end of the second one's work.
+        std::vector<const DeliverTask *> of(size_t(n), nullptr);
+        for (int i = 0; i < m; i++) of[size_t(items[size_t(i)].k)] = &deliveries[size_t(i)];
+        StackDelivery plan;
+        stack_delivery_plan(*to, n, of, plan);                           // (no more plain tasks than items: dec_deliver holds them)
+        Event done2;
+        if (c->dec_runs.reserve(std::max<size_t>(plan.runs.size(), 1)) != hipSuccess || c->dec_slices.reserve(std::max<size_t>(plan.slices.size(), 1)) != hipSuccess ||
+            done2.create(hipEventDisableTiming) != hipSuccess || hipEventRecord(done2, c->dec_stream2) != hipSuccess ||
+            hipStreamWaitEvent(c->dec_stream, done2, 0) != hipSuccess ||
+            !stack_delivery_queue(c, plan, c->dec_deliver, c->dec_runs, c->dec_slices, c->dec_stream)) return fail("the stack delivery");
+        if (hipStreamSynchronize(c->dec_stream) != hipSuccess) return fail("the stack delivery");      // (done2 goes when this block ends)
+        stack_delivery_timed(c, plan);
+    }
     if (hipStreamSynchronize(c->dec_stream) != hipSuccess || hipStreamSynchronize(c->dec_stream2) != hipSuccess) return fail("the last chunk");
     for (int i = 0; i < m; i++) status[items[size_t(i)].k] = heads[size_t(i)].status == kDone ? 0 : -1;
+    if (stack)                                                           // what the gates did on the device: behind a failed plane of a run, no delivered slice has its pixels
+        for (int s = 0; s + to->depth <= n; s += to->depth)
+            for (int d = 1, bad = status[s] != 0; d < to->depth; d++) {
+                if (to->slice_modes[s + d] == kStackKey) bad = 0;
+                bad = bad || status[s + d] != 0;
+                if (bad && !to->skipped(s + d)) status[s + d] = -1;
+            }
     if (rct)                                                             // what the gates did on the device: a frame with a failed plane has none
         for (int f = 0; f + 2 < n; f += 3)
             if (to->mode_of(f) != kColorPlain && (status[f] != 0 || status[f + 1] != 0 || status[f + 2] != 0)) status[f] = status[f + 1] = status[f + 2] = -1;
@@ -3713,6 +3885,18 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
                             !A.it.near && !B.it.near && !D.it.near && same_window(A.deliver, B.deliver) && same_window(A.deliver, D.deliver);
             if (!ok) A.live = B.live = D.live = false;
         }
+    if (to && to->slice_modes)                                           // a stack with a delta stands or falls as a whole: slices of one size and one window, lossless inside its runs
+        for (int s = 0; s + to->depth <= n; s += to->depth) {
+            if (!to->stack_has_delta(s)) continue;
+            const IdxDecImage &A = all[size_t(s)];
+            bool ok = true;
+            for (int k = s; k < s + to->depth && ok; k++) {
+                const IdxDecImage &I = all[size_t(k)];
+                const bool in_run = to->slice_modes[k] == kStackDelta || (k + 1 < s + to->depth && to->slice_modes[k + 1] == kStackDelta);
+                ok = A.live && I.live && I.it.h == A.it.h && I.it.w == A.it.w && same_window(I.deliver, A.deliver) && !(in_run && I.it.near);
+            }
+            if (!ok) for (int k = s; k < s + to->depth; k++) all[size_t(k)].live = false;
+        }
     for (int k = 0; k < n; k++) {
         IdxDecImage &I = all[size_t(k)];
         if (!I.live) continue;
@@ -3965,7 +4149,29 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
             const size_t skip = size_t(I->row0 - G.base) * size_t(I->it.w);
             I->deliver.ref = G.d_plane + skip; I->deliver.ref_bytes = G.plane_bytes - skip; I->deliver.ref_pitch = uint32_t(I->it.w);
         }
-    for (IdxDecImage *I : live) {
+    const bool stack = to && to->slice_modes;
+    StackDelivery stack_plan;
+    if (stack) {
+        // ONE k_deliver launch for the lone key slices and ONE k_deliver_stack launch for the runs: a damaged plane is known
+        // here, so it and every later slice of its run get zeros (the record's zero) and -1; a skipped slice has its plane's status.
+        std::vector<const DeliverTask *> of(size_t(n), nullptr);
+        for (IdxDecImage *I : live) {
+            I->deliver.zero = I->bad ? 1u : 0u;
+            of[size_t(I->k)] = &I->deliver;
+            status[I->k] = I->bad ? -1 : 0;
+        }
+        stack_delivery_plan(*to, n, of, stack_plan);
+        // (the call's workspace is a pool of its own: the three tables are three more blocks of it)
+        if (!stack_delivery_queue(c, stack_plan, mem.make<DeliverTask>(stack_plan.plain.size()), mem.make<StackDeliverTask>(stack_plan.runs.size()),
+                                  mem.make<StackSlice>(stack_plan.slices.size()), st)) return fail("delivery");
+        for (int s = 0; s + to->depth <= n; s += to->depth)
+            for (int d = 1, bad = status[s] != 0; d < to->depth; d++) {
+                if (to->slice_modes[s + d] == kStackKey) bad = 0;
+                bad = bad || status[s + d] != 0;
+                if (bad && !to->skipped(s + d)) status[s + d] = -1;
+            }
+    }
+    if (!stack) for (IdxDecImage *I : live) {
         const size_t f = size_t(I->k - I->k % 3);
         if (I->bad || (to && to->mode_of(I->k) != kColorPlain && (all[f].bad || all[f + 1].bad || all[f + 2].bad))) {
             if (to) { I->deliver.zero = 1; deliveries.push_back(I->deliver); }
@@ -3979,6 +4185,7 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
     // `to`: ONE launch delivers every live image's window -- zeros for the images that failed above
     if (to && !deliver_queue(deliveries.data(), deliveries.size(), reinterpret_cast<DeliverTask *>(d_call + verdict_bytes + unpack_task_bytes), st, c)) return fail("delivery");
     if (hipStreamSynchronize(st) != hipSuccess) return fail("rows");
+    if (stack) stack_delivery_timed(c, stack_plan);
     split[3] = ms_since(t0);
     { std::lock_guard<std::mutex> l(c->stat_m); for (int k = 0; k < 4; k++) c->idxdec_split[k] = split[k]; }
     for (int k = 0; k < n; k++) every = every && status[k] == 0;
@@ -5454,6 +5661,307 @@ int nblic_amd_debug_color_cost(nblic_amd_ctx *c, int n, const void *const *srcs,
     return ok ? 0 : -2;
 }
 
+// ---- slice stacks: the plan, and the two kernels on caller-made inputs (stack.h) ---------------------------------------------
+// The tasks' places in ONE k_stack_cost launch, the upload of the two tables and the launch, queued on st.  The costs are the
+// caller's to zero.
+static bool stack_cost_queue(nblic_amd_ctx *c, StackCostTask *tasks, size_t n, const StackCostSlice *slices, size_t n_slices, StackCostTask *d_tasks,
+                             StackCostSlice *d_slices, hipStream_t st) {
+    unsigned long long tiles = 0, pixels = 0;
+    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(tiles); tiles += stack_task_tiles(tasks[i]); pixels += (unsigned long long)(tasks[i].count) * tasks[i].rows * tasks[i].cols; }
+    if (n == 0) return true;
+    if (tiles >= (1ull << 31) || n >= (size_t(1) << 30) || n_slices >= (size_t(1) << 30)) return false;
+    c->stack_counts[0] += 1; c->stack_counts[1] += long(pixels);
+    return hipMemcpyAsync(d_tasks, tasks, n * sizeof(StackCostTask), hipMemcpyHostToDevice, st) == hipSuccess &&
+           hipMemcpyAsync(d_slices, slices, n_slices * sizeof(StackCostSlice), hipMemcpyHostToDevice, st) == hipSuccess &&
+           stack_cost_launch(d_tasks, int(n), d_slices, uint32_t(tiles), st);
+}
+
+int nblic_amd_stack_plan(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias, int depth, int key_every,
+                         unsigned char *slice_modes, unsigned long long *costs) {
+    if (!c || c->broken || n_images < 0 || depth < 1 || n_images % depth != 0 || key_every < 0 || !srcs || !slice_modes || format >= int(kCollectFormats) ||
+        !deliver_args_ok(format, scale, bias) || hipSetDevice(c->device) != hipSuccess) return -1;
+    const size_t D = size_t(depth), stacks = size_t(n_images) / D;
+    std::lock_guard<std::mutex> g(c->api);
+    CollectFrom from{};
+    from.srcs = srcs; from.format = uint32_t(format); from.scale = scale; from.bias = bias;
+    std::vector<StackCostTask> tasks;
+    std::vector<StackCostSlice> slices;
+    std::vector<size_t> stack_of;
+    for (size_t s = 0; s < stacks; s++) {                                // a stack with a refused source, or sources of unequal size: 0xFF, and nothing is launched for it
+        StackCostTask T{};
+        T.first_slice = uint32_t(slices.size()); T.count = uint32_t(D);
+        bool ok = true;
+        for (size_t d = 0; d < D && ok; d++) {
+            CollectTask S;
+            ok = collect_src_task(c, from, int(s * D + d), S) != kSrcRefused && (d == 0 || (S.rows == T.rows && S.cols == T.cols));
+            if (!ok) break;
+            T.rows = S.rows; T.cols = S.cols;
+            slices.push_back(StackCostSlice{S.src, S.pitch, S.step, 0u});
+        }
+        for (size_t d = 0; d < D; d++) slice_modes[s * D + d] = uint8_t(kStackRefused);
+        if (!ok) { slices.resize(T.first_slice); continue; }
+        T.format = uint32_t(format); T.scale = scale; T.bias = bias;
+        tasks.push_back(T); stack_of.push_back(s);
+    }
+    std::vector<unsigned long long> table(size_t(n_images) * 2, 0ull);
+    if (!tasks.empty()) {
+        Stream st;
+        Event t0, t1;
+        DevPool mem;
+        const size_t sums = tasks.size() * D * 2;
+        unsigned long long *d_costs = mem.make<unsigned long long>(sums);
+        StackCostTask *d_tasks = mem.make<StackCostTask>(tasks.size());
+        StackCostSlice *d_slices = mem.make<StackCostSlice>(slices.size());
+        std::vector<unsigned long long> back(sums);
+        if (!d_costs || !d_tasks || !d_slices || st.create(hipStreamNonBlocking) != hipSuccess || t0.create(hipEventDefault) != hipSuccess || t1.create(hipEventDefault) != hipSuccess) return -1;
+        for (size_t i = 0; i < tasks.size(); i++) tasks[i].costs = d_costs + i * D * 2;
+        const bool ok = [&]() -> bool {                                  // the launch, then ONE copy of the whole table
+            HIP_OK(hipMemsetAsync(d_costs, 0, sums * sizeof(unsigned long long), st));
+            HIP_OK(hipEventRecord(t0, st));
+            if (!stack_cost_queue(c, tasks.data(), tasks.size(), slices.data(), slices.size(), d_tasks, d_slices, st)) return false;
+            HIP_OK(hipEventRecord(t1, st));
+            HIP_OK(hipMemcpyAsync(back.data(), d_costs, sums * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            return true;
+        }();
+        if (st) hipStreamSynchronize(st);
+        if (!ok) return -1;
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, t0, t1) == hipSuccess) { std::lock_guard<std::mutex> l(c->stat_m); c->stack_ms = double(ms); }
+        for (size_t i = 0; i < tasks.size(); i++) {
+            const size_t s = stack_of[i];
+            memcpy(&table[s * D * 2], &back[i * D * 2], D * 2 * sizeof(unsigned long long));
+            for (size_t d = 0; d < D; d++)
+                slice_modes[s * D + d] = stack_slice_mode(uint32_t(d), uint32_t(key_every), back[(i * D + d) * 2], back[(i * D + d) * 2 + 1]);
+        }
+    }
+    if (costs) memcpy(costs, table.data(), table.size() * sizeof(unsigned long long));
+    return 0;
+}
+
+int nblic_amd_stack_choose(unsigned long long intra, unsigned long long delta) { return int(stack_choose(intra, delta)); }
+int nblic_amd_stack_slice_mode(int d, int key_every, unsigned long long intra, unsigned long long delta) {
+    return d < 0 || key_every < 0 ? -1 : int(stack_slice_mode(uint32_t(d), uint32_t(key_every), intra, delta));
+}
+int nblic_amd_stack_mode_valid(int mode) { return mode >= 0 && mode < 256 && stack_mode_valid(uint32_t(mode)) ? 1 : 0; }
+int nblic_amd_stack_modes_valid(int n_images, int depth, const unsigned char *slice_modes) { return stack_modes_ok(n_images, depth, slice_modes) ? 1 : 0; }
+
+int nblic_amd_stack_plan_stats(nblic_amd_ctx *c, long out[4], double *last_ms) {
+    if (!c || !out) return -1;
+    for (int k = 0; k < 4; k++) out[k] = c->stack_counts[k].load();
+    if (last_ms) { std::lock_guard<std::mutex> l(c->stat_m); last_ms[0] = c->stack_ms; last_ms[1] = c->stack_deliver_ms; }
+    return 0;
+}
+
+// A debug stack's task: all but the sources' addresses and costs.  false: an argument no task can hold.
+static bool debug_stack_cost_task(StackCostTask &T, int count, int rows, int cols, int format, float scale, float bias) {
+    T = StackCostTask{};
+    if (count < 1 || count > 65536 || rows < 1 || cols < 1 || format < 0 || format >= int(kCollectFormats)) return false;
+    T.count = uint32_t(count); T.rows = uint32_t(rows); T.cols = uint32_t(cols); T.format = uint32_t(format); T.scale = scale; T.bias = bias;
+    return true;
+}
+
+// Host only: the shared tile walk (stack.h stack_cost_host) over the `count` sources of ONE stack, cap_bytes[d] readable from
+// srcs[d].  costs: two sums per slice (intra, delta); tiles: how many workgroups the kernel would run.  -1: refused.
+int nblic_amd_debug_stack_cost_host(int count, const void *const *srcs, const size_t *cap_bytes, const size_t *pitches, const size_t *steps, int rows, int cols,
+                                    int format, float scale, float bias, unsigned long long *costs, unsigned long long *tiles) {
+    StackCostTask T;
+    if (!srcs || !cap_bytes || !pitches || !steps || !costs || !debug_stack_cost_task(T, count, rows, cols, format, scale, bias)) return -1;
+    std::vector<StackCostSlice> slices(static_cast<size_t>(count));
+    std::vector<unsigned long long> caps(static_cast<size_t>(count));
+    for (int d = 0; d < count; d++) {
+        if (steps[d] > 0xFFFFFFFFull) return -1;
+        slices[size_t(d)] = StackCostSlice{static_cast<const uint8_t *>(srcs[d]), pitches[d], uint32_t(steps[d]), 0u};
+        caps[size_t(d)] = cap_bytes[d];
+    }
+    T.costs = costs;
+    if (!stack_cost_task_ok(T, slices.data(), caps.data())) return -1;
+    if (tiles) *tiles = stack_task_tiles(T);
+    for (int k = 0; k < 2 * count; k++) costs[k] = 0;
+    stack_cost_host(T, slices.data());
+    return 0;
+}
+
+// ONE k_stack_cost launch over n caller-made stacks as n tasks.  Stack k has counts[k] sources; srcs / src_bytes /
+// base_offsets / pitches / steps have one entry per source, the stacks' one after the other, each source uploaded at byte
+// base_offsets[] (0 .. 255) of a region of its own filled with 0xFF that is larger.  costs: two sums per source.
+// -1: refused; -2: a HIP call failed.
+int nblic_amd_debug_stack_cost(nblic_amd_ctx *c, int n, const int *counts, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets,
+                               const size_t *pitches, const size_t *steps, const int *rows, const int *cols, const int *formats,
+                               const float *scales, const float *biases, unsigned long long *costs) {
+    constexpr int kMaxTasks = 65536;
+    if (!c || n < 1 || n > kMaxTasks || !counts || !srcs || !src_bytes || !base_offsets || !pitches || !steps || !rows || !cols || !formats || !scales || !biases || !costs) return -1;
+    const size_t count = size_t(n);
+    std::vector<StackCostTask> tasks(count);
+    std::vector<StackCostSlice> slices;
+    std::vector<size_t> src_at;
+    size_t srcs_total = 0;
+    for (size_t i = 0; i < count; i++) {
+        if (!debug_stack_cost_task(tasks[i], counts[i], rows[i], cols[i], formats[i], scales[i], biases[i]) || slices.size() + size_t(counts[i]) > (size_t(1) << 20)) return -1;
+        tasks[i].first_slice = uint32_t(slices.size());
+        for (int d = 0; d < counts[i]; d++) {
+            const size_t s = slices.size();
+            if (!srcs[s] || base_offsets[s] > 255 || src_bytes[s] > (size_t(1) << 30) || steps[s] > 0xFFFFFFFFull) return -1;
+            src_at.push_back(srcs_total); srcs_total += up256(base_offsets[s] + src_bytes[s] + 256);
+            slices.push_back(StackCostSlice{nullptr, pitches[s], uint32_t(steps[s]), 0u});
+        }
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    Stream st;
+    DevPool mem;
+    uint8_t *d_srcs = mem.make<uint8_t>(srcs_total);
+    unsigned long long *d_costs = mem.make<unsigned long long>(slices.size() * 2);
+    StackCostTask *d_tasks = mem.make<StackCostTask>(count);
+    StackCostSlice *d_slices = mem.make<StackCostSlice>(slices.size());
+    if (!d_srcs || !d_costs || !d_tasks || !d_slices || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    for (size_t i = 0; i < count; i++) {                                 // the addresses are known now: the rest of the checks
+        StackCostTask &T = tasks[i];
+        std::vector<unsigned long long> caps(T.count);
+        for (uint32_t d = 0; d < T.count; d++) {
+            const size_t s = T.first_slice + d;
+            slices[s].src = d_srcs + src_at[s] + base_offsets[s]; caps[d] = src_bytes[s];
+        }
+        T.costs = d_costs + size_t(T.first_slice) * 2;
+        if (!stack_cost_task_ok(T, slices.data(), caps.data())) return -1;      // nothing outside the uploaded bytes is the task's to read
+    }
+    const bool ok = [&]() -> bool {
+        HIP_OK(hipMemsetAsync(d_srcs, 0xFF, srcs_total, st));
+        HIP_OK(hipMemsetAsync(d_costs, 0, slices.size() * 2 * sizeof(unsigned long long), st));
+        for (size_t s = 0; s < slices.size(); s++) HIP_OK(hipMemcpyAsync(d_srcs + src_at[s] + base_offsets[s], srcs[s], src_bytes[s], hipMemcpyHostToDevice, st));
+        if (!stack_cost_queue(c, tasks.data(), count, slices.data(), slices.size(), d_tasks, d_slices, st)) return false;
+        HIP_OK(hipMemcpyAsync(costs, d_costs, slices.size() * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    return ok ? 0 : -2;
+}
+
+// A debug run's task and slice records: all but the addresses.  window: row0, row1, col0, col1 of planes of plane_rows x
+// width; per slice a scale, a bias, a zero flag, a pitch and a step (0: the element size).  false: an argument no task can hold.
+static bool debug_stack_run(StackDeliverTask &R, StackSlice *S, int count, int plane_rows, int width, const int *window, int format, const float *scales,
+                            const float *biases, const int *zeros, const size_t *pitches, const size_t *steps) {
+    R = StackDeliverTask{};
+    if (count < 1 || count > 65536 || plane_rows < 1 || width < 1 || !window || format < 0 || format >= int(kDeliverFormats)) return false;
+    if (window[0] < 0 || window[1] <= window[0] || window[1] > plane_rows || window[2] < 0 || window[3] <= window[2] || window[3] > width) return false;
+    R.count = uint32_t(count); R.rows = uint32_t(window[1] - window[0]); R.col0 = uint32_t(window[2]); R.col1 = uint32_t(window[3]);
+    R.src_pitch = uint32_t(width); R.format = uint32_t(format);
+    for (int d = 0; d < count; d++) {
+        if (!deliver_args_ok(format, scales[d], biases[d]) || steps[d] > kDeliverMaxStep || pitches[d] > (size_t(1) << 40)) return false;
+        S[d] = StackSlice{};
+        S[d].scale = scales[d]; S[d].bias = biases[d]; S[d].zero = zeros[d] ? 1u : 0u;
+        S[d].dst_pitch = pitches[d]; S[d].dst_step = steps[d] ? uint32_t(steps[d]) : deliver_elem(R.format);
+    }
+    return true;
+}
+// Does slice S of run R, with a destination, stay inside the out_bytes - dst_offset bytes behind it?
+static bool debug_stack_fits(const StackDeliverTask &R, const StackSlice &S, size_t out_bytes, size_t dst_offset) {
+    return dst_offset <= out_bytes && deliver_extent(R.rows, R.col1 - R.col0, R.format, S.dst_pitch, S.dst_step) <= out_bytes - dst_offset;
+}
+
+// Host only: the shared walk (stack.h stack_deliver_host) over ONE run of `count` caller-made planes of plane_rows x width
+// bytes each; slice d goes to outs[d] + dst_offsets[d] (outs[d] NULL: a skipped slice), gate_status[d] stands for its gate
+// (-1: none).  units / chunks: what a launch would count for the task.  -1: refused.
+int nblic_amd_debug_stack_deliver_host(int count, const unsigned char *const *planes, int plane_rows, int width, const int *window, int format,
+                                       const float *scales, const float *biases, const int *zeros, const int *gate_status, unsigned char *const *outs,
+                                       const size_t *out_bytes, const size_t *dst_offsets, const size_t *pitches, const size_t *steps,
+                                       unsigned long long *units, unsigned long long *chunks) {
+    if (!planes || !scales || !biases || !zeros || !gate_status || !outs || !out_bytes || !dst_offsets || !pitches || !steps || count < 1 || count > 65536) return -1;
+    StackDeliverTask R;
+    std::vector<StackSlice> S(static_cast<size_t>(count));
+    if (!debug_stack_run(R, S.data(), count, plane_rows, width, window, format, scales, biases, zeros, pitches, steps)) return -1;
+    std::vector<int> gates(static_cast<size_t>(count));
+    const size_t skip = size_t(window[0]) * size_t(width);
+    for (int d = 0; d < count; d++) {
+        if (!planes[d]) return -1;
+        S[size_t(d)].src = planes[d] + skip; S[size_t(d)].src_bytes = size_t(plane_rows) * size_t(width) - skip;
+        if (outs[d]) {
+            if (!debug_stack_fits(R, S[size_t(d)], out_bytes[d], dst_offsets[d])) return -1;
+            S[size_t(d)].dst = outs[d] + dst_offsets[d];
+        }
+        gates[size_t(d)] = gate_status[d] == -1 ? int(kDone) : gate_status[d];
+    }
+    if (!stack_task_ok(R, S.data())) return -1;
+    if (units) *units = stack_task_units(R);
+    if (chunks) *chunks = stack_task_chunks(R);
+    stack_deliver_host(R, S.data(), gates.data());
+    return 0;
+}
+
+// ONE k_deliver_stack launch over n caller-made runs as n tasks.  Run k has counts[k] planes of plane_rows[k] x widths[k]
+// bytes; planes / base_offsets / scales / biases / zeros / pitches / steps / dst_offsets / out_bytes / outs / gate_status have
+// one entry per plane, the runs' one after the other.  A plane is uploaded at byte base_offsets[] (0 .. 15) of a zeroed
+// region that is larger and may be read for up256(rows * width) bytes, as the decoders' planes allow; a destination lies at
+// byte dst_offsets[] of a buffer of out_bytes[] bytes filled with 0x5A, which comes back whole in outs[] (NULL: a skipped
+// slice); gate_status[] != -1 is put into a SerialState on the device, the slice's gate.  -1: refused; -2: a HIP call failed.
+int nblic_amd_debug_stack_deliver(nblic_amd_ctx *c, int n, const int *counts, const unsigned char *const *planes, const size_t *base_offsets,
+                                  const int *plane_rows, const int *widths, const int *windows, const int *formats, const float *scales, const float *biases,
+                                  const int *zeros, const size_t *pitches, const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes,
+                                  unsigned char *const *outs, const int *gate_status) {
+    constexpr int kMaxTasks = 65536;
+    constexpr uint8_t kPattern = 0x5A;
+    if (!c || n < 1 || n > kMaxTasks || !counts || !planes || !base_offsets || !plane_rows || !widths || !windows || !formats || !scales || !biases ||
+        !zeros || !pitches || !steps || !dst_offsets || !out_bytes || !outs || !gate_status) return -1;
+    const size_t count = size_t(n);
+    size_t total = 0;
+    for (size_t i = 0; i < count; i++) { if (counts[i] < 1 || counts[i] > 65536) return -1; total += size_t(counts[i]); }
+    if (total > (size_t(1) << 20)) return -1;
+    std::vector<StackDeliverTask> runs(count);
+    std::vector<StackSlice> S(total);
+    std::vector<size_t> plane_at(total), out_at(total), plane_len(total);
+    size_t planes_total = 0, outs_total = 0, s0 = 0;
+    for (size_t i = 0; i < count; i++) {
+        if (!debug_stack_run(runs[i], S.data() + s0, counts[i], plane_rows[i], widths[i], windows + 4 * i, formats[i], scales + s0, biases + s0, zeros + s0, pitches + s0, steps + s0)) return -1;
+        runs[i].first_slice = uint32_t(s0);
+        const size_t bytes = size_t(plane_rows[i]) * size_t(widths[i]);
+        if (bytes > (size_t(1) << 30)) return -1;
+        for (size_t s = s0; s < s0 + size_t(counts[i]); s++) {
+            if (!planes[s] || base_offsets[s] > 15 || out_bytes[s] > (size_t(1) << 30)) return -1;
+            if (outs[s] && !debug_stack_fits(runs[i], S[s], out_bytes[s], dst_offsets[s])) return -1;
+            plane_len[s] = bytes;
+            plane_at[s] = planes_total; planes_total += up256(base_offsets[s] + up256(bytes) + 16);
+            out_at[s] = outs_total; outs_total += up256(outs[s] ? out_bytes[s] : 0);
+        }
+        s0 += size_t(counts[i]);
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    Stream st;
+    DevPool mem;
+    uint8_t *d_planes = mem.make<uint8_t>(planes_total), *d_outs = mem.make<uint8_t>(std::max<size_t>(outs_total, 256));
+    SerialState *d_gates = mem.make<SerialState>(total);
+    StackDeliverTask *d_runs = mem.make<StackDeliverTask>(count);
+    StackSlice *d_slices = mem.make<StackSlice>(total);
+    if (!d_planes || !d_outs || !d_gates || !d_runs || !d_slices || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    for (size_t i = 0; i < count; i++) {                                 // the addresses are known now: the rest of the checks
+        const size_t skip = size_t(windows[4 * i]) * size_t(widths[i]);
+        for (size_t s = runs[i].first_slice; s < size_t(runs[i].first_slice) + runs[i].count; s++) {
+            S[s].src = d_planes + plane_at[s] + base_offsets[s] + skip; S[s].src_bytes = up256(plane_len[s]) - skip;
+            if (outs[s]) S[s].dst = d_outs + out_at[s] + dst_offsets[s];
+            if (gate_status[s] != -1) S[s].gate = d_gates + s;
+        }
+        if (!stack_task_ok(runs[i], S.data())) return -1;
+    }
+    std::vector<uint8_t> back(std::max<size_t>(outs_total, 1));
+    std::vector<SerialState> gates(total);
+    for (size_t s = 0; s < total; s++) gates[s].status = gate_status[s];
+    const bool ok = [&]() -> bool {
+        HIP_OK(hipMemsetAsync(d_planes, 0, planes_total, st));
+        HIP_OK(hipMemsetAsync(d_outs, kPattern, std::max<size_t>(outs_total, 256), st));
+        HIP_OK(hipMemcpyAsync(d_gates, gates.data(), total * sizeof(SerialState), hipMemcpyHostToDevice, st));
+        for (size_t s = 0; s < total; s++) HIP_OK(hipMemcpyAsync(d_planes + plane_at[s] + base_offsets[s], planes[s], plane_len[s], hipMemcpyHostToDevice, st));
+        c->stack_counts[2] += 1; c->stack_counts[3] += long(count);
+        unsigned long long chunks = 0;
+        if (!deliver_stack_upload(runs.data(), count, S.data(), total, d_runs, d_slices, st, chunks) || !deliver_stack_launch(d_runs, n, d_slices, uint32_t(chunks), st)) return false;
+        if (outs_total) HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    if (!ok) return -2;
+    for (size_t s = 0; s < total; s++) if (outs[s]) memcpy(outs[s], back.data() + out_at[s], out_bytes[s]);
+    return 0;
+}
+
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
 
 int nblic_amd_copy_stats(nblic_amd_ctx *c, long out[4]) {
@@ -5603,10 +6111,12 @@ int nblic_amd_decode_batch_to(nblic_amd_ctx *c, int n_images, const unsigned cha
     return nblic_amd_decode_batch_to_ex(c, n_images, streams, stream_lens, ex.data(), format, heights, widths, nears, efforts, status);
 }
 static int decode_batch_to_modes(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens, const nblic_amd_dest_ex *dests,
-                                 int format, const uint8_t *modes, int *heights, int *widths, int *nears, int *efforts, int *status) {
+                                 int format, const uint8_t *modes, int *heights, int *widths, int *nears, int *efforts, int *status, const StackArg *stack = nullptr) {
     if (!c || c->broken || n_images < 0 || !streams || !stream_lens || !dests || !heights || !widths || !nears || !efforts || !status || format < 0 || format >= int(kDeliverFormats)) return -1;
     for (int k = 0; k < n_images; k++) if (!streams[k]) return -1;
-    const DeliverTo to{dests, uint32_t(format), modes};
+    if (stack && !stack_modes_ok(n_images, stack->depth, stack->modes)) return -1;
+    DeliverTo to{dests, uint32_t(format), modes};
+    if (stack) { to.slice_modes = stack->modes; to.depth = stack->depth; }
     std::lock_guard<std::mutex> g(c->api);
     deliver_stats_reset(c);
     if (!decode_batch(c, n_images, streams, stream_lens, nullptr, nullptr, heights, widths, nears, efforts, status, &to)) return -1;
@@ -5761,8 +6271,23 @@ int nblic_amd_decode_batch_to_ex_color(nblic_amd_ctx *c, int n_images, const uns
 // ---- ENCODE FROM DEVICE MEMORY: the four batch encoders on sources instead of planes ------------------------------------------
 // What every _from call starts with: the whole-call refusals, then the sources checked one by one (collect_plan).
 // frame_modes: the _color calls' (one valid byte per frame); NULL: none but what NBLIC_AMD_FORMAT_RCT in `format` says.
+// stack: the _stack calls' depth and slice modes (StackArg, beside DeliverTo), which do not go with colour frames.
+// The near rule of a _stack call: near > 0 only on a key slice whose successor in the stack, if any, is a key slice too (a
+// plane off by +-near would wrap in the difference, and would drift along the run).
+static bool stack_nears_ok(int n, const StackArg &stack, const int *nears) {
+    if (!nears) return true;
+    for (int k = 0; k < n; k++) {
+        if (nears[k] <= 0) continue;
+        if (stack.modes[k] != kStackKey || ((k + 1) % stack.depth != 0 && stack.modes[k + 1] != kStackKey)) return false;
+    }
+    return true;
+}
 static bool collect_from_begin(nblic_amd_ctx *c, int n, const nblic_amd_src *srcs, int format, float scale, float bias, CollectFrom &from,
-                               const unsigned char *frame_modes = nullptr) {
+                               const unsigned char *frame_modes = nullptr, const StackArg *stack = nullptr) {
+    if (stack) {
+        if (frame_modes || format < 0 || format >= int(kCollectFormats) || !stack_modes_ok(n, stack->depth, stack->modes)) return false;
+        from.slice_modes.assign(stack->modes, stack->modes + n); from.depth = stack->depth;
+    }
     if (frame_modes) {
         if (!color_modes_ok(n, frame_modes)) return false;
         from.modes.assign(frame_modes, frame_modes + n / 3);
@@ -5778,13 +6303,14 @@ static bool collect_from_begin(nblic_amd_ctx *c, int n, const nblic_amd_src *src
 
 static int encode_batch_modes_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
                                    const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
-                                   unsigned char *const *recons, const unsigned char *frame_modes) {
+                                   unsigned char *const *recons, const unsigned char *frame_modes, const StackArg *stack = nullptr) {
     CollectFrom from{};
+    if (stack && (!stack_modes_ok(n_images, stack->depth, stack->modes) || !stack_nears_ok(n_images, *stack, nears))) return -1;
     if (format >= 0 && (format & NBLIC_AMD_FORMAT_RCT) && !frame_modes && nears)         // a difference plane off by +-near wraps to +-255 in R or B
         for (int k = 0; k < n_images; k++) if (nears[k] > 0) return -1;
     if (frame_modes && nears && color_modes_ok(n_images, frame_modes))   // the same, frame by frame: mode 0 has no difference plane
         for (int k = 0; k < n_images; k++) if (nears[k] > 0 && frame_modes[k / 3] != kColorPlain) return -1;
-    if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from, frame_modes)) return -1;
+    if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from, frame_modes, stack)) return -1;
     const bool ok = run_batch(c, nblic_amd_ctx::SubmitItem{nullptr, 0, n_images, from.imgs.data(), true, from.hs.data(), from.ws.data(), outs, out_caps, out_lens, nears, efforts, recons, &from});
     if (nothing_outstanding(c)) for (auto &g : c->groups) collect_timing(c, g);       // (nblic_amd_stage_times, as nblic_amd_encode_batch leaves them)
     return ok ? 0 : -1;
@@ -5816,9 +6342,10 @@ int nblic_amd_encode_batch_modes_from_to(nblic_amd_ctx *c, int n_images, const n
     return ok ? 0 : -1;
 }
 static int qencode_batch_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
-                              uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words, const unsigned char *frame_modes) {
+                              uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words, const unsigned char *frame_modes,
+                              const StackArg *stack = nullptr) {
     CollectFrom from{};
-    if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from, frame_modes)) return -1;
+    if (!collect_from_begin(c, n_images, srcs, format, scale, bias, from, frame_modes, stack)) return -1;
     return run_batch(c, nblic_amd_ctx::SubmitItem{nullptr, 1, n_images, from.imgs.data(), true, from.hs.data(), from.ws.data(), reinterpret_cast<unsigned char *const *>(outs),
                                                   out_caps_words, out_len_words, nullptr, nullptr, nullptr, &from}) ? 0 : -1;
 }
@@ -5834,9 +6361,9 @@ int nblic_amd_qencode_batch_from_color(nblic_amd_ctx *c, int n_images, const nbl
 extern "C++" template <class Out>
 static int indexed_batch_from(const IdxCodec &F, nblic_amd_ctx *c, int n, const nblic_amd_src *srcs, int format, float scale, float bias, const int *every, int band_rows,
                               Out *const *outs, const size_t *caps, long *lens, unsigned char *const *indexes, const size_t *icaps, long *ilens,
-                              const unsigned char *frame_modes = nullptr) {
+                              const unsigned char *frame_modes = nullptr, const StackArg *stack = nullptr) {
     CollectFrom from{};
-    if (n < 1 || !collect_from_begin(c, n, srcs, format, scale, bias, from, frame_modes)) return -1;
+    if (n < 1 || !collect_from_begin(c, n, srcs, format, scale, bias, from, frame_modes, stack)) return -1;
     return indexed_batch(F, c, n, from.imgs.data(), true, from.hs.data(), from.ws.data(), every, band_rows, outs, caps, lens, indexes, icaps, ilens, &from);
 }
 int nblic_amd_encode_batch_indexed_from(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
@@ -5862,6 +6389,31 @@ int nblic_amd_qencode_batch_indexed_from_color(nblic_amd_ctx *c, int n_images, c
                                                long *index_lens) {
     if (!frame_modes || format < 0 || format >= int(kCollectFormats)) return -1;
     return indexed_batch_from(kIdxQnblic, c, n_images, srcs, format, scale, bias, every_rows, band_rows, outs, out_caps_words, out_len_words, indexes, index_caps, index_lens, frame_modes);
+}
+// The _stack siblings of the four _from encoders (stack.h): image s * depth + d is slice d of stack s, coded in slice_modes[].
+int nblic_amd_encode_batch_modes_from_stack(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                            int depth, const unsigned char *slice_modes, const int *nears, const int *efforts, unsigned char *const *outs,
+                                            const size_t *out_caps, long *out_lens, unsigned char *const *recons) {
+    const StackArg stack{depth, slice_modes};
+    return encode_batch_modes_from(c, n_images, srcs, format, scale, bias, nears, efforts, outs, out_caps, out_lens, recons, nullptr, &stack);
+}
+int nblic_amd_qencode_batch_from_stack(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                       int depth, const unsigned char *slice_modes, uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words) {
+    const StackArg stack{depth, slice_modes};
+    return qencode_batch_from(c, n_images, srcs, format, scale, bias, outs, out_caps_words, out_len_words, nullptr, &stack);
+}
+int nblic_amd_encode_batch_indexed_from_stack(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                              int depth, const unsigned char *slice_modes, const int *every_rows, int band_rows, unsigned char *const *outs,
+                                              const size_t *out_caps, long *out_lens, unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
+    const StackArg stack{depth, slice_modes};
+    return indexed_batch_from(kIdxNblic, c, n_images, srcs, format, scale, bias, every_rows, band_rows, outs, out_caps, out_lens, indexes, index_caps, index_lens, nullptr, &stack);
+}
+int nblic_amd_qencode_batch_indexed_from_stack(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
+                                               int depth, const unsigned char *slice_modes, const int *every_rows, int band_rows, uint16_t *const *outs,
+                                               const size_t *out_caps_words, long *out_len_words, unsigned char *const *indexes, const size_t *index_caps,
+                                               long *index_lens) {
+    const StackArg stack{depth, slice_modes};
+    return indexed_batch_from(kIdxQnblic, c, n_images, srcs, format, scale, bias, every_rows, band_rows, outs, out_caps_words, out_len_words, indexes, index_caps, index_lens, nullptr, &stack);
 }
 
 long nblic_amd_debug_q_entropy(int height, int width, const uint16_t *words, const unsigned int *hist, const int *entry_rows, int n_entries,
@@ -5906,6 +6458,21 @@ int nblic_amd_decode_batch_indexed_to_ex(nblic_amd_ctx *c, int n_images, const u
     if (!dests || format < 0 || format >= int(kDeliverFormats) || (rct && (n_images < 0 || n_images % 3 != 0))) return -1;
     const std::vector<uint8_t> modes = rct_modes(rct ? n_images : 0);
     const DeliverTo to{dests, uint32_t(format), rct ? modes.data() : nullptr};
+    deliver_stats_reset(c);
+    return decode_batch_indexed(c, n_images, streams, stream_lens, indexes, index_lens, nullptr, nullptr, nullptr, nullptr, heights, widths, nears, efforts, status, &to);
+}
+// The _stack siblings of the two _to_ex decoders (stack.h).
+int nblic_amd_decode_batch_to_ex_stack(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens, const nblic_amd_dest_ex *dests,
+                                       int format, int depth, const unsigned char *slice_modes, int *heights, int *widths, int *nears, int *efforts, int *status) {
+    const StackArg stack{depth, slice_modes};
+    return decode_batch_to_modes(c, n_images, streams, stream_lens, dests, format, nullptr, heights, widths, nears, efforts, status, &stack);
+}
+int nblic_amd_decode_batch_indexed_to_ex_stack(nblic_amd_ctx *c, int n_images, const unsigned char *const *streams, const size_t *stream_lens,
+                                               const void *const *indexes, const size_t *index_lens, const nblic_amd_dest_ex *dests, int format,
+                                               int depth, const unsigned char *slice_modes, int *heights, int *widths, int *nears, int *efforts, int *status) {
+    if (!dests || format < 0 || format >= int(kDeliverFormats) || !stack_modes_ok(n_images, depth, slice_modes)) return -1;
+    DeliverTo to{dests, uint32_t(format)};
+    to.slice_modes = slice_modes; to.depth = depth;
     deliver_stats_reset(c);
     return decode_batch_indexed(c, n_images, streams, stream_lens, indexes, index_lens, nullptr, nullptr, nullptr, nullptr, heights, widths, nears, efforts, status, &to);
 }

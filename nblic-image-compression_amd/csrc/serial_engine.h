@@ -21,6 +21,7 @@
 #include "deliver.h"
 #include "collect.h"
 #include "color_plan.h"
+#include "stack.h"
 
 namespace nblic {
 
@@ -213,6 +214,17 @@ bool collect_launch(const CollectTask *d_tasks, int n, uint32_t chunks, hipStrea
 // not depend on the launch's geometry or order.  The costs are zeroed by the caller.  d_tasks[0..n) with first_chunk
 // filled in (from 0), `tiles` their sum.  false: the launch failed.
 bool color_cost_launch(const ColorCostTask *d_tasks, int n, uint32_t tiles, hipStream_t s);
+
+// ---- slice stacks (stack.h) ---------------------------------------------------------------------------------------------------
+// k_deliver_stack, beside k_deliver: one task is one RUN -- a key slice and the delta slices behind it -- with its slices in
+// d_slices.  A lane walks the run's slices for its unit of sixteen window pixels with the running pixels in registers, so
+// no task waits for another one's output and every plane byte of the window is read once.  d_tasks[0..n) with first_chunk
+// filled in (from 0), `chunks` their sum.  false: the launch failed.
+bool deliver_stack_launch(const StackDeliverTask *d_tasks, int n, const StackSlice *d_slices, uint32_t chunks, hipStream_t s);
+// k_stack_cost, beside k_color_cost: one task is one STACK with its sources in d_slices, one workgroup per tile position.
+// The workgroup walks the slices with two LDS tile buffers and adds two sums per slice -- the slice's own cost and that of
+// its difference against the slice before -- to the task's costs (zeroed by the caller) with 64-bit atomics.
+bool stack_cost_launch(const StackCostTask *d_tasks, int n, const StackCostSlice *d_slices, uint32_t tiles, hipStream_t s);
 
 // ---- a packed index (index_pack.h), expanded on the device ------------------------------------------------------------------
 // A packed index is uploaded as it is (any address).  The bodies of the entries a round needs are written, unpacked, into an

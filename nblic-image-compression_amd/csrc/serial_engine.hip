@@ -2086,6 +2086,138 @@ bool color_cost_launch(const ColorCostTask *d_tasks, int n, uint32_t tiles, hipS
     return hipGetLastError() == hipSuccess;
 }
 
+// ---- slice stacks: the delivery of a run of differences, and the two costs of a slice (stack.h) ---------------------------------
+// One workgroup per chunk of kDeliverChunkUnits units, one unit per lane and step: sixteen consecutive window pixels of one
+// row.  The lane walks the run's slices for its unit with the running pixels in four words: it loads each plane's sixteen
+// bytes (deliver_load), adds them bytewise to what it carries (stack.h stack_restore4) and stores into every slice that has a
+// destination -- whole 16-byte blocks where stack_wide_store allows them, element by element otherwise.  A slice whose
+// plane, or a plane in front of it in the run, is not kDone gets zeros, and so does every later one; their planes are not
+// read.  No LDS, no atomics; every plane byte of the window is read once, nothing outside the readable bytes is read and
+// nothing outside the windows written.
+__global__ void __launch_bounds__(kIndexThreads) k_deliver_stack(const StackDeliverTask *__restrict__ tasks, int n, const StackSlice *__restrict__ slices) {
+    const StackDeliverTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
+    const DeliverTask W = stack_window(T);
+    const uint32_t units = uint32_t(stack_task_units(T)), u0 = (blockIdx.x - T.first_chunk) * kDeliverChunkUnits;
+    const uint32_t elem = deliver_elem(T.format);
+    for (uint32_t j = threadIdx.x; j < kDeliverChunkUnits; j += kIndexThreads) {
+        const uint32_t u = u0 + j;
+        if (u >= units) break;
+        const DeliverUnit U = deliver_strided_unit_of(W, u);
+        const uint32_t k_hi = U.c_hi - U.c_lo;
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        bool ok = true;
+        for (uint32_t d = 0; d < T.count; d++) {
+            const StackSlice S = slices[T.first_slice + d];
+            ok = ok && !S.zero && (!S.gate || gp(S.gate)->status == kDone);
+            if (ok) {
+                const u32x4 t = deliver_load(gp(S.src) + size_t(U.row) * T.src_pitch + size_t(T.col0) + U.c_lo, uintptr_t(S.src), uintptr_t(S.src) + S.src_bytes, 0u, k_hi);
+                const uint32_t tw[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+                for (uint32_t b = 0; b < 4; b++) w[b] = d == 0 ? tw[b] : stack_restore4(tw[b], w[b]);
+            }
+            if (!S.dst) continue;
+            const bool zero = !ok;
+            NB_GLOBAL uint8_t *o = gp(S.dst) + size_t(U.row) * size_t(S.dst_pitch) + size_t(U.c_lo) * size_t(S.dst_step);
+            auto pixel = [&](uint32_t k) { return zero ? 0u : (w[k >> 2] >> ((k & 3) * 8)) & 0xFFu; };
+            if (stack_wide_store(S, elem, U.row, U.c_lo, U.c_hi)) {
+                switch (T.format) {                                          // (zero: +0.0 is zero bytes in every format)
+                    case kDeliverU8: deliver_store<1>(o, 0u, 16u, pixel); break;
+                    case kDeliverF16: deliver_store<2>(o, 0u, 16u, [&](uint32_t k) { return zero ? 0u : deliver_value(pixel(k), kDeliverF16, S.scale, S.bias); }); break;
+                    case kDeliverBF16: deliver_store<2>(o, 0u, 16u, [&](uint32_t k) { return zero ? 0u : deliver_value(pixel(k), kDeliverBF16, S.scale, S.bias); }); break;
+                    default: deliver_store<4>(o, 0u, 16u, [&](uint32_t k) { return zero ? 0u : deliver_value(pixel(k), kDeliverF32, S.scale, S.bias); }); break;
+                }
+                continue;
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 16; k++) {
+                if (k >= k_hi) continue;
+                const uint32_t v = zero ? 0u : deliver_value(pixel(k), T.format, S.scale, S.bias);
+                NB_GLOBAL uint8_t *e = o + size_t(k) * size_t(S.dst_step);
+                if (elem == 1) *e = uint8_t(v);
+                else if (elem == 2) *(NB_GLOBAL uint16_t *)e = uint16_t(v);
+                else *(NB_GLOBAL uint32_t *)e = v;
+            }
+        }
+    }
+}
+
+bool deliver_stack_launch(const StackDeliverTask *d_tasks, int n, const StackSlice *d_slices, uint32_t chunks, hipStream_t s) {
+    if (n <= 0 || chunks == 0) return true;
+    hipLaunchKernelGGL(k_deliver_stack, dim3(chunks), dim3(kIndexThreads), 0, s, d_tasks, n, d_slices);
+    return hipGetLastError() == hipSuccess;
+}
+
+// One workgroup per tile POSITION of one stack: it walks the stack's slices with two LDS tile buffers, the slice before and
+// the current one, swapped by index, each laid out like k_color_cost's (the row above, the column to the left).  STAGE: as
+// k_color_cost, through collect_unit_load -- every source element is converted once apart from the halo, nothing outside the
+// image is read.  COST: a lane per column, a wave per sixteen rows, top down; the slice's own cost and that of its
+// difference against the buffer of the slice before (stack.h stack_pixel_costs).  SUM: wave shuffles, the four waves in
+// LDS, then two 64-bit atomic adds per slice.
+__global__ void __launch_bounds__(kIndexThreads) k_stack_cost(const StackCostTask *__restrict__ tasks, int n, const StackCostSlice *__restrict__ slices) {
+    __shared__ uint32_t lds[2 * kColorLdsRows * kColorLdsPitch / 4];
+    __shared__ uint32_t part[kIndexThreads / 64][2];
+    const StackCostTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
+    const uint32_t rows = T.rows, cols = T.cols;
+    CollectTask C{};                                                 // what the loader reads of a task: the format, the quantisation, the width
+    C.format = T.format; C.scale = T.scale; C.bias = T.bias; C.rows = rows; C.cols = cols;
+    const uint32_t across = stack_tiles_across(T), tile = blockIdx.x - T.first_chunk;
+    const uint32_t y0 = (tile / across) * kColorTile, x0 = (tile % across) * kColorTile;
+    uint8_t *bytes = reinterpret_cast<uint8_t *>(lds);
+    const uint32_t wave = threadIdx.x / 64u, lane = threadIdx.x % 64u, x = x0 + lane;
+    for (uint32_t d = 0; d < T.count; d++) {
+        const StackCostSlice S = slices[T.first_slice + d];
+        const uint32_t cur = d & 1u, prv = cur ^ 1u;
+        // LDS row r of a buffer holds image row y0 + r - 1
+        for (uint32_t j = threadIdx.x; j < kColorLdsRows * kColorRowUnits; j += kIndexThreads) {
+            const uint32_t r = j / kColorRowUnits, q = j % kColorRowUnits;
+            const uint32_t y = y0 + r - 1u, xx = x0 + q * kCollectUnitPixels;
+            if ((r == 0 && y0 == 0) || y >= rows || xx >= cols) continue;
+            uint32_t word[4];
+            collect_unit_load(C, gp(S.src), S.pitch, S.step, y, xx, 0u, cols - xx < 16u ? cols - xx : 16u, word);
+            uint32_t *o = lds + ((cur * kColorLdsRows + r) * kColorLdsPitch + 4u + q * kCollectUnitPixels) / 4u;
+#pragma unroll
+            for (int i = 0; i < 4; i++) o[i] = word[i];
+        }
+        if (x0 > 0 && threadIdx.x < kColorLdsRows) {
+            const uint32_t r = threadIdx.x, y = y0 + r - 1u;
+            if (!(r == 0 && y0 == 0) && y < rows) {
+                uint32_t word[4];
+                collect_unit_load(C, gp(S.src), S.pitch, S.step, y, x0 - 1u, 0u, 1u, word);
+                bytes[(cur * kColorLdsRows + r) * kColorLdsPitch + 3u] = uint8_t(word[0]);
+            }
+        }
+        __syncthreads();
+        uint32_t intra = 0u, delta = 0u;
+        if (x < cols) {
+            const uint32_t r0 = wave * 16u;                          // the wave's first tile row; LDS row r0 is the one above it
+            const uint8_t *a = bytes + (cur * kColorLdsRows + r0) * kColorLdsPitch + 3u + lane;
+            const uint8_t *b = bytes + (prv * kColorLdsRows + r0) * kColorLdsPitch + 3u + lane;
+            uint32_t nw = a[0], nn = a[1], pnw = b[0], pn = b[1];    // (row 0 or column 0 of the image: never looked at)
+            for (uint32_t r = r0; r < r0 + 16u && y0 + r < rows; r++) {
+                a += kColorLdsPitch; b += kColorLdsPitch;
+                const uint32_t w = a[0], p = a[1], pw = b[0], pp = b[1];
+                stack_pixel_costs(p, w, nn, nw, pp, pw, pn, pnw, d > 0, y0 + r, x, intra, delta);
+                nn = p; nw = w; pn = pp; pnw = pw;
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { intra += __shfl_down(intra, off, 64); delta += __shfl_down(delta, off, 64); }      // (at most 16 x 17 a lane)
+        if (lane == 0) { part[wave][0] = intra; part[wave][1] = delta; }
+        __syncthreads();                                             // every lane is done with the buffer of the slice before: the next slice goes there
+        if (threadIdx.x < 2) {
+            unsigned long long total = 0;
+            for (uint32_t wv = 0; wv < kIndexThreads / 64; wv++) total += part[wv][threadIdx.x];
+            atomicAdd(T.costs + 2u * d + threadIdx.x, total);
+        }
+    }
+}
+
+bool stack_cost_launch(const StackCostTask *d_tasks, int n, const StackCostSlice *d_slices, uint32_t tiles, hipStream_t s) {
+    if (n <= 0 || tiles == 0) return true;
+    hipLaunchKernelGGL(k_stack_cost, dim3(tiles), dim3(kIndexThreads), 0, s, d_tasks, n, d_slices);
+    return hipGetLastError() == hipSuccess;
+}
+
 
 // ---- a packed index, expanded on the device (serial_engine.h IndexUnpackTask; the format: index_pack.h) --------------------
 constexpr uint32_t kUnpackWaves = kIndexThreads / 64;
