@@ -1233,6 +1233,106 @@ int nblic_amd_debug_stack_cost(nblic_amd_ctx *ctx, int n, const int *counts, con
                                const size_t *pitches, const size_t *steps, const int *rows, const int *cols, const int *formats,
                                const float *scales, const float *biases, unsigned long long *costs);
 
+/* DEEP PIXELS: an image of 16-bit elements -- uint16, or int16 such as Hounsfield units -- coded as TWO ordinary 8-bit
+ * images, a HIGH and a LOW plane (csrc/deep.h).  With u the element as an unsigned 16-bit number
+ * (uint16: u = x; int16: u = x + 32768, the sign bit flipped): hi = u >> 8, lo = u & 255.
+ *   streams       a call on n_deep images has 2 x n_deep streams: stream 2k is the HIGH plane of deep image k, stream 2k + 1
+ *                 its LOW plane.  Every per-stream array (outs, caps, lens, nears, efforts, every_rows, indexes, status,
+ *                 heights, ...) has 2 x n_deep entries; srcs, dests and modes have n_deep.  There is no container and no new
+ *                 stream format: each stream and index is byte for byte what the call without _deep returns for that 8-bit
+ *                 plane, and a plain decoder -- the reference tool included -- gets the two planes back.
+ *   modes         one byte per deep image, which the CALLER keeps with the image's two streams (nothing in them names it).
+ *                 Bit 0 (NBLIC_AMD_DEEP_FOLD): the low plane holds 255 - lo wherever hi is odd -- the sawtooth of the low
+ *                 byte, which jumps by 255 whenever the high byte steps, becomes a continuous triangle wave.  Bit 1
+ *                 (NBLIC_AMD_DEEP_SIGNED): the source was int16, the value is u - 32768.  Valid: 0 .. 3; 0xFF is what
+ *                 nblic_amd_deep_plan gives an image it refuses.
+ *   deep_format   of a source: 0 uint16 (NBLIC_AMD_DEEP_U16), 1 int16 (NBLIC_AMD_DEEP_I16).  Of a destination: 0 uint16, 1 int16,
+ *                 2 float16, 3 bfloat16, 4 float32 (NBLIC_AMD_DEEP_TO_*).  The numbering is the deep calls' own; the calls
+ *                 without _deep keep refusing format 4 and above.
+ * ENCODE: the four _from_deep calls are the four _from encoders on 16-bit sources: nblic_amd_src with pointer, pitch and
+ * step multiples of 2, no scale and no bias -- a 16-bit integer is coded as it is.  ONE launch of k_collect_deep writes both
+ * planes of every image (one task per plane) into a block of the call's own, which the encoder then uses in place.
+ *   near          the high plane must be lossless: a non-zero nears[2k] refuses the whole call.  The low plane may have any
+ *                 near: its reconstruction stays in 0 .. 255 and the high byte is exact, and the fold is an isometry of the
+ *                 low byte, so the restored value differs from the source by AT MOST nears[2k + 1], folded or not.
+ *   recons        host buffers of the two planes' reconstructions, as nblic_amd_encode_batch_modes_from leaves them.
+ * DECODE: the two _to_ex_deep calls are the two _to_ex decoders with one nblic_amd_dest_ex per deep image: window, row range
+ * and index semantics are theirs.  ONE launch of k_deliver_deep joins the planes: uint16 / int16 get the value, the float
+ * formats float(v) x scale + bias with v the unsigned or signed value (exact as a float), two float32 roundings, never
+ * fused, then round-to-nearest-even into the format (a float16 overflow goes to infinity).
+ * REFUSED, the whole call (-1, nothing launched): a mode byte that is not valid (0xFF included); on encode a mode whose bit 1
+ * disagrees with deep_format; a NULL array; an unknown format.
+ * REFUSED, that image alone (both streams -1, nothing written, the others unaffected): a source or destination that fails
+ * the pointer, pitch, step, cap or device checks of the calls without _deep (element size 2, or 4 for float32); a size the
+ * encoder does not take; on decode two streams of unequal size, and a uint16 / int16 destination whose signedness
+ * contradicts the mode's bit 1; scale != 1 or bias != 0 with an integer destination.
+ * A plane that fails on the device: zeros in the image's window and -1 for both of its streams.
+ * PLAN: nblic_amd_deep_plan measures and chooses.  ONE launch of k_deep_cost computes per image the COSTS of its three
+ * candidate planes -- high, low, folded low: the sum over the pixels of 2 x bitlen(|e|) + 1, e the MED residual NOT wrapped
+ * mod 256 (a wrapped residual would rate the sawtooth's jumps at nothing) -- and the minimum and maximum of u.
+ * nblic_amd_deep_choose is THE RULE (pure, host only): fold iff cost(folded low) < cost(low), ties are plain, no margin;
+ * bit 1 from deep_format.  costs (may be NULL): n_deep x 3; ranges (may be NULL): n_deep x 2, min and max of u -- so a
+ * caller sees that the data fits 8 or 12 bits.  A source the encoders refuse: mode 0xFF, zeros, nothing launched for it.
+ * nblic_amd_deep_plan_stats: out[0] launches of k_deep_cost, [1] of k_collect_deep, [2] of k_deliver_deep, [3] images
+ * costed, since the context was made; last_ms (may be NULL), three values: GPU milliseconds of the last plan's k_deep_cost
+ * launch, of the last _from_deep call's k_collect_deep launch and of the last _to_ex_deep call's k_deliver_deep launch. */
+#define NBLIC_AMD_DEEP_FOLD 1
+#define NBLIC_AMD_DEEP_SIGNED 2
+#define NBLIC_AMD_DEEP_U16 0
+#define NBLIC_AMD_DEEP_I16 1
+#define NBLIC_AMD_DEEP_TO_U16 0
+#define NBLIC_AMD_DEEP_TO_I16 1
+#define NBLIC_AMD_DEEP_TO_F16 2
+#define NBLIC_AMD_DEEP_TO_BF16 3
+#define NBLIC_AMD_DEEP_TO_F32 4
+int nblic_amd_deep_plan(nblic_amd_ctx *ctx, int n_deep, const nblic_amd_src *srcs, int deep_format, unsigned char *modes, unsigned long long *costs,
+                        unsigned int *ranges);
+int nblic_amd_deep_choose(const unsigned long long costs[3], int deep_format);       /* host only, pure: the mode byte; -1: NULL or an unknown format */
+int nblic_amd_deep_mode_valid(int mode);                                             /* 1 / 0 */
+int nblic_amd_deep_plan_stats(nblic_amd_ctx *ctx, long out[4], double last_ms[3]);
+int nblic_amd_encode_batch_modes_from_deep(nblic_amd_ctx *ctx, int n_deep, const nblic_amd_src *srcs, int deep_format, const unsigned char *modes,
+                                           const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
+                                           unsigned char *const *recons);
+int nblic_amd_qencode_batch_from_deep(nblic_amd_ctx *ctx, int n_deep, const nblic_amd_src *srcs, int deep_format, const unsigned char *modes,
+                                      uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words);
+int nblic_amd_encode_batch_indexed_from_deep(nblic_amd_ctx *ctx, int n_deep, const nblic_amd_src *srcs, int deep_format, const unsigned char *modes,
+                                             const int *every_rows, int band_rows, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
+                                             unsigned char *const *indexes, const size_t *index_caps, long *index_lens);
+int nblic_amd_qencode_batch_indexed_from_deep(nblic_amd_ctx *ctx, int n_deep, const nblic_amd_src *srcs, int deep_format, const unsigned char *modes,
+                                              const int *every_rows, int band_rows, uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words,
+                                              unsigned char *const *indexes, const size_t *index_caps, long *index_lens);
+int nblic_amd_decode_batch_to_ex_deep(nblic_amd_ctx *ctx, int n_deep, const unsigned char *const *streams, const size_t *stream_lens,
+                                      const nblic_amd_dest_ex *dests, int format, const unsigned char *modes, int *heights, int *widths, int *nears,
+                                      int *efforts, int *status);
+int nblic_amd_decode_batch_indexed_to_ex_deep(nblic_amd_ctx *ctx, int n_deep, const unsigned char *const *streams, const size_t *stream_lens,
+                                              const void *const *indexes, const size_t *index_lens, const nblic_amd_dest_ex *dests, int format,
+                                              const unsigned char *modes, int *heights, int *widths, int *nears, int *efforts, int *status);
+/* Debug hooks used by the deep tests: the three kernels and their host walks alone (csrc/deep.h), one launch or one walk each.
+ * nblic_amd_debug_deep_collect(_host): as nblic_amd_debug_collect(_host) with a deep_format and a part (0 high, 1 low,
+ * 2 folded low) in place of format, scale and bias.
+ * nblic_amd_debug_deep_deliver(_host): as nblic_amd_debug_deliver_ex / _host_ex with two planes per task (base_offsets and
+ * gate_status: two entries per task, high then low), a destination format of the deep numbering and a mode byte; steps 0:
+ * the element size.
+ * nblic_amd_debug_deep_cost(_host): sums receives five numbers per source -- the costs of the high, the low and the folded
+ * low plane, min and max of u; tiles (may be NULL) the kernel's workgroups.  Each source is uploaded at byte base_offsets[]
+ * (0 .. 255) of a region of its own filled with 0xFF.  -1: refused; -2: a HIP call failed. */
+int nblic_amd_debug_deep_collect_host(const void *src, size_t cap_bytes, int rows, int cols, size_t pitch_bytes, size_t step_bytes, int deep_format, int part,
+                                      const int *range, unsigned char *out, size_t out_bytes, unsigned long long *units, unsigned long long *chunks);
+int nblic_amd_debug_deep_collect(nblic_amd_ctx *ctx, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets, const int *rows,
+                                 const int *cols, const size_t *pitches, const size_t *steps, const int *deep_formats, const int *parts, const int *ranges,
+                                 unsigned char *const *outs, const size_t *out_bytes);
+int nblic_amd_debug_deep_deliver_host(const unsigned char *hi, const unsigned char *lo, int plane_rows, int width, const int *window, int format, int mode,
+                                      float scale, float bias, int zero, const int *gate_status, unsigned char *out, size_t out_bytes, size_t dst_offset,
+                                      size_t pitch_bytes, size_t step_bytes, unsigned long long *units, unsigned long long *chunks);
+int nblic_amd_debug_deep_deliver(nblic_amd_ctx *ctx, int n, const unsigned char *const *his, const unsigned char *const *los, const size_t *base_offsets,
+                                 const int *plane_rows, const int *widths, const int *windows, const int *formats, const int *modes, const float *scales,
+                                 const float *biases, const int *zeros, const size_t *pitches, const size_t *steps, const size_t *dst_offsets,
+                                 const size_t *out_bytes, unsigned char *const *outs, const int *gate_status);
+int nblic_amd_debug_deep_cost_host(const void *src, size_t cap_bytes, int rows, int cols, size_t pitch_bytes, size_t step_bytes, int deep_format,
+                                   unsigned long long *sums, unsigned long long *tiles);
+int nblic_amd_debug_deep_cost(nblic_amd_ctx *ctx, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets, const int *rows,
+                              const int *cols, const size_t *pitches, const size_t *steps, const int *deep_formats, unsigned long long *sums);
+
 /* Debug hook used by the indexed effort-0 batch's host tests: QNBLIC's entropy stage (histogram normalisation, histogram
  * code, the rANS pass) on caller-made records, reporting the coder in front of entry rows as the batch's workers read it.
  * Host only: no context, no device.  words[height x width] = level | symbol << 8 per pixel, hist[12 x 256] the counts

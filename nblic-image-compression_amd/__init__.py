@@ -66,6 +66,11 @@ EXPORTS = (
     "nblic_amd_encode_batch_modes_from_stack", "nblic_amd_qencode_batch_from_stack", "nblic_amd_encode_batch_indexed_from_stack",
     "nblic_amd_qencode_batch_indexed_from_stack", "nblic_amd_decode_batch_to_ex_stack", "nblic_amd_decode_batch_indexed_to_ex_stack",
     "nblic_amd_debug_stack_deliver_host", "nblic_amd_debug_stack_deliver", "nblic_amd_debug_stack_cost_host", "nblic_amd_debug_stack_cost",
+    "nblic_amd_deep_plan", "nblic_amd_deep_choose", "nblic_amd_deep_mode_valid", "nblic_amd_deep_plan_stats",
+    "nblic_amd_encode_batch_modes_from_deep", "nblic_amd_qencode_batch_from_deep", "nblic_amd_encode_batch_indexed_from_deep",
+    "nblic_amd_qencode_batch_indexed_from_deep", "nblic_amd_decode_batch_to_ex_deep", "nblic_amd_decode_batch_indexed_to_ex_deep",
+    "nblic_amd_debug_deep_collect_host", "nblic_amd_debug_deep_collect", "nblic_amd_debug_deep_deliver_host", "nblic_amd_debug_deep_deliver",
+    "nblic_amd_debug_deep_cost_host", "nblic_amd_debug_deep_cost",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
     "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats", "nblic_amd_copy_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
@@ -381,6 +386,43 @@ def load_library() -> C.CDLL:
         lib.nblic_amd_debug_stack_cost_host.argtypes = [C.c_int, vpp, szp, szp, szp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, ullp, ullp]
         lib.nblic_amd_debug_stack_cost.restype = C.c_int
         lib.nblic_amd_debug_stack_cost.argtypes = [C.c_void_p, C.c_int, ip, vpp, szp, szp, szp, szp, ip, ip, ip, fp, fp, ullp]
+    if hasattr(lib, "nblic_amd_deep_plan"):                         # (an older build loaded through NBLIC_AMD_LIB has none of these)
+        vpp, szp, fp, ullp, lp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_float), C.POINTER(C.c_ulonglong), C.POINTER(C.c_long)
+        xp, ubp = C.POINTER(DestEx), C.POINTER(C.c_ubyte)
+        head = [C.c_void_p, C.c_int, C.POINTER(Src), C.c_int, ubp]
+        lib.nblic_amd_deep_plan.restype = C.c_int
+        lib.nblic_amd_deep_plan.argtypes = head + [ullp, C.POINTER(C.c_uint)]
+        lib.nblic_amd_deep_choose.restype = C.c_int
+        lib.nblic_amd_deep_choose.argtypes = [ullp, C.c_int]
+        lib.nblic_amd_deep_mode_valid.restype = C.c_int
+        lib.nblic_amd_deep_mode_valid.argtypes = [C.c_int]
+        lib.nblic_amd_deep_plan_stats.restype = C.c_int
+        lib.nblic_amd_deep_plan_stats.argtypes = [C.c_void_p, lp, C.POINTER(C.c_double)]
+        lib.nblic_amd_encode_batch_modes_from_deep.restype = C.c_int
+        lib.nblic_amd_encode_batch_modes_from_deep.argtypes = head + [ip, ip, vpp, szp, lp, vpp]
+        lib.nblic_amd_qencode_batch_from_deep.restype = C.c_int
+        lib.nblic_amd_qencode_batch_from_deep.argtypes = head + [vpp, szp, lp]
+        lib.nblic_amd_encode_batch_indexed_from_deep.restype = C.c_int
+        lib.nblic_amd_encode_batch_indexed_from_deep.argtypes = head + [ip, C.c_int, vpp, szp, lp, vpp, szp, lp]
+        lib.nblic_amd_qencode_batch_indexed_from_deep.restype = C.c_int
+        lib.nblic_amd_qencode_batch_indexed_from_deep.argtypes = lib.nblic_amd_encode_batch_indexed_from_deep.argtypes
+        lib.nblic_amd_decode_batch_to_ex_deep.restype = C.c_int
+        lib.nblic_amd_decode_batch_to_ex_deep.argtypes = [C.c_void_p, C.c_int, vpp, szp, xp, C.c_int, ubp] + [ip] * 5
+        lib.nblic_amd_decode_batch_indexed_to_ex_deep.restype = C.c_int
+        lib.nblic_amd_decode_batch_indexed_to_ex_deep.argtypes = [C.c_void_p, C.c_int, vpp, szp, vpp, szp, xp, C.c_int, ubp] + [ip] * 5
+        lib.nblic_amd_debug_deep_collect_host.restype = C.c_int
+        lib.nblic_amd_debug_deep_collect_host.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, ip, C.c_void_p, C.c_size_t, ullp, ullp]
+        lib.nblic_amd_debug_deep_collect.restype = C.c_int
+        lib.nblic_amd_debug_deep_collect.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, ip, ip, szp, szp, ip, ip, ip, vpp, szp]
+        lib.nblic_amd_debug_deep_deliver_host.restype = C.c_int
+        lib.nblic_amd_debug_deep_deliver_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, ip, C.c_void_p,
+                                                          C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, ullp, ullp]
+        lib.nblic_amd_debug_deep_deliver.restype = C.c_int
+        lib.nblic_amd_debug_deep_deliver.argtypes = [C.c_void_p, C.c_int, vpp, vpp, szp, ip, ip, ip, ip, ip, fp, fp, ip, szp, szp, szp, szp, vpp, ip]
+        lib.nblic_amd_debug_deep_cost_host.restype = C.c_int
+        lib.nblic_amd_debug_deep_cost_host.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, ullp, ullp]
+        lib.nblic_amd_debug_deep_cost.restype = C.c_int
+        lib.nblic_amd_debug_deep_cost.argtypes = [C.c_void_p, C.c_int, vpp, szp, szp, ip, ip, szp, szp, ip, ullp]
     if hasattr(lib, "nblic_amd_index_build_batch"):
         vpp, szp = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
         lib.nblic_amd_index_build_batch.restype = C.c_int
@@ -620,12 +662,13 @@ def _per_image_floats(arg, n: int, what: str) -> List[float]:
     return [float(arg)] * n
 
 
-def _dests_ex_of(views, dims, rows, cols, scale, bias) -> Tuple[list, int]:
+def _dests_ex_of(views, dims, rows, cols, scale, bias, fmt_of=None, elems=None) -> Tuple[list, int]:
     """One ``(ptr, pitch, step, cap, row0, row1, col0, col1, scale, bias)`` per image and the call's format, from tensors
     used duck-typed as :func:`_dests_of` uses them, with any non-negative strides (``layout="any"``).  A tensor whose shape
     is not its image's window gets a null pointer: the library refuses that image alone."""
     n = len(views)
-    fmts = {deliver_format(v.dtype) for v in views if v is not None}
+    fmt_of, elems = fmt_of or deliver_format, elems or DELIVER_ELEM  # (the deep calls number their formats themselves)
+    fmts = {fmt_of(v.dtype) for v in views if v is not None}
     if len(fmts) > 1:
         raise ValueError("out: one dtype per call")
     fmt = fmts.pop() if fmts else 0
@@ -639,7 +682,7 @@ def _dests_ex_of(views, dims, rows, cols, scale, bias) -> Tuple[list, int]:
         elem = int(v.element_size())
         hh, ww = (int(x) for x in v.shape)
         s0, s1 = (int(x) for x in v.stride())
-        if s0 < 0 or s1 < 0 or elem != DELIVER_ELEM[fmt]:
+        if s0 < 0 or s1 < 0 or elem != elems[fmt]:
             raise ValueError("out: strides must not be negative")
         (r0, r1), (c0, c1) = rows[k], cols[k]
         h, w = dims[k]
@@ -1088,6 +1131,179 @@ def _stack_arg(stack, depth, arg, n: int):
     return depth, modes.astype(np.uint8)
 
 
+DEEP_FOLD, DEEP_SIGNED, DEEP_REFUSED = 1, 2, 0xFF                               # NBLIC_AMD_DEEP_FOLD / _SIGNED; what deep_plan gives a refused image
+DEEP_HIGH, DEEP_LOW, DEEP_LOW_FOLDED = 0, 1, 2                                  # the plane a deep collect task writes; the order of an image's three costs
+DEEP_SRC_FORMATS = {"uint16": 0, "int16": 1}                                    # the `deep_format` of a source, by dtype name
+DEEP_DEST_FORMATS = {"uint16": 0, "int16": 1, "float16": 2, "bfloat16": 3, "float32": 4}     # of a destination: the deep calls' own numbering
+DEEP_DEST_ELEM = (2, 2, 2, 2, 4)
+
+
+def _dtype_name(dtype) -> str:
+    if isinstance(dtype, type) and issubclass(dtype, np.generic):   # (np.int16 itself, not an instance of np.dtype)
+        dtype = np.dtype(dtype)
+    return str(getattr(dtype, "name", dtype)).split(".")[-1]
+
+
+def deep_src_format(dtype) -> int:
+    """The ``deep_format`` a source dtype stands for (``torch.uint16``, ``np.int16``, ``"int16"`` ...); ``ValueError`` for any other."""
+    if _dtype_name(dtype) not in DEEP_SRC_FORMATS:
+        raise ValueError(f"no deep source format for dtype {dtype}: uint16 or int16")
+    return DEEP_SRC_FORMATS[_dtype_name(dtype)]
+
+
+def deep_dest_format(dtype) -> int:
+    """The destination format of the deep calls a dtype stands for; ``ValueError`` for any other."""
+    if _dtype_name(dtype) not in DEEP_DEST_FORMATS:
+        raise ValueError(f"no deep destination format for dtype {dtype}: uint16, int16, float16, bfloat16 or float32")
+    return DEEP_DEST_FORMATS[_dtype_name(dtype)]
+
+
+def deep_mode_valid(mode: int) -> bool:
+    """Is ``mode`` one of the four deep mode bytes (``nblic_amd_deep_mode_valid``)?"""
+    return bool(load_library().nblic_amd_deep_mode_valid(int(mode)))
+
+
+def deep_choose(costs, deep_format) -> int:
+    """THE RULE (``nblic_amd_deep_choose``; host only): the mode byte for the three costs (high, low, folded low) of an
+    image of ``deep_format`` (0 / 1 or a dtype): fold iff the folded low plane is strictly cheaper."""
+    fmt = deep_format if isinstance(deep_format, int) else deep_src_format(deep_format)
+    c = (C.c_ulonglong * 3)(*[int(v) for v in costs])
+    mode = int(load_library().nblic_amd_deep_choose(c, int(fmt)))
+    if mode < 0:
+        raise ValueError("nblic_amd_deep_choose refused its arguments")
+    return mode
+
+
+def deep_forward(x: np.ndarray, mode: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The two planes (high, low; uint8) of a uint16 or int16 array under mode byte ``mode``, in numpy alone: what the
+    _from_deep calls encode.  Bit 1 of the mode agrees with the dtype."""
+    x = np.asarray(x)
+    if x.dtype not in (np.uint16, np.int16) or not 0 <= int(mode) < 4 or bool(int(mode) & DEEP_SIGNED) != (x.dtype == np.int16):
+        raise ValueError("deep_forward: uint16 with mode 0 / 1, or int16 with mode 2 / 3")
+    u = x.view(np.uint16) ^ np.uint16(0x8000 if x.dtype == np.int16 else 0)
+    hi, lo = (u >> 8).astype(np.uint8), (u & 255).astype(np.uint8)
+    if int(mode) & DEEP_FOLD:
+        lo = np.where(hi & 1, 255 - lo, lo).astype(np.uint8)
+    return hi, lo
+
+
+def deep_inverse(hi: np.ndarray, lo: np.ndarray, mode: int) -> np.ndarray:
+    """The uint16 (mode 0 / 1) or int16 (mode 2 / 3) array of two uint8 planes: :func:`deep_forward` undone."""
+    hi, lo = np.asarray(hi, np.uint8), np.asarray(lo, np.uint8)
+    if hi.shape != lo.shape or not 0 <= int(mode) < 4:
+        raise ValueError("deep_inverse: two planes of one shape and a mode 0 .. 3")
+    if int(mode) & DEEP_FOLD:
+        lo = np.where(hi & 1, 255 - lo, lo).astype(np.uint8)
+    u = (hi.astype(np.uint16) << 8) | lo
+    return (u ^ np.uint16(0x8000)).view(np.int16) if int(mode) & DEEP_SIGNED else u
+
+
+def _deep_raw(array, rows, cols, pitch, step, offset, cap):
+    """(base address, cap, rows, cols, pitch, step) of a deep source given as a 2-D view or as raw bytes (``collect_host``'s two ways)."""
+    if rows is None or cols is None:
+        if array.ndim != 2 or array.itemsize != 2 or any(s < 0 for s in array.strides):
+            raise ValueError("a 2-D view of 16-bit elements with non-negative strides, or raw bytes with rows and cols")
+        rows, cols = array.shape
+        pitch, step = (array.strides[0] if rows > 1 else max(array.strides[0], cols * array.strides[1])), array.strides[1] if cols > 1 else 2
+        return array.ctypes.data, max(rows - 1, 0) * pitch + max(cols - 1, 0) * step + 2, int(rows), int(cols), int(pitch), int(step)
+    raw = array.reshape(-1).view(np.uint8)
+    pitch = cols * 2 if pitch is None else pitch
+    step = 2 if step is None else step
+    if int(pitch) < 0 or int(step) < 0:
+        raise ValueError("a negative pitch or step")
+    return raw.ctypes.data + int(offset), max(raw.size - int(offset) if cap is None else int(cap), 0), int(rows), int(cols), int(pitch), int(step)
+
+
+def deep_collect_host(array: np.ndarray, deep_format, part: int, pitch: Optional[int] = None, step: Optional[int] = None, offset: int = 0,
+                      rows: Optional[int] = None, cols: Optional[int] = None, cap: Optional[int] = None, px_range=None, info: Optional[dict] = None) -> np.ndarray:
+    """The deep collect kernel's unit walk on the host (``nblic_amd_debug_deep_collect_host``; no device): plane ``part``
+    (``DEEP_HIGH``, ``DEEP_LOW``, ``DEEP_LOW_FOLDED``) of a source of ``deep_format`` (0 / 1 or a dtype), given as
+    :func:`collect_host` takes its sources.  Returns the plane (rows x cols, uint8; 0x5A outside ``px_range``); ``info``
+    receives ``units`` and ``chunks``.  ``ValueError`` when refused."""
+    fmt = deep_format if isinstance(deep_format, int) else deep_src_format(deep_format)
+    base, cap, rows, cols, pitch, step = _deep_raw(array, rows, cols, pitch, step, offset, cap)
+    store = np.full(max(rows * cols, 1) + 16, COLLECT_PATTERN, np.uint8)
+    lead = (-store.ctypes.data) % 16
+    out = store[lead: lead + max(rows * cols, 0)]
+    rng = None if px_range is None else (C.c_int * 2)(int(px_range[0]), int(px_range[1]))
+    units, chunks = C.c_ulonglong(0), C.c_ulonglong(0)
+    rc = load_library().nblic_amd_debug_deep_collect_host(base, cap, rows, cols, pitch, step, int(fmt), int(part), rng, out.ctypes.data if out.size else None, out.size,
+                                                          C.byref(units), C.byref(chunks))
+    if rc != 0:
+        raise ValueError("nblic_amd_debug_deep_collect_host refused its arguments")
+    if info is not None:
+        info["units"], info["chunks"] = int(units.value), int(chunks.value)
+    return out.reshape(rows, cols)
+
+
+def deep_cost_host(array: np.ndarray, deep_format, pitch: Optional[int] = None, step: Optional[int] = None, offset: int = 0, rows: Optional[int] = None,
+                   cols: Optional[int] = None, cap: Optional[int] = None, info: Optional[dict] = None) -> np.ndarray:
+    """The deep cost kernel's tile walk on the host (``nblic_amd_debug_deep_cost_host``; no device) over ONE source given as
+    :func:`deep_collect_host` takes it.  Returns five numbers (uint64): the costs of the high, the low and the folded low
+    plane, then the minimum and the maximum of u.  ``info`` receives ``tiles``.  ``ValueError`` when refused."""
+    fmt = deep_format if isinstance(deep_format, int) else deep_src_format(deep_format)
+    base, cap, rows, cols, pitch, step = _deep_raw(array, rows, cols, pitch, step, offset, cap)
+    sums = np.zeros(5, np.uint64)
+    tiles = C.c_ulonglong(0)
+    rc = load_library().nblic_amd_debug_deep_cost_host(base, cap, rows, cols, pitch, step, int(fmt), sums.ctypes.data_as(C.POINTER(C.c_ulonglong)), C.byref(tiles))
+    if rc != 0:
+        raise ValueError("nblic_amd_debug_deep_cost_host refused its arguments")
+    if info is not None:
+        info["tiles"] = int(tiles.value)
+    return sums
+
+
+def deep_deliver_host(hi: np.ndarray, lo: np.ndarray, window, fmt, mode: int, scale: float = 1.0, bias: float = 0.0, pitch: Optional[int] = None,
+                      offset: int = 0, out_bytes: Optional[int] = None, zero: bool = False, gate_status=(-1, -1), step: Optional[int] = None,
+                      info: Optional[dict] = None) -> np.ndarray:
+    """The deep delivery kernel's unit walk on the host (``nblic_amd_debug_deep_deliver_host``; no device): the window
+    ``(row0, row1, col0, col1)`` of the two 2-D uint8 planes of one deep image of mode byte ``mode``, in destination format
+    ``fmt`` (0 .. 4 of the deep numbering, or a dtype), to byte ``offset`` of a buffer of ``out_bytes`` bytes that holds 0x5A
+    and starts at a multiple of 16, as :func:`deliver_host` lays it out.  ``gate_status``: the statuses of the two planes'
+    gate records (-1: none).  Returns the buffer (uint8); ``info`` receives ``units`` and ``chunks``.  ``ValueError`` when refused."""
+    hi, lo = np.ascontiguousarray(hi, np.uint8), np.ascontiguousarray(lo, np.uint8)
+    if hi.ndim != 2 or hi.shape != lo.shape:
+        raise ValueError("deep_deliver_host: two 2-D uint8 planes of one shape")
+    fmt = fmt if isinstance(fmt, int) else deep_dest_format(fmt)
+    r0, r1, c0, c1 = (int(v) for v in window)
+    elem = DEEP_DEST_ELEM[fmt] if 0 <= fmt < 5 else 2
+    stride = elem if step is None else int(step)
+    if stride < 0:
+        raise ValueError("deep_deliver_host: a negative step")
+    if pitch is None:
+        pitch = (c1 - c0) * stride
+    if out_bytes is None:
+        out_bytes = offset + max(r1 - r0 - 1, 0) * pitch + max(c1 - c0 - 1, 0) * stride + elem
+    raw = np.full(int(out_bytes) + 16, DELIVER_PATTERN, np.uint8)
+    lead = (-raw.ctypes.data) % 16
+    out = raw[lead: lead + int(out_bytes)]
+    units, chunks = C.c_ulonglong(0), C.c_ulonglong(0)
+    rc = load_library().nblic_amd_debug_deep_deliver_host(hi.ctypes.data if hi.size else None, lo.ctypes.data if lo.size else None, hi.shape[0], hi.shape[1],
+                                                          (C.c_int * 4)(r0, r1, c0, c1), int(fmt), int(mode), float(scale), float(bias), int(bool(zero)),
+                                                          (C.c_int * 2)(int(gate_status[0]), int(gate_status[1])), out.ctypes.data, out.size, int(offset), int(pitch),
+                                                          0 if step is None else int(step), C.byref(units), C.byref(chunks))
+    if rc != 0:
+        raise ValueError("nblic_amd_debug_deep_deliver_host refused its arguments")
+    if info is not None:
+        info["units"], info["chunks"] = int(units.value), int(chunks.value)
+    return out
+
+
+def _deep_arg(deep, n: int):
+    """What ``deep`` stands for: None, the string ``"plan"``, or n mode bytes without bit 1 (``"plain"``: 0, ``"fold"``: 1) --
+    the caller adds bit 1 from the dtype -- or the bytes of an array as they are."""
+    if deep is None or (isinstance(deep, str) and deep == "plan"):
+        return deep
+    if isinstance(deep, str):
+        if deep not in ("plain", "fold"):
+            raise ValueError('deep: None, "plain", "fold", "plan", or one mode byte per deep image')
+        return np.full(n, DEEP_FOLD if deep == "fold" else 0, np.uint8)
+    modes = np.array([int(v) for v in np.asarray(deep).reshape(-1)], np.int64)
+    if modes.shape != (n,) or modes.min(initial=0) < 0 or modes.max(initial=0) > 255:
+        raise ValueError("deep: one mode byte per deep image")
+    return modes.astype(np.uint8)
+
+
 def _src_views(src):
     """The 2-D view of every image: ``src`` is one tensor [N, H, W] or [N, C, H, W] (every channel an image, n-major), or
     a list of 2-D tensors or views."""
@@ -1106,12 +1322,12 @@ def _src_views(src):
     return views
 
 
-def _srcs_of(views, rows, cols) -> Tuple[list, int]:
+def _srcs_of(views, rows, cols, fmt_of=None) -> Tuple[list, int]:
     """One ``(ptr, pitch, step, cap, rows, cols)`` per image and the call's format, from tensors used duck-typed
     (``data_ptr()``, ``stride()``, ``element_size()``, ``shape``, ``dtype``): any non-negative strides.  ``rows`` / ``cols``
     crop -- ``(a, b)`` with b == 0 for "to the end", as :func:`_pairs_for` takes them -- by offsetting the pointer."""
     n = len(views)
-    fmts = {collect_format(v.dtype) for v in views}
+    fmts = {(fmt_of or collect_format)(v.dtype) for v in views}
     if len(fmts) > 1:
         raise ValueError("src: one dtype per call")
     fmt = fmts.pop() if fmts else 0
@@ -1897,7 +2113,7 @@ class Context:
         return _dests_ex_of(views, dims, rows, cols, scale, bias)
 
     def decode_batch_indexed_into(self, pairs, out, rows=None, cols=None, scale=1.0, bias=0.0, info: Optional[dict] = None, layout: str = "rows",
-                                  color=None, stack=None, depth=None) -> List[int]:
+                                  color=None, stack=None, depth=None, deep=None) -> List[int]:
         """A window of every image of ``decode_batch_indexed`` straight into device tensors: no pixel crosses the bus.
         ``out`` is one tensor [N, H', W'] or [N, 1, H', W'] on this context's device, or a list of 2-D tensors -- views
         with any batch and row stride, last stride 1; the dtype chooses the format: uint8 (a copy), float16, bfloat16 or
@@ -1931,8 +2147,25 @@ class Context:
         reference only: for one slice of a volume hand in the streams of its run from the key to the target with one
         destination.  The slices of a stack with a delta have one size and one window; such a stack is refused as a whole.
         A plane that fails leaves zeros and -1 in its slice and the later ones of its run.  Not with ``color``
-        (``ValueError``); an invalid byte refuses the whole call."""
+        (``ValueError``); an invalid byte refuses the whole call.
+
+        ``deep="plain"``, ``"fold"`` or one mode byte per deep image (what ``encode_batch_from(..., deep=...)`` used or
+        returned): ``pairs`` holds TWO (stream, index) pairs per deep image, high plane then low plane, and ``out`` one
+        destination per deep image -- taken as with ``layout="any"``, of dtype uint16, int16 (the value), float16, bfloat16
+        or float32 (``value * scale + bias``).  With a string the mode's bit 1 is set for an int16 ``out`` only: hand in the
+        bytes to get signed values into a float tensor.  A deep image stands or falls as a whole: both statuses are -1 when
+        a stream or the destination is refused (nothing is written) or a plane fails (zeros).  Not with ``color`` or
+        ``stack`` (``ValueError``); an invalid byte, or an integer ``out`` of the other signedness, refuses."""
         n = len(pairs)
+        if deep is not None:
+            if color is not None or stack is not None:
+                raise ValueError("deep goes with neither color nor stack")
+            dims = []
+            for _, x in pairs:
+                x = _bytes_arg(x if x is not None else b"")
+                h, w = (int(v) for v in np.frombuffer(x[16:24].tobytes(), "<i4")) if x.size >= INDEX_HEAD_BYTES else (0, 0)
+                dims.append((h, w) if 0 < h <= 65535 and 0 < w <= 65535 else (0, 0))
+            return self._deep_decode([s for s, _ in pairs], [x for _, x in pairs], out, deep, dims, rows, cols, scale, bias, info)
         flag, modes = _color_arg(color, out)
         sdepth, smodes = _stack_arg(stack, depth, out, n)
         if smodes is not None and color is not None:
@@ -1963,12 +2196,18 @@ class Context:
         return status
 
     def decode_batch_into(self, streams, out, rows=None, cols=None, scale=1.0, bias=0.0, info: Optional[dict] = None, layout: str = "rows",
-                          color=None, stack=None, depth=None) -> List[int]:
+                          color=None, stack=None, depth=None, deep=None) -> List[int]:
         """``decode_batch`` with a window of every plane delivered into device tensors (no index: every stream is decoded
         whole, from its start).  ``out``, ``layout``, ``rows``, ``cols``, ``scale``, ``bias``, the result and ``info`` as
         ``decode_batch_indexed_into``; a stream that fails on the device leaves zeros.  ``color="rct"`` or ``color=modes`` as
         there: the three planes of a frame may be of different codecs and efforts.  ``stack`` and ``depth`` as there: the
-        slices of a run may be of different codecs and efforts too."""
+        slices of a run may be of different codecs and efforts too.  ``deep`` as there: two streams per deep image, which may
+        be of different codecs and efforts."""
+        if deep is not None:
+            if color is not None or stack is not None:
+                raise ValueError("deep goes with neither color nor stack")
+            dims = [_stream_dims(_bytes_arg(s if s is not None else b"")) or (0, 0) for s in streams]
+            return self._deep_decode(list(streams), None, out, deep, dims, rows, cols, scale, bias, info)
         flag, modes = _color_arg(color, out)
         sdepth, smodes = _stack_arg(stack, depth, out, len(streams))
         if smodes is not None and color is not None:
@@ -2097,6 +2336,216 @@ class Context:
         if self.lib.nblic_amd_stack_plan_stats(self.handle, v, ms) != 0:
             raise RuntimeError("nblic_amd_stack_plan_stats failed")
         return dict(cost_launches=int(v[0]), elements=int(v[1]), deliver_launches=int(v[2]), runs=int(v[3]), plan_ms=float(ms[0]), deliver_ms=float(ms[1]))
+
+    def _deep_srcs(self, src, rows, cols):
+        """(Src array, n, deep_format, the (ptr, ...) tuples) of 16-bit sources as ``encode_batch_from`` takes its tensors."""
+        srcs, fmt = _srcs_of(_src_views(src), rows, cols, fmt_of=deep_src_format)
+        arr = (Src * max(len(srcs), 1))()
+        for k, s in enumerate(srcs):
+            arr[k] = Src(*[int(x) if i else (int(x) or None) for i, x in enumerate(s)])
+        return arr, len(srcs), fmt, srcs
+
+    def deep_plan(self, src, costs: bool = False, rows=None, cols=None):
+        """Choose a deep mode byte per 16-bit image from costs measured on the device (``nblic_amd_deep_plan``).  ``src`` as
+        ``encode_batch_from(..., deep=...)`` takes it: ``torch.uint16`` or ``torch.int16``, a tensor [N, H, W] or
+        [N, C, H, W] or a list of 2-D views, any strides, with the same ``rows`` and ``cols``.  Returns a uint8 array of one
+        mode per image for ``deep=`` of the encoder and the decoders -- bit 0 where the folded low plane is strictly cheaper
+        (:func:`deep_choose`), bit 1 from the dtype; ``DEEP_REFUSED`` (0xFF) marks a source the library refuses.
+        ``costs=True``: also the [n, 3] uint64 table (high, low, folded low; zeros for a refused image) and the [n, 2]
+        int64 table of the smallest and the largest source VALUE (signed for int16), so a caller sees that the data fits 8
+        or 12 bits.  ``ValueError`` when the library refuses the whole call."""
+        arr, n, fmt, _ = self._deep_srcs(src, rows, cols)
+        modes, table, ranges = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 3), np.uint64), np.zeros((max(n, 1), 2), np.uint32)
+        rc = self.lib.nblic_amd_deep_plan(self.handle, n, arr, int(fmt), _modes_ptr(modes), table.ctypes.data_as(C.POINTER(C.c_ulonglong)) if costs else None,
+                                          ranges.ctypes.data_as(C.POINTER(C.c_uint)) if costs else None)
+        if rc != 0:
+            raise ValueError("nblic_amd_deep_plan refused the call")
+        if not costs:
+            return modes[:n]
+        values = ranges[:n].astype(np.int64) - (32768 if fmt == 1 else 0)
+        values[modes[:n] == DEEP_REFUSED] = 0
+        return modes[:n], table[:n], values
+
+    def deep_plan_stats(self) -> dict:
+        """Since the context was created (``nblic_amd_deep_plan_stats``): ``plan_launches`` of k_deep_cost, ``collect_launches``
+        of k_collect_deep, ``deliver_launches`` of k_deliver_deep, ``images`` costed; ``plan_ms``, ``collect_ms``,
+        ``deliver_ms``: the GPU milliseconds of the last :meth:`deep_plan`'s launch, of the last encode's k_collect_deep launch
+        and of the last decode's k_deliver_deep launch."""
+        v, ms = (C.c_long * 4)(), (C.c_double * 3)()
+        if self.lib.nblic_amd_deep_plan_stats(self.handle, v, ms) != 0:
+            raise RuntimeError("nblic_amd_deep_plan_stats failed")
+        return dict(plan_launches=int(v[0]), collect_launches=int(v[1]), deliver_launches=int(v[2]), images=int(v[3]), plan_ms=float(ms[0]),
+                    collect_ms=float(ms[1]), deliver_ms=float(ms[2]))
+
+    def encode_deep_srcs(self, src, modes, rows=None, cols=None, near=0, effort=1, every_rows=None, band_rows: int = 0, info: Optional[dict] = None):
+        """The four _from_deep calls on 16-bit sources given as :meth:`deep_plan` takes them, in mode bytes ``modes`` (one per
+        deep image, bit 1 included).  ``near`` / ``effort``: one value, or one per STREAM (2 n of them: high, low, high, ...);
+        one ``near`` for all is the low planes' -- the high plane is always lossless.  Returns 2 n streams (``None`` for a
+        refused or failed image's two), or (stream, index) pairs with ``every_rows``; ``info`` receives ``rc`` and, for the
+        mode call, ``recons``.  ``ValueError`` when the library refuses the whole call."""
+        arr, nd, fmt, srcs = self._deep_srcs(src, rows, cols)
+        n = 2 * nd
+        nears = [0 if k % 2 == 0 else int(near) for k in range(n)] if np.isscalar(near) else _per_image(near, n, "near")
+        efforts = _per_image(effort, n, "effort")
+        q = n > 0 and all(e == 0 for e in efforts)
+        if (not q and any(e == 0 for e in efforts)) or (q and any(nears)):
+            raise ValueError("effort 0 (QNBLIC) is lossless and takes a whole call")
+        if every_rows is not None and not q and (any(nears) or any(e != 1 for e in efforts)):
+            raise ValueError("the indexed calls are lossless -e1 or effort 0")
+        modes = np.ascontiguousarray(modes, np.uint8)
+        if modes.shape != (nd,):
+            raise ValueError("deep: one mode byte per deep image")
+        shapes = [(max(int(srcs[k // 2][4]), 1), max(int(srcs[k // 2][5]), 1)) for k in range(n)]
+        outs = [np.empty(out_capacity(h, w) // (2 if q else 1), np.uint16 if q else np.uint8) for h, w in shapes]
+        m = max(n, 1)
+        op = (C.c_void_p * m)(*[C.c_void_p(o.ctypes.data) for o in outs])
+        caps = (C.c_size_t * m)(*[o.size for o in outs])
+        lens = (C.c_long * m)(*([-2] * m))                      # (the library writes every length once it has accepted the call)
+        head = (self.handle, nd, arr, int(fmt), _modes_ptr(modes))
+        recs = idxs = xlens = None
+        if every_rows is not None:
+            every = _every_rows_list(every_rows, n)
+            idxs = [np.empty(max(index_bytes(1 if q else 0, h, w, 0 if q else 1, r), 1), np.uint8) for (h, w), r in zip(shapes, every)]
+            xp = (C.c_void_p * m)(*[C.c_void_p(x.ctypes.data) for x in idxs])
+            xcaps, xlens = (C.c_size_t * m)(*[x.size for x in idxs]), (C.c_long * m)()
+            call = self.lib.nblic_amd_qencode_batch_indexed_from_deep if q else self.lib.nblic_amd_encode_batch_indexed_from_deep
+            rc = call(*head, (C.c_int * m)(*every), int(band_rows), op, caps, lens, xp, xcaps, xlens)
+        elif q:
+            rc = self.lib.nblic_amd_qencode_batch_from_deep(*head, op, caps, lens)
+        else:
+            if info is not None:
+                recs = [np.zeros(s, np.uint8) for s in shapes]
+            rp = (C.c_void_p * m)(*[C.c_void_p(r.ctypes.data) for r in recs]) if recs is not None else None
+            rc = self.lib.nblic_amd_encode_batch_modes_from_deep(*head, (C.c_int * m)(*nears), (C.c_int * m)(*efforts), op, caps, lens, rp)
+        if rc != 0 and n > 0 and all(v == -2 for v in lens[:n]):
+            raise ValueError("the library refused the whole call")
+        if info is not None:
+            info["rc"] = int(rc)
+            if recs is not None:
+                info["recons"] = recs
+        streams = [o[:v].tobytes() if v >= 0 else None for o, v in zip(outs, lens[:n])]
+        if every_rows is None:
+            return streams
+        return list(zip(streams, [x[:v].tobytes() if v > 0 else None for x, v in zip(idxs, xlens[:n])]))
+
+    def _deep_decode(self, streams, indexes, out, deep, dims, rows, cols, scale, bias, info):
+        """The two _to_ex_deep calls: 2 n streams (with their indexes, or None) into n destinations of any layout."""
+        n = len(streams)
+        if n % 2:
+            raise ValueError("deep: two streams per deep image, high then low")
+        views = _src_views(out)
+        if len(views) != n // 2:
+            raise ValueError("out: one 2-D tensor per deep image")
+        modes = _deep_arg(deep, n // 2)
+        if isinstance(modes, str) or modes is None:
+            raise ValueError('deep: "plan" is the encoder\'s; a decoder takes "plain", "fold" or the mode bytes')
+        dests, fmt = _dests_ex_of(views, [dims[2 * k] for k in range(n // 2)], rows, cols, scale, bias, fmt_of=deep_dest_format, elems=DEEP_DEST_ELEM)
+        if isinstance(deep, str):                              # bit 1 from the destination where it tells, else unsigned
+            modes = modes | np.uint8(DEEP_SIGNED if fmt == 1 else 0)
+        ss = [_bytes_arg(s if s is not None else b"") for s in streams]
+        nothing = np.zeros(1, np.uint8)
+        ip = C.POINTER(C.c_int)
+        vp = lambda arrs: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else nothing.ctypes.data for a in arrs])
+        sz = lambda arrs: (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        meta = [np.full(max(n, 1), -1, np.int32) for _ in range(5)]
+        if indexes is None:
+            rc = self.lib.nblic_amd_decode_batch_to_ex_deep(self.handle, n // 2, vp(ss), sz(ss), _dest_ex_array(dests), int(fmt), _modes_ptr(modes),
+                                                            *[m.ctypes.data_as(ip) for m in meta])
+        else:
+            xs = [_bytes_arg(x if x is not None else b"") for x in indexes]
+            rc = self.lib.nblic_amd_decode_batch_indexed_to_ex_deep(self.handle, n // 2, vp(ss), sz(ss), vp(xs), sz(xs), _dest_ex_array(dests), int(fmt), _modes_ptr(modes),
+                                                                    *[m.ctypes.data_as(ip) for m in meta])
+        status = [int(v) for v in meta[4][:n]]
+        if info is not None:
+            info["status"], info["rc"], info["dims"] = status, int(rc), [(int(meta[0][k]), int(meta[1][k])) for k in range(n)]
+        return status
+
+    def debug_deep_collect(self, tasks) -> List[np.ndarray]:
+        """``nblic_amd_debug_deep_collect``: ONE k_collect_deep launch over ``tasks``, each a dict with ``raw`` (the source's
+        bytes, any array), ``rows``, ``cols``, ``fmt`` (0 uint16 / 1 int16) and ``part``, and optionally ``pitch``, ``step``
+        (bytes; default: contiguous), ``base_offset`` (0 .. 255: where the device copy starts) and ``px_range``.  Returns
+        every task's whole output buffer (uint8): ``COLLECT_GUARD`` bytes of 0x5A, the plane, padding and a guard of 0x5A."""
+        n = len(tasks)
+        raws = [np.ascontiguousarray(t["raw"]).reshape(-1).view(np.uint8) for t in tasks]
+        hs, ws = [int(t["rows"]) for t in tasks], [int(t["cols"]) for t in tasks]
+        sizes = [COLLECT_GUARD + ((h * w + 255) & ~255) + COLLECT_GUARD for h, w in zip(hs, ws)]
+        outs = [np.zeros(max(b, 1), np.uint8) for b in sizes]
+        ranges = None
+        if any("px_range" in t for t in tasks):
+            flat = []
+            for t in tasks:
+                flat += [int(v) for v in t.get("px_range", (0, 0))]
+            ranges = (C.c_int * (2 * n))(*flat)
+        sz = lambda vals: (C.c_size_t * max(n, 1))(*[int(v) for v in vals])
+        iv = lambda vals: (C.c_int * max(n, 1))(*[int(v) for v in vals])
+        vp = lambda arrs: (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        rc = self.lib.nblic_amd_debug_deep_collect(self.handle, n, vp(raws), sz(r.size for r in raws), sz(t.get("base_offset", 0) for t in tasks), iv(hs), iv(ws),
+                                                   sz(t.get("pitch", 2 * int(t["cols"])) for t in tasks), sz(t.get("step", 2) for t in tasks),
+                                                   iv(t["fmt"] for t in tasks), iv(t["part"] for t in tasks), ranges, vp(outs), sz(sizes))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_deep_collect refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_deep_collect failed (%d)" % rc)
+        return outs
+
+    def debug_deep_deliver(self, tasks) -> List[np.ndarray]:
+        """``nblic_amd_debug_deep_deliver``: ONE k_deliver_deep launch over ``tasks``, each a dict with ``hi`` and ``lo`` (2-D
+        uint8, one shape), ``window`` (row0, row1, col0, col1), ``fmt`` (0 .. 4 of the deep numbering) and ``mode``, and
+        optionally ``scale``, ``bias``, ``step`` (default: the element size), ``pitch`` (default: ``cols * step``), ``offset``
+        (of the destination in its 0x5A-filled buffer), ``out_bytes``, ``zero``, ``gate_status`` (two statuses; -1: no gate)
+        and ``base_offsets`` (two values 0 .. 15: of the planes in their device buffers).  Returns every task's whole buffer."""
+        n = len(tasks)
+        his = [np.ascontiguousarray(t["hi"], np.uint8) for t in tasks]
+        los = [np.ascontiguousarray(t["lo"], np.uint8) for t in tasks]
+        if n < 1 or any(h.ndim != 2 or h.shape != l.shape for h, l in zip(his, los)):
+            raise ValueError("debug_deep_deliver: two 2-D uint8 planes of one shape per task")
+        wins, steps, pitches, offsets, sizes, bases, gates = [], [], [], [], [], [], []
+        for t in tasks:
+            r0, r1, c0, c1 = (int(v) for v in t["window"])
+            fmt = int(t["fmt"])
+            elem = DEEP_DEST_ELEM[fmt] if 0 <= fmt < 5 else 2
+            step = int(t.get("step", elem))
+            pitch = int(t.get("pitch", (c1 - c0) * step))
+            off = int(t.get("offset", 0))
+            wins += [r0, r1, c0, c1]; steps.append(step); pitches.append(pitch); offsets.append(off)
+            sizes.append(int(t.get("out_bytes", off + max(r1 - r0 - 1, 0) * pitch + max(c1 - c0 - 1, 0) * step + elem)))
+            bases += [int(v) for v in t.get("base_offsets", (0, 0))]; gates += [int(v) for v in t.get("gate_status", (-1, -1))]
+        if min(steps + pitches + offsets + sizes + bases) < 0 or len(bases) != 2 * n or len(gates) != 2 * n:
+            raise ValueError("debug_deep_deliver: non-negative steps, pitches, offsets and sizes; two base offsets and two gate statuses per task")
+        outs = [np.zeros(max(b, 1), np.uint8) for b in sizes]
+        sz = lambda vals: (C.c_size_t * len(vals))(*[int(v) for v in vals])
+        iv = lambda vals: (C.c_int * len(vals))(*[int(v) for v in vals])
+        fv = lambda vals: (C.c_float * len(vals))(*vals)
+        vp = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data if a.size else None for a in arrs])
+        rc = self.lib.nblic_amd_debug_deep_deliver(self.handle, n, vp(his), vp(los), sz(bases), iv([h.shape[0] for h in his]), iv([h.shape[1] for h in his]), iv(wins),
+                                                   iv([t["fmt"] for t in tasks]), iv([t["mode"] for t in tasks]), fv([float(t.get("scale", 1.0)) for t in tasks]),
+                                                   fv([float(t.get("bias", 0.0)) for t in tasks]), iv([int(bool(t.get("zero", False))) for t in tasks]), sz(pitches),
+                                                   sz(steps), sz(offsets), sz(sizes), vp(outs), iv(gates))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_deep_deliver refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_deep_deliver failed (%d)" % rc)
+        return [o[:b] for o, b in zip(outs, sizes)]
+
+    def debug_deep_cost(self, tasks) -> np.ndarray:
+        """``nblic_amd_debug_deep_cost``: ONE k_deep_cost launch over ``tasks``, each a dict with ``raw`` (the source's bytes),
+        ``rows``, ``cols``, ``fmt`` (0 uint16 / 1 int16) and optionally ``pitch``, ``step`` (bytes; default: contiguous) and
+        ``base_offset`` (0 .. 255).  Returns the [n, 5] uint64 table: the costs of the high, the low and the folded low
+        plane, then the minimum and the maximum of u."""
+        n = len(tasks)
+        raws = [np.ascontiguousarray(t["raw"]).reshape(-1).view(np.uint8) for t in tasks]
+        out = np.zeros((max(n, 1), 5), np.uint64)
+        sz = lambda vals: (C.c_size_t * max(n, 1))(*[int(v) for v in vals])
+        iv = lambda vals: (C.c_int * max(n, 1))(*[int(v) for v in vals])
+        rc = self.lib.nblic_amd_debug_deep_cost(self.handle, n, (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in raws]), sz(r.size for r in raws),
+                                                sz(t.get("base_offset", 0) for t in tasks), iv(t["rows"] for t in tasks), iv(t["cols"] for t in tasks),
+                                                sz(t.get("pitch", 2 * int(t["cols"])) for t in tasks), sz(t.get("step", 2) for t in tasks), iv(t["fmt"] for t in tasks),
+                                                out.ctypes.data_as(C.POINTER(C.c_ulonglong)))
+        if rc == -1:
+            raise ValueError("nblic_amd_debug_deep_cost refused its arguments")
+        if rc != 0:
+            raise RuntimeError("nblic_amd_debug_deep_cost failed (%d)" % rc)
+        return out[:n]
 
     def debug_stack_cost(self, tasks) -> List[np.ndarray]:
         """``nblic_amd_debug_stack_cost``: ONE k_stack_cost launch over ``tasks``, each a dict with ``raws`` (the bytes of the
@@ -2304,7 +2753,7 @@ class Context:
 
     def encode_batch_from(self, src, rows=None, cols=None, scale: float = 1.0, bias: float = 0.0, near=0, effort=1, every_rows=None,
                           band_rows: int = 0, info: Optional[dict] = None, recon_out=None, recon_scale=1.0, recon_bias=0.0, color=None,
-                          stack=None, depth=None):
+                          stack=None, depth=None, deep=None):
         """Encode images that lie in device memory in any layout, as pixels or as floats quantised on the way (the _from
         calls; include/nblic_amd.h says what the pixel of an element is).  ``src``: one tensor [N, H, W], one tensor
         [N, C, H, W] -- every channel is an image, n-major -- or a list of 2-D tensors or views, of ONE dtype (uint8,
@@ -2342,7 +2791,34 @@ class Context:
         :meth:`stack_plan` chooses per slice.  Ordinary streams again, and nothing in them names the mode: keep the bytes.
         The slices of a stack with a delta have one size; such a stack with a refused source has ``None`` everywhere.
         ``near`` > 0 only on a key slice whose successor is a key slice; not with ``color`` or ``recon_out``
-        (``ValueError``, as for an invalid byte)."""
+        (``ValueError``, as for an invalid byte).
+
+        ``deep="plain"``, ``"fold"``, ``"plan"`` or one mode byte per image: ``src`` holds DEEP images, ``torch.uint16`` or
+        ``torch.int16`` in the same shapes, and image k becomes TWO streams, 2 k its high and 2 k + 1 its low plane
+        (:func:`deep_forward`): ordinary streams, which any decoder turns into those planes and
+        ``decode_batch_into(..., deep=...)`` into the image.  ``"fold"`` folds every low plane on the parity of the high
+        byte, ``"plan"`` lets :meth:`deep_plan` choose per image and returns the bytes in ``info["deep_modes"]``; bit 1 of a
+        mode byte is the dtype's (int16: set).  Nothing in a stream names the mode: keep the byte.  ``scale`` and ``bias`` do
+        not apply; one ``near`` is the low planes' (the high plane is lossless; the restored value is then off by at most
+        ``near``), or one per stream; ``every_rows`` as ever.  A refused image has two ``None``.  Not with ``color``,
+        ``stack`` or ``recon_out``, and not with any other dtype (``ValueError``, as for an invalid byte)."""
+        if deep is not None:
+            if color is not None or stack is not None or recon_out is not None:
+                raise ValueError("deep goes with neither color, stack nor recon_out")
+            views = _src_views(src)
+            if any(_dtype_name(v.dtype) not in DEEP_SRC_FORMATS for v in views):
+                raise ValueError("deep: the sources are uint16 or int16")
+            signed = DEEP_SIGNED if views and _dtype_name(views[0].dtype) == "int16" else 0
+            modes = _deep_arg(deep, len(views))
+            if isinstance(modes, str):                          # "plan"
+                modes = self.deep_plan(src, rows=rows, cols=cols)
+                if np.any(modes == DEEP_REFUSED):               # the encoder refuses those sources too: any valid byte will do for them
+                    modes = np.where(modes == DEEP_REFUSED, np.uint8(signed), modes).astype(np.uint8)
+            elif isinstance(deep, str):
+                modes = modes | np.uint8(signed)
+            if info is not None:
+                info["deep_modes"] = modes.copy()
+            return self.encode_deep_srcs(src, modes, rows, cols, near, effort, every_rows, band_rows, info)
         flag, modes = _color_arg(color, src)
         if color is not None and recon_out is not None:
             raise ValueError('color="rct" is lossless: there is no reconstruction to deliver')

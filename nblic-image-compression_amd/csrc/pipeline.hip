@@ -320,6 +320,9 @@ struct nblic_amd_ctx {
     std::atomic<long> stack_counts[4] = {};     // nblic_amd_stack_plan_stats: k_stack_cost launches, source elements read, k_deliver_stack launches, runs delivered
     double stack_ms = 0, stack_deliver_ms = 0;  // GPU time of the last nblic_amd_stack_plan's launch / of the last timed k_deliver_stack launch.  Guarded by stat_m
     long deliver_tasks = 0, deliver_strided = 0;     // nblic_amd_deliver_stats: of the last call that delivers.  Guarded by stat_m (at the end: no member has moved)
+    DevBuf<DeepDeliverTask> dec_deep;           // nblic_amd_decode_batch_to_ex_deep: the tasks of the call's k_deliver_deep launch (grow-only)
+    std::atomic<long> deep_counts[4] = {};      // nblic_amd_deep_plan_stats: k_deep_cost, k_collect_deep and k_deliver_deep launches, deep images planned
+    double deep_ms[3] = {0, 0, 0};              // GPU time of the last k_deep_cost, k_collect_deep and k_deliver_deep launch of a plan, an encoder and a decoder.  Guarded by stat_m
 };
 
 namespace nblic {
@@ -1719,6 +1722,9 @@ static bool decode_launch(const DecodeItem &first, const SerialJob *d_jobs, cons
 struct DeliverTo {
     const nblic_amd_dest_ex *dests; uint32_t format; const uint8_t *modes = nullptr;
     const uint8_t *slice_modes = nullptr; int depth = 0;
+    // deep_modes (the _deep calls, deep.h): streams 2i and 2i + 1 are the high and the low plane of deep image i, dests[i] is
+    // its destination and deep_format the destinations' format in the deep calls' own numbering (`format` is not read)
+    const uint8_t *deep_modes = nullptr; uint32_t deep_format = 0;
     uint32_t mode_of(int k) const { return modes ? modes[k / 3] : 0u; }  // of the frame image k belongs to
     bool skipped(int k) const { return slice_modes && !dests[k].ptr && dests[k].cap_bytes == 0; }      // a slice decoded as a reference only
     bool stack_has_delta(int k) const {                                  // does the stack image k belongs to hold a delta slice?
@@ -1839,6 +1845,74 @@ static void deliver_zeros(std::vector<DeliverTask> &tasks, hipStream_t st) {
     DevBuf<DeliverTask> d_tasks;
     for (DeliverTask &T : tasks) { T.zero = 1; T.gate = nullptr; }
     if (d_tasks.alloc(tasks.size()) == hipSuccess && deliver_queue(tasks.data(), tasks.size(), d_tasks, st)) hipStreamSynchronize(st);
+}
+
+// ---- the delivery of a _deep call (deep.h, serial_engine.h k_deliver_deep) ------------------------------------------------------
+// Stream k of a _deep call is plane k % 2 of deep image k / 2, decoded into a plane of h x w like any image.  The window that
+// the image's destination names, as a task WITHOUT a destination (dst null: k_deliver never sees it) -- row0 .. col1 and
+// src_pitch; src, src_bytes, gate and zero are the caller's.  false: refused on the host, as deliver_dest_task refuses, and a
+// uint16 / int16 destination whose signedness contradicts the image's mode.
+static bool deep_dest_window(const nblic_amd_ctx *c, const DeliverTo &to, int k, int h, int w, DeliverTask &T) {
+    const nblic_amd_dest_ex &D = to.dests[k / 2];
+    const uint32_t mode = to.deep_modes[k / 2], format = to.deep_format;
+    T = DeliverTask{};
+    T.row0 = D.row0; T.row1 = D.row1 ? D.row1 : h; T.col0 = D.col0; T.col1 = D.col1 ? D.col1 : w;
+    if (T.row0 < 0 || T.row1 <= T.row0 || T.row1 > h || T.col0 < 0 || T.col1 <= T.col0 || T.col1 > w) return false;
+    if ((format == kDeepToU16 && (mode & kDeepSigned)) || (format == kDeepToI16 && !(mode & kDeepSigned))) return false;
+    if (!(D.scale - D.scale == 0.0f) || !(D.bias - D.bias == 0.0f) || (format <= kDeepToI16 && (D.scale != 1.0f || D.bias != 0.0f))) return false;
+    const size_t elem = deep_dest_elem(format), rows = size_t(T.row1 - T.row0), cols = size_t(T.col1 - T.col0);
+    if (!D.ptr || uintptr_t(D.ptr) % elem || D.pitch_bytes % elem || D.step_bytes % elem || D.step_bytes < elem || D.step_bytes > kDeliverMaxStep) return false;
+    if (D.pitch_bytes < (D.step_bytes == elem ? cols * elem : elem) || D.pitch_bytes > kDeliverMaxPitch) return false;
+    const unsigned long long extent = deep_dest_extent(uint32_t(rows), uint32_t(cols), format, D.pitch_bytes, D.step_bytes);
+    if (extent > D.cap_bytes || !device_range_ok(c, D.ptr, extent)) return false;
+    T.src_pitch = uint32_t(w);
+    return true;
+}
+// The task of deep image i from the two planes' window tasks (above, with src, src_bytes, gate and zero filled in; their row0
+// counts from the first row of src, which may differ between the planes).
+static DeepDeliverTask deep_deliver_task(const DeliverTo &to, int i, const DeliverTask &H, const DeliverTask &L) {
+    const nblic_amd_dest_ex &D = to.dests[i];
+    const size_t skip_h = size_t(H.row0) * size_t(H.src_pitch), skip_l = size_t(L.row0) * size_t(L.src_pitch);
+    DeepDeliverTask T{};
+    T.hi = H.src + skip_h; T.hi_bytes = H.src_bytes - skip_h; T.gate_hi = H.gate;
+    T.lo = L.src + skip_l; T.lo_bytes = L.src_bytes - skip_l; T.gate_lo = L.gate;
+    T.dst = static_cast<uint8_t *>(D.ptr); T.dst_pitch = D.pitch_bytes; T.dst_step = uint32_t(D.step_bytes);
+    T.src_pitch = H.src_pitch; T.rows = uint32_t(H.row1 - H.row0); T.col0 = uint32_t(H.col0); T.col1 = uint32_t(H.col1);
+    T.format = to.deep_format; T.mode = to.deep_modes[i]; T.scale = D.scale; T.bias = D.bias;
+    T.zero = (H.zero || L.zero) ? 1u : 0u;
+    return T;
+}
+// The tasks' places in ONE k_deliver_deep launch, their upload to d_tasks and the launch, queued on st.  marks: two events,
+// made here and recorded around the launch (nblic_amd_deep_plan_stats).
+static bool deliver_deep_queue(nblic_amd_ctx *c, DeepDeliverTask *tasks, size_t n, DeepDeliverTask *d_tasks, hipStream_t st, Event *marks = nullptr) {
+    unsigned long long chunks = 0;
+    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(chunks); chunks += deep_deliver_chunks(tasks[i]); }
+    if (n == 0) return true;
+    if (!d_tasks || chunks >= (1ull << 31) || n >= (size_t(1) << 30)) return false;
+    if (c) c->deep_counts[2] += 1;
+    if (hipMemcpyAsync(d_tasks, tasks, n * sizeof(DeepDeliverTask), hipMemcpyHostToDevice, st) != hipSuccess) return false;
+    if (marks && (marks[0].create(hipEventDefault) != hipSuccess || marks[1].create(hipEventDefault) != hipSuccess || hipEventRecord(marks[0], st) != hipSuccess)) return false;
+    if (!deliver_deep_launch(d_tasks, int(n), uint32_t(chunks), st)) return false;
+    return !marks || hipEventRecord(marks[1], st) == hipSuccess;
+}
+// After the stream has been waited for: the GPU time between two recorded marks into slot `which` of the context's deep figures.
+static void deep_timed(nblic_amd_ctx *c, Event *marks, int which) {
+    float ms = 0.0f;
+    if (marks[0] && marks[1] && hipEventElapsedTime(&ms, marks[0], marks[1]) == hipSuccess) { std::lock_guard<std::mutex> l(c->stat_m); c->deep_ms[which] = double(ms); }
+}
+// After a device failure: zero bytes into the window of every deep image both of whose planes were accepted (of[k]: stream
+// k's window task, null for none), by the same kernel, as far as the stream still works.
+static void deliver_deep_zeros(const DeliverTo &to, const std::vector<const DeliverTask *> &of, hipStream_t st) {
+    std::vector<DeepDeliverTask> tasks;
+    for (size_t k = 0; k + 1 < of.size(); k += 2) {
+        if (!of[k] || !of[k + 1]) continue;
+        DeepDeliverTask T = deep_deliver_task(to, int(k / 2), *of[k], *of[k + 1]);
+        T.zero = 1; T.gate_hi = T.gate_lo = nullptr;
+        tasks.push_back(T);
+    }
+    if (tasks.empty() || !st) return;
+    DevBuf<DeepDeliverTask> d_tasks;
+    if (d_tasks.alloc(tasks.size()) == hipSuccess && deliver_deep_queue(nullptr, tasks.data(), tasks.size(), d_tasks, st)) hipStreamSynchronize(st);
 }
 
 // ---- the delivery of a _stack call (stack.h, serial_engine.h k_deliver_stack) ---------------------------------------------------
@@ -2006,7 +2080,7 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         if (r != Described::ok) continue;
         if (to) {                                                        // the planes stay on the device: a window of each goes to the caller's memory there
             DeliverTask T;
-            if (!deliver_dest_task(c, *to, k, it.h, it.w, T)) continue;
+            if (!(to->deep_modes ? deep_dest_window(c, *to, k, it.h, it.w, T) : deliver_dest_task(c, *to, k, it.h, it.w, T))) continue;
             T.first_chunk = uint32_t(k);                                 // (until the sort below: the image it belongs to)
             deliveries.push_back(T);
         } else if (size_t(it.h) * size_t(it.w) > img_caps[k]) continue;
@@ -2072,6 +2146,21 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         }
         items.swap(kept_items); deliveries.swap(kept_tasks);
     }
+    if (to && to->deep_modes) {
+        // a deep image stands or falls as a whole: two planes of one size
+        auto bytes_of = [](const DecodeItem &it) {
+            return stream_buf_bytes(it.len) + up256(size_t(it.h) * size_t(it.w)) + up256(lsq_stats_bytes(it.kind, it.effort, it.w)) + up256(record_state_bytes(it.kind)) + (it.kind ? up256(kQTab) : 0);
+        };
+        std::vector<int> at(size_t(n), -1);
+        for (size_t i = 0; i < items.size(); i++) at[size_t(items[i].k)] = int(i);
+        std::vector<DecodeItem> kept_items; std::vector<DeliverTask> kept_tasks;
+        for (size_t i = 0; i < items.size(); i++) {
+            const int other = at[size_t(items[i].k ^ 1)];
+            if (other >= 0 && items[size_t(other)].h == items[i].h && items[size_t(other)].w == items[i].w) { kept_items.push_back(items[i]); kept_tasks.push_back(deliveries[i]); }
+            else arena -= bytes_of(items[i]);
+        }
+        items.swap(kept_items); deliveries.swap(kept_tasks);
+    }
     if (items.empty()) return true;
     std::stable_sort(items.begin(), items.end(), [](const DecodeItem &a, const DecodeItem &b) { return a.kind * 4 + a.effort < b.kind * 4 + b.effort; });
     const int m = int(items.size());
@@ -2104,7 +2193,7 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
             T.src = recon; T.src_bytes = up256(size_t(it.h) * size_t(it.w)); T.gate = state;
         }
     }
-    const bool rct = to && to->modes, stack = to && to->slice_modes;
+    const bool rct = to && to->modes, stack = to && to->slice_modes, deep = to && to->deep_modes;
     if (rct) {                                                           // every task of a frame with a difference is gated by its three records; a difference refers to the base's plane
         std::vector<int> at(size_t(n), -1);
         for (int i = 0; i < m; i++) at[size_t(items[size_t(i)].k)] = i;
@@ -2136,7 +2225,11 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
     auto fail = [&](const char *what) {
         fprintf(stderr, "[nblic_amd] decode: %s failed\n", what);
         hipStreamSynchronize(c->dec_stream); hipStreamSynchronize(c->dec_stream2);
-        if (to) deliver_zeros(deliveries, c->dec_stream);
+        if (to && to->deep_modes) {
+            std::vector<const DeliverTask *> of(size_t(n), nullptr);
+            for (size_t i = 0; i < items.size(); i++) of[size_t(items[i].k)] = &deliveries[i];
+            deliver_deep_zeros(*to, of, c->dec_stream);
+        } else if (to) deliver_zeros(deliveries, c->dec_stream);
         return false;
     };
     auto upload_and_launch = [&](const Chunk &ch) {
@@ -2164,7 +2257,7 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
             if (!to && hipMemcpyAsync(imgs[it.k], jobs[size_t(i)].recon, size_t(it.h) * size_t(it.w), hipMemcpyDeviceToHost, ch.st) != hipSuccess) return false;
         }
         // the chunk's windows: ONE launch on its stream, behind its decode launches (colour frames: one for the call, below)
-        return !to || rct || stack || deliver_queue(deliveries.data() + ch.i0, size_t(ch.i1 - ch.i0), c->dec_deliver + ch.i0, ch.st, c);
+        return !to || rct || stack || deep || deliver_queue(deliveries.data() + ch.i0, size_t(ch.i1 - ch.i0), c->dec_deliver + ch.i0, ch.st, c);
     };
     for (size_t n = 0; n < chunks.size(); n++) {
         if (n >= 2 && hipStreamSynchronize(chunks[n].st) != hipSuccess) return fail("a chunk");      // heads[] of chunk n - 2 have landed before its stream is reused (its H2D reads heads of chunk n)
@@ -2196,8 +2289,27 @@ static bool decode_batch(nblic_amd_ctx *c, int n, const unsigned char *const *st
         if (hipStreamSynchronize(c->dec_stream) != hipSuccess) return fail("the stack delivery");      // (done2 goes when this block ends)
         stack_delivery_timed(c, plan);
     }
+    if (deep) {
+        // As for colour frames: the two planes of an image may lie in chunks of both streams.  ONE k_deliver_deep launch for
+        // the call, a task per deep image gated by both planes' records, on the first stream behind the second one's work.
+        std::vector<int> at(size_t(n), -1);
+        for (int i = 0; i < m; i++) at[size_t(items[size_t(i)].k)] = i;
+        std::vector<DeepDeliverTask> tasks;
+        for (int k = 0; k + 1 < n; k += 2)
+            if (at[size_t(k)] >= 0 && at[size_t(k) + 1] >= 0) tasks.push_back(deep_deliver_task(*to, k / 2, deliveries[size_t(at[size_t(k)])], deliveries[size_t(at[size_t(k) + 1])]));
+        Event done2, marks[2];
+        if (c->dec_deep.reserve(std::max<size_t>(tasks.size(), 1)) != hipSuccess ||
+            done2.create(hipEventDisableTiming) != hipSuccess || hipEventRecord(done2, c->dec_stream2) != hipSuccess ||
+            hipStreamWaitEvent(c->dec_stream, done2, 0) != hipSuccess ||
+            !deliver_deep_queue(c, tasks.data(), tasks.size(), c->dec_deep, c->dec_stream, marks)) return fail("the deep delivery");
+        if (hipStreamSynchronize(c->dec_stream) != hipSuccess) return fail("the deep delivery");       // (done2 goes when this block ends)
+        deep_timed(c, marks, 2);
+    }
     if (hipStreamSynchronize(c->dec_stream) != hipSuccess || hipStreamSynchronize(c->dec_stream2) != hipSuccess) return fail("the last chunk");
     for (int i = 0; i < m; i++) status[items[size_t(i)].k] = heads[size_t(i)].status == kDone ? 0 : -1;
+    if (deep)                                                            // what the gates did on the device: an image with a failed plane has zeros
+        for (int k = 0; k + 1 < n; k += 2)
+            if (status[k] != 0 || status[k + 1] != 0) status[k] = status[k + 1] = -1;
     if (stack)                                                           // what the gates did on the device: behind a failed plane of a run, no delivered slice has its pixels
         for (int s = 0; s + to->depth <= n; s += to->depth)
             for (int d = 1, bad = status[s] != 0; d < to->depth; d++) {
@@ -3857,7 +3969,7 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
         const DecodeItem &it = I.it;
         hs[k] = it.h; ws[k] = it.w; nears[k] = it.near; efforts[k] = it.effort;
         if (to) {                                                        // the window's rows choose the segments; its columns do not shorten the decode
-            if (!deliver_dest_task(c, *to, k, it.h, it.w, I.deliver)) continue;
+            if (!(to->deep_modes ? deep_dest_window(c, *to, k, it.h, it.w, I.deliver) : deliver_dest_task(c, *to, k, it.h, it.w, I.deliver))) continue;
             I.row0 = I.deliver.row0; I.row1 = I.deliver.row1;
         } else {
             I.row0 = row0 ? row0[k] : 0; I.row1 = row1 ? row1[k] : it.h;
@@ -3897,6 +4009,11 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
             }
             if (!ok) for (int k = s; k < s + to->depth; k++) all[size_t(k)].live = false;
         }
+    if (to && to->deep_modes)                                            // a deep image stands or falls as a whole: two planes of one size
+        for (int k = 0; k + 1 < n; k += 2) {
+            IdxDecImage &A = all[size_t(k)], &B = all[size_t(k) + 1];
+            if (!(A.live && B.live && A.it.h == B.it.h && A.it.w == B.it.w)) A.live = B.live = false;
+        }
     for (int k = 0; k < n; k++) {
         IdxDecImage &I = all[size_t(k)];
         if (!I.live) continue;
@@ -3916,7 +4033,11 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
         fprintf(stderr, "[nblic_amd] indexed batch decode: %s\n", what);
         if (st) hipStreamSynchronize(st);
         for (IdxDecImage *I : live) { status[I->k] = -1; if (!to) memset(outs[I->k], 0, I->out_bytes); }
-        if (to) {
+        if (to && to->deep_modes) {
+            std::vector<const DeliverTask *> of(size_t(n), nullptr);
+            for (IdxDecImage *I : live) of[size_t(I->k)] = &I->deliver;
+            deliver_deep_zeros(*to, of, st);
+        } else if (to) {
             std::vector<DeliverTask> zeros;
             for (IdxDecImage *I : live) zeros.push_back(I->deliver);
             deliver_zeros(zeros, st);
@@ -4171,7 +4292,21 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
                 if (bad && !to->skipped(s + d)) status[s + d] = -1;
             }
     }
-    if (!stack) for (IdxDecImage *I : live) {
+    const bool deep = to && to->deep_modes;
+    std::vector<DeepDeliverTask> deep_tasks;                             // (alive until the stream has been waited for)
+    Event deep_marks[2];
+    if (deep) {
+        // ONE k_deliver_deep launch, a task per deep image: a damaged plane is known here, so its image gets zeros and -1 for both
+        for (int k = 0; k + 1 < n; k += 2) {
+            IdxDecImage &A = all[size_t(k)], &B = all[size_t(k) + 1];
+            if (!A.live || !B.live) continue;
+            A.deliver.zero = B.deliver.zero = (A.bad || B.bad) ? 1u : 0u;
+            deep_tasks.push_back(deep_deliver_task(*to, k / 2, A.deliver, B.deliver));
+            status[k] = status[k + 1] = (A.bad || B.bad) ? -1 : 0;
+        }
+        if (!deliver_deep_queue(c, deep_tasks.data(), deep_tasks.size(), mem.make<DeepDeliverTask>(deep_tasks.size()), st, deep_marks)) return fail("delivery");
+    }
+    if (!stack && !deep) for (IdxDecImage *I : live) {
         const size_t f = size_t(I->k - I->k % 3);
         if (I->bad || (to && to->mode_of(I->k) != kColorPlain && (all[f].bad || all[f + 1].bad || all[f + 2].bad))) {
             if (to) { I->deliver.zero = 1; deliveries.push_back(I->deliver); }
@@ -4186,6 +4321,7 @@ static int decode_batch_indexed(nblic_amd_ctx *c, int n, const unsigned char *co
     if (to && !deliver_queue(deliveries.data(), deliveries.size(), reinterpret_cast<DeliverTask *>(d_call + verdict_bytes + unpack_task_bytes), st, c)) return fail("delivery");
     if (hipStreamSynchronize(st) != hipSuccess) return fail("rows");
     if (stack) stack_delivery_timed(c, stack_plan);
+    if (deep) deep_timed(c, deep_marks, 2);
     split[3] = ms_since(t0);
     { std::lock_guard<std::mutex> l(c->stat_m); for (int k = 0; k < 4; k++) c->idxdec_split[k] = split[k]; }
     for (int k = 0; k < n; k++) every = every && status[k] == 0;
@@ -6484,6 +6620,447 @@ int nblic_amd_decode_batch_indexed_to_ex_color(nblic_amd_ctx *c, int n_images, c
     deliver_stats_reset(c);
     return decode_batch_indexed(c, n_images, streams, stream_lens, indexes, index_lens, nullptr, nullptr, nullptr, nullptr, heights, widths, nears, efforts, status, &to);
 }
+// ---- DEEP PIXELS: 16-bit images as a high and a (folded) low plane (deep.h) ------------------------------------------------------
+// A deep source as the checks see it: an image the encoders take, deep.h's rules, and device memory of this context's device.
+static bool deep_src_ok(const nblic_amd_ctx *c, const nblic_amd_src &S, int deep_format) {
+    if (!size_ok(S.rows, S.cols, c->max_px) || S.step_bytes > kCollectMaxStep) return false;
+    if (!deep_source_ok(static_cast<const uint8_t *>(S.ptr), S.pitch_bytes, S.step_bytes, uint32_t(S.rows), uint32_t(S.cols), uint32_t(deep_format), S.cap_bytes)) return false;
+    return device_range_ok(c, S.ptr, deep_src_extent(uint32_t(S.rows), uint32_t(S.cols), S.pitch_bytes, S.step_bytes));
+}
+static bool deep_modes_ok(int n_deep, const unsigned char *modes, int deep_format) {          // valid bytes whose bit 1 is the source format's
+    if (n_deep < 0 || !modes || deep_format < 0 || deep_format >= int(kDeepSrcFormats)) return false;
+    for (int i = 0; i < n_deep; i++)
+        if (!deep_mode_valid(modes[i]) || ((modes[i] & kDeepSigned) != 0) != (deep_format == int(kDeepI16))) return false;
+    return true;
+}
+
+// The tasks' places in ONE k_deep_cost launch, their upload and the launch, queued on st.  The sums are the caller's to set.
+static bool deep_cost_queue(nblic_amd_ctx *c, DeepCostTask *tasks, size_t n, DeepCostTask *d_tasks, hipStream_t st) {
+    unsigned long long tiles = 0;
+    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(tiles); tiles += deep_task_tiles(tasks[i]); }
+    if (n == 0) return true;
+    if (tiles >= (1ull << 31) || n >= (size_t(1) << 30)) return false;
+    c->deep_counts[0] += 1; c->deep_counts[3] += long(n);
+    return hipMemcpyAsync(d_tasks, tasks, n * sizeof(DeepCostTask), hipMemcpyHostToDevice, st) == hipSuccess && deep_cost_launch(d_tasks, int(n), uint32_t(tiles), st);
+}
+// What the sums of n tasks hold before a launch: zero costs, the largest u as the minimum, zero as the maximum.
+static std::vector<unsigned long long> deep_sums_initial(size_t n) {
+    std::vector<unsigned long long> v(n * kDeepSums, 0ull);
+    for (size_t i = 0; i < n; i++) v[i * kDeepSums + 3] = 0xFFFFull;
+    return v;
+}
+
+int nblic_amd_deep_plan(nblic_amd_ctx *c, int n_deep, const nblic_amd_src *srcs, int deep_format, unsigned char *modes, unsigned long long *costs,
+                        unsigned int *ranges) {
+    if (!c || c->broken || n_deep < 0 || !srcs || !modes || deep_format < 0 || deep_format >= int(kDeepSrcFormats) || hipSetDevice(c->device) != hipSuccess) return -1;
+    std::lock_guard<std::mutex> g(c->api);
+    const size_t count = size_t(n_deep);
+    std::vector<DeepCostTask> tasks;
+    std::vector<size_t> image_of;
+    for (size_t i = 0; i < count; i++) {                                 // a refused source: 0xFF, and nothing is launched for it
+        modes[i] = uint8_t(kDeepRefused);
+        if (costs) costs[3 * i] = costs[3 * i + 1] = costs[3 * i + 2] = 0;
+        if (ranges) ranges[2 * i] = ranges[2 * i + 1] = 0;
+        const nblic_amd_src &S = srcs[i];
+        if (!deep_src_ok(c, S, deep_format)) continue;
+        DeepCostTask T{};
+        T.src = static_cast<const uint8_t *>(S.ptr); T.pitch = S.pitch_bytes; T.step = uint32_t(S.step_bytes);
+        T.rows = uint32_t(S.rows); T.cols = uint32_t(S.cols); T.format = uint32_t(deep_format);
+        tasks.push_back(T); image_of.push_back(i);
+    }
+    if (tasks.empty()) return 0;
+    Stream st;
+    Event t0, t1;
+    DevPool mem;
+    const size_t m = tasks.size();
+    unsigned long long *d_sums = mem.make<unsigned long long>(m * kDeepSums);
+    DeepCostTask *d_tasks = mem.make<DeepCostTask>(m);
+    std::vector<unsigned long long> sums = deep_sums_initial(m);
+    if (!d_sums || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess || t0.create(hipEventDefault) != hipSuccess || t1.create(hipEventDefault) != hipSuccess) return -1;
+    for (size_t i = 0; i < m; i++) tasks[i].sums = d_sums + i * kDeepSums;
+    const bool ok = [&]() -> bool {                                      // the launch, then ONE copy of the whole table
+        HIP_OK(hipMemcpyAsync(d_sums, sums.data(), sums.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+        HIP_OK(hipEventRecord(t0, st));
+        if (!deep_cost_queue(c, tasks.data(), m, d_tasks, st)) return false;
+        HIP_OK(hipEventRecord(t1, st));
+        HIP_OK(hipMemcpyAsync(sums.data(), d_sums, sums.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    if (!ok) return -1;
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, t0, t1) == hipSuccess) { std::lock_guard<std::mutex> l(c->stat_m); c->deep_ms[0] = double(ms); }
+    for (size_t i = 0; i < m; i++) {
+        const size_t k = image_of[i];
+        const unsigned long long *s = &sums[i * kDeepSums];
+        modes[k] = deep_choose(s, uint32_t(deep_format));
+        if (costs) { costs[3 * k] = s[0]; costs[3 * k + 1] = s[1]; costs[3 * k + 2] = s[2]; }
+        if (ranges) { ranges[2 * k] = uint32_t(s[3]); ranges[2 * k + 1] = uint32_t(s[4]); }
+    }
+    return 0;
+}
+int nblic_amd_deep_choose(const unsigned long long *costs, int deep_format) {
+    return !costs || deep_format < 0 || deep_format >= int(kDeepSrcFormats) ? -1 : int(deep_choose(costs, uint32_t(deep_format)));
+}
+int nblic_amd_deep_mode_valid(int mode) { return mode >= 0 && mode < 256 && deep_mode_valid(uint32_t(mode)) ? 1 : 0; }
+int nblic_amd_deep_plan_stats(nblic_amd_ctx *c, long out[4], double *last_ms) {
+    if (!c || !out) return -1;
+    for (int k = 0; k < 4; k++) out[k] = c->deep_counts[k].load();
+    if (last_ms) { std::lock_guard<std::mutex> l(c->stat_m); for (int k = 0; k < 3; k++) last_ms[k] = c->deep_ms[k]; }
+    return 0;
+}
+
+// The planes of a _from_deep call: ONE k_collect_deep launch writes both planes of every accepted image into a block of the
+// call's own, and the parent encoder takes them from there IN PLACE as 2 * n_deep uint8 sources (streams 2i and 2i + 1) -- the
+// block stands where the planes that the groups would collect into stand for any other source.  A refused image becomes two
+// sources that the parent refuses.  false: the whole call is refused, nothing was launched.
+struct DeepPlanes { DevPool mem; std::vector<nblic_amd_src> srcs; };
+static bool deep_collect(nblic_amd_ctx *c, int n_deep, const nblic_amd_src *srcs, int deep_format, const unsigned char *modes, DeepPlanes &P) {
+    if (!c || c->broken || !srcs || n_deep > (1 << 29) || !deep_modes_ok(n_deep, modes, deep_format) || hipSetDevice(c->device) != hipSuccess) return false;
+    const size_t count = size_t(n_deep);
+    P.srcs.assign(2 * count, nblic_amd_src{nullptr, 0, 0, 0, 0, 0});
+    std::vector<DeepCollectTask> tasks;
+    std::vector<size_t> at;
+    size_t total = 0;
+    unsigned long long chunks = 0;
+    for (size_t i = 0; i < count; i++) {
+        const nblic_amd_src &S = srcs[i];
+        if (!deep_src_ok(c, S, deep_format)) continue;
+        const size_t plane = size_t(S.rows) * size_t(S.cols);
+        for (uint32_t part : {uint32_t(kDeepHigh), (modes[i] & kDeepFold) ? uint32_t(kDeepLowFolded) : uint32_t(kDeepLow)}) {
+            DeepCollectTask T{};
+            T.src = static_cast<const uint8_t *>(S.ptr); T.pitch = S.pitch_bytes; T.step = uint32_t(S.step_bytes);
+            T.rows = uint32_t(S.rows); T.cols = uint32_t(S.cols); T.px0 = 0; T.px1 = T.rows * T.cols;
+            T.format = uint32_t(deep_format); T.part = part;
+            T.first_chunk = uint32_t(chunks); chunks += deep_collect_chunks(T);
+            tasks.push_back(T); at.push_back(total); total += up256(plane);
+        }
+        for (size_t j = 2 * i; j < 2 * i + 2; j++) P.srcs[j] = nblic_amd_src{nullptr, size_t(S.cols), 1, plane, S.rows, S.cols};
+    }
+    if (tasks.empty()) return true;
+    if (chunks >= (1ull << 31)) return false;
+    Stream st;
+    Event marks[2];
+    uint8_t *d_planes = P.mem.make<uint8_t>(total);
+    DeepCollectTask *d_tasks = P.mem.make<DeepCollectTask>(tasks.size());
+    if (!d_planes || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess || marks[0].create(hipEventDefault) != hipSuccess || marks[1].create(hipEventDefault) != hipSuccess) return false;
+    size_t t = 0;
+    for (size_t j = 0; j < 2 * count; j++) {
+        if (!P.srcs[j].rows) continue;
+        tasks[t].dst = d_planes + at[t];
+        P.srcs[j].ptr = tasks[t].dst;
+        t++;
+    }
+    const bool ok = [&]() -> bool {
+        HIP_OK(hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(DeepCollectTask), hipMemcpyHostToDevice, st));
+        c->deep_counts[1] += 1;
+        HIP_OK(hipEventRecord(marks[0], st));
+        if (!collect_deep_launch(d_tasks, int(tasks.size()), uint32_t(chunks), st)) return false;
+        HIP_OK(hipEventRecord(marks[1], st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    if (ok) deep_timed(c, marks, 1);
+    return ok;
+}
+// The near rule of a _deep call: the high plane is lossless.
+static bool deep_nears_ok(int n_deep, const int *nears) {
+    for (int i = 0; nears && i < n_deep; i++) if (nears[2 * i] != 0) return false;
+    return true;
+}
+
+// The _deep siblings of the four _from encoders: streams 2i and 2i + 1 are the high and the low plane of deep image i.
+int nblic_amd_encode_batch_modes_from_deep(nblic_amd_ctx *c, int n_deep, const nblic_amd_src *srcs, int deep_format, const unsigned char *modes,
+                                           const int *nears, const int *efforts, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
+                                           unsigned char *const *recons) {
+    DeepPlanes P;
+    if (!outs || !out_caps || !out_lens || n_deep < 0 || !deep_nears_ok(n_deep, nears) || !deep_collect(c, n_deep, srcs, deep_format, modes, P)) return -1;
+    return encode_batch_modes_from(c, 2 * n_deep, P.srcs.data(), int(kCollectU8), 1.0f, 0.0f, nears, efforts, outs, out_caps, out_lens, recons, nullptr);
+}
+int nblic_amd_qencode_batch_from_deep(nblic_amd_ctx *c, int n_deep, const nblic_amd_src *srcs, int deep_format, const unsigned char *modes,
+                                      uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words) {
+    DeepPlanes P;
+    if (!outs || !out_caps_words || !out_len_words || n_deep < 0 || !deep_collect(c, n_deep, srcs, deep_format, modes, P)) return -1;
+    return qencode_batch_from(c, 2 * n_deep, P.srcs.data(), int(kCollectU8), 1.0f, 0.0f, outs, out_caps_words, out_len_words, nullptr);
+}
+int nblic_amd_encode_batch_indexed_from_deep(nblic_amd_ctx *c, int n_deep, const nblic_amd_src *srcs, int deep_format, const unsigned char *modes,
+                                             const int *every_rows, int band_rows, unsigned char *const *outs, const size_t *out_caps, long *out_lens,
+                                             unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
+    DeepPlanes P;
+    if (!every_rows || !outs || !out_caps || !out_lens || !indexes || !index_caps || !index_lens || n_deep < 1 || !deep_collect(c, n_deep, srcs, deep_format, modes, P)) return -1;
+    return indexed_batch_from(kIdxNblic, c, 2 * n_deep, P.srcs.data(), int(kCollectU8), 1.0f, 0.0f, every_rows, band_rows, outs, out_caps, out_lens, indexes, index_caps, index_lens);
+}
+int nblic_amd_qencode_batch_indexed_from_deep(nblic_amd_ctx *c, int n_deep, const nblic_amd_src *srcs, int deep_format, const unsigned char *modes,
+                                              const int *every_rows, int band_rows, uint16_t *const *outs, const size_t *out_caps_words, long *out_len_words,
+                                              unsigned char *const *indexes, const size_t *index_caps, long *index_lens) {
+    DeepPlanes P;
+    if (!every_rows || !outs || !out_caps_words || !out_len_words || !indexes || !index_caps || !index_lens || n_deep < 1 || !deep_collect(c, n_deep, srcs, deep_format, modes, P)) return -1;
+    return indexed_batch_from(kIdxQnblic, c, 2 * n_deep, P.srcs.data(), int(kCollectU8), 1.0f, 0.0f, every_rows, band_rows, outs, out_caps_words, out_len_words, indexes, index_caps, index_lens);
+}
+
+// The _deep siblings of the two _to_ex decoders: 2 * n_deep streams, n_deep destinations and mode bytes.
+static bool deep_to_ok(int n_deep, const nblic_amd_dest_ex *dests, int format, const unsigned char *modes) {
+    if (n_deep < 0 || n_deep > (1 << 29) || !dests || !modes || format < 0 || format >= int(kDeepDestFormats)) return false;
+    for (int i = 0; i < n_deep; i++) if (!deep_mode_valid(modes[i])) return false;
+    return true;
+}
+int nblic_amd_decode_batch_to_ex_deep(nblic_amd_ctx *c, int n_deep, const unsigned char *const *streams, const size_t *stream_lens, const nblic_amd_dest_ex *dests,
+                                      int format, const unsigned char *modes, int *heights, int *widths, int *nears, int *efforts, int *status) {
+    if (!c || c->broken || !streams || !stream_lens || !heights || !widths || !nears || !efforts || !status || !deep_to_ok(n_deep, dests, format, modes)) return -1;
+    const int n = 2 * n_deep;
+    for (int k = 0; k < n; k++) if (!streams[k]) return -1;
+    DeliverTo to{dests, 0u};
+    to.deep_modes = modes; to.deep_format = uint32_t(format);
+    std::lock_guard<std::mutex> g(c->api);
+    if (!decode_batch(c, n, streams, stream_lens, nullptr, nullptr, heights, widths, nears, efforts, status, &to)) return -1;
+    for (int k = 0; k < n; k++) if (status[k] != 0) return -1;
+    return 0;
+}
+int nblic_amd_decode_batch_indexed_to_ex_deep(nblic_amd_ctx *c, int n_deep, const unsigned char *const *streams, const size_t *stream_lens,
+                                              const void *const *indexes, const size_t *index_lens, const nblic_amd_dest_ex *dests, int format,
+                                              const unsigned char *modes, int *heights, int *widths, int *nears, int *efforts, int *status) {
+    if (!deep_to_ok(n_deep, dests, format, modes)) return -1;
+    DeliverTo to{dests, 0u};
+    to.deep_modes = modes; to.deep_format = uint32_t(format);
+    return decode_batch_indexed(c, 2 * n_deep, streams, stream_lens, indexes, index_lens, nullptr, nullptr, nullptr, nullptr, heights, widths, nears, efforts, status, &to);
+}
+
+// ---- the three deep kernels on caller-made inputs, and their host walks (tests/test_deep_host.py, tests/test_deep_kernels.py) ----
+static bool debug_deep_collect_task(DeepCollectTask &T, int rows, int cols, size_t pitch, size_t step, int deep_format, int part, const int *range) {
+    if (rows < 1 || cols < 1 || rows > int(kCollectMaxSide) || cols > int(kCollectMaxSide) || step > kCollectMaxStep || deep_format < 0 || part < 0) return false;
+    T = DeepCollectTask{};
+    T.pitch = pitch; T.step = uint32_t(step); T.rows = uint32_t(rows); T.cols = uint32_t(cols);
+    T.px0 = range ? uint32_t(range[0]) : 0u; T.px1 = range && range[1] ? uint32_t(range[1]) : T.rows * T.cols;
+    T.format = uint32_t(deep_format); T.part = uint32_t(part);
+    return !range || (range[0] >= 0 && range[1] >= 0);
+}
+// Host only: the shared unit walk (deep.h deep_collect_host) over the source at src -- cap_bytes readable from there -- into
+// the plane at out, which must be a multiple of 16 and hold rows x cols bytes.  range: the pixels [px0, px1) of the flat plane
+// (NULL: all of it; px1 == 0: to the end).  -1: refused.
+int nblic_amd_debug_deep_collect_host(const void *src, size_t cap_bytes, int rows, int cols, size_t pitch_bytes, size_t step_bytes, int deep_format, int part,
+                                      const int *range, unsigned char *out, size_t out_bytes, unsigned long long *units, unsigned long long *chunks) {
+    DeepCollectTask T;
+    if (!src || !out || !debug_deep_collect_task(T, rows, cols, pitch_bytes, step_bytes, deep_format, part, range)) return -1;
+    T.src = static_cast<const uint8_t *>(src); T.dst = out;
+    if (!deep_collect_task_ok(T, cap_bytes) || size_t(T.rows) * size_t(T.cols) > out_bytes) return -1;
+    if (units) *units = deep_collect_units(T);
+    if (chunks) *chunks = deep_collect_chunks(T);
+    deep_collect_host(T);
+    return 0;
+}
+// ONE k_collect_deep launch over n caller-made sources as n tasks, laid out as nblic_amd_debug_collect lays its own out: the
+// bytes of source k at byte base_offsets[k] (0 .. 255) of a region filled with 0xFF that is larger, plane k at byte 256 of a
+// region filled with 0x5A, which comes back whole in outs[k]: out_bytes[k] = 256 + up256(rows x cols) + 256.
+int nblic_amd_debug_deep_collect(nblic_amd_ctx *c, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets, const int *rows,
+                                 const int *cols, const size_t *pitches, const size_t *steps, const int *deep_formats, const int *parts, const int *ranges,
+                                 unsigned char *const *outs, const size_t *out_bytes) {
+    constexpr int kMaxTasks = 65536;
+    constexpr size_t kGuard = 256;
+    if (!c || n < 1 || n > kMaxTasks || !srcs || !src_bytes || !base_offsets || !rows || !cols || !pitches || !steps || !deep_formats || !parts || !outs || !out_bytes) return -1;
+    const size_t count = size_t(n);
+    std::vector<DeepCollectTask> tasks(count);
+    std::vector<size_t> src_at(count), out_at(count);
+    size_t srcs_total = 0, outs_total = 0;
+    for (int k = 0; k < n; k++) {
+        const size_t i = size_t(k);
+        if (!srcs[k] || !outs[k] || base_offsets[k] > 255 || src_bytes[k] > (size_t(1) << 30) ||
+            !debug_deep_collect_task(tasks[i], rows[k], cols[k], pitches[k], steps[k], deep_formats[k], parts[k], ranges ? ranges + 2 * i : nullptr)) return -1;
+        const size_t plane = size_t(rows[k]) * size_t(cols[k]);
+        if (plane > (size_t(1) << 30) || out_bytes[k] != kGuard + up256(plane) + kGuard) return -1;
+        src_at[i] = srcs_total; srcs_total += up256(base_offsets[k] + src_bytes[k] + 256);
+        out_at[i] = outs_total; outs_total += out_bytes[k];
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    Stream st;
+    DevPool mem;
+    uint8_t *d_srcs = mem.make<uint8_t>(srcs_total), *d_outs = mem.make<uint8_t>(outs_total);
+    DeepCollectTask *d_tasks = mem.make<DeepCollectTask>(count);
+    if (!d_srcs || !d_outs || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    unsigned long long chunks = 0;
+    for (int k = 0; k < n; k++) {                                        // the addresses are known now: the rest of the checks
+        const size_t i = size_t(k);
+        DeepCollectTask &T = tasks[i];
+        T.src = d_srcs + src_at[i] + base_offsets[k];
+        T.dst = d_outs + out_at[i] + kGuard;
+        if (!deep_collect_task_ok(T, src_bytes[k])) return -1;           // nothing outside the uploaded bytes is the task's to read
+        T.first_chunk = uint32_t(chunks); chunks += deep_collect_chunks(T);
+    }
+    if (chunks >= (1ull << 31)) return -1;
+    std::vector<uint8_t> back(outs_total);
+    const bool ok = [&]() -> bool {
+        HIP_OK(hipMemsetAsync(d_srcs, 0xFF, srcs_total, st));
+        HIP_OK(hipMemsetAsync(d_outs, 0x5A, outs_total, st));
+        for (int k = 0; k < n; k++)
+            HIP_OK(hipMemcpyAsync(d_srcs + src_at[size_t(k)] + base_offsets[k], srcs[k], src_bytes[k], hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_tasks, tasks.data(), count * sizeof(DeepCollectTask), hipMemcpyHostToDevice, st));
+        c->deep_counts[1] += 1;
+        if (!collect_deep_launch(d_tasks, n, uint32_t(chunks), st)) return false;
+        HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    if (!ok) return -2;
+    for (int k = 0; k < n; k++) memcpy(outs[k], back.data() + out_at[size_t(k)], out_bytes[k]);
+    return 0;
+}
+
+// A debug deep delivery's task: all but the addresses.  window: row0, row1, col0, col1 of planes of plane_rows x width.
+static bool debug_deep_deliver_task(DeepDeliverTask &T, int plane_rows, int width, const int *window, int format, int mode, float scale, float bias, int zero,
+                                    size_t pitch, size_t step) {
+    if (plane_rows < 1 || width < 1 || !window || format < 0 || format >= int(kDeepDestFormats) || mode < 0 || mode > 255 || step > kDeliverMaxStep || pitch > (size_t(1) << 40)) return false;
+    if (window[0] < 0 || window[1] <= window[0] || window[1] > plane_rows || window[2] < 0 || window[3] <= window[2] || window[3] > width) return false;
+    T = DeepDeliverTask{};
+    T.src_pitch = uint32_t(width); T.rows = uint32_t(window[1] - window[0]); T.col0 = uint32_t(window[2]); T.col1 = uint32_t(window[3]);
+    T.format = uint32_t(format); T.mode = uint32_t(mode); T.scale = scale; T.bias = bias; T.zero = zero ? 1u : 0u;
+    T.dst_pitch = pitch; T.dst_step = step ? uint32_t(step) : deep_dest_elem(T.format);
+    return true;
+}
+// Host only: the shared unit walk (deep.h deep_deliver_host) over the caller's two planes of plane_rows x width bytes into
+// out + dst_offset.  The unit grid follows the destination's address as the kernel's does.  gate_status: two ints, the
+// statuses of the high and the low plane's gate records (-1: none).  step_bytes 0 stands for the element size.
+int nblic_amd_debug_deep_deliver_host(const unsigned char *hi, const unsigned char *lo, int plane_rows, int width, const int *window, int format, int mode,
+                                      float scale, float bias, int zero, const int *gate_status, unsigned char *out, size_t out_bytes, size_t dst_offset,
+                                      size_t pitch_bytes, size_t step_bytes, unsigned long long *units, unsigned long long *chunks) {
+    DeepDeliverTask T;
+    if (!hi || !lo || !out || !gate_status || !debug_deep_deliver_task(T, plane_rows, width, window, format, mode, scale, bias, zero, pitch_bytes, step_bytes)) return -1;
+    const size_t skip = size_t(window[0]) * size_t(width), bytes = size_t(plane_rows) * size_t(width) - skip;
+    T.hi = hi + skip; T.lo = lo + skip; T.hi_bytes = T.lo_bytes = bytes;
+    T.dst = out + dst_offset;
+    if (dst_offset > out_bytes || !deep_deliver_task_ok(T)) return -1;
+    if (deep_dest_extent(T.rows, T.col1 - T.col0, T.format, T.dst_pitch, T.dst_step) > out_bytes - dst_offset) return -1;
+    if (units) *units = deep_deliver_units(T);
+    if (chunks) *chunks = deep_deliver_chunks(T);
+    deep_deliver_host(T, gate_status[0] == -1 ? int(kDone) : gate_status[0], gate_status[1] == -1 ? int(kDone) : gate_status[1]);
+    return 0;
+}
+// ONE k_deliver_deep launch over n caller-made plane pairs as n tasks, laid out as nblic_amd_debug_deliver lays its own out:
+// a plane at byte base_offsets[] (0 .. 15; two entries per task: high, low) of a zeroed region of its own that may be read
+// for up256(rows * width) bytes, destination k at byte dst_offsets[k] of a buffer of out_bytes[k] bytes filled with 0x5A, which
+// comes back whole in outs[k]; gate_status: two ints per task.
+int nblic_amd_debug_deep_deliver(nblic_amd_ctx *c, int n, const unsigned char *const *his, const unsigned char *const *los, const size_t *base_offsets,
+                                 const int *plane_rows, const int *widths, const int *windows, const int *formats, const int *modes, const float *scales,
+                                 const float *biases, const int *zeros, const size_t *pitches, const size_t *steps, const size_t *dst_offsets,
+                                 const size_t *out_bytes, unsigned char *const *outs, const int *gate_status) {
+    constexpr int kMaxTasks = 65536;
+    constexpr uint8_t kPattern = 0x5A;
+    if (!c || n < 1 || n > kMaxTasks || !his || !los || !base_offsets || !plane_rows || !widths || !windows || !formats || !modes || !scales || !biases ||
+        !zeros || !pitches || !steps || !dst_offsets || !out_bytes || !outs || !gate_status) return -1;
+    const size_t count = size_t(n);
+    std::vector<DeepDeliverTask> tasks(count);
+    std::vector<size_t> plane_at(2 * count), out_at(count), plane_len(count);
+    size_t planes_total = 0, outs_total = 0;
+    for (int k = 0; k < n; k++) {
+        const size_t i = size_t(k);
+        if (!his[k] || !los[k] || !outs[k] || base_offsets[2 * i] > 15 || base_offsets[2 * i + 1] > 15 ||
+            !debug_deep_deliver_task(tasks[i], plane_rows[k], widths[k], windows + 4 * i, formats[k], modes[k], scales[k], biases[k], zeros[k], pitches[k], steps[k])) return -1;
+        plane_len[i] = size_t(plane_rows[k]) * size_t(widths[k]);
+        if (plane_len[i] > (size_t(1) << 30) || out_bytes[k] > (size_t(1) << 30) || dst_offsets[k] > out_bytes[k]) return -1;
+        for (size_t p = 0; p < 2; p++) { plane_at[2 * i + p] = planes_total; planes_total += up256(base_offsets[2 * i + p] + up256(plane_len[i]) + 16); }
+        out_at[i] = outs_total; outs_total += up256(out_bytes[k]);
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    Stream st;
+    DevPool mem;
+    uint8_t *d_planes = mem.make<uint8_t>(planes_total), *d_outs = mem.make<uint8_t>(std::max<size_t>(outs_total, 256));
+    SerialState *d_gates = mem.make<SerialState>(2 * count);
+    DeepDeliverTask *d_tasks = mem.make<DeepDeliverTask>(count);
+    if (!d_planes || !d_outs || !d_gates || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    for (int k = 0; k < n; k++) {                                        // the addresses are known now: the rest of the checks
+        const size_t i = size_t(k);
+        DeepDeliverTask &T = tasks[i];
+        const size_t skip = size_t(windows[4 * i]) * size_t(widths[k]);
+        T.hi = d_planes + plane_at[2 * i] + base_offsets[2 * i] + skip; T.lo = d_planes + plane_at[2 * i + 1] + base_offsets[2 * i + 1] + skip;
+        T.hi_bytes = T.lo_bytes = up256(plane_len[i]) - skip;
+        T.dst = d_outs + out_at[i] + dst_offsets[k];
+        if (gate_status[2 * i] != -1) T.gate_hi = d_gates + 2 * i;
+        if (gate_status[2 * i + 1] != -1) T.gate_lo = d_gates + 2 * i + 1;
+        if (!deep_deliver_task_ok(T) || deep_dest_extent(T.rows, T.col1 - T.col0, T.format, T.dst_pitch, T.dst_step) > out_bytes[k] - dst_offsets[k]) return -1;
+    }
+    std::vector<uint8_t> back(std::max<size_t>(outs_total, 1));
+    std::vector<SerialState> gates(2 * count);
+    for (size_t k = 0; k < gates.size(); k++) gates[k].status = gate_status[k];
+    const bool ok = [&]() -> bool {
+        HIP_OK(hipMemsetAsync(d_planes, 0, planes_total, st));
+        HIP_OK(hipMemsetAsync(d_outs, kPattern, std::max<size_t>(outs_total, 256), st));
+        HIP_OK(hipMemcpyAsync(d_gates, gates.data(), gates.size() * sizeof(SerialState), hipMemcpyHostToDevice, st));
+        for (int k = 0; k < n; k++) {
+            const size_t i = size_t(k);
+            HIP_OK(hipMemcpyAsync(d_planes + plane_at[2 * i] + base_offsets[2 * i], his[k], plane_len[i], hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemcpyAsync(d_planes + plane_at[2 * i + 1] + base_offsets[2 * i + 1], los[k], plane_len[i], hipMemcpyHostToDevice, st));
+        }
+        if (!deliver_deep_queue(c, tasks.data(), count, d_tasks, st)) return false;
+        HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    if (!ok) return -2;
+    for (int k = 0; k < n; k++) memcpy(outs[k], back.data() + out_at[size_t(k)], out_bytes[k]);
+    return 0;
+}
+
+static bool debug_deep_cost_task(DeepCostTask &T, int rows, int cols, size_t pitch, size_t step, int deep_format) {
+    if (rows < 1 || cols < 1 || rows > int(kCollectMaxSide) || cols > int(kCollectMaxSide) || step > kCollectMaxStep || deep_format < 0) return false;
+    T = DeepCostTask{};
+    T.pitch = pitch; T.step = uint32_t(step); T.rows = uint32_t(rows); T.cols = uint32_t(cols); T.format = uint32_t(deep_format);
+    return true;
+}
+// Host only: the shared tile walk (deep.h deep_cost_host) over ONE source, cap_bytes readable from src.  sums: the costs of
+// the high, the low and the folded low plane, then min and max of u; tiles (may be NULL): the kernel's workgroups.
+int nblic_amd_debug_deep_cost_host(const void *src, size_t cap_bytes, int rows, int cols, size_t pitch_bytes, size_t step_bytes, int deep_format,
+                                   unsigned long long *sums, unsigned long long *tiles) {
+    DeepCostTask T;
+    if (!src || !sums || !debug_deep_cost_task(T, rows, cols, pitch_bytes, step_bytes, deep_format)) return -1;
+    T.src = static_cast<const uint8_t *>(src); T.sums = sums;
+    if (!deep_cost_task_ok(T, cap_bytes)) return -1;
+    if (tiles) *tiles = deep_task_tiles(T);
+    const std::vector<unsigned long long> init = deep_sums_initial(1);
+    memcpy(sums, init.data(), kDeepSums * sizeof(unsigned long long));
+    deep_cost_host(T);
+    return 0;
+}
+// ONE k_deep_cost launch over n caller-made sources as n tasks, each uploaded at byte base_offsets[k] (0 .. 255) of a region
+// of its own filled with 0xFF that is larger.  sums: five numbers per task.
+int nblic_amd_debug_deep_cost(nblic_amd_ctx *c, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets, const int *rows,
+                              const int *cols, const size_t *pitches, const size_t *steps, const int *deep_formats, unsigned long long *sums) {
+    constexpr int kMaxTasks = 65536;
+    if (!c || n < 1 || n > kMaxTasks || !srcs || !src_bytes || !base_offsets || !rows || !cols || !pitches || !steps || !deep_formats || !sums) return -1;
+    const size_t count = size_t(n);
+    std::vector<DeepCostTask> tasks(count);
+    std::vector<size_t> src_at(count);
+    size_t srcs_total = 0;
+    for (size_t i = 0; i < count; i++) {
+        if (!srcs[i] || base_offsets[i] > 255 || src_bytes[i] > (size_t(1) << 30) || !debug_deep_cost_task(tasks[i], rows[i], cols[i], pitches[i], steps[i], deep_formats[i])) return -1;
+        src_at[i] = srcs_total; srcs_total += up256(base_offsets[i] + src_bytes[i] + 256);
+    }
+    if (hipSetDevice(c->device) != hipSuccess) return -2;
+    Stream st;
+    DevPool mem;
+    uint8_t *d_srcs = mem.make<uint8_t>(srcs_total);
+    unsigned long long *d_sums = mem.make<unsigned long long>(count * kDeepSums);
+    DeepCostTask *d_tasks = mem.make<DeepCostTask>(count);
+    if (!d_srcs || !d_sums || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    for (size_t i = 0; i < count; i++) {                                 // the addresses are known now: the rest of the checks
+        tasks[i].src = d_srcs + src_at[i] + base_offsets[i]; tasks[i].sums = d_sums + i * kDeepSums;
+        if (!deep_cost_task_ok(tasks[i], src_bytes[i])) return -1;       // nothing outside the uploaded bytes is the task's to read
+    }
+    const std::vector<unsigned long long> init = deep_sums_initial(count);
+    const bool ok = [&]() -> bool {
+        HIP_OK(hipMemsetAsync(d_srcs, 0xFF, srcs_total, st));
+        HIP_OK(hipMemcpyAsync(d_sums, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+        for (size_t i = 0; i < count; i++) HIP_OK(hipMemcpyAsync(d_srcs + src_at[i] + base_offsets[i], srcs[i], src_bytes[i], hipMemcpyHostToDevice, st));
+        if (!deep_cost_queue(c, tasks.data(), count, d_tasks, st)) return false;
+        HIP_OK(hipMemcpyAsync(sums, d_sums, count * kDeepSums * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return true;
+    }();
+    if (st) hipStreamSynchronize(st);
+    return ok ? 0 : -2;
+}
+
 int nblic_amd_indexed_decode_split(nblic_amd_ctx *c, double ms[4]) {
     if (!c || !ms) return -1;
     std::lock_guard<std::mutex> l(c->stat_m);

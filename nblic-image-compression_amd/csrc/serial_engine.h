@@ -22,6 +22,7 @@
 #include "collect.h"
 #include "color_plan.h"
 #include "stack.h"
+#include "deep.h"
 
 namespace nblic {
 
@@ -225,6 +226,17 @@ bool deliver_stack_launch(const StackDeliverTask *d_tasks, int n, const StackSli
 // The workgroup walks the slices with two LDS tile buffers and adds two sums per slice -- the slice's own cost and that of
 // its difference against the slice before -- to the task's costs (zeroed by the caller) with 64-bit atomics.
 bool stack_cost_launch(const StackCostTask *d_tasks, int n, const StackCostSlice *d_slices, uint32_t tiles, hipStream_t s);
+
+// ---- deep pixels (deep.h) ------------------------------------------------------------------------------------------------------
+// k_collect_deep, beside k_collect: one task is one PLANE of a 16-bit source -- high, low or folded low -- in k_collect's
+// units; sixteen neighbouring elements are read as eight aligned words where the step is 2 and the address allows.
+bool collect_deep_launch(const DeepCollectTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
+// k_deliver_deep, beside k_deliver: one task is one deep image -- both planes, both gates, the mode, the window -- in
+// k_deliver's units; a contiguous uint16 unit is two 16-byte stores, a float32 unit four.
+bool deliver_deep_launch(const DeepDeliverTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
+// k_deep_cost, beside k_color_cost: one workgroup per tile of one image; three sums, the minimum and the maximum of u per
+// image, by 64-bit atomics (sums zeroed, min 0xFFFF and max 0 before the launch: the caller's).
+bool deep_cost_launch(const DeepCostTask *d_tasks, int n, uint32_t tiles, hipStream_t s);
 
 // ---- a packed index (index_pack.h), expanded on the device ------------------------------------------------------------------
 // A packed index is uploaded as it is (any address).  The bodies of the entries a round needs are written, unpacked, into an

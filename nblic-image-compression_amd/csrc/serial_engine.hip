@@ -2218,6 +2218,210 @@ bool stack_cost_launch(const StackCostTask *d_tasks, int n, const StackCostSlice
     return hipGetLastError() == hipSuccess;
 }
 
+// ---- deep pixels: a 16-bit source as a high and a (folded) low plane (deep.h) ---------------------------------------------------
+// The sixteen 16-bit values u of a unit, slot k in half k of cell[] (slot 2i in the low half of cell[i]), the slots outside
+// [k_lo, k_hi) zero.  (row, col): the image position of slot k_lo.  Sixteen elements that are neighbours in one row
+// (step == 2) at a multiple of four bytes are read as eight aligned words, every other unit element by element: no byte is
+// read that is not part of an element of the image.
+__device__ __forceinline__ void deep_unit_load(const NB_GLOBAL uint8_t *src, unsigned long long pitch, uint32_t step, uint32_t cols, uint32_t format,
+                                               uint32_t row, uint32_t col, uint32_t k_lo, uint32_t k_hi, uint32_t cell[8]) {
+    const NB_GLOBAL uint8_t *s = src + (unsigned long long)(row) * pitch + (unsigned long long)(col) * step;
+    if (step == 2 && k_hi - k_lo == 16 && cols - col >= 16 && !(uintptr_t(s) & 3)) {
+        const NB_GLOBAL uint32_t *q = (const NB_GLOBAL uint32_t *)s;
+        const uint32_t flip = format == kDeepI16 ? 0x80008000u : 0u;     // deep_u of both halves at once
+#pragma unroll
+        for (int i = 0; i < 8; i++) cell[i] = q[i] ^ flip;
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) cell[i] = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++) {
+        if (k < k_lo || k >= k_hi) continue;
+        cell[k >> 1] |= deep_u(*(const NB_GLOBAL uint16_t *)s, format) << ((k & 1) * 16);
+        if (++col == cols) { col = 0; row++; s = src + (unsigned long long)(row) * pitch; } else s += step;
+    }
+}
+
+// k_collect's launch shape and units (collect.h): one workgroup per chunk, one unit per lane and step -- sixteen consecutive
+// bytes of the flat plane, out of sixteen source elements loaded by deep_unit_load.  A whole unit is one 16-byte store; the
+// shorter first and last units of a task are written in words and bytes.  No LDS, no atomics; nothing is written outside
+// the task's pixels [px0, px1).
+__global__ void __launch_bounds__(kIndexThreads) k_collect_deep(const DeepCollectTask *__restrict__ tasks, int n) {
+    const DeepCollectTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
+    const CollectTask W = deep_collect_walk(T);
+    const uint32_t units = collect_task_units(W), u0 = (blockIdx.x - T.first_chunk) * kCollectChunkUnits;
+    for (uint32_t j = threadIdx.x; j < kCollectChunkUnits; j += kIndexThreads) {
+        const uint32_t u = u0 + j;
+        if (u >= units) break;
+        const CollectUnit U = collect_unit_of(W, u);
+        const uint32_t k_lo = U.p_lo - U.p0, k_hi = U.p_hi - U.p0;
+        const uint32_t row = U.p_lo / T.cols, col = U.p_lo - row * T.cols;
+        uint32_t cell[8], word[4] = {0u, 0u, 0u, 0u};
+        deep_unit_load(gp(T.src), T.pitch, T.step, T.cols, T.format, row, col, k_lo, k_hi, cell);
+#pragma unroll
+        for (uint32_t k = 0; k < 16; k++) word[k >> 2] |= deep_part((cell[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu, T.part) << ((k & 3) * 8);
+        NB_GLOBAL uint8_t *d = gp(T.dst) + U.p0;
+        if (k_hi - k_lo == 16) { *(NB_GLOBAL u32x4 *)d = u32x4{word[0], word[1], word[2], word[3]}; continue; }
+#pragma unroll
+        for (uint32_t b = 0; b < 4; b++) {
+            if (k_lo <= 4 * b && 4 * b + 4 <= k_hi) { ((NB_GLOBAL uint32_t *)d)[b] = word[b]; continue; }
+#pragma unroll
+            for (uint32_t k = 4 * b; k < 4 * b + 4; k++)
+                if (k >= k_lo && k < k_hi) d[k] = uint8_t(word[b] >> ((k & 3) * 8));
+        }
+    }
+}
+
+bool collect_deep_launch(const DeepCollectTask *d_tasks, int n, uint32_t chunks, hipStream_t s) {
+    if (n <= 0 || chunks == 0) return true;
+    hipLaunchKernelGGL(k_collect_deep, dim3(chunks), dim3(kIndexThreads), 0, s, d_tasks, n);
+    return hipGetLastError() == hipSuccess;
+}
+
+// k_deliver's launch shape and units (deliver.h): one workgroup per chunk, one unit per lane and step.  A contiguous
+// destination: the unit's sixteen bytes of BOTH planes (deliver_load), joined and converted (deep.h deep_join, deep_value),
+// stored in whole 16-byte blocks but for a row's head and tail (deliver_store: two blocks for a 2-byte element, four for
+// float32).  A strided destination: the lanes along the row, element by element, as deliver_strided_chunk.  If the task's
+// zero flag is set or either gate is not kDone the window gets zeros and no plane is read.  No LDS, no atomics; nothing is
+// read outside the planes' readable bytes and nothing written outside the window.
+__global__ void __launch_bounds__(kIndexThreads) k_deliver_deep(const DeepDeliverTask *__restrict__ tasks, int n) {
+    const DeepDeliverTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
+    const DeliverTask W = deep_window(T);
+    const bool zero = T.zero != 0 || (T.gate_hi && gp(T.gate_hi)->status != kDone) || (T.gate_lo && gp(T.gate_lo)->status != kDone);
+    const uint32_t units = uint32_t(deliver_task_units(W)), u0 = (blockIdx.x - T.first_chunk) * kDeliverChunkUnits;
+    const uint32_t elem = deep_dest_elem(T.format);
+    if (deliver_strided(W)) {
+        for (uint32_t p = threadIdx.x; p < kDeliverChunkUnits * kDeliverUnitPixels; p += kIndexThreads) {
+            const uint32_t u = u0 + p / kDeliverUnitPixels;
+            if (u >= units) break;
+            const DeliverUnit U = deliver_strided_unit_of(W, u);
+            const uint32_t c = U.c_lo + p % kDeliverUnitPixels;
+            if (c >= U.c_hi) continue;
+            uint32_t v = 0u;
+            if (!zero) {
+                const size_t at = size_t(U.row) * T.src_pitch + size_t(T.col0) + c;
+                v = deep_value(deep_join(gp(T.hi)[at], gp(T.lo)[at], T.mode), T.mode, T.format, T.scale, T.bias);
+            }
+            NB_GLOBAL uint8_t *d = gp(T.dst) + size_t(U.row) * size_t(T.dst_pitch) + size_t(c) * size_t(T.dst_step);
+            if (elem == 2) *(NB_GLOBAL uint16_t *)d = uint16_t(v);
+            else *(NB_GLOBAL uint32_t *)d = v;
+        }
+        return;
+    }
+    for (uint32_t j = threadIdx.x; j < kDeliverChunkUnits; j += kIndexThreads) {
+        const uint32_t u = u0 + j;
+        if (u >= units) break;
+        const DeliverUnit U = deliver_unit_of(W, u);
+        if (U.c_lo == U.c_hi) continue;
+        const uint32_t k_lo = uint32_t(int(U.c_lo) - U.c0), k_hi = uint32_t(int(U.c_hi) - U.c0);
+        NB_GLOBAL uint8_t *d = gp(T.dst) + size_t(U.row) * size_t(T.dst_pitch) + ptrdiff_t(U.c0) * ptrdiff_t(elem);
+        u32x4 h = u32x4{0u, 0u, 0u, 0u}, l = h;
+        if (!zero) {
+            h = deliver_load(gp(T.hi) + size_t(U.row) * T.src_pitch + size_t(T.col0) + ptrdiff_t(U.c0), uintptr_t(T.hi), uintptr_t(T.hi) + T.hi_bytes, k_lo, k_hi);
+            l = deliver_load(gp(T.lo) + size_t(U.row) * T.src_pitch + size_t(T.col0) + ptrdiff_t(U.c0), uintptr_t(T.lo), uintptr_t(T.lo) + T.lo_bytes, k_lo, k_hi);
+        }
+        const uint32_t hw[4] = {h.x, h.y, h.z, h.w}, lw[4] = {l.x, l.y, l.z, l.w};
+        auto joined = [&](uint32_t k) { return deep_join((hw[k >> 2] >> ((k & 3) * 8)) & 0xFFu, (lw[k >> 2] >> ((k & 3) * 8)) & 0xFFu, T.mode); };
+        switch (T.format) {                                              // (zero: +0.0 is zero bytes in every format)
+            case kDeepToU16: deliver_store<2>(d, k_lo, k_hi, [&](uint32_t k) { return zero ? 0u : deep_value(joined(k), T.mode, kDeepToU16, 1.0f, 0.0f); }); break;
+            case kDeepToI16: deliver_store<2>(d, k_lo, k_hi, [&](uint32_t k) { return zero ? 0u : deep_value(joined(k), T.mode, kDeepToI16, 1.0f, 0.0f); }); break;
+            case kDeepToF16: deliver_store<2>(d, k_lo, k_hi, [&](uint32_t k) { return zero ? 0u : deep_value(joined(k), T.mode, kDeepToF16, T.scale, T.bias); }); break;
+            case kDeepToBF16: deliver_store<2>(d, k_lo, k_hi, [&](uint32_t k) { return zero ? 0u : deep_value(joined(k), T.mode, kDeepToBF16, T.scale, T.bias); }); break;
+            default: deliver_store<4>(d, k_lo, k_hi, [&](uint32_t k) { return zero ? 0u : deep_value(joined(k), T.mode, kDeepToF32, T.scale, T.bias); }); break;
+        }
+    }
+}
+
+bool deliver_deep_launch(const DeepDeliverTask *d_tasks, int n, uint32_t chunks, hipStream_t s) {
+    if (n <= 0 || chunks == 0) return true;
+    hipLaunchKernelGGL(k_deliver_deep, dim3(chunks), dim3(kIndexThreads), 0, s, d_tasks, n);
+    return hipGetLastError() == hipSuccess;
+}
+
+// LDS row r of a tile holds image row y0 + r - 1 in 2-byte cells: cell 1 the column to the left, cells 2 .. 65 the tile's
+// columns (cell 0 is not used), so a unit of sixteen cells is eight whole words.  33 words a row: the pitch is odd, as
+// k_color_cost's 17, so the words of neighbouring rows lie on different banks when the staging lanes of a wave -- four units
+// of sixteen rows -- write them; the cost lanes of a wave read 65 neighbouring cells of ONE row, 33 neighbouring words, two
+// lanes to a word, and meet no conflict at any pitch.
+constexpr uint32_t kDeepLdsRows = kColorTile + 1;
+constexpr uint32_t kDeepLdsPitch = kColorTile / 2 + 1;               // words
+constexpr uint32_t kDeepLdsCells = 2 * kDeepLdsPitch;
+
+// One workgroup per tile.  STAGE: the tile's rows and the row above as units of sixteen elements (deep_unit_load: aligned
+// words where the elements are neighbours), the column to the left element by element; every source element is read once
+// apart from the halo and nothing outside the image is read.  COST: a lane per column, a wave per sixteen rows, top down, so
+// N and NW of a pixel are the lane's own value and W of the row before; the three planes' costs by deep.h's own functions.
+// SUM: over the wave by shuffles, over the four waves in LDS, then three 64-bit atomic adds, one atomic min and one max.
+__global__ void __launch_bounds__(kIndexThreads) k_deep_cost(const DeepCostTask *__restrict__ tasks, int n) {
+    __shared__ uint32_t lds[kDeepLdsRows * kDeepLdsPitch];
+    __shared__ uint32_t part[kIndexThreads / 64][kDeepSums];
+    const DeepCostTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
+    const uint32_t rows = T.rows, cols = T.cols;
+    const uint32_t across = deep_tiles_across(T), tile = blockIdx.x - T.first_chunk;
+    const uint32_t y0 = (tile / across) * kColorTile, x0 = (tile % across) * kColorTile;
+    uint16_t *cells = reinterpret_cast<uint16_t *>(lds);
+    for (uint32_t j = threadIdx.x; j < kDeepLdsRows * kColorRowUnits; j += kIndexThreads) {
+        const uint32_t r = j / kColorRowUnits, q = j % kColorRowUnits;
+        const uint32_t y = y0 + r - 1u, x = x0 + q * kCollectUnitPixels;
+        if ((r == 0 && y0 == 0) || y >= rows || x >= cols) continue;
+        uint32_t cell[8];
+        deep_unit_load(gp(T.src), T.pitch, T.step, cols, T.format, y, x, 0u, cols - x < 16u ? cols - x : 16u, cell);
+        uint32_t *o = lds + r * kDeepLdsPitch + 1u + q * (kCollectUnitPixels / 2u);
+#pragma unroll
+        for (int i = 0; i < 8; i++) o[i] = cell[i];
+    }
+    if (x0 > 0 && threadIdx.x < kDeepLdsRows) {
+        const uint32_t r = threadIdx.x, y = y0 + r - 1u;
+        if (!(r == 0 && y0 == 0) && y < rows) {
+            uint32_t cell[8];
+            deep_unit_load(gp(T.src), T.pitch, T.step, cols, T.format, y, x0 - 1u, 0u, 1u, cell);
+            cells[r * kDeepLdsCells + 1u] = uint16_t(cell[0]);
+        }
+    }
+    __syncthreads();
+    const uint32_t wave = threadIdx.x / 64u, lane = threadIdx.x % 64u, x = x0 + lane;
+    uint32_t sums[kDeepParts] = {}, lo = 0xFFFFu, hi = 0u;
+    if (x < cols) {
+        const uint32_t r0 = wave * 16u;                              // the wave's first tile row; LDS row r0 is the one above it
+        const uint16_t *row = cells + r0 * kDeepLdsCells + 1u + lane;
+        uint32_t nw = row[0], nn = row[1];                           // (row 0 or column 0 of the image: never looked at)
+        for (uint32_t r = r0; r < r0 + 16u && y0 + r < rows; r++) {
+            row += kDeepLdsCells;
+            const uint32_t w = row[0], p = row[1];
+            deep_pixel_costs(p, w, nn, nw, y0 + r, x, sums);
+            lo = p < lo ? p : lo; hi = p > hi ? p : hi;
+            nn = p; nw = w;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (uint32_t k = 0; k < kDeepParts; k++) sums[k] += __shfl_down(sums[k], off, 64);      // (at most 16 x 17 a lane)
+        const uint32_t a = __shfl_down(lo, off, 64), b = __shfl_down(hi, off, 64);
+        lo = a < lo ? a : lo; hi = b > hi ? b : hi;
+    }
+    if (lane == 0) { part[wave][0] = sums[0]; part[wave][1] = sums[1]; part[wave][2] = sums[2]; part[wave][3] = lo; part[wave][4] = hi; }
+    __syncthreads();
+    if (threadIdx.x < kDeepSums) {
+        const uint32_t k = threadIdx.x;
+        unsigned long long total = part[0][k];
+        for (uint32_t wv = 1; wv < kIndexThreads / 64; wv++) {
+            const unsigned long long v = part[wv][k];
+            total = k < kDeepParts ? total + v : (k == 3 ? (v < total ? v : total) : (v > total ? v : total));
+        }
+        if (k < kDeepParts) atomicAdd(T.sums + k, total);
+        else if (k == 3) atomicMin(T.sums + 3, total);
+        else atomicMax(T.sums + 4, total);
+    }
+}
+
+bool deep_cost_launch(const DeepCostTask *d_tasks, int n, uint32_t tiles, hipStream_t s) {
+    if (n <= 0 || tiles == 0) return true;
+    hipLaunchKernelGGL(k_deep_cost, dim3(tiles), dim3(kIndexThreads), 0, s, d_tasks, n);
+    return hipGetLastError() == hipSuccess;
+}
+
 
 // ---- a packed index, expanded on the device (serial_engine.h IndexUnpackTask; the format: index_pack.h) --------------------
 constexpr uint32_t kUnpackWaves = kIndexThreads / 64;

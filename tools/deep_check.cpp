@@ -1,0 +1,206 @@
+// Stand-alone check of csrc/deep.h (host only): the three walks -- collect, deliver, cost -- over the host tests' shapes and
+// layouts, for both source formats, all three parts, all five destination formats and all four modes, against restatements
+// that know nothing of units, words or tiles.  Every source and plane is a heap block of EXACTLY its extent -- a read outside
+// it is an overrun the sanitizer reports -- and every destination a block filled with a pattern that is compared whole, so a
+// byte written outside a window shows wherever it lands.  The restatements work in wide integers and doubles: a plane byte by
+// division and remainder, a delivered element by two roundings through doubles, a cost by a plane walk with its own MED and
+// its own bit length.  Also the round trip of every 16-bit value under every mode, and the rule.
+// Build and run:
+//   g++ -std=c++17 -O2 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -o deep_check tools/deep_check.cpp && ./deep_check
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <random>
+#include <vector>
+
+#include "../nblic-image-compression_amd/csrc/deep.h"
+
+using namespace nblic;
+
+#define CHECK(x) do { if (!(x)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); return 1; } } while (0)
+
+static const int kShapes[][2] = {{1, 1}, {1, 17}, {3, 5}, {33, 65}, {64, 64}, {65, 130}};
+static const uint32_t kEdges[] = {0, 255, 256, 257, 0x7FFF, 0x8000, 0xFFFF};
+constexpr uint8_t kPattern = 0x5A;
+
+// u of a source element, restated: the value as a wide integer, plus 32768 for a signed source.
+static long u_ref(uint16_t bits, uint32_t format) { return format == kDeepI16 ? long(int16_t(bits)) + 32768 : long(bits); }
+static uint8_t part_ref(long u, uint32_t part) {
+    const long hi = u / 256, lo = u % 256;
+    return uint8_t(part == kDeepHigh ? hi : (part == kDeepLow || hi % 2 == 0 ? lo : 255 - lo));
+}
+// One delivered element's bits, restated: the two roundings through doubles, then the format.
+static uint32_t element_ref(long u, uint32_t mode, uint32_t format, float scale, float bias) {
+    if (format == kDeepToU16) return uint32_t(u);
+    if (format == kDeepToI16) return uint32_t(uint16_t(int16_t(u - 32768)));
+    const long v = (mode & kDeepSigned) ? u - 32768 : u;
+    const float prod = float(double(v) * double(scale));
+    const float val = float(double(prod) + double(bias));
+    uint32_t bits;
+    memcpy(&bits, &val, 4);
+    if (format == kDeepToF32) return bits;
+    if (format == kDeepToBF16) return deliver_bf16_bits(bits);
+    // binary16 by its definition: the nearest of the representable neighbours, ties to even, overflow to infinity
+    if (val != val) return 0x7E00u;
+    const uint32_t sign = bits >> 31 ? 0x8000u : 0u;
+    const double a = std::fabs(double(val));
+    if (a >= 65520.0) return sign | 0x7C00u;
+    if (a < std::ldexp(1.0, -25)) return sign;
+    int e;
+    std::frexp(a, &e);                                                // a = m * 2^e, m in [0.5, 1)
+    const int q = std::max(e - 11, -24);                              // the spacing of halves around a is 2^q
+    const double units = std::nearbyint(std::ldexp(a, -q));           // ties to even (the default rounding mode)
+    const double r = std::ldexp(units, q);
+    if (r >= 65520.0) return sign | 0x7C00u;
+    int e2;
+    std::frexp(r, &e2);
+    if (r < std::ldexp(1.0, -14)) return sign | uint32_t(std::ldexp(r, 24));
+    return sign | (uint32_t(e2 - 1 + 15) << 10) | (uint32_t(std::ldexp(r, 11 - e2)) & 0x3FFu);
+}
+static int bitlen_ref(long v) { int k = 0; while (v > 0) { v /= 2; k++; } return k; }
+static unsigned long long plane_cost_ref(const std::vector<long> &p, int h, int w) {
+    unsigned long long sum = 0;
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            long pred;
+            if (y == 0) pred = x == 0 ? 128 : p[size_t(x) - 1];
+            else if (x == 0) pred = p[size_t(y - 1) * w];
+            else {
+                const long W = p[size_t(y) * w + x - 1], N = p[size_t(y - 1) * w + x], NW = p[size_t(y - 1) * w + x - 1];
+                pred = NW >= std::max(W, N) ? std::min(W, N) : (NW <= std::min(W, N) ? std::max(W, N) : W + N - NW);
+            }
+            sum += 2ull * unsigned(bitlen_ref(std::labs(p[size_t(y) * w + x] - pred))) + 1ull;
+        }
+    return sum;
+}
+
+struct Source { std::vector<uint8_t> *block; const uint8_t *src; size_t pitch, step, cap; std::vector<uint16_t> bits; };
+// An h x w image in layout k (0 contiguous, 1 pitched, 2 step 6, 3 an odd number of elements into the block), the bytes
+// between the elements 0xFF, the block exactly as long as offset + extent.
+static Source lay_out(std::mt19937 &rng, int h, int w, int k, std::vector<std::vector<uint8_t> *> &keep) {
+    Source S;
+    S.step = k == 2 ? 6 : 2;
+    S.pitch = size_t(w) * S.step + (k == 0 ? 0 : 2 * (1 + rng() % 8));
+    const size_t offset = k == 3 ? 2 * (2 * (rng() % 8) + 1) : 0;
+    S.cap = size_t(h - 1) * S.pitch + size_t(w - 1) * S.step + 2;
+    S.block = new std::vector<uint8_t>(offset + S.cap, 0xFF);
+    keep.push_back(S.block);
+    S.src = S.block->data() + offset;
+    S.bits.resize(size_t(h) * w);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            uint16_t v = uint16_t(20000 + 37 * x + 91 * y + int(rng() % 600) - 300);
+            if (rng() % 16 == 0) v = uint16_t(kEdges[rng() % 7]);
+            S.bits[size_t(y) * w + x] = v;
+            memcpy(S.block->data() + offset + size_t(y) * S.pitch + size_t(x) * S.step, &v, 2);
+        }
+    return S;
+}
+
+int main() {
+    std::mt19937 rng(28);
+    std::vector<std::vector<uint8_t> *> keep;
+    long collects = 0, delivers = 0, costs = 0;
+    // every 16-bit value through both directions, under every mode
+    for (uint32_t mode = 0; mode < 4; mode++)
+        for (uint32_t x = 0; x < 65536; x++) {
+            const uint32_t format = (mode & kDeepSigned) ? kDeepI16 : kDeepU16, u = deep_u(x, format);
+            CHECK(long(u) == u_ref(uint16_t(x), format));
+            const uint32_t hi = deep_part(u, kDeepHigh), lo = deep_part(u, (mode & kDeepFold) ? kDeepLowFolded : kDeepLow);
+            CHECK(hi == part_ref(u, kDeepHigh) && lo == part_ref(u, (mode & kDeepFold) ? kDeepLowFolded : kDeepLow));
+            CHECK(deep_join(hi, lo, mode) == u);
+            CHECK(deep_value(u, mode, format == kDeepI16 ? kDeepToI16 : kDeepToU16, 1.0f, 0.0f) == x);
+            for (uint32_t f = kDeepToF16; f <= kDeepToF32; f++)
+                for (int n = 0; n < 2; n++) {
+                    const float scale = n ? 1.0f / 257.0f : 1.0f, bias = n ? -3.5f : 0.0f;
+                    CHECK(deep_value(u, mode, f, scale, bias) == element_ref(u, mode, f, scale, bias));
+                }
+        }
+    // the fold makes the low byte continuous
+    for (uint32_t u = 1; u < 65536; u++) CHECK(std::abs(int(deep_part(u, kDeepLowFolded)) - int(deep_part(u - 1, kDeepLowFolded))) <= 1);
+    // the rule: strictly cheaper folds, a tie is plain, bit 1 from the format
+    {
+        const unsigned long long a[3] = {5, 10, 9}, b[3] = {5, 10, 10}, c[3] = {5, 9, 10}, d[3] = {0, ~0ull, ~0ull - 1};
+        CHECK(deep_choose(a, kDeepU16) == 1 && deep_choose(a, kDeepI16) == 3 && deep_choose(b, kDeepU16) == 0 && deep_choose(b, kDeepI16) == 2);
+        CHECK(deep_choose(c, kDeepU16) == 0 && deep_choose(d, kDeepU16) == 1);
+        CHECK(deep_mode_valid(0) && deep_mode_valid(3) && !deep_mode_valid(4) && !deep_mode_valid(kDeepRefused));
+    }
+    for (const auto &shape : kShapes) {
+        const int h = shape[0], w = shape[1];
+        for (int layout = 0; layout < 4; layout++)
+            for (uint32_t format = 0; format < kDeepSrcFormats; format++) {
+                const Source S = lay_out(rng, h, w, layout, keep);
+                std::vector<long> u(S.bits.size());
+                for (size_t i = 0; i < u.size(); i++) u[i] = u_ref(S.bits[i], format);
+                // collect: every part, whole and as a range with a short first and a short last unit
+                for (uint32_t part = 0; part < kDeepParts; part++)
+                    for (int ranged = 0; ranged < 2; ranged++) {
+                        const uint32_t n = uint32_t(h) * uint32_t(w), p0 = ranged && n > 40 ? 5 : 0, p1 = ranged && n > 40 ? n - 3 : n;
+                        std::vector<uint8_t> store(n + 16, kPattern);
+                        uint8_t *out = store.data() + (16 - uintptr_t(store.data()) % 16) % 16;
+                        DeepCollectTask T{};
+                        T.src = S.src; T.dst = out; T.pitch = S.pitch; T.step = uint32_t(S.step); T.rows = uint32_t(h); T.cols = uint32_t(w);
+                        T.px0 = p0; T.px1 = p1; T.format = format; T.part = part;
+                        CHECK(deep_collect_task_ok(T, S.cap) && !deep_collect_task_ok(T, S.cap - 1));
+                        deep_collect_host(T);
+                        for (uint32_t i = 0; i < n; i++) CHECK(out[i] == (i >= p0 && i < p1 ? part_ref(u[i], part) : kPattern));
+                        collects++;
+                    }
+                // cost
+                {
+                    unsigned long long sums[kDeepSums] = {0, 0, 0, 0xFFFF, 0};
+                    DeepCostTask T{};
+                    T.src = S.src; T.pitch = S.pitch; T.step = uint32_t(S.step); T.rows = uint32_t(h); T.cols = uint32_t(w); T.format = format; T.sums = sums;
+                    CHECK(deep_cost_task_ok(T, S.cap) && !deep_cost_task_ok(T, S.cap - 1));
+                    deep_cost_host(T);
+                    for (uint32_t part = 0; part < kDeepParts; part++) {
+                        std::vector<long> p(u.size());
+                        for (size_t i = 0; i < u.size(); i++) p[i] = part_ref(u[i], part);
+                        CHECK(sums[part] == plane_cost_ref(p, h, w));
+                    }
+                    CHECK(long(sums[3]) == *std::min_element(u.begin(), u.end()) && long(sums[4]) == *std::max_element(u.begin(), u.end()));
+                    costs++;
+                }
+                // deliver: the planes as blocks of exactly rows x cols bytes; every destination format, contiguous at 2 mod 16
+                // with a pitch of its own, strided, and transposed; a window with a head and a tail; a gate that is not done
+                for (uint32_t dformat = 0; dformat < kDeepDestFormats; dformat++)
+                    for (int kind = 0; kind < 4; kind++) {
+                        uint32_t mode = (rng() & 1u) | (format == kDeepI16 ? kDeepSigned : 0u);
+                        if (dformat == kDeepToU16) mode &= ~uint32_t(kDeepSigned);
+                        if (dformat == kDeepToI16) mode |= kDeepSigned;
+                        std::vector<uint8_t> *hi = new std::vector<uint8_t>(u.size()), *lo = new std::vector<uint8_t>(u.size());
+                        keep.push_back(hi); keep.push_back(lo);
+                        for (size_t i = 0; i < u.size(); i++) { (*hi)[i] = part_ref(u[i], kDeepHigh); (*lo)[i] = part_ref(u[i], (mode & kDeepFold) ? kDeepLowFolded : kDeepLow); }
+                        const bool inner = kind != 0 && h > 2 && w > 2;
+                        const uint32_t r0 = inner ? 1 : 0, r1 = uint32_t(h) - (inner ? 1 : 0), c0 = inner ? 1 : 0, c1 = uint32_t(w) - (inner ? 1 : 0);
+                        const uint32_t rows = r1 - r0, cols = c1 - c0, elem = deep_dest_elem(dformat);
+                        const size_t step = kind == 2 ? 3 * elem : (kind == 3 ? size_t(rows + 1) * elem : elem);
+                        const size_t pitch = kind == 3 ? elem : cols * step + (kind == 0 ? 0 : 6 * elem);
+                        const size_t offset = kind == 0 ? 32 : 16 + elem * (1 + rng() % 3);
+                        const size_t bytes = offset + deep_dest_extent(rows, cols, dformat, pitch, step) + 24;
+                        std::vector<uint8_t> store(bytes + 16, kPattern), want(bytes, kPattern);
+                        uint8_t *out = store.data() + (16 - uintptr_t(store.data()) % 16) % 16;
+                        const bool floats = dformat >= kDeepToF16;
+                        const int gates[2] = {kind == 2 && layout == 1 ? 3 : 1, 1};
+                        DeepDeliverTask T{};
+                        T.hi = hi->data() + size_t(r0) * w; T.lo = lo->data() + size_t(r0) * w; T.hi_bytes = T.lo_bytes = size_t(h - int(r0)) * w;
+                        T.dst = out + offset; T.dst_pitch = pitch; T.dst_step = uint32_t(step);
+                        T.src_pitch = uint32_t(w); T.rows = rows; T.col0 = c0; T.col1 = c1; T.format = dformat; T.mode = mode;
+                        T.scale = floats && layout % 2 ? 1.0f / 257.0f : 1.0f; T.bias = floats && layout % 2 ? -3.5f : 0.0f;
+                        CHECK(deep_deliver_task_ok(T));
+                        deep_deliver_host(T, gates[0], gates[1]);
+                        for (uint32_t r = 0; r < rows; r++)
+                            for (uint32_t c = 0; c < cols; c++) {
+                                const uint32_t v = gates[0] == 1 ? element_ref(u[size_t(r0 + r) * w + c0 + c], mode, dformat, T.scale, T.bias) : 0u;
+                                memcpy(want.data() + offset + r * pitch + c * step, &v, elem);
+                            }
+                        CHECK(memcmp(out, want.data(), bytes) == 0);
+                        delivers++;
+                    }
+            }
+    }
+    for (auto *b : keep) delete b;
+    printf("deep_check: ok -- %ld collect walks, %ld deliver walks, %ld cost walks, 4 x 65536 values round-tripped\n", collects, delivers, costs);
+    return 0;
+}
