@@ -154,6 +154,24 @@ void nblic_amd_device_coder_stats(nblic_amd_ctx *ctx, double *bins, long *packs,
  * No output byte depends on the path.  Returns 0, -1 for bad arguments.                                          */
 int nblic_amd_copy_stats(nblic_amd_ctx *ctx, long out[4]);
 
+/* How the context's group streams were spread over the hardware queues of the process when it was created.  A process
+ * has a few in-order hardware queues and the runtime deals every stream to one of them by a rule of its own; a context
+ * of three groups or more therefore creates candidate streams, sorts them into classes with a probe ("does a short
+ * kernel on b wait behind a 1 ms kernel on a?"; the least of three repetitions decides), gives the groups streams whose
+ * classes hold numbers of groups that differ by one at the most, and destroys the rest.  It asks the runtime for no
+ * queue it would not have given anyway.  NBLIC_AMD_QUEUE_PLAN=0 (read at creation) switches the plan off.
+ *   out[0] 0 the plan is on; otherwise every group created its own stream, as the runtime dealt them, because
+ *          1 the context has fewer than three groups (nothing ran)   2 the switch   3 one class only was found
+ *          4 a probe was inconclusive                               5 a call of the runtime failed
+ *   out[1] classes found (the hardware queues the candidates reached; 0 when the classification did not finish)
+ *   out[2] candidate streams created            out[3] groups of the context
+ *   out[4] largest minus smallest number of groups over the classes found, as planned
+ *   out[5] the same for the first out[3] candidates: what not planning would have given
+ *   out[8 + k], k < out[1]: groups in class k (0 on: they sum to out[3]; 3: all in class 0)
+ * *plan_ms (may be NULL): host milliseconds the plan took.  No output byte depends on any of this.  Returns 0, -1 for
+ * bad arguments.                                                                                                  */
+int nblic_amd_queue_plan_stats(nblic_amd_ctx *ctx, long out[40], double *plan_ms);
+
 /* Opt-in: raise the pixel-count limit above NBLIC_MAX_IMG_SIZE for this context (config 5 of
  * BASELINE.json exceeds the reference's own limit, src/NBLIC.h:31).  0 restores the reference limit.
  * ctx == NULL addresses the context behind the drop-in entry points of section 1.                   */

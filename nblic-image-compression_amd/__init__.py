@@ -72,7 +72,7 @@ EXPORTS = (
     "nblic_amd_debug_deep_collect_host", "nblic_amd_debug_deep_collect", "nblic_amd_debug_deep_deliver_host", "nblic_amd_debug_deep_deliver",
     "nblic_amd_debug_deep_cost_host", "nblic_amd_debug_deep_cost",
     "nblic_amd_cli_main", "nblic_amd_cli_parse", "nblic_amd_read_gray", "nblic_amd_write_gray",
-    "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats", "nblic_amd_copy_stats",
+    "nblic_amd_set_device_coder", "nblic_amd_device_coder_stats", "nblic_amd_copy_stats", "nblic_amd_queue_plan_stats",
     "nblic_amd_range_code", "nblic_amd_range_code_multi", "nblic_amd_range_code_chunked", "nblic_amd_range_code_packs", "nblic_amd_pack_groups_host", "nblic_amd_selftest", "nblic_amd_syn1", "nblic_amd_version",
 )
 
@@ -160,6 +160,9 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "nblic_amd_copy_stats"):                       # (an older build loaded through NBLIC_AMD_LIB has none)
         lib.nblic_amd_copy_stats.restype = C.c_int
         lib.nblic_amd_copy_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+    if hasattr(lib, "nblic_amd_queue_plan_stats"):                 # (likewise)
+        lib.nblic_amd_queue_plan_stats.restype = C.c_int
+        lib.nblic_amd_queue_plan_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_double)]
     lib.nblic_amd_lsq_redo_counts.restype = C.c_int
     lib.nblic_amd_lsq_redo_counts.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
     lib.nblic_amd_serial_plan.restype = C.c_int
@@ -3053,6 +3056,19 @@ class Context:
         if self.lib.nblic_amd_copy_stats(self.handle, v) != 0:
             raise RuntimeError("nblic_amd_copy_stats failed")
         return {"engine": int(v[0]), "runtime": int(v[1]), "fallbacks": int(v[2]), "available": bool(v[3])}
+
+    QUEUE_PLAN_STATES = ("on", "few_groups", "switched_off", "one_class", "inconclusive", "error")
+
+    def queue_plan(self) -> dict:
+        """How this context's group streams were spread over the process's hardware queues when it was created
+        (``nblic_amd_queue_plan_stats``): ``state`` ("on", or why every group has the stream the runtime dealt it), ``on``,
+        ``classes`` found, ``candidates`` created, ``n_groups``, ``groups_per_class``, ``spread`` and ``unplanned_spread``
+        (largest minus smallest number of groups per class, with the plan and as the runtime deals), ``plan_ms``."""
+        v, ms = (C.c_long * 40)(), C.c_double(0.0)
+        if self.lib.nblic_amd_queue_plan_stats(self.handle, v, C.byref(ms)) != 0:
+            raise RuntimeError("nblic_amd_queue_plan_stats failed")
+        return {"state": self.QUEUE_PLAN_STATES[int(v[0])], "on": int(v[0]) == 0, "classes": int(v[1]), "candidates": int(v[2]), "n_groups": int(v[3]),
+                "spread": int(v[4]), "unplanned_spread": int(v[5]), "groups_per_class": [int(v[8 + k]) for k in range(int(v[1]))], "plan_ms": float(ms.value)}
 
     def lsq_redo_counts(self, reset: bool = False) -> Tuple[int, int]:
         """Pixels (efforts 2 / 3) whose least-squares system 0 / 1 left the exact range of the doubles and was redone with

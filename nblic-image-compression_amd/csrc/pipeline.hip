@@ -42,6 +42,7 @@
 #include "model.h"
 #include "q_device_coder.h"
 #include "q_entropy.h"
+#include "queue_plan.h"
 #include "range_coder.h"
 #include "serial_engine.h"
 #include "sha256.h"
@@ -323,6 +324,7 @@ struct nblic_amd_ctx {
     DevBuf<DeepDeliverTask> dec_deep;           // nblic_amd_decode_batch_to_ex_deep: the tasks of the call's k_deliver_deep launch (grow-only)
     std::atomic<long> deep_counts[4] = {};      // nblic_amd_deep_plan_stats: k_deep_cost, k_collect_deep and k_deliver_deep launches, deep images planned
     double deep_ms[3] = {0, 0, 0};              // GPU time of the last k_deep_cost, k_collect_deep and k_deliver_deep launch of a plan, an encoder and a decoder.  Guarded by stat_m
+    QueuePlan queue_plan;                       // nblic_amd_queue_plan_stats: how the group streams were spread over the hardware queues (queue_plan.h); written once, by create_ex
 };
 
 namespace nblic {
@@ -383,10 +385,99 @@ static uint8_t *begin_stream_out(const ReadyImage &im, size_t *room) {
     return im.outs[im.job] + kHeaderBytes;
 }
 
-static bool group_init(Group &g, int id, int n_slots, nblic_amd_ctx *c) {
+// ---- the queue plan's probe (queue_plan.h): "does stream b wait behind stream a?" -------------------------------------
+// A wave that reads the clock until `ticks` have passed, `cap` times at the most, so it ends whatever the clock does.  It
+// writes nothing.
+__global__ void k_queue_probe_busy(unsigned long long ticks, unsigned cap) {
+    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+    for (unsigned i = 0; i < cap; i++) {
+        if (__builtin_amdgcn_s_memtime() - t0 >= ticks) break;
+        __builtin_amdgcn_s_sleep(16);
+    }
+}
+__global__ void k_queue_probe_empty() {}
+
+struct QueueProbe {
+    static constexpr unsigned kCap = 20000;                          // each turn of the loop sleeps ~1000 clocks: some 10 ms at the most
+    static constexpr double kWantMs = 1.0;
+    unsigned long long ticks = 2000000;                              // ~1 ms: s_memtime counts shader clocks here (2-2.4 GHz); calibrate() measures what that is and corrects it once where the clock is another
+    double busy_ms = 0;                                              // the busy kernel alone, launch to drained, as the host sees it
+    static double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+    // The busy kernel's own duration on stream a: the least of three.  kProbeFree: measured and usable.
+    int measure(hipStream_t a) {
+        busy_ms = 1e30;
+        for (int rep = 0; rep < 3; rep++) {
+            const auto t0 = std::chrono::steady_clock::now();
+            hipLaunchKernelGGL(k_queue_probe_busy, dim3(1), dim3(64), 0, a, ticks, kCap);
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(a) != hipSuccess) return kProbeError;
+            busy_ms = std::min(busy_ms, ms_since(t0));
+        }
+        return kProbeFree;
+    }
+    int calibrate(hipStream_t a) {
+        hipLaunchKernelGGL(k_queue_probe_empty, dim3(1), dim3(64), 0, a);              // the code object is loaded and the stream has its queue before anything is timed
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(a) != hipSuccess) return kProbeError;
+        int r = measure(a);
+        if (r != kProbeFree) return r;
+        if (busy_ms < 0.5 * kWantMs && busy_ms > 0.001) {            // a faster clock than assumed: once more with the ticks scaled (the cap still bounds the kernel)
+            ticks = (unsigned long long)(double(ticks) * kWantMs / busy_ms);
+            if ((r = measure(a)) != kProbeFree) return r;
+        }
+        return busy_ms >= 0.3 * kWantMs && busy_ms <= 20.0 * kWantMs ? kProbeFree : kProbeInconclusive;
+    }
+    // b waits behind a when an empty kernel on b, launched behind the busy kernel on a, takes more than half the busy
+    // kernel's duration to drain in EVERY one of three repetitions: on one queue all are slow, on two one fast one is
+    // enough, so what other tenants of the card do can only err toward "free".
+    int blocks(hipStream_t a, hipStream_t b) {
+        for (int rep = 0; rep < 3; rep++) {
+            hipLaunchKernelGGL(k_queue_probe_busy, dim3(1), dim3(64), 0, a, ticks, kCap);
+            if (hipGetLastError() != hipSuccess) return kProbeError;
+            const auto t0 = std::chrono::steady_clock::now();
+            hipLaunchKernelGGL(k_queue_probe_empty, dim3(1), dim3(64), 0, b);
+            const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(b) == hipSuccess;
+            const double ms = ms_since(t0);
+            if (hipStreamSynchronize(a) != hipSuccess || !ok) return kProbeError;
+            if (ms < 0.5 * busy_ms) return kProbeFree;
+        }
+        return kProbeBlocks;
+    }
+};
+
+// The group streams of a context with three groups or more, spread over the hardware queues the process has (queue_plan.h):
+// streams[g] is group g's, or the vector is empty and every group creates its own, as the runtime deals them.  Runs on
+// the creating thread before any other thread of the context exists.
+static void plan_group_streams(nblic_amd_ctx *c, int n_groups, std::vector<Stream> &streams) {
+    QueuePlan &p = c->queue_plan;
+    p.n_groups = n_groups;
+    if (n_groups < 3) { p.state = kPlanFewGroups; return; }
+    if (const char *v = getenv("NBLIC_AMD_QUEUE_PLAN")) if (atoi(v) == 0) { p.state = kPlanSwitchedOff; }
+    if (p.state != kPlanSwitchedOff) {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<Stream> cand;
+        QueueProbe probe;
+        bool calibrated = false;
+        p = plan_queues(n_groups,
+            [&]() -> int {
+                cand.emplace_back();
+                if (cand.back().create(hipStreamNonBlocking) != hipSuccess) { cand.pop_back(); return -1; }
+                return int(cand.size()) - 1;
+            },
+            [&](int a, int b) -> int {
+                if (!calibrated) { const int r = probe.calibrate(cand[size_t(a)]); if (r != kProbeFree) return r; calibrated = true; }
+                return probe.blocks(cand[size_t(a)], cand[size_t(b)]);
+            },
+            [&](int id) { cand[size_t(id)] = Stream(); });
+        if (p.state == kPlanOn) for (int id : p.chosen) streams.push_back(std::move(cand[size_t(id)]));
+        p.plan_ms = QueueProbe::ms_since(t0);
+    }
+    if (p.state != kPlanOn) fprintf(stderr, "[nblic_amd] queue plan off (%s): one stream per group as the runtime deals them\n", queue_plan_state_name(p.state));
+}
+
+static bool group_init(Group &g, int id, int n_slots, nblic_amd_ctx *c, Stream *planned = nullptr) {
     g.id = id; g.ctx = c;
     g.slots.resize(size_t(n_slots));
-    HIP_OK(g.stream.create(hipStreamNonBlocking));
+    if (planned) g.stream = std::move(*planned);
+    else HIP_OK(g.stream.create(hipStreamNonBlocking));
     HIP_OK(g.done.create(hipEventDisableTiming | hipEventBlockingSync));
     if (c->engine.available()) HIP_OK(g.released.create(hipEventDisableTiming | hipEventReleaseToSystem));
     for (int k = 0; k < kE1Marks; k++) { HIP_OK(g.tm_ev[k].create(hipEventDefault)); g.tm.ev[k] = g.tm_ev[k]; }
@@ -4721,8 +4812,10 @@ nblic_amd_ctx *nblic_amd_create_ex(int device, int n_groups, int group_size, int
         if (!ce || atoi(ce) != 0) c->engine.open();
     }
     c->groups.resize(size_t(n_groups));
+    std::vector<Stream> planned;                                     // empty: every group creates its own
+    plan_group_streams(c, n_groups, planned);
     for (int i = 0; i < n_groups; i++) {
-        if (!group_init(c->groups[size_t(i)], i, group_size, c)) { nblic_amd_destroy(c); return nullptr; }
+        if (!group_init(c->groups[size_t(i)], i, group_size, c, planned.empty() ? nullptr : &planned[size_t(i)])) { nblic_amd_destroy(c); return nullptr; }
         c->free_groups.push_back(i);
     }
     c->cbufs.resize(size_t(n_host_buffers));
@@ -6103,6 +6196,17 @@ void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k
 int nblic_amd_copy_stats(nblic_amd_ctx *c, long out[4]) {
     if (!c || !out) return -1;
     c->engine.stats(out);
+    return 0;
+}
+
+int nblic_amd_queue_plan_stats(nblic_amd_ctx *c, long out[40], double *plan_ms) {
+    static_assert(kPlanMaxClasses == 32, "the header says 8 + 32 values");
+    if (!c || !out) return -1;
+    const QueuePlan &p = c->queue_plan;                              // written once, before create_ex returned
+    std::fill(out, out + 40, 0L);
+    out[0] = p.state; out[1] = p.classes; out[2] = p.candidates; out[3] = p.n_groups; out[4] = p.spread(); out[5] = p.unplanned_spread();
+    for (int k = 0; k < p.classes; k++) out[8 + k] = p.groups_per_class[k];
+    if (plan_ms) *plan_ms = p.plan_ms;
     return 0;
 }
 
