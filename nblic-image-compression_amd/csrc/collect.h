@@ -1,8 +1,10 @@
 // collect.h -- an image out of caller-owned memory into the encoders' contiguous uint8 plane: any pitch, any step between
 // the pixels of a row, pixels or floats that are quantised on the way.  The task, the cut into units and the pixel of one
 // source element, shared by the host and the device: the device kernel's lanes (serial_engine.hip, k_collect) and the
-// host-only collect_host below call the same functions, so the unit walk, the arithmetic and the roundings are tested
-// without a GPU (tests/test_collect_host.py, tools/collect_check.cpp).  The counterpart of deliver.h.
+// host-only collect_host below call the same functions, so the unit walk is tested without a GPU
+// (tests/test_collect_host.py, tools/collect_check.cpp).  The arithmetic and the roundings of collect_value have two
+// bodies: the host body is tested without a GPU (the same files, and tests/test_float_edges_host.py against an exact
+// reference), the device body by tests/test_float_edges.py against the same reference.  The counterpart of deliver.h.
 //
 // The collected plane is contiguous (row r starts at byte r * cols) and its base is a multiple of 16 bytes, so a UNIT --
 // one lane's work -- is sixteen consecutive bytes of the FLAT plane at a multiple of 16: it runs across row ends whenever

@@ -2,8 +2,10 @@
 // a HIGH plane and a LOW plane that may be FOLDED.  The mode byte, the tasks, the unit and tile walks, the pixel arithmetic
 // and the three costs of an image, shared by the host and the device: the kernels' lanes (serial_engine.hip, k_collect_deep,
 // k_deliver_deep and k_deep_cost) and the host-only deep_collect_host, deep_deliver_host and deep_cost_host below call the
-// same functions, so the walks and the arithmetic are tested without a GPU (tests/test_deep_host.py, tools/deep_check.cpp).
-// Built on collect.h, deliver.h and color_plan.h.
+// same functions, so the walks and the integer arithmetic are tested without a GPU (tests/test_deep_host.py,
+// tools/deep_check.cpp).  The float arithmetic of deep_value has two bodies: the host body is tested without a GPU (the same
+// files, and tests/test_float_edges_host.py against an exact reference), the device body by tests/test_float_edges.py
+// against the same reference.  Built on collect.h, deliver.h and color_plan.h.
 //
 // THE PLANES.  With u the element as an unsigned 16-bit number (uint16: u = x; int16: u = x + 32768, the sign bit flipped):
 // hi = u >> 8, lo = u & 255.  Stream 2k of a call is the high plane of deep image k, stream 2k + 1 its low plane; both are

@@ -1,7 +1,9 @@
 // deliver.h -- a window of a decoded plane into caller-owned memory, as pixels or as normalised floats: the task, the
 // cut into units and the value of one element, shared by the host and the device.  The device kernel's lanes
-// (serial_engine.hip, k_deliver) and the host-only deliver_host below call the same functions, so the unit walk, the
-// arithmetic and the roundings are tested without a GPU (tests/test_deliver_host.py, tools/deliver_check.cpp).
+// (serial_engine.hip, k_deliver) and the host-only deliver_host below call the same functions, so the unit walk is tested
+// without a GPU (tests/test_deliver_host.py, tools/deliver_check.cpp).  The arithmetic and the roundings of deliver_value
+// have two bodies: the host body is tested without a GPU (the same files, and tests/test_float_edges_host.py against an
+// exact reference), the device body by tests/test_float_edges.py against the same reference.
 //
 // A UNIT is one lane's work: at most sixteen pixels of ONE row of the window, laid so that its first element's place in
 // the destination row is a multiple of 16 bytes.  The destination row starts at any multiple of the element size, so the
