@@ -1771,6 +1771,42 @@ def _batch_args(ptrs: Sequence[int], shapes: Sequence[Tuple[int, int]], outs: Se
             (C.c_void_p * k)(*[C.c_void_p(o.ctypes.data) for o in outs]), (C.c_size_t * k)(*[o.size for o in outs]), (C.c_long * k)())
 
 
+# ---- what the Context.debug_* wrappers of the pixel-side kernels and the three plan calls share ----------------------
+def _c_sizes(vals):
+    vals = [int(v) for v in vals]
+    return (C.c_size_t * max(len(vals), 1))(*vals)
+
+
+def _c_ints(vals):
+    vals = [int(v) for v in vals]
+    return (C.c_int * max(len(vals), 1))(*vals)
+
+
+def _c_floats(vals):
+    vals = list(vals)
+    return (C.c_float * max(len(vals), 1))(*vals)
+
+
+def _c_ptrs(arrs):
+    """The arrays' addresses; NULL for None."""
+    arrs = list(arrs)
+    return (C.c_void_p * max(len(arrs), 1))(*[None if a is None else a.ctypes.data for a in arrs])
+
+
+def _debug_rc(rc: int, name: str) -> None:
+    if rc == -1:
+        raise ValueError("%s refused its arguments" % name)
+    if rc != 0:
+        raise RuntimeError("%s failed (%d)" % (name, rc))
+
+
+def _plan_tail(rc: int, name: str, costs: bool, modes, *tables):
+    """``ValueError`` when the library refused the plan call; else the mode bytes, with the tables when ``costs``."""
+    if rc != 0:
+        raise ValueError("%s refused the call" % name)
+    return (modes,) + tables if costs else modes
+
+
 class Context:
     """Several images in flight on one GPU (``nblic_amd_create``)."""
 
@@ -2249,23 +2285,15 @@ class Context:
         if any(p.ndim != 2 or p.size == 0 for p in planes):
             raise ValueError("debug_deliver: every plane is a 2-D uint8 array")
         outs = [np.zeros(max(b, 1), np.uint8) for b in sizes]
-        m = max(n, 1)
-        vp = lambda arrs: (C.c_void_p * m)(*[a.ctypes.data for a in arrs])
-        sz = lambda vals: (C.c_size_t * m)(*[int(v) for v in vals])
-        iv = lambda vals, k=1: (C.c_int * (m * k))(*[int(v) for v in vals])
-        fv = lambda vals: (C.c_float * m)(*vals)
-        head = (self.handle, n, vp(planes), sz(p.size for p in planes), sz(bases), iv(p.shape[0] for p in planes), iv(p.shape[1] for p in planes), iv(wins, 4),
-                iv(fmts), fv(scales), fv(biases), iv(zeros), sz(pitches))
+        head = (self.handle, n, _c_ptrs(planes), _c_sizes(p.size for p in planes), _c_sizes(bases), _c_ints(p.shape[0] for p in planes), _c_ints(p.shape[1] for p in planes), _c_ints(wins),
+                _c_ints(fmts), _c_floats(scales), _c_floats(biases), _c_ints(zeros), _c_sizes(pitches))
         if ex:
             if any(v < 0 for v in steps):
                 raise ValueError("debug_deliver: a negative step")
-            rc = self.lib.nblic_amd_debug_deliver_ex(*head, sz(steps), sz(offsets), sz(sizes), vp(outs), iv(gates))
+            rc = self.lib.nblic_amd_debug_deliver_ex(*head, _c_sizes(steps), _c_sizes(offsets), _c_sizes(sizes), _c_ptrs(outs), _c_ints(gates))
         else:
-            rc = self.lib.nblic_amd_debug_deliver(*head, sz(offsets), sz(sizes), vp(outs), iv(gates))
-        if rc == -1:
-            raise ValueError("nblic_amd_debug_deliver refused its arguments")
-        if rc != 0:
-            raise RuntimeError("nblic_amd_debug_deliver failed (%d)" % rc)
+            rc = self.lib.nblic_amd_debug_deliver(*head, _c_sizes(offsets), _c_sizes(sizes), _c_ptrs(outs), _c_ints(gates))
+        _debug_rc(rc, "nblic_amd_debug_deliver")
         return [o[:b] for o, b in zip(outs, sizes)]
 
     def collect_stats(self) -> Tuple[int, int, int, int]:
@@ -2301,9 +2329,7 @@ class Context:
         modes, table = np.zeros(max(n // 3, 1), np.uint8), np.zeros((max(n // 3, 1), 9), np.uint64)
         rc = self.lib.nblic_amd_color_plan(self.handle, n, arr, int(fmt), float(scale), float(bias), _modes_ptr(modes),
                                            table.ctypes.data_as(C.POINTER(C.c_ulonglong)) if costs else None)
-        if rc != 0:
-            raise ValueError("nblic_amd_color_plan refused the call")
-        return (modes[:n // 3], table[:n // 3]) if costs else modes[:n // 3]
+        return _plan_tail(rc, "nblic_amd_color_plan", costs, modes[:n // 3], table[:n // 3])
 
     def stack_plan(self, src, depth=None, key_every: int = 0, scale: float = 1.0, bias: float = 0.0, costs: bool = False, rows=None, cols=None):
         """Choose a slice mode per image from costs measured on the device (``nblic_amd_stack_plan``).  ``src`` as
@@ -2327,9 +2353,7 @@ class Context:
         modes, table = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 2), np.uint64)
         rc = self.lib.nblic_amd_stack_plan(self.handle, n, arr, int(fmt), float(scale), float(bias), int(depth), int(key_every), _modes_ptr(modes),
                                            table.ctypes.data_as(C.POINTER(C.c_ulonglong)) if costs else None)
-        if rc != 0:
-            raise ValueError("nblic_amd_stack_plan refused the call")
-        return (modes[:n], table[:n]) if costs else modes[:n]
+        return _plan_tail(rc, "nblic_amd_stack_plan", costs, modes[:n], table[:n])
 
     def stack_plan_stats(self) -> dict:
         """Since the context was created (``nblic_amd_stack_plan_stats``): ``cost_launches`` of k_stack_cost, ``elements``
@@ -2361,13 +2385,9 @@ class Context:
         modes, table, ranges = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 3), np.uint64), np.zeros((max(n, 1), 2), np.uint32)
         rc = self.lib.nblic_amd_deep_plan(self.handle, n, arr, int(fmt), _modes_ptr(modes), table.ctypes.data_as(C.POINTER(C.c_ulonglong)) if costs else None,
                                           ranges.ctypes.data_as(C.POINTER(C.c_uint)) if costs else None)
-        if rc != 0:
-            raise ValueError("nblic_amd_deep_plan refused the call")
-        if not costs:
-            return modes[:n]
         values = ranges[:n].astype(np.int64) - (32768 if fmt == 1 else 0)
         values[modes[:n] == DEEP_REFUSED] = 0
-        return modes[:n], table[:n], values
+        return _plan_tail(rc, "nblic_amd_deep_plan", costs, modes[:n], table[:n], values)
 
     def deep_plan_stats(self) -> dict:
         """Since the context was created (``nblic_amd_deep_plan_stats``): ``plan_launches`` of k_deep_cost, ``collect_launches``
@@ -2479,16 +2499,10 @@ class Context:
             for t in tasks:
                 flat += [int(v) for v in t.get("px_range", (0, 0))]
             ranges = (C.c_int * (2 * n))(*flat)
-        sz = lambda vals: (C.c_size_t * max(n, 1))(*[int(v) for v in vals])
-        iv = lambda vals: (C.c_int * max(n, 1))(*[int(v) for v in vals])
-        vp = lambda arrs: (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
-        rc = self.lib.nblic_amd_debug_deep_collect(self.handle, n, vp(raws), sz(r.size for r in raws), sz(t.get("base_offset", 0) for t in tasks), iv(hs), iv(ws),
-                                                   sz(t.get("pitch", 2 * int(t["cols"])) for t in tasks), sz(t.get("step", 2) for t in tasks),
-                                                   iv(t["fmt"] for t in tasks), iv(t["part"] for t in tasks), ranges, vp(outs), sz(sizes))
-        if rc == -1:
-            raise ValueError("nblic_amd_debug_deep_collect refused its arguments")
-        if rc != 0:
-            raise RuntimeError("nblic_amd_debug_deep_collect failed (%d)" % rc)
+        rc = self.lib.nblic_amd_debug_deep_collect(self.handle, n, _c_ptrs(raws), _c_sizes(r.size for r in raws), _c_sizes(t.get("base_offset", 0) for t in tasks), _c_ints(hs), _c_ints(ws),
+                                                   _c_sizes(t.get("pitch", 2 * int(t["cols"])) for t in tasks), _c_sizes(t.get("step", 2) for t in tasks),
+                                                   _c_ints(t["fmt"] for t in tasks), _c_ints(t["part"] for t in tasks), ranges, _c_ptrs(outs), _c_sizes(sizes))
+        _debug_rc(rc, "nblic_amd_debug_deep_collect")
         return outs
 
     def debug_deep_deliver(self, tasks) -> List[np.ndarray]:
@@ -2516,18 +2530,11 @@ class Context:
         if min(steps + pitches + offsets + sizes + bases) < 0 or len(bases) != 2 * n or len(gates) != 2 * n:
             raise ValueError("debug_deep_deliver: non-negative steps, pitches, offsets and sizes; two base offsets and two gate statuses per task")
         outs = [np.zeros(max(b, 1), np.uint8) for b in sizes]
-        sz = lambda vals: (C.c_size_t * len(vals))(*[int(v) for v in vals])
-        iv = lambda vals: (C.c_int * len(vals))(*[int(v) for v in vals])
-        fv = lambda vals: (C.c_float * len(vals))(*vals)
-        vp = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data if a.size else None for a in arrs])
-        rc = self.lib.nblic_amd_debug_deep_deliver(self.handle, n, vp(his), vp(los), sz(bases), iv([h.shape[0] for h in his]), iv([h.shape[1] for h in his]), iv(wins),
-                                                   iv([t["fmt"] for t in tasks]), iv([t["mode"] for t in tasks]), fv([float(t.get("scale", 1.0)) for t in tasks]),
-                                                   fv([float(t.get("bias", 0.0)) for t in tasks]), iv([int(bool(t.get("zero", False))) for t in tasks]), sz(pitches),
-                                                   sz(steps), sz(offsets), sz(sizes), vp(outs), iv(gates))
-        if rc == -1:
-            raise ValueError("nblic_amd_debug_deep_deliver refused its arguments")
-        if rc != 0:
-            raise RuntimeError("nblic_amd_debug_deep_deliver failed (%d)" % rc)
+        rc = self.lib.nblic_amd_debug_deep_deliver(self.handle, n, _c_ptrs(his), _c_ptrs(los), _c_sizes(bases), _c_ints([h.shape[0] for h in his]), _c_ints([h.shape[1] for h in his]), _c_ints(wins),
+                                                   _c_ints([t["fmt"] for t in tasks]), _c_ints([t["mode"] for t in tasks]), _c_floats([float(t.get("scale", 1.0)) for t in tasks]),
+                                                   _c_floats([float(t.get("bias", 0.0)) for t in tasks]), _c_ints([int(bool(t.get("zero", False))) for t in tasks]), _c_sizes(pitches),
+                                                   _c_sizes(steps), _c_sizes(offsets), _c_sizes(sizes), _c_ptrs(outs), _c_ints(gates))
+        _debug_rc(rc, "nblic_amd_debug_deep_deliver")
         return [o[:b] for o, b in zip(outs, sizes)]
 
     def debug_deep_cost(self, tasks) -> np.ndarray:
@@ -2538,16 +2545,11 @@ class Context:
         n = len(tasks)
         raws = [np.ascontiguousarray(t["raw"]).reshape(-1).view(np.uint8) for t in tasks]
         out = np.zeros((max(n, 1), 5), np.uint64)
-        sz = lambda vals: (C.c_size_t * max(n, 1))(*[int(v) for v in vals])
-        iv = lambda vals: (C.c_int * max(n, 1))(*[int(v) for v in vals])
-        rc = self.lib.nblic_amd_debug_deep_cost(self.handle, n, (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in raws]), sz(r.size for r in raws),
-                                                sz(t.get("base_offset", 0) for t in tasks), iv(t["rows"] for t in tasks), iv(t["cols"] for t in tasks),
-                                                sz(t.get("pitch", 2 * int(t["cols"])) for t in tasks), sz(t.get("step", 2) for t in tasks), iv(t["fmt"] for t in tasks),
+        rc = self.lib.nblic_amd_debug_deep_cost(self.handle, n, _c_ptrs(raws), _c_sizes(r.size for r in raws),
+                                                _c_sizes(t.get("base_offset", 0) for t in tasks), _c_ints(t["rows"] for t in tasks), _c_ints(t["cols"] for t in tasks),
+                                                _c_sizes(t.get("pitch", 2 * int(t["cols"])) for t in tasks), _c_sizes(t.get("step", 2) for t in tasks), _c_ints(t["fmt"] for t in tasks),
                                                 out.ctypes.data_as(C.POINTER(C.c_ulonglong)))
-        if rc == -1:
-            raise ValueError("nblic_amd_debug_deep_cost refused its arguments")
-        if rc != 0:
-            raise RuntimeError("nblic_amd_debug_deep_cost failed (%d)" % rc)
+        _debug_rc(rc, "nblic_amd_debug_deep_cost")
         return out[:n]
 
     def debug_stack_cost(self, tasks) -> List[np.ndarray]:
@@ -2573,15 +2575,9 @@ class Context:
         if n < 1 or len(pitches) != total or len(steps) != total or len(bases) != total or min(pitches + steps + bases) < 0:
             raise ValueError("debug_stack_cost: one non-negative pitch, step and offset per source")
         out = np.zeros((total, 2), np.uint64)
-        sz = lambda vals: (C.c_size_t * total)(*[int(v) for v in vals])
-        iv = lambda vals: (C.c_int * n)(*[int(v) for v in vals])
-        fv = lambda vals: (C.c_float * n)(*vals)
-        rc = self.lib.nblic_amd_debug_stack_cost(self.handle, n, iv(counts), (C.c_void_p * total)(*[a.ctypes.data for a in raws]), sz(r.size for r in raws), sz(bases),
-                                                 sz(pitches), sz(steps), iv(hs), iv(ws), iv(fmts), fv(scales), fv(biases), out.ctypes.data_as(C.POINTER(C.c_ulonglong)))
-        if rc == -1:
-            raise ValueError("nblic_amd_debug_stack_cost refused its arguments")
-        if rc != 0:
-            raise RuntimeError("nblic_amd_debug_stack_cost failed (%d)" % rc)
+        rc = self.lib.nblic_amd_debug_stack_cost(self.handle, n, _c_ints(counts), _c_ptrs(raws), _c_sizes(r.size for r in raws), _c_sizes(bases),
+                                                 _c_sizes(pitches), _c_sizes(steps), _c_ints(hs), _c_ints(ws), _c_ints(fmts), _c_floats(scales), _c_floats(biases), out.ctypes.data_as(C.POINTER(C.c_ulonglong)))
+        _debug_rc(rc, "nblic_amd_debug_stack_cost")
         ends = np.cumsum(counts)
         return [out[e - c:e] for c, e in zip(counts, ends)]
 
@@ -2606,17 +2602,10 @@ class Context:
         if n < 1:
             raise ValueError("debug_stack_deliver: at least one task")
         outs = [None if s else np.zeros(max(b, 1), np.uint8) for s, b in zip(flat["skip"], flat["sizes"])]
-        vp = lambda arrs: (C.c_void_p * total)(*[a.ctypes.data if a is not None else None for a in arrs])
-        sz = lambda vals: (C.c_size_t * total)(*[int(v) for v in vals])
-        iv = lambda vals: (C.c_int * len(vals))(*[int(v) for v in vals])
-        fv = lambda vals: (C.c_float * total)(*vals)
-        rc = self.lib.nblic_amd_debug_stack_deliver(self.handle, n, iv(counts), vp(flat["planes"]), sz(flat["bases"]), iv(hs), iv(ws), iv(wins), iv(fmts),
-                                                    fv(flat["scales"]), fv(flat["biases"]), iv(flat["zeros"]), sz(flat["pitches"]), sz(flat["steps"]),
-                                                    sz(flat["offsets"]), sz(flat["sizes"]), vp(outs), iv(flat["gates"]))
-        if rc == -1:
-            raise ValueError("nblic_amd_debug_stack_deliver refused its arguments")
-        if rc != 0:
-            raise RuntimeError("nblic_amd_debug_stack_deliver failed (%d)" % rc)
+        rc = self.lib.nblic_amd_debug_stack_deliver(self.handle, n, _c_ints(counts), _c_ptrs(flat["planes"]), _c_sizes(flat["bases"]), _c_ints(hs), _c_ints(ws), _c_ints(wins), _c_ints(fmts),
+                                                    _c_floats(flat["scales"]), _c_floats(flat["biases"]), _c_ints(flat["zeros"]), _c_sizes(flat["pitches"]), _c_sizes(flat["steps"]),
+                                                    _c_sizes(flat["offsets"]), _c_sizes(flat["sizes"]), _c_ptrs(outs), _c_ints(flat["gates"]))
+        _debug_rc(rc, "nblic_amd_debug_stack_deliver")
         res, at = [], 0
         for c in counts:
             res.append([None if o is None else o[:b] for o, b in zip(outs[at:at + c], flat["sizes"][at:at + c])])
@@ -2653,16 +2642,9 @@ class Context:
             raise ValueError("debug_color_cost: a negative pitch, step or offset")
         m = max(n, 1)
         out = np.zeros((m, 9), np.uint64)
-        vp = (C.c_void_p * (3 * m))(*[a.ctypes.data for a in raws])
-        sz = lambda vals: (C.c_size_t * (3 * m))(*[int(v) for v in vals])
-        iv = lambda vals: (C.c_int * m)(*[int(v) for v in vals])
-        fv = lambda vals: (C.c_float * m)(*vals)
-        rc = self.lib.nblic_amd_debug_color_cost(self.handle, n, vp, sz(r.size for r in raws), sz(bases), sz(pitches), sz(steps), iv(hs), iv(ws), iv(fmts),
-                                                 fv(scales), fv(biases), out.ctypes.data_as(C.POINTER(C.c_ulonglong)))
-        if rc == -1:
-            raise ValueError("nblic_amd_debug_color_cost refused its arguments")
-        if rc != 0:
-            raise RuntimeError("nblic_amd_debug_color_cost failed (%d)" % rc)
+        rc = self.lib.nblic_amd_debug_color_cost(self.handle, n, _c_ptrs(raws), _c_sizes(r.size for r in raws), _c_sizes(bases), _c_sizes(pitches), _c_sizes(steps), _c_ints(hs), _c_ints(ws), _c_ints(fmts),
+                                                 _c_floats(scales), _c_floats(biases), out.ctypes.data_as(C.POINTER(C.c_ulonglong)))
+        _debug_rc(rc, "nblic_amd_debug_color_cost")
         return out[:n]
 
     def encode_from_srcs(self, srcs, fmt: int, scale: float = 1.0, bias: float = 0.0, near=0, effort=1, every_rows=None, band_rows: int = 0,
@@ -2863,17 +2845,9 @@ class Context:
             ranges += [int(v) for v in t.get("px_range", (0, 0))]
         sizes = [2 * COLLECT_GUARD + ((max(h * w, 0) + 255) & ~255) for h, w in zip(hs, ws)]
         outs = [np.zeros(b, np.uint8) for b in sizes]
-        m = max(n, 1)
-        vp = lambda arrs: (C.c_void_p * m)(*[a.ctypes.data for a in arrs])
-        sz = lambda vals: (C.c_size_t * m)(*[int(v) for v in vals])
-        iv = lambda vals, k=1: (C.c_int * (m * k))(*[int(v) for v in vals])
-        fv = lambda vals: (C.c_float * m)(*vals)
-        rc = self.lib.nblic_amd_debug_collect(self.handle, n, vp(raws), sz(r.size for r in raws), sz(bases), iv(hs), iv(ws), sz(pitches), sz(steps),
-                                              iv(fmts), fv(scales), fv(biases), iv(ranges, 2), vp(outs), sz(sizes))
-        if rc == -1:
-            raise ValueError("nblic_amd_debug_collect refused its arguments")
-        if rc != 0:
-            raise RuntimeError("nblic_amd_debug_collect failed (%d)" % rc)
+        rc = self.lib.nblic_amd_debug_collect(self.handle, n, _c_ptrs(raws), _c_sizes(r.size for r in raws), _c_sizes(bases), _c_ints(hs), _c_ints(ws), _c_sizes(pitches), _c_sizes(steps),
+                                              _c_ints(fmts), _c_floats(scales), _c_floats(biases), _c_ints(ranges), _c_ptrs(outs), _c_sizes(sizes))
+        _debug_rc(rc, "nblic_amd_debug_collect")
         return outs
 
     def debug_collect_ref(self, tasks) -> List[np.ndarray]:
@@ -2895,18 +2869,10 @@ class Context:
             ranges += [int(v) for v in t.get("px_range", (0, 0))]
         sizes = [2 * COLLECT_GUARD + ((max(h * w, 0) + 255) & ~255) for h, w in zip(hs, ws)]
         outs = [np.zeros(b, np.uint8) for b in sizes]
-        m = max(n, 1)
-        vp = lambda arrs: (C.c_void_p * m)(*[a.ctypes.data if a is not None else None for a in arrs])
-        sz = lambda vals: (C.c_size_t * m)(*[int(v) for v in vals])
-        iv = lambda vals, k=1: (C.c_int * (m * k))(*[int(v) for v in vals])
-        fv = lambda vals: (C.c_float * m)(*vals)
-        rc = self.lib.nblic_amd_debug_collect_ref(self.handle, n, vp(raws), sz(r.size for r in raws), sz(bases),
-                                                  vp(refs), sz(r.size if r is not None else 0 for r in refs), sz(rbases), sz(rpitches), sz(rsteps),
-                                                  iv(hs), iv(ws), sz(pitches), sz(steps), iv(fmts), fv(scales), fv(biases), iv(ranges, 2), vp(outs), sz(sizes))
-        if rc == -1:
-            raise ValueError("nblic_amd_debug_collect_ref refused its arguments")
-        if rc != 0:
-            raise RuntimeError("nblic_amd_debug_collect_ref failed (%d)" % rc)
+        rc = self.lib.nblic_amd_debug_collect_ref(self.handle, n, _c_ptrs(raws), _c_sizes(r.size for r in raws), _c_sizes(bases),
+                                                  _c_ptrs(refs), _c_sizes(r.size if r is not None else 0 for r in refs), _c_sizes(rbases), _c_sizes(rpitches), _c_sizes(rsteps),
+                                                  _c_ints(hs), _c_ints(ws), _c_sizes(pitches), _c_sizes(steps), _c_ints(fmts), _c_floats(scales), _c_floats(biases), _c_ints(ranges), _c_ptrs(outs), _c_sizes(sizes))
+        _debug_rc(rc, "nblic_amd_debug_collect_ref")
         return outs
 
     def debug_deliver_ref(self, tasks) -> List[np.ndarray]:
@@ -2937,19 +2903,11 @@ class Context:
             sizes.append(int(t.get("out_bytes", offset + max(r1 - r0 - 1, 0) * pitch + max(c1 - c0 - 1, 0) * step + elem)))
             bases.append(int(t.get("base_offset", 0))); rbases.append(int(t.get("ref_base_offset", 0))); gates += g
         outs = [np.zeros(max(b, 1), np.uint8) for b in sizes]
-        m = max(n, 1)
-        vp = lambda arrs: (C.c_void_p * m)(*[a.ctypes.data if a is not None else None for a in arrs])
-        sz = lambda vals: (C.c_size_t * m)(*[int(v) for v in vals])
-        iv = lambda vals, k=1: (C.c_int * (m * k))(*[int(v) for v in vals])
-        fv = lambda vals: (C.c_float * m)(*vals)
-        rc = self.lib.nblic_amd_debug_deliver_ref(self.handle, n, vp(planes), sz(p.size for p in planes), sz(bases), vp(refs), sz(rbases),
-                                                  iv(r.shape[0] if r is not None else 0 for r in refs), iv(p.shape[0] for p in planes), iv(p.shape[1] for p in planes),
-                                                  iv(wins, 4), iv(fmts), fv(scales), fv(biases), iv(zeros), sz(pitches), sz(steps), sz(offsets), sz(sizes), vp(outs),
-                                                  iv(gates, 3))
-        if rc == -1:
-            raise ValueError("nblic_amd_debug_deliver_ref refused its arguments")
-        if rc != 0:
-            raise RuntimeError("nblic_amd_debug_deliver_ref failed (%d)" % rc)
+        rc = self.lib.nblic_amd_debug_deliver_ref(self.handle, n, _c_ptrs(planes), _c_sizes(p.size for p in planes), _c_sizes(bases), _c_ptrs(refs), _c_sizes(rbases),
+                                                  _c_ints(r.shape[0] if r is not None else 0 for r in refs), _c_ints(p.shape[0] for p in planes), _c_ints(p.shape[1] for p in planes),
+                                                  _c_ints(wins), _c_ints(fmts), _c_floats(scales), _c_floats(biases), _c_ints(zeros), _c_sizes(pitches), _c_sizes(steps), _c_sizes(offsets), _c_sizes(sizes), _c_ptrs(outs),
+                                                  _c_ints(gates))
+        _debug_rc(rc, "nblic_amd_debug_deliver_ref")
         return [o[:b] for o, b in zip(outs, sizes)]
 
     def indexed_decode_split(self) -> dict:

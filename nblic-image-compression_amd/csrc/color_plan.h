@@ -3,7 +3,8 @@
 // shared by the host and the device: the kernel's lanes (serial_engine.hip, k_color_cost) and the host-only color_cost_host
 // below call the same functions, so the tile walk and the arithmetic are tested without a GPU
 // (tests/test_color_plan_host.py, tools/color_plan_check.cpp).  Built on collect.h: a source element becomes a pixel by
-// collect_value, so the costs are those of exactly the planes k_collect would write.
+// collect_value, so the costs are those of exactly the planes k_collect would write.  The tile geometry, the MED prediction,
+// the bit length and the host's tile walk live in cost_tile.h, which stack.h and deep.h share.
 //
 // THE MODE.  Bits 0..1: the base channel b (0 = R, 1 = G, 2 = B).  Bit 2: the lower-numbered of the two other channels is
 // coded as (c - b + 128) mod 256.  Bit 3: the same for the higher-numbered one.  The base, and a channel whose bit is
@@ -17,12 +18,12 @@
 // the pixels: integer adds commute.
 #pragma once
 #include "collect.h"
+#include "cost_tile.h"
 
 namespace nblic {
 
 enum : uint32_t { kColorPlain = 0, kColorRct = 0x0D, kColorRefused = 0xFF };
 constexpr uint32_t kColorCosts = 9;
-constexpr uint32_t kColorTile = 64;                                  // a workgroup's tile: 64 x 64 pixels, one wave per sixteen rows
 
 // One frame: three sources of rows x cols in one format, scale and bias, and where its nine sums go.
 struct ColorCostTask {
@@ -38,15 +39,8 @@ struct ColorCostTask {
 };
 static_assert(sizeof(ColorCostTask) == 96, "uploaded as bytes");
 
-CL_HD uint32_t color_tiles_across(const ColorCostTask &t) { return (t.cols + kColorTile - 1) / kColorTile; }
-CL_HD uint32_t color_task_tiles(const ColorCostTask &t) { return color_tiles_across(t) * ((t.rows + kColorTile - 1) / kColorTile); }       // (<= 1024^2)
-
-// Tile k of a task, row-major: its first row and column.
-struct ColorTile { uint32_t y0, x0; };
-CL_HD ColorTile color_tile_of(const ColorCostTask &t, uint32_t k) {
-    const uint32_t across = color_tiles_across(t);
-    return ColorTile{(k / across) * kColorTile, (k % across) * kColorTile};
-}
+CL_HD uint32_t color_task_tiles(const ColorCostTask &t) { return cost_tiles(t.rows, t.cols); }
+CL_HD CostTile color_tile_of(const ColorCostTask &t, uint32_t k) { return cost_tile_of(t.rows, t.cols, k); }
 
 // The source of channel ch as the collect task whose loader and checks it shares (all but dst and the pixel range).
 CL_HD CollectTask color_source(const ColorCostTask &t, uint32_t ch) {
@@ -57,24 +51,10 @@ CL_HD CollectTask color_source(const ColorCostTask &t, uint32_t ch) {
     return c;
 }
 
-// MED of the three neighbours' pixels at image position (y, x); neighbours that do not exist are not looked at.
-CL_HD uint32_t color_pred(uint32_t w, uint32_t n, uint32_t nw, uint32_t y, uint32_t x) {
-    if (y == 0) return x == 0 ? 128u : w;
-    if (x == 0) return n;
-    const uint32_t lo = w < n ? w : n, hi = w < n ? n : w;
-    if (nw >= hi) return lo;
-    if (nw <= lo) return hi;
-    return w + n - nw;
-}
-CL_HD uint32_t color_bitlen(uint32_t v) {                            // v <= 128
-    uint32_t k = 0;
-    while (v) { v >>= 1; k++; }
-    return k;
-}
 // The cost of pixel p with prediction pred, both 0..255.
 CL_HD uint32_t color_pixel_cost(uint32_t p, uint32_t pred) {
     const uint32_t d = (p - pred) & 255u;                            // e = d < 128 ? d : d - 256
-    return 2u * color_bitlen(d < 128u ? d : 256u - d) + 1u;
+    return 2u * cost_bitlen(d < 128u ? d : 256u - d) + 1u;
 }
 
 // The nine planes: which channel a plane is made of, and which it is taken against (-1: none).
@@ -94,7 +74,7 @@ CL_HD void color_pixel_costs(const uint32_t p[3], const uint32_t w[3], const uin
         const int a = color_plane_own(k), r = color_plane_ref(k);
         uint32_t P = p[a], W = w[a], N = n[a], NW = nw[a];
         if (r >= 0) { P = collect_rct(P, p[r]); W = collect_rct(W, w[r]); N = collect_rct(N, n[r]); NW = collect_rct(NW, nw[r]); }
-        sums[k] += color_pixel_cost(P, color_pred(W, N, NW, y, x));
+        sums[k] += color_pixel_cost(P, cost_pred(W, N, NW, y, x));
     }
 }
 
@@ -141,28 +121,19 @@ inline bool color_task_ok(const ColorCostTask &t, const unsigned long long cap[3
 
 // The host walk: every tile of the task, one after the other, pixel by pixel; each element is read where it lies.
 inline void color_cost_host(const ColorCostTask &t) {
-    const uint32_t elem = collect_elem(t.format), tiles = color_task_tiles(t);
+    const uint32_t elem = collect_elem(t.format);
     unsigned long long sums[kColorCosts] = {};
-    auto pixel = [&](uint32_t ch, uint32_t y, uint32_t x) {
-        uint32_t v = 0;
-        memcpy(&v, t.src[ch] + (unsigned long long)(y) * t.pitch[ch] + (unsigned long long)(x) * t.step[ch], elem);
-        return collect_value(v, t.format, t.scale, t.bias);
-    };
-    for (uint32_t k = 0; k < tiles; k++) {
-        const ColorTile T = color_tile_of(t, k);
-        const uint32_t y1 = t.rows - T.y0 > kColorTile ? T.y0 + kColorTile : t.rows, x1 = t.cols - T.x0 > kColorTile ? T.x0 + kColorTile : t.cols;
-        for (uint32_t y = T.y0; y < y1; y++)
-            for (uint32_t x = T.x0; x < x1; x++) {
-                uint32_t p[3], w[3] = {0, 0, 0}, n[3] = {0, 0, 0}, nw[3] = {0, 0, 0};
-                for (uint32_t ch = 0; ch < 3; ch++) {
-                    p[ch] = pixel(ch, y, x);
-                    if (x) w[ch] = pixel(ch, y, x - 1);
-                    if (y) n[ch] = pixel(ch, y - 1, x);
-                    if (x && y) nw[ch] = pixel(ch, y - 1, x - 1);
-                }
-                color_pixel_costs(p, w, n, nw, y, x, sums);
+    cost_walk_tiles(t.rows, t.cols, [&](const CostTile &T) {
+        cost_tile_pixels(T, [&](uint32_t y, uint32_t x) {
+            uint32_t p[3], w[3], n[3], nw[3];
+            for (uint32_t ch = 0; ch < 3; ch++) {
+                uint32_t v[4];
+                cost_neighbours([&](uint32_t yy, uint32_t xx) { return collect_value(cost_element(t.src[ch], t.pitch[ch], t.step[ch], elem, yy, xx), t.format, t.scale, t.bias); }, y, x, v);
+                p[ch] = v[0]; w[ch] = v[1]; n[ch] = v[2]; nw[ch] = v[3];
             }
-    }
+            color_pixel_costs(p, w, n, nw, y, x, sums);
+        });
+    });
     for (uint32_t k = 0; k < kColorCosts; k++) t.costs[k] += sums[k];
 }
 

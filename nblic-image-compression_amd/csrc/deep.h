@@ -5,7 +5,8 @@
 // same functions, so the walks and the integer arithmetic are tested without a GPU (tests/test_deep_host.py,
 // tools/deep_check.cpp).  The float arithmetic of deep_value has two bodies: the host body is tested without a GPU (the same
 // files, and tests/test_float_edges_host.py against an exact reference), the device body by tests/test_float_edges.py
-// against the same reference.  Built on collect.h, deliver.h and color_plan.h.
+// against the same reference.  Built on collect.h and deliver.h; the tile geometry, the MED prediction, the bit length and the
+// host's tile walk live in cost_tile.h.
 //
 // THE PLANES.  With u the element as an unsigned 16-bit number (uint16: u = x; int16: u = x + 32768, the sign bit flipped):
 // hi = u >> 8, lo = u & 255.  Stream 2k of a call is the high plane of deep image k, stream 2k + 1 its low plane; both are
@@ -17,13 +18,14 @@
 // the value is u - 32768.  Valid bytes: 0..3; 0xFF is what the plan gives an image it refuses.
 //
 // THE COSTS of an image are those of its three candidate planes -- high, low, folded low -- each the sum over its pixels of
-// 2 * bitlen(|e|) + 1 with e = p - pred, pred the MED prediction of color_plan.h (color_pred).  e is NOT wrapped here
+// 2 * bitlen(|e|) + 1 with e = p - pred, pred the MED prediction of cost_tile.h (cost_pred).  e is NOT wrapped here
 // (|e| <= 255, bitlen <= 8): the one deliberate difference from color_pixel_cost, which wraps mod 256.  A wrapped residual
 // would rate the sawtooth's jumps of 255 at nothing -- and those jumps are exactly what the fold removes and what NBLIC, which
 // does not wrap its residuals, pays for.
 #pragma once
 #include "deliver.h"
-#include "color_plan.h"
+#include "collect.h"
+#include "cost_tile.h"
 
 namespace nblic {
 
@@ -221,18 +223,17 @@ struct DeepCostTask {
 };
 static_assert(sizeof(DeepCostTask) == 48, "uploaded as bytes");
 
-CL_HD uint32_t deep_tiles_across(const DeepCostTask &t) { return (t.cols + kColorTile - 1) / kColorTile; }
-CL_HD uint32_t deep_task_tiles(const DeepCostTask &t) { return deep_tiles_across(t) * ((t.rows + kColorTile - 1) / kColorTile); }
+CL_HD uint32_t deep_task_tiles(const DeepCostTask &t) { return cost_tiles(t.rows, t.cols); }
 
 // The cost of pixel p with prediction pred, both 0..255: the residual is NOT wrapped (the head of this file says why).
-CL_HD uint32_t deep_pixel_cost(uint32_t p, uint32_t pred) { return 2u * color_bitlen(p > pred ? p - pred : pred - p) + 1u; }
+CL_HD uint32_t deep_pixel_cost(uint32_t p, uint32_t pred) { return 2u * cost_bitlen(p > pred ? p - pred : pred - p) + 1u; }
 
 // The three costs of the pixel at (y, x): u, w, n, nw are its own and its neighbours' 16-bit values (neighbours that do not
 // exist are not looked at).
 template <class Sum>
 CL_HD void deep_pixel_costs(uint32_t u, uint32_t w, uint32_t n, uint32_t nw, uint32_t y, uint32_t x, Sum sums[kDeepParts]) {
     for (uint32_t k = 0; k < kDeepParts; k++)
-        sums[k] += deep_pixel_cost(deep_part(u, k), color_pred(deep_part(w, k), deep_part(n, k), deep_part(nw, k), y, x));
+        sums[k] += deep_pixel_cost(deep_part(u, k), cost_pred(deep_part(w, k), deep_part(n, k), deep_part(nw, k), y, x));
 }
 
 inline bool deep_cost_task_ok(const DeepCostTask &t, unsigned long long cap_bytes) {
@@ -241,24 +242,16 @@ inline bool deep_cost_task_ok(const DeepCostTask &t, unsigned long long cap_byte
 
 // The host walk: every tile of the task, one after the other, pixel by pixel; each element is read where it lies.
 inline void deep_cost_host(const DeepCostTask &t) {
-    const uint32_t tiles = deep_task_tiles(t), across = deep_tiles_across(t);
-    auto value = [&](uint32_t y, uint32_t x) {
-        uint32_t v = 0;
-        memcpy(&v, t.src + (unsigned long long)(y) * t.pitch + (unsigned long long)(x) * t.step, 2);
-        return deep_u(v, t.format);
-    };
     unsigned long long sums[kDeepParts] = {}, lo = t.sums[3], hi = t.sums[4];
-    for (uint32_t k = 0; k < tiles; k++) {
-        const uint32_t y0 = (k / across) * kColorTile, x0 = (k % across) * kColorTile;
-        const uint32_t y1 = t.rows - y0 > kColorTile ? y0 + kColorTile : t.rows, x1 = t.cols - x0 > kColorTile ? x0 + kColorTile : t.cols;
-        for (uint32_t y = y0; y < y1; y++)
-            for (uint32_t x = x0; x < x1; x++) {
-                const uint32_t u = value(y, x), w = x ? value(y, x - 1) : 0u, n = y ? value(y - 1, x) : 0u, nw = x && y ? value(y - 1, x - 1) : 0u;
-                deep_pixel_costs(u, w, n, nw, y, x, sums);
-                if (u < lo) lo = u;
-                if (u > hi) hi = u;
-            }
-    }
+    cost_walk_tiles(t.rows, t.cols, [&](const CostTile &T) {
+        cost_tile_pixels(T, [&](uint32_t y, uint32_t x) {
+            uint32_t v[4];                                           // u, w, n, nw
+            cost_neighbours([&](uint32_t yy, uint32_t xx) { return deep_u(cost_element(t.src, t.pitch, t.step, 2, yy, xx), t.format); }, y, x, v);
+            deep_pixel_costs(v[0], v[1], v[2], v[3], y, x, sums);
+            if (v[0] < lo) lo = v[0];
+            if (v[0] > hi) hi = v[0];
+        });
+    });
     for (uint32_t k = 0; k < kDeepParts; k++) t.sums[k] += sums[k];
     t.sums[3] = lo; t.sums[4] = hi;
 }

@@ -4679,6 +4679,123 @@ static nblic_amd_ctx *default_ctx() {
     return g_default;
 }
 
+// ---- what the three cost plans share (colour, slice stacks, deep pixels) ----------------------------------------------------------
+// The tasks' places in ONE launch of a cost kernel -- first_chunk, from tiles_of(task) -- the limits, counted() (the launch is
+// going to be made: the context's counters), the upload of the task table, and of a second table if the launch has one, and
+// launch(d_tasks, n, tiles), all queued on st.  The sums are the caller's to set.
+template <class Task, class TilesOf, class Counted, class Launch, class Second = char>
+static bool cost_queue(Task *tasks, size_t n, Task *d_tasks, hipStream_t st, TilesOf tiles_of, Counted counted, Launch launch,
+                       const Second *second = nullptr, size_t n_second = 0, Second *d_second = nullptr) {
+    unsigned long long tiles = 0;
+    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(tiles); tiles += tiles_of(tasks[i]); }
+    if (n == 0) return true;
+    if (tiles >= (1ull << 31) || n >= (size_t(1) << 30) || n_second >= (size_t(1) << 30)) return false;
+    counted();
+    return hipMemcpyAsync(d_tasks, tasks, n * sizeof(Task), hipMemcpyHostToDevice, st) == hipSuccess &&
+           (!second || hipMemcpyAsync(d_second, second, n_second * sizeof(Second), hipMemcpyHostToDevice, st) == hipSuccess) &&
+           launch(d_tasks, int(n), uint32_t(tiles));
+}
+
+// A plan's device side: a table of 64-bit sums, set to given values, filled by ONE timed queue step and copied back once.
+// It owns the stream, the two events and the device memory -- the sums, and the task tables the plan makes from `mem`
+// between begin and run, so that nothing is allocated between the events.
+struct SumsRun {
+    Stream st;
+    Event t0, t1;
+    DevPool mem;
+    unsigned long long *d_sums = nullptr;
+    bool begin(size_t n_sums) {
+        d_sums = mem.make<unsigned long long>(n_sums);
+        return d_sums && st.create(hipStreamNonBlocking) == hipSuccess && t0.create(hipEventDefault) == hipSuccess && t1.create(hipEventDefault) == hipSuccess;
+    }
+    // sums: the initial values, then the results.  queue(stream) queues the uploads and the launch; the GPU time it took goes
+    // to *ms (guarded by c->stat_m).  false: a HIP call failed.
+    template <class Queue> bool run(nblic_amd_ctx *c, std::vector<unsigned long long> &sums, double *ms, Queue queue) {
+        const size_t bytes = sums.size() * sizeof(unsigned long long);
+        const bool ok = [&]() -> bool {                                  // the launch, then ONE copy of the whole table
+            HIP_OK(hipMemcpyAsync(d_sums, sums.data(), bytes, hipMemcpyHostToDevice, st));
+            HIP_OK(hipEventRecord(t0, st));
+            if (!queue(hipStream_t(st))) return false;
+            HIP_OK(hipEventRecord(t1, st));
+            HIP_OK(hipMemcpyAsync(sums.data(), d_sums, bytes, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            return true;
+        }();
+        if (st) hipStreamSynchronize(st);
+        if (!ok) return false;
+        float t = 0.0f;
+        if (hipEventElapsedTime(&t, t0, t1) == hipSuccess) { std::lock_guard<std::mutex> l(c->stat_m); *ms = double(t); }
+        return true;
+    }
+};
+
+// ---- the kernel test bench: what the debug entry points of the pixel-side kernels stage alike --------------------------------------
+// INPUTS, each at a byte offset inside a region of its own that is larger and filled with one byte; OUTPUTS, each a region
+// filled with one byte that comes back whole in the caller's buffer; optionally a table of GATE records.  An entry point
+// registers them, allocates, builds its tasks on the device addresses, and runs: the fills and the uploads, its launch, ONE
+// copy back.  The numbers the tests' guards see are here: a SOURCE (the collect side) lies in 0xFF -- NaN in every float
+// format, 255 as a pixel -- with 256 more bytes behind it; a PLANE (the deliver side) lies in zeros, may be read for
+// up256(bytes) as the decoders' planes allow, and has 16 more bytes behind that; an output is filled with 0x5A.
+class DebugBench {
+    struct Input { const void *src; size_t bytes, at, offset, region; uint8_t fill; };     // the region: [at, at + region) of d_in_
+    struct Output { void *dst; size_t bytes, at; uint8_t fill; };
+    Stream st_;
+    DevPool mem_;
+    std::vector<Input> in_;
+    std::vector<Output> out_;
+    std::vector<SerialState> gates_;
+    size_t in_total_ = 0, out_total_ = 0;
+    uint8_t *d_in_ = nullptr, *d_out_ = nullptr;
+    SerialState *d_gates_ = nullptr;
+    size_t input(const void *src, size_t bytes, size_t offset, uint8_t fill, size_t span) {
+        in_.push_back(Input{src, bytes, in_total_, offset, up256(offset + span), fill});
+        in_total_ += in_.back().region;
+        return in_.size() - 1;
+    }
+public:
+    static constexpr size_t kGuard = 256;                            // in front of and behind a plane that a collect-side kernel writes
+    // Each returns the number of what it registered, for in() and out().
+    size_t source(const void *src, size_t bytes, size_t offset) { return input(src, bytes, offset, 0xFF, bytes + 256); }
+    size_t plane(const void *src, size_t bytes, size_t offset) { return input(src, bytes, offset, 0x00, up256(bytes) + 16); }
+    size_t output(void *dst, size_t bytes, uint8_t fill = 0x5A) {
+        out_.push_back(Output{dst, bytes, out_total_, fill});
+        out_total_ += up256(bytes);
+        return out_.size() - 1;
+    }
+    void gates(const int *status, size_t n) {
+        gates_.resize(n);
+        for (size_t k = 0; k < n; k++) gates_[k].status = status[k];
+    }
+    bool alloc(int device) {                                         // false: a HIP call failed
+        if (hipSetDevice(device) != hipSuccess) return false;
+        d_in_ = mem_.make<uint8_t>(in_total_); d_out_ = mem_.make<uint8_t>(out_total_); d_gates_ = mem_.make<SerialState>(gates_.size());
+        return d_in_ && d_out_ && d_gates_ && st_.create(hipStreamNonBlocking) == hipSuccess;
+    }
+    template <class T> T *table(size_t n) { return mem_.make<T>(n); }                      // null: failed
+    uint8_t *in(size_t k) const { return d_in_ + in_[k].at + in_[k].offset; }              // where the first byte of input k lies
+    uint8_t *out(size_t k) const { return d_out_ + out_[k].at; }
+    SerialState *gate(size_t k) const { return d_gates_ + k; }
+    // The fills, the gates and the inputs; launch(stream); every output back in ONE copy and into the callers' buffers.
+    // 0, or -2: a HIP call failed.
+    template <class Launch> int run(Launch launch) {
+        std::vector<uint8_t> back(out_total_);
+        const bool ok = [&]() -> bool {
+            for (const Input &r : in_) HIP_OK(hipMemsetAsync(d_in_ + r.at, r.fill, r.region, st_));
+            for (const Output &r : out_) if (r.bytes) HIP_OK(hipMemsetAsync(d_out_ + r.at, r.fill, up256(r.bytes), st_));
+            if (!gates_.empty()) HIP_OK(hipMemcpyAsync(d_gates_, gates_.data(), gates_.size() * sizeof(SerialState), hipMemcpyHostToDevice, st_));
+            for (const Input &r : in_) if (r.bytes) HIP_OK(hipMemcpyAsync(d_in_ + r.at + r.offset, r.src, r.bytes, hipMemcpyHostToDevice, st_));
+            if (!launch(hipStream_t(st_))) return false;
+            if (out_total_) HIP_OK(hipMemcpyAsync(back.data(), d_out_, out_total_, hipMemcpyDeviceToHost, st_));
+            HIP_OK(hipStreamSynchronize(st_));
+            return true;
+        }();
+        if (st_) hipStreamSynchronize(st_);
+        if (!ok) return -2;
+        for (const Output &r : out_) memcpy(r.dst, back.data() + r.at, r.bytes);
+        return 0;
+    }
+};
+
 }  // namespace nblic
 
 // =============================================================================================
@@ -5430,21 +5547,76 @@ static bool debug_deliver_task(DeliverTask &T, int plane_rows, int width, const 
     return pitch <= (size_t(1) << 40);
 }
 
-// (ref / refs: the reference planes of the _ref hooks, ref_rows x width bytes each; gates: statuses per task -- one without, three with refs)
-static int debug_deliver_host(const unsigned char *plane, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero, int gate_status,
-                              unsigned char *out, size_t out_bytes, size_t dst_offset, size_t pitch_bytes, size_t step_bytes, unsigned long long *units, unsigned long long *chunks,
-                              const unsigned char *ref = nullptr, int ref_rows = 0, int gate2_status = -1, int gate3_status = -1);
-static int debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const *planes, const size_t *plane_bytes, const size_t *base_offsets, const int *plane_rows,
-                         const int *widths, const int *windows, const int *formats, const float *scales, const float *biases, const int *zeros, const size_t *pitches,
-                         const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs, const int *gate_status,
-                         const unsigned char *const *refs = nullptr, const size_t *ref_base_offsets = nullptr, const int *ref_rows = nullptr);
-
 // The reference of a debug task: the plane at `ref` has ref_rows rows of the task's width; the task names it from its
 // window's first row on.  false: it does not reach that row.
 static bool debug_deliver_ref(DeliverTask &T, const uint8_t *ref, int ref_rows, size_t readable) {
     if (ref_rows <= T.row0 || size_t(T.row0) * T.src_pitch > readable) return false;
     T.ref = ref + size_t(T.row0) * T.src_pitch; T.ref_pitch = T.src_pitch; T.ref_bytes = readable - size_t(T.row0) * T.src_pitch;
     return true;
+}
+
+// (ref: the reference plane of the _ref hook, ref_rows x width bytes; three gate statuses with it, one without)
+static int debug_deliver_host(const unsigned char *plane, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero,
+                              int gate_status, unsigned char *out, size_t out_bytes, size_t dst_offset, size_t pitch_bytes, size_t step_bytes,
+                              unsigned long long *units, unsigned long long *chunks, const unsigned char *ref = nullptr, int ref_rows = 0,
+                              int gate2_status = -1, int gate3_status = -1) {
+    DeliverTask T;
+    if (!plane || !out || !debug_deliver_task(T, plane_rows, width, window, format, scale, bias, zero, pitch_bytes, step_bytes)) return -1;
+    T.src = plane; T.src_bytes = size_t(plane_rows) * size_t(width);
+    T.dst = out + dst_offset;
+    if (ref && (ref_rows < 1 || !debug_deliver_ref(T, ref, ref_rows, size_t(ref_rows) * size_t(width)))) return -1;
+    if (dst_offset > out_bytes || !deliver_task_ok(T, uint32_t(plane_rows))) return -1;
+    if (deliver_extent(uint32_t(T.row1 - T.row0), uint32_t(T.col1 - T.col0), T.format, pitch_bytes, T.dst_step) > out_bytes - dst_offset) return -1;
+    if (units) *units = deliver_task_units(T);
+    if (chunks) *chunks = deliver_task_chunks(T);
+    deliver_host(T, gate_status == -1 ? int(kDone) : gate_status, gate2_status == -1 ? int(kDone) : gate2_status, gate3_status == -1 ? int(kDone) : gate3_status);
+    return 0;
+}
+// (refs: the reference planes of the _ref hook, ref_rows[k] x widths[k] bytes each; three gate statuses per task with them, one without)
+static int debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const *planes, const size_t *plane_bytes, const size_t *base_offsets,
+                         const int *plane_rows, const int *widths, const int *windows, const int *formats, const float *scales, const float *biases,
+                         const int *zeros, const size_t *pitches, const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs,
+                         const int *gate_status, const unsigned char *const *refs = nullptr, const size_t *ref_base_offsets = nullptr, const int *ref_rows = nullptr) {
+    constexpr int kMaxTasks = 65536;
+    if (!c || n < 1 || n > kMaxTasks || !planes || !plane_bytes || !base_offsets || !plane_rows || !widths || !windows || !formats || !scales || !biases ||
+        !zeros || !pitches || !dst_offsets || !out_bytes || !outs || !gate_status) return -1;
+    const size_t count = size_t(n);
+    std::vector<DeliverTask> tasks(count);
+    std::vector<size_t> plane_in(count), ref_in(count, 0);
+    const size_t n_gates = refs ? 3 : 1;                                 // statuses, and records on the device, per task
+    DebugBench bench;
+    for (int k = 0; k < n; k++) {
+        const size_t i = size_t(k);
+        DeliverTask &T = tasks[i];
+        if (!planes[k] || !outs[k] || base_offsets[k] > 15 || !debug_deliver_task(T, plane_rows[k], widths[k], windows + 4 * i, formats[k], scales[k], biases[k], zeros[k], pitches[k], steps ? steps[k] : 0))
+            return -1;
+        if (plane_bytes[k] != size_t(plane_rows[k]) * size_t(widths[k]) || plane_bytes[k] > (size_t(1) << 30) || out_bytes[k] > (size_t(1) << 30) || dst_offsets[k] > out_bytes[k]) return -1;
+        T.src_bytes = up256(plane_bytes[k]);
+        plane_in[i] = bench.plane(planes[k], plane_bytes[k], base_offsets[k]);
+        if (refs && refs[k]) {
+            if (ref_base_offsets[k] > 15 || ref_rows[k] < 1 || size_t(ref_rows[k]) * size_t(widths[k]) > (size_t(1) << 30)) return -1;
+            ref_in[i] = bench.plane(refs[k], size_t(ref_rows[k]) * size_t(widths[k]), ref_base_offsets[k]);
+        }
+        bench.output(outs[k], out_bytes[k]);
+    }
+    bench.gates(gate_status, count * n_gates);
+    DeliverTask *d_tasks = bench.alloc(c->device) ? bench.table<DeliverTask>(count) : nullptr;
+    if (!d_tasks) return -2;
+    for (int k = 0; k < n; k++) {                                        // the addresses are known now: the rest of the checks
+        const size_t i = size_t(k);
+        DeliverTask &T = tasks[i];
+        T.src = bench.in(plane_in[i]);
+        T.dst = bench.out(i) + dst_offsets[k];
+        if (gate_status[n_gates * i] != -1) T.gate = bench.gate(n_gates * i);
+        if (refs) {
+            if (gate_status[3 * i + 1] != -1) T.gate2 = bench.gate(3 * i + 1);
+            if (gate_status[3 * i + 2] != -1) T.gate3 = bench.gate(3 * i + 2);
+            if (refs[k] && !debug_deliver_ref(T, bench.in(ref_in[i]), ref_rows[k], up256(size_t(ref_rows[k]) * size_t(widths[k])))) return -1;
+        }
+        if (!deliver_task_ok(T, uint32_t(plane_rows[k])) || (T.ref && uint32_t(ref_rows[k]) < uint32_t(T.row1)) ||
+            deliver_extent(uint32_t(T.row1 - T.row0), uint32_t(T.col1 - T.col0), T.format, T.dst_pitch, T.dst_step) > out_bytes[k] - dst_offsets[k]) return -1;
+    }
+    return bench.run([&](hipStream_t st) { deliver_stats_reset(c); return deliver_queue(tasks.data(), count, d_tasks, st, c); });
 }
 
 // Host only: the shared unit walk (deliver.h deliver_host) over the caller's plane of plane_rows x width into out + dst_offset,
@@ -5461,21 +5633,6 @@ int nblic_amd_debug_deliver_host_ex(const unsigned char *plane, int plane_rows, 
     if (step_bytes == 0) return -1;
     return debug_deliver_host(plane, plane_rows, width, window, format, scale, bias, zero, gate_status, out, out_bytes, dst_offset, pitch_bytes, step_bytes, units, chunks);
 }
-static int debug_deliver_host(const unsigned char *plane, int plane_rows, int width, const int *window, int format, float scale, float bias, int zero,
-                              int gate_status, unsigned char *out, size_t out_bytes, size_t dst_offset, size_t pitch_bytes, size_t step_bytes,
-                              unsigned long long *units, unsigned long long *chunks, const unsigned char *ref, int ref_rows, int gate2_status, int gate3_status) {
-    DeliverTask T;
-    if (!plane || !out || !debug_deliver_task(T, plane_rows, width, window, format, scale, bias, zero, pitch_bytes, step_bytes)) return -1;
-    T.src = plane; T.src_bytes = size_t(plane_rows) * size_t(width);
-    T.dst = out + dst_offset;
-    if (ref && (ref_rows < 1 || !debug_deliver_ref(T, ref, ref_rows, size_t(ref_rows) * size_t(width)))) return -1;
-    if (dst_offset > out_bytes || !deliver_task_ok(T, uint32_t(plane_rows))) return -1;
-    if (deliver_extent(uint32_t(T.row1 - T.row0), uint32_t(T.col1 - T.col0), T.format, pitch_bytes, T.dst_step) > out_bytes - dst_offset) return -1;
-    if (units) *units = deliver_task_units(T);
-    if (chunks) *chunks = deliver_task_chunks(T);
-    deliver_host(T, gate_status == -1 ? int(kDone) : gate_status, gate2_status == -1 ? int(kDone) : gate2_status, gate3_status == -1 ? int(kDone) : gate3_status);
-    return 0;
-}
 // The host walk of a task with a reference plane (ref_rows x width bytes; NULL: none) and three gate statuses; step_bytes 0
 // stands for the element size.
 int nblic_amd_debug_deliver_ref_host(const unsigned char *plane, int plane_rows, int width, const unsigned char *ref, int ref_rows, const int *window, int format,
@@ -5487,7 +5644,7 @@ int nblic_amd_debug_deliver_ref_host(const unsigned char *plane, int plane_rows,
 }
 
 // ONE k_deliver launch over n caller-made planes as n tasks.  Plane k (plane_rows[k] x widths[k]) is uploaded at byte
-// base_offsets[k] (0 .. 15) of a zeroed buffer that is larger; the task may read up256(rows * width) bytes from there, as the
+// base_offsets[k] (0 .. 15) of a zeroed region that is larger; the task may read up256(rows * width) bytes from there, as the
 // decoders' planes allow.  Destination k lies at byte dst_offsets[k] of a buffer of out_bytes[k] bytes filled with 0x5A, which
 // comes back whole in outs[k].  gate_status[k] != -1 is put into a SerialState on the device, the task's gate.  windows: four
 // ints per task (row0, row1, col0, col1).  -1: refused; -2: a HIP call failed.
@@ -5517,77 +5674,6 @@ int nblic_amd_debug_deliver_ref(nblic_amd_ctx *c, int n, const unsigned char *co
     return debug_deliver(c, n, planes, plane_bytes, base_offsets, plane_rows, widths, windows, formats, scales, biases, zeros, pitches, steps, dst_offsets, out_bytes, outs, gate_status,
                          refs, ref_base_offsets, ref_rows);
 }
-static int debug_deliver(nblic_amd_ctx *c, int n, const unsigned char *const *planes, const size_t *plane_bytes, const size_t *base_offsets,
-                         const int *plane_rows, const int *widths, const int *windows, const int *formats, const float *scales, const float *biases,
-                         const int *zeros, const size_t *pitches, const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes, unsigned char *const *outs,
-                         const int *gate_status, const unsigned char *const *refs, const size_t *ref_base_offsets, const int *ref_rows) {
-    constexpr int kMaxTasks = 65536;
-    constexpr uint8_t kPattern = 0x5A;
-    if (!c || n < 1 || n > kMaxTasks || !planes || !plane_bytes || !base_offsets || !plane_rows || !widths || !windows || !formats || !scales || !biases ||
-        !zeros || !pitches || !dst_offsets || !out_bytes || !outs || !gate_status) return -1;
-    const size_t count = size_t(n);
-    std::vector<DeliverTask> tasks(count);
-    std::vector<size_t> plane_at(count), out_at(count), ref_at(count, 0);
-    const size_t n_gates = refs ? 3 : 1;                                 // statuses, and records on the device, per task
-    size_t planes_total = 0, outs_total = 0;
-    for (int k = 0; k < n; k++) {
-        const size_t i = size_t(k);
-        DeliverTask &T = tasks[i];
-        if (!planes[k] || !outs[k] || base_offsets[k] > 15 || !debug_deliver_task(T, plane_rows[k], widths[k], windows + 4 * i, formats[k], scales[k], biases[k], zeros[k], pitches[k], steps ? steps[k] : 0))
-            return -1;
-        if (plane_bytes[k] != size_t(plane_rows[k]) * size_t(widths[k]) || plane_bytes[k] > (size_t(1) << 30) || out_bytes[k] > (size_t(1) << 30) || dst_offsets[k] > out_bytes[k]) return -1;
-        T.src_bytes = up256(plane_bytes[k]);
-        plane_at[i] = planes_total; planes_total += up256(base_offsets[k] + T.src_bytes + 16);
-        if (refs && refs[k]) {
-            if (ref_base_offsets[k] > 15 || ref_rows[k] < 1 || size_t(ref_rows[k]) * size_t(widths[k]) > (size_t(1) << 30)) return -1;
-            ref_at[i] = planes_total; planes_total += up256(ref_base_offsets[k] + up256(size_t(ref_rows[k]) * size_t(widths[k])) + 16);
-        }
-        out_at[i] = outs_total; outs_total += up256(out_bytes[k]);
-    }
-    if (hipSetDevice(c->device) != hipSuccess) return -2;
-    Stream st;
-    DevPool mem;
-    uint8_t *d_planes = mem.make<uint8_t>(planes_total), *d_outs = mem.make<uint8_t>(outs_total);
-    SerialState *d_gates = mem.make<SerialState>(count * n_gates);
-    DeliverTask *d_tasks = mem.make<DeliverTask>(count);
-    if (!d_planes || !d_outs || !d_gates || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
-    for (int k = 0; k < n; k++) {                                        // the addresses are known now: the rest of the checks
-        const size_t i = size_t(k);
-        DeliverTask &T = tasks[i];
-        T.src = d_planes + plane_at[i] + base_offsets[k];
-        T.dst = d_outs + out_at[i] + dst_offsets[k];
-        if (gate_status[n_gates * i] != -1) T.gate = d_gates + n_gates * i;
-        if (refs) {
-            if (gate_status[3 * i + 1] != -1) T.gate2 = d_gates + 3 * i + 1;
-            if (gate_status[3 * i + 2] != -1) T.gate3 = d_gates + 3 * i + 2;
-            if (refs[k] && !debug_deliver_ref(T, d_planes + ref_at[i] + ref_base_offsets[k], ref_rows[k], up256(size_t(ref_rows[k]) * size_t(widths[k])))) return -1;
-        }
-        if (!deliver_task_ok(T, uint32_t(plane_rows[k])) || (T.ref && uint32_t(ref_rows[k]) < uint32_t(T.row1)) ||
-            deliver_extent(uint32_t(T.row1 - T.row0), uint32_t(T.col1 - T.col0), T.format, T.dst_pitch, T.dst_step) > out_bytes[k] - dst_offsets[k]) return -1;
-    }
-    std::vector<uint8_t> back(outs_total);
-    std::vector<SerialState> gates(count * n_gates);
-    for (size_t k = 0; k < gates.size(); k++) gates[k].status = gate_status[k];
-    const bool ok = [&]() -> bool {
-        HIP_OK(hipMemsetAsync(d_planes, 0, planes_total, st));
-        HIP_OK(hipMemsetAsync(d_outs, kPattern, outs_total, st));
-        HIP_OK(hipMemcpyAsync(d_gates, gates.data(), gates.size() * sizeof(SerialState), hipMemcpyHostToDevice, st));
-        for (int k = 0; k < n; k++) {
-            HIP_OK(hipMemcpyAsync(d_planes + plane_at[size_t(k)] + base_offsets[k], planes[k], plane_bytes[k], hipMemcpyHostToDevice, st));
-            if (refs && refs[k])
-                HIP_OK(hipMemcpyAsync(d_planes + ref_at[size_t(k)] + ref_base_offsets[k], refs[k], size_t(ref_rows[k]) * size_t(widths[k]), hipMemcpyHostToDevice, st));
-        }
-        deliver_stats_reset(c);
-        if (!deliver_queue(tasks.data(), count, d_tasks, st, c)) return false;
-        HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        return true;
-    }();
-    if (st) hipStreamSynchronize(st);
-    if (!ok) return -2;
-    for (int k = 0; k < n; k++) memcpy(outs[k], back.data() + out_at[size_t(k)], out_bytes[k]);
-    return 0;
-}
 
 // ---- k_collect on caller-made sources (tests/test_encode_from_device.py), and its host walk (tests/test_collect_host.py) ------
 static bool debug_collect_task(CollectTask &T, const void *src, int rows, int cols, int format, float scale, float bias, size_t pitch, size_t step, const int *range) {
@@ -5607,11 +5693,61 @@ static bool debug_collect_ref(CollectTask &T, const void *ref, size_t pitch, siz
 }
 static int debug_collect_host(const void *src, size_t cap_bytes, const void *ref, size_t ref_cap_bytes, size_t ref_pitch_bytes, size_t ref_step_bytes, int rows, int cols,
                               size_t pitch_bytes, size_t step_bytes, int format, float scale, float bias, const int *range, unsigned char *out, size_t out_bytes,
-                              unsigned long long *units, unsigned long long *chunks);
+                              unsigned long long *units, unsigned long long *chunks) {
+    CollectTask T;
+    if (!src || !out || !debug_collect_task(T, src, rows, cols, format, scale, bias, pitch_bytes, step_bytes, range)) return -1;
+    T.dst = out;
+    if (ref && !debug_collect_ref(T, ref, ref_pitch_bytes, ref_step_bytes)) return -1;
+    if (!collect_task_ok(T, cap_bytes, ref_cap_bytes) || size_t(T.rows) * size_t(T.cols) > out_bytes) return -1;
+    if (units) *units = collect_task_units(T);
+    if (chunks) *chunks = collect_task_chunks(T);
+    collect_host(T);
+    return 0;
+}
+// What the collect-side entry points ask of a task's plane: out_bytes = a guard, up256(rows x cols), a guard.
+static bool debug_plane_out_ok(int rows, int cols, size_t out_bytes) {
+    const size_t plane = size_t(rows) * size_t(cols);
+    return plane <= (size_t(1) << 30) && out_bytes == DebugBench::kGuard + up256(plane) + DebugBench::kGuard;
+}
 static int debug_collect(nblic_amd_ctx *c, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets,
                          const void *const *refs, const size_t *ref_bytes, const size_t *ref_base_offsets, const size_t *ref_pitches, const size_t *ref_steps,
                          const int *rows, const int *cols, const size_t *pitches, const size_t *steps, const int *formats, const float *scales, const float *biases,
-                         const int *ranges, unsigned char *const *outs, const size_t *out_bytes);
+                         const int *ranges, unsigned char *const *outs, const size_t *out_bytes) {
+    constexpr int kMaxTasks = 65536;
+    if (!c || n < 1 || n > kMaxTasks || !srcs || !src_bytes || !base_offsets || !rows || !cols || !pitches || !steps || !formats || !scales || !biases || !outs || !out_bytes) return -1;
+    const size_t count = size_t(n);
+    std::vector<CollectTask> tasks(count);
+    std::vector<size_t> src_in(count), ref_in(count, 0);
+    DebugBench bench;
+    for (int k = 0; k < n; k++) {
+        const size_t i = size_t(k);
+        if (!srcs[k] || !outs[k] || base_offsets[k] > 255 || src_bytes[k] > (size_t(1) << 30) ||
+            !debug_collect_task(tasks[i], nullptr, rows[k], cols[k], formats[k], scales[k], biases[k], pitches[k], steps[k], ranges ? ranges + 2 * i : nullptr)) return -1;
+        if (!debug_plane_out_ok(rows[k], cols[k], out_bytes[k])) return -1;
+        src_in[i] = bench.source(srcs[k], src_bytes[k], base_offsets[k]);
+        if (refs && refs[k]) {
+            if (ref_base_offsets[k] > 255 || ref_bytes[k] > (size_t(1) << 30)) return -1;
+            ref_in[i] = bench.source(refs[k], ref_bytes[k], ref_base_offsets[k]);
+        }
+        bench.output(outs[k], out_bytes[k]);
+    }
+    CollectTask *d_tasks = bench.alloc(c->device) ? bench.table<CollectTask>(count) : nullptr;
+    if (!d_tasks) return -2;
+    unsigned long long chunks = 0;
+    for (int k = 0; k < n; k++) {                                        // the addresses are known now: the rest of the checks
+        const size_t i = size_t(k);
+        CollectTask &T = tasks[i];
+        T.src = bench.in(src_in[i]);
+        T.dst = bench.out(i) + DebugBench::kGuard;
+        if (refs && refs[k] && !debug_collect_ref(T, bench.in(ref_in[i]), ref_pitches[k], ref_steps[k])) return -1;
+        if (!collect_task_ok(T, src_bytes[k], T.ref ? ref_bytes[k] : 0)) return -1;                // nothing outside the uploaded bytes is the task's to read
+        T.first_chunk = uint32_t(chunks); chunks += collect_task_chunks(T);
+    }
+    if (chunks >= (1ull << 31)) return -1;
+    return bench.run([&](hipStream_t st) {
+        return hipMemcpyAsync(d_tasks, tasks.data(), count * sizeof(CollectTask), hipMemcpyHostToDevice, st) == hipSuccess && collect_launch(d_tasks, n, uint32_t(chunks), st);
+    });
+}
 
 // Host only: the shared unit walk (collect.h collect_host) over the source at src -- cap_bytes readable from there -- into
 // the plane at out, which must be a multiple of 16 and hold rows x cols bytes.  range: the pixels [px0, px1) of the flat plane
@@ -5626,20 +5762,6 @@ int nblic_amd_debug_collect_ref_host(const void *src, size_t cap_bytes, const vo
                                      unsigned char *out, size_t out_bytes, unsigned long long *units, unsigned long long *chunks) {
     return debug_collect_host(src, cap_bytes, ref, ref_cap_bytes, ref_pitch_bytes, ref_step_bytes, rows, cols, pitch_bytes, step_bytes, format, scale, bias, range, out, out_bytes, units, chunks);
 }
-static int debug_collect_host(const void *src, size_t cap_bytes, const void *ref, size_t ref_cap_bytes, size_t ref_pitch_bytes, size_t ref_step_bytes, int rows, int cols,
-                              size_t pitch_bytes, size_t step_bytes, int format, float scale, float bias, const int *range, unsigned char *out, size_t out_bytes,
-                              unsigned long long *units, unsigned long long *chunks) {
-    CollectTask T;
-    if (!src || !out || !debug_collect_task(T, src, rows, cols, format, scale, bias, pitch_bytes, step_bytes, range)) return -1;
-    T.dst = out;
-    if (ref && !debug_collect_ref(T, ref, ref_pitch_bytes, ref_step_bytes)) return -1;
-    if (!collect_task_ok(T, cap_bytes, ref_cap_bytes) || size_t(T.rows) * size_t(T.cols) > out_bytes) return -1;
-    if (units) *units = collect_task_units(T);
-    if (chunks) *chunks = collect_task_chunks(T);
-    collect_host(T);
-    return 0;
-}
-
 // ONE k_collect launch over n caller-made sources as n tasks.  The bytes of source k (src_bytes[k] of them) are uploaded at
 // byte base_offsets[k] (0 .. 255) of a region filled with 0xFF -- NaN in every float format, 255 as a pixel -- that is larger;
 // the image's element (0, 0) is the first of them.  Plane k (rows x cols bytes) lies at byte 256 of a region filled with
@@ -5659,66 +5781,6 @@ int nblic_amd_debug_collect_ref(nblic_amd_ctx *c, int n, const void *const *srcs
     if (!refs || !ref_bytes || !ref_base_offsets || !ref_pitches || !ref_steps) return -1;
     return debug_collect(c, n, srcs, src_bytes, base_offsets, refs, ref_bytes, ref_base_offsets, ref_pitches, ref_steps, rows, cols, pitches, steps, formats, scales, biases, ranges, outs, out_bytes);
 }
-static int debug_collect(nblic_amd_ctx *c, int n, const void *const *srcs, const size_t *src_bytes, const size_t *base_offsets,
-                         const void *const *refs, const size_t *ref_bytes, const size_t *ref_base_offsets, const size_t *ref_pitches, const size_t *ref_steps,
-                         const int *rows, const int *cols, const size_t *pitches, const size_t *steps, const int *formats, const float *scales, const float *biases,
-                         const int *ranges, unsigned char *const *outs, const size_t *out_bytes) {
-    constexpr int kMaxTasks = 65536;
-    constexpr size_t kGuard = 256;
-    if (!c || n < 1 || n > kMaxTasks || !srcs || !src_bytes || !base_offsets || !rows || !cols || !pitches || !steps || !formats || !scales || !biases || !outs || !out_bytes) return -1;
-    const size_t count = size_t(n);
-    std::vector<CollectTask> tasks(count);
-    std::vector<size_t> src_at(count), out_at(count), ref_at(count, 0);
-    size_t srcs_total = 0, outs_total = 0;
-    for (int k = 0; k < n; k++) {
-        const size_t i = size_t(k);
-        if (!srcs[k] || !outs[k] || base_offsets[k] > 255 || src_bytes[k] > (size_t(1) << 30) ||
-            !debug_collect_task(tasks[i], nullptr, rows[k], cols[k], formats[k], scales[k], biases[k], pitches[k], steps[k], ranges ? ranges + 2 * i : nullptr)) return -1;
-        const size_t plane = size_t(rows[k]) * size_t(cols[k]);
-        if (plane > (size_t(1) << 30) || out_bytes[k] != kGuard + up256(plane) + kGuard) return -1;
-        src_at[i] = srcs_total; srcs_total += up256(base_offsets[k] + src_bytes[k] + 256);
-        if (refs && refs[k]) {
-            if (ref_base_offsets[k] > 255 || ref_bytes[k] > (size_t(1) << 30)) return -1;
-            ref_at[i] = srcs_total; srcs_total += up256(ref_base_offsets[k] + ref_bytes[k] + 256);
-        }
-        out_at[i] = outs_total; outs_total += out_bytes[k];
-    }
-    if (hipSetDevice(c->device) != hipSuccess) return -2;
-    Stream st;
-    DevPool mem;
-    uint8_t *d_srcs = mem.make<uint8_t>(srcs_total), *d_outs = mem.make<uint8_t>(outs_total);
-    CollectTask *d_tasks = mem.make<CollectTask>(count);
-    if (!d_srcs || !d_outs || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
-    unsigned long long chunks = 0;
-    for (int k = 0; k < n; k++) {                                        // the addresses are known now: the rest of the checks
-        const size_t i = size_t(k);
-        CollectTask &T = tasks[i];
-        T.src = d_srcs + src_at[i] + base_offsets[k];
-        T.dst = d_outs + out_at[i] + kGuard;
-        if (refs && refs[k] && !debug_collect_ref(T, d_srcs + ref_at[i] + ref_base_offsets[k], ref_pitches[k], ref_steps[k])) return -1;
-        if (!collect_task_ok(T, src_bytes[k], T.ref ? ref_bytes[k] : 0)) return -1;                // nothing outside the uploaded bytes is the task's to read
-        T.first_chunk = uint32_t(chunks); chunks += collect_task_chunks(T);
-    }
-    if (chunks >= (1ull << 31)) return -1;
-    std::vector<uint8_t> back(outs_total);
-    const bool ok = [&]() -> bool {
-        HIP_OK(hipMemsetAsync(d_srcs, 0xFF, srcs_total, st));
-        HIP_OK(hipMemsetAsync(d_outs, 0x5A, outs_total, st));
-        for (int k = 0; k < n; k++)
-            HIP_OK(hipMemcpyAsync(d_srcs + src_at[size_t(k)] + base_offsets[k], srcs[k], src_bytes[k], hipMemcpyHostToDevice, st));
-        for (int k = 0; k < n; k++)
-            if (refs && refs[k]) HIP_OK(hipMemcpyAsync(d_srcs + ref_at[size_t(k)] + ref_base_offsets[k], refs[k], ref_bytes[k], hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(d_tasks, tasks.data(), count * sizeof(CollectTask), hipMemcpyHostToDevice, st));
-        if (!collect_launch(d_tasks, n, uint32_t(chunks), st)) return false;
-        HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        return true;
-    }();
-    if (st) hipStreamSynchronize(st);
-    if (!ok) return -2;
-    for (int k = 0; k < n; k++) memcpy(outs[k], back.data() + out_at[size_t(k)], out_bytes[k]);
-    return 0;
-}
 
 // Call it when nothing is outstanding on the context: it reads the groups' marks.
 int nblic_amd_collect_ms(nblic_amd_ctx *c, double *ms, long *timed_launches) {
@@ -5737,14 +5799,13 @@ int nblic_amd_collect_stats(nblic_amd_ctx *c, long out[4]) {
 }
 
 // ---- the colour plan: costs on the device, the choice on the host (color_plan.h, serial_engine.h k_color_cost) --------------
-// The tasks' places in ONE k_color_cost launch, their upload and the launch, queued on st.  The costs are the caller's to zero.
+// ONE k_color_cost launch over the tasks, queued on st (cost_queue).  The costs are the caller's to zero.
 static bool color_cost_queue(nblic_amd_ctx *c, ColorCostTask *tasks, size_t n, ColorCostTask *d_tasks, hipStream_t st) {
-    unsigned long long tiles = 0, pixels = 0;
-    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(tiles); tiles += color_task_tiles(tasks[i]); pixels += 3ull * tasks[i].rows * tasks[i].cols; }
-    if (n == 0) return true;
-    if (tiles >= (1ull << 31) || n >= (size_t(1) << 30)) return false;
-    c->color_counts[0] += 1; c->color_counts[1] += long(pixels);
-    return hipMemcpyAsync(d_tasks, tasks, n * sizeof(ColorCostTask), hipMemcpyHostToDevice, st) == hipSuccess && color_cost_launch(d_tasks, int(n), uint32_t(tiles), st);
+    return cost_queue(tasks, n, d_tasks, st, color_task_tiles, [&] {
+        unsigned long long pixels = 0;
+        for (size_t i = 0; i < n; i++) pixels += 3ull * tasks[i].rows * tasks[i].cols;
+        c->color_counts[0] += 1; c->color_counts[1] += long(pixels);
+    }, [&](const ColorCostTask *d, int m, uint32_t tiles) { return color_cost_launch(d, m, tiles, st); });
 }
 
 int nblic_amd_color_plan(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias,
@@ -5771,35 +5832,19 @@ int nblic_amd_color_plan(nblic_amd_ctx *c, int n_images, const nblic_amd_src *sr
         T.format = uint32_t(format); T.scale = scale; T.bias = bias;
         tasks.push_back(T); frame_of.push_back(f);
     }
-    std::vector<unsigned long long> table(frames * kColorCosts, 0ull);
+    std::vector<unsigned long long> sums(tasks.size() * kColorCosts, 0ull);
     if (!tasks.empty()) {
-        Stream st;
-        Event t0, t1;
-        DevPool mem;
-        unsigned long long *d_costs = mem.make<unsigned long long>(tasks.size() * kColorCosts);
-        ColorCostTask *d_tasks = mem.make<ColorCostTask>(tasks.size());
-        std::vector<unsigned long long> back(tasks.size() * kColorCosts);
-        if (!d_costs || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess || t0.create(hipEventDefault) != hipSuccess || t1.create(hipEventDefault) != hipSuccess) return -1;
-        for (size_t i = 0; i < tasks.size(); i++) tasks[i].costs = d_costs + i * kColorCosts;
-        const bool ok = [&]() -> bool {                                  // the launch, then ONE copy of the whole table
-            HIP_OK(hipMemsetAsync(d_costs, 0, back.size() * sizeof(unsigned long long), st));
-            HIP_OK(hipEventRecord(t0, st));
-            if (!color_cost_queue(c, tasks.data(), tasks.size(), d_tasks, st)) return false;
-            HIP_OK(hipEventRecord(t1, st));
-            HIP_OK(hipMemcpyAsync(back.data(), d_costs, back.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-            return true;
-        }();
-        if (st) hipStreamSynchronize(st);
-        if (!ok) return -1;
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, t0, t1) == hipSuccess) { std::lock_guard<std::mutex> l(c->stat_m); c->color_ms = double(ms); }
-        for (size_t i = 0; i < tasks.size(); i++) {
-            memcpy(&table[frame_of[i] * kColorCosts], &back[i * kColorCosts], kColorCosts * sizeof(unsigned long long));
-            frame_modes[frame_of[i]] = color_choose(&back[i * kColorCosts]);
-        }
+        SumsRun run;
+        ColorCostTask *d_tasks = run.begin(sums.size()) ? run.mem.make<ColorCostTask>(tasks.size()) : nullptr;
+        if (!d_tasks) return -1;
+        for (size_t i = 0; i < tasks.size(); i++) tasks[i].costs = run.d_sums + i * kColorCosts;
+        if (!run.run(c, sums, &c->color_ms, [&](hipStream_t st) { return color_cost_queue(c, tasks.data(), tasks.size(), d_tasks, st); })) return -1;
     }
-    if (costs) memcpy(costs, table.data(), table.size() * sizeof(unsigned long long));
+    if (costs) std::fill(costs, costs + frames * kColorCosts, 0ull);
+    for (size_t i = 0; i < tasks.size(); i++) {
+        if (costs) memcpy(costs + frame_of[i] * kColorCosts, &sums[i * kColorCosts], kColorCosts * sizeof(unsigned long long));
+        frame_modes[frame_of[i]] = color_choose(&sums[i * kColorCosts]);
+    }
     return 0;
 }
 
@@ -5854,55 +5899,36 @@ int nblic_amd_debug_color_cost(nblic_amd_ctx *c, int n, const void *const *srcs,
     if (!c || n < 1 || n > kMaxTasks || !srcs || !src_bytes || !base_offsets || !pitches || !steps || !rows || !cols || !formats || !scales || !biases || !costs) return -1;
     const size_t count = size_t(n);
     std::vector<ColorCostTask> tasks(count);
-    std::vector<size_t> src_at(3 * count);
-    size_t srcs_total = 0;
+    DebugBench bench;
     for (size_t i = 0; i < count; i++) {
         if (!debug_color_task(tasks[i], pitches + 3 * i, steps + 3 * i, rows[i], cols[i], formats[i], scales[i], biases[i])) return -1;
         for (size_t s = 3 * i; s < 3 * i + 3; s++) {
             if (!srcs[s] || base_offsets[s] > 255 || src_bytes[s] > (size_t(1) << 30)) return -1;
-            src_at[s] = srcs_total; srcs_total += up256(base_offsets[s] + src_bytes[s] + 256);
+            bench.source(srcs[s], src_bytes[s], base_offsets[s]);
         }
     }
-    if (hipSetDevice(c->device) != hipSuccess) return -2;
-    Stream st;
-    DevPool mem;
-    uint8_t *d_srcs = mem.make<uint8_t>(srcs_total);
-    unsigned long long *d_costs = mem.make<unsigned long long>(count * kColorCosts);
-    ColorCostTask *d_tasks = mem.make<ColorCostTask>(count);
-    if (!d_srcs || !d_costs || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    bench.output(costs, count * kColorCosts * sizeof(unsigned long long), 0);
+    ColorCostTask *d_tasks = bench.alloc(c->device) ? bench.table<ColorCostTask>(count) : nullptr;
+    if (!d_tasks) return -2;
     for (size_t i = 0; i < count; i++) {                                 // the addresses are known now: the rest of the checks
         ColorCostTask &T = tasks[i];
         unsigned long long caps[3];
-        for (size_t ch = 0; ch < 3; ch++) { T.src[ch] = d_srcs + src_at[3 * i + ch] + base_offsets[3 * i + ch]; caps[ch] = src_bytes[3 * i + ch]; }
-        T.costs = d_costs + i * kColorCosts;
+        for (size_t ch = 0; ch < 3; ch++) { T.src[ch] = bench.in(3 * i + ch); caps[ch] = src_bytes[3 * i + ch]; }
+        T.costs = reinterpret_cast<unsigned long long *>(bench.out(0)) + i * kColorCosts;
         if (!color_task_ok(T, caps)) return -1;                          // nothing outside the uploaded bytes is the task's to read
     }
-    const bool ok = [&]() -> bool {
-        HIP_OK(hipMemsetAsync(d_srcs, 0xFF, srcs_total, st));
-        HIP_OK(hipMemsetAsync(d_costs, 0, count * kColorCosts * sizeof(unsigned long long), st));
-        for (size_t s = 0; s < 3 * count; s++) HIP_OK(hipMemcpyAsync(d_srcs + src_at[s] + base_offsets[s], srcs[s], src_bytes[s], hipMemcpyHostToDevice, st));
-        if (!color_cost_queue(c, tasks.data(), count, d_tasks, st)) return false;
-        HIP_OK(hipMemcpyAsync(costs, d_costs, count * kColorCosts * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        return true;
-    }();
-    if (st) hipStreamSynchronize(st);
-    return ok ? 0 : -2;
+    return bench.run([&](hipStream_t st) { return color_cost_queue(c, tasks.data(), count, d_tasks, st); });
 }
 
 // ---- slice stacks: the plan, and the two kernels on caller-made inputs (stack.h) ---------------------------------------------
-// The tasks' places in ONE k_stack_cost launch, the upload of the two tables and the launch, queued on st.  The costs are the
-// caller's to zero.
+// ONE k_stack_cost launch over the tasks and their slices, queued on st (cost_queue).  The costs are the caller's to zero.
 static bool stack_cost_queue(nblic_amd_ctx *c, StackCostTask *tasks, size_t n, const StackCostSlice *slices, size_t n_slices, StackCostTask *d_tasks,
                              StackCostSlice *d_slices, hipStream_t st) {
-    unsigned long long tiles = 0, pixels = 0;
-    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(tiles); tiles += stack_task_tiles(tasks[i]); pixels += (unsigned long long)(tasks[i].count) * tasks[i].rows * tasks[i].cols; }
-    if (n == 0) return true;
-    if (tiles >= (1ull << 31) || n >= (size_t(1) << 30) || n_slices >= (size_t(1) << 30)) return false;
-    c->stack_counts[0] += 1; c->stack_counts[1] += long(pixels);
-    return hipMemcpyAsync(d_tasks, tasks, n * sizeof(StackCostTask), hipMemcpyHostToDevice, st) == hipSuccess &&
-           hipMemcpyAsync(d_slices, slices, n_slices * sizeof(StackCostSlice), hipMemcpyHostToDevice, st) == hipSuccess &&
-           stack_cost_launch(d_tasks, int(n), d_slices, uint32_t(tiles), st);
+    return cost_queue(tasks, n, d_tasks, st, stack_task_tiles, [&] {
+        unsigned long long pixels = 0;
+        for (size_t i = 0; i < n; i++) pixels += (unsigned long long)(tasks[i].count) * tasks[i].rows * tasks[i].cols;
+        c->stack_counts[0] += 1; c->stack_counts[1] += long(pixels);
+    }, [&](const StackCostTask *d, int m, uint32_t tiles) { return stack_cost_launch(d, m, d_slices, tiles, st); }, slices, n_slices, d_slices);
 }
 
 int nblic_amd_stack_plan(nblic_amd_ctx *c, int n_images, const nblic_amd_src *srcs, int format, float scale, float bias, int depth, int key_every,
@@ -5932,39 +5958,22 @@ int nblic_amd_stack_plan(nblic_amd_ctx *c, int n_images, const nblic_amd_src *sr
         T.format = uint32_t(format); T.scale = scale; T.bias = bias;
         tasks.push_back(T); stack_of.push_back(s);
     }
-    std::vector<unsigned long long> table(size_t(n_images) * 2, 0ull);
+    std::vector<unsigned long long> sums(tasks.size() * D * 2, 0ull);
     if (!tasks.empty()) {
-        Stream st;
-        Event t0, t1;
-        DevPool mem;
-        const size_t sums = tasks.size() * D * 2;
-        unsigned long long *d_costs = mem.make<unsigned long long>(sums);
-        StackCostTask *d_tasks = mem.make<StackCostTask>(tasks.size());
-        StackCostSlice *d_slices = mem.make<StackCostSlice>(slices.size());
-        std::vector<unsigned long long> back(sums);
-        if (!d_costs || !d_tasks || !d_slices || st.create(hipStreamNonBlocking) != hipSuccess || t0.create(hipEventDefault) != hipSuccess || t1.create(hipEventDefault) != hipSuccess) return -1;
-        for (size_t i = 0; i < tasks.size(); i++) tasks[i].costs = d_costs + i * D * 2;
-        const bool ok = [&]() -> bool {                                  // the launch, then ONE copy of the whole table
-            HIP_OK(hipMemsetAsync(d_costs, 0, sums * sizeof(unsigned long long), st));
-            HIP_OK(hipEventRecord(t0, st));
-            if (!stack_cost_queue(c, tasks.data(), tasks.size(), slices.data(), slices.size(), d_tasks, d_slices, st)) return false;
-            HIP_OK(hipEventRecord(t1, st));
-            HIP_OK(hipMemcpyAsync(back.data(), d_costs, sums * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-            return true;
-        }();
-        if (st) hipStreamSynchronize(st);
-        if (!ok) return -1;
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, t0, t1) == hipSuccess) { std::lock_guard<std::mutex> l(c->stat_m); c->stack_ms = double(ms); }
-        for (size_t i = 0; i < tasks.size(); i++) {
-            const size_t s = stack_of[i];
-            memcpy(&table[s * D * 2], &back[i * D * 2], D * 2 * sizeof(unsigned long long));
-            for (size_t d = 0; d < D; d++)
-                slice_modes[s * D + d] = stack_slice_mode(uint32_t(d), uint32_t(key_every), back[(i * D + d) * 2], back[(i * D + d) * 2 + 1]);
-        }
+        SumsRun run;
+        StackCostTask *d_tasks = run.begin(sums.size()) ? run.mem.make<StackCostTask>(tasks.size()) : nullptr;
+        StackCostSlice *d_slices = d_tasks ? run.mem.make<StackCostSlice>(slices.size()) : nullptr;
+        if (!d_slices) return -1;
+        for (size_t i = 0; i < tasks.size(); i++) tasks[i].costs = run.d_sums + i * D * 2;
+        if (!run.run(c, sums, &c->stack_ms, [&](hipStream_t st) { return stack_cost_queue(c, tasks.data(), tasks.size(), slices.data(), slices.size(), d_tasks, d_slices, st); })) return -1;
     }
-    if (costs) memcpy(costs, table.data(), table.size() * sizeof(unsigned long long));
+    if (costs) std::fill(costs, costs + size_t(n_images) * 2, 0ull);
+    for (size_t i = 0; i < tasks.size(); i++) {
+        const size_t s = stack_of[i];
+        if (costs) memcpy(costs + s * D * 2, &sums[i * D * 2], D * 2 * sizeof(unsigned long long));
+        for (size_t d = 0; d < D; d++)
+            slice_modes[s * D + d] = stack_slice_mode(uint32_t(d), uint32_t(key_every), sums[(i * D + d) * 2], sums[(i * D + d) * 2 + 1]);
+    }
     return 0;
 }
 
@@ -6023,47 +6032,32 @@ int nblic_amd_debug_stack_cost(nblic_amd_ctx *c, int n, const int *counts, const
     const size_t count = size_t(n);
     std::vector<StackCostTask> tasks(count);
     std::vector<StackCostSlice> slices;
-    std::vector<size_t> src_at;
-    size_t srcs_total = 0;
+    DebugBench bench;
     for (size_t i = 0; i < count; i++) {
         if (!debug_stack_cost_task(tasks[i], counts[i], rows[i], cols[i], formats[i], scales[i], biases[i]) || slices.size() + size_t(counts[i]) > (size_t(1) << 20)) return -1;
         tasks[i].first_slice = uint32_t(slices.size());
         for (int d = 0; d < counts[i]; d++) {
             const size_t s = slices.size();
             if (!srcs[s] || base_offsets[s] > 255 || src_bytes[s] > (size_t(1) << 30) || steps[s] > 0xFFFFFFFFull) return -1;
-            src_at.push_back(srcs_total); srcs_total += up256(base_offsets[s] + src_bytes[s] + 256);
+            bench.source(srcs[s], src_bytes[s], base_offsets[s]);
             slices.push_back(StackCostSlice{nullptr, pitches[s], uint32_t(steps[s]), 0u});
         }
     }
-    if (hipSetDevice(c->device) != hipSuccess) return -2;
-    Stream st;
-    DevPool mem;
-    uint8_t *d_srcs = mem.make<uint8_t>(srcs_total);
-    unsigned long long *d_costs = mem.make<unsigned long long>(slices.size() * 2);
-    StackCostTask *d_tasks = mem.make<StackCostTask>(count);
-    StackCostSlice *d_slices = mem.make<StackCostSlice>(slices.size());
-    if (!d_srcs || !d_costs || !d_tasks || !d_slices || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    bench.output(costs, slices.size() * 2 * sizeof(unsigned long long), 0);
+    StackCostTask *d_tasks = bench.alloc(c->device) ? bench.table<StackCostTask>(count) : nullptr;
+    StackCostSlice *d_slices = d_tasks ? bench.table<StackCostSlice>(slices.size()) : nullptr;
+    if (!d_slices) return -2;
     for (size_t i = 0; i < count; i++) {                                 // the addresses are known now: the rest of the checks
         StackCostTask &T = tasks[i];
         std::vector<unsigned long long> caps(T.count);
         for (uint32_t d = 0; d < T.count; d++) {
             const size_t s = T.first_slice + d;
-            slices[s].src = d_srcs + src_at[s] + base_offsets[s]; caps[d] = src_bytes[s];
+            slices[s].src = bench.in(s); caps[d] = src_bytes[s];
         }
-        T.costs = d_costs + size_t(T.first_slice) * 2;
+        T.costs = reinterpret_cast<unsigned long long *>(bench.out(0)) + size_t(T.first_slice) * 2;
         if (!stack_cost_task_ok(T, slices.data(), caps.data())) return -1;      // nothing outside the uploaded bytes is the task's to read
     }
-    const bool ok = [&]() -> bool {
-        HIP_OK(hipMemsetAsync(d_srcs, 0xFF, srcs_total, st));
-        HIP_OK(hipMemsetAsync(d_costs, 0, slices.size() * 2 * sizeof(unsigned long long), st));
-        for (size_t s = 0; s < slices.size(); s++) HIP_OK(hipMemcpyAsync(d_srcs + src_at[s] + base_offsets[s], srcs[s], src_bytes[s], hipMemcpyHostToDevice, st));
-        if (!stack_cost_queue(c, tasks.data(), count, slices.data(), slices.size(), d_tasks, d_slices, st)) return false;
-        HIP_OK(hipMemcpyAsync(costs, d_costs, slices.size() * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        return true;
-    }();
-    if (st) hipStreamSynchronize(st);
-    return ok ? 0 : -2;
+    return bench.run([&](hipStream_t st) { return stack_cost_queue(c, tasks.data(), count, slices.data(), slices.size(), d_tasks, d_slices, st); });
 }
 
 // A debug run's task and slice records: all but the addresses.  window: row0, row1, col0, col1 of planes of plane_rows x
@@ -6128,7 +6122,6 @@ int nblic_amd_debug_stack_deliver(nblic_amd_ctx *c, int n, const int *counts, co
                                   const int *zeros, const size_t *pitches, const size_t *steps, const size_t *dst_offsets, const size_t *out_bytes,
                                   unsigned char *const *outs, const int *gate_status) {
     constexpr int kMaxTasks = 65536;
-    constexpr uint8_t kPattern = 0x5A;
     if (!c || n < 1 || n > kMaxTasks || !counts || !planes || !base_offsets || !plane_rows || !widths || !windows || !formats || !scales || !biases ||
         !zeros || !pitches || !steps || !dst_offsets || !out_bytes || !outs || !gate_status) return -1;
     const size_t count = size_t(n);
@@ -6137,8 +6130,9 @@ int nblic_amd_debug_stack_deliver(nblic_amd_ctx *c, int n, const int *counts, co
     if (total > (size_t(1) << 20)) return -1;
     std::vector<StackDeliverTask> runs(count);
     std::vector<StackSlice> S(total);
-    std::vector<size_t> plane_at(total), out_at(total), plane_len(total);
-    size_t planes_total = 0, outs_total = 0, s0 = 0;
+    std::vector<size_t> out_of(total, 0), plane_len(total);
+    DebugBench bench;
+    size_t s0 = 0;
     for (size_t i = 0; i < count; i++) {
         if (!debug_stack_run(runs[i], S.data() + s0, counts[i], plane_rows[i], widths[i], windows + 4 * i, formats[i], scales + s0, biases + s0, zeros + s0, pitches + s0, steps + s0)) return -1;
         runs[i].first_slice = uint32_t(s0);
@@ -6148,47 +6142,29 @@ int nblic_amd_debug_stack_deliver(nblic_amd_ctx *c, int n, const int *counts, co
             if (!planes[s] || base_offsets[s] > 15 || out_bytes[s] > (size_t(1) << 30)) return -1;
             if (outs[s] && !debug_stack_fits(runs[i], S[s], out_bytes[s], dst_offsets[s])) return -1;
             plane_len[s] = bytes;
-            plane_at[s] = planes_total; planes_total += up256(base_offsets[s] + up256(bytes) + 16);
-            out_at[s] = outs_total; outs_total += up256(outs[s] ? out_bytes[s] : 0);
+            bench.plane(planes[s], bytes, base_offsets[s]);
+            if (outs[s]) out_of[s] = bench.output(outs[s], out_bytes[s]);
         }
         s0 += size_t(counts[i]);
     }
-    if (hipSetDevice(c->device) != hipSuccess) return -2;
-    Stream st;
-    DevPool mem;
-    uint8_t *d_planes = mem.make<uint8_t>(planes_total), *d_outs = mem.make<uint8_t>(std::max<size_t>(outs_total, 256));
-    SerialState *d_gates = mem.make<SerialState>(total);
-    StackDeliverTask *d_runs = mem.make<StackDeliverTask>(count);
-    StackSlice *d_slices = mem.make<StackSlice>(total);
-    if (!d_planes || !d_outs || !d_gates || !d_runs || !d_slices || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    bench.gates(gate_status, total);
+    StackDeliverTask *d_runs = bench.alloc(c->device) ? bench.table<StackDeliverTask>(count) : nullptr;
+    StackSlice *d_slices = d_runs ? bench.table<StackSlice>(total) : nullptr;
+    if (!d_slices) return -2;
     for (size_t i = 0; i < count; i++) {                                 // the addresses are known now: the rest of the checks
         const size_t skip = size_t(windows[4 * i]) * size_t(widths[i]);
         for (size_t s = runs[i].first_slice; s < size_t(runs[i].first_slice) + runs[i].count; s++) {
-            S[s].src = d_planes + plane_at[s] + base_offsets[s] + skip; S[s].src_bytes = up256(plane_len[s]) - skip;
-            if (outs[s]) S[s].dst = d_outs + out_at[s] + dst_offsets[s];
-            if (gate_status[s] != -1) S[s].gate = d_gates + s;
+            S[s].src = bench.in(s) + skip; S[s].src_bytes = up256(plane_len[s]) - skip;
+            if (outs[s]) S[s].dst = bench.out(out_of[s]) + dst_offsets[s];
+            if (gate_status[s] != -1) S[s].gate = bench.gate(s);
         }
         if (!stack_task_ok(runs[i], S.data())) return -1;
     }
-    std::vector<uint8_t> back(std::max<size_t>(outs_total, 1));
-    std::vector<SerialState> gates(total);
-    for (size_t s = 0; s < total; s++) gates[s].status = gate_status[s];
-    const bool ok = [&]() -> bool {
-        HIP_OK(hipMemsetAsync(d_planes, 0, planes_total, st));
-        HIP_OK(hipMemsetAsync(d_outs, kPattern, std::max<size_t>(outs_total, 256), st));
-        HIP_OK(hipMemcpyAsync(d_gates, gates.data(), total * sizeof(SerialState), hipMemcpyHostToDevice, st));
-        for (size_t s = 0; s < total; s++) HIP_OK(hipMemcpyAsync(d_planes + plane_at[s] + base_offsets[s], planes[s], plane_len[s], hipMemcpyHostToDevice, st));
+    return bench.run([&](hipStream_t st) {
         c->stack_counts[2] += 1; c->stack_counts[3] += long(count);
         unsigned long long chunks = 0;
-        if (!deliver_stack_upload(runs.data(), count, S.data(), total, d_runs, d_slices, st, chunks) || !deliver_stack_launch(d_runs, n, d_slices, uint32_t(chunks), st)) return false;
-        if (outs_total) HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        return true;
-    }();
-    if (st) hipStreamSynchronize(st);
-    if (!ok) return -2;
-    for (size_t s = 0; s < total; s++) if (outs[s]) memcpy(outs[s], back.data() + out_at[s], out_bytes[s]);
-    return 0;
+        return deliver_stack_upload(runs.data(), count, S.data(), total, d_runs, d_slices, st, chunks) && deliver_stack_launch(d_runs, n, d_slices, uint32_t(chunks), st);
+    });
 }
 
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
@@ -6738,14 +6714,10 @@ static bool deep_modes_ok(int n_deep, const unsigned char *modes, int deep_forma
     return true;
 }
 
-// The tasks' places in ONE k_deep_cost launch, their upload and the launch, queued on st.  The sums are the caller's to set.
+// ONE k_deep_cost launch over the tasks, queued on st (cost_queue).  The sums are the caller's to set.
 static bool deep_cost_queue(nblic_amd_ctx *c, DeepCostTask *tasks, size_t n, DeepCostTask *d_tasks, hipStream_t st) {
-    unsigned long long tiles = 0;
-    for (size_t i = 0; i < n; i++) { tasks[i].first_chunk = uint32_t(tiles); tiles += deep_task_tiles(tasks[i]); }
-    if (n == 0) return true;
-    if (tiles >= (1ull << 31) || n >= (size_t(1) << 30)) return false;
-    c->deep_counts[0] += 1; c->deep_counts[3] += long(n);
-    return hipMemcpyAsync(d_tasks, tasks, n * sizeof(DeepCostTask), hipMemcpyHostToDevice, st) == hipSuccess && deep_cost_launch(d_tasks, int(n), uint32_t(tiles), st);
+    return cost_queue(tasks, n, d_tasks, st, deep_task_tiles, [&] { c->deep_counts[0] += 1; c->deep_counts[3] += long(n); },
+                      [&](const DeepCostTask *d, int m, uint32_t tiles) { return deep_cost_launch(d, m, tiles, st); });
 }
 // What the sums of n tasks hold before a launch: zero costs, the largest u as the minimum, zero as the maximum.
 static std::vector<unsigned long long> deep_sums_initial(size_t n) {
@@ -6773,28 +6745,13 @@ int nblic_amd_deep_plan(nblic_amd_ctx *c, int n_deep, const nblic_amd_src *srcs,
         tasks.push_back(T); image_of.push_back(i);
     }
     if (tasks.empty()) return 0;
-    Stream st;
-    Event t0, t1;
-    DevPool mem;
     const size_t m = tasks.size();
-    unsigned long long *d_sums = mem.make<unsigned long long>(m * kDeepSums);
-    DeepCostTask *d_tasks = mem.make<DeepCostTask>(m);
     std::vector<unsigned long long> sums = deep_sums_initial(m);
-    if (!d_sums || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess || t0.create(hipEventDefault) != hipSuccess || t1.create(hipEventDefault) != hipSuccess) return -1;
-    for (size_t i = 0; i < m; i++) tasks[i].sums = d_sums + i * kDeepSums;
-    const bool ok = [&]() -> bool {                                      // the launch, then ONE copy of the whole table
-        HIP_OK(hipMemcpyAsync(d_sums, sums.data(), sums.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-        HIP_OK(hipEventRecord(t0, st));
-        if (!deep_cost_queue(c, tasks.data(), m, d_tasks, st)) return false;
-        HIP_OK(hipEventRecord(t1, st));
-        HIP_OK(hipMemcpyAsync(sums.data(), d_sums, sums.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        return true;
-    }();
-    if (st) hipStreamSynchronize(st);
-    if (!ok) return -1;
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, t0, t1) == hipSuccess) { std::lock_guard<std::mutex> l(c->stat_m); c->deep_ms[0] = double(ms); }
+    SumsRun run;
+    DeepCostTask *d_tasks = run.begin(sums.size()) ? run.mem.make<DeepCostTask>(m) : nullptr;
+    if (!d_tasks) return -1;
+    for (size_t i = 0; i < m; i++) tasks[i].sums = run.d_sums + i * kDeepSums;
+    if (!run.run(c, sums, &c->deep_ms[0], [&](hipStream_t st) { return deep_cost_queue(c, tasks.data(), m, d_tasks, st); })) return -1;
     for (size_t i = 0; i < m; i++) {
         const size_t k = image_of[i];
         const unsigned long long *s = &sums[i * kDeepSums];
@@ -6961,54 +6918,34 @@ int nblic_amd_debug_deep_collect(nblic_amd_ctx *c, int n, const void *const *src
                                  const int *cols, const size_t *pitches, const size_t *steps, const int *deep_formats, const int *parts, const int *ranges,
                                  unsigned char *const *outs, const size_t *out_bytes) {
     constexpr int kMaxTasks = 65536;
-    constexpr size_t kGuard = 256;
     if (!c || n < 1 || n > kMaxTasks || !srcs || !src_bytes || !base_offsets || !rows || !cols || !pitches || !steps || !deep_formats || !parts || !outs || !out_bytes) return -1;
     const size_t count = size_t(n);
     std::vector<DeepCollectTask> tasks(count);
-    std::vector<size_t> src_at(count), out_at(count);
-    size_t srcs_total = 0, outs_total = 0;
+    DebugBench bench;
     for (int k = 0; k < n; k++) {
         const size_t i = size_t(k);
         if (!srcs[k] || !outs[k] || base_offsets[k] > 255 || src_bytes[k] > (size_t(1) << 30) ||
             !debug_deep_collect_task(tasks[i], rows[k], cols[k], pitches[k], steps[k], deep_formats[k], parts[k], ranges ? ranges + 2 * i : nullptr)) return -1;
-        const size_t plane = size_t(rows[k]) * size_t(cols[k]);
-        if (plane > (size_t(1) << 30) || out_bytes[k] != kGuard + up256(plane) + kGuard) return -1;
-        src_at[i] = srcs_total; srcs_total += up256(base_offsets[k] + src_bytes[k] + 256);
-        out_at[i] = outs_total; outs_total += out_bytes[k];
+        if (!debug_plane_out_ok(rows[k], cols[k], out_bytes[k])) return -1;
+        bench.source(srcs[k], src_bytes[k], base_offsets[k]);
+        bench.output(outs[k], out_bytes[k]);
     }
-    if (hipSetDevice(c->device) != hipSuccess) return -2;
-    Stream st;
-    DevPool mem;
-    uint8_t *d_srcs = mem.make<uint8_t>(srcs_total), *d_outs = mem.make<uint8_t>(outs_total);
-    DeepCollectTask *d_tasks = mem.make<DeepCollectTask>(count);
-    if (!d_srcs || !d_outs || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    DeepCollectTask *d_tasks = bench.alloc(c->device) ? bench.table<DeepCollectTask>(count) : nullptr;
+    if (!d_tasks) return -2;
     unsigned long long chunks = 0;
-    for (int k = 0; k < n; k++) {                                        // the addresses are known now: the rest of the checks
-        const size_t i = size_t(k);
+    for (size_t i = 0; i < count; i++) {                                 // the addresses are known now: the rest of the checks
         DeepCollectTask &T = tasks[i];
-        T.src = d_srcs + src_at[i] + base_offsets[k];
-        T.dst = d_outs + out_at[i] + kGuard;
-        if (!deep_collect_task_ok(T, src_bytes[k])) return -1;           // nothing outside the uploaded bytes is the task's to read
+        T.src = bench.in(i);
+        T.dst = bench.out(i) + DebugBench::kGuard;
+        if (!deep_collect_task_ok(T, src_bytes[i])) return -1;           // nothing outside the uploaded bytes is the task's to read
         T.first_chunk = uint32_t(chunks); chunks += deep_collect_chunks(T);
     }
     if (chunks >= (1ull << 31)) return -1;
-    std::vector<uint8_t> back(outs_total);
-    const bool ok = [&]() -> bool {
-        HIP_OK(hipMemsetAsync(d_srcs, 0xFF, srcs_total, st));
-        HIP_OK(hipMemsetAsync(d_outs, 0x5A, outs_total, st));
-        for (int k = 0; k < n; k++)
-            HIP_OK(hipMemcpyAsync(d_srcs + src_at[size_t(k)] + base_offsets[k], srcs[k], src_bytes[k], hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(d_tasks, tasks.data(), count * sizeof(DeepCollectTask), hipMemcpyHostToDevice, st));
+    return bench.run([&](hipStream_t st) {
+        if (hipMemcpyAsync(d_tasks, tasks.data(), count * sizeof(DeepCollectTask), hipMemcpyHostToDevice, st) != hipSuccess) return false;
         c->deep_counts[1] += 1;
-        if (!collect_deep_launch(d_tasks, n, uint32_t(chunks), st)) return false;
-        HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        return true;
-    }();
-    if (st) hipStreamSynchronize(st);
-    if (!ok) return -2;
-    for (int k = 0; k < n; k++) memcpy(outs[k], back.data() + out_at[size_t(k)], out_bytes[k]);
-    return 0;
+        return collect_deep_launch(d_tasks, n, uint32_t(chunks), st);
+    });
 }
 
 // A debug deep delivery's task: all but the addresses.  window: row0, row1, col0, col1 of planes of plane_rows x width.
@@ -7049,61 +6986,37 @@ int nblic_amd_debug_deep_deliver(nblic_amd_ctx *c, int n, const unsigned char *c
                                  const float *biases, const int *zeros, const size_t *pitches, const size_t *steps, const size_t *dst_offsets,
                                  const size_t *out_bytes, unsigned char *const *outs, const int *gate_status) {
     constexpr int kMaxTasks = 65536;
-    constexpr uint8_t kPattern = 0x5A;
     if (!c || n < 1 || n > kMaxTasks || !his || !los || !base_offsets || !plane_rows || !widths || !windows || !formats || !modes || !scales || !biases ||
         !zeros || !pitches || !steps || !dst_offsets || !out_bytes || !outs || !gate_status) return -1;
     const size_t count = size_t(n);
     std::vector<DeepDeliverTask> tasks(count);
-    std::vector<size_t> plane_at(2 * count), out_at(count), plane_len(count);
-    size_t planes_total = 0, outs_total = 0;
+    std::vector<size_t> plane_len(count);
+    DebugBench bench;
     for (int k = 0; k < n; k++) {
         const size_t i = size_t(k);
         if (!his[k] || !los[k] || !outs[k] || base_offsets[2 * i] > 15 || base_offsets[2 * i + 1] > 15 ||
             !debug_deep_deliver_task(tasks[i], plane_rows[k], widths[k], windows + 4 * i, formats[k], modes[k], scales[k], biases[k], zeros[k], pitches[k], steps[k])) return -1;
         plane_len[i] = size_t(plane_rows[k]) * size_t(widths[k]);
         if (plane_len[i] > (size_t(1) << 30) || out_bytes[k] > (size_t(1) << 30) || dst_offsets[k] > out_bytes[k]) return -1;
-        for (size_t p = 0; p < 2; p++) { plane_at[2 * i + p] = planes_total; planes_total += up256(base_offsets[2 * i + p] + up256(plane_len[i]) + 16); }
-        out_at[i] = outs_total; outs_total += up256(out_bytes[k]);
+        bench.plane(his[k], plane_len[i], base_offsets[2 * i]);          // inputs 2 i and 2 i + 1
+        bench.plane(los[k], plane_len[i], base_offsets[2 * i + 1]);
+        bench.output(outs[k], out_bytes[k]);
     }
-    if (hipSetDevice(c->device) != hipSuccess) return -2;
-    Stream st;
-    DevPool mem;
-    uint8_t *d_planes = mem.make<uint8_t>(planes_total), *d_outs = mem.make<uint8_t>(std::max<size_t>(outs_total, 256));
-    SerialState *d_gates = mem.make<SerialState>(2 * count);
-    DeepDeliverTask *d_tasks = mem.make<DeepDeliverTask>(count);
-    if (!d_planes || !d_outs || !d_gates || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
+    bench.gates(gate_status, 2 * count);
+    DeepDeliverTask *d_tasks = bench.alloc(c->device) ? bench.table<DeepDeliverTask>(count) : nullptr;
+    if (!d_tasks) return -2;
     for (int k = 0; k < n; k++) {                                        // the addresses are known now: the rest of the checks
         const size_t i = size_t(k);
         DeepDeliverTask &T = tasks[i];
         const size_t skip = size_t(windows[4 * i]) * size_t(widths[k]);
-        T.hi = d_planes + plane_at[2 * i] + base_offsets[2 * i] + skip; T.lo = d_planes + plane_at[2 * i + 1] + base_offsets[2 * i + 1] + skip;
+        T.hi = bench.in(2 * i) + skip; T.lo = bench.in(2 * i + 1) + skip;
         T.hi_bytes = T.lo_bytes = up256(plane_len[i]) - skip;
-        T.dst = d_outs + out_at[i] + dst_offsets[k];
-        if (gate_status[2 * i] != -1) T.gate_hi = d_gates + 2 * i;
-        if (gate_status[2 * i + 1] != -1) T.gate_lo = d_gates + 2 * i + 1;
+        T.dst = bench.out(i) + dst_offsets[k];
+        if (gate_status[2 * i] != -1) T.gate_hi = bench.gate(2 * i);
+        if (gate_status[2 * i + 1] != -1) T.gate_lo = bench.gate(2 * i + 1);
         if (!deep_deliver_task_ok(T) || deep_dest_extent(T.rows, T.col1 - T.col0, T.format, T.dst_pitch, T.dst_step) > out_bytes[k] - dst_offsets[k]) return -1;
     }
-    std::vector<uint8_t> back(std::max<size_t>(outs_total, 1));
-    std::vector<SerialState> gates(2 * count);
-    for (size_t k = 0; k < gates.size(); k++) gates[k].status = gate_status[k];
-    const bool ok = [&]() -> bool {
-        HIP_OK(hipMemsetAsync(d_planes, 0, planes_total, st));
-        HIP_OK(hipMemsetAsync(d_outs, kPattern, std::max<size_t>(outs_total, 256), st));
-        HIP_OK(hipMemcpyAsync(d_gates, gates.data(), gates.size() * sizeof(SerialState), hipMemcpyHostToDevice, st));
-        for (int k = 0; k < n; k++) {
-            const size_t i = size_t(k);
-            HIP_OK(hipMemcpyAsync(d_planes + plane_at[2 * i] + base_offsets[2 * i], his[k], plane_len[i], hipMemcpyHostToDevice, st));
-            HIP_OK(hipMemcpyAsync(d_planes + plane_at[2 * i + 1] + base_offsets[2 * i + 1], los[k], plane_len[i], hipMemcpyHostToDevice, st));
-        }
-        if (!deliver_deep_queue(c, tasks.data(), count, d_tasks, st)) return false;
-        HIP_OK(hipMemcpyAsync(back.data(), d_outs, outs_total, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        return true;
-    }();
-    if (st) hipStreamSynchronize(st);
-    if (!ok) return -2;
-    for (int k = 0; k < n; k++) memcpy(outs[k], back.data() + out_at[size_t(k)], out_bytes[k]);
-    return 0;
+    return bench.run([&](hipStream_t st) { return deliver_deep_queue(c, tasks.data(), count, d_tasks, st); });
 }
 
 static bool debug_deep_cost_task(DeepCostTask &T, int rows, int cols, size_t pitch, size_t step, int deep_format) {
@@ -7134,35 +7047,24 @@ int nblic_amd_debug_deep_cost(nblic_amd_ctx *c, int n, const void *const *srcs, 
     if (!c || n < 1 || n > kMaxTasks || !srcs || !src_bytes || !base_offsets || !rows || !cols || !pitches || !steps || !deep_formats || !sums) return -1;
     const size_t count = size_t(n);
     std::vector<DeepCostTask> tasks(count);
-    std::vector<size_t> src_at(count);
-    size_t srcs_total = 0;
+    DebugBench bench;
     for (size_t i = 0; i < count; i++) {
         if (!srcs[i] || base_offsets[i] > 255 || src_bytes[i] > (size_t(1) << 30) || !debug_deep_cost_task(tasks[i], rows[i], cols[i], pitches[i], steps[i], deep_formats[i])) return -1;
-        src_at[i] = srcs_total; srcs_total += up256(base_offsets[i] + src_bytes[i] + 256);
-    }
-    if (hipSetDevice(c->device) != hipSuccess) return -2;
-    Stream st;
-    DevPool mem;
-    uint8_t *d_srcs = mem.make<uint8_t>(srcs_total);
-    unsigned long long *d_sums = mem.make<unsigned long long>(count * kDeepSums);
-    DeepCostTask *d_tasks = mem.make<DeepCostTask>(count);
-    if (!d_srcs || !d_sums || !d_tasks || st.create(hipStreamNonBlocking) != hipSuccess) return -2;
-    for (size_t i = 0; i < count; i++) {                                 // the addresses are known now: the rest of the checks
-        tasks[i].src = d_srcs + src_at[i] + base_offsets[i]; tasks[i].sums = d_sums + i * kDeepSums;
-        if (!deep_cost_task_ok(tasks[i], src_bytes[i])) return -1;       // nothing outside the uploaded bytes is the task's to read
+        bench.source(srcs[i], src_bytes[i], base_offsets[i]);
     }
     const std::vector<unsigned long long> init = deep_sums_initial(count);
-    const bool ok = [&]() -> bool {
-        HIP_OK(hipMemsetAsync(d_srcs, 0xFF, srcs_total, st));
-        HIP_OK(hipMemcpyAsync(d_sums, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-        for (size_t i = 0; i < count; i++) HIP_OK(hipMemcpyAsync(d_srcs + src_at[i] + base_offsets[i], srcs[i], src_bytes[i], hipMemcpyHostToDevice, st));
-        if (!deep_cost_queue(c, tasks.data(), count, d_tasks, st)) return false;
-        HIP_OK(hipMemcpyAsync(sums, d_sums, count * kDeepSums * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        return true;
-    }();
-    if (st) hipStreamSynchronize(st);
-    return ok ? 0 : -2;
+    bench.output(sums, init.size() * sizeof(unsigned long long), 0);
+    DeepCostTask *d_tasks = bench.alloc(c->device) ? bench.table<DeepCostTask>(count) : nullptr;
+    if (!d_tasks) return -2;
+    unsigned long long *d_sums = reinterpret_cast<unsigned long long *>(bench.out(0));
+    for (size_t i = 0; i < count; i++) {                                 // the addresses are known now: the rest of the checks
+        tasks[i].src = bench.in(i); tasks[i].sums = d_sums + i * kDeepSums;
+        if (!deep_cost_task_ok(tasks[i], src_bytes[i])) return -1;       // nothing outside the uploaded bytes is the task's to read
+    }
+    return bench.run([&](hipStream_t st) {
+        return hipMemcpyAsync(d_sums, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st) == hipSuccess &&
+               deep_cost_queue(c, tasks.data(), count, d_tasks, st);
+    });
 }
 
 int nblic_amd_indexed_decode_split(nblic_amd_ctx *c, double ms[4]) {

@@ -208,8 +208,8 @@ bool deliver_launch(const DeliverTask *d_tasks, int n, uint32_t chunks, hipStrea
 bool collect_launch(const CollectTask *d_tasks, int n, uint32_t chunks, hipStream_t s);
 
 // ---- the cost of a colour frame's nine candidate planes (color_plan.h ColorCostTask) ------------------------------------------
-// k_color_cost, beside k_collect: tasks with first_chunk, one workgroup per tile of kColorTile x kColorTile pixels of one
-// frame.  The workgroup stages the tile's R, G, B pixels -- quantised by k_collect's loader, each source element once -- with
+// k_color_cost, beside k_collect: tasks with first_chunk, one workgroup per tile of kCostTile x kCostTile pixels of one
+// frame (cost_tile.h).  The workgroup stages the tile's R, G, B pixels -- quantised by k_collect's loader, each source element once -- with
 // one row above and one column to the left in LDS, computes the nine residual costs of every pixel from there, and adds its
 // nine sums (lanes, then waves in LDS) to the task's costs with one 64-bit atomic each: integer adds, so the result does
 // not depend on the launch's geometry or order.  The costs are zeroed by the caller.  d_tasks[0..n) with first_chunk

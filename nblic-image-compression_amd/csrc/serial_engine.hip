@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "lsq_f64.h"
 #include "lane_table.h"
@@ -2000,49 +2001,96 @@ bool collect_launch(const CollectTask *d_tasks, int n, uint32_t chunks, hipStrea
     return hipGetLastError() == hipSuccess;
 }
 
-// ---- the costs of a colour frame's nine candidate planes (color_plan.h ColorCostTask) ------------------------------------------
-static_assert(kColorTile == 64 && kIndexThreads == 4 * 64, "a lane per tile column, sixteen rows per wave");
-constexpr uint32_t kColorLdsRows = kColorTile + 1;                   // the row above the tile, then its rows
-constexpr uint32_t kColorLdsPitch = kColorTile + 4;                  // bytes: byte 3 is the column to the left, byte 4 tile column 0 -- units are whole words,
-                                                                     // and 17 words a row keep the words of neighbouring rows on different banks
-constexpr uint32_t kColorRowUnits = kColorTile / kCollectUnitPixels;
+// ---- the cost passes (cost_tile.h; color_plan.h, stack.h, deep.h): one workgroup per tile ----------------------------------------
+static_assert(kCostTile == 64 && kIndexThreads == 4 * 64, "a lane per tile column, sixteen rows per wave");
+// A tile PLANE in LDS, in cells of kCell bytes (1: pixels, 2: 16-bit values): row r holds image row y0 + r - 1 -- the row above
+// the tile, then its rows -- and in a row the cell in front of byte 4 is the column to the left and the tile's columns follow
+// from byte 4 on, so a unit of sixteen cells is 4 * kCell whole words.  The pitch is an odd number of words (17 and 33), so
+// the words of neighbouring rows lie on different banks when the staging lanes of a wave write them; the cost lanes of a
+// wave read neighbouring cells of ONE row and meet no conflict at any pitch.
+constexpr uint32_t kCostLdsRows = kCostTile + 1;
+constexpr uint32_t kCostRowUnits = kCostTile / kCollectUnitPixels;
+constexpr uint32_t cost_lds_pitch(uint32_t cell) { return kCostTile * cell + 4; }            // bytes
+constexpr uint32_t cost_lds_words(uint32_t cell) { return kCostLdsRows * cost_lds_pitch(cell) / 4; }
+constexpr uint32_t kCostWaves = kIndexThreads / 64;
 
-// One workgroup per tile.  STAGE: the tile's rows and the row above, as units of sixteen pixels of one row (one unit per
-// lane and step, neighbouring lanes on neighbouring units, loaded by k_collect's collect_unit_load: aligned words where
-// the elements are neighbours, element by element where they are strided), and the column to the left element by element;
-// every source element is converted once and nothing outside the image is read.  COST: a lane per column, a wave per
-// sixteen rows, top down, so N and NW of a pixel are the lane's P and W of the row before; the nine planes' costs by
-// color_plan.h's own functions.  SUM: over the wave by shuffles, over the four waves in LDS, then nine 64-bit atomic adds.
-__global__ void __launch_bounds__(kIndexThreads) k_color_cost(const ColorCostTask *__restrict__ tasks, int n) {
-    __shared__ uint32_t lds[3 * kColorLdsRows * kColorLdsPitch / 4];
-    __shared__ uint32_t part[kIndexThreads / 64][kColorCosts];
-    const ColorCostTask *tp = tasks + index_task_of(tasks, n, blockIdx.x);
-    const uint32_t rows = tp->rows, cols = tp->cols;
-    CollectTask C{};                                                 // what the loader reads of a task: the format, the quantisation, the width
-    C.format = tp->format; C.scale = tp->scale; C.bias = tp->bias; C.rows = rows; C.cols = cols;
-    const uint32_t across = (cols + kColorTile - 1) / kColorTile, tile = blockIdx.x - tp->first_chunk;
-    const uint32_t y0 = (tile / across) * kColorTile, x0 = (tile % across) * kColorTile;
-    uint8_t *bytes = reinterpret_cast<uint8_t *>(lds);
-    // LDS row r of a channel holds image row y0 + r - 1
-    for (uint32_t j = threadIdx.x; j < 3 * kColorLdsRows * kColorRowUnits; j += kIndexThreads) {
-        const uint32_t ch = j / (kColorLdsRows * kColorRowUnits), r = (j / kColorRowUnits) % kColorLdsRows, q = j % kColorRowUnits;
+// STAGE kPlanes tile planes, one behind the other from lds on, in ONE loop over their units: one unit of sixteen cells of one
+// row per lane and step, neighbouring lanes on neighbouring units, then the column to the left cell by cell.
+// load(plane, y, x, count, word) puts the `count` elements from (y, x) of the plane's source into the cells of
+// word[4 * kCell]; every source element is loaded once apart from the halo and nothing outside the image is asked for.
+template <uint32_t kPlanes, uint32_t kCell, class Load>
+__device__ __forceinline__ void cost_stage(uint32_t *lds, uint32_t rows, uint32_t cols, uint32_t y0, uint32_t x0, Load load) {
+    constexpr uint32_t kUnitWords = 4 * kCell, kPitchWords = cost_lds_pitch(kCell) / 4;
+    for (uint32_t j = threadIdx.x; j < kPlanes * kCostLdsRows * kCostRowUnits; j += kIndexThreads) {
+        const uint32_t row = j / kCostRowUnits, q = j % kCostRowUnits, pl = kPlanes == 1 ? 0u : row / kCostLdsRows, r = row - pl * kCostLdsRows;
         const uint32_t y = y0 + r - 1u, x = x0 + q * kCollectUnitPixels;
         if ((r == 0 && y0 == 0) || y >= rows || x >= cols) continue;
-        uint32_t word[4];
-        collect_unit_load(C, gp(tp->src[ch]), tp->pitch[ch], tp->step[ch], y, x, 0u, cols - x < 16u ? cols - x : 16u, word);
-        uint32_t *d = lds + ((ch * kColorLdsRows + r) * kColorLdsPitch + 4u + q * kCollectUnitPixels) / 4u;
+        uint32_t word[kUnitWords];
+        load(pl, y, x, cols - x < 16u ? cols - x : 16u, word);
+        // (a byte index over four, not a word index: from the latter the compiler makes code that needs some thirty scalar
+        // registers more, and k_stack_cost falls from eight waves a SIMD to seven)
+        uint32_t *d = lds + ((pl * kCostLdsRows + r) * cost_lds_pitch(kCell) + 4u + q * kCollectUnitPixels * kCell) / 4u;
 #pragma unroll
-        for (int i = 0; i < 4; i++) d[i] = word[i];
+        for (uint32_t i = 0; i < kUnitWords; i++) d[i] = word[i];
     }
-    if (x0 > 0 && threadIdx.x < 3 * kColorLdsRows) {
-        const uint32_t ch = threadIdx.x / kColorLdsRows, r = threadIdx.x % kColorLdsRows, y = y0 + r - 1u;
+    if (x0 > 0 && threadIdx.x < kPlanes * kCostLdsRows) {
+        const uint32_t pl = kPlanes == 1 ? 0u : threadIdx.x / kCostLdsRows, r = threadIdx.x - pl * kCostLdsRows, y = y0 + r - 1u;
         if (!(r == 0 && y0 == 0) && y < rows) {
-            uint32_t word[4];
-            collect_unit_load(C, gp(tp->src[ch]), tp->pitch[ch], tp->step[ch], y, x0 - 1u, 0u, 1u, word);
-            bytes[(ch * kColorLdsRows + r) * kColorLdsPitch + 3u] = uint8_t(word[0]);
+            uint32_t word[kUnitWords];
+            load(pl, y, x0 - 1u, 1u, word);
+            using Cell = typename std::conditional<kCell == 1, uint8_t, uint16_t>::type;
+            reinterpret_cast<Cell *>(lds + (pl * kCostLdsRows + r) * kPitchWords)[4u / kCell - 1u] = Cell(word[0]);
         }
     }
+}
+// The 8-bit planes are loaded by k_collect's collect_unit_load -- aligned words where the elements are neighbours, element by
+// element where they are strided -- so every source element is converted once, as k_collect would.  This is its task.
+__device__ __forceinline__ CollectTask cost_loader_task(uint32_t rows, uint32_t cols, uint32_t format, float scale, float bias) {
+    CollectTask C{};                                                 // what the loader reads of a task: the format, the quantisation, the width
+    C.format = format; C.scale = scale; C.bias = bias; C.rows = rows; C.cols = cols;
+    return C;
+}
+
+// SUM: v[k] of every lane combined by op(k, a, b) over the wave by shuffles, over the four waves through part[], and the
+// block's value of number k handed to lane k of the block: done(k, total).  One barrier, between the waves' stores to part[]
+// and the first lanes' loads.
+template <uint32_t N, class Op, class Done>
+__device__ __forceinline__ void cost_block_reduce(uint32_t (&v)[N], uint32_t (*part)[N], Op op, Done done) {
+    const uint32_t wave = threadIdx.x / 64u, lane = threadIdx.x % 64u;
+#pragma unroll
+    for (uint32_t k = 0; k < N; k++) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[k] = op(k, v[k], uint32_t(__shfl_down(v[k], off, 64)));
+        if (lane == 0) part[wave][k] = v[k];
+    }
     __syncthreads();
+    if (threadIdx.x < N) {
+        unsigned long long total = part[0][threadIdx.x];
+        for (uint32_t wv = 1; wv < kCostWaves; wv++) total = op(threadIdx.x, total, (unsigned long long)(part[wv][threadIdx.x]));
+        done(threadIdx.x, total);
+    }
+}
+// (a sum of a lane is at most 16 x 17: the shuffles cannot overflow 32 bits)
+struct CostAdd { template <class T> __device__ T operator()(uint32_t, T a, T b) const { return a + b; } };
+
+// The costs of a colour frame's nine candidate planes (color_plan.h ColorCostTask).  STAGE: the three channels' planes
+// (cost_stage, collect_unit_load).  COST: a lane per column, a wave per sixteen rows, top down, so N and NW of a pixel are the
+// lane's P and W of the row before; the nine planes' costs by color_plan.h's own functions.  SUM: cost_block_reduce, then
+// nine 64-bit atomic adds.
+__global__ void __launch_bounds__(kIndexThreads) k_color_cost(const ColorCostTask *__restrict__ tasks, int n) {
+    constexpr uint32_t kPitch = cost_lds_pitch(1);
+    __shared__ uint32_t lds[3 * cost_lds_words(1)];
+    __shared__ uint32_t part[kCostWaves][kColorCosts];
+    const ColorCostTask *tp = tasks + index_task_of(tasks, n, blockIdx.x);
+    const uint32_t rows = tp->rows, cols = tp->cols;
+    const CollectTask C = cost_loader_task(rows, cols, tp->format, tp->scale, tp->bias);
+    const CostTile T = cost_tile_of(rows, cols, blockIdx.x - tp->first_chunk);
+    const uint32_t y0 = T.y0, x0 = T.x0;
+    cost_stage<3, 1>(lds, rows, cols, y0, x0, [&](uint32_t ch, uint32_t y, uint32_t x, uint32_t count, uint32_t word[4]) {
+        collect_unit_load(C, gp(tp->src[ch]), tp->pitch[ch], tp->step[ch], y, x, 0u, count, word);
+    });
+    __syncthreads();
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(lds);
     const uint32_t wave = threadIdx.x / 64u, lane = threadIdx.x % 64u, x = x0 + lane;
     uint32_t sums[kColorCosts] = {};
     if (x < cols) {
@@ -2050,14 +2098,14 @@ __global__ void __launch_bounds__(kIndexThreads) k_color_cost(const ColorCostTas
         uint32_t nn[3], nw[3];
 #pragma unroll
         for (uint32_t ch = 0; ch < 3; ch++) {
-            const uint8_t *row = bytes + (ch * kColorLdsRows + r0) * kColorLdsPitch + 3u + lane;
+            const uint8_t *row = bytes + (ch * kCostLdsRows + r0) * kPitch + 3u + lane;
             nw[ch] = row[0]; nn[ch] = row[1];                        // (row 0 or column 0 of the image: never looked at)
         }
         for (uint32_t r = r0; r < r0 + 16u && y0 + r < rows; r++) {
             uint32_t p[3], w[3];
 #pragma unroll
             for (uint32_t ch = 0; ch < 3; ch++) {
-                const uint8_t *row = bytes + (ch * kColorLdsRows + r + 1u) * kColorLdsPitch + 3u + lane;
+                const uint8_t *row = bytes + (ch * kCostLdsRows + r + 1u) * kPitch + 3u + lane;
                 w[ch] = row[0]; p[ch] = row[1];
             }
             color_pixel_costs(p, w, nn, nw, y0 + r, x, sums);
@@ -2065,19 +2113,7 @@ __global__ void __launch_bounds__(kIndexThreads) k_color_cost(const ColorCostTas
             for (uint32_t ch = 0; ch < 3; ch++) { nn[ch] = p[ch]; nw[ch] = w[ch]; }
         }
     }
-#pragma unroll
-    for (uint32_t k = 0; k < kColorCosts; k++) {
-        uint32_t v = sums[k];                                        // (at most 16 x 17 a lane)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane == 0) part[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < kColorCosts) {
-        unsigned long long total = 0;
-        for (uint32_t wv = 0; wv < kIndexThreads / 64; wv++) total += part[wv][threadIdx.x];
-        atomicAdd(tp->costs + threadIdx.x, total);
-    }
+    cost_block_reduce(sums, part, CostAdd{}, [&](uint32_t k, unsigned long long total) { atomicAdd(tp->costs + k, total); });
 }
 
 bool color_cost_launch(const ColorCostTask *d_tasks, int n, uint32_t tiles, hipStream_t s) {
@@ -2147,68 +2183,43 @@ bool deliver_stack_launch(const StackDeliverTask *d_tasks, int n, const StackSli
     return hipGetLastError() == hipSuccess;
 }
 
-// One workgroup per tile POSITION of one stack: it walks the stack's slices with two LDS tile buffers, the slice before and
-// the current one, swapped by index, each laid out like k_color_cost's (the row above, the column to the left).  STAGE: as
-// k_color_cost, through collect_unit_load -- every source element is converted once apart from the halo, nothing outside the
-// image is read.  COST: a lane per column, a wave per sixteen rows, top down; the slice's own cost and that of its
-// difference against the buffer of the slice before (stack.h stack_pixel_costs).  SUM: wave shuffles, the four waves in
-// LDS, then two 64-bit atomic adds per slice.
+// One workgroup per tile POSITION of one stack: it walks the stack's slices with two LDS tile planes, the slice before and
+// the current one, swapped by index.  STAGE: the slice's plane (cost_stage, collect_unit_load), as k_color_cost.  COST: a
+// lane per column, a wave per sixteen rows, top down; the slice's own cost and that of its difference against the plane of
+// the slice before (stack.h stack_pixel_costs).  SUM: cost_block_reduce, then two 64-bit atomic adds per slice.
 __global__ void __launch_bounds__(kIndexThreads) k_stack_cost(const StackCostTask *__restrict__ tasks, int n, const StackCostSlice *__restrict__ slices) {
-    __shared__ uint32_t lds[2 * kColorLdsRows * kColorLdsPitch / 4];
-    __shared__ uint32_t part[kIndexThreads / 64][2];
+    constexpr uint32_t kPitch = cost_lds_pitch(1);
+    __shared__ uint32_t lds[2 * cost_lds_words(1)];
+    __shared__ uint32_t part[kCostWaves][2];
     const StackCostTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
     const uint32_t rows = T.rows, cols = T.cols;
-    CollectTask C{};                                                 // what the loader reads of a task: the format, the quantisation, the width
-    C.format = T.format; C.scale = T.scale; C.bias = T.bias; C.rows = rows; C.cols = cols;
-    const uint32_t across = stack_tiles_across(T), tile = blockIdx.x - T.first_chunk;
-    const uint32_t y0 = (tile / across) * kColorTile, x0 = (tile % across) * kColorTile;
-    uint8_t *bytes = reinterpret_cast<uint8_t *>(lds);
+    const CollectTask C = cost_loader_task(rows, cols, T.format, T.scale, T.bias);
+    const CostTile tile = cost_tile_of(rows, cols, blockIdx.x - T.first_chunk);
+    const uint32_t y0 = tile.y0, x0 = tile.x0;
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(lds);
     const uint32_t wave = threadIdx.x / 64u, lane = threadIdx.x % 64u, x = x0 + lane;
     for (uint32_t d = 0; d < T.count; d++) {
         const StackCostSlice S = slices[T.first_slice + d];
         const uint32_t cur = d & 1u, prv = cur ^ 1u;
-        // LDS row r of a buffer holds image row y0 + r - 1
-        for (uint32_t j = threadIdx.x; j < kColorLdsRows * kColorRowUnits; j += kIndexThreads) {
-            const uint32_t r = j / kColorRowUnits, q = j % kColorRowUnits;
-            const uint32_t y = y0 + r - 1u, xx = x0 + q * kCollectUnitPixels;
-            if ((r == 0 && y0 == 0) || y >= rows || xx >= cols) continue;
-            uint32_t word[4];
-            collect_unit_load(C, gp(S.src), S.pitch, S.step, y, xx, 0u, cols - xx < 16u ? cols - xx : 16u, word);
-            uint32_t *o = lds + ((cur * kColorLdsRows + r) * kColorLdsPitch + 4u + q * kCollectUnitPixels) / 4u;
-#pragma unroll
-            for (int i = 0; i < 4; i++) o[i] = word[i];
-        }
-        if (x0 > 0 && threadIdx.x < kColorLdsRows) {
-            const uint32_t r = threadIdx.x, y = y0 + r - 1u;
-            if (!(r == 0 && y0 == 0) && y < rows) {
-                uint32_t word[4];
-                collect_unit_load(C, gp(S.src), S.pitch, S.step, y, x0 - 1u, 0u, 1u, word);
-                bytes[(cur * kColorLdsRows + r) * kColorLdsPitch + 3u] = uint8_t(word[0]);
-            }
-        }
+        cost_stage<1, 1>(lds + cur * cost_lds_words(1), rows, cols, y0, x0, [&](uint32_t, uint32_t y, uint32_t xx, uint32_t count, uint32_t word[4]) {
+            collect_unit_load(C, gp(S.src), S.pitch, S.step, y, xx, 0u, count, word);
+        });
         __syncthreads();
-        uint32_t intra = 0u, delta = 0u;
+        uint32_t sums[2] = {0u, 0u};                                 // intra, delta
         if (x < cols) {
             const uint32_t r0 = wave * 16u;                          // the wave's first tile row; LDS row r0 is the one above it
-            const uint8_t *a = bytes + (cur * kColorLdsRows + r0) * kColorLdsPitch + 3u + lane;
-            const uint8_t *b = bytes + (prv * kColorLdsRows + r0) * kColorLdsPitch + 3u + lane;
+            const uint8_t *a = bytes + (cur * kCostLdsRows + r0) * kPitch + 3u + lane;
+            const uint8_t *b = bytes + (prv * kCostLdsRows + r0) * kPitch + 3u + lane;
             uint32_t nw = a[0], nn = a[1], pnw = b[0], pn = b[1];    // (row 0 or column 0 of the image: never looked at)
             for (uint32_t r = r0; r < r0 + 16u && y0 + r < rows; r++) {
-                a += kColorLdsPitch; b += kColorLdsPitch;
+                a += kPitch; b += kPitch;
                 const uint32_t w = a[0], p = a[1], pw = b[0], pp = b[1];
-                stack_pixel_costs(p, w, nn, nw, pp, pw, pn, pnw, d > 0, y0 + r, x, intra, delta);
+                stack_pixel_costs(p, w, nn, nw, pp, pw, pn, pnw, d > 0, y0 + r, x, sums[0], sums[1]);
                 nn = p; nw = w; pn = pp; pnw = pw;
             }
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { intra += __shfl_down(intra, off, 64); delta += __shfl_down(delta, off, 64); }      // (at most 16 x 17 a lane)
-        if (lane == 0) { part[wave][0] = intra; part[wave][1] = delta; }
-        __syncthreads();                                             // every lane is done with the buffer of the slice before: the next slice goes there
-        if (threadIdx.x < 2) {
-            unsigned long long total = 0;
-            for (uint32_t wv = 0; wv < kIndexThreads / 64; wv++) total += part[wv][threadIdx.x];
-            atomicAdd(T.costs + 2u * d + threadIdx.x, total);
-        }
+        // (past the reduction's barrier every lane is done with the plane of the slice before: the next slice goes there)
+        cost_block_reduce(sums, part, CostAdd{}, [&](uint32_t k, unsigned long long total) { atomicAdd(T.costs + 2u * d + k, total); });
     }
 }
 
@@ -2339,81 +2350,44 @@ bool deliver_deep_launch(const DeepDeliverTask *d_tasks, int n, uint32_t chunks,
     return hipGetLastError() == hipSuccess;
 }
 
-// LDS row r of a tile holds image row y0 + r - 1 in 2-byte cells: cell 1 the column to the left, cells 2 .. 65 the tile's
-// columns (cell 0 is not used), so a unit of sixteen cells is eight whole words.  33 words a row: the pitch is odd, as
-// k_color_cost's 17, so the words of neighbouring rows lie on different banks when the staging lanes of a wave -- four units
-// of sixteen rows -- write them; the cost lanes of a wave read 65 neighbouring cells of ONE row, 33 neighbouring words, two
-// lanes to a word, and meet no conflict at any pitch.
-constexpr uint32_t kDeepLdsRows = kColorTile + 1;
-constexpr uint32_t kDeepLdsPitch = kColorTile / 2 + 1;               // words
-constexpr uint32_t kDeepLdsCells = 2 * kDeepLdsPitch;
-
-// One workgroup per tile.  STAGE: the tile's rows and the row above as units of sixteen elements (deep_unit_load: aligned
-// words where the elements are neighbours), the column to the left element by element; every source element is read once
-// apart from the halo and nothing outside the image is read.  COST: a lane per column, a wave per sixteen rows, top down, so
-// N and NW of a pixel are the lane's own value and W of the row before; the three planes' costs by deep.h's own functions.
-// SUM: over the wave by shuffles, over the four waves in LDS, then three 64-bit atomic adds, one atomic min and one max.
+// The three costs and the range of a deep image (deep.h DeepCostTask).  STAGE: one plane of 16-bit cells (cost_stage,
+// deep_unit_load: aligned words where the elements are neighbours).  COST: a lane per column, a wave per sixteen rows, top
+// down, so N and NW of a pixel are the lane's own value and W of the row before; the three planes' costs by deep.h's own
+// functions.  SUM: cost_block_reduce -- three sums, a minimum and a maximum -- then three 64-bit atomic adds, one atomic min
+// and one max.
 __global__ void __launch_bounds__(kIndexThreads) k_deep_cost(const DeepCostTask *__restrict__ tasks, int n) {
-    __shared__ uint32_t lds[kDeepLdsRows * kDeepLdsPitch];
-    __shared__ uint32_t part[kIndexThreads / 64][kDeepSums];
+    constexpr uint32_t kCells = cost_lds_pitch(2) / 2;
+    __shared__ uint32_t lds[cost_lds_words(2)];
+    __shared__ uint32_t part[kCostWaves][kDeepSums];
     const DeepCostTask T = tasks[index_task_of(tasks, n, blockIdx.x)];
     const uint32_t rows = T.rows, cols = T.cols;
-    const uint32_t across = deep_tiles_across(T), tile = blockIdx.x - T.first_chunk;
-    const uint32_t y0 = (tile / across) * kColorTile, x0 = (tile % across) * kColorTile;
-    uint16_t *cells = reinterpret_cast<uint16_t *>(lds);
-    for (uint32_t j = threadIdx.x; j < kDeepLdsRows * kColorRowUnits; j += kIndexThreads) {
-        const uint32_t r = j / kColorRowUnits, q = j % kColorRowUnits;
-        const uint32_t y = y0 + r - 1u, x = x0 + q * kCollectUnitPixels;
-        if ((r == 0 && y0 == 0) || y >= rows || x >= cols) continue;
-        uint32_t cell[8];
-        deep_unit_load(gp(T.src), T.pitch, T.step, cols, T.format, y, x, 0u, cols - x < 16u ? cols - x : 16u, cell);
-        uint32_t *o = lds + r * kDeepLdsPitch + 1u + q * (kCollectUnitPixels / 2u);
-#pragma unroll
-        for (int i = 0; i < 8; i++) o[i] = cell[i];
-    }
-    if (x0 > 0 && threadIdx.x < kDeepLdsRows) {
-        const uint32_t r = threadIdx.x, y = y0 + r - 1u;
-        if (!(r == 0 && y0 == 0) && y < rows) {
-            uint32_t cell[8];
-            deep_unit_load(gp(T.src), T.pitch, T.step, cols, T.format, y, x0 - 1u, 0u, 1u, cell);
-            cells[r * kDeepLdsCells + 1u] = uint16_t(cell[0]);
-        }
-    }
+    const CostTile tile = cost_tile_of(rows, cols, blockIdx.x - T.first_chunk);
+    const uint32_t y0 = tile.y0, x0 = tile.x0;
+    cost_stage<1, 2>(lds, rows, cols, y0, x0, [&](uint32_t, uint32_t y, uint32_t x, uint32_t count, uint32_t cell[8]) {
+        deep_unit_load(gp(T.src), T.pitch, T.step, cols, T.format, y, x, 0u, count, cell);
+    });
     __syncthreads();
+    const uint16_t *cells = reinterpret_cast<const uint16_t *>(lds);
     const uint32_t wave = threadIdx.x / 64u, lane = threadIdx.x % 64u, x = x0 + lane;
-    uint32_t sums[kDeepParts] = {}, lo = 0xFFFFu, hi = 0u;
+    uint32_t v[kDeepSums] = {0u, 0u, 0u, 0xFFFFu, 0u};               // the three costs, then min and max of u
     if (x < cols) {
         const uint32_t r0 = wave * 16u;                              // the wave's first tile row; LDS row r0 is the one above it
-        const uint16_t *row = cells + r0 * kDeepLdsCells + 1u + lane;
+        const uint16_t *row = cells + r0 * kCells + 1u + lane;
         uint32_t nw = row[0], nn = row[1];                           // (row 0 or column 0 of the image: never looked at)
         for (uint32_t r = r0; r < r0 + 16u && y0 + r < rows; r++) {
-            row += kDeepLdsCells;
+            row += kCells;
             const uint32_t w = row[0], p = row[1];
-            deep_pixel_costs(p, w, nn, nw, y0 + r, x, sums);
-            lo = p < lo ? p : lo; hi = p > hi ? p : hi;
+            deep_pixel_costs(p, w, nn, nw, y0 + r, x, v);
+            v[3] = p < v[3] ? p : v[3]; v[4] = p > v[4] ? p : v[4];
             nn = p; nw = w;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (uint32_t k = 0; k < kDeepParts; k++) sums[k] += __shfl_down(sums[k], off, 64);      // (at most 16 x 17 a lane)
-        const uint32_t a = __shfl_down(lo, off, 64), b = __shfl_down(hi, off, 64);
-        lo = a < lo ? a : lo; hi = b > hi ? b : hi;
-    }
-    if (lane == 0) { part[wave][0] = sums[0]; part[wave][1] = sums[1]; part[wave][2] = sums[2]; part[wave][3] = lo; part[wave][4] = hi; }
-    __syncthreads();
-    if (threadIdx.x < kDeepSums) {
-        const uint32_t k = threadIdx.x;
-        unsigned long long total = part[0][k];
-        for (uint32_t wv = 1; wv < kIndexThreads / 64; wv++) {
-            const unsigned long long v = part[wv][k];
-            total = k < kDeepParts ? total + v : (k == 3 ? (v < total ? v : total) : (v > total ? v : total));
-        }
+    cost_block_reduce(v, part, [](uint32_t k, auto a, auto b) { return k < kDeepParts ? a + b : (k == 3 ? (b < a ? b : a) : (b > a ? b : a)); },
+                      [&](uint32_t k, unsigned long long total) {
         if (k < kDeepParts) atomicAdd(T.sums + k, total);
         else if (k == 3) atomicMin(T.sums + 3, total);
         else atomicMax(T.sums + 4, total);
-    }
+    });
 }
 
 bool deep_cost_launch(const DeepCostTask *d_tasks, int n, uint32_t tiles, hipStream_t s) {

@@ -3,7 +3,8 @@
 // differences, the byte arithmetic, the delivery of a run and the two costs of a slice, shared by the host and the device:
 // the kernels' lanes (serial_engine.hip, k_deliver_stack and k_stack_cost) and the host-only stack_deliver_host and
 // stack_cost_host below call the same functions, so the walks and the arithmetic are tested without a GPU
-// (tests/test_stack_host.py, tools/stack_check.cpp).  Built on collect.h, deliver.h and color_plan.h.
+// (tests/test_stack_host.py, tools/stack_check.cpp).  Built on collect.h, deliver.h and color_plan.h (a slice's cost is a colour
+// plane's: color_pixel_cost); the tile geometry, the MED prediction and the host's tile walk live in cost_tile.h.
 //
 // THE STACK.  A call has a depth D >= 1 and n_images % D == 0; image s * D + d is slice d of stack s (n-major, as a
 // [N, D, H, W] tensor is read).  The slices of a stack have one size.
@@ -168,8 +169,7 @@ struct StackCostTask {
 };
 static_assert(sizeof(StackCostTask) == 40, "uploaded as bytes");
 
-CL_HD uint32_t stack_tiles_across(const StackCostTask &t) { return (t.cols + kColorTile - 1) / kColorTile; }
-CL_HD uint32_t stack_task_tiles(const StackCostTask &t) { return stack_tiles_across(t) * ((t.rows + kColorTile - 1) / kColorTile); }
+CL_HD uint32_t stack_task_tiles(const StackCostTask &t) { return cost_tiles(t.rows, t.cols); }
 
 // Slice d's source as the collect task whose loader and checks it shares (all but dst and the pixel range).
 CL_HD CollectTask stack_source(const StackCostTask &t, const StackCostSlice &s) {
@@ -185,8 +185,8 @@ CL_HD CollectTask stack_source(const StackCostTask &t, const StackCostSlice &s) 
 template <class Sum>
 CL_HD void stack_pixel_costs(uint32_t p, uint32_t w, uint32_t n, uint32_t nw, uint32_t pp, uint32_t pw, uint32_t pn, uint32_t pnw, bool has_prev,
                              uint32_t y, uint32_t x, Sum &intra, Sum &delta) {
-    intra += color_pixel_cost(p, color_pred(w, n, nw, y, x));
-    if (has_prev) delta += color_pixel_cost(stack_delta(p, pp), color_pred(stack_delta(w, pw), stack_delta(n, pn), stack_delta(nw, pnw), y, x));
+    intra += color_pixel_cost(p, cost_pred(w, n, nw, y, x));
+    if (has_prev) delta += color_pixel_cost(stack_delta(p, pp), cost_pred(stack_delta(w, pw), stack_delta(n, pn), stack_delta(nw, pnw), y, x));
 }
 
 inline bool stack_cost_task_ok(const StackCostTask &t, const StackCostSlice *slices, const unsigned long long *caps) {
@@ -199,32 +199,21 @@ inline bool stack_cost_task_ok(const StackCostTask &t, const StackCostSlice *sli
 // The host walk: every tile of the task, one after the other; the stack's slices for each, pixel by pixel; each element is
 // read where it lies.
 inline void stack_cost_host(const StackCostTask &t, const StackCostSlice *slices) {
-    const uint32_t elem = collect_elem(t.format), tiles = stack_task_tiles(t), across = stack_tiles_across(t);
-    auto pixel = [&](uint32_t d, uint32_t y, uint32_t x) {
-        const StackCostSlice &s = slices[t.first_slice + d];
-        uint32_t v = 0;
-        memcpy(&v, s.src + (unsigned long long)(y) * s.pitch + (unsigned long long)(x) * s.step, elem);
-        return collect_value(v, t.format, t.scale, t.bias);
-    };
-    for (uint32_t k = 0; k < tiles; k++) {
-        const uint32_t y0 = (k / across) * kColorTile, x0 = (k % across) * kColorTile;
-        const uint32_t y1 = t.rows - y0 > kColorTile ? y0 + kColorTile : t.rows, x1 = t.cols - x0 > kColorTile ? x0 + kColorTile : t.cols;
+    const uint32_t elem = collect_elem(t.format);
+    cost_walk_tiles(t.rows, t.cols, [&](const CostTile &T) {
         for (uint32_t d = 0; d < t.count; d++) {
             unsigned long long intra = 0, delta = 0;
-            for (uint32_t y = y0; y < y1; y++)
-                for (uint32_t x = x0; x < x1; x++) {
-                    uint32_t v[2][4] = {};                           // [this slice, the one before][p, w, n, nw]
-                    for (uint32_t b = 0; b < (d ? 2u : 1u); b++) {
-                        v[b][0] = pixel(d - b, y, x);
-                        if (x) v[b][1] = pixel(d - b, y, x - 1);
-                        if (y) v[b][2] = pixel(d - b, y - 1, x);
-                        if (x && y) v[b][3] = pixel(d - b, y - 1, x - 1);
-                    }
-                    stack_pixel_costs(v[0][0], v[0][1], v[0][2], v[0][3], v[1][0], v[1][1], v[1][2], v[1][3], d > 0, y, x, intra, delta);
+            cost_tile_pixels(T, [&](uint32_t y, uint32_t x) {
+                uint32_t v[2][4] = {};                               // [this slice, the one before][p, w, n, nw]
+                for (uint32_t b = 0; b < (d ? 2u : 1u); b++) {
+                    const StackCostSlice &s = slices[t.first_slice + d - b];
+                    cost_neighbours([&](uint32_t yy, uint32_t xx) { return collect_value(cost_element(s.src, s.pitch, s.step, elem, yy, xx), t.format, t.scale, t.bias); }, y, x, v[b]);
                 }
+                stack_pixel_costs(v[0][0], v[0][1], v[0][2], v[0][3], v[1][0], v[1][1], v[1][2], v[1][3], d > 0, y, x, intra, delta);
+            });
             t.costs[2 * d] += intra; t.costs[2 * d + 1] += delta;
         }
-    }
+    });
 }
 
 }  // namespace nblic

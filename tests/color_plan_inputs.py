@@ -8,9 +8,10 @@ import inputs
 from collect_inputs import ELEM, NORMS, as_values, element_bits, lay_out
 from rct_inputs import exhaustive_frame
 
-TILE = 64                                                      # color_plan.h kColorTile
+TILE = 64                                                      # cost_tile.h kCostTile
 # a pixel, one row, one column, a few of each; one tile exactly; a row and a column more; two tiles each way plus one
-SHAPES = ((1, 1), (1, 17), (17, 1), (3, 5), (TILE, TILE), (TILE + 1, TILE + 1), (2 * TILE + 1, 2 * TILE + 1))
+SHAPES = ((1, 1), (1, 17), (17, 1), (3, 5), (TILE, TILE), (TILE + 1, TILE + 1), (2 * TILE + 1, 2 * TILE + 1),
+          (TILE + 1, 2 * TILE + 2), (2 * TILE + 2, TILE + 1))       # (2 x 3 and 3 x 2 tiles: a grid that is not square)
 LAYOUTS = ("contiguous", "interleaved", "pitched")
 
 

@@ -11,7 +11,7 @@ PATTERN = 0x5A                                                   # what every ou
 GUARD = 256                                                      # bytes of it around a collected plane on the device
 # a pixel; one row with a unit and a pixel; fewer pixels than a unit; a unit and a tile edge on both sides; one tile
 # exactly; a row and two columns more than a tile, two units and two more than eight
-SHAPES = ((1, 1), (1, 17), (3, 5), (33, 65), (64, 64), (65, 130))
+SHAPES = ((1, 1), (1, 17), (3, 5), (33, 65), (64, 64), (65, 130), (130, 65))   # (the last two: 2 x 3 and 3 x 2 tiles)
 LAYOUTS = ("contiguous", "pitched", "step 6", "odd offset")
 EDGE_U = (0, 255, 256, 257, 0x7FFF, 0x8000, 0xFFFF)               # u at the byte and the sign boundaries
 EDGE_I16 = (-32768, -1, 0)

@@ -11,7 +11,7 @@ from test_deliver_strided_host import NORMS as DELIVER_NORMS, PATTERN, scatter
 
 # a pixel, one row, one column, a few of each, no multiple of sixteen; one cost tile exactly; a row and a column more; two
 # tiles each way plus one
-SHAPES = ((1, 1), (1, 17), (17, 1), (3, 5), (33, 17), (64, 64), (65, 65), (129, 129))
+SHAPES = ((1, 1), (1, 17), (17, 1), (3, 5), (33, 17), (64, 64), (65, 65), (129, 129), (65, 130), (130, 65))   # (the last two: 2 x 3 and 3 x 2 tiles)
 DEPTHS = (1, 2, 3, 5, 9)
 PATTERNS = ("all keys", "all deltas", "a key in the middle", "a key last")
 

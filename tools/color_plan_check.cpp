@@ -101,9 +101,10 @@ static int one_frame(std::mt19937 &rng, uint32_t format, uint32_t rows, uint32_t
     for (uint32_t ch = 0; ch < 3; ch++) { caps[ch]--; CHECK(!color_task_ok(T, caps)); caps[ch]++; }
     uint32_t covered = 0;                                            // the tiles cover the frame once
     for (uint32_t k = 0; k < color_task_tiles(T); k++) {
-        const ColorTile t = color_tile_of(T, k);
-        CHECK(t.y0 % kColorTile == 0 && t.x0 % kColorTile == 0 && t.y0 < rows && t.x0 < cols);
-        covered += std::min(kColorTile, rows - t.y0) * std::min(kColorTile, cols - t.x0);
+        const CostTile t = color_tile_of(T, k);
+        CHECK(t.y0 % kCostTile == 0 && t.x0 % kCostTile == 0 && t.y0 < rows && t.x0 < cols);
+        CHECK(t.y1 == std::min(t.y0 + kCostTile, rows) && t.x1 == std::min(t.x0 + kCostTile, cols));
+        covered += std::min(kCostTile, rows - t.y0) * std::min(kCostTile, cols - t.x0);
     }
     CHECK(covered == rows * cols);
     color_cost_host(T);
@@ -154,7 +155,7 @@ int main() {
     if (modes_and_rule()) return 1;
     std::mt19937 rng(26);
     const float norms[][2] = {{1.0f, 0.0f}, {255.0f, 0.0f}, {127.5f, 127.5f}};
-    const uint32_t shapes[][2] = {{1, 1}, {1, 17}, {17, 1}, {3, 5}, {64, 64}, {65, 65}, {129, 129}, {2, 200}, {130, 3}};
+    const uint32_t shapes[][2] = {{1, 1}, {1, 17}, {17, 1}, {3, 5}, {64, 64}, {65, 65}, {129, 129}, {2, 200}, {130, 3}, {65, 130}, {130, 65}};
     long frames = 0;
     for (uint32_t format = 0; format < kCollectFormats; format++)
         for (auto &hw : shapes)

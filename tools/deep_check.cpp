@@ -20,7 +20,7 @@ using namespace nblic;
 
 #define CHECK(x) do { if (!(x)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); return 1; } } while (0)
 
-static const int kShapes[][2] = {{1, 1}, {1, 17}, {3, 5}, {33, 65}, {64, 64}, {65, 130}};
+static const int kShapes[][2] = {{1, 1}, {1, 17}, {3, 5}, {33, 65}, {64, 64}, {65, 130}, {130, 65}};
 static const uint32_t kEdges[] = {0, 255, 256, 257, 0x7FFF, 0x8000, 0xFFFF};
 constexpr uint8_t kPattern = 0x5A;
 

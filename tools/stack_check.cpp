@@ -20,7 +20,7 @@ using namespace nblic;
 
 #define CHECK(x) do { if (!(x)) { fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #x); return 1; } } while (0)
 
-static const int kShapes[][2] = {{1, 1}, {1, 17}, {17, 1}, {3, 5}, {33, 17}, {64, 64}, {65, 65}, {129, 129}};
+static const int kShapes[][2] = {{1, 1}, {1, 17}, {17, 1}, {3, 5}, {33, 17}, {64, 64}, {65, 65}, {129, 129}, {65, 130}, {130, 65}};
 static const int kDepths[] = {1, 2, 3, 5, 9};
 
 static double half_value(uint32_t h) {
