@@ -778,6 +778,20 @@ long nblic_amd_debug_stage(nblic_amd_ctx *ctx, const unsigned char *img, int hei
  * and band encoders, [3] streams + events.  Needs no context and makes no GPU call.                                  */
 void nblic_amd_debug_live(long counts[4]);
 
+/* Debug hook used by the workspace-history tests: a read-only report of the grow-only device workspaces, so that a test
+ * can tell that a call ran in the memory an earlier call left (capacities and addresses unchanged) and not in fresh one.
+ * group >= 0: slot `slot` of group `group` --
+ *   out[0] px_cap, out[1] ev_cap: entries the pixel-sized / event-sized buffers hold   out[2] bytes of the slot's pool
+ *   out[3], out[4] the addresses of rec1 and events, as integers (0: not allocated yet)
+ *   out[5], out[6], out[7] capacities of the slot's image copy (bytes), reconstruction (bytes) and LSQ statistics (doubles)
+ * group < 0 (slot is ignored): the context --
+ *   out[0] coded-bin buffers, out[1] how many of them hold memory, out[2] their summed capacity in 16-bit records
+ *   out[3] pack buffers, out[4] how many of them hold memory, out[5] their summed capacity in 64-bit words
+ *   out[6] bytes of the decode arena   out[7] job records the decode batches' device array holds
+ * Launches nothing, allocates nothing and changes nothing; call it while no batch of the context is in flight.  Returns
+ * 0, -1 for a null pointer or a group / slot the context does not have.                                              */
+int nblic_amd_debug_workspaces(nblic_amd_ctx *ctx, int group, int slot, long out[8]);
+
 /* Debug hook used by the hand-over tests: takes[k] = how many times a host coder thread took k images together since
  * the last batch began (k = 0..24; 1 = an image on its own, the scalar coder; more = whole packs).               */
 void nblic_amd_debug_takes(nblic_amd_ctx *ctx, long takes[25]);

@@ -37,7 +37,7 @@ _lib = None
 EXPORTS = (
     "NBLICcompress", "NBLICdecompress", "QNBLICcompress", "QNBLICdecompress", "QNBLICcompressMultiThread",
     "nblic_amd_create", "nblic_amd_create_ex", "nblic_amd_destroy", "nblic_amd_encode_batch", "nblic_amd_encode_batch_begin", "nblic_amd_encode_batch_end", "nblic_amd_qencode_batch", "nblic_amd_set_max_pixels",
-    "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage", "nblic_amd_debug_live", "nblic_amd_debug_takes", "nblic_amd_debug_pack_rows", "nblic_amd_debug_device_code", "nblic_amd_debug_model_stages", "nblic_amd_debug_back_half", "nblic_amd_debug_entropy_front",
+    "nblic_amd_enable_timing", "nblic_amd_stage_times", "nblic_amd_last_launches", "nblic_amd_last_stats", "nblic_amd_debug_stage", "nblic_amd_debug_live", "nblic_amd_debug_workspaces","nblic_amd_debug_takes", "nblic_amd_debug_pack_rows", "nblic_amd_debug_device_code", "nblic_amd_debug_model_stages", "nblic_amd_debug_back_half", "nblic_amd_debug_entropy_front",
     "nblic_amd_encode_batch_modes", "nblic_amd_decode_batch", "nblic_amd_serial_selftest",
     "nblic_amd_set_serial_rows", "nblic_amd_serial_launches", "nblic_amd_set_long_chains", "nblic_amd_long_chain_stats", "nblic_amd_lsq_redo_counts", "nblic_amd_serial_plan", "nblic_amd_lsq_probe", "nblic_amd_set_feed_chunk", "nblic_amd_last_fed_bytes",
     "nblic_amd_stream_begin", "nblic_amd_stream_resume", "nblic_amd_stream_run", "nblic_amd_stream_checkpoint", "nblic_amd_stream_progress",
@@ -448,6 +448,9 @@ def load_library() -> C.CDLL:
     lib.nblic_amd_debug_stage.argtypes = [C.c_void_p, _u8p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     lib.nblic_amd_debug_live.restype = None
     lib.nblic_amd_debug_live.argtypes = [C.POINTER(C.c_long)]
+    if hasattr(lib, "nblic_amd_debug_workspaces"):                 # (an older build loaded through NBLIC_AMD_LIB has none)
+        lib.nblic_amd_debug_workspaces.restype = C.c_int
+        lib.nblic_amd_debug_workspaces.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_long)]
     lib.nblic_amd_range_code.restype = C.c_size_t
     lib.nblic_amd_range_code.argtypes = [C.POINTER(C.c_uint16), C.c_size_t, _u8p, C.c_size_t]
     lib.nblic_amd_range_code_multi.restype = C.c_int
@@ -3218,6 +3221,25 @@ class Context:
         if cnt < 0:
             raise RuntimeError("nblic_amd_debug_stage failed")
         return out[:cnt].copy()
+
+    def debug_workspaces(self) -> dict:
+        """A read-only report of the grow-only device workspaces (``nblic_amd_debug_workspaces``; launches nothing):
+        ``{"slots": [[slot, ...] per group], "context": {...}}``.  A slot gives ``px_cap``, ``ev_cap``, ``pool_bytes``, the
+        addresses ``rec1`` and ``events`` and the capacities ``img``, ``recon`` and ``stats``; the context gives number,
+        how many hold memory and summed capacity of ``cbufs`` and ``pbufs`` and the capacities ``dec_arena`` / ``dec_jobs``.
+        Two reports are equal exactly when nothing was reallocated between them."""
+        v = (C.c_long * 8)()
+        if self.lib.nblic_amd_debug_workspaces(self.handle, -1, 0, v) != 0:
+            raise RuntimeError("nblic_amd_debug_workspaces failed")
+        ctx = dict(zip(("cbufs", "cbufs_held", "cbufs_cap", "pbufs", "pbufs_held", "pbufs_cap", "dec_arena", "dec_jobs"), (int(x) for x in v)))
+        names = ("px_cap", "ev_cap", "pool_bytes", "rec1", "events", "img", "recon", "stats")
+        groups = []
+        while self.lib.nblic_amd_debug_workspaces(self.handle, len(groups), 0, v) == 0:
+            slots = []
+            while self.lib.nblic_amd_debug_workspaces(self.handle, len(groups), len(slots), v) == 0:
+                slots.append(dict(zip(names, (int(x) for x in v))))
+            groups.append(slots)
+        return {"slots": groups, "context": ctx}
 
     def takes(self) -> dict:
         """{k: how many times a host coder thread took k images together} since the last batch began (``nblic_amd_debug_takes``)."""

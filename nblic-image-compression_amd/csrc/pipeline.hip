@@ -6169,6 +6169,27 @@ int nblic_amd_debug_stack_deliver(nblic_amd_ctx *c, int n, const int *counts, co
 
 void nblic_amd_debug_live(long counts[4]) { for (int k = 0; k < 4; k++) counts[k] = g_live[k].load(std::memory_order_relaxed); }
 
+int nblic_amd_debug_workspaces(nblic_amd_ctx *c, int group, int slot, long out[8]) {
+    if (!c || !out) return -1;
+    std::lock_guard<std::mutex> g(c->api);                                   // no batch of this context is in flight
+    if (group < 0) {
+        long held[2] = {0, 0}, cap[2] = {0, 0};
+        std::lock_guard<std::mutex> l(c->fm);
+        for (const CodedBuf &b : c->cbufs) { held[0] += b.get() != nullptr; cap[0] += long(b.capacity()); }
+        for (const PackRows &p : c->pbufs) { held[1] += p.get() != nullptr; cap[1] += long(p.capacity_words()); }
+        out[0] = long(c->cbufs.size()); out[1] = held[0]; out[2] = cap[0];
+        out[3] = long(c->pbufs.size()); out[4] = held[1]; out[5] = cap[1];
+        out[6] = long(c->dec_arena.capacity()); out[7] = long(c->dec_jobs.capacity());
+        return 0;
+    }
+    if (size_t(group) >= c->groups.size() || slot < 0 || size_t(slot) >= c->groups[size_t(group)].slots.size()) return -1;
+    const Slot &s = c->groups[size_t(group)].slots[size_t(slot)];
+    out[0] = long(s.px_cap); out[1] = long(s.ev_cap); out[2] = long(s.mem.bytes());
+    out[3] = long(reinterpret_cast<uintptr_t>(s.b.rec1)); out[4] = long(reinterpret_cast<uintptr_t>(s.b.events));
+    out[5] = long(s.d_img.capacity()); out[6] = long(s.d_recon.capacity()); out[7] = long(s.d_stats.capacity());
+    return 0;
+}
+
 int nblic_amd_copy_stats(nblic_amd_ctx *c, long out[4]) {
     if (!c || !out) return -1;
     c->engine.stats(out);

@@ -23,7 +23,7 @@ def test_library_exports_every_declared_symbol(pkg):
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     names = declared_symbols(text)
     assert {"NBLICcompress", "NBLICdecompress", "QNBLICcompress", "QNBLICdecompress",
-            "QNBLICcompressMultiThread", "nblic_amd_encode_batch"} <= names
+            "QNBLICcompressMultiThread", "nblic_amd_encode_batch", "nblic_amd_debug_workspaces"} <= names
     assert names == set(pkg.EXPORTS)
     for n in names:
         assert hasattr(lib, n), n
